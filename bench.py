@@ -11,6 +11,13 @@ A "step" is one pass of the hot path over the whole synthetic read set resident 
     + kmercount of every canonical 31-mer (table reset included), + for N > 1 the owner-partition exchange.
 Weak scaling: every rank holds its own read shard of that size (same genome, different read seed); value is the
 whole-job aggregate.  Prints ONE JSON line on rank 0.
+
+A plain run only sets up, warms up, times the K steps and prints the line.  `--full` adds everything else the line can
+carry: the library's per-kernel timers over the timed steps (kernels, roofline, alu), the oracle parity and count checks,
+the pinned-host leg, the CPU baseline and, for the default workload on one GPU, the other BASELINE configurations.
+The kernel timers record hipEvents around every launch: a plain line's ms_per_step is timed without them, so a --full
+line of the same build can read a few tenths of a percent higher.
+`--dump-outputs DIR` writes what the last timed step computed (rank 0's shard) as DIR/<name>.npy, see dump_outputs().
 """
 import argparse
 import json
@@ -45,7 +52,12 @@ def parse():
     ap.add_argument("--no-parity", action="store_true", help="skip the oracle check of the timed output")
     ap.add_argument("--sketch-size", type=int, default=0)
     ap.add_argument("--no-configs", action="store_true",
-                    help="skip the timed lines of the other BASELINE configurations (`configs` of the default one-GPU run)")
+                    help="skip the timed lines of the other BASELINE configurations (`configs` of the --full one-GPU run)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the per-kernel timers, roofline, checks, host leg, CPU baseline and configs (the --no-* options "
+                         "above switch parts of it off)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float64 / float32, seeded samples)")
     return ap.parse_args()
 
 
@@ -217,7 +229,7 @@ def run_configs(steps=5, warmup=3, runner=_run_child, environ=None, timeout_note
     environ = dict(os.environ if environ is None else environ)
     for w in CONFIG_WORKLOADS:
         cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--workload", w, "--steps", str(steps), "--warmup", str(warmup),
-               "--no-cpu-baseline", "--no-host-leg", "--no-configs"]
+               "--full", "--no-cpu-baseline", "--no-host-leg", "--no-configs"]
         t0 = time.time()
         rc, text = runner(cmd, environ)
         line = _last_json_line(text)
@@ -397,8 +409,11 @@ def main():
             el = float(tt.item())
         return el, ev0.elapsed_time(ev1)
 
-    elapsed, dev_ms = timed(step_device, True)
-    stats = ctx.profile_get()
+    full = args.full
+    elapsed, dev_ms = timed(step_device, full)
+    stats = ctx.profile_get() if full else {}
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, cfg, ctx, bases, offsets, sig, counter, nth)
     comm_stats = ctx.comm_stats() if use_comm and cfg["count"] else None
     comm_ranks = None
     if world > 1:  # what every rank measured: its exchange (the link rate the route model assumes) and its kernels
@@ -416,11 +431,11 @@ def main():
     else:
         job_bases = float(total_bases)
 
-    # ---- sanity of what was computed in the timed steps (not timed) ----------------------------------------
+    # ---- sanity of what was computed in the timed steps (not timed; --full) -----------------------------------
     checks = {}
-    if cfg["sketch"]:
+    if full and cfg["sketch"]:
         checks["sig_checksum"] = int(sig.view(torch.int64 if sig.element_size() == 8 else torch.int32).sum().item())
-    if cfg["count"]:
+    if full and cfg["count"]:
         occ = counter.nb_occurrences()
         dis = counter.nb_distinct()
         if world > 1:
@@ -440,7 +455,7 @@ def main():
             sat = int(t1.item())
         checks["count_saturated_kmers"] = sat
         checks["count_conservation_ok"] = bool(occ == nk_job if sat == 0 else occ <= nk_job)
-    if not args.no_parity:
+    if full and not args.no_parity:
         # every rank checks what ITS timed steps left behind against the oracle (rows of its first 1 000 reads; counts of
         # their k-mers, filtered by owner at N > 1); the booleans are AND-ed over the ranks
         mine = parity_check(cfg, ctx, bases, offsets, sig, counter, nth, rank=rank, world=world if use_comm else 1)
@@ -456,7 +471,7 @@ def main():
 
     # ---- the same step from pinned host memory to pinned host memory (SURVEY 8d's definition of the metric) ---------
     host = None
-    if cfg["sketch"] and not args.no_host_leg and not cfg.get("protein"):
+    if full and cfg["sketch"] and not args.no_host_leg and not cfg.get("protein"):
         h_bases = torch.empty(total_bases, dtype=torch.uint8).pin_memory()
         h_bases.copy_(bases[:total_bases])
         h_off = offsets.cpu().pin_memory()
@@ -505,10 +520,10 @@ def main():
                                      "alu": pmc_alu(cfg, total_bases, n, e["avg_ms"], e.get("per_step"))}
                                  for n, e in kern.items() if "alg_bytes" in e}
         cpu = None
-        if not args.no_cpu_baseline and world == 1:
+        if full and not args.no_cpu_baseline and world == 1:
             cpu = cpu_baseline(cfg, bases, offsets, lens, args.cpu_sample_reads, args.cpu_threads)
         configs = None
-        if world == 1 and cfg["name"] == "ont_k31" and not args.no_configs and not (args.reads or args.bases or args.genome):
+        if full and world == 1 and cfg["name"] == "ont_k31" and not args.no_configs and not (args.reads or args.bases or args.genome):
             # the children get the whole card: this process first gives its device memory back (a child that finds the card half
             # full takes other routes -- config 3's list-emitting route wants 52 GB of scratch -- and would not be the workload)
             if counter is not None:
@@ -535,12 +550,12 @@ def main():
             # SURVEY.md 8(d) defines the metric host to host (bases in host memory -> signatures in host memory + counts on the
             # device); `value` is the bench contract's device-resident figure.  Quote THIS one as the 8(d) number.
             "metric_value_8d": host["value"] if host else None,
-            "kernels": kern, "device_ms_per_step": dev_ms / args.steps,
+            "kernels": kern if full else None, "device_ms_per_step": dev_ms / args.steps,
             # for whoever samples the card from outside (a sampler that saw 0 % busy): the launches the library timed
             # inside the timed region, their summed device time (hipEvents), and the region's wall time
             "gpu_work": {"timed_kernel_launches": int(sum(ln for ln, _ in stats.values())), "timed_kernel_ms": float(sum(ms for _, ms in stats.values())),
-                         "timed_region_wall_ms": elapsed * 1e3, "timed_region_device_ms": dev_ms},
-            "checks": checks, "comm": _comm_summary(comm_stats, transport, comm_fallbacks, comm_ranks), "gen_seconds": t_gen,
+                         "timed_region_wall_ms": elapsed * 1e3, "timed_region_device_ms": dev_ms} if full else None,
+            "checks": checks if full else None, "full": full, "comm": _comm_summary(comm_stats, transport, comm_fallbacks, comm_ranks), "gen_seconds": t_gen,
             # the other BASELINE configurations on this GPU (configs 4 / 5: one GPU's shard), each timed by a child of this run
             "configs": configs,
         }
@@ -647,6 +662,72 @@ def _np_int32_hash(key):
         key = key * np.uint32(2057)
         key = key ^ (key >> np.uint32(16))
     return key
+
+
+DUMP_SEED = 0xD5
+DUMP_SIG_BYTES = 32 << 20        # signature rows (float64 halves): 32 MiB
+DUMP_COUNT_KEYS = 1 << 21        # table counts of the canonical k-mers of sampled reads (float64): 16 MiB
+DUMP_NTHASH_POSITIONS = 1 << 19  # positions x 2 float64 arrays: 8 MiB
+
+
+def _u64_halves(a):
+    """uint64 -> (high 32 bits, low 32 bits) as float64: both exact"""
+    a = np.ascontiguousarray(a).view(np.uint64)
+    return (a >> np.uint64(32)).astype(np.float64), (a & np.uint64(0xFFFFFFFF)).astype(np.float64)
+
+
+def dump_outputs(out_dir, cfg, ctx, bases, offsets, sig, counter, nth):
+    """--dump-outputs: what the last timed step left behind, as out_dir/<name>.npy (float64, float32 signatures as float32),
+    at most 64 MB in all.  Fixed, seeded samples (DUMP_SEED) of what is larger, so that two builds can be compared file by file:
+      signatures[_hi32|_lo32]  rows of a sample of the reads (8-byte integer signatures split into two exact halves)
+      count_totals             [nb_distinct, nb_unique, nb_occurrences, nb_saturated] of the table
+      count_sample             the table's count of every canonical k-mer of the first sampled reads
+      nthash_hi32 / _lo32      the per-position ntHash output at a sample of positions
+    """
+    import torch
+    from kmerutils_amd import _abi as A
+    os.makedirs(out_dir, exist_ok=True)
+    ctx.synchronize()
+    if torch.cuda.is_available():
+        torch.cuda.synchronize()
+    rng = np.random.default_rng(DUMP_SEED)
+    n_reads = len(offsets) - 1
+    rows = np.arange(n_reads)
+    if sig is not None:
+        m = sig.shape[1]
+        n_rows = max(1, min(n_reads, DUMP_SIG_BYTES // (m * 16)))
+        rows = np.sort(rng.choice(n_reads, n_rows, replace=False)) if n_rows < n_reads else rows
+        got = sig[torch.from_numpy(rows).to(sig.device)].cpu().numpy()
+        if cfg["sig"] == A.SIG_F32:
+            np.save(os.path.join(out_dir, "signatures.npy"), got.astype(np.float32))
+        elif cfg["sig"] == A.SIG_F64:
+            np.save(os.path.join(out_dir, "signatures.npy"), got.astype(np.float64))
+        elif got.dtype.itemsize == 4:
+            np.save(os.path.join(out_dir, "signatures.npy"), got.view(np.uint32).astype(np.float64))
+        else:
+            hi, lo = _u64_halves(got)
+            np.save(os.path.join(out_dir, "signatures_hi32.npy"), hi)
+            np.save(os.path.join(out_dir, "signatures_lo32.npy"), lo)
+    if counter is not None:
+        tot = [counter.nb_distinct(), counter.nb_unique(), counter.nb_occurrences(), counter.nb_saturated()]
+        np.save(os.path.join(out_dir, "count_totals.npy"), np.array(tot, np.float64))
+        # the reads of the sample (or of a fresh one when nothing was sketched), until DUMP_COUNT_KEYS k-mers
+        pick = rows if sig is not None else np.sort(rng.choice(n_reads, min(n_reads, 4096), replace=False))
+        ho = offsets.cpu().numpy()
+        lens = ho[pick + 1] - ho[pick]
+        pick = pick[:max(1, int(np.searchsorted(np.cumsum(np.maximum(lens - cfg["k"] + 1, 0)), DUMP_COUNT_KEYS, side="right")))]
+        sub = torch.cat([bases[int(ho[i]):int(ho[i + 1])] for i in pick])
+        soff = torch.from_numpy(np.concatenate([[0], np.cumsum(ho[pick + 1] - ho[pick])]).astype(np.int64)).to(bases.device)
+        keys = ctx.kmer_hashes_compact(sub, soff, cfg["kmer_type"], cfg["k"], A.FHASH_CANON_VALUE)[:DUMP_COUNT_KEYS]
+        got = counter.query(keys)
+        ctx.synchronize()
+        np.save(os.path.join(out_dir, "count_sample.npy"), got.cpu().numpy().astype(np.float64))
+    if nth is not None:
+        total = int(offsets[-1].item())
+        pos = np.sort(rng.choice(total, min(total, DUMP_NTHASH_POSITIONS), replace=False))
+        hi, lo = _u64_halves(nth[torch.from_numpy(pos).to(nth.device)].cpu().numpy())
+        np.save(os.path.join(out_dir, "nthash_hi32.npy"), hi)
+        np.save(os.path.join(out_dir, "nthash_lo32.npy"), lo)
 
 
 def parity_check(cfg, ctx, bases, offsets, sig, counter, nth, n_check=1000, rank=0, world=1):

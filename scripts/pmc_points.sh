@@ -1,16 +1,17 @@
 #!/bin/bash
 # diagnostics: SQ counters of the two sketch kernels on the sketch-only bench workload
 export TMPDIR=/tmp; R=$GRAFT_REPO_ROOT; cd /tmp
+export OUT=${OUT:-$R/scripts_out}; mkdir -p $OUT  # what the runs write
 i=0
 for set in "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD" "SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_SCA SQ_WAIT_INST_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAVES SQ_INSTS_SMEM"; do
   i=$((i+1))
-  timeout -k 10 200 rocprofv3 --pmc $set --output-format csv -d $R/gpurun_out/pmc_pt_$i -- python3 $R/bench.py --workload ont_k31_sketch --steps 1 --warmup 0 --no-cpu-baseline > $R/gpurun_out/pmc_pt_$i.log 2>&1 || echo "pass $i failed"
+  timeout -k 10 200 rocprofv3 --pmc $set --output-format csv -d $OUT/pmc_pt_$i -- python3 $R/bench.py --full --workload ont_k31_sketch --steps 1 --warmup 0 --no-cpu-baseline > $OUT/pmc_pt_$i.log 2>&1 || echo "pass $i failed"
 done
 python3 - <<'PY'
 import csv,glob,os,collections
 R=os.environ["GRAFT_REPO_ROOT"]
 acc=collections.defaultdict(lambda: collections.defaultdict(float))
-for f in sorted(glob.glob(R+"/gpurun_out/pmc_pt_*/*/*_counter_collection.csv")):
+for f in sorted(glob.glob(os.environ["OUT"]+"/pmc_pt_*/*/*_counter_collection.csv")):
     for r in csv.DictReader(open(f)):
         n=r["Kernel_Name"].split("(")[0].split("<")[0].replace("void ","").replace("kmu::","").strip()
         if n.startswith("k_pmh") or n.startswith("k_sketch"):

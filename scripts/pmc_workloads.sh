@@ -5,8 +5,9 @@
 tag=$1; shift
 W=${@:-"c3_k8 c5_aa c1_super c2_nthash_count c4_count"}
 cd $GRAFT_REPO_ROOT
+export OUT=${OUT:-$PWD/scripts_out}; mkdir -p $OUT  # what the runs write
 for w in $W; do
-  PMC_NO_LATEST=1 bash scripts/pmc_bench.sh ${tag}_$w --workload $w > gpurun_out/pmc_${tag}_$w.log 2>&1 || { echo "pmc passes of $w failed"; tail -5 gpurun_out/pmc_${tag}_$w.log; exit 1; }
+  PMC_NO_LATEST=1 bash scripts/pmc_bench.sh ${tag}_$w --workload $w > $OUT/pmc_${tag}_$w.log 2>&1 || { echo "pmc passes of $w failed"; tail -5 $OUT/pmc_${tag}_$w.log; exit 1; }
   python3 - <<PY
 import json
 b = json.load(open("profiles/${tag}_${w}_bench.json"))

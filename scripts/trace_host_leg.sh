@@ -1,7 +1,7 @@
 #!/bin/bash
 # timeline of the host-to-host leg: kernel trace + memory-copy trace of one run, summarised as (start, end, what) rows of the last leg
-export TMPDIR=/tmp; R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/trace_host; rm -rf $O; mkdir -p $O; cd /tmp
-timeout -k 10 400 rocprofv3 --kernel-trace --memory-copy-trace --output-format csv -d $O -- python3 $R/bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-parity > $O/run.log 2>&1 || { tail -5 $O/run.log; exit 1; }
+export TMPDIR=/tmp; R=$(cd "$(dirname "$0")/.." && pwd); export OUT=${OUT:-$R/scripts_out}; O=$OUT/trace_host; rm -rf $O; mkdir -p $O; cd /tmp
+timeout -k 10 400 rocprofv3 --kernel-trace --memory-copy-trace --output-format csv -d $O -- python3 $R/bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --no-parity > $O/run.log 2>&1 || { tail -5 $O/run.log; exit 1; }
 python3 - $O <<'PY'
 import csv, glob, sys
 d = sys.argv[1]

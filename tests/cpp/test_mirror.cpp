@@ -44,6 +44,12 @@ struct Reg {
     Reg reg_##name(#name, name);                                                                                      \
     void name()
 
+// the files the cases write go to $KMU_TEST_TMPDIR (the pytest driver gives every run a directory of its own), else /tmp
+std::string tmp_file(const std::string &name) {
+    const char *d = std::getenv("KMU_TEST_TMPDIR");
+    return std::string(d && *d ? d : "/tmp") + "/" + name;
+}
+
 // the 80 bases every DNA test of the reference uses
 const std::string SEQSTR = "TCAAAGGGAAACATTCAAAATCAGTATGCGCCCGTTCAGTTACGTATTGCTCTCGCTAATGAGATGGGCTGGGTACAGAG";
 const std::string AA1 = "MTEQIELIKLYSTRILALAAQMPHVGSLDNPDASAMKRSPLCGSKVTVDVIMQNGKITFDGFEVLAPASEYKNRHASILLSLDATAEACASIAAQNSA";
@@ -726,7 +732,7 @@ TEST(test_count_kmer_threaded_one_to_many) {
     }
     CHECK(pool->get_count_nb_bits() == 8);
     kmo_count_destroy(oc);
-    const std::string fname = "/tmp/kmu_test_mirror.multi_kmer.bin";
+    const std::string fname = tmp_file("kmu_test_mirror.multi_kmer.bin");
     CHECK(pool->dump_kmer_counter(fname) == gk.size());
     std::ifstream in(fname, std::ios::binary);
     uint32_t magic; uint8_t k, nbc; uint64_t nrec;
@@ -775,7 +781,7 @@ TEST(test_kmer_filter1_once_kmers) {
         const Kmer16b32bit kmin = kmers[wp[i]].reverse_complement().min(kmers[wp[i]]);
         CHECK(kmin.v == uint32_t(wk[i]));
     }
-    const std::string fname = "/tmp/kmu_test_mirror.once_kmer.bin";
+    const std::string fname = tmp_file("kmu_test_mirror.once_kmer.bin");
     CHECK(filter->dump_in_file_once_kmer16b32bit(fname, seqvec) == n);
     {   // KmerCountReload (kmercount.rs:1356-1486) reads the dump back
         auto reload = KmerCountReload::load_unique_kmer_from_file(fname);
@@ -791,7 +797,7 @@ TEST(test_kmer_filter1_once_kmers) {
         CHECK(c16->get_nb_unique() == filter->get_nb_once());
         auto pool = count_kmer_thread_independant<Kmer16b32bit>(seqvec, 4, 16);
         CHECK(pool->get_nb_distinct() == c16->get_nb_distinct() && pool->above2_entries() == c16->above2_entries());
-        const std::string mname = "/tmp/kmu_test_mirror16.multi_kmer.bin";
+        const std::string mname = tmp_file("kmu_test_mirror16.multi_kmer.bin");
         const size_t nm = pool->dump_kmer_counter(mname);
         auto multi = KmerCountReload::load_multiple_kmers_from_file(mname);
         CHECK(multi && multi->get_kmer_size() == 16 && multi->kmers().size() == nm);
@@ -854,7 +860,7 @@ TEST(test_parse_fastq_and_signature_dump) {
     for (const std::string &s : kept) seqs.emplace_back(s);
     SeqSketcher sketcher(8, 200);
     auto sigs = sketcher.sketch_probminhash3a<Kmer32bit>(detail::pointers(seqs), kmer_revcomp_hash_fn);
-    const std::string fname = "/tmp/kmu_test_mirror.sig";
+    const std::string fname = tmp_file("kmu_test_mirror.sig");
     {
         std::ofstream out = sketcher.create_signature_dump(fname);
         SeqSketcher::dump_signatures_block_u32(sigs, out);
@@ -874,7 +880,7 @@ TEST(test_parse_fastq_and_signature_dump) {
     CHECK(!reader.next().has_value());
     std::remove(fname.c_str());
     // the parameter dumps next to it (serde_json layout)
-    const std::string dir = "/tmp/kmu_test_mirror_json";
+    const std::string dir = tmp_file("kmu_test_mirror_json");
     std::filesystem::create_directories(dir);
     SeqSketcherParams(8, 200, SketchAlgo::PROB3A, DataType::DNA).dump_json(dir + "/sketchparams_dump.json");
     {
@@ -930,7 +936,7 @@ TEST(test_device_resident_reads) {
         text += "@r\n" + s + "\n+\n" + std::string(s.size(), 'I') + "\n";
         seqs.emplace_back(s);
     }
-    const std::string fname = "/tmp/kmu_test_mirror_dev.fastq";
+    const std::string fname = tmp_file("kmu_test_mirror_dev.fastq");
     { std::ofstream(fname, std::ios::binary) << text; }
     Context &ctx = Context::global();
     DeviceReads reads = DeviceReads::from_file(fname, ctx, 4096);   // small slabs: several uploads

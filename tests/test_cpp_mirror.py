@@ -48,8 +48,9 @@ def test_host_programs_build_and_refuse_to_run_without_a_device(host_programs):
 
 
 @pytest.fixture(scope="module")
-def mirror_results(host_programs):
-    r = subprocess.run([TEST_BIN], capture_output=True, text=True, timeout=900)
+def mirror_results(host_programs, tmp_path_factory):
+    env = dict(os.environ, KMU_TEST_TMPDIR=str(tmp_path_factory.mktemp("mirror")))  # (the files the cases write)
+    r = subprocess.run([TEST_BIN], capture_output=True, text=True, timeout=900, env=env)
     res = {}
     for line in r.stdout.splitlines():
         m = re.match(r"(ok|FAIL) (\w+)(: .*)?$", line)

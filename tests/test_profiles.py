@@ -162,8 +162,8 @@ def test_the_default_run_times_every_baseline_configuration():
 
     out = bench.run_configs(runner=runner, environ={"PATH": os.environ["PATH"]})
     assert set(out) == set(bench.CONFIG_WORKLOADS) == {"c1_super", "c2_nthash_count", "c3_k8", "c4_count", "c5_aa"}
-    for cmd in seen:  # a plain one-GPU child each: no cpu baseline, no nested configs, 3 warm-up + 5 steps
-        assert cmd[1].endswith("bench.py") and "--no-configs" in cmd and "--no-cpu-baseline" in cmd
+    for cmd in seen:  # a --full one-GPU child each (roofline, parity): no cpu baseline, no nested configs, 3 warm-up + 5 steps
+        assert cmd[1].endswith("bench.py") and "--full" in cmd and "--no-configs" in cmd and "--no-cpu-baseline" in cmd
         assert cmd[cmd.index("--steps") + 1] == "5" and cmd[cmd.index("--warmup") + 1] == "3" and cmd[cmd.index("--gpus") + 1] == "1"
     assert "error" in out["c4_count"] and "exit code 1" in out["c4_count"]["error"]
     for w in ("c1_super", "c3_k8", "c5_aa", "c2_nthash_count"):
@@ -172,3 +172,87 @@ def test_the_default_run_times_every_baseline_configuration():
         assert e["ms_per_step"] == 7.5 and e["roofline_frac"] == 0.2 and e["steps"] == 5 and e["warmup"] == 3
     assert out["c5_aa"]["unit"] == "Gresidues/s" and out["c3_k8"]["unit"] == "Gbases/s"
     assert out["c1_super"]["parity_ok"] is True and out["c2_nthash_count"]["parity_ok"] is False  # every parity_* check must hold
+
+
+def test_dumped_u64_halves_are_exact():
+    """--dump-outputs writes 8-byte integer outputs (u64 signatures, ntHash values) as two float64 arrays of 32 bits each"""
+    import bench
+    import numpy as np
+    a = np.array([0, 1, 0xFFFFFFFF, 1 << 32, (1 << 64) - 1, 0x0123456789ABCDEF], np.uint64)
+    hi, lo = bench._u64_halves(a.view(np.int64))
+    assert hi.dtype == lo.dtype == np.float64
+    assert np.array_equal((hi.astype(np.uint64) << np.uint64(32)) | lo.astype(np.uint64), a)
+
+
+class _FakeCtx:
+    """what dump_outputs asks of a Context, on CPU tensors: canonical k-mer values made from the bases they are given"""
+    def synchronize(self):
+        pass
+
+    def kmer_hashes_compact(self, bases, offsets, kmer_type, k, fhash):
+        import torch
+        keys = [bases[o:o + n - k + 1].long() * 1000003 + torch.arange(n - k + 1) * 7
+                for o, n in zip(offsets[:-1].tolist(), (offsets[1:] - offsets[:-1]).tolist()) if n >= k]
+        return torch.cat(keys) if keys else torch.zeros(0, dtype=torch.int64)
+
+
+class _FakeCounter:
+    def nb_distinct(self):
+        return 123456789
+
+    def nb_unique(self):
+        return 12345678
+
+    def nb_occurrences(self):
+        return 4357236706
+
+    def nb_saturated(self):
+        return 0
+
+    def query(self, keys):
+        return (keys % 251).to(dtype=__import__("torch").int32)
+
+
+def _dump(tmp, cfg, n_reads, read_len, m=None, sig_dtype=None, nth=False):
+    import bench
+    import numpy as np
+    import torch
+    g = torch.Generator().manual_seed(7)
+    bases = torch.randint(65, 91, (n_reads * read_len + 64,), dtype=torch.uint8, generator=g)
+    offsets = torch.arange(n_reads + 1, dtype=torch.int64) * read_len
+    sig = torch.randint(-2 ** 62, 2 ** 62, (n_reads, m), generator=g).to(sig_dtype) if m else None
+    nthv = torch.randint(-2 ** 62, 2 ** 62, (n_reads * read_len + 64,), generator=g) if nth else None
+    counter = _FakeCounter() if cfg["count"] else None
+    bench.dump_outputs(str(tmp), cfg, _FakeCtx(), bases, offsets, sig, counter, nthv)
+    files = {f.name: np.load(f) for f in sorted(tmp.iterdir())}
+    return files, sum(f.stat().st_size for f in tmp.iterdir())
+
+
+def test_dump_outputs_names_dtypes_bound_and_repeatability(tmp_path):
+    """bench.dump_outputs on CPU stand-ins of the timed path's results: the files it writes for the headline's shape (u64 rows
+    + count table), for config 2 (ntHash + count) and for f64 / u32 rows; float64 (float32 rows stay float32), 64 MB at most in
+    all, seeded samples, and two calls on the same results write the same files"""
+    import bench
+    import numpy as np
+    import torch
+    from kmerutils_amd import _abi as A
+    base = dict(k=31, kmer_type=A.KMER64BIT, sig=A.SIG_U64, count=True)
+    # headline shape: m = 200 u64 rows and a count table; enough reads that every sample is capped
+    a, size_a = _dump(tmp_path / "a", base, 20_000, 600, m=200, sig_dtype=torch.int64)
+    b, _ = _dump(tmp_path / "b", base, 20_000, 600, m=200, sig_dtype=torch.int64)
+    assert sorted(a) == ["count_sample.npy", "count_totals.npy", "signatures_hi32.npy", "signatures_lo32.npy"]
+    assert all(v.dtype == np.float64 for v in a.values())
+    assert a["signatures_hi32.npy"].shape == (bench.DUMP_SIG_BYTES // (200 * 16), 200)
+    assert bench.DUMP_COUNT_KEYS - 600 < a["count_sample.npy"].size <= bench.DUMP_COUNT_KEYS  # whole reads up to the cap
+    assert list(a["count_totals.npy"]) == [123456789, 12345678, 4357236706, 0]
+    assert size_a <= 64e6
+    assert all(np.array_equal(a[f], b[f]) for f in a)
+    # config 2: no rows, ntHash per position + counts
+    c, size_c = _dump(tmp_path / "c", dict(base, k=21, sig=A.SIG_U64), 50_000, 150, nth=True)
+    assert sorted(c) == ["count_sample.npy", "count_totals.npy", "nthash_hi32.npy", "nthash_lo32.npy"] and size_c <= 64e6
+    assert all(v.dtype == np.float64 for v in c.values())
+    # f64 and u32 rows, no table
+    d, _ = _dump(tmp_path / "d", dict(base, sig=A.SIG_F64, count=False), 500, 300, m=64, sig_dtype=torch.float64)
+    assert sorted(d) == ["signatures.npy"] and d["signatures.npy"].dtype == np.float64 and d["signatures.npy"].shape == (500, 64)
+    e, _ = _dump(tmp_path / "e", dict(base, sig=A.SIG_U32, count=False), 500, 300, m=200, sig_dtype=torch.int32)
+    assert sorted(e) == ["signatures.npy"] and e["signatures.npy"].dtype == np.float64 and e["signatures.npy"].min() >= 0
