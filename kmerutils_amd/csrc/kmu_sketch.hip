@@ -64,6 +64,8 @@ int launch_dens_merge(kmu_ctx *ctx, const kmu_sketch_params *p, const uint64_t *
 // the sketches kept as m bins / registers with one independent update per k-mer occurrence (kmu_sketch_dens.hip)
 static bool algo_is_dens(int algo) { return algo == KMU_ALGO_OPTDENS || algo == KMU_ALGO_REVOPTDENS || algo == KMU_ALGO_HLL; }
 
+static int atoi_or(const char *s, int dflt) { return s ? atoi(s) : dflt; }
+
 // ProbMinHash3a of whole DNA sequences with k <= 8 (Kmer32bit) and a closure that is injective on the (canonical) k-mer:
 // the histogram route of k_sketch_smallk.  KMU_PMH_SMALLK=0 keeps the general kernels (diagnostics, A/B).
 static bool smallk_route(const kmu_sketch_params *p, int hashed_bytes, bool partial, bool blocks) {
@@ -75,21 +77,137 @@ static bool smallk_route(const kmu_sketch_params *p, int hashed_bytes, bool part
     case KMU_FHASH_INVHASH_RAW: case KMU_FHASH_CANON_VALUE: break;
     default: return false; // (ntHash is not injective in principle)
     }
-    const char *e = getenv("KMU_PMH_SMALLK");
-    return !(e && atoi(e) == 0);
+    return atoi_or(getenv("KMU_PMH_SMALLK"), 1) != 0;
 }
 
-// k_pmh_points over the lists of a.n_seq reads; reads with more than KMU_PMH_PTS_LONG list entries (default 32 768; 0: none)
-// are listed first (k_pts_long_list) and taken by whole workgroups
-static int launch_points(kmu_ctx *ctx, SketchArgs a, int cus) {
+// What a launch_pmh3a call sketches besides the sequences of `ds`; every field may stay at its default.
+struct PmhInputs {
+    const uint64_t *d_block_rows = nullptr; // block mode: row offsets per read
+    uint32_t *d_counts = nullptr;           // bottom-k counts, or null
+    const void *hashed = nullptr;           // pre-hashed values (hashed_bytes = 4 / 8 each) instead of bases
+    int hashed_bytes = 0;
+    uint64_t *part_h = nullptr, *part_k = nullptr; // slot minima per "sequence" instead of signature rows
+    uint32_t skip_longer = 0;               // sequences with more k-mers are left to the global (partitioned) route
+    const uint64_t *len_stats = nullptr;    // longest sequence, all bases (whole sequences only), or null
+};
+
+// The routes of a ProbMinHash3a / bottom-k call and the kernels they launch:
+//  SMALLK    k <= 8: k_sketch_smallk, with lists + k_pmh_points
+//  SHORT     whole unpacked reads of at most 256 k-mers: k_multiset_short + k_pmh_points_short
+//  UQ        whole unpacked reads: k_multiset_uq (two shapes), the list-emitting k_sketch_pmh3a for the rest, k_pmh_points
+//  LISTS     whole reads, packed (or KMU_PMH_PLAIN=0): the list-emitting k_sketch_pmh3a + k_pmh_points
+//  ONE_PASS  whole unpacked reads without lists: PLAIN k_sketch_pmh3a, the reads it hands back through the general one
+//  GENERAL   the general k_sketch_pmh3a: bottom-k, AA / pre-hashed, packed, partial rows, blocks
+enum class PmhRoute { SMALLK, SHORT, UQ, LISTS, ONE_PASS, GENERAL };
+struct PmhPlan {
+    PmhRoute route = PmhRoute::GENERAL;
+    bool lists = false;        // (key, weight) lists in HBM: SHORT, UQ, LISTS, and SMALLK when they fit
+    uint64_t list_bases = 0;   // their capacity: the bases of the batch
+    uint32_t pts_long = 32768; // KMU_PMH_PTS_LONG, as given (launch_points clamps it).  (bench: the device leg is the same with or
+                               //  without; the host leg's chunks gain 1.3 ms of 128; 16 384: +0.4 ms on the device leg, 8 192: +2)
+    int cus = 0;               // CUs the kernels spread over (KMU_PMH_RESERVE_CUS)
+};
+
+// the (key, weight) lists of the two-kernel routes, one entry per base of the batch.  8 bytes per key: the same scratch the
+// count build uses for its first partition level ("cnt.partA"); a context never runs the two at the same time, and at
+// 4.4 Gbases per GPU a second copy would not fit next to the count table and the exchange buffers
+static int alloc_lists(kmu_ctx *ctx, SketchArgs &a, uint64_t bases) {
+    void *lk, *lw, *ln;
+    KMU_TRY(dev_buf(ctx, "cnt.partA", bases * 8 + 64, &lk));
+    KMU_TRY(dev_buf(ctx, "pmh.lst_w", bases * 4 + 64, &lw));
+    KMU_TRY(dev_buf(ctx, "pmh.lst_n", (size_t) a.n_seq * 8 + 64, &ln));
+    a.lst_keys = (uint64_t *) lk;
+    a.lst_w = (uint32_t *) lw;
+    a.lst_n = (uint32_t *) ln;
+    a.lst_nu = a.lst_n + a.n_seq;
+    KMU_HIP(ctx, hipMemsetAsync(a.lst_nu, 0, (size_t) a.n_seq * 4, ctx->stream));
+    return KMU_OK;
+}
+
+// The one route decision of a call; the sketch route's KMU_PMH_* switches are read here, once each.
+static int pmh_route(kmu_ctx *ctx, const kmu_sketch_params *p, const DevSeqs &ds, const PmhInputs &in, PmhPlan *plan) {
+    const int split_mode = atoi_or(getenv("KMU_PMH_SPLIT"), -1);     // 0 / 1: never / always the lists
+    const bool plain_on = atoi_or(getenv("KMU_PMH_PLAIN"), 1) != 0; // 0: never the PLAIN instantiation (diagnostics)
+    const bool short_on = atoi_or(getenv("KMU_PMH_SHORT"), 1) != 0; // 0: short reads through k_multiset_uq (A/B)
+    plan->pts_long = (uint32_t) std::max(0, atoi_or(getenv("KMU_PMH_PTS_LONG"), 32768));
+    const int cus = ctx->num_cus; // less the CUs left to concurrent work (RCCL kernels of an exchange in flight)
+    plan->cus = std::max(cus / 2, cus - std::max(0, atoi_or(getenv("KMU_PMH_RESERVE_CUS"), 0)));
+    const bool smallk = smallk_route(p, in.hashed_bytes, in.part_h != nullptr, in.d_block_rows != nullptr);
+    // whole sequences of bases to signature rows
+    const bool whole = p->algo != KMU_ALGO_BOTTOMK && !kmer_is_aa(p->kmer_type) && !in.hashed_bytes && !in.part_h &&
+                       !in.d_block_rows && p->block_size == 0;
+    // SMALLK: the distinct (key, weight) pairs go to k_pmh_points through the lists unless that memory is not to be had: then
+    // the histogram kernel makes the points itself.
+    // Big batches of whole DNA sequences go through two kernels: the multiset kernel leaves the (key, weight) pairs of
+    // every read in HBM, k_pmh_points (one wave per read, no workgroup barrier, 5 waves per SIMD) generates the points.
+    // ONT workload: 53.3 + 21.2 ms against 88.7 ms in one kernel, for 12 bytes of scratch per base.  One wave per read
+    // has a tail: the longest read keeps its wave busy while the others have run out of reads.  The route is taken
+    // when the gain (16 % of the single kernel's time) exceeds the expected overhang of that read; figures of an MI355X
+    // (a wave of k_pmh_points does 4.0e4 k-mers per ms, the single kernel 4.9e7 per ms with 256 CUs).
+    bool lists = (size_t) 4 * (2 * (size_t) p->sketch_size + PTS_WAVE_WORDS) * 8 + WINV_LUT * 8 <= 150 * 1024 && // four waves' arrays fit one workgroup
+                 split_mode != 0 && (smallk || (whole && !in.skip_longer && (split_mode == 1 || in.len_stats)));
+    const bool judge = !smallk && split_mode != 1; // (KMU_PMH_SPLIT=1: the two-kernel route whatever it costs)
+    if (lists) {
+        uint64_t &total = plan->list_bases; // the lists' capacity: bases in the batch
+        if (in.len_stats) total = in.len_stats[1];
+        else if (!ds.h_offsets.empty()) total = ds.h_offsets[ds.n_seq] - ds.h_offsets[0];
+        else {
+            uint64_t ends[2] = {0, 0};
+            KMU_HIP(ctx, hipMemcpyAsync(&ends[0], ds.offsets, 8, hipMemcpyDeviceToHost, ctx->stream));
+            KMU_HIP(ctx, hipMemcpyAsync(&ends[1], ds.offsets + ds.n_seq, 8, hipMemcpyDeviceToHost, ctx->stream));
+            KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
+            total = ends[1] - ends[0];
+        }
+        if (judge) {
+            const uint64_t longest = in.len_stats[0];
+            const double cu_share = (double) ctx->num_cus / 256.0;
+            // (a wave of k_pmh_points does 4.0e4 k-mers per ms; a read beyond KMU_PMH_PTS_LONG is taken by four)
+            const double wave_rate = plan->pts_long && longest > plan->pts_long ? 1.6e5 : 4.0e4;
+            const double t_ideal = (double) total / (2.35e8 * cu_share), t_tail = (double) longest / wave_rate; // ms
+            const double overhang = t_tail >= t_ideal ? t_tail - 0.5 * t_ideal : t_tail * t_tail / (2.0 * t_ideal);
+            // (r02: with the reads that fit a workgroup's registers on k_multiset_uq the two-kernel route takes 53 ms where the
+            //  single kernel takes 87 on the ONT workload: 39 % of the single kernel's time, 16 % before)
+            // (r03: 49.8 ms, 43 %; the points kernel 18.5 ms for 4.36 G k-mers)
+            const double gain = 0.43 * (double) total / (4.9e7 * cu_share);
+            if (gain <= overhang + 0.02) lists = false; // (0.02 ms: the second launch)
+        }
+        if (lists && (smallk || judge)) { // the lists would crowd out what comes after this call: one kernel, no lists
+            const size_t need_k = total * 8 + 64, need_w = total * 4 + 64;
+            size_t grow = 0, free_b = 0, total_b = 0;
+            if (ctx->bufs["cnt.partA"].bytes < need_k) grow += need_k + need_k / 8;
+            if (ctx->bufs["pmh.lst_w"].bytes < need_w) grow += need_w + need_w / 8;
+            if (grow && hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b < grow + total_b / 8) lists = false;
+        }
+    }
+    plan->lists = lists;
+    const bool plain = whole && !ds.packed && plain_on;
+    // (every read of the batch with at most 256 k-mers: one wave per read)
+    const bool short_reads = in.len_stats && in.len_stats[0] < (uint64_t) SHORT_KEYS + (uint64_t) p->kmer_size && short_on;
+    plan->route = smallk         ? PmhRoute::SMALLK
+                  : lists && plain ? (short_reads ? PmhRoute::SHORT : PmhRoute::UQ)
+                  : lists          ? PmhRoute::LISTS
+                  : plain          ? PmhRoute::ONE_PASS
+                                   : PmhRoute::GENERAL;
+    return KMU_OK;
+}
+
+static int alloc_queue(kmu_ctx *ctx, SketchArgs &a) {
+    void *q;
+    KMU_TRY(dev_buf(ctx, "queue", 256, &q)); // u32 words: [0] read cursor, [48] queue2, [56] count of long / redo reads
+    KMU_HIP(ctx, hipMemsetAsync(q, 0, 256, ctx->stream));
+    a.queue = (uint32_t *) q;
+    return KMU_OK;
+}
+
+// k_pmh_points over the lists of a.n_seq reads; reads with more than pts_long list entries (KMU_PMH_PTS_LONG, default 32 768;
+// 0: none) are listed first (k_pts_long_list) and taken by whole workgroups
+static int launch_points(kmu_ctx *ctx, SketchArgs a, int cus, uint32_t thr) {
     void (*const kpts)(SketchArgs) = a.sig_bytes == 4 ? k_pmh_points<true> : k_pmh_points<false>;
     const size_t lds2 = (size_t) 4 * (2 * (size_t) a.m + PTS_WAVE_WORDS) * 8 + WINV_LUT * 8;
     if (lds2 > 64 * 1024)
         KMU_HIP(ctx, hipFuncSetAttribute((const void *) kpts, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     const int per_cu = (int) std::max<size_t>(1, std::min<size_t>(8, (160 * 1024) / lds2));
     const int grid2 = (int) std::max<uint64_t>(1, std::min<uint64_t>(((uint64_t) a.n_seq + 3) / 4, (uint64_t) cus * per_cu)); // (cus: see KMU_PMH_RESERVE_CUS)
-    uint32_t thr = 32768; // (bench: the device leg is the same with or without; the host leg's chunks gain 1.3 ms of 128; 16 384: +0.4 ms on the device leg, 8 192: +2)
-    if (const char *e = getenv("KMU_PMH_PTS_LONG")) thr = (uint32_t) std::max(0, atoi(e));
     a.pts_long = nullptr;
     a.pts_long_t = thr;
     if (thr && a.n_seq) {
@@ -107,195 +225,51 @@ static int launch_points(kmu_ctx *ctx, SketchArgs a, int cus) {
     return KMU_OK;
 }
 
-static int launch_pmh3a(kmu_ctx *ctx, const kmu_sketch_params *p, const DevSeqs &ds, const uint64_t *d_block_rows,
-                        void *d_sig, uint32_t *d_counts, uint32_t *d_err, const void *hashed = nullptr,
-                        int hashed_bytes = 0, uint64_t *part_h = nullptr, uint64_t *part_k = nullptr,
-                        uint32_t skip_longer = 0, const uint64_t *len_stats = nullptr /* longest sequence, all bases */) {
-    const bool bottomk = p->algo == KMU_ALGO_BOTTOMK;
-    SketchArgs a;
-    memset(&a, 0, sizeof a);
-    a.skip_longer = skip_longer;
-    a.hashed = hashed;
-    a.hashed_bytes = hashed_bytes;
-    a.part_h = part_h;
-    a.part_k = part_k;
-    a.bases = ds.bases;
-    a.offsets = ds.offsets;
-    a.packed_offsets = ds.packed_offsets;
-    a.block_rows = d_block_rows;
-    a.n_seq = ds.n_seq;
-    a.n_queue = ds.n_seq;
-    a.packed = ds.packed;
-    a.total_bytes = ds.total_bytes;
-    a.cfg = KmerCfg{p->kmer_type, hashed_bytes ? 1 : p->kmer_size, p->fhash};
-    a.m = p->sketch_size;
-    a.hasher = p->hasher;
-    a.rand08 = (p->flags & KMU_FLAG_RAND08) ? 1 : 0;
-    a.sig_bytes = kmer_val_bytes(p->kmer_type);
-    a.block_size = (uint32_t) p->block_size;
-    {
-        uint32_t m32 = (uint32_t) a.m;
-        a.idx_thresh = (0u - m32) % m32;
-        uint64_t m64 = (uint64_t) a.m;
-        a.idx_zone = 0xFFFFFFFFFFFFFFFFull - (0xFFFFFFFFFFFFFFFFull - m64 + 1ull) % m64;
-    }
-    // ExpRestricted01::new(lambda), lambda = ln(m / (m-1)) -- same libm expressions as the crate / the oracle
-    double lambda = a.m >= 2 ? std::log((double) a.m / (double) (a.m - 1)) : 1.0;
-    a.e01.lambda = lambda;
-    a.e01.c1 = (std::exp(lambda) - 1.0) / lambda;
-    a.e01.c2 = std::log(2.0 / (1.0 + std::exp(-lambda))) / lambda;
-    a.e01.c3 = (1.0 - std::exp(-lambda)) / lambda;
-    a.sig_out = d_sig;
-    a.err = d_err;
-    a.ablate = 0u;
-#if KMU_DIAG // (diagnostic builds: parts of the kernels switched off / clocked, scripts/r05_pts_parts.sh)
-    if (const char *ab = getenv("KMU_PMH_ABLATE")) a.ablate = (uint32_t) atoi(ab);
-#endif
-    const bool aa = kmer_is_aa(p->kmer_type) || hashed_bytes != 0; // pre-hashed values use the byte-stream instantiation
-    typedef void (*sketch_kernel_t)(SketchArgs);
-    if (smallk_route(p, hashed_bytes, part_h != nullptr, d_block_rows != nullptr)) { // k <= 8: direct-indexed histogram
-        // the distinct (key, weight) pairs go to k_pmh_points through lists in HBM (12 bytes per base of scratch, the lists
-        // of the two-kernel route) unless that memory is not to be had: then the histogram kernel makes the points itself
-        bool emit = (size_t) 4 * (2 * (size_t) p->sketch_size + PTS_WAVE_WORDS) * 8 + WINV_LUT * 8 <= 150 * 1024;
-        if (const char *e = getenv("KMU_PMH_SPLIT")) emit = emit && atoi(e) != 0;
-        uint64_t total = 0;
-        if (emit) {
-            if (len_stats) total = len_stats[1];
-            else if (!ds.h_offsets.empty()) total = ds.h_offsets[ds.n_seq] - ds.h_offsets[0];
-            else {
-                uint64_t ends[2] = {0, 0};
-                KMU_HIP(ctx, hipMemcpyAsync(&ends[0], ds.offsets, 8, hipMemcpyDeviceToHost, ctx->stream));
-                KMU_HIP(ctx, hipMemcpyAsync(&ends[1], ds.offsets + ds.n_seq, 8, hipMemcpyDeviceToHost, ctx->stream));
-                KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
-                total = ends[1] - ends[0];
-            }
-            const size_t need_k = total * 8 + 64, need_w = total * 4 + 64;
-            size_t grow = 0, free_b = 0, total_b = 0;
-            if (ctx->bufs["cnt.partA"].bytes < need_k) grow += need_k + need_k / 8;
-            if (ctx->bufs["pmh.lst_w"].bytes < need_w) grow += need_w + need_w / 8;
-            if (grow && hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b < grow + total_b / 8) emit = false;
-            if (emit) {
-                void *lk, *lw, *ln;
-                KMU_TRY(dev_buf(ctx, "cnt.partA", need_k, &lk));
-                KMU_TRY(dev_buf(ctx, "pmh.lst_w", need_w, &lw));
-                KMU_TRY(dev_buf(ctx, "pmh.lst_n", (size_t) ds.n_seq * 8 + 64, &ln));
-                a.lst_keys = (uint64_t *) lk;
-                a.lst_w = (uint32_t *) lw;
-                a.lst_n = (uint32_t *) ln;
-                a.lst_nu = a.lst_n + ds.n_seq;
-                KMU_HIP(ctx, hipMemsetAsync(a.lst_nu, 0, (size_t) ds.n_seq * 4, ctx->stream));
-            }
-        }
-        // (Round 4, measured and not kept: the first point of every one of the 4^k possible keys from a table made once per call -- no
-        //  generator in pass 1 -- but 4e9 gathers of 16 bytes out of a 1 MB table are 4e9 lines from L2: k_pmh_points 26.1 against 18.9 ms
-        //  on config 3; 16-bit lower bounds of the samples in LDS in front of the gather: 52 ms.)
-        const sketch_kernel_t kern = emit ? k_sketch_smallk<true> : k_sketch_smallk<false>;
-        // LDS: histogram | slot minima (only when the kernel makes the points itself) | list of u16 indices | staged words
-        const size_t lds_fixed = (size_t) SMALLK_WORDS * 4 + (emit ? 0 : (size_t) 16 * a.m) + ((size_t) SMALLK_TILE + 2) * 4 + 64;
-        a.cap = (uint32_t) ((160 * 1024 - lds_fixed) / 2) & ~2047u;
-        if (a.cap > 32768u) a.cap = 32768u;
-        const size_t lds = lds_fixed + (size_t) a.cap * 2;
-        KMU_HIP(ctx, hipFuncSetAttribute((const void *) kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        void *q;
-        KMU_TRY(dev_buf(ctx, "queue", 256, &q));
-        KMU_HIP(ctx, hipMemsetAsync(q, 0, 256, ctx->stream));
-        a.queue = (uint32_t *) q;
-        a.queue2 = a.queue + 48;
-        int cus = ctx->num_cus;
-        if (const char *rs = getenv("KMU_PMH_RESERVE_CUS")) cus = std::max(cus / 2, cus - std::max(0, atoi(rs)));
-        const int grid = (int) std::max<uint64_t>(1, std::min<uint64_t>((uint64_t) ds.n_seq, (uint64_t) cus));
-        {
-            KernelTimer t(ctx, "k_sketch_smallk");
-            hipLaunchKernelGGL(kern, dim3(grid), dim3(1024), lds, ctx->stream, a);
-        }
-        KMU_HIP(ctx, hipGetLastError());
-        if (emit) {
-            KMU_TRY(launch_points(ctx, a, cus));
-        }
-        return KMU_OK;
-    }
-    // Big batches of whole DNA sequences go through two kernels: the multiset kernel leaves the (key, weight) pairs of
-    // every read in HBM, k_pmh_points (one wave per read, no workgroup barrier, 5 waves per SIMD) generates the points.
-    // ONT workload: 53.3 + 21.2 ms against 88.7 ms in one kernel, for 12 bytes of scratch per base.  One wave per read
-    // has a tail: the longest read keeps its wave busy while the others have run out of reads.  The route is taken
-    // when the gain (16 % of the single kernel's time) exceeds the expected overhang of that read; figures of an MI355X
-    // (a wave of k_pmh_points does 4.0e4 k-mers per ms, the single kernel 4.9e7 per ms with 256 CUs).
-    // KMU_PMH_SPLIT = 0 / 1: never / always.
-    const char *split_env = getenv("KMU_PMH_SPLIT");
-    const int split_mode = split_env ? atoi(split_env) : -1;
-    bool split = !bottomk && !aa && !part_h && !d_block_rows && p->block_size == 0 && !skip_longer &&
-                 (size_t) 4 * (2 * (size_t) p->sketch_size + PTS_WAVE_WORDS) * 8 + WINV_LUT * 8 <= 150 * 1024 && // four waves' arrays fit one workgroup
-                 split_mode != 0 && (split_mode == 1 || len_stats);
-    uint64_t list_total = 0; // number of bases = capacity of the (key, weight) lists
-    if (split) {
-        uint64_t &total = list_total;
-        if (len_stats) total = len_stats[1];
-        else if (!ds.h_offsets.empty()) total = ds.h_offsets[ds.n_seq] - ds.h_offsets[0];
-        else {
-            uint64_t ends[2] = {0, 0};
-            KMU_HIP(ctx, hipMemcpyAsync(&ends[0], ds.offsets, 8, hipMemcpyDeviceToHost, ctx->stream));
-            KMU_HIP(ctx, hipMemcpyAsync(&ends[1], ds.offsets + ds.n_seq, 8, hipMemcpyDeviceToHost, ctx->stream));
-            KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            total = ends[1] - ends[0];
-        }
-        if (split_mode != 1) {
-            const double cu_share = (double) ctx->num_cus / 256.0;
-            // (a wave of k_pmh_points does 4.0e4 k-mers per ms; a read beyond KMU_PMH_PTS_LONG is taken by four)
-            const char *ple = getenv("KMU_PMH_PTS_LONG");
-            const uint64_t pts_thr = ple ? (uint64_t) std::max(0, atoi(ple)) : 32768u;
-            const double wave_rate = pts_thr && len_stats[0] > pts_thr ? 1.6e5 : 4.0e4;
-            const double t_ideal = (double) total / (2.35e8 * cu_share), t_tail = (double) len_stats[0] / wave_rate; // ms
-            const double overhang = t_tail >= t_ideal ? t_tail - 0.5 * t_ideal : t_tail * t_tail / (2.0 * t_ideal);
-            // (r02: with the reads that fit a workgroup's registers on k_multiset_uq the two-kernel route takes 53 ms where the
-            //  single kernel takes 87 on the ONT workload: 39 % of the single kernel's time, 16 % before)
-            // (r03: 49.8 ms, 43 %; the points kernel 18.5 ms for 4.36 G k-mers)
-            const double gain = 0.43 * (double) total / (4.9e7 * cu_share);
-            if (gain <= overhang + 0.02) split = false; // (0.02 ms: the second launch)
-        }
-    }
-    if (split) {
-        const uint64_t total = list_total;
-        // 8 bytes per base: the same scratch the count build uses for its first partition level ("cnt.partA"); a
-        // context never runs the two at the same time, and at 4.4 Gbases per GPU a second copy would not fit next to
-        // the count table and the exchange buffers
-        const size_t need_k = total * 8 + 64, need_w = total * 4 + 64;
-        size_t grow = 0;
-        if (ctx->bufs["cnt.partA"].bytes < need_k) grow += need_k + need_k / 8;
-        if (ctx->bufs["pmh.lst_w"].bytes < need_w) grow += need_w + need_w / 8;
-        size_t free_b = 0, total_b = 0;
-        if (grow && split_mode != 1 && hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b < grow + total_b / 8)
-            split = false; // the lists would crowd out what comes after this call: one kernel, no lists
-        if (split) {
-            void *lk, *lw, *ln;
-            KMU_TRY(dev_buf(ctx, "cnt.partA", need_k, &lk));
-            KMU_TRY(dev_buf(ctx, "pmh.lst_w", need_w, &lw));
-            KMU_TRY(dev_buf(ctx, "pmh.lst_n", (size_t) ds.n_seq * 8 + 64, &ln));
-            a.lst_keys = (uint64_t *) lk;
-            a.lst_w = (uint32_t *) lw;
-            a.lst_n = (uint32_t *) ln;
-            a.lst_nu = a.lst_n + ds.n_seq;
-            KMU_HIP(ctx, hipMemsetAsync(a.lst_nu, 0, (size_t) ds.n_seq * 4, ctx->stream));
-        }
-    }
-    const char *plain_env = getenv("KMU_PMH_PLAIN"); // diagnostics: 0 = always the general instantiation
-    const bool plain = !bottomk && !aa && !part_h && !d_block_rows && p->block_size == 0 && !ds.packed &&
-                 !(plain_env && atoi(plain_env) == 0);
-    const sketch_kernel_t kern = bottomk ? (aa ? k_sketch_pmh3a<true, true> : k_sketch_pmh3a<false, true>)
-                                 : aa    ? k_sketch_pmh3a<true, false>
-                                 : split ? (plain ? k_sketch_pmh3a<false, false, true, true> : k_sketch_pmh3a<false, false, true>)
-                                 : plain ? k_sketch_pmh3a<false, false, false, true>
-                                         : k_sketch_pmh3a<false, false>;
-    const void *fn = (const void *) kern;
-    a.counts_out = d_counts;
+typedef void (*sketch_kernel_t)(SketchArgs);
+
+static int launch_main(kmu_ctx *ctx, const SketchArgs &a, sketch_kernel_t kern, int grid, size_t lds, const char *name) {
+    KernelTimer t(ctx, name);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(1024), lds, ctx->stream, a);
+    KMU_HIP(ctx, hipGetLastError());
+    return KMU_OK;
+}
+
+static int launch_smallk(kmu_ctx *ctx, SketchArgs a, const PmhPlan &plan) {
+    // (Round 4, measured and not kept: the first point of every one of the 4^k possible keys from a table made once per call -- no
+    //  generator in pass 1 -- but 4e9 gathers of 16 bytes out of a 1 MB table are 4e9 lines from L2: k_pmh_points 26.1 against 18.9 ms
+    //  on config 3; 16-bit lower bounds of the samples in LDS in front of the gather: 52 ms.)
+    const sketch_kernel_t kern = plan.lists ? k_sketch_smallk<true> : k_sketch_smallk<false>;
+    // LDS: histogram | slot minima (only when the kernel makes the points itself) | list of u16 indices | staged words
+    const size_t lds_fixed = (size_t) SMALLK_WORDS * 4 + (plan.lists ? 0 : (size_t) 16 * a.m) + ((size_t) SMALLK_TILE + 2) * 4 + 64;
+    a.cap = (uint32_t) ((160 * 1024 - lds_fixed) / 2) & ~2047u;
+    if (a.cap > 32768u) a.cap = 32768u;
+    const size_t lds = lds_fixed + (size_t) a.cap * 2;
+    KMU_HIP(ctx, hipFuncSetAttribute((const void *) kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    KMU_TRY(alloc_queue(ctx, a));
+    a.queue2 = a.queue + 48;
+    const int grid = (int) std::max<uint64_t>(1, std::min<uint64_t>((uint64_t) a.n_seq, (uint64_t) plan.cus));
+    KMU_TRY(launch_main(ctx, a, kern, grid, lds, "k_sketch_smallk"));
+    if (plan.lists) KMU_TRY(launch_points(ctx, a, plan.cus, plan.pts_long));
+    return KMU_OK;
+}
+
+// The general kernel's launch shape, shared by every route but SMALLK
+struct PmhShape {
+    size_t lds;     // what one workgroup takes
+    uint64_t slots; // workgroups resident at once on the CUs in use
+    int grid;
+};
+
+// LDS budget (tile_words, cap, part_target, tile_shift) of `kern`, the read queue, the grid and the scratch sized by it;
+// plain: the routes whose reads may be handed back to the general instantiation (redo list)
+static int pmh_shape(kmu_ctx *ctx, const kmu_sketch_params *p, SketchArgs &a, sketch_kernel_t kern, bool plain, int cus, PmhShape *g) {
+    const bool bottomk = p->algo == KMU_ALGO_BOTTOMK, aa = kmer_is_aa(p->kmer_type) || a.hashed_bytes != 0;
     a.bk_shift = (a.sig_bytes == 4 && p->hasher == KMU_HASHER_NOHASH) ? 20 : 52; // NoHashHasher of a u32 is < 2^32
     a.bk_mask = p->hasher == KMU_HASHER_INT64HASH ? 0xFFu : 0xFFFFu;
-    size_t lds_max = 160 * 1024;
-    {
-        hipFuncAttributes fa;
-        KMU_HIP(ctx, hipFuncGetAttributes(&fa, fn));
-        lds_max -= fa.sharedSizeBytes; // static LDS (none today) comes out of the same 160 KiB
-    }
-    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds_max) != hipSuccess) {
+    hipFuncAttributes fa;
+    KMU_HIP(ctx, hipFuncGetAttributes(&fa, (const void *) kern));
+    size_t lds_max = 160 * 1024 - fa.sharedSizeBytes; // static LDS (none today) comes out of the same 160 KiB
+    if (hipFuncSetAttribute((const void *) kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds_max) != hipSuccess) {
         (void) hipGetLastError();
         lds_max = 64 * 1024;
     }
@@ -317,178 +291,184 @@ static int launch_pmh3a(kmu_ctx *ctx, const kmu_sketch_params *p, const DevSeqs 
     a.inv_part_target = 1.0 / (double) a.part_target;
     if (plain && a.part_target > (uint32_t) KREG * 1024u)
         return fail(ctx, KMU_E_HIP, "internal: a single pass (%u k-mers) must fit the register keys of the PLAIN kernel", a.part_target);
-    {
-        const uint32_t tp = (a.tile_words - 2) * 16; // 4096 or 1024 words of 16 bases
-        a.tile_shift = 0;
-        while ((1u << a.tile_shift) < tp) a.tile_shift++;
-        if ((1u << a.tile_shift) != tp) return fail(ctx, KMU_E_HIP, "internal: tile size %u is not a power of two", tp);
-    }
-    size_t lds = (size_t) 12 * cap + fixed;
-    void *q;
-    KMU_TRY(dev_buf(ctx, "queue", 256, &q)); // [0] read cursor; u64 words 8..23: phase clocks (diagnostics)
-    KMU_HIP(ctx, hipMemsetAsync(q, 0, 256, ctx->stream));
-    a.queue = (uint32_t *) q;
-    const int threads = 1024;
-    int blocks_per_cu = std::max<int>(1, (int) (lds_max / lds));
-    int cus = ctx->num_cus;
-    if (const char *rs = getenv("KMU_PMH_RESERVE_CUS")) // CUs left to concurrent work (RCCL kernels of an exchange in flight)
-        cus = std::max(cus / 2, cus - std::max(0, atoi(rs)));
-    int grid = (int) std::min<uint64_t>((uint64_t) ds.n_seq, (uint64_t) cus * blocks_per_cu);
-    if (grid < 1) grid = 1;
-    {
-        void *sk, *si, *sw, *bk = nullptr, *bc = nullptr;
-        KMU_TRY(dev_buf(ctx, "pmh.scr_keys", (size_t) grid * cap * 8, &sk));
-        KMU_TRY(dev_buf(ctx, "pmh.scr_info", (size_t) grid * cap * 4, &si));
-        KMU_TRY(dev_buf(ctx, "pmh.scr_w", (size_t) grid * cap * 4, &sw));
-        a.scr_keys = (uint64_t *) sk;
-        a.scr_info = (uint32_t *) si;
-        a.scr_w = (uint32_t *) sw;
-        void *dkq;
-        KMU_TRY(dev_buf(ctx, "pmh.def_keys", (size_t) grid * DEF_CAP * 8, &dkq));
-        a.def_keys = (uint64_t *) dkq;
-        a.bk_keys = (uint64_t *) bk;
-        a.bk_cnt = (uint32_t *) bc;
-    }
-    if (split) a.queue2 = a.queue + 48;
+    const uint32_t tp = (a.tile_words - 2) * 16; // 4096 or 1024 words of 16 bases
+    a.tile_shift = 0;
+    while ((1u << a.tile_shift) < tp) a.tile_shift++;
+    if ((1u << a.tile_shift) != tp) return fail(ctx, KMU_E_HIP, "internal: tile size %u is not a power of two", tp);
+    g->lds = (size_t) 12 * cap + fixed;
+    KMU_TRY(alloc_queue(ctx, a));
+    g->slots = (uint64_t) cus * std::max<int>(1, (int) (lds_max / g->lds));
+    g->grid = (int) std::max<uint64_t>(1, std::min<uint64_t>((uint64_t) a.n_seq, g->slots));
+    void *sk, *si, *sw, *dk;
+    KMU_TRY(dev_buf(ctx, "pmh.scr_keys", (size_t) g->grid * cap * 8, &sk));
+    KMU_TRY(dev_buf(ctx, "pmh.scr_info", (size_t) g->grid * cap * 4, &si));
+    KMU_TRY(dev_buf(ctx, "pmh.scr_w", (size_t) g->grid * cap * 4, &sw));
+    KMU_TRY(dev_buf(ctx, "pmh.def_keys", (size_t) g->grid * DEF_CAP * 8, &dk));
+    a.scr_keys = (uint64_t *) sk;
+    a.scr_info = (uint32_t *) si;
+    a.scr_w = (uint32_t *) sw;
+    a.def_keys = (uint64_t *) dk;
     if (plain) {
         void *rl;
-        KMU_TRY(dev_buf(ctx, "pmh.redo", (size_t) ds.n_seq * 4 + 64, &rl));
+        KMU_TRY(dev_buf(ctx, "pmh.redo", (size_t) a.n_seq * 4 + 64, &rl));
         a.redo_list = (uint32_t *) rl;
     }
-    // Whole unpacked DNA reads on the two-kernel route: the reads that fit one workgroup's registers (<= 10 240 k-mers: 87 % of
-    // the reads, 64 % of the bases of the ONT workload) go through k_multiset_uq, which does not sort what occurs once; the
-    // longer ones (and the rare read with too many repeated keys) are handed to the general list-emitting kernel.
-    const char *uq_env = getenv("KMU_PMH_UQ"); // 0: every read through the counting-sort kernel (A/B)
-    const bool uq = split && plain && !(uq_env && atoi(uq_env) == 0);
-    bool main_launched = false, short_route = false;
-    const char *sh_env = getenv("KMU_PMH_SHORT"); // 0: short reads through k_multiset_uq like the others (A/B)
-    if (uq && len_stats && len_stats[0] < (uint64_t) SHORT_KEYS + (uint64_t) p->kmer_size && !(sh_env && atoi(sh_env) == 0)) {
-        // every read of the batch has at most 256 k-mers: one wave per read (k_multiset_short)
-        const size_t lds_s = 4 * SHORT_WAVE_BYTES;
-        const int per_cu = 5; // (88 registers: five waves per SIMD)
+    return KMU_OK;
+}
+
+// the general kernel over the n reads of a.redo_list (their count in queue[56], read back by the caller)
+static int launch_listed(kmu_ctx *ctx, SketchArgs a, sketch_kernel_t kern, const PmhShape &g, uint32_t n, const char *name) {
+    KMU_HIP(ctx, hipMemsetAsync(a.queue, 0, 256, ctx->stream));
+    a.read_list = a.redo_list;
+    a.n_queue = n;
+    return launch_main(ctx, a, kern, (int) std::min<uint64_t>((uint64_t) n, g.slots), g.lds, name);
+}
+
+// the count of long / redo reads the last launch listed (a host synchronisation)
+static int read_count(kmu_ctx *ctx, const SketchArgs &a, uint32_t *n) {
+    KMU_HIP(ctx, hipMemcpyAsync(n, a.queue + 56, 4, hipMemcpyDeviceToHost, ctx->stream));
+    KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return KMU_OK;
+}
+
+// every read of the batch has at most 256 k-mers: one wave per read builds its list (k_multiset_short), and one wave per
+// list keeps all keys of a read in its registers, round by round (k_pmh_points_short)
+static int launch_short(kmu_ctx *ctx, const SketchArgs &a, int cus) {
+    const size_t lds_s = 4 * SHORT_WAVE_BYTES;
+    const int per_cu = 5; // (88 registers: five waves per SIMD)
+    {
         KernelTimer t(ctx, "k_multiset_short");
-        hipLaunchKernelGGL(k_multiset_short, dim3((unsigned) std::max<uint64_t>(1, std::min<uint64_t>(((uint64_t) ds.n_seq + 3) / 4, (uint64_t) cus * per_cu))),
+        hipLaunchKernelGGL(k_multiset_short, dim3((unsigned) std::max<uint64_t>(1, std::min<uint64_t>(((uint64_t) a.n_seq + 3) / 4, (uint64_t) cus * per_cu))),
                            dim3(256), lds_s, ctx->stream, a);
-        KMU_HIP(ctx, hipGetLastError());
-        KMU_HIP(ctx, hipMemsetAsync(a.queue, 0, 256, ctx->stream)); // (the points kernel's cursor)
-        main_launched = true;
-        short_route = true;
-    } else if (uq) {
-        {
-            const auto ka = k_multiset_uq<512, UQ1_BM, UQ1_COLL, 4>;
-            const size_t lds_a = UqShape<512, UQ1_BM, UQ1_COLL>::LDS;
-            KMU_HIP(ctx, hipFuncSetAttribute((const void *) ka, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024));
-            KernelTimer t(ctx, "k_multiset_uq");
-            hipLaunchKernelGGL(ka, dim3((unsigned) std::max<uint64_t>(1, std::min<uint64_t>(ds.n_seq, (uint64_t) cus * 2))), dim3(512), lds_a,
-                               ctx->stream, a);
-        }
-        KMU_HIP(ctx, hipGetLastError());
-        uint32_t n_long = 0;
-        KMU_HIP(ctx, hipMemcpyAsync(&n_long, a.queue + 56, 4, hipMemcpyDeviceToHost, ctx->stream));
-        KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        if (ABL(256u)) { // diagnostics: thread-0 clocks of the first shape, share per phase
-            unsigned long long ph[10];
-            KMU_HIP(ctx, hipMemcpy(ph, (const uint64_t *) a.queue + 8, sizeof ph, hipMemcpyDeviceToHost));
-            static const char *nm[9] = {"stage+wipe", "B1", "keys+bitmaps", "B2", "next fetch", "sort out", "B3", "collisions", "end"};
-            double tot = 0;
-            for (int i = 0; i < 9; i++) tot += (double) ph[i];
-            fprintf(stderr, "[kmu uq phases]");
-            for (int i = 0; i < 9; i++) fprintf(stderr, " %s %.1f%%", nm[i], 100.0 * (double) ph[i] / (tot > 0 ? tot : 1));
-            fprintf(stderr, "  (%.3g clocks)\n", tot);
-        }
-        if (n_long) { // the second shape: reads of up to 20 480 k-mers, from the first one's list
-            const auto kb = k_multiset_uq<1024, UQ2_BM, UQ2_COLL, 4>;
-            const size_t lds_b = UqShape<1024, UQ2_BM, UQ2_COLL>::LDS;
-            void *rl2;
-            KMU_TRY(dev_buf(ctx, "pmh.redo2", (size_t) ds.n_seq * 4 + 64, &rl2));
-            KMU_HIP(ctx, hipFuncSetAttribute((const void *) kb, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            KMU_HIP(ctx, hipMemsetAsync(a.queue, 0, 256, ctx->stream));
-            uint32_t *list1 = a.redo_list;
-            a.read_list = list1;
-            a.redo_list = (uint32_t *) rl2;
-            a.n_queue = n_long;
-            {
-                KernelTimer t(ctx, "k_multiset_uq");
-                hipLaunchKernelGGL(kb, dim3((unsigned) std::max<uint64_t>(1, std::min<uint64_t>(n_long, (uint64_t) cus))), dim3(1024), lds_b, ctx->stream, a);
-            }
-            KMU_HIP(ctx, hipGetLastError());
-            KMU_HIP(ctx, hipMemcpyAsync(&n_long, a.queue + 56, 4, hipMemcpyDeviceToHost, ctx->stream));
-            KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            a.read_list = nullptr;
-            a.n_queue = ds.n_seq;
-        }
-        if (n_long) {
-            const sketch_kernel_t kgen = k_sketch_pmh3a<false, false, true>; // reads its reads from a list; repetitive reads in rounds
-            if (lds_max > 64 * 1024 && hipFuncSetAttribute((const void *) kgen, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds_max) != hipSuccess)
-                return fail(ctx, KMU_E_HIP, "hipFuncSetAttribute failed for the general list-emitting kernel");
-            KMU_HIP(ctx, hipMemsetAsync(a.queue, 0, 256, ctx->stream));
-            a.read_list = a.redo_list;
-            a.n_queue = n_long;
-            const int gridl = (int) std::min<uint64_t>((uint64_t) n_long, (uint64_t) cus * blocks_per_cu);
-            KernelTimer t(ctx, "k_sketch_pmh3a");
-            hipLaunchKernelGGL(kgen, dim3(gridl), dim3(threads), lds, ctx->stream, a);
-            KMU_HIP(ctx, hipGetLastError());
-            a.read_list = nullptr;
-            a.n_queue = ds.n_seq;
-            if (ABL(256u)) { // diagnostics: the phases of the list-emitting launch (the words are wiped for the points kernel below)
-                unsigned long long ph[10];
-                KMU_HIP(ctx, hipMemcpy(ph, (const uint64_t *) a.queue + 8, sizeof ph, hipMemcpyDeviceToHost));
-                static const char *nm[10] = {"header", "stage", "A1", "scan", "place", "A3", "B1", "B2+clear", "row", "next+parked"};
-                double tot = 0;
-                for (int i = 0; i < 10; i++) tot += (double) ph[i];
-                fprintf(stderr, "[kmu list phases] grid %d, %u reads:", gridl, n_long);
-                for (int i = 0; i < 10; i++) fprintf(stderr, " %s %.1f%%", nm[i], 100.0 * (double) ph[i] / (tot > 0 ? tot : 1));
-                fprintf(stderr, "  (clocks/wg %.3g)\n", tot / gridl);
-            }
-        }
-        KMU_HIP(ctx, hipMemsetAsync(a.queue, 0, 256, ctx->stream)); // (the points kernel's cursor; nothing is left to redo)
-        main_launched = true;
-    }
-    if (!main_launched) {
-        KernelTimer t(ctx, bottomk ? "k_sketch_bottomk" : "k_sketch_pmh3a");
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), lds, ctx->stream, a);
     }
     KMU_HIP(ctx, hipGetLastError());
-    if (split && short_route) { // lists of at most 256 pairs: all keys of a read in a wave's registers, round by round
-        const sketch_kernel_t kpts = a.sig_bytes == 4 ? k_pmh_points_short<true> : k_pmh_points_short<false>;
-        const size_t lds2 = (size_t) 4 * (2 * (size_t) a.m + 2) * 8 + WINV_LUT * 8;
-        if (lds2 > 64 * 1024)
-            KMU_HIP(ctx, hipFuncSetAttribute((const void *) kpts, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        const int per_cu = (int) std::max<size_t>(1, std::min<size_t>(4, (160 * 1024) / lds2));
-        const int grid2 = (int) std::max<uint64_t>(1, std::min<uint64_t>(((uint64_t) ds.n_seq + 3) / 4, (uint64_t) cus * per_cu));
-        KernelTimer t(ctx, "k_pmh_points_short");
-        hipLaunchKernelGGL(kpts, dim3(grid2), dim3(256), lds2, ctx->stream, a);
-        KMU_HIP(ctx, hipGetLastError());
-    } else if (split) {
-        KMU_TRY(launch_points(ctx, a, cus));
-    }
-    if (plain && !uq) { // (after the points kernel, whose row for such a sequence is empty)
-        // sequences whose k-mers overflowed a pass (repetitive ones): the general instantiation redoes them in rounds
-        uint32_t n_redo = 0;
-        KMU_HIP(ctx, hipMemcpyAsync(&n_redo, a.queue + 56, 4, hipMemcpyDeviceToHost, ctx->stream));
-        KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        if (n_redo) {
-            KMU_HIP(ctx, hipMemsetAsync(a.queue, 0, 256, ctx->stream));
-            a.read_list = a.redo_list;
-            a.n_queue = n_redo;
-            const int grid2 = (int) std::min<uint64_t>((uint64_t) n_redo, (uint64_t) cus * blocks_per_cu);
-            KernelTimer t(ctx, "k_sketch_pmh3a_redo");
-            hipLaunchKernelGGL(kern_redo, dim3(grid2), dim3(threads), lds, ctx->stream, a);
-            KMU_HIP(ctx, hipGetLastError());
-        }
-    }
-    if (ABL(256u)) { // diagnostics: mean clocks per workgroup and phase
-        unsigned long long ph[10];
-        KMU_HIP(ctx, hipMemcpyAsync(ph, (const uint64_t *) a.queue + 8, sizeof ph, hipMemcpyDeviceToHost, ctx->stream));
-        KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        static const char *nm[10] = {"header", "stage", "A1", "scan", "place", "A3", "B1", "B2+clear", "row", "next+parked"};
-        double tot = 0;
-        for (int i = 0; i < 10; i++) tot += (double) ph[i];
-        fprintf(stderr, "[kmu phases] grid %d:", grid);
-        for (int i = 0; i < 10; i++) fprintf(stderr, " %s %.1f%%", nm[i], 100.0 * (double) ph[i] / (tot > 0 ? tot : 1));
-        fprintf(stderr, "  (clocks/wg %.3g)\n", tot / grid);
-    }
+    KMU_HIP(ctx, hipMemsetAsync(a.queue, 0, 256, ctx->stream)); // (the points kernel's cursor)
+    const sketch_kernel_t kpts = a.sig_bytes == 4 ? k_pmh_points_short<true> : k_pmh_points_short<false>;
+    const size_t lds2 = (size_t) 4 * (2 * (size_t) a.m + 2) * 8 + WINV_LUT * 8;
+    if (lds2 > 64 * 1024)
+        KMU_HIP(ctx, hipFuncSetAttribute((const void *) kpts, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    const int per_cu2 = (int) std::max<size_t>(1, std::min<size_t>(4, (160 * 1024) / lds2));
+    const int grid2 = (int) std::max<uint64_t>(1, std::min<uint64_t>(((uint64_t) a.n_seq + 3) / 4, (uint64_t) cus * per_cu2));
+    KernelTimer t(ctx, "k_pmh_points_short");
+    hipLaunchKernelGGL(kpts, dim3(grid2), dim3(256), lds2, ctx->stream, a);
+    KMU_HIP(ctx, hipGetLastError());
     return KMU_OK;
+}
+
+// Whole unpacked DNA reads on the two-kernel route: the reads that fit one workgroup's registers (<= 10 240 k-mers: 87 % of
+// the reads, 64 % of the bases of the ONT workload) go through k_multiset_uq, which does not sort what occurs once; the
+// longer ones (and the rare read with too many repeated keys) are handed to the second shape, then to the general
+// list-emitting kernel (`kern`, reading its reads from a list; repetitive reads in rounds).
+static int launch_uq(kmu_ctx *ctx, SketchArgs a, sketch_kernel_t kern, const PmhShape &g, const PmhPlan &plan) {
+    {
+        const auto ka = k_multiset_uq<512, UQ1_BM, UQ1_COLL, 4>;
+        const size_t lds_a = UqShape<512, UQ1_BM, UQ1_COLL>::LDS;
+        KMU_HIP(ctx, hipFuncSetAttribute((const void *) ka, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024));
+        KernelTimer t(ctx, "k_multiset_uq");
+        hipLaunchKernelGGL(ka, dim3((unsigned) std::max<uint64_t>(1, std::min<uint64_t>(a.n_seq, (uint64_t) plan.cus * 2))), dim3(512), lds_a,
+                           ctx->stream, a);
+    }
+    KMU_HIP(ctx, hipGetLastError());
+    uint32_t n_long = 0;
+    KMU_TRY(read_count(ctx, a, &n_long));
+    if (n_long) { // the second shape: reads of up to 20 480 k-mers, from the first one's list
+        const auto kb = k_multiset_uq<1024, UQ2_BM, UQ2_COLL, 4>;
+        const size_t lds_b = UqShape<1024, UQ2_BM, UQ2_COLL>::LDS;
+        void *rl2;
+        KMU_TRY(dev_buf(ctx, "pmh.redo2", (size_t) a.n_seq * 4 + 64, &rl2));
+        KMU_HIP(ctx, hipFuncSetAttribute((const void *) kb, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        KMU_HIP(ctx, hipMemsetAsync(a.queue, 0, 256, ctx->stream));
+        SketchArgs b = a;
+        b.read_list = a.redo_list;
+        b.redo_list = (uint32_t *) rl2;
+        b.n_queue = n_long;
+        {
+            KernelTimer t(ctx, "k_multiset_uq");
+            hipLaunchKernelGGL(kb, dim3((unsigned) std::max<uint64_t>(1, std::min<uint64_t>(n_long, (uint64_t) plan.cus))), dim3(1024), lds_b, ctx->stream, b);
+        }
+        KMU_HIP(ctx, hipGetLastError());
+        KMU_TRY(read_count(ctx, a, &n_long));
+        a.redo_list = b.redo_list;
+    }
+    if (n_long) KMU_TRY(launch_listed(ctx, a, kern, g, n_long, "k_sketch_pmh3a"));
+    KMU_HIP(ctx, hipMemsetAsync(a.queue, 0, 256, ctx->stream)); // (the points kernel's cursor; nothing is left to redo)
+    return launch_points(ctx, a, plan.cus, plan.pts_long);
+}
+
+// PLAIN, one kernel; the sequences whose k-mers overflowed a pass (repetitive ones) are redone in rounds by the general
+// instantiation, after the first launch (whose row for such a sequence is empty)
+static int launch_one_pass(kmu_ctx *ctx, const SketchArgs &a, sketch_kernel_t kern, const PmhShape &g) {
+    KMU_TRY(launch_main(ctx, a, kern, g.grid, g.lds, "k_sketch_pmh3a"));
+    uint32_t n_redo = 0;
+    KMU_TRY(read_count(ctx, a, &n_redo));
+    if (n_redo) KMU_TRY(launch_listed(ctx, a, k_sketch_pmh3a<false, false>, g, n_redo, "k_sketch_pmh3a_redo"));
+    return KMU_OK;
+}
+
+static SketchArgs sketch_args(const kmu_sketch_params *p, const DevSeqs &ds, void *d_sig, uint32_t *d_err, const PmhInputs &in) {
+    SketchArgs a;
+    memset(&a, 0, sizeof a); // (bk_keys, bk_cnt and ablate stay null / 0)
+    a.skip_longer = in.skip_longer;
+    a.hashed = in.hashed;
+    a.hashed_bytes = in.hashed_bytes;
+    a.part_h = in.part_h;
+    a.part_k = in.part_k;
+    a.bases = ds.bases;
+    a.offsets = ds.offsets;
+    a.packed_offsets = ds.packed_offsets;
+    a.block_rows = in.d_block_rows;
+    a.n_seq = ds.n_seq;
+    a.n_queue = ds.n_seq;
+    a.packed = ds.packed;
+    a.total_bytes = ds.total_bytes;
+    a.cfg = KmerCfg{p->kmer_type, in.hashed_bytes ? 1 : p->kmer_size, p->fhash};
+    a.m = p->sketch_size;
+    a.hasher = p->hasher;
+    a.rand08 = (p->flags & KMU_FLAG_RAND08) ? 1 : 0;
+    a.sig_bytes = kmer_val_bytes(p->kmer_type);
+    a.block_size = (uint32_t) p->block_size;
+    const uint32_t m32 = (uint32_t) a.m;
+    const uint64_t m64 = (uint64_t) a.m;
+    a.idx_thresh = (0u - m32) % m32;
+    a.idx_zone = 0xFFFFFFFFFFFFFFFFull - (0xFFFFFFFFFFFFFFFFull - m64 + 1ull) % m64;
+    // ExpRestricted01::new(lambda), lambda = ln(m / (m-1)) -- same libm expressions as the crate / the oracle
+    double lambda = a.m >= 2 ? std::log((double) a.m / (double) (a.m - 1)) : 1.0;
+    a.e01.lambda = lambda;
+    a.e01.c1 = (std::exp(lambda) - 1.0) / lambda;
+    a.e01.c2 = std::log(2.0 / (1.0 + std::exp(-lambda))) / lambda;
+    a.e01.c3 = (1.0 - std::exp(-lambda)) / lambda;
+    a.sig_out = d_sig;
+    a.err = d_err;
+    return a;
+}
+
+static int launch_pmh3a(kmu_ctx *ctx, const kmu_sketch_params *p, const DevSeqs &ds, void *d_sig, uint32_t *d_err,
+                        const PmhInputs &in = PmhInputs()) {
+    SketchArgs a = sketch_args(p, ds, d_sig, d_err, in);
+    PmhPlan plan;
+    KMU_TRY(pmh_route(ctx, p, ds, in, &plan));
+    if (plan.lists) KMU_TRY(alloc_lists(ctx, a, plan.list_bases));
+    if (plan.route == PmhRoute::SMALLK) return launch_smallk(ctx, a, plan);
+    const bool bottomk = p->algo == KMU_ALGO_BOTTOMK, aa = kmer_is_aa(p->kmer_type) || in.hashed_bytes != 0;
+    const bool plain = plan.route == PmhRoute::SHORT || plan.route == PmhRoute::UQ || plan.route == PmhRoute::ONE_PASS;
+    const sketch_kernel_t kern = plan.lists                    ? k_sketch_pmh3a<false, false, true>
+                                 : plan.route == PmhRoute::ONE_PASS ? k_sketch_pmh3a<false, false, false, true>
+                                 : bottomk                     ? (aa ? k_sketch_pmh3a<true, true> : k_sketch_pmh3a<false, true>)
+                                 : aa                          ? k_sketch_pmh3a<true, false>
+                                                               : k_sketch_pmh3a<false, false>;
+    a.counts_out = in.d_counts;
+    PmhShape g;
+    KMU_TRY(pmh_shape(ctx, p, a, kern, plain, plan.cus, &g));
+    if (plan.lists) a.queue2 = a.queue + 48;
+    switch (plan.route) {
+    case PmhRoute::SHORT: return launch_short(ctx, a, plan.cus);
+    case PmhRoute::UQ: return launch_uq(ctx, a, kern, g, plan);
+    case PmhRoute::LISTS:
+        KMU_TRY(launch_main(ctx, a, kern, g.grid, g.lds, "k_sketch_pmh3a"));
+        return launch_points(ctx, a, plan.cus, plan.pts_long);
+    case PmhRoute::ONE_PASS: return launch_one_pass(ctx, a, kern, g);
+    default: return launch_main(ctx, a, kern, g.grid, g.lds, bottomk ? "k_sketch_bottomk" : "k_sketch_pmh3a");
+    }
 }
 
 // One sketch over a device array of n pre-hashed values (u64, zero-extended Kmer::Val).
@@ -513,7 +493,12 @@ static int sketch_all_hashed(kmu_ctx *ctx, const kmu_sketch_params *p, const uin
         leaves.offsets = bounds;
         leaves.n_seq = (uint32_t) n_leaves;
         leaves.total_bytes = 1; // unused for pre-hashed input
-        KMU_TRY(launch_pmh3a(ctx, p, leaves, nullptr, nullptr, nullptr, d_err, items, 8, (uint64_t *) ph, (uint64_t *) pk));
+        PmhInputs in;
+        in.hashed = items;
+        in.hashed_bytes = 8;
+        in.part_h = (uint64_t *) ph;
+        in.part_k = (uint64_t *) pk;
+        KMU_TRY(launch_pmh3a(ctx, p, leaves, nullptr, d_err, in));
         {
             KernelTimer t(ctx, "k_pmh_reduce");
             hipLaunchKernelGGL(k_pmh_reduce, dim3(m), dim3(256), 0, ctx->stream, (const uint64_t *) ph, (const uint64_t *) pk,
@@ -553,8 +538,10 @@ static int sketch_pmh_per_seq(kmu_ctx *ctx, const kmu_sketch_params *p, const De
     uint32_t skip_longer = 0;
     uint64_t len_stats[2] = {0, 0}; // longest sequence, all bases (whole sequences only)
     std::vector<uint32_t> long_seqs;
+    PmhInputs in;
+    in.d_block_rows = d_block_rows;
     if (p->block_size == 0 && smallk_route(p, 0, false, d_block_rows != nullptr)) // any length fits the histogram
-        return launch_pmh3a(ctx, p, ds, d_block_rows, d_sig, nullptr, d_err);
+        return launch_pmh3a(ctx, p, ds, d_sig, d_err, in);
     if (p->block_size == 0) {
         std::vector<uint64_t> h_off;
         if (h_offsets) {
@@ -584,7 +571,9 @@ static int sketch_pmh_per_seq(kmu_ctx *ctx, const kmu_sketch_params *p, const De
             skip_longer = LONG_SEQ_KMERS;
         }
     }
-    KMU_TRY(launch_pmh3a(ctx, p, ds, d_block_rows, d_sig, nullptr, d_err, nullptr, 0, nullptr, nullptr, skip_longer, len_stats));
+    in.skip_longer = skip_longer;
+    in.len_stats = len_stats;
+    KMU_TRY(launch_pmh3a(ctx, p, ds, d_sig, d_err, in));
     for (uint32_t i : long_seqs) {
         DevSeqs one = ds;
         one.offsets = ds.offsets + i;
@@ -707,7 +696,11 @@ extern "C" int kmu_sketch(kmu_ctx *ctx, const kmu_sketch_params *p_in, const uin
         case KMU_ALGO_OPTDENS:
         case KMU_ALGO_REVOPTDENS:
         case KMU_ALGO_HLL: KMU_TRY(launch_dens(ctx, p, ds, d_sig, d_err, nullptr, 0)); break;
-        case KMU_ALGO_BOTTOMK: KMU_TRY(launch_pmh3a(ctx, p, ds, nullptr, d_sig, d_counts, d_err)); break;
+        case KMU_ALGO_BOTTOMK: {
+            PmhInputs in;
+            in.d_counts = d_counts;
+            KMU_TRY(launch_pmh3a(ctx, p, ds, d_sig, d_err, in));
+        } break;
         default: return fail(ctx, KMU_E_UNSUPPORTED, "no per-sequence kernel for algo %d", p->algo);
         }
     }
@@ -788,7 +781,13 @@ extern "C" int kmu_sketch_hashed(kmu_ctx *ctx, const kmu_sketch_params *p_in, co
         ds.n_seq = n_seq;
         ds.total_bytes = 1;
         if (p->algo == KMU_ALGO_SUPER || p->algo == KMU_ALGO_SUPER2) KMU_TRY(launch_super(ctx, p, ds, d_sig, d_err, d_vals, w, nullptr));
-        else KMU_TRY(launch_pmh3a(ctx, p, ds, nullptr, d_sig, d_counts, d_err, d_vals, w));
+        else {
+            PmhInputs in;
+            in.d_counts = d_counts;
+            in.hashed = d_vals;
+            in.hashed_bytes = w;
+            KMU_TRY(launch_pmh3a(ctx, p, ds, d_sig, d_err, in));
+        }
     }
     if (p->mem == KMU_MEM_HOST) {
         KMU_HIP(ctx, hipMemcpyAsync(sig_out, d_sig, rows * m * sigb, hipMemcpyDeviceToHost, ctx->stream));

@@ -34,8 +34,8 @@ struct SketchArgs {
     // bottom-k (MinHashCount, src/sketching/minhash.rs:62-99)
     int bk_shift;         // bucket = (key >> bk_shift) & 0xFFF: the 12 most significant *used* bits of the hash
     uint32_t bk_mask;     // count wrap mask: 0xFFFF (u16 counts) or 0xFF (MinInvHashCountKmer)
-    uint64_t *bk_keys;    // per-workgroup running list between partition passes: [grid][m]
-    uint32_t *bk_cnt;
+    uint64_t *bk_keys;    // (unused, always null: see `ablate`)
+    uint32_t *bk_cnt;     // (unused, always null)
     uint32_t *counts_out; // may be null
     // pre-hashed input (kmu_sketch_hashed, and the leaves of a sketch over all sequences): the "sequence" is an array
     // of Kmer::Val values, offsets count values; runs on the AA instantiation (no code-word staging) with k = 1
@@ -63,7 +63,10 @@ struct SketchArgs {
     uint32_t tile_words;  // staged code words per tile (16 bases each)
     uint32_t idx_thresh;  // rand 0.9 Uniform<usize>(0, m): reject while lo < (2^32 - m) % m
     uint64_t idx_zone;    // rand 0.8 Uniform<usize>(0, m): accept while lo <= zone
-    uint32_t ablate;      // diagnostics only (KMU_PMH_ABLATE): 1 skip pass B math, 2 skip table insert, 4 skip hashing
+    // (unused, always 0.  It, bk_keys and bk_cnt stay because the layout of this block steers the register allocation of the
+    //  hot kernels: without `ablate` k_sketch_pmh3a<false, false> spills 309 SGPRs instead of 292, k_pmh_points<true> 34 instead
+    //  of 32.  Removing them is a performance change of its own.)
+    uint32_t ablate;
     Exp01 e01;
     void *sig_out;
     uint32_t *queue; // atomic read counter
@@ -105,9 +108,6 @@ static constexpr size_t SHORT_WAVE_BYTES = (size_t) SHORT_SLOTS * 12 + SHORT_WOR
 static constexpr uint32_t SMALLK_WORDS = 32768;  // LDS words of the histogram (128 KiB)
 static constexpr uint32_t SMALLK_TILE = 1024;    // staged code words per tile
 
-// diagnostic builds (-DKMU_DIAG=1): bits of KMU_PMH_ABLATE leave phases of the kernels out / clock them
-#define ABL(bits) (KMU_DIAG && (a.ablate & (bits)))
-
 // ---- the kernels (definitions and comments: kmu_sketch_kernels.hip) ------------------------------------------------------------
 template <bool AA, bool BOTTOMK, bool EMIT = false, bool PLAIN = false>
 __global__ void k_sketch_pmh3a(SketchArgs a);
@@ -132,7 +132,7 @@ __global__ void k_widen_u32(const uint32_t *in, uint64_t n, uint64_t *out);
 // the forms of the template kernels the host launches: instantiated in kmu_sketch_kernels.hip, declared for everybody else
 #define KMU_SKETCH_KERNEL_FORMS(X)                                                                                                  \
     X(k_sketch_pmh3a<false, false>) X(k_sketch_pmh3a<false, false, true>) X(k_sketch_pmh3a<true, true>) X(k_sketch_pmh3a<true, false>) \
-    X(k_sketch_pmh3a<false, true>) X(k_sketch_pmh3a<false, false, true, true>) X(k_sketch_pmh3a<false, false, false, true>)            \
+    X(k_sketch_pmh3a<false, true>) X(k_sketch_pmh3a<false, false, false, true>)                                                       \
     X(k_pmh_points<true>) X(k_pmh_points<false>) X(k_pmh_points_short<true>) X(k_pmh_points_short<false>)                             \
     X(k_multiset_uq<512, UQ1_BM, UQ1_COLL, 4>) X(k_multiset_uq<1024, UQ2_BM, UQ2_COLL, 4>) X(k_sketch_smallk<true>) X(k_sketch_smallk<false>)
 #ifndef KMU_SKETCH_KERNELS_TU

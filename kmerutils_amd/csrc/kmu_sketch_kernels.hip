@@ -295,6 +295,7 @@ __device__ __forceinline__ void bucket_clear(uint32_t *bst) {
 // it: 93.7 against 89.1 ms -- the allocator trades the shorter hashing code for spills elsewhere.)
 template <bool AA, bool BOTTOMK, bool EMIT, bool PLAIN>
 __global__ void __launch_bounds__(1024) k_sketch_pmh3a(SketchArgs a) {
+    static_assert(!(EMIT && PLAIN), "no route emits lists from the PLAIN form: those reads take k_multiset_uq");
     if constexpr (PLAIN) { // the compiler sees constants wherever these are read below
         a.packed = 0;
         a.block_size = 0;
@@ -386,21 +387,8 @@ __global__ void __launch_bounds__(1024) k_sketch_pmh3a(SketchArgs a) {
     uint32_t flag_sel = 0; // uniform
     uint32_t nv_r = 0xFFFFFFFFu, pf_r = 0xFFFFFFFFu, pf_nw = 0;
     u32x4 raw_pf = (u32x4) (0u); // PLAIN: this thread's parked chunk of the next read
-    // diagnostics (KMU_PMH_ABLATE & 256): thread 0 accumulates the clock spent in every phase of the read loop
-    uint64_t ph_acc[10], ph_t = 0;
-#pragma unroll
-    for (int i = 0; i < 10; i++) ph_acc[i] = 0;
-    const bool ph_on = KMU_DIAG && ABL(256u) && tid == 0;
-    auto phase = [&](int i) {
-        if (ph_on) {
-            const uint64_t t = __builtin_readcyclecounter();
-            ph_acc[i] += t - ph_t;
-            ph_t = t;
-        }
-    };
     lds_barrier();
     uint32_t r = uniform_u32(misc[M_READ]);
-    if (ph_on) ph_t = __builtin_readcyclecounter();
     while (r < a.n_queue) {
         // Thread 0 takes the next read now (the atomic's latency hides under this read's work), posts it in
         // misc[M_NEXT] before the first barrier after the ranks are taken, and everybody picks it up behind that barrier.
@@ -433,7 +421,6 @@ __global__ void __launch_bounds__(1024) k_sketch_pmh3a(SketchArgs a) {
         const uint32_t B = a.block_size ? a.block_size : (nk_all ? nk_all : 1u);
         uint32_t nblocks = a.block_size ? (uint32_t) (((uint64_t) L + B - 1) / B) : 1u;
         if (a.skip_longer && nk_all > a.skip_longer) nblocks = 0; // its row comes from the global path
-        phase(0); // read header
         for (uint32_t blk = 0; blk < nblocks; blk++) {
             const uint64_t pb64 = (uint64_t) blk * B, pe64 = pb64 + B;
             const uint32_t pb = pb64 > nk_all ? nk_all : (uint32_t) pb64, pe = pe64 > nk_all ? nk_all : (uint32_t) pe64;
@@ -441,7 +428,6 @@ __global__ void __launch_bounds__(1024) k_sketch_pmh3a(SketchArgs a) {
             // number of hash partitions: any P with nk / P comfortably below the dense capacity will do (the multiset is
             // exact for every P), so no 64-bit division: a product with the reciprocal, rounded up
             uint32_t P = nk == 0 ? 0u : nk <= a.part_target ? 1u : (uint32_t) ((double) nk * a.inv_part_target) + 1u;
-            if (ABL(64u)) P = 0;
             uint32_t bad = 0;
             bool full = false;
             bool redo = false; // uniform; PLAIN only
@@ -536,8 +522,7 @@ __global__ void __launch_bounds__(1024) k_sketch_pmh3a(SketchArgs a) {
                                     }
                                     lds_barrier();
                                 }
-                                phase(1); // read header + code words staged
-                                for (uint32_t pr = tp0; pr < tp1 && !ABL(4096u); pr += (uint32_t) KREG * nthreads) {
+                                for (uint32_t pr = tp0; pr < tp1; pr += (uint32_t) KREG * nthreads) {
                                     // Where a key waits for the scan: in registers (one pass over a read that fits: its first
                                     // KREG * nthreads positions), parked unsorted in the still unused dense arrays (a pass of
                                     // a partitioned read keeps 1/P of the positions it scans), else in the global scratch.
@@ -546,7 +531,7 @@ __global__ void __launch_bounds__(1024) k_sketch_pmh3a(SketchArgs a) {
 #pragma unroll
                                     for (int q = 0; q < KREG; q++) {
                                         const uint32_t p = pr + (uint32_t) q * nthreads + tid;
-                                        if (p < tp1 && !ABL(32u)) {
+                                        if (p < tp1) {
                                             uint64_t val, rc = 0;
                                             if (AA && a.hashed_bytes) {
                                                 val = a.hashed_bytes == 4
@@ -567,14 +552,13 @@ __global__ void __launch_bounds__(1024) k_sketch_pmh3a(SketchArgs a) {
                                                 val = v >> (64 - 2 * k);
                                                 rc = revcomp_val(val, k);
                                             }
-                                            bool go = !ABL(4u);
+                                            bool go = true;
                                             uint64_t key = 0;
                                             uint32_t h = 0;
                                             if (go) {
                                                 key = (AA && a.hashed_bytes) ? val : fast64 ? int64_hash(rc < val ? rc : val) : apply_fhash(cfg, val, rc);
                                                 if (BOTTOMK) key = hasher_finish(a.hasher, key, sig32);
                                                 h = mix32(key);
-                                                if (ABL(2u)) go = false;
                                                 const uint32_t kp = P > 1 ? mulhi32(h * 0x85EBCA6Bu, P) : 0u;
                                                 if (kp != part) {
                                                     go = false;
@@ -607,7 +591,6 @@ __global__ void __launch_bounds__(1024) k_sketch_pmh3a(SketchArgs a) {
                             __syncthreads();
                             if (defer_on) def_valid = uniform_u32(misc[M_DEF]) == 0u; // complete (every position scanned) if all fitted
                             // ---- A2: counts -> starts, dense placement ---------------------------------------------
-                            phase(2); // A1
                             r_follow = uniform_u32(misc[M_NEXT]);
                             if (nv_r != r_follow && r_follow < a.n_queue) { nv = view_of(r_follow); nv_r = r_follow; }
                             // parked keys move to the registers (the barriers of the scan separate this from the placement)
@@ -621,15 +604,13 @@ __global__ void __launch_bounds__(1024) k_sketch_pmh3a(SketchArgs a) {
                                 }
 
                             }
-                            phase(9); // next read's header, parked keys -> registers
-                            if (!ABL(128u)) bucket_scan(bst, wtot);
-                            phase(3); // scan
+                            bucket_scan(bst, wtot);
                             const uint32_t n_keys = uniform_u32(bst[NBUCKETS]);
                             // (PLAIN: a single pass keeps every key in registers -- the host checks part_target -- and a
                             //  partitioned one parks them: the scratch lists are not used)
                             const uint32_t n_scr = (PLAIN || parked_pass) ? 0u : uniform_u32(misc[M_NSCR]);
                             if (n_keys > cap || n_scr > cap || n_park > (uint32_t) KREG * nthreads || n_park > cap) overflow = true;
-                            if (!overflow && !ABL(1024u)) {
+                            if (!overflow) {
                                 // (all bucket starts are requested before the first store: a load behind a store to LDS
                                 // cannot be moved up by the compiler, and ten dependent round trips are the phase)
 #pragma unroll
@@ -653,10 +634,9 @@ __global__ void __launch_bounds__(1024) k_sketch_pmh3a(SketchArgs a) {
                                 }
                             }
                             __syncthreads();
-                            phase(4); // placement
                             // ---- A3: a key with an earlier equal key in its bucket segment hands its weight over ------
                             const bool do_pf = !AA && !BOTTOMK && !a.packed && !overflow && last_round && blk + 1 == nblocks &&
-                                               part + 1 == P && nv_r == r_follow && r_follow < a.n_queue && !ABL(512u) &&
+                                               part + 1 == P && nv_r == r_follow && r_follow < a.n_queue &&
                                                (size_t) a.tile_words * 4 >= (size_t) nthreads * 16;
                             if (do_pf) {
                                 uint32_t n = first_tile_words(nv);
@@ -668,7 +648,7 @@ __global__ void __launch_bounds__(1024) k_sketch_pmh3a(SketchArgs a) {
                                 pf_r = r_follow;
                                 pf_nw = n;
                             }
-                            if (!overflow && !ABL(2048u)) {
+                            if (!overflow) {
                                 // rb[q] becomes (own position << 16) | cursor; the walks of a thread's keys advance together,
                                 // five LDS reads in flight at a time, instead of one key after the other
 #pragma unroll
@@ -718,7 +698,6 @@ __global__ void __launch_bounds__(1024) k_sketch_pmh3a(SketchArgs a) {
                                 }
                             }
                             __syncthreads();
-                            phase(5); // A3
                             if (!PLAIN && !overflow && !last_round) {
                                 // ---- compact the distinct pairs into the carry list (scr_keys / scr_w) ------------------
                                 if (tid == 0) misc[M_NSCR] = 0;
@@ -768,9 +747,9 @@ __global__ void __launch_bounds__(1024) k_sketch_pmh3a(SketchArgs a) {
                                         uint32_t w = 0;
                                         if (i < n_keys) { key = dk[i]; w = dw[i]; }
                                         const bool have = w != 0u;
-                                        if (__any(have) && !ABL(1u)) {
+                                        if (__any(have)) {
                                             const bool deferred = pmh3a_first_point(a, sig32, hmin, sig, qmax_sh, ((chunk + wave) & B1_REFRESH_MASK) == 0u, have, key, w);
-                                            if (deferred && !ABL(16u)) { dw[i] = w | 0x80000000u; any_deferred = true; }
+                                            if (deferred) { dw[i] = w | 0x80000000u; any_deferred = true; }
                                         }
                                     }
                                     // ---- B2: more points for the remembered keys that still lie below q_max -----------
@@ -779,11 +758,10 @@ __global__ void __launch_bounds__(1024) k_sketch_pmh3a(SketchArgs a) {
                                     // alternates with every pass: it is cleared one pass after it was read)
                                     if (__any(any_deferred) && lane_id() == 0) misc[M_FLAGS + flag_sel] = 1u;
                                     lds_barrier();
-                                    phase(6); // B1
                                     const bool run_b2 = uniform_u32(misc[M_FLAGS + flag_sel]) != 0u;
                                     flag_sel ^= 1u;
                                     if (tid == 0) misc[M_FLAGS + flag_sel] = 0u;
-                                    if (run_b2 && !ABL(8u)) {
+                                    if (run_b2) {
                                         uint64_t qb = wave_qmax(hmin, a.m);
                                         for (uint32_t base = 0; base < n_keys; base += nthreads) {
                                             const uint32_t i = base + tid;
@@ -830,7 +808,6 @@ __global__ void __launch_bounds__(1024) k_sketch_pmh3a(SketchArgs a) {
                                     if ((uint32_t) tid < pf_nw) raw_pf = reinterpret_cast<const u32x4 *>(words)[tid];
                                 }
                                 lds_barrier(); // the points are final (-> signature row); bst is clean for the next pass
-                                phase(7); // B2 + clear
                             }
                         }
                         if (!overflow) part_done = true;
@@ -865,10 +842,7 @@ __global__ void __launch_bounds__(1024) k_sketch_pmh3a(SketchArgs a) {
                 }
                 bk_n = 0;
             } else if (EMIT) {
-                if (tid == 0) { // the row is written by k_pmh_points (PLAIN, overflow: an empty list; the redo launch writes the row)
-                    a.lst_n[seq_of(r)] = (PLAIN && redo) ? 0u : emit_n;
-                    if (PLAIN && redo) a.redo_list[atomicAdd(a.queue + 56, 1u)] = r;
-                }
+                if (tid == 0) a.lst_n[seq_of(r)] = emit_n; // the row is written by k_pmh_points
                 emit_n = 0;
             } else {
                 // ---- signature of this block: arg-min key per slot, initobj (0) for an empty multiset -----------
@@ -906,11 +880,7 @@ __global__ void __launch_bounds__(1024) k_sketch_pmh3a(SketchArgs a) {
             lds_barrier();
         }
         r = r_follow;
-        phase(8); // row out
     }
-    if (ph_on)
-        for (int i = 0; i < 10; i++)
-            atomicAdd(reinterpret_cast<unsigned long long *>(a.queue) + 8 + i, (unsigned long long) ph_acc[i]);
 }
 
 // the cheap half of pmh3a_first_point: can the first point of this key lie below q_max (bits `qb`)?  Needs two of the four
@@ -1041,11 +1011,8 @@ __device__ __forceinline__ void pts_one_read(const SketchArgs &a, uint32_t r, ui
             if (lane == 0) *qmax_sh = qb;
         }
         uint64_t s0 = 0, s3 = 0;
-        // (diagnostic builds, KMU_PMH_ABLATE: 16384 = no key passes and the test is not computed -- the list walk alone; 8192 = the
-        //  keys that pass are queued but not worked off -- walk + cheap test; wrong rows, the parts' share of the instructions)
-        const bool pass = ABL(16384u) ? false
-                          : c + 64u <= n_u ? have && pmh3a_first_point_may_matter<true>(a, sig32, qb, key, w, winv_lut, s0, s3) // (uniform)
-                                           : have && pmh3a_first_point_may_matter(a, sig32, qb, key, w, winv_lut, s0, s3);
+        const bool pass = c + 64u <= n_u ? have && pmh3a_first_point_may_matter<true>(a, sig32, qb, key, w, winv_lut, s0, s3) // (uniform)
+                                         : have && pmh3a_first_point_may_matter(a, sig32, qb, key, w, winv_lut, s0, s3);
         const uint64_t pm = __ballot(pass);
         if (pass) {
             const uint32_t pos = qn + (uint32_t) __popcll(pm & ((1ull << lane) - 1ull));
@@ -1057,14 +1024,12 @@ __device__ __forceinline__ void pts_one_read(const SketchArgs &a, uint32_t r, ui
         qn += (uint32_t) __popcll(pm);
         if (qn >= 64u) { // the newest 64
             qn -= 64u;
-            if (!ABL(8192u))
             pmh3a_first_point_rest(a, sig32, hmin, sig, qmax_sh, true, qk[qn + lane], qw[qn + lane], qs0[qn + lane], qs3[qn + lane],
                                    winv_lut);
         }
     }
     if (qn) {
         const bool have = (uint32_t) lane < qn;
-        if (!ABL(8192u))
         pmh3a_first_point_rest(a, sig32, hmin, sig, qmax_sh, have, have ? qk[lane] : 0ull, have ? qw[lane] : 1u, have ? qs0[lane] : 0ull,
                                have ? qs3[lane] : 0ull, winv_lut);
     }
@@ -1076,7 +1041,7 @@ __device__ __forceinline__ void pts_one_read(const SketchArgs &a, uint32_t r, ui
         qb = wg4_qmax(arrays, wave_words, a.m);
     } else qb = wave_qmax(hmin, a.m);
     wmax = (uint32_t) wave_max_u64((uint64_t) wmax);
-    if (n && wmax && winv_of(winv_lut, wmax) < __longlong_as_double((long long) qb) && !ABL(512u)) { // (ABL: diagnostic builds, pass 2 left out: wrong rows, its share of the time)
+    if (n && wmax && winv_of(winv_lut, wmax) < __longlong_as_double((long long) qb)) {
         // (a key of weight 1 draws again only while q_max > 1: with every slot hit q_max < 1 -- Exp01 is restricted to
         //  [0, 1) -- and the weight-1 prefix of the list is not read a second time)
         const uint32_t c0 = 1.0 < __longlong_as_double((long long) qb) ? 0u : (n_u & ~63u);
@@ -1248,12 +1213,6 @@ __global__ void __launch_bounds__(UQ_THREADS, MINW) k_multiset_uq(SketchArgs a) 
         nv_mine = fits(nv);
     }
     __syncthreads(); // (misc[5] is rewritten at the top of the first turn)
-    // diagnostic builds (KMU_PMH_ABLATE=256): thread-0 clocks per phase -> a.queue words 8..17 (u64)
-    const bool ph_on = KMU_DIAG && ABL(256u) && tid == 0;
-    uint64_t ph_acc[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, ph_t = ph_on ? __builtin_readcyclecounter() : 0;
-    auto phase = [&](int i) {
-        if (ph_on) { const uint64_t n = __builtin_readcyclecounter(); ph_acc[i] += n - ph_t; ph_t = n; }
-    };
     uint32_t pf_bad = 0; // non-ACGT bytes among this thread's words of the current read, fetched a read ahead
     bool pf_valid = false;                    // uniform
     auto n_words = [&](const SeqView &v) -> uint32_t { // staged words of a read of 1 .. UQ_KEYS k-mers (its k-mers' windows + 1)
@@ -1290,9 +1249,7 @@ __global__ void __launch_bounds__(UQ_THREADS, MINW) k_multiset_uq(SketchArgs a) 
                 zb[tid + z * UQ_THREADS] = make_uint4(0u, 0u, 0u, 0u);
             }
         }
-        phase(0); // queue, staging, wipe
         lds_barrier();
-        phase(1);
         const uint32_t r_nn = uniform_u32(misc[5]);
         const bool has_nn = r_nn < a.n_queue;
         // the header of the read after next: requested now, looked at at the end of this turn
@@ -1364,9 +1321,7 @@ __global__ void __launch_bounds__(UQ_THREADS, MINW) k_multiset_uq(SketchArgs a) 
             };
             if (cfg.fhash == KMU_FHASH_CANON_INVHASH && cfg.kmer_type == KMU_KMER64BIT) key_phase(std::true_type{});
             else key_phase(std::false_type{});
-            phase(2); // keys, closure, bitmaps
             lds_barrier();
-            phase(3);
         }
         // ---- the next read's chunks have landed: its code words replace this read's (every key of this read is in a register by
         // now -- the barrier behind the key phase -- and nothing below looks at `words`).  Round 5: they used to wait in three registers
@@ -1386,7 +1341,6 @@ __global__ void __launch_bounds__(UQ_THREADS, MINW) k_multiset_uq(SketchArgs a) 
             }
         }
         const uint64_t lb = sv.begin - off_first; // list entries of read r start here
-        phase(4); // the next read's header and words requested
         if (mine) {
             // ---- sort out: B bit clear = occurs once = list entry (key, 1) from the register; else collect ----
             // (r03: all twenty B bits read at once and ONE atomic pair per wave instead of five -- 15.9 against 13.0 ms per launch:
@@ -1433,9 +1387,7 @@ __global__ void __launch_bounds__(UQ_THREADS, MINW) k_multiset_uq(SketchArgs a) 
                     cb += (uint32_t) __popcll(cm[u]);
                 }
             }
-            phase(5); // sort out: unique keys to the lists, the others collected
             lds_barrier();
-            phase(6);
             const uint32_t n_u = uniform_u32(misc[0]), n_c = uniform_u32(misc[1]);
             over = n_c > UQ_COLL;
             if (!over && n_c) {
@@ -1496,7 +1448,6 @@ __global__ void __launch_bounds__(UQ_THREADS, MINW) k_multiset_uq(SketchArgs a) 
             }
             if (tid == 0 && !over) { a.lst_n[rs] = n_u + n_c; a.lst_nu[rs] = n_u; }
         }
-        phase(7); // collision groups
         if (tid == 0) {
             if (nk == 0) a.lst_n[rs] = 0u; // no k-mer: k_pmh_points writes the row of an empty multiset
             else if (!mine || over) {       // the next kernel's: longer than the registers, or too repetitive
@@ -1518,11 +1469,7 @@ __global__ void __launch_bounds__(UQ_THREADS, MINW) k_multiset_uq(SketchArgs a) 
             nv_mine = fits(nv);
         }
         lds_barrier();
-        phase(8); // end of the read's turn
     }
-    if (ph_on)
-        for (int i = 0; i < 10; i++)
-            atomicAdd(reinterpret_cast<unsigned long long *>(a.queue) + 8 + i, (unsigned long long) ph_acc[i]);
 }
 
 // ---- reads of at most 256 k-mers (short-read sequencers): the multiset by ONE WAVE per read ---------------------------------
@@ -1892,7 +1839,7 @@ __global__ void __launch_bounds__(1024) k_sketch_smallk(SketchArgs a) {
                 // four positions per thread and step: the window reads, then the four counter atomics, are requested
                 // together, and the first touches of all four are appended with ONE atomic per wave (the loop is bound by
                 // dependent LDS round trips, not by instructions)
-                for (uint32_t p0 = tp0; p0 < tp1 && !ABL(1u); p0 += 4u * nthreads) { // uniform trip count (ballots)
+                for (uint32_t p0 = tp0; p0 < tp1; p0 += 4u * nthreads) { // uniform trip count (ballots)
                     uint32_t idx[4], old[4];
                     bool act[4], first[4];
 #pragma unroll
@@ -1959,7 +1906,7 @@ __global__ void __launch_bounds__(1024) k_sketch_smallk(SketchArgs a) {
                 // read's turn orders that before the next read's appends.  Three barriers less per read than the general form.
                 const uint32_t n_list = uniform_u32(misc[0]);
                 const uint64_t lbase = off_r - off_first;
-                for (uint32_t i = tid; i < n_list && !ABL(2u); i += nthreads) {
+                for (uint32_t i = tid; i < n_list; i += nthreads) {
                     const uint32_t idx = list[i];
                     const uint32_t c = cnt[idx >> 1];
                     a.lst_keys[lbase + i] = key_of(idx);
@@ -2001,7 +1948,7 @@ __global__ void __launch_bounds__(1024) k_sketch_smallk(SketchArgs a) {
                     uint32_t chunk = 0;
                     if (EMIT) {
                         const uint64_t lbase = off_r - off_first + emit_n;
-                        for (uint32_t i = tid; i < n_list && !ABL(2u); i += nthreads) {
+                        for (uint32_t i = tid; i < n_list; i += nthreads) {
                             const uint32_t idx = list[i];
                             const uint32_t c = wide ? cnt[idx & 0x7FFFu] : cnt[idx >> 1];
                             a.lst_keys[lbase + i] = key_of(idx);

@@ -1,7 +1,7 @@
 #!/bin/bash
 # diagnostics: build a library variant kmerutils_amd/libkmu_<tag>.so (select it with KMU_LIB=...): the named sources are
 # recompiled with extra flags, the other objects come from the product build (kmerutils_amd/build/).
-# usage: scripts/build_variant.sh <tag> "<extra hipcc flags>" <source> [<source> ...]      e.g.  d "-DKMU_DIAG=1" kmu_count
+# usage: scripts/build_variant.sh <tag> "<extra hipcc flags>" <source> [<source> ...]      e.g.  o2 "-O2" kmu_count
 set -e
 cd "$(dirname "$0")/.."
 tag=$1; flags=$2; shift 2
