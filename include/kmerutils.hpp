@@ -1010,6 +1010,71 @@ std::pair<double, std::optional<std::vector<D>>> probminhash_get_jaccard_objects
     return {double(inter) / double(siga.size()), std::move(common)};
 }
 
+/// One entry of a neighbour list (the shape of hnsw_rs's `Neighbour`): row of the database, distance = (m - eq) / m
+struct Neighbour {
+    uint32_t idx;
+    float distance;
+};
+
+/// kmu_sig_knn on row-major host signatures (`m` words per row): idx / eq lists of `k` entries per query row, ordered by
+/// eq descending then row ascending; rows with group_q[i] == group_db[j] are never paired (null, null: no groups)
+template <class D>
+void sig_knn(const D *sig_q, size_t nq, const D *sig_db, size_t ndb, size_t m, size_t k, const uint32_t *group_q,
+             const uint32_t *group_db, std::vector<uint32_t> &idx, std::vector<uint16_t> &eq, Context &ctx = Context::global()) {
+    idx.assign(std::max<size_t>(nq * k, 1), KMU_KNN_NONE);
+    eq.assign(std::max<size_t>(nq * k, 1), 0);
+    const D none{};
+    ctx.check(kmu_sig_knn(ctx.raw(), nq ? sig_q : &none, uint32_t(nq), ndb ? sig_db : &none, uint32_t(ndb), uint32_t(m),
+                          detail::sig_type_of<D>(), uint32_t(k), group_q, group_db, KMU_MEM_HOST, idx.data(), eq.data()));
+    idx.resize(nq * k);
+    eq.resize(nq * k);
+}
+
+/// The exact answer to the query an HNSW index under DistHamming / DistBlockSketched approximates
+/// (datasketcher.rs:137-192): per query row the k nearest database rows, nearest first; lists are shorter than k
+/// when fewer candidates exist.
+template <class D>
+std::vector<std::vector<Neighbour>> nearest_neighbours(const std::vector<std::vector<D>> &sig_q,
+                                                       const std::vector<std::vector<D>> &sig_db, size_t k,
+                                                       const std::vector<uint32_t> *group_q = nullptr,
+                                                       const std::vector<uint32_t> *group_db = nullptr,
+                                                       Context &ctx = Context::global()) {
+    const size_t m = sig_q.empty() ? (sig_db.empty() ? 1 : sig_db[0].size()) : sig_q[0].size();
+    std::vector<D> fq, fdb;
+    for (const auto &r : sig_q) {
+        if (r.size() != m) throw std::invalid_argument("signatures of different lengths");
+        fq.insert(fq.end(), r.begin(), r.end());
+    }
+    for (const auto &r : sig_db) {
+        if (r.size() != m) throw std::invalid_argument("signatures of different lengths");
+        fdb.insert(fdb.end(), r.begin(), r.end());
+    }
+    std::vector<uint32_t> idx;
+    std::vector<uint16_t> eq;
+    sig_knn(fq.data(), sig_q.size(), fdb.data(), sig_db.size(), m, k, group_q ? group_q->data() : nullptr,
+            group_db ? group_db->data() : nullptr, idx, eq, ctx);
+    std::vector<std::vector<Neighbour>> out(sig_q.size());
+    for (size_t i = 0; i < sig_q.size(); i++)
+        for (size_t l = 0; l < k && idx[i * k + l] != KMU_KNN_NONE; l++)
+            out[i].push_back(Neighbour{idx[i * k + l], float(m - eq[i * k + l]) / float(m)});
+    return out;
+}
+
+/// The neighbour file `datasketcher ... ann` writes beside a signature dump (this project's format, not hnsw_rs's graph
+/// dump): magic u32, n_rows u64, k u32, sketch_size u32, n_rows x k u32 indices, n_rows x k u16 equal-slot counts
+inline void write_neighbour_file(const std::string &fname, const std::vector<uint32_t> &idx, const std::vector<uint16_t> &eq,
+                                 uint64_t n_rows, uint32_t k, uint32_t sketch_size) {
+    std::ofstream out(fname, std::ios::binary);
+    if (!out) throw std::runtime_error("write_neighbour_file: cannot open " + fname);
+    const uint32_t magic = 0xceab0a22u;
+    out.write(reinterpret_cast<const char *>(&magic), 4);
+    out.write(reinterpret_cast<const char *>(&n_rows), 8);
+    out.write(reinterpret_cast<const char *>(&k), 4);
+    out.write(reinterpret_cast<const char *>(&sketch_size), 4);
+    out.write(reinterpret_cast<const char *>(idx.data()), std::streamsize(n_rows * k * 4));
+    out.write(reinterpret_cast<const char *>(eq.data()), std::streamsize(n_rows * k * 2));
+}
+
 /// jaccard_index_probminhash3a(seqa, vseqb, sketch_size, kmer_size, fhash) -> Vec<f64> (seqsketchjaccard.rs:423-495):
 /// P-Jaccard estimate of seqa against every sequence of vseqb
 template <class Kmer, class F>

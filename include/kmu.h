@@ -548,6 +548,23 @@ int kmu_sig_equal_pairs(kmu_ctx *ctx, const void *sig_a, uint32_t na, const void
 /* all pairs: out[i * nb + j] (m <= 65535) */
 int kmu_sig_equal_matrix(kmu_ctx *ctx, const void *sig_a, uint32_t na, const void *sig_b, uint32_t nb, uint32_t m,
                          int sig_type, int mem, uint16_t *out);
+/* Exact k nearest neighbours: what `datasketcher ... ann --nb N` asks of an HNSW index under DistHamming /
+ * DistBlockSketched (src/bin/datasketcher.rs:98-109, 137-192, 261-309), by brute force with the selection fused
+ * behind the compare (no nq x ndb intermediate: nq x ndb may be far beyond memory).
+ *   eq(i, j) = number of slots t < m with Q[i][t] == DB[j][t] (raw words, as above); distance = (m - eq) / m.
+ *   Candidates of query i: every j < ndb, except -- when groups are given -- those with group_q[i] == group_db[j]
+ *   (DistBlockSketched's rule, seqblocksketch.rs:419-440: blocks of one sequence are never paired; a self-join of
+ *   whole-read signatures passes group = 0, 1, 2, ... on both sides so that a row is not its own neighbour).
+ *   idx_out[i * k ..], eq_out[i * k ..]: the min(k, #candidates) best candidates by eq DESCENDING, then j ASCENDING
+ *   (the same rule decides who enters at the k-th place); the remaining entries are idx = KMU_KNN_NONE, eq = 0.
+ *   Candidates with eq == 0 are candidates like any other.  The result is a pure function of the inputs.
+ * KMU_E_BAD_ARG: null pointer, m == 0, k == 0, bad sig_type, one group array without the other.
+ * KMU_E_UNSUPPORTED: m > 65535, k > KMU_KNN_MAX_K, ndb == 0xFFFFFFFF.  nq == 0: KMU_OK; ndb == 0: lists of "none". */
+#define KMU_KNN_MAX_K 64
+#define KMU_KNN_NONE 0xFFFFFFFFu /* idx of a list entry that does not exist */
+int kmu_sig_knn(kmu_ctx *ctx, const void *sig_q, uint32_t nq, const void *sig_db, uint32_t ndb, uint32_t m, int sig_type,
+                uint32_t k, const uint32_t *group_q, const uint32_t *group_db, int mem, uint32_t *idx_out,
+                uint16_t *eq_out);
 /* minhash_distance / mininvhash_distance (src/sketching/minhash.rs:134-190, :295-340) on KMU_ALGO_BOTTOMK rows
  * (ascending hashes, u64::MAX padding).  out[3p..3p+2] = common, total, i: jaccard = common / total,
  * containment = common / i (MinHashDist). */

@@ -21,6 +21,8 @@ SIG_U32, SIG_U64, SIG_F32, SIG_F64, SIG_U16 = 0, 1, 2, 3, 4
 HASHER_NOHASH, HASHER_FNV1A, HASHER_INT64HASH = 0, 1, 2
 MODE_PER_SEQ, MODE_ALL_SEQS = 0, 1
 FLAG_RAND08 = 0x1
+KNN_MAX_K = 64          # kmu_sig_knn: the longest neighbour list
+KNN_NONE = 0xFFFFFFFF   # idx of a list entry that does not exist
 
 
 def kmer_val_bytes(kmer_type):

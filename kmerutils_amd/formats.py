@@ -9,6 +9,9 @@ what the Julia companion reads); where upstream's own reader disagrees with its 
   k-mer counts      KmerCounterPool::dump_kmer_counter (COUNTER_MULTIPLE) src/base/kmercount.rs:35-41, 467-531
                     Kmer*::dump                                           src/base/kmer64bit.rs:98-104, kmer32bit.rs:141-144
 
+  neighbour file    write_neighbour_file / read_neighbour_file: this project's own format (below), what `datasketcher ... ann`
+                    writes to `<dumpfile>-ann` in place of the reference's HNSW graph dump (datasketcher.rs:326-343)
+
 All integers little-endian (`to_le_bytes`, or `transmute` on the little-endian hosts the reference runs on).
 """
 import json
@@ -75,6 +78,40 @@ class SigSketchFileReader:
     def read_all(self):
         rows = np.frombuffer(self.f.read(), "<u4")
         return rows[:rows.size - rows.size % self.sketch_size].reshape(-1, self.sketch_size).copy()
+
+
+# ---- neighbour lists (kmu_sig_knn) ------------------------------------------------------------------------------------
+MAGIC_NEIGHBOURS = 0xCEAB0A22     # this project's: an HNSW graph is not reproducible and nothing here reads one
+KNN_NONE = 0xFFFFFFFF
+
+
+def write_neighbour_file(fname, idx, eq, sketch_size):
+    """magic u32, n_rows u64, k u32, sketch_size u32, then n_rows x k u32 row indices and n_rows x k u16 equal-slot
+    counts (distance = (sketch_size - eq) / sketch_size).  Row numbers are those of the signature dump written beside
+    the file; an entry that does not exist is idx = 0xFFFFFFFF, eq = 0."""
+    idx = np.ascontiguousarray(idx).astype("<u4", copy=False)
+    eq = np.ascontiguousarray(eq).astype("<u2", copy=False)
+    if idx.ndim != 2 or idx.shape != eq.shape:
+        raise ValueError("idx and eq must be [n_rows, k] arrays of one shape")
+    with open(fname, "wb") as f:
+        f.write(struct.pack("<IQII", MAGIC_NEIGHBOURS, idx.shape[0], idx.shape[1], sketch_size))
+        f.write(idx.tobytes())
+        f.write(eq.tobytes())
+
+
+def read_neighbour_file(fname):
+    """(idx uint32 [n_rows, k], eq uint16 [n_rows, k], sketch_size) of a file of write_neighbour_file"""
+    with open(fname, "rb") as f:
+        head = f.read(20)
+        if len(head) < 20 or struct.unpack("<I", head[:4])[0] != MAGIC_NEIGHBOURS:
+            raise IOError("file is not a neighbour file")
+        n, k, sketch_size = struct.unpack("<QII", head[4:])
+        body = f.read()
+    if len(body) != n * k * 6:
+        raise IOError("neighbour file is truncated: %d bytes of lists, %d expected" % (len(body), n * k * 6))
+    idx = np.frombuffer(body, "<u4", n * k).reshape(n, k).copy()
+    eq = np.frombuffer(body, "<u2", n * k, offset=n * k * 4).reshape(n, k).copy()
+    return idx, eq, sketch_size
 
 
 # ---- block signatures ------------------------------------------------------------------------------------------------

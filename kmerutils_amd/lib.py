@@ -23,7 +23,7 @@ SYMBOLS = [
     "kmu_kmer_hashes", "kmu_sketch", "kmu_block_layout", "kmu_sketch_hashed", "kmu_count_create", "kmu_count_destroy",
     "kmu_count_reset", "kmu_count_add_reads", "kmu_count_add_kmers", "kmu_count_query", "kmu_count_nb_distinct",
     "kmu_count_nb_unique", "kmu_count_dump", "kmu_count_export_part", "kmu_count_merge_entries",
-    "kmu_count_retain_part", "kmu_count_extract_by_owner", "kmu_sig_equal_pairs", "kmu_sig_equal_matrix",
+    "kmu_count_retain_part", "kmu_count_extract_by_owner", "kmu_sig_equal_pairs", "kmu_sig_equal_matrix", "kmu_sig_knn",
     "kmu_minhash_distance_pairs", "kmu_ingest_fastq", "kmu_ingest_fasta", "kmu_ingest_fastx", "kmu_dev_alloc", "kmu_dev_free",
     "kmu_copy_to_device", "kmu_copy_to_host", "kmu_count_once_positions", "kmu_count_eliminate_once", "kmu_sketch_partial_words",
     "kmu_sketch_partial", "kmu_sketch_hashed_partial", "kmu_sketch_merge_partials", "kmu_kmer_hashes_compact", "kmu_set_hll_params",
@@ -109,6 +109,7 @@ def load():
     L.kmu_count_extract_by_owner.argtypes = [vp, vp, vp, C.c_uint32, C.c_int, C.c_uint32, C.POINTER(vp), vp]
     L.kmu_sig_equal_pairs.argtypes = [vp, vp, C.c_uint32, vp, C.c_uint32, C.c_uint32, C.c_int, vp, vp, C.c_uint64, C.c_int, vp]
     L.kmu_sig_equal_matrix.argtypes = [vp, vp, C.c_uint32, vp, C.c_uint32, C.c_uint32, C.c_int, C.c_int, vp]
+    L.kmu_sig_knn.argtypes = [vp, vp, C.c_uint32, vp, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, vp, vp, C.c_int, vp, vp]
     L.kmu_minhash_distance_pairs.argtypes = [vp, vp, C.c_uint32, vp, C.c_uint32, C.c_uint32, vp, vp, C.c_uint64, C.c_int, vp]
     L.kmu_set_hll_params.argtypes = [vp, C.POINTER(A.HllParams)]
     L.kmu_kmer_hashes_compact.argtypes = [vp, C.POINTER(A.HashParams), vp, vp, vp, C.c_uint32, vp, C.c_uint64, u64p]
@@ -649,6 +650,25 @@ class Context:
         self._check(self.L.kmu_sig_equal_matrix(self.h, _ptr(sig_a)[0], sig_a.shape[0], _ptr(sig_b)[0], sig_b.shape[0],
                                                 sig_a.shape[1], self._sig_type_of(sig_a), mem, _ptr(out)[0]))
         return out[:sig_a.shape[0], :sig_b.shape[0]]
+
+    def sig_knn(self, sig_q, sig_db, k, group_q=None, group_db=None):
+        """kmu_sig_knn: for every row of sig_q the k rows of sig_db with the most equal slots (ties: lower row first),
+        rows of the query's own group left out.  Returns (idx uint32 [nq, k], eq uint16 [nq, k]); entries that do not
+        exist are idx = KNN_NONE, eq = 0.  Device tensors in give device tensors out (int32 / int16 holding the same
+        bits, like the other comparison calls)."""
+        mem = self._mem(sig_q, sig_db, group_q, group_db)
+        self._wait_producers(sig_q, sig_db)
+        nq, ndb, k = int(sig_q.shape[0]), int(sig_db.shape[0]), int(k)
+        if self._sig_type_of(sig_q) != self._sig_type_of(sig_db) or sig_q.shape[1] != sig_db.shape[1]:
+            raise ValueError("query and database signatures differ in type or sketch size")
+        idx = self._new_like(sig_q, (max(nq, 1), max(k, 1)), np.uint32, "int32")
+        eq = self._new_like(sig_q, (max(nq, 1), max(k, 1)), np.uint16, "int16")
+        # an empty array has no address worth passing: the library reads no row of it
+        pq = _ptr(sig_q)[0] if nq else _ptr(idx)[0]
+        pdb = _ptr(sig_db)[0] if ndb else _ptr(idx)[0]
+        self._check(self.L.kmu_sig_knn(self.h, pq, nq, pdb, ndb, sig_q.shape[1], self._sig_type_of(sig_q), k,
+                                       _ptr(group_q)[0], _ptr(group_db)[0], mem, _ptr(idx)[0], _ptr(eq)[0]))
+        return idx[:nq, :k], eq[:nq, :k]
 
     def minhash_distance_pairs(self, hashes_a, hashes_b, ia, ib):
         """kmu_minhash_distance_pairs on bottom-k rows: (common, total, i) per pair."""

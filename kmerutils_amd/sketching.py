@@ -299,6 +299,26 @@ def jaccard_matrix(sig_a, sig_b=None, ctx=None):
     return (eq.astype(np.float64) if isinstance(eq, np.ndarray) else eq.double()) / m
 
 
+def nearest_neighbours(sig_q, sig_db, k, group_q=None, group_db=None, ctx=None):
+    """Exact k nearest rows of sig_db for every row of sig_q under the reference's DistHamming (datasketcher.rs:156-185):
+    kmu_sig_knn.  Returns (idx uint32 [nq, k], distance float32 = (m - eq) / m), ordered by distance, then row; entries
+    that do not exist are idx = KNN_NONE, distance = 1.0.  Rows with group_q[i] == group_db[j] are never paired."""
+    ctx = ctx or default_context()
+    idx, eq = ctx.sig_knn(sig_q, sig_db, k, group_q, group_db)
+    m = sig_q.shape[1]
+    if isinstance(eq, np.ndarray):
+        return idx, (np.float32(m) - eq.astype(np.float32)) / np.float32(m)
+    return idx, (m - (eq.int() & 0xFFFF).float()) / m
+
+
+def block_nearest_neighbours(rows, numseq, k, ctx=None):
+    """The neighbour query of DistBlockSketched (seqblocksketch.rs:419-440) over block signatures: blocks of one
+    sequence are at distance 1.0 "as we want to pair reads", so they never appear in each other's lists."""
+    g = np.ascontiguousarray(numseq, np.uint32)
+    rows = np.ascontiguousarray(rows)
+    return nearest_neighbours(rows, rows, k, g, g, ctx=ctx)
+
+
 class DistBlockSketched:
     """Distance<BlockSketched>, src/sketching/seqblocksketch.rs:419-431: 1.0 inside one sequence, else the fraction of
     differing slots.  `eval_pairs` takes block rows + their numseq (BlockSeqSketcher.blocksketch_sequences) and index
