@@ -399,6 +399,8 @@ int kmu_profile_reset(kmu_ctx *ctx) {
     if (!ctx) return KMU_E_BAD_ARG;
     profile_collect(ctx);
     ctx->stats.clear();
+    auto tr = ctx->bufs.find("pmh.tau_redo");
+    if (tr != ctx->bufs.end() && tr->second.p) KMU_HIP(ctx, hipMemsetAsync(tr->second.p, 0, 4, ctx->stream));
     return KMU_OK;
 }
 int kmu_profile_get(kmu_ctx *ctx, kmu_kernel_stat *stats, int cap) {
@@ -413,6 +415,21 @@ int kmu_profile_get(kmu_ctx *ctx, kmu_kernel_stat *stats, int cap) {
             stats[n].total_ms = kv.second.ms;
         }
         n++;
+    }
+    // not a kernel: `launches` = the reads k_pmh_points did again because its a-priori q_max bound failed (since the last reset)
+    auto tr = ctx->bufs.find("pmh.tau_redo");
+    if (tr != ctx->bufs.end() && tr->second.p) {
+        uint32_t redone = 0;
+        KMU_HIP(ctx, hipMemcpyAsync(&redone, tr->second.p, 4, hipMemcpyDeviceToHost, ctx->stream));
+        KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        if (redone) {
+            if (stats && n < cap) {
+                memset(&stats[n], 0, sizeof(kmu_kernel_stat));
+                strncpy(stats[n].name, "pmh_tau_redone_reads", sizeof(stats[n].name) - 1);
+                stats[n].launches = redone;
+            }
+            n++;
+        }
     }
     return n;
 }

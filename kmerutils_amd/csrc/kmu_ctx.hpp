@@ -48,6 +48,9 @@ struct kmu_ctx {
         double ms = 0;
     };
     std::map<std::string, Stat> stats;
+    // k_pmh_points' a-priori q_max bound: c of KMU_PMH_TAU_C, read at the first launch (0: no bound)
+    bool pmh_tau_read = false;
+    double pmh_tau_c = 0.0;
     int num_cus = 256;
     size_t lds_per_block = 65536;
     // kmu_sketch_count on host buffers: uploads and downloads run on streams of their own, next to the kernels

@@ -219,6 +219,20 @@ static int launch_points(kmu_ctx *ctx, SketchArgs a, int cus, uint32_t thr) {
         hipLaunchKernelGGL(k_pts_long_list, dim3((a.n_seq + 255) / 256), dim3(256), 0, ctx->stream, (const uint32_t *) a.lst_n, a.n_seq, thr,
                            (uint32_t *) pl);
     }
+    // the a-priori q_max bound of pts_one_read.  KMU_PMH_TAU_C (read once per context): unset = PTS_TAU_C; 0 / off = no bound;
+    // a negative c makes nearly every read fail the bound and start over (tests of that path)
+    if (!ctx->pmh_tau_read) {
+        const char *e = getenv("KMU_PMH_TAU_C");
+        ctx->pmh_tau_c = !e ? PTS_TAU_C : (!strcmp(e, "off") ? 0.0 : atof(e));
+        ctx->pmh_tau_read = true;
+    }
+    const bool fresh = !ctx->bufs.count("pmh.tau_redo");
+    void *tr;
+    KMU_TRY(dev_buf(ctx, "pmh.tau_redo", 4, &tr));
+    if (fresh) KMU_HIP(ctx, hipMemsetAsync(tr, 0, 4, ctx->stream)); // (counts until kmu_profile_reset)
+    a.tau_redo = (uint32_t *) tr;
+    a.tau_num = (double) a.m * (std::log((double) a.m) + ctx->pmh_tau_c);
+    a.tau_min_n = ctx->pmh_tau_c != 0.0 && a.tau_num > 0.0 ? (uint32_t) std::min(a.tau_num, 4.0e9) : 0xFFFFFFFFu;
     KernelTimer t(ctx, "k_pmh_points");
     hipLaunchKernelGGL(kpts, dim3(grid2), dim3(256), lds2, ctx->stream, a);
     KMU_HIP(ctx, hipGetLastError());
@@ -407,7 +421,7 @@ static int launch_one_pass(kmu_ctx *ctx, const SketchArgs &a, sketch_kernel_t ke
 
 static SketchArgs sketch_args(const kmu_sketch_params *p, const DevSeqs &ds, void *d_sig, uint32_t *d_err, const PmhInputs &in) {
     SketchArgs a;
-    memset(&a, 0, sizeof a); // (bk_keys, bk_cnt and ablate stay null / 0)
+    memset(&a, 0, sizeof a);
     a.skip_longer = in.skip_longer;
     a.hashed = in.hashed;
     a.hashed_bytes = in.hashed_bytes;

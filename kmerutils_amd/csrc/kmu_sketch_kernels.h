@@ -34,8 +34,12 @@ struct SketchArgs {
     // bottom-k (MinHashCount, src/sketching/minhash.rs:62-99)
     int bk_shift;         // bucket = (key >> bk_shift) & 0xFFF: the 12 most significant *used* bits of the hash
     uint32_t bk_mask;     // count wrap mask: 0xFFFF (u16 counts) or 0xFF (MinInvHashCountKmer)
-    uint64_t *bk_keys;    // (unused, always null: see `ablate`)
-    uint32_t *bk_cnt;     // (unused, always null)
+    // k_pmh_points' a-priori bound of a read's final q_max (pts_one_read): tau = tau_num / (k-mer occurrences of the read),
+    // tau_num = m (ln m + c); reads it fails for are done again without it and counted in *tau_redo (KMU_PMH_TAU_C, launch_points).
+    // (The three fields stand where three unused ones stood: the layout of this block steers the register allocation of the hot
+    //  kernels -- without the last of them k_sketch_pmh3a<false, false> spilled 309 SGPRs instead of 292.)
+    uint32_t *tau_redo;
+    double tau_num;
     uint32_t *counts_out; // may be null
     // pre-hashed input (kmu_sketch_hashed, and the leaves of a sketch over all sequences): the "sequence" is an array
     // of Kmer::Val values, offsets count values; runs on the AA instantiation (no code-word staging) with k = 1
@@ -63,10 +67,7 @@ struct SketchArgs {
     uint32_t tile_words;  // staged code words per tile (16 bases each)
     uint32_t idx_thresh;  // rand 0.9 Uniform<usize>(0, m): reject while lo < (2^32 - m) % m
     uint64_t idx_zone;    // rand 0.8 Uniform<usize>(0, m): accept while lo <= zone
-    // (unused, always 0.  It, bk_keys and bk_cnt stay because the layout of this block steers the register allocation of the
-    //  hot kernels: without `ablate` k_sketch_pmh3a<false, false> spills 309 SGPRs instead of 292, k_pmh_points<true> 34 instead
-    //  of 32.  Removing them is a performance change of its own.)
-    uint32_t ablate;
+    uint32_t tau_min_n;   // ... lists with fewer entries get no bound (~ tau_num: the keys tau wants below it); 2^32 - 1: bound off
     Exp01 e01;
     void *sig_out;
     uint32_t *queue; // atomic read counter
@@ -88,6 +89,9 @@ static constexpr int KREG = 10;                      // keys a thread keeps in r
 static constexpr uint32_t WINV_LUT = 256;
 // k_pmh_points, u64 words per wave beside the 2 m slot words: q_max (2), queue of 128 keys, weights (64), state words (256)
 static constexpr size_t PTS_WAVE_WORDS = 2 + 128 + 64 + 256;
+// k_pmh_points: c of the a-priori q_max bound tau = m (ln m + c) / W of a read with W k-mer occurrences: the bound fails (the read
+// starts over) with probability ~ e^-c, ~ m (ln m + c) keys reach the expensive half of a first point.  DESIGN 3.2 has the table.
+static constexpr double PTS_TAU_C = 4.6;
 static constexpr int UQ_KREG = 20;
 // The two shapes' bitmap sizes (log2 bits) and collected-key capacities.  Round 4: bitmaps twice as large (nearly every key of a
 // collision group of an ONT read is a false positive of the bitmap: 9 % of the keys at 2^16 bits, 4.5 % at 2^17), collected-key

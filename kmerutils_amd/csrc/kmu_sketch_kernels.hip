@@ -976,70 +976,97 @@ __device__ __forceinline__ void pts_one_read(const SketchArgs &a, uint32_t r, ui
     const uint64_t base = a.offsets[r] - a.offsets[0];
     const uint32_t n = uniform_u32(a.lst_n[r]);
     const uint32_t n_u = uniform_u32(a.lst_nu[r]); // leading entries of weight 1 without a weight word
-    for (int t = lane; t < a.m; t += 64) { hmin[t] = H_INIT; sig[t] = 0; }
-    if (lane == 0) *qmax_sh = H_INIT;
-    if (WG) __syncthreads(); // (the other waves' arrays are looked at from the first refresh on)
-    // ---- pass 1 ----
-    uint32_t chunk = 0, qn = 0; // qn: queued pairs (uniform)
+    // tau: an a-priori guess of an upper bound of the read's FINAL q_max.  The first point of a key of weight w lies below t with
+    // probability ~ min(1, w t) (Exp01 at lambda = ln(m / (m - 1)) is almost uniform) in a uniformly drawn slot, so with W k-mer
+    // occurrences in the read a slot stays without a point below t with probability ~ exp(-t W / m): tau = m (ln m + c) / W leaves
+    // one of the m slots empty with probability ~ e^-c, and only ~ m (ln m + c) keys lie below it however long the read is -- the
+    // running q_max lets ~ 1180 (1 + ln(n / 1180)) of n keys into the expensive half.  Pass 1 prunes with min(q_max, tau); the guess
+    // is verified below, and a read it fails for is done again without it.  No bound (H_INIT) where tau >= 1, where the list has
+    // fewer entries than the keys tau wants below it, and with the bound switched off (tau_min_n = 2^32 - 1).
+    uint64_t tau_b = H_INIT;
+    if (n >= a.tau_min_n) {
+        const uint64_t len = a.offsets[r + 1] - a.offsets[r];
+        const uint64_t kk = (uint64_t) a.cfg.k;
+        const double tau = a.tau_num / (double) (len >= kk ? len - kk + 1 : 0); // (W from the read's length: non-ACGT is an error anyway)
+        if (tau < 1.0) tau_b = (uint64_t) __double_as_longlong(tau);
+        tau_b = uniform_u64(tau_b);
+    }
     uint32_t wmax = 0;          // largest weight this lane saw
     uint64_t qb = H_INIT;
-    // (Round 5, measured and not kept: the keys of 2 / 4 / 8 chunks in flight instead of one -- 18.40 / 18.42 / 19.60 against 18.38 ms,
-    //  profiles/r05_pts_ahead.txt.  With everything but the list walk switched off the kernel takes 9.3 ms -- 38 GB of lists at
-    //  4.1 TB/s -- but the whole kernel is bound by instruction issue: 1.008e10 vector wave-instructions at the half-rate peak are
-    //  18 ms, the walk's loads are under them already; profiles/r05_pts_parts.txt.)
-    uint64_t key_nx = 0; // the next chunk's pair is requested one iteration ahead
-    uint32_t w_nx = 1;
-    {
-        const uint32_t i = cstart + (uint32_t) lane;
-        if (i < n) { key_nx = a.lst_keys[base + i]; w_nx = i < n_u ? 1u : a.lst_w[base + i]; }
-    }
-    for (uint32_t c = cstart; c < n; c += cstride, chunk++) { // uniform trip count
-        const uint32_t i = c + (uint32_t) lane;
-        const uint64_t key = key_nx;
-        const uint32_t w = w_nx;
-        const bool have = i < n && w != 0u; // weight 0: a repeat of an earlier entry
-        if (have) wmax = w > wmax ? w : wmax;
-        if (i + cstride < n) key_nx = a.lst_keys[base + i + cstride];
-        w_nx = 1u;
-        if (c + cstride + 64u > n_u) { // (uniform: the next chunk reaches beyond the weight-1 prefix)
-            if (i + cstride < n && i + cstride >= n_u) w_nx = a.lst_w[base + i + cstride];
+    for (int turn = 0; turn < 2; turn++) { // the second turn runs without tau: H_INIT bounds every q_max, it cannot fail
+        for (int t = lane; t < a.m; t += 64) { hmin[t] = H_INIT; sig[t] = 0; }
+        if (lane == 0) *qmax_sh = tau_b;
+        if (WG) __syncthreads(); // (the other waves' arrays are looked at from the first refresh on)
+        // ---- pass 1 ----
+        uint32_t chunk = 0, qn = 0; // qn: queued pairs (uniform)
+        qb = tau_b;
+        // (Round 5, measured and not kept: the keys of 2 / 4 / 8 chunks in flight instead of one -- 18.40 / 18.42 / 19.60 against 18.38 ms,
+        //  profiles/r05_pts_ahead.txt.  With everything but the list walk switched off the kernel takes 9.3 ms -- 38 GB of lists at
+        //  4.1 TB/s -- but the whole kernel is bound by instruction issue: 1.008e10 vector wave-instructions at the half-rate peak are
+        //  18 ms, the walk's loads are under them already; profiles/r05_pts_parts.txt.)
+        uint64_t key_nx = 0; // the next chunk's pair is requested one iteration ahead
+        uint32_t w_nx = 1;
+        {
+            const uint32_t i = cstart + (uint32_t) lane;
+            if (i < n) { key_nx = a.lst_keys[base + i]; w_nx = i < n_u ? 1u : a.lst_w[base + i]; }
         }
-        // (WG: the four waves advance through the list together, so the merged q_max is refreshed four times as often per own
-        //  chunk while it still falls fast -- the first 64 own chunks -- and at the single wave's cadence per own chunk after that)
-        if ((chunk & (WG && chunk < 64u ? PTS_REFRESH_MASK >> 2 : PTS_REFRESH_MASK)) == 0u) {
-            qb = WG ? wg4_qmax(arrays, wave_words, a.m) : wave_qmax(hmin, a.m);
-            if (lane == 0) *qmax_sh = qb;
+        for (uint32_t c = cstart; c < n; c += cstride, chunk++) { // uniform trip count
+            const uint32_t i = c + (uint32_t) lane;
+            const uint64_t key = key_nx;
+            const uint32_t w = w_nx;
+            const bool have = i < n && w != 0u; // weight 0: a repeat of an earlier entry
+            if (have) wmax = w > wmax ? w : wmax;
+            if (i + cstride < n) key_nx = a.lst_keys[base + i + cstride];
+            w_nx = 1u;
+            if (c + cstride + 64u > n_u) { // (uniform: the next chunk reaches beyond the weight-1 prefix)
+                if (i + cstride < n && i + cstride >= n_u) w_nx = a.lst_w[base + i + cstride];
+            }
+            // (WG: the four waves advance through the list together, so the merged q_max is refreshed four times as often per own
+            //  chunk while it still falls fast -- the first 64 own chunks -- and at the single wave's cadence per own chunk after that)
+            if ((chunk & (WG && chunk < 64u ? PTS_REFRESH_MASK >> 2 : PTS_REFRESH_MASK)) == 0u) {
+                qb = WG ? wg4_qmax(arrays, wave_words, a.m) : wave_qmax(hmin, a.m);
+                qb = qb < tau_b ? qb : tau_b;
+                if (lane == 0) *qmax_sh = qb;
+            }
+            uint64_t s0 = 0, s3 = 0;
+            const bool pass = c + 64u <= n_u ? have && pmh3a_first_point_may_matter<true>(a, sig32, qb, key, w, winv_lut, s0, s3) // (uniform)
+                                             : have && pmh3a_first_point_may_matter(a, sig32, qb, key, w, winv_lut, s0, s3);
+            const uint64_t pm = __ballot(pass);
+            if (pass) {
+                const uint32_t pos = qn + (uint32_t) __popcll(pm & ((1ull << lane) - 1ull));
+                qk[pos] = key;
+                qw[pos] = w;
+                qs0[pos] = s0;
+                qs3[pos] = s3;
+            }
+            qn += (uint32_t) __popcll(pm);
+            if (qn >= 64u) { // the newest 64
+                qn -= 64u;
+                pmh3a_first_point_rest(a, sig32, hmin, sig, qmax_sh, true, qk[qn + lane], qw[qn + lane], qs0[qn + lane], qs3[qn + lane],
+                                       winv_lut);
+            }
         }
-        uint64_t s0 = 0, s3 = 0;
-        const bool pass = c + 64u <= n_u ? have && pmh3a_first_point_may_matter<true>(a, sig32, qb, key, w, winv_lut, s0, s3) // (uniform)
-                                         : have && pmh3a_first_point_may_matter(a, sig32, qb, key, w, winv_lut, s0, s3);
-        const uint64_t pm = __ballot(pass);
-        if (pass) {
-            const uint32_t pos = qn + (uint32_t) __popcll(pm & ((1ull << lane) - 1ull));
-            qk[pos] = key;
-            qw[pos] = w;
-            qs0[pos] = s0;
-            qs3[pos] = s3;
+        if (qn) {
+            const bool have = (uint32_t) lane < qn;
+            pmh3a_first_point_rest(a, sig32, hmin, sig, qmax_sh, have, have ? qk[lane] : 0ull, have ? qw[lane] : 1u, have ? qs0[lane] : 0ull,
+                                   have ? qs3[lane] : 0ull, winv_lut);
         }
-        qn += (uint32_t) __popcll(pm);
-        if (qn >= 64u) { // the newest 64
-            qn -= 64u;
-            pmh3a_first_point_rest(a, sig32, hmin, sig, qmax_sh, true, qk[qn + lane], qw[qn + lane], qs0[qn + lane], qs3[qn + lane],
-                                   winv_lut);
-        }
-    }
-    if (qn) {
-        const bool have = (uint32_t) lane < qn;
-        pmh3a_first_point_rest(a, sig32, hmin, sig, qmax_sh, have, have ? qk[lane] : 0ull, have ? qw[lane] : 1u, have ? qs0[lane] : 0ull,
-                               have ? qs3[lane] : 0ull, winv_lut);
+        // ---- the true q_max after all first points; tau held if every slot has a point below it (an empty slot is H_INIT) ----
+        if (WG) {
+            __syncthreads(); // every wave's first points are in
+            qb = wg4_qmax(arrays, wave_words, a.m);
+        } else qb = wave_qmax(hmin, a.m);
+        // (every pruned point lay at or above min(running q_max, tau) >= this q_max: none of them is a slot's minimum.  WG: the
+        //  four waves decide alike -- a wave that goes on to pass 2 only lowers minima, one that starts over waits at the barrier)
+        if (tau_b == H_INIT || qb < tau_b) break;
+        tau_b = H_INIT;
+        if (lane == 0 && (!WG || wave == 0)) atomicAdd(a.tau_redo, 1u);
+        if (WG) __syncthreads(); // (nobody is still looking at the arrays that are wiped now)
     }
     // ---- pass 2 ----
     // (only a key with 1 / w < q_max draws again: with the largest weight of the read at hand the lists are read a
-    //  second time only where that can happen at all)
-    if (WG) {
-        __syncthreads(); // every wave's first points are in
-        qb = wg4_qmax(arrays, wave_words, a.m);
-    } else qb = wave_qmax(hmin, a.m);
+    //  second time only where that can happen at all.  Every key is tested again against the settled q_max and its generator is
+    //  replayed from the seed: nothing here depends on which keys pass 1 worked off)
     wmax = (uint32_t) wave_max_u64((uint64_t) wmax);
     if (n && wmax && winv_of(winv_lut, wmax) < __longlong_as_double((long long) qb)) {
         // (a key of weight 1 draws again only while q_max > 1: with every slot hit q_max < 1 -- Exp01 is restricted to
