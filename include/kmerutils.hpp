@@ -567,6 +567,25 @@ size_t run_sketch_flat(Context &ctx, const Batch &b, int algo, size_t k, size_t 
     return rows;
 }
 
+/// one ALL_SEQS signature per inner list of `groups`, in one library call (kmu_sketch_groups)
+template <class Kmer, class Sig, class Seq>
+std::vector<std::vector<Sig>> run_sketch_groups(Context &ctx, const std::vector<std::vector<const Seq *>> &groups, int algo, size_t k,
+                                                size_t m, int sig_type, int hasher, FHash fhash, uint32_t flags = 0) {
+    std::vector<const Seq *> all;
+    std::vector<uint64_t> group_offsets(1, 0);
+    for (const auto &g : groups) {
+        all.insert(all.end(), g.begin(), g.end());
+        group_offsets.push_back(all.size());
+    }
+    const Batch b = gather(all);
+    kmu_sketch_params p = sketch_params(algo, Kmer::kmu_type, k, m, sig_type, hasher, int(fhash), 0, KMU_MODE_ALL_SEQS, b.input_kind);
+    p.flags = flags;
+    std::vector<Sig> flat(std::max<size_t>(groups.size(), 1) * m);
+    ctx.check(kmu_sketch_groups(ctx.raw(), &p, b.bytes.data(), b.offsets.data(), b.packed_ptr(), b.n(), group_offsets.data(),
+                                uint32_t(groups.size()), flat.data()));
+    return split_rows(flat, groups.size(), m);
+}
+
 template <class Kmer, class Sig, class F>
 std::vector<std::vector<Sig>> run_sketch(Context &ctx, const Batch &b, int algo, size_t k, size_t m, int hasher, F fhash,
                                          int mode, uint32_t flags = 0) {
@@ -713,6 +732,10 @@ template <class Kmer, class SigT> class SeqSketcherT {
     /// ONE signature for the whole list (outer length 1)
     virtual std::vector<std::vector<Sig>> sketch_compressedkmer_seqs(const std::vector<const Seq *> &vseq,
                                                                      FHash fhash) const = 0;
+    /// sketch_compressedkmer_seqs of every inner list (a genome's contigs, a proteome's proteins): row g <-> groups[g], one
+    /// library call for all of them (what gsearch runs file by file)
+    virtual std::vector<std::vector<Sig>> sketch_compressedkmer_seqs_groups(const std::vector<std::vector<const Seq *>> &groups,
+                                                                            FHash fhash) const = 0;
     // the AA trait's names for the same two calls
     std::vector<std::vector<Sig>> sketch_compressedkmeraa(const std::vector<const Seq *> &vseq, FHash fhash) const {
         return sketch_compressedkmer(vseq, fhash);
@@ -738,6 +761,11 @@ template <class Kmer, class Sig, int ALGO> class SketcherImpl : public SeqSketch
     std::vector<std::vector<Sig>> sketch_compressedkmer_seqs(const std::vector<const Seq *> &vseq,
                                                              FHash fhash) const override {
         return run(vseq, fhash, KMU_MODE_ALL_SEQS);
+    }
+    std::vector<std::vector<Sig>> sketch_compressedkmer_seqs_groups(const std::vector<std::vector<const Seq *>> &groups,
+                                                                    FHash fhash) const override {
+        return run_sketch_groups<Kmer, Sig>(ctx_, groups, ALGO, params_.get_kmer_size(), params_.get_sketch_size(),
+                                            sig_type_of<Sig>(), hasher_, fhash);
     }
     /// arbitrary closure: evaluated on the host, multiset + sketch on the device
     template <class F, class = std::enable_if_t<!std::is_same_v<std::decay_t<F>, FHash>>>
@@ -829,6 +857,13 @@ template <class Kmer, class S> class HyperLogLogSketch : public SeqSketcherT<Kme
     }
     std::vector<std::vector<S>> sketch_compressedkmer_seqs(const std::vector<const Seq *> &vseq, FHash fhash) const override {
         return run(vseq, fhash, KMU_MODE_ALL_SEQS);
+    }
+    std::vector<std::vector<S>> sketch_compressedkmer_seqs_groups(const std::vector<std::vector<const Seq *>> &groups,
+                                                                  FHash fhash) const override {
+        kmu_hll_params hp{hll_.b, hll_.a, hll_.q, 0};
+        ctx_.check(kmu_set_hll_params(ctx_.raw(), &hp));
+        const int sig = std::is_same_v<S, uint16_t> ? KMU_SIG_U16 : std::is_same_v<S, uint32_t> ? KMU_SIG_U32 : KMU_SIG_U64;
+        return detail::run_sketch_groups<Kmer, S>(ctx_, groups, KMU_ALGO_HLL, params_.get_kmer_size(), hll_.m, sig, KMU_HASHER_NOHASH, fhash);
     }
 
   private:

@@ -288,6 +288,21 @@ int kmu_kmer_hashes_compact(kmu_ctx *ctx, const kmu_hash_params *p, const uint8_
 int kmu_sketch(kmu_ctx *ctx, const kmu_sketch_params *p, const uint8_t *bases, const uint64_t *offsets,
                const uint64_t *packed_offsets, uint32_t n_seq, const uint64_t *block_row_offsets, void *sig_out,
                uint32_t *counts_out);
+/* One signature per GROUP of consecutive sequences: row g = sketch_compressedkmer_seqs over the sequences
+ * [group_offsets[g], group_offsets[g+1]) -- what gsearch does per genome / proteome file (setsketchert.rs:160-202, 299-335,
+ * 1007-1045) --, bit for bit the row kmu_sketch gives in mode ALL_SEQS for those sequences alone.
+ * group_offsets: n_groups + 1 sequence indices, group_offsets[0] == 0, non-decreasing, group_offsets[n_groups] == n_seq
+ * (KMU_E_BAD_ARG otherwise, before any kernel reads through them); it lives where `offsets` lives (p->mem).  An empty group is
+ * allowed and gets the ALL_SEQS row of n_seq = 0.  sig_out: n_groups rows of sketch_size signatures.  n_groups == 0: KMU_OK,
+ * nothing is written.  p->mode is ignored; block_size > 0 and KMU_ALGO_BOTTOMK are KMU_E_UNSUPPORTED; what the kernels find
+ * (KMU_E_NON_ACGT, KMU_E_EMPTY_SEQ, ...) is reported as kmu_sketch reports it, with the same sticky rules in async_device contexts.
+ * Routes:  PROB3A, PROB3, SUPER, SUPER2: one batched pass over all groups -- the kernel launches and the host synchronisations
+ *          (one small device-to-host copy) of a call do not depend on n_groups.
+ *          OPTDENS, REVOPTDENS, HLL (context's kmu_set_hll_params): an internal loop over the groups through the ALL_SEQS
+ *          route of kmu_sketch: same rows, one round of launches per group. */
+int kmu_sketch_groups(kmu_ctx *ctx, const kmu_sketch_params *p, const uint8_t *bases, const uint64_t *offsets,
+                      const uint64_t *packed_offsets, uint32_t n_seq, const uint64_t *group_offsets, uint32_t n_groups,
+                      void *sig_out);
 /* nb_blocks_i = ceil(L_i / block_size) (seqblocksketch.rs:108-112); block_row_offsets_out[n_seq+1], host memory,
  * offsets in host memory */
 int kmu_block_layout(const uint64_t *offsets, uint32_t n_seq, uint32_t block_size, uint64_t *block_row_offsets_out);

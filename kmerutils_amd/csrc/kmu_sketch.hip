@@ -625,6 +625,38 @@ static int resolve_algo(kmu_ctx *ctx, const kmu_sketch_params *p_in, kmu_sketch_
     return KMU_OK;
 }
 
+// What kmu_sketch_groups.hip takes from this file: the checks kmu_sketch makes of an ALL_SEQS call, in its order and with its
+// texts (*p: the resolved parameters, mode set to ALL_SEQS), and ProbMinHash3a slot minima of n_leaves lists of pre-hashed values
+// (the leaf step of sketch_all_hashed).
+namespace kmu {
+int sketch_groups_params(kmu_ctx *ctx, const kmu_sketch_params *p_in, kmu_sketch_params *p) {
+    kmu_sketch_params q = *p_in;
+    q.mode = KMU_MODE_ALL_SEQS;
+    KMU_TRY(resolve_algo(ctx, &q, p));
+    KMU_TRY(check_kmer(ctx, p->kmer_type, p->kmer_size));
+    KMU_TRY(sketch_params_check(ctx, p));
+    if (!fhash_valid(p->fhash, p->kmer_type)) return fail(ctx, KMU_E_BAD_ARG, "fhash %d not valid for kmer_type %d", p->fhash, p->kmer_type);
+    if (p->input_kind == KMU_INPUT_PACKED2 && (kmer_is_aa(p->kmer_type) || p->fhash == KMU_FHASH_CANON_NTHASH_8B))
+        return fail(ctx, KMU_E_BAD_ARG, "packed input not valid for this kmer_type / fhash");
+    if (p->algo == KMU_ALGO_BOTTOMK) return fail(ctx, KMU_E_UNSUPPORTED, "the reference has no bottom-k sketch over a list of sequences");
+    return KMU_OK;
+}
+int launch_pmh3a_leaves(kmu_ctx *ctx, const kmu_sketch_params *p, const uint64_t *items, const uint64_t *bounds, uint32_t n_leaves,
+                        uint64_t *part_h, uint64_t *part_k, uint32_t *d_err) {
+    DevSeqs leaves;
+    leaves.bases = reinterpret_cast<const uint8_t *>(items);
+    leaves.offsets = bounds;
+    leaves.n_seq = n_leaves;
+    leaves.total_bytes = 1; // unused for pre-hashed input
+    PmhInputs in;
+    in.hashed = items;
+    in.hashed_bytes = 8;
+    in.part_h = part_h;
+    in.part_k = part_k;
+    return launch_pmh3a(ctx, p, leaves, nullptr, d_err, in);
+}
+} // namespace kmu
+
 extern "C" int kmu_sketch(kmu_ctx *ctx, const kmu_sketch_params *p_in, const uint8_t *bases, const uint64_t *offsets,
                           const uint64_t *packed_offsets, uint32_t n_seq, const uint64_t *block_row_offsets,
                           void *sig_out, uint32_t *counts_out) {

@@ -1,0 +1,528 @@
+// kmu_sketch_groups.hip -- kmu_sketch_groups: one signature per GROUP of consecutive sequences in one call; row g is what
+// kmu_sketch(KMU_MODE_ALL_SEQS) gives for the sequences of group g alone.  Reference: SeqSketcherT::sketch_compressedkmer_seqs
+// called once per genome / proteome file (src/sketching/setsketchert.rs:160-202, 299-335, 1007-1045).
+//
+// Routes (the kernel launches and host synchronisations of the first two do not depend on the number of groups):
+//  ProbMinHash3a / 3   k_nk_scan + k_seq_hashes_compact over all sequences (groups are runs of consecutive sequences, so the
+//                      compact hash array is already grouped), k_group_plan, a segmented partition of every group into leaves
+//                      of ~4 k keys (k_grp_hist, k_grp_bounds, k_grp_scatter), ONE k_sketch_pmh3a over the leaves of all
+//                      groups, k_pmh_reduce_groups.
+//                      Exact because a key's weight is its multiplicity over its group and the signature is the per-slot
+//                      minimum of (h, key) over disjoint key sets: equal keys of one group land in one leaf (the leaf is a
+//                      function of (group, key)); nothing else about the cut, nor the order inside a leaf, matters.
+//  SuperMinHash(2)     items are independent: chunks of <= 16 384 hashes that never straddle a group (k_grp_chunk_offsets),
+//                      ONE k_sketch_super over all chunks, k_super_reduce_groups.
+//  OptDens / RevOptDens / HLL   a loop over the groups through launch_dens (the ALL_SEQS route of kmu_sketch, per group).
+#include <algorithm>
+#include <vector>
+
+#include "kmu_sketch_kernels.h"
+
+namespace kmu {
+
+int launch_super(kmu_ctx *ctx, const kmu_sketch_params *p, const DevSeqs &ds, void *d_sig, uint32_t *d_err, const void *hashed,
+                 int hashed_bytes, uint64_t *part_rows);
+int launch_dens(kmu_ctx *ctx, const kmu_sketch_params *p, const DevSeqs &ds, void *d_sig, uint32_t *d_err, const void *hashed,
+                int hashed_bytes);
+// kmu_sketch.hip
+int sketch_groups_params(kmu_ctx *ctx, const kmu_sketch_params *p_in, kmu_sketch_params *p);
+int launch_pmh3a_leaves(kmu_ctx *ctx, const kmu_sketch_params *p, const uint64_t *items, const uint64_t *bounds, uint32_t n_leaves,
+                        uint64_t *part_h, uint64_t *part_k, uint32_t *d_err);
+
+static constexpr uint64_t GRP_H_INIT = 0x7FEFFFFFFFFFFFFFull; // an empty slot of k_sketch_pmh3a's partial rows: bits of f64::MAX
+static constexpr uint32_t GRP_TILE = 4096;                    // keys a workgroup takes at a time: 16 per thread
+static constexpr uint32_t GRP_LDS_BITS = 12;                  // groups of up to 2^12 leaves count their tiles in LDS
+static constexpr uint32_t GRP_BAD_START = 1u, GRP_BAD_ORDER = 2u, GRP_BAD_END = 4u;
+
+// the groups on the device: group g holds the hashes [gk[g], gk[g + 1]) and the leaves (chunks) [leaf_base[g], leaf_base[g + 1])
+struct GroupArgs {
+    const uint64_t *gk;        // n_groups + 1
+    const uint64_t *leaf_base; // n_groups + 1
+    const uint32_t *bits;      // ProbMinHash: group g has 2^bits[g] leaves
+    uint32_t n_groups;
+};
+
+// leaves of ~4k keys: the rule of sketch_all_hashed
+__device__ __forceinline__ uint32_t grp_leaf_bits(uint64_t n) {
+    uint32_t b = 0;
+    while (b < 22 && (n >> b) > 4096) b++;
+    return b;
+}
+// chunks of a SuperMinHash group: the rule of sketch_all_hashed
+__device__ __forceinline__ uint64_t grp_chunks(uint64_t n) {
+    const uint64_t c = (n + 16383) / 16384;
+    return c < 1 ? 1 : (c > 8192 ? 8192 : c);
+}
+// leaf of a key inside its group (b >= 1): the top bits of a 64-bit finaliser (MurmurHash3's)
+__device__ __forceinline__ uint32_t grp_bucket(uint64_t x, uint32_t b) {
+    x ^= x >> 33;
+    x *= 0xff51afd7ed558ccdull;
+    x ^= x >> 33;
+    x *= 0xc4ceb9fe1a85ec53ull;
+    x ^= x >> 33;
+    return (uint32_t) (x >> (64 - b));
+}
+// the group of item i, searched in [lo, hi] (gk[lo] <= i < gk[hi + 1]): the last g with gk[g] <= i -- never an empty group
+__device__ __forceinline__ uint32_t grp_of(const uint64_t *gk, uint32_t lo, uint32_t hi, uint64_t i) {
+    while (lo < hi) {
+        const uint32_t mid = lo + (hi - lo + 1) / 2;
+        if (gk[mid] <= i) lo = mid;
+        else hi = mid - 1;
+    }
+    return lo;
+}
+__device__ __forceinline__ uint64_t grp_shfl_up(uint64_t v, int d) {
+    return ((uint64_t) (uint32_t) __shfl_up((int) (v >> 32), d, 64) << 32) | (uint32_t) __shfl_up((int) (uint32_t) v, d, 64);
+}
+// exclusive scan of v over a workgroup of 1024 threads, on top of *carry; *carry becomes the running total.  All threads call it.
+__device__ __forceinline__ uint64_t grp_block_scan(uint64_t v, uint64_t *wtot, uint64_t *carry) {
+    uint64_t incl = v;
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint64_t o = grp_shfl_up(incl, d);
+        if (lane_id() >= d) incl += o;
+    }
+    if (lane_id() == 63) wtot[threadIdx.x >> 6] = incl;
+    __syncthreads();
+    uint64_t pre = *carry;
+    for (int w = 0; w < (int) (threadIdx.x >> 6); w++) pre += wtot[w];
+    __syncthreads();
+    if (threadIdx.x == blockDim.x - 1) *carry = pre + incl;
+    __syncthreads();
+    return pre + incl - v;
+}
+
+// The plan of a call, one workgroup: checks group_offsets (every index is clamped to n_seq before it is used, so a malformed
+// array is never read through), gk[g] = koff[group_offsets[g]], the leaves (super: chunks) of every group and their exclusive
+// scan.  head: [0] hashes of the call, [1] leaves of the call, [2] GRP_BAD_* bits.
+__global__ void __launch_bounds__(1024) k_group_plan(const uint64_t *go, uint32_t n_groups, uint32_t n_seq, const uint64_t *koff, int super,
+                                                     uint64_t *gk, uint64_t *leaf_base, uint32_t *bits, uint64_t *head) {
+    __shared__ uint64_t wtot[16];
+    __shared__ uint64_t carry;
+    __shared__ uint32_t bad;
+    if (threadIdx.x == 0) {
+        carry = 0;
+        bad = 0;
+    }
+    __syncthreads();
+    for (uint32_t base = 0; base < n_groups; base += blockDim.x) {
+        const uint32_t g = base + threadIdx.x;
+        uint64_t v = 0;
+        if (g < n_groups) {
+            const uint64_t s0 = go[g], s1 = go[g + 1];
+            uint32_t e = 0;
+            if (g == 0 && s0 != 0) e |= GRP_BAD_START;
+            if (s1 < s0) e |= GRP_BAD_ORDER;
+            if (g == n_groups - 1 && s1 != (uint64_t) n_seq) e |= GRP_BAD_END;
+            if (e) atomicOr(&bad, e);
+            const uint64_t k0 = koff[s0 < n_seq ? s0 : n_seq], k1 = koff[s1 < n_seq ? s1 : n_seq];
+            const uint64_t n = k1 > k0 ? k1 - k0 : 0;
+            gk[g] = k0;
+            if (g == n_groups - 1) gk[n_groups] = k1;
+            if (super) v = grp_chunks(n);
+            else {
+                const uint32_t b = grp_leaf_bits(n);
+                bits[g] = b;
+                v = 1ull << b;
+            }
+        }
+        const uint64_t excl = grp_block_scan(v, wtot, &carry);
+        if (g < n_groups) leaf_base[g] = excl;
+    }
+    if (threadIdx.x == 0) {
+        leaf_base[n_groups] = carry;
+        head[0] = koff[n_seq];
+        head[1] = carry;
+        head[2] = bad;
+    }
+}
+
+// keys per leaf.  A tile inside one group counts in LDS and adds its non-empty bins at the end; a tile across a group
+// boundary (and a group of more than 2^12 leaves) counts key by key.  Single-leaf groups are not counted: k_grp_bounds knows them.
+__global__ void __launch_bounds__(256) k_grp_hist(const uint64_t *keys, uint64_t n, GroupArgs ga, unsigned long long *cnt) {
+    __shared__ uint32_t h[1u << GRP_LDS_BITS];
+    __shared__ uint32_t sg[2];
+    const uint32_t tid = threadIdx.x;
+    const uint64_t n_tiles = (n + GRP_TILE - 1) / GRP_TILE;
+    for (uint64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        const uint64_t t0 = tile * GRP_TILE, t1 = t0 + GRP_TILE < n ? t0 + GRP_TILE : n;
+        if (tid == 0) {
+            sg[0] = grp_of(ga.gk, 0, ga.n_groups - 1, t0);
+            sg[1] = grp_of(ga.gk, sg[0], ga.n_groups - 1, t1 - 1);
+        }
+        __syncthreads();
+        const uint32_t g0 = sg[0], g1 = sg[1];
+        __syncthreads();
+        if (g0 == g1) {
+            const uint32_t b = ga.bits[g0];
+            if (b == 0) continue;
+            const uint64_t lb = ga.leaf_base[g0];
+            if (b <= GRP_LDS_BITS) {
+                for (uint32_t x = tid; x < (1u << b); x += 256) h[x] = 0;
+                __syncthreads();
+                for (uint32_t j = 0; j < GRP_TILE / 512; j++) {
+                    const uint64_t i = t0 + ((uint64_t) j * 256 + tid) * 2;
+                    if (i + 1 < t1) {
+                        const ulonglong2 v = *reinterpret_cast<const ulonglong2 *>(keys + i);
+                        atomicAdd(&h[grp_bucket(v.x, b)], 1u);
+                        atomicAdd(&h[grp_bucket(v.y, b)], 1u);
+                    } else if (i < t1)
+                        atomicAdd(&h[grp_bucket(keys[i], b)], 1u);
+                }
+                __syncthreads();
+                for (uint32_t x = tid; x < (1u << b); x += 256)
+                    if (h[x]) atomicAdd(&cnt[lb + x], (unsigned long long) h[x]);
+                __syncthreads();
+            } else {
+                for (uint64_t i = t0 + tid; i < t1; i += 256) atomicAdd(&cnt[lb + grp_bucket(keys[i], b)], 1ull);
+            }
+        } else {
+            for (uint64_t i = t0 + tid; i < t1; i += 256) {
+                const uint32_t g = grp_of(ga.gk, g0, g1, i), b = ga.bits[g];
+                if (b) atomicAdd(&cnt[ga.leaf_base[g] + grp_bucket(keys[i], b)], 1ull);
+            }
+        }
+    }
+}
+
+// the leaves' bounds in the partitioned array: inside group g an exclusive scan of its counts on top of gk[g].  One workgroup
+// per group.  cnt holds the counts on entry and the same bounds on exit: the cursors of k_grp_scatter.
+__global__ void __launch_bounds__(1024) k_grp_bounds(GroupArgs ga, unsigned long long *cnt, uint64_t *bounds) {
+    __shared__ uint64_t wtot[16];
+    __shared__ uint64_t carry;
+    for (uint32_t g = blockIdx.x; g < ga.n_groups; g += gridDim.x) {
+        const uint32_t b = ga.bits[g];
+        const uint64_t lb = ga.leaf_base[g], first = ga.gk[g];
+        if (b == 0) {
+            if (threadIdx.x == 0) {
+                bounds[lb] = first;
+                cnt[lb] = first;
+            }
+        } else {
+            __syncthreads();
+            if (threadIdx.x == 0) carry = first;
+            __syncthreads();
+            const uint64_t nb = 1ull << b;
+            for (uint64_t x0 = 0; x0 < nb; x0 += blockDim.x) {
+                const uint64_t x = x0 + threadIdx.x;
+                const uint64_t v = x < nb ? (uint64_t) cnt[lb + x] : 0;
+                const uint64_t excl = grp_block_scan(v, wtot, &carry);
+                if (x < nb) {
+                    bounds[lb + x] = excl;
+                    cnt[lb + x] = excl;
+                }
+            }
+        }
+        if (g == ga.n_groups - 1 && threadIdx.x == 0) bounds[ga.leaf_base[ga.n_groups]] = ga.gk[ga.n_groups];
+    }
+}
+
+// the keys into their leaves.  A tile inside one group ranks its keys per leaf in LDS and reserves one range per non-empty leaf
+// with one atomic; a key of a single-leaf group keeps its place (a copy).  The order inside a leaf is arbitrary: a leaf is a multiset.
+__global__ void __launch_bounds__(256) k_grp_scatter(const uint64_t *keys, uint64_t n, GroupArgs ga, unsigned long long *cursor,
+                                                     uint64_t *out) {
+    __shared__ uint32_t h[1u << GRP_LDS_BITS];
+    __shared__ uint32_t sg[2];
+    const uint32_t tid = threadIdx.x;
+    const uint64_t n_tiles = (n + GRP_TILE - 1) / GRP_TILE;
+    for (uint64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        const uint64_t t0 = tile * GRP_TILE, t1 = t0 + GRP_TILE < n ? t0 + GRP_TILE : n;
+        if (tid == 0) {
+            sg[0] = grp_of(ga.gk, 0, ga.n_groups - 1, t0);
+            sg[1] = grp_of(ga.gk, sg[0], ga.n_groups - 1, t1 - 1);
+        }
+        __syncthreads();
+        const uint32_t g0 = sg[0], g1 = sg[1];
+        __syncthreads();
+        if (g0 == g1) {
+            const uint32_t b = ga.bits[g0];
+            const uint64_t lb = ga.leaf_base[g0], first = ga.gk[g0];
+            if (b == 0) {
+                for (uint32_t j = 0; j < GRP_TILE / 512; j++) {
+                    const uint64_t i = t0 + ((uint64_t) j * 256 + tid) * 2;
+                    if (i + 1 < t1) *reinterpret_cast<ulonglong2 *>(out + i) = *reinterpret_cast<const ulonglong2 *>(keys + i);
+                    else if (i < t1) out[i] = keys[i];
+                }
+            } else if (b <= GRP_LDS_BITS) {
+                constexpr uint32_t NONE = 0xFFFFFFFFu;
+                uint64_t k[GRP_TILE / 256];
+                uint32_t rk[GRP_TILE / 256];
+                for (uint32_t x = tid; x < (1u << b); x += 256) h[x] = 0;
+                __syncthreads();
+#pragma unroll
+                for (uint32_t j = 0; j < GRP_TILE / 512; j++) {
+                    const uint64_t i = t0 + ((uint64_t) j * 256 + tid) * 2;
+                    k[2 * j] = k[2 * j + 1] = 0;
+                    rk[2 * j] = rk[2 * j + 1] = NONE;
+                    if (i + 1 < t1) {
+                        const ulonglong2 v = *reinterpret_cast<const ulonglong2 *>(keys + i);
+                        k[2 * j] = v.x;
+                        k[2 * j + 1] = v.y;
+                        rk[2 * j] = atomicAdd(&h[grp_bucket(v.x, b)], 1u);
+                        rk[2 * j + 1] = atomicAdd(&h[grp_bucket(v.y, b)], 1u);
+                    } else if (i < t1) {
+                        k[2 * j] = keys[i];
+                        rk[2 * j] = atomicAdd(&h[grp_bucket(k[2 * j], b)], 1u);
+                    }
+                }
+                __syncthreads();
+                // (a group of at most 2^12 leaves has fewer than 2^25 keys: places relative to the group's first fit 32 bits)
+                for (uint32_t x = tid; x < (1u << b); x += 256) {
+                    const uint32_t c = h[x];
+                    if (c) h[x] = (uint32_t) ((uint64_t) atomicAdd(&cursor[lb + x], (unsigned long long) c) - first);
+                }
+                __syncthreads();
+#pragma unroll
+                for (uint32_t j = 0; j < GRP_TILE / 256; j++)
+                    if (rk[j] != NONE) out[first + h[grp_bucket(k[j], b)] + rk[j]] = k[j];
+                __syncthreads();
+            } else {
+                for (uint64_t i = t0 + tid; i < t1; i += 256) {
+                    const uint64_t key = keys[i];
+                    out[atomicAdd(&cursor[lb + grp_bucket(key, b)], 1ull)] = key;
+                }
+            }
+        } else {
+            for (uint64_t i = t0 + tid; i < t1; i += 256) {
+                const uint32_t g = grp_of(ga.gk, g0, g1, i), b = ga.bits[g];
+                const uint64_t key = keys[i];
+                if (b == 0) out[i] = key;
+                else out[atomicAdd(&cursor[ga.leaf_base[g] + grp_bucket(key, b)], 1ull)] = key;
+            }
+        }
+    }
+}
+
+// k_pmh_reduce per group: per slot the smallest (h, key) over the leaves of group blockIdx.x.  A wave reads 64 consecutive slots
+// of one leaf row (512 contiguous bytes), the four waves of the workgroup take every fourth leaf.
+__global__ void __launch_bounds__(256) k_pmh_reduce_groups(const uint64_t *part_h, const uint64_t *part_k, const uint64_t *leaf_base, int m,
+                                                           int sig_bytes, void *sig_out) {
+    __shared__ uint64_t sh[256], sk[256];
+    const uint32_t g = blockIdx.x, lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
+    const uint64_t l0 = leaf_base[g], l1 = leaf_base[g + 1];
+    for (uint32_t st = blockIdx.y; st * 64u < (uint32_t) m; st += gridDim.y) {
+        const uint32_t t = st * 64u + lane;
+        uint64_t bh = GRP_H_INIT, bk = 0;
+        if (t < (uint32_t) m)
+            for (uint64_t i = l0 + w; i < l1; i += 4) {
+                const uint64_t hh = part_h[i * (uint64_t) m + t], key = part_k[i * (uint64_t) m + t];
+                if (hh < bh || (hh == bh && hh != GRP_H_INIT && key < bk)) { bh = hh; bk = key; }
+            }
+        sh[threadIdx.x] = bh;
+        sk[threadIdx.x] = bk;
+        __syncthreads();
+        if (w == 0 && t < (uint32_t) m) {
+            for (uint32_t ww = 1; ww < 4; ww++) {
+                const uint64_t hh = sh[ww * 64 + lane], key = sk[ww * 64 + lane];
+                if (hh < bh || (hh == bh && hh != GRP_H_INIT && key < bk)) { bh = hh; bk = key; }
+            }
+            const uint64_t v = bh == GRP_H_INIT ? 0ull : bk;
+            if (sig_bytes == 4) reinterpret_cast<uint32_t *>(sig_out)[(uint64_t) g * m + t] = (uint32_t) v;
+            else reinterpret_cast<uint64_t *>(sig_out)[(uint64_t) g * m + t] = v;
+        }
+        __syncthreads();
+    }
+}
+
+// the chunks of every group: chunk c of nc starts at gk[g] + n c / nc (one wave per group)
+__global__ void __launch_bounds__(256) k_grp_chunk_offsets(GroupArgs ga, uint64_t *off) {
+    const uint32_t wave = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), n_waves = gridDim.x * (blockDim.x >> 6);
+    for (uint32_t g = wave; g < ga.n_groups; g += n_waves) {
+        const uint64_t k0 = ga.gk[g], n = ga.gk[g + 1] - k0, lb = ga.leaf_base[g], nc = ga.leaf_base[g + 1] - lb;
+        for (uint64_t c = lane_id(); c < nc; c += 64) off[lb + c] = k0 + n * c / nc;
+        if (g == ga.n_groups - 1 && lane_id() == 0) off[lb + nc] = k0 + n;
+    }
+}
+
+// k_super_reduce per group: element-wise minimum of the chunk rows of group blockIdx.x (order-preserving bit patterns)
+__global__ void __launch_bounds__(256) k_super_reduce_groups(const uint64_t *part_rows, const uint64_t *leaf_base, int m, int mode,
+                                                             uint64_t init_bits, void *sig_out) {
+    const uint32_t g = blockIdx.x;
+    const uint64_t l0 = leaf_base[g], l1 = leaf_base[g + 1];
+    for (uint32_t t = blockIdx.y * blockDim.x + threadIdx.x; t < (uint32_t) m; t += gridDim.y * blockDim.x) {
+        uint64_t best = init_bits;
+        for (uint64_t i = l0; i < l1; i++) {
+            const uint64_t v = part_rows[i * (uint64_t) m + t];
+            best = v < best ? v : best;
+        }
+        if (mode == 0 || mode == 2) reinterpret_cast<uint64_t *>(sig_out)[(uint64_t) g * m + t] = best;
+        else reinterpret_cast<uint32_t *>(sig_out)[(uint64_t) g * m + t] = (uint32_t) best;
+    }
+}
+
+} // namespace kmu
+
+using namespace kmu;
+
+static const char *groups_bad_text(uint32_t bits) {
+    return bits & GRP_BAD_START ? "group_offsets[0] must be 0"
+           : bits & GRP_BAD_ORDER ? "group_offsets must not decrease"
+                                  : "group_offsets[n_groups] must be n_seq";
+}
+static uint32_t groups_check_host(const uint64_t *go, uint32_t n_groups, uint32_t n_seq) {
+    uint32_t e = go[0] != 0 ? GRP_BAD_START : 0u;
+    for (uint32_t g = 0; g < n_groups; g++)
+        if (go[g + 1] < go[g]) e |= GRP_BAD_ORDER;
+    if (go[n_groups] != (uint64_t) n_seq) e |= GRP_BAD_END;
+    return e;
+}
+
+// OptDens / RevOptDens / HLL: the ALL_SEQS route of kmu_sketch, group by group
+static int groups_dens(kmu_ctx *ctx, const kmu_sketch_params *p, const DevSeqs &ds, const uint64_t *h_go, const uint64_t *d_go,
+                       uint32_t n_groups, uint8_t *d_sig, size_t row_bytes, uint32_t *d_err) {
+    std::vector<uint64_t> tmp;
+    if (!h_go) { // device memory: the one copy of the call, checked before anything goes through it
+        tmp.resize((size_t) n_groups + 1);
+        KMU_HIP(ctx, hipMemcpyAsync(tmp.data(), d_go, ((size_t) n_groups + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
+        KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        h_go = tmp.data();
+        const uint32_t e = groups_check_host(h_go, n_groups, ds.n_seq);
+        if (e) return fail(ctx, KMU_E_BAD_ARG, "%s", groups_bad_text(e));
+    }
+    for (uint32_t g = 0; g < n_groups; g++) {
+        DevSeqs one = ds;
+        one.offsets = ds.offsets + h_go[g];
+        one.packed_offsets = ds.packed_offsets ? ds.packed_offsets + h_go[g] : nullptr;
+        one.n_seq = (uint32_t) (h_go[g + 1] - h_go[g]);
+        KMU_TRY(launch_dens(ctx, p, one, d_sig + (size_t) g * row_bytes, d_err, nullptr, 0));
+    }
+    return KMU_OK;
+}
+
+// ProbMinHash3a / 3 and SuperMinHash(2): one batched pass over all groups
+static int groups_batched(kmu_ctx *ctx, const kmu_sketch_params *p, const DevSeqs &ds, const uint64_t *d_go, uint32_t n_groups,
+                          void *d_sig, uint32_t *d_err) {
+    const uint32_t n_seq = ds.n_seq;
+    const int m = p->sketch_size;
+    const bool super = p->algo != KMU_ALGO_PROB3A;
+    void *koff, *gk, *lbase, *bits, *head, *hk;
+    KMU_TRY(dev_buf(ctx, "all.koff", ((size_t) n_seq + 1) * 8, &koff));
+    KMU_TRY(dev_buf(ctx, "grp.gk", ((size_t) n_groups + 1) * 8, &gk));
+    KMU_TRY(dev_buf(ctx, "grp.leaf_base", ((size_t) n_groups + 1) * 8, &lbase));
+    KMU_TRY(dev_buf(ctx, "grp.bits", (size_t) n_groups * 4, &bits));
+    KMU_TRY(dev_buf(ctx, "grp.head", 64, &head));
+    hipLaunchKernelGGL(k_nk_scan, dim3(1), dim3(1024), 0, ctx->stream, ds.offsets, n_seq, p->kmer_size, (uint64_t *) koff, d_err);
+    {
+        KernelTimer t(ctx, "k_group_plan");
+        hipLaunchKernelGGL(k_group_plan, dim3(1), dim3(1024), 0, ctx->stream, d_go, n_groups, n_seq, (const uint64_t *) koff, super ? 1 : 0,
+                           (uint64_t *) gk, (uint64_t *) lbase, (uint32_t *) bits, (uint64_t *) head);
+    }
+    KMU_HIP(ctx, hipGetLastError());
+    uint64_t h_head[3] = {0, 0, 0}; // the one device-to-host copy of the call
+    KMU_HIP(ctx, hipMemcpyAsync(h_head, head, sizeof h_head, hipMemcpyDeviceToHost, ctx->stream));
+    KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (h_head[2]) {
+        if (!(p->mem == KMU_MEM_DEVICE && ctx->async_device)) (void) check_err_word(ctx, d_err); // (read, so that it starts clear next time)
+        return fail(ctx, KMU_E_BAD_ARG, "%s", groups_bad_text((uint32_t) h_head[2]));
+    }
+    const uint64_t n_items = h_head[0], n_leaves = h_head[1];
+    if (n_leaves > 0x7FFFFFFFull) return fail(ctx, KMU_E_UNSUPPORTED, "%llu leaves in one call", (unsigned long long) n_leaves);
+    KMU_TRY(dev_buf(ctx, "all.hashes", n_items * 8 + 64, &hk));
+    if (n_seq) {
+        KmerCfg cfg{p->kmer_type, p->kmer_size, p->fhash};
+        const int spread = n_seq < (uint32_t) ctx->num_cus * 4 ? 1 : 0;
+        const int grid = spread ? ctx->num_cus * 8 : (int) std::min<uint32_t>(n_seq, (uint32_t) ctx->num_cus * 8);
+        KernelTimer t(ctx, "k_seq_hashes_compact");
+        hipLaunchKernelGGL(k_seq_hashes_compact, dim3(grid), dim3(256), 0, ctx->stream, ds.bases, ds.offsets, ds.packed_offsets, n_seq,
+                           ds.packed, ds.total_bytes, cfg, (const uint64_t *) koff, (uint64_t *) hk, d_err, spread);
+    }
+    KMU_HIP(ctx, hipGetLastError());
+    GroupArgs ga{(const uint64_t *) gk, (const uint64_t *) lbase, (const uint32_t *) bits, n_groups};
+    const unsigned tile_grid = (unsigned) std::max<uint64_t>(1, std::min<uint64_t>((n_items + GRP_TILE - 1) / GRP_TILE, (uint64_t) ctx->num_cus * 8));
+    const unsigned slot_tiles = (unsigned) std::min<uint32_t>(65535u, ((uint32_t) m + 63u) / 64u);
+    if (!super) {
+        void *cnt, *bounds, *items, *ph, *pk;
+        KMU_TRY(dev_buf(ctx, "grp.cursor", n_leaves * 8 + 64, &cnt));
+        KMU_TRY(dev_buf(ctx, "grp.bounds", (n_leaves + 1) * 8 + 64, &bounds));
+        KMU_TRY(dev_buf(ctx, "grp.items", n_items * 8 + 64, &items));
+        KMU_TRY(dev_buf(ctx, "all.part_h", n_leaves * m * 8, &ph));
+        KMU_TRY(dev_buf(ctx, "all.part_k", n_leaves * m * 8, &pk));
+        KMU_HIP(ctx, hipMemsetAsync(cnt, 0, n_leaves * 8, ctx->stream));
+        {
+            KernelTimer t(ctx, "k_grp_hist");
+            hipLaunchKernelGGL(k_grp_hist, dim3(tile_grid), dim3(256), 0, ctx->stream, (const uint64_t *) hk, n_items, ga, (unsigned long long *) cnt);
+        }
+        {
+            KernelTimer t(ctx, "k_grp_bounds");
+            hipLaunchKernelGGL(k_grp_bounds, dim3(std::min<uint32_t>(n_groups, (uint32_t) ctx->num_cus * 2)), dim3(1024), 0, ctx->stream, ga,
+                               (unsigned long long *) cnt, (uint64_t *) bounds);
+        }
+        {
+            KernelTimer t(ctx, "k_grp_scatter");
+            hipLaunchKernelGGL(k_grp_scatter, dim3(tile_grid), dim3(256), 0, ctx->stream, (const uint64_t *) hk, n_items, ga,
+                               (unsigned long long *) cnt, (uint64_t *) items);
+        }
+        KMU_HIP(ctx, hipGetLastError());
+        KMU_TRY(launch_pmh3a_leaves(ctx, p, (const uint64_t *) items, (const uint64_t *) bounds, (uint32_t) n_leaves, (uint64_t *) ph,
+                                    (uint64_t *) pk, d_err));
+        {
+            KernelTimer t(ctx, "k_pmh_reduce_groups");
+            hipLaunchKernelGGL(k_pmh_reduce_groups, dim3(n_groups, slot_tiles), dim3(256), 0, ctx->stream, (const uint64_t *) ph, (const uint64_t *) pk,
+                               (const uint64_t *) lbase, m, kmer_val_bytes(p->kmer_type), d_sig);
+        }
+        KMU_HIP(ctx, hipGetLastError());
+        return KMU_OK;
+    }
+    // SuperMinHash / SuperMinHash2
+    void *d_off, *pr;
+    KMU_TRY(dev_buf(ctx, "all.chunk_off", (n_leaves + 1) * 8, &d_off));
+    KMU_TRY(dev_buf(ctx, "all.part_rows", n_leaves * m * 8, &pr));
+    hipLaunchKernelGGL(k_grp_chunk_offsets, dim3(std::max<uint32_t>(1, std::min<uint32_t>((n_groups + 3) / 4, (uint32_t) ctx->num_cus * 8))), dim3(256), 0,
+                       ctx->stream, ga, (uint64_t *) d_off);
+    KMU_HIP(ctx, hipGetLastError());
+    DevSeqs chunks;
+    chunks.bases = reinterpret_cast<const uint8_t *>(hk);
+    chunks.offsets = (const uint64_t *) d_off;
+    chunks.n_seq = (uint32_t) n_leaves;
+    chunks.total_bytes = 1;
+    KMU_TRY(launch_super(ctx, p, chunks, nullptr, d_err, hk, 8, (uint64_t *) pr));
+    const int mode = p->algo == KMU_ALGO_SUPER ? (p->sig_type == KMU_SIG_F32 ? 1 : 0) : (p->sig_type == KMU_SIG_U32 ? 3 : 2);
+    // the initial slot patterns of k_sketch_super (super_init_bits): F::from(u32::MAX) as f64 / f32, all ones of u64 / u32
+    const uint64_t init_bits = mode == 0 ? 0x41EFFFFFFFE00000ull : mode == 1 ? 0x4F800000ull : mode == 2 ? 0xFFFFFFFFFFFFFFFFull : 0xFFFFFFFFull;
+    {
+        KernelTimer t(ctx, "k_super_reduce_groups");
+        hipLaunchKernelGGL(k_super_reduce_groups, dim3(n_groups, (unsigned) std::min<uint32_t>(65535u, ((uint32_t) m + 255u) / 256u)), dim3(256), 0,
+                           ctx->stream, (const uint64_t *) pr, (const uint64_t *) lbase, m, mode, init_bits, d_sig);
+    }
+    KMU_HIP(ctx, hipGetLastError());
+    return KMU_OK;
+}
+
+extern "C" int kmu_sketch_groups(kmu_ctx *ctx, const kmu_sketch_params *p_in, const uint8_t *bases, const uint64_t *offsets,
+                                 const uint64_t *packed_offsets, uint32_t n_seq, const uint64_t *group_offsets, uint32_t n_groups,
+                                 void *sig_out) {
+    if (!ctx || !p_in || !sig_out || !group_offsets) return KMU_E_BAD_ARG;
+    kmu_sketch_params p_res;
+    KMU_TRY(sketch_groups_params(ctx, p_in, &p_res));
+    const kmu_sketch_params *p = &p_res;
+    if (p->mem != KMU_MEM_HOST && p->mem != KMU_MEM_DEVICE) return fail(ctx, KMU_E_BAD_ARG, "bad mem %d", p->mem);
+    if (!offsets || (!bases && n_seq)) return fail(ctx, KMU_E_BAD_ARG, "null sequence buffers");
+    if (n_groups == 0) return KMU_OK;
+    const bool host = p->mem == KMU_MEM_HOST;
+    if (host) {
+        const uint32_t e = groups_check_host(group_offsets, n_groups, n_seq);
+        if (e) return fail(ctx, KMU_E_BAD_ARG, "%s", groups_bad_text(e));
+    }
+    KMU_HIP(ctx, hipSetDevice(ctx->device));
+    DevSeqs ds;
+    KMU_TRY(stage_sequences(ctx, bases, offsets, packed_offsets, n_seq, p->input_kind, p->mem, &ds));
+    const size_t sigb = p->sig_type == KMU_SIG_U16 ? 2 : (p->sig_type == KMU_SIG_U32 || p->sig_type == KMU_SIG_F32) ? 4 : 8;
+    const size_t row_bytes = (size_t) p->sketch_size * sigb;
+    void *d_sig = sig_out;
+    const uint64_t *d_go = group_offsets;
+    if (host) {
+        void *q;
+        KMU_TRY(dev_buf(ctx, "out.sig", (size_t) n_groups * row_bytes + 64, &q));
+        d_sig = q;
+        KMU_TRY(dev_buf(ctx, "grp.go", ((size_t) n_groups + 1) * 8, &q));
+        KMU_HIP(ctx, hipMemcpyAsync(q, group_offsets, ((size_t) n_groups + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
+        d_go = (const uint64_t *) q;
+    }
+    uint32_t *d_err;
+    KMU_TRY(get_err_word(ctx, &d_err));
+    const bool dens = p->algo == KMU_ALGO_OPTDENS || p->algo == KMU_ALGO_REVOPTDENS || p->algo == KMU_ALGO_HLL;
+    if (dens) KMU_TRY(groups_dens(ctx, p, ds, host ? group_offsets : nullptr, d_go, n_groups, (uint8_t *) d_sig, row_bytes, d_err));
+    else KMU_TRY(groups_batched(ctx, p, ds, d_go, n_groups, d_sig, d_err));
+    if (host) KMU_HIP(ctx, hipMemcpyAsync(sig_out, d_sig, (size_t) n_groups * row_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    if (!(p->mem == KMU_MEM_DEVICE && ctx->async_device)) KMU_TRY(check_err_word(ctx, d_err));
+    return finish_call(ctx, p->mem);
+}

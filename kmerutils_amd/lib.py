@@ -27,7 +27,7 @@ SYMBOLS = [
     "kmu_minhash_distance_pairs", "kmu_ingest_fastq", "kmu_ingest_fasta", "kmu_ingest_fastx", "kmu_dev_alloc", "kmu_dev_free",
     "kmu_copy_to_device", "kmu_copy_to_host", "kmu_count_once_positions", "kmu_count_eliminate_once", "kmu_sketch_partial_words",
     "kmu_sketch_partial", "kmu_sketch_hashed_partial", "kmu_sketch_merge_partials", "kmu_kmer_hashes_compact", "kmu_set_hll_params",
-    "kmu_kmer_hashes_range", "kmu_kmer_distribution", "kmu_nthash",
+    "kmu_kmer_hashes_range", "kmu_kmer_distribution", "kmu_nthash", "kmu_sketch_groups",
     "kmu_comm_get_id", "kmu_comm_init", "kmu_comm_init_custom", "kmu_comm_set_transport", "kmu_comm_transport", "kmu_comm_destroy", "kmu_comm_rank", "kmu_comm_nranks",
     "kmu_comm_allgather", "kmu_comm_get_stats", "kmu_count_finalize", "kmu_kmer_owner",
     "kmu_sketch_count", "kmu_host_alloc", "kmu_host_free", "kmu_count_nb_occurrences", "kmu_count_table_info",
@@ -91,6 +91,7 @@ def load():
     L.kmu_count_extract_superkmers.argtypes = [vp, vp, vp, C.c_uint32, C.c_int, C.c_uint32, C.POINTER(vp), vp, vp]
     L.kmu_count_add_superkmers.argtypes = [vp, vp, C.c_uint64, C.c_int]
     L.kmu_sketch.argtypes = [vp, C.POINTER(A.SketchParams), vp, vp, vp, C.c_uint32, vp, vp, vp]
+    L.kmu_sketch_groups.argtypes = [vp, C.POINTER(A.SketchParams), vp, vp, vp, C.c_uint32, vp, C.c_uint32, vp]
     L.kmu_block_layout.argtypes = [vp, C.c_uint32, C.c_uint32, vp]
     L.kmu_sketch_hashed.argtypes = [vp, C.POINTER(A.SketchParams), vp, vp, C.c_uint32, vp, vp]
     L.kmu_count_create.argtypes = [vp, C.POINTER(A.CountParams), C.POINTER(vp)]
@@ -487,6 +488,30 @@ class Context:
         if want_counts:
             return out, counts_out[:rows]
         return out
+
+    def sketch_groups(self, bases, offsets, group_offsets, params, packed_offsets=None, out=None):
+        """kmu_sketch_groups: one signature per group of consecutive sequences, sig [n_groups, m]; row g is the ALL_SEQS row of
+        the sequences group_offsets[g] .. group_offsets[g + 1].  Host (numpy) or device (torch cuda) buffers, `group_offsets`
+        on the same side as `offsets`."""
+        n = len(offsets) - 1
+        if not _is_torch(group_offsets):
+            group_offsets = np.ascontiguousarray(group_offsets, np.uint64)
+        n_groups = len(group_offsets) - 1
+        mem = self._mem(bases, offsets, group_offsets)
+        p = A.SketchParams.from_buffer_copy(params)
+        p.mem = mem
+        m = p.sketch_size
+        if out is None:
+            if mem == A.MEM_DEVICE:
+                import torch
+                tdt = {A.SIG_U32: torch.int32, A.SIG_U64: torch.int64, A.SIG_F32: torch.float32,
+                       A.SIG_F64: torch.float64, A.SIG_U16: torch.int16}[p.sig_type]
+                out = torch.zeros((max(n_groups, 1), m), dtype=tdt, device=bases.device)
+            else:
+                out = np.zeros((max(n_groups, 1), m), dtype=A.SIG_NP[p.sig_type])
+        self._check(self.L.kmu_sketch_groups(self.h, C.byref(p), _ptr(bases)[0], _ptr(offsets)[0], _ptr(packed_offsets)[0],
+                                             n, _ptr(group_offsets)[0], n_groups, _ptr(out)[0]))
+        return out[:n_groups]
 
     def sketch_count(self, bases, offsets, params, counter=None, out=None):
         """kmu_sketch_count: the reads once, both results -- signature rows (returned) and, if `counter` is given, the

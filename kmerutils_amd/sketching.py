@@ -103,6 +103,14 @@ class _SketcherBase:
         bases, offsets = _as_arrays(vseq)
         return self.ctx.sketch(bases, offsets, self._params(fhash, A.MODE_ALL_SEQS, flags=flags))
 
+    def sketch_compressedkmer_seqs_groups(self, groups, fhash, flags=0):
+        """sketch_compressedkmer_seqs of every inner list of `groups` (a genome's contigs, a proteome's proteins), one row per
+        inner list, in ONE library call (kmu_sketch_groups): what gsearch runs file by file"""
+        group_offsets = np.zeros(len(groups) + 1, dtype=np.uint64)
+        group_offsets[1:] = np.cumsum([len(g) for g in groups], dtype=np.uint64)
+        bases, offsets = _as_arrays([s for g in groups for s in g])
+        return self.ctx.sketch_groups(bases, offsets, group_offsets, self._params(fhash, A.MODE_ALL_SEQS, flags=flags))
+
 
 class ProbHash3aSketch(_SketcherBase):
     """type Sig = Kmer::Val (setsketchert.rs:107)"""
