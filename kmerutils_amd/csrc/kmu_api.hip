@@ -35,6 +35,18 @@ bool fhash_valid(int fhash, int t) {
     return true;
 }
 
+int check_fhash_input(kmu_ctx *ctx, int kmer_type, int fhash, int input_kind) {
+    if (!fhash_valid(fhash, kmer_type)) return fail(ctx, KMU_E_BAD_ARG, "fhash %d not valid for kmer_type %d", fhash, kmer_type);
+    if (input_kind == KMU_INPUT_PACKED2 && (kmer_is_aa(kmer_type) || fhash == KMU_FHASH_CANON_NTHASH_8B))
+        return fail(ctx, KMU_E_BAD_ARG, "packed input not valid for this kmer_type / fhash");
+    return KMU_OK;
+}
+
+int check_hash_params(kmu_ctx *ctx, const kmu_hash_params *p) {
+    KMU_TRY(check_kmer(ctx, p->kmer_type, p->kmer_size));
+    return check_fhash_input(ctx, p->kmer_type, p->fhash, p->input_kind);
+}
+
 int stage_sequences(kmu_ctx *ctx, const uint8_t *bases, const uint64_t *offsets, const uint64_t *packed_offsets,
                     uint32_t n_seq, int input_kind, int mem, DevSeqs *out) {
     if (!offsets || (!bases && n_seq)) return fail(ctx, KMU_E_BAD_ARG, "null sequence buffers");
@@ -491,10 +503,7 @@ static int kmer_hashes_impl(kmu_ctx *ctx, const kmu_hash_params *p, const uint8_
                             const uint64_t *packed_offsets, uint32_t n_seq, const uint64_t *range_begin,
                             const uint64_t *range_end, uint64_t *out) {
     if (!ctx || !p || !out) return KMU_E_BAD_ARG;
-    KMU_TRY(check_kmer(ctx, p->kmer_type, p->kmer_size));
-    if (!fhash_valid(p->fhash, p->kmer_type)) return fail(ctx, KMU_E_BAD_ARG, "fhash %d not valid for kmer_type %d", p->fhash, p->kmer_type);
-    if (p->input_kind == KMU_INPUT_PACKED2 && (kmer_is_aa(p->kmer_type) || p->fhash == KMU_FHASH_CANON_NTHASH_8B))
-        return fail(ctx, KMU_E_BAD_ARG, "packed input not valid for this kmer_type / fhash");
+    KMU_TRY(check_hash_params(ctx, p));
     KMU_HIP(ctx, hipSetDevice(ctx->device));
     const uint64_t *d_rb = range_begin, *d_re = range_end;
     if (range_begin && p->mem == KMU_MEM_HOST) {
@@ -539,8 +548,7 @@ static int kmer_hashes_impl(kmu_ctx *ctx, const kmu_hash_params *p, const uint8_
     KMU_HIP(ctx, hipGetLastError());
     if (p->mem == KMU_MEM_HOST)
         KMU_HIP(ctx, hipMemcpyAsync(out + off0, d_out, (size_t) total * 8, hipMemcpyDeviceToHost, ctx->stream));
-    if (!(p->mem == KMU_MEM_DEVICE && ctx->async_device)) KMU_TRY(check_err_word(ctx, d_err));
-    return finish_call(ctx, p->mem);
+    return finish_checked(ctx, p->mem, d_err);
 }
 
 int kmu_kmer_hashes(kmu_ctx *ctx, const kmu_hash_params *p, const uint8_t *bases, const uint64_t *offsets,

@@ -445,8 +445,7 @@ int add_entries(kmu_counter *c, const uint64_t *kmers, const uint32_t *counts, u
         if (force && !strcmp(force, "partitioned")) partitioned = !counts;
         if (partitioned) {
             KMU_TRY(partitioned_add_kmers(c, d_k, n, d_err));
-            if (!(mem == KMU_MEM_DEVICE && ctx->async_device)) KMU_TRY(check_err_word(ctx, d_err));
-            return finish_call(ctx, mem);
+            return finish_checked(ctx, mem, d_err);
         }
     }
     KMU_TRY(materialize(c));
@@ -456,8 +455,7 @@ int add_entries(kmu_counter *c, const uint64_t *kmers, const uint32_t *counts, u
                            table_of(c), d_err);
     }
     KMU_HIP(ctx, hipGetLastError());
-    if (!(mem == KMU_MEM_DEVICE && ctx->async_device)) KMU_TRY(check_err_word(ctx, d_err));
-    return finish_call(ctx, mem);
+    return finish_checked(ctx, mem, d_err);
 }
 
 // the k-mers of n_rec super-k-mer records in device memory (kmu_smer.h: what the owner of a key range receives) into this
@@ -673,16 +671,14 @@ int kmu_count_add_reads(kmu_counter *c, const uint8_t *bases, const uint64_t *of
         if (n_seq) KMU_TRY(flat_stream_extent(ctx, offsets, n_seq, mem, ds, &total_bases));
         KMU_TRY(dist_add_begin(c, ds, total_bases, d_err));
         KMU_TRY(dist_add_end(c));
-        if (!(mem == KMU_MEM_DEVICE && ctx->async_device)) KMU_TRY(check_err_word(ctx, d_err));
-        return finish_call(ctx, mem);
+        return finish_checked(ctx, mem, d_err);
     }
     if (n_seq) {
         uint64_t total_bases = 0;
         if (!ds.packed) KMU_TRY(flat_stream_extent(ctx, offsets, n_seq, mem, ds, &total_bases));
         KMU_TRY(local_add(c, ds, total_bases, d_err));
     }
-    if (!(mem == KMU_MEM_DEVICE && ctx->async_device)) KMU_TRY(check_err_word(ctx, d_err));
-    return finish_call(ctx, mem);
+    return finish_checked(ctx, mem, d_err);
 }
 
 int kmu_count_add_kmers(kmu_counter *c, const uint64_t *canon_kmers, uint64_t n, int mem) {

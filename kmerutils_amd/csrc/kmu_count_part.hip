@@ -1615,7 +1615,7 @@ static int partition_by_plan(kmu_ctx *ctx, const uint64_t *in, uint64_t n, const
 }
 
 // Partition a device array of u64 keys by the top `region_bits` bits of khash(key) into 2^region_bits leaves (<= 22 bits: two
-// 11-bit passes): the sketch path's partition of pre-hashed values (kmu_sketch.hip)
+// 11-bit passes): the sketch path's partition of pre-hashed values (sketch_all_hashed, kmu_sketch.hip)
 int partition_u64(kmu_ctx *ctx, const uint64_t *in, uint64_t n, int region_bits, const uint64_t **items_out,
                   const uint64_t **bounds_out, bool hashed_out) {
     if (region_bits > 22) return fail(ctx, KMU_E_UNSUPPORTED, "too many partitions (2^%d)", region_bits);

@@ -185,6 +185,11 @@ int finish_call(kmu_ctx *ctx, int mem);
 enum : uint32_t { DERR_NON_ACGT = 1u, DERR_TABLE_FULL = 2u, DERR_BAD_AA = 4u, DERR_EMPTY_SEQ = 8u, DERR_BAD_RANGE = 16u };
 int get_err_word(kmu_ctx *ctx, uint32_t **out); // zeroed on the stream
 int check_err_word(kmu_ctx *ctx, uint32_t *d_err);
+// the end of a call whose kernels had the error word: read it (an asynchronous device call leaves that to a later one), finish_call
+inline int finish_checked(kmu_ctx *ctx, int mem, uint32_t *d_err) {
+    if (!(mem == KMU_MEM_DEVICE && ctx->async_device)) KMU_TRY(check_err_word(ctx, d_err));
+    return finish_call(ctx, mem);
+}
 
 void comm_free(kmu_ctx *ctx); // kmu_comm.hip
 // kmu_count.hip, for kmu_sketch_count
@@ -200,6 +205,10 @@ int check_kmer(kmu_ctx *ctx, int kmer_type, int k);
 inline bool kmer_is_aa(int t) { return t == KMU_KMERAA32BIT || t == KMU_KMERAA64BIT; }
 inline int kmer_val_bytes(int t) { return (t == KMU_KMER64BIT || t == KMU_KMERAA64BIT) ? 8 : 4; }
 bool fhash_valid(int fhash, int kmer_type);
+// fhash_valid, and packed (2-bit) input only where the k-mer type and the fhash are defined on it
+int check_fhash_input(kmu_ctx *ctx, int kmer_type, int fhash, int input_kind);
+// check_kmer and check_fhash_input of a call that takes kmu_hash_params
+int check_hash_params(kmu_ctx *ctx, const kmu_hash_params *p);
 
 // exclusive scan of n u32 values into u64 offsets, out[n] = total (kmu_ingest.hip)
 int device_scan_u32(kmu_ctx *ctx, const uint32_t *in, uint64_t n, uint64_t *out);

@@ -15,15 +15,11 @@
 #include <vector>
 
 #include "kmu_ctx.hpp"
+#include "kmu_sketch_host.hpp"
 #include "kmu_smer.hpp"
 #include "kmu_stream.h"
 
 namespace kmu {
-
-__global__ void k_nk_scan(const uint64_t *offsets, uint32_t n_seq, int k, uint64_t *koff, uint32_t *err);
-__global__ void k_seq_hashes_compact(const uint8_t *bases, const uint64_t *offsets, const uint64_t *packed_offsets, uint32_t n_seq,
-                                     int packed, uint64_t total, KmerCfg cfg, const uint64_t *koff, uint64_t *out, uint32_t *err,
-                                     int spread);
 
 // ------------------------------------------------------------------------------------------------------------------------
 // k-mer distribution
@@ -461,18 +457,14 @@ extern "C" int kmu_nthash(kmu_ctx *ctx, const kmu_nthash_params *p, const uint8_
         KMU_HIP(ctx, hipMemcpyAsync(hashes_out + off0 * p->n_hashes, d_out, (size_t) total * 8 * p->n_hashes, hipMemcpyDeviceToHost, ctx->stream));
         if (strand_out) KMU_HIP(ctx, hipMemcpyAsync(strand_out + off0, d_strand, (size_t) total, hipMemcpyDeviceToHost, ctx->stream));
     }
-    if (!(p->mem == KMU_MEM_DEVICE && ctx->async_device)) KMU_TRY(check_err_word(ctx, d_err));
-    return finish_call(ctx, p->mem);
+    return finish_checked(ctx, p->mem, d_err);
 }
 
 extern "C" int kmu_kmer_distribution(kmu_ctx *ctx, const kmu_hash_params *p, const uint8_t *bases, const uint64_t *offsets,
                                      const uint64_t *packed_offsets, uint32_t n_seq, uint64_t *kmers_out, uint32_t *mult_out,
                                      uint64_t cap, uint64_t *dist_offsets_out, uint64_t *n_out) {
     if (!ctx || !p || !n_out || (kmers_out && !mult_out)) return KMU_E_BAD_ARG;
-    KMU_TRY(check_kmer(ctx, p->kmer_type, p->kmer_size));
-    if (!fhash_valid(p->fhash, p->kmer_type)) return fail(ctx, KMU_E_BAD_ARG, "fhash %d not valid for kmer_type %d", p->fhash, p->kmer_type);
-    if (p->input_kind == KMU_INPUT_PACKED2 && (kmer_is_aa(p->kmer_type) || p->fhash == KMU_FHASH_CANON_NTHASH_8B))
-        return fail(ctx, KMU_E_BAD_ARG, "packed input not valid for this kmer_type / fhash");
+    KMU_TRY(check_hash_params(ctx, p));
     KMU_HIP(ctx, hipSetDevice(ctx->device));
     *n_out = 0;
     if (n_seq == 0) {
@@ -483,21 +475,10 @@ extern "C" int kmu_kmer_distribution(kmu_ctx *ctx, const kmu_hash_params *p, con
     KMU_TRY(stage_sequences(ctx, bases, offsets, packed_offsets, n_seq, p->input_kind, p->mem, &ds));
     uint32_t *d_err;
     KMU_TRY(get_err_word(ctx, &d_err));
-    void *koff, *vals, *passes, *item_off, *nd, *tk, *tc, *doff, *queue;
-    KMU_TRY(dev_buf(ctx, "all.koff", ((size_t) n_seq + 1) * 8, &koff));
-    hipLaunchKernelGGL(k_nk_scan, dim3(1), dim3(1024), 0, ctx->stream, ds.offsets, n_seq, p->kmer_size, (uint64_t *) koff, d_err);
+    void *passes, *item_off, *nd, *tk, *tc, *doff, *queue;
+    const uint64_t *koff, *vals;
     uint64_t n_kmers = 0;
-    KMU_HIP(ctx, hipMemcpyAsync(&n_kmers, (uint64_t *) koff + n_seq, 8, hipMemcpyDeviceToHost, ctx->stream));
-    KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    KMU_TRY(dev_buf(ctx, "all.hashes", n_kmers * 8 + 64, &vals));
-    {
-        KmerCfg cfg{p->kmer_type, p->kmer_size, p->fhash};
-        const int spread = n_seq < (uint32_t) ctx->num_cus * 4 ? 1 : 0;
-        const int grid = spread ? ctx->num_cus * 8 : (int) std::min<uint32_t>(n_seq, (uint32_t) ctx->num_cus * 8);
-        KernelTimer t(ctx, "k_seq_hashes_compact");
-        hipLaunchKernelGGL(k_seq_hashes_compact, dim3(grid), dim3(256), 0, ctx->stream, ds.bases, ds.offsets, ds.packed_offsets,
-                           n_seq, ds.packed, ds.total_bytes, cfg, (const uint64_t *) koff, (uint64_t *) vals, d_err, spread);
-    }
+    KMU_TRY(hash_all_kmers(ctx, ds, KmerCfg{p->kmer_type, p->kmer_size, p->fhash}, d_err, &koff, &vals, &n_kmers));
     KMU_TRY(dev_buf(ctx, "dist.passes", ((size_t) n_seq + 1) * 4, &passes));
     KMU_TRY(dev_buf(ctx, "dist.item_off", ((size_t) n_seq + 1) * 8, &item_off));
     KMU_TRY(dev_buf(ctx, "dist.nd", ((size_t) n_seq + 1) * 4, &nd));
@@ -508,7 +489,7 @@ extern "C" int kmu_kmer_distribution(kmu_ctx *ctx, const kmu_hash_params *p, con
     KMU_HIP(ctx, hipMemsetAsync(nd, 0, ((size_t) n_seq + 1) * 4, ctx->stream));
     KMU_HIP(ctx, hipMemsetAsync(queue, 0, 64, ctx->stream));
     const int grid_s = (int) std::min<uint64_t>(((uint64_t) n_seq + 255) / 256, (uint64_t) ctx->num_cus * 8);
-    hipLaunchKernelGGL(k_dist_plan, dim3(grid_s), dim3(256), 0, ctx->stream, (const uint64_t *) koff, n_seq, (uint32_t *) passes);
+    hipLaunchKernelGGL(k_dist_plan, dim3(grid_s), dim3(256), 0, ctx->stream, koff, n_seq, (uint32_t *) passes);
     KMU_TRY(device_scan_u32(ctx, (const uint32_t *) passes, n_seq, (uint64_t *) item_off));
     uint64_t n_items = 0;
     KMU_HIP(ctx, hipMemcpyAsync(&n_items, (uint64_t *) item_off + n_seq, 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -516,7 +497,7 @@ extern "C" int kmu_kmer_distribution(kmu_ctx *ctx, const kmu_hash_params *p, con
     if (n_items) {
         const int grid = (int) std::min<uint64_t>(n_items, (uint64_t) ctx->num_cus * 3);
         KernelTimer t(ctx, "k_kmer_dist");
-        hipLaunchKernelGGL(k_kmer_dist, dim3(grid), dim3(DIST_THREADS), 0, ctx->stream, (const uint64_t *) vals, (const uint64_t *) koff,
+        hipLaunchKernelGGL(k_kmer_dist, dim3(grid), dim3(DIST_THREADS), 0, ctx->stream, vals, koff,
                            (const uint64_t *) item_off, n_seq, n_items, (uint64_t *) tk, (uint32_t *) tc, (uint32_t *) nd,
                            (unsigned long long *) queue, d_err);
     }
@@ -544,7 +525,7 @@ extern "C" int kmu_kmer_distribution(kmu_ctx *ctx, const kmu_hash_params *p, con
     if (n_pairs) {
         const int grid = (int) std::min<uint32_t>(n_seq, (uint32_t) ctx->num_cus * 8);
         hipLaunchKernelGGL(k_dist_compact, dim3(grid), dim3(256), 0, ctx->stream, (const uint64_t *) tk, (const uint32_t *) tc,
-                           (const uint64_t *) koff, (const uint64_t *) doff, n_seq, d_k, d_c);
+                           koff, (const uint64_t *) doff, n_seq, d_k, d_c);
     }
     KMU_HIP(ctx, hipGetLastError());
     if (p->mem == KMU_MEM_HOST) {

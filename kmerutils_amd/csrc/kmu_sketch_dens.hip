@@ -21,7 +21,7 @@
 #include <algorithm>
 #include <vector>
 
-#include "kmu_ctx.hpp"
+#include "kmu_sketch_host.hpp"
 #include "kmu_stream.h"
 
 namespace kmu {
@@ -472,7 +472,7 @@ int launch_dens(kmu_ctx *ctx, const kmu_sketch_params *p, const DevSeqs &ds, voi
     a.val_w32 = kmer_val_bytes(p->kmer_type) == 4;
     a.rev = p->algo == KMU_ALGO_REVOPTDENS;
     a.hll = p->algo == KMU_ALGO_HLL;
-    a.sig_bytes = p->sig_type == KMU_SIG_U16 ? 2 : (p->sig_type == KMU_SIG_U32 || p->sig_type == KMU_SIG_F32) ? 4 : 8;
+    a.sig_bytes = (int) sig_elem_bytes(p->sig_type);
     a.idx_thresh = (0u - (uint32_t) a.m) % (uint32_t) a.m;
     a.idx_zone = 0xFFFFFFFFFFFFFFFFull - (0xFFFFFFFFFFFFFFFFull - (uint64_t) a.m + 1ull) % (uint64_t) a.m;
     if (a.hll) { // SetSketchParams of the context; 1 / ln b with the kernels' own logarithm (same formula on the host)
@@ -581,7 +581,7 @@ int launch_dens_merge(kmu_ctx *ctx, const kmu_sketch_params *p, const uint64_t *
     a.f32 = p->sig_type == KMU_SIG_F32;
     a.rev = p->algo == KMU_ALGO_REVOPTDENS;
     a.hll = p->algo == KMU_ALGO_HLL;
-    a.sig_bytes = p->sig_type == KMU_SIG_U16 ? 2 : (p->sig_type == KMU_SIG_U32 || p->sig_type == KMU_SIG_F32) ? 4 : 8;
+    a.sig_bytes = (int) sig_elem_bytes(p->sig_type);
     a.sig_out = d_sig;
     const size_t lds_full = ((size_t) 8 * a.m + 4 * ((size_t) (a.m + 31) / 32) + 16 + (a.rev ? (size_t) 4 * a.m : 0) + 15) & ~(size_t) 15;
     if (lds_full > 160 * 1024) return fail(ctx, KMU_E_UNSUPPORTED, "sketch_size %d: the bins do not fit the LDS", a.m);

@@ -16,18 +16,10 @@
 #include <algorithm>
 #include <vector>
 
+#include "kmu_sketch_host.hpp"
 #include "kmu_sketch_kernels.h"
 
 namespace kmu {
-
-int launch_super(kmu_ctx *ctx, const kmu_sketch_params *p, const DevSeqs &ds, void *d_sig, uint32_t *d_err, const void *hashed,
-                 int hashed_bytes, uint64_t *part_rows);
-int launch_dens(kmu_ctx *ctx, const kmu_sketch_params *p, const DevSeqs &ds, void *d_sig, uint32_t *d_err, const void *hashed,
-                int hashed_bytes);
-// kmu_sketch.hip
-int sketch_groups_params(kmu_ctx *ctx, const kmu_sketch_params *p_in, kmu_sketch_params *p);
-int launch_pmh3a_leaves(kmu_ctx *ctx, const kmu_sketch_params *p, const uint64_t *items, const uint64_t *bounds, uint32_t n_leaves,
-                        uint64_t *part_h, uint64_t *part_k, uint32_t *d_err);
 
 static constexpr uint64_t GRP_H_INIT = 0x7FEFFFFFFFFFFFFFull; // an empty slot of k_sketch_pmh3a's partial rows: bits of f64::MAX
 static constexpr uint32_t GRP_TILE = 4096;                    // keys a workgroup takes at a time: 16 per thread
@@ -42,17 +34,6 @@ struct GroupArgs {
     uint32_t n_groups;
 };
 
-// leaves of ~4k keys: the rule of sketch_all_hashed
-__device__ __forceinline__ uint32_t grp_leaf_bits(uint64_t n) {
-    uint32_t b = 0;
-    while (b < 22 && (n >> b) > 4096) b++;
-    return b;
-}
-// chunks of a SuperMinHash group: the rule of sketch_all_hashed
-__device__ __forceinline__ uint64_t grp_chunks(uint64_t n) {
-    const uint64_t c = (n + 16383) / 16384;
-    return c < 1 ? 1 : (c > 8192 ? 8192 : c);
-}
 // leaf of a key inside its group (b >= 1): the top bits of a 64-bit finaliser (MurmurHash3's)
 __device__ __forceinline__ uint32_t grp_bucket(uint64_t x, uint32_t b) {
     x ^= x >> 33;
@@ -118,9 +99,9 @@ __global__ void __launch_bounds__(1024) k_group_plan(const uint64_t *go, uint32_
             const uint64_t n = k1 > k0 ? k1 - k0 : 0;
             gk[g] = k0;
             if (g == n_groups - 1) gk[n_groups] = k1;
-            if (super) v = grp_chunks(n);
+            if (super) v = super_chunk_count(n);
             else {
-                const uint32_t b = grp_leaf_bits(n);
+                const uint32_t b = pmh_leaf_bits(n);
                 bits[g] = b;
                 v = 1ull << b;
             }
@@ -394,16 +375,16 @@ static int groups_batched(kmu_ctx *ctx, const kmu_sketch_params *p, const DevSeq
     const uint32_t n_seq = ds.n_seq;
     const int m = p->sketch_size;
     const bool super = p->algo != KMU_ALGO_PROB3A;
-    void *koff, *gk, *lbase, *bits, *head, *hk;
-    KMU_TRY(dev_buf(ctx, "all.koff", ((size_t) n_seq + 1) * 8, &koff));
+    void *gk, *lbase, *bits, *head, *hk;
+    const uint64_t *koff;
     KMU_TRY(dev_buf(ctx, "grp.gk", ((size_t) n_groups + 1) * 8, &gk));
     KMU_TRY(dev_buf(ctx, "grp.leaf_base", ((size_t) n_groups + 1) * 8, &lbase));
     KMU_TRY(dev_buf(ctx, "grp.bits", (size_t) n_groups * 4, &bits));
     KMU_TRY(dev_buf(ctx, "grp.head", 64, &head));
-    hipLaunchKernelGGL(k_nk_scan, dim3(1), dim3(1024), 0, ctx->stream, ds.offsets, n_seq, p->kmer_size, (uint64_t *) koff, d_err);
+    KMU_TRY(launch_nk_scan(ctx, ds, p->kmer_size, d_err, &koff));
     {
         KernelTimer t(ctx, "k_group_plan");
-        hipLaunchKernelGGL(k_group_plan, dim3(1), dim3(1024), 0, ctx->stream, d_go, n_groups, n_seq, (const uint64_t *) koff, super ? 1 : 0,
+        hipLaunchKernelGGL(k_group_plan, dim3(1), dim3(1024), 0, ctx->stream, d_go, n_groups, n_seq, koff, super ? 1 : 0,
                            (uint64_t *) gk, (uint64_t *) lbase, (uint32_t *) bits, (uint64_t *) head);
     }
     KMU_HIP(ctx, hipGetLastError());
@@ -417,15 +398,7 @@ static int groups_batched(kmu_ctx *ctx, const kmu_sketch_params *p, const DevSeq
     const uint64_t n_items = h_head[0], n_leaves = h_head[1];
     if (n_leaves > 0x7FFFFFFFull) return fail(ctx, KMU_E_UNSUPPORTED, "%llu leaves in one call", (unsigned long long) n_leaves);
     KMU_TRY(dev_buf(ctx, "all.hashes", n_items * 8 + 64, &hk));
-    if (n_seq) {
-        KmerCfg cfg{p->kmer_type, p->kmer_size, p->fhash};
-        const int spread = n_seq < (uint32_t) ctx->num_cus * 4 ? 1 : 0;
-        const int grid = spread ? ctx->num_cus * 8 : (int) std::min<uint32_t>(n_seq, (uint32_t) ctx->num_cus * 8);
-        KernelTimer t(ctx, "k_seq_hashes_compact");
-        hipLaunchKernelGGL(k_seq_hashes_compact, dim3(grid), dim3(256), 0, ctx->stream, ds.bases, ds.offsets, ds.packed_offsets, n_seq,
-                           ds.packed, ds.total_bytes, cfg, (const uint64_t *) koff, (uint64_t *) hk, d_err, spread);
-    }
-    KMU_HIP(ctx, hipGetLastError());
+    KMU_TRY(launch_hashes_compact(ctx, ds, KmerCfg{p->kmer_type, p->kmer_size, p->fhash}, koff, (uint64_t *) hk, d_err));
     GroupArgs ga{(const uint64_t *) gk, (const uint64_t *) lbase, (const uint32_t *) bits, n_groups};
     const unsigned tile_grid = (unsigned) std::max<uint64_t>(1, std::min<uint64_t>((n_items + GRP_TILE - 1) / GRP_TILE, (uint64_t) ctx->num_cus * 8));
     const unsigned slot_tiles = (unsigned) std::min<uint32_t>(65535u, ((uint32_t) m + 63u) / 64u);
@@ -469,19 +442,12 @@ static int groups_batched(kmu_ctx *ctx, const kmu_sketch_params *p, const DevSeq
     hipLaunchKernelGGL(k_grp_chunk_offsets, dim3(std::max<uint32_t>(1, std::min<uint32_t>((n_groups + 3) / 4, (uint32_t) ctx->num_cus * 8))), dim3(256), 0,
                        ctx->stream, ga, (uint64_t *) d_off);
     KMU_HIP(ctx, hipGetLastError());
-    DevSeqs chunks;
-    chunks.bases = reinterpret_cast<const uint8_t *>(hk);
-    chunks.offsets = (const uint64_t *) d_off;
-    chunks.n_seq = (uint32_t) n_leaves;
-    chunks.total_bytes = 1;
-    KMU_TRY(launch_super(ctx, p, chunks, nullptr, d_err, hk, 8, (uint64_t *) pr));
-    const int mode = p->algo == KMU_ALGO_SUPER ? (p->sig_type == KMU_SIG_F32 ? 1 : 0) : (p->sig_type == KMU_SIG_U32 ? 3 : 2);
-    // the initial slot patterns of k_sketch_super (super_init_bits): F::from(u32::MAX) as f64 / f32, all ones of u64 / u32
-    const uint64_t init_bits = mode == 0 ? 0x41EFFFFFFFE00000ull : mode == 1 ? 0x4F800000ull : mode == 2 ? 0xFFFFFFFFFFFFFFFFull : 0xFFFFFFFFull;
+    KMU_TRY(launch_super(ctx, p, hashed_seqs(hk, (const uint64_t *) d_off, (uint32_t) n_leaves), nullptr, d_err, hk, 8, (uint64_t *) pr));
+    const int mode = super_mode(p);
     {
         KernelTimer t(ctx, "k_super_reduce_groups");
         hipLaunchKernelGGL(k_super_reduce_groups, dim3(n_groups, (unsigned) std::min<uint32_t>(65535u, ((uint32_t) m + 255u) / 256u)), dim3(256), 0,
-                           ctx->stream, (const uint64_t *) pr, (const uint64_t *) lbase, m, mode, init_bits, d_sig);
+                           ctx->stream, (const uint64_t *) pr, (const uint64_t *) lbase, m, mode, super_init_bits(mode), d_sig);
     }
     KMU_HIP(ctx, hipGetLastError());
     return KMU_OK;
@@ -491,8 +457,9 @@ extern "C" int kmu_sketch_groups(kmu_ctx *ctx, const kmu_sketch_params *p_in, co
                                  const uint64_t *packed_offsets, uint32_t n_seq, const uint64_t *group_offsets, uint32_t n_groups,
                                  void *sig_out) {
     if (!ctx || !p_in || !sig_out || !group_offsets) return KMU_E_BAD_ARG;
-    kmu_sketch_params p_res;
-    KMU_TRY(sketch_groups_params(ctx, p_in, &p_res));
+    kmu_sketch_params p_all = *p_in, p_res; // the checks kmu_sketch makes of an ALL_SEQS call, in its order and with its texts
+    p_all.mode = KMU_MODE_ALL_SEQS;
+    KMU_TRY(sketch_params(ctx, &p_all, &p_res));
     const kmu_sketch_params *p = &p_res;
     if (p->mem != KMU_MEM_HOST && p->mem != KMU_MEM_DEVICE) return fail(ctx, KMU_E_BAD_ARG, "bad mem %d", p->mem);
     if (!offsets || (!bases && n_seq)) return fail(ctx, KMU_E_BAD_ARG, "null sequence buffers");
@@ -505,8 +472,7 @@ extern "C" int kmu_sketch_groups(kmu_ctx *ctx, const kmu_sketch_params *p_in, co
     KMU_HIP(ctx, hipSetDevice(ctx->device));
     DevSeqs ds;
     KMU_TRY(stage_sequences(ctx, bases, offsets, packed_offsets, n_seq, p->input_kind, p->mem, &ds));
-    const size_t sigb = p->sig_type == KMU_SIG_U16 ? 2 : (p->sig_type == KMU_SIG_U32 || p->sig_type == KMU_SIG_F32) ? 4 : 8;
-    const size_t row_bytes = (size_t) p->sketch_size * sigb;
+    const size_t row_bytes = (size_t) p->sketch_size * sig_elem_bytes(p->sig_type);
     void *d_sig = sig_out;
     const uint64_t *d_go = group_offsets;
     if (host) {
@@ -519,10 +485,8 @@ extern "C" int kmu_sketch_groups(kmu_ctx *ctx, const kmu_sketch_params *p_in, co
     }
     uint32_t *d_err;
     KMU_TRY(get_err_word(ctx, &d_err));
-    const bool dens = p->algo == KMU_ALGO_OPTDENS || p->algo == KMU_ALGO_REVOPTDENS || p->algo == KMU_ALGO_HLL;
-    if (dens) KMU_TRY(groups_dens(ctx, p, ds, host ? group_offsets : nullptr, d_go, n_groups, (uint8_t *) d_sig, row_bytes, d_err));
+    if (algo_is_dens(p->algo)) KMU_TRY(groups_dens(ctx, p, ds, host ? group_offsets : nullptr, d_go, n_groups, (uint8_t *) d_sig, row_bytes, d_err));
     else KMU_TRY(groups_batched(ctx, p, ds, d_go, n_groups, d_sig, d_err));
     if (host) KMU_HIP(ctx, hipMemcpyAsync(sig_out, d_sig, (size_t) n_groups * row_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    if (!(p->mem == KMU_MEM_DEVICE && ctx->async_device)) KMU_TRY(check_err_word(ctx, d_err));
-    return finish_call(ctx, p->mem);
+    return finish_checked(ctx, p->mem, d_err);
 }

@@ -1,4 +1,4 @@
-// kmu_sketch_kernels.h -- what the host side of the sketch path (kmu_sketch.hip: routes, launches, the C entry points) needs of
+// kmu_sketch_kernels.h -- what the host side of the sketch path (kmu_sketch_pmh.hip: routes, launches; kmu_sketch.hip: the C entry points) needs of
 // the per-sequence sketch kernels (kmu_sketch_kernels.hip): their argument block, the constants their LDS budgets are made of,
 // and their declarations (the template kernels are instantiated in kmu_sketch_kernels.hip for exactly the forms listed here).
 #pragma once

@@ -15,7 +15,7 @@
 // a second LDS column: with it a wave took 16 KiB at m = 128 and a CU held eight waves.)
 #include <algorithm>
 
-#include "kmu_ctx.hpp"
+#include "kmu_sketch_host.hpp"
 #include "kmu_stream.h"
 
 namespace kmu {
@@ -44,14 +44,6 @@ struct SuperArgs {
     uint32_t *err;
 };
 
-__device__ __forceinline__ uint64_t super_init_bits(int mode) {
-    switch (mode) {
-    case 0: return (uint64_t) __double_as_longlong(4294967295.0); // F::from(u32::MAX)
-    case 1: return (uint64_t) __float_as_uint(4294967296.0f);
-    case 2: return 0xFFFFFFFFFFFFFFFFull;
-    default: return 0xFFFFFFFFull;
-    }
-}
 // min(floor(value), m-1) of a slot bit pattern
 __device__ __forceinline__ uint32_t super_floor(uint64_t bits, int mode, int m, int lg) {
     uint32_t f;
@@ -266,7 +258,7 @@ __global__ void __launch_bounds__(256) k_super_reduce(const uint64_t *part_rows,
 }
 
 int launch_super_reduce(kmu_ctx *ctx, const kmu_sketch_params *p, const uint64_t *part_rows, uint64_t n_parts, void *d_sig) {
-    int mode = p->algo == KMU_ALGO_SUPER ? (p->sig_type == KMU_SIG_F32 ? 1 : 0) : (p->sig_type == KMU_SIG_U32 ? 3 : 2);
+    const int mode = super_mode(p);
     KernelTimer t(ctx, "k_super_reduce");
     hipLaunchKernelGGL(k_super_reduce, dim3((p->sketch_size + 255) / 256), dim3(256), 0, ctx->stream, part_rows, n_parts,
                        p->sketch_size, mode, d_sig, ctx->partial_out);
@@ -293,8 +285,7 @@ int launch_super(kmu_ctx *ctx, const kmu_sketch_params *p, const DevSeqs &ds, vo
     while ((1 << a.lg) < a.m) a.lg++;
     a.hasher = p->hasher;
     a.rand08 = (p->flags & KMU_FLAG_RAND08) ? 1 : 0;
-    if (p->algo == KMU_ALGO_SUPER) a.mode = p->sig_type == KMU_SIG_F32 ? 1 : 0;
-    else a.mode = p->sig_type == KMU_SIG_U32 ? 3 : 2;
+    a.mode = super_mode(p);
     a.val_w32 = kmer_val_bytes(p->kmer_type) == 4;
     a.sig_out = d_sig;
     a.err = d_err;

@@ -1,5 +1,6 @@
 // Host-only code of include/kmerutils.hpp under AddressSanitizer + UndefinedBehaviorSanitizer (`make sanitize`; no GPU, no
-// libkmu call): packed sequences, k-mer values, parameter files, the signature dump writer / reader, the k-mer count reloader.
+// libkmu call): packed sequences, k-mer values, parameter files, the signature dump writer / reader, the k-mer count reloader,
+// and the chunk plan of kmu_sketch_count's host pipeline (kmerutils_amd/csrc/kmu_pipe_plan.hpp, host arithmetic of libkmu).
 // The reference leans on Rust ownership and bounds checks for these (src/base/sequence.rs, src/sketching/seqsketchjaccard.rs:385-712,
 // src/base/kmercount.rs:1148-1503); this side is C++ and gets the sanitizers instead.
 #include <cstdio>
@@ -8,6 +9,7 @@
 #include <string>
 
 #include "../../include/kmerutils.hpp"
+#include "../../kmerutils_amd/csrc/kmu_pipe_plan.hpp"
 
 using namespace kmerutils;
 
@@ -151,6 +153,63 @@ int main(int argc, char **argv) {
         CHECK(r && r->kmers().size() == 3 && !r->get_multi_kmer_counts());
         auto p = r ? r->get_coord_from_rank(2) : std::nullopt;
         CHECK(p && !r->get_coord_from_rank(3));
+    }
+    // ---- the chunk plan of kmu_sketch_count's host pipeline (kmu_pipe_plan.hpp) ----
+    {
+        using kmu::pipe_chunk_plan;
+        std::vector<uint32_t> cut;
+        std::vector<uint64_t> pk;
+        auto offsets_of = [](const std::vector<uint64_t> &len) {
+            std::vector<uint64_t> h(1, 0);
+            for (uint64_t l : len) h.push_back(h.back() + l);
+            return h;
+        };
+        // random read-length sets: empty reads, a single read longer than every target, n_seq of 0 and 1, growth 1 and 3
+        for (int it = 0; it < 4000; it++) {
+            const uint32_t n_seq = it < 40 ? uint32_t(it & 1) : uint32_t(rng() % 60);
+            std::vector<uint64_t> len(n_seq);
+            for (auto &l : len) l = rng() % 4 == 0 ? 0 : rng() % (1 + rng() % 6000);
+            if (n_seq && it % 5 == 0) len[rng() % n_seq] = 200000 + rng() % 100000;  // longer than every target below
+            const std::vector<uint64_t> h = offsets_of(len);
+            const uint64_t total = h[n_seq], chunk = 1 + rng() % 20000, growth = it & 2 ? 3 : 1;
+            pipe_chunk_plan(h, n_seq, total, chunk, growth, true, &cut, &pk);
+            CHECK(!cut.empty() && cut.front() == 0 && cut.back() == n_seq);
+            for (size_t c = 0; c + 1 < cut.size(); c++) CHECK(cut[c] < cut[c + 1]);
+            const size_t n_chunks = cut.size() - 1;
+            CHECK(n_chunks ? pk.size() == n_chunks + 1 : pk.empty());
+            if (n_chunks) CHECK(pk.front() == 0 && pk.back() == total);
+            for (size_t c = 0; c < n_chunks; c++) {
+                CHECK(pk[c] <= pk[c + 1]);
+                if (c + 1 < n_chunks) CHECK(pk[c + 1] % 16 == 0 || pk[c + 1] == total);
+                CHECK(pk[c + 1] >= std::min(total, h[cut[c + 1]]));
+            }
+            pipe_chunk_plan(h, n_seq, total, chunk, growth, false, &cut, &pk);
+            CHECK(pk.empty() && cut.back() == n_seq);
+        }
+        // the headline's 4.38 G bases as 438 000 reads of 10 000, 512 MiB chunks, growth 3: 64 MiB, 192 MiB, 576 MiB, 1 728 MiB and the
+        // rest, each ended at the first read boundary at or behind its target
+        std::vector<uint64_t> h(438000 + 1);
+        for (size_t i = 0; i < h.size(); i++) h[i] = i * 10000ull;
+        pipe_chunk_plan(h, 438000, h.back(), 512ull << 20, 3, true, &cut, &pk);
+        CHECK(cut.size() == 6);
+        uint64_t target = 0;
+        for (size_t c = 0; c + 2 < cut.size(); c++) {
+            const uint64_t mib[4] = {64, 192, 576, 1728};
+            target += mib[c] << 20;
+            CHECK(h[cut[c + 1]] >= target && h[cut[c + 1] - 1] < target);
+        }
+        // expected values generated once from the lines this function was taken from (kmu_sketch.hip before the split)
+        CHECK((cut == std::vector<uint32_t>{0u, 6711u, 26844u, 87242u, 268436u, 438000u}));
+        CHECK((pk == std::vector<uint64_t>{0ull, 67110000ull, 268440000ull, 872420000ull, 2684360000ull, 4380000000ull}));
+        pipe_chunk_plan(h, 438000, h.back(), 512ull << 20, 1, false, &cut, &pk);
+        CHECK((cut == std::vector<uint32_t>{0u, 6711u, 60623u, 114534u, 168445u, 222356u, 276267u, 330178u, 384089u, 438000u}) && pk.empty());
+        const std::vector<uint64_t> s = offsets_of({700, 0, 1300, 50, 0, 9000, 10, 10, 10, 400, 2500, 0, 1});
+        pipe_chunk_plan(s, 13, s.back(), 8192, 3, true, &cut, &pk);
+        CHECK((cut == std::vector<uint32_t>{0u, 3u, 6u, 13u}) && (pk == std::vector<uint64_t>{0ull, 2000ull, 11056ull, 13981ull}));
+        pipe_chunk_plan(s, 13, s.back(), 4096, 1, true, &cut, &pk);
+        CHECK((cut == std::vector<uint32_t>{0u, 1u, 6u, 7u, 13u}) && (pk == std::vector<uint64_t>{0ull, 704ull, 11056ull, 11072ull, 13981ull}));
+        pipe_chunk_plan(s, 13, s.back(), 2048, 2, false, &cut, &pk);
+        CHECK((cut == std::vector<uint32_t>{0u, 1u, 3u, 4u, 6u, 7u, 13u}) && pk.empty());
     }
     std::printf("%s: %d failure(s)\n", argv[0], failures);
     return failures ? 1 : 0;
