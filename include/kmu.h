@@ -296,10 +296,14 @@ int kmu_sketch(kmu_ctx *ctx, const kmu_sketch_params *p, const uint8_t *bases, c
  * allowed and gets the ALL_SEQS row of n_seq = 0.  sig_out: n_groups rows of sketch_size signatures.  n_groups == 0: KMU_OK,
  * nothing is written.  p->mode is ignored; block_size > 0 and KMU_ALGO_BOTTOMK are KMU_E_UNSUPPORTED; what the kernels find
  * (KMU_E_NON_ACGT, KMU_E_EMPTY_SEQ, ...) is reported as kmu_sketch reports it, with the same sticky rules in async_device contexts.
- * Routes:  PROB3A, PROB3, SUPER, SUPER2: one batched pass over all groups -- the kernel launches and the host synchronisations
- *          (one small device-to-host copy) of a call do not depend on n_groups.
- *          OPTDENS, REVOPTDENS, HLL (context's kmu_set_hll_params): an internal loop over the groups through the ALL_SEQS
- *          route of kmu_sketch: same rows, one round of launches per group. */
+ * Routes:  every algorithm takes one batched pass over all groups -- the kernel launches and the host synchronisations (at most
+ *          one small device-to-host copy) of a call do not depend on n_groups.
+ *          PROB3A, PROB3, SUPER, SUPER2: the k-mer hashes of all sequences, cut into leaves / chunks per group, one sketch
+ *          kernel over all of them, one reduction per group.
+ *          OPTDENS, REVOPTDENS, HLL (context's kmu_set_hll_params): no hash array; one persistent kernel walks tiles of equally
+ *          many bases of the concatenated sequences into one row of bins / registers per group (8 * sketch_size bytes of
+ *          workspace per group), one kernel densifies and stores the rows.  Neither the launches nor the load of the device
+ *          depend on how the bases are cut into sequences and groups (sequences above 2^20 k-mers included). */
 int kmu_sketch_groups(kmu_ctx *ctx, const kmu_sketch_params *p, const uint8_t *bases, const uint64_t *offsets,
                       const uint64_t *packed_offsets, uint32_t n_seq, const uint64_t *group_offsets, uint32_t n_groups,
                       void *sig_out);

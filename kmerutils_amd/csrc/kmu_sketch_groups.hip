@@ -2,7 +2,7 @@
 // kmu_sketch(KMU_MODE_ALL_SEQS) gives for the sequences of group g alone.  Reference: SeqSketcherT::sketch_compressedkmer_seqs
 // called once per genome / proteome file (src/sketching/setsketchert.rs:160-202, 299-335, 1007-1045).
 //
-// Routes (the kernel launches and host synchronisations of the first two do not depend on the number of groups):
+// Routes (the kernel launches and host synchronisations of a call do not depend on the number of groups):
 //  ProbMinHash3a / 3   k_nk_scan + k_seq_hashes_compact over all sequences (groups are runs of consecutive sequences, so the
 //                      compact hash array is already grouped), k_group_plan, a segmented partition of every group into leaves
 //                      of ~4 k keys (k_grp_hist, k_grp_bounds, k_grp_scatter), ONE k_sketch_pmh3a over the leaves of all
@@ -12,10 +12,18 @@
 //                      function of (group, key)); nothing else about the cut, nor the order inside a leaf, matters.
 //  SuperMinHash(2)     items are independent: chunks of <= 16 384 hashes that never straddle a group (k_grp_chunk_offsets),
 //                      ONE k_sketch_super over all chunks, k_super_reduce_groups.
-//  OptDens / RevOptDens / HLL   a loop over the groups through launch_dens (the ALL_SEQS route of kmu_sketch, per group).
+//  OptDens / RevOptDens / HLL   no hashes, no plan the host sees: k_grp_dens_plan checks group_offsets, flags empty sequences, fills
+//                      one row of bins / registers per group and cuts the concatenated bases into tiles of equally many bases;
+//                      ONE persistent k_grp_dens_walk takes tiles from a queue, finds the sequences and groups of a tile by binary
+//                      search, walks their steps straight from the bases (oph_walk) into bins in LDS and merges them into the
+//                      group's row whenever the group changes; k_grp_dens_finish densifies and stores row g.
+//                      Exact because a bin is a minimum and a register a maximum over independent k-mer occurrences: every step
+//                      of every sequence is walked by exactly one wave (the tile its first base lies in), and no cut or order
+//                      of minima / maxima changes them.
 #include <algorithm>
 #include <vector>
 
+#include "kmu_sketch_dens.h"
 #include "kmu_sketch_host.hpp"
 #include "kmu_sketch_kernels.h"
 
@@ -44,6 +52,7 @@ __device__ __forceinline__ uint32_t grp_bucket(uint64_t x, uint32_t b) {
     return (uint32_t) (x >> (64 - b));
 }
 // the group of item i, searched in [lo, hi] (gk[lo] <= i < gk[hi + 1]): the last g with gk[g] <= i -- never an empty group
+// (k_grp_dens_walk: also the sequence of a base in `offsets`, never an empty sequence)
 __device__ __forceinline__ uint32_t grp_of(const uint64_t *gk, uint32_t lo, uint32_t hi, uint64_t i) {
     while (lo < hi) {
         const uint32_t mid = lo + (hi - lo + 1) / 2;
@@ -330,6 +339,153 @@ __global__ void __launch_bounds__(256) k_super_reduce_groups(const uint64_t *par
     }
 }
 
+// ---- OptDens / RevOptDens / HLL ----------------------------------------------------------------------------------------------
+// head of the route (u64 words): first base, end of the bases, bases per tile, GRP_BAD_* bits
+enum { GD_BASE0 = 0, GD_END = 1, GD_TILE = 2, GD_BAD = 3, GD_WORDS = 4 };
+static constexpr uint64_t GD_TILE_MIN = 4096, GD_TILE_MAX = 1u << 17; // bases of a tile: one step per wave .. 32 per wave
+static constexpr uint32_t GD_NONE = 0xFFFFFFFFu;
+#ifndef KMU_GRP_HLL_SEED
+#define KMU_GRP_HLL_SEED 1 // (0: diagnostics, scripts/build_variant.sh -- every unit starts its K_low at 0)
+#endif
+
+// Before the walk, the whole grid: group_offsets checked (as k_group_plan checks them; nothing is read through them here), an empty
+// sequence is KMU_E_EMPTY_SEQ wherever it stands, the n_groups rows start neutral, and the tile: as many bases as give every
+// workgroup of the walk ~4 turns, a multiple of the DNA step, within [GD_TILE_MIN, GD_TILE_MAX].
+__global__ void __launch_bounds__(256) k_grp_dens_plan(const uint64_t *go, uint32_t n_groups, const uint64_t *offsets, uint32_t n_seq,
+                                                       uint64_t *rows, uint64_t n_rows_words, uint64_t neutral, uint32_t walk_grid,
+                                                       unsigned long long *head, uint32_t *err) {
+    const uint64_t tid = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x, nthreads = (uint64_t) gridDim.x * blockDim.x;
+    uint32_t e = 0;
+    for (uint64_t g = tid; g < n_groups; g += nthreads) {
+        const uint64_t s0 = go[g], s1 = go[g + 1];
+        if (g == 0 && s0 != 0) e |= GRP_BAD_START;
+        if (s1 < s0) e |= GRP_BAD_ORDER;
+        if (g == n_groups - 1 && s1 != (uint64_t) n_seq) e |= GRP_BAD_END;
+    }
+    if (e) atomicOr(&head[GD_BAD], (unsigned long long) e);
+    bool empty = false;
+    for (uint64_t i = tid; i < n_seq; i += nthreads) empty |= offsets[i + 1] == offsets[i];
+    if (empty) atomicOr(err, DERR_EMPTY_SEQ);
+    for (uint64_t i = tid; i < n_rows_words; i += nthreads) rows[i] = neutral;
+    if (tid == 0) {
+        const uint64_t b0 = offsets[0], b1 = offsets[n_seq], total = b1 > b0 ? b1 - b0 : 0, turns = (uint64_t) walk_grid * 4;
+        uint64_t tile = ((total + turns - 1) / turns + 1023) / 1024 * 1024;
+        tile = tile < GD_TILE_MIN ? GD_TILE_MIN : tile > GD_TILE_MAX ? GD_TILE_MAX : tile;
+        head[GD_BASE0] = b0;
+        head[GD_END] = b0 + total;
+        head[GD_TILE] = tile;
+    }
+}
+
+// The bins / registers of all groups.  Persistent workgroups take tiles [t0, t1) of the concatenated bases from a queue.  Step st
+// of sequence r (oph_steps: 1024 bases from base 1024 st - lead, 64 residues from residue 64 st) belongs to the tile that holds
+// its first base offsets[r] + max(0, 1024 st - lead) -- every step to exactly one tile, whatever the sequences' lengths: work is
+// cut by amount of sequence.  The four waves share the steps of a tile round-robin across sequence boundaries (`c`), so a tile of
+// many short reads keeps them all busy; they only meet where the group changes.  The bins stay in LDS across tiles while the
+// group is the same and are merged into the group's row (oph_merge_to_row) when it changes and at the end.
+// LDS: hs[m] | w[8]: w[0] this tile, w[1] K_low, w[4 .. 7] the waves' minima of the group's row.
+template <bool HLL>
+__global__ void __launch_bounds__(256) k_grp_dens_walk(DensArgs a, const uint64_t *go, uint32_t n_groups, uint64_t *rows,
+                                                       const unsigned long long *head) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    uint64_t *hs = reinterpret_cast<uint64_t *>(smem);
+    uint32_t *w = reinterpret_cast<uint32_t *>(hs + a.m);
+    const int tid = threadIdx.x, nthreads = blockDim.x;
+    const uint32_t wave = (uint32_t) tid >> 6;
+    const bool aa = a.cfg.kmer_type == KMU_KMERAA32BIT || a.cfg.kmer_type == KMU_KMERAA64BIT;
+    const uint64_t step_len = aa ? 64 : 1024;
+    const uint64_t neutral = oph_neutral(a);
+    const uint64_t base0 = head[GD_BASE0], end = head[GD_END], tile = head[GD_TILE];
+    const uint64_t n_tiles = (end - base0 + tile - 1) / tile;
+    const uint32_t n_seq = a.n_seq;
+    uint32_t cur_g = GD_NONE, bad = 0;
+    if (tid == 0) w[0] = atomicAdd(a.queue, 1u);
+    __syncthreads();
+    for (;;) {
+        const uint64_t t = w[0];
+        __syncthreads(); // everyone holds t before thread 0 posts the next one
+        if (t >= n_tiles) break;
+        uint32_t t_next = 0;
+        if (tid == 0) t_next = atomicAdd(a.queue, 1u);
+        const uint64_t t0 = base0 + t * tile, t1 = t0 + tile < end ? t0 + tile : end;
+        const uint32_t r0 = grp_of(a.offsets, 0, n_seq - 1, t0), r1 = grp_of(a.offsets, r0, n_seq - 1, t1 - 1);
+        uint32_t c = 0; // steps of this tile so far, modulo the waves
+        for (uint32_t r = r0; r <= r1;) {
+            const uint32_t g = grp_of(go, cur_g != GD_NONE ? cur_g : 0, n_groups - 1, (uint64_t) r) /* (tiles and sequences only go up) */;
+            const uint64_t g_end = go[g + 1] < (uint64_t) n_seq ? go[g + 1] : (uint64_t) n_seq; // (clamped like every index taken from go)
+            uint32_t r_end = g_end - 1 < (uint64_t) r1 ? (uint32_t) (g_end - 1) : r1;
+            r_end = r_end < r ? r : r_end;
+            if (g != cur_g) {
+                __syncthreads(); // the waves are through with the group before
+                if (cur_g != GD_NONE) {
+                    a.row = rows + (uint64_t) cur_g * a.m;
+                    oph_merge_to_row(a, hs);
+                }
+                for (int s = tid; s < a.m; s += nthreads) hs[s] = neutral; // (the entries this thread merged)
+                if constexpr (HLL) {
+                    // K_low of the new group: never the one of the group before.  Seeded with the minimum of the group's global
+                    // row as it stands -- exact: the global registers only grow, so their minimum now is a lower bound of the
+                    // final registers, and an update with k <= that bound changes none of them.  Only where other units may
+                    // have merged into the row: a group that reaches beyond this tile.
+                    uint64_t mn = 0;
+                    const uint64_t g_first = go[g] < (uint64_t) n_seq ? go[g] : (uint64_t) n_seq;
+                    if (KMU_GRP_HLL_SEED && (a.offsets[g_first] < t0 || a.offsets[g_end] > t1)) {
+                        mn = ~0ull;
+                        for (int s = tid; s < a.m; s += nthreads) {
+                            const uint64_t v = __hip_atomic_load(&rows[(uint64_t) g * a.m + s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                            mn = v < mn ? v : mn;
+                        }
+                        mn = ~wave_max_u64(~mn);
+                    }
+                    if (lane_id() == 0) w[4 + wave] = (uint32_t) mn;
+                    __syncthreads();
+                    if (tid == 0) w[1] = min(min(w[4], w[5]), min(w[6], w[7]));
+                }
+                __syncthreads();
+                cur_g = g;
+            }
+            for (uint32_t rr = r; rr <= r_end; rr++) {
+                const SeqView sv = dens_view(a, rr);
+                if (sv.len == 0) continue; // (KMU_E_EMPTY_SEQ: k_grp_dens_plan)
+                const uint64_t off = a.offsets[rr], lead = aa ? 0 : seq_lead(sv), n_st = oph_steps(sv, aa);
+                const uint64_t lo = t0 > off ? (t0 - off + lead + step_len - 1) / step_len : 0;
+                uint64_t hi = (t1 - off + lead + step_len - 1) / step_len;
+                hi = hi < n_st ? hi : n_st;
+                if (lo >= hi) continue;
+                const uint64_t nk = sv.len >= (uint64_t) a.cfg.k ? sv.len - a.cfg.k + 1 : 0; // 0: the walk only validates
+                bad |= oph_walk<HLL>(a, sv, hs, &w[1], aa, nk, lo + ((wave - c) & 3u), 4, hi);
+                c += (uint32_t) (hi - lo);
+            }
+            r = r_end + 1;
+        }
+        if (tid == 0) w[0] = t_next;
+        __syncthreads();
+    }
+    if (cur_g != GD_NONE) { // (the break above came after a barrier behind the last walk)
+        a.row = rows + (uint64_t) cur_g * a.m;
+        oph_merge_to_row(a, hs);
+    }
+    if (bad) atomicOr(a.err, aa ? DERR_BAD_AA : DERR_NON_ACGT);
+}
+
+// k_oph_finish per group: the group's row -> LDS -> densified (not HLL) -> signature row g
+__global__ void __launch_bounds__(256) k_grp_dens_finish(DensArgs a, const uint64_t *rows, uint32_t n_groups) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    uint64_t *hs;
+    uint32_t *filled, *cnt, *claim;
+    oph_lds(a, smem, hs, filled, cnt, claim);
+    for (uint32_t g = blockIdx.x; g < n_groups; g += gridDim.x) {
+        for (int s = threadIdx.x; s < a.m; s += blockDim.x) {
+            hs[s] = rows[(uint64_t) g * a.m + s];
+            if (a.rev) claim[s] = 0xFFFFFFFFu;
+        }
+        __syncthreads();
+        if (!a.hll) oph_densify(a, hs, filled, claim, cnt);
+        oph_store_row(a, hs, (uint64_t) g);
+        __syncthreads();
+    }
+}
+
 } // namespace kmu
 
 using namespace kmu;
@@ -347,25 +503,56 @@ static uint32_t groups_check_host(const uint64_t *go, uint32_t n_groups, uint32_
     return e;
 }
 
-// OptDens / RevOptDens / HLL: the ALL_SEQS route of kmu_sketch, group by group
-static int groups_dens(kmu_ctx *ctx, const kmu_sketch_params *p, const DevSeqs &ds, const uint64_t *h_go, const uint64_t *d_go,
-                       uint32_t n_groups, uint8_t *d_sig, size_t row_bytes, uint32_t *d_err) {
-    std::vector<uint64_t> tmp;
-    if (!h_go) { // device memory: the one copy of the call, checked before anything goes through it
-        tmp.resize((size_t) n_groups + 1);
-        KMU_HIP(ctx, hipMemcpyAsync(tmp.data(), d_go, ((size_t) n_groups + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
+// OptDens / RevOptDens / HLL: plan, one walk over all groups, finish.  host_checked: group_offsets were checked on the host
+// (host memory); else their check bits are the one device-to-host copy of the call.
+static int groups_dens(kmu_ctx *ctx, const kmu_sketch_params *p, const DevSeqs &ds, const uint64_t *d_go, uint32_t n_groups, void *d_sig,
+                       uint32_t *d_err, bool host_checked) {
+    DensArgs a;
+    dens_args(ctx, p, ds, d_sig, d_err, nullptr, 0, &a);
+    const void *fns[3] = {(const void *) k_grp_dens_walk<false>, (const void *) k_grp_dens_walk<true>, (const void *) k_grp_dens_finish};
+    KMU_TRY(dens_lds_check(ctx, a, fns, 3));
+    const size_t lds_full = dens_lds_full(a), lds_walk = (size_t) 8 * a.m + 32;
+    const uint64_t n_words = (uint64_t) n_groups * a.m;
+    void *rows, *head, *q;
+    KMU_TRY(dev_buf(ctx, "grp.rows", n_words * 8 + 64, &rows));
+    KMU_TRY(dev_buf(ctx, "grp.head", 64, &head));
+    KMU_TRY(dev_buf(ctx, "queue", 64, &q));
+    KMU_HIP(ctx, hipMemsetAsync(head, 0, 64, ctx->stream));
+    KMU_HIP(ctx, hipMemsetAsync(q, 0, 64, ctx->stream));
+    a.queue = (uint32_t *) q;
+    // persistent: the workgroups a CU holds, by LDS and by registers (82 VGPRs: five waves per SIMD; the HLL walk 150: three)
+    const unsigned walk_grid = (unsigned) ctx->num_cus * (unsigned) std::max<size_t>(1, std::min<size_t>(a.hll ? 3 : 5, DENS_LDS_MAX / lds_walk));
+    {
+        KernelTimer t(ctx, "k_grp_dens_plan");
+        const uint64_t work = std::max<uint64_t>(std::max<uint64_t>(n_words, ds.n_seq), n_groups);
+        hipLaunchKernelGGL(k_grp_dens_plan, dim3((unsigned) std::min<uint64_t>((work + 255) / 256, (uint64_t) ctx->num_cus * 8)), dim3(256), 0,
+                           ctx->stream, d_go, n_groups, ds.offsets, ds.n_seq, (uint64_t *) rows, n_words, dens_neutral_bits(a), walk_grid,
+                           (unsigned long long *) head, d_err);
+    }
+    KMU_HIP(ctx, hipGetLastError());
+    if (!host_checked) {
+        uint64_t h_head[GD_WORDS] = {0, 0, 0, 0}; // the one device-to-host copy of the call
+        KMU_HIP(ctx, hipMemcpyAsync(h_head, head, sizeof h_head, hipMemcpyDeviceToHost, ctx->stream));
         KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        h_go = tmp.data();
-        const uint32_t e = groups_check_host(h_go, n_groups, ds.n_seq);
-        if (e) return fail(ctx, KMU_E_BAD_ARG, "%s", groups_bad_text(e));
+        if (h_head[GD_BAD]) {
+            if (!ctx->async_device) (void) check_err_word(ctx, d_err); // (read, so that it starts clear next time)
+            return fail(ctx, KMU_E_BAD_ARG, "%s", groups_bad_text((uint32_t) h_head[GD_BAD]));
+        }
     }
-    for (uint32_t g = 0; g < n_groups; g++) {
-        DevSeqs one = ds;
-        one.offsets = ds.offsets + h_go[g];
-        one.packed_offsets = ds.packed_offsets ? ds.packed_offsets + h_go[g] : nullptr;
-        one.n_seq = (uint32_t) (h_go[g + 1] - h_go[g]);
-        KMU_TRY(launch_dens(ctx, p, one, d_sig + (size_t) g * row_bytes, d_err, nullptr, 0));
+    {
+        KernelTimer t(ctx, "k_grp_dens_walk");
+        if (a.hll) hipLaunchKernelGGL(k_grp_dens_walk<true>, dim3(walk_grid), dim3(256), lds_walk, ctx->stream, a, d_go, n_groups, (uint64_t *) rows,
+                                      (const unsigned long long *) head);
+        else hipLaunchKernelGGL(k_grp_dens_walk<false>, dim3(walk_grid), dim3(256), lds_walk, ctx->stream, a, d_go, n_groups, (uint64_t *) rows,
+                                (const unsigned long long *) head);
     }
+    {
+        KernelTimer t(ctx, "k_grp_dens_finish");
+        const unsigned per_cu = (unsigned) std::max<size_t>(1, std::min<size_t>(8, DENS_LDS_MAX / lds_full));
+        hipLaunchKernelGGL(k_grp_dens_finish, dim3(std::min<uint32_t>(n_groups, (uint32_t) ctx->num_cus * per_cu)), dim3(256), lds_full, ctx->stream, a,
+                           (const uint64_t *) rows, n_groups);
+    }
+    KMU_HIP(ctx, hipGetLastError());
     return KMU_OK;
 }
 
@@ -485,7 +672,7 @@ extern "C" int kmu_sketch_groups(kmu_ctx *ctx, const kmu_sketch_params *p_in, co
     }
     uint32_t *d_err;
     KMU_TRY(get_err_word(ctx, &d_err));
-    if (algo_is_dens(p->algo)) KMU_TRY(groups_dens(ctx, p, ds, host ? group_offsets : nullptr, d_go, n_groups, (uint8_t *) d_sig, row_bytes, d_err));
+    if (algo_is_dens(p->algo)) KMU_TRY(groups_dens(ctx, p, ds, d_go, n_groups, d_sig, d_err, host));
     else KMU_TRY(groups_batched(ctx, p, ds, d_go, n_groups, d_sig, d_err));
     if (host) KMU_HIP(ctx, hipMemcpyAsync(sig_out, d_sig, (size_t) n_groups * row_bytes, hipMemcpyDeviceToHost, ctx->stream));
     return finish_checked(ctx, p->mem, d_err);

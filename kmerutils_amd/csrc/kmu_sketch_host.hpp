@@ -1,7 +1,7 @@
 // kmu_sketch_host.hpp -- the host side of the sketch unit: what its .hip files call in each other, and the small rules that more
 // than one of them (host or device code) states.  kmu_sketch.hip: entry points, the all-sequences path, the shared helpers;
 // kmu_sketch_pmh.hip: ProbMinHash3a / bottom-k routes; kmu_sketch_pipe.hip: kmu_sketch_count; kmu_sketch_super.hip,
-// kmu_sketch_dens.hip, kmu_sketch_groups.hip: kernels and launchers of their own.
+// kmu_sketch_dens.hip, kmu_sketch_groups.hip: kernels and launchers of their own (what the last two share: kmu_sketch_dens.h).
 #pragma once
 
 #include "kmu_ctx.hpp"

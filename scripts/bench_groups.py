@@ -1,8 +1,12 @@
 #!/usr/bin/env python3
 """kmu_sketch_groups against the loop it replaces: one kmu_sketch(..., ALL_SEQS) call per group over the same device-resident
-data (existing code, the yardstick).  Two seeded synthetic workloads:
-  genomes    512 groups x 50 contigs x 40 kbases (1.0 Gbases), Kmer64bit k = 21, ProbMinHash3a m = 1000, u64
-  proteomes  2000 groups x 3000 proteins x ~330 residues, KmerAA64bit k = 7, SuperMinHash2 m = 1000
+data (existing code, the yardstick).  Seeded synthetic workloads:
+  genomes          512 groups x 50 contigs x 40 kbases (1.0 Gbases), Kmer64bit k = 21, ProbMinHash3a m = 1000, u64
+  proteomes        2000 groups x 3000 proteins x ~330 residues, KmerAA64bit k = 7, SuperMinHash2 m = 1000
+  genomes_optdens  the genomes layout, OptDens f64 m = 1000
+  genomes_hll      the genomes layout, HLL (SetSketch registers) u16 m = 4096
+  chromosomes_hll  64 groups x 8 sequences x 2 Mbases (1.0 Gbases; every sequence above 2^20 k-mers), HLL u16 m = 4096
+(KMU_LIB=<another build of the library> times that build on the same workloads: the second yardstick of a change to the route.)
 Per workload: row equality of the two ways first, then warm-up, then timed runs of the two ways in alternation (host clock
 around a call that ends in a device synchronise), median / min / max of each, and the per-kernel profile of one grouped call
 (in a run of its own, after the timing).  Every workload runs in a child process under its own time limit; a failed step
@@ -20,7 +24,7 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-WORKLOADS = ("genomes", "proteomes")
+WORKLOADS = ("genomes", "proteomes", "genomes_optdens", "genomes_hll", "chromosomes_hll")
 
 
 def make_workload(name, scale, dev):
@@ -28,13 +32,15 @@ def make_workload(name, scale, dev):
     import torch
     from kmerutils_amd import _abi as A
     g = torch.Generator(device=dev)
-    if name == "genomes":
+    if name != "proteomes":
         g.manual_seed(0x6E0)
-        n_groups, per, length = max(2, int(512 * scale)), 50, 40_000
+        n_groups, per, length = (max(2, int(64 * scale)), 8, 2_000_000) if name == "chromosomes_hll" else (max(2, int(512 * scale)), 50, 40_000)
         n_seq = n_groups * per
         lens = torch.full((n_seq,), length, dtype=torch.int64, device=dev)
         alpha = torch.tensor(list(b"ACGT"), dtype=torch.uint8, device=dev)
-        p = A.SketchParams(A.ALGO_PROB3A, A.KMER64BIT, 21, 1000, A.SIG_U64, A.HASHER_NOHASH, A.FHASH_CANON_INVHASH, 0,
+        algo, sig, m = {"genomes": (A.ALGO_PROB3A, A.SIG_U64, 1000), "genomes_optdens": (A.ALGO_OPTDENS, A.SIG_F64, 1000)}.get(
+            name, (A.ALGO_HLL, A.SIG_U16, 4096))
+        p = A.SketchParams(algo, A.KMER64BIT, 21, m, sig, A.HASHER_NOHASH, A.FHASH_CANON_INVHASH, 0,
                            A.MODE_ALL_SEQS, A.INPUT_ASCII, A.MEM_DEVICE, 0)
     else:
         g.manual_seed(0x9207)
@@ -60,6 +66,7 @@ def make_workload(name, scale, dev):
 
 def run_step(name, repeats, scale):
     import torch
+    from kmerutils_amd import _abi as A
     from kmerutils_amd import lib
     dev = torch.device("cuda", 0)
     ctx = lib.Context(0)
@@ -67,8 +74,9 @@ def run_step(name, repeats, scale):
     n_groups = go.numel() - 1
     h_go = go.cpu().tolist()
     m = p.sketch_size
-    out_g = torch.zeros((n_groups, m), dtype=torch.int64, device=dev)
-    out_l = torch.zeros((n_groups, m), dtype=torch.int64, device=dev)
+    tdt = torch.int16 if p.sig_type == A.SIG_U16 else torch.int64  # (f64 rows compared as their bits)
+    out_g = torch.zeros((n_groups, m), dtype=tdt, device=dev)
+    out_l = torch.zeros((n_groups, m), dtype=tdt, device=dev)
     slices = [offsets[h_go[i]:h_go[i + 1] + 1] for i in range(n_groups)]
     rows = [out_l[i:i + 1] for i in range(n_groups)]
 
@@ -114,6 +122,7 @@ def run_step(name, repeats, scale):
            "rows_equal": True, "first_call_s": t_first, "grouped": stat(times["grouped"]), "loop": stat(times["loop"]),
            "grouped_profile_ms": {k: {"launches": n, "ms": round(ms, 3)} for k, (n, ms) in sorted(prof.items())}}
     res["speedup_median"] = res["loop"]["median_s"] / res["grouped"]["median_s"]
+    res["library"] = os.path.basename(lib.SO_PATH)
     print(json.dumps(res))
 
 
@@ -133,7 +142,7 @@ def main():
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--scale", type=float, default=1.0)
     ap.add_argument("--step-timeout", type=int, default=900)
-    ap.add_argument("--only", choices=WORKLOADS, default=None)
+    ap.add_argument("--only", default=None, help="comma-separated workload names")
     ap.add_argument("--step", choices=WORKLOADS, default=None, help="(internal) run one workload in this process")
     a = ap.parse_args()
     if a.step:
@@ -143,7 +152,7 @@ def main():
              "box before:"] + ["  " + ln for ln in box_state()]
     rc = 0
     for name in WORKLOADS:
-        if a.only and name != a.only:
+        if a.only and name not in a.only.split(","):
             continue
         cmd = ["timeout", "-k", "10", str(a.step_timeout), sys.executable, os.path.abspath(__file__), "--step", name,
                "--repeats", str(a.repeats), "--scale", str(a.scale)]
@@ -155,7 +164,8 @@ def main():
         res = json.loads(r.stdout.strip().splitlines()[-1])
         print(json.dumps(res))
         lines.append("")
-        lines.append("%s: %d groups, %d sequences, %d symbols; rows equal: %s" % (name, res["groups"], res["sequences"], res["symbols"], res["rows_equal"]))
+        lines.append("%s (%s): %d groups, %d sequences, %d symbols; rows equal: %s" %
+                     (name, res["library"], res["groups"], res["sequences"], res["symbols"], res["rows_equal"]))
         for way in ("grouped", "loop"):
             s = res[way]
             lines.append("  %-8s median %9.2f ms   min %9.2f   max %9.2f   (n = %d; first call %.2f ms)" %
