@@ -1458,6 +1458,36 @@ template <class Kmer> class KmerCounter : public KmerCountT<Kmer> {
         c.resize(n);
         return {std::move(k), std::move(c)};
     }
+    /// the count spectrum: hist[v] = distinct k-mers whose count (saturated at 2^nb_bits - 1) is v; hist[0] is 0
+    std::vector<uint64_t> get_count_histogram() {
+        std::vector<uint64_t> h(size_t(1) << nb_bits_, 0);
+        if (!counter_) return h;
+        flush();
+        ctx_.check(kmu_count_histogram(counter_, h.data(), uint32_t(h.size()), KMU_MEM_HOST));
+        return h;
+    }
+    /// the reads against this counter: the count of the canonical k-mer at every k-mer start (counts[offsets[i] + p], the last
+    /// k - 1 positions of a read 0) and one record per read (solid: count >= solid_min)
+    struct ReadsAbundance {
+        std::vector<uint16_t> counts;
+        std::vector<kmu_read_abundance> stats;
+    };
+    ReadsAbundance get_reads_abundance(const std::vector<const Sequence *> &seqvec, uint32_t solid_min = 2) {
+        return get_reads_abundance(detail::gather(seqvec), solid_min);
+    }
+    ReadsAbundance get_reads_abundance(const detail::Batch &reads, uint32_t solid_min = 2) {
+        const detail::Batch b = detail::unpacked(reads); // kmu_count_read_profile takes unpacked bases
+        if (!counter_) throw KmuError(KMU_E_BAD_ARG, "get_reads_abundance: nothing has been inserted (the k-mer size is not known yet)");
+        flush();
+        ReadsAbundance r;
+        r.counts.assign(std::max<size_t>(b.offsets.empty() ? 0 : size_t(b.offsets.back()), 1), 0);
+        r.stats.assign(std::max<size_t>(b.n(), 1), kmu_read_abundance{});
+        if (b.mem() != KMU_MEM_HOST) throw KmuError(KMU_E_UNSUPPORTED, "get_reads_abundance takes host-resident reads");
+        ctx_.check(kmu_count_read_profile(counter_, b.bytes.data(), b.offsets.data(), b.n(), KMU_MEM_HOST, solid_min, r.counts.data(),
+                                          r.stats.data()));
+        r.stats.resize(b.n());
+        return r;
+    }
     uint8_t kmer_size() const { return kmer_size_; }
     /// the device counter with everything inserted so far (null before the first insertion)
     kmu_counter *raw() {

@@ -403,6 +403,34 @@ int kmu_count_eliminate_once(kmu_counter *c);
  * Unpacked (ASCII) input.  Call with kmers_out == NULL for the number of records in *n_out. */
 int kmu_count_once_positions(kmu_counter *c, const uint8_t *bases, const uint64_t *offsets, uint32_t n_seq, int mem,
                              uint64_t *kmers_out, uint32_t *numseq_out, uint32_t *numkmer_out, uint64_t cap, uint64_t *n_out);
+/* ---- reading the table back (no counterpart upstream: the reference's filters cannot be enumerated) ----
+ * The count spectrum.  hist_out[v], v < n_bins: the number of distinct canonical k-mers held whose REPORTED count -- what
+ * kmu_count_query answers: min(multiplicity, 2^counter_bits - 1) -- is v; the last bin collects every count >= n_bins - 1.
+ * hist_out[0] is always 0 (an entry that left for its owner is absent for every reader).  2 <= n_bins <= 65536; bins above
+ * 2^counter_bits - 1 stay 0.  A distributed counter answers for its own partition after kmu_count_finalize (owners are
+ * disjoint: the ranks' arrays add up). */
+int kmu_count_histogram(kmu_counter *c, uint64_t *hist_out, uint32_t n_bins, int mem);
+
+typedef struct kmu_read_abundance { /* 32 bytes */
+    uint32_t n_kmers;  /* L - k + 1; 0 when L < k (all other fields 0 then) */
+    uint32_t n_absent; /* reported count 0 */
+    uint32_t n_once;   /* reported count 1 */
+    uint32_t n_solid;  /* reported count >= solid_min */
+    uint16_t min, median, max; /* of the reported counts; median = the value of rank (n_kmers - 1) / 2 in ascending order */
+    uint16_t reserved; /* 0 */
+    uint64_t sum;      /* of the reported counts */
+} kmu_read_abundance;
+
+/* The abundance of the k-mers of reads in the table.  For every k-mer start p of every sequence i: the reported count of its
+ * canonical k-mer.
+ * counts_out (may be NULL): counts_out[offsets[i] + p], p in [0, L_i - k + 1) -- the layout of kmu_kmer_hashes, including
+ *   offsets[0] != 0 and what happens to the last k - 1 positions of a sequence (untouched in device arrays, zero in host arrays).
+ * stats_out (may be NULL): n_seq records.  At least one of the two must be given.
+ * Unpacked (ASCII) input.  A sequence shorter than k gets the all-zero record; non-ACGT bytes are KMU_E_NON_ACGT as in
+ * kmu_count_add_reads.  KMU_E_UNSUPPORTED: a counter distributed over more than one rank (its table holds only its own keys), a
+ * sequence of 2^32 bases or more.  With stats_out alone the counts pass through a bounded workspace. */
+int kmu_count_read_profile(kmu_counter *c, const uint8_t *bases, const uint64_t *offsets, uint32_t n_seq, int mem,
+                           uint32_t solid_min, uint16_t *counts_out, kmu_read_abundance *stats_out);
 /* multi-GPU merge (one process per GPU): export the entries whose owner (int64_hash(kmer) % n_parts,
  * kmercount.rs:412-420) is `part` as device/host arrays, and merge entries received from peers.
  * The exchange itself is done by the host layer (RCCL all_to_all over xGMI). */

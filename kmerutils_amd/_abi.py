@@ -89,6 +89,17 @@ class CountTableInfo(C.Structure):
                 ("count_field_bits", C.c_uint32), ("count_ceiling", C.c_uint64)]
 
 
+class ReadAbundance(C.Structure):
+    """kmu_read_abundance: one read's k-mers against a counter (kmu_count_read_profile)"""
+    _fields_ = [("n_kmers", C.c_uint32), ("n_absent", C.c_uint32), ("n_once", C.c_uint32), ("n_solid", C.c_uint32),
+                ("min", C.c_uint16), ("median", C.c_uint16), ("max", C.c_uint16), ("reserved", C.c_uint16), ("sum", C.c_uint64)]
+
+
+# the same record as a numpy dtype (np.dtype(READ_ABUNDANCE_DTYPE): 32 bytes, the field offsets of the structure)
+READ_ABUNDANCE_DTYPE = [("n_kmers", "<u4"), ("n_absent", "<u4"), ("n_once", "<u4"), ("n_solid", "<u4"), ("min", "<u2"),
+                        ("median", "<u2"), ("max", "<u2"), ("reserved", "<u2"), ("sum", "<u8")]
+
+
 ALLTOALLV_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_void_p,
                            C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_uint32, C.c_void_p)
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64)

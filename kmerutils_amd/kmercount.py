@@ -56,6 +56,17 @@ class KmerCounter:
         """kmercount.rs:110-117: forget the k-mers seen once"""
         self._c.eliminate_once()
 
+    def get_count_histogram(self):
+        """the count spectrum: hist[v] = distinct k-mers whose count (saturated at 2^nb_bits - 1) is v; hist[0] is 0"""
+        return self._c.histogram()
+
+    def get_reads_abundance(self, vseq, solid_min=2):
+        """(counts, stats) of the reads against this counter: the count of the canonical k-mer at every k-mer start
+        (counts[offsets[i] + p]) and one A.READ_ABUNDANCE_DTYPE record per read (n_kmers, n_absent, n_once, n_solid -- count >=
+        solid_min --, min, median, max, sum)"""
+        bases, offsets = _as_arrays(vseq)
+        return self._c.read_profile(bases, offsets, solid_min)
+
     def get_count_nb_bits(self):
         return self._c.p.counter_bits
 

@@ -32,6 +32,7 @@ SYMBOLS = [
     "kmu_comm_allgather", "kmu_comm_get_stats", "kmu_count_finalize", "kmu_kmer_owner",
     "kmu_sketch_count", "kmu_host_alloc", "kmu_host_free", "kmu_count_nb_occurrences", "kmu_count_table_info",
     "kmu_count_nb_saturated", "kmu_kmer_owner_minimizer", "kmu_count_owner_kind", "kmu_count_extract_superkmers", "kmu_count_add_superkmers",
+    "kmu_count_histogram", "kmu_count_read_profile",
 ]
 
 
@@ -121,6 +122,8 @@ def load():
     L.kmu_sketch_merge_partials.argtypes = [vp, C.POINTER(A.SketchParams), vp, C.c_uint32, vp]
     L.kmu_count_eliminate_once.argtypes = [vp]
     L.kmu_count_once_positions.argtypes = [vp, vp, vp, C.c_uint32, C.c_int, vp, vp, vp, C.c_uint64, u64p]
+    L.kmu_count_histogram.argtypes = [vp, vp, C.c_uint32, C.c_int]
+    L.kmu_count_read_profile.argtypes = [vp, vp, vp, C.c_uint32, C.c_int, C.c_uint32, vp, vp]
     L.kmu_dev_alloc.argtypes = [vp, C.c_uint64, C.POINTER(vp)]
     L.kmu_dev_free.argtypes = [vp, vp]
     L.kmu_copy_to_device.argtypes = [vp, vp, vp, C.c_uint64]
@@ -831,6 +834,52 @@ class Counter:
         self.ctx._check(self.L.kmu_count_once_positions(self.h, _ptr(bases)[0], _ptr(offsets)[0], nseq, mem, _ptr(k)[0], _ptr(s)[0],
                                                         _ptr(p)[0], n.value, C.byref(n)))
         return k[:n.value], s[:n.value], p[:n.value]
+
+    def histogram(self, n_bins=None, device=None):
+        """kmu_count_histogram: hist[v] = distinct k-mers whose reported count is v, the last bin collecting every count
+        >= n_bins - 1 (default 2^counter_bits bins); a numpy uint64 array, or a torch int64 cuda tensor when device is given"""
+        if n_bins is None:
+            n_bins = 1 << self.p.counter_bits
+        if device is not None:
+            import torch
+            h = torch.zeros(max(n_bins, 1), dtype=torch.int64, device=device)
+            mem = A.MEM_DEVICE
+        else:
+            h = np.zeros(max(n_bins, 1), np.uint64)
+            mem = A.MEM_HOST
+        self.ctx._check(self.L.kmu_count_histogram(self.h, _ptr(h)[0], n_bins, mem))
+        return h[:n_bins]
+
+    def read_profile(self, bases, offsets, solid_min=2, want_counts=True, want_stats=True, counts_out=None):
+        """kmu_count_read_profile: the reported count of the canonical k-mer at every k-mer start of every read, and one
+        kmu_read_abundance record per read.  Returns (counts, stats), or the one asked for.
+        counts: counts[offsets[i] + p] (the layout of kmer_hashes) -- a numpy uint16 array for host input, a torch int16 cuda
+        tensor (the same bits) for device input; `counts_out` gives the array to fill instead of a new one of zeros.
+        stats: a numpy array of A.READ_ABUNDANCE_DTYPE records for host input; for device input a torch uint8 cuda tensor
+        [n_seq, 32] holding the same records (`.cpu().numpy().view(A.READ_ABUNDANCE_DTYPE).reshape(-1)`)."""
+        mem = Context._mem(bases, offsets)
+        self.ctx._wait_producers(bases)
+        nseq = len(offsets) - 1
+        counts = stats = None
+        if mem == A.MEM_DEVICE:
+            import torch
+            if want_counts:
+                counts = counts_out if counts_out is not None else torch.zeros(max(int(offsets[-1].item()), 1), dtype=torch.int16,
+                                                                               device=bases.device)
+            if want_stats:
+                stats = torch.zeros((max(nseq, 1), 32), dtype=torch.uint8, device=bases.device)
+        else:
+            if want_counts:
+                counts = counts_out if counts_out is not None else np.zeros(max(int(offsets[-1]), 1), np.uint16)
+            if want_stats:
+                stats = np.zeros(max(nseq, 1), np.dtype(A.READ_ABUNDANCE_DTYPE))
+        self.ctx._check(self.L.kmu_count_read_profile(self.h, _ptr(bases)[0], _ptr(offsets)[0], nseq, mem, solid_min,
+                                                      _ptr(counts)[0], _ptr(stats)[0]))
+        if stats is not None:
+            stats = stats[:nseq]
+        if want_counts and want_stats:
+            return counts, stats
+        return counts if want_counts else stats
 
     def export_part(self, part, n_parts, device=None):
         """entries owned by `part`: (kmers, counts) as numpy arrays, or torch cuda tensors when device is given"""

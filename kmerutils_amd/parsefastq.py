@@ -35,6 +35,8 @@ def main(argv=None):
     ap.add_argument("--outdir", default=".", help="directory of <file>.multi_kmer.bin (the tool writes to the cwd)")
     ap.add_argument("--unique", action="store_true", help="dump the 16-mers seen exactly once with their positions "
                     "(KmerProcessing::Unicity, parsefastq.rs:238-247) instead of counting")
+    ap.add_argument("--histo", metavar="FILE", help="after the count: the count spectrum, one `count<TAB>number of distinct "
+                    "k-mers` line per non-empty bin, ascending")
     ap.add_argument("--device", type=int, default=0)
     args = ap.parse_args(argv)
     kmer_type, val_bytes = kmer_type_for(args.kmer_size)
@@ -65,6 +67,11 @@ def main(argv=None):
     n = formats.dump_kmer_counter(out, kmers, counts, args.kmer_size, val_bytes)
     print("dump_kmer_counter, number of kmer dumped : %d (distinct %d, unique %d), elapsed time (s) %.3f" %
           (n, counter.nb_distinct(), counter.nb_unique(), time.time() - t0), file=sys.stderr)
+    if args.histo:
+        hist = counter.histogram()
+        with open(args.histo, "w") as f:
+            for v in np.flatnonzero(hist):
+                f.write("%d\t%d\n" % (v, hist[v]))
     ctx.close()
     return 0
 

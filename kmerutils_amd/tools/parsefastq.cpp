@@ -1,10 +1,12 @@
-// parsefastq -f reads.fastq kmer (--count -s <kmer size> | --unique) [-t threads] [-b 2] [--outdir dir] [--device n]
+// parsefastq -f reads.fastq kmer (--count -s <kmer size> | --unique) [-t threads] [-b 2] [--outdir dir] [--device n] [--histo file]
 //
 // The counting branch of the reference's tool (src/bin/parsefastq.rs:215-236: `kmer --count`) on the GPU path: the FASTQ
 // text is filtered on the device like parse_with_needletail does on the host (src/io.rs:37-57), every canonical k-mer of
 // the accepted reads is counted (count_kmer_threaded_one_to_many, src/base/kmercount.rs:881-974) and the k-mers seen at
 // least twice are written as a COUNTER_MULTIPLE dump to <fastq>.multi_kmer.bin (kmercount.rs:467-531).  `--unique` is the
 // Unicity branch (parsefastq.rs:238-247): the 16-mers seen exactly once, with (sequence, position), to <fastq>.once_kmer.bin.
+// `--histo <file>` (with --count; no counterpart upstream): the count spectrum of the table, one `count<TAB>number of distinct
+// k-mers` line per non-empty bin, ascending (counts saturate at 255).
 // Kmer type by size as upstream: k <= 14 Kmer32bit, k == 16 Kmer16b32bit, else Kmer64bit (k <= 31).
 #include <chrono>
 #include <cstdio>
@@ -16,21 +18,30 @@
 using namespace kmerutils;
 
 static void usage() {
-    std::fprintf(stderr, "usage: parsefastq -f <fastq> kmer (--count -s <kmer size> | --unique) [-t <threads>] [-b 2] [--outdir <dir>] [--device <n>]\n");
+    std::fprintf(stderr, "usage: parsefastq -f <fastq> kmer (--count -s <kmer size> | --unique) [-t <threads>] [-b 2] [--outdir <dir>] [--device <n>] [--histo <file>]\n");
     std::exit(2);
 }
 
-template <class Kmer> static void count_and_dump(const DeviceReads &reads, uint8_t kmer_size, const std::string &dumpfname, Context &ctx) {
+template <class Kmer>
+static void count_and_dump(const DeviceReads &reads, uint8_t kmer_size, const std::string &dumpfname, const std::string &histofname, Context &ctx) {
     KmerCounterPool<Kmer> pool(std::max<uint64_t>(reads.info.kept_bases, 1024), 8, ctx);
     pool.counter().insert_reads(reads.batch(0, reads.nb_reads()), kmer_size);
     std::fprintf(stderr, " nb distinct kmers %llu, nb unique kmers %llu\n", (unsigned long long) pool.get_nb_distinct(),
                  (unsigned long long) pool.get_nb_unique());
     const size_t n = pool.dump_kmer_counter(dumpfname);
     std::fprintf(stderr, " dumped %zu kmers seen at least twice in %s\n", n, dumpfname.c_str());
+    if (!histofname.empty()) {
+        const std::vector<uint64_t> h = pool.counter().get_count_histogram();
+        std::FILE *f = std::fopen(histofname.c_str(), "w");
+        if (!f) throw std::runtime_error("cannot write " + histofname);
+        for (size_t v = 0; v < h.size(); v++)
+            if (h[v]) std::fprintf(f, "%zu\t%llu\n", v, (unsigned long long) h[v]);
+        std::fclose(f);
+    }
 }
 
 int main(int argc, char **argv) {
-    std::string fname, outdir = ".";
+    std::string fname, outdir = ".", histo;
     long kmer_size = 0, device = 0;
     bool count = false, kmer_cmd = false, unique = false;
     for (int i = 1; i < argc; i++) {
@@ -52,6 +63,7 @@ int main(int argc, char **argv) {
             }
         } else if (a == "--outdir") outdir = next();
         else if (a == "--device") device = std::atol(next());
+        else if (a == "--histo") histo = next();
         else usage();
     }
     if (fname.empty() || !kmer_cmd || (!count && !unique) || (count && (kmer_size < 1 || kmer_size > 31))) usage();
@@ -74,9 +86,9 @@ int main(int argc, char **argv) {
             const size_t n = filter.dump_in_file_once_kmer16b32bit(oncefname, all);
             std::fprintf(stderr, "dump_in_file_once_kmer16b32bit, number of kmer dumped : %zu (distinct once-k-mers %llu)\n", n,
                          (unsigned long long) filter.get_nb_once());
-        } else if (kmer_size <= 14) count_and_dump<Kmer32bit>(reads, uint8_t(kmer_size), dumpfname, ctx);
-        else if (kmer_size == 16) count_and_dump<Kmer16b32bit>(reads, uint8_t(kmer_size), dumpfname, ctx);
-        else count_and_dump<Kmer64bit>(reads, uint8_t(kmer_size), dumpfname, ctx);
+        } else if (kmer_size <= 14) count_and_dump<Kmer32bit>(reads, uint8_t(kmer_size), dumpfname, histo, ctx);
+        else if (kmer_size == 16) count_and_dump<Kmer16b32bit>(reads, uint8_t(kmer_size), dumpfname, histo, ctx);
+        else count_and_dump<Kmer64bit>(reads, uint8_t(kmer_size), dumpfname, histo, ctx);
         std::fprintf(stderr, " elapsed time (s) %.3f\n",
                      std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
     } catch (const std::exception &e) {
