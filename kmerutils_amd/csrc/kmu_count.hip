@@ -10,6 +10,7 @@
 #include <cmath>
 #include <vector>
 
+#include "kmu_count_plan.hpp"
 #include "kmu_count_table.h"
 #include "kmu_flat.h"
 #include "kmu_stream.h"
@@ -806,7 +807,7 @@ int kmu_count_once_positions(kmu_counter *c, const uint8_t *bases, const uint64_
     KMU_TRY(flat_stream_extent(ctx, offsets, n_seq, mem, ds, &total_bases));
     if (total_bases == 0) return KMU_OK;
     KMU_TRY(materialize(c));
-    const uint64_t nsteps = ((total_bases + 15) / 16 + 63) / 64;
+    const uint64_t nsteps = flat_wave_steps(total_bases);
     void *cnt, *base;
     KMU_TRY(dev_buf(ctx, "once.cnt", nsteps * 4 + 64, &cnt));
     KMU_TRY(dev_buf(ctx, "once.base", (nsteps + 1) * 8 + 64, &base));

@@ -5,6 +5,7 @@
 #include <algorithm>
 #include <vector>
 
+#include "kmu_count_plan.hpp"
 #include "kmu_count_table.h"
 
 namespace kmu {
@@ -111,7 +112,7 @@ int dist_add_begin(kmu_counter *c, DevSeqs &ds, uint64_t total_bases, uint32_t *
     // ---- census + sample ----
     void *slist, *sn;
     const uint64_t units = smer ? smer_units(ctx, total_bases)
-                                : std::min<uint64_t>(std::max<uint64_t>(1, ((total_bases + 15) / 16 + 63) / 64), (uint64_t) ctx->num_cus * 8);
+                                : unit_split(flat_wave_steps(total_bases), (uint64_t) ctx->num_cus * 8).asked; // (as sample_ratio)
     const uint64_t kmers_per_unit = (total_bases + units - 1) / units;
     uint32_t shift = 0; // ~1024 sampled k-mers per workgroup (its LDS list holds 4096)
     while (shift < 24 && (kmers_per_unit >> shift) > 1024) shift++;

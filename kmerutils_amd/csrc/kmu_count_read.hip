@@ -15,6 +15,7 @@
 #include <algorithm>
 #include <vector>
 
+#include "kmu_count_plan.hpp"
 #include "kmu_count_table.h"
 #include "kmu_flat.h"
 
@@ -593,7 +594,7 @@ int kmu_count_read_profile(kmu_counter *c, const uint8_t *bases, const uint64_t 
     if (!pc.empty) KMU_TRY(materialize(c));
     uint64_t chunk = std::max<uint64_t>(env_u64("KMU_PROFILE_CHUNK", PROFILE_CHUNK), 2048);
     chunk = (chunk + 1023) & ~(uint64_t) 1023;
-    const uint64_t nsteps = ((total_bases + 15) / 16 + 63) / 64;
+    const uint64_t nsteps = flat_wave_steps(total_bases);
     if (counts_out || total_bases <= chunk) { // every count at once: in the caller's array, its staging copy, or the workspace
         uint16_t *d_counts;
         if (counts_out && mem == KMU_MEM_DEVICE) d_counts = counts_out + shift;

@@ -1,14 +1,17 @@
 // Host-only code of include/kmerutils.hpp under AddressSanitizer + UndefinedBehaviorSanitizer (`make sanitize`; no GPU, no
 // libkmu call): packed sequences, k-mer values, parameter files, the signature dump writer / reader, the k-mer count reloader,
-// and the chunk plan of kmu_sketch_count's host pipeline (kmerutils_amd/csrc/kmu_pipe_plan.hpp, host arithmetic of libkmu).
+// the chunk plan of kmu_sketch_count's host pipeline (kmerutils_amd/csrc/kmu_pipe_plan.hpp) and the plans of the partitioned
+// count build (kmerutils_amd/csrc/kmu_count_plan.hpp): host arithmetic of libkmu.
 // The reference leans on Rust ownership and bounds checks for these (src/base/sequence.rs, src/sketching/seqsketchjaccard.rs:385-712,
 // src/base/kmercount.rs:1148-1503); this side is C++ and gets the sanitizers instead.
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <random>
 #include <string>
 
 #include "../../include/kmerutils.hpp"
+#include "../../kmerutils_amd/csrc/kmu_count_plan.hpp"
 #include "../../kmerutils_amd/csrc/kmu_pipe_plan.hpp"
 
 using namespace kmerutils;
@@ -210,6 +213,72 @@ int main(int argc, char **argv) {
         CHECK((cut == std::vector<uint32_t>{0u, 1u, 6u, 7u, 13u}) && (pk == std::vector<uint64_t>{0ull, 704ull, 11056ull, 11072ull, 13981ull}));
         pipe_chunk_plan(s, 13, s.back(), 2048, 2, false, &cut, &pk);
         CHECK((cut == std::vector<uint32_t>{0u, 1u, 3u, 4u, 6u, 7u, 13u}) && pk.empty());
+    }
+    // ---- the plans of the partitioned count build (kmu_count_plan.hpp) ----
+    {
+        using namespace kmu;
+        CHECK(flat_wave_steps(0) == 0 && flat_wave_steps(1) == 1 && flat_wave_steps(1024) == 1 && flat_wave_steps(1025) == 2);
+        // the unit split: every step in exactly one unit, no unit without a step, no more units than the cap
+        for (uint64_t cap : {uint64_t(256), uint64_t(2048)})
+            for (uint64_t nsteps : {uint64_t(0), uint64_t(1), uint64_t(2), cap - 1, cap, cap + 1, 3 * cap + 1, uint64_t(1) << 33}) {
+                const UnitSplit u = unit_split(nsteps, cap);
+                const uint64_t n = std::max<uint64_t>(nsteps, 1);
+                CHECK(u.units >= 1 && u.units <= cap && u.asked == std::min(n, cap));
+                CHECK((uint64_t) u.units * u.steps_per_unit >= n && n > (uint64_t) (u.units - 1) * u.steps_per_unit);
+            }
+        // stream capacities: whole 128-byte lines, never below mean + 5 sigma + 32 at the full share, monotone in the mean
+        uint64_t prev = 0;
+        for (double mean = 0.0; mean < 3e9; mean = mean * 1.37 + 0.61) {
+            const uint64_t cap = seg_cap_for(mean, 1.0);
+            CHECK(cap % 16 == 0 && (double) cap >= mean + 5.0 * std::sqrt(mean) + 32.0 && cap >= prev);
+            CHECK(seg_cap_for(mean, 0.6) % 16 == 0 && seg_cap_for(mean, 0.6) <= cap);
+            prev = cap;
+        }
+        for (uint32_t cus : {1u, 2u, 15u, 16u, 17u, 256u})
+            for (uint64_t bases : {uint64_t(0), uint64_t(1), uint64_t(1024), uint64_t(16 * 1024 + 1), uint64_t(300000), uint64_t(4380000000ull)}) {
+                const SegPlan sp = seg_plan(cus, bases, 128, 40, 1.0);
+                const UnitSplit u = unit_split(flat_wave_steps(bases), cus);
+                CHECK(sp.units1 == u.units && sp.steps_per_unit == u.steps_per_unit);
+                CHECK(sp.sets >= 1 && sp.sets <= std::min(16u, sp.units1) && sp.cap1 % 16 == 0 && sp.cap2 % 16 == 0);
+                const SegPlan sa = seg_plan_array(cus, bases, 128, 40, 1.0);
+                CHECK(sa.units1 == cus && sa.sets == std::min(16u, cus) && sa.cap1 >= (uint64_t) ((double) bases / sa.sets / 128));
+            }
+        // the headline's level 1 (256 CUs, 4.38 G bases, 2^11 groups): expected values from the lines this was taken from
+        {
+            const SegPlan sp = seg_plan(256, 4380000000ull, 2048, 1024, 1.0);
+            CHECK(sp.units1 == 256 && sp.steps_per_unit == 16709 && sp.sets == 16 && sp.cap1 == 135536 && sp.cap2 == 2352);
+        }
+        // 2^bits leaves as 2^b1 groups of n2
+        for (int bits = 0; bits <= 22; bits++) {
+            int b1 = -1;
+            uint32_t n2 = 0;
+            region_split(bits, &b1, &n2);
+            CHECK(((uint64_t) 1 << b1) * n2 == (uint64_t) 1 << bits && b1 >= 0 && b1 <= 11 && n2 <= 2048 && (b1 == 0) == (bits <= 11));
+        }
+        // the rounds of level 1 under an upload: random arrivals (repeats, a jump straight to the end), unit counts and minima
+        for (int it = 0; it < 20000; it++) {
+            const uint64_t total = it < 50 ? uint64_t(it) : rng() % (it % 7 == 0 ? 5000000 : 70000);
+            const uint32_t units1 = 1 + uint32_t(rng() % 300);
+            const uint64_t min_per_unit = rng() % 3 == 0 ? 0 : rng() % 70, nsteps = flat_wave_steps(total);
+            uint64_t ready = 0, done = 0;
+            bool finished = false;
+            for (int call = 0; call < 1000 && !finished; call++) {
+                const uint64_t r = rng() % 8;
+                if (r == 0) ready = total;                                       // straight to the end
+                else if (r > 2) ready = std::min(total, ready + rng() % (total / 3 + 2)); // (else: the same value again)
+                if (call == 999) ready = total;
+                const SegRound sr = seg_round(total, ready, done, units1, min_per_unit);
+                CHECK(sr.launch == (sr.n_new != 0) && sr.last == (ready >= total));
+                if (sr.n_new) CHECK(sr.last || sr.n_new >= (uint64_t) units1 * min_per_unit);
+                if (!sr.last) CHECK(sr.n_new == 0 || (ready >= 32 && (done + sr.n_new) * 1024 <= ready - 32));
+                done += sr.n_new; // the launched ranges are [done, done + n_new): in order, no gap, no overlap
+                CHECK(done <= nsteps);
+                finished = sr.last;
+            }
+            CHECK(finished && done == nsteps); // the last call completes whatever was held back
+            const SegRound after = seg_round(total, total, done, units1, min_per_unit);
+            CHECK(!after.launch && after.n_new == 0);
+        }
     }
     std::printf("%s: %d failure(s)\n", argv[0], failures);
     return failures ? 1 : 0;

@@ -132,6 +132,72 @@ def test_region_maps_that_are_no_powers_of_two(ctx, oracle, monkeypatch, regions
     c.close()
 
 
+@pytest.fixture(scope="module")
+def tripled_kmers(oracle):
+    """~150 000 distinct canonical 31-mers, each three times, shuffled; the oracle's table of one such batch and of two"""
+    bases, off = synth.genome_reads(50, np.full(50, 3030, np.int64), 4_000_000, 0xD9)
+    o = oracle.Counter(A.KMER64BIT, 31, 8, 1 << 20)
+    o.add_reads(bases, off)
+    distinct = o.dump(1)[0]
+    assert 140_000 <= distinct.size <= 150_000
+    arr = np.repeat(distinct, 3)
+    np.random.default_rng(0xDA).shuffle(arr)
+    o = oracle.Counter(A.KMER64BIT, 31, 8, 1 << 20)
+    o.add_kmers(arr)
+    once = o.dump(1)
+    o.add_kmers(arr)
+    return arr, once, o.dump(1)
+
+
+def _add_kmers_twice_on_two_levels(ctx, tripled_kmers):
+    """the array into a table of 128 groups of 40 regions, twice; returns the kernels of the first add"""
+    import torch
+    arr, (wk, wc), (wk2, wc2) = tripled_kmers
+    d_arr = torch.from_numpy(arr.view(np.int64)).cuda()
+    c = ctx.counter(A.KMER64BIT, 31, 8, 1024)
+    try:
+        ctx.profile_reset()
+        ctx.profile_enable(True)
+        c.add_kmers(d_arr)
+        ctx.profile_enable(False)
+        prof = ctx.profile_get()
+        gk, gc = c.dump(1)
+        assert np.array_equal(gk, wk) and np.array_equal(gc, wc) and (gc == 3).all()
+        c.add_kmers(d_arr)  # onto the occupied image
+        gk, gc = c.dump(1)
+        assert np.array_equal(gk, wk2) and np.array_equal(gc, wc2) and (gc == 6).all()
+    finally:
+        c.close()
+    return prof
+
+
+def test_add_kmers_on_the_exact_levels_of_a_two_level_table(ctx, tripled_kmers, monkeypatch):
+    """explicit k-mers through BOTH exact array levels (keys in, khash out; then khash to khash) into a two-level table: the
+    single-pass partition is off, the levels are the array's own (k_arr_hist), not the reads' (k_part_hist1)"""
+    monkeypatch.setenv("KMU_COUNT_REGIONS", "5000")
+    monkeypatch.setenv("KMU_COUNT_PATH", "partitioned")
+    monkeypatch.setenv("KMU_COUNT_SEG", "0")
+    prof = _add_kmers_twice_on_two_levels(ctx, tripled_kmers)
+    assert "k_arr_hist" in prof and "k_part_hist1" not in prof, sorted(prof)
+
+
+def test_add_kmers_single_pass_overflow_on_a_fresh_context(tripled_kmers, monkeypatch):
+    """the array twin of test_count_single_pass_overflow_on_a_fresh_context (test_gpu_parity.py): streams of 60 % of their
+    expected fill overflow the spill list of the single-pass attempt on the array, it returns untaken, and the exact array
+    levels allocate "cnt.partA" / "cnt.partB" anew on a context that had no scratch buffers: the same table, twice"""
+    from kmerutils_amd import lib
+    monkeypatch.setenv("KMU_COUNT_REGIONS", "5000")
+    monkeypatch.setenv("KMU_COUNT_PATH", "partitioned")
+    monkeypatch.setenv("KMU_COUNT_SEG", "2")
+    monkeypatch.setenv("KMU_COUNT_SEG_PCT", "60")
+    fresh = lib.Context(0)
+    try:
+        prof = _add_kmers_twice_on_two_levels(fresh, tripled_kmers)
+        assert "k_arr_hist" in prof and "k_part_hist1" not in prof, sorted(prof)  # the exact array levels ran
+    finally:
+        fresh.close()
+
+
 def test_table_load_factor_switch(ctx, oracle, monkeypatch):
     """KMU_COUNT_LOAD (per cent; A/B runs of the region build): the same counts from a table at a load of 0.85 at the hint"""
     bases, off = synth.ont_reads(400, 1_500_000, 0xD8)
