@@ -23,7 +23,7 @@ namespace kmu {
 __global__ void __launch_bounds__(256) k_count_add_flat(const uint8_t *bases, const uint64_t *offsets, uint32_t n_seq,
                                                         int k, CountTable t, uint32_t *err) {
     const uint64_t total = offsets[n_seq], start = offsets[0];
-    const uint64_t nsteps = ((total + 15) / 16 + 63) / 64;
+    const uint64_t nsteps = flat_wave_steps(total);
     const uint64_t wave_global = ((uint64_t) blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const uint64_t nwaves_global = ((uint64_t) gridDim.x * blockDim.x) >> 6;
     uint32_t anybad = 0, full = 0, r_hint = 0xFFFFFFFFu;
@@ -41,48 +41,21 @@ __global__ void __launch_bounds__(256) k_count_add_flat(const uint8_t *bases, co
 __device__ __forceinline__ uint32_t once_step(const uint8_t *bases, const uint64_t *offsets, uint32_t n_seq, uint64_t total,
                                               uint64_t start, int k, uint64_t st, uint32_t &r_hint, const CountTable &t,
                                               uint64_t (&canon)[16], uint32_t (&rd)[16]) {
-    SeqView s;
-    s.base = bases; s.begin = 0; s.len = total; s.total = total; s.packed = 0;
-    const int lane = lane_id();
-    const uint64_t widx = st * 64 + lane;
-    uint32_t bad, bad2;
-    uint32_t w0 = load_code_word(s, widx, bad);
-    uint32_t ex = load_code_word(s, st * 64 + 64 + (uint64_t) (lane & 1), bad2);
-    uint32_t e0 = bcast_u32(ex, 0), e1 = bcast_u32(ex, 1);
-    uint32_t w1 = shfl_down_u32(w0, 1), w2 = shfl_down_u32(w0, 2);
-    if (lane == 63) { w1 = e0; w2 = e1; }
-    if (lane == 62) { w2 = e0; }
-    uint32_t r = wave_find_read_from(offsets, n_seq, st * 1024 < total ? st * 1024 : total - 1, r_hint);
-    r_hint = r;
-    const uint64_t g0 = widx * 16;
     uint32_t mask = 0;
-    if (g0 < total && g0 + 16 > start) {
-        uint64_t rend = offsets[r + 1];
-        const uint64_t hi = ((uint64_t) w0 << 32) | w1;
-        const int sh = 64 - 2 * k;
-#pragma unroll
-        for (int j = 0; j < 16; j++) {
-            const uint64_t g = g0 + j;
-            while (g >= rend && r + 1 < n_seq) { r++; rend = offsets[r + 1]; }
-            if (g >= start && g + k <= rend) {
-                const uint64_t v = (hi << (2 * j)) | (((uint64_t) w2 << (2 * j)) >> 32);
-                const uint64_t val = v >> sh, rc = revcomp_val(val, k);
-                const uint64_t c = rc < val ? rc : val;
-                if (count_lookup(t, c) == 1u) {
-                    mask |= 1u << j;
-                    canon[j] = c;
-                    rd[j] = r;
-                }
-            }
+    flat_step_visit<false>(bases, offsets, n_seq, total, start, k, st, r_hint, [&](int j, uint64_t c, uint32_t r) {
+        if (count_lookup(t, c) == 1u) {
+            mask |= 1u << j;
+            canon[j] = c;
+            rd[j] = r;
         }
-    }
+    });
     return mask;
 }
 
 __global__ void __launch_bounds__(256) k_once_count(const uint8_t *bases, const uint64_t *offsets, uint32_t n_seq, int k,
                                                     CountTable t, uint32_t *cnt) {
     const uint64_t total = offsets[n_seq], start = offsets[0];
-    const uint64_t nsteps = ((total + 15) / 16 + 63) / 64;
+    const uint64_t nsteps = flat_wave_steps(total);
     const uint64_t wave_global = ((uint64_t) blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const uint64_t nwaves_global = ((uint64_t) gridDim.x * blockDim.x) >> 6;
     uint32_t r_hint = 0xFFFFFFFFu;
@@ -100,7 +73,7 @@ __global__ void __launch_bounds__(256) k_once_emit(const uint8_t *bases, const u
                                                    CountTable t, const uint64_t *base, uint64_t *kmers_out,
                                                    uint32_t *numseq_out, uint32_t *numkmer_out) {
     const uint64_t total = offsets[n_seq], start = offsets[0];
-    const uint64_t nsteps = ((total + 15) / 16 + 63) / 64;
+    const uint64_t nsteps = flat_wave_steps(total);
     const uint64_t wave_global = ((uint64_t) blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const uint64_t nwaves_global = ((uint64_t) gridDim.x * blockDim.x) >> 6;
     uint32_t r_hint = 0xFFFFFFFFu;
@@ -182,14 +155,12 @@ __global__ void __launch_bounds__(256) k_count_stats(CountTable t, uint64_t nslo
         }
     }
     if (__any(sat != 0)) {
-        for (int o = 32; o >= 1; o >>= 1) sat += (uint64_t) (uint32_t) __shfl_xor((int) (uint32_t) sat, o, 64);
+        sat = wave_sum_u64(sat);
         if (lane_id() == 0) atomicAdd((unsigned long long *) &scalars[2], (unsigned long long) sat);
     }
-    for (int o = 32; o >= 1; o >>= 1) {
-        d += ((uint64_t) (uint32_t) __shfl_xor((int) (d >> 32), o, 64) << 32) | (uint32_t) __shfl_xor((int) (uint32_t) d, o, 64);
-        u += ((uint64_t) (uint32_t) __shfl_xor((int) (u >> 32), o, 64) << 32) | (uint32_t) __shfl_xor((int) (uint32_t) u, o, 64);
-        tot += ((uint64_t) (uint32_t) __shfl_xor((int) (tot >> 32), o, 64) << 32) | (uint32_t) __shfl_xor((int) (uint32_t) tot, o, 64);
-    }
+    d = wave_sum_u64(d);
+    u = wave_sum_u64(u);
+    tot = wave_sum_u64(tot);
     if (lane_id() == 0) {
         if (d) atomicAdd((unsigned long long *) &scalars[0], (unsigned long long) d);
         if (u) atomicAdd((unsigned long long *) &scalars[1], (unsigned long long) u);
@@ -347,20 +318,22 @@ int materialize(kmu_counter *c) {
 // wipe it first) 19.2 against 36.9 at 1/16 of the slots, 16.0 against 23.4 at 1/32, 13.9 against 18.0 at 1/64.  One rule for every
 // way in (reads, k-mer arrays, super-k-mer records, the chunked host leg).
 bool partitioned_batch_wanted(const kmu_counter *c, uint64_t n) { return n * (c->empty ? 64u : 10u) >= c->nslots && n >= (1u << 16); }
+// the choice for a batch of n k-mers that the partitioned build can take (`eligible`); KMU_COUNT_PATH=direct / partitioned (tests) forces it
+static bool partitioned_chosen(const kmu_counter *c, uint64_t n, bool eligible) {
+    if (!eligible) return false;
+    if (const char *force = getenv("KMU_COUNT_PATH")) {
+        if (!strcmp(force, "direct")) return false;
+        if (!strcmp(force, "partitioned")) return true;
+    }
+    return partitioned_batch_wanted(c, n);
+}
 
 // the canonical k-mers of device-resident reads into THIS table: the streaming build for big batches of unpacked reads,
 // direct insertion otherwise (total_bases: extent of the flat stream, 0 for packed input)
 int local_add(kmu_counter *c, const DevSeqs &ds, uint64_t total_bases, uint32_t *d_err) {
     kmu_ctx *ctx = c->ctx;
     KMU_TRY(table_alloc_for(c, &ds, total_bases, d_err));
-    bool partitioned = false;
-    const char *force = getenv("KMU_COUNT_PATH"); // "direct" / "partitioned": tests
-    if (!ds.packed) {
-        partitioned = partitioned_batch_wanted(c, total_bases);
-        if (force && !strcmp(force, "direct")) partitioned = false;
-        if (force && !strcmp(force, "partitioned")) partitioned = total_bases > 0;
-    }
-    if (partitioned) return partitioned_add(c, ds, total_bases, d_err);
+    if (partitioned_chosen(c, total_bases, !ds.packed && total_bases > 0)) return partitioned_add(c, ds, total_bases, d_err);
     KMU_TRY(materialize(c));
     CountTable t = table_of(c);
     if (!ds.packed) {
@@ -439,15 +412,9 @@ int add_entries(kmu_counter *c, const uint64_t *kmers, const uint32_t *counts, u
     uint32_t *d_err;
     KMU_TRY(get_err_word(ctx, &d_err));
     KMU_TRY(table_alloc_for(c, nullptr, 0, d_err, 0.0, std::max<uint64_t>(c->p.capacity_hint, n)));
-    {
-        const char *force = getenv("KMU_COUNT_PATH");
-        bool partitioned = !counts && partitioned_batch_wanted(c, n);
-        if (force && !strcmp(force, "direct")) partitioned = false;
-        if (force && !strcmp(force, "partitioned")) partitioned = !counts;
-        if (partitioned) {
-            KMU_TRY(partitioned_add_kmers(c, d_k, n, d_err));
-            return finish_checked(ctx, mem, d_err);
-        }
+    if (partitioned_chosen(c, n, !counts)) {
+        KMU_TRY(partitioned_add_kmers(c, d_k, n, d_err));
+        return finish_checked(ctx, mem, d_err);
     }
     KMU_TRY(materialize(c));
     {
@@ -469,13 +436,9 @@ int add_superkmers(kmu_counter *c, const void *recs, uint64_t n_rec, uint64_t n_
     uint32_t *d_err;
     KMU_TRY(get_err_word(ctx, &d_err));
     KMU_TRY(table_alloc_for(c, nullptr, 0, d_err, 0.0, std::max<uint64_t>(c->p.capacity_hint, n_kmers)));
-    const char *force = getenv("KMU_COUNT_PATH");
-    bool partitioned = partitioned_batch_wanted(c, n_kmers);
-    if (force && !strcmp(force, "direct")) partitioned = false;
-    if (force && !strcmp(force, "partitioned")) partitioned = true;
     PartPlan pl;
     bool overflowed = false;
-    if (partitioned && part_plan_for(c, &pl) && pl.b1 && seg_partition_wanted(n_kmers)) {
+    if (partitioned_chosen(c, n_kmers, true) && part_plan_for(c, &pl) && pl.b1 && seg_partition_wanted(n_kmers)) {
         int taken = 0;
         KMU_TRY(seg_partitioned_add_kmers(c, nullptr, n_kmers, pl, d_err, &taken, recs, n_rec));
         if (taken) {
@@ -580,6 +543,22 @@ int select_entries(kmu_counter *c, uint32_t min_count, uint32_t maxc, uint32_t p
             memcpy(counts_out, c2.data(), n * 4);
         }
     }
+    return KMU_OK;
+}
+
+// the table rebuilt from its own entries of count >= min_count (owned by `part` of n_parts, when n_parts > 0)
+static int rebuild_from_selection(kmu_counter *c, uint32_t min_count, uint32_t part, uint32_t n_parts) {
+    kmu_ctx *ctx = c->ctx;
+    KMU_HIP(ctx, hipSetDevice(ctx->device));
+    uint64_t n = 0, n2 = 0; // raw counts, as kmu_count_export_part has them
+    KMU_TRY(select_entries(c, min_count, 0xFFFFFFFFu, part, n_parts, nullptr, nullptr, 0, KMU_MEM_DEVICE, false, &n));
+    void *k = nullptr, *cc = nullptr;
+    KMU_TRY(dev_buf(ctx, "cnt.keep.k", n * 8 + 8, &k));
+    KMU_TRY(dev_buf(ctx, "cnt.keep.c", n * 4 + 8, &cc));
+    KMU_TRY(select_entries(c, min_count, 0xFFFFFFFFu, part, n_parts, (uint64_t *) k, (uint32_t *) cc, n, KMU_MEM_DEVICE, false, &n2));
+    KMU_TRY(kmu_count_reset(c));
+    KMU_TRY(add_entries(c, (const uint64_t *) k, (const uint32_t *) cc, n2, KMU_MEM_DEVICE));
+    KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return KMU_OK;
 }
 
@@ -759,39 +738,13 @@ int kmu_count_export_part(kmu_counter *c, uint32_t part, uint32_t n_parts, uint6
 
 int kmu_count_retain_part(kmu_counter *c, uint32_t part, uint32_t n_parts) {
     if (!c || n_parts == 0 || part >= n_parts) return KMU_E_BAD_ARG;
-    kmu_ctx *ctx = c->ctx;
-    KMU_HIP(ctx, hipSetDevice(ctx->device));
-    uint64_t n = 0;
-    KMU_TRY(kmu_count_export_part(c, part, n_parts, nullptr, nullptr, 0, KMU_MEM_DEVICE, &n));
-    void *k = nullptr, *cc = nullptr;
-    KMU_TRY(dev_buf(ctx, "cnt.keep.k", n * 8 + 8, &k));
-    KMU_TRY(dev_buf(ctx, "cnt.keep.c", n * 4 + 8, &cc));
-    uint64_t n2 = 0;
-    KMU_TRY(kmu_count_export_part(c, part, n_parts, (uint64_t *) k, (uint32_t *) cc, n, KMU_MEM_DEVICE, &n2));
-    KMU_TRY(kmu_count_reset(c));
-    int rc = add_entries(c, (const uint64_t *) k, (const uint32_t *) cc, n2, KMU_MEM_DEVICE);
-    if (rc) return rc;
-    KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return KMU_OK;
+    return rebuild_from_selection(c, 1u, part, n_parts);
 }
 
 // KmerCounter::eliminate_once_kmer (kmercount.rs:110-117): the singletons are dropped, counts >= 2 stay
 int kmu_count_eliminate_once(kmu_counter *c) {
     if (!c) return KMU_E_BAD_ARG;
-    kmu_ctx *ctx = c->ctx;
-    KMU_HIP(ctx, hipSetDevice(ctx->device));
-    uint64_t n = 0;
-    KMU_TRY(select_entries(c, 2u, 0xFFFFFFFFu, 0, 0, nullptr, nullptr, 0, KMU_MEM_DEVICE, false, &n));
-    void *k = nullptr, *cc = nullptr;
-    KMU_TRY(dev_buf(ctx, "cnt.keep.k", n * 8 + 8, &k));
-    KMU_TRY(dev_buf(ctx, "cnt.keep.c", n * 4 + 8, &cc));
-    uint64_t n2 = 0;
-    KMU_TRY(select_entries(c, 2u, 0xFFFFFFFFu, 0, 0, (uint64_t *) k, (uint32_t *) cc, n, KMU_MEM_DEVICE, false, &n2));
-    KMU_TRY(kmu_count_reset(c));
-    int rc = add_entries(c, (const uint64_t *) k, (const uint32_t *) cc, n2, KMU_MEM_DEVICE);
-    if (rc) return rc;
-    KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return KMU_OK;
+    return rebuild_from_selection(c, 2u, 0, 0);
 }
 
 int kmu_count_once_positions(kmu_counter *c, const uint8_t *bases, const uint64_t *offsets, uint32_t n_seq, int mem,

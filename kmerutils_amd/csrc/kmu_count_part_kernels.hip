@@ -25,7 +25,7 @@ __global__ void __launch_bounds__(256) k_part_hist1(const uint8_t *bases, const 
     if (sa.list && threadIdx.x == 0) ls_n[0] = 0;
     __syncthreads();
     const uint64_t total = offsets[n_seq], start = offsets[0];
-    const uint64_t nsteps = ((total + 15) / 16 + 63) / 64;
+    const uint64_t nsteps = flat_wave_steps(total);
     const uint64_t s0 = (uint64_t) blockIdx.x * pl.steps_per_unit;
     const uint64_t s1 = s0 + pl.steps_per_unit < nsteps ? s0 + pl.steps_per_unit : nsteps;
     const int wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
@@ -430,21 +430,7 @@ __device__ __forceinline__ void tile_scatter_seg(uint64_t (&it)[16], const SegLd
     }
 }
 
-// the code words of wave step `st`: this lane's word and (lanes 0/1) the two words after the wave's last
-__device__ __forceinline__ void flat_step_load(const uint8_t *bases, uint64_t total, uint64_t st, bool active, uint32_t &w0,
-                                               uint32_t &ex, uint32_t *bad_acc = nullptr) {
-    w0 = 0;
-    ex = 0;
-    if (!active) return; // wave-uniform
-    SeqView s;
-    s.base = bases; s.begin = 0; s.len = total; s.total = total; s.packed = 0;
-    uint32_t bad, bad2;
-    w0 = load_code_word(s, st * 64 + (uint64_t) lane_id(), bad);
-    ex = load_code_word(s, st * 64 + 64 + (uint64_t) (lane_id() & 1), bad2);
-    if (bad_acc) *bad_acc |= bad; // (every word is some step's own word: the halo words need no second look)
-}
-
-// The same in two halves, for prefetching: flat_step_fetch requests the two aligned 16-byte chunks (this lane's word, the
+// flat_step_load (kmu_flat.h) in two halves, for prefetching: flat_step_fetch requests the two aligned 16-byte chunks (this lane's word, the
 // halo word of lane & 1) and the lane's 16 "no k-mer" bits (flat_novalid, kmu_smer.hpp), and nothing looks at them until
 // flat_step_words turns them into code words one tile later -- the requests are UNCONDITIONAL loads from clamped addresses
 // (needs total >= 16), so that their number in flight is a constant for the compiler's s_waitcnt placement (a load under a
@@ -490,42 +476,8 @@ __device__ __forceinline__ void flat_step_items(const uint64_t *offsets, uint32_
 #pragma unroll
     for (int j = 0; j < 16; j++) it[j] = CKEY_EMPTY;
     if (!active) return; // wave-uniform
-    const int lane = lane_id();
-    const uint64_t widx = st * 64 + lane;
-    uint32_t e0 = bcast_u32(ex, 0), e1 = bcast_u32(ex, 1);
-    uint32_t w1 = shfl_down_u32(w0, 1), w2 = shfl_down_u32(w0, 2);
-    if (lane == 63) { w1 = e0; w2 = e1; }
-    if (lane == 62) { w2 = e0; }
-    const uint64_t g0 = widx * 16;
-    const bool in = g0 < total && g0 + 16 > start;
-    uint64_t rend = 0;
-    uint32_t r = wave_find_read_from(offsets, n_seq, st * 1024 < total ? st * 1024 : total - 1, r_hint);
-    r_hint = r;
-    if (in) {
-        rend = offsets[r + 1];
-        while (g0 >= rend && r + 1 < n_seq) { r++; rend = offsets[r + 1]; } // the read of this lane's first base
-    }
-    const uint64_t hi = ((uint64_t) w0 << 32) | w1; // (this form keeps the reverse complement per k-mer: the exact levels' kernel has no registers for the window's)
-    const int sh = 64 - 2 * k;
-    if (__all(!in || (g0 >= start && rend - g0 >= (uint64_t) (15 + k)))) { // every lane well inside a read: no per-k-mer boundary tests
-        if (in) {
-#pragma unroll
-            for (int j = 0; j < 16; j++) {
-                const uint64_t val = ((hi << (2 * j)) | (((uint64_t) w2 << (2 * j)) >> 32)) >> sh, rc = revcomp_val(val, k);
-                it[j] = rc < val ? rc : val;
-            }
-        }
-    } else if (in) {
-#pragma unroll
-        for (int j = 0; j < 16; j++) {
-            const uint64_t g = g0 + j;
-            while (g >= rend && r + 1 < n_seq) { r++; rend = offsets[r + 1]; }
-            if (g >= start && g + k <= rend) {
-                const uint64_t val = ((hi << (2 * j)) | (((uint64_t) w2 << (2 * j)) >> 32)) >> sh, rc = revcomp_val(val, k);
-                it[j] = rc < val ? rc : val;
-            }
-        }
-    }
+    // (the step keeps the reverse complement per k-mer: the exact levels' kernel has no registers for the window's)
+    flat_step_visit_words<true>(offsets, n_seq, total, start, k, st, w0, ex, r_hint, [&](int j, uint64_t canon, uint32_t) { it[j] = canon; });
 }
 
 // the same from the lane's "no k-mer" bits: no read offsets, no search, no dependent look-up; a wave whose lanes are all-or-nothing
@@ -534,11 +486,8 @@ __device__ __forceinline__ void flat_step_items_nv(int k, bool active, uint32_t 
 #pragma unroll
     for (int j = 0; j < 16; j++) it[j] = CKEY_EMPTY;
     if (!active) return; // wave-uniform
-    const int lane = lane_id();
-    uint32_t e0 = bcast_u32(ex, 0), e1 = bcast_u32(ex, 1);
-    uint32_t w1 = shfl_down_u32(w0, 1), w2 = shfl_down_u32(w0, 2);
-    if (lane == 63) { w1 = e0; w2 = e1; }
-    if (lane == 62) { w2 = e0; }
+    uint32_t w1, w2;
+    flat_window(w0, ex, w1, w2);
     const uint32_t V = ~nv & 0xFFFFu;
     const StepWin sw = step_win(w0, w1, w2, k);
     if (__all(V == 0xFFFFu || V == 0u)) {
@@ -567,7 +516,7 @@ __global__ void __launch_bounds__(1024) k_part_scatter1_exact(const uint8_t *bas
     if (threadIdx.x == 0) l.lstart[bins1] = 0;
     lds_barrier();
     const uint64_t total = offsets[n_seq], start = offsets[0];
-    const uint64_t nsteps = ((total + 15) / 16 + 63) / 64;
+    const uint64_t nsteps = flat_wave_steps(total);
     const uint64_t s0 = (uint64_t) blockIdx.x * pl.steps_per_unit;
     const uint64_t s1 = s0 + pl.steps_per_unit < nsteps ? s0 + pl.steps_per_unit : nsteps;
     const int wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
@@ -601,7 +550,7 @@ __global__ void __launch_bounds__(1024) k_part_scatter1(const uint8_t *bases, co
     for (uint32_t b = threadIdx.x; b < bins1 + 2; b += blockDim.x) ls.cnt[b] = 0;
     lds_barrier();
     const uint64_t total = offsets[n_seq];
-    const uint64_t nsteps_all = ((total + 15) / 16 + 63) / 64;
+    const uint64_t nsteps_all = flat_wave_steps(total);
     const uint64_t nsteps = seg.step_end ? seg.step_end : nsteps_all;
     const uint64_t s0 = seg.step_base + (uint64_t) blockIdx.x * pl.steps_per_unit;
     const uint64_t s1 = s0 + pl.steps_per_unit < nsteps ? s0 + pl.steps_per_unit : nsteps;

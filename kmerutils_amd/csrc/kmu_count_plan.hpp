@@ -9,8 +9,9 @@
 
 namespace kmu {
 
-// wave steps of a flat stream of `bases` bases: a lane takes a 16-base word, a wave 64 of them (the kernels compute the same)
-inline uint64_t flat_wave_steps(uint64_t bases) { return ((bases + 15) / 16 + 63) / 64; }
+// wave steps of a flat stream of `bases` bases: a lane takes a 16-base word, a wave 64 of them.  constexpr: the kernels call it
+// too (hipcc compiles a constexpr function for host and device alike), g++ sees plain C++.
+constexpr uint64_t flat_wave_steps(uint64_t bases) { return ((bases + 15) / 16 + 63) / 64; }
 
 // The wave steps of a stream dealt out to at most `unit_cap` units (workgroups) of steps_per_unit consecutive steps each; no
 // steps at all: one unit of one step.  asked: the unit count before it is re-rounded to what steps_per_unit leaves (the

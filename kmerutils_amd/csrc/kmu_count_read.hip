@@ -6,7 +6,7 @@
 //  * k_count_hist: one streaming pass over the slots (the shape of k_count_stats).  Counts 1 and 2 -- most of a real spectrum -- are
 //    counted in registers, the other counts below 256 in per-wave LDS sub-histograms, the rare ones above in global memory; one
 //    64-bit global add per non-zero bin and block at the end.
-//  * k_count_profile: the flat-stream walk of once_step (kmu_count.hip), one look-up per k-mer, the clamped count stored as uint16.
+//  * k_count_profile: the flat-stream wave step (kmu_flat.h), one look-up per k-mer, the clamped count stored as uint16.
 //  * k_profile_stats: per read, from the uint16 counts: wave reductions, and the exact median by counting (a 256-bin LDS histogram
 //    of the high byte, then of the low byte inside the selected bin; 8-bit counters: one round).  Two shapes, chosen per read:
 //    one WAVE per read up to PROFILE_SHORT_MAX k-mers, one BLOCK per read above.
@@ -44,10 +44,8 @@ __global__ void __launch_bounds__(256) k_count_hist(CountTable t, uint64_t nslot
             else atomicAdd(&hist[v], 1ull); // (16-bit counters only, and rare)
         }
     }
-    for (int o = 32; o >= 1; o >>= 1) {
-        n1 += (uint32_t) __shfl_xor((int) n1, o, 64);
-        n2 += (uint32_t) __shfl_xor((int) n2, o, 64);
-    }
+    n1 = wave_sum_u32(n1);
+    n2 = wave_sum_u32(n2);
     if (lane_id() == 0) {
         sub[wave][1] = n1; // (bins 1 and 2 of the sub-histograms are written here only)
         if (last_bin >= 2u) sub[wave][2] = n2;
@@ -74,53 +72,34 @@ __global__ void __launch_bounds__(256) k_count_profile(const uint8_t *bases, con
     if (hi > total) hi = total;
     const uint64_t wave_global = ((uint64_t) blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const uint64_t nwaves_global = ((uint64_t) gridDim.x * blockDim.x) >> 6;
-    const int lane = lane_id();
-    SeqView s;
-    s.base = bases; s.begin = 0; s.len = total; s.total = total; s.packed = 0;
     uint32_t r_hint = 0xFFFFFFFFu, anybad = 0;
     for (uint64_t st = st0 + wave_global; st < st1; st += nwaves_global) {
-        const uint64_t widx = st * 64 + lane;
-        uint32_t bad, bad2;
-        uint32_t w0 = load_code_word(s, widx, bad);
-        uint32_t ex = load_code_word(s, st * 64 + 64 + (uint64_t) (lane & 1), bad2);
-        uint32_t e0 = bcast_u32(ex, 0), e1 = bcast_u32(ex, 1);
-        uint32_t w1 = shfl_down_u32(w0, 1), w2 = shfl_down_u32(w0, 2);
-        if (lane == 63) { w1 = e0; w2 = e1; }
-        if (lane == 62) { w2 = e0; }
-        uint32_t r = wave_find_read_from(offsets, n_seq, st * 1024 < total ? st * 1024 : total - 1, r_hint);
-        r_hint = r;
-        const uint64_t g0 = widx * 16;
-        if (!(g0 < hi && g0 + 16 > lo)) continue;
-        if (bad) { // only the bytes of [lo, hi) are this call's
+        const uint64_t g0 = (st * 64 + (uint64_t) lane_id()) * 16;
+        // the lanes of this call: g0 < hi && g0 + 16 > lo.  The step is the whole wave's and tests the second half itself; a lane
+        // at or past hi gets its callbacks and drops them.
+        const bool mine = g0 < hi;
+        uint32_t pk[8] = {0, 0, 0, 0, 0, 0, 0, 0}, mask = 0;
+        const uint32_t bad = flat_step_visit<false>(bases, offsets, n_seq, total, lo, k, st, r_hint, [&](int j, uint64_t canon, uint32_t) {
+            if (!mine) return;
+            uint32_t c = 0;
+            if (!empty) {
+                c = count_lookup(t, canon);
+                c = c > maxc ? maxc : c;
+            }
+            pk[j >> 1] |= c << (16 * (j & 1));
+            mask |= 1u << j;
+        });
+        if (bad && mine && g0 + 16 > lo) { // only the bytes of [lo, hi) are this call's
             const uint32_t blo = lo > g0 ? (uint32_t) (lo - g0) : 0u, bhi = hi - g0 > 16 ? 16u : (uint32_t) (hi - g0);
             anybad |= bad & ((1u << bhi) - 1u) & ~((1u << blo) - 1u);
         }
-        uint64_t rend = offsets[r + 1];
-        const uint64_t hi64 = ((uint64_t) w0 << 32) | w1;
-        const int sh = 64 - 2 * k;
-        uint32_t pk[8] = {0, 0, 0, 0, 0, 0, 0, 0}, mask = 0;
-#pragma unroll
-        for (int j = 0; j < 16; j++) {
-            const uint64_t g = g0 + j;
-            while (g >= rend && r + 1 < n_seq) { r++; rend = offsets[r + 1]; }
-            if (g >= lo && g + k <= rend) {
-                uint32_t c = 0;
-                if (!empty) {
-                    const uint64_t v = (hi64 << (2 * j)) | (((uint64_t) w2 << (2 * j)) >> 32);
-                    const uint64_t val = v >> sh, rc = revcomp_val(val, k);
-                    c = count_lookup(t, rc < val ? rc : val);
-                    c = c > maxc ? maxc : c;
-                }
-                pk[j >> 1] |= c << (16 * (j & 1));
-                mask |= 1u << j;
-            }
-        }
+        if (!mask) continue;
         uint16_t *o = counts + (g0 - cbase);
         if (mask == 0xFFFFu && vec) {
             uint4 *o4 = reinterpret_cast<uint4 *>(o);
             o4[0] = make_uint4(pk[0], pk[1], pk[2], pk[3]);
             o4[1] = make_uint4(pk[4], pk[5], pk[6], pk[7]);
-        } else if (mask) {
+        } else {
 #pragma unroll
             for (int j = 0; j < 16; j++)
                 if ((mask >> j) & 1u) o[j] = (uint16_t) (pk[j >> 1] >> (16 * (j & 1)));
@@ -161,17 +140,6 @@ __device__ __forceinline__ uint32_t wave_select256(const uint32_t *h, uint32_t r
     below = bcast_u32(bel, src);
     return bcast_u32(bin + 4u * (uint32_t) lane, src);
 }
-
-__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
-    for (int o = 32; o >= 1; o >>= 1) v += (uint32_t) __shfl_xor((int) v, o, 64);
-    return v;
-}
-__device__ __forceinline__ uint64_t wave_sum_u64(uint64_t v) {
-    for (int o = 32; o >= 1; o >>= 1)
-        v += ((uint64_t) (uint32_t) __shfl_xor((int) (v >> 32), o, 64) << 32) | (uint32_t) __shfl_xor((int) (uint32_t) v, o, 64);
-    return v;
-}
-__device__ __forceinline__ uint32_t wave_min_u32(uint32_t v) { return ~wave_max_u32(~v); }
 
 // what the waves of a block hand each other (block shape)
 struct ProfShared {

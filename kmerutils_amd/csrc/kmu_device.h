@@ -376,6 +376,27 @@ __device__ __forceinline__ uint64_t wave_max_u64(uint64_t v) {
     }
     return v;
 }
+__device__ __forceinline__ uint32_t wave_min_u32(uint32_t v) { return ~wave_max_u32(~v); }
+// sums over the 64 lanes, in every lane
+__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
+    for (int o = 32; o >= 1; o >>= 1) v += (uint32_t) __shfl_xor((int) v, o, 64);
+    return v;
+}
+__device__ __forceinline__ uint64_t wave_sum_u64(uint64_t v) {
+    for (int o = 32; o >= 1; o >>= 1)
+        v += ((uint64_t) (uint32_t) __shfl_xor((int) (v >> 32), o, 64) << 32) | (uint32_t) __shfl_xor((int) (uint32_t) v, o, 64);
+    return v;
+}
+// The 48-base window of a lane in a wave step of 64 code words: its own word w0 and the two after it, w1 and w2, from the
+// neighbouring lanes.  `ex` holds, in lanes 0 and 1, the two halo words that follow the wave's last: lane 63 takes both, lane 62 the first.
+__device__ __forceinline__ void flat_window(uint32_t w0, uint32_t ex, uint32_t &w1, uint32_t &w2) {
+    const int lane = lane_id();
+    const uint32_t e0 = bcast_u32(ex, 0), e1 = bcast_u32(ex, 1);
+    w1 = shfl_down_u32(w0, 1);
+    w2 = shfl_down_u32(w0, 2);
+    if (lane == 63) { w1 = e0; w2 = e1; }
+    if (lane == 62) { w2 = e0; }
+}
 
 // ---------------------------------------------------------------------------------------------------
 // Streaming one sequence through a wave: 64 lanes x 16 bases per step.

@@ -1,6 +1,8 @@
-// kmu_flat.h -- the reads of a batch as ONE flat stream of bases: which read holds a given base (device code).
+// kmu_flat.h -- the reads of a batch as ONE flat stream of bases (device code): which read holds a given base, and the wave step
+// that every kernel walking the stream is written on (flat_step_visit_words; flat_wave_steps of kmu_count_plan.hpp counts the steps).
 #pragma once
 
+#include "kmu_count_plan.hpp"
 #include "kmu_device.h"
 
 namespace kmu {
@@ -31,55 +33,84 @@ __device__ __forceinline__ uint32_t wave_find_read_from(const uint64_t *offsets,
     return wave_find_read(offsets, n, g);
 }
 
-// One wave step (64 words = 1024 bases) of the flat base stream: f(canon) for every k-mer that lies inside one read
-// (kmer.reverse_complement().min(kmer), kmercount.rs:938).  Returns a non-zero mask if this lane saw a non-ACGT byte.
-// The reads occupy [offsets[0], total) of the stream: `start` = offsets[0] need not be 0 (a range of a larger read set).
-template <typename F>
-__device__ __forceinline__ uint32_t flat_step_canon(const uint8_t *bases, const uint64_t *offsets, uint32_t n_seq,
-                                                    uint64_t total, uint64_t start, int k, uint64_t st, uint32_t &r_hint, F &&f) {
+// the code words of wave step `st`: this lane's word and (lanes 0/1) the two words after the wave's last
+__device__ __forceinline__ void flat_step_load(const uint8_t *bases, uint64_t total, uint64_t st, bool active, uint32_t &w0,
+                                               uint32_t &ex, uint32_t *bad_acc = nullptr) {
+    w0 = 0;
+    ex = 0;
+    if (!active) return; // wave-uniform
     SeqView s;
     s.base = bases; s.begin = 0; s.len = total; s.total = total; s.packed = 0;
-    const int lane = lane_id();
-    const uint64_t widx = st * 64 + lane;
     uint32_t bad, bad2;
-    uint32_t w0 = load_code_word(s, widx, bad);
-    uint32_t ex = load_code_word(s, st * 64 + 64 + (uint64_t) (lane & 1), bad2);
-    uint32_t e0 = bcast_u32(ex, 0), e1 = bcast_u32(ex, 1);
-    uint32_t w1 = shfl_down_u32(w0, 1), w2 = shfl_down_u32(w0, 2);
-    if (lane == 63) { w1 = e0; w2 = e1; }
-    if (lane == 62) { w2 = e0; }
+    w0 = load_code_word(s, st * 64 + (uint64_t) lane_id(), bad);
+    ex = load_code_word(s, st * 64 + 64 + (uint64_t) (lane_id() & 1), bad2);
+    if (bad_acc) *bad_acc |= bad; // (every word is some step's own word: the halo words need no second look)
+}
+
+// One wave step (64 words = 1024 bases) of the flat base stream, from its loaded words (flat_step_load): f(j, canon, r) for
+// every k-mer start g = (st * 64 + lane) * 16 + j of this lane with g >= lo whose k-mer lies inside one read, g + k <= the end
+// of the read r that holds base g.  canon: kmer.reverse_complement().min(kmer), kmercount.rs:938.  The reads occupy
+// [offsets[0], total) of the stream; offsets[0] need not be 0 (a range of a larger read set) and callers pass lo >= offsets[0].
+// The whole wave calls it.  FAST: a wave whose lanes all sit well inside a read (long reads: most waves) skips the per-k-mer
+// boundary tests; r is the lane's read there too.
+template <bool FAST, typename F>
+__device__ __forceinline__ void flat_step_visit_words(const uint64_t *offsets, uint32_t n_seq, uint64_t total, uint64_t lo, int k,
+                                                      uint64_t st, uint32_t w0, uint32_t ex, uint32_t &r_hint, F &&f) {
+    uint32_t w1, w2;
+    flat_window(w0, ex, w1, w2);
+    // the read of the wave's first base (read 0 where the step begins before offsets[0]).  The search wants a base below `total`:
+    // a step that begins at or past the end of the stream (no caller's loop gets there) would look for the last base
     uint32_t r = wave_find_read_from(offsets, n_seq, st * 1024 < total ? st * 1024 : total - 1, r_hint);
     r_hint = r;
-    const uint64_t g0 = widx * 16;
-    const bool in = g0 < total && g0 + 16 > start;
-    uint64_t rend = 0;
-    if (in) {
-        rend = offsets[r + 1];
-        while (g0 >= rend && r + 1 < n_seq) { r++; rend = offsets[r + 1]; } // the read of this lane's first base
-    }
+    const uint64_t g0 = (st * 64 + (uint64_t) lane_id()) * 16;
+    const bool in = g0 < total && g0 + 16 > lo;
+    uint64_t rend = in ? offsets[r + 1] : 0;
+    // on to the read that holds base g.  The last lane's starts may lie at or past `total`, where no read ends beyond g: the
+    // bound r + 1 < n_seq stops at the last read and keeps offsets[r + 1] inside the array.
+    auto advance = [&](uint64_t g) {
+        while (g >= rend && r + 1 < n_seq) { r++; rend = offsets[r + 1]; }
+    };
     const uint64_t hi = ((uint64_t) w0 << 32) | w1;
     const int sh = 64 - 2 * k;
-    // A wave whose lanes all sit well inside a read (long reads: most waves) skips the per-k-mer boundary tests.
-    if (__all(!in || (g0 >= start && rend - g0 >= (uint64_t) (15 + k)))) {
-        if (in) {
+    auto canon = [&](int j) {
+        const uint64_t val = ((hi << (2 * j)) | (((uint64_t) w2 << (2 * j)) >> 32)) >> sh, rc = revcomp_val(val, k);
+        return rc < val ? rc : val;
+    };
+    if (FAST) {
+        if (in) advance(g0); // the read of this lane's first base
+        if (__all(!in || (g0 >= lo && rend - g0 >= (uint64_t) (15 + k)))) {
+            if (in) {
 #pragma unroll
-            for (int j = 0; j < 16; j++) {
-                const uint64_t val = ((hi << (2 * j)) | (((uint64_t) w2 << (2 * j)) >> 32)) >> sh, rc = revcomp_val(val, k);
-                f(rc < val ? rc : val);
+                for (int j = 0; j < 16; j++) f(j, canon(j), r);
             }
+            return;
         }
-    } else if (in) {
+    }
+    if (in) {
 #pragma unroll
         for (int j = 0; j < 16; j++) {
             const uint64_t g = g0 + j;
-            while (g >= rend && r + 1 < n_seq) { r++; rend = offsets[r + 1]; }
-            if (g >= start && g + k <= rend) {
-                const uint64_t val = ((hi << (2 * j)) | (((uint64_t) w2 << (2 * j)) >> 32)) >> sh, rc = revcomp_val(val, k);
-                f(rc < val ? rc : val);
-            }
+            advance(g);
+            if (g >= lo && g + k <= rend) f(j, canon(j), r);
         }
     }
+}
+
+// the same from the bases: load + visit.  Returns a non-zero mask if this lane saw a non-ACGT byte.
+template <bool FAST, typename F>
+__device__ __forceinline__ uint32_t flat_step_visit(const uint8_t *bases, const uint64_t *offsets, uint32_t n_seq, uint64_t total,
+                                                    uint64_t lo, int k, uint64_t st, uint32_t &r_hint, F &&f) {
+    uint32_t w0, ex, bad = 0;
+    flat_step_load(bases, total, st, true, w0, ex, &bad);
+    flat_step_visit_words<FAST>(offsets, n_seq, total, lo, k, st, w0, ex, r_hint, f);
     return bad;
+}
+
+// f(canon) for every k-mer of the step
+template <typename F>
+__device__ __forceinline__ uint32_t flat_step_canon(const uint8_t *bases, const uint64_t *offsets, uint32_t n_seq,
+                                                    uint64_t total, uint64_t start, int k, uint64_t st, uint32_t &r_hint, F &&f) {
+    return flat_step_visit<true>(bases, offsets, n_seq, total, start, k, st, r_hint, [&](int, uint64_t canon, uint32_t) { f(canon); });
 }
 
 } // namespace kmu

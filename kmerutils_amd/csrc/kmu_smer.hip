@@ -135,7 +135,7 @@ __global__ void __launch_bounds__(256) k_smer_novalid(const uint64_t *offsets, u
 }
 
 // what a wave step needs from memory, requested a step ahead: the lane's 16 bases and its 16 "no k-mer" bits.  Unconditional
-// loads from clamped addresses: their number in flight is a constant for the compiler's waits (see flat_step_fetch, kmu_count.hip).
+// loads from clamped addresses: their number in flight is a constant for the compiler's waits (see flat_step_fetch, kmu_count_part_kernels.hip).
 struct SmerRaw {
     uint4 c;
     uint32_t nv;
