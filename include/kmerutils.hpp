@@ -20,6 +20,7 @@
  *                 BlockSeqSketcher, BlockSketched, BlockSketchedSeq, DistBlockSketched
  *                                                            src/sketching/seqblocksketch.rs:38-227, 419-440
  *                 MinInvHashCountKmer, minhash_distance      src/sketching/minhash.rs:134-340
+ *   anchors       AnchorsGeneratorParameters, SliceAnchor, ReadAnchors, gen_read_anchors   src/anchor.rs:29-329
  *   counting      KmerCountT (trait), KmerCounter, KmerCounterPool, count_kmer_threaded_one_to_many
  *                                                            src/base/kmercount.rs:48-123, 424-565, 881-974
  *   io            FASTQ reader rule, signature / count dumps src/io.rs:12-72, src/bin/datasketcher.rs:358-388,
@@ -1358,6 +1359,94 @@ inline MinHashDist minhash_distance(const std::vector<HashCount> &sk1, const std
     ctx.check(kmu_minhash_distance_pairs(ctx.raw(), ha.data(), 1, hb.data(), 1, uint32_t(ha.size()), &zero, &zero, 1,
                                          KMU_MEM_HOST, out));
     return MinHashDist{double(out[0]) / double(out[2]), double(out[0]) / double(out[1]), out[0], out[1]};
+}
+
+// =====================================================================================================================
+// read anchors (anchor.rs, without its redis storage)
+// =====================================================================================================================
+
+/// AnchorsGeneratorParameters::new(fasta_name, window, nbkmer, kmer_size, overlap) (anchor.rs:29-78)
+class AnchorsGeneratorParameters {
+  public:
+    AnchorsGeneratorParameters(std::string fasta_name, uint32_t window, uint32_t nbkmer, uint16_t kmer_size, uint32_t overlap)
+        : fasta_name_(std::move(fasta_name)), window_(window), nbkmer_(nbkmer), overlap_(overlap), kmer_size_(kmer_size) {}
+    const std::string &get_fasta_name() const { return fasta_name_; }
+    uint32_t get_window() const { return window_; }
+    uint32_t get_nbkmer() const { return nbkmer_; }
+    uint16_t get_kmer_size() const { return kmer_size_; }
+    uint32_t get_overlap() const { return overlap_; }
+
+  private:
+    std::string fasta_name_;
+    uint32_t window_, nbkmer_, overlap_;
+    uint16_t kmer_size_;
+};
+
+/// SliceAnchor<Kmer> (anchor.rs:97-105): one window of a read -- the read, the first base of the slice, and its (hash, count)
+/// pairs ascending by hash (empty for a slice that holds no k-mer)
+template <class Kmer> struct SliceAnchor {
+    uint32_t readnum;
+    uint32_t slicepos;
+    std::vector<InvHashCount> minhash;
+    /// the slice's key in the inverse index (get_minhash_key_for_redis, anchor.rs:149-158)
+    uint64_t get_minhash_key() const { return minhash.at(0).hashed; }
+};
+
+/// ReadAnchors<Kmer> (anchor.rs:265-329): the slices of one read
+template <class Kmer> struct ReadAnchors {
+    uint32_t readnum;
+    std::vector<SliceAnchor<Kmer>> anchors;
+    size_t get_nb_slice() const { return anchors.size(); }
+};
+
+/// ReadAnchors::generate_anchors for every read of a batch in one library call (kmu_read_anchors): read i is numbered
+/// numfirst + i.  The defaults are the reference's MinInvHashCountKmer (forward k-mers, int64_hash of the compressed value,
+/// u8 counts); FHash::canon_value gives strand-independent anchors.
+template <class Kmer>
+std::vector<ReadAnchors<Kmer>> gen_read_anchors(const AnchorsGeneratorParameters &params, size_t numfirst, const detail::Batch &batch,
+                                                FHash fhash = FHash::value_masked, int hasher = KMU_HASHER_INT64HASH,
+                                                Context &ctx = Context::global()) {
+    const detail::Batch b = detail::unpacked(batch);
+    const size_t m = params.get_nbkmer();
+    std::vector<uint64_t> rows(b.n() + 1);
+    ctx.check(kmu_anchor_layout(b.offsets.data(), b.n(), params.get_window(), params.get_overlap(), rows.data()));
+    kmu_sketch_params p = detail::sketch_params(KMU_ALGO_BOTTOMK, Kmer::kmu_type, params.get_kmer_size(), m, KMU_SIG_U64, hasher,
+                                                int(fhash), 0, KMU_MODE_PER_SEQ, KMU_INPUT_ASCII);
+    p.mem = b.mem();
+    const size_t n_rows = size_t(std::max<uint64_t>(rows.back(), 1));
+    std::vector<uint64_t> h(n_rows * m);
+    std::vector<uint32_t> c(n_rows * m), n(n_rows);
+    if (b.on_device()) {
+        DeviceBuffer d_rows(ctx, rows.size() * 8), d_h(ctx, h.size() * 8), d_c(ctx, c.size() * 4), d_n(ctx, n.size() * 4);
+        d_rows.upload(rows.data(), rows.size() * 8);
+        ctx.check(kmu_read_anchors(ctx.raw(), &p, b.dev_bytes, b.dev_offsets, b.n(), params.get_window(), params.get_overlap(),
+                                   d_rows.as<uint64_t>(), d_h.as<uint64_t>(), d_c.as<uint32_t>(), d_n.as<uint32_t>()));
+        if (rows.back()) {
+            d_h.download(h.data(), h.size() * 8);
+            d_c.download(c.data(), c.size() * 4);
+            d_n.download(n.data(), n.size() * 4);
+        }
+    } else {
+        ctx.check(kmu_read_anchors(ctx.raw(), &p, b.bytes.data(), b.offsets.data(), b.n(), params.get_window(), params.get_overlap(),
+                                   rows.data(), h.data(), c.data(), n.data()));
+    }
+    const uint32_t stride = params.get_window() - params.get_overlap();
+    std::vector<ReadAnchors<Kmer>> out(b.n());
+    for (uint32_t i = 0; i < b.n(); i++) {
+        out[i].readnum = uint32_t(numfirst + i);
+        for (uint64_t r = rows[i]; r < rows[i + 1]; r++) {
+            SliceAnchor<Kmer> s{uint32_t(numfirst + i), uint32_t((r - rows[i]) * stride), {}};
+            for (uint32_t t = 0; t < n[r]; t++) s.minhash.push_back({h[r * m + t], uint16_t(c[r * m + t])});
+            out[i].anchors.push_back(std::move(s));
+        }
+    }
+    return out;
+}
+template <class Kmer>
+std::vector<ReadAnchors<Kmer>> gen_read_anchors(const AnchorsGeneratorParameters &params, size_t numfirst,
+                                                const std::vector<const Sequence *> &seqs, FHash fhash = FHash::value_masked,
+                                                int hasher = KMU_HASHER_INT64HASH, Context &ctx = Context::global()) {
+    return gen_read_anchors<Kmer>(params, numfirst, detail::gather(seqs), fhash, hasher, ctx);
 }
 
 // =====================================================================================================================

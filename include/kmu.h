@@ -311,6 +311,42 @@ int kmu_sketch_groups(kmu_ctx *ctx, const kmu_sketch_params *p, const uint8_t *b
  * offsets in host memory */
 int kmu_block_layout(const uint64_t *offsets, uint32_t n_seq, uint32_t block_size, uint64_t *block_row_offsets_out);
 
+/* ---- read anchors: bottom-k sketches of overlapping windows of every read -----------------------------------------
+ * ReadAnchors / AnchorsGeneratorParameters (src/anchor.rs:228-329): a read of L bases is cut into slices of `window` bases
+ * that overlap by `overlap` bases (stride = window - overlap; window > 0 and window > overlap, anchor.rs:295-296, else
+ * KMU_E_BAD_ARG).  Slice s starts at beg = s * stride for every beg < L (anchor.rs:307-318): ceil(L / stride) slices, none for
+ * L = 0 (not an error).  Its range is [beg, end) with end = min(beg + window, L - 1) (anchor.rs:242: the reference's
+ * `seq.size() - 1` is kept, the last base of a read lies in no anchor), its k-mers those lying wholly inside the range
+ * (IterSequence::set_range, sequence.rs:562-585): max(0, end - beg - k + 1) of them.
+ * The row of a slice is bit for bit the row (and the counts) kmu_sketch gives for the bases [beg, end) handed over as a
+ * sequence of their own with KMU_ALGO_BOTTOMK: the p->sketch_size (the reference's nbkmer) smallest hasher(fhash(kmer))
+ * ascending, padded with UINT64_MAX; counts of padded entries are 0.  The reference's own anchors (MinInvHashCountKmer,
+ * minhash.rs:204-289) are KMU_HASHER_INT64HASH + KMU_FHASH_VALUE_MASKED (u8 counts that wrap); every hasher / fhash pair
+ * kmu_sketch accepts for BOTTOMK on DNA k-mers is accepted.  Column 0 of a non-empty row is the slice's index key
+ * (get_minhash_key_for_redis, anchor.rs:149-158).
+ * DEVIATION (the only one): a slice with end - beg < k -- beg == end included, which happens when L = 1 (mod stride) and
+ * makes the reference panic (kmergenerator.rs:283-285) -- gets an empty row: all padding, n = 0.
+ * Rows: anchor_row_offsets[i] .. anchor_row_offsets[i + 1] are the slices of read i, in order (kmu_anchor_layout).
+ *   KMU_MEM_HOST: the library checks anchor_row_offsets against its own layout (KMU_E_BAD_ARG before any kernel runs).
+ *   KMU_MEM_DEVICE: anchor_row_offsets lives where `offsets` lives and is trusted as kmu_sketch trusts block_row_offsets.
+ * p: algo KMU_ALGO_BOTTOMK and block_size 0 (else KMU_E_BAD_ARG), 1 <= sketch_size <= KMU_ANCHOR_MAX_NBKMER (above:
+ * KMU_E_UNSUPPORTED), input_kind KMU_INPUT_ASCII (KMU_INPUT_PACKED2: KMU_E_UNSUPPORTED), a DNA k-mer type (amino acids:
+ * KMU_E_BAD_ALPHABET); p->mode is ignored.  A non-ACGT byte anywhere in a read is KMU_E_NON_ACGT, reported as kmu_sketch
+ * reports it (sticky in async_device contexts).  More than 2^32 - 1 rows: KMU_E_UNSUPPORTED.  n_seq == 0 or no row at all:
+ * KMU_OK, nothing is written.
+ * One kernel launch per call whatever the number of reads and windows; a row reads its bases from the batch's base array
+ * (nothing is copied per window) and selects in tiles of KMU_ANCHOR_TILE_KMERS k-mers, so no window size is refused. */
+#define KMU_ANCHOR_MAX_NBKMER 256
+#define KMU_ANCHOR_TILE_KMERS 768
+/* rows per read: ceil(L_i / (window - overlap)); row_offsets_out[n_seq + 1]; host memory, like kmu_block_layout.  Plain host
+ * C: no context, no device. */
+int kmu_anchor_layout(const uint64_t *offsets, uint32_t n_seq, uint32_t window, uint32_t overlap, uint64_t *row_offsets_out);
+int kmu_read_anchors(kmu_ctx *ctx, const kmu_sketch_params *p, const uint8_t *bases, const uint64_t *offsets, uint32_t n_seq,
+                     uint32_t window, uint32_t overlap, const uint64_t *anchor_row_offsets,
+                     uint64_t *hashes_out,   /* rows x p->sketch_size */
+                     uint32_t *counts_out,   /* rows x p->sketch_size, may be NULL */
+                     uint32_t *n_out);       /* rows: valid entries of each row, may be NULL */
+
 /* The reads ONCE, both results: the per-sequence signatures of kmu_sketch and the k-mer counts of kmu_count_add_reads for
  * one batch of unpacked reads -- the reference's alternation "read a pack of sequences, sketch it" (src/bin/datasketcher.rs:
  * 243-260) and its counting pass (src/bin/parsefastq.rs:215-236) as one stream-ordered pipeline.

@@ -1,0 +1,133 @@
+"""Read anchors: bottom-k sketches of overlapping windows of reads (the reference's src/anchor.rs, without its redis storage).
+
+`gen_read_anchors` runs kmu_read_anchors over a batch of reads; `ReadAnchors` / `SliceAnchor` are views over the arrays it
+returns, named like the reference's structs; `anchors_by_minhash` is the inverse index min hash -> [(readnum, slicepos)] that
+the reference's `redis_dump` stores under MINHASH_1, as a plain dict on the host.
+"""
+import numpy as np
+
+from . import _abi as A
+from . import parsefastq
+
+
+class AnchorsGeneratorParameters:
+    """AnchorsGeneratorParameters::new(fasta_name, window, nbkmer, kmer_size, overlap) (anchor.rs:29-78)"""
+
+    def __init__(self, fasta_name, window, nbkmer, kmer_size, overlap):
+        self.fasta_name = str(fasta_name)
+        self.window = int(window)
+        self.nbkmer = int(nbkmer)
+        self.kmer_size = int(kmer_size)
+        self.overlap = int(overlap)
+
+    def get_fasta_name(self):
+        return self.fasta_name
+
+    def get_window(self):
+        return self.window
+
+    def get_nbkmer(self):
+        return self.nbkmer
+
+    def get_kmer_size(self):
+        return self.kmer_size
+
+    def get_overlap(self):
+        return self.overlap
+
+    def get_stride(self):
+        """window - overlap: the distance between the starts of two consecutive slices (anchor.rs:318)"""
+        return self.window - self.overlap
+
+    def sketch_params(self, hasher=A.HASHER_INT64HASH, fhash=A.FHASH_VALUE_MASKED):
+        """the kmu_sketch_params of these anchors; the defaults are the reference's MinInvHashCountKmer: forward k-mers,
+        int64_hash(get_compressed_value()), u8 counts.  fhash=A.FHASH_CANON_VALUE gives strand-independent anchors."""
+        kmer_type, _ = parsefastq.kmer_type_for(self.kmer_size)
+        return A.SketchParams(A.ALGO_BOTTOMK, kmer_type, self.kmer_size, self.nbkmer, A.SIG_U64, hasher, fhash, 0,
+                              A.MODE_PER_SEQ, A.INPUT_ASCII, A.MEM_HOST, 0)
+
+    def __str__(self):
+        return "slice size : %d nb kmer : %d kmer size : %d overlap : %d" % (self.window, self.nbkmer, self.kmer_size, self.overlap)
+
+
+class SliceAnchor:
+    """SliceAnchor (anchor.rs:97-105): one window of a read.  readnum, slicepos (first base of the slice in its read) and
+    minhash: the (hash, count) pairs of the slice, ascending by hash; empty for a slice that holds no k-mer."""
+
+    def __init__(self, params, readnum, slicepos, hashes, counts, n):
+        self.params = params
+        self.readnum = int(readnum)
+        self.slicepos = int(slicepos)
+        self._hashes, self._counts, self._n = hashes, counts, int(n)
+
+    @property
+    def minhash(self):
+        c = self._counts
+        return [(int(self._hashes[t]), int(c[t]) if c is not None else None) for t in range(self._n)]
+
+    def get_minhash_key(self):
+        """the smallest hash of the slice: its key in the inverse index (get_minhash_key_for_redis, anchor.rs:149-158)"""
+        if self._n == 0:
+            raise IndexError("slice %d:%d holds no k-mer" % (self.readnum, self.slicepos))
+        return int(self._hashes[0])
+
+
+class ReadAnchors:
+    """ReadAnchors (anchor.rs:265-329): the slices of one read, a view over rows [row_begin, row_end) of the arrays"""
+
+    def __init__(self, params, readnum, hashes, counts, n, row_begin, row_end):
+        self.slice_params = params
+        self.readnum = int(readnum)
+        self._hashes, self._counts, self._n = hashes, counts, n
+        self._rows = (int(row_begin), int(row_end))
+
+    def get_nb_slice(self):
+        return self._rows[1] - self._rows[0]
+
+    @property
+    def anchors(self):
+        stride = self.slice_params.get_stride()
+        b, e = self._rows
+        return [SliceAnchor(self.slice_params, self.readnum, (r - b) * stride, self._hashes[r],
+                            self._counts[r] if self._counts is not None else None, self._n[r]) for r in range(b, e)]
+
+    def __len__(self):
+        return self.get_nb_slice()
+
+    def __getitem__(self, s):
+        return self.anchors[s]
+
+
+def _host(x):
+    """a numpy view of the bits of a result array (device tensors come back as int64 / int32)"""
+    if x is None:
+        return None
+    if type(x).__module__.startswith("torch"):
+        x = x.cpu().numpy()
+    x = np.ascontiguousarray(x)
+    return x.view({8: np.uint64, 4: np.uint32}[x.dtype.itemsize])
+
+
+def gen_read_anchors(ctx, bases, offsets, params, first_readnum=0, hasher=A.HASHER_INT64HASH, fhash=A.FHASH_VALUE_MASKED,
+                     want_counts=True):
+    """ReadAnchors::generate_anchors for every read of a batch, in one library call: a list of ReadAnchors, read i of the batch
+    numbered first_readnum + i.  `bases` / `offsets`: numpy arrays or torch cuda tensors (the rows come back to the host)."""
+    hashes, counts, n, rows = ctx.read_anchors(bases, offsets, params.sketch_params(hasher, fhash), params.get_window(),
+                                               params.get_overlap(), want_counts=want_counts)
+    hashes, counts, n = _host(hashes), _host(counts), _host(n)
+    return [ReadAnchors(params, first_readnum + i, hashes, counts, n, rows[i], rows[i + 1]) for i in range(len(rows) - 1)]
+
+
+def anchors_by_minhash(hashes, n, row_offsets, stride, first_readnum=0):
+    """The inverse index of `redis_dump` (MINHASH_1, anchor.rs:187-197): {smallest hash of a slice: [(readnum, slicepos), ...]}
+    in row order.  hashes [rows, nbkmer], n [rows], row_offsets [n_reads + 1] as kmu_read_anchors gives them; slices with n = 0
+    are skipped (their minhash[0] does not exist)."""
+    hashes, n = _host(hashes), _host(n)
+    row_offsets = np.asarray(row_offsets).astype(np.int64)
+    index = {}
+    for i in range(len(row_offsets) - 1):
+        for r in range(int(row_offsets[i]), int(row_offsets[i + 1])):
+            if n[r] == 0:
+                continue
+            index.setdefault(int(hashes[r, 0]), []).append((first_readnum + i, (r - int(row_offsets[i])) * int(stride)))
+    return index

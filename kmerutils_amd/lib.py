@@ -32,7 +32,7 @@ SYMBOLS = [
     "kmu_comm_allgather", "kmu_comm_get_stats", "kmu_count_finalize", "kmu_kmer_owner",
     "kmu_sketch_count", "kmu_host_alloc", "kmu_host_free", "kmu_count_nb_occurrences", "kmu_count_table_info",
     "kmu_count_nb_saturated", "kmu_kmer_owner_minimizer", "kmu_count_owner_kind", "kmu_count_extract_superkmers", "kmu_count_add_superkmers",
-    "kmu_count_histogram", "kmu_count_read_profile",
+    "kmu_count_histogram", "kmu_count_read_profile", "kmu_anchor_layout", "kmu_read_anchors",
 ]
 
 
@@ -94,6 +94,8 @@ def load():
     L.kmu_sketch.argtypes = [vp, C.POINTER(A.SketchParams), vp, vp, vp, C.c_uint32, vp, vp, vp]
     L.kmu_sketch_groups.argtypes = [vp, C.POINTER(A.SketchParams), vp, vp, vp, C.c_uint32, vp, C.c_uint32, vp]
     L.kmu_block_layout.argtypes = [vp, C.c_uint32, C.c_uint32, vp]
+    L.kmu_anchor_layout.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp]
+    L.kmu_read_anchors.argtypes = [vp, C.POINTER(A.SketchParams), vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp]
     L.kmu_sketch_hashed.argtypes = [vp, C.POINTER(A.SketchParams), vp, vp, C.c_uint32, vp, vp]
     L.kmu_count_create.argtypes = [vp, C.POINTER(A.CountParams), C.POINTER(vp)]
     L.kmu_count_destroy.argtypes = [vp]
@@ -158,7 +160,7 @@ class _StreamOrdered:
     Doing it here, at the one place every call passes through, covers the buffers of every present and future method."""
 
     _PLAIN = ("kmu_last_error", "kmu_destroy", "kmu_stream", "kmu_version", "kmu_device_count", "kmu_create",
-              "kmu_block_layout", "kmu_sketch_partial_words", "kmu_count_destroy", "kmu_comm_get_id", "kmu_comm_rank",
+              "kmu_block_layout", "kmu_anchor_layout", "kmu_sketch_partial_words", "kmu_count_destroy", "kmu_comm_get_id", "kmu_comm_rank",
               "kmu_comm_nranks", "kmu_comm_get_stats", "kmu_kmer_owner", "kmu_comm_destroy")
 
     def __init__(self, lib, ctx):
@@ -515,6 +517,38 @@ class Context:
         self._check(self.L.kmu_sketch_groups(self.h, C.byref(p), _ptr(bases)[0], _ptr(offsets)[0], _ptr(packed_offsets)[0],
                                              n, _ptr(group_offsets)[0], n_groups, _ptr(out)[0]))
         return out[:n_groups]
+
+    def anchor_layout(self, offsets_host, window, overlap):
+        """kmu_anchor_layout: first row of every read, ceil(L / (window - overlap)) rows per read (host arithmetic)"""
+        return anchor_layout(offsets_host, window, overlap)
+
+    def read_anchors(self, bases, offsets, params, window, overlap, want_counts=True):
+        """kmu_read_anchors: one bottom-k row per overlapping window of every read (ReadAnchors, anchor.rs:228-329).
+        Host (numpy) or device (torch cuda) buffers.  Returns (hashes [rows, nbkmer], counts [rows, nbkmer] or None,
+        n [rows], row_offsets [n_seq + 1]): numpy arrays for host input; for device input torch tensors holding the same bits
+        (int64 / int32), row_offsets as a numpy array (it is computed on the host from a host copy of `offsets`)."""
+        nseq = len(offsets) - 1
+        mem = self._mem(bases, offsets)
+        p = A.SketchParams.from_buffer_copy(params)
+        p.mem = mem
+        m = p.sketch_size
+        h_off = np.ascontiguousarray(offsets.cpu().numpy() if _is_torch(offsets) else offsets).astype(np.uint64)
+        row_offsets = anchor_layout(h_off, window, overlap)
+        rows = int(row_offsets[-1])
+        if mem == A.MEM_DEVICE:
+            import torch
+            d_rows = torch.from_numpy(row_offsets.astype(np.int64)).to(bases.device)
+            hashes = torch.zeros((max(rows, 1), m), dtype=torch.int64, device=bases.device)
+            counts = torch.zeros((max(rows, 1), m), dtype=torch.int32, device=bases.device) if want_counts else None
+            n = torch.zeros(max(rows, 1), dtype=torch.int32, device=bases.device)
+        else:
+            d_rows = row_offsets
+            hashes = np.zeros((max(rows, 1), m), np.uint64)
+            counts = np.zeros((max(rows, 1), m), np.uint32) if want_counts else None
+            n = np.zeros(max(rows, 1), np.uint32)
+        self._check(self.L.kmu_read_anchors(self.h, C.byref(p), _ptr(bases)[0], _ptr(offsets)[0], nseq, window, overlap,
+                                            _ptr(d_rows)[0], _ptr(hashes)[0], _ptr(counts)[0], _ptr(n)[0]))
+        return hashes[:rows], (counts[:rows] if want_counts else None), n[:rows], row_offsets
 
     def sketch_count(self, bases, offsets, params, counter=None, out=None):
         """kmu_sketch_count: the reads once, both results -- signature rows (returned) and, if `counter` is given, the
@@ -959,6 +993,17 @@ class Counter:
 
     def retain_part(self, part, n_parts):
         self.ctx._check(self.L.kmu_count_retain_part(self.h, part, n_parts))
+
+
+def anchor_layout(offsets_host, window, overlap):
+    """kmu_anchor_layout: row_offsets[n_seq + 1] of the anchors of reads given by host offsets (no device needed)"""
+    L = load()
+    off = np.ascontiguousarray(offsets_host, np.uint64)
+    out = np.zeros(off.size, np.uint64)
+    rc = L.kmu_anchor_layout(_ptr(off)[0], off.size - 1, window, overlap, _ptr(out)[0])
+    if rc:
+        raise KmuError(rc, "kmu_anchor_layout: window %d, overlap %d" % (window, overlap))
+    return out
 
 
 def kmer_owner(kmer_type, canon_kmers, n_parts):
