@@ -21,6 +21,7 @@
  *                                                            src/sketching/seqblocksketch.rs:38-227, 419-440
  *                 MinInvHashCountKmer, minhash_distance      src/sketching/minhash.rs:134-340
  *   anchors       AnchorsGeneratorParameters, SliceAnchor, ReadAnchors, gen_read_anchors   src/anchor.rs:29-329
+ *                 AnchorMatch, match_read_anchors (the join behind redis_dump's index)     src/anchor.rs:187-197
  *   counting      KmerCountT (trait), KmerCounter, KmerCounterPool, count_kmer_threaded_one_to_many
  *                                                            src/base/kmercount.rs:48-123, 424-565, 881-974
  *   io            FASTQ reader rule, signature / count dumps src/io.rs:12-72, src/bin/datasketcher.rs:358-388,
@@ -1447,6 +1448,50 @@ std::vector<ReadAnchors<Kmer>> gen_read_anchors(const AnchorsGeneratorParameters
                                                 const std::vector<const Sequence *> &seqs, FHash fhash = FHash::value_masked,
                                                 int hasher = KMU_HASHER_INT64HASH, Context &ctx = Context::global()) {
     return gen_read_anchors<Kmer>(params, numfirst, detail::gather(seqs), fhash, hasher, ctx);
+}
+
+/// one hit of match_read_anchors: slice a (readnum_a, slicepos_a) and slice b of another read share one of their smallest hashes;
+/// common / total are mininvhash_distance's counts for (a first, b second)
+struct AnchorMatch {
+    uint32_t readnum_a, slicepos_a, readnum_b, slicepos_b, common, total;
+    bool operator==(const AnchorMatch &o) const {
+        return readnum_a == o.readnum_a && slicepos_a == o.slicepos_a && readnum_b == o.readnum_b && slicepos_b == o.slicepos_b &&
+               common == o.common && total == o.total;
+    }
+};
+
+/// What looking every slice up in the inverse index of `redis_dump` (anchor.rs:187-197; n_keys = 1 is its MINHASH_1) finds among the
+/// slices of `reads` (the result of gen_read_anchors), with mininvhash_distance for each hit: kmu_anchor_match as a self-join with
+/// group = read.  Slices of one read are never paired; hits with common < min_common are dropped; (a, b) and (b, a) are both
+/// reported.  Order: slice a in the order of `reads`, then the shared hash, then slice b.
+template <class Kmer>
+std::vector<AnchorMatch> match_read_anchors(const std::vector<ReadAnchors<Kmer>> &reads, const AnchorsGeneratorParameters &params,
+                                            uint32_t n_keys = 1, uint32_t min_common = 1, Context &ctx = Context::global()) {
+    const size_t m = params.get_nbkmer();
+    std::vector<const SliceAnchor<Kmer> *> slices;
+    std::vector<uint32_t> group;
+    for (size_t i = 0; i < reads.size(); i++)
+        for (const SliceAnchor<Kmer> &s : reads[i].anchors) {
+            slices.push_back(&s);
+            group.push_back(uint32_t(i));
+        }
+    std::vector<uint64_t> h(std::max<size_t>(slices.size(), 1) * m, UINT64_MAX);
+    for (size_t r = 0; r < slices.size(); r++)
+        for (size_t t = 0; t < slices[r]->minhash.size() && t < m; t++) h[r * m + t] = slices[r]->minhash[t].hashed;
+    const uint32_t rows = uint32_t(slices.size());
+    uint64_t total = 0;
+    ctx.check(kmu_anchor_match(ctx.raw(), h.data(), rows, h.data(), rows, uint32_t(m), n_keys, min_common, group.data(), group.data(),
+                               KMU_MEM_HOST, nullptr, nullptr, 0, &total));
+    std::vector<uint32_t> pairs(size_t(total) * 2), dist(size_t(total) * 3);
+    if (total)
+        ctx.check(kmu_anchor_match(ctx.raw(), h.data(), rows, h.data(), rows, uint32_t(m), n_keys, min_common, group.data(),
+                                   group.data(), KMU_MEM_HOST, pairs.data(), dist.data(), total, &total));
+    std::vector<AnchorMatch> out(static_cast<size_t>(total));
+    for (size_t p = 0; p < out.size(); p++) {
+        const SliceAnchor<Kmer> &a = *slices[pairs[2 * p]], &b = *slices[pairs[2 * p + 1]];
+        out[p] = AnchorMatch{a.readnum, a.slicepos, b.readnum, b.slicepos, dist[3 * p], dist[3 * p + 1]};
+    }
+    return out;
 }
 
 // =====================================================================================================================

@@ -654,6 +654,35 @@ int kmu_sig_knn(kmu_ctx *ctx, const void *sig_q, uint32_t nq, const void *sig_db
 int kmu_minhash_distance_pairs(kmu_ctx *ctx, const uint64_t *hashes_a, uint32_t na, const uint64_t *hashes_b, uint32_t nb,
                                uint32_t m, const uint32_t *ia, const uint32_t *ib, uint64_t n_pairs, int mem,
                                uint32_t *out);
+/* Anchor matching: the pairs of bottom-k rows that share one of their smallest hashes, with the distance of every pair -- the
+ * join behind the reference's inverse index smallest hash -> (readnum, slicepos) (redis_dump, src/anchor.rs:187-197; MINHASH_1 is
+ * n_keys = 1) and mininvhash_distance on what it finds, without the rows leaving the device.
+ *   Rows (hashes_q: nq x m, hashes_db: ndb x m, possibly the same array) hold ascending distinct hashes padded with UINT64_MAX, as
+ *   kmu_read_anchors and kmu_sketch(KMU_ALGO_BOTTOMK) write them; they are trusted to have that shape, as
+ *   kmu_minhash_distance_pairs trusts them.  n(r) = the entries of row r in front of its padding.
+ *   keys(r) = the first min(n_keys, n(r)) hashes of row r.  The padding is never a key: an empty row matches nothing.
+ *   Candidates: (a in q, b in db) with keys(a) and keys(b) intersecting and, when groups are given, group_q[a] != group_db[b]
+ *   (DistBlockSketched's rule, as in kmu_sig_knn: slices of one read are never paired).  A self-join passes the same array twice
+ *   with group = read of the row and gets (a, b) and (b, a) both.
+ *   Distance of a candidate: the triple (common, total, i) of kmu_minhash_distance_pairs for (row a first, row b second), bit for
+ *   bit, early stop and top-up rules included -- common may be 0 (the walk stops after n(a) steps).
+ *   Reported: the candidates with common >= min_common (0: all of them), each ONCE, under h* = min(keys(a) & keys(b)) -- which is
+ *   also the smallest hash the two rows share at all.  Order: a ascending, then h*, then b.  A pure function of the inputs.
+ *   *n_out (host memory in both modes) is always the total number of pairs.  pairs_out == NULL: nothing else is written (the
+ *   count-only call).  Otherwise pairs_out[2p..] = (a, b) and, unless dist_out is NULL, dist_out[3p..] = common, total, i;
+ *   cap < total: KMU_E_BAD_ARG with *n_out set and the outputs unspecified (the rule of kmu_count_dump).
+ * KMU_MEM_DEVICE: every array except n_out is device memory; the call synchronises the stream once, to hand n_out over (also in
+ * async_device contexts), as kmu_read_anchors reads its row count.
+ * KMU_E_BAD_ARG: null ctx / hashes / n_out, m == 0, n_keys == 0 or > m, one group array without the other.
+ * KMU_E_UNSUPPORTED: m > KMU_ANCHOR_MAX_NBKMER, ndb * n_keys >= 2^32.  nq == 0 or ndb == 0: KMU_OK, *n_out = 0.
+ * How: the ndb * n_keys (key, row) entries are sorted by key on the device (a stable 8-bit LSD radix sort, one wave per tile of
+ * KMU_ANCHOR_SORT_TILE entries and pass); one wave per query row then looks its keys up and walks each bucket 64 candidates at a
+ * time, once to count and once to write.  One wave owns a whole bucket: a key shared by very many rows is slow and gives
+ * quadratic output (no repeat mask here). */
+#define KMU_ANCHOR_SORT_TILE 1024 /* entries one workgroup ranks per radix pass */
+int kmu_anchor_match(kmu_ctx *ctx, const uint64_t *hashes_q, uint32_t nq, const uint64_t *hashes_db, uint32_t ndb, uint32_t m,
+                     uint32_t n_keys, uint32_t min_common, const uint32_t *group_q, const uint32_t *group_db, int mem,
+                     uint32_t *pairs_out, uint32_t *dist_out, uint64_t cap, uint64_t *n_out);
 
 #ifdef __cplusplus
 }

@@ -25,6 +25,7 @@ KNN_MAX_K = 64          # kmu_sig_knn: the longest neighbour list
 KNN_NONE = 0xFFFFFFFF   # idx of a list entry that does not exist
 ANCHOR_MAX_NBKMER = 256  # kmu_read_anchors: the largest sketch_size (nbkmer)
 ANCHOR_TILE_KMERS = 768  # ... and the k-mers of a window it selects from at a time
+ANCHOR_SORT_TILE = 1024  # kmu_anchor_match: the index entries one workgroup ranks per radix pass
 
 
 def kmer_val_bytes(kmer_type):

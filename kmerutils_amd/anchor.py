@@ -2,7 +2,8 @@
 
 `gen_read_anchors` runs kmu_read_anchors over a batch of reads; `ReadAnchors` / `SliceAnchor` are views over the arrays it
 returns, named like the reference's structs; `anchors_by_minhash` is the inverse index min hash -> [(readnum, slicepos)] that
-the reference's `redis_dump` stores under MINHASH_1, as a plain dict on the host.
+the reference's `redis_dump` stores under MINHASH_1, as a plain dict on the host; `match_read_anchors` is the join that index
+exists for, on the device (kmu_anchor_match), and `rows_to_slices` names its rows.
 """
 import numpy as np
 
@@ -131,3 +132,34 @@ def anchors_by_minhash(hashes, n, row_offsets, stride, first_readnum=0):
                 continue
             index.setdefault(int(hashes[r, 0]), []).append((first_readnum + i, (r - int(row_offsets[i])) * int(stride)))
     return index
+
+
+def rows_to_slices(rows, row_offsets, stride, first_readnum=0):
+    """(readnum, slicepos) of anchor rows: row r of a batch laid out by kmu_anchor_layout belongs to the read i with
+    row_offsets[i] <= r < row_offsets[i + 1], numbered first_readnum + i, and starts at base (r - row_offsets[i]) * stride of it.
+    Pure numpy; `rows` of any shape, two int64 arrays of that shape back."""
+    rows = np.asarray(rows).astype(np.int64)
+    row_offsets = np.asarray(row_offsets).astype(np.int64)
+    read = np.searchsorted(row_offsets, rows, side="right") - 1
+    return read + int(first_readnum), (rows - row_offsets[read]) * int(stride)
+
+
+def match_read_anchors(ctx, hashes, row_offsets, params, n_keys=1, min_common=1, first_readnum=0):
+    """The slices of a batch that share one of their n_keys smallest hashes and belong to different reads: kmu_anchor_match as a
+    self-join of the rows `hashes` (ctx.read_anchors: numpy, or torch on the device -- the join then runs on the resident rows)
+    with group = read of the row.  What a lookup of every slice in the reference's inverse index (redis_dump, anchor.rs:187-197)
+    finds, with mininvhash_distance for each hit.  Returns an int64 array [n, 6] of records (readnum_a, slicepos_a, readnum_b,
+    slicepos_b, common, total), ordered by row a, shared hash, row b; (a, b) and (b, a) are both there."""
+    row_offsets = np.asarray(row_offsets).astype(np.int64)
+    nrows = int(hashes.shape[0])
+    group = np.ascontiguousarray(rows_to_slices(np.arange(nrows), row_offsets, 1)[0].astype(np.uint32))
+    if type(hashes).__module__.startswith("torch") and hashes.is_cuda:
+        import torch
+        group = torch.from_numpy(group.view(np.int32)).to(hashes.device)
+    pairs, dist = ctx.anchor_match(hashes, hashes, n_keys=n_keys, min_common=min_common, group_q=group, group_db=group)
+    pairs, dist = _host(pairs).astype(np.int64), _host(dist).astype(np.int64)
+    out = np.zeros((pairs.shape[0], 6), np.int64)
+    out[:, 0], out[:, 1] = rows_to_slices(pairs[:, 0], row_offsets, params.get_stride(), first_readnum)
+    out[:, 2], out[:, 3] = rows_to_slices(pairs[:, 1], row_offsets, params.get_stride(), first_readnum)
+    out[:, 4:6] = dist[:, 0:2]
+    return out

@@ -86,26 +86,7 @@ __global__ void __launch_bounds__(256) k_minhash_distance(const uint64_t *a, con
                                                           const uint32_t *ib, uint64_t n_pairs, uint32_t *out) {
     for (uint64_t p = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x; p < n_pairs; p += (uint64_t) gridDim.x * blockDim.x) {
         const uint64_t *r1 = a + (uint64_t) ia[p] * m, *r2 = b + (uint64_t) ib[p] * m;
-        uint32_t n1 = 0, n2 = 0;
-        while (n1 < m && r1[n1] != 0xFFFFFFFFFFFFFFFFull) n1++;
-        while (n2 < m && r2[n2] != 0xFFFFFFFFFFFFFFFFull) n2++;
-        uint32_t i = 0, j = 0, common = 0, total = 0;
-        while (i < n1 && j < n2) { // minhash.rs:150-164
-            const uint64_t x = r1[i], y = r2[j];
-            if (x < y) i++;
-            else if (y < x) j++;
-            else { i++; j++; common++; }
-            total++;
-            if (total >= n1) break;
-        }
-        if (total < n1) { // minhash.rs:168-180 -- both top-ups are measured against the FIRST sketch's length, as upstream
-            if (i < n1) total += n1 - i;
-            if (j < n1) total += n1 - j;
-            if (total > n1) total = n1;
-        }
-        out[3 * p] = common;
-        out[3 * p + 1] = total;
-        out[3 * p + 2] = i;
+        minhash_walk(r1, bottomk_row_len(r1, m), r2, bottomk_row_len(r2, m), out + 3 * p); // kmu_device.h
     }
 }
 

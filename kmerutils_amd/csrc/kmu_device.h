@@ -335,6 +335,38 @@ __device__ __forceinline__ double exp01_sample(const Exp01 &e, Xoshiro &rng) {
 }
 
 // ---------------------------------------------------------------------------------------------------
+// bottom-k rows: ascending distinct hashes padded with u64::MAX (kmu_sketch KMU_ALGO_BOTTOMK, kmu_read_anchors)
+// ---------------------------------------------------------------------------------------------------
+// number of entries of a row in front of its padding
+__device__ __forceinline__ uint32_t bottomk_row_len(const uint64_t *r, uint32_t m) {
+    uint32_t n = 0;
+    while (n < m && r[n] != 0xFFFFFFFFFFFFFFFFull) n++;
+    return n;
+}
+// minhash_distance / mininvhash_distance (minhash.rs:134-190, :295-340) of the first n1 entries of r1 against the first n2 of
+// r2, one thread: out[0..2] = common, total, i (the number of items of the first row walked).  k_minhash_distance and the
+// candidates of k_anchor_match share this walk.
+__device__ __forceinline__ void minhash_walk(const uint64_t *r1, uint32_t n1, const uint64_t *r2, uint32_t n2, uint32_t *out) {
+    uint32_t i = 0, j = 0, common = 0, total = 0;
+    while (i < n1 && j < n2) { // minhash.rs:150-164
+        const uint64_t x = r1[i], y = r2[j];
+        if (x < y) i++;
+        else if (y < x) j++;
+        else { i++; j++; common++; }
+        total++;
+        if (total >= n1) break;
+    }
+    if (total < n1) { // minhash.rs:168-180 -- both top-ups are measured against the FIRST sketch's length, as upstream
+        if (i < n1) total += n1 - i;
+        if (j < n1) total += n1 - j;
+        if (total > n1) total = n1;
+    }
+    out[0] = common;
+    out[1] = total;
+    out[2] = i;
+}
+
+// ---------------------------------------------------------------------------------------------------
 // wave helpers
 // ---------------------------------------------------------------------------------------------------
 __device__ __forceinline__ int lane_id() { return (int) (threadIdx.x & 63u); }

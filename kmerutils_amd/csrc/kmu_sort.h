@@ -1,0 +1,108 @@
+// kmu_sort.h -- device sort of (u64 key, u32 value) entries: a stable LSD radix sort, 8-bit digits, eight passes.
+//
+// Per pass and per tile of SORT_TILE consecutive entries (one wave, a 64-thread workgroup, per tile):
+//   k_sort_hist     the tile's count of every digit, hist[digit * n_tiles + tile]
+//   device_scan_u32 an exclusive scan over that digit-major array: where the tile's entries of a digit go
+//   k_sort_scatter  the tile again, 64 entries at a time in input order.  The lanes that hold the same digit find each other with
+//                   eight ballots (match-any, one per bit of the digit); an entry's rank among them is popc(peers & lanes below),
+//                   so equal digits keep their input order inside a chunk, chunks follow each other through the running offsets
+//                   in LDS, and tiles through the scan: every pass is stable by construction, and so is the sort.
+// It moves 12 bytes per entry and pass and is not tuned beyond that (no digit skipping, no fused histograms).
+// Entries: n < 2^32.  Workspace through dev_buf ("sort.hist", "sort.offs"); the caller brings the ping-pong pair.
+#pragma once
+
+#include <utility>
+
+#include "kmu_ctx.hpp"
+#include "kmu_device.h"
+
+namespace kmu {
+
+static constexpr uint32_t SORT_TILE = KMU_ANCHOR_SORT_TILE;
+static_assert(SORT_TILE % 64 == 0, "a tile is walked in chunks of one wave");
+
+// the lanes of `valid` whose 8-bit digit equals this lane's.  All 64 lanes must be active.
+__device__ __forceinline__ uint64_t wave_match_digit(uint32_t d, uint64_t valid) {
+    uint64_t peers = valid;
+#pragma unroll
+    for (int b = 0; b < 8; b++) {
+        const bool bit = (d >> b) & 1u;
+        const uint64_t v = __ballot(bit);
+        peers &= bit ? v : ~v;
+    }
+    return peers;
+}
+
+static __global__ void __launch_bounds__(64) k_sort_hist(const uint64_t *keys, uint64_t n, uint32_t shift, uint32_t n_tiles,
+                                                         uint32_t *hist) {
+    __shared__ uint32_t h[256];
+    const uint32_t lane = (uint32_t) lane_id(), tile = blockIdx.x;
+    for (uint32_t d = lane; d < 256; d += 64) h[d] = 0;
+    __syncthreads();
+    const uint64_t t0 = (uint64_t) tile * SORT_TILE;
+    for (uint32_t c = 0; c < SORT_TILE; c += 64) {
+        const uint64_t e = t0 + c + lane;
+        if (e < n) atomicAdd(&h[(uint32_t) (keys[e] >> shift) & 255u], 1u);
+    }
+    __syncthreads();
+    for (uint32_t d = lane; d < 256; d += 64) hist[(uint64_t) d * n_tiles + tile] = h[d];
+}
+
+static __global__ void __launch_bounds__(64) k_sort_scatter(const uint64_t *keys, const uint32_t *vals, uint64_t n, uint32_t shift,
+                                                            uint32_t n_tiles, const uint64_t *offs, uint64_t *keys_out,
+                                                            uint32_t *vals_out) {
+    __shared__ uint32_t base[256]; // where the tile's next entry of every digit goes
+    const uint32_t lane = (uint32_t) lane_id(), tile = blockIdx.x;
+    for (uint32_t d = lane; d < 256; d += 64) base[d] = (uint32_t) offs[(uint64_t) d * n_tiles + tile];
+    __syncthreads();
+    const uint64_t t0 = (uint64_t) tile * SORT_TILE;
+    for (uint32_t c = 0; c < SORT_TILE; c += 64) { // uniform trip count: the ballots see all lanes
+        const uint64_t e = t0 + c + lane;
+        const bool valid = e < n;
+        const uint64_t key = valid ? keys[e] : 0ull;
+        const uint32_t val = valid ? vals[e] : 0u;
+        const uint32_t d = (uint32_t) (key >> shift) & 255u;
+        const uint64_t peers = wave_match_digit(d, __ballot(valid));
+        const uint32_t rank = (uint32_t) __popcll(peers & ((1ull << lane) - 1ull));
+        const uint32_t dst = base[d] + rank;
+        __syncthreads(); // every lane has read its offset
+        if (valid && (peers >> lane) == 1ull) base[d] = dst + 1; // the last lane of a digit moves its offset on
+        __syncthreads();
+        if (valid && dst < n) {
+            keys_out[dst] = key;
+            vals_out[dst] = val;
+        }
+    }
+}
+
+// Sorts the n entries (k0[i], v0[i]) by key, ascending; entries of equal keys keep their order.  (k1, v1) is scratch of the same
+// size; eight passes, so the sorted entries are back in (k0, v0).  All pointers are device memory; nothing is synchronised.
+static inline int radix_sort_pairs(kmu_ctx *ctx, uint64_t *k0, uint32_t *v0, uint64_t *k1, uint32_t *v1, uint64_t n) {
+    if (n == 0) return KMU_OK;
+    if (n > 0xFFFFFFFFull) return fail(ctx, KMU_E_UNSUPPORTED, "radix_sort_pairs: %llu entries, more than 2^32 - 1", (unsigned long long) n);
+    const uint32_t n_tiles = (uint32_t) ((n + SORT_TILE - 1) / SORT_TILE);
+    void *hist, *offs;
+    KMU_TRY(dev_buf(ctx, "sort.hist", (size_t) n_tiles * 256 * 4, &hist));
+    KMU_TRY(dev_buf(ctx, "sort.offs", ((size_t) n_tiles * 256 + 1) * 8, &offs));
+    for (uint32_t pass = 0; pass < 8; pass++) {
+        const uint32_t shift = 8 * pass;
+        {
+            KernelTimer t(ctx, "k_sort_hist");
+            hipLaunchKernelGGL(k_sort_hist, dim3(n_tiles), dim3(64), 0, ctx->stream, (const uint64_t *) k0, n, shift, n_tiles,
+                               (uint32_t *) hist);
+        }
+        KMU_HIP(ctx, hipGetLastError());
+        KMU_TRY(device_scan_u32(ctx, (const uint32_t *) hist, (uint64_t) n_tiles * 256, (uint64_t *) offs));
+        {
+            KernelTimer t(ctx, "k_sort_scatter");
+            hipLaunchKernelGGL(k_sort_scatter, dim3(n_tiles), dim3(64), 0, ctx->stream, (const uint64_t *) k0, (const uint32_t *) v0, n,
+                               shift, n_tiles, (const uint64_t *) offs, k1, v1);
+        }
+        KMU_HIP(ctx, hipGetLastError());
+        std::swap(k0, k1);
+        std::swap(v0, v1);
+    }
+    return KMU_OK;
+}
+
+} // namespace kmu

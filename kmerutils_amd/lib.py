@@ -32,7 +32,7 @@ SYMBOLS = [
     "kmu_comm_allgather", "kmu_comm_get_stats", "kmu_count_finalize", "kmu_kmer_owner",
     "kmu_sketch_count", "kmu_host_alloc", "kmu_host_free", "kmu_count_nb_occurrences", "kmu_count_table_info",
     "kmu_count_nb_saturated", "kmu_kmer_owner_minimizer", "kmu_count_owner_kind", "kmu_count_extract_superkmers", "kmu_count_add_superkmers",
-    "kmu_count_histogram", "kmu_count_read_profile", "kmu_anchor_layout", "kmu_read_anchors",
+    "kmu_count_histogram", "kmu_count_read_profile", "kmu_anchor_layout", "kmu_read_anchors", "kmu_anchor_match",
 ]
 
 
@@ -115,6 +115,8 @@ def load():
     L.kmu_sig_equal_matrix.argtypes = [vp, vp, C.c_uint32, vp, C.c_uint32, C.c_uint32, C.c_int, C.c_int, vp]
     L.kmu_sig_knn.argtypes = [vp, vp, C.c_uint32, vp, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, vp, vp, C.c_int, vp, vp]
     L.kmu_minhash_distance_pairs.argtypes = [vp, vp, C.c_uint32, vp, C.c_uint32, C.c_uint32, vp, vp, C.c_uint64, C.c_int, vp]
+    L.kmu_anchor_match.argtypes = [vp, vp, C.c_uint32, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, C.c_int, vp, vp,
+                                   C.c_uint64, u64p]
     L.kmu_set_hll_params.argtypes = [vp, C.POINTER(A.HllParams)]
     L.kmu_kmer_hashes_compact.argtypes = [vp, C.POINTER(A.HashParams), vp, vp, vp, C.c_uint32, vp, C.c_uint64, u64p]
     L.kmu_sketch_partial_words.argtypes = [C.POINTER(A.SketchParams)]
@@ -742,6 +744,30 @@ class Context:
                                                       hashes_b.shape[0], hashes_a.shape[1], _ptr(ia)[0], _ptr(ib)[0], n,
                                                       mem, _ptr(out)[0]))
         return out[:n]
+
+    def anchor_match(self, hashes_q, hashes_db, n_keys=1, min_common=1, group_q=None, group_db=None):
+        """kmu_anchor_match: the pairs (row of hashes_q, row of hashes_db) of bottom-k rows that share one of their n_keys
+        smallest hashes (rows of one group left out), with (common, total, i) of kmu_minhash_distance_pairs for each, kept when
+        common >= min_common; ordered by query row, shared hash, database row.  Returns (pairs uint32 [n, 2], dist uint32
+        [n, 3]); device tensors in give device tensors out (int32 holding the same bits).  Two library calls: one that counts,
+        one with exactly that capacity."""
+        mem = self._mem(hashes_q, hashes_db, group_q, group_db)
+        nq, ndb = int(hashes_q.shape[0]), int(hashes_db.shape[0])
+        if hashes_q.shape[1] != hashes_db.shape[1]:
+            raise ValueError("query and database rows differ in length")
+        m = int(hashes_q.shape[1])
+        none = self._new_like(hashes_q, 2, np.uint64, "int64")  # an empty array has no address worth passing
+        pq = _ptr(hashes_q)[0] if nq else _ptr(none)[0]
+        pdb = _ptr(hashes_db)[0] if ndb else _ptr(none)[0]
+        total = C.c_uint64(0)
+        args = (self.h, pq, nq, pdb, ndb, m, int(n_keys), int(min_common), _ptr(group_q)[0], _ptr(group_db)[0], mem)
+        self._check(self.L.kmu_anchor_match(*args, None, None, 0, C.byref(total)))
+        n = int(total.value)
+        pairs = self._new_like(hashes_q, (max(n, 1), 2), np.uint32, "int32")
+        dist = self._new_like(hashes_q, (max(n, 1), 3), np.uint32, "int32")
+        if n:
+            self._check(self.L.kmu_anchor_match(*args, _ptr(pairs)[0], _ptr(dist)[0], n, C.byref(total)))
+        return pairs[:n], dist[:n]
 
     def counter(self, kmer_type, k, counter_bits=8, capacity_hint=1 << 20, distributed=False, owner_hash=False, hint_occurrences=False):
         return Counter(self, kmer_type, k, counter_bits, capacity_hint, distributed, owner_hash, hint_occurrences)
