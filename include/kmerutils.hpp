@@ -22,6 +22,7 @@
  *                 MinInvHashCountKmer, minhash_distance      src/sketching/minhash.rs:134-340
  *   anchors       AnchorsGeneratorParameters, SliceAnchor, ReadAnchors, gen_read_anchors   src/anchor.rs:29-329
  *                 AnchorMatch, match_read_anchors (the join behind redis_dump's index)     src/anchor.rs:187-197
+ *                 Overlap, anchor_overlaps, read_overlaps (read pairs from matched slices)  (beyond the reference)
  *   counting      KmerCountT (trait), KmerCounter, KmerCounterPool, count_kmer_threaded_one_to_many
  *                                                            src/base/kmercount.rs:48-123, 424-565, 881-974
  *   io            FASTQ reader rule, signature / count dumps src/io.rs:12-72, src/bin/datasketcher.rs:358-388,
@@ -1491,6 +1492,79 @@ std::vector<AnchorMatch> match_read_anchors(const std::vector<ReadAnchors<Kmer>>
         const SliceAnchor<Kmer> &a = *slices[pairs[2 * p]], &b = *slices[pairs[2 * p + 1]];
         out[p] = AnchorMatch{a.readnum, a.slicepos, b.readnum, b.slicepos, dist[3 * p], dist[3 * p + 1]};
     }
+    return out;
+}
+
+/// kmu_anchor_overlaps on host arrays: the read pairs behind the window pairs `pairs` (2 per pair, rows of the two sides) of
+/// kmu_anchor_match, one kmu_overlap each (include/kmu.h has the rules).  `dist` (3 per pair) weighs a pair by its common; empty:
+/// every pair weighs 1.  row_offsets_*: the arrays of kmu_anchor_layout of the two sides.  upper: only read_a < read_b.
+inline std::vector<kmu_overlap> anchor_overlaps(const std::vector<uint32_t> &pairs, const std::vector<uint32_t> &dist,
+                                                const std::vector<uint64_t> &row_offsets_q, const std::vector<uint64_t> &row_offsets_db,
+                                                uint32_t strands = 2, uint32_t band = 1, uint32_t min_score = 1, bool upper = false,
+                                                Context &ctx = Context::global()) {
+    if (row_offsets_q.empty() || row_offsets_db.empty()) throw std::invalid_argument("anchor_overlaps: row offsets hold n_reads + 1 entries");
+    if (!dist.empty() && dist.size() / 3 != pairs.size() / 2) throw std::invalid_argument("anchor_overlaps: dist holds 3 values per pair");
+    const uint64_t n_pairs = pairs.size() / 2;
+    const uint32_t flags = upper ? KMU_OVL_UPPER : 0u, nq = uint32_t(row_offsets_q.size() - 1), ndb = uint32_t(row_offsets_db.size() - 1);
+    const uint32_t none[2] = {0, 0}; // an empty vector has no address worth passing
+    const uint32_t *pp = n_pairs ? pairs.data() : none, *pd = dist.empty() ? nullptr : dist.data();
+    uint64_t total = 0;
+    ctx.check(kmu_anchor_overlaps(ctx.raw(), pp, pd, n_pairs, row_offsets_q.data(), nq, row_offsets_db.data(), ndb, strands, band,
+                                  min_score, flags, KMU_MEM_HOST, nullptr, 0, &total));
+    std::vector<kmu_overlap> out(static_cast<size_t>(total));
+    if (total)
+        ctx.check(kmu_anchor_overlaps(ctx.raw(), pp, pd, n_pairs, row_offsets_q.data(), nq, row_offsets_db.data(), ndb, strands, band,
+                                      min_score, flags, KMU_MEM_HOST, out.data(), total, &total));
+    return out;
+}
+
+/// one read pair of read_overlaps: read b lies on `strand` of read a (0: the same, 1: the opposite) at `offset` bases -- the first
+/// diagonal of the winning band times the stride; the difference of the slice positions on strand 0, their sum on strand 1 -- with
+/// the band's weight, its number of matched slices, and the first and last slicepos of read a among them
+struct Overlap {
+    uint32_t readnum_a, readnum_b, strand;
+    int64_t offset;
+    uint32_t score, votes, slicepos_a_first, slicepos_a_last;
+    bool operator==(const Overlap &o) const {
+        return readnum_a == o.readnum_a && readnum_b == o.readnum_b && strand == o.strand && offset == o.offset && score == o.score &&
+               votes == o.votes && slicepos_a_first == o.slicepos_a_first && slicepos_a_last == o.slicepos_a_last;
+    }
+};
+
+/// Which of `reads` (the result of gen_read_anchors) overlap: the self-join of match_read_anchors, then kmu_anchor_overlaps with
+/// the common of every matched pair of slices as its weight, each read pair once (a in front of b in `reads`).  strands = 2 is for
+/// anchors made with FHash::canon_value.  Order: read a, then read b, in the order of `reads`.
+template <class Kmer>
+std::vector<Overlap> read_overlaps(const std::vector<ReadAnchors<Kmer>> &reads, const AnchorsGeneratorParameters &params,
+                                   uint32_t n_keys = 1, uint32_t min_common = 1, uint32_t strands = 2, uint32_t band = 1,
+                                   uint32_t min_score = 2, Context &ctx = Context::global()) {
+    const size_t m = params.get_nbkmer();
+    std::vector<uint64_t> row_offsets(reads.size() + 1, 0);
+    std::vector<uint32_t> group;
+    for (size_t i = 0; i < reads.size(); i++) {
+        row_offsets[i + 1] = row_offsets[i] + reads[i].anchors.size();
+        group.insert(group.end(), reads[i].anchors.size(), uint32_t(i));
+    }
+    const uint32_t rows = uint32_t(group.size());
+    std::vector<uint64_t> h(std::max<size_t>(rows, 1) * m, UINT64_MAX);
+    size_t r = 0;
+    for (const ReadAnchors<Kmer> &ra : reads)
+        for (const SliceAnchor<Kmer> &s : ra.anchors) {
+            for (size_t t = 0; t < s.minhash.size() && t < m; t++) h[r * m + t] = s.minhash[t].hashed;
+            r++;
+        }
+    uint64_t total = 0;
+    ctx.check(kmu_anchor_match(ctx.raw(), h.data(), rows, h.data(), rows, uint32_t(m), n_keys, min_common, group.data(), group.data(),
+                               KMU_MEM_HOST, nullptr, nullptr, 0, &total));
+    std::vector<uint32_t> pairs(size_t(total) * 2), dist(size_t(total) * 3);
+    if (total)
+        ctx.check(kmu_anchor_match(ctx.raw(), h.data(), rows, h.data(), rows, uint32_t(m), n_keys, min_common, group.data(),
+                                   group.data(), KMU_MEM_HOST, pairs.data(), dist.data(), total, &total));
+    const int64_t stride = int64_t(params.get_window()) - int64_t(params.get_overlap());
+    std::vector<Overlap> out;
+    for (const kmu_overlap &o : anchor_overlaps(pairs, dist, row_offsets, row_offsets, strands, band, min_score, true, ctx))
+        out.push_back(Overlap{reads[o.read_a].readnum, reads[o.read_b].readnum, o.strand, int64_t(o.diag) * stride, o.score, o.votes,
+                              uint32_t(o.slice_a_min * stride), uint32_t(o.slice_a_max * stride)});
     return out;
 }
 

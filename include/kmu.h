@@ -683,6 +683,53 @@ int kmu_minhash_distance_pairs(kmu_ctx *ctx, const uint64_t *hashes_a, uint32_t 
 int kmu_anchor_match(kmu_ctx *ctx, const uint64_t *hashes_q, uint32_t nq, const uint64_t *hashes_db, uint32_t ndb, uint32_t m,
                      uint32_t n_keys, uint32_t min_common, const uint32_t *group_q, const uint32_t *group_db, int mem,
                      uint32_t *pairs_out, uint32_t *dist_out, uint64_t cap, uint64_t *n_out);
+/* Read overlaps: from the window pairs of kmu_anchor_match to read pairs -- which reads overlap, on which strand, at which
+ * relative offset, with how much support -- by a vote over diagonals, without the pairs leaving the device.
+ *   pairs[2p..] = (a, b) and dist[3p..] = (common, total, i) exactly as kmu_anchor_match writes them, in any order: the result
+ *   does not depend on the order of the input.  dist == NULL: every pair weighs 1; otherwise the weight of pair p is dist[3p]
+ *   (common).  row_offsets_q / row_offsets_db (n_reads + 1 entries each) are the arrays of kmu_anchor_layout, possibly the same
+ *   array (a self-join).  Row a belongs to the read i with row_offsets_q[i] <= a < row_offsets_q[i + 1] and
+ *   slice_a = a - row_offsets_q[i]; the same for b on the db side.  The offsets are trusted to be ascending; a row at or beyond the
+ *   last offset is undefined input, as bad rows are in kmu_minhash_distance_pairs.
+ *   Integer arithmetic only, a pure function of the inputs:
+ *   For a read pair (A, B) and a strand s in {0 .. strands - 1}, every window pair of (A, B) has a diagonal:
+ *   d = slice_a - slice_b for s = 0, d = slice_a + slice_b for s = 1.
+ *   W_s(d) is the sum of the weights on diagonal d, V_s(d) the number of window pairs on it.
+ *   For every occupied diagonal (V > 0) the band score is S_s(d) = sum of W_s(e) over e = d .. d + band.
+ *   The winner of (A, B) is the (s, d) with the largest S; ties go to s = 0 before s = 1, then to the smallest d.
+ *   The winner's record: diag = d, score = min(S, 2^32 - 1), votes = sum of V over the band, slice_a_min / slice_a_max over the
+ *   window pairs in the band.
+ *   Reported: one record per read pair that has at least one window pair, whose score is >= min_score and, under KMU_OVL_UPPER,
+ *   whose read_a < read_b (a self-join: each pair once).  Order: read_a ascending, then read_b.
+ *   band is there because two reads cut their windows at unrelated phases, so one true overlap lands on two neighbouring
+ *   diagonals; band = 0 is the plain vote per diagonal.  strands = 2 is for strand-independent anchors (KMU_FHASH_CANON_VALUE),
+ *   strands = 1 for the reference's forward anchors.
+ *   *n_out (host memory in both modes) is always the total number of records.  out == NULL: nothing else is written (the
+ *   count-only call).  cap < total: KMU_E_BAD_ARG with *n_out set and out unspecified.
+ * KMU_MEM_DEVICE: every array except n_out is device memory; the call synchronises the stream once, to hand n_out over (also in
+ * async_device contexts).  The row offsets are then read on the device and a refusal because of them comes at that point.
+ * KMU_E_BAD_ARG: null ctx / pairs / offsets / n_out, strands not 1 or 2, unknown flag bits, pairs but n_reads_q or n_reads_db == 0.
+ * KMU_E_UNSUPPORTED: band > KMU_OVL_MAX_BAND, n_pairs * strands >= 2^32, a last row offset >= 2^31 or, with strands = 2, the two
+ * last offsets above 2^31 together (both kinds of diagonal must fit the biased 32-bit field and the int32 of the record).
+ * n_pairs == 0: KMU_OK, *n_out = 0, nothing else is written.
+ * How: one entry per window pair and strand, sorted by (read_a, read_b, strand, diagonal) with two stable radix sorts (the
+ * diagonal key first, then the read pair; the passes of bytes that are the same in every key are skipped); equal keys are a run,
+ * reduced by one wave; one wave per read pair then takes the band sums of its runs and the first largest, once to count and once
+ * to write. */
+#define KMU_OVL_MAX_BAND 8
+#define KMU_OVL_UPPER 1u          /* flags: keep only read pairs with read_a < read_b (self-join: each pair once) */
+typedef struct {                  /* 32 bytes */
+    uint32_t read_a, read_b;      /* index into row_offsets_q / row_offsets_db */
+    uint32_t strand;              /* 0: same strand (diag = slice_a - slice_b); 1: opposite (diag = slice_a + slice_b) */
+    int32_t  diag;                /* first diagonal of the winning band, in slices */
+    uint32_t score;               /* sum of weights in the band, clamped to UINT32_MAX */
+    uint32_t votes;               /* number of matched window pairs in the band */
+    uint32_t slice_a_min, slice_a_max; /* over the window pairs in the band */
+} kmu_overlap;
+int kmu_anchor_overlaps(kmu_ctx *ctx, const uint32_t *pairs, const uint32_t *dist, uint64_t n_pairs,
+                        const uint64_t *row_offsets_q, uint32_t n_reads_q, const uint64_t *row_offsets_db, uint32_t n_reads_db,
+                        uint32_t strands, uint32_t band, uint32_t min_score, uint32_t flags, int mem,
+                        kmu_overlap *out, uint64_t cap, uint64_t *n_out);
 
 #ifdef __cplusplus
 }

@@ -26,6 +26,8 @@ KNN_NONE = 0xFFFFFFFF   # idx of a list entry that does not exist
 ANCHOR_MAX_NBKMER = 256  # kmu_read_anchors: the largest sketch_size (nbkmer)
 ANCHOR_TILE_KMERS = 768  # ... and the k-mers of a window it selects from at a time
 ANCHOR_SORT_TILE = 1024  # kmu_anchor_match: the index entries one workgroup ranks per radix pass
+OVL_MAX_BAND = 8         # kmu_anchor_overlaps: the widest band
+OVL_UPPER = 1            # ... and its flag: only read pairs with read_a < read_b
 
 
 def kmer_val_bytes(kmer_type):
@@ -101,6 +103,17 @@ class ReadAbundance(C.Structure):
 # the same record as a numpy dtype (np.dtype(READ_ABUNDANCE_DTYPE): 32 bytes, the field offsets of the structure)
 READ_ABUNDANCE_DTYPE = [("n_kmers", "<u4"), ("n_absent", "<u4"), ("n_once", "<u4"), ("n_solid", "<u4"), ("min", "<u2"),
                         ("median", "<u2"), ("max", "<u2"), ("reserved", "<u2"), ("sum", "<u8")]
+
+
+class Overlap(C.Structure):
+    """kmu_overlap: one read pair of kmu_anchor_overlaps"""
+    _fields_ = [("read_a", C.c_uint32), ("read_b", C.c_uint32), ("strand", C.c_uint32), ("diag", C.c_int32),
+                ("score", C.c_uint32), ("votes", C.c_uint32), ("slice_a_min", C.c_uint32), ("slice_a_max", C.c_uint32)]
+
+
+# the same record as a numpy dtype (32 bytes)
+OVERLAP_DTYPE = [("read_a", "<u4"), ("read_b", "<u4"), ("strand", "<u4"), ("diag", "<i4"), ("score", "<u4"), ("votes", "<u4"),
+                 ("slice_a_min", "<u4"), ("slice_a_max", "<u4")]
 
 
 ALLTOALLV_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_void_p,

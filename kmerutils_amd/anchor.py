@@ -3,7 +3,8 @@
 `gen_read_anchors` runs kmu_read_anchors over a batch of reads; `ReadAnchors` / `SliceAnchor` are views over the arrays it
 returns, named like the reference's structs; `anchors_by_minhash` is the inverse index min hash -> [(readnum, slicepos)] that
 the reference's `redis_dump` stores under MINHASH_1, as a plain dict on the host; `match_read_anchors` is the join that index
-exists for, on the device (kmu_anchor_match), and `rows_to_slices` names its rows.
+exists for, on the device (kmu_anchor_match), and `rows_to_slices` names its rows; `read_overlaps` goes on from the matched
+slices to read pairs (kmu_anchor_overlaps).
 """
 import numpy as np
 
@@ -162,4 +163,40 @@ def match_read_anchors(ctx, hashes, row_offsets, params, n_keys=1, min_common=1,
     out[:, 0], out[:, 1] = rows_to_slices(pairs[:, 0], row_offsets, params.get_stride(), first_readnum)
     out[:, 2], out[:, 3] = rows_to_slices(pairs[:, 1], row_offsets, params.get_stride(), first_readnum)
     out[:, 4:6] = dist[:, 0:2]
+    return out
+
+
+def _read_groups(hashes, row_offsets):
+    """the read of every row, as the group array of a self-join (on the device when the rows are)"""
+    group = np.ascontiguousarray(rows_to_slices(np.arange(int(hashes.shape[0])), row_offsets, 1)[0].astype(np.uint32))
+    if type(hashes).__module__.startswith("torch") and hashes.is_cuda:
+        import torch
+        group = torch.from_numpy(group.view(np.int32)).to(hashes.device)
+    return group
+
+
+def read_overlaps(ctx, hashes, row_offsets, params, n_keys=1, min_common=1, strands=2, band=1, min_score=2, first_readnum=0):
+    """Which reads of a batch overlap: the self-join of match_read_anchors followed by kmu_anchor_overlaps, each read pair once
+    (read a in front of read b in the batch).  With `hashes` on the device the matched slices never leave it.  The weight of a
+    matched pair of slices is its `common`; `band` + 1 neighbouring diagonals vote together; strands=2 also looks for read b on
+    the opposite strand (rows made with fhash=A.FHASH_CANON_VALUE), where the diagonal is the SUM of the two slice numbers.
+    Returns an int64 array [n, 8] of records (readnum_a, readnum_b, strand, offset in bases = diag * stride, score, votes, first
+    and last slicepos_a of the band), ordered by readnum_a, readnum_b."""
+    row_offsets = np.asarray(row_offsets).astype(np.int64)
+    group = _read_groups(hashes, row_offsets)
+    pairs, dist = ctx.anchor_match(hashes, hashes, n_keys=n_keys, min_common=min_common, group_q=group, group_db=group)
+    rec = ctx.anchor_overlaps(pairs, dist, row_offsets.astype(np.uint64), strands=strands, band=band, min_score=min_score, upper=True)
+    if type(rec).__module__.startswith("torch"):
+        rec = rec.cpu().numpy()
+    rec = np.ascontiguousarray(rec).view(np.dtype(A.OVERLAP_DTYPE)).reshape(-1)
+    stride = params.get_stride()
+    out = np.zeros((rec.shape[0], 8), np.int64)
+    out[:, 0] = rec["read_a"].astype(np.int64) + int(first_readnum)
+    out[:, 1] = rec["read_b"].astype(np.int64) + int(first_readnum)
+    out[:, 2] = rec["strand"]
+    out[:, 3] = rec["diag"].astype(np.int64) * stride
+    out[:, 4] = rec["score"]
+    out[:, 5] = rec["votes"]
+    out[:, 6] = rec["slice_a_min"].astype(np.int64) * stride
+    out[:, 7] = rec["slice_a_max"].astype(np.int64) * stride
     return out

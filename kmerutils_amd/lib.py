@@ -33,6 +33,7 @@ SYMBOLS = [
     "kmu_sketch_count", "kmu_host_alloc", "kmu_host_free", "kmu_count_nb_occurrences", "kmu_count_table_info",
     "kmu_count_nb_saturated", "kmu_kmer_owner_minimizer", "kmu_count_owner_kind", "kmu_count_extract_superkmers", "kmu_count_add_superkmers",
     "kmu_count_histogram", "kmu_count_read_profile", "kmu_anchor_layout", "kmu_read_anchors", "kmu_anchor_match",
+    "kmu_anchor_overlaps",
 ]
 
 
@@ -117,6 +118,8 @@ def load():
     L.kmu_minhash_distance_pairs.argtypes = [vp, vp, C.c_uint32, vp, C.c_uint32, C.c_uint32, vp, vp, C.c_uint64, C.c_int, vp]
     L.kmu_anchor_match.argtypes = [vp, vp, C.c_uint32, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, C.c_int, vp, vp,
                                    C.c_uint64, u64p]
+    L.kmu_anchor_overlaps.argtypes = [vp, vp, vp, C.c_uint64, vp, C.c_uint32, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                      C.c_uint32, C.c_int, vp, C.c_uint64, u64p]
     L.kmu_set_hll_params.argtypes = [vp, C.POINTER(A.HllParams)]
     L.kmu_kmer_hashes_compact.argtypes = [vp, C.POINTER(A.HashParams), vp, vp, vp, C.c_uint32, vp, C.c_uint64, u64p]
     L.kmu_sketch_partial_words.argtypes = [C.POINTER(A.SketchParams)]
@@ -768,6 +771,42 @@ class Context:
         if n:
             self._check(self.L.kmu_anchor_match(*args, _ptr(pairs)[0], _ptr(dist)[0], n, C.byref(total)))
         return pairs[:n], dist[:n]
+
+    def anchor_overlaps(self, pairs, dist, row_offsets_q, row_offsets_db=None, strands=2, band=1, min_score=1, upper=False):
+        """kmu_anchor_overlaps: the read pairs behind the window pairs of anchor_match (pairs [n, 2], dist [n, 3] or None: every
+        pair weighs 1), one record each -- the strand and first diagonal of the band of `band` + 1 diagonals with the largest
+        weight, its score, votes and extent in slices of read a (include/kmu.h has the rules).  row_offsets_*: the layout arrays
+        of the two sides (db defaults to q: a self-join); upper: only read_a < read_b.  numpy arrays give a structured array
+        (A.OVERLAP_DTYPE); torch cuda tensors stay on the device and give an int32 tensor [n, 8] holding the same bits (offsets
+        that are numpy arrays are copied up).  Two library calls: one that counts, one with exactly that capacity."""
+        mem = self._mem(pairs, dist)
+        n_pairs = int(pairs.shape[0])
+
+        def offsets(x):
+            if _is_torch(x):
+                if x.is_cuda == (mem == A.MEM_DEVICE):
+                    return x
+                x = x.cpu().numpy()
+            x = np.ascontiguousarray(np.asarray(x).astype(np.uint64))
+            if mem == A.MEM_DEVICE:
+                import torch
+                return torch.from_numpy(x.view(np.int64)).to(pairs.device)
+            return x
+        off_q = offsets(row_offsets_q)
+        off_db = off_q if row_offsets_db is None or row_offsets_db is row_offsets_q else offsets(row_offsets_db)
+        none = self._new_like(pairs, 2, np.uint32, "int32")  # an empty array has no address worth passing
+        total = C.c_uint64(0)
+        args = (self.h, _ptr(pairs)[0] if n_pairs else _ptr(none)[0], _ptr(dist)[0], n_pairs, _ptr(off_q)[0], int(off_q.shape[0]) - 1,
+                _ptr(off_db)[0], int(off_db.shape[0]) - 1, int(strands), int(band), int(min_score), A.OVL_UPPER if upper else 0, mem)
+        self._check(self.L.kmu_anchor_overlaps(*args, None, 0, C.byref(total)))
+        n = int(total.value)
+        if mem == A.MEM_DEVICE:
+            out = self._new_like(pairs, (max(n, 1), 8), np.int32, "int32")
+        else:
+            out = np.zeros(max(n, 1), np.dtype(A.OVERLAP_DTYPE))
+        if n:
+            self._check(self.L.kmu_anchor_overlaps(*args, _ptr(out)[0], n, C.byref(total)))
+        return out[:n]
 
     def counter(self, kmer_type, k, counter_bits=8, capacity_hint=1 << 20, distributed=False, owner_hash=False, hint_occurrences=False):
         return Counter(self, kmer_type, k, counter_bits, capacity_hint, distributed, owner_hash, hint_occurrences)
