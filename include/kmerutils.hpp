@@ -22,6 +22,7 @@
  *                 MinInvHashCountKmer, minhash_distance      src/sketching/minhash.rs:134-340
  *   anchors       AnchorsGeneratorParameters, SliceAnchor, ReadAnchors, gen_read_anchors   src/anchor.rs:29-329
  *                 AnchorMatch, match_read_anchors (the join behind redis_dump's index)     src/anchor.rs:187-197
+ *                 AnchorIndex (that index as a resident object, with a repeat mask)        src/anchor.rs:187-197
  *                 Overlap, anchor_overlaps, read_overlaps (read pairs from matched slices)  (beyond the reference)
  *   counting      KmerCountT (trait), KmerCounter, KmerCounterPool, count_kmer_threaded_one_to_many
  *                                                            src/base/kmercount.rs:48-123, 424-565, 881-974
@@ -1461,13 +1462,94 @@ struct AnchorMatch {
     }
 };
 
+/// kmu_anchor_index: bottom-k rows (ndb x m, ascending, UINT64_MAX padding), their n_keys smallest hashes sorted into buckets and
+/// optionally the group of every row, kept on the device -- the inverse index of `redis_dump` (anchor.rs:187-197) as an object that
+/// is built once and matched against by any number of query batches.  It copies what it is given and must not outlive its context.
+class AnchorIndex {
+  public:
+    /// `group_db` empty: no groups (then match takes none either)
+    AnchorIndex(const std::vector<uint64_t> &hashes_db, uint32_t ndb, uint32_t m, uint32_t n_keys = 1,
+                const std::vector<uint32_t> &group_db = {}, Context &ctx = Context::global())
+        : ctx_(&ctx), m_(m) {
+        if (hashes_db.size() < size_t(ndb) * m || (!group_db.empty() && group_db.size() < ndb))
+            throw std::invalid_argument("AnchorIndex: hashes_db holds ndb x m hashes, group_db ndb groups");
+        const uint64_t none[2] = {UINT64_MAX, UINT64_MAX}; // an empty vector has no address worth passing
+        ctx.check(kmu_anchor_index_create(ctx.raw(), ndb ? hashes_db.data() : none, ndb, m, n_keys,
+                                          group_db.empty() ? nullptr : group_db.data(), KMU_MEM_HOST, &ix_));
+    }
+    ~AnchorIndex() { kmu_anchor_index_destroy(ix_); }
+    AnchorIndex(AnchorIndex &&o) noexcept : ctx_(o.ctx_), ix_(o.ix_), m_(o.m_) { o.ix_ = nullptr; }
+    AnchorIndex(const AnchorIndex &) = delete;
+    AnchorIndex &operator=(const AnchorIndex &) = delete;
+
+    kmu_anchor_index *raw() const { return ix_; }
+    kmu_anchor_index_info_t info() const {
+        kmu_anchor_index_info_t t{};
+        ctx_->check(kmu_anchor_index_info(ix_, &t));
+        return t;
+    }
+    /// hist[c] = the distinct keys that c database rows carry; the last bin collects every c >= n_bins - 1
+    std::vector<uint64_t> occupancy(uint32_t n_bins) const {
+        std::vector<uint64_t> hist(n_bins, 0);
+        ctx_->check(kmu_anchor_index_occupancy(ix_, hist.data(), n_bins, KMU_MEM_HOST));
+        return hist;
+    }
+    /// kmu_anchor_index_match of nq query rows (nq x m; `group_q` empty iff the index has no groups): `pairs` gets (a, b) and
+    /// `dist` (common, total, i) of every pair, ordered by a, shared hash, b.  max_occ > 0: hashes that are keys of more than
+    /// max_occ database rows seed no pair; 0: the result of kmu_anchor_match.  Returns the number of pairs.
+    uint64_t match(const std::vector<uint64_t> &hashes_q, uint32_t nq, const std::vector<uint32_t> &group_q, uint32_t min_common,
+                   uint32_t max_occ, std::vector<uint32_t> &pairs, std::vector<uint32_t> &dist) const {
+        if (hashes_q.size() < size_t(nq) * m_ || (!group_q.empty() && group_q.size() < nq))
+            throw std::invalid_argument("AnchorIndex::match: hashes_q holds nq x m hashes, group_q nq groups");
+        const uint64_t none[2] = {UINT64_MAX, UINT64_MAX};
+        const uint64_t *q = nq ? hashes_q.data() : none;
+        const uint32_t *g = group_q.empty() ? nullptr : group_q.data();
+        uint64_t total = 0;
+        ctx_->check(kmu_anchor_index_match(ix_, q, nq, g, min_common, max_occ, KMU_MEM_HOST, nullptr, nullptr, 0, &total));
+        pairs.assign(size_t(total) * 2, 0);
+        dist.assign(size_t(total) * 3, 0);
+        if (total)
+            ctx_->check(kmu_anchor_index_match(ix_, q, nq, g, min_common, max_occ, KMU_MEM_HOST, pairs.data(), dist.data(), total, &total));
+        return total;
+    }
+
+  private:
+    Context *ctx_;
+    kmu_anchor_index *ix_ = nullptr;
+    uint32_t m_;
+};
+
+namespace detail {
+/// the window pairs of `rows` bottom-k rows against themselves, slices of one group never paired: kmu_anchor_match, or with a repeat
+/// mask (max_occ > 0) an AnchorIndex of the rows
+inline void anchor_self_join(const std::vector<uint64_t> &h, uint32_t rows, uint32_t m, uint32_t n_keys, uint32_t min_common,
+                             const std::vector<uint32_t> &group, uint32_t max_occ, Context &ctx, std::vector<uint32_t> &pairs,
+                             std::vector<uint32_t> &dist) {
+    if (max_occ) {
+        if (rows) AnchorIndex(h, rows, m, n_keys, group, ctx).match(h, rows, group, min_common, max_occ, pairs, dist);
+        else { pairs.clear(); dist.clear(); }
+        return;
+    }
+    uint64_t total = 0;
+    ctx.check(kmu_anchor_match(ctx.raw(), h.data(), rows, h.data(), rows, m, n_keys, min_common, group.data(), group.data(),
+                               KMU_MEM_HOST, nullptr, nullptr, 0, &total));
+    pairs.assign(size_t(total) * 2, 0);
+    dist.assign(size_t(total) * 3, 0);
+    if (total)
+        ctx.check(kmu_anchor_match(ctx.raw(), h.data(), rows, h.data(), rows, m, n_keys, min_common, group.data(), group.data(),
+                                   KMU_MEM_HOST, pairs.data(), dist.data(), total, &total));
+}
+}  // namespace detail
+
 /// What looking every slice up in the inverse index of `redis_dump` (anchor.rs:187-197; n_keys = 1 is its MINHASH_1) finds among the
 /// slices of `reads` (the result of gen_read_anchors), with mininvhash_distance for each hit: kmu_anchor_match as a self-join with
 /// group = read.  Slices of one read are never paired; hits with common < min_common are dropped; (a, b) and (b, a) are both
-/// reported.  Order: slice a in the order of `reads`, then the shared hash, then slice b.
+/// reported.  Order: slice a in the order of `reads`, then the shared hash, then slice b.  max_occ > 0: hashes that are keys of more
+/// than max_occ slices seed no pair (an AnchorIndex of the slices).
 template <class Kmer>
 std::vector<AnchorMatch> match_read_anchors(const std::vector<ReadAnchors<Kmer>> &reads, const AnchorsGeneratorParameters &params,
-                                            uint32_t n_keys = 1, uint32_t min_common = 1, Context &ctx = Context::global()) {
+                                            uint32_t n_keys = 1, uint32_t min_common = 1, uint32_t max_occ = 0,
+                                            Context &ctx = Context::global()) {
     const size_t m = params.get_nbkmer();
     std::vector<const SliceAnchor<Kmer> *> slices;
     std::vector<uint32_t> group;
@@ -1480,14 +1562,9 @@ std::vector<AnchorMatch> match_read_anchors(const std::vector<ReadAnchors<Kmer>>
     for (size_t r = 0; r < slices.size(); r++)
         for (size_t t = 0; t < slices[r]->minhash.size() && t < m; t++) h[r * m + t] = slices[r]->minhash[t].hashed;
     const uint32_t rows = uint32_t(slices.size());
-    uint64_t total = 0;
-    ctx.check(kmu_anchor_match(ctx.raw(), h.data(), rows, h.data(), rows, uint32_t(m), n_keys, min_common, group.data(), group.data(),
-                               KMU_MEM_HOST, nullptr, nullptr, 0, &total));
-    std::vector<uint32_t> pairs(size_t(total) * 2), dist(size_t(total) * 3);
-    if (total)
-        ctx.check(kmu_anchor_match(ctx.raw(), h.data(), rows, h.data(), rows, uint32_t(m), n_keys, min_common, group.data(),
-                                   group.data(), KMU_MEM_HOST, pairs.data(), dist.data(), total, &total));
-    std::vector<AnchorMatch> out(static_cast<size_t>(total));
+    std::vector<uint32_t> pairs, dist;
+    detail::anchor_self_join(h, rows, uint32_t(m), n_keys, min_common, group, max_occ, ctx, pairs, dist);
+    std::vector<AnchorMatch> out(pairs.size() / 2);
     for (size_t p = 0; p < out.size(); p++) {
         const SliceAnchor<Kmer> &a = *slices[pairs[2 * p]], &b = *slices[pairs[2 * p + 1]];
         out[p] = AnchorMatch{a.readnum, a.slicepos, b.readnum, b.slicepos, dist[3 * p], dist[3 * p + 1]};
@@ -1533,11 +1610,12 @@ struct Overlap {
 
 /// Which of `reads` (the result of gen_read_anchors) overlap: the self-join of match_read_anchors, then kmu_anchor_overlaps with
 /// the common of every matched pair of slices as its weight, each read pair once (a in front of b in `reads`).  strands = 2 is for
-/// anchors made with FHash::canon_value.  Order: read a, then read b, in the order of `reads`.
+/// anchors made with FHash::canon_value.  Order: read a, then read b, in the order of `reads`.  max_occ: the repeat mask of
+/// match_read_anchors.
 template <class Kmer>
 std::vector<Overlap> read_overlaps(const std::vector<ReadAnchors<Kmer>> &reads, const AnchorsGeneratorParameters &params,
                                    uint32_t n_keys = 1, uint32_t min_common = 1, uint32_t strands = 2, uint32_t band = 1,
-                                   uint32_t min_score = 2, Context &ctx = Context::global()) {
+                                   uint32_t min_score = 2, uint32_t max_occ = 0, Context &ctx = Context::global()) {
     const size_t m = params.get_nbkmer();
     std::vector<uint64_t> row_offsets(reads.size() + 1, 0);
     std::vector<uint32_t> group;
@@ -1553,13 +1631,8 @@ std::vector<Overlap> read_overlaps(const std::vector<ReadAnchors<Kmer>> &reads, 
             for (size_t t = 0; t < s.minhash.size() && t < m; t++) h[r * m + t] = s.minhash[t].hashed;
             r++;
         }
-    uint64_t total = 0;
-    ctx.check(kmu_anchor_match(ctx.raw(), h.data(), rows, h.data(), rows, uint32_t(m), n_keys, min_common, group.data(), group.data(),
-                               KMU_MEM_HOST, nullptr, nullptr, 0, &total));
-    std::vector<uint32_t> pairs(size_t(total) * 2), dist(size_t(total) * 3);
-    if (total)
-        ctx.check(kmu_anchor_match(ctx.raw(), h.data(), rows, h.data(), rows, uint32_t(m), n_keys, min_common, group.data(),
-                                   group.data(), KMU_MEM_HOST, pairs.data(), dist.data(), total, &total));
+    std::vector<uint32_t> pairs, dist;
+    detail::anchor_self_join(h, rows, uint32_t(m), n_keys, min_common, group, max_occ, ctx, pairs, dist);
     const int64_t stride = int64_t(params.get_window()) - int64_t(params.get_overlap());
     std::vector<Overlap> out;
     for (const kmu_overlap &o : anchor_overlaps(pairs, dist, row_offsets, row_offsets, strands, band, min_score, true, ctx))

@@ -678,7 +678,7 @@ int kmu_minhash_distance_pairs(kmu_ctx *ctx, const uint64_t *hashes_a, uint32_t 
  * How: the ndb * n_keys (key, row) entries are sorted by key on the device (a stable 8-bit LSD radix sort, one wave per tile of
  * KMU_ANCHOR_SORT_TILE entries and pass); one wave per query row then looks its keys up and walks each bucket 64 candidates at a
  * time, once to count and once to write.  One wave owns a whole bucket: a key shared by very many rows is slow and gives
- * quadratic output (no repeat mask here). */
+ * quadratic output (no repeat mask here: kmu_anchor_index_match has one). */
 #define KMU_ANCHOR_SORT_TILE 1024 /* entries one workgroup ranks per radix pass */
 int kmu_anchor_match(kmu_ctx *ctx, const uint64_t *hashes_q, uint32_t nq, const uint64_t *hashes_db, uint32_t ndb, uint32_t m,
                      uint32_t n_keys, uint32_t min_common, const uint32_t *group_q, const uint32_t *group_db, int mem,
@@ -730,6 +730,47 @@ int kmu_anchor_overlaps(kmu_ctx *ctx, const uint32_t *pairs, const uint32_t *dis
                         const uint64_t *row_offsets_q, uint32_t n_reads_q, const uint64_t *row_offsets_db, uint32_t n_reads_db,
                         uint32_t strands, uint32_t band, uint32_t min_score, uint32_t flags, int mem,
                         kmu_overlap *out, uint64_t cap, uint64_t *n_out);
+
+/* Anchor index: the database side of kmu_anchor_match as an object -- built once, kept on the device, matched against by any
+ * number of query batches (the reference's persistent inverse index, redis_dump, src/anchor.rs:187-197) -- with a repeat mask.
+ *   kmu_anchor_index_create: ndb bottom-k rows of length m (trusted as kmu_anchor_match trusts them), a fixed n_keys and optional
+ *   groups.  keys(b) = the first min(n_keys, n(b)) hashes of row b; the padding is never a key.  occ(h) = the number of database
+ *   rows b with h in keys(b); query rows never count towards it.  The index owns device copies of the rows and the groups (its own
+ *   allocations, not the context's workspace): the caller's arrays may be freed or overwritten once the call returns, any other
+ *   library call may run between two matches, and the index is destroyed before its context, like a kmu_counter.  The call may
+ *   synchronise.  ndb == 0 is a valid index that matches nothing.
+ *   kmu_anchor_index_match: nq query rows of the index's m.  A hash h is MASKED iff max_occ > 0 and occ(h) > max_occ.
+ *   U(a, b) = the hashes of keys(a) & keys(b) that are not masked.  Candidates: the pairs (a, b) with U(a, b) not empty and, with
+ *   groups, group_q[a] != group_db[b].  Distance: the triple of kmu_minhash_distance_pairs over the WHOLE rows, bit for bit -- the
+ *   mask decides only which pairs are seeded, never what a walk sees.  Reported: the candidates with common >= min_common, each
+ *   once, under h* = min U(a, b).  Order: a ascending, then h*, then b.  Under a mask h* is NOT "the smallest hash the two rows
+ *   share at all": the rows may share smaller hashes that are masked.  max_occ == 0 gives exactly the pairs, triples and order of
+ *   kmu_anchor_match with the same arguments, and so does any max_occ >= the largest occupancy.  *n_out, the count-only call
+ *   (pairs_out == NULL), the cap rule and the one synchronisation of a KMU_MEM_DEVICE call are those of kmu_anchor_match.
+ *   kmu_anchor_index_occupancy: hist_out[c], c < n_bins, = the number of distinct keys with occupancy c; the last bin collects
+ *   every occupancy >= n_bins - 1; hist_out[0] is 0; 2 <= n_bins <= 65536 (the conventions of kmu_count_histogram).
+ *   kmu_anchor_index_info: sizes; n_entries = the sum of |keys(b)|, n_distinct = the distinct keys, max_occupancy = the largest occ.
+ * KMU_E_BAD_ARG: null ctx / index / hashes / out / n_out, m == 0, n_keys == 0 or > m, bad mem, bad n_bins, group_q given where the
+ * index has no groups or missing where it has.  KMU_E_UNSUPPORTED: m > KMU_ANCHOR_MAX_NBKMER, ndb * n_keys >= 2^32.
+ * How: the sorted (key, row) entries of kmu_anchor_match, then a directory of the distinct keys (ukeys[d], ubeg[d]: the first
+ * entry of the bucket) so that an occupancy is a subtraction; the sorted keys are dropped.  A match looks the keys of a query row
+ * up one lane per key, by one binary search in the directory, and never touches the bucket of a masked key. */
+typedef struct kmu_anchor_index kmu_anchor_index;
+typedef struct {
+    uint32_t ndb, m, n_keys, has_groups;
+    uint64_t n_entries;      /* sum of |keys(b)| */
+    uint64_t n_distinct;     /* distinct keys */
+    uint32_t max_occupancy, pad;
+    uint64_t device_bytes;   /* device memory the index owns */
+} kmu_anchor_index_info_t;
+int kmu_anchor_index_create(kmu_ctx *ctx, const uint64_t *hashes_db, uint32_t ndb, uint32_t m, uint32_t n_keys,
+                            const uint32_t *group_db /* or NULL */, int mem, kmu_anchor_index **out);
+void kmu_anchor_index_destroy(kmu_anchor_index *ix); /* NULL: no-op */
+int kmu_anchor_index_info(const kmu_anchor_index *ix, kmu_anchor_index_info_t *out);
+int kmu_anchor_index_occupancy(kmu_anchor_index *ix, uint64_t *hist_out, uint32_t n_bins, int mem);
+int kmu_anchor_index_match(kmu_anchor_index *ix, const uint64_t *hashes_q, uint32_t nq, const uint32_t *group_q,
+                           uint32_t min_common, uint32_t max_occ, int mem, uint32_t *pairs_out, uint32_t *dist_out, uint64_t cap,
+                           uint64_t *n_out);
 
 #ifdef __cplusplus
 }

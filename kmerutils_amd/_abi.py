@@ -116,6 +116,13 @@ OVERLAP_DTYPE = [("read_a", "<u4"), ("read_b", "<u4"), ("strand", "<u4"), ("diag
                  ("slice_a_min", "<u4"), ("slice_a_max", "<u4")]
 
 
+class AnchorIndexInfo(C.Structure):
+    """kmu_anchor_index_info_t: the sizes of an anchor index (kmu_anchor_index_info)"""
+    _fields_ = [("ndb", C.c_uint32), ("m", C.c_uint32), ("n_keys", C.c_uint32), ("has_groups", C.c_uint32),
+                ("n_entries", C.c_uint64), ("n_distinct", C.c_uint64), ("max_occupancy", C.c_uint32), ("pad", C.c_uint32),
+                ("device_bytes", C.c_uint64)]
+
+
 ALLTOALLV_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_void_p,
                            C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_uint32, C.c_void_p)
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64)

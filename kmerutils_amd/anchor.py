@@ -4,7 +4,8 @@
 returns, named like the reference's structs; `anchors_by_minhash` is the inverse index min hash -> [(readnum, slicepos)] that
 the reference's `redis_dump` stores under MINHASH_1, as a plain dict on the host; `match_read_anchors` is the join that index
 exists for, on the device (kmu_anchor_match), and `rows_to_slices` names its rows; `read_overlaps` goes on from the matched
-slices to read pairs (kmu_anchor_overlaps).
+slices to read pairs (kmu_anchor_overlaps).  Both take `max_occ`, the repeat mask of the anchor index (ctx.anchor_index), and
+`max_occ_for_fraction` chooses it from the index's occupancy histogram.
 """
 import numpy as np
 
@@ -145,19 +146,41 @@ def rows_to_slices(rows, row_offsets, stride, first_readnum=0):
     return read + int(first_readnum), (rows - row_offsets[read]) * int(stride)
 
 
-def match_read_anchors(ctx, hashes, row_offsets, params, n_keys=1, min_common=1, first_readnum=0):
+def max_occ_for_fraction(hist, frac):
+    """The `max_occ` that drops the most frequent seeds: the smallest c such that at most `frac` of the distinct keys have an
+    occupancy above c.  hist: AnchorIndex.occupancy(n_bins) -- hist[c] = keys carried by c database rows, the last bin folded;
+    choose n_bins above max_occupancy, or the answer cannot pass the last bin.  Pure numpy.  frac = 0 gives the largest occupancy
+    present (nothing is masked), frac >= 1 and an empty histogram give 0 -- which, as max_occ, also means "no mask"."""
+    hist = np.asarray(hist).astype(np.int64)
+    total = int(hist.sum())
+    if total == 0:
+        return 0
+    above = total - np.cumsum(hist)  # above[c] = keys with occupancy > c; above[-1] = 0
+    return int(np.nonzero(above <= max(float(frac), 0.0) * total)[0][0])
+
+
+def _self_join(ctx, hashes, group, n_keys, min_common, max_occ):
+    """the window pairs of a batch against itself: ctx.anchor_match, or with a repeat mask an index of the batch"""
+    if not max_occ:
+        return ctx.anchor_match(hashes, hashes, n_keys=n_keys, min_common=min_common, group_q=group, group_db=group)
+    with ctx.anchor_index(hashes, n_keys=n_keys, group_db=group) as index:
+        return index.match(hashes, group_q=group, min_common=min_common, max_occ=max_occ)
+
+
+def match_read_anchors(ctx, hashes, row_offsets, params, n_keys=1, min_common=1, first_readnum=0, max_occ=0):
     """The slices of a batch that share one of their n_keys smallest hashes and belong to different reads: kmu_anchor_match as a
     self-join of the rows `hashes` (ctx.read_anchors: numpy, or torch on the device -- the join then runs on the resident rows)
     with group = read of the row.  What a lookup of every slice in the reference's inverse index (redis_dump, anchor.rs:187-197)
     finds, with mininvhash_distance for each hit.  Returns an int64 array [n, 6] of records (readnum_a, slicepos_a, readnum_b,
-    slicepos_b, common, total), ordered by row a, shared hash, row b; (a, b) and (b, a) are both there."""
+    slicepos_b, common, total), ordered by row a, shared hash, row b; (a, b) and (b, a) are both there.  max_occ > 0: hashes that
+    are keys of more than max_occ slices seed no pair (kmu_anchor_index_match on an index of the batch)."""
     row_offsets = np.asarray(row_offsets).astype(np.int64)
     nrows = int(hashes.shape[0])
     group = np.ascontiguousarray(rows_to_slices(np.arange(nrows), row_offsets, 1)[0].astype(np.uint32))
     if type(hashes).__module__.startswith("torch") and hashes.is_cuda:
         import torch
         group = torch.from_numpy(group.view(np.int32)).to(hashes.device)
-    pairs, dist = ctx.anchor_match(hashes, hashes, n_keys=n_keys, min_common=min_common, group_q=group, group_db=group)
+    pairs, dist = _self_join(ctx, hashes, group, n_keys, min_common, max_occ)
     pairs, dist = _host(pairs).astype(np.int64), _host(dist).astype(np.int64)
     out = np.zeros((pairs.shape[0], 6), np.int64)
     out[:, 0], out[:, 1] = rows_to_slices(pairs[:, 0], row_offsets, params.get_stride(), first_readnum)
@@ -175,16 +198,17 @@ def _read_groups(hashes, row_offsets):
     return group
 
 
-def read_overlaps(ctx, hashes, row_offsets, params, n_keys=1, min_common=1, strands=2, band=1, min_score=2, first_readnum=0):
+def read_overlaps(ctx, hashes, row_offsets, params, n_keys=1, min_common=1, strands=2, band=1, min_score=2, first_readnum=0,
+                  max_occ=0):
     """Which reads of a batch overlap: the self-join of match_read_anchors followed by kmu_anchor_overlaps, each read pair once
     (read a in front of read b in the batch).  With `hashes` on the device the matched slices never leave it.  The weight of a
     matched pair of slices is its `common`; `band` + 1 neighbouring diagonals vote together; strands=2 also looks for read b on
     the opposite strand (rows made with fhash=A.FHASH_CANON_VALUE), where the diagonal is the SUM of the two slice numbers.
     Returns an int64 array [n, 8] of records (readnum_a, readnum_b, strand, offset in bases = diag * stride, score, votes, first
-    and last slicepos_a of the band), ordered by readnum_a, readnum_b."""
+    and last slicepos_a of the band), ordered by readnum_a, readnum_b.  max_occ > 0: the repeat mask of match_read_anchors."""
     row_offsets = np.asarray(row_offsets).astype(np.int64)
     group = _read_groups(hashes, row_offsets)
-    pairs, dist = ctx.anchor_match(hashes, hashes, n_keys=n_keys, min_common=min_common, group_q=group, group_db=group)
+    pairs, dist = _self_join(ctx, hashes, group, n_keys, min_common, max_occ)
     rec = ctx.anchor_overlaps(pairs, dist, row_offsets.astype(np.uint64), strands=strands, band=band, min_score=min_score, upper=True)
     if type(rec).__module__.startswith("torch"):
         rec = rec.cpu().numpy()

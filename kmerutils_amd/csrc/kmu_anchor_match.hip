@@ -2,8 +2,8 @@
 // reference's inverse index smallest hash -> (readnum, slicepos) (redis_dump, src/anchor.rs:187-197) with mininvhash_distance
 // (src/sketching/minhash.rs:295-340) on every pair it finds, without leaving the device.
 //
-//  k_anchor_entries  the index: entry e = row * n_keys + t is (db[row][t], row), in row order.  The padding of a short row comes
-//                    along as key u64::MAX: it sorts to the end and no query asks for it.
+//  k_anchor_entries  (kmu_anchor_cand.h) the index: entry e = row * n_keys + t is (db[row][t], row), in row order.  The padding of
+//                    a short row comes along as key u64::MAX: it sorts to the end and no query asks for it.
 //  radix_sort_pairs  kmu_sort.h: the entries by key, stable -- ascending rows inside a key, which the output order rests on.
 //  k_anchor_match    instantiated twice, COUNT and WRITE, so that both passes walk identically.  One wave (a 64-thread
 //                    workgroup) per query row, rows dealt grid-stride, the row in LDS.  For each of its keys, in ascending order:
@@ -11,42 +11,31 @@
 //                    group test, "is this key the smallest hash the two rows share" (a merge of the two rows up to the key: a
 //                    smaller common hash is a smaller shared key, and the pair is reported there), the walk of
 //                    k_minhash_distance (minhash_walk, kmu_device.h), the min_common filter.  Survivors are compacted in lane
-//                    order with a ballot and a prefix count.  COUNT leaves one count per query row; device_scan_u32 turns the
+//                    order with a ballot and a prefix count (anchor_candidates, kmu_anchor_cand.h, which the anchor index shares).  COUNT leaves one count per query row; device_scan_u32 turns the
 //                    counts into u64 offsets; WRITE puts every pair at its offset.  Output order: query row, key, database row.
 //  One wave owns a whole bucket: a key shared by very many rows (low-complexity windows) is walked by 64 lanes and gives
-//  quadratic output.
+//  quadratic output; the repeat mask lives in the anchor index (kmu_anchor_index.hip).
 #include <algorithm>
 
+#include "kmu_anchor_cand.h"
 #include "kmu_sort.h"
 
 namespace kmu {
 
 struct MatchArgs {
-    const uint64_t *q, *db; // nq x m, ndb x m
-    uint32_t nq, ndb, m, n_keys, min_common;
-    const uint32_t *gq, *gdb; // both or neither
-    const uint64_t *skeys;    // n_entries sorted keys
-    const uint32_t *srows;    // their rows
+    const uint64_t *q; // nq x m
+    uint32_t nq, n_keys;
+    const uint32_t *gq;    // with c.gdb: both or neither
+    const uint64_t *skeys; // n_entries sorted keys (c.srows: their rows)
     uint32_t n_entries;
     uint32_t *counts;     // COUNT: pairs of every query row
     const uint64_t *offs; // WRITE: nq + 1 offsets, offs[nq] = total
-    uint64_t total;
-    uint32_t *pairs, *dist; // WRITE: total x 2, total x 3 (dist may be null)
+    CandArgs c;
 };
-
-__global__ void __launch_bounds__(256) k_anchor_entries(const uint64_t *db, uint32_t m, uint32_t n_keys, uint32_t n_entries,
-                                                        uint64_t *keys, uint32_t *rows) {
-    for (uint64_t e = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x; e < n_entries; e += (uint64_t) gridDim.x * blockDim.x) {
-        const uint32_t row = (uint32_t) (e / n_keys), t = (uint32_t) (e % n_keys);
-        keys[e] = db[(uint64_t) row * m + t];
-        rows[e] = row;
-    }
-}
 
 template <bool WRITE> __global__ void __launch_bounds__(64) k_anchor_match(MatchArgs a) {
     __shared__ uint64_t row[KMU_ANCHOR_MAX_NBKMER];
-    const uint32_t lane = (uint32_t) lane_id(), m = a.m;
-    const uint64_t below = (1ull << lane) - 1ull;
+    const uint32_t lane = (uint32_t) lane_id(), m = a.c.m;
     for (uint32_t r = blockIdx.x; r < a.nq; r += gridDim.x) {
         uint32_t n1 = 0;
         for (uint32_t t0 = 0; t0 < m; t0 += 64) { // uniform trip count
@@ -75,60 +64,12 @@ template <bool WRITE> __global__ void __launch_bounds__(64) k_anchor_match(Match
                 else hi = mid;
             }
             const uint32_t end = lo;
-            for (uint32_t c = beg; c < end; c += 64) { // uniform: all lanes reach the ballot
-                const uint32_t e = c + lane;
-                bool pass = e < end;
-                uint32_t b = 0, d[3] = {0, 0, 0};
-                if (pass) {
-                    b = a.srows[e];
-                    pass = b < a.ndb; // (always: an entry names a row of db)
-                    if (pass && a.gq) pass = a.gdb[b] != g;
-                }
-                if (pass) {
-                    const uint64_t *rb = a.db + (uint64_t) b * m;
-                    // the pair belongs to the smallest hash its rows share: none in front of row[kk] (rb holds row[kk], so
-                    // with ascending rows j stays in range; the bound keeps a malformed row from running on)
-                    uint32_t i = 0, j = 0;
-                    while (i < kk && j < m) {
-                        const uint64_t x = row[i], y = rb[j];
-                        if (x == y) break;
-                        if (x < y) i++;
-                        else j++;
-                    }
-                    pass = i == kk;
-                    if (pass) {
-                        minhash_walk(row, n1, rb, bottomk_row_len(rb, m), d);
-                        pass = d[0] >= a.min_common;
-                    }
-                }
-                const uint64_t bal = __ballot(pass);
-                if (WRITE) {
-                    const uint64_t o = at + (uint64_t) __popcll(bal & below);
-                    if (pass && o < a.total) {
-                        a.pairs[2 * o] = r;
-                        a.pairs[2 * o + 1] = b;
-                        if (a.dist) {
-                            a.dist[3 * o] = d[0];
-                            a.dist[3 * o + 1] = d[1];
-                            a.dist[3 * o + 2] = d[2];
-                        }
-                    }
-                }
-                at += (uint64_t) __popcll(bal);
-            }
+            for (uint32_t c = beg; c < end; c += 64) // uniform: all lanes reach the ballot
+                anchor_candidates<WRITE>(a.c, row, n1, r, g, kk, nullptr, c + lane, end, at);
         }
         if (!WRITE && lane == 0) a.counts[r] = (uint32_t) at;
         __syncthreads(); // the next row overwrites the LDS copy
     }
-}
-
-static int am_to_device(kmu_ctx *ctx, const char *name, const void *p, size_t bytes, int mem, const void **out) {
-    if (mem == KMU_MEM_DEVICE || !p) { *out = p; return KMU_OK; }
-    void *d;
-    KMU_TRY(dev_buf(ctx, name, bytes ? bytes : 1, &d));
-    if (bytes) KMU_HIP(ctx, hipMemcpyAsync(d, p, bytes, hipMemcpyHostToDevice, ctx->stream));
-    *out = d;
-    return KMU_OK;
 }
 
 } // namespace kmu
@@ -155,22 +96,22 @@ extern "C" int kmu_anchor_match(kmu_ctx *ctx, const uint64_t *hashes_q, uint32_t
     const void *p;
     KMU_TRY(am_to_device(ctx, "am.q", hashes_q, (size_t) nq * m * 8, mem, &p));
     a.q = (const uint64_t *) p;
-    if (hashes_db == hashes_q && ndb == nq) a.db = a.q; // a self-join is staged once
+    if (hashes_db == hashes_q && ndb == nq) a.c.db = a.q; // a self-join is staged once
     else {
         KMU_TRY(am_to_device(ctx, "am.db", hashes_db, (size_t) ndb * m * 8, mem, &p));
-        a.db = (const uint64_t *) p;
+        a.c.db = (const uint64_t *) p;
     }
     if (group_q) {
         KMU_TRY(am_to_device(ctx, "am.gq", group_q, (size_t) nq * 4, mem, &p));
         a.gq = (const uint32_t *) p;
         KMU_TRY(am_to_device(ctx, "am.gdb", group_db, (size_t) ndb * 4, mem, &p));
-        a.gdb = (const uint32_t *) p;
+        a.c.gdb = (const uint32_t *) p;
     }
     a.nq = nq;
-    a.ndb = ndb;
-    a.m = m;
+    a.c.ndb = ndb;
+    a.c.m = m;
     a.n_keys = n_keys;
-    a.min_common = min_common;
+    a.c.min_common = min_common;
     a.n_entries = n_entries;
 
     // the index
@@ -184,13 +125,13 @@ extern "C" int kmu_anchor_match(kmu_ctx *ctx, const uint64_t *hashes_q, uint32_t
     {
         const uint32_t grid = (uint32_t) std::min<uint64_t>(((uint64_t) n_entries + 255) / 256, (uint64_t) ctx->num_cus * 8);
         KernelTimer t(ctx, "k_anchor_entries");
-        hipLaunchKernelGGL(k_anchor_entries, dim3(grid), dim3(256), 0, ctx->stream, a.db, m, n_keys, n_entries, (uint64_t *) k0,
+        hipLaunchKernelGGL(k_anchor_entries, dim3(grid), dim3(256), 0, ctx->stream, a.c.db, m, n_keys, n_entries, (uint64_t *) k0,
                            (uint32_t *) v0);
     }
     KMU_HIP(ctx, hipGetLastError());
     KMU_TRY(radix_sort_pairs(ctx, (uint64_t *) k0, (uint32_t *) v0, (uint64_t *) k1, (uint32_t *) v1, n_entries));
     a.skeys = (const uint64_t *) k0;
-    a.srows = (const uint32_t *) v0;
+    a.c.srows = (const uint32_t *) v0;
 
     // COUNT, offsets, total
     const uint32_t grid = (uint32_t) std::min<uint64_t>(nq, (uint64_t) ctx->num_cus * 32);
@@ -213,16 +154,16 @@ extern "C" int kmu_anchor_match(kmu_ctx *ctx, const uint64_t *hashes_q, uint32_t
 
     // WRITE
     a.offs = (const uint64_t *) offs;
-    a.total = total;
-    a.pairs = pairs_out;
-    a.dist = dist_out;
+    a.c.total = total;
+    a.c.pairs = pairs_out;
+    a.c.dist = dist_out;
     if (mem == KMU_MEM_HOST) {
         void *d;
         KMU_TRY(dev_buf(ctx, "am.pairs", total * 8, &d));
-        a.pairs = (uint32_t *) d;
+        a.c.pairs = (uint32_t *) d;
         if (dist_out) {
             KMU_TRY(dev_buf(ctx, "am.dist", total * 12, &d));
-            a.dist = (uint32_t *) d;
+            a.c.dist = (uint32_t *) d;
         }
     }
     {
@@ -231,8 +172,8 @@ extern "C" int kmu_anchor_match(kmu_ctx *ctx, const uint64_t *hashes_q, uint32_t
     }
     KMU_HIP(ctx, hipGetLastError());
     if (mem == KMU_MEM_HOST) {
-        KMU_HIP(ctx, hipMemcpyAsync(pairs_out, a.pairs, total * 8, hipMemcpyDeviceToHost, ctx->stream));
-        if (dist_out) KMU_HIP(ctx, hipMemcpyAsync(dist_out, a.dist, total * 12, hipMemcpyDeviceToHost, ctx->stream));
+        KMU_HIP(ctx, hipMemcpyAsync(pairs_out, a.c.pairs, total * 8, hipMemcpyDeviceToHost, ctx->stream));
+        if (dist_out) KMU_HIP(ctx, hipMemcpyAsync(dist_out, a.c.dist, total * 12, hipMemcpyDeviceToHost, ctx->stream));
     }
     return finish_call(ctx, mem);
 }

@@ -33,7 +33,8 @@ SYMBOLS = [
     "kmu_sketch_count", "kmu_host_alloc", "kmu_host_free", "kmu_count_nb_occurrences", "kmu_count_table_info",
     "kmu_count_nb_saturated", "kmu_kmer_owner_minimizer", "kmu_count_owner_kind", "kmu_count_extract_superkmers", "kmu_count_add_superkmers",
     "kmu_count_histogram", "kmu_count_read_profile", "kmu_anchor_layout", "kmu_read_anchors", "kmu_anchor_match",
-    "kmu_anchor_overlaps",
+    "kmu_anchor_overlaps", "kmu_anchor_index_create", "kmu_anchor_index_destroy", "kmu_anchor_index_info",
+    "kmu_anchor_index_occupancy", "kmu_anchor_index_match",
 ]
 
 
@@ -120,6 +121,12 @@ def load():
                                    C.c_uint64, u64p]
     L.kmu_anchor_overlaps.argtypes = [vp, vp, vp, C.c_uint64, vp, C.c_uint32, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                       C.c_uint32, C.c_int, vp, C.c_uint64, u64p]
+    L.kmu_anchor_index_create.argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, C.c_int, C.POINTER(vp)]
+    L.kmu_anchor_index_destroy.argtypes = [vp]
+    L.kmu_anchor_index_destroy.restype = None
+    L.kmu_anchor_index_info.argtypes = [vp, C.POINTER(A.AnchorIndexInfo)]
+    L.kmu_anchor_index_occupancy.argtypes = [vp, vp, C.c_uint32, C.c_int]
+    L.kmu_anchor_index_match.argtypes = [vp, vp, C.c_uint32, vp, C.c_uint32, C.c_uint32, C.c_int, vp, vp, C.c_uint64, u64p]
     L.kmu_set_hll_params.argtypes = [vp, C.POINTER(A.HllParams)]
     L.kmu_kmer_hashes_compact.argtypes = [vp, C.POINTER(A.HashParams), vp, vp, vp, C.c_uint32, vp, C.c_uint64, u64p]
     L.kmu_sketch_partial_words.argtypes = [C.POINTER(A.SketchParams)]
@@ -166,7 +173,7 @@ class _StreamOrdered:
 
     _PLAIN = ("kmu_last_error", "kmu_destroy", "kmu_stream", "kmu_version", "kmu_device_count", "kmu_create",
               "kmu_block_layout", "kmu_anchor_layout", "kmu_sketch_partial_words", "kmu_count_destroy", "kmu_comm_get_id", "kmu_comm_rank",
-              "kmu_comm_nranks", "kmu_comm_get_stats", "kmu_kmer_owner", "kmu_comm_destroy")
+              "kmu_comm_nranks", "kmu_comm_get_stats", "kmu_kmer_owner", "kmu_comm_destroy", "kmu_anchor_index_info", "kmu_anchor_index_destroy")
 
     def __init__(self, lib, ctx):
         self._lib = lib
@@ -808,8 +815,82 @@ class Context:
             self._check(self.L.kmu_anchor_overlaps(*args, _ptr(out)[0], n, C.byref(total)))
         return out[:n]
 
+    def anchor_index(self, hashes_db, n_keys=1, group_db=None):
+        """kmu_anchor_index_create: the database side of anchor_match as an object that stays on the device (AnchorIndex)"""
+        return AnchorIndex(self, hashes_db, n_keys, group_db)
+
     def counter(self, kmer_type, k, counter_bits=8, capacity_hint=1 << 20, distributed=False, owner_hash=False, hint_occurrences=False):
         return Counter(self, kmer_type, k, counter_bits, capacity_hint, distributed, owner_hash, hint_occurrences)
+
+
+class AnchorIndex:
+    """kmu_anchor_index: ndb bottom-k rows (numpy, or a torch cuda tensor), their n_keys smallest hashes sorted into buckets, and
+    optionally the group of every row, kept on the device: built once, matched against by any number of query batches, and the
+    owner of the bucket sizes behind the repeat mask `max_occ` (include/kmu.h has the rules).  The index copies what it is given;
+    close it before its context."""
+
+    def __init__(self, ctx, hashes_db, n_keys=1, group_db=None):
+        self.ctx = ctx
+        self.L = ctx.L
+        self.h = None
+        mem = ctx._mem(hashes_db, group_db)
+        ndb, self.m = int(hashes_db.shape[0]), int(hashes_db.shape[1])
+        none = ctx._new_like(hashes_db, 2, np.uint64, "int64")  # an empty array has no address worth passing
+        h = C.c_void_p()
+        ctx._check(self.L.kmu_anchor_index_create(ctx.h, _ptr(hashes_db)[0] if ndb else _ptr(none)[0], ndb, self.m, int(n_keys),
+                                                  _ptr(group_db)[0], mem, C.byref(h)))
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None) and self.ctx.h:
+            self.L.kmu_anchor_index_destroy(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def info(self):
+        """kmu_anchor_index_info as a dict: ndb, m, n_keys, has_groups, n_entries, n_distinct, max_occupancy, device_bytes"""
+        t = A.AnchorIndexInfo()
+        self.ctx._check(self.L.kmu_anchor_index_info(self.h, C.byref(t)))
+        return {k: int(getattr(t, k)) for k, _ in A.AnchorIndexInfo._fields_ if k != "pad"}
+
+    def occupancy(self, n_bins):
+        """kmu_anchor_index_occupancy: hist[c] = the distinct keys that c database rows carry, the last bin collecting every
+        c >= n_bins - 1 (a numpy uint64 array: it feeds anchor.max_occ_for_fraction on the host)"""
+        hist = np.zeros(int(n_bins), np.uint64)
+        self.ctx._check(self.L.kmu_anchor_index_occupancy(self.h, _ptr(hist)[0], int(n_bins), A.MEM_HOST))
+        return hist
+
+    def match(self, hashes_q, group_q=None, min_common=1, max_occ=0):
+        """kmu_anchor_index_match: anchor_match of hashes_q against the index's rows, seeded only by keys that at most max_occ
+        database rows carry (0: no mask, the result of anchor_match).  Returns (pairs uint32 [n, 2], dist uint32 [n, 3]); device
+        tensors in give device tensors out (int32 holding the same bits).  Two library calls, one that counts and one with exactly
+        that capacity, on the one index."""
+        ctx = self.ctx
+        mem = ctx._mem(hashes_q, group_q)
+        nq = int(hashes_q.shape[0])
+        if int(hashes_q.shape[1]) != self.m:
+            raise ValueError("query rows and the index's rows differ in length")
+        none = ctx._new_like(hashes_q, 2, np.uint64, "int64")  # an empty array has no address worth passing
+        total = C.c_uint64(0)
+        args = (self.h, _ptr(hashes_q)[0] if nq else _ptr(none)[0], nq, _ptr(group_q)[0], int(min_common), int(max_occ), mem)
+        ctx._check(self.L.kmu_anchor_index_match(*args, None, None, 0, C.byref(total)))
+        n = int(total.value)
+        pairs = ctx._new_like(hashes_q, (max(n, 1), 2), np.uint32, "int32")
+        dist = ctx._new_like(hashes_q, (max(n, 1), 3), np.uint32, "int32")
+        if n:
+            ctx._check(self.L.kmu_anchor_index_match(*args, _ptr(pairs)[0], _ptr(dist)[0], n, C.byref(total)))
+        return pairs[:n], dist[:n]
 
 
 class Counter:
