@@ -14,7 +14,7 @@ LINK     := -Lkmerutils_amd -lkmu -Wl,-rpath-link,/opt/rocm/lib
 
 all: $(LIB) $(BIN)/datasketcher $(BIN)/parsefastq examples/sketch_c
 
-$(OBJDIR)/%.o: $(CSRC)/%.hip $(CSRC)/kmu_device.h $(CSRC)/kmu_stream.h $(CSRC)/kmu_ctx.hpp $(CSRC)/kmu_comm.hpp $(CSRC)/kmu_flat.h $(CSRC)/kmu_count_table.h $(CSRC)/kmu_count_part_kernels.h $(CSRC)/kmu_count_plan.hpp $(CSRC)/kmu_sketch_kernels.h $(CSRC)/kmu_sketch_host.hpp $(CSRC)/kmu_sketch_dens.h $(CSRC)/kmu_pipe_plan.hpp $(CSRC)/kmu_smer.h $(CSRC)/kmu_smer.hpp $(CSRC)/kmu_hostpack.hpp $(CSRC)/kmu_sort.h $(CSRC)/kmu_anchor_cand.h include/kmu.h
+$(OBJDIR)/%.o: $(CSRC)/%.hip $(CSRC)/kmu_device.h $(CSRC)/kmu_stream.h $(CSRC)/kmu_ctx.hpp $(CSRC)/kmu_comm.hpp $(CSRC)/kmu_flat.h $(CSRC)/kmu_count_table.h $(CSRC)/kmu_count_part_kernels.h $(CSRC)/kmu_count_plan.hpp $(CSRC)/kmu_sketch_kernels.h $(CSRC)/kmu_sketch_host.hpp $(CSRC)/kmu_sketch_dens.h $(CSRC)/kmu_pipe_plan.hpp $(CSRC)/kmu_smer.h $(CSRC)/kmu_smer.hpp $(CSRC)/kmu_hostpack.hpp $(CSRC)/kmu_sort.h $(CSRC)/kmu_anchor_db.h include/kmu.h
 	@mkdir -p $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 

@@ -1462,6 +1462,20 @@ struct AnchorMatch {
     }
 };
 
+namespace detail {
+/// The call pair of anchor matching: `call(pairs_out, dist_out, cap, n_out)` once to count, then once with exactly that capacity.
+/// Returns the number of pairs; `pairs` holds 2 and `dist` 3 values for each.
+template <class Call>
+uint64_t count_then_write(Context &ctx, std::vector<uint32_t> &pairs, std::vector<uint32_t> &dist, Call call) {
+    uint64_t total = 0;
+    ctx.check(call(nullptr, nullptr, 0, &total));
+    pairs.assign(size_t(total) * 2, 0);
+    dist.assign(size_t(total) * 3, 0);
+    if (total) ctx.check(call(pairs.data(), dist.data(), total, &total));
+    return total;
+}
+}  // namespace detail
+
 /// kmu_anchor_index: bottom-k rows (ndb x m, ascending, UINT64_MAX padding), their n_keys smallest hashes sorted into buckets and
 /// optionally the group of every row, kept on the device -- the inverse index of `redis_dump` (anchor.rs:187-197) as an object that
 /// is built once and matched against by any number of query batches.  It copies what it is given and must not outlive its context.
@@ -1504,13 +1518,9 @@ class AnchorIndex {
         const uint64_t none[2] = {UINT64_MAX, UINT64_MAX};
         const uint64_t *q = nq ? hashes_q.data() : none;
         const uint32_t *g = group_q.empty() ? nullptr : group_q.data();
-        uint64_t total = 0;
-        ctx_->check(kmu_anchor_index_match(ix_, q, nq, g, min_common, max_occ, KMU_MEM_HOST, nullptr, nullptr, 0, &total));
-        pairs.assign(size_t(total) * 2, 0);
-        dist.assign(size_t(total) * 3, 0);
-        if (total)
-            ctx_->check(kmu_anchor_index_match(ix_, q, nq, g, min_common, max_occ, KMU_MEM_HOST, pairs.data(), dist.data(), total, &total));
-        return total;
+        return detail::count_then_write(*ctx_, pairs, dist, [&](uint32_t *p, uint32_t *d, uint64_t cap, uint64_t *n) {
+            return kmu_anchor_index_match(ix_, q, nq, g, min_common, max_occ, KMU_MEM_HOST, p, d, cap, n);
+        });
     }
 
   private:
@@ -1530,14 +1540,10 @@ inline void anchor_self_join(const std::vector<uint64_t> &h, uint32_t rows, uint
         else { pairs.clear(); dist.clear(); }
         return;
     }
-    uint64_t total = 0;
-    ctx.check(kmu_anchor_match(ctx.raw(), h.data(), rows, h.data(), rows, m, n_keys, min_common, group.data(), group.data(),
-                               KMU_MEM_HOST, nullptr, nullptr, 0, &total));
-    pairs.assign(size_t(total) * 2, 0);
-    dist.assign(size_t(total) * 3, 0);
-    if (total)
-        ctx.check(kmu_anchor_match(ctx.raw(), h.data(), rows, h.data(), rows, m, n_keys, min_common, group.data(), group.data(),
-                                   KMU_MEM_HOST, pairs.data(), dist.data(), total, &total));
+    count_then_write(ctx, pairs, dist, [&](uint32_t *p, uint32_t *d, uint64_t cap, uint64_t *n) {
+        return kmu_anchor_match(ctx.raw(), h.data(), rows, h.data(), rows, m, n_keys, min_common, group.data(), group.data(), KMU_MEM_HOST,
+                                p, d, cap, n);
+    });
 }
 }  // namespace detail
 

@@ -175,11 +175,7 @@ def match_read_anchors(ctx, hashes, row_offsets, params, n_keys=1, min_common=1,
     slicepos_b, common, total), ordered by row a, shared hash, row b; (a, b) and (b, a) are both there.  max_occ > 0: hashes that
     are keys of more than max_occ slices seed no pair (kmu_anchor_index_match on an index of the batch)."""
     row_offsets = np.asarray(row_offsets).astype(np.int64)
-    nrows = int(hashes.shape[0])
-    group = np.ascontiguousarray(rows_to_slices(np.arange(nrows), row_offsets, 1)[0].astype(np.uint32))
-    if type(hashes).__module__.startswith("torch") and hashes.is_cuda:
-        import torch
-        group = torch.from_numpy(group.view(np.int32)).to(hashes.device)
+    group = _read_groups(hashes, row_offsets)
     pairs, dist = _self_join(ctx, hashes, group, n_keys, min_common, max_occ)
     pairs, dist = _host(pairs).astype(np.int64), _host(dist).astype(np.int64)
     out = np.zeros((pairs.shape[0], 6), np.int64)

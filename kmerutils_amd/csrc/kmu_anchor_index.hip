@@ -1,27 +1,28 @@
-// kmu_anchor_index.hip -- the anchor index: the database side of kmu_anchor_match built once and kept on the device (the
-// reference's persistent inverse index smallest hash -> (readnum, slicepos), redis_dump, src/anchor.rs:187-197), with the bucket
-// sizes that a repeat mask needs.
+// kmu_anchor_index.hip -- the sorted directory of a database side of the anchor join, and the anchor index: that side built once
+// and kept on the device (the reference's persistent inverse index smallest hash -> (readnum, slicepos), redis_dump,
+// src/anchor.rs:187-197), with the bucket sizes that a repeat mask needs.
 //
-//  create   k_anchor_entries and radix_sort_pairs as kmu_anchor_match runs them, then a directory of the distinct keys:
+//  anchor_db_build  for kmu_anchor_match (kmu_anchor_match.hip) and for create, in the workspace, without waiting for the stream:
+//           k_anchor_entries  entry e = row * n_keys + t is (db[row][t], row), in row order.  The padding of a short row comes
+//                           along as key u64::MAX and sorts to the end.
+//           radix_sort_pairs  kmu_sort.h: the entries by key, stable -- ascending rows inside a key, which the output order rests on
 //           k_aix_heads     one lane per sorted entry: "this key is not padding and differs from the one before"; the entry behind
 //                           which the padding starts leaves the number of real entries
-//           device_scan_u32 the flags into directory slots
+//           device_scan_u32 the flags into directory slots; behind the last, the number of distinct keys
 //           k_aix_directory ukeys[d] = the d-th distinct key, ubeg[d] = its first entry, ubeg[n_distinct] = the real entries: the
 //                           occupancy of a key (the database rows that have it among their keys) is a subtraction, and the
-//                           padding tail is in no bucket
-//           k_aix_max_occ   the largest occupancy: wave maximum, one atomic per wave
-//           The sorted keys stay in the workspace and are forgotten; the index owns srows, ukeys, ubeg, the rows and the groups.
+//                           padding tail is in no bucket.  Both counts stay on the device; the buffers have room for
+//                           ndb * n_keys entries.
+//  create   anchor_db_build, the two counts to the host, then what only a resident object needs: srows, ukeys, ubeg at their
+//           sizes as hipMallocs of the index's own, beside its copy of the rows and the groups (other calls resize the
+//           workspace), and k_aix_max_occ: the largest occupancy, wave maximum, one atomic per wave.
 //  occupancy  k_aix_occupancy: one lane per distinct key, bins below AIX_LDS_BINS meet in LDS first, one 64-bit atomic per bin
 //           and workgroup behind them.
-//  match    k_anchor_index_match<COUNT / WRITE>: one wave per query row as in k_anchor_match, but the row's keys are looked up one
-//           lane per key -- one binary search in ukeys -- and bucket begin, end and "masked" (max_occ > 0 and occupancy >
-//           max_occ) wait in LDS next to the row.  A masked key is skipped without touching its bucket; the candidates of the
-//           others go through anchor_candidates (kmu_anchor_cand.h) as k_anchor_match's do, with the flags of the query's own
-//           keys: a hash common to both rows and smaller than a shared key is among the keys of both, so a masked common hash in
-//           front of the key is one of them and is stepped over.
+//  match    its own checks and query side, then k_anchor_match through anchor_match_run (kmu_anchor_match.hip) with max_occ.
 #include <algorithm>
 
-#include "kmu_anchor_cand.h"
+#include "kmu_anchor_db.h"
+#include "kmu_device.h"
 #include "kmu_sort.h"
 
 struct kmu_anchor_index {
@@ -37,12 +38,23 @@ struct kmu_anchor_index {
     uint32_t *srows = nullptr;  // n_entries: the row of every real entry, by key, ascending inside a key
     uint64_t *ukeys = nullptr;  // n_distinct
     uint32_t *ubeg = nullptr;   // n_distinct + 1
+    uint32_t *n_distinct_dev = nullptr; // n_distinct where k_anchor_match reads it
 };
 
 namespace kmu {
 
 static constexpr uint32_t AIX_LDS_BINS = 1024;
 static constexpr uint64_t PADDING = 0xFFFFFFFFFFFFFFFFull;
+
+// entry e = row * n_keys + t is (db[row][t], row), in row order.  The padding of a short row comes along as key u64::MAX.
+__global__ void __launch_bounds__(256) k_anchor_entries(const uint64_t *db, uint32_t m, uint32_t n_keys, uint32_t n_entries, uint64_t *keys,
+                                                        uint32_t *rows) {
+    for (uint64_t e = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x; e < n_entries; e += (uint64_t) gridDim.x * blockDim.x) {
+        const uint32_t row = (uint32_t) (e / n_keys), t = (uint32_t) (e % n_keys);
+        keys[e] = db[(uint64_t) row * m + t];
+        rows[e] = row;
+    }
+}
 
 // flags[e] = 1 where a bucket starts; *n_real = the entries in front of the padding (zeroed by the host: no real entry, no write)
 __global__ void __launch_bounds__(256) k_aix_heads(const uint64_t *skeys, uint32_t n, uint32_t *flags, uint32_t *n_real) {
@@ -53,13 +65,18 @@ __global__ void __launch_bounds__(256) k_aix_heads(const uint64_t *skeys, uint32
     }
 }
 
-__global__ void __launch_bounds__(256) k_aix_directory(const uint64_t *skeys, const uint32_t *flags, const uint64_t *slot,
-                                                       uint32_t n_real, uint32_t n_distinct, uint64_t *ukeys, uint32_t *ubeg) {
-    for (uint64_t e = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x; e < n_real; e += (uint64_t) gridDim.x * blockDim.x) {
-        if (e == 0) ubeg[n_distinct] = n_real;
+// over all n >= 1 entries (no padding entry has a flag); slot[n] = the distinct keys, which entry 0 leaves in *n_distinct
+__global__ void __launch_bounds__(256) k_aix_directory(const uint64_t *skeys, const uint32_t *flags, const uint64_t *slot, uint32_t n,
+                                                       const uint32_t *n_real, uint64_t *ukeys, uint32_t *ubeg, uint32_t *n_distinct) {
+    const uint64_t nd = slot[n];
+    for (uint64_t e = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (uint64_t) gridDim.x * blockDim.x) {
+        if (e == 0) {
+            ubeg[nd] = *n_real;
+            *n_distinct = (uint32_t) nd;
+        }
         if (!flags[e]) continue;
         const uint64_t d = slot[e];
-        if (d < n_distinct) {
+        if (d < nd) {
             ukeys[d] = skeys[e];
             ubeg[d] = (uint32_t) e;
         }
@@ -91,64 +108,6 @@ __global__ void __launch_bounds__(256) k_aix_occupancy(const uint32_t *ubeg, uin
         if (bins[i]) atomicAdd(&hist[i], (unsigned long long) bins[i]);
 }
 
-struct IndexMatchArgs {
-    const uint64_t *q; // nq x m
-    uint32_t nq, n_keys, max_occ;
-    const uint32_t *gq;    // with c.gdb: both or neither
-    const uint64_t *ukeys; // n_distinct distinct keys, ascending
-    const uint32_t *ubeg;  // n_distinct + 1: the bucket of ukeys[d] is c.srows[ubeg[d] .. ubeg[d + 1])
-    uint32_t n_distinct;
-    uint32_t *counts;     // COUNT: pairs of every query row
-    const uint64_t *offs; // WRITE: nq + 1 offsets, offs[nq] = total
-    CandArgs c;
-};
-
-template <bool WRITE> __global__ void __launch_bounds__(64) k_anchor_index_match(IndexMatchArgs a) {
-    __shared__ uint64_t row[KMU_ANCHOR_MAX_NBKMER];
-    __shared__ uint32_t kbeg[KMU_ANCHOR_MAX_NBKMER], kend[KMU_ANCHOR_MAX_NBKMER]; // the bucket of every key of the row
-    __shared__ uint8_t kmask[KMU_ANCHOR_MAX_NBKMER];                              // 1: the key is masked
-    const uint32_t lane = (uint32_t) lane_id(), m = a.c.m;
-    for (uint32_t r = blockIdx.x; r < a.nq; r += gridDim.x) {
-        uint32_t n1 = 0;
-        for (uint32_t t0 = 0; t0 < m; t0 += 64) { // uniform trip count
-            const uint32_t t = t0 + lane;
-            const uint64_t h = t < m ? a.q[(uint64_t) r * m + t] : PADDING;
-            if (t < m) row[t] = h;
-            n1 += (uint32_t) __popcll(__ballot(h != PADDING));
-        }
-        __syncthreads();
-        const uint32_t nk = min(a.n_keys, n1);
-        for (uint32_t t = lane; t < nk; t += 64) { // one lane per key
-            const uint64_t key = row[t];
-            uint32_t lo = 0, hi = a.n_distinct;
-            while (lo < hi) { // first distinct key >= key
-                const uint32_t mid = lo + (hi - lo) / 2;
-                if (a.ukeys[mid] < key) lo = mid + 1;
-                else hi = mid;
-            }
-            uint32_t beg = 0, end = 0;
-            if (lo < a.n_distinct && a.ukeys[lo] == key) {
-                beg = a.ubeg[lo];
-                end = a.ubeg[lo + 1];
-            }
-            kbeg[t] = beg;
-            kend[t] = end;
-            kmask[t] = a.max_occ > 0 && end - beg > a.max_occ;
-        }
-        __syncthreads();
-        const uint32_t g = a.gq ? a.gq[r] : 0u;
-        uint64_t at = WRITE ? a.offs[r] : 0ull; // where the next pair of this row goes / how many it has so far
-        for (uint32_t kk = 0; kk < nk; kk++) {
-            if (kmask[kk]) continue; // (the same byte in every lane)
-            const uint32_t end = kend[kk];
-            for (uint32_t c = kbeg[kk]; c < end; c += 64) // uniform: all lanes reach the ballot
-                anchor_candidates<WRITE>(a.c, row, n1, r, g, kk, kmask, c + lane, end, at);
-        }
-        if (!WRITE && lane == 0) a.counts[r] = (uint32_t) at;
-        __syncthreads(); // the next row overwrites the LDS copies
-    }
-}
-
 static uint32_t aix_grid(kmu_ctx *ctx, uint64_t n) {
     return (uint32_t) std::max<uint64_t>(1, std::min<uint64_t>((n + 255) / 256, (uint64_t) ctx->num_cus * 8));
 }
@@ -159,31 +118,22 @@ static int aix_alloc(kmu_anchor_index *ix, void **p, size_t bytes) {
     return KMU_OK;
 }
 
-// everything behind the argument checks of kmu_anchor_index_create; on failure the caller destroys what exists
-static int aix_build(kmu_anchor_index *ix, const uint64_t *hashes_db, const uint32_t *group_db, int mem) {
-    kmu_ctx *ctx = ix->ctx;
-    const uint32_t ndb = ix->ndb, m = ix->m, n_keys = ix->n_keys;
-    if (ndb == 0) return KMU_OK;
-    const hipMemcpyKind up = mem == KMU_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
-    KMU_TRY(aix_alloc(ix, (void **) &ix->rows, (size_t) ndb * m * 8));
-    KMU_HIP(ctx, hipMemcpyAsync(ix->rows, hashes_db, (size_t) ndb * m * 8, up, ctx->stream));
-    if (group_db) {
-        KMU_TRY(aix_alloc(ix, (void **) &ix->groups, (size_t) ndb * 4));
-        KMU_HIP(ctx, hipMemcpyAsync(ix->groups, group_db, (size_t) ndb * 4, up, ctx->stream));
-    }
-    const uint32_t n = ndb * n_keys; // entries, padding included
-    void *k0, *v0, *k1, *v1, *flags, *slot, *stat;
+int anchor_db_build(kmu_ctx *ctx, AnchorDb *db, const uint32_t **n_real) {
+    const uint32_t n = db->ndb * db->n_keys; // entries, padding included: the host's upper bound of both counts
+    void *k0, *v0, *k1, *v1, *flags, *slot, *stat, *ukeys, *ubeg;
     KMU_TRY(dev_buf(ctx, "am.keys0", (size_t) n * 8, &k0));
     KMU_TRY(dev_buf(ctx, "am.rows0", (size_t) n * 4, &v0));
     KMU_TRY(dev_buf(ctx, "am.keys1", (size_t) n * 8, &k1));
     KMU_TRY(dev_buf(ctx, "am.rows1", (size_t) n * 4, &v1));
     KMU_TRY(dev_buf(ctx, "aix.flags", (size_t) n * 4, &flags));
     KMU_TRY(dev_buf(ctx, "aix.slot", ((size_t) n + 1) * 8, &slot));
-    KMU_TRY(dev_buf(ctx, "aix.stat", 8, &stat)); // [0] real entries, [1] largest occupancy
+    KMU_TRY(dev_buf(ctx, "aix.ukeys", (size_t) n * 8, &ukeys));
+    KMU_TRY(dev_buf(ctx, "aix.ubeg", ((size_t) n + 1) * 4, &ubeg));
+    KMU_TRY(dev_buf(ctx, "aix.stat", 8, &stat)); // [0] real entries, [1] distinct keys
     KMU_HIP(ctx, hipMemsetAsync(stat, 0, 8, ctx->stream));
     {
         KernelTimer t(ctx, "k_anchor_entries");
-        hipLaunchKernelGGL(k_anchor_entries, dim3(aix_grid(ctx, n)), dim3(256), 0, ctx->stream, (const uint64_t *) ix->rows, m, n_keys, n,
+        hipLaunchKernelGGL(k_anchor_entries, dim3(aix_grid(ctx, n)), dim3(256), 0, ctx->stream, db->rows, db->m, db->n_keys, n,
                            (uint64_t *) k0, (uint32_t *) v0);
     }
     KMU_HIP(ctx, hipGetLastError());
@@ -195,33 +145,68 @@ static int aix_build(kmu_anchor_index *ix, const uint64_t *hashes_db, const uint
     }
     KMU_HIP(ctx, hipGetLastError());
     KMU_TRY(device_scan_u32(ctx, (const uint32_t *) flags, n, (uint64_t *) slot));
-    uint64_t n_distinct = 0;
-    uint32_t h_stat[2] = {0, 0};
-    KMU_HIP(ctx, hipMemcpyAsync(&n_distinct, (const uint64_t *) slot + n, 8, hipMemcpyDeviceToHost, ctx->stream));
-    KMU_HIP(ctx, hipMemcpyAsync(h_stat, stat, 4, hipMemcpyDeviceToHost, ctx->stream));
+    {
+        KernelTimer t(ctx, "k_aix_directory");
+        hipLaunchKernelGGL(k_aix_directory, dim3(aix_grid(ctx, n)), dim3(256), 0, ctx->stream, (const uint64_t *) k0,
+                           (const uint32_t *) flags, (const uint64_t *) slot, n, (const uint32_t *) stat, (uint64_t *) ukeys,
+                           (uint32_t *) ubeg, (uint32_t *) stat + 1);
+    }
+    KMU_HIP(ctx, hipGetLastError());
+    db->srows = (const uint32_t *) v0;
+    db->ukeys = (const uint64_t *) ukeys;
+    db->ubeg = (const uint32_t *) ubeg;
+    db->n_distinct = (const uint32_t *) stat + 1;
+    if (n_real) *n_real = (const uint32_t *) stat;
+    return KMU_OK;
+}
+
+// the index as k_anchor_match reads it (before create has built the directory: its rows and groups)
+static AnchorDb aix_view(const kmu_anchor_index *ix) {
+    return AnchorDb{ix->rows, ix->groups, ix->srows, ix->ukeys, ix->ubeg, ix->n_distinct_dev, ix->ndb, ix->m, ix->n_keys};
+}
+
+// everything behind the argument checks of kmu_anchor_index_create; on failure the caller destroys what exists
+static int aix_create(kmu_anchor_index *ix, const uint64_t *hashes_db, const uint32_t *group_db, int mem) {
+    kmu_ctx *ctx = ix->ctx;
+    const uint32_t ndb = ix->ndb, m = ix->m;
+    if (ndb == 0) return KMU_OK;
+    const hipMemcpyKind up = mem == KMU_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
+    KMU_TRY(aix_alloc(ix, (void **) &ix->rows, (size_t) ndb * m * 8));
+    KMU_HIP(ctx, hipMemcpyAsync(ix->rows, hashes_db, (size_t) ndb * m * 8, up, ctx->stream));
+    if (group_db) {
+        KMU_TRY(aix_alloc(ix, (void **) &ix->groups, (size_t) ndb * 4));
+        KMU_HIP(ctx, hipMemcpyAsync(ix->groups, group_db, (size_t) ndb * 4, up, ctx->stream));
+    }
+    AnchorDb ws = aix_view(ix); // the index's rows with the directory still in the workspace
+    const uint32_t *d_real;
+    KMU_TRY(anchor_db_build(ctx, &ws, &d_real));
+    const uint64_t n = (uint64_t) ndb * ix->n_keys;
+    uint32_t n_real = 0, n_distinct = 0;
+    KMU_HIP(ctx, hipMemcpyAsync(&n_real, d_real, 4, hipMemcpyDeviceToHost, ctx->stream));
+    KMU_HIP(ctx, hipMemcpyAsync(&n_distinct, ws.n_distinct, 4, hipMemcpyDeviceToHost, ctx->stream));
     KMU_HIP(ctx, hipStreamSynchronize(ctx->stream)); // the directory is allocated at its size
-    const uint32_t n_real = h_stat[0];
-    if (n_distinct > n_real || n_real > n) return fail(ctx, KMU_E_HIP, "anchor index: %llu keys over %u of %u entries", (unsigned long long) n_distinct, n_real, n);
+    if (n_distinct > n_real || n_real > n) return fail(ctx, KMU_E_HIP, "anchor index: %u keys over %u of %llu entries", n_distinct, n_real, (unsigned long long) n);
     ix->n_entries = n_real;
     ix->n_distinct = n_distinct;
     if (n_distinct == 0) return finish_call(ctx, mem); // every row is empty
     KMU_TRY(aix_alloc(ix, (void **) &ix->srows, (size_t) n_real * 4));
     KMU_TRY(aix_alloc(ix, (void **) &ix->ukeys, (size_t) n_distinct * 8));
     KMU_TRY(aix_alloc(ix, (void **) &ix->ubeg, ((size_t) n_distinct + 1) * 4));
-    KMU_HIP(ctx, hipMemcpyAsync(ix->srows, v0, (size_t) n_real * 4, hipMemcpyDeviceToDevice, ctx->stream));
-    {
-        KernelTimer t(ctx, "k_aix_directory");
-        hipLaunchKernelGGL(k_aix_directory, dim3(aix_grid(ctx, n_real)), dim3(256), 0, ctx->stream, (const uint64_t *) k0,
-                           (const uint32_t *) flags, (const uint64_t *) slot, n_real, (uint32_t) n_distinct, ix->ukeys, ix->ubeg);
-    }
-    KMU_HIP(ctx, hipGetLastError());
+    KMU_TRY(aix_alloc(ix, (void **) &ix->n_distinct_dev, 4));
+    KMU_HIP(ctx, hipMemcpyAsync(ix->srows, ws.srows, (size_t) n_real * 4, hipMemcpyDeviceToDevice, ctx->stream));
+    KMU_HIP(ctx, hipMemcpyAsync(ix->ukeys, ws.ukeys, (size_t) n_distinct * 8, hipMemcpyDeviceToDevice, ctx->stream));
+    KMU_HIP(ctx, hipMemcpyAsync(ix->ubeg, ws.ubeg, ((size_t) n_distinct + 1) * 4, hipMemcpyDeviceToDevice, ctx->stream));
+    KMU_HIP(ctx, hipMemcpyAsync(ix->n_distinct_dev, ws.n_distinct, 4, hipMemcpyDeviceToDevice, ctx->stream));
+    void *d_max;
+    KMU_TRY(dev_buf(ctx, "aix.max_occ", 4, &d_max));
+    KMU_HIP(ctx, hipMemsetAsync(d_max, 0, 4, ctx->stream));
     {
         KernelTimer t(ctx, "k_aix_max_occ");
-        hipLaunchKernelGGL(k_aix_max_occ, dim3(aix_grid(ctx, n_distinct)), dim3(256), 0, ctx->stream, (const uint32_t *) ix->ubeg,
-                           (uint32_t) n_distinct, (uint32_t *) stat + 1);
+        hipLaunchKernelGGL(k_aix_max_occ, dim3(aix_grid(ctx, n_distinct)), dim3(256), 0, ctx->stream, (const uint32_t *) ix->ubeg, n_distinct,
+                           (uint32_t *) d_max);
     }
     KMU_HIP(ctx, hipGetLastError());
-    KMU_HIP(ctx, hipMemcpyAsync(&ix->max_occupancy, (const uint32_t *) stat + 1, 4, hipMemcpyDeviceToHost, ctx->stream));
+    KMU_HIP(ctx, hipMemcpyAsync(&ix->max_occupancy, d_max, 4, hipMemcpyDeviceToHost, ctx->stream));
     // the caller's arrays are free from here on, in both modes
     KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
     if (ctx->profiling) profile_collect(ctx);
@@ -240,7 +225,8 @@ void kmu_anchor_index_destroy(kmu_anchor_index *ix) {
         (void) hipSetDevice(ix->ctx->device);
         (void) hipStreamSynchronize(ix->ctx->stream); // a match may still be reading the index
     }
-    for (void *p : {(void *) ix->rows, (void *) ix->groups, (void *) ix->srows, (void *) ix->ukeys, (void *) ix->ubeg})
+    for (void *p : {(void *) ix->rows, (void *) ix->groups, (void *) ix->srows, (void *) ix->ukeys, (void *) ix->ubeg,
+                    (void *) ix->n_distinct_dev})
         if (p) (void) hipFree(p);
     delete ix;
 }
@@ -261,7 +247,7 @@ int kmu_anchor_index_create(kmu_ctx *ctx, const uint64_t *hashes_db, uint32_t nd
     ix->m = m;
     ix->n_keys = n_keys;
     ix->has_groups = group_db != nullptr;
-    const int rc = aix_build(ix, hashes_db, group_db, mem);
+    const int rc = aix_create(ix, hashes_db, group_db, mem);
     if (rc != KMU_OK) {
         kmu_anchor_index_destroy(ix);
         return rc;
@@ -310,75 +296,19 @@ int kmu_anchor_index_match(kmu_anchor_index *ix, const uint64_t *hashes_q, uint3
     *n_out = 0;
     KMU_HIP(ctx, hipSetDevice(ctx->device));
     if (nq == 0 || ix->n_distinct == 0) return KMU_OK;
-    const uint32_t m = ix->m;
 
-    IndexMatchArgs a{};
+    MatchArgs a{};
     const void *p;
-    KMU_TRY(am_to_device(ctx, "am.q", hashes_q, (size_t) nq * m * 8, mem, &p));
+    KMU_TRY(stage_to_device(ctx, "am.q", hashes_q, (size_t) nq * ix->m * 8, mem, &p));
     a.q = (const uint64_t *) p;
     if (group_q) {
-        KMU_TRY(am_to_device(ctx, "am.gq", group_q, (size_t) nq * 4, mem, &p));
+        KMU_TRY(stage_to_device(ctx, "am.gq", group_q, (size_t) nq * 4, mem, &p));
         a.gq = (const uint32_t *) p;
     }
-    a.nq = nq;
-    a.n_keys = ix->n_keys;
+    a.db = aix_view(ix);
+    a.min_common = min_common;
     a.max_occ = max_occ;
-    a.ukeys = ix->ukeys;
-    a.ubeg = ix->ubeg;
-    a.n_distinct = (uint32_t) ix->n_distinct;
-    a.c.db = ix->rows;
-    a.c.gdb = ix->groups;
-    a.c.srows = ix->srows;
-    a.c.ndb = ix->ndb;
-    a.c.m = m;
-    a.c.min_common = min_common;
-
-    // COUNT, offsets, total
-    void *counts, *offs;
-    KMU_TRY(dev_buf(ctx, "am.counts", (size_t) nq * 4, &counts));
-    KMU_TRY(dev_buf(ctx, "am.offs", ((size_t) nq + 1) * 8, &offs));
-    const uint32_t grid = (uint32_t) std::min<uint64_t>(nq, (uint64_t) ctx->num_cus * 32);
-    a.counts = (uint32_t *) counts;
-    {
-        KernelTimer t(ctx, "k_anchor_index_match_count");
-        hipLaunchKernelGGL(k_anchor_index_match<false>, dim3(grid), dim3(64), 0, ctx->stream, a);
-    }
-    KMU_HIP(ctx, hipGetLastError());
-    KMU_TRY(device_scan_u32(ctx, (const uint32_t *) counts, nq, (uint64_t *) offs));
-    uint64_t total = 0;
-    KMU_HIP(ctx, hipMemcpyAsync(&total, (const uint64_t *) offs + nq, 8, hipMemcpyDeviceToHost, ctx->stream));
-    KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    *n_out = total;
-    if (!pairs_out || total == 0) return finish_call(ctx, mem);
-    if (cap < total) {
-        (void) finish_call(ctx, mem);
-        return fail(ctx, KMU_E_BAD_ARG, "%llu pairs, room for %llu", (unsigned long long) total, (unsigned long long) cap);
-    }
-
-    // WRITE
-    a.offs = (const uint64_t *) offs;
-    a.c.total = total;
-    a.c.pairs = pairs_out;
-    a.c.dist = dist_out;
-    if (mem == KMU_MEM_HOST) {
-        void *d;
-        KMU_TRY(dev_buf(ctx, "am.pairs", total * 8, &d));
-        a.c.pairs = (uint32_t *) d;
-        if (dist_out) {
-            KMU_TRY(dev_buf(ctx, "am.dist", total * 12, &d));
-            a.c.dist = (uint32_t *) d;
-        }
-    }
-    {
-        KernelTimer t(ctx, "k_anchor_index_match_write");
-        hipLaunchKernelGGL(k_anchor_index_match<true>, dim3(grid), dim3(64), 0, ctx->stream, a);
-    }
-    KMU_HIP(ctx, hipGetLastError());
-    if (mem == KMU_MEM_HOST) {
-        KMU_HIP(ctx, hipMemcpyAsync(pairs_out, a.c.pairs, total * 8, hipMemcpyDeviceToHost, ctx->stream));
-        if (dist_out) KMU_HIP(ctx, hipMemcpyAsync(dist_out, a.c.dist, total * 12, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    return finish_call(ctx, mem);
+    return anchor_match_run(ctx, a, nq, mem, pairs_out, dist_out, cap, n_out);
 }
 
 } // extern "C"

@@ -1,75 +1,181 @@
 // kmu_anchor_match.hip -- pair bottom-k rows that share one of their smallest hashes (kmu_anchor_match): the join behind the
 // reference's inverse index smallest hash -> (readnum, slicepos) (redis_dump, src/anchor.rs:187-197) with mininvhash_distance
-// (src/sketching/minhash.rs:295-340) on every pair it finds, without leaving the device.
+// (src/sketching/minhash.rs:295-340) on every pair it finds, without leaving the device.  The match kernel and its driver live
+// here, for this call and for the anchor index (kmu_anchor_index.hip) alike.
 //
-//  k_anchor_entries  (kmu_anchor_cand.h) the index: entry e = row * n_keys + t is (db[row][t], row), in row order.  The padding of
-//                    a short row comes along as key u64::MAX: it sorts to the end and no query asks for it.
-//  radix_sort_pairs  kmu_sort.h: the entries by key, stable -- ascending rows inside a key, which the output order rests on.
+//  anchor_db_build   kmu_anchor_index.hip: the database's (key, row) entries sorted by key and a directory of the distinct keys,
+//                    in the workspace.  kmu_anchor_match is "a directory in the workspace, matched once, forgotten".
 //  k_anchor_match    instantiated twice, COUNT and WRITE, so that both passes walk identically.  One wave (a 64-thread
-//                    workgroup) per query row, rows dealt grid-stride, the row in LDS.  For each of its keys, in ascending order:
-//                    lower and upper bound in the sorted keys, then the bucket 64 entries at a time, one lane per candidate:
-//                    group test, "is this key the smallest hash the two rows share" (a merge of the two rows up to the key: a
-//                    smaller common hash is a smaller shared key, and the pair is reported there), the walk of
-//                    k_minhash_distance (minhash_walk, kmu_device.h), the min_common filter.  Survivors are compacted in lane
-//                    order with a ballot and a prefix count (anchor_candidates, kmu_anchor_cand.h, which the anchor index shares).  COUNT leaves one count per query row; device_scan_u32 turns the
-//                    counts into u64 offsets; WRITE puts every pair at its offset.  Output order: query row, key, database row.
+//                    workgroup) per query row, rows dealt grid-stride, the row in LDS.  Its keys are looked up one lane per key
+//                    -- one binary search in the distinct keys -- and bucket begin, end and "masked" (max_occ > 0 and occupancy >
+//                    max_occ; kmu_anchor_match passes 0: nothing is) wait in LDS next to the row.  A masked key is skipped
+//                    without touching its bucket; the others, in ascending order, are walked 64 entries at a time, one lane per
+//                    candidate (anchor_candidates): group test, "is this key the smallest unmasked hash the two rows share" (a
+//                    merge of the two rows up to the key), the walk of k_minhash_distance (minhash_walk, kmu_device.h), the
+//                    min_common filter; survivors are compacted in lane order with a ballot and a prefix count.
+//  anchor_match_run  COUNT leaves one count per query row; device_scan_u32 turns the counts into u64 offsets; the total crosses
+//                    to the host; WRITE puts every pair at its offset.  Output order: query row, key, database row.
 //  One wave owns a whole bucket: a key shared by very many rows (low-complexity windows) is walked by 64 lanes and gives
-//  quadratic output; the repeat mask lives in the anchor index (kmu_anchor_index.hip).
+//  quadratic output; the repeat mask is the anchor index's max_occ.
 #include <algorithm>
 
-#include "kmu_anchor_cand.h"
-#include "kmu_sort.h"
+#include "kmu_anchor_db.h"
+#include "kmu_device.h"
 
 namespace kmu {
 
-struct MatchArgs {
-    const uint64_t *q; // nq x m
-    uint32_t nq, n_keys;
-    const uint32_t *gq;    // with c.gdb: both or neither
-    const uint64_t *skeys; // n_entries sorted keys (c.srows: their rows)
-    uint32_t n_entries;
-    uint32_t *counts;     // COUNT: pairs of every query row
-    const uint64_t *offs; // WRITE: nq + 1 offsets, offs[nq] = total
-    CandArgs c;
-};
+static constexpr uint64_t PADDING = 0xFFFFFFFFFFFFFFFFull;
+
+// One chunk of a bucket, by one whole wave: lane l has candidate entry e = chunk + l of the bucket that ends at `end` (lanes
+// behind the end stand by: every lane reaches the ballot).  `row` is query row r (n1 entries, group g) and row[kk] the key of
+// the bucket.  Group test; "is row[kk] the smallest hash under which the pair is seeded" -- a merge of the two rows up to the
+// key: a common hash in front of it is a smaller shared key and the pair is reported there, unless `masked` says that this key
+// of the query is masked: then it seeds nothing and is stepped over --; the walk of k_minhash_distance over the whole rows; the
+// min_common filter.  Survivors are compacted in lane order with a ballot and a prefix count behind `at`, which moves on by
+// their number (COUNT: only that).
+template <bool WRITE>
+__device__ __forceinline__ void anchor_candidates(const MatchArgs &a, const uint64_t *row, uint32_t n1, uint32_t r, uint32_t g,
+                                                  uint32_t kk, const uint8_t *masked, uint32_t e, uint32_t end, uint64_t &at) {
+    const uint32_t m = a.db.m;
+    bool pass = e < end;
+    uint32_t b = 0, d[3] = {0, 0, 0};
+    if (pass) {
+        b = a.db.srows[e];
+        pass = b < a.db.ndb; // (always: an entry names a row of the database)
+        if (pass && a.db.groups) pass = a.db.groups[b] != g;
+    }
+    if (pass) {
+        const uint64_t *rb = a.db.rows + (uint64_t) b * m;
+        // none in front of row[kk] (rb holds row[kk], so with ascending rows j stays in range; the bound keeps a malformed row
+        // from running on)
+        uint32_t i = 0, j = 0;
+        while (i < kk && j < m) {
+            const uint64_t x = row[i], y = rb[j];
+            if (x == y) {
+                if (!masked[i]) break;
+                i++;
+                j++;
+            } else if (x < y) i++;
+            else j++;
+        }
+        pass = i == kk;
+        if (pass) {
+            minhash_walk(row, n1, rb, bottomk_row_len(rb, m), d);
+            pass = d[0] >= a.min_common;
+        }
+    }
+    const uint64_t bal = __ballot(pass);
+    if (WRITE) {
+        const uint64_t o = at + (uint64_t) __popcll(bal & ((1ull << lane_id()) - 1ull));
+        if (pass && o < a.total) {
+            a.pairs[2 * o] = r;
+            a.pairs[2 * o + 1] = b;
+            if (a.dist) {
+                a.dist[3 * o] = d[0];
+                a.dist[3 * o + 1] = d[1];
+                a.dist[3 * o + 2] = d[2];
+            }
+        }
+    }
+    at += (uint64_t) __popcll(bal);
+}
 
 template <bool WRITE> __global__ void __launch_bounds__(64) k_anchor_match(MatchArgs a) {
     __shared__ uint64_t row[KMU_ANCHOR_MAX_NBKMER];
-    const uint32_t lane = (uint32_t) lane_id(), m = a.c.m;
+    __shared__ uint32_t kbeg[KMU_ANCHOR_MAX_NBKMER], kend[KMU_ANCHOR_MAX_NBKMER]; // the bucket of every key of the row
+    __shared__ uint8_t kmask[KMU_ANCHOR_MAX_NBKMER];                              // 1: the key is masked
+    const uint32_t lane = (uint32_t) lane_id(), m = a.db.m;
+    const uint32_t n_distinct = *a.db.n_distinct;
     for (uint32_t r = blockIdx.x; r < a.nq; r += gridDim.x) {
         uint32_t n1 = 0;
         for (uint32_t t0 = 0; t0 < m; t0 += 64) { // uniform trip count
             const uint32_t t = t0 + lane;
-            const uint64_t h = t < m ? a.q[(uint64_t) r * m + t] : 0xFFFFFFFFFFFFFFFFull;
+            const uint64_t h = t < m ? a.q[(uint64_t) r * m + t] : PADDING;
             if (t < m) row[t] = h;
-            n1 += (uint32_t) __popcll(__ballot(h != 0xFFFFFFFFFFFFFFFFull));
+            n1 += (uint32_t) __popcll(__ballot(h != PADDING));
         }
         __syncthreads();
-        const uint32_t nk = min(a.n_keys, n1);
+        const uint32_t nk = min(a.db.n_keys, n1);
+        for (uint32_t t = lane; t < nk; t += 64) { // one lane per key
+            const uint64_t key = row[t];
+            uint32_t lo = 0, hi = n_distinct;
+            while (lo < hi) { // first distinct key >= key
+                const uint32_t mid = lo + (hi - lo) / 2;
+                if (a.db.ukeys[mid] < key) lo = mid + 1;
+                else hi = mid;
+            }
+            uint32_t beg = 0, end = 0; // a key the directory does not have, or an empty directory: an empty bucket
+            if (lo < n_distinct && a.db.ukeys[lo] == key) {
+                beg = a.db.ubeg[lo];
+                end = a.db.ubeg[lo + 1];
+            }
+            kbeg[t] = beg;
+            kend[t] = end;
+            kmask[t] = a.max_occ > 0 && end - beg > a.max_occ;
+        }
+        __syncthreads();
         const uint32_t g = a.gq ? a.gq[r] : 0u;
         uint64_t at = WRITE ? a.offs[r] : 0ull; // where the next pair of this row goes / how many it has so far
         for (uint32_t kk = 0; kk < nk; kk++) {
-            const uint64_t key = row[kk];
-            uint32_t lo = 0, hi = a.n_entries;
-            while (lo < hi) { // first entry with skeys >= key
-                const uint32_t mid = lo + (hi - lo) / 2;
-                if (a.skeys[mid] < key) lo = mid + 1;
-                else hi = mid;
-            }
-            const uint32_t beg = lo;
-            hi = a.n_entries;
-            while (lo < hi) { // first entry with skeys > key
-                const uint32_t mid = lo + (hi - lo) / 2;
-                if (a.skeys[mid] <= key) lo = mid + 1;
-                else hi = mid;
-            }
-            const uint32_t end = lo;
-            for (uint32_t c = beg; c < end; c += 64) // uniform: all lanes reach the ballot
-                anchor_candidates<WRITE>(a.c, row, n1, r, g, kk, nullptr, c + lane, end, at);
+            if (kmask[kk]) continue; // (the same byte in every lane)
+            const uint32_t end = kend[kk];
+            for (uint32_t c = kbeg[kk]; c < end; c += 64) // uniform: all lanes reach the ballot
+                anchor_candidates<WRITE>(a, row, n1, r, g, kk, kmask, c + lane, end, at);
         }
         if (!WRITE && lane == 0) a.counts[r] = (uint32_t) at;
-        __syncthreads(); // the next row overwrites the LDS copy
+        __syncthreads(); // the next row overwrites the LDS copies
     }
+}
+
+int anchor_match_run(kmu_ctx *ctx, MatchArgs &a, uint32_t nq, int mem, uint32_t *pairs_out, uint32_t *dist_out, uint64_t cap,
+                     uint64_t *n_out) {
+    // COUNT, offsets, total
+    void *counts, *offs;
+    KMU_TRY(dev_buf(ctx, "am.counts", (size_t) nq * 4, &counts));
+    KMU_TRY(dev_buf(ctx, "am.offs", ((size_t) nq + 1) * 8, &offs));
+    const uint32_t grid = (uint32_t) std::min<uint64_t>(nq, (uint64_t) ctx->num_cus * 32);
+    a.nq = nq;
+    a.counts = (uint32_t *) counts;
+    {
+        KernelTimer t(ctx, "k_anchor_match_count");
+        hipLaunchKernelGGL(k_anchor_match<false>, dim3(grid), dim3(64), 0, ctx->stream, a);
+    }
+    KMU_HIP(ctx, hipGetLastError());
+    KMU_TRY(device_scan_u32(ctx, (const uint32_t *) counts, nq, (uint64_t *) offs));
+    uint64_t total = 0;
+    KMU_HIP(ctx, hipMemcpyAsync(&total, (const uint64_t *) offs + nq, 8, hipMemcpyDeviceToHost, ctx->stream));
+    KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    *n_out = total;
+    if (!pairs_out || total == 0) return finish_call(ctx, mem);
+    if (cap < total) {
+        (void) finish_call(ctx, mem);
+        return fail(ctx, KMU_E_BAD_ARG, "%llu pairs, room for %llu", (unsigned long long) total, (unsigned long long) cap);
+    }
+
+    // WRITE
+    a.offs = (const uint64_t *) offs;
+    a.total = total;
+    a.pairs = pairs_out;
+    a.dist = dist_out;
+    if (mem == KMU_MEM_HOST) {
+        void *d;
+        KMU_TRY(dev_buf(ctx, "am.pairs", total * 8, &d));
+        a.pairs = (uint32_t *) d;
+        if (dist_out) {
+            KMU_TRY(dev_buf(ctx, "am.dist", total * 12, &d));
+            a.dist = (uint32_t *) d;
+        }
+    }
+    {
+        KernelTimer t(ctx, "k_anchor_match_write");
+        hipLaunchKernelGGL(k_anchor_match<true>, dim3(grid), dim3(64), 0, ctx->stream, a);
+    }
+    KMU_HIP(ctx, hipGetLastError());
+    if (mem == KMU_MEM_HOST) {
+        KMU_HIP(ctx, hipMemcpyAsync(pairs_out, a.pairs, total * 8, hipMemcpyDeviceToHost, ctx->stream));
+        if (dist_out) KMU_HIP(ctx, hipMemcpyAsync(dist_out, a.dist, total * 12, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    return finish_call(ctx, mem);
 }
 
 } // namespace kmu
@@ -90,90 +196,26 @@ extern "C" int kmu_anchor_match(kmu_ctx *ctx, const uint64_t *hashes_q, uint32_t
     *n_out = 0;
     KMU_HIP(ctx, hipSetDevice(ctx->device));
     if (nq == 0 || ndb == 0) return KMU_OK;
-    const uint32_t n_entries = ndb * n_keys;
 
     MatchArgs a{};
     const void *p;
-    KMU_TRY(am_to_device(ctx, "am.q", hashes_q, (size_t) nq * m * 8, mem, &p));
+    KMU_TRY(stage_to_device(ctx, "am.q", hashes_q, (size_t) nq * m * 8, mem, &p));
     a.q = (const uint64_t *) p;
-    if (hashes_db == hashes_q && ndb == nq) a.c.db = a.q; // a self-join is staged once
+    if (hashes_db == hashes_q && ndb == nq) a.db.rows = a.q; // a self-join is staged once
     else {
-        KMU_TRY(am_to_device(ctx, "am.db", hashes_db, (size_t) ndb * m * 8, mem, &p));
-        a.c.db = (const uint64_t *) p;
+        KMU_TRY(stage_to_device(ctx, "am.db", hashes_db, (size_t) ndb * m * 8, mem, &p));
+        a.db.rows = (const uint64_t *) p;
     }
     if (group_q) {
-        KMU_TRY(am_to_device(ctx, "am.gq", group_q, (size_t) nq * 4, mem, &p));
+        KMU_TRY(stage_to_device(ctx, "am.gq", group_q, (size_t) nq * 4, mem, &p));
         a.gq = (const uint32_t *) p;
-        KMU_TRY(am_to_device(ctx, "am.gdb", group_db, (size_t) ndb * 4, mem, &p));
-        a.c.gdb = (const uint32_t *) p;
+        KMU_TRY(stage_to_device(ctx, "am.gdb", group_db, (size_t) ndb * 4, mem, &p));
+        a.db.groups = (const uint32_t *) p;
     }
-    a.nq = nq;
-    a.c.ndb = ndb;
-    a.c.m = m;
-    a.n_keys = n_keys;
-    a.c.min_common = min_common;
-    a.n_entries = n_entries;
-
-    // the index
-    void *k0, *v0, *k1, *v1, *counts, *offs;
-    KMU_TRY(dev_buf(ctx, "am.keys0", (size_t) n_entries * 8, &k0));
-    KMU_TRY(dev_buf(ctx, "am.rows0", (size_t) n_entries * 4, &v0));
-    KMU_TRY(dev_buf(ctx, "am.keys1", (size_t) n_entries * 8, &k1));
-    KMU_TRY(dev_buf(ctx, "am.rows1", (size_t) n_entries * 4, &v1));
-    KMU_TRY(dev_buf(ctx, "am.counts", (size_t) nq * 4, &counts));
-    KMU_TRY(dev_buf(ctx, "am.offs", ((size_t) nq + 1) * 8, &offs));
-    {
-        const uint32_t grid = (uint32_t) std::min<uint64_t>(((uint64_t) n_entries + 255) / 256, (uint64_t) ctx->num_cus * 8);
-        KernelTimer t(ctx, "k_anchor_entries");
-        hipLaunchKernelGGL(k_anchor_entries, dim3(grid), dim3(256), 0, ctx->stream, a.c.db, m, n_keys, n_entries, (uint64_t *) k0,
-                           (uint32_t *) v0);
-    }
-    KMU_HIP(ctx, hipGetLastError());
-    KMU_TRY(radix_sort_pairs(ctx, (uint64_t *) k0, (uint32_t *) v0, (uint64_t *) k1, (uint32_t *) v1, n_entries));
-    a.skeys = (const uint64_t *) k0;
-    a.c.srows = (const uint32_t *) v0;
-
-    // COUNT, offsets, total
-    const uint32_t grid = (uint32_t) std::min<uint64_t>(nq, (uint64_t) ctx->num_cus * 32);
-    a.counts = (uint32_t *) counts;
-    {
-        KernelTimer t(ctx, "k_anchor_match_count");
-        hipLaunchKernelGGL(k_anchor_match<false>, dim3(grid), dim3(64), 0, ctx->stream, a);
-    }
-    KMU_HIP(ctx, hipGetLastError());
-    KMU_TRY(device_scan_u32(ctx, (const uint32_t *) counts, nq, (uint64_t *) offs));
-    uint64_t total = 0;
-    KMU_HIP(ctx, hipMemcpyAsync(&total, (const uint64_t *) offs + nq, 8, hipMemcpyDeviceToHost, ctx->stream));
-    KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    *n_out = total;
-    if (!pairs_out || total == 0) return finish_call(ctx, mem);
-    if (cap < total) {
-        (void) finish_call(ctx, mem);
-        return fail(ctx, KMU_E_BAD_ARG, "%llu pairs, room for %llu", (unsigned long long) total, (unsigned long long) cap);
-    }
-
-    // WRITE
-    a.offs = (const uint64_t *) offs;
-    a.c.total = total;
-    a.c.pairs = pairs_out;
-    a.c.dist = dist_out;
-    if (mem == KMU_MEM_HOST) {
-        void *d;
-        KMU_TRY(dev_buf(ctx, "am.pairs", total * 8, &d));
-        a.c.pairs = (uint32_t *) d;
-        if (dist_out) {
-            KMU_TRY(dev_buf(ctx, "am.dist", total * 12, &d));
-            a.c.dist = (uint32_t *) d;
-        }
-    }
-    {
-        KernelTimer t(ctx, "k_anchor_match_write");
-        hipLaunchKernelGGL(k_anchor_match<true>, dim3(grid), dim3(64), 0, ctx->stream, a);
-    }
-    KMU_HIP(ctx, hipGetLastError());
-    if (mem == KMU_MEM_HOST) {
-        KMU_HIP(ctx, hipMemcpyAsync(pairs_out, a.c.pairs, total * 8, hipMemcpyDeviceToHost, ctx->stream));
-        if (dist_out) KMU_HIP(ctx, hipMemcpyAsync(dist_out, a.c.dist, total * 12, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    return finish_call(ctx, mem);
+    a.db.ndb = ndb;
+    a.db.m = m;
+    a.db.n_keys = n_keys;
+    a.min_common = min_common; // (max_occ stays 0: no mask)
+    KMU_TRY(anchor_db_build(ctx, &a.db, nullptr));
+    return anchor_match_run(ctx, a, nq, mem, pairs_out, dist_out, cap, n_out);
 }

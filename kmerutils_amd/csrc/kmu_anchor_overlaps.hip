@@ -252,15 +252,6 @@ template <bool WRITE> __global__ void __launch_bounds__(64) k_ovl_best(OvlArgs a
     }
 }
 
-static int ovl_to_device(kmu_ctx *ctx, const char *name, const void *p, size_t bytes, int mem, const void **out) {
-    if (mem == KMU_MEM_DEVICE || !p) { *out = p; return KMU_OK; }
-    void *d;
-    KMU_TRY(dev_buf(ctx, name, bytes ? bytes : 1, &d));
-    if (bytes) KMU_HIP(ctx, hipMemcpyAsync(d, p, bytes, hipMemcpyHostToDevice, ctx->stream));
-    *out = d;
-    return KMU_OK;
-}
-
 // the radix passes that can tell two read ids below n apart: one bit per byte of n - 1 (at least the lowest)
 static uint32_t ovl_id_passes(uint32_t n) {
     uint32_t m = 1, top = n - 1;
@@ -299,15 +290,15 @@ extern "C" int kmu_anchor_overlaps(kmu_ctx *ctx, const uint32_t *pairs, const ui
 
     OvlArgs a{};
     const void *p;
-    KMU_TRY(ovl_to_device(ctx, "ovl.pairs", pairs, (size_t) n_pairs * 8, mem, &p));
+    KMU_TRY(stage_to_device(ctx, "ovl.pairs", pairs, (size_t) n_pairs * 8, mem, &p));
     a.pairs = (const uint32_t *) p;
-    KMU_TRY(ovl_to_device(ctx, "ovl.dist", dist, (size_t) n_pairs * 12, mem, &p));
+    KMU_TRY(stage_to_device(ctx, "ovl.dist", dist, (size_t) n_pairs * 12, mem, &p));
     a.dist = (const uint32_t *) p;
-    KMU_TRY(ovl_to_device(ctx, "ovl.offq", row_offsets_q, ((size_t) n_reads_q + 1) * 8, mem, &p));
+    KMU_TRY(stage_to_device(ctx, "ovl.offq", row_offsets_q, ((size_t) n_reads_q + 1) * 8, mem, &p));
     a.off_q = (const uint64_t *) p;
     if (row_offsets_db == row_offsets_q && n_reads_db == n_reads_q) a.off_db = a.off_q; // a self-join is staged once
     else {
-        KMU_TRY(ovl_to_device(ctx, "ovl.offdb", row_offsets_db, ((size_t) n_reads_db + 1) * 8, mem, &p));
+        KMU_TRY(stage_to_device(ctx, "ovl.offdb", row_offsets_db, ((size_t) n_reads_db + 1) * 8, mem, &p));
         a.off_db = (const uint64_t *) p;
     }
     a.n_pairs = n_pairs;

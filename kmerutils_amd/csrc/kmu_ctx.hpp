@@ -103,6 +103,15 @@ inline int dev_buf(kmu_ctx *ctx, const char *name, size_t bytes, void **out) {
     *out = b.p;
     return KMU_OK;
 }
+// a host array of a KMU_MEM_HOST call staged in workspace `name`; a device array (or null) as it is
+inline int stage_to_device(kmu_ctx *ctx, const char *name, const void *p, size_t bytes, int mem, const void **out) {
+    if (mem == KMU_MEM_DEVICE || !p) { *out = p; return KMU_OK; }
+    void *d;
+    KMU_TRY(dev_buf(ctx, name, bytes ? bytes : 1, &d));
+    if (bytes) KMU_HIP(ctx, hipMemcpyAsync(d, p, bytes, hipMemcpyHostToDevice, ctx->stream));
+    *out = d;
+    return KMU_OK;
+}
 inline int host_buf(kmu_ctx *ctx, const char *name, size_t bytes, void **out) {
     auto &b = ctx->hbufs[name];
     if (b.bytes < bytes) {

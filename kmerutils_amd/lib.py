@@ -769,14 +769,19 @@ class Context:
         none = self._new_like(hashes_q, 2, np.uint64, "int64")  # an empty array has no address worth passing
         pq = _ptr(hashes_q)[0] if nq else _ptr(none)[0]
         pdb = _ptr(hashes_db)[0] if ndb else _ptr(none)[0]
-        total = C.c_uint64(0)
         args = (self.h, pq, nq, pdb, ndb, m, int(n_keys), int(min_common), _ptr(group_q)[0], _ptr(group_db)[0], mem)
-        self._check(self.L.kmu_anchor_match(*args, None, None, 0, C.byref(total)))
+        return self._count_then_write(self.L.kmu_anchor_match, args, hashes_q)
+
+    def _count_then_write(self, fn, args, like):
+        """the call pair of anchor_match and AnchorIndex.match: fn(*args, pairs_out, dist_out, cap, n_out) once to count, then
+        once with exactly that capacity; (pairs [n, 2], dist [n, 3]) allocated where `like` lives"""
+        total = C.c_uint64(0)
+        self._check(fn(*args, None, None, 0, C.byref(total)))
         n = int(total.value)
-        pairs = self._new_like(hashes_q, (max(n, 1), 2), np.uint32, "int32")
-        dist = self._new_like(hashes_q, (max(n, 1), 3), np.uint32, "int32")
+        pairs = self._new_like(like, (max(n, 1), 2), np.uint32, "int32")
+        dist = self._new_like(like, (max(n, 1), 3), np.uint32, "int32")
         if n:
-            self._check(self.L.kmu_anchor_match(*args, _ptr(pairs)[0], _ptr(dist)[0], n, C.byref(total)))
+            self._check(fn(*args, _ptr(pairs)[0], _ptr(dist)[0], n, C.byref(total)))
         return pairs[:n], dist[:n]
 
     def anchor_overlaps(self, pairs, dist, row_offsets_q, row_offsets_db=None, strands=2, band=1, min_score=1, upper=False):
@@ -882,15 +887,8 @@ class AnchorIndex:
         if int(hashes_q.shape[1]) != self.m:
             raise ValueError("query rows and the index's rows differ in length")
         none = ctx._new_like(hashes_q, 2, np.uint64, "int64")  # an empty array has no address worth passing
-        total = C.c_uint64(0)
         args = (self.h, _ptr(hashes_q)[0] if nq else _ptr(none)[0], nq, _ptr(group_q)[0], int(min_common), int(max_occ), mem)
-        ctx._check(self.L.kmu_anchor_index_match(*args, None, None, 0, C.byref(total)))
-        n = int(total.value)
-        pairs = ctx._new_like(hashes_q, (max(n, 1), 2), np.uint32, "int32")
-        dist = ctx._new_like(hashes_q, (max(n, 1), 3), np.uint32, "int32")
-        if n:
-            ctx._check(self.L.kmu_anchor_index_match(*args, _ptr(pairs)[0], _ptr(dist)[0], n, C.byref(total)))
-        return pairs[:n], dist[:n]
+        return ctx._count_then_write(self.L.kmu_anchor_index_match, args, hashes_q)
 
 
 class Counter:

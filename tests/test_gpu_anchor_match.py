@@ -312,6 +312,77 @@ def test_empty_sides_and_argument_errors(ctx, batch):
     assert e.value.code == bad
 
 
+# ---- the directory of the database, built in the workspace for the one call ----------------------------------------------------
+@pytest.mark.parametrize("n_keys", [1, 4])
+@pytest.mark.parametrize("ndb", [1, 65])
+def test_database_rows_all_empty(ctx, ndb, n_keys):
+    """nothing but padding on the database side: a directory without a key, which only the device knows"""
+    hq = mk_rows([[1, 2, 3, 4, 5], [7], list(range(10, 26))], 16)
+    hdb = np.full((ndb, 16), MAXH, np.uint64)
+    p, d = ctx.anchor_match(hq, hdb, n_keys=n_keys, min_common=0)
+    assert p.shape == (0, 2) and d.shape == (0, 3)
+    out = np.zeros((4, 2), np.uint32)
+    assert raw(ctx, hq, 3, hdb, ndb, 16, n_keys, 0, None, None, out, None, 4) == (A.OK, 0)
+    assert (out == 0).all()
+
+
+def test_database_rows_shorter_than_n_keys_and_empty_rows(ctx, oracle):
+    """short, empty and full database rows: their padding is sorted behind the real entries and is in no bucket"""
+    rng = np.random.default_rng(55)
+    pool = make_pool(rng, 600)
+    lens = rng.integers(0, 17, 400)
+    lens[:6] = [0, 3, 16, 0, 1, 2]
+    lens[-1] = 0
+    assert (lens < 4).sum() > 20 and (lens == 16).sum() > 5
+    hdb = pool_rows(rng, 400, 16, pool, lens=lens)
+    hq = pool_rows(rng, 80, 16, pool)
+    got_p, _ = check(ctx, oracle, hq, hdb, 4, 1)
+    assert not (set(got_p[:, 1].tolist()) & {0, 3, 399})  # empty rows match nothing
+    check(ctx, oracle, hq, hdb, 4, 0)
+    # a query row of nothing but padding asks for no key, and a full one's later hashes are not keys
+    hq2 = np.concatenate([np.full((1, 16), MAXH, np.uint64), hq[:5]])
+    got_p, _ = check(ctx, oracle, hq2, hdb, 4, 0)
+    assert 0 not in got_p[:, 0].tolist()
+
+
+def test_keys_the_directory_does_not_have(ctx, oracle):
+    """query keys below the smallest database key, above the largest, and strictly between two neighbours, next to hits"""
+    hdb = mk_rows([[100, 200, 900], [200, 300, 901], [300, 400, 902]], 4)  # keys (n_keys = 2): 100, 200, 300, 400
+    hq = mk_rows([[5, 50, 200],       # both keys below the smallest
+                  [500, 0xFFFFFFFFFFFFFFFE],  # both above the largest
+                  [150, 250, 300],    # both between two neighbours (300 is its third hash: no key)
+                  [99, 100, 200],     # a miss below, then a hit
+                  [300, 350, 400],    # a hit, then a miss between
+                  [400, 401],         # the largest key, then a miss above
+                  [250, 300]], 4)     # a miss between, then a hit
+    got_p, _ = check(ctx, oracle, hq, hdb, 2, 0)
+    assert got_p.tolist() == [[3, 0], [4, 1], [4, 2], [5, 2], [6, 1], [6, 2]]
+    check(ctx, oracle, hq, hdb, 1, 0)
+
+
+def test_the_workspace_directory_and_an_index_do_not_meet(oracle):
+    """an index owns its directory: a one-shot call that grows and overwrites the workspace in between leaves it alone (a context
+    of its own, so that the workspace is as small as the index's build left it)"""
+    rng = np.random.default_rng(31)
+    pool = make_pool(rng, 500)
+    ha = pool_rows(rng, 70, 8, pool, lens=rng.integers(1, 9, 70))
+    pool_b = make_pool(rng, 9000)
+    hb = pool_rows(rng, 3000, 8, pool_b, lens=np.full(3000, 8))
+    hq = pool_rows(rng, 60, 8, np.concatenate([pool, pool_b[:200]]))
+    want_p, want_d = brute(oracle, hq, ha, 4, 1)
+    assert want_p.shape[0] > 0
+    ctx = lib.Context(0)
+    try:
+        with ctx.anchor_index(ha, n_keys=4) as index:
+            check(ctx, oracle, hq, hb, 4, 0)
+            got_p, got_d = index.match(hq, min_common=1)
+            assert np.array_equal(got_p, want_p) and np.array_equal(got_d, want_d)
+            one_p, one_d = ctx.anchor_match(hq, ha, n_keys=4, min_common=1)
+            assert np.array_equal(one_p, got_p) and np.array_equal(one_d, got_d)
+    finally:
+        ctx.close()
+
+
 # ---- end to end ---------------------------------------------------------------------------------------------------------------
 def test_read_anchors_then_match(ctx, oracle):
     rng = np.random.default_rng(2024)
