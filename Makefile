@@ -6,7 +6,9 @@ CC       ?= gcc
 HIPFLAGS ?= --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -Wall -Wno-unused-function
 CSRC     := kmerutils_amd/csrc
 OBJDIR   := kmerutils_amd/build
-SOURCES  := kmu_api kmu_sketch kmu_sketch_pmh kmu_sketch_pipe kmu_sketch_kernels kmu_sketch_super kmu_sketch_dens kmu_sketch_groups kmu_anchor kmu_count kmu_count_read kmu_count_part kmu_count_part_kernels kmu_count_dist kmu_smer kmu_hostpack kmu_compare kmu_knn kmu_anchor_match kmu_anchor_index kmu_anchor_overlaps kmu_ingest kmu_kmergen kmu_comm
+# one source list: every .hip under csrc/ is a translation unit of the library, every header there (and the C header) a dependency of all
+SOURCES  := $(sort $(patsubst $(CSRC)/%.hip,%,$(wildcard $(CSRC)/*.hip)))
+HEADERS  := $(sort $(wildcard $(CSRC)/*.h $(CSRC)/*.hpp)) include/kmu.h
 OBJS     := $(SOURCES:%=$(OBJDIR)/%.o)
 LIB      := kmerutils_amd/libkmu.so
 BIN      := kmerutils_amd/bin
@@ -14,7 +16,7 @@ LINK     := -Lkmerutils_amd -lkmu -Wl,-rpath-link,/opt/rocm/lib
 
 all: $(LIB) $(BIN)/datasketcher $(BIN)/parsefastq examples/sketch_c
 
-$(OBJDIR)/%.o: $(CSRC)/%.hip $(CSRC)/kmu_device.h $(CSRC)/kmu_stream.h $(CSRC)/kmu_ctx.hpp $(CSRC)/kmu_comm.hpp $(CSRC)/kmu_flat.h $(CSRC)/kmu_count_table.h $(CSRC)/kmu_count_part_kernels.h $(CSRC)/kmu_count_plan.hpp $(CSRC)/kmu_sketch_kernels.h $(CSRC)/kmu_sketch_host.hpp $(CSRC)/kmu_sketch_dens.h $(CSRC)/kmu_pipe_plan.hpp $(CSRC)/kmu_smer.h $(CSRC)/kmu_smer.hpp $(CSRC)/kmu_hostpack.hpp $(CSRC)/kmu_sort.h $(CSRC)/kmu_anchor_db.h include/kmu.h
+$(OBJDIR)/%.o: $(CSRC)/%.hip $(HEADERS)
 	@mkdir -p $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 

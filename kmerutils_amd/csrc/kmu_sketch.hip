@@ -3,7 +3,7 @@
 // unit's files share: parameter checks, compact hashing, the per-sequence dispatch (kmu_sketch_host.hpp).  The ProbMinHash3a /
 // bottom-k routes are in kmu_sketch_pmh.hip, kmu_sketch_count in kmu_sketch_pipe.hip, kmu_sketch_groups in kmu_sketch_groups.hip.
 // Reference: SeqSketcherT::sketch_compressedkmer / sketch_compressedkmer_seqs (src/sketching/setsketchert.rs:54-80,
-// seqsketchjaccard.rs:211-319), datasketcher's loop (src/bin/datasketcher.rs:222-226).  The kernels are in kmu_sketch_kernels.hip.
+// seqsketchjaccard.rs:211-319), datasketcher's loop (src/bin/datasketcher.rs:222-226).  The kernels are in kmu_pmh_*.hip (one file per route) and kmu_sketch_aux.hip.
 #include <algorithm>
 
 #include "kmu_sketch_host.hpp"

@@ -1,6 +1,7 @@
 // kmu_sketch_kernels.h -- what the host side of the sketch path (kmu_sketch_pmh.hip: routes, launches; kmu_sketch.hip: the C entry points) needs of
-// the per-sequence sketch kernels (kmu_sketch_kernels.hip): their argument block, the constants their LDS budgets are made of,
-// and their declarations (the template kernels are instantiated in kmu_sketch_kernels.hip for exactly the forms listed here).
+// the per-sequence sketch kernels (one file per route: kmu_pmh_general.hip, kmu_pmh_uq.hip, kmu_pmh_short.hip, kmu_pmh_smallk.hip, kmu_pmh_points.hip;
+// the small ones in kmu_sketch_aux.hip): their argument block, the constants their LDS budgets are made of, and their declarations (every
+// kernel file instantiates the template kernels it defines for exactly the forms listed here).
 #pragma once
 
 #include "kmu_ctx.hpp"
@@ -112,19 +113,21 @@ static constexpr size_t SHORT_WAVE_BYTES = (size_t) SHORT_SLOTS * 12 + SHORT_WOR
 static constexpr uint32_t SMALLK_WORDS = 32768;  // LDS words of the histogram (128 KiB)
 static constexpr uint32_t SMALLK_TILE = 1024;    // staged code words per tile
 
-// ---- the kernels (definitions and comments: kmu_sketch_kernels.hip) ------------------------------------------------------------
+// ---- the kernels (definitions and comments: kmu_pmh_*.hip, kmu_sketch_aux.hip) -------------------------------------------------
+// (the template kernels carry their launch bounds HERE as well: the `extern template` lines below instantiate the declaration they see, and a
+//  bound that only the definition has is then lost -- k_pmh_points was compiled for 1 024 threads instead of 256 that way)
 template <bool AA, bool BOTTOMK, bool EMIT = false, bool PLAIN = false>
-__global__ void k_sketch_pmh3a(SketchArgs a);
+__global__ void __launch_bounds__(1024) k_sketch_pmh3a(SketchArgs a);
 __global__ void k_pts_long_list(const uint32_t *lst_n, uint32_t n_seq, uint32_t thr, uint32_t *out);
 template <bool SIG32>
-__global__ void k_pmh_points(SketchArgs a);
+__global__ void __launch_bounds__(256) k_pmh_points(SketchArgs a);
 template <int UQ_THREADS, uint32_t UQ_BM_BITS, uint32_t UQ_COLL, int MINW>
-__global__ void k_multiset_uq(SketchArgs a);
+__global__ void __launch_bounds__(UQ_THREADS, MINW) k_multiset_uq(SketchArgs a);
 __global__ void k_multiset_short(SketchArgs a);
 template <bool SIG32>
-__global__ void k_pmh_points_short(SketchArgs a);
+__global__ void __launch_bounds__(256) k_pmh_points_short(SketchArgs a);
 template <bool EMIT>
-__global__ void k_sketch_smallk(SketchArgs a);
+__global__ void __launch_bounds__(1024) k_sketch_smallk(SketchArgs a);
 __global__ void k_pmh_reduce(const uint64_t *part_h, const uint64_t *part_k, uint64_t n_parts, int m, uint64_t stride, int sig_bytes, void *sig_out,
                              uint64_t *part_out);
 __global__ void k_max_len(const uint64_t *offsets, uint32_t n_seq, uint64_t *out);
@@ -133,16 +136,18 @@ __global__ void k_seq_hashes_compact(const uint8_t *bases, const uint64_t *offse
                                      uint64_t total, KmerCfg cfg, const uint64_t *koff, uint64_t *out, uint32_t *err, int spread);
 __global__ void k_widen_u32(const uint32_t *in, uint64_t n, uint64_t *out);
 
-// the forms of the template kernels the host launches: instantiated in kmu_sketch_kernels.hip, declared for everybody else
-#define KMU_SKETCH_KERNEL_FORMS(X)                                                                                                  \
+// the forms of the template kernels the host launches, by the file that defines and instantiates them; declared for everybody
+#define KMU_PMH_GENERAL_FORMS(X)                                                                                                    \
     X(k_sketch_pmh3a<false, false>) X(k_sketch_pmh3a<false, false, true>) X(k_sketch_pmh3a<true, true>) X(k_sketch_pmh3a<true, false>) \
-    X(k_sketch_pmh3a<false, true>) X(k_sketch_pmh3a<false, false, false, true>)                                                       \
-    X(k_pmh_points<true>) X(k_pmh_points<false>) X(k_pmh_points_short<true>) X(k_pmh_points_short<false>)                             \
-    X(k_multiset_uq<512, UQ1_BM, UQ1_COLL, 4>) X(k_multiset_uq<1024, UQ2_BM, UQ2_COLL, 4>) X(k_sketch_smallk<true>) X(k_sketch_smallk<false>)
-#ifndef KMU_SKETCH_KERNELS_TU
+    X(k_sketch_pmh3a<false, true>) X(k_sketch_pmh3a<false, false, false, true>)
+#define KMU_PMH_POINTS_FORMS(X) X(k_pmh_points<true>) X(k_pmh_points<false>)
+#define KMU_PMH_SHORT_FORMS(X) X(k_pmh_points_short<true>) X(k_pmh_points_short<false>)
+#define KMU_PMH_UQ_FORMS(X) X(k_multiset_uq<512, UQ1_BM, UQ1_COLL, 4>) X(k_multiset_uq<1024, UQ2_BM, UQ2_COLL, 4>)
+#define KMU_PMH_SMALLK_FORMS(X) X(k_sketch_smallk<true>) X(k_sketch_smallk<false>)
+#define KMU_SKETCH_KERNEL_FORMS(X) \
+    KMU_PMH_GENERAL_FORMS(X) KMU_PMH_POINTS_FORMS(X) KMU_PMH_SHORT_FORMS(X) KMU_PMH_UQ_FORMS(X) KMU_PMH_SMALLK_FORMS(X)
 #define KMU_X_EXTERN(...) extern template __global__ void __VA_ARGS__(SketchArgs);
 KMU_SKETCH_KERNEL_FORMS(KMU_X_EXTERN)
 #undef KMU_X_EXTERN
-#endif
 
 } // namespace kmu

@@ -1,6 +1,6 @@
 // kmu_sketch_pmh.hip -- the host side of ProbMinHash3a / bottom-k: which kernels a batch takes (routes chosen per call from the
 // batch's shape), their launches and scratch buffers, and the long-sequence detour of the per-sequence path.
-// The kernels are in kmu_sketch_kernels.hip.
+// The kernels are in kmu_pmh_*.hip, one file per route (declarations: kmu_sketch_kernels.h; shared device steps: kmu_pmh_steps.h).
 #include <algorithm>
 #include <cmath>
 
