@@ -24,6 +24,8 @@
  *                 AnchorMatch, match_read_anchors (the join behind redis_dump's index)     src/anchor.rs:187-197
  *                 AnchorIndex (that index as a resident object, with a repeat mask)        src/anchor.rs:187-197
  *                 Overlap, anchor_overlaps, read_overlaps (read pairs from matched slices)  (beyond the reference)
+ *                 Components, components, components_knn, ReadClusters, read_clusters       (beyond the reference)
+ *                                                            (connected components of overlap records / neighbour lists)
  *   counting      KmerCountT (trait), KmerCounter, KmerCounterPool, count_kmer_threaded_one_to_many
  *                                                            src/base/kmercount.rs:48-123, 424-565, 881-974
  *   io            FASTQ reader rule, signature / count dumps src/io.rs:12-72, src/bin/datasketcher.rs:358-388,
@@ -1614,14 +1616,13 @@ struct Overlap {
     }
 };
 
-/// Which of `reads` (the result of gen_read_anchors) overlap: the self-join of match_read_anchors, then kmu_anchor_overlaps with
-/// the common of every matched pair of slices as its weight, each read pair once (a in front of b in `reads`).  strands = 2 is for
-/// anchors made with FHash::canon_value.  Order: read a, then read b, in the order of `reads`.  max_occ: the repeat mask of
-/// match_read_anchors.
+namespace detail {
+/// the kmu_overlap records of `reads` against themselves (each read pair once, read indices into `reads`): the front of
+/// read_overlaps and read_clusters
 template <class Kmer>
-std::vector<Overlap> read_overlaps(const std::vector<ReadAnchors<Kmer>> &reads, const AnchorsGeneratorParameters &params,
-                                   uint32_t n_keys = 1, uint32_t min_common = 1, uint32_t strands = 2, uint32_t band = 1,
-                                   uint32_t min_score = 2, uint32_t max_occ = 0, Context &ctx = Context::global()) {
+std::vector<kmu_overlap> read_overlap_records(const std::vector<ReadAnchors<Kmer>> &reads, const AnchorsGeneratorParameters &params,
+                                              uint32_t n_keys, uint32_t min_common, uint32_t strands, uint32_t band, uint32_t min_score,
+                                              uint32_t max_occ, Context &ctx) {
     const size_t m = params.get_nbkmer();
     std::vector<uint64_t> row_offsets(reads.size() + 1, 0);
     std::vector<uint32_t> group;
@@ -1638,12 +1639,107 @@ std::vector<Overlap> read_overlaps(const std::vector<ReadAnchors<Kmer>> &reads, 
             r++;
         }
     std::vector<uint32_t> pairs, dist;
-    detail::anchor_self_join(h, rows, uint32_t(m), n_keys, min_common, group, max_occ, ctx, pairs, dist);
+    anchor_self_join(h, rows, uint32_t(m), n_keys, min_common, group, max_occ, ctx, pairs, dist);
+    return anchor_overlaps(pairs, dist, row_offsets, row_offsets, strands, band, min_score, true, ctx);
+}
+}  // namespace detail
+
+/// Which of `reads` (the result of gen_read_anchors) overlap: the self-join of match_read_anchors, then kmu_anchor_overlaps with
+/// the common of every matched pair of slices as its weight, each read pair once (a in front of b in `reads`).  strands = 2 is for
+/// anchors made with FHash::canon_value.  Order: read a, then read b, in the order of `reads`.  max_occ: the repeat mask of
+/// match_read_anchors.
+template <class Kmer>
+std::vector<Overlap> read_overlaps(const std::vector<ReadAnchors<Kmer>> &reads, const AnchorsGeneratorParameters &params,
+                                   uint32_t n_keys = 1, uint32_t min_common = 1, uint32_t strands = 2, uint32_t band = 1,
+                                   uint32_t min_score = 2, uint32_t max_occ = 0, Context &ctx = Context::global()) {
     const int64_t stride = int64_t(params.get_window()) - int64_t(params.get_overlap());
     std::vector<Overlap> out;
-    for (const kmu_overlap &o : anchor_overlaps(pairs, dist, row_offsets, row_offsets, strands, band, min_score, true, ctx))
+    for (const kmu_overlap &o : detail::read_overlap_records(reads, params, n_keys, min_common, strands, band, min_score, max_occ, ctx))
         out.push_back(Overlap{reads[o.read_a].readnum, reads[o.read_b].readnum, o.strand, int64_t(o.diag) * stride, o.score, o.votes,
                               uint32_t(o.slice_a_min * stride), uint32_t(o.slice_a_max * stride)});
+    return out;
+}
+
+/// what kmu_components gives for n nodes: label[v] the smallest node of v's component, cluster[v] its dense number (clusters in
+/// the order of their smallest node), size[c] for c < n_components, members the nodes by (cluster, node)
+struct Components {
+    std::vector<uint32_t> label, cluster, size, members;
+    uint32_t n_components = 0;
+};
+
+namespace detail {
+template <class Call> Components components_call(Context &ctx, uint32_t n_nodes, Call call) {
+    Components c;
+    const size_t n = std::max<size_t>(n_nodes, 1); // an empty vector has no address worth passing
+    c.label.assign(n, 0);
+    c.cluster.assign(n, 0);
+    c.size.assign(n, 0);
+    c.members.assign(n, 0);
+    ctx.check(call(c.label.data(), c.cluster.data(), c.size.data(), c.members.data(), &c.n_components));
+    c.label.resize(n_nodes);
+    c.cluster.resize(n_nodes);
+    c.members.resize(n_nodes);
+    c.size.resize(c.n_components);
+    return c;
+}
+}  // namespace detail
+
+/// kmu_components on host arrays: the connected components of the graph over nodes 0 .. n_nodes - 1 whose edges are the records of
+/// `stride` words in `edges` (words 0 and 1: the ends); with weight_at != 0 a record counts iff its word weight_at >= min_weight
+/// (include/kmu.h has the rules).
+inline Components components(const std::vector<uint32_t> &edges, uint32_t n_nodes, uint32_t stride = 2, uint32_t weight_at = 0,
+                             uint32_t min_weight = 0, Context &ctx = Context::global()) {
+    if (stride < 2 || edges.size() % stride != 0) throw std::invalid_argument("components: edges holds records of stride >= 2 words");
+    const uint32_t none[2] = {0, 0};
+    const uint64_t n_edges = edges.size() / stride;
+    return detail::components_call(ctx, n_nodes, [&](uint32_t *l, uint32_t *c, uint32_t *s, uint32_t *m, uint32_t *n) {
+        return kmu_components(ctx.raw(), n_nodes, n_edges ? edges.data() : none, n_edges, stride, weight_at, min_weight, KMU_MEM_HOST, l, c,
+                              s, m, n);
+    });
+}
+
+/// ... on the records of anchor_overlaps as they are: a record counts iff its score (by_votes: its votes) >= min_weight
+inline Components components(const std::vector<kmu_overlap> &records, uint32_t n_nodes, uint32_t min_weight = 0, bool by_votes = false,
+                             Context &ctx = Context::global()) {
+    static_assert(sizeof(kmu_overlap) == 32, "a record is 8 words");
+    const kmu_overlap none{};
+    return detail::components_call(ctx, n_nodes, [&](uint32_t *l, uint32_t *c, uint32_t *s, uint32_t *m, uint32_t *n) {
+        return kmu_components(ctx.raw(), n_nodes, reinterpret_cast<const uint32_t *>(records.empty() ? &none : records.data()),
+                              records.size(), 8, by_votes ? 5 : 4, min_weight, KMU_MEM_HOST, l, c, s, m, n);
+    });
+}
+
+/// kmu_components_knn on the lists of a sig_knn self-join: n_nodes rows of k entries; row i is joined to idx[i * k + j] iff
+/// eq[i * k + j] >= min_eq (an empty `eq`: every entry counts, min_eq must be 0); KMU_KNN_NONE entries join nothing
+inline Components components_knn(const std::vector<uint32_t> &idx, const std::vector<uint16_t> &eq, uint32_t n_nodes, uint32_t k,
+                                 uint32_t min_eq = 0, Context &ctx = Context::global()) {
+    if (idx.size() != size_t(n_nodes) * k) throw std::invalid_argument("components_knn: idx holds n_nodes x k entries");
+    if (!eq.empty() && eq.size() != idx.size()) throw std::invalid_argument("components_knn: eq holds one value per entry of idx");
+    const uint32_t none[2] = {0, 0};
+    return detail::components_call(ctx, n_nodes, [&](uint32_t *l, uint32_t *c, uint32_t *s, uint32_t *m, uint32_t *n) {
+        return kmu_components_knn(ctx.raw(), n_nodes, idx.empty() ? none : idx.data(), eq.empty() ? nullptr : eq.data(), k, min_eq,
+                                  KMU_MEM_HOST, l, c, s, m, n);
+    });
+}
+
+/// the reads that belong together: cluster[i] of reads[i] (clusters numbered in the order of their first read), the number of reads
+/// in every cluster, and the readnum of the reads ordered by (cluster, position in `reads`)
+struct ReadClusters {
+    std::vector<uint32_t> cluster, size, members;
+};
+
+/// read_overlaps, then the connected components of the graph whose nodes are the reads and whose edges are the overlap records
+/// with score >= min_score (by_votes: the records with votes >= min_score; the vote itself then drops nothing).  A read that
+/// overlaps nothing is a cluster of one.
+template <class Kmer>
+ReadClusters read_clusters(const std::vector<ReadAnchors<Kmer>> &reads, const AnchorsGeneratorParameters &params, uint32_t n_keys = 1,
+                           uint32_t min_common = 1, uint32_t strands = 2, uint32_t band = 1, uint32_t min_score = 2,
+                           uint32_t max_occ = 0, bool by_votes = false, Context &ctx = Context::global()) {
+    const auto records =
+        detail::read_overlap_records(reads, params, n_keys, min_common, strands, band, by_votes ? 0u : min_score, max_occ, ctx);
+    Components c = components(records, uint32_t(reads.size()), min_score, by_votes, ctx);
+    ReadClusters out{std::move(c.cluster), std::move(c.size), std::move(c.members)};
+    for (uint32_t &r : out.members) r = reads[r].readnum;
     return out;
 }
 

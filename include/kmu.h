@@ -772,6 +772,46 @@ int kmu_anchor_index_match(kmu_anchor_index *ix, const uint64_t *hashes_q, uint3
                            uint32_t min_common, uint32_t max_occ, int mem, uint32_t *pairs_out, uint32_t *dist_out, uint64_t cap,
                            uint64_t *n_out);
 
+/* Connected components: from edges between items -- the kmu_overlap records of kmu_anchor_overlaps, the pairs of kmu_anchor_match,
+ * the neighbour lists of kmu_sig_knn -- to which items belong together, without the edges leaving the device.
+ *   Graph: undirected, over the nodes 0 .. n_nodes - 1.
+ *   kmu_components: edge e is the record edges[e * stride .. e * stride + stride - 1] (uint32 words, e * stride in 64 bits): u = word 0,
+ *   v = word 1.  weight_at == 0: every edge counts.  Otherwise 2 <= weight_at < stride and the edge counts iff word weight_at >=
+ *   min_weight.  Pairs of kmu_anchor_match: stride 2, weight_at 0; kmu_overlap records: stride 8, weight_at 4 (score) or 5 (votes).
+ *   kmu_components_knn: the lists of a kmu_sig_knn self-join (nq == ndb == n_nodes): edge (i, idx[i * k + j]) counts iff
+ *   eq[i * k + j] >= min_eq; eq == NULL (min_eq must then be 0): every edge counts.
+ *   An edge that does not count is skipped, and so is a self loop (u == v).  An edge with an endpoint >= n_nodes is skipped and never
+ *   used as an index (KMU_KNN_NONE entries fall out by this rule): no input makes a kernel read or write out of bounds.  Duplicate
+ *   edges and edges given in both directions change nothing.
+ *   label_out[v] (n_nodes entries, required): the smallest node of v's component.
+ *   cluster_out[v] (n_nodes entries, or NULL): the number of components whose smallest node is below label_out[v] -- dense ids
+ *   0 .. n_components - 1 in the order of the smallest member.
+ *   size_out[c] (n_nodes entries, or NULL): the size of cluster c for c < n_components, 0 from there on.
+ *   members_out (n_nodes entries, or NULL): the nodes ordered by (cluster, node); cluster c occupies the entries from the exclusive
+ *   prefix sum of size_out.
+ *   *n_components_out (host memory in both modes, or NULL): the number of components.
+ *   A pure function of the inputs: the result does not depend on the order of the edges, on the launch shape or on timing.
+ * n_nodes == 0: KMU_OK, 0 components, no array is written.  n_edges == 0: every node is its own cluster.
+ * KMU_MEM_DEVICE: every array except n_components_out is device memory.  The count is the only thing that has to cross to the
+ * host: with n_components_out the call synchronises the stream once to hand it over (also in async_device contexts); with NULL an
+ * async_device context enqueues and returns, which is how a pipeline keeps going.  KMU_MEM_HOST: the inputs go up through the
+ * context's workspace and the results come back, as in kmu_anchor_overlaps.
+ * KMU_E_BAD_ARG: null ctx / label_out, null edges with n_edges > 0 (null idx with n_nodes > 0), stride < 2, weight_at == 1 or
+ * >= stride, k == 0 with n_nodes > 0, null eq with min_eq > 0, bad mem.  KMU_E_UNSUPPORTED: n_nodes == 0xFFFFFFFF.
+ * How: a lock-free union-find with label_out as the parent array.  One lane per edge finds the roots of both ends (relaxed
+ * agent-scope atomic loads, path halving), leaves if they are equal -- once a component has formed most of its edges touch no root
+ * with an atomic -- and otherwise hooks the LARGER root under the SMALLER by compare-and-swap; a lane that loses the race goes on
+ * with the value it saw, so no lane ever waits for another.  parent[v] <= v holds throughout and entries only decrease: the root a
+ * component ends with is its smallest node, whoever won which race.  Then every node takes its root; the roots are flagged and
+ * scanned for the dense numbers; sizes are integer atomic adds; the member lists are a stable radix sort of (cluster, node). */
+int kmu_components(kmu_ctx *ctx, uint32_t n_nodes, const uint32_t *edges, uint64_t n_edges, uint32_t stride,
+                   uint32_t weight_at, uint32_t min_weight, int mem,
+                   uint32_t *label_out, uint32_t *cluster_out, uint32_t *size_out, uint32_t *members_out,
+                   uint32_t *n_components_out);
+int kmu_components_knn(kmu_ctx *ctx, uint32_t n_nodes, const uint32_t *idx, const uint16_t *eq, uint32_t k, uint32_t min_eq,
+                       int mem, uint32_t *label_out, uint32_t *cluster_out, uint32_t *size_out, uint32_t *members_out,
+                       uint32_t *n_components_out);
+
 #ifdef __cplusplus
 }
 #endif

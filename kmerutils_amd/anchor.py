@@ -4,8 +4,9 @@
 returns, named like the reference's structs; `anchors_by_minhash` is the inverse index min hash -> [(readnum, slicepos)] that
 the reference's `redis_dump` stores under MINHASH_1, as a plain dict on the host; `match_read_anchors` is the join that index
 exists for, on the device (kmu_anchor_match), and `rows_to_slices` names its rows; `read_overlaps` goes on from the matched
-slices to read pairs (kmu_anchor_overlaps).  Both take `max_occ`, the repeat mask of the anchor index (ctx.anchor_index), and
-`max_occ_for_fraction` chooses it from the index's occupancy histogram.
+slices to read pairs (kmu_anchor_overlaps), and `read_clusters` from those to the sets of reads that belong together
+(kmu_components).  All three take `max_occ`, the repeat mask of the anchor index (ctx.anchor_index), and `max_occ_for_fraction`
+chooses it from the index's occupancy histogram.
 """
 import numpy as np
 
@@ -220,3 +221,28 @@ def read_overlaps(ctx, hashes, row_offsets, params, n_keys=1, min_common=1, stra
     out[:, 6] = rec["slice_a_min"].astype(np.int64) * stride
     out[:, 7] = rec["slice_a_max"].astype(np.int64) * stride
     return out
+
+
+def read_clusters(ctx, hashes, row_offsets, params, n_keys=1, min_common=1, strands=2, band=1, min_score=2, first_readnum=0,
+                  max_occ=0, by="score", want_members=False):
+    """Which reads of a batch belong together: the self-join and the vote of read_overlaps, then the connected components of the
+    graph whose nodes are the reads and whose edges are the overlap records that count (kmu_components on the records as they
+    are: stride 8).  by="score": a record counts iff its score >= min_score (word 4); by="votes": iff its votes >= min_score (word
+    5; the vote itself then drops nothing).  With `hashes` on the device neither the matched slices nor the records leave it.
+    Returns (cluster int64 [n_reads], sizes int64 [n_clusters]): the cluster of every read -- clusters are numbered in the order
+    of their first read -- and the number of reads in each; a read that overlaps nothing is a cluster of one.  want_members=True
+    adds the read numbers (from first_readnum) ordered by (cluster, read): cluster c is members[sizes[:c].sum():][:sizes[c]]."""
+    if by not in ("score", "votes"):
+        raise ValueError("by must be 'score' or 'votes'")
+    row_offsets = np.asarray(row_offsets).astype(np.int64)
+    n_reads = int(row_offsets.shape[0]) - 1
+    group = _read_groups(hashes, row_offsets)
+    pairs, dist = _self_join(ctx, hashes, group, n_keys, min_common, max_occ)
+    rec = ctx.anchor_overlaps(pairs, dist, row_offsets.astype(np.uint64), strands=strands, band=band,
+                              min_score=min_score if by == "score" else 0, upper=True)
+    want = ("cluster", "size", "members") if want_members else ("cluster", "size")
+    res = ctx.components(rec, n_reads, weight_at=4 if by == "score" else 5, min_weight=min_score, want=want)
+    cluster, sizes = _host(res.cluster).astype(np.int64), _host(res.size).astype(np.int64)
+    if not want_members:
+        return cluster, sizes
+    return cluster, sizes, _host(res.members).astype(np.int64) + int(first_readnum)

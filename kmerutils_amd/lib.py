@@ -3,6 +3,7 @@
 The product path: every compute call goes to hand-written gfx950 kernels.  There is no CPU fallback -- if the
 shared library is missing or no HIP device is present this module raises, loudly.
 """
+import collections
 import ctypes as C
 import os
 
@@ -34,8 +35,15 @@ SYMBOLS = [
     "kmu_count_nb_saturated", "kmu_kmer_owner_minimizer", "kmu_count_owner_kind", "kmu_count_extract_superkmers", "kmu_count_add_superkmers",
     "kmu_count_histogram", "kmu_count_read_profile", "kmu_anchor_layout", "kmu_read_anchors", "kmu_anchor_match",
     "kmu_anchor_overlaps", "kmu_anchor_index_create", "kmu_anchor_index_destroy", "kmu_anchor_index_info",
-    "kmu_anchor_index_occupancy", "kmu_anchor_index_match",
+    "kmu_anchor_index_occupancy", "kmu_anchor_index_match", "kmu_components", "kmu_components_knn",
 ]
+
+
+# what Context.components / components_knn return: label [n] (the smallest node of every node's component), cluster [n] (dense
+# ids in the order of the smallest member), size [n_components], members [n] (nodes by (cluster, node)) and n_components; a
+# field that was not asked for is None
+Components = collections.namedtuple("Components", "label cluster size members n_components")
+COMPONENTS_WANT = ("cluster", "size", "members")
 
 
 class KmuError(RuntimeError):
@@ -127,6 +135,9 @@ def load():
     L.kmu_anchor_index_info.argtypes = [vp, C.POINTER(A.AnchorIndexInfo)]
     L.kmu_anchor_index_occupancy.argtypes = [vp, vp, C.c_uint32, C.c_int]
     L.kmu_anchor_index_match.argtypes = [vp, vp, C.c_uint32, vp, C.c_uint32, C.c_uint32, C.c_int, vp, vp, C.c_uint64, u64p]
+    u32p = C.POINTER(C.c_uint32)
+    L.kmu_components.argtypes = [vp, C.c_uint32, vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, vp, vp, vp, vp, u32p]
+    L.kmu_components_knn.argtypes = [vp, C.c_uint32, vp, vp, C.c_uint32, C.c_uint32, C.c_int, vp, vp, vp, vp, u32p]
     L.kmu_set_hll_params.argtypes = [vp, C.POINTER(A.HllParams)]
     L.kmu_kmer_hashes_compact.argtypes = [vp, C.POINTER(A.HashParams), vp, vp, vp, C.c_uint32, vp, C.c_uint64, u64p]
     L.kmu_sketch_partial_words.argtypes = [C.POINTER(A.SketchParams)]
@@ -819,6 +830,61 @@ class Context:
         if n:
             self._check(self.L.kmu_anchor_overlaps(*args, _ptr(out)[0], n, C.byref(total)))
         return out[:n]
+
+    def _components(self, call, like, n_nodes, want, count):
+        """the outputs of kmu_components / kmu_components_knn allocated where `like` lives, call(*output pointers) run on them,
+        and the named tuple"""
+        unknown = [w for w in want if w not in COMPONENTS_WANT]
+        if unknown:
+            raise ValueError("want holds %r: the optional outputs are %r" % (unknown, COMPONENTS_WANT))
+        n = int(n_nodes)
+        label = self._new_like(like, max(n, 1), np.uint32, "int32")
+        cluster, size, members = (self._new_like(like, max(n, 1), np.uint32, "int32") if w in want else None for w in COMPONENTS_WANT)
+        total = C.c_uint32(0)
+        self._check(call(_ptr(label)[0], _ptr(cluster)[0], _ptr(size)[0], _ptr(members)[0], C.byref(total) if count else None))
+        n_comp = int(total.value) if count else None
+        return Components(label[:n], cluster[:n] if cluster is not None else None,
+                          size[:n_comp if count else n] if size is not None else None, members[:n] if members is not None else None, n_comp)
+
+    def components(self, edges, n_nodes, weight_at=0, min_weight=0, want=COMPONENTS_WANT, count=True):
+        """kmu_components: connected components of the undirected graph over nodes 0 .. n_nodes - 1 whose edges are the rows of
+        `edges` -- a [n, stride] uint32 / int32 array (words 0 and 1 are the ends), or a structured A.OVERLAP_DTYPE array (stride
+        8).  weight_at = 0: every edge counts; otherwise an edge counts iff its word weight_at is >= min_weight (4: the score of
+        an overlap record, 5: its votes).  Self loops, edges that do not count and edges with an end >= n_nodes are skipped.
+        Returns Components(label, cluster, size[:n_components], members, n_components); `want` names the optional outputs to
+        compute ("cluster", "size", "members"), the others are None.  count=False leaves n_components None and `size` whole
+        (n_nodes entries, 0 behind the last cluster): nothing crosses to the host, and an async_device context does not wait.
+        numpy in gives numpy (uint32) out; torch cuda tensors stay on the device (int32 tensors holding the same bits)."""
+        if not _is_torch(edges):
+            edges = np.ascontiguousarray(edges)
+            if edges.dtype.names is not None:
+                if edges.dtype != np.dtype(A.OVERLAP_DTYPE):
+                    raise ValueError("a structured edge array must be of A.OVERLAP_DTYPE")
+                edges = edges.reshape(-1).view(np.uint32).reshape(-1, 8)
+        if edges.ndim != 2 or edges.dtype.itemsize != 4 or str(edges.dtype).replace("torch.", "") not in ("uint32", "int32"):
+            raise ValueError("edges must be a [n, stride] array of uint32 / int32 words")
+        n_edges, stride = int(edges.shape[0]), int(edges.shape[1])
+        mem = self._mem(edges)
+        none = self._new_like(edges, 2, np.uint32, "int32")  # an empty array has no address worth passing
+        pe = _ptr(edges)[0] if n_edges else _ptr(none)[0]
+
+        def call(*outs):
+            return self.L.kmu_components(self.h, int(n_nodes), pe, n_edges, stride, int(weight_at), int(min_weight), mem, *outs)
+        return self._components(call, edges, n_nodes, want, count)
+
+    def components_knn(self, idx, eq, min_eq=0, want=COMPONENTS_WANT, count=True):
+        """kmu_components_knn: the components of the neighbour lists of a sig_knn self-join (idx [n, k], eq [n, k] or None): node i
+        is joined to idx[i, j] iff eq[i, j] >= min_eq; KNN_NONE entries join nothing.  Returns what `components` returns."""
+        n, k = int(idx.shape[0]), int(idx.shape[1])
+        mem = self._mem(idx, eq)
+        if eq is not None and tuple(eq.shape) != (n, k):
+            raise ValueError("idx and eq differ in shape")
+        none = self._new_like(idx, 2, np.uint32, "int32")
+        pi = _ptr(idx)[0] if n * k else _ptr(none)[0]
+
+        def call(*outs):
+            return self.L.kmu_components_knn(self.h, n, pi, _ptr(eq)[0], k, int(min_eq), mem, *outs)
+        return self._components(call, idx, n, want, count)
 
     def anchor_index(self, hashes_db, n_keys=1, group_db=None):
         """kmu_anchor_index_create: the database side of anchor_match as an object that stays on the device (AnchorIndex)"""

@@ -13,6 +13,8 @@ A Rust closure `fhash` cannot cross the FFI: pass one of the FHASH_* modes (the 
 use, include/kmu.h `kmu_fhash`).  Sequences are given as a list of `bytes` (ASCII), or as (bases, offsets) arrays
 (numpy on the host, torch tensors on the device).  Errors surface as KmuError where the reference panics.
 """
+import math
+
 import numpy as np
 
 from . import _abi as A
@@ -317,6 +319,21 @@ def nearest_neighbours(sig_q, sig_db, k, group_q=None, group_db=None, ctx=None):
     if isinstance(eq, np.ndarray):
         return idx, (np.float32(m) - eq.astype(np.float32)) / np.float32(m)
     return idx, (m - (eq.int() & 0xFFFF).float()) / m
+
+
+def neighbour_clusters(idx, eq, m, threshold, ctx=None, want=("cluster", "size", "members")):
+    """Dereplication from neighbour lists: the connected components of the graph that joins row i to idx[i, j] whenever their
+    identity eq[i, j] / m is at least `threshold` (kmu_components_knn with min_eq = ceil(threshold * m)).  idx, eq: what
+    ctx.sig_knn returns for a self-join (numpy, or torch tensors on the device, where they stay); m: the sketch size.  Returns
+    lib.Components(label, cluster, size, members, n_components)."""
+    ctx = ctx or default_context()
+    return ctx.components_knn(idx, eq, min_eq_for_identity(threshold, m), want=want)
+
+
+def min_eq_for_identity(threshold, m):
+    """the smallest number of equal slots out of m whose fraction reaches `threshold`: ceil(threshold * m), computed so that a
+    product like 0.9 * 10 = 9.000000000000002 does not round up to 10"""
+    return max(int(math.ceil(float(threshold) * int(m) - 1e-9)), 0)
 
 
 def block_nearest_neighbours(rows, numseq, k, ctx=None):
