@@ -1,6 +1,6 @@
 // kmu_count_part.hip -- the host side of the radix-partitioned build of the count table (the throughput path of
 // kmu_count_add_reads / kmu_sketch_count): big batches never touch the table with atomics, HBM sees only streams.  The kernels
-// are in kmu_count_part_kernels.hip (declared in kmu_count_part_kernels.h), the arithmetic of the plans in kmu_count_plan.hpp.
+// are in kmu_count_part_{level1,array,build}.hip (declared in kmu_count_part_kernels.h), the arithmetic of the plans in kmu_count_plan.hpp.
 // Every stage has ONE host function here and the routes are made of them: the SINGLE-PASS partition (default for big batches:
 // no histogram passes; seg_buffers, a level 1, seg_tails, seg_level2_build) and, where its spill list fills up, the EXACT levels
 // (reads_census, reads_scatter_exact, arr_level_exact; also one-level tables, the owner grouping of a distributed add with

@@ -1,7 +1,7 @@
 // kmu_count_part_kernels.h -- what the host side of the partitioned build (kmu_count_part.hip: routes, buffers, launches) needs of
-// its kernels (kmu_count_part_kernels.hip): their plan blocks, the constants and byte functions their launches and LDS budgets
-// are made of, and their declarations (the template kernels are instantiated in kmu_count_part_kernels.hip for exactly the
-// forms listed here).
+// its kernels (one file per stage: kmu_count_part_level1.hip, kmu_count_part_array.hip, kmu_count_part_build.hip): their plan blocks,
+// the constants and byte functions their launches and LDS budgets are made of, and their declarations (every kernel file instantiates
+// the template kernels it defines for exactly the forms listed here).
 #pragma once
 
 #include "kmu_count_table.h"
@@ -50,40 +50,48 @@ static constexpr int BUILD_PRE = 6;
 // region in LDS: 32 + 6 KiB per workgroup, four workgroups per CU as before)
 static constexpr uint32_t BUILD_POOL = 96, BUILD_PASSES = 3; // batched probes of an item before it goes to the pool (1 / 2 / 3: 21.1 / 18.8 / 18.4 ms)
 
-// ---- the kernels (definitions and comments: kmu_count_part_kernels.hip) ---------------------------------------------------------
-__global__ void k_part_hist1(const uint8_t *bases, const uint64_t *offsets, uint32_t n_seq, int k, PartPlan pl, uint32_t *hist1, uint32_t *err,
-                             SampleArgs sa);
-__global__ void k_sample_distinct(const uint64_t *list, uint32_t n, uint64_t *table, uint32_t mask, uint32_t *n_distinct);
-__global__ void k_part_scan1a(const uint32_t *hist1, PartPlan pl, uint64_t *offs1, uint64_t *tot1);
-__global__ void k_part_scan1b(const uint64_t *tot1, PartPlan pl, uint64_t *binstart1);
-__global__ void k_part_scatter1_exact(const uint8_t *bases, const uint64_t *offsets, uint32_t n_seq, int k, PartPlan pl, const uint64_t *offs1,
-                                      const uint64_t *binstart1, uint64_t *out);
-__global__ void k_part_scatter1(const uint8_t *bases, const uint64_t *offsets, uint32_t n_seq, int k, PartPlan pl, uint64_t *out, SegPlan1 seg);
+// ---- the kernels (definitions and comments: kmu_count_part_level1.hip, kmu_count_part_array.hip, kmu_count_part_build.hip) -----------
+// (every declaration carries the launch bounds of its definition: the `extern template` lines below instantiate the declaration they
+//  see, and a bound that only the definition has is then lost -- k_part_build_q's four workgroups per CU rest on its bound)
+// kmu_count_part_level1.hip
+__global__ void __launch_bounds__(256) k_part_hist1(const uint8_t *bases, const uint64_t *offsets, uint32_t n_seq, int k, PartPlan pl, uint32_t *hist1,
+                                                    uint32_t *err, SampleArgs sa);
+__global__ void __launch_bounds__(256) k_sample_distinct(const uint64_t *list, uint32_t n, uint64_t *table, uint32_t mask, uint32_t *n_distinct);
+__global__ void __launch_bounds__(256) k_part_scan1a(const uint32_t *hist1, PartPlan pl, uint64_t *offs1, uint64_t *tot1);
+__global__ void __launch_bounds__(256) k_part_scan1b(const uint64_t *tot1, PartPlan pl, uint64_t *binstart1);
+__global__ void __launch_bounds__(SCATTER_THREADS) k_part_scatter1_exact(const uint8_t *bases, const uint64_t *offsets, uint32_t n_seq, int k, PartPlan pl,
+                                                                         const uint64_t *offs1, const uint64_t *binstart1, uint64_t *out);
+__global__ void __launch_bounds__(SCATTER_THREADS) k_part_scatter1(const uint8_t *bases, const uint64_t *offsets, uint32_t n_seq, int k, PartPlan pl,
+                                                                   uint64_t *out, SegPlan1 seg);
+// kmu_count_part_array.hip
 template <int IT>
-__global__ void k_arr_hist(const uint64_t *in, const uint64_t *bounds, ArrPlan pl, uint32_t *hist);
-__global__ void k_arr_scan_a(const uint32_t *hist, ArrPlan pl, uint32_t T, uint64_t *offs_rel, uint64_t *tot);
-__global__ void k_arr_scan_b(const uint64_t *tot, const uint64_t *bounds, ArrPlan pl, uint64_t *outbounds);
+__global__ void __launch_bounds__(256) k_arr_hist(const uint64_t *in, const uint64_t *bounds, ArrPlan pl, uint32_t *hist);
+__global__ void __launch_bounds__(256) k_arr_scan_a(const uint32_t *hist, ArrPlan pl, uint32_t T, uint64_t *offs_rel, uint64_t *tot);
+__global__ void __launch_bounds__(256) k_arr_scan_b(const uint64_t *tot, const uint64_t *bounds, ArrPlan pl, uint64_t *outbounds);
 template <int IT>
-__global__ void k_arr_scatter_exact(const uint64_t *in, const uint64_t *bounds, ArrPlan pl, const uint64_t *offs_rel, const uint64_t *outbounds,
-                                    uint64_t *out);
+__global__ void __launch_bounds__(SCATTER_THREADS) k_arr_scatter_exact(const uint64_t *in, const uint64_t *bounds, ArrPlan pl, const uint64_t *offs_rel,
+                                                                       const uint64_t *outbounds, uint64_t *out);
 template <int IT, bool LEAF6>
-__global__ void k_arr_scatter_seg(const uint64_t *in, const uint64_t *bounds, ArrPlan pl, uint64_t *out, uint64_t seg_cap, uint32_t *seg_ovf,
-                                  uint32_t *leafcnt, const uint32_t *lox);
-__global__ void k_smer_scatter1(const uint32_t *recs, uint64_t n_rec, int k, ArrPlan pl, uint64_t *out, uint64_t seg_cap, uint32_t *seg_ovf,
-                                uint32_t *cursors);
-__global__ void k_spill_header(uint32_t *ovf, uint32_t cap, uint64_t *list);
-__global__ void k_seg_tails(const uint32_t *cursor, uint32_t n_streams, uint32_t cap, uint64_t *out);
-__global__ void k_count_add_spill(const uint64_t *items, const uint32_t *ovf, CountTable t, uint32_t *err);
-__global__ void k_fill_linear(uint64_t *out, uint64_t n, uint64_t stride);
+__global__ void __launch_bounds__(SCATTER_THREADS) k_arr_scatter_seg(const uint64_t *in, const uint64_t *bounds, ArrPlan pl, uint64_t *out, uint64_t seg_cap,
+                                                                     uint32_t *seg_ovf, uint32_t *leafcnt, const uint32_t *lox);
+__global__ void __launch_bounds__(SCATTER_THREADS) k_smer_scatter1(const uint32_t *recs, uint64_t n_rec, int k, ArrPlan pl, uint64_t *out, uint64_t seg_cap,
+                                                                   uint32_t *seg_ovf, uint32_t *cursors);
+__global__ void __launch_bounds__(64) k_spill_header(uint32_t *ovf, uint32_t cap, uint64_t *list);
+__global__ void __launch_bounds__(256) k_seg_tails(const uint32_t *cursor, uint32_t n_streams, uint32_t cap, uint64_t *out);
+__global__ void __launch_bounds__(256) k_fill_linear(uint64_t *out, uint64_t n, uint64_t stride);
+// kmu_count_part_build.hip
 template <int IT, bool LEAF6>
-__global__ void k_part_build_q(const uint64_t *__restrict__ items, const uint64_t *__restrict__ leafstart, uint32_t n_regions, CountTable t,
-                               int in_mode, uint32_t *err, uint64_t leaf_stride, const uint32_t *__restrict__ leafcnt);
+__global__ void __launch_bounds__(BUILD_THREADS, 8) k_part_build_q(const uint64_t *__restrict__ items, const uint64_t *__restrict__ leafstart,
+                                                                   uint32_t n_regions, CountTable t, int in_mode, uint32_t *err, uint64_t leaf_stride,
+                                                                   const uint32_t *__restrict__ leafcnt);
 template <int IT>
-__global__ void k_part_build(const uint64_t *__restrict__ items, const uint64_t *__restrict__ leafstart, uint32_t n_regions, CountTable t,
-                             int in_mode, uint32_t *err, uint64_t leaf_stride, const uint32_t *__restrict__ leafcnt);
+__global__ void __launch_bounds__(BUILD_THREADS) k_part_build(const uint64_t *__restrict__ items, const uint64_t *__restrict__ leafstart, uint32_t n_regions,
+                                                              CountTable t, int in_mode, uint32_t *err, uint64_t leaf_stride,
+                                                              const uint32_t *__restrict__ leafcnt);
+__global__ void __launch_bounds__(256) k_count_add_spill(const uint64_t *items, const uint32_t *ovf, CountTable t, uint32_t *err);
 
-// the forms of the template kernels the host launches: instantiated in kmu_count_part_kernels.hip, declared for everybody else
-#define KMU_COUNT_PART_KERNEL_FORMS(X)                                                                                               \
+// the forms of the template kernels the host launches, by the file that defines and instantiates them; declared for everybody
+#define KMU_COUNT_PART_ARRAY_FORMS(X)                                                                                                \
     X(k_arr_hist<IT_HASH>(const uint64_t *, const uint64_t *, ArrPlan, uint32_t *))                                                  \
     X(k_arr_hist<IT_KEY>(const uint64_t *, const uint64_t *, ArrPlan, uint32_t *))                                                   \
     X(k_arr_scatter_exact<IT_HASH>(const uint64_t *, const uint64_t *, ArrPlan, const uint64_t *, const uint64_t *, uint64_t *))         \
@@ -91,16 +99,16 @@ __global__ void k_part_build(const uint64_t *__restrict__ items, const uint64_t 
     X(k_arr_scatter_exact<IT_KEY_TO_HASH>(const uint64_t *, const uint64_t *, ArrPlan, const uint64_t *, const uint64_t *, uint64_t *))  \
     X(k_arr_scatter_seg<IT_HASH, false>(const uint64_t *, const uint64_t *, ArrPlan, uint64_t *, uint64_t, uint32_t *, uint32_t *, const uint32_t *))        \
     X(k_arr_scatter_seg<IT_HASH, true>(const uint64_t *, const uint64_t *, ArrPlan, uint64_t *, uint64_t, uint32_t *, uint32_t *, const uint32_t *))         \
-    X(k_arr_scatter_seg<IT_KEY_TO_HASH, false>(const uint64_t *, const uint64_t *, ArrPlan, uint64_t *, uint64_t, uint32_t *, uint32_t *, const uint32_t *)) \
+    X(k_arr_scatter_seg<IT_KEY_TO_HASH, false>(const uint64_t *, const uint64_t *, ArrPlan, uint64_t *, uint64_t, uint32_t *, uint32_t *, const uint32_t *))
+#define KMU_COUNT_PART_BUILD_FORMS(X)                                                                                                \
     X(k_part_build_q<IT_HASH, false>(const uint64_t *__restrict__, const uint64_t *__restrict__, uint32_t, CountTable, int, uint32_t *, uint64_t, const uint32_t *__restrict__)) \
     X(k_part_build_q<IT_HASH, true>(const uint64_t *__restrict__, const uint64_t *__restrict__, uint32_t, CountTable, int, uint32_t *, uint64_t, const uint32_t *__restrict__))  \
     X(k_part_build_q<IT_KEY, false>(const uint64_t *__restrict__, const uint64_t *__restrict__, uint32_t, CountTable, int, uint32_t *, uint64_t, const uint32_t *__restrict__))  \
     X(k_part_build<IT_HASH>(const uint64_t *__restrict__, const uint64_t *__restrict__, uint32_t, CountTable, int, uint32_t *, uint64_t, const uint32_t *__restrict__))           \
     X(k_part_build<IT_KEY>(const uint64_t *__restrict__, const uint64_t *__restrict__, uint32_t, CountTable, int, uint32_t *, uint64_t, const uint32_t *__restrict__))
-#ifndef KMU_COUNT_PART_KERNELS_TU
+#define KMU_COUNT_PART_KERNEL_FORMS(X) KMU_COUNT_PART_ARRAY_FORMS(X) KMU_COUNT_PART_BUILD_FORMS(X)
 #define KMU_X_EXTERN(...) extern template __global__ void __VA_ARGS__;
 KMU_COUNT_PART_KERNEL_FORMS(KMU_X_EXTERN)
 #undef KMU_X_EXTERN
-#endif
 
 } // namespace kmu

@@ -1,6 +1,6 @@
 // kmu_count_table.h -- the count table of libkmu: where a canonical k-mer lives, what a slot holds, direct insertion and look-up.
-// Shared by the translation units of the counter (kmu_count.hip: the table API; kmu_count_part.hip and kmu_count_part_kernels.hip:
-// the partitioned build, host side and kernels; kmu_count_dist.hip: the distributed counter).
+// Shared by the translation units of the counter (kmu_count.hip: the table API; kmu_count_part.hip and
+// kmu_count_part_{level1,array,build}.hip: the partitioned build, host side and kernels; kmu_count_dist.hip: the distributed counter).
 //
 // Reference (src/base/kmercount.rs:241-277): a cuckoo filter holds k-mers seen once, a counting Bloom filter the counts >= 2;
 // both are randomised per process, so the observable contract is "exact multiplicity of the canonical k-mer, reported

@@ -1,8 +1,10 @@
 // kmu_flat.h -- the reads of a batch as ONE flat stream of bases (device code): which read holds a given base, and the wave step
-// that every kernel walking the stream is written on (flat_step_visit_words; flat_wave_steps of kmu_count_plan.hpp counts the steps).
+// that every kernel walking the stream is written on (flat_step_visit_words; flat_wave_steps of kmu_count_plan.hpp counts the steps),
+// with its prefetching halves (flat_step_fetch / flat_step_words) and the two callbacks that collect a lane's k-mers as tile items.
 #pragma once
 
 #include "kmu_count_plan.hpp"
+#include "kmu_count_table.h" // CKEY_EMPTY, the "no k-mer" mark of flat_step_items
 #include "kmu_device.h"
 
 namespace kmu {
@@ -111,6 +113,78 @@ template <typename F>
 __device__ __forceinline__ uint32_t flat_step_canon(const uint8_t *bases, const uint64_t *offsets, uint32_t n_seq,
                                                     uint64_t total, uint64_t start, int k, uint64_t st, uint32_t &r_hint, F &&f) {
     return flat_step_visit<true>(bases, offsets, n_seq, total, start, k, st, r_hint, [&](int, uint64_t canon, uint32_t) { f(canon); });
+}
+
+// flat_step_load in two halves, for prefetching: flat_step_fetch requests the two aligned 16-byte chunks (this lane's word, the
+// halo word of lane & 1) and the lane's 16 "no k-mer" bits (flat_novalid, kmu_smer.hpp), and nothing looks at them until
+// flat_step_words turns them into code words one tile later -- the requests are UNCONDITIONAL loads from clamped addresses
+// (needs total >= 16), so that their number in flight is a constant for the compiler's s_waitcnt placement (a load under a
+// branch makes it wait for everything at the first use of anything).  All vector-memory waits of the scatter loop that uses them
+// (k_part_scatter1) are explicit waits for vmcnt(0): once before the loop, once per tile just before the write-out, when the requests
+// of the next tile have had the whole tile sort to arrive and the stores of the last tile are long gone.
+struct FlatRaw {
+    uint4 c0, cx;
+    uint32_t nv;
+};
+__device__ __forceinline__ void flat_step_fetch(const uint8_t *bases, uint64_t total, uint64_t st, FlatRaw &r, const uint16_t *novalid, uint64_t last_step) {
+    r.c0 = make_uint4(0u, 0u, 0u, 0u);
+    r.cx = r.c0;
+    r.nv = novalid[(st < last_step ? st : last_step) * 64 + (uint64_t) lane_id()];
+    if (total < 16) return; // (wave-uniform; flat_step_words then reads the ragged chunk itself)
+    const uint64_t lastc = (total - 16) & ~15ull;
+    const uint64_t a0 = (st * 64 + (uint64_t) lane_id()) * 16, ax = (st * 64 + 64 + (uint64_t) (lane_id() & 1)) * 16;
+    r.c0 = *reinterpret_cast<const uint4 *>(bases + (a0 < lastc ? a0 : lastc));
+    r.cx = *reinterpret_cast<const uint4 *>(bases + (ax < lastc ? ax : lastc));
+}
+__device__ __forceinline__ void flat_step_words(const uint8_t *bases, uint64_t total, uint64_t st, bool active, const FlatRaw &r,
+                                                uint32_t &w0, uint32_t &ex, uint32_t &bad_acc) {
+    w0 = 0;
+    ex = 0;
+    if (!active) return; // wave-uniform
+    const uint64_t i0 = st * 64 + (uint64_t) lane_id(), ix = st * 64 + 64 + (uint64_t) (lane_id() & 1);
+    uint32_t bad = 0, bad2 = 0;
+    if (__all(ix * 16 + 16 <= total)) { // (every chunk of the step whole: all but the last step of the stream)
+        w0 = pack16_ascii(r.c0, bad);
+        ex = pack16_ascii(r.cx, bad2);
+    } else {
+        SeqView s;
+        s.base = bases; s.begin = 0; s.len = total; s.total = total; s.packed = 0;
+        w0 = load_code_word(s, i0, bad);
+        ex = load_code_word(s, ix, bad2);
+    }
+    bad_acc |= bad; // (every word is some step's own word: the halo words need no second look)
+}
+
+// up to 16 canonical k-mers of this lane for wave step `st` (CKEY_EMPTY where a k-mer would straddle a read end); the exact levels
+__device__ __forceinline__ void flat_step_items(const uint64_t *offsets, uint32_t n_seq, uint64_t total, uint64_t start, int k,
+                                                uint64_t st, bool active, uint32_t w0, uint32_t ex, uint32_t &r_hint, uint64_t (&it)[16]) {
+#pragma unroll
+    for (int j = 0; j < 16; j++) it[j] = CKEY_EMPTY;
+    if (!active) return; // wave-uniform
+    // (the step keeps the reverse complement per k-mer: the exact levels' kernel has no registers for the window's)
+    flat_step_visit_words<true>(offsets, n_seq, total, start, k, st, w0, ex, r_hint, [&](int j, uint64_t canon, uint32_t) { it[j] = canon; });
+}
+
+// the same from the lane's "no k-mer" bits: no read offsets, no search, no dependent look-up; a wave whose lanes are all-or-nothing
+// (long reads: nearly every wave) skips the per-k-mer tests
+__device__ __forceinline__ void flat_step_items_nv(int k, bool active, uint32_t w0, uint32_t ex, uint32_t nv, uint64_t (&it)[16]) {
+#pragma unroll
+    for (int j = 0; j < 16; j++) it[j] = CKEY_EMPTY;
+    if (!active) return; // wave-uniform
+    uint32_t w1, w2;
+    flat_window(w0, ex, w1, w2);
+    const uint32_t V = ~nv & 0xFFFFu;
+    const StepWin sw = step_win(w0, w1, w2, k);
+    if (__all(V == 0xFFFFu || V == 0u)) {
+        if (V) {
+#pragma unroll
+            for (int j = 0; j < 16; j++) it[j] = step_canonical(sw, j);
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < 16; j++)
+            if ((V >> j) & 1u) it[j] = step_canonical(sw, j);
+    }
 }
 
 } // namespace kmu

@@ -104,4 +104,12 @@ KMU_HD uint64_t smer_rec_kmer(const SmerRec &r, int k, uint32_t j) {
     return v >> (64 - 2 * k);
 }
 
+// ---- up to eight owners (one node's GPUs) counted in the eight 8-bit fields of a register (the census of kmu_smer.hip, k_part_hist1):
+// the fields spread to 16-bit fields before a wave sums them -- word i holds owner (i >> 1) + 4 (i & 1) in its low half and that + 2
+// in its high half
+KMU_HD void spread8(uint64_t p, uint32_t (&w)[4]) {
+    const uint64_t ev = p & 0x00FF00FF00FF00FFull, od = (p >> 8) & 0x00FF00FF00FF00FFull;
+    w[0] = (uint32_t) ev; w[1] = (uint32_t) (ev >> 32); w[2] = (uint32_t) od; w[3] = (uint32_t) (od >> 32);
+}
+
 } // namespace kmu

@@ -135,7 +135,7 @@ __global__ void __launch_bounds__(256) k_smer_novalid(const uint64_t *offsets, u
 }
 
 // what a wave step needs from memory, requested a step ahead: the lane's 16 bases and its 16 "no k-mer" bits.  Unconditional
-// loads from clamped addresses: their number in flight is a constant for the compiler's waits (see flat_step_fetch, kmu_count_part_kernels.hip).
+// loads from clamped addresses: their number in flight is a constant for the compiler's waits (see flat_step_fetch, kmu_flat.h).
 struct SmerRaw {
     uint4 c;
     uint32_t nv;
@@ -203,12 +203,7 @@ __device__ __forceinline__ void smer_step(const uint8_t *bases, uint64_t total, 
     if (lane >= (uint32_t) SMER_STEP_WORDS) a.bad = 0; // (a halo word is some other step's own word)
 }
 
-// the fields of two packed per-owner counters (eight 8-bit fields each: owners 0 .. 7) spread to 16-bit fields:
-// word i holds owner (i >> 1) + 4 (i & 1) in its low half and that + 2 in its high half
-__device__ __forceinline__ void spread8(uint64_t p, uint32_t (&w)[4]) {
-    const uint64_t ev = p & 0x00FF00FF00FF00FFull, od = (p >> 8) & 0x00FF00FF00FF00FFull;
-    w[0] = (uint32_t) ev; w[1] = (uint32_t) (ev >> 32); w[2] = (uint32_t) od; w[3] = (uint32_t) (od >> 32);
-}
+// (spread8: kmu_smer.h)
 __device__ __forceinline__ uint32_t field16(const uint32_t (&w)[4], uint32_t o) { // owner o's field of spread words
     const uint32_t i = ((o & 1u) << 1) | ((o >> 2) & 1u);
     const uint32_t x = i == 0u ? w[0] : i == 1u ? w[1] : i == 2u ? w[2] : w[3];
