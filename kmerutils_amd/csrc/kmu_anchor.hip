@@ -214,24 +214,13 @@ extern "C" int kmu_read_anchors(kmu_ctx *ctx, const kmu_sketch_params *p_in, con
         KMU_TRY(dev_buf(ctx, "in.anchorrows", ((size_t) n_seq + 1) * 8, &q));
         KMU_HIP(ctx, hipMemcpyAsync(q, anchor_row_offsets, ((size_t) n_seq + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
         a.row_off = (const uint64_t *) q;
-        KMU_TRY(dev_buf(ctx, "out.sig", rows * m * 8 + 64, &q));
-        a.hashes_out = (uint64_t *) q;
-        if (counts_out) {
-            KMU_TRY(dev_buf(ctx, "out.counts", rows * m * 4 + 64, &q));
-            a.counts_out = (uint32_t *) q;
-        }
-        if (n_out) {
-            KMU_TRY(dev_buf(ctx, "out.anchor_n", rows * 4 + 64, &q));
-            a.n_out = (uint32_t *) q;
-        }
+        KMU_TRY(dev_array(ctx, "out.sig", rows * m + 8, &a.hashes_out));
+        if (counts_out) KMU_TRY(dev_array(ctx, "out.counts", rows * m + 16, &a.counts_out));
+        if (n_out) KMU_TRY(dev_array(ctx, "out.anchor_n", rows + 16, &a.n_out));
     }
     KMU_TRY(get_err_word(ctx, &a.err));
-    {
-        const uint32_t grid = (uint32_t) std::min<uint64_t>(rows, (uint64_t) ctx->num_cus * 40);
-        KernelTimer t(ctx, "k_read_anchors");
-        hipLaunchKernelGGL(k_read_anchors, dim3(grid), dim3(64), 0, ctx->stream, a);
-    }
-    KMU_HIP(ctx, hipGetLastError());
+    const uint32_t grid = (uint32_t) std::min<uint64_t>(rows, (uint64_t) ctx->num_cus * 40);
+    KMU_TRY(launch(ctx, "k_read_anchors", k_read_anchors, dim3(grid), dim3(64), 0, a));
     if (p->mem == KMU_MEM_HOST) {
         KMU_HIP(ctx, hipMemcpyAsync(hashes_out, a.hashes_out, rows * m * 8, hipMemcpyDeviceToHost, ctx->stream));
         if (counts_out) KMU_HIP(ctx, hipMemcpyAsync(counts_out, a.counts_out, rows * m * 4, hipMemcpyDeviceToHost, ctx->stream));

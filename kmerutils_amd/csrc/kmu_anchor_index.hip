@@ -108,10 +108,6 @@ __global__ void __launch_bounds__(256) k_aix_occupancy(const uint32_t *ubeg, uin
         if (bins[i]) atomicAdd(&hist[i], (unsigned long long) bins[i]);
 }
 
-static uint32_t aix_grid(kmu_ctx *ctx, uint64_t n) {
-    return (uint32_t) std::max<uint64_t>(1, std::min<uint64_t>((n + 255) / 256, (uint64_t) ctx->num_cus * 8));
-}
-
 static int aix_alloc(kmu_anchor_index *ix, void **p, size_t bytes) {
     KMU_HIP(ix->ctx, hipMalloc(p, bytes));
     ix->device_bytes += bytes;
@@ -120,41 +116,28 @@ static int aix_alloc(kmu_anchor_index *ix, void **p, size_t bytes) {
 
 int anchor_db_build(kmu_ctx *ctx, AnchorDb *db, const uint32_t **n_real) {
     const uint32_t n = db->ndb * db->n_keys; // entries, padding included: the host's upper bound of both counts
-    void *k0, *v0, *k1, *v1, *flags, *slot, *stat, *ukeys, *ubeg;
-    KMU_TRY(dev_buf(ctx, "am.keys0", (size_t) n * 8, &k0));
-    KMU_TRY(dev_buf(ctx, "am.rows0", (size_t) n * 4, &v0));
-    KMU_TRY(dev_buf(ctx, "am.keys1", (size_t) n * 8, &k1));
-    KMU_TRY(dev_buf(ctx, "am.rows1", (size_t) n * 4, &v1));
-    KMU_TRY(dev_buf(ctx, "aix.flags", (size_t) n * 4, &flags));
-    KMU_TRY(dev_buf(ctx, "aix.slot", ((size_t) n + 1) * 8, &slot));
-    KMU_TRY(dev_buf(ctx, "aix.ukeys", (size_t) n * 8, &ukeys));
-    KMU_TRY(dev_buf(ctx, "aix.ubeg", ((size_t) n + 1) * 4, &ubeg));
+    uint32_t *ubeg, *flags, *v1, *v0;
+    uint64_t *ukeys, *slot, *k1, *k0;
+    void *stat;
+    KMU_TRY(dev_array(ctx, "am.keys0", (size_t) n, &k0));
+    KMU_TRY(dev_array(ctx, "am.rows0", (size_t) n, &v0));
+    KMU_TRY(dev_array(ctx, "am.keys1", (size_t) n, &k1));
+    KMU_TRY(dev_array(ctx, "am.rows1", (size_t) n, &v1));
+    KMU_TRY(dev_array(ctx, "aix.flags", (size_t) n, &flags));
+    KMU_TRY(dev_array(ctx, "aix.slot", (size_t) n + 1, &slot));
+    KMU_TRY(dev_array(ctx, "aix.ukeys", (size_t) n, &ukeys));
+    KMU_TRY(dev_array(ctx, "aix.ubeg", (size_t) n + 1, &ubeg));
     KMU_TRY(dev_buf(ctx, "aix.stat", 8, &stat)); // [0] real entries, [1] distinct keys
     KMU_HIP(ctx, hipMemsetAsync(stat, 0, 8, ctx->stream));
-    {
-        KernelTimer t(ctx, "k_anchor_entries");
-        hipLaunchKernelGGL(k_anchor_entries, dim3(aix_grid(ctx, n)), dim3(256), 0, ctx->stream, db->rows, db->m, db->n_keys, n,
-                           (uint64_t *) k0, (uint32_t *) v0);
-    }
-    KMU_HIP(ctx, hipGetLastError());
-    KMU_TRY(radix_sort_pairs(ctx, (uint64_t *) k0, (uint32_t *) v0, (uint64_t *) k1, (uint32_t *) v1, n));
-    {
-        KernelTimer t(ctx, "k_aix_heads");
-        hipLaunchKernelGGL(k_aix_heads, dim3(aix_grid(ctx, n)), dim3(256), 0, ctx->stream, (const uint64_t *) k0, n, (uint32_t *) flags,
-                           (uint32_t *) stat);
-    }
-    KMU_HIP(ctx, hipGetLastError());
-    KMU_TRY(device_scan_u32(ctx, (const uint32_t *) flags, n, (uint64_t *) slot));
-    {
-        KernelTimer t(ctx, "k_aix_directory");
-        hipLaunchKernelGGL(k_aix_directory, dim3(aix_grid(ctx, n)), dim3(256), 0, ctx->stream, (const uint64_t *) k0,
-                           (const uint32_t *) flags, (const uint64_t *) slot, n, (const uint32_t *) stat, (uint64_t *) ukeys,
-                           (uint32_t *) ubeg, (uint32_t *) stat + 1);
-    }
-    KMU_HIP(ctx, hipGetLastError());
-    db->srows = (const uint32_t *) v0;
-    db->ukeys = (const uint64_t *) ukeys;
-    db->ubeg = (const uint32_t *) ubeg;
+    KMU_TRY(launch(ctx, "k_anchor_entries", k_anchor_entries, dim3(grid_for(ctx, n, 256)), dim3(256), 0, db->rows, db->m, db->n_keys, n, k0, v0));
+    KMU_TRY(radix_sort_pairs(ctx, k0, v0, k1, v1, n));
+    KMU_TRY(launch(ctx, "k_aix_heads", k_aix_heads, dim3(grid_for(ctx, n, 256)), dim3(256), 0, k0, n, flags, (uint32_t *) stat));
+    KMU_TRY(device_scan_u32(ctx, flags, n, slot));
+    KMU_TRY(launch(ctx, "k_aix_directory", k_aix_directory, dim3(grid_for(ctx, n, 256)), dim3(256), 0, k0, flags, slot, n, (const uint32_t *) stat,
+                   ukeys, ubeg, (uint32_t *) stat + 1));
+    db->srows = v0;
+    db->ukeys = ukeys;
+    db->ubeg = ubeg;
     db->n_distinct = (const uint32_t *) stat + 1;
     if (n_real) *n_real = (const uint32_t *) stat;
     return KMU_OK;
@@ -200,12 +183,8 @@ static int aix_create(kmu_anchor_index *ix, const uint64_t *hashes_db, const uin
     void *d_max;
     KMU_TRY(dev_buf(ctx, "aix.max_occ", 4, &d_max));
     KMU_HIP(ctx, hipMemsetAsync(d_max, 0, 4, ctx->stream));
-    {
-        KernelTimer t(ctx, "k_aix_max_occ");
-        hipLaunchKernelGGL(k_aix_max_occ, dim3(aix_grid(ctx, n_distinct)), dim3(256), 0, ctx->stream, (const uint32_t *) ix->ubeg, n_distinct,
-                           (uint32_t *) d_max);
-    }
-    KMU_HIP(ctx, hipGetLastError());
+    KMU_TRY(launch(ctx, "k_aix_max_occ", k_aix_max_occ, dim3(grid_for(ctx, n_distinct, 256)), dim3(256), 0, (const uint32_t *) ix->ubeg, n_distinct,
+                   (uint32_t *) d_max));
     KMU_HIP(ctx, hipMemcpyAsync(&ix->max_occupancy, d_max, 4, hipMemcpyDeviceToHost, ctx->stream));
     // the caller's arrays are free from here on, in both modes
     KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -270,17 +249,11 @@ int kmu_anchor_index_occupancy(kmu_anchor_index *ix, uint64_t *hist_out, uint32_
     if (mem != KMU_MEM_HOST && mem != KMU_MEM_DEVICE) return fail(ctx, KMU_E_BAD_ARG, "bad mem %d", mem);
     KMU_HIP(ctx, hipSetDevice(ctx->device));
     uint64_t *d_h = hist_out;
-    if (mem == KMU_MEM_HOST) {
-        void *q;
-        KMU_TRY(dev_buf(ctx, "aix.hist", (size_t) n_bins * 8, &q));
-        d_h = (uint64_t *) q;
-    }
+    if (mem == KMU_MEM_HOST) KMU_TRY(dev_array(ctx, "aix.hist", (size_t) n_bins, &d_h));
     KMU_HIP(ctx, hipMemsetAsync(d_h, 0, (size_t) n_bins * 8, ctx->stream));
     if (ix->n_distinct) {
-        KernelTimer t(ctx, "k_aix_occupancy");
-        hipLaunchKernelGGL(k_aix_occupancy, dim3(aix_grid(ctx, ix->n_distinct)), dim3(256), 0, ctx->stream, (const uint32_t *) ix->ubeg,
-                           (uint32_t) ix->n_distinct, n_bins - 1, (unsigned long long *) d_h);
-        KMU_HIP(ctx, hipGetLastError());
+        KMU_TRY(launch(ctx, "k_aix_occupancy", k_aix_occupancy, dim3(grid_for(ctx, ix->n_distinct, 256)), dim3(256), 0, (const uint32_t *) ix->ubeg,
+                       (uint32_t) ix->n_distinct, n_bins - 1, (unsigned long long *) d_h));
     }
     if (mem == KMU_MEM_HOST) KMU_HIP(ctx, hipMemcpyAsync(hist_out, d_h, (size_t) n_bins * 8, hipMemcpyDeviceToHost, ctx->stream));
     return finish_call(ctx, mem);

@@ -130,20 +130,17 @@ template <bool WRITE> __global__ void __launch_bounds__(64) k_anchor_match(Match
 int anchor_match_run(kmu_ctx *ctx, MatchArgs &a, uint32_t nq, int mem, uint32_t *pairs_out, uint32_t *dist_out, uint64_t cap,
                      uint64_t *n_out) {
     // COUNT, offsets, total
-    void *counts, *offs;
-    KMU_TRY(dev_buf(ctx, "am.counts", (size_t) nq * 4, &counts));
-    KMU_TRY(dev_buf(ctx, "am.offs", ((size_t) nq + 1) * 8, &offs));
+    uint64_t *offs;
+    uint32_t *counts;
+    KMU_TRY(dev_array(ctx, "am.counts", (size_t) nq, &counts));
+    KMU_TRY(dev_array(ctx, "am.offs", (size_t) nq + 1, &offs));
     const uint32_t grid = (uint32_t) std::min<uint64_t>(nq, (uint64_t) ctx->num_cus * 32);
     a.nq = nq;
-    a.counts = (uint32_t *) counts;
-    {
-        KernelTimer t(ctx, "k_anchor_match_count");
-        hipLaunchKernelGGL(k_anchor_match<false>, dim3(grid), dim3(64), 0, ctx->stream, a);
-    }
-    KMU_HIP(ctx, hipGetLastError());
-    KMU_TRY(device_scan_u32(ctx, (const uint32_t *) counts, nq, (uint64_t *) offs));
+    a.counts = counts;
+    KMU_TRY(launch(ctx, "k_anchor_match_count", k_anchor_match<false>, dim3(grid), dim3(64), 0, a));
+    KMU_TRY(device_scan_u32(ctx, counts, nq, offs));
     uint64_t total = 0;
-    KMU_HIP(ctx, hipMemcpyAsync(&total, (const uint64_t *) offs + nq, 8, hipMemcpyDeviceToHost, ctx->stream));
+    KMU_HIP(ctx, hipMemcpyAsync(&total, offs + nq, 8, hipMemcpyDeviceToHost, ctx->stream));
     KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
     *n_out = total;
     if (!pairs_out || total == 0) return finish_call(ctx, mem);
@@ -153,7 +150,7 @@ int anchor_match_run(kmu_ctx *ctx, MatchArgs &a, uint32_t nq, int mem, uint32_t 
     }
 
     // WRITE
-    a.offs = (const uint64_t *) offs;
+    a.offs = offs;
     a.total = total;
     a.pairs = pairs_out;
     a.dist = dist_out;
@@ -166,11 +163,7 @@ int anchor_match_run(kmu_ctx *ctx, MatchArgs &a, uint32_t nq, int mem, uint32_t 
             a.dist = (uint32_t *) d;
         }
     }
-    {
-        KernelTimer t(ctx, "k_anchor_match_write");
-        hipLaunchKernelGGL(k_anchor_match<true>, dim3(grid), dim3(64), 0, ctx->stream, a);
-    }
-    KMU_HIP(ctx, hipGetLastError());
+    KMU_TRY(launch(ctx, "k_anchor_match_write", k_anchor_match<true>, dim3(grid), dim3(64), 0, a));
     if (mem == KMU_MEM_HOST) {
         KMU_HIP(ctx, hipMemcpyAsync(pairs_out, a.pairs, total * 8, hipMemcpyDeviceToHost, ctx->stream));
         if (dist_out) KMU_HIP(ctx, hipMemcpyAsync(dist_out, a.dist, total * 12, hipMemcpyDeviceToHost, ctx->stream));

@@ -252,14 +252,6 @@ template <bool WRITE> __global__ void __launch_bounds__(64) k_ovl_best(OvlArgs a
     }
 }
 
-// the radix passes that can tell two read ids below n apart: one bit per byte of n - 1 (at least the lowest)
-static uint32_t ovl_id_passes(uint32_t n) {
-    uint32_t m = 1, top = n - 1;
-    for (uint32_t b = 1; b < 4; b++)
-        if (top >> (8 * b)) m |= 1u << b;
-    return m;
-}
-
 } // namespace kmu
 
 using namespace kmu;
@@ -310,112 +302,66 @@ extern "C" int kmu_anchor_overlaps(kmu_ctx *ctx, const uint32_t *pairs, const ui
     a.upper = (flags & KMU_OVL_UPPER) ? 1u : 0u;
     a.n_max = n_max;
 
-    void *info, *counts, *coff, *prim, *sa, *sb, *w, *k0v, *v0v, *k1v, *v1v, *rhead, *phead, *keep, *ridx, *pidx, *ooff, *rstart,
-        *pstart, *rsec, *rw, *rmin, *rmax;
-    KMU_TRY(dev_buf(ctx, "ovl.info", sizeof(OvlInfo), &info));
-    KMU_TRY(dev_buf(ctx, "ovl.counts", (size_t) n_tiles * 4, &counts));
-    KMU_TRY(dev_buf(ctx, "ovl.coff", ((size_t) n_tiles + 1) * 8, &coff));
-    KMU_TRY(dev_buf(ctx, "ovl.prim", (size_t) n_pairs * 8, &prim));
-    KMU_TRY(dev_buf(ctx, "ovl.sa", (size_t) n_pairs * 4, &sa));
-    KMU_TRY(dev_buf(ctx, "ovl.sb", (size_t) n_pairs * 4, &sb));
-    KMU_TRY(dev_buf(ctx, "ovl.w", (size_t) n_pairs * 4, &w));
-    KMU_TRY(dev_buf(ctx, "ovl.keys0", (size_t) n_max * 8, &k0v));
-    KMU_TRY(dev_buf(ctx, "ovl.vals0", (size_t) n_max * 4, &v0v));
-    KMU_TRY(dev_buf(ctx, "ovl.keys1", (size_t) n_max * 8, &k1v));
-    KMU_TRY(dev_buf(ctx, "ovl.vals1", (size_t) n_max * 4, &v1v));
-    KMU_TRY(dev_buf(ctx, "ovl.rhead", (size_t) n_max * 4, &rhead));
-    KMU_TRY(dev_buf(ctx, "ovl.phead", (size_t) n_max * 4, &phead));
-    KMU_TRY(dev_buf(ctx, "ovl.keep", (size_t) n_max * 4, &keep));
-    KMU_TRY(dev_buf(ctx, "ovl.ridx", ((size_t) n_max + 1) * 8, &ridx));
-    KMU_TRY(dev_buf(ctx, "ovl.pidx", ((size_t) n_max + 1) * 8, &pidx));
-    KMU_TRY(dev_buf(ctx, "ovl.ooff", ((size_t) n_max + 1) * 8, &ooff));
-    KMU_TRY(dev_buf(ctx, "ovl.rstart", ((size_t) n_max + 1) * 4, &rstart));
-    KMU_TRY(dev_buf(ctx, "ovl.pstart", ((size_t) n_max + 1) * 4, &pstart));
-    KMU_TRY(dev_buf(ctx, "ovl.rsec", (size_t) n_max * 8, &rsec));
-    KMU_TRY(dev_buf(ctx, "ovl.rw", (size_t) n_max * 8, &rw));
-    KMU_TRY(dev_buf(ctx, "ovl.rmin", (size_t) n_max * 4, &rmin));
-    KMU_TRY(dev_buf(ctx, "ovl.rmax", (size_t) n_max * 4, &rmax));
-    a.info = (OvlInfo *) info;
-    a.prim = (uint64_t *) prim;
-    a.sa = (uint32_t *) sa;
-    a.sb = (uint32_t *) sb;
-    a.w = (uint32_t *) w;
-    a.rhead = (uint32_t *) rhead;
-    a.phead = (uint32_t *) phead;
-    a.keep = (uint32_t *) keep;
-    a.ridx = (const uint64_t *) ridx;
-    a.pidx = (const uint64_t *) pidx;
-    a.ooff = (const uint64_t *) ooff;
-    a.rstart = (uint32_t *) rstart;
-    a.pstart = (uint32_t *) pstart;
-    a.rsec = (uint64_t *) rsec;
-    a.rw = (uint64_t *) rw;
-    a.rmin = (uint32_t *) rmin;
-    a.rmax = (uint32_t *) rmax;
-    uint64_t *k0 = (uint64_t *) k0v, *k1 = (uint64_t *) k1v;
-    uint32_t *v0 = (uint32_t *) v0v, *v1 = (uint32_t *) v1v;
+    uint32_t *counts, *v0, *v1;
+    uint64_t *coff, *k0, *k1, *ridx, *pidx, *ooff; // (the scans write what the kernels read through OvlArgs)
+    KMU_TRY(dev_array(ctx, "ovl.info", 1, &a.info));
+    KMU_TRY(dev_array(ctx, "ovl.counts", n_tiles, &counts));
+    KMU_TRY(dev_array(ctx, "ovl.coff", (size_t) n_tiles + 1, &coff));
+    KMU_TRY(dev_array(ctx, "ovl.prim", n_pairs, &a.prim));
+    KMU_TRY(dev_array(ctx, "ovl.sa", n_pairs, &a.sa));
+    KMU_TRY(dev_array(ctx, "ovl.sb", n_pairs, &a.sb));
+    KMU_TRY(dev_array(ctx, "ovl.w", n_pairs, &a.w));
+    KMU_TRY(dev_array(ctx, "ovl.keys0", n_max, &k0));
+    KMU_TRY(dev_array(ctx, "ovl.vals0", n_max, &v0));
+    KMU_TRY(dev_array(ctx, "ovl.keys1", n_max, &k1));
+    KMU_TRY(dev_array(ctx, "ovl.vals1", n_max, &v1));
+    KMU_TRY(dev_array(ctx, "ovl.rhead", n_max, &a.rhead));
+    KMU_TRY(dev_array(ctx, "ovl.phead", n_max, &a.phead));
+    KMU_TRY(dev_array(ctx, "ovl.keep", n_max, &a.keep));
+    KMU_TRY(dev_array(ctx, "ovl.ridx", (size_t) n_max + 1, &ridx));
+    KMU_TRY(dev_array(ctx, "ovl.pidx", (size_t) n_max + 1, &pidx));
+    KMU_TRY(dev_array(ctx, "ovl.ooff", (size_t) n_max + 1, &ooff));
+    KMU_TRY(dev_array(ctx, "ovl.rstart", (size_t) n_max + 1, &a.rstart));
+    KMU_TRY(dev_array(ctx, "ovl.pstart", (size_t) n_max + 1, &a.pstart));
+    KMU_TRY(dev_array(ctx, "ovl.rsec", n_max, &a.rsec));
+    KMU_TRY(dev_array(ctx, "ovl.rw", n_max, &a.rw));
+    KMU_TRY(dev_array(ctx, "ovl.rmin", n_max, &a.rmin));
+    KMU_TRY(dev_array(ctx, "ovl.rmax", n_max, &a.rmax));
+    a.ridx = ridx;
+    a.pidx = pidx;
+    a.ooff = ooff;
     const uint64_t *n_dev = &a.info->n;
 
     // entries
     if (a.upper) {
-        {
-            KernelTimer t(ctx, "k_ovl_keys_count");
-            hipLaunchKernelGGL(k_ovl_keys<false>, dim3(n_tiles), dim3(64), 0, ctx->stream, a, (uint32_t *) counts,
-                               (const uint64_t *) nullptr, n_tiles, k0, v0);
-        }
-        KMU_HIP(ctx, hipGetLastError());
-        KMU_TRY(device_scan_u32(ctx, (const uint32_t *) counts, n_tiles, (uint64_t *) coff));
+        KMU_TRY(launch(ctx, "k_ovl_keys_count", k_ovl_keys<false>, dim3(n_tiles), dim3(64), 0, a, counts, nullptr, n_tiles, k0, v0));
+        KMU_TRY(device_scan_u32(ctx, counts, n_tiles, coff));
     }
-    {
-        KernelTimer t(ctx, "k_ovl_keys_write");
-        hipLaunchKernelGGL(k_ovl_keys<true>, dim3(n_tiles), dim3(64), 0, ctx->stream, a, (uint32_t *) counts,
-                           a.upper ? (const uint64_t *) coff : (const uint64_t *) nullptr, n_tiles, k0, v0);
-    }
-    KMU_HIP(ctx, hipGetLastError());
+    KMU_TRY(launch(ctx, "k_ovl_keys_write", k_ovl_keys<true>, dim3(n_tiles), dim3(64), 0, a, counts, a.upper ? coff : nullptr, n_tiles, k0, v0));
 
     // by diagonal, then (stable) by read pair
-    const uint32_t flat = (uint32_t) std::min<uint64_t>((n_max + 255) / 256, (uint64_t) ctx->num_cus * 8);
+    const uint32_t flat = grid_for(ctx, n_max, 256);
     KMU_TRY(radix_sort_pairs_passes(ctx, k0, v0, k1, v1, n_max, strands == 2 ? 0x1Fu : 0x0Fu, n_dev));
-    {
-        KernelTimer t(ctx, "k_ovl_gather");
-        hipLaunchKernelGGL(k_ovl_gather, dim3(flat), dim3(256), 0, ctx->stream, a, (const uint32_t *) v0, k0);
-    }
-    KMU_HIP(ctx, hipGetLastError());
-    KMU_TRY(radix_sort_pairs_passes(ctx, k0, v0, k1, v1, n_max, ovl_id_passes(n_reads_db) | (ovl_id_passes(n_reads_q) << 4), n_dev));
+    KMU_TRY(launch(ctx, "k_ovl_gather", k_ovl_gather, dim3(flat), dim3(256), 0, a, v0, k0));
+    KMU_TRY(radix_sort_pairs_passes(ctx, k0, v0, k1, v1, n_max, radix_id_passes(n_reads_db) | (radix_id_passes(n_reads_q) << 4), n_dev));
     a.skeys = k0;
     a.svals = v0;
 
     // runs and read pairs
-    {
-        KernelTimer t(ctx, "k_ovl_heads");
-        hipLaunchKernelGGL(k_ovl_heads, dim3(flat), dim3(256), 0, ctx->stream, a);
-    }
-    KMU_HIP(ctx, hipGetLastError());
-    KMU_TRY(device_scan_u32(ctx, (const uint32_t *) rhead, n_max, (uint64_t *) ridx));
-    KMU_TRY(device_scan_u32(ctx, (const uint32_t *) phead, n_max, (uint64_t *) pidx));
-    {
-        KernelTimer t(ctx, "k_ovl_starts");
-        hipLaunchKernelGGL(k_ovl_starts, dim3(flat), dim3(256), 0, ctx->stream, a);
-    }
-    KMU_HIP(ctx, hipGetLastError());
-    const uint32_t waves = (uint32_t) std::min<uint64_t>(n_max, (uint64_t) ctx->num_cus * 32);
-    {
-        KernelTimer t(ctx, "k_ovl_runs");
-        hipLaunchKernelGGL(k_ovl_runs, dim3(waves), dim3(64), 0, ctx->stream, a);
-    }
-    KMU_HIP(ctx, hipGetLastError());
+    KMU_TRY(launch(ctx, "k_ovl_heads", k_ovl_heads, dim3(flat), dim3(256), 0, a));
+    KMU_TRY(device_scan_u32(ctx, a.rhead, n_max, ridx));
+    KMU_TRY(device_scan_u32(ctx, a.phead, n_max, pidx));
+    KMU_TRY(launch(ctx, "k_ovl_starts", k_ovl_starts, dim3(flat), dim3(256), 0, a));
+    const uint32_t waves = grid_for(ctx, n_max, 1, 32);
+    KMU_TRY(launch(ctx, "k_ovl_runs", k_ovl_runs, dim3(waves), dim3(64), 0, a));
 
     // COUNT, offsets, total
-    {
-        KernelTimer t(ctx, "k_ovl_best_count");
-        hipLaunchKernelGGL(k_ovl_best<false>, dim3(waves), dim3(64), 0, ctx->stream, a);
-    }
-    KMU_HIP(ctx, hipGetLastError());
-    KMU_TRY(device_scan_u32(ctx, (const uint32_t *) keep, n_max, (uint64_t *) ooff));
+    KMU_TRY(launch(ctx, "k_ovl_best_count", k_ovl_best<false>, dim3(waves), dim3(64), 0, a));
+    KMU_TRY(device_scan_u32(ctx, a.keep, n_max, ooff));
     uint64_t total = 0;
     OvlInfo h_info{};
-    KMU_HIP(ctx, hipMemcpyAsync(&total, (const uint64_t *) ooff + n_max, 8, hipMemcpyDeviceToHost, ctx->stream));
-    KMU_HIP(ctx, hipMemcpyAsync(&h_info, info, sizeof h_info, hipMemcpyDeviceToHost, ctx->stream));
+    KMU_HIP(ctx, hipMemcpyAsync(&total, ooff + n_max, 8, hipMemcpyDeviceToHost, ctx->stream));
+    KMU_HIP(ctx, hipMemcpyAsync(&h_info, a.info, sizeof h_info, hipMemcpyDeviceToHost, ctx->stream));
     KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
     if (h_info.bad) { // (device memory: the offsets were read there)
         (void) finish_call(ctx, mem);
@@ -431,16 +377,8 @@ extern "C" int kmu_anchor_overlaps(kmu_ctx *ctx, const uint32_t *pairs, const ui
     // WRITE
     a.total = total;
     a.out = out;
-    if (mem == KMU_MEM_HOST) {
-        void *d;
-        KMU_TRY(dev_buf(ctx, "ovl.out", total * sizeof(kmu_overlap), &d));
-        a.out = (kmu_overlap *) d;
-    }
-    {
-        KernelTimer t(ctx, "k_ovl_best_write");
-        hipLaunchKernelGGL(k_ovl_best<true>, dim3(waves), dim3(64), 0, ctx->stream, a);
-    }
-    KMU_HIP(ctx, hipGetLastError());
+    if (mem == KMU_MEM_HOST) KMU_TRY(dev_array(ctx, "ovl.out", total, &a.out));
+    KMU_TRY(launch(ctx, "k_ovl_best_write", k_ovl_best<true>, dim3(waves), dim3(64), 0, a));
     if (mem == KMU_MEM_HOST) KMU_HIP(ctx, hipMemcpyAsync(out, a.out, total * sizeof(kmu_overlap), hipMemcpyDeviceToHost, ctx->stream));
     return finish_call(ctx, mem);
 }

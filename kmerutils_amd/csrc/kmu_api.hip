@@ -89,19 +89,20 @@ int stage_sequences(kmu_ctx *ctx, const uint8_t *bases, const uint64_t *offsets,
             h_poff = out->h_packed_offsets.data();
         }
     }
-    void *d_b, *d_o, *d_p = nullptr;
+    uint64_t *d_p = nullptr, *d_o;
+    void *d_b;
     KMU_TRY(dev_buf(ctx, "in.bases", total_bytes + 64, &d_b));
-    KMU_TRY(dev_buf(ctx, "in.offsets", (size_t) (n_seq + 1) * 8, &d_o));
+    KMU_TRY(dev_array(ctx, "in.offsets", (size_t) (n_seq + 1), &d_o));
     KMU_HIP(ctx, hipMemcpyAsync(d_b, bases + first_byte, total_bytes, hipMemcpyHostToDevice, ctx->stream));
     KMU_HIP(ctx, hipMemcpyAsync(d_o, h_off, (size_t) (n_seq + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
     if (out->packed) {
-        KMU_TRY(dev_buf(ctx, "in.poffsets", (size_t) (n_seq + 1) * 8, &d_p));
+        KMU_TRY(dev_array(ctx, "in.poffsets", (size_t) (n_seq + 1), &d_p));
         KMU_HIP(ctx, hipMemcpyAsync(d_p, h_poff, (size_t) n_seq * 8, hipMemcpyHostToDevice, ctx->stream));
     }
     if (h_off != offsets) KMU_HIP(ctx, hipStreamSynchronize(ctx->stream)); // the temporaries are read by the copies above
     out->bases = (const uint8_t *) d_b;
-    out->offsets = (const uint64_t *) d_o;
-    out->packed_offsets = (const uint64_t *) d_p;
+    out->offsets = d_o;
+    out->packed_offsets = d_p;
     out->total_bytes = total_bytes;
     return KMU_OK;
 }
@@ -453,18 +454,11 @@ int kmu_count_non_acgt(kmu_ctx *ctx, const uint8_t *bases, const uint64_t *offse
     DevSeqs ds;
     KMU_TRY(stage_sequences(ctx, bases, offsets, nullptr, n_seq, KMU_INPUT_ASCII, mem, &ds));
     uint64_t *d_counts = counts_out;
-    if (mem == KMU_MEM_HOST) {
-        void *p;
-        KMU_TRY(dev_buf(ctx, "out.u64", (size_t) n_seq * 8 + 8, &p));
-        d_counts = (uint64_t *) p;
-    }
+    if (mem == KMU_MEM_HOST) KMU_TRY(dev_array(ctx, "out.u64", (size_t) n_seq + 1, &d_counts));
     if (n_seq) {
-        int grid = (int) std::min<uint32_t>(n_seq, (uint32_t) ctx->num_cus * 8);
-        KernelTimer t(ctx, "k_count_non_acgt");
-        hipLaunchKernelGGL(k_count_non_acgt, dim3(grid), dim3(256), 0, ctx->stream, ds.bases, ds.offsets, n_seq,
-                           ds.total_bytes, d_counts);
+        const int grid = grid_for(ctx, n_seq, 1);
+        KMU_TRY(launch(ctx, "k_count_non_acgt", k_count_non_acgt, dim3(grid), dim3(256), 0, ds.bases, ds.offsets, n_seq, ds.total_bytes, d_counts));
     }
-    KMU_HIP(ctx, hipGetLastError());
     if (mem == KMU_MEM_HOST)
         KMU_HIP(ctx, hipMemcpyAsync(counts_out, d_counts, (size_t) n_seq * 8, hipMemcpyDeviceToHost, ctx->stream));
     return finish_call(ctx, mem);
@@ -480,20 +474,19 @@ int kmu_pack2b(kmu_ctx *ctx, const uint8_t *bases, const uint64_t *offsets, uint
         packed_offsets_out[i + 1] = packed_offsets_out[i] + (offsets[i + 1] - offsets[i] + 3) / 4;
     DevSeqs ds;
     KMU_TRY(stage_sequences(ctx, bases, offsets, nullptr, n_seq, KMU_INPUT_ASCII, mem, &ds));
-    void *d_po, *d_out;
+    uint64_t *d_po;
+    void *d_out;
     uint64_t total_out = packed_offsets_out[n_seq];
-    KMU_TRY(dev_buf(ctx, "pack.offsets", (size_t) (n_seq + 1) * 8, &d_po));
+    KMU_TRY(dev_array(ctx, "pack.offsets", (size_t) (n_seq + 1), &d_po));
     KMU_TRY(dev_buf(ctx, "pack.out", total_out + 16, &d_out));
     KMU_HIP(ctx, hipMemcpyAsync(d_po, packed_offsets_out, (size_t) (n_seq + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
     uint32_t *d_err;
     KMU_TRY(get_err_word(ctx, &d_err));
     if (n_seq) {
-        int grid = (int) std::min<uint32_t>(n_seq, (uint32_t) ctx->num_cus * 8);
-        KernelTimer t(ctx, "k_pack2b");
-        hipLaunchKernelGGL(k_pack2b, dim3(grid), dim3(256), 0, ctx->stream, ds.bases, ds.offsets, n_seq, ds.total_bytes,
-                           (const uint64_t *) d_po, (uint8_t *) d_out, d_err);
+        const int grid = grid_for(ctx, n_seq, 1);
+        KMU_TRY(launch(ctx, "k_pack2b", k_pack2b, dim3(grid), dim3(256), 0, ds.bases, ds.offsets, n_seq, ds.total_bytes, d_po, (uint8_t *) d_out,
+                       d_err));
     }
-    KMU_HIP(ctx, hipGetLastError());
     KMU_HIP(ctx, hipMemcpyAsync(packed_out, d_out, total_out, hipMemcpyDeviceToHost, ctx->stream));
     KMU_TRY(check_err_word(ctx, d_err));
     return finish_call(ctx, mem);
@@ -512,13 +505,13 @@ static int kmer_hashes_impl(kmu_ctx *ctx, const kmu_hash_params *p, const uint8_
                 return fail(ctx, KMU_E_BAD_ARG, "bad range [%llu, %llu) for kmer iteration on sequence %u of %llu bases",
                             (unsigned long long) range_begin[i], (unsigned long long) range_end[i], i,
                             (unsigned long long) (offsets[i + 1] - offsets[i]));
-        void *q;
-        KMU_TRY(dev_buf(ctx, "in.range_b", (size_t) n_seq * 8 + 8, &q));
+        uint64_t *q;
+        KMU_TRY(dev_array(ctx, "in.range_b", (size_t) n_seq + 1, &q));
         KMU_HIP(ctx, hipMemcpyAsync(q, range_begin, (size_t) n_seq * 8, hipMemcpyHostToDevice, ctx->stream));
-        d_rb = (const uint64_t *) q;
-        KMU_TRY(dev_buf(ctx, "in.range_e", (size_t) n_seq * 8 + 8, &q));
+        d_rb = q;
+        KMU_TRY(dev_array(ctx, "in.range_e", (size_t) n_seq + 1, &q));
         KMU_HIP(ctx, hipMemcpyAsync(q, range_end, (size_t) n_seq * 8, hipMemcpyHostToDevice, ctx->stream));
-        d_re = (const uint64_t *) q;
+        d_re = q;
     }
     DevSeqs ds;
     KMU_TRY(stage_sequences(ctx, bases, offsets, packed_offsets, n_seq, p->input_kind, p->mem, &ds));
@@ -527,9 +520,7 @@ static int kmer_hashes_impl(kmu_ctx *ctx, const kmu_hash_params *p, const uint8_
     const uint64_t off0 = p->mem == KMU_MEM_HOST && n_seq ? offsets[0] : 0; // host ranges are staged re-based to 0
     if (p->mem == KMU_MEM_HOST) {
         total = offsets[n_seq] - off0;
-        void *q;
-        KMU_TRY(dev_buf(ctx, "out.u64", (size_t) total * 8 + 8, &q));
-        d_out = (uint64_t *) q;
+        KMU_TRY(dev_array(ctx, "out.u64", (size_t) total + 1, &d_out));
         // host arrays come back whole.  Range form: positions outside the ranges keep what the caller's array holds, so it
         // goes up first; plain form: the only positions that start no k-mer are the last k - 1 of every sequence -- they
         // come back as zeros (no upload of 8 bytes per base of possibly uninitialised caller memory for their sake)
@@ -540,12 +531,10 @@ static int kmer_hashes_impl(kmu_ctx *ctx, const kmu_hash_params *p, const uint8_
     KMU_TRY(get_err_word(ctx, &d_err));
     if (n_seq) {
         KmerCfg cfg{p->kmer_type, p->kmer_size, p->fhash};
-        int grid = (int) std::min<uint32_t>(n_seq, (uint32_t) ctx->num_cus * 8);
-        KernelTimer t(ctx, "k_kmer_hashes");
-        hipLaunchKernelGGL(k_kmer_hashes, dim3(grid), dim3(256), 0, ctx->stream, ds.bases, ds.offsets, ds.packed_offsets,
-                           n_seq, ds.packed, ds.total_bytes, cfg, d_rb, d_re, d_out, d_err);
+        const int grid = grid_for(ctx, n_seq, 1);
+        KMU_TRY(launch(ctx, "k_kmer_hashes", k_kmer_hashes, dim3(grid), dim3(256), 0, ds.bases, ds.offsets, ds.packed_offsets, n_seq, ds.packed,
+                       ds.total_bytes, cfg, d_rb, d_re, d_out, d_err));
     }
-    KMU_HIP(ctx, hipGetLastError());
     if (p->mem == KMU_MEM_HOST)
         KMU_HIP(ctx, hipMemcpyAsync(out + off0, d_out, (size_t) total * 8, hipMemcpyDeviceToHost, ctx->stream));
     return finish_checked(ctx, p->mem, d_err);

@@ -124,22 +124,10 @@ int kmu_sig_equal_pairs(kmu_ctx *ctx, const void *sig_a, uint32_t na, const void
     KMU_TRY(to_device(ctx, "cmp.ia", ia, n_pairs * 4, mem, &dia));
     KMU_TRY(to_device(ctx, "cmp.ib", ib, n_pairs * 4, mem, &dib));
     uint32_t *dout = out;
-    if (mem == KMU_MEM_HOST) {
-        void *q;
-        KMU_TRY(dev_buf(ctx, "cmp.out", n_pairs * 4, &q));
-        dout = (uint32_t *) q;
-    }
-    const int grid = (int) std::min<uint64_t>((n_pairs + 3) / 4, (uint64_t) ctx->num_cus * 16);
-    {
-        KernelTimer t(ctx, "k_sig_equal_pairs");
-        if (wb == 4)
-            hipLaunchKernelGGL(k_sig_equal_pairs<uint32_t>, dim3(grid), dim3(256), 0, ctx->stream, (const uint32_t *) da,
-                               (const uint32_t *) db, m, (const uint32_t *) dia, (const uint32_t *) dib, n_pairs, dout);
-        else
-            hipLaunchKernelGGL(k_sig_equal_pairs<uint64_t>, dim3(grid), dim3(256), 0, ctx->stream, (const uint64_t *) da,
-                               (const uint64_t *) db, m, (const uint32_t *) dia, (const uint32_t *) dib, n_pairs, dout);
-    }
-    KMU_HIP(ctx, hipGetLastError());
+    if (mem == KMU_MEM_HOST) KMU_TRY(dev_array(ctx, "cmp.out", n_pairs, &dout));
+    const int grid = grid_for(ctx, n_pairs, 4, 16);
+    if (wb == 4) KMU_TRY(launch(ctx, "k_sig_equal_pairs", k_sig_equal_pairs<uint32_t>, dim3(grid), dim3(256), 0, da, db, m, dia, dib, n_pairs, dout));
+    else KMU_TRY(launch(ctx, "k_sig_equal_pairs", k_sig_equal_pairs<uint64_t>, dim3(grid), dim3(256), 0, da, db, m, dia, dib, n_pairs, dout));
     if (mem == KMU_MEM_HOST) KMU_HIP(ctx, hipMemcpyAsync(out, dout, n_pairs * 4, hipMemcpyDeviceToHost, ctx->stream));
     return finish_call(ctx, mem);
 }
@@ -156,23 +144,11 @@ int kmu_sig_equal_matrix(kmu_ctx *ctx, const void *sig_a, uint32_t na, const voi
     KMU_TRY(to_device(ctx, "cmp.a", sig_a, (size_t) na * m * wb, mem, &da));
     KMU_TRY(to_device(ctx, "cmp.b", sig_b, (size_t) nb * m * wb, mem, &db));
     uint16_t *dout = out;
-    if (mem == KMU_MEM_HOST) {
-        void *q;
-        KMU_TRY(dev_buf(ctx, "cmp.out", (size_t) na * nb * 2, &q));
-        dout = (uint16_t *) q;
-    }
+    if (mem == KMU_MEM_HOST) KMU_TRY(dev_array(ctx, "cmp.out", (size_t) na * nb, &dout));
     const uint64_t tiles = (uint64_t) ((na + MT - 1) / MT) * ((nb + MT - 1) / MT);
     if (tiles > 0x7FFFFFFFull) return fail(ctx, KMU_E_UNSUPPORTED, "matrix too large for one launch: split the rows");
-    {
-        KernelTimer t(ctx, "k_sig_equal_matrix");
-        if (wb == 4)
-            hipLaunchKernelGGL(k_sig_equal_matrix<uint32_t>, dim3((uint32_t) tiles), dim3(256), 0, ctx->stream,
-                               (const uint32_t *) da, na, (const uint32_t *) db, nb, m, dout);
-        else
-            hipLaunchKernelGGL(k_sig_equal_matrix<uint64_t>, dim3((uint32_t) tiles), dim3(256), 0, ctx->stream,
-                               (const uint64_t *) da, na, (const uint64_t *) db, nb, m, dout);
-    }
-    KMU_HIP(ctx, hipGetLastError());
+    if (wb == 4) KMU_TRY(launch(ctx, "k_sig_equal_matrix", k_sig_equal_matrix<uint32_t>, dim3((uint32_t) tiles), dim3(256), 0, da, na, db, nb, m, dout));
+    else KMU_TRY(launch(ctx, "k_sig_equal_matrix", k_sig_equal_matrix<uint64_t>, dim3((uint32_t) tiles), dim3(256), 0, da, na, db, nb, m, dout));
     if (mem == KMU_MEM_HOST)
         KMU_HIP(ctx, hipMemcpyAsync(out, dout, (size_t) na * nb * 2, hipMemcpyDeviceToHost, ctx->stream));
     return finish_call(ctx, mem);
@@ -199,12 +175,8 @@ int kmu_minhash_distance_pairs(kmu_ctx *ctx, const uint64_t *hashes_a, uint32_t 
         dout = (uint32_t *) q;
     }
     const int grid = (int) std::min<uint64_t>((n_pairs + 255) / 256, (uint64_t) ctx->num_cus * 8);
-    {
-        KernelTimer t(ctx, "k_minhash_distance");
-        hipLaunchKernelGGL(k_minhash_distance, dim3(grid), dim3(256), 0, ctx->stream, (const uint64_t *) da,
-                           (const uint64_t *) db, m, (const uint32_t *) dia, (const uint32_t *) dib, n_pairs, dout);
-    }
-    KMU_HIP(ctx, hipGetLastError());
+    KMU_TRY(launch(ctx, "k_minhash_distance", k_minhash_distance, dim3(grid), dim3(256), 0, (const uint64_t *) da, (const uint64_t *) db, m,
+                   (const uint32_t *) dia, (const uint32_t *) dib, n_pairs, dout));
     if (mem == KMU_MEM_HOST) KMU_HIP(ctx, hipMemcpyAsync(out, dout, n_pairs * 12, hipMemcpyDeviceToHost, ctx->stream));
     return finish_call(ctx, mem);
 }

@@ -133,14 +133,6 @@ __global__ void __launch_bounds__(256) k_cc_number(const uint32_t *label, const 
     }
 }
 
-// the radix passes that can tell two cluster numbers below n apart
-static uint32_t cc_id_passes(uint32_t n) {
-    uint32_t m = 1, top = n - 1;
-    for (uint32_t b = 1; b < 4; b++)
-        if (top >> (8 * b)) m |= 1u << b;
-    return m;
-}
-
 // the common part of both entry points: `edges` reads device memory (staged by the caller), the outputs are the caller's
 template <class E>
 static int components_run(kmu_ctx *ctx, uint32_t n_nodes, const E &edges, uint64_t n_edges, int mem, uint32_t *label_out,
@@ -148,65 +140,33 @@ static int components_run(kmu_ctx *ctx, uint32_t n_nodes, const E &edges, uint64
     const size_t nb = (size_t) n_nodes * 4;
     uint32_t *label = label_out, *cluster = cluster_out, *size = size_out;
     if (mem == KMU_MEM_HOST) {
-        void *d;
-        KMU_TRY(dev_buf(ctx, "cc.label", nb, &d));
-        label = (uint32_t *) d;
-        if (cluster_out) {
-            KMU_TRY(dev_buf(ctx, "cc.cluster", nb, &d));
-            cluster = (uint32_t *) d;
-        }
-        if (size_out) {
-            KMU_TRY(dev_buf(ctx, "cc.size", nb, &d));
-            size = (uint32_t *) d;
-        }
+        KMU_TRY(dev_array(ctx, "cc.label", n_nodes, &label));
+        if (cluster_out) KMU_TRY(dev_array(ctx, "cc.cluster", n_nodes, &cluster));
+        if (size_out) KMU_TRY(dev_array(ctx, "cc.size", n_nodes, &size));
     }
     const bool numbered = cluster_out || size_out || members_out;
     const bool ranked = numbered || n_components_out;
-    void *is_root = nullptr, *rank = nullptr, *k0v = nullptr, *v0v = nullptr, *k1v = nullptr, *v1v = nullptr;
+    uint32_t *is_root = nullptr, *v0 = nullptr, *v1 = nullptr;
+    uint64_t *rank = nullptr, *k0 = nullptr, *k1 = nullptr;
     if (ranked) {
-        KMU_TRY(dev_buf(ctx, "cc.isroot", nb, &is_root));
-        KMU_TRY(dev_buf(ctx, "cc.rank", ((size_t) n_nodes + 1) * 8, &rank));
+        KMU_TRY(dev_array(ctx, "cc.isroot", n_nodes, &is_root));
+        KMU_TRY(dev_array(ctx, "cc.rank", (size_t) n_nodes + 1, &rank));
     }
     if (members_out) {
-        KMU_TRY(dev_buf(ctx, "cc.keys0", (size_t) n_nodes * 8, &k0v));
-        KMU_TRY(dev_buf(ctx, "cc.vals0", nb, &v0v));
-        KMU_TRY(dev_buf(ctx, "cc.keys1", (size_t) n_nodes * 8, &k1v));
-        KMU_TRY(dev_buf(ctx, "cc.vals1", nb, &v1v));
+        KMU_TRY(dev_array(ctx, "cc.keys0", n_nodes, &k0));
+        KMU_TRY(dev_array(ctx, "cc.vals0", n_nodes, &v0));
+        KMU_TRY(dev_array(ctx, "cc.keys1", n_nodes, &k1));
+        KMU_TRY(dev_array(ctx, "cc.vals1", n_nodes, &v1));
     }
 
-    const uint32_t cap = (uint32_t) ctx->num_cus * 8; // about 2048 workgroups at most, the rest by grid stride
-    const uint32_t node_grid = (uint32_t) std::min<uint64_t>(((uint64_t) n_nodes + 255) / 256, cap);
-    {
-        KernelTimer t(ctx, "k_cc_init");
-        hipLaunchKernelGGL(k_cc_init, dim3(node_grid), dim3(256), 0, ctx->stream, label, n_nodes);
-    }
-    KMU_HIP(ctx, hipGetLastError());
-    if (n_edges) {
-        const uint32_t edge_grid = (uint32_t) std::min<uint64_t>((n_edges + 255) / 256, cap);
-        {
-            KernelTimer t(ctx, "k_cc_hook");
-            hipLaunchKernelGGL(k_cc_hook<E>, dim3(edge_grid), dim3(256), 0, ctx->stream, edges, n_edges, label, n_nodes);
-        }
-        KMU_HIP(ctx, hipGetLastError());
-    }
-    {
-        KernelTimer t(ctx, "k_cc_flatten");
-        hipLaunchKernelGGL(k_cc_flatten, dim3(node_grid), dim3(256), 0, ctx->stream, label, n_nodes, (uint32_t *) is_root, size);
-    }
-    KMU_HIP(ctx, hipGetLastError());
-    if (ranked) KMU_TRY(device_scan_u32(ctx, (const uint32_t *) is_root, n_nodes, (uint64_t *) rank));
-    if (numbered) {
-        {
-            KernelTimer t(ctx, "k_cc_number");
-            hipLaunchKernelGGL(k_cc_number, dim3(node_grid), dim3(256), 0, ctx->stream, (const uint32_t *) label, (const uint64_t *) rank,
-                               n_nodes, cluster, size, (uint64_t *) k0v, (uint32_t *) v0v);
-        }
-        KMU_HIP(ctx, hipGetLastError());
-    }
+    const int node_grid = grid_for(ctx, n_nodes, 256); // about 2048 workgroups at most, the rest by grid stride
+    KMU_TRY(launch(ctx, "k_cc_init", k_cc_init, dim3(node_grid), dim3(256), 0, label, n_nodes));
+    if (n_edges) KMU_TRY(launch(ctx, "k_cc_hook", k_cc_hook<E>, dim3(grid_for(ctx, n_edges, 256)), dim3(256), 0, edges, n_edges, label, n_nodes));
+    KMU_TRY(launch(ctx, "k_cc_flatten", k_cc_flatten, dim3(node_grid), dim3(256), 0, label, n_nodes, is_root, size));
+    if (ranked) KMU_TRY(device_scan_u32(ctx, is_root, n_nodes, rank));
+    if (numbered) KMU_TRY(launch(ctx, "k_cc_number", k_cc_number, dim3(node_grid), dim3(256), 0, label, rank, n_nodes, cluster, size, k0, v0));
     if (members_out) {
-        uint64_t *k0 = (uint64_t *) k0v, *k1 = (uint64_t *) k1v;
-        uint32_t *v0 = (uint32_t *) v0v, *v1 = (uint32_t *) v1v;
-        KMU_TRY(radix_sort_pairs_passes(ctx, k0, v0, k1, v1, n_nodes, cc_id_passes(n_nodes), nullptr));
+        KMU_TRY(radix_sort_pairs_passes(ctx, k0, v0, k1, v1, n_nodes, radix_id_passes(n_nodes), nullptr));
         KMU_HIP(ctx, hipMemcpyAsync(members_out, v0, nb, mem == KMU_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice,
                                     ctx->stream));
     }
@@ -217,7 +177,7 @@ static int components_run(kmu_ctx *ctx, uint32_t n_nodes, const E &edges, uint64
     }
     if (n_components_out) { // the one synchronisation of a device call: the count crosses to the host
         uint64_t total = 0;
-        KMU_HIP(ctx, hipMemcpyAsync(&total, (const uint64_t *) rank + n_nodes, 8, hipMemcpyDeviceToHost, ctx->stream));
+        KMU_HIP(ctx, hipMemcpyAsync(&total, rank + n_nodes, 8, hipMemcpyDeviceToHost, ctx->stream));
         KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
         *n_components_out = (uint32_t) total;
     }

@@ -338,16 +338,12 @@ int local_add(kmu_counter *c, const DevSeqs &ds, uint64_t total_bases, uint32_t 
     CountTable t = table_of(c);
     if (!ds.packed) {
         int grid = ctx->num_cus * 8;
-        KernelTimer tm(ctx, "k_count_add_flat");
-        hipLaunchKernelGGL(k_count_add_flat, dim3(grid), dim3(256), 0, ctx->stream, ds.bases, ds.offsets, ds.n_seq, c->p.kmer_size, t,
-                           d_err);
+        KMU_TRY(launch(ctx, "k_count_add_flat", k_count_add_flat, dim3(grid), dim3(256), 0, ds.bases, ds.offsets, ds.n_seq, c->p.kmer_size, t, d_err));
     } else {
         int grid = (int) std::min<uint64_t>(ds.n_seq, (uint64_t) ctx->num_cus * 8);
-        KernelTimer tm(ctx, "k_count_add_reads");
-        hipLaunchKernelGGL(k_count_add_reads, dim3(grid), dim3(256), 0, ctx->stream, ds.bases, ds.offsets, ds.packed_offsets, ds.n_seq,
-                           ds.packed, ds.total_bytes, c->p.kmer_size, t, d_err);
+        KMU_TRY(launch(ctx, "k_count_add_reads", k_count_add_reads, dim3(grid), dim3(256), 0, ds.bases, ds.offsets, ds.packed_offsets, ds.n_seq,
+                       ds.packed, ds.total_bytes, c->p.kmer_size, t, d_err));
     }
-    KMU_HIP(ctx, hipGetLastError());
     return KMU_OK;
 }
 
@@ -366,12 +362,12 @@ int flat_stream_extent(kmu_ctx *ctx, const uint64_t *host_offsets, uint32_t n_se
     KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
     const uint64_t shift = first & ~(uint64_t) 1023;
     if (shift) {
-        void *q;
-        KMU_TRY(dev_buf(ctx, "in.offsets", ((size_t) n_seq + 1) * 8, &q));
-        const int grid = (int) std::min<uint64_t>(((uint64_t) n_seq + 256) / 256, (uint64_t) ctx->num_cus * 8);
-        hipLaunchKernelGGL(k_rebase_offsets, dim3(grid), dim3(256), 0, ctx->stream, ds.offsets, (uint64_t) n_seq + 1, shift, (uint64_t *) q);
+        uint64_t *q;
+        KMU_TRY(dev_array(ctx, "in.offsets", (size_t) n_seq + 1, &q));
+        const int grid = grid_for(ctx, (uint64_t) n_seq + 1, 256);
+        KMU_TRY(launch(ctx, nullptr, k_rebase_offsets, dim3(grid), dim3(256), 0, ds.offsets, (uint64_t) n_seq + 1, shift, q));
         ds.bases += shift;
-        ds.offsets = (const uint64_t *) q;
+        ds.offsets = q;
     }
     *total_out = last - shift;
     return KMU_OK;
@@ -417,12 +413,7 @@ int add_entries(kmu_counter *c, const uint64_t *kmers, const uint32_t *counts, u
         return finish_checked(ctx, mem, d_err);
     }
     KMU_TRY(materialize(c));
-    {
-        KernelTimer tm(ctx, "k_count_add_kmers");
-        hipLaunchKernelGGL(k_count_add_kmers, dim3(grid_for(ctx, n, 256)), dim3(256), 0, ctx->stream, d_k, d_c, n,
-                           table_of(c), d_err);
-    }
-    KMU_HIP(ctx, hipGetLastError());
+    KMU_TRY(launch(ctx, "k_count_add_kmers", k_count_add_kmers, dim3(grid_for(ctx, n, 256)), dim3(256), 0, d_k, d_c, n, table_of(c), d_err));
     return finish_checked(ctx, mem, d_err);
 }
 
@@ -447,12 +438,13 @@ int add_superkmers(kmu_counter *c, const void *recs, uint64_t n_rec, uint64_t n_
         }
         overflowed = true; // a segment and the spill list overflowed, the table is untouched: the exact levels, on the k-mers
     }
-    void *x, *cur;
-    KMU_TRY(dev_buf(ctx, "cnt.smer_x", n_kmers * 8 + 64, &x));
+    uint64_t *x;
+    void *cur;
+    KMU_TRY(dev_array(ctx, "cnt.smer_x", n_kmers + 8, &x));
     KMU_TRY(dev_buf(ctx, "cnt.smer_cur", 64, &cur));
-    KMU_TRY(smer_expand(ctx, recs, n_rec, c->p.kmer_size, (uint64_t *) x, (uint64_t *) cur));
+    KMU_TRY(smer_expand(ctx, recs, n_rec, c->p.kmer_size, x, (uint64_t *) cur));
     c->no_seg = overflowed;
-    const int rc = add_entries(c, (const uint64_t *) x, nullptr, n_kmers, KMU_MEM_DEVICE);
+    const int rc = add_entries(c, x, nullptr, n_kmers, KMU_MEM_DEVICE);
     c->no_seg = false;
     return rc;
 }
@@ -475,12 +467,8 @@ static int count_stats(kmu_counter *c, uint64_t *distinct, uint64_t *unique, uin
         return KMU_OK;
     }
     KMU_HIP(ctx, hipMemsetAsync(c->scalars, 0, 32, ctx->stream));
-    {
-        KernelTimer tm(ctx, "k_count_stats");
-        hipLaunchKernelGGL(k_count_stats, dim3(grid_for(ctx, c->nslots, 1024)), dim3(256), 0, ctx->stream, table_of(c),
-                           c->nslots, c->scalars, (uint32_t) std::min<uint64_t>(count_ceiling(c), 0xFFFFFFFFull));
-    }
-    KMU_HIP(ctx, hipGetLastError());
+    KMU_TRY(launch(ctx, "k_count_stats", k_count_stats, dim3(grid_for(ctx, c->nslots, 1024)), dim3(256), 0, table_of(c), c->nslots, c->scalars,
+                   (uint32_t) std::min<uint64_t>(count_ceiling(c), 0xFFFFFFFFull)));
     uint64_t h[4];
     KMU_HIP(ctx, hipMemcpyAsync(h, c->scalars, 32, hipMemcpyDeviceToHost, ctx->stream));
     KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -506,23 +494,16 @@ int select_entries(kmu_counter *c, uint32_t min_count, uint32_t maxc, uint32_t p
     uint32_t *d_c = nullptr;
     if (kmers_out) {
         if (mem == KMU_MEM_HOST) {
-            void *q;
-            KMU_TRY(dev_buf(ctx, "cnt.sel.k", cap * 8 + 8, &q));
-            d_k = (uint64_t *) q;
-            KMU_TRY(dev_buf(ctx, "cnt.sel.c", cap * 4 + 8, &q));
-            d_c = (uint32_t *) q;
+            KMU_TRY(dev_array(ctx, "cnt.sel.k", cap + 1, &d_k));
+            KMU_TRY(dev_array(ctx, "cnt.sel.c", cap + 2, &d_c));
         } else {
             d_k = kmers_out;
             d_c = counts_out;
         }
     }
     KMU_HIP(ctx, hipMemsetAsync(c->scalars, 0, 32, ctx->stream));
-    {
-        KernelTimer tm(ctx, "k_count_select");
-        hipLaunchKernelGGL(k_count_select, dim3(grid_for(ctx, c->nslots, 1024)), dim3(256), 0, ctx->stream, table_of(c),
-                           c->nslots, min_count, maxc, w32, part, n_parts, cap, d_k, d_c, c->scalars + 2);
-    }
-    KMU_HIP(ctx, hipGetLastError());
+    KMU_TRY(launch(ctx, "k_count_select", k_count_select, dim3(grid_for(ctx, c->nslots, 1024)), dim3(256), 0, table_of(c), c->nslots, min_count, maxc,
+                   w32, part, n_parts, cap, d_k, d_c, c->scalars + 2));
     uint64_t n = 0;
     KMU_HIP(ctx, hipMemcpyAsync(&n, c->scalars + 2, 8, hipMemcpyDeviceToHost, ctx->stream));
     KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -552,12 +533,13 @@ static int rebuild_from_selection(kmu_counter *c, uint32_t min_count, uint32_t p
     KMU_HIP(ctx, hipSetDevice(ctx->device));
     uint64_t n = 0, n2 = 0; // raw counts, as kmu_count_export_part has them
     KMU_TRY(select_entries(c, min_count, 0xFFFFFFFFu, part, n_parts, nullptr, nullptr, 0, KMU_MEM_DEVICE, false, &n));
-    void *k = nullptr, *cc = nullptr;
-    KMU_TRY(dev_buf(ctx, "cnt.keep.k", n * 8 + 8, &k));
-    KMU_TRY(dev_buf(ctx, "cnt.keep.c", n * 4 + 8, &cc));
-    KMU_TRY(select_entries(c, min_count, 0xFFFFFFFFu, part, n_parts, (uint64_t *) k, (uint32_t *) cc, n, KMU_MEM_DEVICE, false, &n2));
+    uint32_t *cc = nullptr;
+    uint64_t *k = nullptr;
+    KMU_TRY(dev_array(ctx, "cnt.keep.k", n + 1, &k));
+    KMU_TRY(dev_array(ctx, "cnt.keep.c", n + 2, &cc));
+    KMU_TRY(select_entries(c, min_count, 0xFFFFFFFFu, part, n_parts, k, cc, n, KMU_MEM_DEVICE, false, &n2));
     KMU_TRY(kmu_count_reset(c));
-    KMU_TRY(add_entries(c, (const uint64_t *) k, (const uint32_t *) cc, n2, KMU_MEM_DEVICE));
+    KMU_TRY(add_entries(c, k, cc, n2, KMU_MEM_DEVICE));
     KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return KMU_OK;
 }
@@ -684,15 +666,9 @@ int kmu_count_query(kmu_counter *c, const uint64_t *canon_kmers, uint64_t n, int
         KMU_TRY(dev_buf(ctx, "cnt.in.k", n * 8, &q));
         KMU_HIP(ctx, hipMemcpyAsync(q, canon_kmers, n * 8, hipMemcpyHostToDevice, ctx->stream));
         d_k = (const uint64_t *) q;
-        KMU_TRY(dev_buf(ctx, "cnt.out.c", n * 4, &q));
-        d_o = (uint32_t *) q;
+        KMU_TRY(dev_array(ctx, "cnt.out.c", n, &d_o));
     }
-    {
-        KernelTimer tm(ctx, "k_count_query");
-        hipLaunchKernelGGL(k_count_query, dim3(grid_for(ctx, n, 256)), dim3(256), 0, ctx->stream, d_k, n, table_of(c),
-                           max_count(c), d_o);
-    }
-    KMU_HIP(ctx, hipGetLastError());
+    KMU_TRY(launch(ctx, "k_count_query", k_count_query, dim3(grid_for(ctx, n, 256)), dim3(256), 0, d_k, n, table_of(c), max_count(c), d_o));
     if (mem == KMU_MEM_HOST) KMU_HIP(ctx, hipMemcpyAsync(counts_out, d_o, n * 4, hipMemcpyDeviceToHost, ctx->stream));
     return finish_call(ctx, mem);
 }
@@ -761,18 +737,15 @@ int kmu_count_once_positions(kmu_counter *c, const uint8_t *bases, const uint64_
     if (total_bases == 0) return KMU_OK;
     KMU_TRY(materialize(c));
     const uint64_t nsteps = flat_wave_steps(total_bases);
-    void *cnt, *base;
-    KMU_TRY(dev_buf(ctx, "once.cnt", nsteps * 4 + 64, &cnt));
-    KMU_TRY(dev_buf(ctx, "once.base", (nsteps + 1) * 8 + 64, &base));
-    const int grid = (int) std::min<uint64_t>((nsteps + 3) / 4, (uint64_t) ctx->num_cus * 8);
-    {
-        KernelTimer tm(ctx, "k_once_count");
-        hipLaunchKernelGGL(k_once_count, dim3(grid), dim3(256), 0, ctx->stream, ds.bases, ds.offsets, n_seq, c->p.kmer_size,
-                           table_of(c), (uint32_t *) cnt);
-    }
-    KMU_TRY(device_scan_u32(ctx, (const uint32_t *) cnt, nsteps, (uint64_t *) base));
+    uint64_t *base;
+    uint32_t *cnt;
+    KMU_TRY(dev_array(ctx, "once.cnt", nsteps + 16, &cnt));
+    KMU_TRY(dev_array(ctx, "once.base", nsteps + 1 + 8, &base));
+    const int grid = grid_for(ctx, nsteps, 4);
+    KMU_TRY(launch(ctx, "k_once_count", k_once_count, dim3(grid), dim3(256), 0, ds.bases, ds.offsets, n_seq, c->p.kmer_size, table_of(c), cnt));
+    KMU_TRY(device_scan_u32(ctx, cnt, nsteps, base));
     uint64_t n = 0;
-    KMU_HIP(ctx, hipMemcpyAsync(&n, (const uint64_t *) base + nsteps, 8, hipMemcpyDeviceToHost, ctx->stream));
+    KMU_HIP(ctx, hipMemcpyAsync(&n, base + nsteps, 8, hipMemcpyDeviceToHost, ctx->stream));
     KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
     *n_out = n;
     if (!kmers_out) return KMU_OK; // size query
@@ -781,20 +754,12 @@ int kmu_count_once_positions(kmu_counter *c, const uint8_t *bases, const uint64_
     uint64_t *d_k = kmers_out;
     uint32_t *d_s = numseq_out, *d_p = numkmer_out;
     if (mem == KMU_MEM_HOST) {
-        void *q;
-        KMU_TRY(dev_buf(ctx, "once.k", n * 8 + 64, &q));
-        d_k = (uint64_t *) q;
-        KMU_TRY(dev_buf(ctx, "once.s", n * 4 + 64, &q));
-        d_s = (uint32_t *) q;
-        KMU_TRY(dev_buf(ctx, "once.p", n * 4 + 64, &q));
-        d_p = (uint32_t *) q;
+        KMU_TRY(dev_array(ctx, "once.k", n + 8, &d_k));
+        KMU_TRY(dev_array(ctx, "once.s", n + 16, &d_s));
+        KMU_TRY(dev_array(ctx, "once.p", n + 16, &d_p));
     }
-    {
-        KernelTimer tm(ctx, "k_once_emit");
-        hipLaunchKernelGGL(k_once_emit, dim3(grid), dim3(256), 0, ctx->stream, ds.bases, ds.offsets, n_seq, c->p.kmer_size,
-                           table_of(c), (const uint64_t *) base, d_k, d_s, d_p);
-    }
-    KMU_HIP(ctx, hipGetLastError());
+    KMU_TRY(launch(ctx, "k_once_emit", k_once_emit, dim3(grid), dim3(256), 0, ds.bases, ds.offsets, n_seq, c->p.kmer_size, table_of(c), base, d_k,
+                   d_s, d_p));
     if (mem == KMU_MEM_HOST) {
         KMU_HIP(ctx, hipMemcpyAsync(kmers_out, d_k, n * 8, hipMemcpyDeviceToHost, ctx->stream));
         KMU_HIP(ctx, hipMemcpyAsync(numseq_out, d_s, n * 4, hipMemcpyDeviceToHost, ctx->stream));

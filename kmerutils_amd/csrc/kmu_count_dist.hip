@@ -110,19 +110,20 @@ int dist_add_begin(kmu_counter *c, DevSeqs &ds, uint64_t total_bases, uint32_t *
     comm_stats_reset(ctx);
     cm->stats.owner_kind = c->okind;
     // ---- census + sample ----
-    void *slist, *sn;
+    uint64_t *slist;
+    void *sn;
     const uint64_t units = smer ? smer_units(ctx, total_bases)
                                 : unit_split(flat_wave_steps(total_bases), (uint64_t) ctx->num_cus * 8).asked; // (as sample_ratio)
     const uint64_t kmers_per_unit = (total_bases + units - 1) / units;
     uint32_t shift = 0; // ~1024 sampled k-mers per workgroup (its LDS list holds 4096)
     while (shift < 24 && (kmers_per_unit >> shift) > 1024) shift++;
     const uint32_t cap = (uint32_t) std::min<uint64_t>(units * SAMPLE_LDS, 1u << 26);
-    KMU_TRY(dev_buf(ctx, "cnt.sample", (size_t) cap * 8 + 64, &slist));
+    KMU_TRY(dev_array(ctx, "cnt.sample", (size_t) cap + 8, &slist));
     KMU_TRY(dev_buf(ctx, "cnt.sample_n", 64, &sn));
     KMU_HIP(ctx, hipMemsetAsync(sn, 0, 64, ctx->stream));
     OwnerPlan op;
     SmerGroups sg;
-    const SampleArgs sa{(uint64_t *) slist, (uint32_t *) sn, cap, shift};
+    const SampleArgs sa{slist, (uint32_t *) sn, cap, shift};
     std::vector<uint64_t> bounds(N + 1), kto(N, 0); // groups (k-mers or records) per owner, as a prefix; k-mers per owner
     if (smer) {
         KMU_TRY(smer_census(ctx, ds, total_bases, c->p.kmer_size, N, d_err, sa, &sg));
@@ -141,7 +142,7 @@ int dist_add_begin(kmu_counter *c, DevSeqs &ds, uint64_t total_bases, uint32_t *
     for (uint32_t p = 0; p < N; p++) n_local += kto[p];
     const uint32_t n_s = std::min(h_sn[0], cap);
     uint32_t d_s = 0;
-    if (n_s && !h_sn[1]) KMU_TRY(sample_distinct(ctx, (const uint64_t *) slist, n_s, (uint32_t *) sn + 2, &d_s));
+    if (n_s && !h_sn[1]) KMU_TRY(sample_distinct(ctx, slist, n_s, (uint32_t *) sn + 2, &d_s));
     // ---- the ranks agree: sampled occurrences / distinct, local k-mers, and the send counts of every rank ----
     // (a k-mer's occurrences on different ranks are in different samples: the global distinct count of the sample is not
     //  known; the per-rank ratio is what decides how much MERGE saves on each rank, and the sum of both sides is used)
@@ -293,15 +294,14 @@ int kmu_count_finalize(kmu_counter *c) {
     const uint32_t N = (uint32_t) cm->nranks, me = (uint32_t) cm->rank;
     const int w32 = owner_mode_of(c);
     // who has entries of other owners, and how many for whom
-    void *po;
-    KMU_TRY(dev_buf(ctx, "cnt.per_owner", ((size_t) N + 1) * 8 * 2 + 64, &po));
+    unsigned long long *po;
+    KMU_TRY(dev_array(ctx, "cnt.per_owner", ((size_t) N + 1) * 2 + 8, &po));
     KMU_HIP(ctx, hipMemsetAsync(po, 0, ((size_t) N + 1) * 8 * 2, ctx->stream));
     const bool have = c->unmerged && !c->empty;
     if (have) KMU_TRY(materialize(c)); // (the export probes and rewrites slots)
     if (have) {
-        KernelTimer tm(ctx, "k_owner_census");
-        hipLaunchKernelGGL(k_owner_census, dim3(grid_for(ctx, c->nslots, 1024)), dim3(256), ((size_t) N + 1) * 4, ctx->stream, table_of(c),
-                           c->nslots, w32, N, (unsigned long long *) po);
+        KMU_TRY(launch(ctx, "k_owner_census", k_owner_census, dim3(grid_for(ctx, c->nslots, 1024)), dim3(256), ((size_t) N + 1) * 4, table_of(c),
+                       c->nslots, w32, N, po));
     }
     std::vector<uint64_t> mine(N + 1), all((size_t) (N + 1) * N);
     KMU_HIP(ctx, hipMemcpyAsync(mine.data(), po, ((size_t) N + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -325,18 +325,17 @@ int kmu_count_finalize(kmu_counter *c) {
         rdis[p] = n_recv;
         n_recv += rcnt[p];
     }
-    void *sk, *sc, *rk, *rc;
-    KMU_TRY(dev_buf(ctx, "cnt.send_k", n_send * 8 + 64, &sk));
-    KMU_TRY(dev_buf(ctx, "cnt.send_c", n_send * 4 + 64, &sc));
-    KMU_TRY(dev_buf(ctx, "cnt.recv", n_recv * 8 + 64, &rk));
-    KMU_TRY(dev_buf(ctx, "cnt.recv_c", n_recv * 4 + 64, &rc));
+    uint32_t *rc, *sc;
+    uint64_t *rk, *sk;
+    KMU_TRY(dev_array(ctx, "cnt.send_k", n_send + 8, &sk));
+    KMU_TRY(dev_array(ctx, "cnt.send_c", n_send + 16, &sc));
+    KMU_TRY(dev_array(ctx, "cnt.recv", n_recv + 8, &rk));
+    KMU_TRY(dev_array(ctx, "cnt.recv_c", n_recv + 16, &rc));
     if (n_send) {
-        unsigned long long *cursor = (unsigned long long *) po + (N + 1);
+        unsigned long long *cursor = po + (N + 1);
         KMU_HIP(ctx, hipMemcpyAsync(cursor, sdis.data(), (size_t) N * 8, hipMemcpyHostToDevice, ctx->stream));
-        KernelTimer tm(ctx, "k_owner_emit");
-        hipLaunchKernelGGL(k_owner_emit, dim3(grid_for(ctx, c->nslots, 1024)), dim3(256), 0, ctx->stream, table_of(c), c->nslots, w32, me,
-                           N, cursor, (uint64_t *) sk, (uint32_t *) sc);
-        KMU_HIP(ctx, hipGetLastError());
+        KMU_TRY(launch(ctx, "k_owner_emit", k_owner_emit, dim3(grid_for(ctx, c->nslots, 1024)), dim3(256), 0, table_of(c), c->nslots, w32, me, N,
+                       cursor, sk, sc));
     }
     const uint64_t sent0 = cm->stats.bytes_sent;
     KMU_HIP(ctx, hipEventRecord(cm->ev_a, ctx->stream));
@@ -351,15 +350,16 @@ int kmu_count_finalize(kmu_counter *c) {
     // k-mer of a noisy long-read set occurs once), the table is rebuilt from the entries that stay before the merge.
     // (a local decision: every rank looks at its own table, nothing collective follows from it)
     if ((n_send || n_tomb) && (double) (n_stay + n_send + n_tomb + n_recv) > 0.55 * (double) c->nslots) {
-        void *kk = nullptr, *kc = nullptr;
-        KMU_TRY(dev_buf(ctx, "cnt.keep.k", n_stay * 8 + 8, &kk));
-        KMU_TRY(dev_buf(ctx, "cnt.keep.c", n_stay * 4 + 8, &kc));
+        uint32_t *kc = nullptr;
+        uint64_t *kk = nullptr;
+        KMU_TRY(dev_array(ctx, "cnt.keep.k", n_stay + 1, &kk));
+        KMU_TRY(dev_array(ctx, "cnt.keep.c", n_stay + 2, &kc));
         uint64_t n2 = 0;
-        KMU_TRY(select_entries(c, 1u, 0xFFFFFFFFu, me, N, (uint64_t *) kk, (uint32_t *) kc, n_stay, KMU_MEM_DEVICE, false, &n2, true));
+        KMU_TRY(select_entries(c, 1u, 0xFFFFFFFFu, me, N, kk, kc, n_stay, KMU_MEM_DEVICE, false, &n2, true));
         KMU_TRY(kmu_count_reset(c));
-        if (n2) KMU_TRY(add_entries(c, (const uint64_t *) kk, (const uint32_t *) kc, n2, KMU_MEM_DEVICE));
+        if (n2) KMU_TRY(add_entries(c, kk, kc, n2, KMU_MEM_DEVICE));
     }
-    if (n_recv) KMU_TRY(add_entries(c, (const uint64_t *) rk, (const uint32_t *) rc, n_recv, KMU_MEM_DEVICE));
+    if (n_recv) KMU_TRY(add_entries(c, rk, rc, n_recv, KMU_MEM_DEVICE));
     KMU_HIP(ctx, hipStreamSynchronize(ctx->stream)); // sdis / scnt are locals the copies above read
     return KMU_OK;
 }

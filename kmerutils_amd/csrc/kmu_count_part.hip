@@ -26,14 +26,12 @@ static int launch_build(kmu_counter *c, const uint64_t *items, const uint64_t *l
     const int in_mode = c->empty ? 0 : 1;
     const size_t lds = build_lds(c) + build_pool_lds(c);
     const int per_cu = c->qw ? std::min(32 / (BUILD_THREADS / 64), (int) ((160 * 1024) / lds)) : 3;
-    const int grid = (int) std::min<uint64_t>(n_regions, (uint64_t) ctx->num_cus * per_cu * 8);
+    const int grid = grid_for(ctx, n_regions, 1, per_cu * 8);
     {
         const auto kern = !c->qw ? k_part_build<IT> : leaf6 ? k_part_build_q<IT_HASH, true> : k_part_build_q<IT, false>;
-        KernelTimer tm(ctx, c->qw ? "k_part_build_q" : "k_part_build"); // (the kernels' own names)
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(BUILD_THREADS), lds, ctx->stream, items, leaves, (uint32_t) n_regions, table_of(c), in_mode, d_err,
-                           leaf_stride, leafcnt);
+        KMU_TRY(launch(ctx, c->qw ? "k_part_build_q" : "k_part_build", kern, dim3(grid), dim3(BUILD_THREADS), lds, items, leaves,
+                       (uint32_t) n_regions, table_of(c), in_mode, d_err, leaf_stride, leafcnt));
     }
-    KMU_HIP(ctx, hipGetLastError());
     c->empty = false;
     return KMU_OK;
 }
@@ -103,8 +101,7 @@ static int seg_buffers(kmu_ctx *ctx, const PartPlan &pl, const SegPlan &sp, uint
     const uint64_t spill_cap = std::min<uint64_t>(n_items / 32 + 4096, 0x7FFFFFFFull);
     KMU_TRY(dev_buf(ctx, "cnt.seg_ovf", 64, &b->ovf));
     KMU_TRY(dev_buf(ctx, "cnt.spill", (size_t) spill_cap * 8 + 64, &b->spill));
-    hipLaunchKernelGGL(k_spill_header, dim3(1), dim3(64), 0, ctx->stream, (uint32_t *) b->ovf, (uint32_t) spill_cap, (uint64_t *) b->spill);
-    KMU_HIP(ctx, hipGetLastError());
+    KMU_TRY(launch(ctx, nullptr, k_spill_header, dim3(1), dim3(64), 0, (uint32_t *) b->ovf, (uint32_t) spill_cap, (uint64_t *) b->spill));
     KMU_TRY(dev_buf(ctx, "cnt.seg_state", (size_t) sp.sets * bins1 * 4 + 64, &b->state));
     KMU_HIP(ctx, hipMemsetAsync(b->state, 0, (size_t) sp.sets * bins1 * 4, ctx->stream));
     return scatter_attrs(ctx);
@@ -112,9 +109,8 @@ static int seg_buffers(kmu_ctx *ctx, const PartPlan &pl, const SegPlan &sp, uint
 // behind the last launch of a level 1: "no k-mer" marks from the fill of every (set, bin) stream to its capacity
 static int seg_tails(kmu_ctx *ctx, const PartPlan &pl, const SegPlan &sp, const SegBufs &b) {
     const uint32_t n_streams = sp.sets * plan_bins1(pl);
-    hipLaunchKernelGGL(k_seg_tails, dim3(std::min<uint32_t>(n_streams, (uint32_t) ctx->num_cus * 8u)), dim3(256), 0, ctx->stream,
-                       (const uint32_t *) b.state, n_streams, (uint32_t) sp.cap1, (uint64_t *) b.A);
-    KMU_HIP(ctx, hipGetLastError());
+    KMU_TRY(launch(ctx, nullptr, k_seg_tails, dim3(grid_for(ctx, n_streams, 1)), dim3(256), 0,
+                   (const uint32_t *) b.state, n_streams, (uint32_t) sp.cap1, (uint64_t *) b.A));
     return KMU_OK;
 }
 // The tail of a single-pass partition: level 2 (A, level 1's streams -> the leaves in B, SEG_L2_UNITS units per bin sharing its
@@ -129,21 +125,18 @@ static int seg_level2_build(kmu_counter *c, const PartPlan &pl, const SegPlan &s
     KMU_HIP(ctx, hipMemsetAsync(b.leafcnt, 0, (size_t) ap.nparts * ap.bins * 4, ctx->stream));
     {
         const auto k2 = leaf6 ? k_arr_scatter_seg<IT_HASH, true> : k_arr_scatter_seg<IT_HASH, false>;
-        KernelTimer tm(ctx, "k_arr_scatter");
-        hipLaunchKernelGGL(k2, dim3(ap.nparts * ap.chunks), dim3(SCATTER_THREADS), seg_lds_bytes(ap.bins, leaf6), ctx->stream, (const uint64_t *) b.A,
-                           (const uint64_t *) nullptr, ap, (uint64_t *) b.B, sp.cap2, (uint32_t *) b.ovf, (uint32_t *) b.leafcnt, (const uint32_t *) c->lox);
+        KMU_TRY(launch(ctx, "k_arr_scatter", k2, dim3(ap.nparts * ap.chunks), dim3(SCATTER_THREADS), seg_lds_bytes(ap.bins, leaf6),
+                       (const uint64_t *) b.A, (const uint64_t *) nullptr, ap, (uint64_t *) b.B, sp.cap2, (uint32_t *) b.ovf, (uint32_t *) b.leafcnt,
+                       (const uint32_t *) c->lox));
     }
-    KMU_HIP(ctx, hipGetLastError());
     uint32_t h_ovf[2] = {0, 0}; // [0] the list is full, [1] items spilled
     KMU_HIP(ctx, hipMemcpyAsync(h_ovf, b.ovf, 8, hipMemcpyDeviceToHost, ctx->stream));
     KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
     if (h_ovf[0]) return KMU_OK;
     KMU_TRY(launch_build<IT_HASH>(c, (const uint64_t *) b.B, nullptr, d_err, sp.cap2, (const uint32_t *) b.leafcnt, leaf6));
     if (h_ovf[1]) {
-        KernelTimer tm(ctx, "k_count_add_spill");
-        hipLaunchKernelGGL(k_count_add_spill, dim3(grid_for(ctx, h_ovf[1], 256)), dim3(256), 0, ctx->stream, (const uint64_t *) b.spill,
-                           (const uint32_t *) b.ovf, table_of(c), d_err);
-        KMU_HIP(ctx, hipGetLastError());
+        KMU_TRY(launch(ctx, "k_count_add_spill", k_count_add_spill, dim3(grid_for(ctx, h_ovf[1], 256)), dim3(256), 0, (const uint64_t *) b.spill,
+                       (const uint32_t *) b.ovf, table_of(c), d_err));
     }
     *taken = 1;
     return KMU_OK;
@@ -183,12 +176,10 @@ static int seg_level1(kmu_counter *c, SegRun *run, uint64_t bases_ready) {
     if (r.launch) {
         PartPlan pl = run->pl;
         pl.steps_per_unit = (uint32_t) ((r.n_new + run->sp.units1 - 1) / run->sp.units1);
-        KernelTimer tm(ctx, "k_part_scatter1");
-        hipLaunchKernelGGL(k_part_scatter1, dim3(run->sp.units1), dim3(SCATTER_THREADS), seg_lds_bytes(plan_bins1(pl)), ctx->stream, run->ds.bases,
-                           run->ds.offsets, run->ds.n_seq, c->p.kmer_size, pl, (uint64_t *) run->b.A,
-                           SegPlan1{run->sp.cap1, run->steps_done, run->steps_done + r.n_new, (uint32_t *) run->b.ovf, run->d_err,
-                                    (uint32_t *) run->b.state, run->sp.sets, (const uint16_t *) run->novalid});
-        KMU_HIP(ctx, hipGetLastError());
+        KMU_TRY(launch(ctx, "k_part_scatter1", k_part_scatter1, dim3(run->sp.units1), dim3(SCATTER_THREADS), seg_lds_bytes(plan_bins1(pl)),
+                       run->ds.bases, run->ds.offsets, run->ds.n_seq, c->p.kmer_size, pl, (uint64_t *) run->b.A, SegPlan1{run->sp.cap1,
+                       run->steps_done, run->steps_done + r.n_new, (uint32_t *) run->b.ovf, run->d_err, (uint32_t *) run->b.state, run->sp.sets,
+                       (const uint16_t *) run->novalid}));
     }
     run->steps_done += r.n_new;
     if (r.last) {
@@ -216,18 +207,16 @@ int seg_partitioned_add_kmers(kmu_counter *c, const uint64_t *d_kmers, uint64_t 
     void *b0;
     KMU_TRY(seg_buffers(ctx, pl, sp, n, false, &b));
     KMU_TRY(dev_buf(ctx, "arr.bounds0", 16, &b0));
-    hipLaunchKernelGGL(k_fill_linear, dim3(1), dim3(256), 0, ctx->stream, (uint64_t *) b0, (uint64_t) 2, n);
+    KMU_TRY(launch(ctx, nullptr, k_fill_linear, dim3(1), dim3(256), 0, (uint64_t *) b0, (uint64_t) 2, n));
     const ArrPlan ap1{plan_digit1(pl), bins1, 1u, sp.units1, 0u, 0u, 0u, sp.sets};
     if (recs) {
-        KernelTimer tm(ctx, "k_smer_scatter1");
-        hipLaunchKernelGGL(k_smer_scatter1, dim3(sp.units1), dim3(SCATTER_THREADS), seg_lds_bytes(bins1), ctx->stream, (const uint32_t *) recs, n_rec,
-                           c->p.kmer_size, ap1, (uint64_t *) b.A, sp.cap1, (uint32_t *) b.ovf, (uint32_t *) b.state);
+        KMU_TRY(launch(ctx, "k_smer_scatter1", k_smer_scatter1, dim3(sp.units1), dim3(SCATTER_THREADS), seg_lds_bytes(bins1), (const uint32_t *) recs,
+                       n_rec, c->p.kmer_size, ap1, (uint64_t *) b.A, sp.cap1, (uint32_t *) b.ovf, (uint32_t *) b.state));
     } else {
-        KernelTimer tm(ctx, "k_arr_scatter");
-        hipLaunchKernelGGL((k_arr_scatter_seg<IT_KEY_TO_HASH, false>), dim3(sp.units1), dim3(SCATTER_THREADS), seg_lds_bytes(bins1), ctx->stream, d_kmers,
-                           (const uint64_t *) b0, ap1, (uint64_t *) b.A, sp.cap1, (uint32_t *) b.ovf, (uint32_t *) b.state, (const uint32_t *) nullptr);
+        KMU_TRY(launch(ctx, "k_arr_scatter", k_arr_scatter_seg<IT_KEY_TO_HASH, false>, dim3(sp.units1), dim3(SCATTER_THREADS), seg_lds_bytes(bins1),
+                       d_kmers, (const uint64_t *) b0, ap1, (uint64_t *) b.A, sp.cap1, (uint32_t *) b.ovf, (uint32_t *) b.state,
+                       (const uint32_t *) nullptr));
     }
-    KMU_HIP(ctx, hipGetLastError());
     KMU_TRY(seg_tails(ctx, pl, sp, b));
     return seg_level2_build(c, pl, sp, b, d_err, taken);
 }
@@ -251,30 +240,22 @@ static int reads_census(kmu_counter *c, const DevSeqs &ds, uint32_t *d_err, cons
     KMU_TRY(dev_buf(ctx, "cnt.binstart1", (size_t) (bins1 + 1) * 8, &op->binstart1));
     // (the two words behind the histogram are the sample's counter: a table's digits touch only lh[0 .. bins1))
     const size_t lds = ((size_t) bins1 + 2) * 4 + (sa.list ? 16 + (size_t) SAMPLE_LDS * 8 : 0);
-    {
-        KernelTimer tm(ctx, "k_part_hist1");
-        hipLaunchKernelGGL(k_part_hist1, dim3(pl.units1), dim3(256), lds, ctx->stream, ds.bases, ds.offsets, ds.n_seq, c->p.kmer_size, pl,
-                           (uint32_t *) op->hist1, d_err, sa);
-    }
+    KMU_TRY(launch(ctx, "k_part_hist1", k_part_hist1, dim3(pl.units1), dim3(256), lds, ds.bases, ds.offsets, ds.n_seq, c->p.kmer_size, pl,
+                   (uint32_t *) op->hist1, d_err, sa));
     {
         KernelTimer tm(ctx, "k_part_scan1");
-        hipLaunchKernelGGL(k_part_scan1a, dim3(bins1), dim3(256), 0, ctx->stream, (const uint32_t *) op->hist1, pl, (uint64_t *) op->offs1,
-                           (uint64_t *) op->tot1);
-        hipLaunchKernelGGL(k_part_scan1b, dim3(1), dim3(256), 0, ctx->stream, (const uint64_t *) op->tot1, pl, (uint64_t *) op->binstart1);
+        KMU_TRY(launch(ctx, nullptr, k_part_scan1a, dim3(bins1), dim3(256), 0, (const uint32_t *) op->hist1, pl, (uint64_t *) op->offs1,
+                       (uint64_t *) op->tot1));
+        KMU_TRY(launch(ctx, nullptr, k_part_scan1b, dim3(1), dim3(256), 0, (const uint64_t *) op->tot1, pl, (uint64_t *) op->binstart1));
     }
-    KMU_HIP(ctx, hipGetLastError());
     return KMU_OK;
 }
 // second half: every unit scatters its k-mers into its private ranges of `out` (bin b at op.binstart1[b])
 static int reads_scatter_exact(kmu_counter *c, const DevSeqs &ds, const OwnerPlan &op, uint64_t *out) {
     kmu_ctx *ctx = c->ctx;
     KMU_TRY(scatter_attrs(ctx));
-    {
-        KernelTimer tm(ctx, "k_part_scatter1");
-        hipLaunchKernelGGL(k_part_scatter1_exact, dim3(op.pl.units1), dim3(SCATTER_THREADS), scatter_lds_bytes(plan_bins1(op.pl)), ctx->stream,
-                           ds.bases, ds.offsets, ds.n_seq, c->p.kmer_size, op.pl, (const uint64_t *) op.offs1, (const uint64_t *) op.binstart1, out);
-    }
-    KMU_HIP(ctx, hipGetLastError());
+    KMU_TRY(launch(ctx, "k_part_scatter1", k_part_scatter1_exact, dim3(op.pl.units1), dim3(SCATTER_THREADS), scatter_lds_bytes(plan_bins1(op.pl)),
+                   ds.bases, ds.offsets, ds.n_seq, c->p.kmer_size, op.pl, (const uint64_t *) op.offs1, (const uint64_t *) op.binstart1, out));
     return KMU_OK;
 }
 
@@ -288,31 +269,23 @@ static int arr_level_exact(kmu_ctx *ctx, int it, const ArrPlan &ap, const ArrScr
     KMU_TRY(scatter_attrs(ctx));
     const uint32_t units = ap.nparts * ap.chunks;
     const size_t n_out = (size_t) ap.nparts * ap.bins;
-    void *hist, *offs, *outb, *tot;
-    KMU_TRY(dev_buf(ctx, names.tot, n_out * 8, &tot));
-    KMU_TRY(dev_buf(ctx, names.hist, (size_t) units * ap.bins * 4, &hist));
-    KMU_TRY(dev_buf(ctx, names.offs, (size_t) units * ap.bins * 8, &offs));
-    KMU_TRY(dev_buf(ctx, names.bounds, (n_out + 1) * 8, &outb));
-    {
-        KernelTimer tm(ctx, "k_arr_hist");
-        const auto kern = it == IT_HASH ? k_arr_hist<IT_HASH> : k_arr_hist<IT_KEY>;
-        hipLaunchKernelGGL(kern, dim3(units), dim3(256), ap.bins * 4, ctx->stream, in, bounds, ap, (uint32_t *) hist);
-    }
+    uint64_t *outb, *offs, *tot;
+    uint32_t *hist;
+    KMU_TRY(dev_array(ctx, names.tot, n_out, &tot));
+    KMU_TRY(dev_array(ctx, names.hist, (size_t) units * ap.bins, &hist));
+    KMU_TRY(dev_array(ctx, names.offs, (size_t) units * ap.bins, &offs));
+    KMU_TRY(dev_array(ctx, names.bounds, n_out + 1, &outb));
+    KMU_TRY(launch(ctx, "k_arr_hist", it == IT_HASH ? k_arr_hist<IT_HASH> : k_arr_hist<IT_KEY>, dim3(units), dim3(256), ap.bins * 4, in, bounds, ap,
+                   hist));
     {
         KernelTimer tm(ctx, "k_arr_scan");
         const uint32_t T = std::min<uint32_t>(256u, 1u << (31 - __builtin_clz(std::max<uint32_t>(1u, ap.chunks)))), per_wg = 256u / T;
-        hipLaunchKernelGGL(k_arr_scan_a, dim3(ap.nparts * ((ap.bins + per_wg - 1) / per_wg)), dim3(256), 0, ctx->stream, (const uint32_t *) hist, ap, T,
-                           (uint64_t *) offs, (uint64_t *) tot);
-        hipLaunchKernelGGL(k_arr_scan_b, dim3(ap.nparts), dim3(256), 0, ctx->stream, (const uint64_t *) tot, bounds, ap, (uint64_t *) outb);
+        KMU_TRY(launch(ctx, nullptr, k_arr_scan_a, dim3(ap.nparts * ((ap.bins + per_wg - 1) / per_wg)), dim3(256), 0, hist, ap, T, offs, tot));
+        KMU_TRY(launch(ctx, nullptr, k_arr_scan_b, dim3(ap.nparts), dim3(256), 0, tot, bounds, ap, outb));
     }
-    {
-        KernelTimer tm(ctx, "k_arr_scatter");
-        const auto kern = it == IT_HASH ? k_arr_scatter_exact<IT_HASH> : it == IT_KEY ? k_arr_scatter_exact<IT_KEY> : k_arr_scatter_exact<IT_KEY_TO_HASH>;
-        hipLaunchKernelGGL(kern, dim3(units), dim3(SCATTER_THREADS), scatter_lds_bytes(ap.bins), ctx->stream, in, bounds, ap, (const uint64_t *) offs,
-                           (const uint64_t *) outb, out);
-    }
-    KMU_HIP(ctx, hipGetLastError());
-    *outbounds = (const uint64_t *) outb;
+    const auto scatter = it == IT_HASH ? k_arr_scatter_exact<IT_HASH> : it == IT_KEY ? k_arr_scatter_exact<IT_KEY> : k_arr_scatter_exact<IT_KEY_TO_HASH>;
+    KMU_TRY(launch(ctx, "k_arr_scatter", scatter, dim3(units), dim3(SCATTER_THREADS), scatter_lds_bytes(ap.bins), in, bounds, ap, offs, outb, out));
+    *outbounds = outb;
     return KMU_OK;
 }
 // the radix-partitioned build over device-resident ASCII reads
@@ -335,17 +308,17 @@ int partitioned_add(kmu_counter *c, const DevSeqs &ds, uint64_t total_bases, uin
     // (total_bases == 0 used to divide by zero here and is now one unit of one step; no caller brings it this far: no change of behaviour)
     plan_units(ctx, total_bases, &pl);
     pl.chunks2 = two ? std::max<uint32_t>(1u, 16384u / bins1) : 1u;
-    void *A, *B;
-    KMU_TRY(dev_buf(ctx, "cnt.partA", total_bases * 8 + 64, &A));
+    uint64_t *B, *A;
+    KMU_TRY(dev_array(ctx, "cnt.partA", total_bases + 8, &A));
     KMU_TRY(reads_census(c, ds, d_err, SampleArgs{nullptr, nullptr, 0u, 0u}, &l1));
-    KMU_TRY(reads_scatter_exact(c, ds, l1, (uint64_t *) A));
-    if (!two) return launch_build<IT_HASH>(c, (const uint64_t *) A, (const uint64_t *) l1.binstart1, d_err);
+    KMU_TRY(reads_scatter_exact(c, ds, l1, A));
+    if (!two) return launch_build<IT_HASH>(c, A, (const uint64_t *) l1.binstart1, d_err);
     const uint64_t *leafstart;
     const ArrPlan ap{plan_digit2(pl), pl.n2, bins1, pl.chunks2, 0u, 0u, 0u, 0u};
-    KMU_TRY(dev_buf(ctx, "cnt.partB", total_bases * 8 + 64, &B));
-    KMU_TRY(arr_level_exact(ctx, IT_HASH, ap, ArrScratch{"cnt.tot2", "cnt.hist2", "cnt.offs2", "cnt.leafstart"}, (const uint64_t *) A,
-                            (const uint64_t *) l1.binstart1, (uint64_t *) B, &leafstart));
-    return launch_build<IT_HASH>(c, (const uint64_t *) B, leafstart, d_err);
+    KMU_TRY(dev_array(ctx, "cnt.partB", total_bases + 8, &B));
+    KMU_TRY(arr_level_exact(ctx, IT_HASH, ap, ArrScratch{"cnt.tot2", "cnt.hist2", "cnt.offs2", "cnt.leafstart"}, A,
+                            (const uint64_t *) l1.binstart1, B, &leafstart));
+    return launch_build<IT_HASH>(c, B, leafstart, d_err);
 }
 
 // Partition a device array of u64 keys by the digits of `pl` into its 2^b1 * n2 leaves (exact levels).  Returns the partitioned
@@ -371,10 +344,10 @@ static int partition_by_plan(kmu_ctx *ctx, const uint64_t *in, uint64_t n, const
         const uint32_t chunks = level == 0 ? (uint32_t) std::min<uint64_t>(std::max<uint64_t>(1, n / 65536), 16384)
                                            : std::max<uint32_t>(1u, 16384u / nparts);
         const ArrPlan ap{by_group ? plan_digit1(pl) : plan_digit2(pl), bins, nparts, chunks, 0u, 0u, 0u, 0u};
-        void *out;
-        KMU_TRY(dev_buf(ctx, level == 0 ? "cnt.partA" : "cnt.partB", n * 8 + 64, &out));
-        KMU_TRY(arr_level_exact(ctx, it, ap, names[level], items, bounds, (uint64_t *) out, &bounds));
-        items = (const uint64_t *) out;
+        uint64_t *out;
+        KMU_TRY(dev_array(ctx, level == 0 ? "cnt.partA" : "cnt.partB", n + 8, &out));
+        KMU_TRY(arr_level_exact(ctx, it, ap, names[level], items, bounds, out, &bounds));
+        items = out;
         nparts *= bins;
         if (hashed_out) it = IT_HASH;
     }
@@ -423,9 +396,9 @@ int owner_census(kmu_counter *c, const DevSeqs &ds, uint64_t total_bases, uint32
     return reads_census(c, ds, d_err, sa, op);
 }
 int owner_scatter(kmu_counter *c, const DevSeqs &ds, uint64_t total_bases, const OwnerPlan &op, uint64_t **dev_out) {
-    void *out;
-    KMU_TRY(dev_buf(c->ctx, "cnt.partB", total_bases * 8 + 64, &out));
-    *dev_out = (uint64_t *) out;
+    uint64_t *out;
+    KMU_TRY(dev_array(c->ctx, "cnt.partB", total_bases + 8, &out));
+    *dev_out = out;
     return reads_scatter_exact(c, ds, op, *dev_out);
 }
 // distinct keys of a device list of n sampled k-mers (scratch: "cnt.sample_tab"; d_word: a device word for the count)
@@ -438,12 +411,8 @@ int sample_distinct(kmu_ctx *ctx, const uint64_t *d_list, uint32_t n, uint32_t *
     KMU_TRY(dev_buf(ctx, "cnt.sample_tab", ((size_t) 8 << tbits) + 64, &stab));
     KMU_HIP(ctx, hipMemsetAsync(stab, 0xFF, (size_t) 8 << tbits, ctx->stream));
     KMU_HIP(ctx, hipMemsetAsync(d_word, 0, 4, ctx->stream));
-    {
-        KernelTimer tm(ctx, "k_sample_distinct");
-        hipLaunchKernelGGL(k_sample_distinct, dim3(grid_for(ctx, n, 256)), dim3(256), 0, ctx->stream, d_list, n, (uint64_t *) stab,
-                           (uint32_t) ((1u << tbits) - 1u), d_word);
-    }
-    KMU_HIP(ctx, hipGetLastError());
+    KMU_TRY(launch(ctx, "k_sample_distinct", k_sample_distinct, dim3(grid_for(ctx, n, 256)), dim3(256), 0, d_list, n, (uint64_t *) stab,
+                   (uint32_t) ((1u << tbits) - 1u), d_word));
     KMU_HIP(ctx, hipMemcpyAsync(distinct_out, d_word, 4, hipMemcpyDeviceToHost, ctx->stream));
     KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return KMU_OK;
@@ -452,24 +421,25 @@ int sample_distinct(kmu_ctx *ctx, const uint64_t *d_list, uint32_t n, uint32_t *
 int sample_ratio(kmu_counter *c, const DevSeqs &ds, uint64_t total_bases, uint32_t *d_err, double *ratio_out) {
     kmu_ctx *ctx = c->ctx;
     *ratio_out = 0.0;
-    void *slist, *sn;
+    uint64_t *slist;
+    void *sn;
     const uint64_t units = unit_split(flat_wave_steps(total_bases), (uint64_t) ctx->num_cus * 8).asked; // (the shift goes by the count before re-rounding)
     const uint64_t kmers_per_unit = (total_bases + units - 1) / units;
     uint32_t shift = 0; // ~1024 sampled k-mers per workgroup (its LDS list holds 4096)
     while (shift < 24 && (kmers_per_unit >> shift) > 1024) shift++;
     const uint32_t cap = (uint32_t) std::min<uint64_t>(units * SAMPLE_LDS, 1u << 26);
-    KMU_TRY(dev_buf(ctx, "cnt.sample", (size_t) cap * 8 + 64, &slist));
+    KMU_TRY(dev_array(ctx, "cnt.sample", (size_t) cap + 8, &slist));
     KMU_TRY(dev_buf(ctx, "cnt.sample_n", 64, &sn));
     KMU_HIP(ctx, hipMemsetAsync(sn, 0, 64, ctx->stream));
     OwnerPlan op;
-    KMU_TRY(owner_census(c, ds, total_bases, 1, d_err, &op, SampleArgs{(uint64_t *) slist, (uint32_t *) sn, cap, shift}));
+    KMU_TRY(owner_census(c, ds, total_bases, 1, d_err, &op, SampleArgs{slist, (uint32_t *) sn, cap, shift}));
     uint32_t h_sn[2] = {0, 0};
     KMU_HIP(ctx, hipMemcpyAsync(h_sn, sn, 8, hipMemcpyDeviceToHost, ctx->stream));
     KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
     const uint32_t n_s = std::min(h_sn[0], cap);
     if (!n_s || h_sn[1]) return KMU_OK; // nothing sampled, or a truncated sample: no estimate
     uint32_t d_s = 0;
-    KMU_TRY(sample_distinct(ctx, (const uint64_t *) slist, n_s, (uint32_t *) sn + 2, &d_s));
+    KMU_TRY(sample_distinct(ctx, slist, n_s, (uint32_t *) sn + 2, &d_s));
     if (d_s) *ratio_out = (double) n_s / (double) d_s;
     return KMU_OK;
 }

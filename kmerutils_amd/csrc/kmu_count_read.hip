@@ -410,24 +410,17 @@ struct ProfileCall {
 static int launch_profile(const ProfileCall &pc, uint64_t st0, uint64_t st1, uint64_t lo, uint64_t hi, uint16_t *counts, uint64_t cbase) {
     kmu_ctx *ctx = pc.c->ctx;
     if (st1 <= st0) return KMU_OK;
-    const int grid = (int) std::min<uint64_t>((st1 - st0 + 3) / 4, (uint64_t) ctx->num_cus * 8);
-    KernelTimer tm(ctx, "k_count_profile");
-    hipLaunchKernelGGL(k_count_profile, dim3(grid), dim3(256), 0, ctx->stream, pc.ds->bases, pc.ds->offsets, pc.ds->n_seq,
-                       pc.c->p.kmer_size, table_of(pc.c), pc.empty, max_count(pc.c), st0, st1, lo, hi, counts, cbase,
-                       (int) (((uintptr_t) counts & 15u) == 0), pc.d_err);
-    KMU_HIP(ctx, hipGetLastError());
-    return KMU_OK;
+    const int grid = grid_for(ctx, st1 - st0, 4);
+    return launch(ctx, "k_count_profile", k_count_profile, dim3(grid), dim3(256), 0, pc.ds->bases, pc.ds->offsets, pc.ds->n_seq, pc.c->p.kmer_size,
+                  table_of(pc.c), pc.empty, max_count(pc.c), st0, st1, lo, hi, counts, cbase, (int) (((uintptr_t) counts & 15u) == 0), pc.d_err);
 }
 
 static int launch_stats(const ProfileCall &pc, const uint16_t *counts, uint64_t cbase, uint32_t r0, uint32_t r1, kmu_read_abundance *d_stats) {
     kmu_ctx *ctx = pc.c->ctx;
     if (r1 <= r0) return KMU_OK;
-    const int grid = (int) std::min<uint64_t>(((uint64_t) (r1 - r0) + 63) / 64, (uint64_t) ctx->num_cus * 8);
-    KernelTimer tm(ctx, "k_profile_stats");
-    hipLaunchKernelGGL(k_profile_stats, dim3(grid), dim3(256), 0, ctx->stream, counts, cbase, pc.ds->offsets, r0, r1, pc.c->p.kmer_size,
-                       pc.solid_min, (int) (max_count(pc.c) > 255u), pc.short_max, d_stats);
-    KMU_HIP(ctx, hipGetLastError());
-    return KMU_OK;
+    const int grid = grid_for(ctx, r1 - r0, 64);
+    return launch(ctx, "k_profile_stats", k_profile_stats, dim3(grid), dim3(256), 0, counts, cbase, pc.ds->offsets, r0, r1, pc.c->p.kmer_size,
+                  pc.solid_min, (int) (max_count(pc.c) > 255u), pc.short_max, d_stats);
 }
 
 // statistics alone, the reads longer in all than the workspace: chunk by chunk
@@ -439,8 +432,7 @@ static int stats_chunked(const ProfileCall &pc, uint64_t total_bases, uint64_t c
     KMU_TRY(dev_buf(ctx, "prof.plan", 16 + (size_t) max_ch * sizeof(ProfChunk), &q));
     uint64_t *d_head = (uint64_t *) q;
     ProfChunk *d_plan = (ProfChunk *) (d_head + 2);
-    hipLaunchKernelGGL(k_profile_plan, dim3(1), dim3(64), 0, ctx->stream, pc.ds->offsets, pc.ds->n_seq, chunk, (uint32_t) max_ch, d_head, d_plan);
-    KMU_HIP(ctx, hipGetLastError());
+    KMU_TRY(launch(ctx, nullptr, k_profile_plan, dim3(1), dim3(64), 0, pc.ds->offsets, pc.ds->n_seq, chunk, (uint32_t) max_ch, d_head, d_plan));
     uint64_t head[2] = {0, 0};
     KMU_HIP(ctx, hipMemcpyAsync(head, d_head, 16, hipMemcpyDeviceToHost, ctx->stream));
     KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -457,9 +449,10 @@ static int stats_chunked(const ProfileCall &pc, uint64_t total_bases, uint64_t c
             continue;
         }
         // one read longer than the workspace: its counts pass through it a sub-range at a time
-        void *qa, *qh;
+        uint32_t *qh;
+        void *qa;
         KMU_TRY(dev_buf(ctx, "prof.bigacc", 64, &qa));
-        KMU_TRY(dev_buf(ctx, "prof.bighist", 65536 * 4, &qh));
+        KMU_TRY(dev_array(ctx, "prof.bighist", 65536, &qh));
         unsigned long long *acc = (unsigned long long *) qa;
         KMU_HIP(ctx, hipMemsetAsync(acc, 0, 64, ctx->stream));
         KMU_HIP(ctx, hipMemsetAsync(acc + 3, 0xFF, 8, ctx->stream));
@@ -470,14 +463,10 @@ static int stats_chunked(const ProfileCall &pc, uint64_t total_bases, uint64_t c
             const uint64_t s1 = std::min(s + steps, (ch.e + 1023) / 1024);
             KMU_TRY(launch_profile(pc, s, s1, ch.b, ch.e, ws, s * 1024));
             const uint64_t p0 = std::max(ch.b, s * 1024), p1 = std::min(pend, s1 * 1024);
-            KernelTimer tm(ctx, "k_profile_big_accum");
-            hipLaunchKernelGGL(k_profile_big_accum, dim3(grid_for(ctx, p1 - p0, 4096)), dim3(256), 0, ctx->stream, ws + (p0 - s * 1024), p1 - p0,
-                               pc.solid_min, acc, (uint32_t *) qh);
-            KMU_HIP(ctx, hipGetLastError());
+            KMU_TRY(launch(ctx, "k_profile_big_accum", k_profile_big_accum, dim3(grid_for(ctx, p1 - p0, 4096)), dim3(256), 0, ws + (p0 - s * 1024),
+                           p1 - p0, pc.solid_min, acc, qh));
         }
-        KernelTimer tm(ctx, "k_profile_big_finish");
-        hipLaunchKernelGGL(k_profile_big_finish, dim3(1), dim3(256), 0, ctx->stream, acc, (const uint32_t *) qh, (uint32_t) (pend - ch.b), d_stats + ch.r0);
-        KMU_HIP(ctx, hipGetLastError());
+        KMU_TRY(launch(ctx, "k_profile_big_finish", k_profile_big_finish, dim3(1), dim3(256), 0, acc, qh, (uint32_t) (pend - ch.b), d_stats + ch.r0));
     }
     return KMU_OK;
 }
@@ -493,18 +482,12 @@ int kmu_count_histogram(kmu_counter *c, uint64_t *hist_out, uint32_t n_bins, int
     kmu_ctx *ctx = c->ctx;
     KMU_HIP(ctx, hipSetDevice(ctx->device));
     uint64_t *d_h = hist_out;
-    if (mem == KMU_MEM_HOST) {
-        void *q;
-        KMU_TRY(dev_buf(ctx, "cnt.hist", (size_t) n_bins * 8, &q));
-        d_h = (uint64_t *) q;
-    }
+    if (mem == KMU_MEM_HOST) KMU_TRY(dev_array(ctx, "cnt.hist", (size_t) n_bins, &d_h));
     KMU_HIP(ctx, hipMemsetAsync(d_h, 0, (size_t) n_bins * 8, ctx->stream));
     if (!c->empty) { // (an empty counter, or one whose table waits for its first add: nothing is launched on the table)
         KMU_TRY(materialize(c));
-        KernelTimer tm(ctx, "k_count_hist");
-        hipLaunchKernelGGL(k_count_hist, dim3(grid_for(ctx, c->nslots, 1024)), dim3(256), 0, ctx->stream, table_of(c), c->nslots,
-                           max_count(c), n_bins - 1, (unsigned long long *) d_h);
-        KMU_HIP(ctx, hipGetLastError());
+        KMU_TRY(launch(ctx, "k_count_hist", k_count_hist, dim3(grid_for(ctx, c->nslots, 1024)), dim3(256), 0, table_of(c), c->nslots, max_count(c),
+                       n_bins - 1, (unsigned long long *) d_h));
     }
     if (mem == KMU_MEM_HOST) KMU_HIP(ctx, hipMemcpyAsync(hist_out, d_h, (size_t) n_bins * 8, hipMemcpyDeviceToHost, ctx->stream));
     return finish_call(ctx, mem);
@@ -533,18 +516,14 @@ int kmu_count_read_profile(kmu_counter *c, const uint8_t *bases, const uint64_t 
     if (mem == KMU_MEM_DEVICE && total_bases >= (1ull << 32)) {
         unsigned long long longest = 0;
         KMU_HIP(ctx, hipMemsetAsync(c->scalars, 0, 8, ctx->stream));
-        hipLaunchKernelGGL(k_profile_maxlen, dim3(grid_for(ctx, n_seq, 256)), dim3(256), 0, ctx->stream, ds.offsets, n_seq, (unsigned long long *) c->scalars);
-        KMU_HIP(ctx, hipGetLastError());
+        KMU_TRY(launch(ctx, nullptr, k_profile_maxlen, dim3(grid_for(ctx, n_seq, 256)), dim3(256), 0, ds.offsets, n_seq,
+                       (unsigned long long *) c->scalars));
         KMU_HIP(ctx, hipMemcpyAsync(&longest, c->scalars, 8, hipMemcpyDeviceToHost, ctx->stream));
         KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
         if (longest >= (1ull << 32)) return fail(ctx, KMU_E_UNSUPPORTED, "a sequence has 2^32 bases or more");
     }
     kmu_read_abundance *d_stats = stats_out;
-    if (stats_out && mem == KMU_MEM_HOST) {
-        void *q;
-        KMU_TRY(dev_buf(ctx, "prof.stats", (size_t) n_seq * sizeof(kmu_read_abundance), &q));
-        d_stats = (kmu_read_abundance *) q;
-    }
+    if (stats_out && mem == KMU_MEM_HOST) KMU_TRY(dev_array(ctx, "prof.stats", (size_t) n_seq, &d_stats));
     if (total_bases == 0) { // nothing but empty sequences: no k-mer anywhere
         if (stats_out) {
             KMU_HIP(ctx, hipMemsetAsync(d_stats, 0, (size_t) n_seq * sizeof(kmu_read_abundance), ctx->stream));
@@ -567,9 +546,7 @@ int kmu_count_read_profile(kmu_counter *c, const uint8_t *bases, const uint64_t 
         uint16_t *d_counts;
         if (counts_out && mem == KMU_MEM_DEVICE) d_counts = counts_out + shift;
         else {
-            void *q;
-            KMU_TRY(dev_buf(ctx, "prof.counts", ((size_t) total_bases + 64) * 2, &q));
-            d_counts = (uint16_t *) q;
+            KMU_TRY(dev_array(ctx, "prof.counts", (size_t) total_bases + 64, &d_counts));
             // host arrays come back whole: the positions that start no k-mer (the last k - 1 of every sequence) as zeros
             if (counts_out) KMU_HIP(ctx, hipMemsetAsync(d_counts, 0, (size_t) total_bases * 2, ctx->stream));
         }

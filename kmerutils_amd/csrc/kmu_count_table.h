@@ -265,10 +265,6 @@ inline CountTable table_of(const kmu_counter *c) {
     return t;
 }
 inline uint32_t max_count(const kmu_counter *c) { return c->p.counter_bits == 8 ? 255u : 65535u; }
-inline int grid_for(const kmu_ctx *ctx, uint64_t n, int per_block) {
-    const uint64_t blocks = (n + per_block - 1) / per_block, cap = (uint64_t) ctx->num_cus * 8;
-    return (int) (blocks < 1 ? 1 : blocks < cap ? blocks : cap);
-}
 // kmer_owner's mode for the counter's own owner function (distributed counters)
 inline int owner_mode_of(const kmu_counter *c) { return c->okind == 1 ? owner_mode_smer(c->p.kmer_size) : (kmer_val_bytes(c->p.kmer_type) == 4 ? 1 : 0); }
 

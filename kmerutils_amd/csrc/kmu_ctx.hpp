@@ -1,4 +1,11 @@
-// kmu_ctx.hpp -- host-side context of libkmu: device, stream, error text, workspace arena, per-kernel timing.
+// kmu_ctx.hpp -- host-side context of libkmu: device, stream, error text, workspace arena, per-kernel timing, and the three steps
+// every host driver is written in:
+//   dev_array<T>(ctx, name, count, &p)  workspace `name` as `count` elements of T (dev_buf: the same in bytes, for padded or mixed buffers)
+//   grid_for(ctx, n, per_block, per_cu) ceil(n / per_block) workgroups, at least 1, at most per_cu per CU (the rest by grid stride)
+//   launch(ctx, name, kernel, grid, block, lds, args...)  the ONLY kernel launch of the library: on ctx->stream, timed as `name`
+//                                       (nullptr: not timed), hipGetLastError checked behind every launch
+// A launch that was never timed stays untimed (profile_get reads at most 32 names and tests read the set of names as route probes);
+// a timer that spans two kernels stays ONE KernelTimer scope around two launch(ctx, nullptr, ...).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -103,6 +110,13 @@ inline int dev_buf(kmu_ctx *ctx, const char *name, size_t bytes, void **out) {
     *out = b.p;
     return KMU_OK;
 }
+// dev_buf as `count` elements of T
+template <class T> inline int dev_array(kmu_ctx *ctx, const char *name, size_t count, T **out) {
+    void *p;
+    KMU_TRY(dev_buf(ctx, name, count * sizeof(T), &p));
+    *out = static_cast<T *>(p);
+    return KMU_OK;
+}
 // a host array of a KMU_MEM_HOST call staged in workspace `name`; a device array (or null) as it is
 inline int stage_to_device(kmu_ctx *ctx, const char *name, const void *p, size_t bytes, int mem, const void **out) {
     if (mem == KMU_MEM_DEVICE || !p) { *out = p; return KMU_OK; }
@@ -129,13 +143,13 @@ inline int host_buf(kmu_ctx *ctx, const char *name, size_t bytes, void **out) {
     return KMU_OK;
 }
 
-// RAII-ish timing scope around one kernel launch (hipEvents on the context stream)
+// RAII-ish timing scope around one kernel launch (hipEvents on the context stream); a null name times nothing
 struct KernelTimer {
     kmu_ctx *ctx;
     hipEvent_t a = nullptr, b = nullptr;
     const char *name;
     KernelTimer(kmu_ctx *c, const char *n) : ctx(c), name(n) {
-        if (!ctx->profiling) return;
+        if (!name || !ctx->profiling) return;
         auto get = [&]() {
             hipEvent_t e;
             if (!ctx->event_pool.empty()) {
@@ -151,11 +165,29 @@ struct KernelTimer {
         (void) hipEventRecord(a, ctx->stream);
     }
     ~KernelTimer() {
-        if (!ctx->profiling) return;
+        if (!name || !ctx->profiling) return;
         (void) hipEventRecord(b, ctx->stream);
         ctx->pending.push_back({name, a, b});
     }
 };
+
+// ceil(n / per_block) workgroups, at least one, at most per_cu per CU
+inline int grid_for(const kmu_ctx *ctx, uint64_t n, int per_block, int per_cu = 8) {
+    const uint64_t blocks = (n + per_block - 1) / per_block, cap = (uint64_t) ctx->num_cus * per_cu;
+    return (int) (blocks < 1 ? 1 : blocks < cap ? blocks : cap);
+}
+
+// one kernel launch on the context's stream: timed as `name` (nullptr: not timed), checked.  The arguments are converted to the
+// kernel's own parameter types, so nullptr and pointers to non-const pass as they are.
+template <class... P, class... A>
+inline int launch(kmu_ctx *ctx, const char *name, void (*kern)(P...), dim3 grid, dim3 block, size_t lds, A &&...args) {
+    {
+        KernelTimer t(ctx, name);
+        hipLaunchKernelGGL(kern, grid, block, lds, ctx->stream, static_cast<P>(args)...);
+    }
+    KMU_HIP(ctx, hipGetLastError());
+    return KMU_OK;
+}
 
 inline void profile_collect(kmu_ctx *ctx) {
     if (ctx->pending.empty()) return;

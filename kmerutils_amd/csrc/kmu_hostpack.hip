@@ -172,13 +172,11 @@ __global__ void __launch_bounds__(256) k_unpack2b(const uint32_t *packed, uint64
     }
 }
 
-int launch_unpack2b(kmu_ctx *ctx, const void *packed_dev, uint64_t n_bases, uint8_t *out_dev, hipStream_t s) {
+int launch_unpack2b(kmu_ctx *ctx, const void *packed_dev, uint64_t n_bases, uint8_t *out_dev) {
     if (!n_bases) return KMU_OK;
     const uint64_t nw = (n_bases + 15) / 16;
-    const int grid = (int) std::min<uint64_t>((nw + 255) / 256, (uint64_t) ctx->num_cus * 16);
-    hipLaunchKernelGGL(k_unpack2b, dim3(grid), dim3(256), 0, s, (const uint32_t *) packed_dev, n_bases, out_dev);
-    KMU_HIP(ctx, hipGetLastError());
-    return KMU_OK;
+    const int grid = grid_for(ctx, nw, 256, 16);
+    return launch(ctx, nullptr, k_unpack2b, dim3(grid), dim3(256), 0, packed_dev, n_bases, out_dev);
 }
 
 } // namespace kmu

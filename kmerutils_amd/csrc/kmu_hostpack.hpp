@@ -26,7 +26,7 @@ class PackPipe {
     Impl *im;
 };
 
-// n_bases bases from packed_dev (4-byte aligned) to ASCII at out_dev (16-byte aligned), on stream s
-int launch_unpack2b(kmu_ctx *ctx, const void *packed_dev, uint64_t n_bases, uint8_t *out_dev, hipStream_t s);
+// n_bases bases from packed_dev (4-byte aligned) to ASCII at out_dev (16-byte aligned), on the context's stream
+int launch_unpack2b(kmu_ctx *ctx, const void *packed_dev, uint64_t n_bases, uint8_t *out_dev);
 
 } // namespace kmu

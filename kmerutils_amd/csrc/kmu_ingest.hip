@@ -330,18 +330,14 @@ using namespace kmu;
 // exclusive scan of n values on the context's stream; out[n] = total
 template <typename T> static int device_scan(kmu_ctx *ctx, const T *in, uint64_t n, uint64_t *out) {
     KernelTimer t(ctx, "k_ing_scan");
-    if (n <= 4 * SCAN_TILE) {
-        hipLaunchKernelGGL(k_ing_scan<T>, dim3(1), dim3(1024), 0, ctx->stream, in, n, out);
-        return KMU_OK;
-    }
+    if (n <= 4 * SCAN_TILE) return launch(ctx, nullptr, k_ing_scan<T>, dim3(1), dim3(1024), 0, in, n, out);
     const uint64_t n_tiles = (n + SCAN_TILE - 1) / SCAN_TILE;
-    void *tsum, *toff;
-    KMU_TRY(dev_buf(ctx, "ing.tsum", (n_tiles + 1) * 8, &tsum));
-    KMU_TRY(dev_buf(ctx, "ing.toff", (n_tiles + 1) * 8, &toff));
-    hipLaunchKernelGGL(k_scan_tile_sums<T>, dim3((uint32_t) n_tiles), dim3(1024), 0, ctx->stream, in, n, (uint64_t *) tsum);
-    hipLaunchKernelGGL(k_ing_scan<uint64_t>, dim3(1), dim3(1024), 0, ctx->stream, (const uint64_t *) tsum, n_tiles, (uint64_t *) toff);
-    hipLaunchKernelGGL(k_scan_tiles<T>, dim3((uint32_t) n_tiles), dim3(1024), 0, ctx->stream, in, n, (const uint64_t *) toff, n_tiles, out);
-    return KMU_OK;
+    uint64_t *toff, *tsum;
+    KMU_TRY(dev_array(ctx, "ing.tsum", n_tiles + 1, &tsum));
+    KMU_TRY(dev_array(ctx, "ing.toff", n_tiles + 1, &toff));
+    KMU_TRY(launch(ctx, nullptr, k_scan_tile_sums<T>, dim3((uint32_t) n_tiles), dim3(1024), 0, in, n, tsum));
+    KMU_TRY(launch(ctx, nullptr, k_ing_scan<uint64_t>, dim3(1), dim3(1024), 0, tsum, n_tiles, toff));
+    return launch(ctx, nullptr, k_scan_tiles<T>, dim3((uint32_t) n_tiles), dim3(1024), 0, in, n, toff, n_tiles, out);
 }
 
 namespace kmu {
@@ -353,25 +349,21 @@ int device_scan_u32(kmu_ctx *ctx, const uint32_t *in, uint64_t n, uint64_t *out)
 static int ingest_filter_copy(kmu_ctx *ctx, const uint8_t *d_text, uint64_t n_text, uint64_t n_records, void *sstart, void *send,
                               void *scal, int mem, uint8_t *bases_out, uint64_t bases_cap, uint64_t *offsets_out,
                               uint64_t offsets_cap, uint32_t *record_index_out, kmu_ingest_info *info) {
-    void *keep, *klen, *rank, *ooff;
-    KMU_TRY(dev_buf(ctx, "ing.keep", (n_records + 1) * 4, &keep));
-    KMU_TRY(dev_buf(ctx, "ing.klen", (n_records + 1) * 8, &klen));
-    KMU_TRY(dev_buf(ctx, "ing.rank", (n_records + 1) * 8, &rank));
-    KMU_TRY(dev_buf(ctx, "ing.ooff", (n_records + 1) * 8, &ooff));
-    const int grid_r = (int) std::min<uint64_t>(std::max<uint64_t>(n_records, 1), (uint64_t) ctx->num_cus * 16);
-    {
-        KernelTimer t(ctx, "k_ing_filter");
-        hipLaunchKernelGGL(k_ing_filter, dim3(grid_r), dim3(256), 0, ctx->stream, d_text, n_text, (const uint64_t *) sstart,
-                           (const uint64_t *) send, n_records, (uint32_t *) keep, (uint64_t *) klen,
-                           (unsigned long long *) scal);
-    }
-    KMU_TRY(device_scan(ctx, (const uint32_t *) keep, n_records, (uint64_t *) rank));
-    KMU_TRY(device_scan(ctx, (const uint64_t *) klen, n_records, (uint64_t *) ooff));
-    KMU_HIP(ctx, hipGetLastError());
+    uint64_t *ooff, *rank, *klen;
+    uint32_t *keep;
+    KMU_TRY(dev_array(ctx, "ing.keep", n_records + 1, &keep));
+    KMU_TRY(dev_array(ctx, "ing.klen", n_records + 1, &klen));
+    KMU_TRY(dev_array(ctx, "ing.rank", n_records + 1, &rank));
+    KMU_TRY(dev_array(ctx, "ing.ooff", n_records + 1, &ooff));
+    const int grid_r = grid_for(ctx, n_records, 1, 16);
+    KMU_TRY(launch(ctx, "k_ing_filter", k_ing_filter, dim3(grid_r), dim3(256), 0, d_text, n_text, (const uint64_t *) sstart, (const uint64_t *) send,
+                   n_records, keep, klen, (unsigned long long *) scal));
+    KMU_TRY(device_scan(ctx, keep, n_records, rank));
+    KMU_TRY(device_scan(ctx, klen, n_records, ooff));
     uint64_t h_scal[8], n_kept = 0, kept_bases = 0;
     KMU_HIP(ctx, hipMemcpyAsync(h_scal, scal, 64, hipMemcpyDeviceToHost, ctx->stream));
-    KMU_HIP(ctx, hipMemcpyAsync(&n_kept, (const uint64_t *) rank + n_records, 8, hipMemcpyDeviceToHost, ctx->stream));
-    KMU_HIP(ctx, hipMemcpyAsync(&kept_bases, (const uint64_t *) ooff + n_records, 8, hipMemcpyDeviceToHost, ctx->stream));
+    KMU_HIP(ctx, hipMemcpyAsync(&n_kept, rank + n_records, 8, hipMemcpyDeviceToHost, ctx->stream));
+    KMU_HIP(ctx, hipMemcpyAsync(&kept_bases, ooff + n_records, 8, hipMemcpyDeviceToHost, ctx->stream));
     KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
     const uint32_t errw = (uint32_t) h_scal[4];
     if (errw & IERR_HEADER) return fail(ctx, KMU_E_BAD_ARG, "invalid record: a header line does not start with '@'");
@@ -394,20 +386,11 @@ static int ingest_filter_copy(kmu_ctx *ctx, const uint8_t *d_text, uint64_t n_te
         void *q;
         KMU_TRY(dev_buf(ctx, "ing.bases", kept_bases + 64, &q));
         d_bases = (uint8_t *) q;
-        KMU_TRY(dev_buf(ctx, "ing.off", (n_kept + 1) * 8, &q));
-        d_off = (uint64_t *) q;
-        if (record_index_out) {
-            KMU_TRY(dev_buf(ctx, "ing.idx", (n_kept + 1) * 4, &q));
-            d_idx = (uint32_t *) q;
-        }
+        KMU_TRY(dev_array(ctx, "ing.off", n_kept + 1, &d_off));
+        if (record_index_out) KMU_TRY(dev_array(ctx, "ing.idx", n_kept + 1, &d_idx));
     }
-    {
-        KernelTimer t(ctx, "k_ing_copy");
-        hipLaunchKernelGGL(k_ing_copy, dim3(grid_r), dim3(256), 0, ctx->stream, d_text, (const uint64_t *) sstart,
-                           (const uint32_t *) keep, (const uint64_t *) klen, (const uint64_t *) rank, (const uint64_t *) ooff,
-                           n_records, d_bases, d_off, d_idx);
-    }
-    KMU_HIP(ctx, hipGetLastError());
+    KMU_TRY(launch(ctx, "k_ing_copy", k_ing_copy, dim3(grid_r), dim3(256), 0, d_text, (const uint64_t *) sstart, keep, klen, rank, ooff, n_records,
+                   d_bases, d_off, d_idx));
     if (mem == KMU_MEM_HOST) {
         KMU_HIP(ctx, hipMemcpyAsync(bases_out, d_bases, kept_bases, hipMemcpyDeviceToHost, ctx->stream));
         KMU_HIP(ctx, hipMemcpyAsync(offsets_out, d_off, (n_kept + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -429,20 +412,19 @@ static int ingest_lines(kmu_ctx *ctx, const uint8_t *text, uint64_t n_bytes, int
         d_text = (const uint8_t *) q;
     }
     const uint64_t n_regions = (n_bytes + ING_REGION - 1) / ING_REGION;
-    void *cnt, *lbase, *scal;
-    KMU_TRY(dev_buf(ctx, "ing.cnt", n_regions * 4, &cnt));
-    KMU_TRY(dev_buf(ctx, "ing.lbase", (n_regions + 1) * 8, &lbase));
+    uint64_t *lbase;
+    uint32_t *cnt;
+    void *scal;
+    KMU_TRY(dev_array(ctx, "ing.cnt", n_regions, &cnt));
+    KMU_TRY(dev_array(ctx, "ing.lbase", n_regions + 1, &lbase));
     KMU_TRY(dev_buf(ctx, "ing.scal", 64, &scal)); // [0..2] totals, [4] error word
     KMU_HIP(ctx, hipMemsetAsync(scal, 0, 64, ctx->stream));
-    const int grid_w = (int) std::min<uint64_t>((n_regions + 3) / 4, (uint64_t) ctx->num_cus * 8);
-    {
-        KernelTimer t(ctx, "k_ing_count");
-        hipLaunchKernelGGL(k_ing_count, dim3(grid_w), dim3(256), 0, ctx->stream, d_text, n_bytes, n_regions, (uint32_t *) cnt);
-    }
-    KMU_TRY(device_scan(ctx, (const uint32_t *) cnt, n_regions, (uint64_t *) lbase));
+    const int grid_w = grid_for(ctx, n_regions, 4);
+    KMU_TRY(launch(ctx, "k_ing_count", k_ing_count, dim3(grid_w), dim3(256), 0, d_text, n_bytes, n_regions, cnt));
+    KMU_TRY(device_scan(ctx, cnt, n_regions, lbase));
     uint64_t total_nl = 0;
     uint8_t last = 0;
-    KMU_HIP(ctx, hipMemcpyAsync(&total_nl, (const uint64_t *) lbase + n_regions, 8, hipMemcpyDeviceToHost, ctx->stream));
+    KMU_HIP(ctx, hipMemcpyAsync(&total_nl, lbase + n_regions, 8, hipMemcpyDeviceToHost, ctx->stream));
     KMU_HIP(ctx, hipMemcpyAsync(&last, d_text + n_bytes - 1, 1, hipMemcpyDeviceToHost, ctx->stream));
     KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
     *d_text_out = d_text;
@@ -481,14 +463,11 @@ extern "C" int kmu_ingest_fastq(kmu_ctx *ctx, const uint8_t *text, uint64_t n_by
                     (unsigned long long) n_lines);
     const uint64_t n_records = n_lines / 4;
     if (n_records > 0xFFFFFFFFull) return fail(ctx, KMU_E_UNSUPPORTED, "more than 2^32 records in one call");
-    void *sstart, *send;
-    KMU_TRY(dev_buf(ctx, "ing.sstart", (n_records + 1) * 8, &sstart));
-    KMU_TRY(dev_buf(ctx, "ing.send", (n_records + 1) * 8, &send));
-    {
-        KernelTimer t(ctx, "k_ing_lines");
-        hipLaunchKernelGGL(k_ing_lines, dim3(grid_w), dim3(256), 0, ctx->stream, d_text, n_bytes, n_regions,
-                           (const uint64_t *) lbase, n_records, (uint64_t *) sstart, (uint64_t *) send, (uint32_t *) scal + 8);
-    }
+    uint64_t *send, *sstart;
+    KMU_TRY(dev_array(ctx, "ing.sstart", n_records + 1, &sstart));
+    KMU_TRY(dev_array(ctx, "ing.send", n_records + 1, &send));
+    KMU_TRY(launch(ctx, "k_ing_lines", k_ing_lines, dim3(grid_w), dim3(256), 0, d_text, n_bytes, n_regions, (const uint64_t *) lbase, n_records,
+                   sstart, send, (uint32_t *) scal + 8));
     return ingest_filter_copy(ctx, d_text, n_bytes, n_records, sstart, send, scal, mem, bases_out, bases_cap, offsets_out,
                               offsets_cap, record_index_out, info);
 }
@@ -505,42 +484,41 @@ extern "C" int kmu_ingest_fasta(kmu_ctx *ctx, const uint8_t *text, uint64_t n_by
     uint64_t n_regions, n_lines;
     int grid_w;
     KMU_TRY(ingest_lines(ctx, text, n_bytes, mem, &d_text, &lbase, &scal, &n_regions, &grid_w, &n_lines));
-    void *lstart, *lend, *hdr, *slen, *hrank, *spos;
-    KMU_TRY(dev_buf(ctx, "ing.lstart", (n_lines + 1) * 8, &lstart));
-    KMU_TRY(dev_buf(ctx, "ing.lend", (n_lines + 1) * 8, &lend));
-    KMU_TRY(dev_buf(ctx, "ing.hdr", (n_lines + 1) * 4, &hdr));
-    KMU_TRY(dev_buf(ctx, "ing.slen", (n_lines + 1) * 8, &slen));
-    KMU_TRY(dev_buf(ctx, "ing.hrank", (n_lines + 1) * 8, &hrank));
-    KMU_TRY(dev_buf(ctx, "ing.spos", (n_lines + 1) * 8, &spos));
+    uint64_t *spos, *hrank, *slen, *lend, *lstart;
+    uint32_t *hdr;
+    KMU_TRY(dev_array(ctx, "ing.lstart", n_lines + 1, &lstart));
+    KMU_TRY(dev_array(ctx, "ing.lend", n_lines + 1, &lend));
+    KMU_TRY(dev_array(ctx, "ing.hdr", n_lines + 1, &hdr));
+    KMU_TRY(dev_array(ctx, "ing.slen", n_lines + 1, &slen));
+    KMU_TRY(dev_array(ctx, "ing.hrank", n_lines + 1, &hrank));
+    KMU_TRY(dev_array(ctx, "ing.spos", n_lines + 1, &spos));
     const int grid_l = (int) std::min<uint64_t>((n_lines + 255) / 256, (uint64_t) ctx->num_cus * 16);
     {
         KernelTimer t(ctx, "k_fa_lines");
-        hipLaunchKernelGGL(k_fa_lines, dim3(grid_w), dim3(256), 0, ctx->stream, d_text, n_bytes, n_regions, (const uint64_t *) lbase,
-                           n_lines, (uint64_t *) lstart, (uint64_t *) lend, (uint32_t *) hdr);
-        hipLaunchKernelGGL(k_fa_lens, dim3(grid_l), dim3(256), 0, ctx->stream, (const uint64_t *) lstart, (const uint64_t *) lend,
-                           (const uint32_t *) hdr, n_lines, (uint64_t *) slen);
+        KMU_TRY(launch(ctx, nullptr, k_fa_lines, dim3(grid_w), dim3(256), 0, d_text, n_bytes, n_regions, (const uint64_t *) lbase, n_lines, lstart,
+                       lend, hdr));
+        KMU_TRY(launch(ctx, nullptr, k_fa_lens, dim3(grid_l), dim3(256), 0, lstart, lend, hdr, n_lines, slen));
     }
-    KMU_TRY(device_scan(ctx, (const uint32_t *) hdr, n_lines, (uint64_t *) hrank));
-    KMU_TRY(device_scan(ctx, (const uint64_t *) slen, n_lines, (uint64_t *) spos));
+    KMU_TRY(device_scan(ctx, hdr, n_lines, hrank));
+    KMU_TRY(device_scan(ctx, slen, n_lines, spos));
     uint64_t n_records = 0, n_stream = 0;
     uint32_t first_hdr = 0;
-    KMU_HIP(ctx, hipMemcpyAsync(&n_records, (const uint64_t *) hrank + n_lines, 8, hipMemcpyDeviceToHost, ctx->stream));
-    KMU_HIP(ctx, hipMemcpyAsync(&n_stream, (const uint64_t *) spos + n_lines, 8, hipMemcpyDeviceToHost, ctx->stream));
+    KMU_HIP(ctx, hipMemcpyAsync(&n_records, hrank + n_lines, 8, hipMemcpyDeviceToHost, ctx->stream));
+    KMU_HIP(ctx, hipMemcpyAsync(&n_stream, spos + n_lines, 8, hipMemcpyDeviceToHost, ctx->stream));
     KMU_HIP(ctx, hipMemcpyAsync(&first_hdr, hdr, 4, hipMemcpyDeviceToHost, ctx->stream));
     KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
     if (!first_hdr) return fail(ctx, KMU_E_BAD_ARG, "invalid record: a FASTA text starts with '>'");
     if (n_records > 0xFFFFFFFFull) return fail(ctx, KMU_E_UNSUPPORTED, "more than 2^32 records in one call");
-    void *sstart, *send, *stream;
-    KMU_TRY(dev_buf(ctx, "ing.sstart", (n_records + 1) * 8, &sstart));
-    KMU_TRY(dev_buf(ctx, "ing.send", (n_records + 1) * 8, &send));
+    uint64_t *send, *sstart;
+    void *stream;
+    KMU_TRY(dev_array(ctx, "ing.sstart", n_records + 1, &sstart));
+    KMU_TRY(dev_array(ctx, "ing.send", n_records + 1, &send));
     KMU_TRY(dev_buf(ctx, "ing.stream", n_stream + 64, &stream));
     {
         KernelTimer t(ctx, "k_fa_join");
-        hipLaunchKernelGGL(k_fa_records, dim3(grid_l), dim3(256), 0, ctx->stream, (const uint32_t *) hdr, (const uint64_t *) hrank,
-                           (const uint64_t *) spos, n_lines, n_records, (uint64_t *) sstart, (uint64_t *) send);
-        hipLaunchKernelGGL(k_fa_join, dim3(grid_w), dim3(256), 0, ctx->stream, d_text, n_bytes, n_regions, (const uint64_t *) lbase,
-                           (const uint64_t *) lstart, (const uint64_t *) lend, (const uint32_t *) hdr, (const uint64_t *) spos,
-                           (uint8_t *) stream);
+        KMU_TRY(launch(ctx, nullptr, k_fa_records, dim3(grid_l), dim3(256), 0, hdr, hrank, spos, n_lines, n_records, sstart, send));
+        KMU_TRY(launch(ctx, nullptr, k_fa_join, dim3(grid_w), dim3(256), 0, d_text, n_bytes, n_regions, (const uint64_t *) lbase, lstart, lend, hdr,
+                       spos, (uint8_t *) stream));
     }
     return ingest_filter_copy(ctx, (const uint8_t *) stream, n_stream, n_records, sstart, send, scal, mem, bases_out, bases_cap,
                               offsets_out, offsets_cap, record_index_out, info);

@@ -419,8 +419,7 @@ extern "C" int kmu_nthash(kmu_ctx *ctx, const kmu_nthash_params *p, const uint8_
     if (p->mem == KMU_MEM_HOST) {
         total = n_seq ? offsets[n_seq] - off0 : 0;
         void *q;
-        KMU_TRY(dev_buf(ctx, "out.u64", (size_t) total * 8 * p->n_hashes + 8, &q));
-        d_out = (uint64_t *) q;
+        KMU_TRY(dev_array(ctx, "out.u64", (size_t) total * p->n_hashes + 1, &d_out));
         KMU_HIP(ctx, hipMemsetAsync(d_out, 0, (size_t) total * 8 * p->n_hashes, ctx->stream));
         if (strand_out) {
             KMU_TRY(dev_buf(ctx, "out.u8", (size_t) total + 8, &q));
@@ -441,18 +440,16 @@ extern "C" int kmu_nthash(kmu_ctx *ctx, const kmu_nthash_params *p, const uint8_
             KMU_TRY(flat_novalid(ctx, ds, end, p->kmer_size, (end + 15) / 16 + 128, "nt.novalid", &nvp));
             a.novalid = (const uint16_t *) nvp;
         }
-        KernelTimer t(ctx, "k_nthash");
         if (!ds.packed) { // one flat stream: the lanes are full whatever the read lengths
             const int grid = ctx->num_cus * 8;
             const bool t8 = p->table == KMU_NTHASH_TABLE_8B, one = p->n_hashes == 1;
             const auto kern = t8 ? (one ? k_nthash_flat<true, true> : k_nthash_flat<true, false>) : (one ? k_nthash_flat<false, true> : k_nthash_flat<false, false>);
-            hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, ctx->stream, a);
+            KMU_TRY(launch(ctx, "k_nthash", kern, dim3(grid), dim3(256), 0, a));
         } else {
-            const int grid = (int) std::min<uint32_t>(n_seq, (uint32_t) ctx->num_cus * 8);
-            hipLaunchKernelGGL(k_nthash<false>, dim3(grid), dim3(256), 0, ctx->stream, a);
+            const int grid = grid_for(ctx, n_seq, 1);
+            KMU_TRY(launch(ctx, "k_nthash", k_nthash<false>, dim3(grid), dim3(256), 0, a));
         }
     }
-    KMU_HIP(ctx, hipGetLastError());
     if (p->mem == KMU_MEM_HOST) {
         KMU_HIP(ctx, hipMemcpyAsync(hashes_out + off0 * p->n_hashes, d_out, (size_t) total * 8 * p->n_hashes, hipMemcpyDeviceToHost, ctx->stream));
         if (strand_out) KMU_HIP(ctx, hipMemcpyAsync(strand_out + off0, d_strand, (size_t) total, hipMemcpyDeviceToHost, ctx->stream));
@@ -475,36 +472,35 @@ extern "C" int kmu_kmer_distribution(kmu_ctx *ctx, const kmu_hash_params *p, con
     KMU_TRY(stage_sequences(ctx, bases, offsets, packed_offsets, n_seq, p->input_kind, p->mem, &ds));
     uint32_t *d_err;
     KMU_TRY(get_err_word(ctx, &d_err));
-    void *passes, *item_off, *nd, *tk, *tc, *doff, *queue;
+    uint32_t *tc, *nd, *passes;
+    uint64_t *tk, *doff, *item_off;
+    void *queue;
     const uint64_t *koff, *vals;
     uint64_t n_kmers = 0;
     KMU_TRY(hash_all_kmers(ctx, ds, KmerCfg{p->kmer_type, p->kmer_size, p->fhash}, d_err, &koff, &vals, &n_kmers));
-    KMU_TRY(dev_buf(ctx, "dist.passes", ((size_t) n_seq + 1) * 4, &passes));
-    KMU_TRY(dev_buf(ctx, "dist.item_off", ((size_t) n_seq + 1) * 8, &item_off));
-    KMU_TRY(dev_buf(ctx, "dist.nd", ((size_t) n_seq + 1) * 4, &nd));
-    KMU_TRY(dev_buf(ctx, "dist.doff", ((size_t) n_seq + 1) * 8, &doff));
-    KMU_TRY(dev_buf(ctx, "dist.tmp_k", n_kmers * 8 + 64, &tk));
-    KMU_TRY(dev_buf(ctx, "dist.tmp_c", n_kmers * 4 + 64, &tc));
+    KMU_TRY(dev_array(ctx, "dist.passes", (size_t) n_seq + 1, &passes));
+    KMU_TRY(dev_array(ctx, "dist.item_off", (size_t) n_seq + 1, &item_off));
+    KMU_TRY(dev_array(ctx, "dist.nd", (size_t) n_seq + 1, &nd));
+    KMU_TRY(dev_array(ctx, "dist.doff", (size_t) n_seq + 1, &doff));
+    KMU_TRY(dev_array(ctx, "dist.tmp_k", n_kmers + 8, &tk));
+    KMU_TRY(dev_array(ctx, "dist.tmp_c", n_kmers + 16, &tc));
     KMU_TRY(dev_buf(ctx, "dist.queue", 64, &queue));
     KMU_HIP(ctx, hipMemsetAsync(nd, 0, ((size_t) n_seq + 1) * 4, ctx->stream));
     KMU_HIP(ctx, hipMemsetAsync(queue, 0, 64, ctx->stream));
-    const int grid_s = (int) std::min<uint64_t>(((uint64_t) n_seq + 255) / 256, (uint64_t) ctx->num_cus * 8);
-    hipLaunchKernelGGL(k_dist_plan, dim3(grid_s), dim3(256), 0, ctx->stream, koff, n_seq, (uint32_t *) passes);
-    KMU_TRY(device_scan_u32(ctx, (const uint32_t *) passes, n_seq, (uint64_t *) item_off));
+    const int grid_s = grid_for(ctx, n_seq, 256);
+    KMU_TRY(launch(ctx, nullptr, k_dist_plan, dim3(grid_s), dim3(256), 0, koff, n_seq, passes));
+    KMU_TRY(device_scan_u32(ctx, passes, n_seq, item_off));
     uint64_t n_items = 0;
-    KMU_HIP(ctx, hipMemcpyAsync(&n_items, (uint64_t *) item_off + n_seq, 8, hipMemcpyDeviceToHost, ctx->stream));
+    KMU_HIP(ctx, hipMemcpyAsync(&n_items, item_off + n_seq, 8, hipMemcpyDeviceToHost, ctx->stream));
     KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
     if (n_items) {
         const int grid = (int) std::min<uint64_t>(n_items, (uint64_t) ctx->num_cus * 3);
-        KernelTimer t(ctx, "k_kmer_dist");
-        hipLaunchKernelGGL(k_kmer_dist, dim3(grid), dim3(DIST_THREADS), 0, ctx->stream, vals, koff,
-                           (const uint64_t *) item_off, n_seq, n_items, (uint64_t *) tk, (uint32_t *) tc, (uint32_t *) nd,
-                           (unsigned long long *) queue, d_err);
+        KMU_TRY(launch(ctx, "k_kmer_dist", k_kmer_dist, dim3(grid), dim3(DIST_THREADS), 0, vals, koff, item_off, n_seq, n_items, tk, tc, nd,
+                       (unsigned long long *) queue, d_err));
     }
-    KMU_TRY(device_scan_u32(ctx, (const uint32_t *) nd, n_seq, (uint64_t *) doff));
-    KMU_HIP(ctx, hipGetLastError());
+    KMU_TRY(device_scan_u32(ctx, nd, n_seq, doff));
     uint64_t n_pairs = 0;
-    KMU_HIP(ctx, hipMemcpyAsync(&n_pairs, (uint64_t *) doff + n_seq, 8, hipMemcpyDeviceToHost, ctx->stream));
+    KMU_HIP(ctx, hipMemcpyAsync(&n_pairs, doff + n_seq, 8, hipMemcpyDeviceToHost, ctx->stream));
     KMU_TRY(check_err_word(ctx, d_err)); // (synchronises)
     *n_out = n_pairs;
     if (dist_offsets_out) {
@@ -516,18 +512,13 @@ extern "C" int kmu_kmer_distribution(kmu_ctx *ctx, const kmu_hash_params *p, con
     uint64_t *d_k = kmers_out;
     uint32_t *d_c = mult_out;
     if (p->mem == KMU_MEM_HOST) {
-        void *q;
-        KMU_TRY(dev_buf(ctx, "dist.out_k", n_pairs * 8 + 64, &q));
-        d_k = (uint64_t *) q;
-        KMU_TRY(dev_buf(ctx, "dist.out_c", n_pairs * 4 + 64, &q));
-        d_c = (uint32_t *) q;
+        KMU_TRY(dev_array(ctx, "dist.out_k", n_pairs + 8, &d_k));
+        KMU_TRY(dev_array(ctx, "dist.out_c", n_pairs + 16, &d_c));
     }
     if (n_pairs) {
-        const int grid = (int) std::min<uint32_t>(n_seq, (uint32_t) ctx->num_cus * 8);
-        hipLaunchKernelGGL(k_dist_compact, dim3(grid), dim3(256), 0, ctx->stream, (const uint64_t *) tk, (const uint32_t *) tc,
-                           koff, (const uint64_t *) doff, n_seq, d_k, d_c);
+        const int grid = grid_for(ctx, n_seq, 1);
+        KMU_TRY(launch(ctx, nullptr, k_dist_compact, dim3(grid), dim3(256), 0, tk, tc, koff, doff, n_seq, d_k, d_c));
     }
-    KMU_HIP(ctx, hipGetLastError());
     if (p->mem == KMU_MEM_HOST) {
         KMU_HIP(ctx, hipMemcpyAsync(kmers_out, d_k, n_pairs * 8, hipMemcpyDeviceToHost, ctx->stream));
         KMU_HIP(ctx, hipMemcpyAsync(mult_out, d_c, n_pairs * 4, hipMemcpyDeviceToHost, ctx->stream));

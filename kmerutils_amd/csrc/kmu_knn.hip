@@ -218,11 +218,8 @@ extern "C" int kmu_sig_knn(kmu_ctx *ctx, const void *sig_q, uint32_t nq, const v
     uint16_t *deq = eq_out;
     const size_t n_out = (size_t) nq * k;
     if (mem == KMU_MEM_HOST) {
-        void *p;
-        KMU_TRY(dev_buf(ctx, "knn.idx", n_out * 4, &p));
-        didx = (uint32_t *) p;
-        KMU_TRY(dev_buf(ctx, "knn.eq", n_out * 2, &p));
-        deq = (uint16_t *) p;
+        KMU_TRY(dev_array(ctx, "knn.idx", n_out, &didx));
+        KMU_TRY(dev_array(ctx, "knn.eq", n_out, &deq));
     }
     if (ndb == 0) { // every list is "none"
         KMU_HIP(ctx, hipMemsetAsync(didx, 0xFF, n_out * 4, ctx->stream));
@@ -253,31 +250,21 @@ extern "C" int kmu_sig_knn(kmu_ctx *ctx, const void *sig_q, uint32_t nq, const v
         const uint64_t ws_bytes = env_u64("KMU_KNN_WS_MB", 256) << 20;
         uint64_t slab = ws_bytes / ((uint64_t) nseg * k * 8) / KT * KT;
         slab = std::min<uint64_t>(std::max<uint64_t>(slab, KT), (uint64_t) qtiles_all * KT);
-        void *dpart;
-        KMU_TRY(dev_buf(ctx, "knn.part", std::min<uint64_t>(slab, nq) * nseg * k * 8, &dpart));
+        uint64_t *dpart;
+        KMU_TRY(dev_array(ctx, "knn.part", std::min<uint64_t>(slab, nq) * nseg * k, &dpart));
         for (uint64_t s0 = 0; s0 < nq; s0 += slab) {
             const uint32_t rows = (uint32_t) std::min<uint64_t>(slab, nq - s0);
             const dim3 grid((rows + KT - 1) / KT, nseg);
             const size_t dyn = (size_t) KT * k * 8;
             const uint32_t *gqs = dgq ? (const uint32_t *) dgq + s0 : nullptr;
-            {
-                KernelTimer t(ctx, "k_sig_knn");
-                if (wb == 4)
-                    hipLaunchKernelGGL(k_sig_knn<uint32_t>, grid, dim3(256), dyn, ctx->stream, (const uint32_t *) dq + s0 * m, rows,
-                                       (const uint32_t *) ddb, ndb, m, k, (uint32_t) seg_rows, gqs, (const uint32_t *) dgdb,
-                                       (uint64_t *) dpart);
-                else
-                    hipLaunchKernelGGL(k_sig_knn<uint64_t>, grid, dim3(256), dyn, ctx->stream, (const uint64_t *) dq + s0 * m, rows,
-                                       (const uint64_t *) ddb, ndb, m, k, (uint32_t) seg_rows, gqs, (const uint32_t *) dgdb,
-                                       (uint64_t *) dpart);
-            }
-            KMU_HIP(ctx, hipGetLastError());
-            {
-                KernelTimer t(ctx, "k_sig_knn_merge");
-                hipLaunchKernelGGL(k_sig_knn_merge, dim3((rows + 3) / 4), dim3(256), 0, ctx->stream, (const uint64_t *) dpart, rows,
-                                   nseg, k, didx + s0 * k, deq + s0 * k);
-            }
-            KMU_HIP(ctx, hipGetLastError());
+            if (wb == 4)
+                KMU_TRY(launch(ctx, "k_sig_knn", k_sig_knn<uint32_t>, grid, dim3(256), dyn, (const uint32_t *) dq + s0 * m, rows, ddb, ndb, m, k,
+                               (uint32_t) seg_rows, gqs, dgdb, dpart));
+            else
+                KMU_TRY(launch(ctx, "k_sig_knn", k_sig_knn<uint64_t>, grid, dim3(256), dyn, (const uint64_t *) dq + s0 * m, rows, ddb, ndb, m, k,
+                               (uint32_t) seg_rows, gqs, dgdb, dpart));
+            KMU_TRY(launch(ctx, "k_sig_knn_merge", k_sig_knn_merge, dim3((rows + 3) / 4), dim3(256), 0, dpart, rows, nseg, k, didx + s0 * k,
+                           deq + s0 * k));
         }
     }
     if (mem == KMU_MEM_HOST) {

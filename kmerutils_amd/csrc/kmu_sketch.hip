@@ -76,10 +76,10 @@ int sketch_params(kmu_ctx *ctx, const kmu_sketch_params *p_in, kmu_sketch_params
 }
 
 int launch_nk_scan(kmu_ctx *ctx, const DevSeqs &ds, int kmer_size, uint32_t *d_err, const uint64_t **koff) {
-    void *q;
-    KMU_TRY(dev_buf(ctx, "all.koff", ((size_t) ds.n_seq + 1) * 8, &q));
-    hipLaunchKernelGGL(k_nk_scan, dim3(1), dim3(1024), 0, ctx->stream, ds.offsets, ds.n_seq, kmer_size, (uint64_t *) q, d_err);
-    *koff = (const uint64_t *) q;
+    uint64_t *q;
+    KMU_TRY(dev_array(ctx, "all.koff", (size_t) ds.n_seq + 1, &q));
+    KMU_TRY(launch(ctx, nullptr, k_nk_scan, dim3(1), dim3(1024), 0, ds.offsets, ds.n_seq, kmer_size, q, d_err));
+    *koff = q;
     return KMU_OK;
 }
 
@@ -95,11 +95,9 @@ int launch_hashes_compact(kmu_ctx *ctx, const DevSeqs &ds, const KmerCfg &cfg, c
         // few sequences: every workgroup takes a share of every sequence instead of whole sequences
         const int spread = ds.n_seq < (uint32_t) ctx->num_cus * 4 ? 1 : 0;
         const int grid = spread ? ctx->num_cus * 8 : (int) std::min<uint32_t>(ds.n_seq, (uint32_t) ctx->num_cus * 8);
-        KernelTimer t(ctx, "k_seq_hashes_compact");
-        hipLaunchKernelGGL(k_seq_hashes_compact, dim3(grid), dim3(256), 0, ctx->stream, ds.bases, ds.offsets, ds.packed_offsets, ds.n_seq,
-                           ds.packed, ds.total_bytes, cfg, koff, d_out, d_err, spread);
+        KMU_TRY(launch(ctx, "k_seq_hashes_compact", k_seq_hashes_compact, dim3(grid), dim3(256), 0, ds.bases, ds.offsets, ds.packed_offsets, ds.n_seq,
+                       ds.packed, ds.total_bytes, cfg, koff, d_out, d_err, spread));
     }
-    KMU_HIP(ctx, hipGetLastError());
     return KMU_OK;
 }
 
@@ -126,29 +124,25 @@ int sketch_all_hashed(kmu_ctx *ctx, const kmu_sketch_params *p, const uint64_t *
         const uint64_t *items, *bounds;
         KMU_TRY(partition_u64(ctx, d_vals, n, region_bits, &items, &bounds));
         const uint64_t n_leaves = 1ull << region_bits;
-        void *ph, *pk;
-        KMU_TRY(dev_buf(ctx, "all.part_h", n_leaves * m * 8, &ph));
-        KMU_TRY(dev_buf(ctx, "all.part_k", n_leaves * m * 8, &pk));
-        KMU_TRY(launch_pmh3a_leaves(ctx, p, items, bounds, (uint32_t) n_leaves, (uint64_t *) ph, (uint64_t *) pk, d_err));
-        {
-            KernelTimer t(ctx, "k_pmh_reduce");
-            hipLaunchKernelGGL(k_pmh_reduce, dim3(m), dim3(256), 0, ctx->stream, (const uint64_t *) ph, (const uint64_t *) pk,
-                               n_leaves, m, (uint64_t) m, kmer_val_bytes(p->kmer_type), d_sig, ctx->partial_out);
-        }
-        KMU_HIP(ctx, hipGetLastError());
+        uint64_t *pk, *ph;
+        KMU_TRY(dev_array(ctx, "all.part_h", n_leaves * m, &ph));
+        KMU_TRY(dev_array(ctx, "all.part_k", n_leaves * m, &pk));
+        KMU_TRY(launch_pmh3a_leaves(ctx, p, items, bounds, (uint32_t) n_leaves, ph, pk, d_err));
+        KMU_TRY(launch(ctx, "k_pmh_reduce", k_pmh_reduce, dim3(m), dim3(256), 0, ph, pk, n_leaves, m, (uint64_t) m, kmer_val_bytes(p->kmer_type),
+                       d_sig, ctx->partial_out));
         return KMU_OK;
     }
     // SuperMinHash / SuperMinHash2
     const uint64_t n_chunks = super_chunk_count(n);
     std::vector<uint64_t> h_off(n_chunks + 1);
     for (uint64_t c = 0; c <= n_chunks; c++) h_off[c] = n * c / n_chunks;
-    void *d_off, *pr;
-    KMU_TRY(dev_buf(ctx, "all.chunk_off", (n_chunks + 1) * 8, &d_off));
+    uint64_t *pr, *d_off;
+    KMU_TRY(dev_array(ctx, "all.chunk_off", n_chunks + 1, &d_off));
     KMU_HIP(ctx, hipMemcpyAsync(d_off, h_off.data(), (n_chunks + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
     KMU_HIP(ctx, hipStreamSynchronize(ctx->stream)); // h_off is a local
-    KMU_TRY(dev_buf(ctx, "all.part_rows", n_chunks * m * 8, &pr));
-    KMU_TRY(launch_super(ctx, p, hashed_seqs(d_vals, (const uint64_t *) d_off, (uint32_t) n_chunks), nullptr, d_err, d_vals, 8, (uint64_t *) pr));
-    return launch_super_reduce(ctx, p, (const uint64_t *) pr, n_chunks, d_sig);
+    KMU_TRY(dev_array(ctx, "all.part_rows", n_chunks * m, &pr));
+    KMU_TRY(launch_super(ctx, p, hashed_seqs(d_vals, d_off, (uint32_t) n_chunks), nullptr, d_err, d_vals, 8, pr));
+    return launch_super_reduce(ctx, p, pr, n_chunks, d_sig);
 }
 
 int sketch_per_seq_device(kmu_ctx *ctx, const kmu_sketch_params *p, const DevSeqs &ds, const uint64_t *d_block_rows, uint32_t *d_counts,
@@ -190,18 +184,15 @@ extern "C" int kmu_sketch(kmu_ctx *ctx, const kmu_sketch_params *p_in, const uin
     if (p->mem == KMU_MEM_HOST) {
         if (p->block_size > 0) {
             rows = block_row_offsets[n_seq];
-            void *q;
-            KMU_TRY(dev_buf(ctx, "in.blockrows", (size_t) (n_seq + 1) * 8, &q));
+            uint64_t *q;
+            KMU_TRY(dev_array(ctx, "in.blockrows", (size_t) n_seq + 1, &q));
             KMU_HIP(ctx, hipMemcpyAsync(q, block_row_offsets, (size_t) (n_seq + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
-            d_block_rows = (const uint64_t *) q;
+            d_block_rows = q;
         }
         void *q;
         KMU_TRY(dev_buf(ctx, "out.sig", rows * p->sketch_size * sigb + 64, &q));
         d_sig = q;
-        if (counts_out) {
-            KMU_TRY(dev_buf(ctx, "out.counts", rows * p->sketch_size * 4 + 64, &q));
-            d_counts = (uint32_t *) q;
-        }
+        if (counts_out) KMU_TRY(dev_array(ctx, "out.counts", rows * p->sketch_size + 16, &d_counts));
     } else {
         d_block_rows = block_row_offsets;
     }
@@ -269,10 +260,7 @@ extern "C" int kmu_sketch_hashed(kmu_ctx *ctx, const kmu_sketch_params *p_in, co
         d_off = (const uint64_t *) q;
         KMU_TRY(dev_buf(ctx, "out.sig", rows * m * sigb + 64, &q));
         d_sig = q;
-        if (counts_out) {
-            KMU_TRY(dev_buf(ctx, "out.counts", rows * m * 4 + 64, &q));
-            d_counts = (uint32_t *) q;
-        }
+        if (counts_out) KMU_TRY(dev_array(ctx, "out.counts", rows * m + 16, &d_counts));
     } else {
         KMU_HIP(ctx, hipMemcpyAsync(&n_items, offsets + n_seq, 8, hipMemcpyDeviceToHost, ctx->stream));
         if (n_seq) KMU_HIP(ctx, hipMemcpyAsync(&first_item, offsets, 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -289,8 +277,8 @@ extern "C" int kmu_sketch_hashed(kmu_ctx *ctx, const kmu_sketch_params *p_in, co
         if (w == 4) { // widen to u64 once (the all-sequences path partitions u64 keys)
             void *q;
             KMU_TRY(dev_buf(ctx, "all.hashes", n_items * 8 + 64, &q));
-            hipLaunchKernelGGL(k_widen_u32, dim3((unsigned) std::min<uint64_t>((n_items + 255) / 256 + 1, 65535)), dim3(256), 0,
-                               ctx->stream, (const uint32_t *) d_vals + first_item, n_items, (uint64_t *) q);
+            KMU_TRY(launch(ctx, nullptr, k_widen_u32, dim3((unsigned) std::min<uint64_t>((n_items + 255) / 256 + 1, 65535)), dim3(256), 0,
+                           (const uint32_t *) d_vals + first_item, n_items, (uint64_t *) q));
             v64 = (const uint64_t *) q;
         }
         KMU_TRY(sketch_all_hashed(ctx, p, v64, n_items, d_sig, d_err));
@@ -400,14 +388,13 @@ extern "C" int kmu_sketch_merge_partials(kmu_ctx *ctx, const kmu_sketch_params *
         d_sig = q;
     }
     if (p->algo == KMU_ALGO_PROB3A) {
-        hipLaunchKernelGGL(k_pmh_reduce, dim3(m), dim3(256), 0, ctx->stream, d_parts, d_parts + m, (uint64_t) n_parts, m, words,
-                           kmer_val_bytes(p->kmer_type), d_sig, (uint64_t *) nullptr);
+        KMU_TRY(launch(ctx, nullptr, k_pmh_reduce, dim3(m), dim3(256), 0, d_parts, d_parts + m, (uint64_t) n_parts, m, words,
+                       kmer_val_bytes(p->kmer_type), d_sig, (uint64_t *) nullptr));
     } else if (algo_is_dens(p->algo)) {
         KMU_TRY(launch_dens_merge(ctx, p, d_parts, n_parts, d_sig));
     } else {
         KMU_TRY(launch_super_reduce(ctx, p, d_parts, n_parts, d_sig));
     }
-    KMU_HIP(ctx, hipGetLastError());
     if (p->mem == KMU_MEM_HOST) KMU_HIP(ctx, hipMemcpyAsync(sig_out, d_sig, (size_t) m * sigb, hipMemcpyDeviceToHost, ctx->stream));
     return finish_call(ctx, p->mem);
 }
@@ -432,11 +419,7 @@ extern "C" int kmu_kmer_hashes_compact(kmu_ctx *ctx, const kmu_hash_params *p, c
     if (!out) return KMU_OK;
     if (cap < n_items) return fail(ctx, KMU_E_BAD_ARG, "output too small: %llu values", (unsigned long long) n_items);
     uint64_t *d_out = out;
-    if (p->mem == KMU_MEM_HOST) {
-        void *q;
-        KMU_TRY(dev_buf(ctx, "all.hashes", n_items * 8 + 64, &q));
-        d_out = (uint64_t *) q;
-    }
+    if (p->mem == KMU_MEM_HOST) KMU_TRY(dev_array(ctx, "all.hashes", n_items + 8, &d_out));
     KMU_TRY(launch_hashes_compact(ctx, ds, KmerCfg{p->kmer_type, p->kmer_size, p->fhash}, koff, d_out, d_err));
     if (p->mem == KMU_MEM_HOST) KMU_HIP(ctx, hipMemcpyAsync(out, d_out, n_items * 8, hipMemcpyDeviceToHost, ctx->stream));
     return finish_checked(ctx, p->mem, d_err);

@@ -207,23 +207,22 @@ int launch_dens(kmu_ctx *ctx, const kmu_sketch_params *p, const DevSeqs &ds, voi
                           (const void *) k_oph_long<false>,         (const void *) k_oph_long<true>,
                           (const void *) k_oph_finish};
     KMU_TRY(dens_lds_check(ctx, a, fns, 7));
-    void *q, *row, *mx;
+    uint64_t *row;
+    void *q, *mx;
     KMU_TRY(dev_buf(ctx, "queue", 64, &q));
     KMU_HIP(ctx, hipMemsetAsync(q, 0, 64, ctx->stream));
     a.queue = (uint32_t *) q;
-    KMU_TRY(dev_buf(ctx, "dens.row", (size_t) 8 * a.m + 64, &row));
-    a.row = (uint64_t *) row;
+    KMU_TRY(dev_array(ctx, "dens.row", (size_t) a.m + 8, &row));
+    a.row = row;
     const uint64_t large = dens_neutral_bits(a);
-    auto fill_row = [&]() {
-        hipLaunchKernelGGL(k_oph_fill, dim3((a.m + 255) / 256), dim3(256), 0, ctx->stream, a.row, a.m, large);
-    };
+    auto fill_row = [&]() { return launch(ctx, nullptr, k_oph_fill, dim3((a.m + 255) / 256), dim3(256), 0, a.row, a.m, large); };
     // sequences too long for one workgroup: found on the host from the offsets (only if the longest one calls for it)
     std::vector<uint32_t> long_seqs;
     if (ds.n_seq) {
         KMU_TRY(dev_buf(ctx, "pmh.maxlen", 64, &mx));
         KMU_HIP(ctx, hipMemsetAsync(mx, 0, 8, ctx->stream));
         const uint32_t mgrid = (uint32_t) std::min<uint64_t>(((uint64_t) ds.n_seq + 1023) / 1024, (uint64_t) ctx->num_cus);
-        hipLaunchKernelGGL(k_dens_max_len, dim3(mgrid ? mgrid : 1), dim3(1024), 0, ctx->stream, ds.offsets, ds.n_seq, (uint64_t *) mx);
+        KMU_TRY(launch(ctx, nullptr, k_dens_max_len, dim3(mgrid ? mgrid : 1), dim3(1024), 0, ds.offsets, ds.n_seq, (uint64_t *) mx));
         uint64_t max_len = 0;
         KMU_HIP(ctx, hipMemcpyAsync(&max_len, mx, 8, hipMemcpyDeviceToHost, ctx->stream));
         KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -239,35 +238,27 @@ int launch_dens(kmu_ctx *ctx, const kmu_sketch_params *p, const DevSeqs &ds, voi
         }
     }
     const int per_cu = (int) std::max<size_t>(1, std::min<size_t>(8, lds_max / lds_full));
-    int grid = (int) std::min<uint64_t>(std::max<uint64_t>(ds.n_seq, 1), (uint64_t) ctx->num_cus * per_cu);
-    if (all) fill_row();
-    {
-        KernelTimer t(ctx, "k_oph_reads");
-        if (all && a.hll) hipLaunchKernelGGL((k_oph_reads<true, true>), dim3(grid), dim3(256), lds_full, ctx->stream, a);
-        else if (all) hipLaunchKernelGGL((k_oph_reads<true, false>), dim3(grid), dim3(256), lds_full, ctx->stream, a);
-        else if (a.hll) hipLaunchKernelGGL((k_oph_reads<false, true>), dim3(grid), dim3(256), lds_full, ctx->stream, a);
-        else hipLaunchKernelGGL((k_oph_reads<false, false>), dim3(grid), dim3(256), lds_full, ctx->stream, a);
-    }
+    const int grid = grid_for(ctx, ds.n_seq, 1, per_cu);
+    if (all) KMU_TRY(fill_row());
+    const auto reads = all ? (a.hll ? k_oph_reads<true, true> : k_oph_reads<true, false>) : (a.hll ? k_oph_reads<false, true> : k_oph_reads<false, false>);
+    KMU_TRY(launch(ctx, "k_oph_reads", reads, dim3(grid), dim3(256), lds_full, a));
     const int grid_long = ctx->num_cus * (int) std::max<size_t>(1, std::min<size_t>(8, lds_max / std::max<size_t>(lds_acc, 1024)));
     for (uint32_t i : long_seqs) {
-        if (!all) fill_row();
+        if (!all) KMU_TRY(fill_row());
         a.long_seq = i;
-        KernelTimer t(ctx, "k_oph_long");
-        if (a.hll) hipLaunchKernelGGL(k_oph_long<true>, dim3(grid_long), dim3(256), lds_acc, ctx->stream, a);
-        else hipLaunchKernelGGL(k_oph_long<false>, dim3(grid_long), dim3(256), lds_acc, ctx->stream, a);
+        KernelTimer t(ctx, "k_oph_long"); // (with the finish of the sequence's own row)
+        KMU_TRY(launch(ctx, nullptr, a.hll ? k_oph_long<true> : k_oph_long<false>, dim3(grid_long), dim3(256), lds_acc, a));
         if (!all) {
             a.out_row = i;
-            hipLaunchKernelGGL(k_oph_finish, dim3(1), dim3(256), lds_full, ctx->stream, a);
+            KMU_TRY(launch(ctx, nullptr, k_oph_finish, dim3(1), dim3(256), lds_full, a));
         }
     }
     if (all && ctx->partial_out) { // the bins before densification are what other ranks' bins are merged with
         KMU_HIP(ctx, hipMemcpyAsync(ctx->partial_out, a.row, (size_t) 8 * a.m, hipMemcpyDeviceToDevice, ctx->stream));
     } else if (all) {
         a.out_row = 0;
-        KernelTimer t(ctx, "k_oph_finish");
-        hipLaunchKernelGGL(k_oph_finish, dim3(1), dim3(256), lds_full, ctx->stream, a);
+        KMU_TRY(launch(ctx, "k_oph_finish", k_oph_finish, dim3(1), dim3(256), lds_full, a));
     }
-    KMU_HIP(ctx, hipGetLastError());
     return KMU_OK;
 }
 
@@ -299,14 +290,12 @@ int launch_dens_merge(kmu_ctx *ctx, const kmu_sketch_params *p, const uint64_t *
         (void) hipGetLastError();
         return fail(ctx, KMU_E_UNSUPPORTED, "sketch_size %d needs %zu B of LDS", a.m, lds_full);
     }
-    void *row;
-    KMU_TRY(dev_buf(ctx, "dens.row", (size_t) 8 * a.m + 64, &row));
-    a.row = (uint64_t *) row;
-    hipLaunchKernelGGL(k_oph_merge, dim3((a.m + 255) / 256), dim3(256), 0, ctx->stream, parts, n_parts, a.m, a.hll, a.row);
+    uint64_t *row;
+    KMU_TRY(dev_array(ctx, "dens.row", (size_t) a.m + 8, &row));
+    a.row = row;
+    KMU_TRY(launch(ctx, nullptr, k_oph_merge, dim3((a.m + 255) / 256), dim3(256), 0, parts, n_parts, a.m, a.hll, a.row));
     a.out_row = 0;
-    hipLaunchKernelGGL(k_oph_finish, dim3(1), dim3(256), lds_full, ctx->stream, a);
-    KMU_HIP(ctx, hipGetLastError());
-    return KMU_OK;
+    return launch(ctx, nullptr, k_oph_finish, dim3(1), dim3(256), lds_full, a);
 }
 
 } // namespace kmu

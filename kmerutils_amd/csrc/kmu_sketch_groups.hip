@@ -513,8 +513,9 @@ static int groups_dens(kmu_ctx *ctx, const kmu_sketch_params *p, const DevSeqs &
     KMU_TRY(dens_lds_check(ctx, a, fns, 3));
     const size_t lds_full = dens_lds_full(a), lds_walk = (size_t) 8 * a.m + 32;
     const uint64_t n_words = (uint64_t) n_groups * a.m;
-    void *rows, *head, *q;
-    KMU_TRY(dev_buf(ctx, "grp.rows", n_words * 8 + 64, &rows));
+    uint64_t *rows;
+    void *head, *q;
+    KMU_TRY(dev_array(ctx, "grp.rows", n_words + 8, &rows));
     KMU_TRY(dev_buf(ctx, "grp.head", 64, &head));
     KMU_TRY(dev_buf(ctx, "queue", 64, &q));
     KMU_HIP(ctx, hipMemsetAsync(head, 0, 64, ctx->stream));
@@ -522,14 +523,10 @@ static int groups_dens(kmu_ctx *ctx, const kmu_sketch_params *p, const DevSeqs &
     a.queue = (uint32_t *) q;
     // persistent: the workgroups a CU holds, by LDS and by registers (82 VGPRs: five waves per SIMD; the HLL walk 150: three)
     const unsigned walk_grid = (unsigned) ctx->num_cus * (unsigned) std::max<size_t>(1, std::min<size_t>(a.hll ? 3 : 5, DENS_LDS_MAX / lds_walk));
-    {
-        KernelTimer t(ctx, "k_grp_dens_plan");
-        const uint64_t work = std::max<uint64_t>(std::max<uint64_t>(n_words, ds.n_seq), n_groups);
-        hipLaunchKernelGGL(k_grp_dens_plan, dim3((unsigned) std::min<uint64_t>((work + 255) / 256, (uint64_t) ctx->num_cus * 8)), dim3(256), 0,
-                           ctx->stream, d_go, n_groups, ds.offsets, ds.n_seq, (uint64_t *) rows, n_words, dens_neutral_bits(a), walk_grid,
-                           (unsigned long long *) head, d_err);
-    }
-    KMU_HIP(ctx, hipGetLastError());
+    const uint64_t work = std::max<uint64_t>(std::max<uint64_t>(n_words, ds.n_seq), n_groups);
+    KMU_TRY(launch(ctx, "k_grp_dens_plan", k_grp_dens_plan, dim3((unsigned) std::min<uint64_t>((work + 255) / 256, (uint64_t) ctx->num_cus * 8)),
+                   dim3(256), 0, d_go, n_groups, ds.offsets, ds.n_seq, rows, n_words, dens_neutral_bits(a), walk_grid, (unsigned long long *) head,
+                   d_err));
     if (!host_checked) {
         uint64_t h_head[GD_WORDS] = {0, 0, 0, 0}; // the one device-to-host copy of the call
         KMU_HIP(ctx, hipMemcpyAsync(h_head, head, sizeof h_head, hipMemcpyDeviceToHost, ctx->stream));
@@ -539,21 +536,11 @@ static int groups_dens(kmu_ctx *ctx, const kmu_sketch_params *p, const DevSeqs &
             return fail(ctx, KMU_E_BAD_ARG, "%s", groups_bad_text((uint32_t) h_head[GD_BAD]));
         }
     }
-    {
-        KernelTimer t(ctx, "k_grp_dens_walk");
-        if (a.hll) hipLaunchKernelGGL(k_grp_dens_walk<true>, dim3(walk_grid), dim3(256), lds_walk, ctx->stream, a, d_go, n_groups, (uint64_t *) rows,
-                                      (const unsigned long long *) head);
-        else hipLaunchKernelGGL(k_grp_dens_walk<false>, dim3(walk_grid), dim3(256), lds_walk, ctx->stream, a, d_go, n_groups, (uint64_t *) rows,
-                                (const unsigned long long *) head);
-    }
-    {
-        KernelTimer t(ctx, "k_grp_dens_finish");
-        const unsigned per_cu = (unsigned) std::max<size_t>(1, std::min<size_t>(8, DENS_LDS_MAX / lds_full));
-        hipLaunchKernelGGL(k_grp_dens_finish, dim3(std::min<uint32_t>(n_groups, (uint32_t) ctx->num_cus * per_cu)), dim3(256), lds_full, ctx->stream, a,
-                           (const uint64_t *) rows, n_groups);
-    }
-    KMU_HIP(ctx, hipGetLastError());
-    return KMU_OK;
+    KMU_TRY(launch(ctx, "k_grp_dens_walk", a.hll ? k_grp_dens_walk<true> : k_grp_dens_walk<false>, dim3(walk_grid), dim3(256), lds_walk, a, d_go,
+                   n_groups, rows, (const unsigned long long *) head));
+    const unsigned per_cu = (unsigned) std::max<size_t>(1, std::min<size_t>(8, DENS_LDS_MAX / lds_full));
+    return launch(ctx, "k_grp_dens_finish", k_grp_dens_finish, dim3(std::min<uint32_t>(n_groups, (uint32_t) ctx->num_cus * per_cu)), dim3(256),
+                  lds_full, a, rows, n_groups);
 }
 
 // ProbMinHash3a / 3 and SuperMinHash(2): one batched pass over all groups
@@ -562,19 +549,17 @@ static int groups_batched(kmu_ctx *ctx, const kmu_sketch_params *p, const DevSeq
     const uint32_t n_seq = ds.n_seq;
     const int m = p->sketch_size;
     const bool super = p->algo != KMU_ALGO_PROB3A;
-    void *gk, *lbase, *bits, *head, *hk;
+    uint64_t *hk, *lbase, *gk;
+    uint32_t *bits;
+    void *head;
     const uint64_t *koff;
-    KMU_TRY(dev_buf(ctx, "grp.gk", ((size_t) n_groups + 1) * 8, &gk));
-    KMU_TRY(dev_buf(ctx, "grp.leaf_base", ((size_t) n_groups + 1) * 8, &lbase));
-    KMU_TRY(dev_buf(ctx, "grp.bits", (size_t) n_groups * 4, &bits));
+    KMU_TRY(dev_array(ctx, "grp.gk", (size_t) n_groups + 1, &gk));
+    KMU_TRY(dev_array(ctx, "grp.leaf_base", (size_t) n_groups + 1, &lbase));
+    KMU_TRY(dev_array(ctx, "grp.bits", (size_t) n_groups, &bits));
     KMU_TRY(dev_buf(ctx, "grp.head", 64, &head));
     KMU_TRY(launch_nk_scan(ctx, ds, p->kmer_size, d_err, &koff));
-    {
-        KernelTimer t(ctx, "k_group_plan");
-        hipLaunchKernelGGL(k_group_plan, dim3(1), dim3(1024), 0, ctx->stream, d_go, n_groups, n_seq, koff, super ? 1 : 0,
-                           (uint64_t *) gk, (uint64_t *) lbase, (uint32_t *) bits, (uint64_t *) head);
-    }
-    KMU_HIP(ctx, hipGetLastError());
+    KMU_TRY(launch(ctx, "k_group_plan", k_group_plan, dim3(1), dim3(1024), 0, d_go, n_groups, n_seq, koff, super ? 1 : 0, gk, lbase, bits,
+                   (uint64_t *) head));
     uint64_t h_head[3] = {0, 0, 0}; // the one device-to-host copy of the call
     KMU_HIP(ctx, hipMemcpyAsync(h_head, head, sizeof h_head, hipMemcpyDeviceToHost, ctx->stream));
     KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -584,59 +569,41 @@ static int groups_batched(kmu_ctx *ctx, const kmu_sketch_params *p, const DevSeq
     }
     const uint64_t n_items = h_head[0], n_leaves = h_head[1];
     if (n_leaves > 0x7FFFFFFFull) return fail(ctx, KMU_E_UNSUPPORTED, "%llu leaves in one call", (unsigned long long) n_leaves);
-    KMU_TRY(dev_buf(ctx, "all.hashes", n_items * 8 + 64, &hk));
-    KMU_TRY(launch_hashes_compact(ctx, ds, KmerCfg{p->kmer_type, p->kmer_size, p->fhash}, koff, (uint64_t *) hk, d_err));
-    GroupArgs ga{(const uint64_t *) gk, (const uint64_t *) lbase, (const uint32_t *) bits, n_groups};
-    const unsigned tile_grid = (unsigned) std::max<uint64_t>(1, std::min<uint64_t>((n_items + GRP_TILE - 1) / GRP_TILE, (uint64_t) ctx->num_cus * 8));
+    KMU_TRY(dev_array(ctx, "all.hashes", n_items + 8, &hk));
+    KMU_TRY(launch_hashes_compact(ctx, ds, KmerCfg{p->kmer_type, p->kmer_size, p->fhash}, koff, hk, d_err));
+    GroupArgs ga{gk, lbase, bits, n_groups};
+    const unsigned tile_grid = grid_for(ctx, n_items, GRP_TILE);
     const unsigned slot_tiles = (unsigned) std::min<uint32_t>(65535u, ((uint32_t) m + 63u) / 64u);
     if (!super) {
-        void *cnt, *bounds, *items, *ph, *pk;
-        KMU_TRY(dev_buf(ctx, "grp.cursor", n_leaves * 8 + 64, &cnt));
-        KMU_TRY(dev_buf(ctx, "grp.bounds", (n_leaves + 1) * 8 + 64, &bounds));
-        KMU_TRY(dev_buf(ctx, "grp.items", n_items * 8 + 64, &items));
-        KMU_TRY(dev_buf(ctx, "all.part_h", n_leaves * m * 8, &ph));
-        KMU_TRY(dev_buf(ctx, "all.part_k", n_leaves * m * 8, &pk));
+        uint64_t *pk, *ph, *items, *bounds;
+        unsigned long long *cnt;
+        KMU_TRY(dev_array(ctx, "grp.cursor", n_leaves + 8, &cnt));
+        KMU_TRY(dev_array(ctx, "grp.bounds", n_leaves + 1 + 8, &bounds));
+        KMU_TRY(dev_array(ctx, "grp.items", n_items + 8, &items));
+        KMU_TRY(dev_array(ctx, "all.part_h", n_leaves * m, &ph));
+        KMU_TRY(dev_array(ctx, "all.part_k", n_leaves * m, &pk));
         KMU_HIP(ctx, hipMemsetAsync(cnt, 0, n_leaves * 8, ctx->stream));
-        {
-            KernelTimer t(ctx, "k_grp_hist");
-            hipLaunchKernelGGL(k_grp_hist, dim3(tile_grid), dim3(256), 0, ctx->stream, (const uint64_t *) hk, n_items, ga, (unsigned long long *) cnt);
-        }
-        {
-            KernelTimer t(ctx, "k_grp_bounds");
-            hipLaunchKernelGGL(k_grp_bounds, dim3(std::min<uint32_t>(n_groups, (uint32_t) ctx->num_cus * 2)), dim3(1024), 0, ctx->stream, ga,
-                               (unsigned long long *) cnt, (uint64_t *) bounds);
-        }
-        {
-            KernelTimer t(ctx, "k_grp_scatter");
-            hipLaunchKernelGGL(k_grp_scatter, dim3(tile_grid), dim3(256), 0, ctx->stream, (const uint64_t *) hk, n_items, ga,
-                               (unsigned long long *) cnt, (uint64_t *) items);
-        }
-        KMU_HIP(ctx, hipGetLastError());
-        KMU_TRY(launch_pmh3a_leaves(ctx, p, (const uint64_t *) items, (const uint64_t *) bounds, (uint32_t) n_leaves, (uint64_t *) ph,
-                                    (uint64_t *) pk, d_err));
-        {
-            KernelTimer t(ctx, "k_pmh_reduce_groups");
-            hipLaunchKernelGGL(k_pmh_reduce_groups, dim3(n_groups, slot_tiles), dim3(256), 0, ctx->stream, (const uint64_t *) ph, (const uint64_t *) pk,
-                               (const uint64_t *) lbase, m, kmer_val_bytes(p->kmer_type), d_sig);
-        }
-        KMU_HIP(ctx, hipGetLastError());
+        KMU_TRY(launch(ctx, "k_grp_hist", k_grp_hist, dim3(tile_grid), dim3(256), 0, hk, n_items, ga, cnt));
+        KMU_TRY(launch(ctx, "k_grp_bounds", k_grp_bounds, dim3(std::min<uint32_t>(n_groups, (uint32_t) ctx->num_cus * 2)), dim3(1024), 0, ga, cnt,
+                       bounds));
+        KMU_TRY(launch(ctx, "k_grp_scatter", k_grp_scatter, dim3(tile_grid), dim3(256), 0, hk, n_items, ga, cnt, items));
+        KMU_TRY(launch_pmh3a_leaves(ctx, p, items, bounds, (uint32_t) n_leaves, ph,
+                                    pk, d_err));
+        KMU_TRY(launch(ctx, "k_pmh_reduce_groups", k_pmh_reduce_groups, dim3(n_groups, slot_tiles), dim3(256), 0, ph, pk, lbase, m,
+                       kmer_val_bytes(p->kmer_type), d_sig));
         return KMU_OK;
     }
     // SuperMinHash / SuperMinHash2
-    void *d_off, *pr;
-    KMU_TRY(dev_buf(ctx, "all.chunk_off", (n_leaves + 1) * 8, &d_off));
-    KMU_TRY(dev_buf(ctx, "all.part_rows", n_leaves * m * 8, &pr));
-    hipLaunchKernelGGL(k_grp_chunk_offsets, dim3(std::max<uint32_t>(1, std::min<uint32_t>((n_groups + 3) / 4, (uint32_t) ctx->num_cus * 8))), dim3(256), 0,
-                       ctx->stream, ga, (uint64_t *) d_off);
-    KMU_HIP(ctx, hipGetLastError());
-    KMU_TRY(launch_super(ctx, p, hashed_seqs(hk, (const uint64_t *) d_off, (uint32_t) n_leaves), nullptr, d_err, hk, 8, (uint64_t *) pr));
+    uint64_t *pr, *d_off;
+    KMU_TRY(dev_array(ctx, "all.chunk_off", n_leaves + 1, &d_off));
+    KMU_TRY(dev_array(ctx, "all.part_rows", n_leaves * m, &pr));
+    KMU_TRY(launch(ctx, nullptr, k_grp_chunk_offsets,
+                   dim3(grid_for(ctx, n_groups, 4)), dim3(256), 0, ga, d_off));
+    KMU_TRY(launch_super(ctx, p, hashed_seqs(hk, d_off, (uint32_t) n_leaves), nullptr, d_err, hk, 8, pr));
     const int mode = super_mode(p);
-    {
-        KernelTimer t(ctx, "k_super_reduce_groups");
-        hipLaunchKernelGGL(k_super_reduce_groups, dim3(n_groups, (unsigned) std::min<uint32_t>(65535u, ((uint32_t) m + 255u) / 256u)), dim3(256), 0,
-                           ctx->stream, (const uint64_t *) pr, (const uint64_t *) lbase, m, mode, super_init_bits(mode), d_sig);
-    }
-    KMU_HIP(ctx, hipGetLastError());
+    KMU_TRY(launch(ctx, "k_super_reduce_groups", k_super_reduce_groups,
+                   dim3(n_groups, (unsigned) std::min<uint32_t>(65535u, ((uint32_t) m + 255u) / 256u)), dim3(256), 0, pr, lbase, m, mode,
+                   super_init_bits(mode), d_sig));
     return KMU_OK;
 }
 

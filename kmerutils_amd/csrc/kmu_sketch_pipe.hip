@@ -54,9 +54,10 @@ extern "C" int kmu_sketch_count(kmu_ctx *ctx, const kmu_sketch_params *p_in, kmu
     const uint64_t off0 = n_seq ? offsets[0] : 0, total = n_seq ? offsets[n_seq] - off0 : 0;
     std::vector<uint64_t> h_off((size_t) n_seq + 1);
     for (uint32_t i = 0; i <= n_seq; i++) h_off[i] = offsets[i] - off0;
-    void *d_b, *d_o, *d_sig;
+    uint64_t *d_o;
+    void *d_b, *d_sig;
     KMU_TRY(dev_buf(ctx, "in.bases", total + 64, &d_b));
-    KMU_TRY(dev_buf(ctx, "in.offsets", ((size_t) n_seq + 1) * 8, &d_o));
+    KMU_TRY(dev_array(ctx, "in.offsets", (size_t) n_seq + 1, &d_o));
     KMU_TRY(dev_buf(ctx, "out.sig", (size_t) n_seq * rowb + 64, &d_sig));
     if (!ctx->pipe_h2d) KMU_HIP(ctx, hipStreamCreateWithFlags(&ctx->pipe_h2d, hipStreamNonBlocking));
     if (!ctx->pipe_d2h) KMU_HIP(ctx, hipStreamCreateWithFlags(&ctx->pipe_d2h, hipStreamNonBlocking));
@@ -139,7 +140,7 @@ extern "C" int kmu_sketch_count(kmu_ctx *ctx, const kmu_sketch_params *p_in, kmu
     };
     DevSeqs all;
     all.bases = (const uint8_t *) d_b;
-    all.offsets = (const uint64_t *) d_o;
+    all.offsets = d_o;
     all.n_seq = n_seq;
     all.total_bytes = total;
     // the count's level-1 partition runs under the upload too, for the part of the stream that has arrived
@@ -195,7 +196,7 @@ extern "C" int kmu_sketch_count(kmu_ctx *ctx, const kmu_sketch_params *p_in, kmu
         if (hipStreamWaitEvent(ctx->stream, ev_up[c], 0) != hipSuccess) { rc = fail(ctx, KMU_E_HIP, "hipStreamWaitEvent failed"); break; }
         if (packed_up && pk_bounds[c + 1] > pk_bounds[c]) {
             KernelTimer tm(ctx, "k_unpack2b");
-            rc = launch_unpack2b(ctx, (const uint8_t *) d_packed + pk_bounds[c] / 4, pk_bounds[c + 1] - pk_bounds[c], (uint8_t *) d_b + pk_bounds[c], ctx->stream);
+            rc = launch_unpack2b(ctx, (const uint8_t *) d_packed + pk_bounds[c] / 4, pk_bounds[c + 1] - pk_bounds[c], (uint8_t *) d_b + pk_bounds[c]);
             if (rc != KMU_OK) break;
         }
         rc = sketch_per_seq_device(ctx, p, ds, nullptr, nullptr, d_rows, d_err, h_off.data() + cut[c]);

@@ -46,12 +46,10 @@ struct PmhPlan {
 // count build uses for its first partition level ("cnt.partA"); a context never runs the two at the same time, and at
 // 4.4 Gbases per GPU a second copy would not fit next to the count table and the exchange buffers
 static int alloc_lists(kmu_ctx *ctx, SketchArgs &a, uint64_t bases) {
-    void *lk, *lw, *ln;
-    KMU_TRY(dev_buf(ctx, "cnt.partA", bases * 8 + 64, &lk));
-    KMU_TRY(dev_buf(ctx, "pmh.lst_w", bases * 4 + 64, &lw));
+    void *ln;
+    KMU_TRY(dev_array(ctx, "cnt.partA", bases + 8, &a.lst_keys));
+    KMU_TRY(dev_array(ctx, "pmh.lst_w", bases + 16, &a.lst_w));
     KMU_TRY(dev_buf(ctx, "pmh.lst_n", (size_t) a.n_seq * 8 + 64, &ln));
-    a.lst_keys = (uint64_t *) lk;
-    a.lst_w = (uint32_t *) lw;
     a.lst_n = (uint32_t *) ln;
     a.lst_nu = a.lst_n + a.n_seq;
     KMU_HIP(ctx, hipMemsetAsync(a.lst_nu, 0, (size_t) a.n_seq * 4, ctx->stream));
@@ -146,12 +144,9 @@ static int launch_points(kmu_ctx *ctx, SketchArgs a, int cus, uint32_t thr) {
     a.pts_long_t = thr;
     if (thr && a.n_seq) {
         if (thr < 1024u) a.pts_long_t = thr = 1024u; // (a workgroup's four waves all need chunks of their own)
-        void *pl;
-        KMU_TRY(dev_buf(ctx, "pts.long", ((size_t) a.n_seq + 2) * 4 + 64, &pl));
-        KMU_HIP(ctx, hipMemsetAsync(pl, 0, 8, ctx->stream));
-        a.pts_long = (uint32_t *) pl;
-        hipLaunchKernelGGL(k_pts_long_list, dim3((a.n_seq + 255) / 256), dim3(256), 0, ctx->stream, (const uint32_t *) a.lst_n, a.n_seq, thr,
-                           (uint32_t *) pl);
+        KMU_TRY(dev_array(ctx, "pts.long", (size_t) a.n_seq + 2 + 16, &a.pts_long));
+        KMU_HIP(ctx, hipMemsetAsync(a.pts_long, 0, 8, ctx->stream));
+        KMU_TRY(launch(ctx, nullptr, k_pts_long_list, dim3((a.n_seq + 255) / 256), dim3(256), 0, a.lst_n, a.n_seq, thr, a.pts_long));
     }
     // the a-priori q_max bound of pts_one_read.  KMU_PMH_TAU_C (read once per context): unset = PTS_TAU_C; 0 / off = no bound;
     // a negative c makes nearly every read fail the bound and start over (tests of that path)
@@ -167,19 +162,13 @@ static int launch_points(kmu_ctx *ctx, SketchArgs a, int cus, uint32_t thr) {
     a.tau_redo = (uint32_t *) tr;
     a.tau_num = (double) a.m * (std::log((double) a.m) + ctx->pmh_tau_c);
     a.tau_min_n = ctx->pmh_tau_c != 0.0 && a.tau_num > 0.0 ? (uint32_t) std::min(a.tau_num, 4.0e9) : 0xFFFFFFFFu;
-    KernelTimer t(ctx, "k_pmh_points");
-    hipLaunchKernelGGL(kpts, dim3(grid2), dim3(256), lds2, ctx->stream, a);
-    KMU_HIP(ctx, hipGetLastError());
-    return KMU_OK;
+    return launch(ctx, "k_pmh_points", kpts, dim3(grid2), dim3(256), lds2, a);
 }
 
 typedef void (*sketch_kernel_t)(SketchArgs);
 
 static int launch_main(kmu_ctx *ctx, const SketchArgs &a, sketch_kernel_t kern, int grid, size_t lds, const char *name) {
-    KernelTimer t(ctx, name);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(1024), lds, ctx->stream, a);
-    KMU_HIP(ctx, hipGetLastError());
-    return KMU_OK;
+    return launch(ctx, name, kern, dim3(grid), dim3(1024), lds, a);
 }
 
 static int launch_smallk(kmu_ctx *ctx, SketchArgs a, const PmhPlan &plan) {
@@ -247,20 +236,11 @@ static int pmh_shape(kmu_ctx *ctx, const kmu_sketch_params *p, SketchArgs &a, sk
     KMU_TRY(alloc_queue(ctx, a));
     g->slots = (uint64_t) cus * std::max<int>(1, (int) (lds_max / g->lds));
     g->grid = (int) std::max<uint64_t>(1, std::min<uint64_t>((uint64_t) a.n_seq, g->slots));
-    void *sk, *si, *sw, *dk;
-    KMU_TRY(dev_buf(ctx, "pmh.scr_keys", (size_t) g->grid * cap * 8, &sk));
-    KMU_TRY(dev_buf(ctx, "pmh.scr_info", (size_t) g->grid * cap * 4, &si));
-    KMU_TRY(dev_buf(ctx, "pmh.scr_w", (size_t) g->grid * cap * 4, &sw));
-    KMU_TRY(dev_buf(ctx, "pmh.def_keys", (size_t) g->grid * DEF_CAP * 8, &dk));
-    a.scr_keys = (uint64_t *) sk;
-    a.scr_info = (uint32_t *) si;
-    a.scr_w = (uint32_t *) sw;
-    a.def_keys = (uint64_t *) dk;
-    if (plain) {
-        void *rl;
-        KMU_TRY(dev_buf(ctx, "pmh.redo", (size_t) a.n_seq * 4 + 64, &rl));
-        a.redo_list = (uint32_t *) rl;
-    }
+    KMU_TRY(dev_array(ctx, "pmh.scr_keys", (size_t) g->grid * cap, &a.scr_keys));
+    KMU_TRY(dev_array(ctx, "pmh.scr_info", (size_t) g->grid * cap, &a.scr_info));
+    KMU_TRY(dev_array(ctx, "pmh.scr_w", (size_t) g->grid * cap, &a.scr_w));
+    KMU_TRY(dev_array(ctx, "pmh.def_keys", (size_t) g->grid * DEF_CAP, &a.def_keys));
+    if (plain) KMU_TRY(dev_array(ctx, "pmh.redo", (size_t) a.n_seq + 16, &a.redo_list));
     return KMU_OK;
 }
 
@@ -284,12 +264,9 @@ static int read_count(kmu_ctx *ctx, const SketchArgs &a, uint32_t *n) {
 static int launch_short(kmu_ctx *ctx, const SketchArgs &a, int cus) {
     const size_t lds_s = 4 * SHORT_WAVE_BYTES;
     const int per_cu = 5; // (88 registers: five waves per SIMD)
-    {
-        KernelTimer t(ctx, "k_multiset_short");
-        hipLaunchKernelGGL(k_multiset_short, dim3((unsigned) std::max<uint64_t>(1, std::min<uint64_t>(((uint64_t) a.n_seq + 3) / 4, (uint64_t) cus * per_cu))),
-                           dim3(256), lds_s, ctx->stream, a);
-    }
-    KMU_HIP(ctx, hipGetLastError());
+    KMU_TRY(launch(ctx, "k_multiset_short", k_multiset_short,
+                   dim3((unsigned) std::max<uint64_t>(1, std::min<uint64_t>(((uint64_t) a.n_seq + 3) / 4, (uint64_t) cus * per_cu))), dim3(256),
+                   lds_s, a));
     KMU_HIP(ctx, hipMemsetAsync(a.queue, 0, 256, ctx->stream)); // (the points kernel's cursor)
     const sketch_kernel_t kpts = a.sig_bytes == 4 ? k_pmh_points_short<true> : k_pmh_points_short<false>;
     const size_t lds2 = (size_t) 4 * (2 * (size_t) a.m + 2) * 8 + WINV_LUT * 8;
@@ -297,10 +274,7 @@ static int launch_short(kmu_ctx *ctx, const SketchArgs &a, int cus) {
         KMU_HIP(ctx, hipFuncSetAttribute((const void *) kpts, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     const int per_cu2 = (int) std::max<size_t>(1, std::min<size_t>(4, (160 * 1024) / lds2));
     const int grid2 = (int) std::max<uint64_t>(1, std::min<uint64_t>(((uint64_t) a.n_seq + 3) / 4, (uint64_t) cus * per_cu2));
-    KernelTimer t(ctx, "k_pmh_points_short");
-    hipLaunchKernelGGL(kpts, dim3(grid2), dim3(256), lds2, ctx->stream, a);
-    KMU_HIP(ctx, hipGetLastError());
-    return KMU_OK;
+    return launch(ctx, "k_pmh_points_short", kpts, dim3(grid2), dim3(256), lds2, a);
 }
 
 // Whole unpacked DNA reads on the two-kernel route: the reads that fit one workgroup's registers (<= 10 240 k-mers: 87 % of
@@ -312,29 +286,24 @@ static int launch_uq(kmu_ctx *ctx, SketchArgs a, sketch_kernel_t kern, const Pmh
         const auto ka = k_multiset_uq<512, UQ1_BM, UQ1_COLL, 4>;
         const size_t lds_a = UqShape<512, UQ1_BM, UQ1_COLL>::LDS;
         KMU_HIP(ctx, hipFuncSetAttribute((const void *) ka, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024));
-        KernelTimer t(ctx, "k_multiset_uq");
-        hipLaunchKernelGGL(ka, dim3((unsigned) std::max<uint64_t>(1, std::min<uint64_t>(a.n_seq, (uint64_t) plan.cus * 2))), dim3(512), lds_a,
-                           ctx->stream, a);
+        KMU_TRY(launch(ctx, "k_multiset_uq", ka, dim3((unsigned) std::max<uint64_t>(1, std::min<uint64_t>(a.n_seq, (uint64_t) plan.cus * 2))),
+                       dim3(512), lds_a, a));
     }
-    KMU_HIP(ctx, hipGetLastError());
     uint32_t n_long = 0;
     KMU_TRY(read_count(ctx, a, &n_long));
     if (n_long) { // the second shape: reads of up to 20 480 k-mers, from the first one's list
         const auto kb = k_multiset_uq<1024, UQ2_BM, UQ2_COLL, 4>;
         const size_t lds_b = UqShape<1024, UQ2_BM, UQ2_COLL>::LDS;
-        void *rl2;
-        KMU_TRY(dev_buf(ctx, "pmh.redo2", (size_t) a.n_seq * 4 + 64, &rl2));
+        uint32_t *rl2;
+        KMU_TRY(dev_array(ctx, "pmh.redo2", (size_t) a.n_seq + 16, &rl2));
         KMU_HIP(ctx, hipFuncSetAttribute((const void *) kb, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         KMU_HIP(ctx, hipMemsetAsync(a.queue, 0, 256, ctx->stream));
         SketchArgs b = a;
         b.read_list = a.redo_list;
-        b.redo_list = (uint32_t *) rl2;
+        b.redo_list = rl2;
         b.n_queue = n_long;
-        {
-            KernelTimer t(ctx, "k_multiset_uq");
-            hipLaunchKernelGGL(kb, dim3((unsigned) std::max<uint64_t>(1, std::min<uint64_t>(n_long, (uint64_t) plan.cus))), dim3(1024), lds_b, ctx->stream, b);
-        }
-        KMU_HIP(ctx, hipGetLastError());
+        KMU_TRY(launch(ctx, "k_multiset_uq", kb, dim3((unsigned) std::max<uint64_t>(1, std::min<uint64_t>(n_long, (uint64_t) plan.cus))), dim3(1024),
+                       lds_b, b));
         KMU_TRY(read_count(ctx, a, &n_long));
         a.redo_list = b.redo_list;
     }
@@ -453,7 +422,7 @@ int sketch_pmh_per_seq(kmu_ctx *ctx, const kmu_sketch_params *p, const DevSeqs &
             KMU_TRY(dev_buf(ctx, "pmh.maxlen", 64, &mx));
             KMU_HIP(ctx, hipMemsetAsync(mx, 0, 8, ctx->stream));
             const uint32_t mgrid = (uint32_t) std::min<uint64_t>(((uint64_t) n_seq + 1023) / 1024, (uint64_t) ctx->num_cus);
-            hipLaunchKernelGGL(k_max_len, dim3(mgrid ? mgrid : 1), dim3(1024), 0, ctx->stream, ds.offsets, n_seq, (uint64_t *) mx);
+            KMU_TRY(launch(ctx, nullptr, k_max_len, dim3(mgrid ? mgrid : 1), dim3(1024), 0, ds.offsets, n_seq, (uint64_t *) mx));
             KMU_HIP(ctx, hipMemcpyAsync(len_stats, mx, 16, hipMemcpyDeviceToHost, ctx->stream));
             KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
         }

@@ -259,11 +259,8 @@ __global__ void __launch_bounds__(256) k_super_reduce(const uint64_t *part_rows,
 
 int launch_super_reduce(kmu_ctx *ctx, const kmu_sketch_params *p, const uint64_t *part_rows, uint64_t n_parts, void *d_sig) {
     const int mode = super_mode(p);
-    KernelTimer t(ctx, "k_super_reduce");
-    hipLaunchKernelGGL(k_super_reduce, dim3((p->sketch_size + 255) / 256), dim3(256), 0, ctx->stream, part_rows, n_parts,
-                       p->sketch_size, mode, d_sig, ctx->partial_out);
-    KMU_HIP(ctx, hipGetLastError());
-    return KMU_OK;
+    return launch(ctx, "k_super_reduce", k_super_reduce, dim3((p->sketch_size + 255) / 256), dim3(256), 0, part_rows, n_parts, p->sketch_size, mode,
+                  d_sig, ctx->partial_out);
 }
 
 int launch_super(kmu_ctx *ctx, const kmu_sketch_params *p, const DevSeqs &ds, void *d_sig, uint32_t *d_err,
@@ -338,14 +335,7 @@ int launch_super(kmu_ctx *ctx, const kmu_sketch_params *p, const DevSeqs &ds, vo
         }
     }
     int blocks_per_cu = std::max<int>(1, std::min<int>(2048 / threads, (int) (lds_max / lds)));
-    int grid = (int) std::min<uint64_t>((uint64_t) ds.n_seq, (uint64_t) ctx->num_cus * blocks_per_cu);
-    if (grid < 1) grid = 1;
-    {
-        KernelTimer t(ctx, "k_sketch_super");
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), lds, ctx->stream, a);
-    }
-    KMU_HIP(ctx, hipGetLastError());
-    return KMU_OK;
+    return launch(ctx, "k_sketch_super", kern, dim3(grid_for(ctx, ds.n_seq, 1, blocks_per_cu)), dim3(threads), lds, a);
 }
 
 } // namespace kmu

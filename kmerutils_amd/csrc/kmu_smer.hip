@@ -529,10 +529,10 @@ int smer_census(kmu_ctx *ctx, const DevSeqs &ds, uint64_t total_bases, int k, ui
     g->n_parts = n_parts;
     g->units = units;
     g->steps_per_unit = spu;
-    void *tot;
+    uint64_t *tot;
     KMU_TRY(dev_buf(ctx, "smer.hist", (size_t) units * n_parts * 4 + 64, &g->hist));
     KMU_TRY(dev_buf(ctx, "smer.offs", (size_t) units * n_parts * 8 + 64, &g->offs));
-    KMU_TRY(dev_buf(ctx, "smer.tot", (size_t) n_parts * 8 + 64, &tot));
+    KMU_TRY(dev_array(ctx, "smer.tot", (size_t) n_parts + 8, &tot));
     KMU_TRY(dev_buf(ctx, "smer.binstart", ((size_t) n_parts + 1) * 8 + 64, &g->binstart));
     KMU_TRY(dev_buf(ctx, "smer.kmers", (size_t) n_parts * 8 + 64, &g->kmers));
     KMU_HIP(ctx, hipMemsetAsync(g->kmers, 0, (size_t) n_parts * 8, ctx->stream));
@@ -541,21 +541,16 @@ int smer_census(kmu_ctx *ctx, const DevSeqs &ds, uint64_t total_bases, int k, ui
     g->total = total_bases;
     const size_t lds = ((size_t) 2 * n_parts + 4) * 4 + (sa.list ? (size_t) SAMPLE_LDS * 8 : 0);
     const SmerCfg cf = smer_cfg(k);
-    {
-        KernelTimer tm(ctx, "k_smer_census");
-        KMU_TRY(smer_dispatch(cf.w, n_parts <= 8, [&](auto W, auto P8) {
-            hipLaunchKernelGGL((k_smer_census<decltype(W)::value, decltype(P8)::value>), dim3(units), dim3(SMER_THREADS), lds, ctx->stream, ds.bases,
-                               (const uint16_t *) g->novalid, total_bases, k, n_parts, spu, (uint32_t *) g->hist, (unsigned long long *) g->kmers, d_err, sa);
-            return (int) KMU_OK;
-        }));
-    }
+    KMU_TRY(smer_dispatch(cf.w, n_parts <= 8, [&](auto W, auto P8) {
+        return launch(ctx, "k_smer_census", k_smer_census<decltype(W)::value, decltype(P8)::value>, dim3(units), dim3(SMER_THREADS), lds, ds.bases,
+                      (const uint16_t *) g->novalid, total_bases, k, n_parts, spu, (uint32_t *) g->hist, (unsigned long long *) g->kmers, d_err, sa);
+    }));
     {
         KernelTimer tm(ctx, "k_smer_scan");
-        hipLaunchKernelGGL(k_smer_scan_a, dim3(n_parts), dim3(256), 0, ctx->stream, (const uint32_t *) g->hist, units, n_parts, (uint64_t *) g->offs,
-                           (uint64_t *) tot);
-        hipLaunchKernelGGL(k_smer_scan_b, dim3(1), dim3(64), 0, ctx->stream, (const uint64_t *) tot, n_parts, (uint64_t *) g->binstart);
+        KMU_TRY(launch(ctx, nullptr, k_smer_scan_a, dim3(n_parts), dim3(256), 0, (const uint32_t *) g->hist, units, n_parts, (uint64_t *) g->offs,
+                       tot));
+        KMU_TRY(launch(ctx, nullptr, k_smer_scan_b, dim3(1), dim3(64), 0, tot, n_parts, (uint64_t *) g->binstart));
     }
-    KMU_HIP(ctx, hipGetLastError());
     return KMU_OK;
 }
 
@@ -563,44 +558,34 @@ int flat_novalid(kmu_ctx *ctx, const DevSeqs &ds, uint64_t total_bases, int k, u
     const uint64_t mask_bytes = (n_words * 2 + 3) & ~(uint64_t) 3;
     KMU_TRY(dev_buf(ctx, buf_name, (size_t) mask_bytes + 64, out));
     KMU_HIP(ctx, hipMemsetAsync(*out, 0, (size_t) mask_bytes, ctx->stream));
-    hipLaunchKernelGGL(k_smer_novalid, dim3((unsigned) (((uint64_t) ds.n_seq + 2 + 255) / 256)), dim3(256), 0, ctx->stream, ds.offsets, ds.n_seq, k,
-                       total_bases, (uint64_t) mask_bytes * 8, (uint32_t *) *out);
-    KMU_HIP(ctx, hipGetLastError());
-    return KMU_OK;
+    return launch(ctx, nullptr, k_smer_novalid, dim3((unsigned) (((uint64_t) ds.n_seq + 2 + 255) / 256)), dim3(256), 0, ds.offsets, ds.n_seq, k,
+                  total_bases, (uint64_t) mask_bytes * 8, (uint32_t *) *out);
 }
 
 int smer_scatter(kmu_ctx *ctx, const DevSeqs &ds, uint64_t total_bases, const SmerGroups &g, void *records_out) {
     if (g.units == 0 || total_bases != g.total) return g.units == 0 ? (int) KMU_OK : fail(ctx, KMU_E_BAD_ARG, "smer_scatter: not the batch of the census");
     const size_t lds = (size_t) g.n_parts * 12 + 4 * 8 * 4 + 16;
     const SmerCfg cf = smer_cfg(g.k);
-    KernelTimer tm(ctx, "k_smer_scatter");
-    KMU_TRY(smer_dispatch(cf.w, g.n_parts <= 8, [&](auto W, auto P8) {
-        hipLaunchKernelGGL((k_smer_scatter<decltype(W)::value, decltype(P8)::value>), dim3(g.units), dim3(SMER_THREADS), lds, ctx->stream, ds.bases,
-                           (const uint16_t *) g.novalid, g.total, g.k, g.n_parts, g.steps_per_unit, (const uint64_t *) g.offs,
-                           (const uint64_t *) g.binstart, (uint32_t *) records_out);
-        return (int) KMU_OK;
-    }));
-    KMU_HIP(ctx, hipGetLastError());
-    return KMU_OK;
+    return smer_dispatch(cf.w, g.n_parts <= 8, [&](auto W, auto P8) {
+        return launch(ctx, "k_smer_scatter", k_smer_scatter<decltype(W)::value, decltype(P8)::value>, dim3(g.units), dim3(SMER_THREADS), lds,
+                      ds.bases, (const uint16_t *) g.novalid, g.total, g.k, g.n_parts, g.steps_per_unit, (const uint64_t *) g.offs,
+                      (const uint64_t *) g.binstart, (uint32_t *) records_out);
+    });
 }
 
 int smer_count_kmers(kmu_ctx *ctx, const void *records, uint64_t n, uint64_t *d_out) {
     KMU_HIP(ctx, hipMemsetAsync(d_out, 0, 8, ctx->stream));
     if (!n) return KMU_OK;
     const int grid = (int) std::min<uint64_t>(std::max<uint64_t>((n + 255) / 256, 8), (uint64_t) ctx->num_cus * 8);
-    hipLaunchKernelGGL(k_smer_count_kmers, dim3(grid), dim3(256), 0, ctx->stream, (const uint32_t *) records, n, (unsigned long long *) d_out);
-    KMU_HIP(ctx, hipGetLastError());
-    return KMU_OK;
+    return launch(ctx, nullptr, k_smer_count_kmers, dim3(grid), dim3(256), 0, (const uint32_t *) records, n, (unsigned long long *) d_out);
 }
 
 int smer_expand(kmu_ctx *ctx, const void *records, uint64_t n, int k, uint64_t *out, uint64_t *d_cursor) {
     KMU_HIP(ctx, hipMemsetAsync(d_cursor, 0, 8, ctx->stream));
     if (!n) return KMU_OK;
-    const int grid = (int) std::min<uint64_t>((n + 255) / 256, (uint64_t) ctx->num_cus * 8);
-    KernelTimer tm(ctx, "k_smer_expand");
-    hipLaunchKernelGGL(k_smer_expand, dim3(grid), dim3(256), 0, ctx->stream, (const uint32_t *) records, n, k, out, (unsigned long long *) d_cursor);
-    KMU_HIP(ctx, hipGetLastError());
-    return KMU_OK;
+    const int grid = grid_for(ctx, n, 256);
+    return launch(ctx, "k_smer_expand", k_smer_expand, dim3(grid), dim3(256), 0, (const uint32_t *) records, n, k, out,
+                  (unsigned long long *) d_cursor);
 }
 
 } // namespace kmu

@@ -88,29 +88,29 @@ static inline int radix_sort_pairs_passes(kmu_ctx *ctx, uint64_t *&k0, uint32_t 
     if (n == 0) return KMU_OK;
     if (n > 0xFFFFFFFFull) return fail(ctx, KMU_E_UNSUPPORTED, "radix_sort_pairs: %llu entries, more than 2^32 - 1", (unsigned long long) n);
     const uint32_t n_tiles = (uint32_t) ((n + SORT_TILE - 1) / SORT_TILE);
-    void *hist, *offs;
-    KMU_TRY(dev_buf(ctx, "sort.hist", (size_t) n_tiles * 256 * 4, &hist));
-    KMU_TRY(dev_buf(ctx, "sort.offs", ((size_t) n_tiles * 256 + 1) * 8, &offs));
+    uint64_t *offs;
+    uint32_t *hist;
+    KMU_TRY(dev_array(ctx, "sort.hist", (size_t) n_tiles * 256, &hist));
+    KMU_TRY(dev_array(ctx, "sort.offs", (size_t) n_tiles * 256 + 1, &offs));
     for (uint32_t pass = 0; pass < 8; pass++) {
         if (!((pass_mask >> pass) & 1u)) continue;
         const uint32_t shift = 8 * pass;
-        {
-            KernelTimer t(ctx, "k_sort_hist");
-            hipLaunchKernelGGL(k_sort_hist, dim3(n_tiles), dim3(64), 0, ctx->stream, (const uint64_t *) k0, n, n_dev, shift, n_tiles,
-                               (uint32_t *) hist);
-        }
-        KMU_HIP(ctx, hipGetLastError());
-        KMU_TRY(device_scan_u32(ctx, (const uint32_t *) hist, (uint64_t) n_tiles * 256, (uint64_t *) offs));
-        {
-            KernelTimer t(ctx, "k_sort_scatter");
-            hipLaunchKernelGGL(k_sort_scatter, dim3(n_tiles), dim3(64), 0, ctx->stream, (const uint64_t *) k0, (const uint32_t *) v0, n,
-                               n_dev, shift, n_tiles, (const uint64_t *) offs, k1, v1);
-        }
-        KMU_HIP(ctx, hipGetLastError());
+        KMU_TRY(launch(ctx, "k_sort_hist", k_sort_hist, dim3(n_tiles), dim3(64), 0, (const uint64_t *) k0, n, n_dev, shift, n_tiles, hist));
+        KMU_TRY(device_scan_u32(ctx, hist, (uint64_t) n_tiles * 256, offs));
+        KMU_TRY(launch(ctx, "k_sort_scatter", k_sort_scatter, dim3(n_tiles), dim3(64), 0, (const uint64_t *) k0, (const uint32_t *) v0, n, n_dev,
+                       shift, n_tiles, offs, k1, v1));
         std::swap(k0, k1);
         std::swap(v0, v1);
     }
     return KMU_OK;
+}
+
+// the pass_mask that can tell two ids below n apart: one bit per byte of n - 1 (at least the lowest)
+static inline uint32_t radix_id_passes(uint32_t n) {
+    uint32_t m = 1, top = n - 1;
+    for (uint32_t b = 1; b < 4; b++)
+        if (top >> (8 * b)) m |= 1u << b;
+    return m;
 }
 
 // Sorts the n entries (k0[i], v0[i]) by key, ascending; entries of equal keys keep their order.  (k1, v1) is scratch of the same
