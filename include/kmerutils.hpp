@@ -1744,6 +1744,83 @@ ReadClusters read_clusters(const std::vector<ReadAnchors<Kmer>> &reads, const An
 }
 
 // =====================================================================================================================
+// window minimizers (kmu_read_minimizers; the reference has no such unit)
+// =====================================================================================================================
+
+/// fhash of every k-mer of a batch as kmu_kmer_hashes lays them out: entry offsets[i] + p is position p of sequence i
+/// (uint64, zero-extended for the u32 types); the last k - 1 entries of a sequence are 0
+template <class Kmer>
+std::vector<uint64_t> kmer_hashes(const detail::Batch &b, size_t k, FHash fhash, Context &ctx = Context::global()) {
+    if (b.on_device()) throw std::invalid_argument("kmer_hashes returns host arrays: it needs the sequences in host memory");
+    kmu_hash_params hp{};
+    hp.kmer_type = Kmer::kmu_type;
+    hp.kmer_size = int32_t(k);
+    hp.fhash = int(fhash);
+    hp.input_kind = b.input_kind;
+    hp.mem = KMU_MEM_HOST;
+    std::vector<uint64_t> out(std::max<uint64_t>(b.offsets.back(), 1), 0);
+    ctx.check(kmu_kmer_hashes(ctx.raw(), &hp, b.bytes.data(), b.offsets.data(), b.packed_ptr(), b.n(), out.data()));
+    return out;
+}
+
+/// kmu_minimizer_layout: win_offsets[n + 1], the windows of w k-mers of every sequence -- an upper bound of its minimizers
+inline std::vector<uint64_t> minimizer_layout(const detail::Batch &b, size_t k, uint32_t w) {
+    std::vector<uint64_t> win(b.offsets.size());
+    const int rc = kmu_minimizer_layout(b.offsets.data(), b.n(), uint32_t(k), w, win.data());
+    if (rc != KMU_OK) throw KmuError(rc, "kmu_minimizer_layout: kmer_size > 0 and 1 <= w <= KMU_MINIMIZER_MAX_W");
+    return win;
+}
+
+/// The (w, k) window minimizers of a batch: entries offsets[i] .. offsets[i + 1] are those of sequence i, ascending in position;
+/// hashes[e] is the kmer_hashes value of position pos[e] of sequence read[e], strand[e] = 1 iff that k-mer's reverse complement
+/// is the smaller one under a canonical fhash (empty under the ntHash orders, which expose no strand).
+struct Minimizers {
+    std::vector<uint64_t> hashes;
+    std::vector<uint32_t> pos, read;
+    std::vector<uint8_t> strand;
+    std::vector<uint64_t> offsets;
+    size_t size() const { return hashes.size(); }
+};
+
+/// kmu_read_minimizers in one call: the window count of kmu_minimizer_layout is the capacity, so nothing is counted first.
+/// Per window of w consecutive k-mers the position of smallest hash, ties to the smallest position, each chosen position once
+/// (include/kmu.h has the rules).  FHash::canon_invhash is the recommended order.
+template <class Kmer>
+Minimizers read_minimizers(const detail::Batch &batch, size_t k, uint32_t w, FHash fhash = FHash::canon_invhash,
+                           Context &ctx = Context::global()) {
+    const detail::Batch b = detail::unpacked(batch);
+    if (b.on_device()) throw std::invalid_argument("read_minimizers returns host arrays: it needs the sequences in host memory");
+    const bool with_strand = fhash != FHash::canon_nthash && fhash != FHash::canon_nthash_8b;
+    const uint64_t cap = minimizer_layout(b, k, w).back();
+    kmu_hash_params hp{};
+    hp.kmer_type = Kmer::kmu_type;
+    hp.kmer_size = int32_t(k);
+    hp.fhash = int(fhash);
+    hp.input_kind = KMU_INPUT_ASCII;
+    hp.mem = KMU_MEM_HOST;
+    Minimizers m;
+    const size_t room = size_t(std::max<uint64_t>(cap, 1)); // an empty vector has no address worth passing
+    m.hashes.assign(room, 0);
+    m.pos.assign(room, 0);
+    m.read.assign(room, 0);
+    if (with_strand) m.strand.assign(room, 0);
+    m.offsets.assign(b.offsets.size(), 0);
+    uint64_t total = 0;
+    ctx.check(kmu_read_minimizers(ctx.raw(), &hp, b.bytes.data(), b.offsets.data(), b.n(), w, m.hashes.data(), m.pos.data(), m.read.data(),
+                                  with_strand ? m.strand.data() : nullptr, cap, m.offsets.data(), &total));
+    m.hashes.resize(size_t(total));
+    m.pos.resize(size_t(total));
+    m.read.resize(size_t(total));
+    if (with_strand) m.strand.resize(size_t(total));
+    return m;
+}
+template <class Kmer>
+Minimizers read_minimizers(const std::vector<const Sequence *> &seqs, size_t k, uint32_t w, FHash fhash = FHash::canon_invhash,
+                           Context &ctx = Context::global()) {
+    return read_minimizers<Kmer>(detail::gather(seqs), k, w, fhash, ctx);
+}
+
+// =====================================================================================================================
 // counting (kmercount.rs)
 // =====================================================================================================================
 

@@ -812,6 +812,56 @@ int kmu_components_knn(kmu_ctx *ctx, uint32_t n_nodes, const uint32_t *idx, cons
                        int mem, uint32_t *label_out, uint32_t *cluster_out, uint32_t *size_out, uint32_t *members_out,
                        uint32_t *n_components_out);
 
+/* ---- window minimizers: the (w, k) minimizers of every read, selected on the device ---------------------------------
+ * Read i has L bases and nk = max(0, L - k + 1) k-mers.  h(p), p in [0, nk), is exactly the value kmu_kmer_hashes writes at
+ * out[offsets[i] + p] for the same kmu_hash_params: 64-bit, zero-extended for the u32 types, p->fhash applied.
+ * Windows (only when nk > 0): window j covers the positions [j, min(j + w, nk)) for j = 0 .. max(nk - w, 0); a read with
+ *   1 <= nk <= w has the single window of all its k-mers; a read with nk == 0 has no window, no minimizer and is no error.
+ * Selection: the minimizer of a window is its position of smallest h; TIES GO TO THE SMALLEST POSITION.  The minimizers of a
+ *   read are the distinct positions its windows choose.  With this tie rule the chosen position never decreases from one window
+ *   to the next, so "distinct" is "differs from the previous window's choice" and the result is strictly ascending in position.
+ * Outputs: the minimizers of all reads, concatenated in read order, in position order within a read;
+ *   mini_offsets_out[i] .. mini_offsets_out[i + 1] are the entries of read i.  Entry e of read i at position p:
+ *   hashes_out[e] = h(p), pos_out[e] = p, read_out[e] = i, strand_out[e] = 1 iff the reverse complement's value is numerically
+ *   smaller than the forward value under KMU_FHASH_CANON_RAW / _VALUE / _INVHASH (the k-mer the hash was taken of is the reverse
+ *   complement; a palindrome gets 0), and 0 under the fhash modes that do not canonicalise.  The two ntHash modes are accepted
+ *   for the ordering; a non-NULL strand_out with them is KMU_E_UNSUPPORTED (the canonical ntHash does not expose its strand here).
+ * Properties: w = 1 returns every k-mer.  A read that is one k-mer repeated (poly-A) returns every window start 0 .. nwin - 1 and
+ *   nothing behind it -- the usual dense behaviour of a leftmost tie rule.  KMU_FHASH_CANON_INVHASH is the recommended order:
+ *   under KMU_FHASH_CANON_VALUE poly-A is everyone's minimizer.  The result is a pure function of the inputs: it does not depend
+ *   on the launch shape or on timing.
+ * Counts and capacity: *n_out (host memory in both modes, required) is always the total number of minimizers.
+ *   hashes_out == NULL is the count-only call: it writes *n_out and, if given, mini_offsets_out, and nothing else.
+ *   cap < total: KMU_E_BAD_ARG with *n_out set and the outputs unspecified.  win_offsets[n_seq] of kmu_minimizer_layout (the
+ *   windows of the reads) is always a sufficient cap: a caller who takes it can skip the count-only call.
+ * KMU_MEM_DEVICE: every array except n_out is device memory (mini_offsets_out lives where `offsets` lives); the call synchronises
+ *   the stream once to hand n_out over, also in async_device contexts.  (The per-tile counts live in a workspace that, like every
+ *   workspace of the context, only grows: a call with more tiles than any call before it on this context counts a second time.)
+ *   The offsets are trusted, as kmu_sketch trusts block_row_offsets.
+ * KMU_MEM_HOST: the inputs go up through the context's workspace and the results come back, as in kmu_read_anchors; a read of
+ *   2^32 bases or more is KMU_E_UNSUPPORTED (positions are uint32).
+ * n_seq == 0: KMU_OK, *n_out = 0.  Empty reads and reads shorter than k contribute nothing.
+ * KMU_E_BAD_ARG: null ctx / p / n_out, w == 0, bad mem.  KMU_E_UNSUPPORTED: w > KMU_MINIMIZER_MAX_W, KMU_INPUT_PACKED2.
+ * KMU_E_BAD_ALPHABET: an amino-acid k-mer type.  A k-mer type and k that kmu_kmer_hashes refuses is refused the same way.  A
+ * non-ACGT byte anywhere in a read (reads shorter than k included) is KMU_E_NON_ACGT, reported as kmu_read_anchors reports it.
+ * How: one wave per tile of KMU_MINIMIZER_TILE consecutive windows of one read, tiles dealt grid-stride, so a chromosome spreads
+ *   over the device as many short reads do; neither the launches nor the host synchronisations of a call depend on the number or
+ *   the lengths of the reads.  DESIGN.md 3.14 has the kernel. */
+#define KMU_MINIMIZER_MAX_W 256
+#define KMU_MINIMIZER_TILE 1024 /* windows one workgroup takes at a time */
+/* windows per read = an upper bound of its minimizers; win_offsets_out[n_seq + 1]; plain host C, no context, no device (like
+ * kmu_anchor_layout).  KMU_E_BAD_ARG: null pointers, kmer_size == 0, w == 0 or > KMU_MINIMIZER_MAX_W. */
+int kmu_minimizer_layout(const uint64_t *offsets, uint32_t n_seq, uint32_t kmer_size, uint32_t w, uint64_t *win_offsets_out);
+int kmu_read_minimizers(kmu_ctx *ctx, const kmu_hash_params *p, const uint8_t *bases, const uint64_t *offsets, uint32_t n_seq,
+                        uint32_t w,
+                        uint64_t *hashes_out,       /* NULL: the count-only call */
+                        uint32_t *pos_out,          /* may be NULL */
+                        uint32_t *read_out,         /* may be NULL */
+                        uint8_t *strand_out,        /* may be NULL */
+                        uint64_t cap,
+                        uint64_t *mini_offsets_out, /* n_seq + 1, lives where `offsets` lives; may be NULL */
+                        uint64_t *n_out);           /* host memory in both modes; required */
+
 #ifdef __cplusplus
 }
 #endif

@@ -28,6 +28,8 @@ ANCHOR_TILE_KMERS = 768  # ... and the k-mers of a window it selects from at a t
 ANCHOR_SORT_TILE = 1024  # kmu_anchor_match: the index entries one workgroup ranks per radix pass
 OVL_MAX_BAND = 8         # kmu_anchor_overlaps: the widest band
 OVL_UPPER = 1            # ... and its flag: only read pairs with read_a < read_b
+MINIMIZER_MAX_W = 256    # kmu_read_minimizers: the widest window (in k-mers)
+MINIMIZER_TILE = 1024    # ... and the windows one workgroup takes at a time
 
 
 def kmer_val_bytes(kmer_type):

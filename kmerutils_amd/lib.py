@@ -36,6 +36,7 @@ SYMBOLS = [
     "kmu_count_histogram", "kmu_count_read_profile", "kmu_anchor_layout", "kmu_read_anchors", "kmu_anchor_match",
     "kmu_anchor_overlaps", "kmu_anchor_index_create", "kmu_anchor_index_destroy", "kmu_anchor_index_info",
     "kmu_anchor_index_occupancy", "kmu_anchor_index_match", "kmu_components", "kmu_components_knn",
+    "kmu_minimizer_layout", "kmu_read_minimizers",
 ]
 
 
@@ -44,6 +45,7 @@ SYMBOLS = [
 # field that was not asked for is None
 Components = collections.namedtuple("Components", "label cluster size members n_components")
 COMPONENTS_WANT = ("cluster", "size", "members")
+MINIMIZERS_WANT = ("pos", "read", "strand")  # the optional outputs of Context.read_minimizers
 
 
 class KmuError(RuntimeError):
@@ -138,6 +140,8 @@ def load():
     u32p = C.POINTER(C.c_uint32)
     L.kmu_components.argtypes = [vp, C.c_uint32, vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, vp, vp, vp, vp, u32p]
     L.kmu_components_knn.argtypes = [vp, C.c_uint32, vp, vp, C.c_uint32, C.c_uint32, C.c_int, vp, vp, vp, vp, u32p]
+    L.kmu_minimizer_layout.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp]
+    L.kmu_read_minimizers.argtypes = [vp, C.POINTER(A.HashParams), vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp, C.c_uint64, vp, u64p]
     L.kmu_set_hll_params.argtypes = [vp, C.POINTER(A.HllParams)]
     L.kmu_kmer_hashes_compact.argtypes = [vp, C.POINTER(A.HashParams), vp, vp, vp, C.c_uint32, vp, C.c_uint64, u64p]
     L.kmu_sketch_partial_words.argtypes = [C.POINTER(A.SketchParams)]
@@ -183,7 +187,7 @@ class _StreamOrdered:
     Doing it here, at the one place every call passes through, covers the buffers of every present and future method."""
 
     _PLAIN = ("kmu_last_error", "kmu_destroy", "kmu_stream", "kmu_version", "kmu_device_count", "kmu_create",
-              "kmu_block_layout", "kmu_anchor_layout", "kmu_sketch_partial_words", "kmu_count_destroy", "kmu_comm_get_id", "kmu_comm_rank",
+              "kmu_block_layout", "kmu_anchor_layout", "kmu_minimizer_layout", "kmu_sketch_partial_words", "kmu_count_destroy", "kmu_comm_get_id", "kmu_comm_rank",
               "kmu_comm_nranks", "kmu_comm_get_stats", "kmu_kmer_owner", "kmu_comm_destroy", "kmu_anchor_index_info", "kmu_anchor_index_destroy")
 
     def __init__(self, lib, ctx):
@@ -572,6 +576,36 @@ class Context:
         self._check(self.L.kmu_read_anchors(self.h, C.byref(p), _ptr(bases)[0], _ptr(offsets)[0], nseq, window, overlap,
                                             _ptr(d_rows)[0], _ptr(hashes)[0], _ptr(counts)[0], _ptr(n)[0]))
         return hashes[:rows], (counts[:rows] if want_counts else None), n[:rows], row_offsets
+
+    def read_minimizers(self, bases, offsets, kmer_type, k, fhash, w, want=MINIMIZERS_WANT):
+        """kmu_read_minimizers: the (w, k) window minimizers of every read -- per window of w consecutive k-mers the position of
+        smallest kmer_hashes value, ties to the smallest position, each chosen position once (include/kmu.h has the rules).
+        Returns (hashes, pos, read, strand, mini_offsets): the minimizers of read i are the entries mini_offsets[i] ..
+        mini_offsets[i + 1], ascending in position; `want` names the optional outputs to compute ("pos", "read", "strand"), the
+        others are None (the ntHash orders have no strand: leave it out).  numpy in gives numpy out (uint64 / uint32 / uint8);
+        torch cuda tensors stay on the device (int64 / int32 / uint8 tensors holding the same bits).  Two library calls: one
+        that counts, one with exactly that capacity."""
+        unknown = [x for x in want if x not in MINIMIZERS_WANT]
+        if unknown:
+            raise ValueError("want holds %r: the optional outputs are %r" % (unknown, MINIMIZERS_WANT))
+        n = len(offsets) - 1
+        mem = self._mem(bases, offsets)
+        hp = A.HashParams(kmer_type, k, fhash, A.INPUT_ASCII, mem, 0)
+        moff = self._new_like(bases, n + 1, np.uint64, "int64")
+        total = C.c_uint64(0)
+        args = (self.h, C.byref(hp), _ptr(bases)[0], _ptr(offsets)[0], n, int(w))
+        # (the strand pointer of the count-only call is NULL: an ntHash order is refused only where a strand is asked for)
+        self._check(self.L.kmu_read_minimizers(*args, None, None, None, None, 0, _ptr(moff)[0], C.byref(total)))
+        m = int(total.value)
+        hashes = self._new_like(bases, max(m, 1), np.uint64, "int64")
+        pos = self._new_like(bases, max(m, 1), np.uint32, "int32") if "pos" in want else None
+        read = self._new_like(bases, max(m, 1), np.uint32, "int32") if "read" in want else None
+        strand = self._new_like(bases, max(m, 1), np.uint8, "uint8") if "strand" in want else None
+        if m or strand is not None:  # (with no minimizer at all the call still says whether a strand can be had)
+            self._check(self.L.kmu_read_minimizers(*args, _ptr(hashes)[0], _ptr(pos)[0], _ptr(read)[0], _ptr(strand)[0], m, None,
+                                                   C.byref(total)))
+        return hashes[:m], (pos[:m] if pos is not None else None), (read[:m] if read is not None else None), \
+            (strand[:m] if strand is not None else None), moff
 
     def sketch_count(self, bases, offsets, params, counter=None, out=None):
         """kmu_sketch_count: the reads once, both results -- signature rows (returned) and, if `counter` is given, the
@@ -1213,6 +1247,18 @@ def anchor_layout(offsets_host, window, overlap):
     rc = L.kmu_anchor_layout(_ptr(off)[0], off.size - 1, window, overlap, _ptr(out)[0])
     if rc:
         raise KmuError(rc, "kmu_anchor_layout: window %d, overlap %d" % (window, overlap))
+    return out
+
+
+def minimizer_layout(offsets_host, k, w):
+    """kmu_minimizer_layout: win_offsets[n_seq + 1], the windows of w k-mers of reads given by host offsets -- an upper bound of
+    their minimizers, and a sufficient `cap` of kmu_read_minimizers (no device needed)"""
+    L = load()
+    off = np.ascontiguousarray(offsets_host, dtype=np.uint64)
+    out = np.zeros(off.size, np.uint64)
+    rc = L.kmu_minimizer_layout(_ptr(off)[0], off.size - 1, k, w, _ptr(out)[0])
+    if rc:
+        raise KmuError(rc, "kmu_minimizer_layout: k %d, w %d" % (k, w))
     return out
 
 

@@ -1,0 +1,68 @@
+"""Window minimizers of reads: base-resolution seeds, and the hits between them.
+
+`read_minimizers` runs kmu_read_minimizers over a batch of reads and returns a `Minimizers` record; `seed_hits` joins the
+minimizers of different reads that carry the same hash.  The join is the anchor index as it is (ctx.anchor_index /
+AnchorIndex.match): every minimizer is a row of ONE hash (m = 1, n_keys = 1) and its read is its group, so a hit is a pair of rows
+of different reads with that hash in common.  A hash equal to UINT64_MAX is the padding of the index's rows: such a minimizer is
+an empty row there and seeds nothing.
+"""
+import collections
+
+import numpy as np
+
+from . import _abi as A
+
+# the minimizers of a batch (Context.read_minimizers): entries offsets[i] .. offsets[i + 1] belong to read i, ascending in
+# position; hashes / pos / read / strand are numpy arrays or torch cuda tensors; k, w, fhash say how they were chosen
+Minimizers = collections.namedtuple("Minimizers", "hashes pos read strand offsets k w fhash")
+
+
+def read_minimizers(ctx, bases, offsets, k, w, fhash=A.FHASH_CANON_INVHASH, kmer_type=None):
+    """The (w, k) minimizers of every read of a batch as a Minimizers record; the k-mer type defaults to the reference's choice
+    for k.  The ntHash orders have no strand: the record's strand is then None."""
+    if kmer_type is None:
+        kmer_type = A.kmer_type_for_k(k)
+    nthash = fhash in (A.FHASH_CANON_NTHASH, A.FHASH_CANON_NTHASH_8B)
+    want = ("pos", "read") if nthash else ("pos", "read", "strand")
+    hashes, pos, read, strand, moff = ctx.read_minimizers(bases, offsets, kmer_type, k, fhash, w, want=want)
+    return Minimizers(hashes, pos, read, strand, moff, int(k), int(w), int(fhash))
+
+
+def _is_torch(x):
+    return type(x).__module__.startswith("torch")
+
+
+def _gather6(pairs, q, db):
+    """(read_a, pos_a, strand_a, read_b, pos_b, strand_b) of the row pairs, int64, where the arrays live"""
+    cols = []
+    if _is_torch(pairs):
+        import torch
+        idx = pairs.long() & 0xFFFFFFFF
+        for side, m in ((0, q), (1, db)):
+            i = idx[:, side]
+            for x in (m.read, m.pos, m.strand):
+                cols.append(torch.zeros_like(i) if x is None else x[i].long() & 0xFFFFFFFF)
+        return torch.stack(cols, dim=1) if cols[0].numel() else torch.zeros((0, 6), dtype=torch.int64, device=pairs.device)
+    idx = np.asarray(pairs).astype(np.int64)
+    for side, m in ((0, q), (1, db)):
+        i = idx[:, side]
+        for x in (m.read, m.pos, m.strand):
+            cols.append(np.zeros(i.shape, np.int64) if x is None else np.asarray(x)[i].astype(np.int64))
+    return np.stack(cols, axis=1) if idx.shape[0] else np.zeros((0, 6), np.int64)
+
+
+def seed_hits(ctx, q, db=None, max_occ=0):
+    """Minimizers of different reads that share a hash.  q, db: Minimizers records (numpy, or torch on the device -- the join
+    then runs on the resident arrays and the hits stay there).  db=None is the self-join of a batch: a minimizer never hits one
+    of its own read, and (a, b) and (b, a) are both there.  With a db of its own every equal hash is a hit (the two batches
+    number their reads independently).  max_occ > 0: a hash that more than max_occ minimizers of db carry seeds nothing (the
+    repeat mask of the anchor index).  Returns an int64 array [n, 6] of records (read_a, pos_a, strand_a, read_b, pos_b,
+    strand_b), a of q and b of db, ordered by the entry of q, then the entry of db; a record's strands are 0 where the minimizers
+    were made without.  A hash equal to UINT64_MAX seeds nothing: it is the padding of the index's rows."""
+    own = db is None
+    if own:
+        db = q
+    rows_q, rows_db = q.hashes.reshape(-1, 1), db.hashes.reshape(-1, 1)
+    with ctx.anchor_index(rows_db, n_keys=1, group_db=db.read if own else None) as index:
+        pairs, _ = index.match(rows_q, group_q=q.read if own else None, min_common=1, max_occ=int(max_occ))
+    return _gather6(pairs, q, db)
