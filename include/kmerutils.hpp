@@ -26,6 +26,8 @@
  *                 Overlap, anchor_overlaps, read_overlaps (read pairs from matched slices)  (beyond the reference)
  *                 Components, components, components_knn, ReadClusters, read_clusters       (beyond the reference)
  *                                                            (connected components of overlap records / neighbour lists)
+ *                 seed_chains, seed_pairs, chain_hits, read_chains (one base-resolution chain per read pair from minimizer
+ *                                                            hits)                          (beyond the reference)
  *   counting      KmerCountT (trait), KmerCounter, KmerCounterPool, count_kmer_threaded_one_to_many
  *                                                            src/base/kmercount.rs:48-123, 424-565, 881-974
  *   io            FASTQ reader rule, signature / count dumps src/io.rs:12-72, src/bin/datasketcher.rs:358-388,
@@ -1818,6 +1820,72 @@ template <class Kmer>
 Minimizers read_minimizers(const std::vector<const Sequence *> &seqs, size_t k, uint32_t w, FHash fhash = FHash::canon_invhash,
                            Context &ctx = Context::global()) {
     return read_minimizers<Kmer>(detail::gather(seqs), k, w, fhash, ctx);
+}
+
+// =====================================================================================================================
+// seed chaining (kmu_seed_chains; the reference has no such unit)
+// =====================================================================================================================
+
+/// kmu_seed_chains on host arrays: one chain per read pair behind `pairs` (2 per pair: an entry of q, an entry of db, in any order),
+/// one kmu_chain each, ordered by (read_a, read_b) (include/kmu.h has the rules).  The count call, then the write call.
+inline std::vector<kmu_chain> seed_chains(const std::vector<uint32_t> &pairs, const Minimizers &q, const Minimizers &db,
+                                          const kmu_chain_params &p, Context &ctx = Context::global()) {
+    if (q.offsets.empty() || db.offsets.empty()) throw std::invalid_argument("seed_chains: offsets hold n_reads + 1 entries");
+    if (q.read.size() != q.pos.size() || db.read.size() != db.pos.size() || (!q.strand.empty() && q.strand.size() != q.pos.size()) ||
+        (!db.strand.empty() && db.strand.size() != db.pos.size()))
+        throw std::invalid_argument("seed_chains: pos, read and strand hold one value per minimizer");
+    const uint64_t n_pairs = pairs.size() / 2;
+    const uint32_t none[2] = {0, 0}; // an empty vector has no address worth passing
+    auto call = [&](kmu_chain *out, uint64_t cap, uint64_t *total) {
+        return kmu_seed_chains(ctx.raw(), n_pairs ? pairs.data() : none, n_pairs, q.pos.empty() ? none : q.pos.data(),
+                               q.read.empty() ? none : q.read.data(), q.strand.empty() ? nullptr : q.strand.data(), uint32_t(q.pos.size()),
+                               uint32_t(q.offsets.size() - 1), db.pos.empty() ? none : db.pos.data(), db.read.empty() ? none : db.read.data(),
+                               db.strand.empty() ? nullptr : db.strand.data(), uint32_t(db.pos.size()), uint32_t(db.offsets.size() - 1), &p,
+                               KMU_MEM_HOST, out, cap, total);
+    };
+    uint64_t total = 0;
+    ctx.check(call(nullptr, 0, &total));
+    std::vector<kmu_chain> out(static_cast<size_t>(total));
+    if (total) ctx.check(call(out.data(), total, &total));
+    return out;
+}
+
+/// The index join behind chain_hits: the pairs (entry of q, entry of db; 2 per pair) of minimizers that carry the same hash, through
+/// an AnchorIndex of rows of one hash.  db == nullptr: the self-join of q, a minimizer never pairs with one of its own read.
+/// max_occ > 0: a hash that more than max_occ minimizers of db carry seeds nothing.
+inline std::vector<uint32_t> seed_pairs(const Minimizers &q, const Minimizers *db = nullptr, uint32_t max_occ = 0,
+                                        Context &ctx = Context::global()) {
+    const Minimizers &d = db ? *db : q;
+    const std::vector<uint32_t> no_group;
+    std::vector<uint32_t> pairs, dist;
+    if (q.size() == 0 || d.size() == 0) return pairs;
+    AnchorIndex(d.hashes, uint32_t(d.size()), 1, 1, db ? no_group : d.read, ctx)
+        .match(q.hashes, uint32_t(q.size()), db ? no_group : q.read, 1, max_occ, pairs, dist);
+    return pairs;
+}
+
+/// From minimizers to one chain per read pair: seed_pairs, then seed_chains.  `span` is the k of the minimizers.  The self-join
+/// (db == nullptr) reports each read pair once, read_a < read_b.
+inline std::vector<kmu_chain> chain_hits(const Minimizers &q, const Minimizers *db, uint32_t span, uint32_t max_occ = 0,
+                                         uint32_t max_gap = 5000, uint32_t band = 500, uint32_t min_seeds = 3, uint32_t min_score = 0,
+                                         Context &ctx = Context::global()) {
+    kmu_chain_params p{};
+    p.span = span;
+    p.max_gap = max_gap;
+    p.band = band;
+    p.min_seeds = min_seeds;
+    p.min_score = min_score;
+    p.flags = db ? 0u : KMU_CHAIN_UPPER;
+    return seed_chains(seed_pairs(q, db, max_occ, ctx), q, db ? *db : q, p, ctx);
+}
+
+/// From the reads of a batch to the chains between them: read_minimizers, then the self-join of chain_hits.
+template <class Kmer>
+std::vector<kmu_chain> read_chains(const detail::Batch &batch, size_t k, uint32_t w, FHash fhash = FHash::canon_invhash,
+                                   uint32_t max_occ = 0, uint32_t max_gap = 5000, uint32_t band = 500, uint32_t min_seeds = 3,
+                                   uint32_t min_score = 0, Context &ctx = Context::global()) {
+    const Minimizers m = read_minimizers<Kmer>(batch, k, w, fhash, ctx);
+    return chain_hits(m, nullptr, uint32_t(k), max_occ, max_gap, band, min_seeds, min_score, ctx);
 }
 
 // =====================================================================================================================

@@ -862,6 +862,65 @@ int kmu_read_minimizers(kmu_ctx *ctx, const kmu_hash_params *p, const uint8_t *b
                         uint64_t *mini_offsets_out, /* n_seq + 1, lives where `offsets` lives; may be NULL */
                         uint64_t *n_out);           /* host memory in both modes; required */
 
+/* ---- seed chaining: from minimizer hits to one colinear chain per read pair, at base resolution ----------------------
+ * pairs[2p..] = (ea, eb): an entry of the query minimizers and an entry of the database minimizers, as kmu_anchor_index_match
+ *   writes them for rows of one hash (minimizer.seed_pairs), in ANY order.  pos_* / read_* / strand_* are the arrays of
+ *   kmu_read_minimizers (n_q / n_db entries, reads below n_reads_q / n_reads_db); a NULL strand array is all 0; the q arrays and the
+ *   db arrays may be the same arrays (a self-join).
+ * Anchors and groups: the pair (ea, eb) is an anchor of the read pair (A, B) = (read_q[ea], read_db[eb]) with relative strand
+ *   s = strand_q[ea] ^ strand_db[eb], x = pos_q[ea] and y = pos_db[eb] for s = 0, y = -pos_db[eb] for s = 1 (the opposite strand is
+ *   colinear when b runs backwards).  A GROUP is the set of anchors of one (A, B, s); inside it the anchors are ordered by (x, y)
+ *   and i indexes that order.  Anchors equal in every field are interchangeable: no result depends on how a sort places them.
+ * Score: integer arithmetic only, exact, nothing clamped before the record.  For j < i of a group, dx = x_i - x_j, dy = y_i - y_j.
+ *   j is a PREDECESSOR of i iff i - KMU_CHAIN_LOOKBACK <= j, 0 < dx <= max_gap, 0 < dy <= max_gap and g = |dx - dy| <= band.  Then
+ *   t(j, i) = f(j) + min(dx, dy, span) - cost(g), cost(0) = 0, cost(g) = ((g * span) >> 7) + (floor(log2 g) >> 1) for g > 0, and
+ *   f(i) = max(span, max over the predecessors of t(j, i)).
+ *   An anchor starts a chain of its own unless some t(j, i) is STRICTLY larger than span; among the predecessors with the same
+ *   largest t the LARGEST j (the nearest) is chosen.  start(i) = start(j) and n(i) = n(j) + 1 of the chosen predecessor, otherwise
+ *   start(i) = i and n(i) = 1.
+ * Winner: per read pair the anchor e with the largest f over both of its groups; ties go to s = 0 before s = 1, then to the
+ *   smallest i.  With b = start(e): score = min(f(e), 2^32 - 1), n_seeds = n(e), n_anchors = the size of e's group,
+ *   a_start = x_b, a_end = x_e + span; s = 0: b_start = pos_db(b), b_end = pos_db(e) + span; s = 1: b_start = pos_db(e),
+ *   b_end = pos_db(b) + span.
+ * Reported: the winner of a read pair iff score >= min_score, n_seeds >= min_seeds and, under KMU_CHAIN_UPPER, read_a < read_b.
+ *   The filters see the winner only: no runner-up takes its place, and there is one chain per read pair (no secondary chains).
+ *   Order: read_a ascending, then read_b.  A pure function of the inputs: the order of the pairs, the launch shape and timing
+ *   change nothing.
+ * *n_out (host memory in both modes) is always the total.  out == NULL: the count-only call.  cap < total: KMU_E_BAD_ARG with
+ *   *n_out set.  n_pairs == 0: KMU_OK, *n_out = 0.  KMU_MEM_DEVICE: every array except p and n_out is device memory and the call
+ *   synchronises the stream once, to hand n_out over.  KMU_MEM_HOST: the arrays go up through the context's workspace and the
+ *   records come back.
+ * max_pos: 0, or a promise that no position is above it -- the sort then skips the passes of bytes no key can differ in.
+ * KMU_E_BAD_ARG: null ctx / pairs / pos / read / p / n_out, span == 0 or > 64, max_gap == 0, min_seeds == 0, unknown flag bits, bad
+ *   mem, pairs while a side has no entries or no reads.
+ * KMU_E_UNSUPPORTED: n_pairs >= 2^32; a pair that names an entry >= n_q / n_db, a read >= n_reads_q / n_reads_db, a position >= 2^31
+ *   or a position above a non-zero max_pos.  The arrays are read on the device in both modes: the refusal comes at the call's one
+ *   synchronisation, and no such pair is ever used as an index.
+ * How: one entry per pair, sorted by (read_a, read_b, s, x, y) with two stable radix sorts; one wave per group then runs the DP
+ *   with the lookback window in registers (the current and the previous 64 anchors, one per lane) and a wave arg-max per anchor;
+ *   one lane per read pair picks the winner, once to count and once to write.  A group of very many anchors is one wave's
+ *   sequential work, and tiny groups leave lanes idle.  DESIGN.md 3.15 has the kernels. */
+#define KMU_CHAIN_LOOKBACK 64      /* predecessors an anchor looks at */
+#define KMU_CHAIN_UPPER 1u         /* flags: only read pairs with read_a < read_b */
+typedef struct kmu_chain_params {
+    uint32_t span;       /* k of the minimizers: the bases a seed covers; 1 .. 64 */
+    uint32_t max_gap;    /* largest step in either read between chained seeds, > 0 */
+    uint32_t band;       /* largest |dx - dy| between chained seeds */
+    uint32_t min_seeds;  /* report chains with at least this many seeds (>= 1) */
+    uint32_t min_score;
+    uint32_t max_pos;    /* 0, or a promise that every position is <= max_pos: lets the sort skip dead passes */
+    uint32_t flags;
+} kmu_chain_params;
+typedef struct {         /* 40 bytes */
+    uint32_t read_a, read_b, strand;   /* strand: 0 same, 1 opposite */
+    uint32_t score, n_seeds, n_anchors;
+    uint32_t a_start, a_end, b_start, b_end;
+} kmu_chain;
+int kmu_seed_chains(kmu_ctx *ctx, const uint32_t *pairs, uint64_t n_pairs,
+                    const uint32_t *pos_q, const uint32_t *read_q, const uint8_t *strand_q, uint32_t n_q, uint32_t n_reads_q,
+                    const uint32_t *pos_db, const uint32_t *read_db, const uint8_t *strand_db, uint32_t n_db, uint32_t n_reads_db,
+                    const kmu_chain_params *p, int mem, kmu_chain *out, uint64_t cap, uint64_t *n_out);
+
 #ifdef __cplusplus
 }
 #endif

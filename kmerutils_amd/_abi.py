@@ -30,6 +30,8 @@ OVL_MAX_BAND = 8         # kmu_anchor_overlaps: the widest band
 OVL_UPPER = 1            # ... and its flag: only read pairs with read_a < read_b
 MINIMIZER_MAX_W = 256    # kmu_read_minimizers: the widest window (in k-mers)
 MINIMIZER_TILE = 1024    # ... and the windows one workgroup takes at a time
+CHAIN_LOOKBACK = 64      # kmu_seed_chains: the predecessors an anchor looks at
+CHAIN_UPPER = 1          # ... and its flag: only read pairs with read_a < read_b
 
 
 def kmer_val_bytes(kmer_type):
@@ -116,6 +118,24 @@ class Overlap(C.Structure):
 # the same record as a numpy dtype (32 bytes)
 OVERLAP_DTYPE = [("read_a", "<u4"), ("read_b", "<u4"), ("strand", "<u4"), ("diag", "<i4"), ("score", "<u4"), ("votes", "<u4"),
                  ("slice_a_min", "<u4"), ("slice_a_max", "<u4")]
+
+
+class ChainParams(C.Structure):
+    """kmu_chain_params: how kmu_seed_chains chains and what it reports"""
+    _fields_ = [("span", C.c_uint32), ("max_gap", C.c_uint32), ("band", C.c_uint32), ("min_seeds", C.c_uint32),
+                ("min_score", C.c_uint32), ("max_pos", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class Chain(C.Structure):
+    """kmu_chain: the chain of one read pair (kmu_seed_chains)"""
+    _fields_ = [("read_a", C.c_uint32), ("read_b", C.c_uint32), ("strand", C.c_uint32), ("score", C.c_uint32),
+                ("n_seeds", C.c_uint32), ("n_anchors", C.c_uint32), ("a_start", C.c_uint32), ("a_end", C.c_uint32),
+                ("b_start", C.c_uint32), ("b_end", C.c_uint32)]
+
+
+# the same record as a numpy dtype (40 bytes)
+CHAIN_DTYPE = [("read_a", "<u4"), ("read_b", "<u4"), ("strand", "<u4"), ("score", "<u4"), ("n_seeds", "<u4"), ("n_anchors", "<u4"),
+               ("a_start", "<u4"), ("a_end", "<u4"), ("b_start", "<u4"), ("b_end", "<u4")]
 
 
 class AnchorIndexInfo(C.Structure):

@@ -14,8 +14,8 @@
 //               every entry in its place; radix_sort_pairs_passes on that (the bytes that n_reads_q and n_reads_db can reach).  The
 //               sort is stable: the order is (read_a, read_b, strand, diagonal).
 //  k_ovl_heads  one lane per sorted entry: does the run change here, does the read pair change here.  device_scan_u32 over each
-//               flag array numbers runs and read pairs; k_ovl_starts writes the first entry of every run and the first run of
-//               every read pair.
+//               flag array numbers runs and read pairs; k_run_starts (kmu_runs.h, shared with kmu_seed_chains.hip; profiled here
+//               as k_ovl_starts) writes the first entry of every run and the first run of every read pair.
 //  k_ovl_runs   one wave per run, runs dealt grid-stride: the lanes walk the run 64 entries at a time (a run of one read pair
 //               matched on thousands of windows is no lane's alone), a wave reduction leaves weight (64 bits), min and max
 //               slice_a; the number of entries is the distance to the next run.
@@ -28,6 +28,7 @@
 // the output does not depend on the order of the input.
 #include <algorithm>
 
+#include "kmu_runs.h"
 #include "kmu_sort.h"
 
 namespace kmu {
@@ -145,19 +146,6 @@ __global__ void __launch_bounds__(256) k_ovl_heads(OvlArgs a) {
         a.rhead[i] = rh;
         a.phead[i] = ph;
         a.keep[i] = 0;
-    }
-}
-
-__global__ void __launch_bounds__(256) k_ovl_starts(OvlArgs a) {
-    const uint64_t n = min(a.info->n, a.n_max);
-    const uint64_t first = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x;
-    for (uint64_t i = first; i < n; i += (uint64_t) gridDim.x * blockDim.x) {
-        if (a.rhead[i]) a.rstart[a.ridx[i]] = (uint32_t) i;
-        if (a.phead[i]) a.pstart[a.pidx[i]] = (uint32_t) a.ridx[i];
-    }
-    if (first == 0) {
-        a.rstart[a.ridx[a.n_max]] = (uint32_t) n;
-        a.pstart[a.pidx[a.n_max]] = (uint32_t) a.ridx[a.n_max];
     }
 }
 
@@ -351,7 +339,8 @@ extern "C" int kmu_anchor_overlaps(kmu_ctx *ctx, const uint32_t *pairs, const ui
     KMU_TRY(launch(ctx, "k_ovl_heads", k_ovl_heads, dim3(flat), dim3(256), 0, a));
     KMU_TRY(device_scan_u32(ctx, a.rhead, n_max, ridx));
     KMU_TRY(device_scan_u32(ctx, a.phead, n_max, pidx));
-    KMU_TRY(launch(ctx, "k_ovl_starts", k_ovl_starts, dim3(flat), dim3(256), 0, a));
+    KMU_TRY(launch(ctx, "k_ovl_starts", k_run_starts, dim3(flat), dim3(256), 0,
+                   RunMarks{n_dev, n_max, a.rhead, a.phead, ridx, pidx, a.rstart, a.pstart}));
     const uint32_t waves = grid_for(ctx, n_max, 1, 32);
     KMU_TRY(launch(ctx, "k_ovl_runs", k_ovl_runs, dim3(waves), dim3(64), 0, a));
 

@@ -36,7 +36,7 @@ SYMBOLS = [
     "kmu_count_histogram", "kmu_count_read_profile", "kmu_anchor_layout", "kmu_read_anchors", "kmu_anchor_match",
     "kmu_anchor_overlaps", "kmu_anchor_index_create", "kmu_anchor_index_destroy", "kmu_anchor_index_info",
     "kmu_anchor_index_occupancy", "kmu_anchor_index_match", "kmu_components", "kmu_components_knn",
-    "kmu_minimizer_layout", "kmu_read_minimizers",
+    "kmu_minimizer_layout", "kmu_read_minimizers", "kmu_seed_chains",
 ]
 
 
@@ -142,6 +142,8 @@ def load():
     L.kmu_components_knn.argtypes = [vp, C.c_uint32, vp, vp, C.c_uint32, C.c_uint32, C.c_int, vp, vp, vp, vp, u32p]
     L.kmu_minimizer_layout.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp]
     L.kmu_read_minimizers.argtypes = [vp, C.POINTER(A.HashParams), vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp, C.c_uint64, vp, u64p]
+    L.kmu_seed_chains.argtypes = [vp, vp, C.c_uint64, vp, vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp, C.c_uint32, C.c_uint32,
+                                  C.POINTER(A.ChainParams), C.c_int, vp, C.c_uint64, u64p]
     L.kmu_set_hll_params.argtypes = [vp, C.POINTER(A.HllParams)]
     L.kmu_kmer_hashes_compact.argtypes = [vp, C.POINTER(A.HashParams), vp, vp, vp, C.c_uint32, vp, C.c_uint64, u64p]
     L.kmu_sketch_partial_words.argtypes = [C.POINTER(A.SketchParams)]
@@ -863,6 +865,37 @@ class Context:
             out = np.zeros(max(n, 1), np.dtype(A.OVERLAP_DTYPE))
         if n:
             self._check(self.L.kmu_anchor_overlaps(*args, _ptr(out)[0], n, C.byref(total)))
+        return out[:n]
+
+    def seed_chains(self, pairs, q, db, span, max_gap, band, min_seeds=1, min_score=0, max_pos=0, upper=False):
+        """kmu_seed_chains: one colinear chain of seeds per read pair behind the entry pairs of minimizer.seed_pairs (pairs [n, 2]:
+        an entry of q, an entry of db, in any order) -- its strand, score, seed count and its start and end on both reads in
+        bases (include/kmu.h has the rules).  q, db: Minimizers records (pos, read, strand or None, offsets with one entry per
+        read and one more); db=None is the self-join.  span: the k of the minimizers; max_pos: 0, or a promise that no position is
+        above it; upper: only read_a < read_b.  numpy arrays give a structured array (A.CHAIN_DTYPE); torch cuda tensors stay on
+        the device and give an int32 tensor [n, 10] holding the same bits.  Two library calls: one that counts, one with exactly
+        that capacity."""
+        if db is None:
+            db = q
+        mem = self._mem(pairs, q.pos, q.read, q.strand, db.pos, db.read, db.strand)
+        n_pairs = int(pairs.shape[0])
+        p = A.ChainParams(int(span), int(max_gap), int(band), int(min_seeds), int(min_score), int(max_pos), A.CHAIN_UPPER if upper else 0)
+        none = self._new_like(pairs, 2, np.uint32, "int32")  # an empty array has no address worth passing
+
+        def side(m):
+            n = int(m.pos.shape[0])
+            return (_ptr(m.pos)[0] if n else _ptr(none)[0], _ptr(m.read)[0] if n else _ptr(none)[0],
+                    _ptr(m.strand)[0] if n else None, n, len(m.offsets) - 1)
+        total = C.c_uint64(0)
+        args = (self.h, _ptr(pairs)[0] if n_pairs else _ptr(none)[0], n_pairs, *side(q), *side(db), C.byref(p), mem)
+        self._check(self.L.kmu_seed_chains(*args, None, 0, C.byref(total)))
+        n = int(total.value)
+        if mem == A.MEM_DEVICE:
+            out = self._new_like(pairs, (max(n, 1), 10), np.int32, "int32")
+        else:
+            out = np.zeros(max(n, 1), np.dtype(A.CHAIN_DTYPE))
+        if n:
+            self._check(self.L.kmu_seed_chains(*args, _ptr(out)[0], n, C.byref(total)))
         return out[:n]
 
     def _components(self, call, like, n_nodes, want, count):

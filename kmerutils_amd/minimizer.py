@@ -4,7 +4,8 @@
 minimizers of different reads that carry the same hash.  The join is the anchor index as it is (ctx.anchor_index /
 AnchorIndex.match): every minimizer is a row of ONE hash (m = 1, n_keys = 1) and its read is its group, so a hit is a pair of rows
 of different reads with that hash in common.  A hash equal to UINT64_MAX is the padding of the index's rows: such a minimizer is
-an empty row there and seeds nothing.
+an empty row there and seeds nothing.  `seed_pairs` is that join as raw entry pairs; `chain_hits` hands them to kmu_seed_chains
+(Context.seed_chains): one colinear chain of seeds per read pair, at base resolution; `read_chains` goes from reads to chains.
 """
 import collections
 
@@ -51,6 +52,19 @@ def _gather6(pairs, q, db):
     return np.stack(cols, axis=1) if idx.shape[0] else np.zeros((0, 6), np.int64)
 
 
+def seed_pairs(ctx, q, db=None, max_occ=0):
+    """The index join behind seed_hits and chain_hits: the raw pairs (entry of q, entry of db) of minimizers that share a hash,
+    uint32 [n, 2] (int32 holding the same bits for torch), ordered by the entry of q, then the entry of db.  db=None is the
+    self-join (a minimizer never pairs with one of its own read); max_occ as in seed_hits."""
+    own = db is None
+    if own:
+        db = q
+    rows_q, rows_db = q.hashes.reshape(-1, 1), db.hashes.reshape(-1, 1)
+    with ctx.anchor_index(rows_db, n_keys=1, group_db=db.read if own else None) as index:
+        pairs, _ = index.match(rows_q, group_q=q.read if own else None, min_common=1, max_occ=int(max_occ))
+    return pairs
+
+
 def seed_hits(ctx, q, db=None, max_occ=0):
     """Minimizers of different reads that share a hash.  q, db: Minimizers records (numpy, or torch on the device -- the join
     then runs on the resident arrays and the hits stay there).  db=None is the self-join of a batch: a minimizer never hits one
@@ -59,10 +73,23 @@ def seed_hits(ctx, q, db=None, max_occ=0):
     repeat mask of the anchor index).  Returns an int64 array [n, 6] of records (read_a, pos_a, strand_a, read_b, pos_b,
     strand_b), a of q and b of db, ordered by the entry of q, then the entry of db; a record's strands are 0 where the minimizers
     were made without.  A hash equal to UINT64_MAX seeds nothing: it is the padding of the index's rows."""
-    own = db is None
-    if own:
-        db = q
-    rows_q, rows_db = q.hashes.reshape(-1, 1), db.hashes.reshape(-1, 1)
-    with ctx.anchor_index(rows_db, n_keys=1, group_db=db.read if own else None) as index:
-        pairs, _ = index.match(rows_q, group_q=q.read if own else None, min_common=1, max_occ=int(max_occ))
-    return _gather6(pairs, q, db)
+    return _gather6(seed_pairs(ctx, q, db, max_occ), q, q if db is None else db)
+
+
+def chain_hits(ctx, q, db=None, max_occ=0, max_gap=5000, band=500, min_seeds=3, min_score=0, upper=None):
+    """From minimizers to one chain per read pair (kmu_seed_chains on the pairs of seed_pairs): which reads overlap, on which
+    strand, from where to where on both reads in bases, with how many seeds and which score.  q, db: Minimizers records of
+    read_minimizers (their offsets say how many reads there are, q.k is the span of a seed); db=None is the self-join, and
+    `upper` then defaults to True: each read pair once, read_a < read_b.  max_gap / band / min_seeds / min_score: the chaining
+    rules of include/kmu.h.  Returns a structured array of A.CHAIN_DTYPE for numpy records; for torch records an int32 tensor
+    [n, 10] holding the same bits, on the device, where the hits never left it."""
+    if upper is None:
+        upper = db is None
+    pairs = seed_pairs(ctx, q, db, max_occ)
+    return ctx.seed_chains(pairs, q, db, span=q.k, max_gap=max_gap, band=band, min_seeds=min_seeds, min_score=min_score, upper=upper)
+
+
+def read_chains(ctx, bases, offsets, k, w, fhash=A.FHASH_CANON_INVHASH, max_occ=0, max_gap=5000, band=500, min_seeds=3, min_score=0):
+    """From the reads of a batch to the chains between them in one call: read_minimizers, then the self-join of chain_hits."""
+    q = read_minimizers(ctx, bases, offsets, k, w, fhash)
+    return chain_hits(ctx, q, None, max_occ, max_gap, band, min_seeds, min_score)
