@@ -387,8 +387,10 @@ __device__ __forceinline__ uint32_t wave_incl_scan_u32(uint32_t v) {
 }
 __device__ __forceinline__ uint32_t shfl_down_u32(uint32_t v, int d) { return (uint32_t) __shfl_down((int) v, d, 64); }
 __device__ __forceinline__ uint32_t bcast_u32(uint32_t v, int src) { return (uint32_t) __shfl((int) v, src, 64); }
+// the value of lane l, in every lane; l is wave-uniform
+__device__ __forceinline__ uint32_t readlane_u32(uint32_t v, uint32_t l) { return (uint32_t) __builtin_amdgcn_readlane((int) v, (int) l); }
 // maximum of a 32-bit value over the 64 lanes, in every lane: DPP row shifts / broadcasts (the inclusive max scan of kmu_smer.hip)
-// and one readlane -- no LDS round trips (wave_max_u64 below makes twelve: ds_bpermute)
+// and one readlane -- no LDS round trips (wave_max_u64 below makes twelve, ds_bpermute; wave_max_u64_dpp behind it none)
 __device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
     auto mx = [](uint32_t a, uint32_t b) { return a > b ? a : b; };
     v = mx(v, (uint32_t) __builtin_amdgcn_update_dpp(0, (int) v, 0x111, 0xf, 0xf, false)); // row_shr:1
@@ -407,6 +409,23 @@ __device__ __forceinline__ uint64_t wave_max_u64(uint64_t v) {
         v = o > v ? o : v;
     }
     return v;
+}
+// one DPP move of wave_max_u32 on both halves of a 64-bit value; a lane that the move gives no source reads 0
+template <int CTRL, int ROWS> __device__ __forceinline__ uint64_t dpp_u64(uint64_t v) {
+    return ((uint64_t) (uint32_t) __builtin_amdgcn_update_dpp(0, (int) (v >> 32), CTRL, ROWS, 0xf, false) << 32) |
+           (uint32_t) __builtin_amdgcn_update_dpp(0, (int) (uint32_t) v, CTRL, ROWS, 0xf, false);
+}
+// the same maximum by the DPP steps of wave_max_u32 (the 0 of a lane without a source is nothing a maximum of unsigned values
+// minds) and two readlanes: no LDS round trips.  All lanes must be active.
+__device__ __forceinline__ uint64_t wave_max_u64_dpp(uint64_t v) {
+    auto mx = [](uint64_t a, uint64_t b) { return a > b ? a : b; };
+    v = mx(v, dpp_u64<0x111, 0xf>(v)); // row_shr:1
+    v = mx(v, dpp_u64<0x112, 0xf>(v)); // row_shr:2
+    v = mx(v, dpp_u64<0x114, 0xf>(v)); // row_shr:4
+    v = mx(v, dpp_u64<0x118, 0xf>(v)); // row_shr:8
+    v = mx(v, dpp_u64<0x142, 0xa>(v)); // row_bcast:15
+    v = mx(v, dpp_u64<0x143, 0xc>(v)); // row_bcast:31
+    return ((uint64_t) readlane_u32((uint32_t) (v >> 32), 63) << 32) | readlane_u32((uint32_t) v, 63);
 }
 __device__ __forceinline__ uint32_t wave_min_u32(uint32_t v) { return ~wave_max_u32(~v); }
 // sums over the 64 lanes, in every lane

@@ -11,7 +11,9 @@ from kmerutils_amd import _abi as A
 from kmerutils_amd import lib, minimizer
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from test_anchor_overlaps_abi import reference_overlaps  # noqa: E402
 from test_chains_abi import Side, one_pair, reference_chains, side  # noqa: E402
+from test_gpu_anchor_overlaps import random_case  # noqa: E402
 from test_gpu_minimizers import expected, rand_reads, reference_hits, revcomp  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -177,6 +179,30 @@ def test_filters_do_not_promote_a_runner_up(ctx):
     full = check(ctx, pairs, q, db, 15, 80, 30)
     some = check(ctx, pairs, q, db, 15, 80, 30, min_seeds=3, min_score=40)
     assert 0 < some.shape[0] < full.shape[0]
+
+
+def test_alternating_with_anchor_overlaps_on_one_context():
+    """kmu_anchor_overlaps and kmu_seed_chains group their entries in one workspace (kmu_runs.h): on a context of its own, a long
+    call of one, a short and a long call of the other, a short call of the first.  No flag, keep word or start that a call left
+    behind the next call's last entry may reach a record: each result equals its reference in every byte."""
+    c = lib.Context(0)
+    try:
+        def overlaps(seed, n_pairs, strands):
+            off, pairs, dist = random_case(np.random.default_rng(seed), n_pairs)
+            want = reference_overlaps(pairs, dist, off, None, strands, 1, 1, False)
+            got = c.anchor_overlaps(pairs, dist, off, strands=strands, band=1)
+            assert want.shape[0] > 0 and got.tobytes() == want.tobytes()
+
+        def chains(seed, n_pairs, upper):
+            pairs, q, db = random_batch(seed, n_pairs)
+            assert check(c, pairs, q, db, 15, 500, 100, upper=upper).shape[0] > 0
+
+        overlaps(31, 513, 2)  # 1026 entries: just over a sort tile
+        chains(32, 5, False)
+        chains(33, 1025, True)
+        overlaps(34, 3, 1)
+    finally:
+        c.close()
 
 
 # ---- call forms -------------------------------------------------------------------------------------------------------------------

@@ -6,12 +6,26 @@ The three are where that step can go wrong:
   a per-read sketch with a genome the helpers of that route (k_max_len, k_nk_scan) were never timed: a launch that passes no name
                                  stays out of the profile (profile_get reads at most 32 names).
 With profiling off the same calls leave the profile empty.  The expected dictionaries are what the library of the commit before
-reported for these calls on an MI355X (and what this one reports)."""
+reported for these calls on an MI355X (and what this one reports).
+
+Two more, pinned to what the library reported before kmu_anchor_overlaps and kmu_seed_chains took their grouping (keys, two sorts
+with a gather between them, heads, scans, starts) from the one pipeline of kmu_runs.h; a lost or doubled sort pass shows here:
+  anchor_overlaps, two strands   five passes over the diagonal keys, two over the read pairs (9 reads: one byte per side);
+  seed_chains with max_pos       five passes over (strand, x, y + max_pos) at max_pos = 2999, two over the read pairs.
+Both with upper=True, so the COUNT form of the keys kernel runs, and both through lib.Context, whose one call is two calls of
+the library: one that counts, one that writes."""
+import os
+import sys
+
 import numpy as np
 import pytest
 
 from kmerutils_amd import _abi as A
 from kmerutils_amd import lib, synth
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from test_chains_abi import side  # noqa: E402
+from test_gpu_anchor_overlaps import random_case  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -22,6 +36,12 @@ COMPONENTS = {"k_cc_init": 1, "k_cc_hook": 1, "k_cc_flatten": 1, "k_cc_number": 
 COUNT_EXACT = {"k_part_hist1": 1, "k_part_scan1": 1, "k_part_scatter1": 1, "k_arr_hist": 1, "k_arr_scan": 1, "k_arr_scatter": 1,
                "k_part_build_q": 1}
 SKETCH_LONG = {"k_sketch_pmh3a": 2, "k_seq_hashes_compact": 1, "k_arr_hist": 1, "k_arr_scan": 1, "k_arr_scatter": 1, "k_pmh_reduce": 1}
+OVERLAPS = {"k_ovl_keys_count": 2, "k_ovl_keys_write": 2, "k_sort_hist": 14, "k_sort_scatter": 14, "k_ovl_gather": 2,
+            "k_ovl_heads": 2, "k_ovl_starts": 2, "k_ovl_runs": 2, "k_ovl_best_count": 2, "k_ovl_best_write": 1,
+            "k_ing_scan": 22}  # (the scans of a library call: the tile counts, one per sort pass, two flag arrays, keep)
+CHAINS = {"k_chain_keys_count": 2, "k_chain_keys_write": 2, "k_sort_hist": 14, "k_sort_scatter": 14, "k_chain_gather": 2,
+          "k_chain_heads": 2, "k_chain_starts": 2, "k_chain_dp": 2, "k_chain_best_count": 2, "k_chain_best_write": 1,
+          "k_ing_scan": 22}
 UNTIMED = ("k_max_len", "k_nk_scan", "k_widen_u32", "k_pts_long_list", "k_fill_linear", "k_spill_header", "k_seg_tails")
 
 
@@ -91,3 +111,27 @@ def test_untimed_helpers_stay_untimed(ctx):
     assert "k_seq_hashes_compact" in prof and "k_pmh_reduce" in prof  # the long sequence did take the all-sequences route
     assert prof == SKETCH_LONG
     assert launches(ctx, sketch, profiling=False) == {}
+
+
+def test_anchor_overlaps_launches(ctx):
+    off, pairs, dist = random_case(np.random.default_rng(0xCC4), 500, n_reads=9)
+
+    def anchor_overlaps():
+        assert ctx.anchor_overlaps(pairs, dist, off, strands=2, band=1, upper=True).shape[0] > 0
+
+    assert launches(ctx, anchor_overlaps) == OVERLAPS
+    assert launches(ctx, anchor_overlaps, profiling=False) == {}
+
+
+def test_seed_chains_launches(ctx):
+    rng = np.random.default_rng(0xCC5)
+    nq, ndb = 60, 50  # entries of 4 and of 3 reads, strands on both sides
+    q = side(rng.integers(0, 3000, nq), rng.integers(0, 4, nq), rng.integers(0, 2, nq), 4)
+    db = side(rng.integers(0, 3000, ndb), rng.integers(0, 3, ndb), rng.integers(0, 2, ndb), 3)
+    pairs = np.stack([rng.integers(0, nq, 1500), rng.integers(0, ndb, 1500)], axis=1).astype(np.uint32)
+
+    def seed_chains():
+        assert ctx.seed_chains(pairs, q, db, 15, 500, 100, max_pos=2999, upper=True).shape[0] > 0
+
+    assert launches(ctx, seed_chains) == CHAINS
+    assert launches(ctx, seed_chains, profiling=False) == {}
