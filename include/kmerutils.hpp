@@ -26,6 +26,7 @@
  *                 Overlap, anchor_overlaps, read_overlaps (read pairs from matched slices)  (beyond the reference)
  *                 Components, components, components_knn, ReadClusters, read_clusters       (beyond the reference)
  *                                                            (connected components of overlap records / neighbour lists)
+ *                 chain_align, align_chains, read_alignments, paf_line (banded edit distance and matches per chain; PAF text)
  *                 seed_chains, seed_pairs, chain_hits, read_chains (one base-resolution chain per read pair from minimizer
  *                                                            hits)                          (beyond the reference)
  *   counting      KmerCountT (trait), KmerCounter, KmerCounterPool, count_kmer_threaded_one_to_many
@@ -1886,6 +1887,61 @@ std::vector<kmu_chain> read_chains(const detail::Batch &batch, size_t k, uint32_
                                    uint32_t min_score = 0, Context &ctx = Context::global()) {
     const Minimizers m = read_minimizers<Kmer>(batch, k, w, fhash, ctx);
     return chain_hits(m, nullptr, uint32_t(k), max_occ, max_gap, band, min_seeds, min_score, ctx);
+}
+
+// =====================================================================================================================
+// chain alignment (kmu_chain_align; the reference has no such unit)
+// =====================================================================================================================
+
+/// kmu_chain_align on host arrays: for every chain record the banded global alignment of the two segments it names -- edit distance,
+/// matching columns, the diagonals of its band and the flags KMU_ALN_DONE / KMU_ALN_EXACT (include/kmu.h has the rules).  q, db:
+/// the batches the chains' reads are numbered in (db == nullptr: the self-join on one batch); packed batches are unpacked first.
+inline std::vector<kmu_chain_aln> chain_align(const std::vector<kmu_chain> &chains, const detail::Batch &q, const detail::Batch *db = nullptr,
+                                              uint32_t band = 64, Context &ctx = Context::global()) {
+    const detail::Batch bq = detail::unpacked(q);
+    detail::Batch bdb_own;
+    if (db) bdb_own = detail::unpacked(*db);
+    const detail::Batch &bdb = db ? bdb_own : bq;
+    if (bq.on_device() || bdb.on_device()) throw std::invalid_argument("chain_align returns host arrays: it needs the sequences in host memory");
+    std::vector<kmu_chain_aln> out(chains.size());
+    if (chains.empty()) return out;
+    kmu_align_params p{};
+    p.band = band;
+    ctx.check(kmu_chain_align(ctx.raw(), chains.data(), chains.size(), bq.bytes.data(), bq.offsets.data(), bq.n(), bdb.bytes.data(),
+                              bdb.offsets.data(), bdb.n(), &p, KMU_MEM_HOST, out.data()));
+    return out;
+}
+/// The same under the name of the Python route (minimizer.align_chains)
+inline std::vector<kmu_chain_aln> align_chains(const std::vector<kmu_chain> &chains, const detail::Batch &q, const detail::Batch *db = nullptr,
+                                               uint32_t band = 64, Context &ctx = Context::global()) {
+    return chain_align(chains, q, db, band, ctx);
+}
+
+/// From the reads of a batch to the chains between them and their alignments: read_chains (band_chain is its band), then
+/// chain_align with `band`.
+template <class Kmer>
+std::pair<std::vector<kmu_chain>, std::vector<kmu_chain_aln>> read_alignments(const detail::Batch &batch, size_t k, uint32_t w,
+                                                                              FHash fhash = FHash::canon_invhash, uint32_t max_occ = 0,
+                                                                              uint32_t max_gap = 5000, uint32_t band_chain = 500,
+                                                                              uint32_t min_seeds = 3, uint32_t min_score = 0,
+                                                                              uint32_t band = 64, Context &ctx = Context::global()) {
+    std::vector<kmu_chain> chains = read_chains<Kmer>(batch, k, w, fhash, max_occ, max_gap, band_chain, min_seeds, min_score, ctx);
+    std::vector<kmu_chain_aln> aln = chain_align(chains, batch, nullptr, band, ctx);
+    return {std::move(chains), std::move(aln)};
+}
+
+/// One PAF line (no newline) of a chain and its alignment: the 12 standard columns -- query name, length, start, end, strand, target
+/// name, length, start, end, matches, matches + edit, mapq 255 -- then NM:i:edit, s1:i:score and cm:i:n_seeds.  A record without
+/// KMU_ALN_DONE writes 0 matches, a block of max(m, n) and no NM tag.  Host code.
+inline std::string paf_line(const kmu_chain &c, const kmu_chain_aln &a, const std::string &name_q, uint64_t len_q,
+                            const std::string &name_db, uint64_t len_db) {
+    const bool done = (a.flags & KMU_ALN_DONE) != 0;
+    const uint64_t block = done ? uint64_t(a.matches) + a.edit : std::max<uint64_t>(c.a_end - c.a_start, c.b_end - c.b_start);
+    std::string s = name_q + "\t" + std::to_string(len_q) + "\t" + std::to_string(c.a_start) + "\t" + std::to_string(c.a_end) + "\t" +
+                    (c.strand ? "-" : "+") + "\t" + name_db + "\t" + std::to_string(len_db) + "\t" + std::to_string(c.b_start) + "\t" +
+                    std::to_string(c.b_end) + "\t" + std::to_string(done ? a.matches : 0u) + "\t" + std::to_string(block) + "\t255";
+    if (done) s += "\tNM:i:" + std::to_string(a.edit);
+    return s + "\ts1:i:" + std::to_string(c.score) + "\tcm:i:" + std::to_string(c.n_seeds);
 }
 
 // =====================================================================================================================

@@ -921,6 +921,55 @@ int kmu_seed_chains(kmu_ctx *ctx, const uint32_t *pairs, uint64_t n_pairs,
                     const uint32_t *pos_db, const uint32_t *read_db, const uint8_t *strand_db, uint32_t n_db, uint32_t n_reads_db,
                     const kmu_chain_params *p, int mem, kmu_chain *out, uint64_t cap, uint64_t *n_out);
 
+/* ---- chain alignment: banded edit distance and matches of the two segments a chain names -----------------------------
+ * Segments: record c names A = read `read_a` of the q batch, bases [a_start, a_end), and B = read `read_b` of the db batch, bases
+ *   [b_start, b_end); bases_* / offsets_* are KMU_INPUT_ASCII batches (letters of ACGTacgt, case does not matter) of n_reads_q /
+ *   n_reads_db reads.  For strand == 1 B is replaced by its reverse complement; the b coordinates stay forward coordinates of read
+ *   b, which is what kmu_seed_chains writes.  The q arrays and the db arrays may be the same arrays (a self-join).  m = |A|,
+ *   n = |B|; either may be 0.
+ * Band: cell (i, j), 0 <= i <= m, 0 <= j <= n, is inside the band iff lo <= j - i <= hi with lo = min(0, n - m) - band and
+ *   hi = max(0, n - m) + band; n_diags = hi - lo + 1 = |n - m| + 2 band + 1.  Both corners are always inside.
+ * Value: global alignment with unit costs.  The value of a cell is the lexicographic minimum of (edits, -matches) over all paths
+ *   from (0, 0) that stay inside the band: a diagonal step over equal bases adds (0, -1); a diagonal step over different bases, a
+ *   horizontal and a vertical step add (1, 0) each.  edit and matches are those of cell (m, n).  The value is unique: a pure
+ *   function of the inputs -- the launch shape and timing change nothing, and no tie rule between moves is needed.  The length of
+ *   the alignment block (PAF column 11) is matches + edit.
+ * Flags: KMU_ALN_DONE iff n_diags <= KMU_ALIGN_MAX_DIAGS; otherwise the record is {UINT32_MAX, 0, n_diags, 0}, the chain does no
+ *   work and its bases are not looked at.  KMU_ALN_EXACT iff DONE and edit - |n - m| <= 2 band: a path with d edits leaves the
+ *   diagonals between 0 and n - m by at most (d - |n - m|) / 2, so every optimal path of the unbanded problem then lies inside the
+ *   band and both fields are the unbanded ones.
+ * Output: out[c] belongs to chains[c]; always n_chains records -- no count call, no capacity.
+ * KMU_MEM_DEVICE: every array except p is device memory (offsets_* live with the bases); the call synchronises the stream once, to
+ *   read the refusal flags, also in async_device contexts.  KMU_MEM_HOST: the arrays go up through the context's workspace and the
+ *   records come back, as in kmu_seed_chains.
+ * n_chains == 0: KMU_OK.  KMU_E_BAD_ARG (nothing is launched): null ctx / chains / bases / offsets / p / out, non-zero flags,
+ *   2 band + 1 > KMU_ALIGN_MAX_DIAGS, bad mem, chains while a side has no reads.
+ * KMU_E_UNSUPPORTED: a record with a read >= n_reads_q / n_reads_db, strand > 1, a start above its end or an end above the length
+ *   of its read.  KMU_E_NON_ACGT: a byte outside ACGTacgt inside an aligned segment (a segment of a chain without DONE is not
+ *   aligned).  Both are found on the device and reported at the call's one synchronisation (UNSUPPORTED first); no such record is
+ *   ever used as an index, and the records of a refused call are unspecified.
+ * How: one wave per chain, chains dealt grid-stride.  The band lives in the lanes -- a lane owns 1, 2, 4 or 8 pairs of adjacent
+ *   diagonals, by the chain's n_diags -- and the wave sweeps the anti-diagonals two at a time with one 64-bit value per diagonal in
+ *   registers and the neighbours' values by DPP wave shifts.  The bases of both segments pass through LDS as 2-bit codes,
+ *   KMU_ALIGN_CHUNK bases of progress at a time; a lane shifts its next 32 of each through a register.  A chain is m + n + 1
+ *   sequential anti-diagonals of one wave: a 50 kb overlap is 100 k steps, which is the accepted limit.  DESIGN.md 3.16 has the
+ *   kernel. */
+#define KMU_ALIGN_MAX_DIAGS 1024   /* the widest band, in diagonals, one chain may need */
+#define KMU_ALIGN_CHUNK 512        /* bases of progress along either segment between two stagings of the kernel */
+#define KMU_ALN_DONE  1u           /* the segment pair was aligned */
+#define KMU_ALN_EXACT 2u           /* edit and matches are those of the unbanded problem */
+typedef struct kmu_align_params {
+    uint32_t band;
+    uint32_t flags;      /* no flag bits yet: must be 0 */
+} kmu_align_params;
+typedef struct {         /* 16 bytes */
+    uint32_t edit, matches, n_diags, flags;
+} kmu_chain_aln;
+int kmu_chain_align(kmu_ctx *ctx, const kmu_chain *chains, uint64_t n_chains,
+                    const uint8_t *bases_q, const uint64_t *offsets_q, uint32_t n_reads_q,
+                    const uint8_t *bases_db, const uint64_t *offsets_db, uint32_t n_reads_db,
+                    const kmu_align_params *p, int mem, kmu_chain_aln *out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -32,6 +32,9 @@ MINIMIZER_MAX_W = 256    # kmu_read_minimizers: the widest window (in k-mers)
 MINIMIZER_TILE = 1024    # ... and the windows one workgroup takes at a time
 CHAIN_LOOKBACK = 64      # kmu_seed_chains: the predecessors an anchor looks at
 CHAIN_UPPER = 1          # ... and its flag: only read pairs with read_a < read_b
+ALIGN_MAX_DIAGS = 1024   # kmu_chain_align: the widest band, in diagonals, one chain may need
+ALIGN_CHUNK = 512        # ... the bases of progress between two stagings of its kernel
+ALN_DONE, ALN_EXACT = 1, 2  # ... and the flags of its records
 
 
 def kmer_val_bytes(kmer_type):
@@ -136,6 +139,20 @@ class Chain(C.Structure):
 # the same record as a numpy dtype (40 bytes)
 CHAIN_DTYPE = [("read_a", "<u4"), ("read_b", "<u4"), ("strand", "<u4"), ("score", "<u4"), ("n_seeds", "<u4"), ("n_anchors", "<u4"),
                ("a_start", "<u4"), ("a_end", "<u4"), ("b_start", "<u4"), ("b_end", "<u4")]
+
+
+class AlignParams(C.Structure):
+    """kmu_align_params: the band of kmu_chain_align"""
+    _fields_ = [("band", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class ChainAln(C.Structure):
+    """kmu_chain_aln: the alignment of one chain's two segments (kmu_chain_align)"""
+    _fields_ = [("edit", C.c_uint32), ("matches", C.c_uint32), ("n_diags", C.c_uint32), ("flags", C.c_uint32)]
+
+
+# the same record as a numpy dtype (16 bytes)
+CHAIN_ALN_DTYPE = [("edit", "<u4"), ("matches", "<u4"), ("n_diags", "<u4"), ("flags", "<u4")]
 
 
 class AnchorIndexInfo(C.Structure):

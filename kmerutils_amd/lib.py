@@ -36,7 +36,7 @@ SYMBOLS = [
     "kmu_count_histogram", "kmu_count_read_profile", "kmu_anchor_layout", "kmu_read_anchors", "kmu_anchor_match",
     "kmu_anchor_overlaps", "kmu_anchor_index_create", "kmu_anchor_index_destroy", "kmu_anchor_index_info",
     "kmu_anchor_index_occupancy", "kmu_anchor_index_match", "kmu_components", "kmu_components_knn",
-    "kmu_minimizer_layout", "kmu_read_minimizers", "kmu_seed_chains",
+    "kmu_minimizer_layout", "kmu_read_minimizers", "kmu_seed_chains", "kmu_chain_align",
 ]
 
 
@@ -144,6 +144,7 @@ def load():
     L.kmu_read_minimizers.argtypes = [vp, C.POINTER(A.HashParams), vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp, C.c_uint64, vp, u64p]
     L.kmu_seed_chains.argtypes = [vp, vp, C.c_uint64, vp, vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp, C.c_uint32, C.c_uint32,
                                   C.POINTER(A.ChainParams), C.c_int, vp, C.c_uint64, u64p]
+    L.kmu_chain_align.argtypes = [vp, vp, C.c_uint64, vp, vp, C.c_uint32, vp, vp, C.c_uint32, C.POINTER(A.AlignParams), C.c_int, vp]
     L.kmu_set_hll_params.argtypes = [vp, C.POINTER(A.HllParams)]
     L.kmu_kmer_hashes_compact.argtypes = [vp, C.POINTER(A.HashParams), vp, vp, vp, C.c_uint32, vp, C.c_uint64, u64p]
     L.kmu_sketch_partial_words.argtypes = [C.POINTER(A.SketchParams)]
@@ -896,6 +897,47 @@ class Context:
             out = np.zeros(max(n, 1), np.dtype(A.CHAIN_DTYPE))
         if n:
             self._check(self.L.kmu_seed_chains(*args, _ptr(out)[0], n, C.byref(total)))
+        return out[:n]
+
+    def chain_align(self, chains, bases_q, offsets_q, bases_db=None, offsets_db=None, band=64):
+        """kmu_chain_align: for every chain record the banded global alignment of the two segments it names -- edit distance,
+        matching columns, the diagonals of its band and the flags A.ALN_DONE / A.ALN_EXACT (include/kmu.h has the rules).  chains:
+        the records of seed_chains; bases_* / offsets_*: the ASCII batches the chains' reads are numbered in (db=None: the
+        self-join on one batch).  numpy in (a structured A.CHAIN_DTYPE array) gives a structured A.CHAIN_ALN_DTYPE array; torch
+        cuda tensors (the int32 [n, 10] records) stay on the device and give an int32 tensor [n, 4] holding the same bits
+        (offsets that are numpy arrays are copied up)."""
+        if bases_db is None:
+            bases_db, offsets_db = bases_q, offsets_q
+        elif offsets_db is None:
+            raise ValueError("bases_db without offsets_db")
+        if not _is_torch(chains):
+            chains = np.ascontiguousarray(chains)
+        mem = self._mem(chains, bases_q, bases_db)
+        n = int(chains.shape[0])
+
+        def offsets(x):
+            if _is_torch(x):
+                if x.is_cuda == (mem == A.MEM_DEVICE):
+                    return x
+                x = x.cpu().numpy()
+            x = np.ascontiguousarray(np.asarray(x).astype(np.uint64))
+            if mem == A.MEM_DEVICE:
+                import torch
+                return torch.from_numpy(x.view(np.int64)).to(chains.device)
+            return x
+        off_q = offsets(offsets_q)
+        off_db = off_q if offsets_db is offsets_q else offsets(offsets_db)
+        p = A.AlignParams(int(band), 0)
+        if mem == A.MEM_DEVICE:
+            out = self._new_like(chains, (max(n, 1), 4), np.int32, "int32")
+        else:
+            out = np.zeros(max(n, 1), np.dtype(A.CHAIN_ALN_DTYPE))
+        none = self._new_like(chains, 16, np.uint8, "uint8")  # an empty array has no address worth passing
+
+        def ptr(x):
+            return _ptr(x)[0] if int(x.shape[0]) else _ptr(none)[0]
+        self._check(self.L.kmu_chain_align(self.h, ptr(chains), n, ptr(bases_q), _ptr(off_q)[0], int(off_q.shape[0]) - 1, ptr(bases_db),
+                                           _ptr(off_db)[0], int(off_db.shape[0]) - 1, C.byref(p), mem, _ptr(out)[0]))
         return out[:n]
 
     def _components(self, call, like, n_nodes, want, count):

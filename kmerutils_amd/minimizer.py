@@ -6,6 +6,9 @@ AnchorIndex.match): every minimizer is a row of ONE hash (m = 1, n_keys = 1) and
 of different reads with that hash in common.  A hash equal to UINT64_MAX is the padding of the index's rows: such a minimizer is
 an empty row there and seeds nothing.  `seed_pairs` is that join as raw entry pairs; `chain_hits` hands them to kmu_seed_chains
 (Context.seed_chains): one colinear chain of seeds per read pair, at base resolution; `read_chains` goes from reads to chains.
+`align_chains` hands the chains and the reads to kmu_chain_align (Context.chain_align): the banded edit distance and the matching
+columns of every chain's two segments; `read_alignments` goes from reads to (chains, alignments), and `paf_lines` writes the two
+record arrays as PAF text on the host.
 """
 import collections
 
@@ -93,3 +96,42 @@ def read_chains(ctx, bases, offsets, k, w, fhash=A.FHASH_CANON_INVHASH, max_occ=
     """From the reads of a batch to the chains between them in one call: read_minimizers, then the self-join of chain_hits."""
     q = read_minimizers(ctx, bases, offsets, k, w, fhash)
     return chain_hits(ctx, q, None, max_occ, max_gap, band, min_seeds, min_score)
+
+
+def align_chains(ctx, chains, bases_q, offsets_q, bases_db=None, offsets_db=None, band=64):
+    """The alignment record of every chain (kmu_chain_align): edit, matches, n_diags and the flags A.ALN_DONE / A.ALN_EXACT of the
+    banded global alignment of the two segments the chain names (include/kmu.h has the rules).  chains: the records of chain_hits;
+    bases_* / offsets_*: the reads the minimizers were taken of (db=None: the self-join).  numpy records give a structured array
+    of A.CHAIN_ALN_DTYPE; torch records an int32 tensor [n, 4] holding the same bits, on the device."""
+    return ctx.chain_align(chains, bases_q, offsets_q, bases_db, offsets_db, band=band)
+
+
+def read_alignments(ctx, bases, offsets, k, w, fhash=A.FHASH_CANON_INVHASH, max_occ=0, max_gap=5000, band_chain=500, min_seeds=3,
+                    min_score=0, band=64):
+    """From the reads of a batch to the chains between them and their alignments in one call: read_chains (band_chain is its
+    band), then align_chains with `band`.  Returns (chains, aln)."""
+    chains = read_chains(ctx, bases, offsets, k, w, fhash, max_occ, max_gap, band_chain, min_seeds, min_score)
+    return chains, align_chains(ctx, chains, bases, offsets, band=band)
+
+
+def paf_lines(chains, aln, names_q, offsets_q, names_db=None, offsets_db=None):
+    """One PAF line per chain, on the host: chains (A.CHAIN_DTYPE) and aln (A.CHAIN_ALN_DTYPE) are numpy records of the same
+    length, names_* the names of the reads, offsets_* their offsets (db=None: the self-join).  The 12 standard columns -- query
+    name, length, start, end, strand, target name, length, start, end, matches, matches + edit, mapq 255 -- then NM:i:edit,
+    s1:i:score and cm:i:n_seeds.  A record without A.ALN_DONE writes 0 matches, a block of max(m, n) and no NM tag."""
+    if names_db is None:
+        names_db, offsets_db = names_q, offsets_q
+    off_q, off_db = np.asarray(offsets_q).astype(np.int64), np.asarray(offsets_db).astype(np.int64)
+    lines = []
+    for c, a in zip(np.asarray(chains).tolist(), np.asarray(aln).tolist()):
+        read_a, read_b, strand, score, n_seeds, _, a_start, a_end, b_start, b_end = c
+        edit, matches, _, flags = a
+        done = bool(flags & A.ALN_DONE)
+        cols = [names_q[read_a], int(off_q[read_a + 1] - off_q[read_a]), a_start, a_end, "-" if strand else "+",
+                names_db[read_b], int(off_db[read_b + 1] - off_db[read_b]), b_start, b_end,
+                matches if done else 0, matches + edit if done else max(a_end - a_start, b_end - b_start), 255]
+        if done:
+            cols.append("NM:i:%d" % edit)
+        cols += ["s1:i:%d" % score, "cm:i:%d" % n_seeds]
+        lines.append("\t".join(str(x) for x in cols))
+    return lines
