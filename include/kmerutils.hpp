@@ -27,6 +27,7 @@
  *                 Components, components, components_knn, ReadClusters, read_clusters       (beyond the reference)
  *                                                            (connected components of overlap records / neighbour lists)
  *                 chain_align, align_chains, read_alignments, paf_line (banded edit distance and matches per chain; PAF text)
+ *                 ChainCigars, chain_cigar, cigar_chains, cigar_string, paf_line with cg:Z: (the path of every chain's alignment)
  *                 seed_chains, seed_pairs, chain_hits, read_chains (one base-resolution chain per read pair from minimizer
  *                                                            hits)                          (beyond the reference)
  *   counting      KmerCountT (trait), KmerCounter, KmerCounterPool, count_kmer_threaded_one_to_many
@@ -1942,6 +1943,80 @@ inline std::string paf_line(const kmu_chain &c, const kmu_chain_aln &a, const st
                     std::to_string(c.b_end) + "\t" + std::to_string(done ? a.matches : 0u) + "\t" + std::to_string(block) + "\t255";
     if (done) s += "\tNM:i:" + std::to_string(a.edit);
     return s + "\ts1:i:" + std::to_string(c.score) + "\tcm:i:" + std::to_string(c.n_seeds);
+}
+
+// =====================================================================================================================
+// chain alignment paths (kmu_chain_cigar; the reference has no such unit)
+// =====================================================================================================================
+
+/// What chain_cigar returns: the records of chain_align with KMU_ALN_PATH where a chain's runs were written, and the runs
+/// (len << 4 | KMU_CIGAR_*) of chain c in ops[op_offsets[c] .. op_offsets[c + 1]), in path order along A.
+struct ChainCigars {
+    std::vector<kmu_chain_aln> aln;
+    std::vector<uint32_t> ops;
+    std::vector<uint64_t> op_offsets;
+};
+
+/// kmu_chain_cigar on host arrays: chain_align and, for every chain, the path of its alignment as CIGAR runs (include/kmu.h has
+/// the rules).  Arguments as chain_align; max_trace_bytes: the workspace the direction bits of one batch of chains may take
+/// (0: KMU_CIGAR_TRACE_DEFAULT).  Two library calls: one that counts, one with exactly that capacity.
+inline ChainCigars chain_cigar(const std::vector<kmu_chain> &chains, const detail::Batch &q, const detail::Batch *db = nullptr,
+                               uint32_t band = 64, uint64_t max_trace_bytes = 0, Context &ctx = Context::global()) {
+    const detail::Batch bq = detail::unpacked(q);
+    detail::Batch bdb_own;
+    if (db) bdb_own = detail::unpacked(*db);
+    const detail::Batch &bdb = db ? bdb_own : bq;
+    if (bq.on_device() || bdb.on_device()) throw std::invalid_argument("chain_cigar returns host arrays: it needs the sequences in host memory");
+    ChainCigars out;
+    out.aln.resize(chains.size());
+    out.op_offsets.assign(chains.size() + 1, 0);
+    if (chains.empty()) return out;
+    kmu_cigar_params p{};
+    p.band = band;
+    p.max_trace_bytes = max_trace_bytes;
+    uint64_t total = 0;
+    auto call = [&](uint32_t *ops, uint64_t cap) {
+        ctx.check(kmu_chain_cigar(ctx.raw(), chains.data(), chains.size(), bq.bytes.data(), bq.offsets.data(), bq.n(), bdb.bytes.data(),
+                                  bdb.offsets.data(), bdb.n(), &p, KMU_MEM_HOST, out.aln.data(), out.op_offsets.data(), ops, cap, &total));
+    };
+    call(nullptr, 0);
+    out.ops.resize(total);
+    if (total) call(out.ops.data(), total);
+    return out;
+}
+/// The same under the name of the Python route (minimizer.cigar_chains)
+inline ChainCigars cigar_chains(const std::vector<kmu_chain> &chains, const detail::Batch &q, const detail::Batch *db = nullptr,
+                                uint32_t band = 64, uint64_t max_trace_bytes = 0, Context &ctx = Context::global()) {
+    return chain_cigar(chains, q, db, band, max_trace_bytes, ctx);
+}
+
+/// The runs of chain c as a CIGAR string ("" for a chain without runs).  extended == false merges = and X into M; reversed writes
+/// the runs in reverse order -- for a chain on strand 1, along the forward strand of the target, as PAF's cg tag wants them.  Host code.
+inline std::string cigar_string(const ChainCigars &r, size_t c, bool extended = true, bool reversed = false) {
+    std::vector<std::pair<uint64_t, char>> runs;
+    for (uint64_t x = r.op_offsets[c]; x < r.op_offsets[c + 1]; x++) {
+        const uint32_t op = r.ops[x] & 15u;
+        char letter = op == KMU_CIGAR_I ? 'I' : op == KMU_CIGAR_D ? 'D' : op == KMU_CIGAR_EQ ? '=' : 'X';
+        if (!extended && (letter == '=' || letter == 'X')) letter = 'M';
+        runs.emplace_back(r.ops[x] >> 4, letter);
+    }
+    if (reversed) std::reverse(runs.begin(), runs.end());
+    std::string s;
+    for (size_t x = 0; x < runs.size(); x++) {
+        uint64_t n = runs[x].first;
+        while (x + 1 < runs.size() && runs[x + 1].second == runs[x].second) n += runs[++x].first;
+        s += std::to_string(n) + runs[x].second;
+    }
+    return s;
+}
+
+/// paf_line with the cg:Z: tag: the runs of chain c of `cigars`, along the target's forward strand, where its record has
+/// KMU_ALN_PATH; the line of the overload above otherwise.
+inline std::string paf_line(const kmu_chain &c, const ChainCigars &cigars, size_t at, const std::string &name_q, uint64_t len_q,
+                            const std::string &name_db, uint64_t len_db) {
+    std::string s = paf_line(c, cigars.aln[at], name_q, len_q, name_db, len_db);
+    if (cigars.aln[at].flags & KMU_ALN_PATH) s += "\tcg:Z:" + cigar_string(cigars, at, true, c.strand != 0);
+    return s;
 }
 
 // =====================================================================================================================

@@ -970,6 +970,70 @@ int kmu_chain_align(kmu_ctx *ctx, const kmu_chain *chains, uint64_t n_chains,
                     const uint8_t *bases_db, const uint64_t *offsets_db, uint32_t n_reads_db,
                     const kmu_align_params *p, int mem, kmu_chain_aln *out);
 
+/* ---- chain alignment paths: the CIGAR of every chain, traced on the device ---------------------------------------------
+ * Segments, band, cell values, KMU_ALN_DONE, KMU_ALN_EXACT and the refusals are exactly those of kmu_chain_align: aln_out[c] is
+ *   the record kmu_chain_align writes for chains[c] at the same band, plus KMU_ALN_PATH, set iff the chain's runs were written.
+ * Path: defined on the cell values only, backwards from (m, n), so it is a pure function of the inputs like the values are.  At
+ *   (0, 0) the walk stops; at i = 0 the step is left, at j = 0 it is up; elsewhere the first of these that applies:
+ *   diagonal, to (i - 1, j - 1), if v(i - 1, j - 1) plus the cost of that step equals v(i, j); otherwise up, to (i - 1, j), if
+ *   v(i - 1, j) plus one edit equals v(i, j); otherwise left, to (i, j - 1).  A diagonal over equal bases is `=`, over different
+ *   bases `X`; up consumes a base of A (the query) only and is `I`; left consumes a base of B' only and is `D`.  A = AA against
+ *   B = A at any band >= 1 is 1I1=, not 1=1I.
+ * Output: the runs of a chain in path order from (0, 0) to (m, n) -- A forward against B, or against the reverse complement of B
+ *   for strand 1 -- each one uint32, len << 4 | op with BAM's codes (KMU_CIGAR_*).  Adjacent runs have different ops, except that
+ *   a run longer than KMU_CIGAR_MAX_RUN is cut: the remainder comes first, every later piece is KMU_CIGAR_MAX_RUN long.  The runs
+ *   of chain c are ops_out[op_offsets_out[c] .. op_offsets_out[c + 1]); op_offsets_out has n_chains + 1 entries and lives where
+ *   the other arrays live.  A chain without PATH has no runs.  For a chain with PATH: sum(=) = matches, sum(X) + sum(I) + sum(D)
+ *   = edit, sum(=) + sum(X) + sum(I) = m, sum(=) + sum(X) + sum(D) = n; m = n = 0 has PATH and no runs.
+ * Counting and capacity: *n_ops_out (host memory in both modes) is always the total.  ops_out == NULL: the count-only call --
+ *   aln_out and op_offsets_out are written all the same.  cap < total: KMU_E_BAD_ARG with *n_ops_out set; nothing is written
+ *   beyond cap.  A chain has at most 2 edit + 1 runs (every run that is not `=` holds an edit; pieces of cut runs come on top),
+ *   so a caller who holds the kmu_chain_aln records of the same band can size ops_out without a count call.
+ * Trace memory: the walk reads two bits per cell that the sweep wrote down: ceil(steps C / 8) * 256 bytes for a chain with
+ *   DONE, steps = (m + n) / 2 + 1 or + 2 and C = 1, 2, 4, 8 for n_diags up to 128, 256, 512, 1024.  The bits of a batch of chains
+ *   live in the context's workspace, and the call never asks the workspace for more than max_trace_bytes of them (the workspace
+ *   rounds a request up by an eighth): it cuts the chains, in their order, into consecutive batches that fit.  No result depends
+ *   on the budget, with one exception: a chain whose own trace is above it is aligned as kmu_chain_align aligns it -- edit,
+ *   matches, DONE, EXACT -- and has no PATH and no runs.  Budgets above 2^40 - 256 bytes are that.
+ * KMU_MEM_DEVICE: every array except p and n_ops_out is device memory.  The call synchronises the stream twice whatever the number
+ *   of batches: once for the plan (the refusal of bad records comes here, before any alignment) and once at the end; KMU_MEM_HOST
+ *   a third time, to bring down the runs once their number is known.
+ * n_chains == 0: KMU_OK, *n_ops_out = 0, op_offsets_out[0] = 0.  KMU_E_BAD_ARG (nothing is launched): null ctx / chains / bases /
+ *   offsets / p / aln_out / op_offsets_out / n_ops_out, non-zero flags, 2 band + 1 > KMU_ALIGN_MAX_DIAGS, bad mem, chains while a
+ *   side has no reads.
+ * KMU_E_UNSUPPORTED: a record with a read >= n_reads_q / n_reads_db, strand > 1, a start above its end or an end above the length
+ *   of its read.  KMU_E_NON_ACGT: a byte outside ACGTacgt inside an aligned segment (a segment of a chain without DONE is not
+ *   aligned).  Both are found on the device and reported at a synchronisation (UNSUPPORTED first); no such record is ever used
+ *   as an index, and the outputs of a refused call are unspecified.
+ * How: the sweep of kmu_chain_align with one more duty: a lane packs the two bits of its cells of 8 / C pair-steps into a word
+ *   and the wave stores the word of all lanes as one 256-byte row; nothing in the sweep waits for these stores.  A second kernel
+ *   walks back, one wave per chain, over rows it stages in LDS 32 at a time, and writes the runs into the end of the chain's own
+ *   slab; a scan of the run counts and a copy put them in place.  One wave per chain in both; the walk is one lane's work.
+ *   DESIGN.md 3.17 has the kernels. */
+#define KMU_ALN_PATH  4u           /* kmu_chain_cigar: the chain's runs were written */
+#define KMU_CIGAR_I 1u             /* BAM's codes: a base of A only */
+#define KMU_CIGAR_D 2u             /* a base of B' only */
+#define KMU_CIGAR_EQ 7u            /* a column of equal bases */
+#define KMU_CIGAR_X 8u             /* a column of different bases */
+#define KMU_CIGAR_MAX_RUN 268435455u /* 2^28 - 1: the longest run one uint32 holds */
+/* 8 GiB.  The workload the project measures with (20 000 ONT-shaped reads, 34 085 chains, 8.0e7 pair-steps) runs at C = 2 for
+ * band 64 (n_diags >= 129): 64 bytes a pair-step, 5.12 GB measured -- one batch with room to spare; band 256 (C = 8, 256 bytes a
+ * pair-step, 20.47 GB measured) is three batches.  Every batch ends with the tail of its longest chains, so a caller with the
+ * memory to spare at wide bands gains from a larger budget (DESIGN.md 3.17 has the figures).  An MI355X has 288 GB; 8 GiB
+ * leaves the rest to the caller's own arrays. */
+#define KMU_CIGAR_TRACE_DEFAULT 8589934592ull
+typedef struct kmu_cigar_params {
+    uint32_t band;
+    uint32_t flags;             /* must be 0 */
+    uint64_t max_trace_bytes;   /* 0 = KMU_CIGAR_TRACE_DEFAULT */
+} kmu_cigar_params;
+int kmu_chain_cigar(kmu_ctx *ctx, const kmu_chain *chains, uint64_t n_chains,
+                    const uint8_t *bases_q, const uint64_t *offsets_q, uint32_t n_reads_q,
+                    const uint8_t *bases_db, const uint64_t *offsets_db, uint32_t n_reads_db,
+                    const kmu_cigar_params *p, int mem,
+                    kmu_chain_aln *aln_out, uint64_t *op_offsets_out,
+                    uint32_t *ops_out, uint64_t cap, uint64_t *n_ops_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -35,6 +35,10 @@ CHAIN_UPPER = 1          # ... and its flag: only read pairs with read_a < read_
 ALIGN_MAX_DIAGS = 1024   # kmu_chain_align: the widest band, in diagonals, one chain may need
 ALIGN_CHUNK = 512        # ... the bases of progress between two stagings of its kernel
 ALN_DONE, ALN_EXACT = 1, 2  # ... and the flags of its records
+ALN_PATH = 4             # kmu_chain_cigar: the chain's runs were written
+CIGAR_I, CIGAR_D, CIGAR_EQ, CIGAR_X = 1, 2, 7, 8  # ... the codes of its runs (BAM's), a run being len << 4 | code
+CIGAR_MAX_RUN = (1 << 28) - 1                      # ... the longest run one uint32 holds
+CIGAR_TRACE_DEFAULT = 8 << 30                      # ... the trace budget of max_trace_bytes = 0
 
 
 def kmer_val_bytes(kmer_type):
@@ -144,6 +148,11 @@ CHAIN_DTYPE = [("read_a", "<u4"), ("read_b", "<u4"), ("strand", "<u4"), ("score"
 class AlignParams(C.Structure):
     """kmu_align_params: the band of kmu_chain_align"""
     _fields_ = [("band", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class CigarParams(C.Structure):
+    """kmu_cigar_params: the band and the trace budget of kmu_chain_cigar"""
+    _fields_ = [("band", C.c_uint32), ("flags", C.c_uint32), ("max_trace_bytes", C.c_uint64)]
 
 
 class ChainAln(C.Structure):

@@ -1,7 +1,8 @@
 // kmu_align_core.h -- the banded alignment of kmu_chain_align as one lane sees it: the geometry of a chain, the value of a cell,
 // the two phases of a pair-step and the 32-base window a lane reads its bases from.  Plain C++ on plain values: the kernel
-// (kmu_chain_align.hip) supplies the registers, the neighbour lanes' values and the staged code words; a host program can drive
-// the same functions over 64 simulated lanes.
+// (kmu_align_sweep.h, for kmu_chain_align.hip and kmu_chain_cigar.hip) supplies the registers, the neighbour lanes' values and the
+// staged code words; a host program can drive the same functions over 64 simulated lanes.  At the end of the file: the path of
+// kmu_chain_cigar -- the direction bits of a cell, where they lie in a chain's trace, and the walk back over them.
 //
 // Diagonals and pairs.  Diagonal e = (j - i) - lo, 0 <= e < n_diags.  Diagonals 2 p and 2 p + 1 are PAIR p; lane l owns the C
 // pairs p = C l .. C l + C - 1 (C = 1, 2, 4, 8: 128, 256, 512, 1024 diagonals in the wave).  A PAIR-STEP u is the two
@@ -152,6 +153,97 @@ KMU_HD AlignStream align_stream(uint32_t seg_lead, uint32_t len, uint32_t strand
     s.n_words = (uint32_t) (((uint64_t) seg_lead + len + 15u) / 16u);
     s.lead = strand ? (uint32_t) (16ull * s.n_words - seg_lead - len) : seg_lead;
     return s;
+}
+
+// ---- the path (kmu_chain_cigar) ---------------------------------------------------------------------------------------------
+// Two bits per cell, from the three neighbour values align_cell takes: the step by which the path that is defined backwards from
+// (m, n) leaves the cell -- the first that applies of diagonal (d <= s), up (up <= left), left -- and, for a diagonal, whether the
+// two bases are equal.  The bits of a cell in row 0 or column 0 or outside the band are never read: the walk knows its way there.
+// Trace: a lane's 4 C bits of a pair-step (pair c: the even cell in bits 4 c + 1 .. 4 c, the odd cell in bits 4 c + 3 .. 4 c + 2)
+// fill one 32-bit word over S = 8 / C pair-steps, the earliest in the lowest bits; ROW r of a chain is that word of pair-steps
+// r S .. r S + S - 1 for all 64 lanes, 256 bytes at word 64 r + lane of the chain's slab.  S divides ALIGN_REFILL, so a row never
+// spans two refills.  A chain's slab is ceil(steps / S) rows.
+constexpr uint32_t ALIGN_DIR_EQ = 0, ALIGN_DIR_X = 1, ALIGN_DIR_UP = 2, ALIGN_DIR_LEFT = 3;
+constexpr uint32_t ALIGN_WALK_ROWS = 32;             // rows the walk has staged at a time: 256 / C pair-steps
+constexpr uint32_t ALIGN_MAX_RUN = (1u << 28) - 1u;  // the longest run one uint32 holds
+constexpr uint32_t ALIGN_DIR_OPS = 0x2187u;          // BAM's code of direction d in bits 4 d + 3 .. 4 d: = 7, X 8, I 1 (up), D 2 (left)
+
+KMU_HD uint32_t align_dir(uint64_t left, uint64_t up, uint64_t dg, uint32_t ca, uint32_t cb) {
+    const uint64_t s = (left < up ? left : up) + ALN_EDIT;
+    const uint64_t d = ca == cb ? dg - 1u : dg + ALN_EDIT;
+    return d <= s ? (ca == cb ? ALIGN_DIR_EQ : ALIGN_DIR_X) : (up <= left ? ALIGN_DIR_UP : ALIGN_DIR_LEFT);
+}
+// the bits of a lane's even cells, from the values align_even is about to replace, and of its odd cells, from those align_even
+// left and align_odd is about to replace: the arguments are the ones of the call that follows
+template <int C>
+KMU_HD uint32_t align_even_dirs(const uint64_t (&ve)[C], const uint64_t (&vo)[C], uint64_t from_left, uint64_t wa, uint64_t wb) {
+    uint32_t bits = 0;
+#pragma unroll
+    for (int c = 0; c < C; c++) {
+        const uint32_t ca = (uint32_t) (wa >> (2 * (C - 1 - c))) & 3u, cb = (uint32_t) (wb >> (2 * c)) & 3u;
+        bits |= align_dir(c ? vo[c ? c - 1 : 0] : from_left, vo[c], ve[c], ca, cb) << (4 * c);
+    }
+    return bits;
+}
+template <int C>
+KMU_HD uint32_t align_odd_dirs(const uint64_t (&ve)[C], const uint64_t (&vo)[C], uint64_t from_right, uint64_t wa, uint64_t wb) {
+    uint32_t bits = 0;
+#pragma unroll
+    for (int c = 0; c < C; c++) {
+        const uint32_t ca = (uint32_t) (wa >> (2 * (C - 1 - c))) & 3u, cb = (uint32_t) (wb >> (2 * (c + 1))) & 3u;
+        bits |= align_dir(ve[c], c + 1 < C ? ve[c + 1 < C ? c + 1 : 0] : from_right, vo[c], ca, cb) << (4 * c + 2);
+    }
+    return bits;
+}
+// the instance a chain's n_diags takes, and the rows of its slab
+KMU_HD uint32_t align_pairs_per_lane(uint32_t n_diags) { return n_diags <= 128u ? 1u : n_diags <= 256u ? 2u : n_diags <= 512u ? 4u : 8u; }
+KMU_HD uint64_t align_trace_rows(uint32_t steps, uint32_t C) { return ((uint64_t) steps * C + 7u) / 8u; }
+
+// where the bits of the in-band cell (i, j) are
+struct AlignSlot {
+    uint32_t row, lane, shift;
+};
+template <int C> KMU_HD AlignSlot align_slot(const AlignGeom &g, uint32_t i, uint32_t j) {
+    constexpr uint32_t S = 8 / C;
+    const uint32_t e = (uint32_t) ((int32_t) (j - i) - g.lo), p = e >> 1;
+    const uint32_t u = i - (uint32_t) g.I0 + p; // the pair-step of row i on pair p
+    return AlignSlot{u / S, p / C, (u % S) * 4u * C + 4u * (p % C) + 2u * (e & 1u)};
+}
+// the first row of the block of ALIGN_WALK_ROWS rows the walk stages when it needs `row` and does not have it: the block ends
+// with that row, because the pair-step never increases along the walk
+KMU_HD uint32_t align_walk_block(uint32_t row) { return row + 1u > ALIGN_WALK_ROWS ? row + 1u - ALIGN_WALK_ROWS : 0u; }
+
+// The walk from (m, n) to (0, 0).  read(slot): the two bits at a slot; emit(run): the runs, len << 4 | BAM code, the LAST run
+// of the path first.  Adjacent runs differ in their code unless a run reached max_run: it is cut there, so in path order the
+// remainder comes first and every later piece is max_run long.  At most two cells of a pair-step are on the path.
+template <int C, class Read, class Emit>
+KMU_HD void align_walk(const AlignGeom &g, Read &&read, Emit &&emit, uint32_t max_run = ALIGN_MAX_RUN) {
+    uint32_t i = g.m, j = g.n, op = 0, len = 0;
+    while (i | j) {
+        uint32_t d, k = 1;
+        if (i == 0) {
+            d = ALIGN_DIR_LEFT;
+            k = j;
+        } else if (j == 0) {
+            d = ALIGN_DIR_UP;
+            k = i;
+        } else {
+            d = read(align_slot<C>(g, i, j));
+        }
+        i -= d == ALIGN_DIR_LEFT ? 0u : k;
+        j -= d == ALIGN_DIR_UP ? 0u : k;
+        while (k) {
+            if (len && (d != op || len == max_run)) {
+                emit((len << 4) | ((ALIGN_DIR_OPS >> (4u * op)) & 15u));
+                len = 0;
+            }
+            op = d;
+            const uint32_t t = k < max_run - len ? k : max_run - len;
+            len += t;
+            k -= t;
+        }
+    }
+    if (len) emit((len << 4) | ((ALIGN_DIR_OPS >> (4u * op)) & 15u));
 }
 
 } // namespace kmu

@@ -37,6 +37,7 @@ SYMBOLS = [
     "kmu_anchor_overlaps", "kmu_anchor_index_create", "kmu_anchor_index_destroy", "kmu_anchor_index_info",
     "kmu_anchor_index_occupancy", "kmu_anchor_index_match", "kmu_components", "kmu_components_knn",
     "kmu_minimizer_layout", "kmu_read_minimizers", "kmu_seed_chains", "kmu_chain_align",
+    "kmu_chain_cigar",
 ]
 
 
@@ -145,6 +146,8 @@ def load():
     L.kmu_seed_chains.argtypes = [vp, vp, C.c_uint64, vp, vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp, C.c_uint32, C.c_uint32,
                                   C.POINTER(A.ChainParams), C.c_int, vp, C.c_uint64, u64p]
     L.kmu_chain_align.argtypes = [vp, vp, C.c_uint64, vp, vp, C.c_uint32, vp, vp, C.c_uint32, C.POINTER(A.AlignParams), C.c_int, vp]
+    L.kmu_chain_cigar.argtypes = [vp, vp, C.c_uint64, vp, vp, C.c_uint32, vp, vp, C.c_uint32, C.POINTER(A.CigarParams), C.c_int, vp, vp,
+                                  vp, C.c_uint64, u64p]
     L.kmu_set_hll_params.argtypes = [vp, C.POINTER(A.HllParams)]
     L.kmu_kmer_hashes_compact.argtypes = [vp, C.POINTER(A.HashParams), vp, vp, vp, C.c_uint32, vp, C.c_uint64, u64p]
     L.kmu_sketch_partial_words.argtypes = [C.POINTER(A.SketchParams)]
@@ -939,6 +942,63 @@ class Context:
         self._check(self.L.kmu_chain_align(self.h, ptr(chains), n, ptr(bases_q), _ptr(off_q)[0], int(off_q.shape[0]) - 1, ptr(bases_db),
                                            _ptr(off_db)[0], int(off_db.shape[0]) - 1, C.byref(p), mem, _ptr(out)[0]))
         return out[:n]
+
+    def chain_cigar(self, chains, bases_q, offsets_q, bases_db=None, offsets_db=None, band=64, max_trace_bytes=0, aln=None):
+        """kmu_chain_cigar: the records of chain_align and, for every chain, the path of its alignment as CIGAR runs (include/kmu.h
+        has the rules).  Returns (aln, ops, op_offsets): aln as chain_align returns it, with A.ALN_PATH set where the chain's runs
+        were written; ops: uint32 runs, len << 4 | code (A.CIGAR_I / D / EQ / X), the runs of chain c being
+        ops[op_offsets[c]:op_offsets[c + 1]], in path order along A; op_offsets: uint64 [n + 1].  numpy in gives numpy out; torch
+        cuda tensors stay on the device (ops int32 and op_offsets int64 holding the same bits).  max_trace_bytes: the workspace the
+        direction bits of one batch of chains may take (0: A.CIGAR_TRACE_DEFAULT); a chain whose own bits need more gets its record
+        without A.ALN_PATH and no runs.  aln: the records chain_align gave for the same chains at the same band -- ops is then sized
+        by 2 edit + 1 runs per chain and the library is called once; without it twice: one call that counts, one that writes."""
+        if bases_db is None:
+            bases_db, offsets_db = bases_q, offsets_q
+        elif offsets_db is None:
+            raise ValueError("bases_db without offsets_db")
+        if not _is_torch(chains):
+            chains = np.ascontiguousarray(chains)
+        mem = self._mem(chains, bases_q, bases_db)
+        n = int(chains.shape[0])
+
+        def offsets(x):
+            if _is_torch(x):
+                if x.is_cuda == (mem == A.MEM_DEVICE):
+                    return x
+                x = x.cpu().numpy()
+            x = np.ascontiguousarray(np.asarray(x).astype(np.uint64))
+            if mem == A.MEM_DEVICE:
+                import torch
+                return torch.from_numpy(x.view(np.int64)).to(chains.device)
+            return x
+        off_q = offsets(offsets_q)
+        off_db = off_q if offsets_db is offsets_q else offsets(offsets_db)
+        p = A.CigarParams(int(band), 0, int(max_trace_bytes))
+        if mem == A.MEM_DEVICE:
+            out = self._new_like(chains, (max(n, 1), 4), np.int32, "int32")
+        else:
+            out = np.zeros(max(n, 1), np.dtype(A.CHAIN_ALN_DTYPE))
+        op_off = self._new_like(chains, n + 1, np.uint64, "int64")
+        none = self._new_like(chains, 16, np.uint8, "uint8")  # an empty array has no address worth passing
+
+        def ptr(x):
+            return _ptr(x)[0] if int(x.shape[0]) else _ptr(none)[0]
+        total = C.c_uint64(0)
+        args = (self.h, ptr(chains), n, ptr(bases_q), _ptr(off_q)[0], int(off_q.shape[0]) - 1, ptr(bases_db), _ptr(off_db)[0],
+                int(off_db.shape[0]) - 1, C.byref(p), mem, _ptr(out)[0], _ptr(op_off)[0])
+        if aln is None:
+            self._check(self.L.kmu_chain_cigar(*args, None, 0, C.byref(total)))
+            cap = int(total.value)
+        else:  # at most 2 edit + 1 runs for a chain that was aligned, none for the others
+            rec = aln.cpu().numpy().view(np.uint32).reshape(-1, 4) if _is_torch(aln) else np.asarray(aln).view(np.uint32).reshape(-1, 4)
+            if rec.shape[0] != n:
+                raise ValueError("aln holds %d records for %d chains" % (rec.shape[0], n))
+            done = (rec[:, 3] & A.ALN_DONE) != 0
+            cap = int((2 * rec[done, 0].astype(np.int64) + 1).sum())
+        ops = self._new_like(chains, max(cap, 1), np.uint32, "int32")
+        if aln is not None or cap:
+            self._check(self.L.kmu_chain_cigar(*args, _ptr(ops)[0], cap, C.byref(total)))
+        return out[:n], ops[:int(total.value)], op_off
 
     def _components(self, call, like, n_nodes, want, count):
         """the outputs of kmu_components / kmu_components_knn allocated where `like` lives, call(*output pointers) run on them,

@@ -8,7 +8,9 @@ an empty row there and seeds nothing.  `seed_pairs` is that join as raw entry pa
 (Context.seed_chains): one colinear chain of seeds per read pair, at base resolution; `read_chains` goes from reads to chains.
 `align_chains` hands the chains and the reads to kmu_chain_align (Context.chain_align): the banded edit distance and the matching
 columns of every chain's two segments; `read_alignments` goes from reads to (chains, alignments), and `paf_lines` writes the two
-record arrays as PAF text on the host.
+record arrays as PAF text on the host.  `cigar_chains` hands the same to kmu_chain_cigar (Context.chain_cigar): the records and the
+path of every alignment as CIGAR runs; `read_cigars` goes from reads to (chains, aln, ops, op_offsets), `cigar_strings` writes the
+runs as text, and `paf_lines(..., cigar=(ops, op_offsets))` appends them as the cg:Z: tag.
 """
 import collections
 
@@ -114,15 +116,65 @@ def read_alignments(ctx, bases, offsets, k, w, fhash=A.FHASH_CANON_INVHASH, max_
     return chains, align_chains(ctx, chains, bases, offsets, band=band)
 
 
-def paf_lines(chains, aln, names_q, offsets_q, names_db=None, offsets_db=None):
+def cigar_chains(ctx, chains, bases_q, offsets_q, bases_db=None, offsets_db=None, band=64, max_trace_bytes=0, aln=None):
+    """The alignment record and the alignment path of every chain (kmu_chain_cigar): (aln, ops, op_offsets) as Context.chain_cigar
+    returns them -- the records of align_chains with A.ALN_PATH where a chain's runs were written, the runs len << 4 | code of
+    chain c in ops[op_offsets[c]:op_offsets[c + 1]].  Arguments as align_chains; max_trace_bytes and aln as Context.chain_cigar."""
+    return ctx.chain_cigar(chains, bases_q, offsets_q, bases_db, offsets_db, band=band, max_trace_bytes=max_trace_bytes, aln=aln)
+
+
+def read_cigars(ctx, bases, offsets, k, w, fhash=A.FHASH_CANON_INVHASH, max_occ=0, max_gap=5000, band_chain=500, min_seeds=3,
+                min_score=0, band=64, max_trace_bytes=0):
+    """From the reads of a batch to the chains between them, their alignments and the alignments' paths in one call: read_chains
+    (band_chain is its band), then cigar_chains with `band`.  Returns (chains, aln, ops, op_offsets)."""
+    chains = read_chains(ctx, bases, offsets, k, w, fhash, max_occ, max_gap, band_chain, min_seeds, min_score)
+    return (chains,) + tuple(cigar_chains(ctx, chains, bases, offsets, band=band, max_trace_bytes=max_trace_bytes))
+
+
+_CIGAR_LETTERS = {A.CIGAR_I: "I", A.CIGAR_D: "D", A.CIGAR_EQ: "=", A.CIGAR_X: "X"}
+
+
+def cigar_strings(ops, op_offsets, chains=None, extended=True):
+    """The runs of kmu_chain_cigar as one CIGAR string per chain, on the host (a chain without runs gives ""): ops and op_offsets
+    are numpy arrays.  extended=False merges `=` and `X` into `M`.  The runs follow the query A forwards; with `chains` given, the
+    runs of a chain on strand 1 are written in reverse order, that is along the forward strand of the target as PAF's cg tag
+    wants them."""
+    ops, off = np.asarray(ops).astype(np.int64) & 0xFFFFFFFF, np.asarray(op_offsets).astype(np.int64)
+    strands = np.zeros(off.shape[0] - 1, np.int64) if chains is None else np.asarray(chains)["strand"]
+    out = []
+    for c in range(off.shape[0] - 1):
+        runs = [(int(v) >> 4, _CIGAR_LETTERS[int(v) & 15]) for v in ops[off[c]:off[c + 1]]]
+        if strands[c]:
+            runs.reverse()
+        if not extended:
+            merged = []
+            for n, letter in runs:
+                letter = "M" if letter in "=X" else letter
+                if merged and merged[-1][1] == letter:
+                    merged[-1] = (merged[-1][0] + n, letter)
+                else:
+                    merged.append((n, letter))
+            runs = merged
+        out.append("".join("%d%s" % r for r in runs))
+    return out
+
+
+def paf_lines(chains, aln, names_q, offsets_q, names_db=None, offsets_db=None, cigar=None):
     """One PAF line per chain, on the host: chains (A.CHAIN_DTYPE) and aln (A.CHAIN_ALN_DTYPE) are numpy records of the same
     length, names_* the names of the reads, offsets_* their offsets (db=None: the self-join).  The 12 standard columns -- query
     name, length, start, end, strand, target name, length, start, end, matches, matches + edit, mapq 255 -- then NM:i:edit,
-    s1:i:score and cm:i:n_seeds.  A record without A.ALN_DONE writes 0 matches, a block of max(m, n) and no NM tag."""
+    s1:i:score and cm:i:n_seeds.  A record without A.ALN_DONE writes 0 matches, a block of max(m, n) and no NM tag.
+    cigar=(ops, op_offsets), the runs of cigar_chains for the same chains: a record with A.ALN_PATH also gets cg:Z: with its runs
+    along the target's forward strand (cigar_strings with `chains`)."""
     if names_db is None:
         names_db, offsets_db = names_q, offsets_q
     off_q, off_db = np.asarray(offsets_q).astype(np.int64), np.asarray(offsets_db).astype(np.int64)
     lines = []
+    if cigar is not None:
+        text = cigar_strings(cigar[0], cigar[1], chains)
+        for line, a, cg in zip(paf_lines(chains, aln, names_q, offsets_q, names_db, offsets_db), np.asarray(aln).tolist(), text):
+            lines.append(line + "\tcg:Z:" + cg if a[3] & A.ALN_PATH else line)
+        return lines
     for c, a in zip(np.asarray(chains).tolist(), np.asarray(aln).tolist()):
         read_a, read_b, strand, score, n_seeds, _, a_start, a_end, b_start, b_end = c
         edit, matches, _, flags = a
