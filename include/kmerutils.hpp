@@ -28,6 +28,7 @@
  *                                                            (connected components of overlap records / neighbour lists)
  *                 chain_align, align_chains, read_alignments, paf_line (banded edit distance and matches per chain; PAF text)
  *                 ChainCigars, chain_cigar, cigar_chains, cigar_string, paf_line with cg:Z: (the path of every chain's alignment)
+ *                 ChainPileups, chain_pileup, pileup_chains, PileCalls, pile_call (per-base votes of the paths, calls per base and read)
  *                 seed_chains, seed_pairs, chain_hits, read_chains (one base-resolution chain per read pair from minimizer
  *                                                            hits)                          (beyond the reference)
  *   counting      KmerCountT (trait), KmerCounter, KmerCounterPool, count_kmer_threaded_one_to_many
@@ -2017,6 +2018,84 @@ inline std::string paf_line(const kmu_chain &c, const ChainCigars &cigars, size_
     std::string s = paf_line(c, cigars.aln[at], name_q, len_q, name_db, len_db);
     if (cigars.aln[at].flags & KMU_ALN_PATH) s += "\tcg:Z:" + cigar_string(cigars, at, true, c.strand != 0);
     return s;
+}
+
+// =====================================================================================================================
+// read pileup (kmu_chain_pileup, kmu_pile_call; the reference has no such unit)
+// =====================================================================================================================
+
+/// What chain_pileup returns: one row of KMU_PILE_COLS counts per base of a batch (include/kmu.h has the columns).  In the
+/// self-join both sides vote into ONE table, `q`, and `shared` is set; otherwise `q` belongs to the q batch and `db` to the db batch
+/// (a side that was not asked for is empty).
+struct ChainPileups {
+    std::vector<uint32_t> q, db;
+    bool shared = false;
+    const std::vector<uint32_t> &of_db() const { return shared ? q : db; }
+    /// A + C + G + T + DEL of a row of `table`
+    static uint64_t depth(const std::vector<uint32_t> &table, uint64_t row) {
+        uint64_t d = 0;
+        for (uint32_t k = 0; k <= KMU_PILE_DEL; k++) d += table[row * KMU_PILE_COLS + k];
+        return d;
+    }
+};
+
+/// kmu_chain_pileup on host arrays: the votes of every chain's runs onto the bases of both reads.  chains and cigars: the chains
+/// given to chain_cigar and what it returned; q, db as there (db == nullptr: the self-join, one shared table); sides: KMU_PILE_Q,
+/// KMU_PILE_DB or both.  into: tables of an earlier call on the same batches to add to (moved from).
+inline ChainPileups chain_pileup(const std::vector<kmu_chain> &chains, const ChainCigars &cigars, const detail::Batch &q,
+                                 const detail::Batch *db = nullptr, uint32_t sides = KMU_PILE_Q | KMU_PILE_DB, ChainPileups into = {},
+                                 Context &ctx = Context::global()) {
+    const detail::Batch bq = detail::unpacked(q);
+    detail::Batch bdb_own;
+    if (db) bdb_own = detail::unpacked(*db);
+    const detail::Batch &bdb = db ? bdb_own : bq;
+    if (bq.on_device() || bdb.on_device()) throw std::invalid_argument("chain_pileup returns host arrays: it needs the sequences in host memory");
+    if (cigars.aln.size() != chains.size() || cigars.op_offsets.size() != chains.size() + 1)
+        throw std::invalid_argument("chain_pileup: the records and run offsets are not those of the chains");
+    ChainPileups out = std::move(into);
+    out.shared = !db && (sides & KMU_PILE_Q) && (sides & KMU_PILE_DB);
+    const bool db_in_q = !db && !(sides & KMU_PILE_Q); // the self-join's one table also when only the B side votes
+    if ((sides & KMU_PILE_Q) || db_in_q) out.q.resize(size_t(bq.offsets.back()) * KMU_PILE_COLS, 0u);
+    if ((sides & KMU_PILE_DB) && db) out.db.resize(size_t(bdb.offsets.back()) * KMU_PILE_COLS, 0u);
+    if (chains.empty()) return out;
+    kmu_pileup_params p{};
+    p.flags = sides;
+    uint32_t *table_db = db ? out.db.data() : out.q.data();
+    ctx.check(kmu_chain_pileup(ctx.raw(), chains.data(), chains.size(), cigars.aln.data(), cigars.op_offsets.data(), cigars.ops.data(),
+                               cigars.ops.size(), bq.bytes.data(), bq.offsets.data(), bq.n(), bdb.bytes.data(), bdb.offsets.data(), bdb.n(), &p,
+                               KMU_MEM_HOST, (sides & KMU_PILE_Q) ? out.q.data() : nullptr, (sides & KMU_PILE_DB) ? table_db : nullptr));
+    return out;
+}
+/// The same under the name of the Python route (minimizer.pileup_chains)
+inline ChainPileups pileup_chains(const std::vector<kmu_chain> &chains, const ChainCigars &cigars, const detail::Batch &q,
+                                  const detail::Batch *db = nullptr, uint32_t sides = KMU_PILE_Q | KMU_PILE_DB, ChainPileups into = {},
+                                  Context &ctx = Context::global()) {
+    return chain_pileup(chains, cigars, q, db, sides, std::move(into), ctx);
+}
+
+/// What pile_call returns: the call byte of every base (code | KMU_CALL_INS | KMU_CALL_DIFF, KMU_CALL_NONE below min_depth) and the
+/// summary of every read.
+struct PileCalls {
+    std::vector<uint8_t> call;
+    std::vector<kmu_read_pile> reads;
+};
+
+/// kmu_pile_call on host arrays: `table` is a table of chain_pileup for `batch`.
+inline PileCalls pile_call(const std::vector<uint32_t> &table, const detail::Batch &batch, uint32_t min_depth = 3, Context &ctx = Context::global()) {
+    const detail::Batch b = detail::unpacked(batch);
+    if (b.on_device()) throw std::invalid_argument("pile_call returns host arrays: it needs the sequences in host memory");
+    if (table.size() != size_t(b.offsets.back()) * KMU_PILE_COLS) throw std::invalid_argument("pile_call: the table is not one of this batch");
+    PileCalls out;
+    out.call.resize(b.offsets.back());
+    out.reads.resize(b.n());
+    if (!b.n()) return out;
+    kmu_pile_call_params p{};
+    p.min_depth = min_depth;
+    uint8_t none = 0;
+    ctx.check(kmu_pile_call(ctx.raw(), table.empty() ? reinterpret_cast<const uint32_t *>(&none) : table.data(),
+                            b.bytes.empty() ? &none : b.bytes.data(), b.offsets.data(), b.n(), &p, KMU_MEM_HOST,
+                            out.call.empty() ? &none : out.call.data(), out.reads.data()));
+    return out;
 }
 
 // =====================================================================================================================

@@ -1034,6 +1034,96 @@ int kmu_chain_cigar(kmu_ctx *ctx, const kmu_chain *chains, uint64_t n_chains,
                     kmu_chain_aln *aln_out, uint64_t *op_offsets_out,
                     uint32_t *ops_out, uint64_t cap, uint64_t *n_ops_out);
 
+/* ---- read pileup: per-base votes of every chain's runs onto both reads ---------------------------------------------------
+ * Inputs: the inputs and the outputs of ONE kmu_chain_cigar call -- chains, aln (its records), op_offsets (n_chains + 1), ops, n_ops
+ *   (the total) -- and the two KMU_INPUT_ASCII batches; the db arrays may be the q arrays (a self-join).
+ * Tables: pile_q / pile_db have one row per base of their batch; row offsets[read] + pos is KMU_PILE_COLS uint32 (32 bytes) indexed
+ *   by KMU_PILE_*.  The call ADDS to what the tables hold: the caller zeroes them, and several calls (several db batches against
+ *   one q batch) accumulate.  pile_q and pile_db may be the same array when the two batches are the same arrays -- the self-join
+ *   under KMU_CHAIN_UPPER, where every read then collects the votes of all its partners.
+ * flags: KMU_PILE_Q votes onto the A side, KMU_PILE_DB onto the B side; at least one; the table of a side not asked for may be NULL.
+ * Which chains vote: those whose aln record has KMU_ALN_PATH.  Every other chain must have no runs and votes nothing.
+ * Coordinates: the runs of a chain follow A forwards against B' (B on strand 0, its reverse complement on strand 1) from
+ *   (i, j) = (0, 0): `=` and `X` advance both and are treated alike, as a diagonal column -- no bases are compared; `I` advances i,
+ *   `D` advances j.  Base i of A is row offsets_q[read_a] + a_start + i; base j of B' is base b_start + j of read b on strand 0 and
+ *   b_end - 1 - j on strand 1.
+ * A side: a diagonal column (i, j) adds 1 to the letter of B' at j (on strand 1 the complement of B's forward letter) in A's row i;
+ *   each base i of an I run adds 1 to DEL in row i; a D run of length L lies between A's bases i - 1 and i and adds 1 to INS and L
+ *   to INS_BASES in row i - 1, nothing for i = 0.
+ * B side, in forward coordinates and forward letters of read b: a diagonal column adds 1 to A's letter at i (complemented on
+ *   strand 1) in B's row for j; each base of a D run adds 1 to DEL; an I run of length L adds 1 to INS and L to INS_BASES in the row
+ *   of the base before the gap in read b's forward direction: B' index j - 1 on strand 0 (nothing for j = 0), B' index j on strand 1
+ *   (nothing for j = n).
+ * ENDS: on each side asked for, a voting chain with a non-empty segment adds 1 at the first row of its segment and 1 at the last (a
+ *   segment of one base gets 2).
+ * It follows: for one voting chain alone A + C + G + T + DEL is 1 on every row of its segment and 0 elsewhere, on both sides; the
+ *   counts are sums of integers, so the order of the chains, the launch shape and timing change nothing; a cut run votes as the two
+ *   runs it is (two INS).
+ * KMU_MEM_DEVICE: every array except p is device memory; the call synchronises the stream twice: after the checks and at the end.
+ *   KMU_MEM_HOST: the arrays go up through the context's workspace and the votes come back added to the caller's tables.
+ * n_chains == 0: KMU_OK.  KMU_E_BAD_ARG (nothing is launched): null ctx / chains / aln / op_offsets / bases / offsets / p, ops null
+ *   with n_ops > 0, flags 0 or with unknown bits, a null table for a side asked for, one table for both sides of two different
+ *   batches, bad mem, chains while a side has no reads.
+ * KMU_E_UNSUPPORTED, found on the device BEFORE any vote -- a refused call leaves both tables untouched: a record kmu_chain_cigar
+ *   would refuse; op_offsets that decrease or end above n_ops; runs on a chain without PATH; a run with an op outside {I, D, =, X} or
+ *   of length 0; a PATH chain whose runs do not sum to m on A and to n on B.  No inconsistent run is ever used as an index.
+ * KMU_E_NON_ACGT: a voted letter outside ACGTacgt (a letter of a side that is not voted is not looked at); the tables are then
+ *   unspecified.
+ * How: the runs of every chain are cut into tiles of 64.  One wave per chain sums the bases its tiles consume -- the checks, and
+ *   (i, j) at the start of every tile; a scan gives the tile offsets.  The vote kernel takes one wave per tile: it scans the tile's
+ *   column counts and walks the columns 64 at a time, one column per lane, so a wave's atomic adds (plain uint32) fall on about 64
+ *   consecutive rows; a run's INS votes come from the lane that owns the run.  A long chain spreads over as many waves as it has
+ *   tiles.  DESIGN.md 3.18 has the kernels. */
+#define KMU_PILE_COLS 8            /* uint32 per row */
+#define KMU_PILE_A 0               /* votes for a letter: A, C, G, T */
+#define KMU_PILE_C 1
+#define KMU_PILE_G 2
+#define KMU_PILE_T 3
+#define KMU_PILE_DEL 4             /* partners aligned over the base that have nothing there */
+#define KMU_PILE_INS 5             /* partners with extra bases behind the base */
+#define KMU_PILE_INS_BASES 6       /* ... and how many bases in all */
+#define KMU_PILE_ENDS 7            /* segments that begin or end at the base */
+#define KMU_PILE_Q 1u              /* flags: vote onto the A side */
+#define KMU_PILE_DB 2u             /* vote onto the B side */
+typedef struct kmu_pileup_params {
+    uint32_t flags;
+} kmu_pileup_params;
+int kmu_chain_pileup(kmu_ctx *ctx, const kmu_chain *chains, uint64_t n_chains, const kmu_chain_aln *aln,
+                     const uint64_t *op_offsets, const uint32_t *ops, uint64_t n_ops,
+                     const uint8_t *bases_q, const uint64_t *offsets_q, uint32_t n_reads_q,
+                     const uint8_t *bases_db, const uint64_t *offsets_db, uint32_t n_reads_db,
+                     const kmu_pileup_params *p, int mem, uint32_t *pile_q, uint32_t *pile_db);
+
+/* ---- pileup calls: a call per base and a summary per read from a table of kmu_chain_pileup ------------------------------
+ * pile: the table of the batch (bases, offsets, n_reads).  Per base g, depth = A + C + G + T + DEL.
+ * call_out[g] (n_bases bytes; may be NULL): bits 0..2 are KMU_CALL_NONE if depth < min_depth, otherwise the code 0..4 (KMU_PILE_A ..
+ *   KMU_PILE_DEL) with the largest count; ties go to the read's own base if it is among the tied codes, otherwise to the smallest
+ *   code; a read base outside ACGTacgt equals no code.  KMU_CALL_INS: called and 2 INS > depth.  KMU_CALL_DIFF: called and the
+ *   code differs from the read's own base (a DEL call always differs).
+ * reads_out[r] (n_reads records; may be NULL, not both): the summary of read r; its counts are of rows with depth >= min_depth.
+ * min_depth >= 1; flags must be 0.  n_reads == 0: KMU_OK.  KMU_E_BAD_ARG: null ctx / pile / bases / offsets / p, both outputs null,
+ *   min_depth == 0, non-zero flags, bad mem.  KMU_MEM_DEVICE: every array except p is device memory; KMU_MEM_HOST: through the
+ *   workspace.  The pileup counts insertions but does not collect the inserted letters.
+ * How: one lane per base for the calls; one wave per read, 64 rows at a time, for the summaries. */
+#define KMU_CALL_NONE 7u           /* bits 0..2: the depth is below min_depth */
+#define KMU_CALL_INS 8u            /* most partners have extra bases behind this one */
+#define KMU_CALL_DIFF 16u          /* the call is not the read's own base */
+typedef struct kmu_pile_call_params {
+    uint32_t min_depth;  /* >= 1 */
+    uint32_t flags;      /* must be 0 */
+} kmu_pile_call_params;
+typedef struct {         /* 32 bytes */
+    uint32_t n_bases;    /* bases of the read */
+    uint32_t covered;    /* rows with depth >= min_depth */
+    uint32_t n_diff;     /* covered rows with KMU_CALL_DIFF */
+    uint32_t n_del;      /* covered rows called KMU_PILE_DEL */
+    uint32_t n_ins;      /* covered rows with KMU_CALL_INS */
+    uint32_t max_depth;  /* largest depth over the read's rows (2^32 - 1 if it is above) */
+    uint64_t depth_sum;  /* sum of depth over all rows of the read */
+} kmu_read_pile;
+int kmu_pile_call(kmu_ctx *ctx, const uint32_t *pile, const uint8_t *bases, const uint64_t *offsets, uint32_t n_reads,
+                  const kmu_pile_call_params *p, int mem, uint8_t *call_out, kmu_read_pile *reads_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -39,6 +39,10 @@ ALN_PATH = 4             # kmu_chain_cigar: the chain's runs were written
 CIGAR_I, CIGAR_D, CIGAR_EQ, CIGAR_X = 1, 2, 7, 8  # ... the codes of its runs (BAM's), a run being len << 4 | code
 CIGAR_MAX_RUN = (1 << 28) - 1                      # ... the longest run one uint32 holds
 CIGAR_TRACE_DEFAULT = 8 << 30                      # ... the trace budget of max_trace_bytes = 0
+PILE_COLS = 8            # kmu_chain_pileup: uint32 per row of a table, indexed by
+PILE_A, PILE_C, PILE_G, PILE_T, PILE_DEL, PILE_INS, PILE_INS_BASES, PILE_ENDS = range(8)
+PILE_Q, PILE_DB = 1, 2   # ... and its flags: vote onto the A side, onto the B side
+CALL_NONE, CALL_INS, CALL_DIFF = 7, 8, 16  # kmu_pile_call: bits 0..2 of an uncalled base, and the two bits above the code
 
 
 def kmer_val_bytes(kmer_type):
@@ -153,6 +157,27 @@ class AlignParams(C.Structure):
 class CigarParams(C.Structure):
     """kmu_cigar_params: the band and the trace budget of kmu_chain_cigar"""
     _fields_ = [("band", C.c_uint32), ("flags", C.c_uint32), ("max_trace_bytes", C.c_uint64)]
+
+
+class PileupParams(C.Structure):
+    """kmu_pileup_params: the sides kmu_chain_pileup votes onto"""
+    _fields_ = [("flags", C.c_uint32)]
+
+
+class PileCallParams(C.Structure):
+    """kmu_pile_call_params: the depth from which kmu_pile_call calls a base"""
+    _fields_ = [("min_depth", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class ReadPile(C.Structure):
+    """kmu_read_pile: the summary of one read's rows (kmu_pile_call)"""
+    _fields_ = [("n_bases", C.c_uint32), ("covered", C.c_uint32), ("n_diff", C.c_uint32), ("n_del", C.c_uint32),
+                ("n_ins", C.c_uint32), ("max_depth", C.c_uint32), ("depth_sum", C.c_uint64)]
+
+
+# the same record as a numpy dtype (32 bytes)
+READ_PILE_DTYPE = [("n_bases", "<u4"), ("covered", "<u4"), ("n_diff", "<u4"), ("n_del", "<u4"), ("n_ins", "<u4"), ("max_depth", "<u4"),
+                   ("depth_sum", "<u8")]
 
 
 class ChainAln(C.Structure):

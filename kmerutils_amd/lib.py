@@ -37,7 +37,7 @@ SYMBOLS = [
     "kmu_anchor_overlaps", "kmu_anchor_index_create", "kmu_anchor_index_destroy", "kmu_anchor_index_info",
     "kmu_anchor_index_occupancy", "kmu_anchor_index_match", "kmu_components", "kmu_components_knn",
     "kmu_minimizer_layout", "kmu_read_minimizers", "kmu_seed_chains", "kmu_chain_align",
-    "kmu_chain_cigar",
+    "kmu_chain_cigar", "kmu_chain_pileup", "kmu_pile_call",
 ]
 
 
@@ -47,6 +47,7 @@ SYMBOLS = [
 Components = collections.namedtuple("Components", "label cluster size members n_components")
 COMPONENTS_WANT = ("cluster", "size", "members")
 MINIMIZERS_WANT = ("pos", "read", "strand")  # the optional outputs of Context.read_minimizers
+PILE_CALL_WANT = ("call", "reads")           # the outputs of Context.pile_call
 
 
 class KmuError(RuntimeError):
@@ -148,6 +149,9 @@ def load():
     L.kmu_chain_align.argtypes = [vp, vp, C.c_uint64, vp, vp, C.c_uint32, vp, vp, C.c_uint32, C.POINTER(A.AlignParams), C.c_int, vp]
     L.kmu_chain_cigar.argtypes = [vp, vp, C.c_uint64, vp, vp, C.c_uint32, vp, vp, C.c_uint32, C.POINTER(A.CigarParams), C.c_int, vp, vp,
                                   vp, C.c_uint64, u64p]
+    L.kmu_chain_pileup.argtypes = [vp, vp, C.c_uint64, vp, vp, vp, C.c_uint64, vp, vp, C.c_uint32, vp, vp, C.c_uint32,
+                                   C.POINTER(A.PileupParams), C.c_int, vp, vp]
+    L.kmu_pile_call.argtypes = [vp, vp, vp, vp, C.c_uint32, C.POINTER(A.PileCallParams), C.c_int, vp, vp]
     L.kmu_set_hll_params.argtypes = [vp, C.POINTER(A.HllParams)]
     L.kmu_kmer_hashes_compact.argtypes = [vp, C.POINTER(A.HashParams), vp, vp, vp, C.c_uint32, vp, C.c_uint64, u64p]
     L.kmu_sketch_partial_words.argtypes = [C.POINTER(A.SketchParams)]
@@ -999,6 +1003,93 @@ class Context:
         if aln is not None or cap:
             self._check(self.L.kmu_chain_cigar(*args, _ptr(ops)[0], cap, C.byref(total)))
         return out[:n], ops[:int(total.value)], op_off
+
+    def _offsets_like(self, x, ref, mem):
+        """the offsets of a batch as uint64 where the arrays of the call live (int64 holding the same bits for torch)"""
+        if _is_torch(x):
+            if x.is_cuda == (mem == A.MEM_DEVICE):
+                return x
+            x = x.cpu().numpy()
+        x = np.ascontiguousarray(np.asarray(x).astype(np.uint64))
+        if mem == A.MEM_DEVICE:
+            import torch
+            return torch.from_numpy(x.view(np.int64)).to(ref.device)
+        return x
+
+    def chain_pileup(self, chains, aln, ops, op_offsets, bases_q, offsets_q, bases_db=None, offsets_db=None, sides=A.PILE_Q | A.PILE_DB,
+                     into=None):
+        """kmu_chain_pileup: the votes of every chain's runs onto the bases of both reads (include/kmu.h has the rules).  chains, aln,
+        ops, op_offsets: the records given to chain_cigar and what it returned; bases_* / offsets_*: the same batches (db=None: the
+        self-join).  Returns (pile_q, pile_db): uint32 [n_bases, A.PILE_COLS] tables, one row per base, columns A.PILE_A ..
+        A.PILE_ENDS; numpy in gives numpy out, torch cuda tensors stay on the device (int32 holding the same bits).  In the
+        self-join both names are the same array, so every read collects the votes of all its partners; the table of a side that
+        `sides` (A.PILE_Q, A.PILE_DB) leaves out is None.  into=(pile_q, pile_db), or one table for the self-join: tables to
+        accumulate into; otherwise they are allocated here, zeroed."""
+        own = bases_db is None
+        if own:
+            bases_db, offsets_db = bases_q, offsets_q
+        elif offsets_db is None:
+            raise ValueError("bases_db without offsets_db")
+        if not _is_torch(chains):
+            chains = np.ascontiguousarray(chains)
+        if not _is_torch(aln):
+            aln = np.ascontiguousarray(aln)
+        mem = self._mem(chains, aln, ops, op_offsets, bases_q, bases_db)
+        n = int(chains.shape[0])
+        if int(aln.shape[0]) != n or int(op_offsets.shape[0]) != n + 1:
+            raise ValueError("%d chains need %d alignment records and %d run offsets" % (n, n, n + 1))
+        off_q = self._offsets_like(offsets_q, chains, mem)
+        off_db = off_q if offsets_db is offsets_q else self._offsets_like(offsets_db, chains, mem)
+        sides = int(sides)
+        if into is None:
+            pile_q = self._new_like(chains, (int(off_q[-1]), A.PILE_COLS), np.uint32, "int32") if sides & A.PILE_Q else None
+            if own and pile_q is not None:
+                pile_db = pile_q if sides & A.PILE_DB else None
+            else:
+                pile_db = self._new_like(chains, (int(off_db[-1]), A.PILE_COLS), np.uint32, "int32") if sides & A.PILE_DB else None
+        else:
+            pile_q, pile_db = into if isinstance(into, (tuple, list)) else (into, into)
+            if (sides & A.PILE_Q and pile_q is None) or (sides & A.PILE_DB and pile_db is None):
+                raise ValueError("into lacks the table of a side that is asked for")
+        p = A.PileupParams(sides)
+        none = self._new_like(chains, 16, np.uint8, "uint8")  # an empty array has no address worth passing
+
+        def ptr(x):
+            return _ptr(x)[0] if int(x.shape[0]) else _ptr(none)[0]
+        self._check(self.L.kmu_chain_pileup(self.h, ptr(chains), n, ptr(aln), _ptr(op_offsets)[0], ptr(ops), int(ops.shape[0]), ptr(bases_q),
+                                            _ptr(off_q)[0], int(off_q.shape[0]) - 1, ptr(bases_db), _ptr(off_db)[0], int(off_db.shape[0]) - 1,
+                                            C.byref(p), mem, ptr(pile_q) if sides & A.PILE_Q else None,
+                                            ptr(pile_db) if sides & A.PILE_DB else None))
+        return pile_q, pile_db
+
+    def pile_call(self, pile, bases, offsets, min_depth=3, want=PILE_CALL_WANT):
+        """kmu_pile_call: from a table of chain_pileup and the batch it belongs to, the call of every base -- uint8 [n_bases]: the code
+        A.PILE_A .. A.PILE_DEL with the largest count (A.CALL_NONE below min_depth) and the bits A.CALL_INS and A.CALL_DIFF -- and the
+        summary of every read (A.READ_PILE_DTYPE records; for torch an int32 tensor [n_reads, 8] holding the same bits).  Returns
+        (call, reads); `want` names the outputs to compute ("call", "reads"), the other is None."""
+        unknown = [w for w in want if w not in PILE_CALL_WANT]
+        if unknown or not want:
+            raise ValueError("want holds %r: the outputs are %r, at least one" % (list(want), PILE_CALL_WANT))
+        mem = self._mem(pile, bases)
+        off = self._offsets_like(offsets, pile, mem)
+        n_reads = int(off.shape[0]) - 1
+        n_bases = int(off[-1])
+        if int(pile.shape[0]) != n_bases or int(bases.shape[0]) != n_bases:
+            raise ValueError("the batch has %d bases: the table and the bases must have as many rows" % n_bases)
+        call = self._new_like(pile, max(n_bases, 1), np.uint8, "uint8") if "call" in want else None
+        if "reads" not in want:
+            reads = None
+        elif mem == A.MEM_DEVICE:
+            reads = self._new_like(pile, (max(n_reads, 1), 8), np.int32, "int32")
+        else:
+            reads = np.zeros(max(n_reads, 1), np.dtype(A.READ_PILE_DTYPE))
+        p = A.PileCallParams(int(min_depth), 0)
+        none = self._new_like(pile, 16, np.uint8, "uint8")  # an empty array has no address worth passing
+
+        def ptr(x):
+            return _ptr(x)[0] if int(x.shape[0]) else _ptr(none)[0]
+        self._check(self.L.kmu_pile_call(self.h, ptr(pile), ptr(bases), _ptr(off)[0], n_reads, C.byref(p), mem, _ptr(call)[0], _ptr(reads)[0]))
+        return (call[:n_bases] if call is not None else None), (reads[:n_reads] if reads is not None else None)
 
     def _components(self, call, like, n_nodes, want, count):
         """the outputs of kmu_components / kmu_components_knn allocated where `like` lives, call(*output pointers) run on them,

@@ -10,7 +10,10 @@ an empty row there and seeds nothing.  `seed_pairs` is that join as raw entry pa
 columns of every chain's two segments; `read_alignments` goes from reads to (chains, alignments), and `paf_lines` writes the two
 record arrays as PAF text on the host.  `cigar_chains` hands the same to kmu_chain_cigar (Context.chain_cigar): the records and the
 path of every alignment as CIGAR runs; `read_cigars` goes from reads to (chains, aln, ops, op_offsets), `cigar_strings` writes the
-runs as text, and `paf_lines(..., cigar=(ops, op_offsets))` appends them as the cg:Z: tag.
+runs as text, and `paf_lines(..., cigar=(ops, op_offsets))` appends them as the cg:Z: tag.  `pileup_chains` hands the chains, their
+records and their runs to kmu_chain_pileup (Context.chain_pileup): for every base of every read, how many partners were aligned
+over it and what they had there; `read_pileups` goes from reads to (chains, aln, pile, call, reads) -- the self-join pileup and the
+calls of kmu_pile_call -- without the runs leaving where the reads live, and `pile_depth` is the depth column of a table.
 """
 import collections
 
@@ -129,6 +132,34 @@ def read_cigars(ctx, bases, offsets, k, w, fhash=A.FHASH_CANON_INVHASH, max_occ=
     (band_chain is its band), then cigar_chains with `band`.  Returns (chains, aln, ops, op_offsets)."""
     chains = read_chains(ctx, bases, offsets, k, w, fhash, max_occ, max_gap, band_chain, min_seeds, min_score)
     return (chains,) + tuple(cigar_chains(ctx, chains, bases, offsets, band=band, max_trace_bytes=max_trace_bytes))
+
+
+def pileup_chains(ctx, chains, aln, ops, op_offsets, bases_q, offsets_q, bases_db=None, offsets_db=None, sides=A.PILE_Q | A.PILE_DB,
+                  into=None):
+    """The votes of every chain's runs onto the bases of both reads (kmu_chain_pileup): (pile_q, pile_db) as Context.chain_pileup
+    returns them -- uint32 [n_bases, A.PILE_COLS], one row per base, columns A.PILE_A .. A.PILE_ENDS; one shared table in the
+    self-join (db=None).  chains, aln, ops, op_offsets: the chains and what cigar_chains gave for them; sides and into as
+    Context.chain_pileup."""
+    return ctx.chain_pileup(chains, aln, ops, op_offsets, bases_q, offsets_q, bases_db, offsets_db, sides=sides, into=into)
+
+
+def read_pileups(ctx, bases, offsets, k, w, fhash=A.FHASH_CANON_INVHASH, max_occ=0, max_gap=5000, band_chain=500, min_seeds=3,
+                 min_score=0, band=64, max_trace_bytes=0, min_depth=3):
+    """From the reads of a batch to the pileup of every read and its calls in one call: read_cigars, then the self-join of
+    pileup_chains (every read collects the votes of all its partners in one table), then Context.pile_call with `min_depth`.
+    Returns (chains, aln, pile, call, reads)."""
+    chains, aln, ops, op_offsets = read_cigars(ctx, bases, offsets, k, w, fhash, max_occ, max_gap, band_chain, min_seeds, min_score, band,
+                                               max_trace_bytes)
+    pile, _ = pileup_chains(ctx, chains, aln, ops, op_offsets, bases, offsets)
+    call, reads = ctx.pile_call(pile, bases, offsets, min_depth=min_depth)
+    return chains, aln, pile, call, reads
+
+
+def pile_depth(pile):
+    """A + C + G + T + DEL of every row of a pileup table: how many partners were aligned over the base (int64; numpy or torch)"""
+    if _is_torch(pile):
+        return (pile[:, :A.PILE_INS].long() & 0xFFFFFFFF).sum(dim=1)
+    return np.asarray(pile)[:, :A.PILE_INS].astype(np.int64).sum(axis=1)
 
 
 _CIGAR_LETTERS = {A.CIGAR_I: "I", A.CIGAR_D: "D", A.CIGAR_EQ: "=", A.CIGAR_X: "X"}
