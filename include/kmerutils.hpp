@@ -29,6 +29,8 @@
  *                 chain_align, align_chains, read_alignments, paf_line (banded edit distance and matches per chain; PAF text)
  *                 ChainCigars, chain_cigar, cigar_chains, cigar_string, paf_line with cg:Z: (the path of every chain's alignment)
  *                 ChainPileups, chain_pileup, pileup_chains, PileCalls, pile_call (per-base votes of the paths, calls per base and read)
+ *                 InsPlan, pile_ins_plan, ChainInsertions, chain_pile_ins, ConsensusReads, pile_consensus, correct_chains, correct_reads
+ *                 (the inserted letters and the corrected reads)
  *                 seed_chains, seed_pairs, chain_hits, read_chains (one base-resolution chain per read pair from minimizer
  *                                                            hits)                          (beyond the reference)
  *   counting      KmerCountT (trait), KmerCounter, KmerCounterPool, count_kmer_threaded_one_to_many
@@ -2096,6 +2098,145 @@ inline PileCalls pile_call(const std::vector<uint32_t> &table, const detail::Bat
                             b.bytes.empty() ? &none : b.bytes.data(), b.offsets.data(), b.n(), &p, KMU_MEM_HOST,
                             out.call.empty() ? &none : out.call.data(), out.reads.data()));
     return out;
+}
+
+// =====================================================================================================================
+// read correction (kmu_pile_ins_plan, kmu_chain_pile_ins, kmu_pile_consensus; the reference has no such unit)
+// =====================================================================================================================
+
+/// What pile_ins_plan returns: the number of insertion slots of every base of a batch, and their sum.  Slot s of row g has the index
+/// S(g) + s, S being the exclusive prefix sum of ins_len.
+struct InsPlan {
+    std::vector<uint8_t> ins_len;
+    uint64_t n_slots = 0;
+};
+
+/// kmu_pile_ins_plan on host arrays: `table` is a table of chain_pileup and `call` the call bytes pile_call made from it.
+inline InsPlan pile_ins_plan(const std::vector<uint32_t> &table, const std::vector<uint8_t> &call, uint32_t max_ins = 16,
+                             Context &ctx = Context::global()) {
+    if (table.size() != call.size() * KMU_PILE_COLS) throw std::invalid_argument("pile_ins_plan: the table and the calls are not of one batch");
+    InsPlan out;
+    out.ins_len.resize(call.size());
+    kmu_ins_plan_params p{};
+    p.max_ins = max_ins;
+    uint8_t none = 0;
+    ctx.check(kmu_pile_ins_plan(ctx.raw(), table.empty() ? reinterpret_cast<const uint32_t *>(&none) : table.data(), call.empty() ? &none : call.data(),
+                                call.size(), &p, KMU_MEM_HOST, out.ins_len.empty() ? &none : out.ins_len.data(), &out.n_slots));
+    return out;
+}
+
+/// What chain_pile_ins returns: KMU_INS_COLS counts (A C G T) per insertion slot of a batch.  As in ChainPileups, the self-join votes
+/// into ONE table, `q`, and `shared` is set.
+struct ChainInsertions {
+    std::vector<uint32_t> q, db;
+    bool shared = false;
+    const std::vector<uint32_t> &of_db() const { return shared ? q : db; }
+};
+
+/// kmu_chain_pile_ins on host arrays: the letters of every chain's gap runs, voted into the slots of both reads.  chains, cigars, q,
+/// db, sides as chain_pileup takes them; plan_q / plan_db: pile_ins_plan of each batch (plan_db == nullptr in the self-join).  into:
+/// tables of an earlier call with the same plans to add to (moved from).
+inline ChainInsertions chain_pile_ins(const std::vector<kmu_chain> &chains, const ChainCigars &cigars, const detail::Batch &q, const InsPlan &plan_q,
+                                      const detail::Batch *db = nullptr, const InsPlan *plan_db = nullptr, uint32_t sides = KMU_PILE_Q | KMU_PILE_DB,
+                                      ChainInsertions into = {}, Context &ctx = Context::global()) {
+    const detail::Batch bq = detail::unpacked(q);
+    detail::Batch bdb_own;
+    if (db) bdb_own = detail::unpacked(*db);
+    const detail::Batch &bdb = db ? bdb_own : bq;
+    if (bq.on_device() || bdb.on_device()) throw std::invalid_argument("chain_pile_ins returns host arrays: it needs the sequences in host memory");
+    if (cigars.aln.size() != chains.size() || cigars.op_offsets.size() != chains.size() + 1)
+        throw std::invalid_argument("chain_pile_ins: the records and run offsets are not those of the chains");
+    if (bool(db) != bool(plan_db)) throw std::invalid_argument("chain_pile_ins: a db batch and its plan come together");
+    const InsPlan &pdb = db ? *plan_db : plan_q;
+    if (plan_q.ins_len.size() != bq.offsets.back() || pdb.ins_len.size() != bdb.offsets.back())
+        throw std::invalid_argument("chain_pile_ins: a plan is not one of its batch");
+    ChainInsertions out = std::move(into);
+    out.shared = !db && (sides & KMU_PILE_Q) && (sides & KMU_PILE_DB);
+    const bool db_in_q = !db && !(sides & KMU_PILE_Q); // the self-join's one table also when only the B side votes
+    if ((sides & KMU_PILE_Q) || db_in_q) out.q.resize(size_t(plan_q.n_slots) * KMU_INS_COLS, 0u);
+    if ((sides & KMU_PILE_DB) && db) out.db.resize(size_t(pdb.n_slots) * KMU_INS_COLS, 0u);
+    if (chains.empty()) return out;
+    kmu_pileup_params p{};
+    p.flags = sides;
+    uint32_t none_q = 0, none_db = 0; // an empty table has no address worth passing
+    uint32_t *table_q = out.q.empty() ? &none_q : out.q.data();
+    uint32_t *table_db = !db ? table_q : out.db.empty() ? &none_db : out.db.data();
+    uint8_t none = 0;
+    ctx.check(kmu_chain_pile_ins(ctx.raw(), chains.data(), chains.size(), cigars.aln.data(), cigars.op_offsets.data(), cigars.ops.data(),
+                                 cigars.ops.size(), bq.bytes.data(), bq.offsets.data(), bq.n(), bdb.bytes.data(), bdb.offsets.data(), bdb.n(), &p,
+                                 KMU_MEM_HOST, plan_q.ins_len.empty() ? &none : plan_q.ins_len.data(), plan_q.n_slots,
+                                 (sides & KMU_PILE_Q) ? table_q : nullptr, pdb.ins_len.empty() ? &none : pdb.ins_len.data(), pdb.n_slots,
+                                 (sides & KMU_PILE_DB) ? table_db : nullptr));
+    return out;
+}
+/// The same under the name of the Python route (minimizer.insertions_chains)
+inline ChainInsertions insertions_chains(const std::vector<kmu_chain> &chains, const ChainCigars &cigars, const detail::Batch &q, const InsPlan &plan_q,
+                                         const detail::Batch *db = nullptr, const InsPlan *plan_db = nullptr,
+                                         uint32_t sides = KMU_PILE_Q | KMU_PILE_DB, ChainInsertions into = {}, Context &ctx = Context::global()) {
+    return chain_pile_ins(chains, cigars, q, plan_q, db, plan_db, sides, std::move(into), ctx);
+}
+
+/// What pile_consensus returns: the corrected reads as a new ASCII batch -- read r is bases[offsets[r] .. offsets[r + 1]).
+struct ConsensusReads {
+    std::vector<uint8_t> bases;
+    std::vector<uint64_t> offsets;
+    std::string read(size_t r) const { return std::string(bases.begin() + offsets[r], bases.begin() + offsets[r + 1]); }
+};
+
+/// kmu_pile_consensus on host arrays: table, call, plan and ins (a table of chain_pile_ins) belong to `batch`.  A row gives at most
+/// one byte and its slots, so the output is sized by n_bases + n_slots and the library is called once.
+inline ConsensusReads pile_consensus(const std::vector<uint32_t> &table, const std::vector<uint8_t> &call, const InsPlan &plan,
+                                     const std::vector<uint32_t> &ins, const detail::Batch &batch, Context &ctx = Context::global()) {
+    const detail::Batch b = detail::unpacked(batch);
+    if (b.on_device()) throw std::invalid_argument("pile_consensus returns host arrays: it needs the sequences in host memory");
+    const size_t n_bases = b.offsets.back();
+    if (table.size() != n_bases * KMU_PILE_COLS || call.size() != n_bases || plan.ins_len.size() != n_bases || ins.size() != plan.n_slots * KMU_INS_COLS)
+        throw std::invalid_argument("pile_consensus: the table, the calls, the plan or the slots are not of this batch");
+    ConsensusReads out;
+    out.offsets.assign(size_t(b.n()) + 1, 0);
+    out.bases.resize(n_bases + plan.n_slots + 1);
+    kmu_consensus_params p{};
+    uint8_t none = 0;
+    uint64_t total = 0;
+    ctx.check(kmu_pile_consensus(ctx.raw(), table.empty() ? reinterpret_cast<const uint32_t *>(&none) : table.data(), call.empty() ? &none : call.data(),
+                                 plan.ins_len.empty() ? &none : plan.ins_len.data(), plan.n_slots, ins.empty() ? nullptr : ins.data(),
+                                 b.bytes.empty() ? &none : b.bytes.data(), b.offsets.data(), b.n(), &p, KMU_MEM_HOST, out.offsets.data(),
+                                 out.bases.data(), out.bases.size(), &total));
+    out.bases.resize(total);
+    return out;
+}
+/// The same under the name of the Python route (minimizer.consensus_reads)
+inline ConsensusReads consensus_reads(const std::vector<uint32_t> &table, const std::vector<uint8_t> &call, const InsPlan &plan,
+                                      const std::vector<uint32_t> &ins, const detail::Batch &batch, Context &ctx = Context::global()) {
+    return pile_consensus(table, call, plan, ins, batch, ctx);
+}
+
+/// What correct_reads returns: the corrected reads and the summaries of pile_call.
+struct CorrectedReads {
+    ConsensusReads cons;
+    std::vector<kmu_read_pile> reads;
+};
+
+/// The corrected reads of the chains of a batch's self-join: chain_cigar, chain_pileup, pile_call with `min_depth`, pile_ins_plan with
+/// `max_ins`, chain_pile_ins, pile_consensus.
+inline CorrectedReads correct_chains(const std::vector<kmu_chain> &chains, const detail::Batch &batch, uint32_t band = 64, uint32_t min_depth = 3,
+                                     uint32_t max_ins = 16, Context &ctx = Context::global()) {
+    const ChainCigars cigars = chain_cigar(chains, batch, nullptr, band, 0, ctx);
+    const ChainPileups pile = chain_pileup(chains, cigars, batch, nullptr, KMU_PILE_Q | KMU_PILE_DB, {}, ctx);
+    PileCalls calls = pile_call(pile.q, batch, min_depth, ctx);
+    const InsPlan plan = pile_ins_plan(pile.q, calls.call, max_ins, ctx);
+    const ChainInsertions ins = chain_pile_ins(chains, cigars, batch, plan, nullptr, nullptr, KMU_PILE_Q | KMU_PILE_DB, {}, ctx);
+    return {pile_consensus(pile.q, calls.call, plan, ins.q, batch, ctx), std::move(calls.reads)};
+}
+
+/// From the reads of a batch to their corrected versions (minimizer.correct_reads): read_chains (band_chain is its band), then
+/// correct_chains.
+template <class Kmer>
+CorrectedReads correct_reads(const detail::Batch &batch, size_t k, uint32_t w, FHash fhash = FHash::canon_invhash, uint32_t max_occ = 0,
+                             uint32_t max_gap = 5000, uint32_t band_chain = 500, uint32_t min_seeds = 3, uint32_t min_score = 0, uint32_t band = 64,
+                             uint32_t min_depth = 3, uint32_t max_ins = 16, Context &ctx = Context::global()) {
+    return correct_chains(read_chains<Kmer>(batch, k, w, fhash, max_occ, max_gap, band_chain, min_seeds, min_score, ctx), batch, band, min_depth,
+                          max_ins, ctx);
 }
 
 // =====================================================================================================================

@@ -1103,7 +1103,8 @@ int kmu_chain_pileup(kmu_ctx *ctx, const kmu_chain *chains, uint64_t n_chains, c
  * reads_out[r] (n_reads records; may be NULL, not both): the summary of read r; its counts are of rows with depth >= min_depth.
  * min_depth >= 1; flags must be 0.  n_reads == 0: KMU_OK.  KMU_E_BAD_ARG: null ctx / pile / bases / offsets / p, both outputs null,
  *   min_depth == 0, non-zero flags, bad mem.  KMU_MEM_DEVICE: every array except p is device memory; KMU_MEM_HOST: through the
- *   workspace.  The pileup counts insertions but does not collect the inserted letters.
+ *   workspace.  The pileup counts insertions; kmu_pile_ins_plan and kmu_chain_pile_ins below collect the inserted letters, and
+ *   kmu_pile_consensus writes the corrected reads.
  * How: one lane per base for the calls; one wave per read, 64 rows at a time, for the summaries. */
 #define KMU_CALL_NONE 7u           /* bits 0..2: the depth is below min_depth */
 #define KMU_CALL_INS 8u            /* most partners have extra bases behind this one */
@@ -1123,6 +1124,87 @@ typedef struct {         /* 32 bytes */
 } kmu_read_pile;
 int kmu_pile_call(kmu_ctx *ctx, const uint32_t *pile, const uint8_t *bases, const uint64_t *offsets, uint32_t n_reads,
                   const kmu_pile_call_params *p, int mem, uint8_t *call_out, kmu_read_pile *reads_out);
+
+/* ---- read correction: the inserted letters, and the consensus sequence of every read -------------------------------------
+ * Three calls close the pipeline reads -> chains -> runs -> pileup -> calls on the device.  kmu_pile_ins_plan gives every base a
+ * number of insertion SLOTS, kmu_chain_pile_ins votes the letters of every chain's gap runs into them, and kmu_pile_consensus writes
+ * the corrected reads as a new KMU_INPUT_ASCII batch.
+ *
+ * kmu_pile_ins_plan.  pile and call: the table of one batch as kmu_chain_pileup left it and the call bytes kmu_pile_call made from
+ *   it; n_bases rows.  ins_len_out[g] (n_bases bytes) is the slot count of row g: 0 unless call[g] has KMU_CALL_INS; otherwise
+ *   min(max_ins, floor((2 INS_BASES - 1) / depth)) with depth = A + C + G + T + DEL, computed in 64 bits (0 where depth or INS_BASES
+ *   is 0, which no call byte made from the table allows).  That is the largest number k of inserted positions at which more than
+ *   half of the depth can still have a letter: the partners with at least k inserted bases number at most INS_BASES / k.  It is at
+ *   least 1 on every row with KMU_CALL_INS, since 2 INS_BASES >= 2 INS > depth.  *n_slots_out (host memory in both modes) is the sum.
+ *   Slot index: slot s of row g has the global index S(g) + s, S being the exclusive prefix sum of ins_len over the batch's rows;
+ *   this is public contract.  The two calls below recompute what they need of S from ins_len alone: a caller holds only the bytes.
+ *   n_bases == 0: KMU_OK, *n_slots_out = 0.  KMU_E_BAD_ARG: null ctx / pile / call / p / ins_len_out / n_slots_out, max_ins 0 or above
+ *   KMU_INS_MAX, non-zero flags, bad mem.
+ *
+ * kmu_chain_pile_ins.  Inputs, flags (KMU_PILE_Q, KMU_PILE_DB), coordinates and the chains that vote are exactly those of
+ *   kmu_chain_pileup.  ins_len_q / ins_len_db and n_slots_q / n_slots_db: the plan of each voted batch.  ins_q / ins_db: uint32
+ *   [n_slots][KMU_INS_COLS], one count per letter A C G T of every slot; the call ADDS to them.  ins_q and ins_db may be the same
+ *   array when the two batches are the same arrays (then ins_len and n_slots must be the same too), as in the pileup; what belongs to
+ *   a side not asked for may be NULL / 0.
+ *   A side: a D run of length L that begins at (i0, j0) with i0 >= 1 has the row g = offsets_q[read_a] + a_start + i0 - 1; for
+ *   k < min(L, ins_len[g]) it adds 1 in slot S(g) + k to the letter of B' at j0 + k (on strand 1 the complement of B's forward letter).
+ *   B side: an I run of length L that begins at (i0, j0) has the row that takes its INS vote in kmu_chain_pileup -- B' index j0 - 1 on
+ *   strand 0, j0 on strand 1, none at the segment's edge -- and its slots run in read b's forward direction: on strand 0 slot k takes
+ *   A's letter at i0 + k, on strand 1 the complement of A's letter at i0 + L - 1 - k.
+ *   A cut run and two adjacent runs of one op vote as the separate runs they are, each from slot 0.  Letters beyond a row's slots are
+ *   dropped.  Integer sums only: the order of the chains, the launch shape and timing change nothing.
+ *   KMU_MEM_DEVICE: every array except p is device memory; the call synchronises the stream four times (the checks of the runs, the
+ *   sizes of the two batches, the check of ins_len, the end).  KMU_MEM_HOST: through the workspace; the votes come back added to the caller's tables.
+ *   n_chains == 0: KMU_OK, nothing is looked at.  KMU_E_BAD_ARG: what kmu_chain_pileup refuses so (the tables being ins_q / ins_db), a
+ *   null ins_len of a side asked for, one table for both sides with two ins_len or two n_slots.
+ *   Found on the device BEFORE any vote, the tables untouched: KMU_E_UNSUPPORTED for everything kmu_chain_pileup refuses so, and where
+ *   the sum of a voted side's ins_len is not its n_slots.  No inconsistent run or ins_len is ever used as an index.
+ *   KMU_E_NON_ACGT: a voted letter outside ACGTacgt; the tables are then unspecified.
+ *   How: the check and tile step of kmu_chain_pileup, the same code.  One wave per tile of 64 runs, one run per lane; only a lane that
+ *   owns a gap run of a voted side loads the byte ins_len[g], and only where that is not 0 it looks up S(g) and does at most ins_len
+ *   letter loads and atomic adds.  S(g): a workspace array holds the exclusive scan of the sums of ins_len over blocks of 64 rows (8
+ *   bytes per 64 rows), and the lane adds the at most 63 bytes before g inside its block.
+ *
+ * kmu_pile_consensus.  pile, call, ins_len, n_slots, ins: of one batch (bases, offsets, n_reads), as the calls above left them; ins
+ *   may be NULL when n_slots is 0.  The output of row g, in order: its own position -- the read's own byte, verbatim, whatever it is,
+ *   where bits 0..2 of call[g] are KMU_CALL_NONE (or 5 or 6, which kmu_pile_call never writes); the letter in upper case where they
+ *   are a code A .. T; nothing where they are KMU_PILE_DEL -- and then, where ins_len[g] > 0, the emitted slots k = 0, 1, ...: with n_k
+ *   the sum of the slot's four counts, slot k is emitted iff 2 n_k > depth(g), and emission stops at the first slot that is not, so any
+ *   table gives a defined result; the letter is the one with the largest count, the smallest code among equals.  The output of read r
+ *   is that of its rows in order: cons_out[cons_offsets_out[r] .. cons_offsets_out[r + 1]); cons_offsets_out has n_reads + 1 entries
+ *   and lives where the other arrays live.  A read may come out empty.
+ *   Counting and capacity: *n_cons_out (host memory in both modes) is always the total.  cons_out == NULL: the count-only call -- the
+ *   offsets are written all the same.  cap < total: KMU_E_BAD_ARG with *n_cons_out set and the offsets written; cons_out is not written.
+ *   A row gives at most one byte and its slots: total <= n_bases + n_slots, so a caller can size cons_out without a count call.
+ *   n_reads == 0: KMU_OK, one offset (0).  KMU_E_BAD_ARG: null ctx / pile / call / ins_len / bases / offsets / p / cons_offsets_out /
+ *   n_cons_out, ins null with n_slots > 0, non-zero flags, bad mem.  KMU_E_UNSUPPORTED, before any output: the sum of ins_len is not
+ *   n_slots.  KMU_MEM_DEVICE: every array except p and n_cons_out is device memory; KMU_MEM_HOST: through the workspace.
+ *   How: tiles are 64 consecutive rows of the batch, not reads, so a chromosome-long read is many waves' work.  One wave per tile, one
+ *   row per lane: three byte loads per row, the pile row and the slots only where ins_len > 0.  A count pass leaves tile sums, a scan
+ *   makes tile offsets, a write pass repeats the row rule behind a wave prefix sum; one lane per read derives its offset from the tile
+ *   that holds its first row.  DESIGN.md 3.19 has the kernels. */
+#define KMU_INS_COLS 4             /* uint32 per slot: votes for A, C, G, T */
+#define KMU_INS_MAX 255u           /* the most slots a base can get */
+typedef struct kmu_ins_plan_params {
+    uint32_t max_ins;    /* 1 .. KMU_INS_MAX */
+    uint32_t flags;      /* must be 0 */
+} kmu_ins_plan_params;
+typedef struct kmu_consensus_params {
+    uint32_t flags;      /* must be 0 */
+} kmu_consensus_params;
+int kmu_pile_ins_plan(kmu_ctx *ctx, const uint32_t *pile, const uint8_t *call, uint64_t n_bases,
+                      const kmu_ins_plan_params *p, int mem, uint8_t *ins_len_out, uint64_t *n_slots_out);
+int kmu_chain_pile_ins(kmu_ctx *ctx, const kmu_chain *chains, uint64_t n_chains, const kmu_chain_aln *aln,
+                       const uint64_t *op_offsets, const uint32_t *ops, uint64_t n_ops,
+                       const uint8_t *bases_q, const uint64_t *offsets_q, uint32_t n_reads_q,
+                       const uint8_t *bases_db, const uint64_t *offsets_db, uint32_t n_reads_db,
+                       const kmu_pileup_params *p, int mem,
+                       const uint8_t *ins_len_q, uint64_t n_slots_q, uint32_t *ins_q,
+                       const uint8_t *ins_len_db, uint64_t n_slots_db, uint32_t *ins_db);
+int kmu_pile_consensus(kmu_ctx *ctx, const uint32_t *pile, const uint8_t *call, const uint8_t *ins_len, uint64_t n_slots,
+                       const uint32_t *ins, const uint8_t *bases, const uint64_t *offsets, uint32_t n_reads,
+                       const kmu_consensus_params *p, int mem,
+                       uint64_t *cons_offsets_out, uint8_t *cons_out, uint64_t cap, uint64_t *n_cons_out);
 
 #ifdef __cplusplus
 }

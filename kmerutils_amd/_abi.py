@@ -43,6 +43,8 @@ PILE_COLS = 8            # kmu_chain_pileup: uint32 per row of a table, indexed 
 PILE_A, PILE_C, PILE_G, PILE_T, PILE_DEL, PILE_INS, PILE_INS_BASES, PILE_ENDS = range(8)
 PILE_Q, PILE_DB = 1, 2   # ... and its flags: vote onto the A side, onto the B side
 CALL_NONE, CALL_INS, CALL_DIFF = 7, 8, 16  # kmu_pile_call: bits 0..2 of an uncalled base, and the two bits above the code
+INS_COLS = 4             # kmu_chain_pile_ins: uint32 per insertion slot, one count per letter A C G T
+INS_MAX = 255            # kmu_pile_ins_plan: the most slots a base can get
 
 
 def kmer_val_bytes(kmer_type):
@@ -167,6 +169,16 @@ class PileupParams(C.Structure):
 class PileCallParams(C.Structure):
     """kmu_pile_call_params: the depth from which kmu_pile_call calls a base"""
     _fields_ = [("min_depth", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class InsPlanParams(C.Structure):
+    """kmu_ins_plan_params: the most insertion slots kmu_pile_ins_plan gives a base"""
+    _fields_ = [("max_ins", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class ConsensusParams(C.Structure):
+    """kmu_consensus_params: kmu_pile_consensus has no options yet"""
+    _fields_ = [("flags", C.c_uint32)]
 
 
 class ReadPile(C.Structure):

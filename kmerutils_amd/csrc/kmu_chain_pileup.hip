@@ -12,9 +12,12 @@
 //                 of a chain from lane 0 of its first tile.  Plain uint32 atomicAdd: integer sums commute.
 //  k_pile_call    one lane per base: the call byte of its row.
 //  k_pile_reads   one wave per read, 64 rows at a time: the summary record.
+// The argument checks and the check-and-tile step (k_pile_count, scan, k_pile_starts) are pile_check_inputs and pile_plan of
+// kmu_pile_plan.h: kmu_chain_pile_ins (kmu_pile_ins.hip) takes the same inputs and goes through the same two functions.
 #include "kmu_ctx.hpp"
 #include "kmu_device.h"
 #include "kmu_pile_core.h"
+#include "kmu_pile_plan.h"
 
 namespace kmu {
 
@@ -25,30 +28,6 @@ static_assert(PILE_COLS == KMU_PILE_COLS && PILE_DEL == KMU_PILE_DEL && PILE_INS
               "the columns are the header's");
 static_assert(PILE_CALL_NONE == KMU_CALL_NONE && PILE_CALL_INS == KMU_CALL_INS && PILE_CALL_DIFF == KMU_CALL_DIFF, "the call bits are the header's");
 static_assert(sizeof(kmu_read_pile) == 32, "kmu_read_pile is 32 bytes");
-
-struct PileTileRec { // where a tile begins
-    uint64_t chain;
-    uint32_t i, j;
-};
-
-struct PileArgs {
-    const kmu_chain *chains;
-    const kmu_chain_aln *aln;
-    uint64_t n_chains;
-    const uint64_t *op_off; // [n_chains + 1]
-    const uint32_t *ops;
-    uint64_t n_ops;
-    const uint8_t *bases_q, *bases_db;
-    const uint64_t *off_q, *off_db;
-    uint32_t n_reads_q, n_reads_db;
-    uint32_t flags;
-    uint32_t *pile_q, *pile_db;
-    uint32_t *n_tiles;      // [n_chains]
-    const uint64_t *tile_off; // [n_chains + 1]
-    PileTileRec *tiles;
-    uint64_t tile_cap;
-    uint32_t *info;         // [0]: refused; [1]: a voted letter outside ACGTacgt
-};
 
 // the checks of kmu_chain_cigar on a record; beg_*: where the two reads begin
 __device__ __forceinline__ bool pile_record_ok(const PileArgs &p, const kmu_chain &rec, uint64_t &beg_a, uint64_t &beg_b) {
@@ -255,68 +234,56 @@ __global__ void __launch_bounds__(256) k_pile_reads(PileCallArgs p) {
 
 using namespace kmu;
 
-extern "C" int kmu_chain_pileup(kmu_ctx *ctx, const kmu_chain *chains, uint64_t n_chains, const kmu_chain_aln *aln, const uint64_t *op_offsets,
-                                const uint32_t *ops, uint64_t n_ops, const uint8_t *bases_q, const uint64_t *offsets_q, uint32_t n_reads_q,
-                                const uint8_t *bases_db, const uint64_t *offsets_db, uint32_t n_reads_db, const kmu_pileup_params *p, int mem,
-                                uint32_t *pile_q, uint32_t *pile_db) {
-    if (!ctx || !chains || !aln || !op_offsets || !bases_q || !offsets_q || !bases_db || !offsets_db || !p) return fail(ctx, KMU_E_BAD_ARG, "null argument");
-    if (!ops && n_ops) return fail(ctx, KMU_E_BAD_ARG, "ops is null with n_ops = %llu", (unsigned long long) n_ops);
-    if (!p->flags || (p->flags & ~(KMU_PILE_Q | KMU_PILE_DB))) return fail(ctx, KMU_E_BAD_ARG, "flags 0x%x: KMU_PILE_Q, KMU_PILE_DB or both", p->flags);
-    const bool side_q = p->flags & KMU_PILE_Q, side_db = p->flags & KMU_PILE_DB;
-    if ((side_q && !pile_q) || (side_db && !pile_db)) return fail(ctx, KMU_E_BAD_ARG, "null table for a side that is asked for");
-    if (mem != KMU_MEM_HOST && mem != KMU_MEM_DEVICE) return fail(ctx, KMU_E_BAD_ARG, "bad mem %d", mem);
-    const bool self = bases_db == bases_q && offsets_db == offsets_q && n_reads_db == n_reads_q;
-    const bool shared = side_q && side_db && pile_q == pile_db;
-    if (shared && !self) return fail(ctx, KMU_E_BAD_ARG, "one table for both sides needs the two batches to be the same arrays");
-    if (n_chains == 0) return KMU_OK;
-    if (n_reads_q == 0 || n_reads_db == 0) return fail(ctx, KMU_E_BAD_ARG, "chains but no reads");
-    KMU_HIP(ctx, hipSetDevice(ctx->device));
+namespace kmu {
 
+int pile_check_inputs(kmu_ctx *ctx, const PileInputs &in, const void *table_q, const void *table_db) {
+    if (!ctx || !in.chains || !in.aln || !in.op_offsets || !in.bases_q || !in.offsets_q || !in.bases_db || !in.offsets_db || !in.p)
+        return fail(ctx, KMU_E_BAD_ARG, "null argument");
+    if (!in.ops && in.n_ops) return fail(ctx, KMU_E_BAD_ARG, "ops is null with n_ops = %llu", (unsigned long long) in.n_ops);
+    const uint32_t flags = in.p->flags;
+    if (!flags || (flags & ~(KMU_PILE_Q | KMU_PILE_DB))) return fail(ctx, KMU_E_BAD_ARG, "flags 0x%x: KMU_PILE_Q, KMU_PILE_DB or both", flags);
+    const bool side_q = flags & KMU_PILE_Q, side_db = flags & KMU_PILE_DB;
+    if ((side_q && !table_q) || (side_db && !table_db)) return fail(ctx, KMU_E_BAD_ARG, "null table for a side that is asked for");
+    if (in.mem != KMU_MEM_HOST && in.mem != KMU_MEM_DEVICE) return fail(ctx, KMU_E_BAD_ARG, "bad mem %d", in.mem);
+    if (side_q && side_db && table_q == table_db && !in.self())
+        return fail(ctx, KMU_E_BAD_ARG, "one table for both sides needs the two batches to be the same arrays");
+    if (in.n_chains && (in.n_reads_q == 0 || in.n_reads_db == 0)) return fail(ctx, KMU_E_BAD_ARG, "chains but no reads");
+    return KMU_OK;
+}
+
+int pile_plan(kmu_ctx *ctx, const PileInputs &in, PileArgs *out, uint64_t *n_tiles_out) {
+    const int mem = in.mem;
+    const uint64_t n_chains = in.n_chains;
     PileArgs a{};
     const void *d;
-    KMU_TRY(stage_to_device(ctx, "pile.chains", chains, (size_t) n_chains * sizeof(kmu_chain), mem, &d));
+    KMU_TRY(stage_to_device(ctx, "pile.chains", in.chains, (size_t) n_chains * sizeof(kmu_chain), mem, &d));
     a.chains = (const kmu_chain *) d;
     a.n_chains = n_chains;
-    KMU_TRY(stage_to_device(ctx, "pile.aln", aln, (size_t) n_chains * sizeof(kmu_chain_aln), mem, &d));
+    KMU_TRY(stage_to_device(ctx, "pile.aln", in.aln, (size_t) n_chains * sizeof(kmu_chain_aln), mem, &d));
     a.aln = (const kmu_chain_aln *) d;
-    KMU_TRY(stage_to_device(ctx, "pile.opoff", op_offsets, (size_t) (n_chains + 1) * 8, mem, &d));
+    KMU_TRY(stage_to_device(ctx, "pile.opoff", in.op_offsets, (size_t) (n_chains + 1) * 8, mem, &d));
     a.op_off = (const uint64_t *) d;
-    KMU_TRY(stage_to_device(ctx, "pile.ops", ops, (size_t) n_ops * 4, mem, &d));
+    KMU_TRY(stage_to_device(ctx, "pile.ops", in.ops, (size_t) in.n_ops * 4, mem, &d));
     a.ops = (const uint32_t *) d;
-    a.n_ops = n_ops;
-    KMU_TRY(stage_to_device(ctx, "pile.basesq", bases_q, mem == KMU_MEM_HOST ? (size_t) offsets_q[n_reads_q] : 0, mem, &d));
+    a.n_ops = in.n_ops;
+    KMU_TRY(stage_to_device(ctx, "pile.basesq", in.bases_q, mem == KMU_MEM_HOST ? (size_t) in.offsets_q[in.n_reads_q] : 0, mem, &d));
     a.bases_q = (const uint8_t *) d;
-    KMU_TRY(stage_to_device(ctx, "pile.offq", offsets_q, ((size_t) n_reads_q + 1) * 8, mem, &d));
+    KMU_TRY(stage_to_device(ctx, "pile.offq", in.offsets_q, ((size_t) in.n_reads_q + 1) * 8, mem, &d));
     a.off_q = (const uint64_t *) d;
-    if (self) { // a self-join is staged once
+    if (in.self()) { // a self-join is staged once
         a.bases_db = a.bases_q;
         a.off_db = a.off_q;
     } else {
-        KMU_TRY(stage_to_device(ctx, "pile.basesdb", bases_db, mem == KMU_MEM_HOST ? (size_t) offsets_db[n_reads_db] : 0, mem, &d));
+        KMU_TRY(stage_to_device(ctx, "pile.basesdb", in.bases_db, mem == KMU_MEM_HOST ? (size_t) in.offsets_db[in.n_reads_db] : 0, mem, &d));
         a.bases_db = (const uint8_t *) d;
-        KMU_TRY(stage_to_device(ctx, "pile.offdb", offsets_db, ((size_t) n_reads_db + 1) * 8, mem, &d));
+        KMU_TRY(stage_to_device(ctx, "pile.offdb", in.offsets_db, ((size_t) in.n_reads_db + 1) * 8, mem, &d));
         a.off_db = (const uint64_t *) d;
     }
-    a.n_reads_q = n_reads_q;
-    a.n_reads_db = n_reads_db;
-    a.flags = p->flags;
-    a.pile_q = side_q ? pile_q : nullptr;
-    a.pile_db = side_db ? pile_db : nullptr;
-    const size_t words_q = mem == KMU_MEM_HOST && side_q ? (size_t) offsets_q[n_reads_q] * PILE_COLS : 0;
-    const size_t words_db = mem == KMU_MEM_HOST && side_db && !shared ? (size_t) offsets_db[n_reads_db] * PILE_COLS : 0;
-    if (mem == KMU_MEM_HOST) { // the votes of this call alone, added to the caller's tables at the end
-        if (side_q) {
-            KMU_TRY(dev_array(ctx, "pile.tableq", words_q ? words_q : 1, &a.pile_q));
-            KMU_HIP(ctx, hipMemsetAsync(a.pile_q, 0, words_q * 4, ctx->stream));
-        }
-        if (shared) a.pile_db = a.pile_q;
-        else if (side_db) {
-            KMU_TRY(dev_array(ctx, "pile.tabledb", words_db ? words_db : 1, &a.pile_db));
-            KMU_HIP(ctx, hipMemsetAsync(a.pile_db, 0, words_db * 4, ctx->stream));
-        }
-    }
+    a.n_reads_q = in.n_reads_q;
+    a.n_reads_db = in.n_reads_db;
+    a.flags = in.p->flags;
     uint64_t *d_tile_off;
-    a.tile_cap = n_ops / PILE_TILE + n_chains; // every chain's tiles, when the offsets are what they must be
+    a.tile_cap = in.n_ops / PILE_TILE + n_chains; // every chain's tiles, when the offsets are what they must be
     KMU_TRY(dev_array(ctx, "pile.info", 2, &a.info));
     KMU_TRY(dev_array(ctx, "pile.ntiles", n_chains, &a.n_tiles));
     KMU_TRY(dev_array(ctx, "pile.tileoff", n_chains + 1, &d_tile_off));
@@ -337,6 +304,43 @@ extern "C" int kmu_chain_pileup(kmu_ctx *ctx, const kmu_chain *chains, uint64_t 
         return fail(ctx, KMU_E_UNSUPPORTED, "a chain record kmu_chain_cigar would refuse, run offsets that decrease or end above n_ops, runs on a chain "
                                             "without PATH, a run with an unknown op or of length 0, or runs that do not sum to the chain's segments");
     }
+    *out = a;
+    *n_tiles_out = n_tiles;
+    return KMU_OK;
+}
+
+} // namespace kmu
+
+extern "C" int kmu_chain_pileup(kmu_ctx *ctx, const kmu_chain *chains, uint64_t n_chains, const kmu_chain_aln *aln, const uint64_t *op_offsets,
+                                const uint32_t *ops, uint64_t n_ops, const uint8_t *bases_q, const uint64_t *offsets_q, uint32_t n_reads_q,
+                                const uint8_t *bases_db, const uint64_t *offsets_db, uint32_t n_reads_db, const kmu_pileup_params *p, int mem,
+                                uint32_t *pile_q, uint32_t *pile_db) {
+    const PileInputs in{chains, n_chains, aln, op_offsets, ops, n_ops, bases_q, offsets_q, n_reads_q, bases_db, offsets_db, n_reads_db, p, mem};
+    KMU_TRY(pile_check_inputs(ctx, in, pile_q, pile_db));
+    const bool side_q = p->flags & KMU_PILE_Q, side_db = p->flags & KMU_PILE_DB;
+    const bool shared = side_q && side_db && pile_q == pile_db;
+    if (n_chains == 0) return KMU_OK;
+    KMU_HIP(ctx, hipSetDevice(ctx->device));
+
+    PileArgs a{};
+    uint64_t n_tiles = 0;
+    KMU_TRY(pile_plan(ctx, in, &a, &n_tiles));
+    a.pile_q = side_q ? pile_q : nullptr;
+    a.pile_db = side_db ? pile_db : nullptr;
+    const size_t words_q = mem == KMU_MEM_HOST && side_q ? (size_t) offsets_q[n_reads_q] * PILE_COLS : 0;
+    const size_t words_db = mem == KMU_MEM_HOST && side_db && !shared ? (size_t) offsets_db[n_reads_db] * PILE_COLS : 0;
+    if (mem == KMU_MEM_HOST) { // the votes of this call alone, added to the caller's tables at the end
+        if (side_q) {
+            KMU_TRY(dev_array(ctx, "pile.tableq", words_q ? words_q : 1, &a.pile_q));
+            KMU_HIP(ctx, hipMemsetAsync(a.pile_q, 0, words_q * 4, ctx->stream));
+        }
+        if (shared) a.pile_db = a.pile_q;
+        else if (side_db) {
+            KMU_TRY(dev_array(ctx, "pile.tabledb", words_db ? words_db : 1, &a.pile_db));
+            KMU_HIP(ctx, hipMemsetAsync(a.pile_db, 0, words_db * 4, ctx->stream));
+        }
+    }
+    uint32_t h_info[2] = {0, 0};
     if (n_tiles) KMU_TRY(launch(ctx, "k_pile_vote", k_pile_vote, dim3(grid_for(ctx, n_tiles, 1, 32)), dim3(64), 0, a, n_tiles));
     KMU_HIP(ctx, hipMemcpyAsync(h_info, a.info, 8, hipMemcpyDeviceToHost, ctx->stream));
     std::vector<uint32_t> got;

@@ -1,0 +1,163 @@
+// kmu_pile_consensus.hip -- the corrected reads: the consensus sequence of every read from its calls and its insertion slots
+// (kmu_pile_consensus).  The contract is in include/kmu.h, the row rule in kmu_cons_core.h.
+//
+// Tiles are 64 consecutive rows of the batch, whatever read they belong to; they are the blocks of the slot index, so the first slot
+// of a lane's row is its tile's block offset (ins_block_offsets) plus the wave's exclusive scan of ins_len.
+//
+//  k_cons_count    one wave per tile, one row per lane: the bytes the row gives -- three byte loads (call, ins_len, and in the write
+//                  pass the read's own base); the 32-byte pile row and the slots only where ins_len > 0.  Leaves the tile's sum.
+//                  device_scan_u32 turns the sums into tile offsets, the last being the total.
+//  k_cons_write    the same walk with the wave's prefix sum of the row lengths: every lane stores its row's bytes.
+//  k_cons_offsets  one lane per read (and one for the end): cons_offsets[r] is the offset of the tile that holds offsets[r] plus the
+//                  lengths of the at most 63 rows before it in that tile.
+#include "kmu_ctx.hpp"
+#include "kmu_device.h"
+#include "kmu_cons_core.h"
+#include "kmu_pile_plan.h"
+
+namespace kmu {
+
+struct ConsArgs {
+    const uint32_t *pile;
+    const uint8_t *call, *ins_len;
+    const uint32_t *ins;       // [n_slots][4]
+    uint64_t n_slots;
+    const uint8_t *bases;
+    const uint64_t *off;       // [n_reads + 1]
+    uint32_t n_reads;
+    uint64_t n_rows, n_tiles;
+    const uint64_t *slot_off;  // [n_tiles + 1]: the first slot of every tile
+    uint32_t *tile_len;        // [n_tiles]: the bytes of every tile
+    const uint64_t *tile_off;  // [n_tiles + 1]
+    uint64_t *cons_off;        // [n_reads + 1]
+    uint8_t *cons;
+};
+
+// the bytes of row g, whose slots begin at `slot`; out == nullptr counts only.  A row whose slots would end above n_slots has none
+// (the sum of ins_len is n_slots: never taken).
+__device__ __forceinline__ uint32_t cons_row_at(const ConsArgs &p, uint64_t g, uint64_t slot, uint8_t *out) {
+    const uint32_t call = p.call[g];
+    uint32_t il = p.ins_len[g];
+    if (slot + il > p.n_slots) il = 0;
+    uint32_t row[PILE_COLS] = {};
+    if (il)
+        for (uint32_t k = 0; k < PILE_COLS; k++) row[k] = p.pile[g * PILE_COLS + k];
+    return cons_row(call, out ? p.bases[g] : 0u, il, row, p.ins + slot * CONS_LETTERS, out);
+}
+
+template <bool WRITE> __global__ void __launch_bounds__(256) k_cons_tiles(ConsArgs p) {
+    const uint32_t lane = (uint32_t) lane_id();
+    for (uint64_t t = (uint64_t) blockIdx.x * 4u + (threadIdx.x >> 6); t < p.n_tiles; t += (uint64_t) gridDim.x * 4u) {
+        const uint64_t g = t * CONS_BLOCK + lane;
+        const bool live = g < p.n_rows;
+        const uint32_t il = live ? p.ins_len[g] : 0u;
+        const uint64_t slot = p.slot_off[t] + (wave_incl_scan_u32(il) - il);
+        const uint32_t n = live ? cons_row_at(p, g, slot, nullptr) : 0u;
+        if (!WRITE) {
+            const uint32_t sum = wave_sum_u32(n);
+            if (lane == 0) p.tile_len[t] = sum;
+        } else {
+            const uint64_t at = p.tile_off[t] + (wave_incl_scan_u32(n) - n);
+            if (n) cons_row_at(p, g, slot, p.cons + at);
+        }
+    }
+}
+
+__global__ void __launch_bounds__(256) k_cons_offsets(ConsArgs p) {
+    for (uint64_t r = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x; r <= p.n_reads; r += (uint64_t) gridDim.x * blockDim.x) {
+        uint64_t g0 = p.off[r];
+        if (g0 > p.n_rows) g0 = p.n_rows; // (offsets that do not ascend to n_rows are the caller's fault; no row beyond is looked at)
+        const uint64_t t = g0 / CONS_BLOCK;
+        uint64_t at = p.tile_off[t], slot = p.slot_off[t]; // (t == n_tiles where g0 == n_rows is a multiple of 64: the totals)
+        for (uint64_t g = t * CONS_BLOCK; g < g0; g++) {
+            at += cons_row_at(p, g, slot, nullptr);
+            slot += p.ins_len[g];
+        }
+        p.cons_off[r] = at;
+    }
+}
+
+} // namespace kmu
+
+using namespace kmu;
+
+extern "C" int kmu_pile_consensus(kmu_ctx *ctx, const uint32_t *pile, const uint8_t *call, const uint8_t *ins_len, uint64_t n_slots, const uint32_t *ins,
+                                  const uint8_t *bases, const uint64_t *offsets, uint32_t n_reads, const kmu_consensus_params *p, int mem,
+                                  uint64_t *cons_offsets_out, uint8_t *cons_out, uint64_t cap, uint64_t *n_cons_out) {
+    if (!ctx || !pile || !call || !ins_len || !bases || !offsets || !p || !cons_offsets_out || !n_cons_out) return fail(ctx, KMU_E_BAD_ARG, "null argument");
+    if (!ins && n_slots) return fail(ctx, KMU_E_BAD_ARG, "ins is null with n_slots = %llu", (unsigned long long) n_slots);
+    if (p->flags) return fail(ctx, KMU_E_BAD_ARG, "unknown flag bits 0x%x", p->flags);
+    if (mem != KMU_MEM_HOST && mem != KMU_MEM_DEVICE) return fail(ctx, KMU_E_BAD_ARG, "bad mem %d", mem);
+    *n_cons_out = 0;
+    KMU_HIP(ctx, hipSetDevice(ctx->device));
+    uint64_t n_rows = 0;
+    if (mem == KMU_MEM_HOST) n_rows = offsets[n_reads];
+    else {
+        KMU_HIP(ctx, hipMemcpyAsync(&n_rows, offsets + n_reads, 8, hipMemcpyDeviceToHost, ctx->stream));
+        KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    }
+
+    ConsArgs a{};
+    const void *d;
+    KMU_TRY(stage_to_device(ctx, "cons.pile", pile, (size_t) n_rows * PILE_COLS * 4, mem, &d));
+    a.pile = (const uint32_t *) d;
+    KMU_TRY(stage_to_device(ctx, "cons.call", call, (size_t) n_rows, mem, &d));
+    a.call = (const uint8_t *) d;
+    KMU_TRY(stage_to_device(ctx, "cons.len", ins_len, (size_t) n_rows, mem, &d));
+    a.ins_len = (const uint8_t *) d;
+    KMU_TRY(stage_to_device(ctx, "cons.ins", ins, (size_t) n_slots * CONS_LETTERS * 4, mem, &d));
+    a.ins = (const uint32_t *) d;
+    a.n_slots = n_slots;
+    KMU_TRY(stage_to_device(ctx, "cons.bases", bases, (size_t) n_rows, mem, &d));
+    a.bases = (const uint8_t *) d;
+    KMU_TRY(stage_to_device(ctx, "cons.off", offsets, ((size_t) n_reads + 1) * 8, mem, &d));
+    a.off = (const uint64_t *) d;
+    a.n_reads = n_reads;
+    a.n_rows = n_rows;
+    a.n_tiles = cons_n_blocks(n_rows);
+
+    // the slot index, and the refusal of an ins_len that does not belong to n_slots: before any output
+    uint64_t *slot_off, total_slots = 0;
+    KMU_TRY(ins_block_offsets(ctx, "cons.slotoff", a.ins_len, n_rows, &slot_off));
+    a.slot_off = slot_off;
+    KMU_HIP(ctx, hipMemcpyAsync(&total_slots, slot_off + a.n_tiles, 8, hipMemcpyDeviceToHost, ctx->stream));
+    KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (total_slots != n_slots) {
+        if (ctx->profiling) profile_collect(ctx);
+        return fail(ctx, KMU_E_UNSUPPORTED, "ins_len sums to %llu slots, not to n_slots = %llu", (unsigned long long) total_slots, (unsigned long long) n_slots);
+    }
+
+    uint64_t *tile_off, total = 0;
+    KMU_TRY(dev_array(ctx, "cons.tilelen", a.n_tiles ? a.n_tiles : 1, &a.tile_len));
+    KMU_TRY(dev_array(ctx, "cons.tileoff", a.n_tiles + 1, &tile_off));
+    a.tile_off = tile_off;
+    const dim3 grid(grid_for(ctx, a.n_tiles, 4));
+    if (a.n_tiles) {
+        KMU_TRY(launch(ctx, "k_cons_count", k_cons_tiles<false>, grid, dim3(256), 0, a));
+        KMU_TRY(device_scan_u32(ctx, a.tile_len, a.n_tiles, tile_off));
+    } else {
+        KMU_HIP(ctx, hipMemsetAsync(tile_off, 0, 8, ctx->stream));
+    }
+    a.cons_off = cons_offsets_out;
+    if (mem == KMU_MEM_HOST) KMU_TRY(dev_array(ctx, "cons.consoff", (size_t) n_reads + 1, &a.cons_off));
+    KMU_TRY(launch(ctx, "k_cons_offsets", k_cons_offsets, dim3(grid_for(ctx, (uint64_t) n_reads + 1, 256)), dim3(256), 0, a));
+    if (mem == KMU_MEM_HOST)
+        KMU_HIP(ctx, hipMemcpyAsync(cons_offsets_out, a.cons_off, ((size_t) n_reads + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
+    // (into a local: nothing may return between this copy and the synchronisation)
+    KMU_HIP(ctx, hipMemcpyAsync(&total, tile_off + a.n_tiles, 8, hipMemcpyDeviceToHost, ctx->stream));
+    KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    *n_cons_out = total;
+    if (cons_out && cap < total) {
+        if (ctx->profiling) profile_collect(ctx);
+        return fail(ctx, KMU_E_BAD_ARG, "cap = %llu is below the %llu bytes", (unsigned long long) cap, (unsigned long long) total);
+    }
+    if (cons_out && total) {
+        a.cons = cons_out;
+        if (mem == KMU_MEM_HOST) KMU_TRY(dev_array(ctx, "cons.cons", total, &a.cons));
+        KMU_TRY(launch(ctx, "k_cons_write", k_cons_tiles<true>, grid, dim3(256), 0, a));
+        if (mem == KMU_MEM_HOST) KMU_HIP(ctx, hipMemcpyAsync(cons_out, a.cons, total, hipMemcpyDeviceToHost, ctx->stream));
+        KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    if (ctx->profiling) profile_collect(ctx);
+    return KMU_OK;
+}

@@ -37,7 +37,7 @@ SYMBOLS = [
     "kmu_anchor_overlaps", "kmu_anchor_index_create", "kmu_anchor_index_destroy", "kmu_anchor_index_info",
     "kmu_anchor_index_occupancy", "kmu_anchor_index_match", "kmu_components", "kmu_components_knn",
     "kmu_minimizer_layout", "kmu_read_minimizers", "kmu_seed_chains", "kmu_chain_align",
-    "kmu_chain_cigar", "kmu_chain_pileup", "kmu_pile_call",
+    "kmu_chain_cigar", "kmu_chain_pileup", "kmu_pile_call", "kmu_pile_ins_plan", "kmu_chain_pile_ins", "kmu_pile_consensus",
 ]
 
 
@@ -152,6 +152,11 @@ def load():
     L.kmu_chain_pileup.argtypes = [vp, vp, C.c_uint64, vp, vp, vp, C.c_uint64, vp, vp, C.c_uint32, vp, vp, C.c_uint32,
                                    C.POINTER(A.PileupParams), C.c_int, vp, vp]
     L.kmu_pile_call.argtypes = [vp, vp, vp, vp, C.c_uint32, C.POINTER(A.PileCallParams), C.c_int, vp, vp]
+    L.kmu_pile_ins_plan.argtypes = [vp, vp, vp, C.c_uint64, C.POINTER(A.InsPlanParams), C.c_int, vp, C.POINTER(C.c_uint64)]
+    L.kmu_chain_pile_ins.argtypes = [vp, vp, C.c_uint64, vp, vp, vp, C.c_uint64, vp, vp, C.c_uint32, vp, vp, C.c_uint32,
+                                     C.POINTER(A.PileupParams), C.c_int, vp, C.c_uint64, vp, vp, C.c_uint64, vp]
+    L.kmu_pile_consensus.argtypes = [vp, vp, vp, vp, C.c_uint64, vp, vp, vp, C.c_uint32, C.POINTER(A.ConsensusParams), C.c_int, vp, vp,
+                                     C.c_uint64, C.POINTER(C.c_uint64)]
     L.kmu_set_hll_params.argtypes = [vp, C.POINTER(A.HllParams)]
     L.kmu_kmer_hashes_compact.argtypes = [vp, C.POINTER(A.HashParams), vp, vp, vp, C.c_uint32, vp, C.c_uint64, u64p]
     L.kmu_sketch_partial_words.argtypes = [C.POINTER(A.SketchParams)]
@@ -1090,6 +1095,106 @@ class Context:
             return _ptr(x)[0] if int(x.shape[0]) else _ptr(none)[0]
         self._check(self.L.kmu_pile_call(self.h, ptr(pile), ptr(bases), _ptr(off)[0], n_reads, C.byref(p), mem, _ptr(call)[0], _ptr(reads)[0]))
         return (call[:n_bases] if call is not None else None), (reads[:n_reads] if reads is not None else None)
+
+    def pile_ins_plan(self, pile, call, max_ins=16):
+        """kmu_pile_ins_plan: how many insertion slots every base of a batch gets, from its table (chain_pileup) and its calls
+        (pile_call): 0 without A.CALL_INS, otherwise min(max_ins, (2 INS_BASES - 1) // depth).  Returns (ins_len, n_slots): uint8
+        [n_bases] where the table lives, and the sum as an int.  Slot s of row g has the index S(g) + s, S being the exclusive
+        prefix sum of ins_len."""
+        mem = self._mem(pile, call)
+        n_bases = int(pile.shape[0])
+        if int(call.shape[0]) != n_bases:
+            raise ValueError("the table has %d rows: call must have as many bytes" % n_bases)
+        ins_len = self._new_like(pile, max(n_bases, 1), np.uint8, "uint8")
+        p = A.InsPlanParams(int(max_ins), 0)
+        none = self._new_like(pile, 16, np.uint8, "uint8")  # an empty array has no address worth passing
+        total = C.c_uint64(0)
+
+        def ptr(x):
+            return _ptr(x)[0] if int(x.shape[0]) else _ptr(none)[0]
+        self._check(self.L.kmu_pile_ins_plan(self.h, ptr(pile), ptr(call), n_bases, C.byref(p), mem, _ptr(ins_len)[0], C.byref(total)))
+        return ins_len[:n_bases], int(total.value)
+
+    def chain_pile_ins(self, chains, aln, ops, op_offsets, bases_q, offsets_q, ins_len_q, n_slots_q, bases_db=None, offsets_db=None,
+                       ins_len_db=None, n_slots_db=None, sides=A.PILE_Q | A.PILE_DB, into=None):
+        """kmu_chain_pile_ins: the letters of every chain's gap runs, voted into the insertion slots of both reads (include/kmu.h has
+        the rules).  chains .. offsets_*: as chain_pileup takes them; ins_len_* / n_slots_*: what pile_ins_plan gave for each batch
+        (db=None: the self-join, one plan).  Returns (ins_q, ins_db): uint32 [n_slots, A.INS_COLS] tables, one count per letter of
+        every slot (int32 holding the same bits for torch); in the self-join both names are the same array; the table of a side
+        that `sides` leaves out is None.  into=(ins_q, ins_db), or one table for the self-join: tables to accumulate into;
+        otherwise they are allocated here, zeroed."""
+        own = bases_db is None
+        if own:
+            bases_db, offsets_db, ins_len_db, n_slots_db = bases_q, offsets_q, ins_len_q, n_slots_q
+        elif offsets_db is None:
+            raise ValueError("bases_db without offsets_db")
+        if not _is_torch(chains):
+            chains = np.ascontiguousarray(chains)
+        if not _is_torch(aln):
+            aln = np.ascontiguousarray(aln)
+        sides = int(sides)
+        if (sides & A.PILE_Q and ins_len_q is None) or (sides & A.PILE_DB and ins_len_db is None):
+            raise ValueError("a side that is asked for needs its ins_len and n_slots")
+        mem = self._mem(chains, aln, ops, op_offsets, bases_q, bases_db, ins_len_q, ins_len_db)
+        n = int(chains.shape[0])
+        if int(aln.shape[0]) != n or int(op_offsets.shape[0]) != n + 1:
+            raise ValueError("%d chains need %d alignment records and %d run offsets" % (n, n, n + 1))
+        off_q = self._offsets_like(offsets_q, chains, mem)
+        off_db = off_q if offsets_db is offsets_q else self._offsets_like(offsets_db, chains, mem)
+        n_slots_q, n_slots_db = int(n_slots_q or 0), int(n_slots_db or 0)
+        if into is None:
+            ins_q = self._new_like(chains, (n_slots_q, A.INS_COLS), np.uint32, "int32") if sides & A.PILE_Q else None
+            if own and ins_q is not None:
+                ins_db = ins_q if sides & A.PILE_DB else None
+            else:
+                ins_db = self._new_like(chains, (n_slots_db, A.INS_COLS), np.uint32, "int32") if sides & A.PILE_DB else None
+        else:
+            ins_q, ins_db = into if isinstance(into, (tuple, list)) else (into, into)
+            if (sides & A.PILE_Q and ins_q is None) or (sides & A.PILE_DB and ins_db is None):
+                raise ValueError("into lacks the table of a side that is asked for")
+        p = A.PileupParams(sides)
+        none = self._new_like(chains, 16, np.uint8, "uint8")  # an empty array has no address worth passing
+
+        def ptr(x):
+            return _ptr(x)[0] if int(x.shape[0]) else _ptr(none)[0]
+        q, db = bool(sides & A.PILE_Q), bool(sides & A.PILE_DB)
+        spare = self._new_like(chains, 16, np.uint8, "uint8")  # two empty tables are still two tables
+
+        def table(x):
+            return _ptr(x)[0] if int(x.shape[0]) else _ptr(none if x is ins_q else spare)[0]
+        self._check(self.L.kmu_chain_pile_ins(self.h, ptr(chains), n, ptr(aln), _ptr(op_offsets)[0], ptr(ops), int(ops.shape[0]), ptr(bases_q),
+                                              _ptr(off_q)[0], int(off_q.shape[0]) - 1, ptr(bases_db), _ptr(off_db)[0], int(off_db.shape[0]) - 1,
+                                              C.byref(p), mem, ptr(ins_len_q) if q else None, n_slots_q, table(ins_q) if q else None,
+                                              ptr(ins_len_db) if db else None, n_slots_db, table(ins_db) if db else None))
+        return ins_q, ins_db
+
+    def pile_consensus(self, pile, call, ins_len, n_slots, ins, bases, offsets):
+        """kmu_pile_consensus: the corrected reads of a batch -- per base the called letter (the read's own byte where there is no
+        call, nothing for a DEL call) and then the emitted insertion slots.  pile, call: of chain_pileup and pile_call; ins_len,
+        n_slots: of pile_ins_plan; ins: of chain_pile_ins.  Returns (cons_bases, cons_offsets): a new ASCII batch, uint8 and uint64
+        [n_reads + 1] (int64 holding the same bits for torch), where the arrays live.  A row gives at most one byte and its slots, so
+        the output is sized by n_bases + n_slots and the library is called once."""
+        mem = self._mem(pile, call, ins_len, ins, bases)
+        off = self._offsets_like(offsets, pile, mem)
+        n_reads = int(off.shape[0]) - 1
+        n_bases = int(off[-1])
+        if any(int(x.shape[0]) != n_bases for x in (pile, call, ins_len, bases)):
+            raise ValueError("the batch has %d bases: the table, call, ins_len and the bases must have as many rows" % n_bases)
+        n_slots = int(n_slots)
+        if int(ins.shape[0]) != n_slots:
+            raise ValueError("ins has %d slots, not n_slots = %d" % (int(ins.shape[0]), n_slots))
+        cons_off = self._new_like(pile, n_reads + 1, np.uint64, "int64")
+        cap = n_bases + n_slots
+        cons = self._new_like(pile, max(cap, 1), np.uint8, "uint8")
+        p = A.ConsensusParams(0)
+        none = self._new_like(pile, 16, np.uint8, "uint8")  # an empty array has no address worth passing
+        total = C.c_uint64(0)
+
+        def ptr(x):
+            return _ptr(x)[0] if int(x.shape[0]) else _ptr(none)[0]
+        self._check(self.L.kmu_pile_consensus(self.h, ptr(pile), ptr(call), ptr(ins_len), n_slots, ptr(ins), ptr(bases), _ptr(off)[0], n_reads,
+                                              C.byref(p), mem, _ptr(cons_off)[0], _ptr(cons)[0], cap, C.byref(total)))
+        return cons[:int(total.value)], cons_off
 
     def _components(self, call, like, n_nodes, want, count):
         """the outputs of kmu_components / kmu_components_knn allocated where `like` lives, call(*output pointers) run on them,

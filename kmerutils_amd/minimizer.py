@@ -14,6 +14,10 @@ runs as text, and `paf_lines(..., cigar=(ops, op_offsets))` appends them as the 
 records and their runs to kmu_chain_pileup (Context.chain_pileup): for every base of every read, how many partners were aligned
 over it and what they had there; `read_pileups` goes from reads to (chains, aln, pile, call, reads) -- the self-join pileup and the
 calls of kmu_pile_call -- without the runs leaving where the reads live, and `pile_depth` is the depth column of a table.
+`insertions_chains` hands the same chains and runs, with the slots Context.pile_ins_plan gave every base, to kmu_chain_pile_ins
+(Context.chain_pile_ins): which letters the partners have where most of them have extra bases; `consensus_reads` turns table,
+calls and slots into the corrected reads (kmu_pile_consensus), a new batch of bases and offsets; `correct_reads` goes from reads
+to (cons_bases, cons_offsets, reads) in one call, and what it returns goes straight back into `read_minimizers` or the counter.
 """
 import collections
 
@@ -153,6 +157,38 @@ def read_pileups(ctx, bases, offsets, k, w, fhash=A.FHASH_CANON_INVHASH, max_occ
     pile, _ = pileup_chains(ctx, chains, aln, ops, op_offsets, bases, offsets)
     call, reads = ctx.pile_call(pile, bases, offsets, min_depth=min_depth)
     return chains, aln, pile, call, reads
+
+
+def insertions_chains(ctx, chains, aln, ops, op_offsets, bases_q, offsets_q, ins_len_q, n_slots_q, bases_db=None, offsets_db=None,
+                      ins_len_db=None, n_slots_db=None, sides=A.PILE_Q | A.PILE_DB, into=None):
+    """The letters of every chain's gap runs, voted into the insertion slots of both reads (kmu_chain_pile_ins): (ins_q, ins_db) as
+    Context.chain_pile_ins returns them -- uint32 [n_slots, A.INS_COLS], one count per letter of every slot; one shared table in
+    the self-join (db=None).  chains, aln, ops, op_offsets: as pileup_chains takes them; ins_len_* / n_slots_*: the plan of
+    Context.pile_ins_plan for each batch; sides and into as Context.chain_pile_ins."""
+    return ctx.chain_pile_ins(chains, aln, ops, op_offsets, bases_q, offsets_q, ins_len_q, n_slots_q, bases_db, offsets_db, ins_len_db,
+                              n_slots_db, sides=sides, into=into)
+
+
+def consensus_reads(ctx, pile, call, ins_len, n_slots, ins, bases, offsets):
+    """The corrected reads of a batch (kmu_pile_consensus): (cons_bases, cons_offsets), a new ASCII batch -- per base the called
+    letter, the read's own byte where there is no call, nothing for a DEL call, and behind it the emitted insertion slots."""
+    return ctx.pile_consensus(pile, call, ins_len, n_slots, ins, bases, offsets)
+
+
+def correct_reads(ctx, bases, offsets, k, w, fhash=A.FHASH_CANON_INVHASH, max_occ=0, max_gap=5000, band_chain=500, min_seeds=3,
+                  min_score=0, band=64, max_trace_bytes=0, min_depth=3, max_ins=16):
+    """From the reads of a batch to their corrected versions in one call: read_cigars, the self-join of pileup_chains,
+    Context.pile_call with `min_depth`, Context.pile_ins_plan with `max_ins`, the self-join of insertions_chains, consensus_reads.
+    Returns (cons_bases, cons_offsets, reads), reads being the summaries of pile_call.  Runs, tables and slots stay where the
+    reads live."""
+    chains, aln, ops, op_offsets = read_cigars(ctx, bases, offsets, k, w, fhash, max_occ, max_gap, band_chain, min_seeds, min_score, band,
+                                               max_trace_bytes)
+    pile, _ = pileup_chains(ctx, chains, aln, ops, op_offsets, bases, offsets)
+    call, reads = ctx.pile_call(pile, bases, offsets, min_depth=min_depth)
+    ins_len, n_slots = ctx.pile_ins_plan(pile, call, max_ins=max_ins)
+    ins, _ = insertions_chains(ctx, chains, aln, ops, op_offsets, bases, offsets, ins_len, n_slots)
+    cons_bases, cons_offsets = consensus_reads(ctx, pile, call, ins_len, n_slots, ins, bases, offsets)
+    return cons_bases, cons_offsets, reads
 
 
 def pile_depth(pile):

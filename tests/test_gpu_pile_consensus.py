@@ -1,0 +1,570 @@
+"""-m gpu: kmu_pile_ins_plan, kmu_chain_pile_ins and kmu_pile_consensus against `reference_ins_plan`, `reference_ins_votes` and
+`reference_consensus` (tests/test_consensus_abi.py: the contracts of include/kmu.h in plain numpy).  Whole arrays are compared byte
+for byte.  The votes depend on the run structure and the letters only, so the edge cases synthesise run lists (synth_chains) and
+tables and need no aligner; the planted truth goes through Context.chain_cigar on hand-made whole-read chain records."""
+import ctypes as C
+import os
+import sys
+
+import numpy as np
+import pytest
+
+from kmerutils_amd import _abi as A
+from kmerutils_amd import lib
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from test_chain_align_abi import batch, chain_recs, revcomp  # noqa: E402
+from test_consensus_abi import (adjacent_runs_case, emission_cases, insertion_cases, reference_consensus, reference_correct,  # noqa: E402
+                                reference_ins_plan, reference_ins_votes, row_rule_cases, slot_count_cases)
+from test_gpu_chain_align import ACGT, mutate  # noqa: E402
+from test_gpu_chain_pileup import SPOILED, _spoil, to_device  # noqa: E402
+from test_pileup_abi import random_runs, reference_call, reference_pileup, synth_chains  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def ctx():
+    c = lib.Context(0)
+    yield c
+    c.close()
+
+
+def same(got, want, what=""):
+    got, want = np.asarray(got), np.asarray(want)
+    assert got.dtype == want.dtype and got.shape == want.shape, (what, got.dtype, got.shape, want.dtype, want.shape)
+    bad = np.nonzero((got != want).reshape(got.shape[0], -1).any(axis=1))[0] if got.size else np.zeros(0, np.int64)
+    assert bad.size == 0, "%s row %d of %d that differ: got %s, want %s" % (what, bad[0], bad.size, got[bad[0]], want[bad[0]])
+
+
+def check_consensus(ctx, pile, call, ins_len, ins, bases, offsets):
+    want = reference_consensus(pile, call, ins_len, ins, bases, offsets)
+    got = ctx.pile_consensus(pile, call, ins_len, ins.shape[0], ins, bases, offsets)
+    same(got[0], want[0], "cons")
+    same(got[1], want[1], "cons_offsets")
+    return got
+
+
+def check_route(ctx, case, max_ins=16, min_depth=1, separate=False):
+    """plan, votes and consensus of the self-join of a case (what synth_chains returns), each equal to its reference in every byte, on
+    the references' tables.  separate: the votes also into two tables of the one batch"""
+    chains, aln, ops, off, bases, offsets = case
+    pile = reference_pileup(*case)[0]
+    call = reference_call(pile, bases, offsets, min_depth)[0]
+    ins_len, n_slots = reference_ins_plan(pile, call, max_ins)
+    got_len, got_n = ctx.pile_ins_plan(pile, call, max_ins=max_ins)
+    same(got_len, ins_len, "ins_len")
+    assert got_n == n_slots
+    want = reference_ins_votes(*case, ins_len)[0]
+    got = ctx.chain_pile_ins(*case, ins_len, n_slots)
+    assert got[0] is got[1]
+    same(got[0], want, "ins")
+    if separate:
+        want_q, want_db = reference_ins_votes(*case, ins_len, bases, offsets, ins_len)
+        got_q, got_db = ctx.chain_pile_ins(*case, ins_len, n_slots, bases, offsets.copy(), ins_len.copy(), n_slots)
+        assert got_q is not got_db
+        same(got_q, want_q, "ins_q")
+        same(got_db, want_db, "ins_db")
+    check_consensus(ctx, pile, call, ins_len, want, bases, offsets)
+    return pile, call, ins_len, want
+
+
+# ---- the hand cases of tests/test_consensus_abi.py, on the device ----------------------------------------------------------------
+def test_hand_cases_on_the_device(ctx):
+    """the tables worked out on paper, which test_consensus_abi.py holds the references to, through the library itself"""
+    def votes(chains, aln, ops, off, bases, offsets, ins_len):
+        return ctx.chain_pile_ins(chains, aln, ops, off, bases, offsets, ins_len, int(ins_len.sum()))[0]
+
+    def consensus(pile, call, ins_len, ins, bases, offsets):
+        return ctx.pile_consensus(pile, call, ins_len, ins.shape[0], ins, bases, offsets)
+    slot_count_cases(lambda pile, call, max_ins: ctx.pile_ins_plan(pile, call, max_ins=max_ins))
+    insertion_cases(votes)
+    adjacent_runs_case(votes)
+    row_rule_cases(consensus)
+    emission_cases(consensus)
+
+
+# ---- the edges of the row tiles ---------------------------------------------------------------------------------------------------
+def random_rows(rng, lengths, max_ins, with_slots=()):
+    """a batch of reads of these lengths with a random table (small counts: many ties, many rows below min_depth), the calls and the
+    plan of the references and a random slot table that is not monotone along a row; with_slots: rows that get slots for sure"""
+    bases, offsets = batch(["".join(rng.choice(list("ACGTacgtNn"), n)) for n in lengths])
+    n = bases.size
+    pile = rng.integers(0, 4, (n, 8)).astype(np.uint32)
+    pile[:, A.PILE_INS_BASES] = pile[:, A.PILE_INS] * rng.integers(1, 400, n).astype(np.uint32)
+    for g in with_slots:
+        if 0 <= g < n:
+            pile[g] = (2, 0, 0, 0, 1, 2, 300, 0)
+    call = reference_call(pile, bases, offsets, 2)[0]
+    ins_len, n_slots = reference_ins_plan(pile, call, max_ins)
+    ins = rng.integers(0, 4, (n_slots, 4)).astype(np.uint32)
+    ins[rng.integers(0, 5, n_slots) == 0] = 0
+    return pile, call, ins_len, n_slots, ins, bases, offsets
+
+
+@pytest.mark.parametrize("n_bases", [0, 1, 63, 64, 65, 127, 128, 129, 1000])
+def test_row_tile_edges(ctx, n_bases):
+    """reads of length 0, a read boundary in the middle of a tile, slots at the first and the last row of a 64-row block and at the
+    last row of the batch; host mode and device mode"""
+    import torch
+    rng = np.random.default_rng(100 + n_bases)
+    first = n_bases // 3
+    for max_ins in (1, 16, 255):
+        pile, call, ins_len, n_slots, ins, bases, offsets = random_rows(rng, [0, first, 0, 0, n_bases - first, 0], max_ins,
+                                                                        with_slots=(0, 63, 64, 127, 128, n_bases - 1))
+        if n_bases:
+            assert ins_len[0] == ins_len[n_bases - 1] == min(max_ins, 199) and (n_bases < 64 or ins_len[63] > 0)
+        got_len, got_n = ctx.pile_ins_plan(pile, call, max_ins=max_ins)
+        same(got_len, ins_len, "ins_len")
+        assert got_n == n_slots
+        cons, coff = check_consensus(ctx, pile, call, ins_len, ins, bases, offsets)
+        assert coff.shape == (7,) and coff[0] == 0 and coff[1] == coff[0] and int(coff[-1]) == cons.size
+        dev = [torch.from_numpy(x.view(t)).cuda() for x, t in ((pile, np.int32), (call, np.uint8), (ins_len, np.uint8), (ins, np.int32), (bases, np.uint8))]
+        d_len, d_n = ctx.pile_ins_plan(dev[0], dev[1], max_ins=max_ins)
+        assert d_len.is_cuda and d_n == n_slots and (d_len.cpu().numpy() == ins_len).all()
+        d_cons, d_off = ctx.pile_consensus(dev[0], dev[1], dev[2], n_slots, dev[3], dev[4], offsets)
+        assert d_cons.is_cuda and d_off.is_cuda and d_off.dtype == torch.int64
+        assert d_cons.cpu().numpy().tobytes() == cons.tobytes() and d_off.cpu().numpy().view(np.uint64).tolist() == coff.tolist()
+
+
+def test_row_outcomes(ctx):
+    """every row of a read called DEL: the read comes out empty and two offsets are equal; uncalled rows holding N and lower-case
+    bytes pass through verbatim; a called row is upper case"""
+    bases, offsets = batch(["acgtN", "CCC", "nNxa"])
+    pile = np.zeros((12, 8), np.uint32)
+    pile[5:8, A.PILE_DEL] = 4
+    pile[0, A.PILE_A] = 4
+    call = reference_call(pile, bases, offsets, 3)[0]
+    ins_len, n_slots = reference_ins_plan(pile, call)
+    assert n_slots == 0
+    cons, coff = check_consensus(ctx, pile, call, ins_len, np.zeros((0, 4), np.uint32), bases, offsets)
+    assert cons.tobytes() == b"AcgtNnNxa" and coff.tolist() == [0, 5, 5, 9]
+
+
+# ---- the edges of the run tiles and of the insertion lengths ---------------------------------------------------------------------
+@pytest.mark.parametrize("n_runs", [0, 1, 63, 64, 65, 129])
+def test_run_tile_edges(ctx, n_runs):
+    """one chain with this many runs on either strand, and a few small ones around it; one shared table and two tables"""
+    rng = np.random.default_rng(200 + n_runs)
+    lists = [random_runs(rng, 3), random_runs(rng, n_runs), random_runs(rng, n_runs), random_runs(rng, 5)]
+    case = synth_chains(rng, lists, [0, 0, 1, 1])
+    pile, call, ins_len, ins = check_route(ctx, case, separate=True)
+    assert n_runs < 63 or ins.sum() > 0
+
+
+@pytest.mark.parametrize("max_ins", [1, 16, 255])
+def test_insertion_lengths(ctx, max_ins):
+    """gap runs of 1, max_ins - 1, max_ins, max_ins + 1 and 5000 letters on both sides and strands, alone between two matches, next
+    to each other (cut runs), at the start and at the end of a chain"""
+    rng = np.random.default_rng(300 + max_ins)
+    lists, strands = [], []
+    for s in (0, 1):
+        for length in sorted({1, max_ins - 1, max_ins, max_ins + 1, 5000} - {0}):
+            for x in "DI":
+                lists += [[(4, "="), (length, x), (5, "=")], [(2, "X"), (length, x), (length, x), (3, "=")], [(length, x), (3, "=")], [(3, "="), (length, x)],
+                          random_runs(rng, 70) + [(length, x)] + random_runs(rng, 4)]
+            lists += [[(2, "="), (length, "I"), (length, "D"), (1, "=")]]
+        strands += [s] * (len(lists) - len(strands))
+    pile, call, ins_len, ins = check_route(ctx, synth_chains(rng, lists, strands, pad=2), max_ins=max_ins)
+    assert int(ins_len.max()) == max_ins
+
+
+def test_contention_200_chains_insert_behind_one_base(ctx):
+    rng = np.random.default_rng(8)
+    lists = [[(40, "="), (3, "D"), (60, "=")] for c in range(200)]
+    case = synth_chains(rng, lists, [c & 1 for c in range(200)], shared_a=(0, 17))
+    pile, call, ins_len, ins = check_route(ctx, case, min_depth=3)
+    g = 17 + 39
+    assert pile[g, A.PILE_INS] == 200 and ins_len[g] == 5 and ins_len.sum() == 5   # (2 * 600 - 1) // 200
+    assert ins.sum(axis=1).tolist() == [200, 200, 200, 0, 0]
+
+
+# ---- sides, accumulation, order, modes -------------------------------------------------------------------------------------------
+def mixed_case(seed=9, n=40):
+    rng = np.random.default_rng(seed)
+    return synth_chains(rng, [random_runs(rng, int(rng.integers(1, 150))) for _ in range(n)], [int(rng.integers(0, 2)) for _ in range(n)])
+
+
+def planned(case, max_ins=16):
+    pile = reference_pileup(*case)[0]
+    call = reference_call(pile, case[4], case[5], 1)[0]
+    return reference_ins_plan(pile, call, max_ins)
+
+
+def test_one_side_only_and_separate_batches(ctx):
+    chains, aln, ops, off, bases, offsets = case = mixed_case()
+    ins_len, n_slots = planned(case)
+    both = reference_ins_votes(*case, ins_len)[0]
+    for side in (A.PILE_Q, A.PILE_DB):
+        want = reference_ins_votes(*case, ins_len, bases, offsets, ins_len, sides=side)
+        got = ctx.chain_pile_ins(*case, ins_len, n_slots, bases, offsets.copy(), ins_len.copy(), n_slots, sides=side)
+        mine, other = (0, 1) if side == A.PILE_Q else (1, 0)
+        assert got[other] is None and not want[other].any() and want[mine].any()
+        same(got[mine], want[mine])
+        pattern = np.full(both.shape, 0xABCD0123, np.uint32)   # a table that is there all the same is not touched
+        tables = [np.zeros_like(pattern), np.zeros_like(pattern)]
+        tables[other] = pattern.copy()
+        ctx.chain_pile_ins(*case, ins_len, n_slots, bases, offsets.copy(), ins_len.copy(), n_slots, sides=side, into=tuple(tables))
+        same(tables[mine], want[mine])
+        assert (tables[other] == pattern).all()
+    # the A segments in one batch, the B segments in another, each with a plan of its own
+    reads = [bases[int(offsets[r]):int(offsets[r + 1])].tobytes().decode() for r in range(len(offsets) - 1)]
+    bq, oq = batch(reads[0::2])
+    bdb, odb = batch(reads[1::2] + ["ACGT"])
+    lq = np.concatenate([ins_len[int(offsets[r]):int(offsets[r + 1])] for r in range(0, len(reads), 2)])
+    ldb = np.concatenate([ins_len[int(offsets[r]):int(offsets[r + 1])] for r in range(1, len(reads), 2)] + [np.array([0, 3, 0, 1], np.uint8)])
+    two = chains.copy()
+    two["read_a"], two["read_b"] = two["read_a"] // 2, two["read_b"] // 2
+    want = reference_ins_votes(two, aln, ops, off, bq, oq, lq, bdb, odb, ldb)
+    got = ctx.chain_pile_ins(two, aln, ops, off, bq, oq, lq, int(lq.sum()), bdb, odb, ldb, int(ldb.sum()))
+    same(got[0], want[0], "q")
+    same(got[1], want[1], "db")
+    assert not got[1][-4:].any()
+    # no slots at all on either side: two empty tables
+    zero_q, zero_db = np.zeros_like(lq), np.zeros_like(ldb)
+    got = ctx.chain_pile_ins(two, aln, ops, off, bq, oq, zero_q, 0, bdb, odb, zero_db, 0)
+    assert got[0].shape == got[1].shape == (0, 4)
+
+
+def test_accumulation_and_order(ctx):
+    chains, aln, ops, off, bases, offsets = case = mixed_case(12, 50)
+    ins_len, n_slots = planned(case)
+    whole = reference_ins_votes(*case, ins_len)[0]
+    cut = 23
+    first = (chains[:cut], aln[:cut], ops[:int(off[cut])], off[:cut + 1], bases, offsets)
+    second = (chains[cut:], aln[cut:], ops[int(off[cut]):], off[cut:] - off[cut], bases, offsets)
+    table = ctx.chain_pile_ins(*first, ins_len, n_slots)[0]
+    assert ctx.chain_pile_ins(*second, ins_len, n_slots, into=table)[0] is table
+    same(table, whole)
+    perm = np.random.default_rng(3).permutation(50)
+    parts = [ops[int(off[c]):int(off[c + 1])] for c in perm]
+    poff = np.zeros(51, np.uint64)
+    poff[1:] = np.cumsum([p.size for p in parts])
+    same(ctx.chain_pile_ins(chains[perm], aln[perm], np.concatenate(parts), poff, bases, offsets, ins_len, n_slots)[0], whole)
+    # chains without a path vote nothing
+    none = aln.copy()
+    none["flags"] = A.ALN_DONE
+    assert not ctx.chain_pile_ins(chains, none, ops[:0], np.zeros(51, np.uint64), bases, offsets, ins_len, n_slots)[0].any()
+
+
+def test_device_mode_equals_host_mode(ctx):
+    import torch
+    case = mixed_case(13, 60)
+    ins_len, n_slots = planned(case)
+    want = reference_ins_votes(*case, ins_len)[0]
+    dev = to_device(case)
+    d_len = torch.from_numpy(ins_len).cuda()
+    got = ctx.chain_pile_ins(*dev, d_len, n_slots)
+    assert got[0] is got[1] and got[0].is_cuda and got[0].dtype == torch.int32 and tuple(got[0].shape) == want.shape
+    same(got[0].cpu().numpy().view(np.uint32), want)
+    again = ctx.chain_pile_ins(*dev, d_len, n_slots, into=got[0])[0]  # accumulates on the device too
+    same(again.cpu().numpy().view(np.uint32), 2 * want)
+    q, db = ctx.chain_pile_ins(*dev, d_len, n_slots, dev[4], dev[5].clone(), d_len.clone(), n_slots)
+    same(q.cpu().numpy().view(np.uint32) + db.cpu().numpy().view(np.uint32), want)
+    assert ctx.chain_pile_ins(dev[0][:0], dev[1][:0], dev[2][:0], dev[3][:1], dev[4], dev[5], d_len, n_slots)[0].sum().item() == 0
+    empty = ctx.chain_pile_ins(case[0][:0], case[1][:0], case[2][:0], case[3][:1], case[4], case[5], ins_len, n_slots)[0]
+    assert empty.shape == want.shape and not empty.any()
+
+
+# ---- capacity -----------------------------------------------------------------------------------------------------------------------
+def raw_consensus(ctx, pile, call, ins_len, n_slots, ins, bases, offsets, cons_off, cons, cap):
+    """kmu_pile_consensus on host arrays as they are; returns (status, total)"""
+    total = C.c_uint64(12345)
+    p = A.ConsensusParams(0)
+
+    def ptr(x):
+        return x.ctypes.data_as(C.c_void_p) if x is not None and x.size else (None if x is None else np.zeros(16, np.uint8).ctypes.data_as(C.c_void_p))
+    rc = ctx.L.kmu_pile_consensus(ctx.h, ptr(pile), ptr(call), ptr(ins_len), n_slots, ptr(ins), ptr(bases), ptr(offsets), len(offsets) - 1, C.byref(p),
+                                  A.MEM_HOST, ptr(cons_off), cons.ctypes.data_as(C.c_void_p) if cons is not None else None, cap, C.byref(total))
+    return rc, int(total.value)
+
+
+def test_capacity(ctx):
+    rng = np.random.default_rng(60)
+    pile, call, ins_len, n_slots, ins, bases, offsets = rows = random_rows(rng, [70, 0, 200], 16, with_slots=(0, 100, 269))
+    want, want_off = reference_consensus(pile, call, ins_len, ins, bases, offsets)
+    coff = np.full(4, 99, np.uint64)
+    assert raw_consensus(ctx, *rows, coff, None, 0) == (0, want.size) and coff.tolist() == want_off.tolist()   # the count-only call
+    coff[:] = 99
+    cons = np.full(want.size + 8, 0xEE, np.uint8)
+    assert raw_consensus(ctx, *rows, coff, cons, want.size) == (0, want.size)                                   # cap exactly the total
+    assert cons[:want.size].tobytes() == want.tobytes() and (cons[want.size:] == 0xEE).all() and coff.tolist() == want_off.tolist()
+    coff[:] = 99
+    cons[:] = 0xEE
+    assert raw_consensus(ctx, *rows, coff, cons, want.size - 1) == (A.E_BAD_ARG, want.size)                     # one short
+    assert (cons[want.size - 1:] == 0xEE).all() and coff.tolist() == want_off.tolist()
+    check_consensus(ctx, pile, call, ins_len, ins, bases, offsets)  # the context goes on working
+
+
+# ---- refusals ----------------------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def refusal_case():
+    rng = np.random.default_rng(14)
+    lists = [[(3, "="), (2, "I"), (4, "X"), (1, "D"), (6, "=")] + random_runs(rng, int(rng.integers(0, 100))) for _ in range(8)]
+    case = synth_chains(rng, lists, [c & 1 for c in range(8)], pad=5)
+    return case, planned(case)
+
+
+@pytest.mark.parametrize("what", SPOILED)
+def test_unsupported_is_found_before_any_vote(ctx, refusal_case, what):
+    """everything kmu_chain_pileup refuses: on the device's own table (device mode), filled with a pattern that must come back
+    unchanged; and on host arrays"""
+    import torch
+    case, (ins_len, n_slots) = refusal_case
+    bad = _spoil(case, what)
+    dev = to_device(bad)
+    table = torch.full((n_slots, A.INS_COLS), 0x5A5A5A5, dtype=torch.int32, device="cuda")
+    with pytest.raises(lib.KmuError) as e:
+        ctx.chain_pile_ins(*dev, torch.from_numpy(ins_len).cuda(), n_slots, into=table)
+    assert e.value.code == A.E_UNSUPPORTED
+    assert (table == 0x5A5A5A5).all().item()
+    host = np.full((n_slots, A.INS_COLS), 77, np.uint32)
+    with pytest.raises(lib.KmuError) as e:
+        ctx.chain_pile_ins(*bad, ins_len, n_slots, into=host)
+    assert e.value.code == A.E_UNSUPPORTED and (host == 77).all()
+    same(ctx.chain_pile_ins(*case, ins_len, n_slots)[0], reference_ins_votes(*case, ins_len)[0])  # the context goes on working
+
+
+def test_a_plan_that_is_not_n_slots_is_refused(ctx, refusal_case):
+    import torch
+    case, (ins_len, n_slots) = refusal_case
+    chains, aln, ops, off, bases, offsets = case
+    assert n_slots > 4
+    more, less = ins_len.copy(), ins_len.copy()
+    more[np.nonzero(ins_len == 0)[0][-1]] = 255   # the sum is above n_slots: no slot index from it is used
+    less[np.nonzero(ins_len)[0][0]] -= 1
+    dev = to_device(case)
+    for spoiled, n in ((more, n_slots), (less, n_slots), (ins_len, n_slots + 1), (ins_len, n_slots - 1)):
+        host = np.full((max(n, n_slots), A.INS_COLS), 77, np.uint32)
+        with pytest.raises(lib.KmuError) as e:
+            ctx.chain_pile_ins(*case, spoiled, n, into=host)
+        assert e.value.code == A.E_UNSUPPORTED and (host == 77).all()
+        table = torch.full((max(n, n_slots), A.INS_COLS), 0x5A5A5A5, dtype=torch.int32, device="cuda")
+        with pytest.raises(lib.KmuError) as e:
+            ctx.chain_pile_ins(*dev, torch.from_numpy(spoiled).cuda(), n, into=table)
+        assert e.value.code == A.E_UNSUPPORTED and (table == 0x5A5A5A5).all().item()
+        # the consensus: offsets and bytes stay as they were
+        pile = reference_pileup(*case)[0]
+        call = reference_call(pile, bases, offsets, 1)[0]
+        coff, cons = np.full(len(offsets), 99, np.uint64), np.full(4 * bases.size, 0xEE, np.uint8)
+        ins = np.ones((n, A.INS_COLS), np.uint32)
+        assert raw_consensus(ctx, pile, call, spoiled, n, ins, bases, offsets, coff, cons, cons.size)[0] == A.E_UNSUPPORTED
+        assert (coff == 99).all() and (cons == 0xEE).all()
+        with pytest.raises(lib.KmuError) as e:
+            ctx.pile_consensus(*(torch.from_numpy(x.view(t)).cuda() for x, t in ((pile, np.int32), (call, np.uint8), (spoiled, np.uint8))), n,
+                               torch.from_numpy(ins.view(np.int32)).cuda(), torch.from_numpy(bases).cuda(), offsets)
+        assert e.value.code == A.E_UNSUPPORTED
+    same(ctx.chain_pile_ins(*case, ins_len, n_slots)[0], reference_ins_votes(*case, ins_len)[0])
+
+
+def test_bad_arguments_and_non_acgt(ctx, refusal_case):
+    case, (ins_len, n_slots) = refusal_case
+    chains, aln, ops, off, bases, offsets = case
+    pile = reference_pileup(*case)[0]
+    call = reference_call(pile, bases, offsets, 1)[0]
+    for max_ins in (0, 256, 1 << 20):
+        with pytest.raises(lib.KmuError) as e:
+            ctx.pile_ins_plan(pile, call, max_ins=max_ins)
+        assert e.value.code == A.E_BAD_ARG
+    for sides in (0, 4, 7):
+        with pytest.raises(lib.KmuError) as e:
+            ctx.chain_pile_ins(*case, ins_len, n_slots, sides=sides, into=np.zeros((n_slots, 4), np.uint32))
+        assert e.value.code == A.E_BAD_ARG
+    with pytest.raises(lib.KmuError) as e:  # one table for two different batches
+        ctx.chain_pile_ins(*case, ins_len, n_slots, bases, offsets.copy(), ins_len, n_slots, into=np.zeros((n_slots, 4), np.uint32))
+    assert e.value.code == A.E_BAD_ARG
+    # an N among the letters of a voted gap run; under a letter that is not voted it is not looked at
+    rec = chains[2]   # 3= 2I 4X 1D: the D run's letter is B' index 7
+    j = 7
+    at = int(offsets[rec["read_b"]]) + (int(rec["b_end"]) - 1 - j if rec["strand"] else int(rec["b_start"]) + j)
+    spoiled = bases.copy()
+    spoiled[at] = ord("N")
+    for sides in (A.PILE_Q | A.PILE_DB, A.PILE_Q):
+        with pytest.raises(lib.KmuError) as e:
+            ctx.chain_pile_ins(chains, aln, ops, off, spoiled, offsets, ins_len, n_slots, sides=sides)
+        assert e.value.code == A.E_NON_ACGT
+    got = ctx.chain_pile_ins(chains, aln, ops, off, spoiled, offsets, ins_len, n_slots, sides=A.PILE_DB)[1]
+    same(got, reference_ins_votes(*case, ins_len, sides=A.PILE_DB)[1])
+    spoiled = bases.copy()
+    spoiled[int(offsets[rec["read_b"]]) + int(rec["b_start"])] = ord("N")   # a base of a diagonal column: the pileup minds, this call does not
+    same(ctx.chain_pile_ins(chains, aln, ops, off, spoiled, offsets, ins_len, n_slots)[0], reference_ins_votes(*case, ins_len)[0])
+
+
+# ---- every KMU_E_BAD_ARG, on a live context, with the outputs compared afterwards ------------------------------------------------
+def _p(x):
+    """the address of a numpy array, None as it is"""
+    return None if x is None else x.ctypes.data_as(C.c_void_p)
+
+
+def test_every_bad_argument_of_the_plan(ctx, refusal_case):
+    case, _ = refusal_case
+    pile = reference_pileup(*case)[0]
+    call = reference_call(pile, case[4], case[5], 1)[0]
+    out = np.full(call.size, 0xEE, np.uint8)
+    total = C.c_uint64(12345)
+
+    def run(pile=pile, call=call, params=(16, 0), mem=A.MEM_HOST, out=out, total=total):
+        p = A.InsPlanParams(*params) if params is not None else None
+        rc = ctx.L.kmu_pile_ins_plan(ctx.h, _p(pile), _p(call), call.size if call is not None else 1, C.byref(p) if p is not None else None, mem,
+                                     _p(out), C.byref(total) if total is not None else None)
+        return rc
+    bad = [dict(pile=None), dict(call=None), dict(params=None), dict(out=None), dict(total=None), dict(params=(0, 0)), dict(params=(256, 0)),
+           dict(params=(16, 1)), dict(params=(16, 0x80000000)), dict(mem=7), dict(mem=-1)]
+    for kw in bad:
+        assert run(**kw) == A.E_BAD_ARG, kw
+        assert (out == 0xEE).all() and total.value == 12345, kw
+    assert run() == 0 and total.value == reference_ins_plan(pile, call, 16)[1] and (out == reference_ins_plan(pile, call, 16)[0]).all()
+
+
+def test_every_bad_argument_of_the_votes(ctx, refusal_case):
+    case, (ins_len, n_slots) = refusal_case
+    chains, aln, ops, off, bases, offsets = case
+    n_reads = len(offsets) - 1
+    bases2, offsets2, ins_len2 = bases.copy(), offsets.copy(), ins_len.copy()
+    table, table2 = np.full((n_slots + 1, 4), 77, np.uint32), np.full((n_slots + 1, 4), 78, np.uint32)
+    base = dict(chains=chains, n_chains=len(chains), aln=aln, op_offsets=off, ops=ops, n_ops=ops.size, bases_q=bases, offsets_q=offsets, n_reads_q=n_reads,
+                bases_db=bases, offsets_db=offsets, n_reads_db=n_reads, flags=A.PILE_Q | A.PILE_DB, mem=A.MEM_HOST, ins_len_q=ins_len, n_slots_q=n_slots,
+                ins_q=table, ins_len_db=ins_len, n_slots_db=n_slots, ins_db=table)
+    two = dict(bases_db=bases2, offsets_db=offsets2, ins_len_db=ins_len2, ins_db=table2)   # two batches, two tables: a good call
+
+    def run(**kw):
+        a = dict(base, **kw)
+        p = A.PileupParams(a["flags"]) if a["flags"] is not None else None
+        return ctx.L.kmu_chain_pile_ins(ctx.h, _p(a["chains"]), a["n_chains"], _p(a["aln"]), _p(a["op_offsets"]), _p(a["ops"]), a["n_ops"], _p(a["bases_q"]),
+                                        _p(a["offsets_q"]), a["n_reads_q"], _p(a["bases_db"]), _p(a["offsets_db"]), a["n_reads_db"],
+                                        C.byref(p) if p is not None else None, a["mem"], _p(a["ins_len_q"]), a["n_slots_q"], _p(a["ins_q"]),
+                                        _p(a["ins_len_db"]), a["n_slots_db"], _p(a["ins_db"]))
+    bad = [dict(chains=None), dict(aln=None), dict(op_offsets=None), dict(bases_q=None), dict(offsets_q=None), dict(bases_db=None), dict(offsets_db=None),
+           dict(flags=None), dict(ops=None), dict(flags=0), dict(flags=4), dict(flags=7), dict(mem=7), dict(mem=-1),
+           dict(ins_q=None), dict(ins_db=None),                                    # a null table for a side asked for
+           dict(two, ins_db=table),                                                # one table for both sides of two batches
+           dict(two, n_reads_q=0), dict(two, n_reads_db=0),                        # chains but no reads
+           dict(ins_len_q=None), dict(ins_len_db=None), dict(two, ins_len_db=None),  # a null ins_len for a side asked for
+           dict(ins_len_db=ins_len2),                                              # one table, two ins_len
+           dict(n_slots_db=n_slots + 1), dict(n_slots_q=n_slots - 1)]              # one table, two n_slots
+    for kw in bad:
+        assert run(**kw) == A.E_BAD_ARG, sorted(kw)
+        assert (table == 77).all() and (table2 == 78).all(), sorted(kw)
+    # what a side that is not asked for may leave out
+    assert run(flags=A.PILE_Q, ins_db=None, ins_len_db=None, n_slots_db=0) == 0
+    assert run(**dict(two, flags=A.PILE_DB, ins_q=None, ins_len_q=None, n_slots_q=0)) == 0
+    want_q, want_db = reference_ins_votes(*case, ins_len, bases, offsets, ins_len, sides=A.PILE_Q)[0], reference_ins_votes(*case, ins_len, bases, offsets, ins_len, sides=A.PILE_DB)[1]
+    assert (table[:n_slots] == 77 + want_q).all() and (table2[:n_slots] == 78 + want_db).all() and (table[n_slots:] == 77).all() and (table2[n_slots:] == 78).all()
+
+
+def test_every_bad_argument_of_the_consensus(ctx):
+    rng = np.random.default_rng(61)
+    pile, call, ins_len, n_slots, ins, bases, offsets = random_rows(rng, [70, 0, 200], 16, with_slots=(0, 100, 269))
+    assert n_slots > 0
+    want, want_off = reference_consensus(pile, call, ins_len, ins, bases, offsets)
+    coff, cons = np.full(4, 99, np.uint64), np.full(bases.size + n_slots, 0xEE, np.uint8)
+    total = C.c_uint64(12345)
+    base = dict(pile=pile, call=call, ins_len=ins_len, n_slots=n_slots, ins=ins, bases=bases, offsets=offsets, flags=0, mem=A.MEM_HOST, coff=coff, cons=cons,
+                total=total)
+
+    def run(**kw):
+        a = dict(base, **kw)
+        p = A.ConsensusParams(a["flags"]) if a["flags"] is not None else None
+        return ctx.L.kmu_pile_consensus(ctx.h, _p(a["pile"]), _p(a["call"]), _p(a["ins_len"]), a["n_slots"], _p(a["ins"]), _p(a["bases"]), _p(a["offsets"]),
+                                        len(offsets) - 1, C.byref(p) if p is not None else None, a["mem"], _p(a["coff"]), _p(a["cons"]), cons.size,
+                                        C.byref(a["total"]) if a["total"] is not None else None)
+    bad = [dict(pile=None), dict(call=None), dict(ins_len=None), dict(bases=None), dict(offsets=None), dict(flags=None), dict(coff=None), dict(total=None),
+           dict(ins=None),                       # ins null with n_slots > 0
+           dict(flags=1), dict(flags=0x80000000), dict(mem=7), dict(mem=-1)]
+    for kw in bad:
+        assert run(**kw) == A.E_BAD_ARG, sorted(kw)
+        assert (coff == 99).all() and (cons == 0xEE).all() and total.value == 12345, sorted(kw)
+    assert run() == 0 and total.value == want.size and coff.tolist() == want_off.tolist() and cons[:want.size].tobytes() == want.tobytes()
+    # ins may be null where there are no slots
+    none = np.zeros_like(ins_len)
+    assert run(ins_len=none, n_slots=0, ins=None) == 0
+    assert cons[:total.value].tobytes() == reference_consensus(pile, call, none, ins[:0], bases, offsets)[0].tobytes()
+
+
+# ---- through the aligner ------------------------------------------------------------------------------------------------------------
+def edit_distance(a, b):
+    """Levenshtein distance of two uint8 arrays, a row at a time"""
+    a, b = np.asarray(a, np.int64), np.asarray(b, np.int64)
+    idx = np.arange(b.size + 1)
+    row = idx.copy()
+    for i in range(a.size):
+        new = np.empty_like(row)
+        new[0] = i + 1
+        new[1:] = np.minimum(row[1:] + 1, row[:-1] + (b != a[i]))
+        row = np.minimum.accumulate(new - idx) + idx
+    return int(row[-1])
+
+
+def test_planted_truth(ctx):
+    """12 mutated copies of one template of 600 bases (5 % substitutions, insertions and deletions), every second one
+    reverse-complemented, every pair chained whole: the device's corrected reads equal the references run on the device's own runs,
+    and they are closer to the template than the raw reads"""
+    rng = np.random.default_rng(70)
+    root = rng.choice(ACGT, 600).astype(np.uint8)
+    copies = [mutate(rng, root, 0.05)[0] for _ in range(12)]
+    reads = [revcomp(bytes(c).decode()) if r & 1 else bytes(c).decode() for r, c in enumerate(copies)]
+    bases, offsets = batch(reads)
+    chains = chain_recs([(r, q, (r ^ q) & 1, 0, len(reads[r]), 0, len(reads[q])) for r in range(12) for q in range(r + 1, 12)])
+    aln, ops, op_off = ctx.chain_cigar(chains, bases, offsets, band=64)
+    assert (aln["flags"] & A.ALN_PATH).all()
+    pile = ctx.chain_pileup(chains, aln, ops, op_off, bases, offsets)[0]
+    call, _ = ctx.pile_call(pile, bases, offsets, min_depth=3)
+    ins_len, n_slots = ctx.pile_ins_plan(pile, call, max_ins=16)
+    ins = ctx.chain_pile_ins(chains, aln, ops, op_off, bases, offsets, ins_len, n_slots)[0]
+    cons, coff = ctx.pile_consensus(pile, call, ins_len, n_slots, ins, bases, offsets)
+    want = reference_correct(chains, aln, ops, op_off, bases, offsets, min_depth=3, max_ins=16)
+    same(pile, want[2], "pile")
+    same(call, want[3], "call")
+    same(ins_len, want[4], "ins_len")
+    same(ins, want[5], "ins")
+    same(cons, want[0], "cons")
+    same(coff, want[1], "cons_offsets")
+    assert n_slots > 0 and ins.sum() > 0
+    template = {0: root, 1: np.frombuffer(revcomp(bytes(root).decode()).encode(), np.uint8)}
+    raw = sum(edit_distance(bases[int(offsets[r]):int(offsets[r + 1])], template[r & 1]) for r in range(12))
+    corrected = sum(edit_distance(cons[int(coff[r]):int(coff[r + 1])], template[r & 1]) for r in range(12))
+    print("summed edit distance to the template: raw %d, corrected %d" % (raw, corrected))
+    assert corrected < raw
+
+
+# ---- end to end -------------------------------------------------------------------------------------------------------------------
+def test_correct_reads_from_reads_to_corrected_reads(ctx):
+    """12 reads of one 3 kb sequence with 3 % edits, every second one reverse-complemented: correct_reads finds the chains itself; its
+    batch equals the step-by-step route; on resident arrays everything stays on the device and holds the same bytes"""
+    import torch
+    from kmerutils_amd import minimizer
+    rng = np.random.default_rng(19)
+    root = rng.choice(ACGT, 3000).astype(np.uint8)
+    reads = []
+    for r in range(12):
+        s = bytes(mutate(rng, root, 0.03)[0]).decode()
+        reads.append(revcomp(s) if r & 1 else s)
+    bases, offsets = batch(reads)
+    cons, coff, summary = minimizer.correct_reads(ctx, bases, offsets, 15, 10, min_depth=2, max_ins=8)
+    chains, aln, ops, op_off = minimizer.read_cigars(ctx, bases, offsets, 15, 10)
+    pile, _ = minimizer.pileup_chains(ctx, chains, aln, ops, op_off, bases, offsets)
+    call, want_summary = ctx.pile_call(pile, bases, offsets, min_depth=2)
+    ins_len, n_slots = ctx.pile_ins_plan(pile, call, max_ins=8)
+    ins, _ = minimizer.insertions_chains(ctx, chains, aln, ops, op_off, bases, offsets, ins_len, n_slots)
+    want = minimizer.consensus_reads(ctx, pile, call, ins_len, n_slots, ins, bases, offsets)
+    assert cons.tobytes() == want[0].tobytes() and coff.tolist() == want[1].tolist() and summary.tobytes() == want_summary.tobytes()
+    same(cons, reference_consensus(pile, call, ins_len, ins, bases, offsets)[0])
+    assert n_slots > 10 and cons.tobytes() != bases.tobytes() and coff.shape == (13,)
+    d = minimizer.correct_reads(ctx, torch.from_numpy(bases).cuda(), torch.from_numpy(offsets.astype(np.int64)).cuda(), 15, 10, min_depth=2, max_ins=8)
+    assert all(x.is_cuda for x in d)
+    assert [x.cpu().numpy().tobytes() for x in d] == [cons.tobytes(), coff.tobytes(), summary.tobytes()]
+    # the corrected batch goes straight back in
+    again = minimizer.read_minimizers(ctx, d[0], d[1], 15, 10)
+    assert again.offsets.shape[0] == 13
+
+
+def test_the_kernels_that_ran(ctx):
+    case = mixed_case(20, 10)
+    ctx.profile_enable(True)
+    ctx.profile_reset()
+    try:
+        check_route(ctx, case)
+        assert {"k_pile_count", "k_pile_starts", "k_ins_plan", "k_ins_blocks", "k_ins_vote", "k_cons_count", "k_cons_write", "k_cons_offsets"} <= set(ctx.profile_get())
+    finally:
+        ctx.profile_enable(False)
+        ctx.profile_reset()
