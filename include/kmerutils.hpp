@@ -31,6 +31,8 @@
  *                 ChainPileups, chain_pileup, pileup_chains, PileCalls, pile_call (per-base votes of the paths, calls per base and read)
  *                 InsPlan, pile_ins_plan, ChainInsertions, chain_pile_ins, ConsensusReads, pile_consensus, correct_chains, correct_reads
  *                 (the inserted letters and the corrected reads)
+ *                 PileSegments, pile_segments, extract_ranges, pile_consensus_pos, trim_reads, correct_trim_chains, correct_trim_reads
+ *                 (supported segments of every read, chimera splits and trimmed reads)
  *                 seed_chains, seed_pairs, chain_hits, read_chains (one base-resolution chain per read pair from minimizer
  *                                                            hits)                          (beyond the reference)
  *   counting      KmerCountT (trait), KmerCounter, KmerCounterPool, count_kmer_threaded_one_to_many
@@ -2237,6 +2239,155 @@ CorrectedReads correct_reads(const detail::Batch &batch, size_t k, uint32_t w, F
                              uint32_t min_depth = 3, uint32_t max_ins = 16, Context &ctx = Context::global()) {
     return correct_chains(read_chains<Kmer>(batch, k, w, fhash, max_occ, max_gap, band_chain, min_seeds, min_score, ctx), batch, band, min_depth,
                           max_ins, ctx);
+}
+
+// =====================================================================================================================
+// read trimming (kmu_pile_segments, kmu_extract_ranges, kmu_pile_consensus_pos; the reference has no such unit)
+// =====================================================================================================================
+
+/// What pile_segments returns: the kept segments in (read, start) order, the first listed segment of every read, and the summary
+/// of every read with its class KMU_TRIM_*.
+struct PileSegments {
+    std::vector<kmu_pile_seg> segs;
+    std::vector<uint64_t> seg_offsets;
+    std::vector<kmu_read_trim> reads;
+};
+
+/// kmu_pile_segments on host arrays: `table` is a table of chain_pileup for the batch with these offsets.  A segment is a maximal run
+/// of rows with depth >= min_depth in which consecutive rows are linked by a spanning depth >= min_span (0: depth only); segments of
+/// at least min_len rows are kept.  longest: list only the longest kept segment of every read.  Kept segments are disjoint and at
+/// least min_len long, so the output is sized by n_bases / min_len and the library is called once.
+inline PileSegments pile_segments(const std::vector<uint32_t> &table, const std::vector<uint64_t> &offsets, uint32_t min_depth = 3, uint32_t min_span = 3,
+                                  uint32_t min_len = 1, bool longest = false, Context &ctx = Context::global()) {
+    if (offsets.empty() || table.size() != size_t(offsets.back()) * KMU_PILE_COLS) throw std::invalid_argument("pile_segments: the table is not one of this batch");
+    PileSegments out;
+    const uint32_t n_reads = uint32_t(offsets.size() - 1);
+    const size_t n_bases = offsets.back(), by_len = n_bases / (min_len ? min_len : 1), cap = longest && n_reads < by_len ? n_reads : by_len;
+    out.seg_offsets.assign(size_t(n_reads) + 1, 0);
+    out.segs.resize(cap + 1);
+    out.reads.resize(n_reads);
+    kmu_pile_seg_params p{};
+    p.min_depth = min_depth;
+    p.min_span = min_span;
+    p.min_len = min_len;
+    p.flags = longest ? KMU_SEG_LONGEST : 0u;
+    uint32_t none = 0;
+    uint64_t total = 0;
+    ctx.check(kmu_pile_segments(ctx.raw(), table.empty() ? &none : table.data(), offsets.data(), n_reads, &p, KMU_MEM_HOST, out.seg_offsets.data(),
+                                out.segs.data(), cap, &total, out.reads.empty() ? nullptr : out.reads.data()));
+    out.segs.resize(total);
+    return out;
+}
+
+/// kmu_extract_ranges on host arrays: a new batch whose read i is bases[begin[i] .. end[i]), verbatim.  Ranges may be empty, overlap,
+/// repeat and come in any order; a range with begin > end or end > bases.size() is refused.
+inline ConsensusReads extract_ranges(const std::vector<uint8_t> &bases, const std::vector<uint64_t> &begin, const std::vector<uint64_t> &end,
+                                     Context &ctx = Context::global()) {
+    if (begin.size() != end.size()) throw std::invalid_argument("extract_ranges: as many ends as begins");
+    ConsensusReads out;
+    out.offsets.assign(begin.size() + 1, 0);
+    uint8_t none = 0;
+    uint64_t none_range = 0, total = 0;
+    const uint8_t *src = bases.empty() ? &none : bases.data();
+    const uint64_t *b = begin.empty() ? &none_range : begin.data(), *e = end.empty() ? &none_range : end.data();
+    ctx.check(kmu_extract_ranges(ctx.raw(), src, bases.size(), b, e, begin.size(), KMU_MEM_HOST, out.offsets.data(), nullptr, 0, &total));
+    out.bases.resize(total);
+    if (total)
+        ctx.check(kmu_extract_ranges(ctx.raw(), src, bases.size(), b, e, begin.size(), KMU_MEM_HOST, out.offsets.data(), out.bases.data(), total, &total));
+    return out;
+}
+
+/// kmu_pile_consensus_pos on host arrays: for every named row of the batch, the number of consensus bytes that the rows before it
+/// produce (rows[i] == n_bases: the total).  The inputs are those of pile_consensus; rows = the batch's offsets gives its offsets.
+inline std::vector<uint64_t> pile_consensus_pos(const std::vector<uint32_t> &table, const std::vector<uint8_t> &call, const InsPlan &plan,
+                                                const std::vector<uint32_t> &ins, const detail::Batch &batch, const std::vector<uint64_t> &rows,
+                                                Context &ctx = Context::global()) {
+    const detail::Batch b = detail::unpacked(batch);
+    if (b.on_device()) throw std::invalid_argument("pile_consensus_pos returns host arrays: it needs the sequences in host memory");
+    const size_t n_bases = b.offsets.back();
+    if (table.size() != n_bases * KMU_PILE_COLS || call.size() != n_bases || plan.ins_len.size() != n_bases || ins.size() != plan.n_slots * KMU_INS_COLS)
+        throw std::invalid_argument("pile_consensus_pos: the table, the calls, the plan or the slots are not of this batch");
+    std::vector<uint64_t> pos(rows.size(), 0);
+    kmu_consensus_params p{};
+    uint8_t none = 0;
+    ctx.check(kmu_pile_consensus_pos(ctx.raw(), table.empty() ? reinterpret_cast<const uint32_t *>(&none) : table.data(), call.empty() ? &none : call.data(),
+                                     plan.ins_len.empty() ? &none : plan.ins_len.data(), plan.n_slots, ins.empty() ? nullptr : ins.data(),
+                                     b.bytes.empty() ? &none : b.bytes.data(), b.offsets.data(), b.n(), &p, KMU_MEM_HOST, rows.empty() ? nullptr : rows.data(),
+                                     rows.size(), pos.empty() ? nullptr : pos.data()));
+    return pos;
+}
+
+/// What trim_reads returns: the trimmed (and split) reads as a new ASCII batch, the segments its reads are, and the summary of every
+/// input read.
+struct TrimmedReads {
+    ConsensusReads out;
+    std::vector<kmu_pile_seg> segs;
+    std::vector<kmu_read_trim> reads;
+};
+
+namespace detail {
+/// (first row, end row) of every segment in its batch
+inline void segment_rows(const std::vector<kmu_pile_seg> &segs, const std::vector<uint64_t> &offsets, std::vector<uint64_t> &first, std::vector<uint64_t> &last) {
+    for (const kmu_pile_seg &s : segs) {
+        first.push_back(offsets[s.read] + s.start);
+        last.push_back(offsets[s.read] + s.end);
+    }
+}
+} // namespace detail
+
+/// The reads of a batch cut down to their supported segments (minimizer.trim_reads): pile_segments on `table`, extract_ranges on the
+/// batch's bytes.  Every kept segment becomes a read: uncovered ends go, a chimera comes out as its parts.
+inline TrimmedReads trim_reads(const std::vector<uint32_t> &table, const detail::Batch &batch, uint32_t min_depth = 3, uint32_t min_span = 3,
+                               uint32_t min_len = 100, bool longest = false, Context &ctx = Context::global()) {
+    const detail::Batch b = detail::unpacked(batch);
+    if (b.on_device()) throw std::invalid_argument("trim_reads returns host arrays: it needs the sequences in host memory");
+    PileSegments s = pile_segments(table, b.offsets, min_depth, min_span, min_len, longest, ctx);
+    std::vector<uint64_t> first, last;
+    detail::segment_rows(s.segs, b.offsets, first, last);
+    return {extract_ranges(b.bytes, first, last, ctx), std::move(s.segs), std::move(s.reads)};
+}
+
+/// What correct_trim_reads returns: the corrected, trimmed and split reads, the segments (in raw read coordinates) they are, the
+/// summaries of pile_call and those of pile_segments.
+struct CorrectedTrimmedReads {
+    ConsensusReads out;
+    std::vector<kmu_pile_seg> segs;
+    std::vector<kmu_read_pile> reads;
+    std::vector<kmu_read_trim> trims;
+};
+
+/// correct_chains and trim_reads on one table: the consensus of every read, the segments of the same table, pile_consensus_pos of
+/// every segment's first row and end row, extract_ranges on the consensus batch.
+inline CorrectedTrimmedReads correct_trim_chains(const std::vector<kmu_chain> &chains, const detail::Batch &batch, uint32_t band = 64, uint32_t min_depth = 3,
+                                                 uint32_t max_ins = 16, uint32_t min_span = 3, uint32_t min_len = 100, bool longest = false,
+                                                 Context &ctx = Context::global()) {
+    const detail::Batch b = detail::unpacked(batch);
+    if (b.on_device()) throw std::invalid_argument("correct_trim_chains returns host arrays: it needs the sequences in host memory");
+    const ChainCigars cigars = chain_cigar(chains, batch, nullptr, band, 0, ctx);
+    const ChainPileups pile = chain_pileup(chains, cigars, batch, nullptr, KMU_PILE_Q | KMU_PILE_DB, {}, ctx);
+    PileCalls calls = pile_call(pile.q, batch, min_depth, ctx);
+    const InsPlan plan = pile_ins_plan(pile.q, calls.call, max_ins, ctx);
+    const ChainInsertions ins = chain_pile_ins(chains, cigars, batch, plan, nullptr, nullptr, KMU_PILE_Q | KMU_PILE_DB, {}, ctx);
+    const ConsensusReads cons = pile_consensus(pile.q, calls.call, plan, ins.q, batch, ctx);
+    PileSegments s = pile_segments(pile.q, b.offsets, min_depth, min_span, min_len, longest, ctx);
+    std::vector<uint64_t> rows, last;
+    detail::segment_rows(s.segs, b.offsets, rows, last);
+    const size_t n = rows.size();
+    rows.insert(rows.end(), last.begin(), last.end());
+    const std::vector<uint64_t> pos = pile_consensus_pos(pile.q, calls.call, plan, ins.q, batch, rows, ctx);
+    return {extract_ranges(cons.bases, std::vector<uint64_t>(pos.begin(), pos.begin() + n), std::vector<uint64_t>(pos.begin() + n, pos.end()), ctx),
+            std::move(s.segs), std::move(calls.reads), std::move(s.reads)};
+}
+
+/// From the reads of a batch to their corrected and trimmed versions (minimizer.correct_trim_reads): read_chains, then
+/// correct_trim_chains.
+template <class Kmer>
+CorrectedTrimmedReads correct_trim_reads(const detail::Batch &batch, size_t k, uint32_t w, FHash fhash = FHash::canon_invhash, uint32_t max_occ = 0,
+                                         uint32_t max_gap = 5000, uint32_t band_chain = 500, uint32_t min_seeds = 3, uint32_t min_score = 0,
+                                         uint32_t band = 64, uint32_t min_depth = 3, uint32_t max_ins = 16, uint32_t min_span = 3, uint32_t min_len = 100,
+                                         bool longest = false, Context &ctx = Context::global()) {
+    return correct_trim_chains(read_chains<Kmer>(batch, k, w, fhash, max_occ, max_gap, band_chain, min_seeds, min_score, ctx), batch, band, min_depth,
+                               max_ins, min_span, min_len, longest, ctx);
 }
 
 // =====================================================================================================================

@@ -1206,6 +1206,96 @@ int kmu_pile_consensus(kmu_ctx *ctx, const uint32_t *pile, const uint8_t *call, 
                        const kmu_consensus_params *p, int mem,
                        uint64_t *cons_offsets_out, uint8_t *cons_out, uint64_t cap, uint64_t *n_cons_out);
 
+/* ---- read trimming: supported segments of every read, byte ranges as a new batch, raw rows in corrected coordinates -----------
+ * kmu_pile_segments.  pile: the table of one batch (offsets, n_reads) as kmu_chain_pileup left it.  Per row g,
+ *   depth(g) = A + C + G + T + DEL and ends(g) = ENDS, both taken in 64 bits (A = 2^32 - 1, C = 1 is depth 2^32, not 0);
+ *   good(g) <=> depth(g) >= min_depth; span(g) = max(depth(g) - ends(g), 0).
+ *   Link: for two consecutive rows g - 1 and g of ONE read, link(g) holds iff both are good and
+ *   max(span(g), span(g - 1)) >= min_span.  min_span == 0 links every good pair.
+ *   Why: the partners that cover both g - 1 and g number exactly depth(g) - begins_at(g) = depth(g - 1) - ends_at(g - 1).  ENDS holds
+ *   begins + ends, so depth - ENDS is a lower bound of that spanning depth which needs nothing but the table, and the larger of the
+ *   two bounds is still one.  At a chimeric join the alignments of the left parent end at g - 1 and those of the right parent begin
+ *   at g: the bound is 0 there although both rows are deep.
+ *   Segment: a maximal run of rows of one read in which consecutive rows are linked; it never crosses a read boundary, even when the
+ *   last row of one read and the first row of the next are both good.  Segments with end - start >= min_len are KEPT.
+ *   segs_out: the kept segments in (read, start) order, [start, end) in read coordinates, rank counting the kept segments of the
+ *   read from 0.  seg_offsets_out (n_reads + 1 entries): the first listed segment of every read.  With KMU_SEG_LONGEST only the
+ *   longest kept segment of each read is listed, the leftmost among equals, with the rank it has among the read's kept segments.
+ *   reads_out[r] does not depend on that flag.
+ *   Counting and capacity: *n_segs_out (host memory in both modes) is always the number of listed segments.  segs_out == NULL: the
+ *   count-only call -- offsets and summaries are written all the same.  cap < total: KMU_E_BAD_ARG with *n_segs_out set, the offsets
+ *   and the summaries written; segs_out is not written.  Kept segments are disjoint and at least min_len long: total <= n_bases /
+ *   min_len (and <= n_reads with KMU_SEG_LONGEST), so a caller can size segs_out without a count call.  (Two kept segments may touch
+ *   -- a flush join -- so no bound divides by min_len + 1.)
+ *   Either of seg_offsets_out and reads_out may be NULL, not both together with segs_out.  n_reads == 0: KMU_OK, one offset (0).
+ *   KMU_E_BAD_ARG, nothing is written: null ctx / pile / offsets / p / n_segs_out, no output at all, min_depth 0, min_len 0, unknown
+ *   flag bits, bad mem.  KMU_MEM_DEVICE: every array except p and n_segs_out is device memory, pile 16-byte aligned; the call
+ *   synchronises the stream three times (the batch's size; the number of runs; the total) and once more behind the copy of the
+ *   segments.  KMU_MEM_HOST: through the context's workspace.
+ *   The result is a pure function of the input: integer compares and integer sums only; the launch shape and timing change nothing.
+ *   How: a bitmap marks the first row of every read.  Tiles are 1024 consecutive rows of the batch, not reads; a wave takes a tile 64
+ *   rows at a time, gets the row before each lane's by a wave shift, and compacts run starts and run ends separately by ballot and
+ *   prefix count (count pass, scan, write pass); the k-th start and the k-th end are one run.  One lane per run finds its read, adds
+ *   its length to the read's n_good and marks it kept; two scans place the kept runs; one lane per read makes the summary.
+ *   DESIGN.md 3.20 has the kernels.
+ *
+ * kmu_extract_ranges.  Output read i is bases[begin[i] .. end[i]), verbatim; out_offsets has n_ranges + 1 entries.  Ranges may be
+ *   empty, overlap, repeat and come in any order.  *n_out (host memory in both modes) is always the total; out == NULL: the
+ *   count-only call, the offsets are written; cap < total: KMU_E_BAD_ARG with *n_out set and the offsets written, out not written.
+ *   n_ranges == 0: KMU_OK, one offset (0).  KMU_E_BAD_ARG: null ctx / out_offsets / n_out, bases null with n_bases > 0, begin or end
+ *   null with n_ranges > 0, bad mem.  KMU_E_UNSUPPORTED, found on the device BEFORE anything is written (out and out_offsets stay
+ *   untouched): any begin[i] > end[i] or end[i] > n_bases.  No range is ever used as an address before the check.
+ *   KMU_MEM_DEVICE: every array except n_out is device memory; two synchronisations (the check with the total; the end).
+ *   How: tiles are 4096 OUTPUT bytes.  A wave finds the range of its tile's first byte by a 64-ary search over out_offsets that takes
+ *   the largest range, so empty ranges are skipped, and walks on 64 bytes at a time: the next 64 offsets sit one per lane, and every
+ *   lane finds its own range among them with six wave shuffles.  One long range spreads over many waves; thousands of one-byte ranges
+ *   share one wave.  Byte loads and stores.
+ *
+ * kmu_pile_consensus_pos.  The inputs of kmu_pile_consensus.  pos_out[i] (n_rows entries, where the arrays live) is the number of
+ *   consensus bytes that the rows before row rows[i] of the batch produce; rows[i] == n_bases gives the total.  Hence rows = offsets
+ *   reproduces cons_offsets_out of kmu_pile_consensus exactly, and read r's raw position x lands at pos(offsets[r] + x) -
+ *   pos(offsets[r]) of the corrected read.  n_rows == 0: KMU_OK.  KMU_E_BAD_ARG: what kmu_pile_consensus refuses so of its inputs;
+ *   rows or pos_out null with n_rows > 0.  KMU_E_UNSUPPORTED, before any output: the sum of ins_len is not n_slots; any rows[i] >
+ *   n_bases.  How: the count pass and the scan of kmu_pile_consensus, then one lane per query adds the at most 63 row lengths before
+ *   its row inside its tile -- the device function that makes the read offsets of kmu_pile_consensus. */
+#define KMU_SEG_LONGEST 1u         /* flags: list only the longest kept segment of every read */
+#define KMU_TRIM_WHOLE 0u          /* cls: one kept segment equal to the whole read */
+#define KMU_TRIM_ENDS 1u           /* one kept segment, shorter than the read */
+#define KMU_TRIM_SPLIT 2u          /* two or more kept segments */
+#define KMU_TRIM_NONE 3u           /* no kept segment; an empty read */
+typedef struct kmu_pile_seg_params {
+    uint32_t min_depth;  /* >= 1 */
+    uint32_t min_span;   /* 0: depth only */
+    uint32_t min_len;    /* >= 1 */
+    uint32_t flags;      /* KMU_SEG_LONGEST or 0 */
+} kmu_pile_seg_params;
+typedef struct {         /* 16 bytes */
+    uint32_t read;
+    uint32_t start;      /* [start, end) in read coordinates */
+    uint32_t end;
+    uint32_t rank;       /* among the read's kept segments, from 0 */
+} kmu_pile_seg;
+typedef struct {         /* 32 bytes */
+    uint32_t n_bases;    /* rows of the read */
+    uint32_t n_good;     /* rows with depth >= min_depth */
+    uint32_t n_segs;     /* kept segments */
+    uint32_t kept;       /* their summed length */
+    uint32_t best_start; /* the longest kept segment, the leftmost among equals; 0, 0 if none */
+    uint32_t best_end;
+    uint32_t inner_bad;  /* (end of the last kept - start of the first kept) - kept */
+    uint32_t cls;        /* KMU_TRIM_* */
+} kmu_read_trim;
+int kmu_pile_segments(kmu_ctx *ctx, const uint32_t *pile, const uint64_t *offsets, uint32_t n_reads,
+                      const kmu_pile_seg_params *p, int mem,
+                      uint64_t *seg_offsets_out, kmu_pile_seg *segs_out, uint64_t cap, uint64_t *n_segs_out,
+                      kmu_read_trim *reads_out);
+int kmu_extract_ranges(kmu_ctx *ctx, const uint8_t *bases, uint64_t n_bases, const uint64_t *begin, const uint64_t *end,
+                       uint64_t n_ranges, int mem, uint64_t *out_offsets, uint8_t *out, uint64_t cap, uint64_t *n_out);
+int kmu_pile_consensus_pos(kmu_ctx *ctx, const uint32_t *pile, const uint8_t *call, const uint8_t *ins_len, uint64_t n_slots,
+                           const uint32_t *ins, const uint8_t *bases, const uint64_t *offsets, uint32_t n_reads,
+                           const kmu_consensus_params *p, int mem,
+                           const uint64_t *rows, uint64_t n_rows, uint64_t *pos_out);
+
 #ifdef __cplusplus
 }
 #endif

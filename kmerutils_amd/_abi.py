@@ -45,6 +45,8 @@ PILE_Q, PILE_DB = 1, 2   # ... and its flags: vote onto the A side, onto the B s
 CALL_NONE, CALL_INS, CALL_DIFF = 7, 8, 16  # kmu_pile_call: bits 0..2 of an uncalled base, and the two bits above the code
 INS_COLS = 4             # kmu_chain_pile_ins: uint32 per insertion slot, one count per letter A C G T
 INS_MAX = 255            # kmu_pile_ins_plan: the most slots a base can get
+SEG_LONGEST = 1          # kmu_pile_segments flags: list only the longest kept segment of every read
+TRIM_WHOLE, TRIM_ENDS, TRIM_SPLIT, TRIM_NONE = 0, 1, 2, 3   # kmu_read_trim.cls
 
 
 def kmer_val_bytes(kmer_type):
@@ -179,6 +181,27 @@ class InsPlanParams(C.Structure):
 class ConsensusParams(C.Structure):
     """kmu_consensus_params: kmu_pile_consensus has no options yet"""
     _fields_ = [("flags", C.c_uint32)]
+
+
+class PileSegParams(C.Structure):
+    """kmu_pile_seg_params: the depth, the spanning depth and the length from which kmu_pile_segments keeps a segment"""
+    _fields_ = [("min_depth", C.c_uint32), ("min_span", C.c_uint32), ("min_len", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class PileSeg(C.Structure):
+    """kmu_pile_seg: one kept segment, [start, end) in read coordinates"""
+    _fields_ = [("read", C.c_uint32), ("start", C.c_uint32), ("end", C.c_uint32), ("rank", C.c_uint32)]
+
+
+class ReadTrim(C.Structure):
+    """kmu_read_trim: the summary of one read's kept segments (kmu_pile_segments)"""
+    _fields_ = [("n_bases", C.c_uint32), ("n_good", C.c_uint32), ("n_segs", C.c_uint32), ("kept", C.c_uint32), ("best_start", C.c_uint32),
+                ("best_end", C.c_uint32), ("inner_bad", C.c_uint32), ("cls", C.c_uint32)]
+
+
+PILE_SEG_DTYPE = [("read", "<u4"), ("start", "<u4"), ("end", "<u4"), ("rank", "<u4")]
+READ_TRIM_DTYPE = [("n_bases", "<u4"), ("n_good", "<u4"), ("n_segs", "<u4"), ("kept", "<u4"), ("best_start", "<u4"), ("best_end", "<u4"),
+                   ("inner_bad", "<u4"), ("cls", "<u4")]
 
 
 class ReadPile(C.Structure):

@@ -10,6 +10,8 @@
 //  k_cons_write    the same walk with the wave's prefix sum of the row lengths: every lane stores its row's bytes.
 //  k_cons_offsets  one lane per read (and one for the end): cons_offsets[r] is the offset of the tile that holds offsets[r] plus the
 //                  lengths of the at most 63 rows before it in that tile.
+//  k_cons_pos      (kmu_pile_consensus_pos) the same step, cons_pos_at, for rows a caller names: one lane per query, after
+//                  k_cons_pos_check has refused a row above n_rows.
 #include "kmu_ctx.hpp"
 #include "kmu_device.h"
 #include "kmu_cons_core.h"
@@ -63,17 +65,37 @@ template <bool WRITE> __global__ void __launch_bounds__(256) k_cons_tiles(ConsAr
     }
 }
 
+// the consensus bytes that the rows before row g0 produce: the offset of the tile that holds g0 plus the lengths of the at most 63 rows
+// before it in that tile (g0 <= n_rows; t == n_tiles where g0 == n_rows is a multiple of 64: the totals)
+__device__ __forceinline__ uint64_t cons_pos_at(const ConsArgs &p, uint64_t g0) {
+    const uint64_t t = g0 / CONS_BLOCK;
+    uint64_t at = p.tile_off[t], slot = p.slot_off[t];
+    for (uint64_t g = t * CONS_BLOCK; g < g0; g++) {
+        at += cons_row_at(p, g, slot, nullptr);
+        slot += p.ins_len[g];
+    }
+    return at;
+}
+
 __global__ void __launch_bounds__(256) k_cons_offsets(ConsArgs p) {
     for (uint64_t r = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x; r <= p.n_reads; r += (uint64_t) gridDim.x * blockDim.x) {
         uint64_t g0 = p.off[r];
         if (g0 > p.n_rows) g0 = p.n_rows; // (offsets that do not ascend to n_rows are the caller's fault; no row beyond is looked at)
-        const uint64_t t = g0 / CONS_BLOCK;
-        uint64_t at = p.tile_off[t], slot = p.slot_off[t]; // (t == n_tiles where g0 == n_rows is a multiple of 64: the totals)
-        for (uint64_t g = t * CONS_BLOCK; g < g0; g++) {
-            at += cons_row_at(p, g, slot, nullptr);
-            slot += p.ins_len[g];
-        }
-        p.cons_off[r] = at;
+        p.cons_off[r] = cons_pos_at(p, g0);
+    }
+}
+
+// kmu_pile_consensus_pos: a query row above n_rows raises info[0], before any output
+__global__ void __launch_bounds__(256) k_cons_pos_check(const uint64_t *rows, uint64_t n, uint64_t n_rows, uint32_t *info) {
+    bool bad = false;
+    for (uint64_t i = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t) gridDim.x * blockDim.x) bad |= rows[i] > n_rows;
+    if (bad) info[0] = 1u;
+}
+// ... one lane per query
+__global__ void __launch_bounds__(256) k_cons_pos(ConsArgs p, const uint64_t *rows, uint64_t n, uint64_t *pos) {
+    for (uint64_t i = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t) gridDim.x * blockDim.x) {
+        const uint64_t g0 = rows[i];
+        pos[i] = cons_pos_at(p, g0 < p.n_rows ? g0 : p.n_rows); // (the check has refused a row above n_rows)
     }
 }
 
@@ -81,15 +103,12 @@ __global__ void __launch_bounds__(256) k_cons_offsets(ConsArgs p) {
 
 using namespace kmu;
 
-extern "C" int kmu_pile_consensus(kmu_ctx *ctx, const uint32_t *pile, const uint8_t *call, const uint8_t *ins_len, uint64_t n_slots, const uint32_t *ins,
-                                  const uint8_t *bases, const uint64_t *offsets, uint32_t n_reads, const kmu_consensus_params *p, int mem,
-                                  uint64_t *cons_offsets_out, uint8_t *cons_out, uint64_t cap, uint64_t *n_cons_out) {
-    if (!ctx || !pile || !call || !ins_len || !bases || !offsets || !p || !cons_offsets_out || !n_cons_out) return fail(ctx, KMU_E_BAD_ARG, "null argument");
-    if (!ins && n_slots) return fail(ctx, KMU_E_BAD_ARG, "ins is null with n_slots = %llu", (unsigned long long) n_slots);
-    if (p->flags) return fail(ctx, KMU_E_BAD_ARG, "unknown flag bits 0x%x", p->flags);
-    if (mem != KMU_MEM_HOST && mem != KMU_MEM_DEVICE) return fail(ctx, KMU_E_BAD_ARG, "bad mem %d", mem);
-    *n_cons_out = 0;
+// the inputs on the device, the slot index with the refusal of an ins_len that does not belong to n_slots (before any output), the
+// count pass and the tile offsets: what kmu_pile_consensus and kmu_pile_consensus_pos share
+static int cons_plan(kmu_ctx *ctx, const uint32_t *pile, const uint8_t *call, const uint8_t *ins_len, uint64_t n_slots, const uint32_t *ins,
+                     const uint8_t *bases, const uint64_t *offsets, uint32_t n_reads, int mem, ConsArgs *out, uint64_t **tile_off_out) {
     KMU_HIP(ctx, hipSetDevice(ctx->device));
+    ConsArgs a{};
     uint64_t n_rows = 0;
     if (mem == KMU_MEM_HOST) n_rows = offsets[n_reads];
     else {
@@ -97,7 +116,6 @@ extern "C" int kmu_pile_consensus(kmu_ctx *ctx, const uint32_t *pile, const uint
         KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
     }
 
-    ConsArgs a{};
     const void *d;
     KMU_TRY(stage_to_device(ctx, "cons.pile", pile, (size_t) n_rows * PILE_COLS * 4, mem, &d));
     a.pile = (const uint32_t *) d;
@@ -127,7 +145,7 @@ extern "C" int kmu_pile_consensus(kmu_ctx *ctx, const uint32_t *pile, const uint
         return fail(ctx, KMU_E_UNSUPPORTED, "ins_len sums to %llu slots, not to n_slots = %llu", (unsigned long long) total_slots, (unsigned long long) n_slots);
     }
 
-    uint64_t *tile_off, total = 0;
+    uint64_t *tile_off;
     KMU_TRY(dev_array(ctx, "cons.tilelen", a.n_tiles ? a.n_tiles : 1, &a.tile_len));
     KMU_TRY(dev_array(ctx, "cons.tileoff", a.n_tiles + 1, &tile_off));
     a.tile_off = tile_off;
@@ -138,6 +156,23 @@ extern "C" int kmu_pile_consensus(kmu_ctx *ctx, const uint32_t *pile, const uint
     } else {
         KMU_HIP(ctx, hipMemsetAsync(tile_off, 0, 8, ctx->stream));
     }
+    *out = a;
+    *tile_off_out = tile_off;
+    return KMU_OK;
+}
+
+extern "C" int kmu_pile_consensus(kmu_ctx *ctx, const uint32_t *pile, const uint8_t *call, const uint8_t *ins_len, uint64_t n_slots, const uint32_t *ins,
+                                  const uint8_t *bases, const uint64_t *offsets, uint32_t n_reads, const kmu_consensus_params *p, int mem,
+                                  uint64_t *cons_offsets_out, uint8_t *cons_out, uint64_t cap, uint64_t *n_cons_out) {
+    if (!ctx || !pile || !call || !ins_len || !bases || !offsets || !p || !cons_offsets_out || !n_cons_out) return fail(ctx, KMU_E_BAD_ARG, "null argument");
+    if (!ins && n_slots) return fail(ctx, KMU_E_BAD_ARG, "ins is null with n_slots = %llu", (unsigned long long) n_slots);
+    if (p->flags) return fail(ctx, KMU_E_BAD_ARG, "unknown flag bits 0x%x", p->flags);
+    if (mem != KMU_MEM_HOST && mem != KMU_MEM_DEVICE) return fail(ctx, KMU_E_BAD_ARG, "bad mem %d", mem);
+    *n_cons_out = 0;
+    ConsArgs a{};
+    uint64_t *tile_off, total = 0;
+    KMU_TRY(cons_plan(ctx, pile, call, ins_len, n_slots, ins, bases, offsets, n_reads, mem, &a, &tile_off));
+    const dim3 grid(grid_for(ctx, a.n_tiles, 4));
     a.cons_off = cons_offsets_out;
     if (mem == KMU_MEM_HOST) KMU_TRY(dev_array(ctx, "cons.consoff", (size_t) n_reads + 1, &a.cons_off));
     KMU_TRY(launch(ctx, "k_cons_offsets", k_cons_offsets, dim3(grid_for(ctx, (uint64_t) n_reads + 1, 256)), dim3(256), 0, a));
@@ -158,6 +193,42 @@ extern "C" int kmu_pile_consensus(kmu_ctx *ctx, const uint32_t *pile, const uint
         if (mem == KMU_MEM_HOST) KMU_HIP(ctx, hipMemcpyAsync(cons_out, a.cons, total, hipMemcpyDeviceToHost, ctx->stream));
         KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
     }
+    if (ctx->profiling) profile_collect(ctx);
+    return KMU_OK;
+}
+
+extern "C" int kmu_pile_consensus_pos(kmu_ctx *ctx, const uint32_t *pile, const uint8_t *call, const uint8_t *ins_len, uint64_t n_slots, const uint32_t *ins,
+                                      const uint8_t *bases, const uint64_t *offsets, uint32_t n_reads, const kmu_consensus_params *p, int mem,
+                                      const uint64_t *rows, uint64_t n_rows_q, uint64_t *pos_out) {
+    if (!ctx || !pile || !call || !ins_len || !bases || !offsets || !p || (n_rows_q && (!rows || !pos_out))) return fail(ctx, KMU_E_BAD_ARG, "null argument");
+    if (!ins && n_slots) return fail(ctx, KMU_E_BAD_ARG, "ins is null with n_slots = %llu", (unsigned long long) n_slots);
+    if (p->flags) return fail(ctx, KMU_E_BAD_ARG, "unknown flag bits 0x%x", p->flags);
+    if (mem != KMU_MEM_HOST && mem != KMU_MEM_DEVICE) return fail(ctx, KMU_E_BAD_ARG, "bad mem %d", mem);
+    ConsArgs a{};
+    uint64_t *tile_off;
+    KMU_TRY(cons_plan(ctx, pile, call, ins_len, n_slots, ins, bases, offsets, n_reads, mem, &a, &tile_off));
+    if (n_rows_q == 0) {
+        if (ctx->profiling) profile_collect(ctx);
+        return KMU_OK;
+    }
+    const void *d;
+    KMU_TRY(stage_to_device(ctx, "cons.rows", rows, (size_t) n_rows_q * 8, mem, &d));
+    uint32_t *info, h_info = 0;
+    KMU_TRY(dev_array(ctx, "cons.info", 1, &info));
+    KMU_HIP(ctx, hipMemsetAsync(info, 0, 4, ctx->stream));
+    const dim3 grid(grid_for(ctx, n_rows_q, 256));
+    KMU_TRY(launch(ctx, "k_cons_pos_check", k_cons_pos_check, grid, dim3(256), 0, (const uint64_t *) d, n_rows_q, a.n_rows, info));
+    KMU_HIP(ctx, hipMemcpyAsync(&h_info, info, 4, hipMemcpyDeviceToHost, ctx->stream));
+    KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (h_info) {
+        if (ctx->profiling) profile_collect(ctx);
+        return fail(ctx, KMU_E_UNSUPPORTED, "a query row above n_bases = %llu", (unsigned long long) a.n_rows);
+    }
+    uint64_t *pos = pos_out;
+    if (mem == KMU_MEM_HOST) KMU_TRY(dev_array(ctx, "cons.pos", (size_t) n_rows_q, &pos));
+    KMU_TRY(launch(ctx, "k_cons_pos", k_cons_pos, grid, dim3(256), 0, a, (const uint64_t *) d, n_rows_q, pos));
+    if (mem == KMU_MEM_HOST) KMU_HIP(ctx, hipMemcpyAsync(pos_out, pos, (size_t) n_rows_q * 8, hipMemcpyDeviceToHost, ctx->stream));
+    KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
     if (ctx->profiling) profile_collect(ctx);
     return KMU_OK;
 }

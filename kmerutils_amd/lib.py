@@ -38,6 +38,7 @@ SYMBOLS = [
     "kmu_anchor_index_occupancy", "kmu_anchor_index_match", "kmu_components", "kmu_components_knn",
     "kmu_minimizer_layout", "kmu_read_minimizers", "kmu_seed_chains", "kmu_chain_align",
     "kmu_chain_cigar", "kmu_chain_pileup", "kmu_pile_call", "kmu_pile_ins_plan", "kmu_chain_pile_ins", "kmu_pile_consensus",
+    "kmu_pile_segments", "kmu_extract_ranges", "kmu_pile_consensus_pos",
 ]
 
 
@@ -157,6 +158,10 @@ def load():
                                      C.POINTER(A.PileupParams), C.c_int, vp, C.c_uint64, vp, vp, C.c_uint64, vp]
     L.kmu_pile_consensus.argtypes = [vp, vp, vp, vp, C.c_uint64, vp, vp, vp, C.c_uint32, C.POINTER(A.ConsensusParams), C.c_int, vp, vp,
                                      C.c_uint64, C.POINTER(C.c_uint64)]
+    L.kmu_pile_segments.argtypes = [vp, vp, vp, C.c_uint32, C.POINTER(A.PileSegParams), C.c_int, vp, vp, C.c_uint64, C.POINTER(C.c_uint64), vp]
+    L.kmu_extract_ranges.argtypes = [vp, vp, C.c_uint64, vp, vp, C.c_uint64, C.c_int, vp, vp, C.c_uint64, C.POINTER(C.c_uint64)]
+    L.kmu_pile_consensus_pos.argtypes = [vp, vp, vp, vp, C.c_uint64, vp, vp, vp, C.c_uint32, C.POINTER(A.ConsensusParams), C.c_int, vp,
+                                         C.c_uint64, vp]
     L.kmu_set_hll_params.argtypes = [vp, C.POINTER(A.HllParams)]
     L.kmu_kmer_hashes_compact.argtypes = [vp, C.POINTER(A.HashParams), vp, vp, vp, C.c_uint32, vp, C.c_uint64, u64p]
     L.kmu_sketch_partial_words.argtypes = [C.POINTER(A.SketchParams)]
@@ -1195,6 +1200,88 @@ class Context:
         self._check(self.L.kmu_pile_consensus(self.h, ptr(pile), ptr(call), ptr(ins_len), n_slots, ptr(ins), ptr(bases), _ptr(off)[0], n_reads,
                                               C.byref(p), mem, _ptr(cons_off)[0], _ptr(cons)[0], cap, C.byref(total)))
         return cons[:int(total.value)], cons_off
+
+    def pile_segments(self, pile, offsets, min_depth=3, min_span=None, min_len=1, longest=False):
+        """kmu_pile_segments: the supported segments of every read of a batch from its table (chain_pileup) -- maximal runs of rows
+        with depth >= min_depth in which consecutive rows are linked (max(depth - ENDS) of the two >= min_span; None: min_depth; 0:
+        depth only), kept from min_len rows on -- and a summary with a class A.TRIM_* per read.  Returns (segs, seg_offsets, reads):
+        A.PILE_SEG_DTYPE records in (read, start) order, uint64 [n_reads + 1], and A.READ_TRIM_DTYPE records; for torch int32
+        tensors [n, 4] and [n_reads, 8] and int64 offsets holding the same bits.  longest=True lists only the longest kept segment
+        of every read.  Kept segments are disjoint and at least min_len long, so the output is sized by n_bases // min_len and the
+        library is called once."""
+        mem = self._mem(pile)
+        off = self._offsets_like(offsets, pile, mem)
+        n_reads = int(off.shape[0]) - 1
+        n_bases = int(off[-1])
+        if int(pile.shape[0]) != n_bases:
+            raise ValueError("the batch has %d bases: the table must have as many rows" % n_bases)
+        min_span = int(min_depth if min_span is None else min_span)
+        cap = min(n_bases // max(int(min_len), 1), n_reads if longest else n_bases)
+        seg_off = self._new_like(pile, n_reads + 1, np.uint64, "int64")
+        if mem == A.MEM_DEVICE:
+            segs = self._new_like(pile, (max(cap, 1), 4), np.int32, "int32")
+            reads = self._new_like(pile, (max(n_reads, 1), 8), np.int32, "int32")
+        else:
+            segs = np.zeros(max(cap, 1), np.dtype(A.PILE_SEG_DTYPE))
+            reads = np.zeros(max(n_reads, 1), np.dtype(A.READ_TRIM_DTYPE))
+        p = A.PileSegParams(int(min_depth), min_span, int(min_len), A.SEG_LONGEST if longest else 0)
+        none = self._new_like(pile, 16, np.uint8, "uint8")  # an empty array has no address worth passing
+        total = C.c_uint64(0)
+        self._check(self.L.kmu_pile_segments(self.h, _ptr(pile if n_bases else none)[0], _ptr(off)[0], n_reads, C.byref(p), mem,
+                                             _ptr(seg_off)[0], _ptr(segs)[0], cap, C.byref(total), _ptr(reads)[0]))
+        return segs[:int(total.value)], seg_off, reads[:n_reads]
+
+    def extract_ranges(self, bases, begin, end):
+        """kmu_extract_ranges: a new batch whose read i is bases[begin[i]:end[i]], verbatim.  Ranges may be empty, overlap, repeat
+        and come in any order; a range with begin > end or end > len(bases) is refused (KmuError, A.E_UNSUPPORTED).  Returns
+        (out_bases, out_offsets): uint8 and uint64 [n_ranges + 1] (int64 holding the same bits for torch), where the arrays
+        live.  The library is called twice: for the total, then for the bytes."""
+        mem = self._mem(bases, begin, end)
+        n = int(begin.shape[0])
+        if int(end.shape[0]) != n:
+            raise ValueError("%d begins need as many ends" % n)
+        if not _is_torch(begin):
+            begin, end = (np.ascontiguousarray(np.asarray(x).astype(np.uint64)) for x in (begin, end))
+        n_bases = int(bases.shape[0])
+        out_off = self._new_like(bases, n + 1, np.uint64, "int64")
+        none = self._new_like(bases, 16, np.uint8, "uint8")  # an empty array has no address worth passing
+
+        def ptr(x):
+            return _ptr(x)[0] if int(x.shape[0]) else _ptr(none)[0]
+        total = C.c_uint64(0)
+        self._check(self.L.kmu_extract_ranges(self.h, ptr(bases), n_bases, ptr(begin), ptr(end), n, mem, _ptr(out_off)[0], None, 0, C.byref(total)))
+        cap = int(total.value)
+        out = self._new_like(bases, max(cap, 1), np.uint8, "uint8")
+        if cap:
+            self._check(self.L.kmu_extract_ranges(self.h, ptr(bases), n_bases, ptr(begin), ptr(end), n, mem, _ptr(out_off)[0], _ptr(out)[0], cap,
+                                                  C.byref(total)))
+        return out[:cap], out_off
+
+    def pile_consensus_pos(self, pile, call, ins_len, n_slots, ins, bases, offsets, rows):
+        """kmu_pile_consensus_pos: where raw rows land in the corrected batch -- pos[i] is the number of consensus bytes that the
+        rows before row rows[i] of the batch produce (rows[i] == n_bases: the total), from the inputs of pile_consensus.  rows =
+        offsets gives the cons_offsets of pile_consensus.  Returns pos: uint64 like rows (int64 for torch), where the arrays live."""
+        mem = self._mem(pile, call, ins_len, ins, bases, rows)
+        off = self._offsets_like(offsets, pile, mem)
+        n_reads = int(off.shape[0]) - 1
+        n_bases = int(off[-1])
+        if any(int(x.shape[0]) != n_bases for x in (pile, call, ins_len, bases)):
+            raise ValueError("the batch has %d bases: the table, call, ins_len and the bases must have as many rows" % n_bases)
+        n_slots = int(n_slots)
+        if int(ins.shape[0]) != n_slots:
+            raise ValueError("ins has %d slots, not n_slots = %d" % (int(ins.shape[0]), n_slots))
+        if not _is_torch(rows):
+            rows = np.ascontiguousarray(np.asarray(rows).astype(np.uint64))
+        n = int(rows.shape[0])
+        pos = self._new_like(pile, max(n, 1), np.uint64, "int64")
+        p = A.ConsensusParams(0)
+        none = self._new_like(pile, 16, np.uint8, "uint8")  # an empty array has no address worth passing
+
+        def ptr(x):
+            return _ptr(x)[0] if int(x.shape[0]) else _ptr(none)[0]
+        self._check(self.L.kmu_pile_consensus_pos(self.h, ptr(pile), ptr(call), ptr(ins_len), n_slots, ptr(ins), ptr(bases), _ptr(off)[0], n_reads,
+                                                  C.byref(p), mem, ptr(rows), n, _ptr(pos)[0]))
+        return pos[:n]
 
     def _components(self, call, like, n_nodes, want, count):
         """the outputs of kmu_components / kmu_components_knn allocated where `like` lives, call(*output pointers) run on them,

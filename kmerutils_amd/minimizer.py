@@ -191,6 +191,62 @@ def correct_reads(ctx, bases, offsets, k, w, fhash=A.FHASH_CANON_INVHASH, max_oc
     return cons_bases, cons_offsets, reads
 
 
+def _segment_rows(segs, offsets):
+    """(first row, end row) of every segment in its batch: offsets[read] + start / end, where the segments live (int64 for torch,
+    uint64 for numpy)"""
+    if _is_torch(segs):
+        off = offsets.long() if _is_torch(offsets) else None
+        if off is None or off.device != segs.device:
+            import torch
+            off = torch.from_numpy(np.asarray(offsets.cpu() if _is_torch(offsets) else offsets).astype(np.int64)).to(segs.device)
+        s = segs.long() & 0xFFFFFFFF
+        beg = off[s[:, 0]]
+        return (beg + s[:, 1]).contiguous(), (beg + s[:, 2]).contiguous()
+    beg = np.asarray(offsets).astype(np.uint64)[segs["read"]]
+    return beg + segs["start"].astype(np.uint64), beg + segs["end"].astype(np.uint64)
+
+
+def trim_reads(ctx, pile, bases, offsets, min_depth=3, min_span=None, min_len=100, longest=False):
+    """The reads of a batch cut down to their supported segments (kmu_pile_segments, kmu_extract_ranges): every kept segment -- rows
+    with depth >= min_depth, consecutive rows linked by a spanning depth >= min_span (None: min_depth), at least min_len long --
+    becomes a read of the new batch, so uncovered ends go, and a chimera comes out as its parts.  longest=True keeps one segment
+    per read.  Returns (trim_bases, trim_offsets, segs, reads): the new ASCII batch, the segments its reads are (Context.pile_segments)
+    and the summary of every input read.  The ranges are computed where the table lives."""
+    segs, _, reads = ctx.pile_segments(pile, offsets, min_depth=min_depth, min_span=min_span, min_len=min_len, longest=longest)
+    begin, end = _segment_rows(segs, offsets)
+    trim_bases, trim_offsets = ctx.extract_ranges(bases, begin, end)
+    return trim_bases, trim_offsets, segs, reads
+
+
+def correct_trim_reads(ctx, bases, offsets, k, w, fhash=A.FHASH_CANON_INVHASH, max_occ=0, max_gap=5000, band_chain=500, min_seeds=3,
+                       min_score=0, band=64, max_trace_bytes=0, min_depth=3, max_ins=16, min_span=None, min_len=100, longest=False):
+    """correct_reads and trim_reads in one call, on one table: read_cigars, the self-join of pileup_chains, Context.pile_call,
+    Context.pile_ins_plan, the self-join of insertions_chains and consensus_reads as correct_reads does them; then
+    Context.pile_segments on the same table, Context.pile_consensus_pos of every segment's first row and end row, and
+    Context.extract_ranges on the consensus batch.  Returns (out_bases, out_offsets, segs, reads, trims): the corrected, trimmed
+    and split reads, the segments (in raw read coordinates) they are, the summaries of pile_call and those of pile_segments.
+    Tables and runs stay where the reads live."""
+    chains, aln, ops, op_offsets = read_cigars(ctx, bases, offsets, k, w, fhash, max_occ, max_gap, band_chain, min_seeds, min_score, band,
+                                               max_trace_bytes)
+    pile, _ = pileup_chains(ctx, chains, aln, ops, op_offsets, bases, offsets)
+    call, reads = ctx.pile_call(pile, bases, offsets, min_depth=min_depth)
+    ins_len, n_slots = ctx.pile_ins_plan(pile, call, max_ins=max_ins)
+    ins, _ = insertions_chains(ctx, chains, aln, ops, op_offsets, bases, offsets, ins_len, n_slots)
+    cons_bases, _ = consensus_reads(ctx, pile, call, ins_len, n_slots, ins, bases, offsets)
+    segs, _, trims = ctx.pile_segments(pile, offsets, min_depth=min_depth, min_span=min_span, min_len=min_len, longest=longest)
+    first, last = _segment_rows(segs, offsets)
+    n = int(first.shape[0])
+    if _is_torch(first):
+        import torch
+        rows = torch.cat([first, last])
+    else:
+        rows = np.concatenate([first, last])
+    pos = ctx.pile_consensus_pos(pile, call, ins_len, n_slots, ins, bases, offsets, rows)
+    out_bases, out_offsets = ctx.extract_ranges(cons_bases, pos[:n].contiguous() if _is_torch(pos) else pos[:n],
+                                                pos[n:].contiguous() if _is_torch(pos) else pos[n:])
+    return out_bases, out_offsets, segs, reads, trims
+
+
 def pile_depth(pile):
     """A + C + G + T + DEL of every row of a pileup table: how many partners were aligned over the base (int64; numpy or torch)"""
     if _is_torch(pile):
