@@ -613,6 +613,8 @@ class Context:
         hp = A.HashParams(kmer_type, k, fhash, A.INPUT_ASCII, mem, 0)
         moff = self._new_like(bases, n + 1, np.uint64, "int64")
         total = C.c_uint64(0)
+        if not int(bases.shape[0]):  # a batch of empty reads: an empty array has no address worth passing
+            bases = self._new_like(bases, 16, np.uint8, "uint8")
         args = (self.h, C.byref(hp), _ptr(bases)[0], _ptr(offsets)[0], n, int(w))
         # (the strand pointer of the count-only call is NULL: an ntHash order is refused only where a strand is asked for)
         self._check(self.L.kmu_read_minimizers(*args, None, None, None, None, 0, _ptr(moff)[0], C.byref(total)))

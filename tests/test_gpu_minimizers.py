@@ -288,6 +288,19 @@ def test_no_read_and_no_kmer(ctx):
     assert got[0].size == 0 and got[4].tolist() == [0, 0, 0, 0]
 
 
+def test_a_batch_of_empty_reads_on_host_and_device_arrays(ctx):
+    """reads but no base at all: an empty tensor has no address, and the binding must not hand the library a null pointer for it"""
+    import torch
+    off = np.zeros(4, np.uint64)
+    got = ctx.read_minimizers(np.zeros(0, np.uint8), off, A.KMER64BIT, 21, A.FHASH_CANON_INVHASH, 10)
+    assert [x.shape for x in got] == [(0,)] * 4 + [(4,)] and got[4].tolist() == [0, 0, 0, 0]
+    d = ctx.read_minimizers(torch.zeros(0, dtype=torch.uint8, device="cuda"), torch.zeros(4, dtype=torch.int64, device="cuda"), A.KMER64BIT, 21,
+                            A.FHASH_CANON_INVHASH, 10)
+    assert all(x.is_cuda for x in d) and [tuple(x.shape) for x in d] == [(0,)] * 4 + [(4,)] and d[4].cpu().tolist() == [0, 0, 0, 0]
+    m = minimizer.read_minimizers(ctx, torch.zeros(0, dtype=torch.uint8, device="cuda"), torch.zeros(4, dtype=torch.int64, device="cuda"), 15, 10)
+    assert minimizer.seed_pairs(ctx, m).shape[0] == 0
+
+
 # ---- errors ---------------------------------------------------------------------------------------------------------------------
 def test_non_acgt_is_reported_and_does_not_stick(ctx, oracle):
     k, w = 21, 10
