@@ -33,6 +33,8 @@
  *                 (the inserted letters and the corrected reads)
  *                 PileSegments, pile_segments, extract_ranges, pile_consensus_pos, trim_reads, correct_trim_chains, correct_trim_reads
  *                 (supported segments of every read, chimera splits and trimmed reads)
+ *                 GraphParams, OverlapClasses, sg_classify, OverlapGraph, overlap_graph, read_graph, unitig_labels, gfa_line
+ *                 (overlap classes, contained reads, the transitively reduced string graph)
  *                 seed_chains, seed_pairs, chain_hits, read_chains (one base-resolution chain per read pair from minimizer
  *                                                            hits)                          (beyond the reference)
  *   counting      KmerCountT (trait), KmerCounter, KmerCounterPool, count_kmer_threaded_one_to_many
@@ -2389,6 +2391,122 @@ CorrectedTrimmedReads correct_trim_reads(const detail::Batch &batch, size_t k, u
     return correct_trim_chains(read_chains<Kmer>(batch, k, w, fhash, max_occ, max_gap, band_chain, min_seeds, min_score, ctx), batch, band, min_depth,
                                max_ins, min_span, min_len, longest, ctx);
 }
+
+// =====================================================================================================================
+// string graph (kmu_sg_classify, kmu_sg_graph; the reference has no such unit)
+// =====================================================================================================================
+
+/// The thresholds of sg_classify and overlap_graph (include/kmu.h has the rules): an overlap is at least min_overlap long on both
+/// reads, internal when its overhang is above max_hang or above int_permille thousandths of its length, and (with alignment
+/// records) dropped below min_identity_permille; fuzz is the slack of the transitive reduction.
+struct GraphParams {
+    uint32_t min_overlap = 500, max_hang = 1000, int_permille = 250, min_identity_permille = 0, fuzz = 10;
+};
+
+/// What sg_classify returns: the class KMU_SG_* of every record and the summary of every read.
+struct OverlapClasses {
+    std::vector<uint8_t> classes;
+    std::vector<kmu_sg_read> reads;
+};
+
+/// What overlap_graph returns: the arcs in (from, to, rec) order, the slice of every vertex (2r: read r forward, 2r + 1: its reverse
+/// complement), and what sg_classify returns with the surviving out-degrees filled in.
+struct OverlapGraph {
+    std::vector<kmu_sg_arc> arcs;
+    std::vector<uint64_t> arc_offsets;
+    std::vector<uint8_t> classes;
+    std::vector<kmu_sg_read> reads;
+};
+
+namespace detail {
+inline kmu_sg_params sg_params(const GraphParams &g) {
+    kmu_sg_params p{};
+    p.min_overlap = g.min_overlap;
+    p.max_hang = g.max_hang;
+    p.int_permille = g.int_permille;
+    p.min_identity_permille = g.min_identity_permille;
+    p.fuzz = g.fuzz;
+    return p;
+}
+inline void sg_check_sizes(const char *who, const std::vector<kmu_chain> &chains, const std::vector<kmu_chain_aln> &aln, const std::vector<uint64_t> &offsets) {
+    if (offsets.empty()) throw std::invalid_argument(std::string(who) + ": the offsets of a batch have at least one entry");
+    if (!aln.empty() && aln.size() != chains.size()) throw std::invalid_argument(std::string(who) + ": as many alignment records as chains, or none");
+}
+} // namespace detail
+
+/// kmu_sg_classify on host arrays: chains of a self-join, their alignment records (empty: no identity test) and the batch's offsets.
+inline OverlapClasses sg_classify(const std::vector<kmu_chain> &chains, const std::vector<kmu_chain_aln> &aln, const std::vector<uint64_t> &offsets,
+                                  const GraphParams &g = GraphParams(), Context &ctx = Context::global()) {
+    detail::sg_check_sizes("sg_classify", chains, aln, offsets);
+    OverlapClasses out;
+    const uint32_t n_reads = uint32_t(offsets.size() - 1);
+    out.classes.assign(chains.size() + 1, 0); // an empty vector has no address worth passing
+    out.reads.assign(size_t(n_reads) + 1, kmu_sg_read{});
+    const kmu_sg_params p = detail::sg_params(g);
+    const kmu_chain none{};
+    ctx.check(kmu_sg_classify(ctx.raw(), chains.empty() ? &none : chains.data(), aln.empty() ? nullptr : aln.data(), chains.size(), offsets.data(), n_reads,
+                              &p, KMU_MEM_HOST, out.classes.data(), out.reads.data()));
+    out.classes.resize(chains.size());
+    out.reads.resize(n_reads);
+    return out;
+}
+
+/// kmu_sg_graph on host arrays (minimizer.overlap_graph): the dovetails between reads that are not contained as a bidirected
+/// graph, transitively reduced.  Two library calls: one that counts, one with exactly that capacity.
+inline OverlapGraph overlap_graph(const std::vector<kmu_chain> &chains, const std::vector<kmu_chain_aln> &aln, const std::vector<uint64_t> &offsets,
+                                  const GraphParams &g = GraphParams(), Context &ctx = Context::global()) {
+    detail::sg_check_sizes("overlap_graph", chains, aln, offsets);
+    OverlapGraph out;
+    const uint32_t n_reads = uint32_t(offsets.size() - 1);
+    const kmu_sg_params p = detail::sg_params(g);
+    const kmu_chain none{};
+    const kmu_chain *c = chains.empty() ? &none : chains.data();
+    const kmu_chain_aln *a = aln.empty() ? nullptr : aln.data();
+    uint64_t total = 0;
+    ctx.check(kmu_sg_graph(ctx.raw(), c, a, chains.size(), offsets.data(), n_reads, &p, KMU_MEM_HOST, nullptr, nullptr, nullptr, 0, nullptr, &total));
+    out.arcs.assign(total + 1, kmu_sg_arc{});
+    out.arc_offsets.assign(2 * size_t(n_reads) + 1, 0);
+    out.classes.assign(chains.size() + 1, 0);
+    out.reads.assign(size_t(n_reads) + 1, kmu_sg_read{});
+    ctx.check(kmu_sg_graph(ctx.raw(), c, a, chains.size(), offsets.data(), n_reads, &p, KMU_MEM_HOST, out.classes.data(), out.reads.data(), out.arcs.data(),
+                           total, out.arc_offsets.data(), &total));
+    out.arcs.resize(total);
+    out.classes.resize(chains.size());
+    out.reads.resize(n_reads);
+    return out;
+}
+
+/// From the reads of a batch to their string graph (minimizer.read_graph): read_alignments, then overlap_graph on its records.
+template <class Kmer>
+OverlapGraph read_graph(const detail::Batch &batch, size_t k, uint32_t w, const GraphParams &g = GraphParams(), FHash fhash = FHash::canon_invhash,
+                        uint32_t max_occ = 0, uint32_t max_gap = 5000, uint32_t band_chain = 500, uint32_t min_seeds = 3, uint32_t min_score = 0,
+                        uint32_t band = 64, Context &ctx = Context::global()) {
+    const detail::Batch b = detail::unpacked(batch);
+    if (b.on_device()) throw std::invalid_argument("read_graph returns host arrays: it needs the sequences in host memory");
+    const auto records = read_alignments<Kmer>(batch, k, w, fhash, max_occ, max_gap, band_chain, min_seeds, min_score, band, ctx);
+    return overlap_graph(records.first, records.second, b.offsets, g, ctx);
+}
+
+/// Which reads lie on one unitig (minimizer.unitig_labels): the components of the 2 n_reads vertices under the arcs whose `unique`
+/// is 1, each unitig once per strand; a read's label is the smaller of the labels of its two vertices.
+inline std::vector<uint32_t> unitig_labels(const std::vector<kmu_sg_arc> &arcs, uint32_t n_reads, Context &ctx = Context::global()) {
+    static_assert(sizeof(kmu_sg_arc) == 32, "a record is 8 words");
+    const kmu_sg_arc none{};
+    const Components c = detail::components_call(ctx, 2 * n_reads, [&](uint32_t *l, uint32_t *cl, uint32_t *s, uint32_t *m, uint32_t *n) {
+        return kmu_components(ctx.raw(), 2 * n_reads, reinterpret_cast<const uint32_t *>(arcs.empty() ? &none : arcs.data()), arcs.size(), 8, 6, 1,
+                              KMU_MEM_HOST, l, cl, s, m, n);
+    });
+    std::vector<uint32_t> labels(n_reads);
+    for (uint32_t r = 0; r < n_reads; r++) labels[r] = std::min(c.label[2 * size_t(r)], c.label[2 * size_t(r) + 1]);
+    return labels;
+}
+
+/// One line of GFA 1 text for an arc: `L from +/- to +/- <ovl>M` (minimizer.gfa_lines writes these for the surviving arcs).
+inline std::string gfa_line(const kmu_sg_arc &a, const std::string &name_from, const std::string &name_to) {
+    return "L\t" + name_from + "\t" + ((a.from & 1u) ? "-" : "+") + "\t" + name_to + "\t" + ((a.to & 1u) ? "-" : "+") + "\t" + std::to_string(a.ovl) + "M";
+}
+/// ... and for a read: `S name * LN:i:len`
+inline std::string gfa_line(const std::string &name, uint64_t len) { return "S\t" + name + "\t*\tLN:i:" + std::to_string(len); }
 
 // =====================================================================================================================
 // counting (kmercount.rs)

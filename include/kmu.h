@@ -1296,6 +1296,97 @@ int kmu_pile_consensus_pos(kmu_ctx *ctx, const uint32_t *pile, const uint8_t *ca
                            const kmu_consensus_params *p, int mem,
                            const uint64_t *rows, uint64_t n_rows, uint64_t *pos_out);
 
+/* ---- string graph: overlap classes, contained reads, the bidirected overlap graph and its transitive reduction -------
+ * Inputs: chains[n_chains], the records of a SELF-JOIN (kmu_seed_chains on one batch); aln[n_chains], the records kmu_chain_align
+ *   or kmu_chain_cigar wrote for them, or NULL; offsets[n_reads + 1] of the batch -- only the lengths are used, no base is read.
+ * Class of a record (class_out[c], one uint8), decided in this order.  la, lb: the lengths of read_a and read_b; s: the strand;
+ *   (bs', be') = (b_start, b_end) for s = 0 and (lb - b_end, lb - b_start) for s = 1 (b in a's orientation); aL = a_start,
+ *   aR = la - a_end, bL = bs', bR = lb - be'; hang = min(aL, bL) + min(aR, bR); maplen = max(a_end - a_start, b_end - b_start).
+ *   1. KMU_SG_SKIP: read_a >= read_b.  The graph takes each unordered pair from the record with read_a < read_b; a self-overlap
+ *      never counts.
+ *   2. KMU_SG_SHORT: a_end - a_start < min_overlap or b_end - b_start < min_overlap.
+ *   3. KMU_SG_LOWID: only with aln.  KMU_ALN_DONE is not set, or matches * 1000 < min_identity_permille * (matches + edit) (64 bits).
+ *   4. KMU_SG_INTERNAL: hang > max_hang or hang * 1000 > maplen * int_permille (64 bits).
+ *   5. KMU_SG_A_CONTAINED iff aL <= bL and aR <= bR; KMU_SG_B_CONTAINED iff aL >= bL and aR >= bR.  If both hold the shorter read is
+ *      the contained one, read_b at equal length.
+ *   6. KMU_SG_DOVETAIL otherwise.  Then aL != bL, and both arc lengths below are >= 1.
+ * Reads (reads_out[r], kmu_sg_read): read r is CONTAINED iff some record has class A_CONTAINED with read_a == r or B_CONTAINED with
+ *   read_b == r.  flags: KMU_SG_READ_CONTAINED; n_records: the records that name r as read_a or read_b and are not SKIP; out_fwd,
+ *   out_rev: the surviving out-degrees of the vertices 2r and 2r + 1 (0 from kmu_sg_classify).
+ * Vertices and arcs: vertex 2r is read r forward, 2r + 1 its reverse complement.  An arc v -> w of length len means that w
+ *   continues v to the right by len bases.  A DOVETAIL record c whose two reads are both not contained makes exactly two arcs, each
+ *   the other's MATE; with a = read_a, b = read_b:
+ *     aL > bL:    (2a -> 2b + s, len bR - aR)           and (2b + (s ^ 1) -> 2a + 1, len aL - bL);
+ *     otherwise:  (2a + 1 -> 2b + (s ^ 1), len bL - aL) and (2b + s -> 2a, len aR - bR).
+ *   An arc record (kmu_sg_arc, 32 bytes) is from, to, len, ovl, rec, flags, unique, 0: ovl is the overlap length on the `from` read
+ *   (a_end - a_start or b_end - b_start), rec is c.  Arcs are listed in (from, to, rec) order; arc_offsets_out[2 n_reads + 1] gives
+ *   every vertex v its slice out(v).  Duplicate records make duplicate arcs, which are kept.
+ * Reduction: a pure function of the arc set.  L(v) = the largest len of out(v) + fuzz (64 bits); first(w) is the arc of out(w) that
+ *   is smallest under (len, to, rec).  For every arc f = v -> w and every arc g = w -> x: if len(f) + len(g) <= L(v), or len(g) < fuzz,
+ *   or g = first(w), then EVERY arc v -> x of out(v) is marked.  An arc carries KMU_SG_ARC_REDUCED iff it or its mate is marked: the
+ *   marks live per record.  This is Myers' rule (2005) without the skip of already eliminated w: a superset of the sequential
+ *   result, equal to it on every consistent layout.
+ * Unique: an arc that is not reduced has unique = 1 iff it is the only surviving (not reduced) arc of out(from) and its mate is the
+ *   only surviving arc of out(to ^ 1); every other arc has unique = 0.  kmu_components over 2 n_reads nodes with stride 8,
+ *   weight_at 6, min_weight 1 then groups the vertices into unitigs, each once per strand.
+ * kmu_sg_classify writes n_chains classes and n_reads summaries, always; no count call.
+ * kmu_sg_graph: *n_out (host memory in both modes) is always the number of arcs.  arcs_out == NULL: the count-only call, which writes
+ *   *n_out and nothing else.  cap < total: KMU_E_BAD_ARG with *n_out set, no output is written.  2 * (the number of DOVETAIL
+ *   records) is always a sufficient cap.  Otherwise class_out, reads_out and arc_offsets_out are written where given (each may be
+ *   NULL), and the arcs.  KMU_MEM_DEVICE: every array except p and n_out is device memory; the call synchronises the stream once, to
+ *   hand over n_out and the refusal flags, also in async_device contexts.  KMU_MEM_HOST: the arrays go up through the context's
+ *   workspace and the results come back.
+ * n_chains == 0: KMU_OK, no arcs, every summary zero, every offset 0.
+ * KMU_E_BAD_ARG (nothing is launched): null ctx / offsets / p / n_out, null chains with n_chains > 0, null class_out or reads_out
+ *   of kmu_sg_classify, non-zero flags, int_permille or min_identity_permille > 1000, bad mem, chains while there are no reads.
+ * KMU_E_UNSUPPORTED: n_reads >= 2^31 or n_chains >= 2^31; a record (of any class) with a read >= n_reads, strand > 1, a start above
+ *   its end, an end above the length of its read, or a read of 2^32 bases or more.  The records are read on the device: the refusal
+ *   comes at the call's synchronisation, no such record is ever used as an index, and the outputs of a refused call are untouched.
+ * The result is a pure function of the inputs: integer compares, idempotent stores and commuting integer atomics only; the order of
+ *   the records matters only through rec, and the launch shape and timing change nothing.
+ * How: one lane per record classifies; one wave per tile of KMU_SG_TILE records compacts the surviving dovetails by ballot and
+ *   prefix count (count, scan, write) into (from << 32 | to, 2c + side); a stable radix sort over the bytes 2 n_reads can reach; one
+ *   lane per arc rebuilds its record; one lane per vertex finds its slice, L(v) and first(v); one wave per arc f walks out(to) and
+ *   marks; one lane per arc sets the flag and counts the degrees; one lane per arc sets unique.  DESIGN.md 3.22 has the kernels. */
+#define KMU_SG_TILE 1024           /* records one wave compacts */
+#define KMU_SG_SKIP        0u
+#define KMU_SG_SHORT       1u
+#define KMU_SG_LOWID       2u
+#define KMU_SG_INTERNAL    3u
+#define KMU_SG_A_CONTAINED 4u
+#define KMU_SG_B_CONTAINED 5u
+#define KMU_SG_DOVETAIL    6u
+#define KMU_SG_READ_CONTAINED 1u   /* kmu_sg_read.flags */
+#define KMU_SG_ARC_REDUCED 1u      /* kmu_sg_arc.flags */
+typedef struct kmu_sg_params {
+    uint32_t min_overlap;            /* on both reads */
+    uint32_t max_hang;
+    uint32_t int_permille;           /* <= 1000 */
+    uint32_t min_identity_permille;  /* <= 1000; used only with aln */
+    uint32_t fuzz;
+    uint32_t flags;                  /* no flag bits yet: must be 0 */
+} kmu_sg_params;
+typedef struct {         /* 16 bytes */
+    uint32_t flags;      /* KMU_SG_READ_CONTAINED */
+    uint32_t n_records;  /* records of the read that are not SKIP */
+    uint32_t out_fwd;    /* surviving arcs of vertex 2r */
+    uint32_t out_rev;    /* surviving arcs of vertex 2r + 1 */
+} kmu_sg_read;
+typedef struct {         /* 32 bytes */
+    uint32_t from, to, len, ovl, rec, flags, unique, zero;
+} kmu_sg_arc;
+int kmu_sg_classify(kmu_ctx *ctx, const kmu_chain *chains, const kmu_chain_aln *aln, uint64_t n_chains,
+                    const uint64_t *offsets, uint32_t n_reads, const kmu_sg_params *p, int mem,
+                    uint8_t *class_out, kmu_sg_read *reads_out);
+int kmu_sg_graph(kmu_ctx *ctx, const kmu_chain *chains, const kmu_chain_aln *aln, uint64_t n_chains,
+                 const uint64_t *offsets, uint32_t n_reads, const kmu_sg_params *p, int mem,
+                 uint8_t *class_out,          /* may be NULL */
+                 kmu_sg_read *reads_out,      /* may be NULL */
+                 kmu_sg_arc *arcs_out,        /* NULL: the count-only call */
+                 uint64_t cap,
+                 uint64_t *arc_offsets_out,   /* 2 n_reads + 1; may be NULL */
+                 uint64_t *n_out);            /* host memory in both modes; required */
+
 #ifdef __cplusplus
 }
 #endif

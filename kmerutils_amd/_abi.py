@@ -47,6 +47,11 @@ INS_COLS = 4             # kmu_chain_pile_ins: uint32 per insertion slot, one co
 INS_MAX = 255            # kmu_pile_ins_plan: the most slots a base can get
 SEG_LONGEST = 1          # kmu_pile_segments flags: list only the longest kept segment of every read
 TRIM_WHOLE, TRIM_ENDS, TRIM_SPLIT, TRIM_NONE = 0, 1, 2, 3   # kmu_read_trim.cls
+SG_TILE = 1024           # records one wave of kmu_sg_graph compacts
+SG_SKIP, SG_SHORT, SG_LOWID, SG_INTERNAL, SG_A_CONTAINED, SG_B_CONTAINED, SG_DOVETAIL = range(7)   # the class of a chain record
+SG_CLASS_NAMES = ("skip", "short", "lowid", "internal", "a_contained", "b_contained", "dovetail")
+SG_READ_CONTAINED = 1    # kmu_sg_read.flags
+SG_ARC_REDUCED = 1       # kmu_sg_arc.flags
 
 
 def kmer_val_bytes(kmer_type):
@@ -202,6 +207,29 @@ class ReadTrim(C.Structure):
 PILE_SEG_DTYPE = [("read", "<u4"), ("start", "<u4"), ("end", "<u4"), ("rank", "<u4")]
 READ_TRIM_DTYPE = [("n_bases", "<u4"), ("n_good", "<u4"), ("n_segs", "<u4"), ("kept", "<u4"), ("best_start", "<u4"), ("best_end", "<u4"),
                    ("inner_bad", "<u4"), ("cls", "<u4")]
+
+
+class SgParams(C.Structure):
+    """kmu_sg_params: the thresholds of kmu_sg_classify and kmu_sg_graph"""
+    _fields_ = [("min_overlap", C.c_uint32), ("max_hang", C.c_uint32), ("int_permille", C.c_uint32), ("min_identity_permille", C.c_uint32),
+                ("fuzz", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class SgRead(C.Structure):
+    """kmu_sg_read: the summary of one read in the string graph"""
+    _fields_ = [("flags", C.c_uint32), ("n_records", C.c_uint32), ("out_fwd", C.c_uint32), ("out_rev", C.c_uint32)]
+
+
+class SgArc(C.Structure):
+    """kmu_sg_arc: one arc of the string graph"""
+    _fields_ = [("from_", C.c_uint32), ("to", C.c_uint32), ("len", C.c_uint32), ("ovl", C.c_uint32), ("rec", C.c_uint32), ("flags", C.c_uint32),
+                ("unique", C.c_uint32), ("zero", C.c_uint32)]
+
+
+# the same records as numpy dtypes (16 and 32 bytes)
+SG_READ_DTYPE = [("flags", "<u4"), ("n_records", "<u4"), ("out_fwd", "<u4"), ("out_rev", "<u4")]
+SG_ARC_DTYPE = [("from", "<u4"), ("to", "<u4"), ("len", "<u4"), ("ovl", "<u4"), ("rec", "<u4"), ("flags", "<u4"), ("unique", "<u4"),
+                ("zero", "<u4")]
 
 
 class ReadPile(C.Structure):

@@ -38,7 +38,7 @@ SYMBOLS = [
     "kmu_anchor_index_occupancy", "kmu_anchor_index_match", "kmu_components", "kmu_components_knn",
     "kmu_minimizer_layout", "kmu_read_minimizers", "kmu_seed_chains", "kmu_chain_align",
     "kmu_chain_cigar", "kmu_chain_pileup", "kmu_pile_call", "kmu_pile_ins_plan", "kmu_chain_pile_ins", "kmu_pile_consensus",
-    "kmu_pile_segments", "kmu_extract_ranges", "kmu_pile_consensus_pos",
+    "kmu_pile_segments", "kmu_extract_ranges", "kmu_pile_consensus_pos", "kmu_sg_classify", "kmu_sg_graph",
 ]
 
 
@@ -162,6 +162,9 @@ def load():
     L.kmu_extract_ranges.argtypes = [vp, vp, C.c_uint64, vp, vp, C.c_uint64, C.c_int, vp, vp, C.c_uint64, C.POINTER(C.c_uint64)]
     L.kmu_pile_consensus_pos.argtypes = [vp, vp, vp, vp, C.c_uint64, vp, vp, vp, C.c_uint32, C.POINTER(A.ConsensusParams), C.c_int, vp,
                                          C.c_uint64, vp]
+    L.kmu_sg_classify.argtypes = [vp, vp, vp, C.c_uint64, vp, C.c_uint32, C.POINTER(A.SgParams), C.c_int, vp, vp]
+    L.kmu_sg_graph.argtypes = [vp, vp, vp, C.c_uint64, vp, C.c_uint32, C.POINTER(A.SgParams), C.c_int, vp, vp, vp, C.c_uint64, vp,
+                               C.POINTER(C.c_uint64)]
     L.kmu_set_hll_params.argtypes = [vp, C.POINTER(A.HllParams)]
     L.kmu_kmer_hashes_compact.argtypes = [vp, C.POINTER(A.HashParams), vp, vp, vp, C.c_uint32, vp, C.c_uint64, u64p]
     L.kmu_sketch_partial_words.argtypes = [C.POINTER(A.SketchParams)]
@@ -1284,6 +1287,65 @@ class Context:
         self._check(self.L.kmu_pile_consensus_pos(self.h, ptr(pile), ptr(call), ptr(ins_len), n_slots, ptr(ins), ptr(bases), _ptr(off)[0], n_reads,
                                                   C.byref(p), mem, ptr(rows), n, _ptr(pos)[0]))
         return pos[:n]
+
+    def _sg_inputs(self, chains, aln, offsets, min_overlap, max_hang, int_permille, min_identity_permille, fuzz):
+        """what sg_classify and sg_graph hand to the library: (the arguments up to `mem`, the arrays behind them -- the chains first,
+        which the outputs are allocated like; they must outlive the call -- mem, n, n_reads)"""
+        if not _is_torch(chains):
+            chains = np.ascontiguousarray(chains)
+        if aln is not None and not _is_torch(aln):
+            aln = np.ascontiguousarray(aln)
+        mem = self._mem(chains, aln)
+        n = int(chains.shape[0])
+        if aln is not None and int(aln.shape[0]) != n:
+            raise ValueError("%d chains need as many alignment records" % n)
+        off = self._offsets_like(offsets, chains, mem)
+        n_reads = int(off.shape[0]) - 1
+        p = A.SgParams(int(min_overlap), int(max_hang), int(int_permille), int(min_identity_permille), int(fuzz), 0)
+        none = self._new_like(chains, 16, np.uint8, "uint8")  # an empty array has no address worth passing
+        args = (self.h, _ptr(chains if n else none)[0], _ptr(aln if n else None)[0] if aln is not None else None, n, _ptr(off)[0], n_reads,
+                C.byref(p), mem)
+        return args, (chains, aln, off, p), mem, n, n_reads
+
+    def sg_classify(self, chains, aln, offsets, min_overlap=500, max_hang=1000, int_permille=250, min_identity_permille=0, fuzz=10):
+        """kmu_sg_classify: the class of every chain record of a self-join (A.SG_SKIP .. A.SG_DOVETAIL; include/kmu.h has the rules)
+        and a summary per read -- A.SG_READ_CONTAINED and the number of its records that are not SKIP.  chains: the records of
+        seed_chains; aln: the records of chain_align for them, or None (no identity test); offsets: the batch's, of which only the
+        lengths count.  Returns (classes, reads): uint8 [n] and A.SG_READ_DTYPE records; for torch cuda tensors a uint8 tensor and
+        an int32 tensor [n_reads, 4] holding the same bits, on the device."""
+        args, keep, mem, n, n_reads = self._sg_inputs(chains, aln, offsets, min_overlap, max_hang, int_permille, min_identity_permille, fuzz)
+        like = keep[0]
+        classes = self._new_like(like, max(n, 1), np.uint8, "uint8")
+        if mem == A.MEM_DEVICE:
+            reads = self._new_like(like, (max(n_reads, 1), 4), np.int32, "int32")
+        else:
+            reads = np.zeros(max(n_reads, 1), np.dtype(A.SG_READ_DTYPE))
+        self._check(self.L.kmu_sg_classify(*args, _ptr(classes)[0], _ptr(reads)[0]))
+        return classes[:n], reads[:n_reads]
+
+    def sg_graph(self, chains, aln, offsets, min_overlap=500, max_hang=1000, int_permille=250, min_identity_permille=0, fuzz=10):
+        """kmu_sg_graph: the string graph of a self-join -- two arcs per dovetail record between reads that are not contained, in
+        (from, to, rec) order, transitively reduced: A.SG_ARC_REDUCED in an arc's flags, and unique = 1 where an arc and its mate
+        are the only surviving arcs of their vertices (include/kmu.h has the rules).  Arguments as sg_classify.  Returns (arcs,
+        arc_offsets, classes, reads): A.SG_ARC_DTYPE records, uint64 [2 n_reads + 1] (vertex 2r is read r forward, 2r + 1 its
+        reverse complement), and what sg_classify returns with the surviving out-degrees filled in; for torch cuda tensors int32
+        [n, 8], int64, uint8 and int32 [n_reads, 4] tensors holding the same bits, on the device.  Two library calls: one that
+        counts, one with exactly that capacity."""
+        args, keep, mem, n, n_reads = self._sg_inputs(chains, aln, offsets, min_overlap, max_hang, int_permille, min_identity_permille, fuzz)
+        like = keep[0]
+        total = C.c_uint64(0)
+        self._check(self.L.kmu_sg_graph(*args, None, None, None, 0, None, C.byref(total)))
+        cap = int(total.value)
+        classes = self._new_like(like, max(n, 1), np.uint8, "uint8")
+        arc_off = self._new_like(like, 2 * n_reads + 1, np.uint64, "int64")
+        if mem == A.MEM_DEVICE:
+            reads = self._new_like(like, (max(n_reads, 1), 4), np.int32, "int32")
+            arcs = self._new_like(like, (max(cap, 1), 8), np.int32, "int32")
+        else:
+            reads = np.zeros(max(n_reads, 1), np.dtype(A.SG_READ_DTYPE))
+            arcs = np.zeros(max(cap, 1), np.dtype(A.SG_ARC_DTYPE))
+        self._check(self.L.kmu_sg_graph(*args, _ptr(classes)[0], _ptr(reads)[0], _ptr(arcs)[0], cap, _ptr(arc_off)[0], C.byref(total)))
+        return arcs[:cap], arc_off, classes[:n], reads[:n_reads]
 
     def _components(self, call, like, n_nodes, want, count):
         """the outputs of kmu_components / kmu_components_knn allocated where `like` lives, call(*output pointers) run on them,

@@ -18,6 +18,9 @@ calls of kmu_pile_call -- without the runs leaving where the reads live, and `pi
 (Context.chain_pile_ins): which letters the partners have where most of them have extra bases; `consensus_reads` turns table,
 calls and slots into the corrected reads (kmu_pile_consensus), a new batch of bases and offsets; `correct_reads` goes from reads
 to (cons_bases, cons_offsets, reads) in one call, and what it returns goes straight back into `read_minimizers` or the counter.
+`classify_chains` and `overlap_graph` hand the chains and their records to kmu_sg_classify / kmu_sg_graph (Context.sg_classify,
+Context.sg_graph): the class of every overlap, the contained reads and the transitively reduced string graph; `read_graph` goes
+from reads to the graph, `unitig_labels` groups the reads of one unitig and `gfa_lines` writes the graph as GFA text on the host.
 """
 import collections
 
@@ -245,6 +248,56 @@ def correct_trim_reads(ctx, bases, offsets, k, w, fhash=A.FHASH_CANON_INVHASH, m
     out_bases, out_offsets = ctx.extract_ranges(cons_bases, pos[:n].contiguous() if _is_torch(pos) else pos[:n],
                                                 pos[n:].contiguous() if _is_torch(pos) else pos[n:])
     return out_bases, out_offsets, segs, reads, trims
+
+
+def classify_chains(ctx, chains, aln, offsets, min_overlap=500, max_hang=1000, int_permille=250, min_identity_permille=0, fuzz=10):
+    """The class of every chain record of a self-join and the contained reads (kmu_sg_classify): (classes, reads) as
+    Context.sg_classify returns them.  chains, aln: the records of read_alignments (aln=None: no identity test); offsets: the
+    batch's.  The thresholds are those of include/kmu.h: an overlap is at least min_overlap long on both reads; it is internal when
+    its overhang is above max_hang or above int_permille thousandths of its length."""
+    return ctx.sg_classify(chains, aln, offsets, min_overlap, max_hang, int_permille, min_identity_permille, fuzz)
+
+
+def overlap_graph(ctx, chains, aln, offsets, min_overlap=500, max_hang=1000, int_permille=250, min_identity_permille=0, fuzz=10):
+    """The string graph of a self-join (kmu_sg_graph): (arcs, arc_offsets, classes, reads) as Context.sg_graph returns them -- the
+    dovetails between reads that are not contained as a bidirected graph (vertex 2r: read r forward, 2r + 1: reverse complement),
+    transitively reduced with `fuzz`."""
+    return ctx.sg_graph(chains, aln, offsets, min_overlap, max_hang, int_permille, min_identity_permille, fuzz)
+
+
+def read_graph(ctx, bases, offsets, k, w, fhash=A.FHASH_CANON_INVHASH, max_occ=0, max_gap=5000, band_chain=500, min_seeds=3, min_score=0,
+               band=64, min_overlap=500, max_hang=1000, int_permille=250, min_identity_permille=0, fuzz=10):
+    """From the reads of a batch to their string graph in one call: read_alignments, then overlap_graph on its records.  Returns
+    (arcs, arc_offsets, classes, reads); with torch cuda tensors nothing leaves the device."""
+    chains, aln = read_alignments(ctx, bases, offsets, k, w, fhash, max_occ, max_gap, band_chain, min_seeds, min_score, band)
+    return overlap_graph(ctx, chains, aln, offsets, min_overlap, max_hang, int_permille, min_identity_permille, fuzz)
+
+
+def unitig_labels(ctx, arcs, n_reads):
+    """Which reads lie on one unitig: Context.components over the 2 n_reads vertices with the arcs whose `unique` is 1 as edges
+    (stride 8, weight_at 6, min_weight 1), which finds every unitig once per strand; a read's label is the smaller of the labels
+    of its two vertices.  arcs: the records of overlap_graph.  Returns uint32 [n_reads] (int32 for torch), where the arcs live."""
+    edges = arcs if _is_torch(arcs) else np.ascontiguousarray(arcs).reshape(-1).view(np.uint32).reshape(-1, 8)
+    label = ctx.components(edges, 2 * int(n_reads), weight_at=6, min_weight=1, want=(), count=False).label
+    if _is_torch(label):
+        import torch
+        return torch.minimum(label[0::2], label[1::2])
+    return np.minimum(label[0::2], label[1::2])
+
+
+def gfa_lines(arcs, names, offsets, reduced=False, reads=None):
+    """The graph as GFA 1 text, on the host: `S name * LN:i:len` for every read (with reads, the summaries of overlap_graph: for
+    every read that is not contained), then `L from +/- to +/- <ovl>M` for every surviving arc in the order of the records;
+    reduced=True also writes the arcs that carry A.SG_ARC_REDUCED.  arcs: numpy A.SG_ARC_DTYPE records."""
+    off = np.asarray(offsets).astype(np.int64)
+    lines = []
+    for r in range(off.shape[0] - 1):
+        if reads is None or not int(reads["flags"][r]) & A.SG_READ_CONTAINED:
+            lines.append("S\t%s\t*\tLN:i:%d" % (names[r], off[r + 1] - off[r]))
+    for v, t, _, ovl, _, flags, _, _ in np.asarray(arcs).tolist():
+        if reduced or not flags & A.SG_ARC_REDUCED:
+            lines.append("L\t%s\t%s\t%s\t%s\t%dM" % (names[v >> 1], "-" if v & 1 else "+", names[t >> 1], "-" if t & 1 else "+", ovl))
+    return lines
 
 
 def pile_depth(pile):
