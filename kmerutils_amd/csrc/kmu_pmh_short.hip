@@ -55,6 +55,7 @@ __global__ void __launch_bounds__(256) k_multiset_short(SketchArgs a) {
         uint32_t n_free_key = 0; // occurrences of the key that looks like a free slot (wave-uniform)
 #pragma unroll
         for (int j = 0; j < (int) (SHORT_KEYS / 64); j++) {
+            if (64u * (uint32_t) j >= nk) break; // (uniform: no lane has a k-mer in this slot or a later one)
             const uint32_t p = (uint32_t) lane + 64u * (uint32_t) j;
             const bool have = p < nk;
             uint64_t key = 0;

@@ -163,6 +163,13 @@ __global__ void __launch_bounds__(UQ_THREADS, MINW) k_multiset_uq(SketchArgs a) 
         auto bm_index = [&](uint64_t key) -> uint32_t {
             return (((uint32_t) key ^ (uint32_t) (key >> 32)) * 0x85EBCA6Bu) >> (32 - UQ_BM_BITS);
         };
+        // Register slots 4 g .. 4 g + 3 of all threads stand for places [4 UQ_THREADS g, 4 UQ_THREADS (g + 1)): a read of `span` places
+        // (its k-mers behind the lead of its first word) fills the first ceil(span / (4 UQ_THREADS)) groups and no slot of the others,
+        // for every thread alike -- a scalar compare per group and phase, and an empty group issues nothing (it used to run its LDS
+        // reads, compares, ballots and branch skeletons for nothing: the mean read of the first shape fills 2.6 of its 5 groups).
+        // Both phases skip by this one test: rk[] of a skipped group holds no key and is not looked at.
+        const uint32_t span = uniform_u32(nk + (lead - 16u * wfirst));
+        auto group_used = [&](int q0) -> bool { return 4u * (uint32_t) UQ_THREADS * (uint32_t) (q0 >> 2) < span; };
         bool over = false; // uniform: too many keys in collision groups
         if (mine) {
             // ---- keys: extract, closure, bitmaps; four positions' LDS round trips in flight at a time ----
@@ -174,6 +181,14 @@ __global__ void __launch_bounds__(UQ_THREADS, MINW) k_multiset_uq(SketchArgs a) 
                 constexpr bool FAST = decltype(fast_tag)::value;
 #pragma unroll
                 for (int q0 = 0; q0 < UQ_KREG; q0 += 4) {
+                    if (!group_used(q0)) {
+                        // (no instruction: the slots are told to hold nothing in particular.  Left alone they would carry the last
+                        //  read's keys around the read loop -- forty registers live through staging, prefetch and collision sort:
+                        //  101 / 66 spilled vector registers instead of 0 / 3)
+#pragma unroll
+                        for (int u = 0; u < 4; u++) rk[q0 + u] = __builtin_nondeterministic_value(rk[q0 + u]);
+                        continue;
+                    }
                     uint32_t bit[4], rbi[UQ_KREG];
                     const uint32_t wi = ((uint32_t) tid >> 2) + (uint32_t) (UQ_THREADS / 4) * (uint32_t) (q0 >> 2); // the quarter's word
                     const StepWin sw = step_win(words[wi], words[wi + 1], words[wi + 2], k);
@@ -234,6 +249,7 @@ __global__ void __launch_bounds__(UQ_THREADS, MINW) k_multiset_uq(SketchArgs a) 
             //  the kernel sits at its 128 registers, twenty more live values spill)
 #pragma unroll
             for (int q0 = 0; q0 < UQ_KREG; q0 += 4) {
+                if (!group_used(q0)) continue; // (its rk[] hold no key: the key phase skipped it by the same test)
                 bool uq[4], co[4];
                 uint64_t um[4], cm[4];
                 uint32_t ut = 0, ct = 0, rbi[UQ_KREG];
