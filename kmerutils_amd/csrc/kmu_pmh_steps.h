@@ -1,5 +1,5 @@
 // kmu_pmh_steps.h -- the device steps that two or more of the sketch kernel files share (kmu_pmh_general.hip, kmu_pmh_uq.hip,
-// kmu_pmh_short.hip, kmu_pmh_smallk.hip, kmu_pmh_points.hip): the slot minima and their q_max, the ProbMinHash3a point process of a key,
+// kmu_pmh_long.hip, kmu_pmh_short.hip, kmu_pmh_smallk.hip, kmu_pmh_points.hip): the slot minima and their q_max, the ProbMinHash3a point process of a key,
 // how reads are taken from the queue, the view of a queue entry, a k-mer out of staged code words.  A step only one file uses lives there.
 #pragma once
 

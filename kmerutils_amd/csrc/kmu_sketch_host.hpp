@@ -35,6 +35,18 @@ __host__ __device__ inline uint32_t pmh_leaf_bits(uint64_t n) {
     while (b < 22 && (n >> b) > 4096) b++;
     return b;
 }
+// k_multiset_long: a read of nk k-mers is cut into ceil(nk / PMH_LONG_TP) sub-lists by key hash.  At 16 384 keys a sub-list expects
+// n^2 / 2^18 = 1 024 keys in collision groups (of UQ2_COLL = 2 048) and stays 4 096 keys (~ 30 standard deviations) under the 20 480 that
+// a workgroup's registers hold.  The per-sequence route keeps reads of up to LONG_SEQ_KMERS = 2^18 k-mers: at most 16 sub-lists.
+// (Measured on the ONT workload, the stage per step: 12 288: 3.19 - 3.22 ms, 14 336: 3.17 - 3.18, 16 384: 3.11 - 3.15)
+static constexpr uint32_t PMH_LONG_TP = 16384;
+__host__ __device__ inline uint32_t pmh_long_parts(uint32_t nk) { return nk / PMH_LONG_TP + (nk % PMH_LONG_TP ? 1u : 0u); }
+// the sub-list of a key, 0 .. parts - 1.  The bitmap index and the collision sort's bucket of k_multiset_uq's step are both functions of
+// lo ^ hi of the key; this is one of lo + c hi, so the keys of one sub-list still spread evenly over bitmap bits and buckets.
+__host__ __device__ inline uint32_t pmh_long_part_of(uint64_t key, uint32_t parts) {
+    const uint32_t z = ((uint32_t) key + (uint32_t) (key >> 32) * 0x9E3779B9u) * 0xC2B2AE3Du;
+    return (uint32_t) (((uint64_t) z * parts) >> 32);
+}
 // SuperMinHash(2) over n pre-hashed values: chunks of at most 16 384, between 1 and 8192 of them
 __host__ __device__ inline uint64_t super_chunk_count(uint64_t n) {
     const uint64_t c = (n + 16383) / 16384;

@@ -1,5 +1,5 @@
 // kmu_sketch_kernels.h -- what the host side of the sketch path (kmu_sketch_pmh.hip: routes, launches; kmu_sketch.hip: the C entry points) needs of
-// the per-sequence sketch kernels (one file per route: kmu_pmh_general.hip, kmu_pmh_uq.hip, kmu_pmh_short.hip, kmu_pmh_smallk.hip, kmu_pmh_points.hip;
+// the per-sequence sketch kernels (one file per route: kmu_pmh_general.hip, kmu_pmh_uq.hip, kmu_pmh_long.hip, kmu_pmh_short.hip, kmu_pmh_smallk.hip, kmu_pmh_points.hip;
 // the small ones in kmu_sketch_aux.hip): their argument block, the constants their LDS budgets are made of, and their declarations (every
 // kernel file instantiates the template kernels it defines for exactly the forms listed here).
 #pragma once
@@ -123,6 +123,7 @@ template <bool SIG32>
 __global__ void __launch_bounds__(256) k_pmh_points(SketchArgs a);
 template <int UQ_THREADS, uint32_t UQ_BM_BITS, uint32_t UQ_COLL, int MINW>
 __global__ void __launch_bounds__(UQ_THREADS, MINW) k_multiset_uq(SketchArgs a);
+__global__ void __launch_bounds__(1024, 4) k_multiset_long(SketchArgs a); // kmu_pmh_long.hip
 __global__ void k_multiset_short(SketchArgs a);
 template <bool SIG32>
 __global__ void __launch_bounds__(256) k_pmh_points_short(SketchArgs a);

@@ -28,7 +28,8 @@ static bool smallk_route(const kmu_sketch_params *p, int hashed_bytes, bool part
 // The routes of a ProbMinHash3a / bottom-k call and the kernels they launch:
 //  SMALLK    k <= 8: k_sketch_smallk, with lists + k_pmh_points
 //  SHORT     whole unpacked reads of at most 256 k-mers: k_multiset_short + k_pmh_points_short
-//  UQ        whole unpacked reads: k_multiset_uq (two shapes), the list-emitting k_sketch_pmh3a for the rest, k_pmh_points
+//  UQ        whole unpacked reads: k_multiset_uq (two shapes), k_multiset_long for the longer ones, the list-emitting k_sketch_pmh3a for
+//            what that one hands back, k_pmh_points
 //  LISTS     whole reads, packed (or KMU_PMH_PLAIN=0): the list-emitting k_sketch_pmh3a + k_pmh_points
 //  ONE_PASS  whole unpacked reads without lists: PLAIN k_sketch_pmh3a, the reads it hands back through the general one
 //  GENERAL   the general k_sketch_pmh3a: bottom-k, AA / pre-hashed, packed, partial rows, blocks
@@ -279,8 +280,10 @@ static int launch_short(kmu_ctx *ctx, const SketchArgs &a, int cus) {
 
 // Whole unpacked DNA reads on the two-kernel route: the reads that fit one workgroup's registers (<= 10 240 k-mers: 87 % of
 // the reads, 64 % of the bases of the ONT workload) go through k_multiset_uq, which does not sort what occurs once; the
-// longer ones (and the rare read with too many repeated keys) are handed to the second shape, then to the general
-// list-emitting kernel (`kern`, reading its reads from a list; repetitive reads in rounds).
+// longer ones (and the rare read with too many repeated keys) are handed to the second shape; what that leaves -- reads of more than
+// 20 480 places, 9.8 % of the k-mers -- to k_multiset_long, which cuts a read into sub-lists by key hash and runs the same step on
+// each; and what THAT leaves (a read too repetitive for its sub-lists; none on the ONT workload) to the general list-emitting kernel
+// (`kern`, reading its reads from a list; repetitive reads in rounds), launched only if the count read back is not zero.
 static int launch_uq(kmu_ctx *ctx, SketchArgs a, sketch_kernel_t kern, const PmhShape &g, const PmhPlan &plan) {
     {
         const auto ka = k_multiset_uq<512, UQ1_BM, UQ1_COLL, 4>;
@@ -305,8 +308,22 @@ static int launch_uq(kmu_ctx *ctx, SketchArgs a, sketch_kernel_t kern, const Pmh
         KMU_TRY(launch(ctx, "k_multiset_uq", kb, dim3((unsigned) std::max<uint64_t>(1, std::min<uint64_t>(n_long, (uint64_t) plan.cus))), dim3(1024),
                        lds_b, b));
         KMU_TRY(read_count(ctx, a, &n_long));
-        a.redo_list = b.redo_list;
+        if (n_long) {
+            // what the second shape leaves (reads of more than 20 480 places, and the rare shorter one with too many repeated keys):
+            // k_multiset_long, one workgroup per CU over the general kernel's scratch (its grid is within pmh_shape's: def_keys is sized
+            // by that).  It writes its own leftovers to the first shape's list, which nobody reads any more.  The timer's name is the
+            // general kernel's: the sketch unit's stages are summed by name.
+            KMU_HIP(ctx, hipFuncSetAttribute((const void *) k_multiset_long, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+            KMU_HIP(ctx, hipMemsetAsync(a.queue, 0, 256, ctx->stream));
+            SketchArgs c = a;
+            c.read_list = rl2;
+            c.n_queue = n_long;
+            const uint64_t grid_c = std::min<uint64_t>(std::min<uint64_t>(n_long, (uint64_t) plan.cus), (uint64_t) g.grid);
+            KMU_TRY(launch(ctx, "k_sketch_pmh3a", k_multiset_long, dim3((unsigned) std::max<uint64_t>(1, grid_c)), dim3(1024), lds_b, c));
+            KMU_TRY(read_count(ctx, a, &n_long));
+        }
     }
+    // ... and the general kernel for the reads that one hands back: a sub-list beyond the registers, or too repetitive (none on the ONT workload)
     if (n_long) KMU_TRY(launch_listed(ctx, a, kern, g, n_long, "k_sketch_pmh3a"));
     KMU_HIP(ctx, hipMemsetAsync(a.queue, 0, 256, ctx->stream)); // (the points kernel's cursor; nothing is left to redo)
     return launch_points(ctx, a, plan.cus, plan.pts_long);
