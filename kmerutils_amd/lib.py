@@ -791,7 +791,10 @@ class Context:
         mem = self._mem(sig_a, sig_b)
         self._wait_producers(sig_a, sig_b)
         out = self._new_like(sig_a, (max(sig_a.shape[0], 1), max(sig_b.shape[0], 1)), np.uint16, "int16")
-        self._check(self.L.kmu_sig_equal_matrix(self.h, _ptr(sig_a)[0], sig_a.shape[0], _ptr(sig_b)[0], sig_b.shape[0],
+        # an empty array has no address worth passing (an empty device tensor's is null): the library reads no row of it
+        pa = _ptr(sig_a)[0] if sig_a.shape[0] else _ptr(out)[0]
+        pb = _ptr(sig_b)[0] if sig_b.shape[0] else _ptr(out)[0]
+        self._check(self.L.kmu_sig_equal_matrix(self.h, pa, sig_a.shape[0], pb, sig_b.shape[0],
                                                 sig_a.shape[1], self._sig_type_of(sig_a), mem, _ptr(out)[0]))
         return out[:sig_a.shape[0], :sig_b.shape[0]]
 
