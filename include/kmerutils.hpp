@@ -35,6 +35,8 @@
  *                 (supported segments of every read, chimera splits and trimmed reads)
  *                 GraphParams, OverlapClasses, sg_classify, OverlapGraph, overlap_graph, read_graph, unitig_labels, gfa_line
  *                 (overlap classes, contained reads, the transitively reduced string graph)
+ *                 Unitigs, sg_unitigs, UnitigSequences, unitig_sequences, ReadUnitigs, read_unitigs, unitig_gfa_line
+ *                 (the ordered reads of every unitig, their coordinates and the unitig's bases)
  *                 seed_chains, seed_pairs, chain_hits, read_chains (one base-resolution chain per read pair from minimizer
  *                                                            hits)                          (beyond the reference)
  *   counting      KmerCountT (trait), KmerCounter, KmerCounterPool, count_kmer_threaded_one_to_many
@@ -2507,6 +2509,103 @@ inline std::string gfa_line(const kmu_sg_arc &a, const std::string &name_from, c
 }
 /// ... and for a read: `S name * LN:i:len`
 inline std::string gfa_line(const std::string &name, uint64_t len) { return "S\t" + name + "\t*\tLN:i:" + std::to_string(len); }
+
+// =====================================================================================================================
+// unitig layout (kmu_sg_unitigs, kmu_sg_unitig_seqs; the reference has no such unit)
+// =====================================================================================================================
+
+/// What sg_unitigs returns: the unitigs numbered by their smallest read, the steps (unitig u's are path[first .. first + n_reads))
+/// and the place of every read (unitig KMU_SG_NONE: a contained read).
+struct Unitigs {
+    std::vector<kmu_sg_unitig> unitigs;
+    std::vector<kmu_sg_step> path;
+    std::vector<kmu_sg_place> place;
+};
+
+/// What unitig_sequences returns: the bases of all unitigs and the offset of every unitig into them.
+struct UnitigSequences {
+    std::vector<uint8_t> seq;
+    std::vector<uint64_t> seq_offsets;
+};
+
+/// What read_unitigs returns.
+struct ReadUnitigs {
+    Unitigs layout;
+    UnitigSequences sequences;
+};
+
+/// kmu_sg_unitigs on host arrays (minimizer.unitig_paths): the arcs whose `unique` is 1 as ordered paths of reads.  arcs, reads: of
+/// overlap_graph (reads empty: no read is contained); offsets: the batch's.  One library call: both counts are at most n_reads.
+inline Unitigs sg_unitigs(const std::vector<kmu_sg_arc> &arcs, const std::vector<kmu_sg_read> &reads, const std::vector<uint64_t> &offsets,
+                          Context &ctx = Context::global()) {
+    if (offsets.empty()) throw std::invalid_argument("sg_unitigs: the offsets of a batch have at least one entry");
+    const uint32_t n_reads = uint32_t(offsets.size() - 1);
+    if (!reads.empty() && reads.size() != n_reads) throw std::invalid_argument("sg_unitigs: as many summaries as reads, or none");
+    Unitigs out;
+    out.unitigs.assign(size_t(n_reads) + 1, kmu_sg_unitig{}); // an empty vector has no address worth passing
+    out.path.assign(size_t(n_reads) + 1, kmu_sg_step{});
+    out.place.assign(size_t(n_reads) + 1, kmu_sg_place{});
+    const kmu_sg_arc none{};
+    uint64_t n_steps = 0, total = 0;
+    ctx.check(kmu_sg_unitigs(ctx.raw(), arcs.empty() ? &none : arcs.data(), arcs.size(), reads.empty() ? nullptr : reads.data(), offsets.data(), n_reads,
+                             KMU_MEM_HOST, out.unitigs.data(), out.path.data(), out.place.data(), &n_steps, &total));
+    out.unitigs.resize(total);
+    out.path.resize(n_steps);
+    out.place.resize(n_reads);
+    return out;
+}
+
+/// kmu_sg_unitig_seqs on host arrays (minimizer.unitig_sequences): the bases of every unitig of a layout.  Two library calls: one
+/// that counts, one with exactly that capacity.
+inline UnitigSequences unitig_sequences(const Unitigs &layout, const std::vector<uint8_t> &bases, const std::vector<uint64_t> &offsets,
+                                        Context &ctx = Context::global()) {
+    if (offsets.empty()) throw std::invalid_argument("unitig_sequences: the offsets of a batch have at least one entry");
+    const uint32_t n_reads = uint32_t(offsets.size() - 1);
+    const kmu_sg_unitig no_unitig{};
+    const kmu_sg_step no_step{};
+    const uint8_t no_base = 0;
+    const kmu_sg_unitig *u = layout.unitigs.empty() ? &no_unitig : layout.unitigs.data();
+    const kmu_sg_step *s = layout.path.empty() ? &no_step : layout.path.data();
+    const uint8_t *b = bases.empty() ? &no_base : bases.data();
+    UnitigSequences out;
+    uint64_t total = 0;
+    ctx.check(kmu_sg_unitig_seqs(ctx.raw(), u, layout.unitigs.size(), s, layout.path.size(), b, offsets.data(), n_reads, KMU_MEM_HOST, nullptr, nullptr, 0,
+                                 &total));
+    out.seq.assign(total + 1, 0);
+    out.seq_offsets.assign(layout.unitigs.size() + 1, 0);
+    ctx.check(kmu_sg_unitig_seqs(ctx.raw(), u, layout.unitigs.size(), s, layout.path.size(), b, offsets.data(), n_reads, KMU_MEM_HOST,
+                                 out.seq_offsets.data(), out.seq.data(), total, &total));
+    out.seq.resize(total);
+    return out;
+}
+
+/// From the reads of a batch to their unitigs and the unitigs' bases (minimizer.read_unitigs): read_graph, sg_unitigs,
+/// unitig_sequences.
+template <class Kmer>
+ReadUnitigs read_unitigs(const detail::Batch &batch, size_t k, uint32_t w, const GraphParams &g = GraphParams(), FHash fhash = FHash::canon_invhash,
+                         uint32_t max_occ = 0, uint32_t max_gap = 5000, uint32_t band_chain = 500, uint32_t min_seeds = 3, uint32_t min_score = 0,
+                         uint32_t band = 64, Context &ctx = Context::global()) {
+    const detail::Batch b = detail::unpacked(batch);
+    if (b.on_device()) throw std::invalid_argument("read_unitigs returns host arrays: it needs the sequences in host memory");
+    const OverlapGraph graph = read_graph<Kmer>(batch, k, w, g, fhash, max_occ, max_gap, band_chain, min_seeds, min_score, band, ctx);
+    ReadUnitigs out;
+    out.layout = sg_unitigs(graph.arcs, graph.reads, b.offsets, ctx);
+    out.sequences = unitig_sequences(out.layout, b.bytes, b.offsets, ctx);
+    return out;
+}
+
+/// One line of GFA text for a unitig: `S utg%06d{l|c} <seq> LN:i:<len>` (minimizer.unitig_gfa_lines), seq being its bases.
+inline std::string unitig_gfa_line(uint64_t number, const kmu_sg_unitig &u, const std::string &seq) {
+    char name[32];
+    snprintf(name, sizeof name, "utg%06llu%c", (unsigned long long) number, (u.flags & KMU_SG_UNITIG_CIRCULAR) ? 'c' : 'l');
+    return std::string("S\t") + name + "\t" + seq + "\tLN:i:" + std::to_string(u.len);
+}
+/// ... and for a step of it: `a <utg> <end - c> <read name> <+|-> <c>`, c = end - before being the bytes the step contributes.
+inline std::string unitig_gfa_line(uint64_t number, const kmu_sg_unitig &u, const kmu_sg_step &s, uint64_t before, const std::string &read_name) {
+    char name[32];
+    snprintf(name, sizeof name, "utg%06llu%c", (unsigned long long) number, (u.flags & KMU_SG_UNITIG_CIRCULAR) ? 'c' : 'l');
+    return std::string("a\t") + name + "\t" + std::to_string(before) + "\t" + read_name + "\t" + (s.strand ? "-" : "+") + "\t" + std::to_string(s.end - before);
+}
 
 // =====================================================================================================================
 // counting (kmercount.rs)

@@ -1387,6 +1387,90 @@ int kmu_sg_graph(kmu_ctx *ctx, const kmu_chain *chains, const kmu_chain_aln *aln
                  uint64_t *arc_offsets_out,   /* 2 n_reads + 1; may be NULL */
                  uint64_t *n_out);            /* host memory in both modes; required */
 
+/* ---- unitig layout: the ordered reads of every unitig, their coordinates and the unitig's bases ----------------------
+ * Inputs of kmu_sg_unitigs: arcs[n_arcs], arc records as kmu_sg_graph writes them, in any order; reads[n_reads], its summaries, or
+ *   NULL (then no read is contained); offsets[n_reads + 1] of the batch -- only the lengths are used.  The result is a pure
+ *   function of the inputs, and the order of arcs does not matter.
+ * Links: only arcs with unique == 1 count.  A unique arc v -> w gives next(v) = w, prev(w) = v and in(w) = its len.  Every other
+ *   arc is ignored, so a branching vertex ends a unitig.
+ * Arc faults, found on the device in every unique arc; the call is refused with KMU_E_UNSUPPORTED at its one synchronisation, every
+ *   output is left untouched and no faulty arc is ever used as an index: from or to >= 2 n_reads; from >> 1 == to >> 1; len above
+ *   the length of the `to` read; the arc also carries KMU_SG_ARC_REDUCED; a vertex has two unique out-arcs or two unique in-arcs; a
+ *   unique arc v -> w has no unique arc w^1 -> v^1 (its mate); a unique arc touches a read that reads flags as contained.
+ *   With these checks the unique arcs form vertex-disjoint paths and cycles, each with a distinct twin on the other strand, and no
+ *   path holds both vertices of a read.  Proof: out- and in-degree are at most 1, so the components are paths and cycles.  The
+ *   mates of a path's arcs form the path of the complemented vertices backwards, its twin (two in-arcs of w would need two mates
+ *   out of w^1, which the out-degree check excludes just as well).  A path from v to v^1 would be its own twin, walked backwards;
+ *   its middle would be a vertex equal to its complement or an arc x -> x^1 between a read and itself, and neither exists.
+ * Members: with reads, a read flagged KMU_SG_READ_CONTAINED is on no unitig and its place is {KMU_SG_NONE, 0, 0, 0}.  Every other
+ *   read is on exactly one unitig; a read without a unique arc is a unitig of one read.
+ * Orientation: of a path (or cycle) and its twin, the one kept is the one whose smallest vertex id is even: the strand on which the
+ *   unitig's smallest read is forward.
+ * Order: a kept path runs from its vertex without prev to its vertex without next.  A kept cycle starts at its smallest vertex,
+ *   2 * min_read, and carries KMU_SG_UNITIG_CIRCULAR; the arc entering the start vertex closes the cycle and is not walked.
+ * Coordinates (64 bits): the contribution c(v) is in(v) if v has a unique in-arc -- the start of a cycle has one -- and the length
+ *   of its read otherwise.  end of a step (kmu_sg_step: read, strand, end) is the running sum of c along the unitig; len of a
+ *   unitig is the end of its last step, so for a cycle the sum of all its arcs' len.
+ * Numbering: unitigs are numbered by increasing min_read.  A unitig record (kmu_sg_unitig) is first, len, n_reads, flags, min_read,
+ *   0: first is the exclusive prefix sum of n_reads over that numbering, and unitig u's steps are path_out[first .. first +
+ *   n_reads).  place_out[r] (kmu_sg_place) = {unitig, rank within it, strand, 0}.  *n_out is the number of unitigs, *n_steps_out
+ *   the number of reads placed (both host memory in both modes); records beyond those counts are left untouched.  Both counts are
+ *   <= n_reads, so there is no count call.
+ * n_arcs == 0: every read that is not contained is its own unitig.  n_reads == 0: KMU_OK with zero unitigs.
+ * KMU_E_BAD_ARG (nothing is launched): null ctx / offsets / n_out / unitigs_out / path_out, null arcs with n_arcs > 0, bad mem,
+ *   arcs while there are no reads.  KMU_E_UNSUPPORTED: n_reads >= 2^31; the arc faults.
+ * KMU_MEM_DEVICE: every array except n_steps_out and n_out is device memory; the call synchronises the stream once, for the two
+ *   counts and the refusal flag, also in async_device contexts.  KMU_MEM_HOST: the arrays go up through the context's workspace and
+ *   the results come back.
+ * How: one lane per arc checks and links; one lane per vertex tests the mate; list ranking by pointer doubling backwards over prev,
+ *   ceil(log2(2 n_reads)) launches that read one buffer and write the other; the smallest vertex of every cycle is cut loose and the
+ *   rounds are launched once more (they return at once where nothing was cut); tails publish at their head, two scans over the reads number the unitigs and place their steps; one lane
+ *   per vertex writes.  The launch count depends on n_reads only.  Integer compares, idempotent stores and commuting integer
+ *   atomics only.  DESIGN.md 3.23 has the kernels.
+ *
+ * kmu_sg_unitig_seqs.  unitigs[n_unitigs] and path[n_steps] as kmu_sg_unitigs writes them (or any records that pass the checks
+ *   below; unitigs may share steps), bases and offsets[n_reads + 1] of the batch.  The sequence of a unitig is the concatenation
+ *   over its steps of the last c bytes of the read in the step's orientation, c = end - previous end with a previous end of 0 at
+ *   the first step.  Strand 0 copies bytes verbatim; strand 1 is the reverse complement: A<->T, C<->G, a<->t, c<->g, every other
+ *   byte N.  seq_offsets_out[n_unitigs + 1] (may be NULL) are the unitigs' offsets into seq_out.
+ *   *n_out (host memory in both modes) is always the total byte count.  seq_out == NULL: the count-only call, which writes *n_out
+ *   and nothing else.  cap < total: KMU_E_BAD_ARG with *n_out set and nothing else written.
+ *   KMU_E_BAD_ARG: null ctx / offsets / n_out, unitigs null with n_unitigs > 0, path null with n_steps > 0, bases null while bytes
+ *   are to be written, bad mem.  KMU_E_UNSUPPORTED, found on the device BEFORE anything is written (the outputs stay untouched):
+ *   first + n_reads > n_steps; a step's read >= n_reads; a strand > 1; ends decrease; a contribution above the read's length; the
+ *   last end is not len (a unitig without steps has len 0).  No record is used as an address before the check.
+ *   KMU_MEM_DEVICE: every array except n_out is device memory; two synchronisations (the check with the totals; the end).
+ *   How: an ITEM is a step of a unitig.  One lane per unitig checks its slice; scans give the offsets and the item numbering; one
+ *   lane per item finds its unitig by binary search and checks its step; after the synchronisation one lane per item stores its
+ *   global end seq_offsets[u] + end, and one wave per tile of 4096 OUTPUT bytes finds the item of its first byte by a 64-ary search
+ *   over those ends and walks on 64 bytes at a time, one per lane, as kmu_extract_ranges does. */
+#define KMU_SG_NONE 0xFFFFFFFFu
+#define KMU_SG_UNITIG_CIRCULAR 1u  /* kmu_sg_unitig.flags */
+typedef struct {         /* 16 bytes: one read of a path */
+    uint32_t read, strand;
+    uint64_t end;
+} kmu_sg_step;
+typedef struct {         /* 32 bytes */
+    uint64_t first, len;
+    uint32_t n_reads, flags, min_read, zero;
+} kmu_sg_unitig;
+typedef struct {         /* 16 bytes: per read */
+    uint32_t unitig, rank, strand, zero;
+} kmu_sg_place;
+int kmu_sg_unitigs(kmu_ctx *ctx, const kmu_sg_arc *arcs, uint64_t n_arcs,
+                   const kmu_sg_read *reads,    /* may be NULL */
+                   const uint64_t *offsets, uint32_t n_reads, int mem,
+                   kmu_sg_unitig *unitigs_out,  /* room for n_reads */
+                   kmu_sg_step *path_out,       /* room for n_reads */
+                   kmu_sg_place *place_out,     /* n_reads; may be NULL */
+                   uint64_t *n_steps_out,       /* host memory in both modes; may be NULL */
+                   uint64_t *n_out);            /* host memory in both modes; required */
+int kmu_sg_unitig_seqs(kmu_ctx *ctx, const kmu_sg_unitig *unitigs, uint64_t n_unitigs, const kmu_sg_step *path,
+                       uint64_t n_steps, const uint8_t *bases, const uint64_t *offsets, uint32_t n_reads, int mem,
+                       uint64_t *seq_offsets_out,   /* n_unitigs + 1; may be NULL */
+                       uint8_t *seq_out,            /* NULL: the count-only call */
+                       uint64_t cap, uint64_t *n_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -52,6 +52,8 @@ SG_SKIP, SG_SHORT, SG_LOWID, SG_INTERNAL, SG_A_CONTAINED, SG_B_CONTAINED, SG_DOV
 SG_CLASS_NAMES = ("skip", "short", "lowid", "internal", "a_contained", "b_contained", "dovetail")
 SG_READ_CONTAINED = 1    # kmu_sg_read.flags
 SG_ARC_REDUCED = 1       # kmu_sg_arc.flags
+SG_NONE = 0xFFFFFFFF     # kmu_sg_place.unitig of a contained read
+SG_UNITIG_CIRCULAR = 1   # kmu_sg_unitig.flags
 
 
 def kmer_val_bytes(kmer_type):
@@ -230,6 +232,10 @@ class SgArc(C.Structure):
 SG_READ_DTYPE = [("flags", "<u4"), ("n_records", "<u4"), ("out_fwd", "<u4"), ("out_rev", "<u4")]
 SG_ARC_DTYPE = [("from", "<u4"), ("to", "<u4"), ("len", "<u4"), ("ovl", "<u4"), ("rec", "<u4"), ("flags", "<u4"), ("unique", "<u4"),
                 ("zero", "<u4")]
+# the records of kmu_sg_unitigs (16, 32 and 16 bytes)
+SG_STEP_DTYPE = [("read", "<u4"), ("strand", "<u4"), ("end", "<u8")]
+SG_UNITIG_DTYPE = [("first", "<u8"), ("len", "<u8"), ("n_reads", "<u4"), ("flags", "<u4"), ("min_read", "<u4"), ("zero", "<u4")]
+SG_PLACE_DTYPE = [("unitig", "<u4"), ("rank", "<u4"), ("strand", "<u4"), ("zero", "<u4")]
 
 
 class ReadPile(C.Structure):

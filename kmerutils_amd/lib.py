@@ -39,6 +39,7 @@ SYMBOLS = [
     "kmu_minimizer_layout", "kmu_read_minimizers", "kmu_seed_chains", "kmu_chain_align",
     "kmu_chain_cigar", "kmu_chain_pileup", "kmu_pile_call", "kmu_pile_ins_plan", "kmu_chain_pile_ins", "kmu_pile_consensus",
     "kmu_pile_segments", "kmu_extract_ranges", "kmu_pile_consensus_pos", "kmu_sg_classify", "kmu_sg_graph",
+    "kmu_sg_unitigs", "kmu_sg_unitig_seqs",
 ]
 
 
@@ -165,6 +166,8 @@ def load():
     L.kmu_sg_classify.argtypes = [vp, vp, vp, C.c_uint64, vp, C.c_uint32, C.POINTER(A.SgParams), C.c_int, vp, vp]
     L.kmu_sg_graph.argtypes = [vp, vp, vp, C.c_uint64, vp, C.c_uint32, C.POINTER(A.SgParams), C.c_int, vp, vp, vp, C.c_uint64, vp,
                                C.POINTER(C.c_uint64)]
+    L.kmu_sg_unitigs.argtypes = [vp, vp, C.c_uint64, vp, vp, C.c_uint32, C.c_int, vp, vp, vp, u64p, u64p]
+    L.kmu_sg_unitig_seqs.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, vp, vp, C.c_uint32, C.c_int, vp, vp, C.c_uint64, u64p]
     L.kmu_set_hll_params.argtypes = [vp, C.POINTER(A.HllParams)]
     L.kmu_kmer_hashes_compact.argtypes = [vp, C.POINTER(A.HashParams), vp, vp, vp, C.c_uint32, vp, C.c_uint64, u64p]
     L.kmu_sketch_partial_words.argtypes = [C.POINTER(A.SketchParams)]
@@ -1349,6 +1352,63 @@ class Context:
             arcs = np.zeros(max(cap, 1), np.dtype(A.SG_ARC_DTYPE))
         self._check(self.L.kmu_sg_graph(*args, _ptr(classes)[0], _ptr(reads)[0], _ptr(arcs)[0], cap, _ptr(arc_off)[0], C.byref(total)))
         return arcs[:cap], arc_off, classes[:n], reads[:n_reads]
+
+    def sg_unitigs(self, arcs, reads, offsets):
+        """kmu_sg_unitigs: the unitigs of a string graph as ordered paths of reads -- the arcs whose `unique` is 1 are the links,
+        every read that is not contained lies on exactly one unitig, a circular one starts at its smallest read (include/kmu.h has
+        the rules).  arcs: the records of sg_graph, in any order; reads: its summaries, or None (no read is contained); offsets: the
+        batch's, of which only the lengths count.  Returns (unitigs, path, place): A.SG_UNITIG_DTYPE records numbered by their
+        smallest read, A.SG_STEP_DTYPE records (unitig u's are path[first : first + n_reads]) and A.SG_PLACE_DTYPE records, one per
+        read; for torch cuda tensors int32 [n, 8], [n_steps, 4] and [n_reads, 4] tensors holding the same bits, on the device.  One
+        library call: both counts are at most n_reads."""
+        if not _is_torch(arcs):
+            arcs = np.ascontiguousarray(arcs)
+        if reads is not None and not _is_torch(reads):
+            reads = np.ascontiguousarray(reads)
+        mem = self._mem(arcs, reads)
+        n = int(arcs.shape[0])
+        off = self._offsets_like(offsets, arcs, mem)
+        n_reads = int(off.shape[0]) - 1
+        if reads is not None and int(reads.shape[0]) != n_reads:
+            raise ValueError("%d reads need as many summaries" % n_reads)
+        if mem == A.MEM_DEVICE:
+            unitigs = self._new_like(arcs, (max(n_reads, 1), 8), np.int32, "int32")
+            path = self._new_like(arcs, (max(n_reads, 1), 4), np.int32, "int32")
+            place = self._new_like(arcs, (max(n_reads, 1), 4), np.int32, "int32")
+        else:
+            unitigs = np.zeros(max(n_reads, 1), np.dtype(A.SG_UNITIG_DTYPE))
+            path = np.zeros(max(n_reads, 1), np.dtype(A.SG_STEP_DTYPE))
+            place = np.zeros(max(n_reads, 1), np.dtype(A.SG_PLACE_DTYPE))
+        none = self._new_like(arcs, 16, np.uint8, "uint8")  # an empty array has no address worth passing
+        n_steps, total = C.c_uint64(0), C.c_uint64(0)
+        self._check(self.L.kmu_sg_unitigs(self.h, _ptr(arcs if n else none)[0], n, _ptr(reads if n_reads else None)[0], _ptr(off)[0], n_reads, mem,
+                                          _ptr(unitigs)[0], _ptr(path)[0], _ptr(place)[0], C.byref(n_steps), C.byref(total)))
+        return unitigs[:int(total.value)], path[:int(n_steps.value)], place[:n_reads]
+
+    def sg_unitig_seqs(self, unitigs, path, bases, offsets):
+        """kmu_sg_unitig_seqs: the bases of every unitig -- over its steps, the last end - previous end bytes of the read in the
+        step's orientation; strand 1 is the reverse complement, which turns every byte that is not one of ACGTacgt into N.  unitigs,
+        path: the records of sg_unitigs; bases, offsets: the batch.  Returns (seq, seq_offsets): uint8 and uint64 [n_unitigs + 1]
+        (int64 holding the same bits for torch), where the arrays live.  The library is called twice: for the total, then for the
+        bytes."""
+        if not _is_torch(unitigs):
+            unitigs, path = np.ascontiguousarray(unitigs), np.ascontiguousarray(path)
+        mem = self._mem(unitigs, path, bases)
+        n, n_steps = int(unitigs.shape[0]), int(path.shape[0])
+        off = self._offsets_like(offsets, bases, mem)
+        n_reads = int(off.shape[0]) - 1
+        seq_off = self._new_like(bases, n + 1, np.uint64, "int64")
+        none = self._new_like(bases, 16, np.uint8, "uint8")  # an empty array has no address worth passing
+
+        def ptr(x):
+            return _ptr(x)[0] if int(x.shape[0]) else _ptr(none)[0]
+        args = (self.h, ptr(unitigs), n, ptr(path), n_steps, ptr(bases), _ptr(off)[0], n_reads, mem)
+        total = C.c_uint64(0)
+        self._check(self.L.kmu_sg_unitig_seqs(*args, None, None, 0, C.byref(total)))
+        cap = int(total.value)
+        seq = self._new_like(bases, max(cap, 1), np.uint8, "uint8")
+        self._check(self.L.kmu_sg_unitig_seqs(*args, _ptr(seq_off)[0], _ptr(seq)[0], cap, C.byref(total)))
+        return seq[:cap], seq_off
 
     def _components(self, call, like, n_nodes, want, count):
         """the outputs of kmu_components / kmu_components_knn allocated where `like` lives, call(*output pointers) run on them,

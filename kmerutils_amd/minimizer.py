@@ -21,6 +21,9 @@ to (cons_bases, cons_offsets, reads) in one call, and what it returns goes strai
 `classify_chains` and `overlap_graph` hand the chains and their records to kmu_sg_classify / kmu_sg_graph (Context.sg_classify,
 Context.sg_graph): the class of every overlap, the contained reads and the transitively reduced string graph; `read_graph` goes
 from reads to the graph, `unitig_labels` groups the reads of one unitig and `gfa_lines` writes the graph as GFA text on the host.
+`unitig_paths` and `unitig_sequences` hand the arcs to kmu_sg_unitigs / kmu_sg_unitig_seqs (Context.sg_unitigs,
+Context.sg_unitig_seqs): the reads of every unitig in walk order with their coordinates, and the unitig's bases; `read_unitigs`
+goes from reads to unitig sequences, and `unitig_gfa_lines` writes them as GFA `S` and `a` lines on the host.
 """
 import collections
 
@@ -283,6 +286,49 @@ def unitig_labels(ctx, arcs, n_reads):
         import torch
         return torch.minimum(label[0::2], label[1::2])
     return np.minimum(label[0::2], label[1::2])
+
+
+def unitig_paths(ctx, arcs, reads, offsets):
+    """The unitigs of a string graph as ordered paths (kmu_sg_unitigs): (unitigs, path, place) as Context.sg_unitigs returns them --
+    which reads lie on every unitig, in which order and orientation, and where each ends.  arcs, reads: the records and the
+    summaries of overlap_graph (reads=None: no read is contained)."""
+    return ctx.sg_unitigs(arcs, reads, offsets)
+
+
+def unitig_sequences(ctx, unitigs, path, bases, offsets):
+    """The bases of every unitig (kmu_sg_unitig_seqs): (seq, seq_offsets) as Context.sg_unitig_seqs returns them.  On error-free
+    reads a unitig's sequence is the genome stretch it covers; on corrected reads (correct_reads, then read_graph on the new batch)
+    it is a draft contig."""
+    return ctx.sg_unitig_seqs(unitigs, path, bases, offsets)
+
+
+def read_unitigs(ctx, bases, offsets, k, w, fhash=A.FHASH_CANON_INVHASH, max_occ=0, max_gap=5000, band_chain=500, min_seeds=3, min_score=0,
+                 band=64, min_overlap=500, max_hang=1000, int_permille=250, min_identity_permille=0, fuzz=10):
+    """From the reads of a batch to their unitigs in one call: read_graph, unitig_paths, unitig_sequences.  Returns (unitigs, path,
+    place, seq, seq_offsets); with torch cuda tensors nothing leaves the device."""
+    arcs, _, _, reads = read_graph(ctx, bases, offsets, k, w, fhash, max_occ, max_gap, band_chain, min_seeds, min_score, band, min_overlap,
+                                   max_hang, int_permille, min_identity_permille, fuzz)
+    unitigs, path, place = unitig_paths(ctx, arcs, reads, offsets)
+    seq, seq_offsets = unitig_sequences(ctx, unitigs, path, bases, offsets)
+    return unitigs, path, place, seq, seq_offsets
+
+
+def unitig_gfa_lines(unitigs, path, seq, seq_offsets, names):
+    """The unitigs as GFA text, on the host: `S utg%06d{l|c} <seq> LN:i:<len>` for every unitig (l: linear, c: circular), each
+    followed by `a <utg> <end - c> <read name> <+|-> <c>` for every step, c being the bytes the step contributes.  unitigs, path:
+    numpy A.SG_UNITIG_DTYPE and A.SG_STEP_DTYPE records; seq, seq_offsets: of unitig_sequences, numpy."""
+    text = np.asarray(seq).astype(np.uint8).tobytes().decode("latin-1")
+    soff = np.asarray(seq_offsets).astype(np.int64)
+    steps = np.asarray(path).tolist()
+    lines = []
+    for u, (first, length, n, flags, _, _) in enumerate(np.asarray(unitigs).tolist()):
+        name = "utg%06d%s" % (u, "c" if flags & A.SG_UNITIG_CIRCULAR else "l")
+        lines.append("S\t%s\t%s\tLN:i:%d" % (name, text[soff[u]:soff[u + 1]], length))
+        before = 0
+        for read, strand, end in steps[first:first + n]:
+            lines.append("a\t%s\t%d\t%s\t%s\t%d" % (name, before, names[read], "-" if strand else "+", end - before))
+            before = end
+    return lines
 
 
 def gfa_lines(arcs, names, offsets, reduced=False, reads=None):
