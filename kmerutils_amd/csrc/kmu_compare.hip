@@ -90,16 +90,6 @@ __global__ void __launch_bounds__(256) k_minhash_distance(const uint64_t *a, con
     }
 }
 
-// stage `bytes` of a host buffer (or pass a device pointer through)
-static int to_device(kmu_ctx *ctx, const char *name, const void *p, size_t bytes, int mem, const void **out) {
-    if (mem == KMU_MEM_DEVICE || !p) { *out = p; return KMU_OK; }
-    void *d;
-    KMU_TRY(dev_buf(ctx, name, bytes ? bytes : 1, &d));
-    if (bytes) KMU_HIP(ctx, hipMemcpyAsync(d, p, bytes, hipMemcpyHostToDevice, ctx->stream));
-    *out = d;
-    return KMU_OK;
-}
-
 } // namespace kmu
 
 using namespace kmu;
@@ -119,10 +109,10 @@ int kmu_sig_equal_pairs(kmu_ctx *ctx, const void *sig_a, uint32_t na, const void
         for (uint64_t p = 0; p < n_pairs; p++)
             if (ia[p] >= na || ib[p] >= nb) return fail(ctx, KMU_E_BAD_ARG, "pair %llu names a row out of range", (unsigned long long) p);
     const void *da, *db, *dia, *dib;
-    KMU_TRY(to_device(ctx, "cmp.a", sig_a, (size_t) na * m * wb, mem, &da));
-    KMU_TRY(to_device(ctx, "cmp.b", sig_b, (size_t) nb * m * wb, mem, &db));
-    KMU_TRY(to_device(ctx, "cmp.ia", ia, n_pairs * 4, mem, &dia));
-    KMU_TRY(to_device(ctx, "cmp.ib", ib, n_pairs * 4, mem, &dib));
+    KMU_TRY(stage_to_device(ctx, "cmp.a", sig_a, (size_t) na * m * wb, mem, &da));
+    KMU_TRY(stage_to_device(ctx, "cmp.b", sig_b, (size_t) nb * m * wb, mem, &db));
+    KMU_TRY(stage_to_device(ctx, "cmp.ia", ia, n_pairs * 4, mem, &dia));
+    KMU_TRY(stage_to_device(ctx, "cmp.ib", ib, n_pairs * 4, mem, &dib));
     uint32_t *dout = out;
     if (mem == KMU_MEM_HOST) KMU_TRY(dev_array(ctx, "cmp.out", n_pairs, &dout));
     const int grid = grid_for(ctx, n_pairs, 4, 16);
@@ -141,8 +131,8 @@ int kmu_sig_equal_matrix(kmu_ctx *ctx, const void *sig_a, uint32_t na, const voi
     if (na == 0 || nb == 0) return KMU_OK;
     const int wb = sig_word_bytes(sig_type);
     const void *da, *db;
-    KMU_TRY(to_device(ctx, "cmp.a", sig_a, (size_t) na * m * wb, mem, &da));
-    KMU_TRY(to_device(ctx, "cmp.b", sig_b, (size_t) nb * m * wb, mem, &db));
+    KMU_TRY(stage_to_device(ctx, "cmp.a", sig_a, (size_t) na * m * wb, mem, &da));
+    KMU_TRY(stage_to_device(ctx, "cmp.b", sig_b, (size_t) nb * m * wb, mem, &db));
     uint16_t *dout = out;
     if (mem == KMU_MEM_HOST) KMU_TRY(dev_array(ctx, "cmp.out", (size_t) na * nb, &dout));
     const uint64_t tiles = (uint64_t) ((na + MT - 1) / MT) * ((nb + MT - 1) / MT);
@@ -164,10 +154,10 @@ int kmu_minhash_distance_pairs(kmu_ctx *ctx, const uint64_t *hashes_a, uint32_t 
         for (uint64_t p = 0; p < n_pairs; p++)
             if (ia[p] >= na || ib[p] >= nb) return fail(ctx, KMU_E_BAD_ARG, "pair %llu names a row out of range", (unsigned long long) p);
     const void *da, *db, *dia, *dib;
-    KMU_TRY(to_device(ctx, "cmp.a", hashes_a, (size_t) na * m * 8, mem, &da));
-    KMU_TRY(to_device(ctx, "cmp.b", hashes_b, (size_t) nb * m * 8, mem, &db));
-    KMU_TRY(to_device(ctx, "cmp.ia", ia, n_pairs * 4, mem, &dia));
-    KMU_TRY(to_device(ctx, "cmp.ib", ib, n_pairs * 4, mem, &dib));
+    KMU_TRY(stage_to_device(ctx, "cmp.a", hashes_a, (size_t) na * m * 8, mem, &da));
+    KMU_TRY(stage_to_device(ctx, "cmp.b", hashes_b, (size_t) nb * m * 8, mem, &db));
+    KMU_TRY(stage_to_device(ctx, "cmp.ia", ia, n_pairs * 4, mem, &dia));
+    KMU_TRY(stage_to_device(ctx, "cmp.ib", ib, n_pairs * 4, mem, &dib));
     uint32_t *dout = out;
     if (mem == KMU_MEM_HOST) {
         void *q;

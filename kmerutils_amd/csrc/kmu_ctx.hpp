@@ -126,6 +126,12 @@ inline int stage_to_device(kmu_ctx *ctx, const char *name, const void *p, size_t
     *out = d;
     return KMU_OK;
 }
+// a device array of the workspace to a caller's array that lives where `mem` says
+inline int copy_out(kmu_ctx *ctx, void *dst, const void *src, size_t bytes, int mem) {
+    if (!dst || !bytes) return KMU_OK;
+    KMU_HIP(ctx, hipMemcpyAsync(dst, src, bytes, mem == KMU_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, ctx->stream));
+    return KMU_OK;
+}
 inline int host_buf(kmu_ctx *ctx, const char *name, size_t bytes, void **out) {
     auto &b = ctx->hbufs[name];
     if (b.bytes < bytes) {

@@ -180,15 +180,6 @@ __global__ void __launch_bounds__(256) k_sig_knn_merge(const uint64_t *__restric
     }
 }
 
-static int knn_to_device(kmu_ctx *ctx, const char *name, const void *p, size_t bytes, int mem, const void **out) {
-    if (mem == KMU_MEM_DEVICE || !p) { *out = p; return KMU_OK; }
-    void *d;
-    KMU_TRY(dev_buf(ctx, name, bytes ? bytes : 1, &d));
-    if (bytes) KMU_HIP(ctx, hipMemcpyAsync(d, p, bytes, hipMemcpyHostToDevice, ctx->stream));
-    *out = d;
-    return KMU_OK;
-}
-
 static uint64_t env_u64(const char *name, uint64_t dflt) {
     const char *e = getenv(name);
     if (!e || !*e) return dflt;
@@ -226,12 +217,12 @@ extern "C" int kmu_sig_knn(kmu_ctx *ctx, const void *sig_q, uint32_t nq, const v
         KMU_HIP(ctx, hipMemsetAsync(deq, 0, n_out * 2, ctx->stream));
     } else {
         const void *dq, *ddb, *dgq = nullptr, *dgdb = nullptr;
-        KMU_TRY(knn_to_device(ctx, "knn.q", sig_q, (size_t) nq * m * wb, mem, &dq));
+        KMU_TRY(stage_to_device(ctx, "knn.q", sig_q, (size_t) nq * m * wb, mem, &dq));
         if (sig_db == sig_q && ndb == nq) ddb = dq; // a self-join is staged once
-        else KMU_TRY(knn_to_device(ctx, "knn.db", sig_db, (size_t) ndb * m * wb, mem, &ddb));
+        else KMU_TRY(stage_to_device(ctx, "knn.db", sig_db, (size_t) ndb * m * wb, mem, &ddb));
         if (group_q) {
-            KMU_TRY(knn_to_device(ctx, "knn.gq", group_q, (size_t) nq * 4, mem, &dgq));
-            KMU_TRY(knn_to_device(ctx, "knn.gdb", group_db, (size_t) ndb * 4, mem, &dgdb));
+            KMU_TRY(stage_to_device(ctx, "knn.gq", group_q, (size_t) nq * 4, mem, &dgq));
+            KMU_TRY(stage_to_device(ctx, "knn.gdb", group_db, (size_t) ndb * 4, mem, &dgdb));
         }
         // database segments: enough workgroups for every CU a few times over, no more (each segment costs a partial list
         // per query row).  KMU_KNN_SEG_ROWS fixes the segment height (tests: several segments on a small database).

@@ -1,5 +1,6 @@
 // kmu_pile_segments.hip -- read trimming: the supported segments of every read with a class per read (kmu_pile_segments), and a new
-// batch from byte ranges of a batch (kmu_extract_ranges).  The contracts are in include/kmu.h, the arithmetic in kmu_seg_core.h.
+// batch from byte ranges of a batch (kmu_extract_ranges).  The contracts are in include/kmu.h, the arithmetic in kmu_seg_core.h; the
+// walk from the ranges' offsets to the output bytes is the segmented byte gather of kmu_gather.h.
 //
 // Tiles are SEG_TILE consecutive POSITIONS 0 .. n_rows of the batch, whatever read they belong to (position g stands for row g and for
 // the end of row g - 1; kmu_seg_core.h says why), so a chromosome-long read is many waves' work.
@@ -18,10 +19,10 @@
 //  k_seg_reads    one lane per read over its kept segments: the ranks, the summary, and whether it has a segment at all.
 //  k_seg_longest  (KMU_SEG_LONGEST) one lane per read that has one: its longest segment, at the scan of the "has" flags.
 //  k_ext_lens     one lane per range: the check, and the length as two 32-bit halves (two scans make 64-bit offsets of them).
-//  k_ext_offsets  one lane per range (and one for the end): out_offsets from the two scans.
-//  k_ext_copy     one wave per tile of EXT_TILE output bytes, 64 bytes per trip, one byte per lane.
+//  k_ext_offsets  one lane per range (and one for the end): out_offsets from the two scans (k_gather_offsets under this timer name).
+//  k_ext_copy     gather_tiles over out_offsets: byte o of range r comes from begin[r] + (o - out_offsets[r]).
 #include "kmu_ctx.hpp"
-#include "kmu_device.h"
+#include "kmu_gather.h"
 #include "kmu_seg_core.h"
 
 namespace kmu {
@@ -114,7 +115,7 @@ __global__ void __launch_bounds__(256) k_seg_keep(SegArgs p) {
         const uint64_t s = p.starts[k], e = p.ends[k];
         uint32_t keep = 0, r = 0;
         if (s < e && e <= p.n_rows) { // (always)
-            r = seg_find_read(p.off, p.n_reads, s);
+            r = (uint32_t) gather_upper_index(p.off, p.n_reads, s); // (at most n_reads)
             if (r < p.n_reads) {
                 const uint32_t len = (uint32_t) (e - s);
                 atomicAdd(&p.reads[r].n_good, len);
@@ -207,67 +208,16 @@ __global__ void __launch_bounds__(256) k_ext_lens(ExtArgs p) {
     if (bad) p.info[0] = 1u;
 }
 
-__global__ void __launch_bounds__(256) k_ext_offsets(ExtArgs p) {
-    for (uint64_t i = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x; i <= p.n_ranges; i += (uint64_t) gridDim.x * blockDim.x)
-        p.out_off[i] = p.off_lo[i] + (p.off_hi[i] << 32);
-}
-
-// largest i in [0, n] with off[i] <= g, g wave-uniform: the 64-ary search of wave_find_read (kmu_flat.h) over a 64-bit index, since
-// n_ranges is a uint64, and over n + 1 entries
-__device__ __forceinline__ uint64_t ext_find_range(const uint64_t *off, uint64_t n, uint64_t g) {
-    uint64_t lo = 0, hi = n + 1u; // off[lo] <= g; off[hi] > g or hi == n + 1
-    const uint32_t lane = (uint32_t) lane_id();
-    while (hi - lo > 1u) {
-        const uint64_t step = (hi - lo + 63u) / 64u, idx = lo + (uint64_t) (lane + 1u) * step;
-        const bool le = idx < hi && off[idx] <= g;
-        const uint32_t c = (uint32_t) __popcll(__ballot(le));
-        const uint64_t nhi = lo + (uint64_t) (c + 1u) * step;
-        lo += (uint64_t) c * step;
-        hi = nhi < hi ? nhi : hi;
-    }
-    return lo;
-}
-
 __global__ void __launch_bounds__(256) k_ext_copy(ExtArgs p) {
-    const uint32_t lane = (uint32_t) lane_id();
-    for (uint64_t t = (uint64_t) blockIdx.x * 4u + (threadIdx.x >> 6); t < p.n_tiles; t += (uint64_t) gridDim.x * 4u) {
-        uint64_t pos = t * EXT_TILE;
-        const uint64_t tile_end = pos + EXT_TILE < p.total ? pos + EXT_TILE : p.total;
-        uint64_t r0 = ext_find_range(p.out_off, p.n_ranges, pos); // out_off[r0] <= pos
-        while (pos < tile_end) {
-            // the window: the 64 offsets behind r0, one per lane (beyond the last: never reached)
-            const uint64_t wi = r0 + 1u + lane, win = wi <= p.n_ranges ? p.out_off[wi] : ~0ull;
-            const uint64_t w63 = ((uint64_t) readlane_u32((uint32_t) (win >> 32), 63) << 32) | readlane_u32((uint32_t) win, 63);
-            if (w63 <= pos) { // 64 ranges that end at or before pos: empty ones
-                r0 += 64u;
-                continue;
-            }
-            uint64_t limit = pos + 64u < tile_end ? pos + 64u : tile_end;
-            limit = w63 < limit ? w63 : limit; // (> pos) every byte below has its range inside the window
-            const uint64_t o = pos + lane;
-            const uint32_t c = ext_window_count(
-                [&](uint32_t j) { return ((uint64_t) (uint32_t) __shfl((int) (win >> 32), (int) j, 64) << 32) | (uint32_t) __shfl((int) (uint32_t) win, (int) j, 64); }, o);
-            if (o < limit) {
-                const uint64_t r = r0 + c; // (c <= 63 and out_off[r] <= o < out_off[r + 1] <= total: r < n_ranges)
-                const uint64_t src = p.begin[r] + (o - p.out_off[r]);
-                if (r < p.n_ranges && src < p.n_bases) p.out[o] = p.bases[src]; // (k_ext_lens has checked the ranges: always)
-            }
-            r0 += (uint32_t) __popcll(__ballot(win <= limit));
-            pos = limit;
-        }
-    }
+    gather_tiles(p.out_off, p.n_ranges, p.total, p.n_tiles, [&](uint64_t r, uint64_t o) {
+        const uint64_t src = p.begin[r] + (o - p.out_off[r]);
+        if (r < p.n_ranges && src < p.n_bases) p.out[o] = p.bases[src]; // (k_ext_lens has checked the ranges: always)
+    });
 }
 
 } // namespace kmu
 
 using namespace kmu;
-
-// a device array of the workspace to a caller's array that lives where `mem` says
-static int seg_copy_out(kmu_ctx *ctx, void *dst, const void *src, size_t bytes, int mem) {
-    if (!dst || !bytes) return KMU_OK;
-    KMU_HIP(ctx, hipMemcpyAsync(dst, src, bytes, mem == KMU_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, ctx->stream));
-    return KMU_OK;
-}
 
 extern "C" int kmu_pile_segments(kmu_ctx *ctx, const uint32_t *pile, const uint64_t *offsets, uint32_t n_reads, const kmu_pile_seg_params *p, int mem,
                                  uint64_t *seg_offsets_out, kmu_pile_seg *segs_out, uint64_t cap, uint64_t *n_segs_out, kmu_read_trim *reads_out) {
@@ -374,8 +324,8 @@ extern "C" int kmu_pile_segments(kmu_ctx *ctx, const uint32_t *pile, const uint6
     }
     uint64_t total = 0;
     KMU_HIP(ctx, hipMemcpyAsync(&total, out_off + n_reads, 8, hipMemcpyDeviceToHost, ctx->stream));
-    KMU_TRY(seg_copy_out(ctx, seg_offsets_out, out_off, ((size_t) n_reads + 1) * 8, mem));
-    KMU_TRY(seg_copy_out(ctx, reads_out, a.reads, (size_t) n_reads * sizeof(kmu_read_trim), mem));
+    KMU_TRY(copy_out(ctx, seg_offsets_out, out_off, ((size_t) n_reads + 1) * 8, mem));
+    KMU_TRY(copy_out(ctx, reads_out, a.reads, (size_t) n_reads * sizeof(kmu_read_trim), mem));
     KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
     *n_segs_out = total;
     if (segs_out && cap < total) {
@@ -383,7 +333,7 @@ extern "C" int kmu_pile_segments(kmu_ctx *ctx, const uint32_t *pile, const uint6
         return fail(ctx, KMU_E_BAD_ARG, "cap = %llu is below the %llu segments", (unsigned long long) cap, (unsigned long long) total);
     }
     if (segs_out && total) {
-        KMU_TRY(seg_copy_out(ctx, segs_out, out_segs, (size_t) total * sizeof(kmu_pile_seg), mem));
+        KMU_TRY(copy_out(ctx, segs_out, out_segs, (size_t) total * sizeof(kmu_pile_seg), mem));
         KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
     }
     if (ctx->profiling) profile_collect(ctx);
@@ -439,10 +389,10 @@ extern "C" int kmu_extract_ranges(kmu_ctx *ctx, const uint8_t *bases, uint64_t n
         return fail(ctx, KMU_E_UNSUPPORTED, "a range with begin > end or end > n_bases = %llu", (unsigned long long) n_bases);
     }
     a.total = t_lo + (t_hi << 32);
-    a.n_tiles = (a.total + EXT_TILE - 1u) / EXT_TILE;
+    a.n_tiles = (a.total + GATHER_TILE - 1u) / GATHER_TILE;
     a.out_off = out_offsets;
     if (mem == KMU_MEM_HOST) KMU_TRY(dev_array(ctx, "ext.outoff", n_ranges + 1, &a.out_off));
-    KMU_TRY(launch(ctx, "k_ext_offsets", k_ext_offsets, grid_n, dim3(256), 0, a));
+    KMU_TRY(launch(ctx, "k_ext_offsets", k_gather_offsets, grid_n, dim3(256), 0, a.off_lo, a.off_hi, n_ranges, a.out_off));
     if (mem == KMU_MEM_HOST) KMU_HIP(ctx, hipMemcpyAsync(out_offsets, a.out_off, (size_t) (n_ranges + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
     *n_out = a.total;
     if (out && cap < a.total) {

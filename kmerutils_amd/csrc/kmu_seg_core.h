@@ -1,7 +1,8 @@
 // kmu_seg_core.h -- the arithmetic of read trimming: what a table row says about its support, when two consecutive rows are linked,
-// where a supported segment starts and ends, the summary of a read from its kept segments, and the window lookup of
+// where a supported segment starts and ends, the summary of a read from its kept segments, and the check of a range of
 // kmu_extract_ranges; for the device and for a host compiler alike (tests/cpp/sim_pile_segments.cpp drives these functions over 64
-// simulated lanes; the contracts are in include/kmu.h).
+// simulated lanes; the contracts are in include/kmu.h).  The read that holds a row (gather_upper_index) and the arithmetic
+// of kmu_extract_ranges' copy are in kmu_gather_core.h.
 //
 // The row pass works on POSITIONS g = 0 .. n_rows, one more than there are rows: the lane of position g knows row g and row g - 1 and
 // decides both "row g starts a run" and "row g - 1 ends a run" (the run's exclusive end is g).  So a lane never needs the row behind
@@ -17,7 +18,6 @@ constexpr uint32_t SEG_TRIPS = 16;                 // trips of 64 positions a wa
 constexpr uint32_t SEG_TILE = 64u * SEG_TRIPS;     // positions per tile
 constexpr uint32_t SEG_FLAG_LONGEST = 1u;          // KMU_SEG_LONGEST
 constexpr uint32_t SEG_WHOLE = 0, SEG_ENDS = 1, SEG_SPLIT = 2, SEG_NONE = 3; // KMU_TRIM_*
-constexpr uint32_t EXT_TILE = 4096;                // output bytes per tile of kmu_extract_ranges
 
 KMU_PILE_HD uint64_t seg_n_tiles(uint64_t n_rows) { return (n_rows + 1u + SEG_TILE - 1u) / SEG_TILE; } // over n_rows + 1 positions
 
@@ -53,17 +53,6 @@ KMU_PILE_HD bool seg_is_end(const SegRow &prev, const SegRow &cur, bool cur_star
 // the bit of position g in the bitmap of read starts
 KMU_PILE_HD bool seg_marked(const uint64_t *marks, uint64_t g) { return (marks[g >> 6] >> (g & 63u)) & 1ull; }
 
-// largest i in [0, n] with offsets[i] <= g (offsets[0] = 0 <= g): the read that holds row g, empty reads skipped
-KMU_PILE_HD uint32_t seg_find_read(const uint64_t *offsets, uint32_t n, uint64_t g) {
-    uint32_t lo = 0, hi = n; // offsets[lo] <= g; every index above hi is > g or does not exist
-    while (lo < hi) {
-        const uint32_t mid = lo + (hi - lo + 1u) / 2u;
-        if (offsets[mid] <= g) lo = mid;
-        else hi = mid - 1u;
-    }
-    return lo;
-}
-
 // the summary of a read from its kept segments in order; add one segment after the other, then finish
 struct SegSummary {
     uint32_t n_segs, kept, best_start, best_end, first_start, last_end, best_rank;
@@ -93,13 +82,5 @@ KMU_PILE_HD uint32_t seg_class(const SegSummary &s, uint32_t n_bases) {
 
 // kmu_extract_ranges: a range is usable iff begin <= end <= n_bases; its length, 0 for a range that is not
 KMU_PILE_HD bool ext_range_ok(uint64_t begin, uint64_t end, uint64_t n_bases) { return begin <= end && end <= n_bases; }
-// a lane's range inside a window of 64 ascending offsets win[j] = out_offsets[r0 + 1 + j]: the number of j with win[j] <= o, for a byte
-// o < win[63].  get(j) returns win[j] (a wave shuffle on the device)
-template <class Get> KMU_PILE_HD uint32_t ext_window_count(Get get, uint64_t o) {
-    uint32_t c = 0;
-    for (uint32_t step = 32u; step >= 1u; step >>= 1)
-        if (get(c + step - 1u) <= o) c += step;
-    return c;
-}
 
 } // namespace kmu

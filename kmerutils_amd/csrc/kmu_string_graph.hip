@@ -191,13 +191,6 @@ __global__ void __launch_bounds__(256) k_sg_unique(SgArgs a) {
 
 using namespace kmu;
 
-// a device array of the workspace to a caller's array that lives where `mem` says
-static int sg_copy_out(kmu_ctx *ctx, void *dst, const void *src, size_t bytes, int mem) {
-    if (!dst || !bytes) return KMU_OK;
-    KMU_HIP(ctx, hipMemcpyAsync(dst, src, bytes, mem == KMU_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, ctx->stream));
-    return KMU_OK;
-}
-
 static const char *const SG_REFUSAL =
     "a record names a read that does not exist, a strand above 1, a start above its end, an end above the length of its read, or a "
     "read of 2^32 bases or more";
@@ -251,8 +244,8 @@ extern "C" int kmu_sg_classify(kmu_ctx *ctx, const kmu_chain *chains, const kmu_
         (void) finish_call(ctx, mem);
         return fail(ctx, KMU_E_UNSUPPORTED, "%s", SG_REFUSAL);
     }
-    KMU_TRY(sg_copy_out(ctx, class_out, a.cls, (size_t) n_chains, mem));
-    KMU_TRY(sg_copy_out(ctx, reads_out, a.reads, (size_t) n_reads * sizeof(kmu_sg_read), mem));
+    KMU_TRY(copy_out(ctx, class_out, a.cls, (size_t) n_chains, mem));
+    KMU_TRY(copy_out(ctx, reads_out, a.reads, (size_t) n_reads * sizeof(kmu_sg_read), mem));
     return finish_call(ctx, mem);
 }
 
@@ -316,10 +309,10 @@ extern "C" int kmu_sg_graph(kmu_ctx *ctx, const kmu_chain *chains, const kmu_cha
         KMU_TRY(launch(ctx, "k_sg_reduce", k_sg_reduce, dim3(grid_for(ctx, a.n_arcs, 4)), dim3(256), 0, a)); // (a wave per arc)
         KMU_TRY(launch(ctx, "k_sg_finish", k_sg_finish, flat, dim3(256), 0, a));
         KMU_TRY(launch(ctx, "k_sg_unique", k_sg_unique, flat, dim3(256), 0, a));
-        if (mem == KMU_MEM_HOST) KMU_TRY(sg_copy_out(ctx, arcs_out, a.arcs, (size_t) a.n_arcs * sizeof(kmu_sg_arc), mem));
+        if (mem == KMU_MEM_HOST) KMU_TRY(copy_out(ctx, arcs_out, a.arcs, (size_t) a.n_arcs * sizeof(kmu_sg_arc), mem));
     }
-    KMU_TRY(sg_copy_out(ctx, class_out, a.cls, (size_t) n_chains, mem));
-    KMU_TRY(sg_copy_out(ctx, reads_out, a.reads, (size_t) n_reads * sizeof(kmu_sg_read), mem));
-    KMU_TRY(sg_copy_out(ctx, arc_offsets_out, a.arc_off, (n_v + 1) * 8, mem));
+    KMU_TRY(copy_out(ctx, class_out, a.cls, (size_t) n_chains, mem));
+    KMU_TRY(copy_out(ctx, reads_out, a.reads, (size_t) n_reads * sizeof(kmu_sg_read), mem));
+    KMU_TRY(copy_out(ctx, arc_offsets_out, a.arc_off, (n_v + 1) * 8, mem));
     return finish_call(ctx, mem);
 }

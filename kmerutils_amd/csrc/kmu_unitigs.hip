@@ -1,6 +1,6 @@
 // kmu_unitigs.hip -- from the unique arcs of the string graph to the unitigs: the ordered reads of every unitig with their
 // coordinates, and the bases of every unitig, on the device (kmu_sg_unitigs, kmu_sg_unitig_seqs; the contract is in include/kmu.h,
-// the arithmetic in kmu_ut_core.h).
+// the arithmetic in kmu_ut_core.h; the walk from the items' ends to the output bytes is the segmented byte gather of kmu_gather.h).
 //
 //  k_ut_links      one lane per arc: a unique arc passes the range checks first (one that fails raises bad and is never used as an
 //                  index), then integer atomic adds count the unique out-degree of `from` and in-degree of `to` -- a count above 1
@@ -20,15 +20,14 @@
 //  k_ut_seq_lens   one lane per unitig: its slice of the step list is checked, its length and its number of steps go to the scans.
 //  k_ut_seq_check  one lane per ITEM (unitig, step of it): the unitig by a binary search over the scanned step counts, the checks of
 //                  the step against the one before it.  Unitigs may share steps, so the items, not the steps, are the work.
-//  k_ut_seq_offs   one lane per unitig: the 64-bit offsets from the two 32-bit scans.
+//  k_ut_seq_offs   one lane per unitig: the 64-bit offsets from the two 32-bit scans (k_gather_offsets under this timer name).
 //  k_ut_seq_ends   one lane per item: the global end seq_offsets[u] + end of the item and its step.
-//  k_ut_seq_copy   one wave per tile of UT_TILE output bytes, in the form of k_ext_copy: a 64-ary search over the global ends for the
-//                  tile's first byte, then 64 bytes per trip, one per lane, coalesced stores; a reverse step reads backwards through
-//                  the complement.  One long unitig spreads over many waves as many short ones share one.
+//  k_ut_seq_copy   gather_tiles (kmu_gather.h) over the global ends: the byte of item r comes from its step's read; a reverse step
+//                  reads backwards through the complement.
 #include <algorithm>
 
 #include "kmu_ut_core.h"
-#include "kmu_device.h"
+#include "kmu_gather.h"
 #include "kmu_ctx.hpp"
 
 namespace kmu {
@@ -190,7 +189,7 @@ __global__ void __launch_bounds__(256) k_ut_seq_lens(UsArgs p) {
 // item j: its unitig and its step; false beyond the last item
 __device__ __forceinline__ bool ut_item(const UsArgs &p, uint64_t j, uint64_t &u, uint64_t &i) {
     if (j >= p.item_off[p.n_unitigs]) return false;
-    u = ut_upper_index(p.item_off, p.n_unitigs, j); // (item_off[u] <= j < item_off[n_unitigs]: u < n_unitigs, and u is not empty)
+    u = gather_upper_index(p.item_off, p.n_unitigs, j); // (item_off[u] <= j < item_off[n_unitigs]: u < n_unitigs, and u is not empty)
     i = j - p.item_off[u];
     return u < p.n_unitigs;
 }
@@ -212,11 +211,6 @@ __global__ void __launch_bounds__(256) k_ut_seq_check(UsArgs p) {
     if (bad) *p.bad = 1u;
 }
 
-__global__ void __launch_bounds__(256) k_ut_seq_offs(UsArgs p) {
-    for (uint64_t u = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x; u <= p.n_unitigs; u += (uint64_t) gridDim.x * blockDim.x)
-        p.seq_off[u] = p.off_lo[u] + (p.off_hi[u] << 32);
-}
-
 __global__ void __launch_bounds__(256) k_ut_seq_ends(UsArgs p) {
     for (uint64_t j = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x; j < p.n_items; j += (uint64_t) gridDim.x * blockDim.x) {
         uint64_t u, i;
@@ -228,65 +222,24 @@ __global__ void __launch_bounds__(256) k_ut_seq_ends(UsArgs p) {
     }
 }
 
-// largest i in [0, n] with off[i] <= g, g wave-uniform: a 64-ary search, one probe per lane and trip
-__device__ __forceinline__ uint64_t ut_find_item(const uint64_t *off, uint64_t n, uint64_t g) {
-    const uint32_t lane = (uint32_t) lane_id();
-    return ut_find_64ary(n, [&](uint64_t lo, uint64_t step, uint64_t hi) {
-        const uint64_t idx = lo + (uint64_t) (lane + 1u) * step;
-        return (uint32_t) __popcll(__ballot(idx < hi && off[idx] <= g));
-    });
-}
-
 __global__ void __launch_bounds__(256) k_ut_seq_copy(UsArgs p) {
-    const uint32_t lane = (uint32_t) lane_id();
-    for (uint64_t t = (uint64_t) blockIdx.x * 4u + (threadIdx.x >> 6); t < p.n_tiles; t += (uint64_t) gridDim.x * 4u) {
-        uint64_t pos = t * UT_TILE;
-        const uint64_t tile_end = pos + UT_TILE < p.total ? pos + UT_TILE : p.total;
-        uint64_t r0 = ut_find_item(p.ends, p.n_items, pos); // ends[r0] <= pos
-        while (pos < tile_end) {
-            // the window: the 64 ends behind r0, one per lane (beyond the last: never reached)
-            const uint64_t wi = r0 + 1u + lane, win = wi <= p.n_items ? p.ends[wi] : ~0ull;
-            const uint64_t w63 = ((uint64_t) readlane_u32((uint32_t) (win >> 32), 63) << 32) | readlane_u32((uint32_t) win, 63);
-            if (w63 <= pos) { // 64 items that end at or before pos: contributions of 0
-                r0 += 64u;
-                continue;
-            }
-            uint64_t limit = pos + 64u < tile_end ? pos + 64u : tile_end;
-            limit = w63 < limit ? w63 : limit; // (> pos) every byte below has its item inside the window
-            const uint64_t o = pos + lane;
-            const uint32_t c = ut_window_count(
-                [&](uint32_t j) { return ((uint64_t) (uint32_t) __shfl((int) (win >> 32), (int) j, 64) << 32) | (uint32_t) __shfl((int) (uint32_t) win, (int) j, 64); }, o);
-            if (o < limit) {
-                const uint64_t r = r0 + c; // (c <= 63 and ends[r] <= o < ends[r + 1] <= total: r < n_items)
-                if (r < p.n_items) {
-                    const uint64_t begin = p.ends[r], at = p.isrc[r];
-                    const kmu_sg_step s = p.path[at < p.n_steps ? at : 0u];
-                    if (s.read < p.n_reads) { // (k_ut_seq_check has checked the steps: always)
-                        const uint64_t b0 = p.off[s.read], len = p.off[s.read + 1u] - b0;
-                        const uint64_t idx = ut_src_index(s.strand, len, p.ends[r + 1u] - begin, o - begin);
-                        if (idx < len) {
-                            const uint8_t b = p.bases[b0 + idx];
-                            p.out[o] = s.strand ? ut_complement(b) : b;
-                        }
-                    }
-                }
-            }
-            r0 += (uint32_t) __popcll(__ballot(win <= limit));
-            pos = limit;
+    gather_tiles(p.ends, p.n_items, p.total, p.n_tiles, [&](uint64_t r, uint64_t o) {
+        if (r >= p.n_items) return; // (never)
+        const uint64_t begin = p.ends[r], at = p.isrc[r];
+        const kmu_sg_step s = p.path[at < p.n_steps ? at : 0u];
+        if (s.read >= p.n_reads) return; // (k_ut_seq_check has checked the steps: never)
+        const uint64_t b0 = p.off[s.read], len = p.off[s.read + 1u] - b0;
+        const uint64_t idx = ut_src_index(s.strand, len, p.ends[r + 1u] - begin, o - begin);
+        if (idx < len) {
+            const uint8_t b = p.bases[b0 + idx];
+            p.out[o] = s.strand ? ut_complement(b) : b;
         }
-    }
+    });
 }
 
 } // namespace kmu
 
 using namespace kmu;
-
-// a device array of the workspace to a caller's array that lives where `mem` says
-static int ut_copy_out(kmu_ctx *ctx, void *dst, const void *src, size_t bytes, int mem) {
-    if (!dst || !bytes) return KMU_OK;
-    KMU_HIP(ctx, hipMemcpyAsync(dst, src, bytes, mem == KMU_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, ctx->stream));
-    return KMU_OK;
-}
 
 extern "C" int kmu_sg_unitigs(kmu_ctx *ctx, const kmu_sg_arc *arcs, uint64_t n_arcs, const kmu_sg_read *reads, const uint64_t *offsets,
                               uint32_t n_reads, int mem, kmu_sg_unitig *unitigs_out, kmu_sg_step *path_out, kmu_sg_place *place_out,
@@ -383,9 +336,9 @@ extern "C" int kmu_sg_unitigs(kmu_ctx *ctx, const kmu_sg_arc *arcs, uint64_t n_a
     *n_out = n_unitigs;
     if (n_steps_out) *n_steps_out = n_steps;
     if (mem == KMU_MEM_HOST) {
-        KMU_TRY(ut_copy_out(ctx, unitigs_out, a.unitigs, (size_t) n_unitigs * sizeof(kmu_sg_unitig), mem));
-        KMU_TRY(ut_copy_out(ctx, path_out, a.path, (size_t) n_steps * sizeof(kmu_sg_step), mem));
-        KMU_TRY(ut_copy_out(ctx, place_out, a.place, (size_t) n_reads * sizeof(kmu_sg_place), mem));
+        KMU_TRY(copy_out(ctx, unitigs_out, a.unitigs, (size_t) n_unitigs * sizeof(kmu_sg_unitig), mem));
+        KMU_TRY(copy_out(ctx, path_out, a.path, (size_t) n_steps * sizeof(kmu_sg_step), mem));
+        KMU_TRY(copy_out(ctx, place_out, a.place, (size_t) n_reads * sizeof(kmu_sg_place), mem));
     }
     return finish_call(ctx, mem);
 }
@@ -461,8 +414,8 @@ extern "C" int kmu_sg_unitig_seqs(kmu_ctx *ctx, const kmu_sg_unitig *unitigs, ui
     }
     a.seq_off = seq_offsets_out;
     if (mem == KMU_MEM_HOST || !seq_offsets_out) KMU_TRY(dev_array(ctx, "us.seqoff", n_unitigs + 1, &a.seq_off));
-    KMU_TRY(launch(ctx, "k_ut_seq_offs", k_ut_seq_offs, per_u, block, 0, a));
-    if (mem == KMU_MEM_HOST) KMU_TRY(ut_copy_out(ctx, seq_offsets_out, a.seq_off, (size_t) (n_unitigs + 1) * 8, mem));
+    KMU_TRY(launch(ctx, "k_ut_seq_offs", k_gather_offsets, per_u, block, 0, a.off_lo, a.off_hi, n_unitigs, a.seq_off));
+    if (mem == KMU_MEM_HOST) KMU_TRY(copy_out(ctx, seq_offsets_out, a.seq_off, (size_t) (n_unitigs + 1) * 8, mem));
     if (a.total) {
         if (mem == KMU_MEM_HOST) { // (the batch's size is its last offset)
             KMU_TRY(stage_to_device(ctx, "us.bases", bases, (size_t) offsets[n_reads], mem, &d));
@@ -472,12 +425,12 @@ extern "C" int kmu_sg_unitig_seqs(kmu_ctx *ctx, const kmu_sg_unitig *unitigs, ui
         }
         KMU_TRY(dev_array(ctx, "us.ends", (size_t) a.n_items + 1, &a.ends));
         KMU_TRY(dev_array(ctx, "us.isrc", (size_t) a.n_items, &a.isrc));
-        a.n_tiles = (a.total + UT_TILE - 1u) / UT_TILE;
+        a.n_tiles = (a.total + GATHER_TILE - 1u) / GATHER_TILE;
         a.out = seq_out;
         if (mem == KMU_MEM_HOST) KMU_TRY(dev_array(ctx, "us.out", (size_t) a.total, &a.out));
         KMU_TRY(launch(ctx, "k_ut_seq_ends", k_ut_seq_ends, dim3(grid_for(ctx, a.n_items, 256)), block, 0, a));
         KMU_TRY(launch(ctx, "k_ut_seq_copy", k_ut_seq_copy, dim3(grid_for(ctx, a.n_tiles, 4)), block, 0, a));
-        if (mem == KMU_MEM_HOST) KMU_TRY(ut_copy_out(ctx, seq_out, a.out, (size_t) a.total, mem));
+        if (mem == KMU_MEM_HOST) KMU_TRY(copy_out(ctx, seq_out, a.out, (size_t) a.total, mem));
     }
     return finish_call(ctx, mem);
 }

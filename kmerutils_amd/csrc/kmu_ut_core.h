@@ -1,7 +1,8 @@
 // kmu_ut_core.h -- the arithmetic of the unitig layout: which unique arcs the device may use as links, the mate test, the state of a
 // vertex under pointer doubling and one round of it, the cut of a cycle, what a tail publishes, the step and the place of a vertex,
 // the checks of a step list and the source byte of an output byte; for the device and for a host compiler alike
-// (tests/cpp/sim_unitigs.cpp drives these functions over simulated lanes; the contract is in include/kmu.h).
+// (tests/cpp/sim_unitigs.cpp drives these functions over simulated lanes; the contract is in include/kmu.h).  The item that holds an
+// output byte and the tile walk of the sequence copy are in kmu_gather_core.h.
 //
 // Doubling runs BACKWARDS over prev.  The state of v describes a SEGMENT: v, prev(v), ... up to but excluding anc; cnt vertices, dist
 // the sum of their contributions, minv the smallest of them, top the last one.  A round joins the segment of v with that of anc.  On
@@ -24,8 +25,6 @@
 namespace kmu {
 
 static_assert(sizeof(kmu_sg_step) == 16 && sizeof(kmu_sg_unitig) == 32 && sizeof(kmu_sg_place) == 16, "the records of include/kmu.h");
-
-constexpr uint32_t UT_TILE = 4096; // output bytes per tile of k_ut_seq_copy
 
 // the doubling rounds that rank every path of up to n_v vertices: ceil(log2(n_v)), at least 1
 KMU_UT_HD uint32_t ut_rounds(uint64_t n_v) {
@@ -98,37 +97,5 @@ KMU_UT_HD uint8_t ut_complement(uint8_t b) {
 }
 // byte k of a step's c bytes (the last c of the read in the step's orientation) as an index into the read of length read_len
 KMU_UT_HD uint64_t ut_src_index(uint32_t strand, uint64_t read_len, uint64_t c, uint64_t k) { return strand ? c - 1u - k : read_len - c + k; }
-
-// the largest i in [0, n] with off[i] <= g, off ascending with off[0] <= g: one lane's binary search
-KMU_UT_HD uint64_t ut_upper_index(const uint64_t *off, uint64_t n, uint64_t g) {
-    uint64_t lo = 0, hi = n + 1u; // off[lo] <= g; off[hi] > g or hi == n + 1
-    while (hi - lo > 1u) {
-        const uint64_t mid = lo + (hi - lo) / 2u;
-        if (off[mid] <= g) lo = mid;
-        else hi = mid;
-    }
-    return lo;
-}
-// the same index for a whole wave, g wave-uniform: a 64-ary search.  Lane l probes idx = lo + (l + 1) * step; count(lo, step, hi) is
-// the number of lanes whose idx is below hi and has off[idx] <= g (a ballot and a population count on the device)
-template <class Count> KMU_UT_HD uint64_t ut_find_64ary(uint64_t n, Count count) {
-    uint64_t lo = 0, hi = n + 1u; // off[lo] <= g; off[hi] > g or hi == n + 1
-    while (hi - lo > 1u) {
-        const uint64_t step = (hi - lo + 63u) / 64u;
-        const uint32_t c = count(lo, step, hi);
-        const uint64_t nhi = lo + (uint64_t) (c + 1u) * step;
-        lo += (uint64_t) c * step;
-        hi = nhi < hi ? nhi : hi;
-    }
-    return lo;
-}
-// a lane's item inside a window of 64 ascending ends win[j]: the number of j with win[j] <= o, for a byte o < win[63].  get(j)
-// returns win[j] (a wave shuffle on the device)
-template <class Get> KMU_UT_HD uint32_t ut_window_count(Get get, uint64_t o) {
-    uint32_t c = 0;
-    for (uint32_t step = 32u; step >= 1u; step >>= 1)
-        if (get(c + step - 1u) <= o) c += step;
-    return c;
-}
 
 } // namespace kmu

@@ -11,7 +11,8 @@ if ROOT not in sys.path:
 TEST_BIN = os.path.join(HERE, "_build", "test_trim")
 SIM_SRC = os.path.join(HERE, "sim_pile_segments.cpp")
 SIM_BIN = os.path.join(HERE, "_build", "sim_pile_segments")
-SIM_DEPS = [SIM_SRC] + [os.path.join(ROOT, "kmerutils_amd", "csrc", h) for h in ("kmu_seg_core.h", "kmu_cons_core.h", "kmu_pile_core.h")]
+SIM_DEPS = [SIM_SRC, os.path.join(HERE, "sim_gather.h")] + [os.path.join(ROOT, "kmerutils_amd", "csrc", h)
+                                                            for h in ("kmu_seg_core.h", "kmu_gather_core.h", "kmu_cons_core.h", "kmu_pile_core.h")]
 
 
 def build_sim(force=False, extra=(), out=SIM_BIN):

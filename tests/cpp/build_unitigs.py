@@ -11,7 +11,8 @@ if ROOT not in sys.path:
 TEST_BIN = os.path.join(HERE, "_build", "test_unitigs")
 SIM_SRC = os.path.join(HERE, "sim_unitigs.cpp")
 SIM_BIN = os.path.join(HERE, "_build", "sim_unitigs")
-SIM_DEPS = [SIM_SRC, os.path.join(ROOT, "kmerutils_amd", "csrc", "kmu_ut_core.h"), os.path.join(ROOT, "include", "kmu.h")]
+SIM_DEPS = [SIM_SRC, os.path.join(HERE, "sim_gather.h"), os.path.join(ROOT, "include", "kmu.h")] + [os.path.join(ROOT, "kmerutils_amd", "csrc", h)
+                                                                                                    for h in ("kmu_ut_core.h", "kmu_gather_core.h")]
 
 
 def build_sim(force=False, extra=(), out=SIM_BIN):

@@ -1,5 +1,5 @@
-// sim_pile_segments -- host only, no device and no libkmu: the functions of kmerutils_amd/csrc/kmu_seg_core.h driven over 64 simulated
-// lanes exactly as k_seg_marks, k_seg_count, k_seg_write, k_seg_keep, k_seg_reads and k_ext_copy drive them.  Random tables over
+// sim_pile_segments -- host only, no device and no libkmu: the functions of kmerutils_amd/csrc/kmu_seg_core.h and kmu_gather_core.h
+// (the copy: sim_gather.h) driven over 64 simulated lanes exactly as k_seg_marks, k_seg_count, k_seg_write, k_seg_keep, k_seg_reads and k_ext_copy drive them.  Random tables over
 // random read lengths (empty reads, reads of many tiles, depths around min_depth, ENDS around the depth).  Checked: every tile counts
 // in the write pass what it counted in the count pass; starts and ends pair up (as many, the k-th start below the k-th end, the k-th
 // end at or below the start after it); the runs equal a straight per-read replay of the text of include/kmu.h; every row is in at most
@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "../../kmerutils_amd/csrc/kmu_seg_core.h"
+#include "sim_gather.h"
 using namespace kmu;
 
 [[noreturn]] static void die(const char *what) {
@@ -160,8 +161,8 @@ static void segment_case(const std::vector<uint32_t> &read_len, const Rule &rule
     std::vector<uint32_t> n_good(n_reads, 0), n_kept(n_reads, 0);
     std::vector<std::array<uint32_t, 3>> kept; // read, start, end
     for (uint64_t k = 0; k < n_runs; k++) {
-        const uint32_t r = seg_find_read(off.data(), n_reads, starts[k]);
-        if (r >= n_reads || off[r] > starts[k] || off[r + 1] <= starts[k]) die("seg_find_read names a read that does not hold the row");
+        const uint32_t r = (uint32_t) gather_upper_index(off.data(), n_reads, starts[k]);
+        if (r >= n_reads || off[r] > starts[k] || off[r + 1] <= starts[k]) die("gather_upper_index names a read that does not hold the row");
         if (ends[k] > off[r + 1]) die("a run crosses a read boundary");
         const uint32_t len = (uint32_t) (ends[k] - starts[k]);
         n_good[r] += len;
@@ -185,51 +186,14 @@ static void segment_case(const std::vector<uint32_t> &read_len, const Rule &rule
     n_checked += n_rows + n_runs;
 }
 
-// k_ext_copy over 64 lanes
+// k_ext_copy over 64 lanes: the walk of sim_gather.h over the ranges' offsets
 static void copy_case(const std::vector<uint32_t> &len) {
-    const uint64_t n_ranges = len.size();
     std::vector<uint64_t> off(1, 0);
     for (uint32_t l : len) off.push_back(off.back() + l);
-    const uint64_t total = off.back(), n_tiles = (total + EXT_TILE - 1) / EXT_TILE;
-    std::vector<uint32_t> hits(total, 0);
-    for (uint64_t t = 0; t < n_tiles; t++) {
-        uint64_t pos = t * EXT_TILE;
-        const uint64_t tile_end = std::min(pos + EXT_TILE, total);
-        uint64_t r0 = seg_find_read(off.data(), (uint32_t) n_ranges, pos); // (the wave's 64-ary search gives the same index)
-        if (off[r0] > pos || (r0 < n_ranges && off[r0 + 1] <= pos)) die("the first range of a tile");
-        uint32_t guard = 0;
-        while (pos < tile_end) {
-            if (++guard > 100000) die("the copy does not advance");
-            uint64_t win[64];
-            for (uint32_t lane = 0; lane < 64; lane++) win[lane] = r0 + 1 + lane <= n_ranges ? off[r0 + 1 + lane] : ~0ull;
-            if (win[63] <= pos) {
-                r0 += 64;
-                continue;
-            }
-            uint64_t limit = std::min(pos + 64, tile_end);
-            limit = std::min(limit, win[63]);
-            if (limit <= pos) die("an empty trip");
-            uint32_t adv = 0;
-            for (uint32_t lane = 0; lane < 64; lane++) {
-                const uint64_t o = pos + lane;
-                adv += win[lane] <= limit;
-                if (o >= limit) continue;
-                const uint32_t c = ext_window_count([&](uint32_t j) { return win[j]; }, o);
-                uint32_t slow = 0;
-                for (uint32_t j = 0; j < 64; j++) slow += win[j] <= o;
-                if (c != slow || c > 63) die("ext_window_count differs from counting");
-                const uint64_t r = r0 + c;
-                if (r >= n_ranges || off[r] > o || off[r + 1] <= o) die("a byte's range does not hold it");
-                hits[o]++;
-            }
-            r0 += adv;
-            if (off[r0] > limit) die("the window advanced past the position");
-            pos = limit;
-        }
-    }
-    for (uint64_t o = 0; o < total; o++)
-        if (hits[o] != 1) die("an output byte written not exactly once");
-    n_checked += total + n_ranges;
+    uint64_t n_bytes = 0;
+    gather_replay(off, die, [&](uint64_t, uint64_t) { n_bytes++; });
+    if (n_bytes != off.back()) die("the copy delivers another number of bytes than the offsets name");
+    n_checked += off.back() + len.size();
 }
 
 int main(int argc, char **argv) {
@@ -255,12 +219,12 @@ int main(int argc, char **argv) {
     }
     copy_case({});
     copy_case({0, 0, 0});
-    copy_case({EXT_TILE * 3 + 5});
+    copy_case({GATHER_TILE * 3 + 5});
     copy_case(std::vector<uint32_t>(5000, 1));
     {
         std::vector<uint32_t> l(300, 0); // more than 64 empty ranges in a row, in front, inside and behind
         l[100] = 7;
-        l[250] = EXT_TILE;
+        l[250] = GATHER_TILE;
         copy_case(l);
     }
     for (uint32_t rep = 0; rep < reps; rep++) {

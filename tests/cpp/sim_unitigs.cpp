@@ -5,9 +5,8 @@
 //             steps of the kernels in their order -- links, mates, init, the doubling rounds from one buffer into the other, the
 //             cut, init and the rounds again, tails, the two scans, write -- against a sequential walk of the contract
 //   faults    one fault planted in such a layout: the simulated checks must refuse it
-//   copies    the tile walk of k_ut_seq_copy -- the search for a tile's first item, windows of 64 ends, ut_window_count per lane,
-//             ut_src_index and ut_complement -- against a byte loop per step, with contributions of 0 and tiles that end inside,
-//             at and after an item
+//   copies    k_ut_seq_copy -- the tile walk of sim_gather.h with ut_src_index and ut_complement per byte -- against a byte loop per
+//             step, with contributions of 0 and tiles that end inside, at and after an item
 // usage: sim_unitigs [cases]; prints "ok sim_unitigs <checked items>" and exits 0, or the first mismatch and exits 1
 #include <algorithm>
 #include <cstdio>
@@ -15,6 +14,7 @@
 #include <vector>
 
 #include "../../kmerutils_amd/csrc/kmu_ut_core.h"
+#include "sim_gather.h"
 
 using namespace kmu;
 
@@ -336,7 +336,7 @@ static void copies(uint32_t cases) {
         for (uint32_t r = 0; r < n_reads; r++) off[r + 1] = off[r] + 1u + below(below(3) == 0 ? 9000u : 300u);
         std::vector<uint8_t> bases(off[n_reads]);
         for (auto &b : bases) b = (uint8_t) "ACGTacgtNn-"[below(11)];
-        const uint64_t target = c % 3 == 0 ? UT_TILE - 1u + (c / 3) % 3 : 0u; // totals at the tile size minus 1, at it and plus 1
+        const uint64_t target = c % 3 == 0 ? GATHER_TILE - 1u + (c / 3) % 3 : 0u; // totals at the tile size minus 1, at it and plus 1
         const uint64_t n_items = target ? 400 + below(100) : 1 + below(300);
         std::vector<kmu_sg_step> steps(n_items);
         std::vector<uint64_t> ends(n_items + 1, 0);
@@ -355,51 +355,17 @@ static void copies(uint32_t cases) {
         }
         const uint64_t total = ends[n_items];
         std::vector<uint8_t> got(total, 0xEE);
-        std::vector<uint32_t> stores(total, 0u);
-        const uint64_t n_tiles = (total + UT_TILE - 1u) / UT_TILE;
-        for (uint64_t t = 0; t < n_tiles; t++) {
-            uint64_t pos = t * UT_TILE;
-            const uint64_t tile_end = std::min<uint64_t>(pos + UT_TILE, total);
-            uint64_t r0 = ut_find_64ary(n_items, [&](uint64_t lo, uint64_t step, uint64_t hi) { // the ballot over 64 lanes
-                uint32_t n = 0;
-                for (uint64_t lane = 0; lane < 64; lane++) n += lo + (lane + 1u) * step < hi && ends[lo + (lane + 1u) * step] <= pos;
-                return n;
-            });
-            CHECK(r0 == ut_upper_index(ends.data(), n_items, pos) && ends[r0] <= pos && (r0 == n_items || ends[r0 + 1] > pos), "tile %llu",
-                  (unsigned long long) t);
-            while (pos < tile_end) {
-                uint64_t win[64];
-                for (uint32_t lane = 0; lane < 64; lane++) win[lane] = r0 + 1u + lane <= n_items ? ends[r0 + 1u + lane] : ~0ull;
-                if (win[63] <= pos) {
-                    r0 += 64u;
-                    continue;
-                }
-                uint64_t limit = std::min<uint64_t>(pos + 64u, tile_end);
-                limit = std::min(limit, win[63]);
-                uint32_t advance = 0;
-                for (uint32_t lane = 0; lane < 64; lane++) {
-                    const uint64_t o = pos + lane;
-                    const uint32_t cnt = ut_window_count([&](uint32_t j) { return win[j]; }, o);
-                    if (o < limit) {
-                        const uint64_t r = r0 + cnt;
-                        CHECK(r < n_items && ends[r] <= o && o < ends[r + 1], "byte %llu", (unsigned long long) o);
-                        const kmu_sg_step s = steps[r];
-                        const uint64_t len = off[s.read + 1] - off[s.read];
-                        const uint64_t idx = ut_src_index(s.strand, len, ends[r + 1] - ends[r], o - ends[r]);
-                        CHECK(idx < len, "byte %llu", (unsigned long long) o);
-                        const uint8_t b = bases[off[s.read] + idx];
-                        got[o] = s.strand ? ut_complement(b) : b;
-                        stores[o]++;
-                    }
-                    advance += win[lane] <= limit;
-                }
-                r0 += advance;
-                pos = limit;
-            }
-        }
+        gather_replay(ends, [](const char *what) { CHECK(false, "%s", what); }, [&](uint64_t r, uint64_t o) {
+            const kmu_sg_step s = steps[r];
+            const uint64_t len = off[s.read + 1] - off[s.read];
+            const uint64_t idx = ut_src_index(s.strand, len, ends[r + 1] - ends[r], o - ends[r]);
+            CHECK(idx < len, "byte %llu", (unsigned long long) o);
+            const uint8_t b = bases[off[s.read] + idx];
+            got[o] = s.strand ? ut_complement(b) : b;
+        });
         for (uint64_t o = 0; o < total; o++)
-            CHECK(got[o] == want[o] && stores[o] == 1u, "case %u byte %llu of %llu: %u against %u, %u stores", c, (unsigned long long) o,
-                  (unsigned long long) total, got[o], want[o], stores[o]);
+            CHECK(got[o] == want[o], "case %u byte %llu of %llu: %u against %u", c, (unsigned long long) o, (unsigned long long) total, got[o],
+                  want[o]);
         g_checked += total;
     }
 }

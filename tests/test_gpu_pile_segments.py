@@ -250,6 +250,13 @@ def test_extract_shapes(ctx):
     check_extract(ctx, bases, [0], [EXT_TILE])                                            # exactly one tile
     check_extract(ctx, bases, [1, 0], [EXT_TILE, 1])                                      # a range that ends on a tile's last byte
     check_extract(ctx, bases[:0], [0, 0], [0, 0])                                         # an empty batch
+    for k in (1, 63, 64, 65, EXT_TILE - 1, EXT_TILE, EXT_TILE + 1):                       # k + 1 offsets: one and two rounds of the 64-ary
+        start = rng.integers(0, n, k)                                                     # search; at 4097 the second tile's first byte
+        check_extract(ctx, bases, start, start + 1)                                       # lies in the last range
+    length = np.array([EXT_TILE] + [0] * 130 + [10] + [0] * 70)                           # a tile that ends on a range's end, more than 64
+    begin = rng.integers(0, n - EXT_TILE, length.size)                                    # empty ranges before the next byte, and empty
+    want = check_extract(ctx, bases, begin, begin + length)                               # ranges behind the last byte
+    assert int(want[1][-1]) == EXT_TILE + 10
 
 
 def test_extract_every_alignment(ctx):

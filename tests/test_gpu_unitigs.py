@@ -271,6 +271,14 @@ def test_sequences_at_the_tile_edges(ctx):
     many = [list(np.random.default_rng(3).integers(0, 200, 1 + i % 70)) for i in range(150)]
     seq, seq_off = check_seqs(ctx, *hand_layout(many, small, seed=4), what="many")
     assert len(seq) > 3 * TILE and len(seq_off) == 151
+    # n one-byte steps: n + 1 ends take one and two rounds of the 64-ary search; at 4097 the second tile's first byte lies in the last item
+    for n in (1, 63, 64, 65, TILE - 1, TILE, TILE + 1):
+        seq, _ = check_seqs(ctx, *hand_layout([[1] * n], small, seed=n), what="%d steps of one byte" % n)
+        assert len(seq) == n
+    # a tile that ends on an item's end, more than 64 items of nothing before the next byte, and items of nothing behind the last byte
+    gaps = [TILE] + [0] * 130 + [10] + [0] * 70
+    seq, _ = check_seqs(ctx, *hand_layout([gaps], lambda n, rng: np.full(n, TILE), seed=8), what="gaps")
+    assert len(seq) == TILE + 10
 
 
 def test_sequences_with_contributions_of_zero(ctx):

@@ -1,6 +1,6 @@
 """-m "not gpu": the segment pass and the range copy of read trimming without a device.  tests/cpp/sim_pile_segments.cpp drives the
-functions of kmerutils_amd/csrc/kmu_seg_core.h -- the code k_seg_count, k_seg_write, k_seg_keep, k_seg_reads and k_ext_copy are made
-of -- over 64 simulated lanes on random tables: starts and ends pair up, the runs equal a straight per-read replay, every row is in
+functions of kmerutils_amd/csrc/kmu_seg_core.h and kmu_gather_core.h -- the code k_seg_count, k_seg_write, k_seg_keep, k_seg_reads and
+k_ext_copy are made of -- over 64 simulated lanes on random tables: starts and ends pair up, the runs equal a straight per-read replay, every row is in
 at most one run and no run crosses a read boundary, the summaries equal the replay's, and every output byte of the copy is written
 exactly once from the range that holds it; g++ only, no libkmu.  The same program built with AddressSanitizer +
 UndefinedBehaviorSanitizer runs as a stand-alone child process on the CPU."""

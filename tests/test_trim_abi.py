@@ -231,7 +231,8 @@ def test_constants_and_struct_sizes_match_the_header():
     assert tail.index("int kmu_pile_segments(") < tail.index("int kmu_extract_ranges(") < tail.index("int kmu_pile_consensus_pos(")
     core = open(os.path.join(ROOT, "kmerutils_amd", "csrc", "kmu_seg_core.h")).read()
     assert int(re.search(r"constexpr uint32_t SEG_TRIPS = (\d+);", core).group(1)) * 64 == SEG_TILE
-    assert int(re.search(r"constexpr uint32_t EXT_TILE = (\d+);", core).group(1)) == EXT_TILE
+    gather = open(os.path.join(ROOT, "kmerutils_amd", "csrc", "kmu_gather_core.h")).read()
+    assert int(re.search(r"constexpr uint32_t GATHER_TILE = (\d+);", gather).group(1)) == EXT_TILE
     # the step from a tile's offset to a row exists once
     cons = open(os.path.join(ROOT, "kmerutils_amd", "csrc", "kmu_pile_consensus.hip")).read()
     assert cons.count("uint64_t cons_pos_at(") == 1 and cons.count("= cons_pos_at(") == 2

@@ -1,5 +1,5 @@
 """-m "not gpu": the kernels of the unitig layout without a device.  tests/cpp/sim_unitigs.cpp drives the functions of
-kmerutils_amd/csrc/kmu_ut_core.h -- the code the kernels of kmu_unitigs.hip are made of -- over simulated lanes: the links, the mate
+kmerutils_amd/csrc/kmu_ut_core.h and kmu_gather_core.h -- the code the kernels of kmu_unitigs.hip are made of -- over simulated lanes: the links, the mate
 test, the doubling rounds from one buffer into the other, the cut of the cycles, the tails, the scans and the write against a
 sequential walk on random forests of paths and cycles (paths of 1, 2, 3, 4, 5, 63, 64, 65, 127, 128, 129 and 1025 reads among them),
 every planted arc fault against its refusal, and the tile walk of the sequence copy against a byte loop; g++ only, no libkmu.  The
