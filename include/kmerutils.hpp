@@ -37,6 +37,7 @@
  *                 (overlap classes, contained reads, the transitively reduced string graph)
  *                 Unitigs, sg_unitigs, UnitigSequences, unitig_sequences, ReadUnitigs, read_unitigs, unitig_gfa_line
  *                 (the ordered reads of every unitig, their coordinates and the unitig's bases)
+ *                 CleanGraph, sg_clean, clean_graph, layout_reads (tips removed and simple bubbles popped before the layout)
  *                 seed_chains, seed_pairs, chain_hits, read_chains (one base-resolution chain per read pair from minimizer
  *                                                            hits)                          (beyond the reference)
  *   counting      KmerCountT (trait), KmerCounter, KmerCounterPool, count_kmer_threaded_one_to_many
@@ -2605,6 +2606,62 @@ inline std::string unitig_gfa_line(uint64_t number, const kmu_sg_unitig &u, cons
     char name[32];
     snprintf(name, sizeof name, "utg%06llu%c", (unsigned long long) number, (u.flags & KMU_SG_UNITIG_CIRCULAR) ? 'c' : 'l');
     return std::string("a\t") + name + "\t" + std::to_string(before) + "\t" + read_name + "\t" + (s.strand ? "-" : "+") + "\t" + std::to_string(s.end - before);
+}
+
+// =====================================================================================================================
+// string graph cleaning (kmu_sg_clean; the reference has no such unit)
+// =====================================================================================================================
+
+/// What sg_clean and clean_graph return: the arcs with KMU_SG_ARC_TIP / KMU_SG_ARC_BUBBLE in the flags of the removed ones and
+/// `unique` recomputed, the summaries with KMU_SG_READ_TIP / KMU_SG_READ_BUBBLE and the final degrees, and the counts.
+struct CleanGraph {
+    std::vector<kmu_sg_arc> arcs;
+    std::vector<kmu_sg_read> reads;
+    kmu_sg_clean_stats stats{};
+};
+
+/// kmu_sg_clean on host arrays (Context.sg_clean): one round -- dead ends of at most max_tip_reads reads are removed, simple bubbles
+/// whose branches hold at most max_bubble_reads reads are popped; 0 turns a phase off.  arcs: of overlap_graph or of an earlier
+/// sg_clean, sorted by `from`; reads: the summaries (empty: none).
+inline CleanGraph sg_clean(const std::vector<kmu_sg_arc> &arcs, const std::vector<kmu_sg_read> &reads, uint32_t n_reads, uint32_t max_tip_reads = 4,
+                           uint32_t max_bubble_reads = 8, Context &ctx = Context::global()) {
+    if (!reads.empty() && reads.size() != n_reads) throw std::invalid_argument("sg_clean: as many summaries as reads, or none");
+    CleanGraph out;
+    out.arcs.assign(arcs.size() + 1, kmu_sg_arc{}); // an empty vector has no address worth passing
+    out.reads.assign(size_t(n_reads) + 1, kmu_sg_read{});
+    const kmu_sg_arc none{};
+    const kmu_sg_clean_params p{max_tip_reads, max_bubble_reads, 0u, 0u};
+    ctx.check(kmu_sg_clean(ctx.raw(), arcs.empty() ? &none : arcs.data(), arcs.size(), reads.empty() ? nullptr : reads.data(), n_reads, &p, KMU_MEM_HOST,
+                           out.arcs.data(), out.reads.data(), &out.stats));
+    out.arcs.resize(arcs.size());
+    out.reads.resize(n_reads);
+    return out;
+}
+
+/// sg_clean repeated on its own output while a round removed something, at most `rounds` times (minimizer.clean_graph): the counts
+/// are summed over the rounds, except n_arcs_left, which is the last round's.  rounds == 0 returns the inputs with zero counts.
+inline CleanGraph clean_graph(const std::vector<kmu_sg_arc> &arcs, const std::vector<kmu_sg_read> &reads, uint32_t n_reads, uint32_t max_tip_reads = 4,
+                              uint32_t max_bubble_reads = 8, uint32_t rounds = 1, Context &ctx = Context::global()) {
+    CleanGraph out;
+    out.arcs = arcs;
+    out.reads = reads;
+    for (uint32_t r = 0; r < rounds; r++) {
+        CleanGraph next = sg_clean(out.arcs, out.reads, n_reads, max_tip_reads, max_bubble_reads, ctx);
+        const kmu_sg_clean_stats s = next.stats, t = out.stats;
+        next.stats = kmu_sg_clean_stats{t.n_tips + s.n_tips, t.n_tip_reads + s.n_tip_reads, t.n_spared + s.n_spared, t.n_bubbles + s.n_bubbles,
+                                        t.n_bubble_reads + s.n_bubble_reads, t.n_arcs_tip + s.n_arcs_tip, t.n_arcs_bubble + s.n_arcs_bubble, s.n_arcs_left};
+        out = std::move(next);
+        if (!s.n_tip_reads && !s.n_bubble_reads) break;
+    }
+    return out;
+}
+
+/// A copy of the summaries in which every read that carries KMU_SG_READ_TIP or KMU_SG_READ_BUBBLE also carries
+/// KMU_SG_READ_CONTAINED (minimizer.layout_reads): sg_unitigs then leaves the removed reads off the layout.
+inline std::vector<kmu_sg_read> layout_reads(std::vector<kmu_sg_read> reads) {
+    for (kmu_sg_read &r : reads)
+        if (r.flags & (KMU_SG_READ_TIP | KMU_SG_READ_BUBBLE)) r.flags |= KMU_SG_READ_CONTAINED;
+    return reads;
 }
 
 // =====================================================================================================================

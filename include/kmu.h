@@ -1471,6 +1471,76 @@ int kmu_sg_unitig_seqs(kmu_ctx *ctx, const kmu_sg_unitig *unitigs, uint64_t n_un
                        uint8_t *seq_out,            /* NULL: the count-only call */
                        uint64_t cap, uint64_t *n_out);
 
+/* ---- string graph cleaning: short dead ends (tips) are removed and simple bubbles are popped --------------------------
+ * Inputs: arcs[n_arcs], arc records in the (from, to, rec) order kmu_sg_graph writes them -- only non-decreasing `from` is required
+ *   (and checked, over EVERY arc: the slices out(v) are found by binary search over the whole list, no offsets are passed);
+ *   reads[n_reads], the summaries, or NULL (then no read is contained and the summaries written are otherwise zero).
+ * An arc SURVIVES iff flags == 0, so the output of one call is a valid input of the next.  out(v) counts the surviving arcs of v;
+ *   in(v) = out(v ^ 1), which by mate symmetry is the number of surviving arcs that enter v.
+ * Phase 1, tips; off when max_tip_reads == 0.  T = max_tip_reads.  v0 is a tip start iff in(v0) = 0 and out(v0) = 1.  Walk
+ *   v(i+1) = the target of the only surviving arc of v(i).  On arriving at w from v(i) the reads so far are v0 .. v(i): if
+ *   in(w) >= 2 the walk ends and is a CANDIDATE tip of i + 1 reads with junction w iff i + 1 <= T; otherwise, if out(w) = 1 and
+ *   i + 1 < T, the walk continues with w; otherwise it is no tip (a line that ends, a stem before a fork, or too long).
+ *   Spare rule: the in-neighbours of a junction w are to ^ 1 over the surviving arcs of out(w ^ 1).  When ALL of them are last
+ *   vertices of candidate tips, the candidate with the most reads is spared, at equal counts the one whose last vertex id is
+ *   smallest; n_spared counts such junctions.  (Without it a contig whose end forks into two short ends would lose both.)
+ *   Every read of a candidate that is not spared gets KMU_SG_READ_TIP, and every surviving arc that touches such a read, at either
+ *   end and on either strand, gets KMU_SG_ARC_TIP.  n_tips and n_tip_reads count the removed candidates and their reads.  A tip
+ *   that LEAVES a junction needs no rule: it is the twin of a tip that enters w ^ 1, and the removal is per read.
+ * Phase 2, simple bubbles; off when max_bubble_reads == 0.  B = max_bubble_reads.  The degrees are those over the arcs that survive
+ *   phase 1.  s is a source iff out(s) = 2.  A branch of s is a1 .. ak with s -> a1 -> ... -> ak -> t, 1 <= k <= B,
+ *   in(aj) = out(aj) = 1 for every j, and in(t) = 2 exactly.  A bubble is a source whose two branches both exist and end at the same
+ *   t with t >> 1 != s >> 1.  The two interiors are then disjoint as reads.  Proof: from an interior vertex x the walk forwards is
+ *   forced, so the first vertex that is not interior reached from x is unique: t; backwards likewise: s.  The twin map sends the
+ *   branch through x to the branch through x ^ 1 of the bubble with source t ^ 1 and end s ^ 1.  A read with x on one branch and
+ *   x ^ 1 on the other would give x ^ 1 the end t as well as s ^ 1, so t = s ^ 1, which is excluded.
+ *   The branch with fewer interior reads loses; at equal counts the branch that does NOT hold the smallest interior read id loses.
+ *   The rule is invariant under the twin map, so s and t ^ 1 decide alike.  The loser's interior reads get KMU_SG_READ_BUBBLE, the
+ *   surviving arcs that touch them KMU_SG_ARC_BUBBLE.  All bubbles are decided on the same graph, then removed.  n_bubbles counts
+ *   each bubble once (at the smaller of s and t ^ 1), n_bubble_reads the removed reads.
+ * Finish: arcs_out[i] is arcs[i] with the new flag; `unique` is recomputed for every arc by the rule of kmu_sg_graph over the arcs
+ *   with flags == 0, an arc with any flag has unique = 0.  reads_out[r] is reads[r] (zero where reads is NULL) with the new flag
+ *   bits OR-ed in and out_fwd, out_rev the final surviving degrees.  n_arcs_tip, n_arcs_bubble: the arcs flagged by this call;
+ *   n_arcs_left: the arcs whose flags are still 0.  Removal is per read and the mate of an arc touches the same two reads, so the
+ *   result is mate-symmetric and kmu_sg_unitigs accepts it; reads that carry TIP or BUBBLE stay single-read unitigs there unless
+ *   the caller also marks them KMU_SG_READ_CONTAINED.
+ * KMU_E_BAD_ARG (nothing is launched): null ctx / p / stats_out; null arcs or arcs_out with n_arcs > 0; non-zero flags or zero; a
+ *   limit above KMU_SG_CLEAN_MAX; bad mem; arcs while there are no reads; arcs_out overlapping arcs.
+ * KMU_E_UNSUPPORTED: n_reads >= 2^31, n_arcs >= 2^32, and the faults, found on the device; the call is refused at its one
+ *   synchronisation, every output (stats_out included) is left untouched and no faulty arc is used as an index: `from` decreases
+ *   from one arc to the next; in a surviving arc, from or to >= 2 n_reads, or from >> 1 == to >> 1; a surviving arc v -> w with rec
+ *   c has no surviving arc w^1 -> v^1 with rec c; with reads, a surviving arc touches a read flagged KMU_SG_READ_CONTAINED.
+ * n_arcs == 0: KMU_OK with zero stats; reads_out is the input summaries with zero degrees.  n_reads == 0: KMU_OK, zero stats.
+ * KMU_MEM_DEVICE: arcs, reads, arcs_out and reads_out are device memory; one synchronisation, which hands over the stats and the
+ *   refusal flag, also in async_device contexts.  KMU_MEM_HOST: the arrays go up through the context's workspace and come back.
+ * The result is a pure function of the input: integer compares, idempotent stores and commuting integer atomics only.  "The only
+ *   surviving arc of v" is the smallest target over out(v), kept by an atomic minimum, and is read only where out(v) = 1.
+ * How: one lane per arc checks, counts the degrees and keeps the sole successor; one lane per vertex walks a tip and publishes its
+ *   read count at its last vertex; one lane per junction applies the spare rule; one lane per tip start walks again and flags; one
+ *   lane per arc flags and recounts; one lane per source walks both branches and the loser again; one lane per arc flags and
+ *   recounts; one lane per arc sets unique; one lane per read writes its summary.  Nine launches whatever the graph; every walk is at
+ *   most KMU_SG_CLEAN_MAX dependent loads.  DESIGN.md 3.24 has the kernels. */
+#define KMU_SG_ARC_TIP     2u   /* kmu_sg_arc.flags */
+#define KMU_SG_ARC_BUBBLE  4u
+#define KMU_SG_READ_TIP    2u   /* kmu_sg_read.flags */
+#define KMU_SG_READ_BUBBLE 4u
+#define KMU_SG_CLEAN_MAX   64u  /* largest max_tip_reads / max_bubble_reads */
+typedef struct {
+    uint32_t max_tip_reads;     /* 0: no tip removal */
+    uint32_t max_bubble_reads;  /* 0: no bubble popping */
+    uint32_t flags;             /* no flag bits yet: must be 0 */
+    uint32_t zero;
+} kmu_sg_clean_params;
+typedef struct {
+    uint64_t n_tips, n_tip_reads, n_spared, n_bubbles, n_bubble_reads, n_arcs_tip, n_arcs_bubble, n_arcs_left;
+} kmu_sg_clean_stats;
+int kmu_sg_clean(kmu_ctx *ctx, const kmu_sg_arc *arcs, uint64_t n_arcs,
+                 const kmu_sg_read *reads,       /* may be NULL */
+                 uint32_t n_reads, const kmu_sg_clean_params *p, int mem,
+                 kmu_sg_arc *arcs_out,           /* n_arcs; must not overlap arcs */
+                 kmu_sg_read *reads_out,         /* n_reads; may be NULL */
+                 kmu_sg_clean_stats *stats_out); /* host memory in both modes; required */
+
 #ifdef __cplusplus
 }
 #endif

@@ -54,6 +54,9 @@ SG_READ_CONTAINED = 1    # kmu_sg_read.flags
 SG_ARC_REDUCED = 1       # kmu_sg_arc.flags
 SG_NONE = 0xFFFFFFFF     # kmu_sg_place.unitig of a contained read
 SG_UNITIG_CIRCULAR = 1   # kmu_sg_unitig.flags
+SG_ARC_TIP, SG_ARC_BUBBLE = 2, 4     # kmu_sg_arc.flags, set by kmu_sg_clean
+SG_READ_TIP, SG_READ_BUBBLE = 2, 4   # kmu_sg_read.flags, set by kmu_sg_clean
+SG_CLEAN_MAX = 64        # the largest max_tip_reads / max_bubble_reads
 
 
 def kmer_val_bytes(kmer_type):
@@ -236,6 +239,23 @@ SG_ARC_DTYPE = [("from", "<u4"), ("to", "<u4"), ("len", "<u4"), ("ovl", "<u4"), 
 SG_STEP_DTYPE = [("read", "<u4"), ("strand", "<u4"), ("end", "<u8")]
 SG_UNITIG_DTYPE = [("first", "<u8"), ("len", "<u8"), ("n_reads", "<u4"), ("flags", "<u4"), ("min_read", "<u4"), ("zero", "<u4")]
 SG_PLACE_DTYPE = [("unitig", "<u4"), ("rank", "<u4"), ("strand", "<u4"), ("zero", "<u4")]
+
+
+class SgCleanParams(C.Structure):
+    """kmu_sg_clean_params: the longest tip and the longest bubble branch kmu_sg_clean removes, in reads"""
+    _fields_ = [("max_tip_reads", C.c_uint32), ("max_bubble_reads", C.c_uint32), ("flags", C.c_uint32), ("zero", C.c_uint32)]
+
+
+SG_CLEAN_STATS = ("n_tips", "n_tip_reads", "n_spared", "n_bubbles", "n_bubble_reads", "n_arcs_tip", "n_arcs_bubble", "n_arcs_left")
+
+
+class SgCleanStats(C.Structure):
+    """kmu_sg_clean_stats: what one call of kmu_sg_clean removed and what it left"""
+    _fields_ = [(name, C.c_uint64) for name in SG_CLEAN_STATS]
+
+
+# the same record as a numpy dtype (64 bytes)
+SG_CLEAN_STATS_DTYPE = [(name, "<u8") for name in SG_CLEAN_STATS]
 
 
 class ReadPile(C.Structure):

@@ -39,7 +39,7 @@ SYMBOLS = [
     "kmu_minimizer_layout", "kmu_read_minimizers", "kmu_seed_chains", "kmu_chain_align",
     "kmu_chain_cigar", "kmu_chain_pileup", "kmu_pile_call", "kmu_pile_ins_plan", "kmu_chain_pile_ins", "kmu_pile_consensus",
     "kmu_pile_segments", "kmu_extract_ranges", "kmu_pile_consensus_pos", "kmu_sg_classify", "kmu_sg_graph",
-    "kmu_sg_unitigs", "kmu_sg_unitig_seqs",
+    "kmu_sg_unitigs", "kmu_sg_unitig_seqs", "kmu_sg_clean",
 ]
 
 
@@ -168,6 +168,7 @@ def load():
                                C.POINTER(C.c_uint64)]
     L.kmu_sg_unitigs.argtypes = [vp, vp, C.c_uint64, vp, vp, C.c_uint32, C.c_int, vp, vp, vp, u64p, u64p]
     L.kmu_sg_unitig_seqs.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, vp, vp, C.c_uint32, C.c_int, vp, vp, C.c_uint64, u64p]
+    L.kmu_sg_clean.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint32, C.POINTER(A.SgCleanParams), C.c_int, vp, vp, C.POINTER(A.SgCleanStats)]
     L.kmu_set_hll_params.argtypes = [vp, C.POINTER(A.HllParams)]
     L.kmu_kmer_hashes_compact.argtypes = [vp, C.POINTER(A.HashParams), vp, vp, vp, C.c_uint32, vp, C.c_uint64, u64p]
     L.kmu_sketch_partial_words.argtypes = [C.POINTER(A.SketchParams)]
@@ -1384,6 +1385,33 @@ class Context:
         self._check(self.L.kmu_sg_unitigs(self.h, _ptr(arcs if n else none)[0], n, _ptr(reads if n_reads else None)[0], _ptr(off)[0], n_reads, mem,
                                           _ptr(unitigs)[0], _ptr(path)[0], _ptr(place)[0], C.byref(n_steps), C.byref(total)))
         return unitigs[:int(total.value)], path[:int(n_steps.value)], place[:n_reads]
+
+    def sg_clean(self, arcs, reads, n_reads, max_tip_reads=4, max_bubble_reads=8):
+        """kmu_sg_clean: one round of graph cleaning on the arcs of sg_graph (or of an earlier sg_clean) -- dead ends of at most
+        max_tip_reads reads are removed, simple bubbles whose branches hold at most max_bubble_reads reads are popped (0 turns a
+        phase off), `unique` and the degrees are recomputed (include/kmu.h has the rules).  arcs: the records, sorted by `from`;
+        reads: the summaries, or None.  Returns (arcs, reads, stats): new arrays with A.SG_ARC_TIP / A.SG_ARC_BUBBLE in the flags of
+        the removed arcs and A.SG_READ_TIP / A.SG_READ_BUBBLE in those of the removed reads, and a dict of the A.SG_CLEAN_STATS
+        counts; for torch cuda tensors int32 [n, 8] and [n_reads, 4] tensors holding the same bits, on the device."""
+        if not _is_torch(arcs):
+            arcs = np.ascontiguousarray(arcs)
+        if reads is not None and not _is_torch(reads):
+            reads = np.ascontiguousarray(reads)
+        mem = self._mem(arcs, reads)
+        n, n_reads = int(arcs.shape[0]), int(n_reads)
+        if reads is not None and int(reads.shape[0]) != n_reads:
+            raise ValueError("%d reads need as many summaries" % n_reads)
+        if mem == A.MEM_DEVICE:
+            arcs_out = self._new_like(arcs, (max(n, 1), 8), np.int32, "int32")
+            reads_out = self._new_like(arcs, (max(n_reads, 1), 4), np.int32, "int32")
+        else:
+            arcs_out = np.zeros(max(n, 1), np.dtype(A.SG_ARC_DTYPE))
+            reads_out = np.zeros(max(n_reads, 1), np.dtype(A.SG_READ_DTYPE))
+        none = self._new_like(arcs, 16, np.uint8, "uint8")  # an empty array has no address worth passing
+        p, stats = A.SgCleanParams(int(max_tip_reads), int(max_bubble_reads), 0, 0), A.SgCleanStats()
+        self._check(self.L.kmu_sg_clean(self.h, _ptr(arcs if n else none)[0], n, _ptr(reads if n_reads else None)[0], n_reads, C.byref(p), mem,
+                                        _ptr(arcs_out)[0], _ptr(reads_out)[0], C.byref(stats)))
+        return arcs_out[:n], reads_out[:n_reads], {name: int(getattr(stats, name)) for name in A.SG_CLEAN_STATS}
 
     def sg_unitig_seqs(self, unitigs, path, bases, offsets):
         """kmu_sg_unitig_seqs: the bases of every unitig -- over its steps, the last end - previous end bytes of the read in the

@@ -24,6 +24,9 @@ from reads to the graph, `unitig_labels` groups the reads of one unitig and `gfa
 `unitig_paths` and `unitig_sequences` hand the arcs to kmu_sg_unitigs / kmu_sg_unitig_seqs (Context.sg_unitigs,
 Context.sg_unitig_seqs): the reads of every unitig in walk order with their coordinates, and the unitig's bases; `read_unitigs`
 goes from reads to unitig sequences, and `unitig_gfa_lines` writes them as GFA `S` and `a` lines on the host.
+`clean_graph` hands the arcs to kmu_sg_clean (Context.sg_clean) before the layout: short dead ends are removed and simple bubbles
+popped, round after round while something goes; `layout_reads` marks the removed reads for `unitig_paths`, and `read_graph` and
+`read_unitigs` do both when given max_tip_reads or max_bubble_reads.
 """
 import collections
 
@@ -268,12 +271,44 @@ def overlap_graph(ctx, chains, aln, offsets, min_overlap=500, max_hang=1000, int
     return ctx.sg_graph(chains, aln, offsets, min_overlap, max_hang, int_permille, min_identity_permille, fuzz)
 
 
+def clean_graph(ctx, arcs, reads, n_reads, max_tip_reads=4, max_bubble_reads=8, rounds=1):
+    """Tips removed and simple bubbles popped (kmu_sg_clean): (arcs, reads, stats) as Context.sg_clean returns them.  The call is
+    repeated on its own output while a round removed something, at most `rounds` times; the stats are summed over the rounds, except
+    n_arcs_left, which is the last round's.  rounds=0 returns the inputs as they are, with zero stats."""
+    total = dict.fromkeys(A.SG_CLEAN_STATS, 0)
+    for _ in range(int(rounds)):
+        arcs, reads, stats = ctx.sg_clean(arcs, reads, n_reads, max_tip_reads, max_bubble_reads)
+        for name in A.SG_CLEAN_STATS:
+            total[name] = stats[name] if name == "n_arcs_left" else total[name] + stats[name]
+        if not stats["n_tip_reads"] and not stats["n_bubble_reads"]:
+            break
+    return arcs, reads, total
+
+
+def layout_reads(reads):
+    """A copy of the summaries in which every read that carries A.SG_READ_TIP or A.SG_READ_BUBBLE also carries
+    A.SG_READ_CONTAINED: unitig_paths then leaves the removed reads off the layout (numpy records, or the int32 [n_reads, 4] tensor)."""
+    removed = A.SG_READ_TIP | A.SG_READ_BUBBLE
+    if _is_torch(reads):
+        out = reads.clone()
+        out[:, 0] |= ((out[:, 0] & removed) != 0).to(out.dtype) * A.SG_READ_CONTAINED
+        return out
+    out = np.array(reads, copy=True)
+    out["flags"] |= ((out["flags"] & removed) != 0).astype(np.uint32) * np.uint32(A.SG_READ_CONTAINED)
+    return out
+
+
 def read_graph(ctx, bases, offsets, k, w, fhash=A.FHASH_CANON_INVHASH, max_occ=0, max_gap=5000, band_chain=500, min_seeds=3, min_score=0,
-               band=64, min_overlap=500, max_hang=1000, int_permille=250, min_identity_permille=0, fuzz=10):
+               band=64, min_overlap=500, max_hang=1000, int_permille=250, min_identity_permille=0, fuzz=10, max_tip_reads=0,
+               max_bubble_reads=0, clean_rounds=1):
     """From the reads of a batch to their string graph in one call: read_alignments, then overlap_graph on its records.  Returns
-    (arcs, arc_offsets, classes, reads); with torch cuda tensors nothing leaves the device."""
+    (arcs, arc_offsets, classes, reads); with torch cuda tensors nothing leaves the device.  With max_tip_reads or max_bubble_reads
+    above 0 the arcs and the summaries are those of clean_graph (the arcs keep their places, so arc_offsets still holds)."""
     chains, aln = read_alignments(ctx, bases, offsets, k, w, fhash, max_occ, max_gap, band_chain, min_seeds, min_score, band)
-    return overlap_graph(ctx, chains, aln, offsets, min_overlap, max_hang, int_permille, min_identity_permille, fuzz)
+    arcs, arc_offsets, classes, reads = overlap_graph(ctx, chains, aln, offsets, min_overlap, max_hang, int_permille, min_identity_permille, fuzz)
+    if max_tip_reads or max_bubble_reads:
+        arcs, reads, _ = clean_graph(ctx, arcs, reads, int(reads.shape[0]), max_tip_reads, max_bubble_reads, clean_rounds)
+    return arcs, arc_offsets, classes, reads
 
 
 def unitig_labels(ctx, arcs, n_reads):
@@ -303,11 +338,15 @@ def unitig_sequences(ctx, unitigs, path, bases, offsets):
 
 
 def read_unitigs(ctx, bases, offsets, k, w, fhash=A.FHASH_CANON_INVHASH, max_occ=0, max_gap=5000, band_chain=500, min_seeds=3, min_score=0,
-                 band=64, min_overlap=500, max_hang=1000, int_permille=250, min_identity_permille=0, fuzz=10):
+                 band=64, min_overlap=500, max_hang=1000, int_permille=250, min_identity_permille=0, fuzz=10, max_tip_reads=0,
+                 max_bubble_reads=0, clean_rounds=1):
     """From the reads of a batch to their unitigs in one call: read_graph, unitig_paths, unitig_sequences.  Returns (unitigs, path,
-    place, seq, seq_offsets); with torch cuda tensors nothing leaves the device."""
+    place, seq, seq_offsets); with torch cuda tensors nothing leaves the device.  With max_tip_reads or max_bubble_reads above 0
+    the graph is cleaned first and the removed reads are on no unitig (layout_reads)."""
     arcs, _, _, reads = read_graph(ctx, bases, offsets, k, w, fhash, max_occ, max_gap, band_chain, min_seeds, min_score, band, min_overlap,
-                                   max_hang, int_permille, min_identity_permille, fuzz)
+                                   max_hang, int_permille, min_identity_permille, fuzz, max_tip_reads, max_bubble_reads, clean_rounds)
+    if max_tip_reads or max_bubble_reads:
+        reads = layout_reads(reads)
     unitigs, path, place = unitig_paths(ctx, arcs, reads, offsets)
     seq, seq_offsets = unitig_sequences(ctx, unitigs, path, bases, offsets)
     return unitigs, path, place, seq, seq_offsets
@@ -334,13 +373,17 @@ def unitig_gfa_lines(unitigs, path, seq, seq_offsets, names):
 def gfa_lines(arcs, names, offsets, reduced=False, reads=None):
     """The graph as GFA 1 text, on the host: `S name * LN:i:len` for every read (with reads, the summaries of overlap_graph: for
     every read that is not contained), then `L from +/- to +/- <ovl>M` for every surviving arc in the order of the records;
-    reduced=True also writes the arcs that carry A.SG_ARC_REDUCED.  arcs: numpy A.SG_ARC_DTYPE records."""
+    reduced=True also writes the arcs that carry A.SG_ARC_REDUCED.  What clean_graph removed is never written: neither the reads
+    with A.SG_READ_TIP or A.SG_READ_BUBBLE nor the arcs with A.SG_ARC_TIP or A.SG_ARC_BUBBLE.  arcs: numpy A.SG_ARC_DTYPE records."""
     off = np.asarray(offsets).astype(np.int64)
     lines = []
+    gone = A.SG_READ_CONTAINED | A.SG_READ_TIP | A.SG_READ_BUBBLE
     for r in range(off.shape[0] - 1):
-        if reads is None or not int(reads["flags"][r]) & A.SG_READ_CONTAINED:
+        if reads is None or not int(reads["flags"][r]) & gone:
             lines.append("S\t%s\t*\tLN:i:%d" % (names[r], off[r + 1] - off[r]))
     for v, t, _, ovl, _, flags, _, _ in np.asarray(arcs).tolist():
+        if flags & (A.SG_ARC_TIP | A.SG_ARC_BUBBLE):
+            continue
         if reduced or not flags & A.SG_ARC_REDUCED:
             lines.append("L\t%s\t%s\t%s\t%s\t%dM" % (names[v >> 1], "-" if v & 1 else "+", names[t >> 1], "-" if t & 1 else "+", ovl))
     return lines
