@@ -38,6 +38,8 @@
  *                 Unitigs, sg_unitigs, UnitigSequences, unitig_sequences, ReadUnitigs, read_unitigs, unitig_gfa_line
  *                 (the ordered reads of every unitig, their coordinates and the unitig's bases)
  *                 CleanGraph, sg_clean, clean_graph, layout_reads (tips removed and simple bubbles popped before the layout)
+ *                 UnitigChains, sg_unitig_chains, unitig_read_chains, PolishedUnitigs, polish_unitigs
+ *                 (every read mapped onto its unitig from the layout, and the consensus of a unitig over its reads)
  *                 seed_chains, seed_pairs, chain_hits, read_chains (one base-resolution chain per read pair from minimizer
  *                                                            hits)                          (beyond the reference)
  *   counting      KmerCountT (trait), KmerCounter, KmerCounterPool, count_kmer_threaded_one_to_many
@@ -2662,6 +2664,112 @@ inline std::vector<kmu_sg_read> layout_reads(std::vector<kmu_sg_read> reads) {
     for (kmu_sg_read &r : reads)
         if (r.flags & (KMU_SG_READ_TIP | KMU_SG_READ_BUBBLE)) r.flags |= KMU_SG_READ_CONTAINED;
     return reads;
+}
+
+// =====================================================================================================================
+// unitig consensus (kmu_sg_unitig_chains and the correction stages over it; the reference has no such unit)
+// =====================================================================================================================
+
+/// What sg_unitig_chains returns: at most one record per read in ascending read id -- read_a the unitig, read_b the read, score 0 for
+/// a layout read and 1 for a contained one -- and the counts.
+struct UnitigChains {
+    std::vector<kmu_chain> records;
+    kmu_um_stats stats{};
+};
+
+/// kmu_sg_unitig_chains on host arrays (Context.sg_unitig_chains): where every read lies on which unitig.  layout: of sg_unitigs;
+/// chains, classes: the self-join and its classes of overlap_graph (both empty: no contained read is placed); offsets: the batch's.
+inline UnitigChains sg_unitig_chains(const Unitigs &layout, const std::vector<kmu_chain> &chains, const std::vector<uint8_t> &classes,
+                                     const std::vector<uint64_t> &offsets, Context &ctx = Context::global()) {
+    if (offsets.empty()) throw std::invalid_argument("sg_unitig_chains: the offsets of a batch have at least one entry");
+    const uint32_t n_reads = uint32_t(offsets.size() - 1);
+    if (layout.place.size() != n_reads) throw std::invalid_argument("sg_unitig_chains: as many places as reads");
+    if (chains.size() != classes.size()) throw std::invalid_argument("sg_unitig_chains: as many classes as chains");
+    UnitigChains out;
+    out.records.assign(size_t(n_reads) + 1, kmu_chain{}); // an empty vector has no address worth passing
+    const kmu_sg_unitig no_unitig{};
+    const kmu_sg_step no_step{};
+    const kmu_sg_place no_place{};
+    const kmu_um_params p{0u, 0u};
+    uint64_t total = 0;
+    ctx.check(kmu_sg_unitig_chains(ctx.raw(), layout.unitigs.empty() ? &no_unitig : layout.unitigs.data(), layout.unitigs.size(),
+                                   layout.path.empty() ? &no_step : layout.path.data(), layout.path.size(),
+                                   layout.place.empty() ? &no_place : layout.place.data(), chains.empty() ? nullptr : chains.data(),
+                                   classes.empty() ? nullptr : classes.data(), chains.size(), offsets.data(), n_reads, &p, KMU_MEM_HOST,
+                                   out.records.data(), &out.stats, &total));
+    out.records.resize(total);
+    return out;
+}
+/// The same under the name of the Python route (minimizer.unitig_read_chains)
+inline UnitigChains unitig_read_chains(const Unitigs &layout, const std::vector<kmu_chain> &chains, const std::vector<uint8_t> &classes,
+                                       const std::vector<uint64_t> &offsets, Context &ctx = Context::global()) {
+    return sg_unitig_chains(layout, chains, classes, offsets, ctx);
+}
+
+/// What polish_unitigs returns: the polished unitigs as a batch, the layout in polished coordinates (the unitigs' len and the steps'
+/// end; the places are unchanged), the summaries of pile_call, and the map's records with their alignments (of the last round).
+struct PolishedUnitigs {
+    ConsensusReads cons;
+    Unitigs layout;
+    std::vector<kmu_read_pile> summaries;
+    std::vector<kmu_chain> records;
+    std::vector<kmu_chain_aln> aln;
+    kmu_um_stats stats{};
+};
+
+/// The consensus of every unitig over its reads (minimizer.polish_unitigs): sg_unitig_chains, then -- with the unitig batch as the q
+/// side and the reads as the db side -- chain_cigar, chain_pileup and chain_pile_ins with KMU_PILE_Q, pile_call with `min_depth`,
+/// pile_ins_plan with `max_ins`, pile_consensus; every step's end goes into polished coordinates through pile_consensus_pos.
+/// rounds > 1 translates the records' a coordinates the same way and runs the stages again on the polished batch.
+inline PolishedUnitigs polish_unitigs(const Unitigs &layout, const UnitigSequences &sequences, const detail::Batch &reads,
+                                      const std::vector<kmu_chain> &chains = {}, const std::vector<uint8_t> &classes = {}, uint32_t band = 64,
+                                      uint64_t max_trace_bytes = 0, uint32_t min_depth = 2, uint32_t max_ins = 16, uint32_t rounds = 1,
+                                      Context &ctx = Context::global()) {
+    const detail::Batch db = detail::unpacked(reads);
+    if (db.on_device()) throw std::invalid_argument("polish_unitigs returns host arrays: it needs the sequences in host memory");
+    UnitigChains map = sg_unitig_chains(layout, chains, classes, db.offsets, ctx);
+    PolishedUnitigs out;
+    out.stats = map.stats;
+    out.layout = layout;
+    out.records = std::move(map.records);
+    detail::Batch q;
+    q.bytes = sequences.seq;
+    q.bytes.resize(q.bytes.size() + 16, 0);
+    q.offsets = sequences.seq_offsets;
+    InsPlan no_slots; // the reads get no votes: a plan without slots stands for their side
+    no_slots.ins_len.assign(db.offsets.back(), 0);
+    for (uint32_t round = 0; round < std::max(rounds, 1u); round++) {
+        const std::vector<kmu_chain> used = out.records;
+        ChainCigars cigars = chain_cigar(used, q, &db, band, max_trace_bytes, ctx);
+        const ChainPileups pile = chain_pileup(used, cigars, q, &db, KMU_PILE_Q, {}, ctx);
+        PileCalls calls = pile_call(pile.q, q, min_depth, ctx);
+        const InsPlan plan = pile_ins_plan(pile.q, calls.call, max_ins, ctx);
+        const ChainInsertions ins = chain_pile_ins(used, cigars, q, plan, &db, &no_slots, KMU_PILE_Q, {}, ctx);
+        out.cons = pile_consensus(pile.q, calls.call, plan, ins.q, q, ctx);
+        std::vector<uint64_t> rows, base;
+        auto ask = [&](uint32_t unitig, uint64_t coord) {
+            rows.push_back(q.offsets[unitig] + coord);
+            base.push_back(out.cons.offsets[unitig]);
+        };
+        for (const kmu_sg_step &s : out.layout.path) ask(out.layout.place[s.read].unitig, s.end);
+        for (const kmu_chain &c : used) ask(c.read_a, c.a_start);
+        for (const kmu_chain &c : used) ask(c.read_a, c.a_end);
+        const std::vector<uint64_t> pos = pile_consensus_pos(pile.q, calls.call, plan, ins.q, q, rows, ctx);
+        const size_t n = out.layout.path.size(), m = used.size();
+        for (size_t i = 0; i < n; i++) out.layout.path[i].end = pos[i] - base[i];
+        for (size_t i = 0; i < m; i++) {
+            out.records[i].a_start = uint32_t(pos[n + i] - base[n + i]);
+            out.records[i].a_end = uint32_t(pos[n + m + i] - base[n + m + i]);
+        }
+        for (size_t u = 0; u < out.layout.unitigs.size(); u++) out.layout.unitigs[u].len = out.cons.offsets[u + 1] - out.cons.offsets[u];
+        out.summaries = std::move(calls.reads);
+        out.aln = std::move(cigars.aln);
+        if (round + 1 == std::max(rounds, 1u)) out.records = used; // the records that were aligned, as the Python route returns them
+        q.bytes = out.cons.bases;
+        q.bytes.resize(q.bytes.size() + 16, 0);
+        q.offsets = out.cons.offsets;
+    }
+    return out;
 }
 
 // =====================================================================================================================

@@ -1541,6 +1541,63 @@ int kmu_sg_clean(kmu_ctx *ctx, const kmu_sg_arc *arcs, uint64_t n_arcs,
                  kmu_sg_read *reads_out,         /* n_reads; may be NULL */
                  kmu_sg_clean_stats *stats_out); /* host memory in both modes; required */
 
+/* ---- unitig map: one chain record per read saying where the read lies on which unitig ---------------------------------
+ * The layout already knows where every read lies, so no seeding or chaining against the unitig bases is needed: the records written
+ *   here feed kmu_chain_cigar / kmu_chain_pileup / ... with the unitig batch (seq, seq_offsets of kmu_sg_unitig_seqs) as the q side
+ *   and the reads as the db side, votes with KMU_PILE_Q, which is the consensus over a unitig's reads.
+ * Inputs: unitigs[n_unitigs], path[n_steps] and place[n_reads] as kmu_sg_unitigs writes them; chains[n_chains] and
+ *   classes[n_chains], the self-join and the class_out of kmu_sg_graph / kmu_sg_classify (both may be NULL with n_chains == 0: then
+ *   no contained read is placed); offsets[n_reads + 1] of the batch -- only the lengths are used.
+ * Output: at most one record per read, in ascending read id; out has room for n_reads, there is no count call; *n_out (host memory)
+ *   is the number of records.  read_a = the unitig, read_b = the read, strand as kmu_chain_align reads it, score = 0 for a layout
+ *   read and 1 for a contained read, n_seeds = the index of the containment record or KMU_SG_NONE, n_anchors = the container read
+ *   or KMU_SG_NONE.
+ * Layout read: place[r] = {u, rank, s}, its step path[unitigs[u].first + rank] has end e, the read has length L, t = min(L, e):
+ *   a = [e - t, e), b = the last t bases of the read in the step's orientation, [L - t, L) for s = 0 and [0, t) for s = 1;
+ *   strand = s.  t < L at the start of a circular unitig and wherever a later read is longer than everything before it.
+ * Contained read: place[c].unitig == KMU_SG_NONE.  Chain x is a CANDIDATE iff classes[x] == KMU_SG_A_CONTAINED and read_a == c
+ *   (the container is g = read_b, c's segment [cs, ce) is the a segment, g's segment [gs, ge) the b segment) or classes[x] ==
+ *   KMU_SG_B_CONTAINED and read_b == c (g = read_a, the segments the other way round) -- no other class is looked at --, g is
+ *   placed (one level only: a read contained only in contained reads stays unplaced), and, with g's step (sg, e_g), its length L_g
+ *   and os = gs for sg = 0, L_g - ge for sg = 1, a_start = e_g - L_g + os (signed 64 bits) is >= 0.  The winner is the candidate
+ *   with the largest ce - cs, at equal lengths the smallest x: one 64-bit atomic maximum of (ce - cs) << 32 | (2^32 - 1 - x) per
+ *   contained read, so timing changes nothing.  Its record: a = [a_start, a_start + (ge - gs)) on g's unitig, b = [cs, ce),
+ *   strand = sg ^ the record's strand.
+ * The a coordinates are NOMINAL: the last c bytes of a read sit exactly where its record says; its earlier bytes lie on stretches
+ *   copied from other reads, so the record is off there by the indel drift between the reads, which the band of the alignment
+ *   absorbs.  On error-free reads the coordinates are exact (overlap hangs are differences on one diagonal).
+ * stats_out (host memory): n_layout reads with a place, n_contained contained reads with a winner, n_unplaced the rest.
+ * KMU_E_BAD_ARG (nothing is launched): null ctx / p / offsets / out / stats_out / n_out; unitigs, path or place null while their
+ *   count is > 0 (place: n_reads); chains or classes null with n_chains > 0; non-zero flags or zero; bad mem.
+ * KMU_E_UNSUPPORTED: n_chains >= 2^32, n_reads >= 2^31, and the faults, found on the device; the call is refused at its one
+ *   synchronisation, every output (stats_out and n_out included) is left untouched and no faulty record is used as an index:
+ *   a unitig with first + n_reads > n_steps or len >= 2^32 (kmu_chain holds 32-bit positions); a step with read >= n_reads,
+ *   strand > 1 or end == 0; a place with a unitig >= n_unitigs that is not KMU_SG_NONE, a rank >= that unitig's n_reads, a step
+ *   that does not name the read with the place's strand, or a step whose end is above the unitig's len; a record of class
+ *   A_CONTAINED or B_CONTAINED with a read >= n_reads, strand > 1, a start above its end or an end above its read's length.
+ * n_reads == 0: KMU_OK with zero counts.
+ * KMU_MEM_DEVICE: every array except p, stats_out and n_out is device memory; one synchronisation, which hands over the counts and
+ *   the refusal flag, also in async_device contexts.  KMU_MEM_HOST: the arrays go up through the context's workspace and the
+ *   records come back.
+ * How: one lane per unitig / step / place checks; one lane per chain tests candidacy and does the atomic maximum; one lane per read
+ *   decides whether it has a record; a scan over the reads; one lane per read writes.  Four kernels and a scan whatever the data;
+ *   integer compares, idempotent stores and commuting integer atomics only.  DESIGN.md 3.25 has the kernels. */
+typedef struct {
+    uint32_t flags;             /* no flag bits yet: must be 0 */
+    uint32_t zero;
+} kmu_um_params;
+typedef struct {
+    uint64_t n_layout, n_contained, n_unplaced;
+} kmu_um_stats;
+int kmu_sg_unitig_chains(kmu_ctx *ctx, const kmu_sg_unitig *unitigs, uint64_t n_unitigs, const kmu_sg_step *path,
+                         uint64_t n_steps,
+                         const kmu_sg_place *place,   /* n_reads, as kmu_sg_unitigs wrote it */
+                         const kmu_chain *chains, const uint8_t *classes, uint64_t n_chains, /* may be NULL with n_chains == 0 */
+                         const uint64_t *offsets, uint32_t n_reads, const kmu_um_params *p, int mem,
+                         kmu_chain *out,              /* room for n_reads */
+                         kmu_um_stats *stats_out,     /* host memory in both modes; required */
+                         uint64_t *n_out);            /* host memory in both modes; required */
+
 #ifdef __cplusplus
 }
 #endif

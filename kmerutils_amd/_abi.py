@@ -258,6 +258,23 @@ class SgCleanStats(C.Structure):
 SG_CLEAN_STATS_DTYPE = [(name, "<u8") for name in SG_CLEAN_STATS]
 
 
+class UmParams(C.Structure):
+    """kmu_um_params: no flag bits yet"""
+    _fields_ = [("flags", C.c_uint32), ("zero", C.c_uint32)]
+
+
+UM_STATS = ("n_layout", "n_contained", "n_unplaced")
+
+
+class UmStats(C.Structure):
+    """kmu_um_stats: how many reads kmu_sg_unitig_chains placed from the layout, how many through a container, how many not"""
+    _fields_ = [(name, C.c_uint64) for name in UM_STATS]
+
+
+# the same record as a numpy dtype (24 bytes)
+UM_STATS_DTYPE = [(name, "<u8") for name in UM_STATS]
+
+
 class ReadPile(C.Structure):
     """kmu_read_pile: the summary of one read's rows (kmu_pile_call)"""
     _fields_ = [("n_bases", C.c_uint32), ("covered", C.c_uint32), ("n_diff", C.c_uint32), ("n_del", C.c_uint32),

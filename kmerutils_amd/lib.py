@@ -39,7 +39,7 @@ SYMBOLS = [
     "kmu_minimizer_layout", "kmu_read_minimizers", "kmu_seed_chains", "kmu_chain_align",
     "kmu_chain_cigar", "kmu_chain_pileup", "kmu_pile_call", "kmu_pile_ins_plan", "kmu_chain_pile_ins", "kmu_pile_consensus",
     "kmu_pile_segments", "kmu_extract_ranges", "kmu_pile_consensus_pos", "kmu_sg_classify", "kmu_sg_graph",
-    "kmu_sg_unitigs", "kmu_sg_unitig_seqs", "kmu_sg_clean",
+    "kmu_sg_unitigs", "kmu_sg_unitig_seqs", "kmu_sg_clean", "kmu_sg_unitig_chains",
 ]
 
 
@@ -169,6 +169,8 @@ def load():
     L.kmu_sg_unitigs.argtypes = [vp, vp, C.c_uint64, vp, vp, C.c_uint32, C.c_int, vp, vp, vp, u64p, u64p]
     L.kmu_sg_unitig_seqs.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, vp, vp, C.c_uint32, C.c_int, vp, vp, C.c_uint64, u64p]
     L.kmu_sg_clean.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint32, C.POINTER(A.SgCleanParams), C.c_int, vp, vp, C.POINTER(A.SgCleanStats)]
+    L.kmu_sg_unitig_chains.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, vp, vp, vp, C.c_uint64, vp, C.c_uint32, C.POINTER(A.UmParams),
+                                       C.c_int, vp, C.POINTER(A.UmStats), u64p]
     L.kmu_set_hll_params.argtypes = [vp, C.POINTER(A.HllParams)]
     L.kmu_kmer_hashes_compact.argtypes = [vp, C.POINTER(A.HashParams), vp, vp, vp, C.c_uint32, vp, C.c_uint64, u64p]
     L.kmu_sketch_partial_words.argtypes = [C.POINTER(A.SketchParams)]
@@ -1412,6 +1414,43 @@ class Context:
         self._check(self.L.kmu_sg_clean(self.h, _ptr(arcs if n else none)[0], n, _ptr(reads if n_reads else None)[0], n_reads, C.byref(p), mem,
                                         _ptr(arcs_out)[0], _ptr(reads_out)[0], C.byref(stats)))
         return arcs_out[:n], reads_out[:n_reads], {name: int(getattr(stats, name)) for name in A.SG_CLEAN_STATS}
+
+    def sg_unitig_chains(self, unitigs, path, place, chains, classes, offsets):
+        """kmu_sg_unitig_chains: one chain record per read saying where the read lies on which unitig -- from the layout for a read
+        on a path, from its longest containment record projected through the container's place for a contained read whose
+        container is on a path (include/kmu.h has the rules).  unitigs, path, place: the records of sg_unitigs; chains, classes:
+        the self-join and the classes of sg_graph / sg_classify for it, or both None (then no contained read is placed); offsets:
+        the batch's, of which only the lengths count.  Returns (records, stats): A.CHAIN_DTYPE records in ascending read id with
+        read_a = the unitig (a read of the batch of sg_unitig_seqs) and read_b = the read, and a dict of the A.UM_STATS counts; for
+        torch cuda tensors an int32 tensor [n, 10] holding the same bits, on the device."""
+        if not _is_torch(unitigs):
+            unitigs, path, place = np.ascontiguousarray(unitigs), np.ascontiguousarray(path), np.ascontiguousarray(place)
+        if (chains is None) != (classes is None):
+            raise ValueError("chains and classes come together")
+        if chains is not None and not _is_torch(chains):
+            chains, classes = np.ascontiguousarray(chains), np.ascontiguousarray(classes)
+        mem = self._mem(unitigs, path, place, chains, classes)
+        n, n_steps = int(unitigs.shape[0]), int(path.shape[0])
+        n_chains = 0 if chains is None else int(chains.shape[0])
+        if n_chains and int(classes.shape[0]) != n_chains:
+            raise ValueError("%d chains need as many classes" % n_chains)
+        off = self._offsets_like(offsets, place, mem)
+        n_reads = int(off.shape[0]) - 1
+        if int(place.shape[0]) != n_reads:
+            raise ValueError("%d reads need as many places" % n_reads)
+        if mem == A.MEM_DEVICE:
+            out = self._new_like(place, (max(n_reads, 1), 10), np.int32, "int32")
+        else:
+            out = np.zeros(max(n_reads, 1), np.dtype(A.CHAIN_DTYPE))
+        none = self._new_like(place, 16, np.uint8, "uint8")  # an empty array has no address worth passing
+
+        def ptr(x):
+            return _ptr(x)[0] if int(x.shape[0]) else _ptr(none)[0]
+        p, stats, total = A.UmParams(0, 0), A.UmStats(), C.c_uint64(0)
+        self._check(self.L.kmu_sg_unitig_chains(self.h, ptr(unitigs), n, ptr(path), n_steps, ptr(place), ptr(chains) if n_chains else None,
+                                                ptr(classes) if n_chains else None, n_chains, _ptr(off)[0], n_reads, C.byref(p), mem,
+                                                _ptr(out)[0], C.byref(stats), C.byref(total)))
+        return out[:int(total.value)], {name: int(getattr(stats, name)) for name in A.UM_STATS}
 
     def sg_unitig_seqs(self, unitigs, path, bases, offsets):
         """kmu_sg_unitig_seqs: the bases of every unitig -- over its steps, the last end - previous end bytes of the read in the

@@ -27,6 +27,11 @@ goes from reads to unitig sequences, and `unitig_gfa_lines` writes them as GFA `
 `clean_graph` hands the arcs to kmu_sg_clean (Context.sg_clean) before the layout: short dead ends are removed and simple bubbles
 popped, round after round while something goes; `layout_reads` marks the removed reads for `unitig_paths`, and `read_graph` and
 `read_unitigs` do both when given max_tip_reads or max_bubble_reads.
+`unitig_read_chains` hands the layout and the self-join's containment records to kmu_sg_unitig_chains (Context.sg_unitig_chains):
+one chain record per read saying where it lies on which unitig; `polish_unitigs` runs cigar_chains, pileup_chains, pile_call,
+pile_ins_plan, insertions_chains and consensus_reads on those records with the unitig batch as the q side -- the consensus of every
+unitig over its reads --, `polished_unitigs` gives the unitig records their new lengths, and `read_contigs` goes from reads to
+polished unitigs.
 """
 import collections
 
@@ -350,6 +355,107 @@ def read_unitigs(ctx, bases, offsets, k, w, fhash=A.FHASH_CANON_INVHASH, max_occ
     unitigs, path, place = unitig_paths(ctx, arcs, reads, offsets)
     seq, seq_offsets = unitig_sequences(ctx, unitigs, path, bases, offsets)
     return unitigs, path, place, seq, seq_offsets
+
+
+def unitig_read_chains(ctx, unitigs, path, place, chains, classes, offsets):
+    """Where every read lies on which unitig, as chain records (kmu_sg_unitig_chains): (records, stats) as Context.sg_unitig_chains
+    returns them.  unitigs, path, place: of unitig_paths; chains, classes: the self-join and the classes of overlap_graph for it, or
+    None for both (then the contained reads stay unplaced); offsets: the batch's.  The records name the unitig batch of
+    unitig_sequences as their q side and the reads as their db side: they go into cigar_chains and what follows it."""
+    return ctx.sg_unitig_chains(unitigs, path, place, chains, classes, offsets)
+
+
+def _polished_coordinates(ctx, tables, seq, seq_offsets, cons_offsets, path, place, records):
+    """(ends, a_start, a_end) in the polished batch: every step's end and every map record's a coordinates through
+    Context.pile_consensus_pos, as correct_trim_reads translates its segment ends; int64, where the arrays live.  A step's unitig is
+    that of its read's place."""
+    pile, call, ins_len, n_slots, ins = tables
+    if _is_torch(path):
+        import torch
+        m32 = 0xFFFFFFFF
+        off, cons = seq_offsets.long(), cons_offsets.long()
+        u_step = place[:, 0].long()[path[:, 0].long() & m32] & m32
+        u_rec = records[:, 0].long() & m32
+        ends = (path[:, 2].long() & m32) | (path[:, 3].long() << 32)
+        rows = torch.cat([off[u_step] + ends, off[u_rec] + (records[:, 6].long() & m32), off[u_rec] + (records[:, 7].long() & m32)]).contiguous()
+        base = torch.cat([cons[u_step], cons[u_rec], cons[u_rec]])
+        pos = ctx.pile_consensus_pos(pile, call, ins_len, n_slots, ins, seq, seq_offsets, rows).long() - base
+    else:
+        off, cons = np.asarray(seq_offsets).astype(np.int64), np.asarray(cons_offsets).astype(np.int64)
+        u_step = place["unitig"][path["read"]].astype(np.int64)
+        u_rec = records["read_a"].astype(np.int64)
+        rows = np.concatenate([off[u_step] + path["end"].astype(np.int64), off[u_rec] + records["a_start"], off[u_rec] + records["a_end"]])
+        pos = ctx.pile_consensus_pos(pile, call, ins_len, n_slots, ins, seq, seq_offsets, rows).astype(np.int64) - np.concatenate(
+            [cons[u_step], cons[u_rec], cons[u_rec]])
+    n, m = int(path.shape[0]), int(records.shape[0])
+    return pos[:n], pos[n:n + m], pos[n + m:]
+
+
+def polish_unitigs(ctx, unitigs, path, place, seq, seq_offsets, bases, offsets, chains=None, classes=None, band=64, max_trace_bytes=0,
+                   min_depth=2, max_ins=16, rounds=1):
+    """The consensus of every unitig over its reads: unitig_read_chains, then -- with the unitig batch (seq, seq_offsets) of
+    unitig_sequences as the q side and the reads as the db side -- cigar_chains, pileup_chains and insertions_chains with
+    sides=A.PILE_Q, Context.pile_call with `min_depth`, Context.pile_ins_plan with `max_ins` and consensus_reads.  chains, classes: the
+    self-join and its classes, through which the contained reads vote too.  Returns (cons_seq, cons_offsets, new_path, summaries,
+    map_records, aln): the polished batch; `path` with every end in polished coordinates (Context.pile_consensus_pos), so that
+    unitig_gfa_lines(polished_unitigs(unitigs, cons_offsets), new_path, cons_seq, cons_offsets, names) holds; the summaries of
+    pile_call; the map's records and their alignment records.  rounds > 1 translates the records' a coordinates the same way and
+    runs the stages again on the polished batch; then map_records and aln are those of the last round.  With torch cuda tensors
+    nothing leaves the device."""
+    records, _ = unitig_read_chains(ctx, unitigs, path, place, chains, classes, offsets)
+    summaries = aln = None
+    for _ in range(max(int(rounds), 1)):
+        aln, ops, op_offsets = cigar_chains(ctx, records, seq, seq_offsets, bases, offsets, band=band, max_trace_bytes=max_trace_bytes)
+        pile, _ = pileup_chains(ctx, records, aln, ops, op_offsets, seq, seq_offsets, bases, offsets, sides=A.PILE_Q)
+        call, summaries = ctx.pile_call(pile, seq, seq_offsets, min_depth=min_depth)
+        ins_len, n_slots = ctx.pile_ins_plan(pile, call, max_ins=max_ins)
+        ins, _ = insertions_chains(ctx, records, aln, ops, op_offsets, seq, seq_offsets, ins_len, n_slots, bases, offsets, sides=A.PILE_Q)
+        cons_seq, cons_offsets = consensus_reads(ctx, pile, call, ins_len, n_slots, ins, seq, seq_offsets)
+        ends, a_start, a_end = _polished_coordinates(ctx, (pile, call, ins_len, n_slots, ins), seq, seq_offsets, cons_offsets, path, place,
+                                                     records)
+        used = records
+        if _is_torch(path):
+            path, records = path.clone(), records.clone()
+            path[:, 2:4] = ends.contiguous().view(path.dtype).reshape(-1, 2)
+            records[:, 6], records[:, 7] = a_start.to(records.dtype), a_end.to(records.dtype)
+        else:
+            path, records = np.array(path, copy=True), np.array(records, copy=True)
+            path["end"] = ends.astype(np.uint64)
+            records["a_start"], records["a_end"] = a_start.astype(np.uint32), a_end.astype(np.uint32)
+        seq, seq_offsets = cons_seq, cons_offsets
+    return seq, seq_offsets, path, summaries, used, aln
+
+
+def polished_unitigs(unitigs, cons_offsets):
+    """A copy of the unitig records whose len is that of the polished batch (numpy records, or the int32 [n, 8] tensor)"""
+    if _is_torch(unitigs):
+        out = unitigs.clone()
+        length = (cons_offsets[1:] - cons_offsets[:-1]).long().contiguous()
+        out[:, 2:4] = length.view(out.dtype).reshape(-1, 2)
+        return out
+    out = np.array(unitigs, copy=True)
+    out["len"] = np.diff(np.asarray(cons_offsets).astype(np.uint64))
+    return out
+
+
+def read_contigs(ctx, bases, offsets, k, w, fhash=A.FHASH_CANON_INVHASH, max_occ=0, max_gap=5000, band_chain=500, min_seeds=3, min_score=0,
+                 band=64, min_overlap=500, max_hang=1000, int_permille=250, min_identity_permille=0, fuzz=10, max_tip_reads=0,
+                 max_bubble_reads=0, clean_rounds=1, min_depth=2, max_ins=16, rounds=1):
+    """From the reads of a batch to polished unitigs in one call: the stages of read_unitigs with the same keywords (its outputs are
+    the same bytes; the chains and their classes are kept here, since the contained reads vote through them), then polish_unitigs.
+    Returns (unitigs, path, place, cons_seq, cons_offsets, summaries): the unitig records with the polished lengths, the steps with
+    polished ends, the places, the polished batch and the summaries of pile_call.  With torch cuda tensors nothing leaves the
+    device."""
+    chains, aln = read_alignments(ctx, bases, offsets, k, w, fhash, max_occ, max_gap, band_chain, min_seeds, min_score, band)
+    arcs, _, classes, reads = overlap_graph(ctx, chains, aln, offsets, min_overlap, max_hang, int_permille, min_identity_permille, fuzz)
+    if max_tip_reads or max_bubble_reads:
+        arcs, reads, _ = clean_graph(ctx, arcs, reads, int(reads.shape[0]), max_tip_reads, max_bubble_reads, clean_rounds)
+        reads = layout_reads(reads)
+    unitigs, path, place = unitig_paths(ctx, arcs, reads, offsets)
+    seq, seq_offsets = unitig_sequences(ctx, unitigs, path, bases, offsets)
+    cons_seq, cons_offsets, new_path, summaries, _, _ = polish_unitigs(ctx, unitigs, path, place, seq, seq_offsets, bases, offsets, chains,
+                                                                       classes, band, 0, min_depth, max_ins, rounds)
+    return polished_unitigs(unitigs, cons_offsets), new_path, place, cons_seq, cons_offsets, summaries
 
 
 def unitig_gfa_lines(unitigs, path, seq, seq_offsets, names):
