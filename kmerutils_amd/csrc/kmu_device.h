@@ -514,6 +514,23 @@ __device__ __forceinline__ void chunk16_to_lds(const uint8_t *src, uint8_t *lds_
     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *) src,
                                      (__attribute__((address_space(3))) void *) lds_wave_base, 16, 0, 0);
 }
+// The same request as an instruction the compiler does not count.  Its s_waitcnt pass takes an LDS-DMA it knows of for a pending
+// write to ALL of LDS and puts `s_waitcnt vmcnt(0)` in front of every later ds_* instruction: a request made to land under an LDS
+// phase is then waited for at the top of that phase.  Here the caller waits itself (vmcnt(0), then reads only what its own lanes asked
+// for, or a barrier first) and nothing else may touch the landing area in between.  lds_wave_addr: the wave's landing address as an
+// LDS byte address (lds_addr), wave-uniform; M0 carries it to the instruction and is put back.  The compiler's counted waits for its
+// own loads stay right with such a request among them: vector memory loads return in order, one more in flight only makes
+// `vmcnt(N)` wait longer.
+__device__ __forceinline__ uint32_t lds_addr(const void *p) {
+    return (uint32_t) (uintptr_t) (const __attribute__((address_space(3))) void *) p;
+}
+__device__ __forceinline__ void chunk16_to_lds_uncounted(const uint8_t *src, uint32_t lds_wave_addr) {
+    uint32_t keep;
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
+                 : "=&s"(keep)
+                 : "v"(src), "s"(__builtin_amdgcn_readfirstlane(lds_wave_addr))
+                 : "memory");
+}
 // true if word `widx` of the sequence's aligned stream is a whole chunk inside the array (chunk16_to_lds may fetch it)
 __device__ __forceinline__ bool chunk_is_plain(const SeqView &s, uint64_t widx) {
     return !s.packed && (s.begin & ~15ull) + 16 * widx + 16 <= s.total;

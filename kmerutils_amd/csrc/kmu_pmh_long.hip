@@ -129,17 +129,29 @@ __global__ void __launch_bounds__(1024, 4) k_multiset_long(SketchArgs a) {
                         if (!(4u * (uint32_t) UQ_THREADS * (uint32_t) (q0 >> 2) < span_t)) continue;
                         const uint32_t wi = ((uint32_t) tid >> 2) + (uint32_t) (UQ_THREADS / 4) * (uint32_t) (q0 >> 2); // the quarter's word
                         const StepWin sw = step_win(words[wi], words[wi + 1], words[wi + 2], k);
+                        // the four keys of the quarter first, then their four ds_add_rtn, then the answers: no answer is looked at inside the
+                        // per-lane branch that asked for it (where it was waited for on the spot: one LDS round trip per key, in turn)
+                        uint64_t key[4];
+                        uint32_t part[4], at[4];
 #pragma unroll
                         for (int u = 0; u < 4; u++) {
+                            key[u] = 0;
+                            part[u] = 0xFFFFFFFFu; // no key
                             if (t0 + place_of(q0 + u) - l0 < nk) {
                                 uint64_t val, rc;
                                 step_val_rc(sw, 4u * ((uint32_t) tid & 3u) + (uint32_t) u, val, rc);
-                                const uint64_t key = FAST ? int64_hash(rc < val ? rc : val) : apply_fhash(cfg, val, rc);
-                                const uint32_t p = pmh_long_part_of(key, P);
-                                const uint32_t at = atomicAdd(&pcnt[p], 1u);
-                                if (at < UQ_KEYS) st_scr(&seg0[(uint64_t) p * DEF_SEG + at], key);
+                                key[u] = FAST ? int64_hash(rc < val ? rc : val) : apply_fhash(cfg, val, rc);
+                                part[u] = pmh_long_part_of(key[u], P);
                             }
                         }
+#pragma unroll
+                        for (int u = 0; u < 4; u++) {
+                            at[u] = 0xFFFFFFFFu;
+                            if (part[u] != 0xFFFFFFFFu) at[u] = atomicAdd(&pcnt[part[u]], 1u);
+                        }
+#pragma unroll
+                        for (int u = 0; u < 4; u++)
+                            if (at[u] < UQ_KEYS) st_scr(&seg0[(uint64_t) part[u] * DEF_SEG + at[u]], key[u]);
                     }
                     lds_barrier(); // (the next tile's words replace these)
                 }
@@ -173,30 +185,29 @@ __global__ void __launch_bounds__(1024, 4) k_multiset_long(SketchArgs a) {
                         for (int u = 0; u < 4; u++) rk[q0 + u] = __builtin_nondeterministic_value(rk[q0 + u]);
                         continue;
                     }
-                    uint32_t bit[4], rbi[4];
+                    uint32_t bit[4], rbw[4], rbb[4]; // a slot's word of the bitmap and its bit there
 #pragma unroll
                     for (int u = 0; u < 4; u++) {
                         const uint32_t e = (uint32_t) (q0 + u) * UQ_THREADS + (uint32_t) tid;
-                        rbi[u] = 0xFFFFFFFFu;
                         rk[q0 + u] = 0;
                         if (e < n_p) rk[q0 + u] = ld_scr(&seg[e]);
                     }
+                    // (as in k_multiset_uq: a slot without a key ORs nothing into its thread's own word, the four ds_or_rtn leave back
+                    //  to back outside every per-lane branch and are looked at together)
 #pragma unroll
                     for (int u = 0; u < 4; u++) {
                         const uint32_t e = (uint32_t) (q0 + u) * UQ_THREADS + (uint32_t) tid;
-                        if (e < n_p) rbi[u] = bm_index(rk[q0 + u]);
+                        const uint32_t bi = bm_index(rk[q0 + u]);
+                        rbw[u] = e < n_p ? bi >> 5 : (uint32_t) tid;
+                        rbb[u] = e < n_p ? 1u << (bi & 31u) : 0u;
                     }
 #pragma unroll
-                    for (int u = 0; u < 4; u++) {
-                        bit[u] = 0;
-                        if (rbi[u] != 0xFFFFFFFFu) {
-                            const uint32_t b = 1u << (rbi[u] & 31u);
-                            bit[u] = atomicOr(&bmA[rbi[u] >> 5], b) & b;
-                        }
-                    }
+                    for (int u = 0; u < 4; u++) bit[u] = atomicOr(&bmA[rbw[u]], rbb[u]);
+#pragma unroll
+                    for (int u = 0; u < 4; u++) bit[u] &= rbb[u];
 #pragma unroll
                     for (int u = 0; u < 4; u++)
-                        if (bit[u]) atomicOr(&bmB[rbi[u] >> 5], bit[u]);
+                        if (bit[u]) atomicOr(&bmB[rbw[u]], bit[u]);
                 }
                 lds_barrier();
                 // ---- sort out: B bit clear = occurs once = list entry (key, 1) from the register; else collect ----
@@ -205,12 +216,14 @@ __global__ void __launch_bounds__(1024, 4) k_multiset_long(SketchArgs a) {
                     if (!group_used(q0)) continue; // (its rk[] hold no key)
                     bool uq[4], co[4];
                     uint64_t um[4], cm[4];
-                    uint32_t ut = 0, ct = 0;
+                    uint32_t ut = 0, ct = 0, bw[4];
+                    // (the four B words are read by every lane -- a slot without a key holds key 0 -- and looked at together)
+#pragma unroll
+                    for (int u = 0; u < 4; u++) bw[u] = bmB[bm_index(rk[q0 + u]) >> 5];
 #pragma unroll
                     for (int u = 0; u < 4; u++) {
                         const bool have = (uint32_t) (q0 + u) * UQ_THREADS + (uint32_t) tid < n_p;
-                        const uint32_t bi = bm_index(rk[q0 + u]);
-                        co[u] = have && (bmB[bi >> 5] & (1u << (bi & 31u))) != 0u;
+                        co[u] = have && (bw[u] & (1u << (bm_index(rk[q0 + u]) & 31u))) != 0u;
                         uq[u] = have && !co[u];
                     }
 #pragma unroll

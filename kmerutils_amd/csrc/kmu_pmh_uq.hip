@@ -29,6 +29,7 @@ __global__ void __launch_bounds__(UQ_THREADS, MINW) k_multiset_uq(SketchArgs a) 
     constexpr uint32_t UQ_KEYS = SH::KEYS, UQ_BM_WORDS = SH::BM_WORDS, UQ_BUCKETS = SH::BUCKETS, UQ_TILE = SH::TILE;
     static_assert((UQ_BM_WORDS / 4) % (uint32_t) UQ_THREADS == 0, "whole 16-byte stores per thread wipe a bitmap");
     static_assert(UQ_COLL % UQ_THREADS == 0 && UQ_COLL / UQ_THREADS <= 4, "collected keys per thread");
+    static_assert((uint32_t) UQ_THREADS <= UQ_BM_WORDS, "every thread has a word of bitmap A of its own");
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     uint32_t *bmA = reinterpret_cast<uint32_t *>(smem);
     uint32_t *bmB = bmA + UQ_BM_WORDS;
@@ -143,7 +144,10 @@ __global__ void __launch_bounds__(UQ_THREADS, MINW) k_multiset_uq(SketchArgs a) 
         const uint32_t rs_nn = has_nn ? seq_of(r_nn) : 0u;
         const uint64_t nn_o0 = has_nn ? a.offsets[rs_nn] : 0ull, nn_o1 = has_nn ? a.offsets[rs_nn + 1] : 0ull;
         // the next read's chunks: requested now, they land in LDS under the key phase and become code words behind it
-        // (round 2 requested them behind the key phase and converted them on the spot: 12 % of a read's turn in that wait)
+        // (round 2 requested them behind the key phase and converted them on the spot: 12 % of a read's turn in that wait).
+        // Requested by an instruction the compiler does not count (chunk16_to_lds_uncounted): behind the builtin it put `vmcnt(0)` in
+        // front of every ds_* of the key phase, and each wave sat out the HBM round trip at the top of the phase that was to hide it.
+        // The one wait for them is vm_wait_lds_loads() behind the key phase; a thread then reads the 16 bytes its own lane asked for.
         uint32_t nwn = 0, wfn = 0;
         if (nv_mine) {
             nwn = n_words(nv);
@@ -152,7 +156,8 @@ __global__ void __launch_bounds__(UQ_THREADS, MINW) k_multiset_uq(SketchArgs a) 
             for (int u = 0; u < 3; u++) {
                 const uint32_t tw = (uint32_t) tid + (uint32_t) u * UQ_THREADS;
                 if (tw < nwn && chunk_is_plain(nv, (uint64_t) wfn + tw))
-                    chunk16_to_lds(nv.base + (nv.begin & ~15ull) + 16 * ((uint64_t) wfn + tw), rawp + (size_t) (tw >> 6) * 1024);
+                    chunk16_to_lds_uncounted(nv.base + (nv.begin & ~15ull) + 16 * ((uint64_t) wfn + tw),
+                                             lds_addr(smem) + RAW_OFF + (uint32_t) (wave + u * (UQ_THREADS / 64)) * 1024u);
             }
         }
         uint64_t rk[UQ_KREG];
@@ -172,7 +177,8 @@ __global__ void __launch_bounds__(UQ_THREADS, MINW) k_multiset_uq(SketchArgs a) 
         auto group_used = [&](int q0) -> bool { return 4u * (uint32_t) UQ_THREADS * (uint32_t) (q0 >> 2) < span; };
         bool over = false; // uniform: too many keys in collision groups
         if (mine) {
-            // ---- keys: extract, closure, bitmaps; four positions' LDS round trips in flight at a time ----
+            // ---- keys: extract, closure, bitmaps; the four ds_or_rtn of a slot group in flight together (in the compiled kernel: back to
+            // back, one counted wait behind them; no vmcnt wait in the phase -- scripts/asm_mix.py --lds-waits) ----
             // (FAST: the closure of the headline -- canonical Kmer64bit through int64_hash, datasketcher.rs:225 -- without the
             //  per-key walk through apply_fhash's cases: the mode is the same for every key of the launch, and a chain of scalar
             //  compares and taken branches per key costs a workgroup of four waves per SIMD more than the arithmetic it selects)
@@ -189,7 +195,7 @@ __global__ void __launch_bounds__(UQ_THREADS, MINW) k_multiset_uq(SketchArgs a) 
                         for (int u = 0; u < 4; u++) rk[q0 + u] = __builtin_nondeterministic_value(rk[q0 + u]);
                         continue;
                     }
-                    uint32_t bit[4], rbi[UQ_KREG];
+                    uint32_t bit[4], rbw[4], rbb[4]; // a slot's word of the bitmap and its bit there
                     const uint32_t wi = ((uint32_t) tid >> 2) + (uint32_t) (UQ_THREADS / 4) * (uint32_t) (q0 >> 2); // the quarter's word
                     const StepWin sw = step_win(words[wi], words[wi + 1], words[wi + 2], k);
                     // (round 4, measured and not kept: a branch-free form for the waves whose quarters are whole -- 10.6 against 10.1 ms
@@ -197,28 +203,30 @@ __global__ void __launch_bounds__(UQ_THREADS, MINW) k_multiset_uq(SketchArgs a) 
 #pragma unroll
                     for (int u = 0; u < 4; u++) {
                         const int q = q0 + u;
-                        rbi[q] = 0xFFFFFFFFu;
+                        // a slot without a key ORs nothing into a word of its thread's own (one word for all such lanes of a wave
+                        // would serialise them): the four ds_or_rtn below then stand outside every per-lane branch
+                        rbw[u] = (uint32_t) tid;
+                        rbb[u] = 0;
                         rk[q] = 0;
                         if (place_of(q) - l0 < nk) {
                             uint64_t val, rc;
                             step_val_rc(sw, 4u * ((uint32_t) tid & 3u) + (uint32_t) u, val, rc);
                             const uint64_t key = FAST ? int64_hash(rc < val ? rc : val) : apply_fhash(cfg, val, rc);
                             rk[q] = key;
-                            rbi[q] = bm_index(key);
+                            const uint32_t bi = bm_index(key);
+                            rbw[u] = bi >> 5;
+                            rbb[u] = 1u << (bi & 31u);
                         }
                     }
+                    // the four round trips leave back to back; an answer is looked at when all four are out (inside the branch that
+                    // issued it, the answer was waited for there: four dependent round trips per group)
 #pragma unroll
-                    for (int u = 0; u < 4; u++) {
-                        const int q = q0 + u;
-                        bit[u] = 0;
-                        if (rbi[q] != 0xFFFFFFFFu) {
-                            const uint32_t b = 1u << (rbi[q] & 31u);
-                            bit[u] = atomicOr(&bmA[rbi[q] >> 5], b) & b;
-                        }
-                    }
+                    for (int u = 0; u < 4; u++) bit[u] = atomicOr(&bmA[rbw[u]], rbb[u]);
+#pragma unroll
+                    for (int u = 0; u < 4; u++) bit[u] &= rbb[u];
 #pragma unroll
                     for (int u = 0; u < 4; u++)
-                        if (bit[u]) atomicOr(&bmB[rbi[q0 + u] >> 5], bit[u]);
+                        if (bit[u]) atomicOr(&bmB[rbw[u]], bit[u]);
                 }
             };
             if (cfg.fhash == KMU_FHASH_CANON_INVHASH && cfg.kmer_type == KMU_KMER64BIT) key_phase(std::true_type{});
@@ -252,13 +260,16 @@ __global__ void __launch_bounds__(UQ_THREADS, MINW) k_multiset_uq(SketchArgs a) 
                 if (!group_used(q0)) continue; // (its rk[] hold no key: the key phase skipped it by the same test)
                 bool uq[4], co[4];
                 uint64_t um[4], cm[4];
-                uint32_t ut = 0, ct = 0, rbi[UQ_KREG];
+                uint32_t ut = 0, ct = 0, bw[4];
+                // the four B words are read by every lane (a slot without a key holds key 0: some word of the bitmap) and looked at
+                // together: one wait per group
+#pragma unroll
+                for (int u = 0; u < 4; u++) bw[u] = bmB[bm_index(rk[q0 + u]) >> 5];
 #pragma unroll
                 for (int u = 0; u < 4; u++) {
                     const int q = q0 + u;
                     const bool have = place_of(q) - (lead - 16u * wfirst) < nk;
-                    rbi[q] = bm_index(rk[q]);
-                    co[u] = have && (bmB[rbi[q] >> 5] & (1u << (rbi[q] & 31u))) != 0u;
+                    co[u] = have && (bw[u] & (1u << (bm_index(rk[q]) & 31u))) != 0u;
                     uq[u] = have && !co[u];
                 }
 #pragma unroll
