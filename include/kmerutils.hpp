@@ -44,6 +44,7 @@
  *                                                            hits)                          (beyond the reference)
  *   counting      KmerCountT (trait), KmerCounter, KmerCounterPool, count_kmer_threaded_one_to_many
  *                                                            src/base/kmercount.rs:48-123, 424-565, 881-974
+ *                 KmerPrefilter, count_repeated_kmers (a Bloom prefilter keeps the k-mers seen once off the table)
  *   io            FASTQ reader rule, signature / count dumps src/io.rs:12-72, src/bin/datasketcher.rs:358-388,
  *                                                            seqsketchjaccard.rs:385-414, kmercount.rs:467-531
  *
@@ -2786,6 +2787,8 @@ template <class Kmer> class KmerCountT {
     virtual uint64_t get_nb_unique() = 0;
 };
 
+template <class Kmer> class KmerPrefilter;   // the count prefilter, below
+
 /// KmerCounter::new(fpr, capacity, nb_bits) (kmercount.rs:70-123).  The device table is exact: the reference's contract
 /// without the false positives of its cuckoo + counting-Bloom pair, so `fpr` is accepted and unused.  Single insertions
 /// are queued on the host and reach the device in batches (at the latest when something is read back).
@@ -2812,6 +2815,17 @@ template <class Kmer> class KmerCounter : public KmerCountT<Kmer> {
         ensure(kmer_size);
         flush();
         ctx_.check(kmu_count_add_reads(counter_, b.bytes_ptr(), b.offsets_ptr(), b.packed_ptr(), b.n(), b.input_kind, b.mem()));
+    }
+    /// the occurrences of the reads whose k-mer the prefilter puts in class 2 (may occur twice or more); returns their number.
+    /// After a filter built from the same reads every count held is exact, every k-mer seen at least twice is held, and
+    /// get_nb_unique counts the singletons that slipped through the filter.
+    uint64_t insert_reads_filtered(KmerPrefilter<Kmer> &filter, const detail::Batch &reads, uint8_t kmer_size) {
+        const detail::Batch b = detail::unpacked(reads);   // kmu_count_add_reads_filtered takes unpacked bases
+        ensure(kmer_size);
+        flush();
+        uint64_t passed = 0;
+        ctx_.check(kmu_count_add_reads_filtered(counter_, filter.raw(), b.bytes_ptr(), b.offsets_ptr(), b.n(), b.mem(), &passed));
+        return passed;
     }
     uint32_t get_count(Kmer kmer) override {
         ensure(kmer.get_nb_base());
@@ -3096,6 +3110,120 @@ template <class Kmer>
 std::unique_ptr<KmerCounterPool<Kmer>> count_kmer_thread_independant(const std::vector<Sequence> &seqvec, size_t nb_threads,
                                                                       uint8_t kmer_size, Context &ctx = Context::global()) {
     return count_kmer_threaded_one_to_many<Kmer>(seqvec, nb_threads, 8, kmer_size, ctx);
+}
+
+/// KmerPrefilter: the count prefilter (kmu_kfilter, include/kmu.h) -- a two-plane Bloom filter that tells the canonical k-mers
+/// inserted once (class 1) from those that may have been inserted twice or more (class 2; 0: never inserted).  It stands where the
+/// reference keeps its cuckoo filter of k-mers seen once (kmercount.rs:70-123): a first pass over the reads builds it, a second
+/// pass (KmerCounter::insert_reads_filtered) counts only what may occur twice.  No k-mer inserted twice is ever missed.
+template <class Kmer> class KmerPrefilter {
+  public:
+    KmerPrefilter(uint8_t kmer_size, uint64_t nb_cells, uint32_t nb_hashes = 4, Context &ctx = Context::global()) : ctx_(ctx) {
+        kmu_kfilter_params p{};
+        p.kmer_type = Kmer::kmu_type;
+        p.kmer_size = kmer_size;
+        p.n_hashes = nb_hashes;
+        p.n_cells = nb_cells;
+        ctx_.check(kmu_kfilter_create(ctx_.raw(), &p, &filter_));
+    }
+    ~KmerPrefilter() {
+        if (filter_) kmu_kfilter_destroy(filter_);
+    }
+    KmerPrefilter(const KmerPrefilter &) = delete;
+    KmerPrefilter &operator=(const KmerPrefilter &) = delete;
+
+    /// cells for `expected_distinct` k-mers at `bits_per_kmer` bits each (16: 0.5 % of the singletons pass with 4 hashes)
+    static uint64_t cells_for(uint64_t expected_distinct, uint32_t bits_per_kmer = 16) {
+        const uint64_t n = kmu_kfilter_cells_for(expected_distinct, bits_per_kmer);
+        if (n == 0) throw KmuError(KMU_E_BAD_ARG, "KmerPrefilter: more cells than a filter can have (2^32 - 1)");
+        return n;
+    }
+    /// one occurrence of every canonical k-mer of every read
+    void insert_reads(const detail::Batch &reads) {
+        const detail::Batch b = detail::unpacked(reads);   // the filter takes unpacked bases
+        ctx_.check(kmu_kfilter_add_reads(filter_, b.bytes_ptr(), b.offsets_ptr(), b.n(), b.mem()));
+    }
+    void insert_reads(const std::vector<const Sequence *> &seqvec) { insert_reads(detail::gather(seqvec)); }
+    /// one occurrence of a canonical k-mer (the caller passes kmer.reverse_complement().min(kmer))
+    void insert_kmer(Kmer kmer) { insert_kmer(std::vector<Kmer>{kmer}); }
+    void insert_kmer(const std::vector<Kmer> &kmers) {
+        std::vector<uint64_t> keys;
+        for (const Kmer &k : kmers) keys.push_back(uint64_t(k.get_compressed_value()));
+        ctx_.check(kmu_kfilter_add_kmers(filter_, keys.data(), keys.size(), KMU_MEM_HOST));
+    }
+    /// 0: never inserted; 1: inserted exactly once; 2: may have been inserted twice or more
+    uint8_t seen_class(Kmer kmer) { return seen_class(std::vector<Kmer>{kmer})[0]; }
+    std::vector<uint8_t> seen_class(const std::vector<Kmer> &kmers) {
+        std::vector<uint64_t> keys;
+        for (const Kmer &k : kmers) keys.push_back(uint64_t(k.get_compressed_value()));
+        std::vector<uint8_t> cls(keys.size());
+        ctx_.check(kmu_kfilter_query(filter_, keys.data(), keys.size(), KMU_MEM_HOST, cls.data()));
+        return cls;
+    }
+    /// cells, bytes, occurrences inserted, set bits of the two planes, and the estimate of the distinct k-mers inserted
+    kmu_kfilter_info_t info() {
+        kmu_kfilter_info_t t{};
+        ctx_.check(kmu_kfilter_info(filter_, &t));
+        return t;
+    }
+    /// this filter becomes the filter of both inputs (same parameters): ranks that each filtered a shard
+    void merge(const KmerPrefilter &other) { ctx_.check(kmu_kfilter_merge(filter_, other.filter_)); }
+    /// the planes, A0 B0 A1 B1 ...
+    std::vector<uint64_t> words() {
+        std::vector<uint64_t> w(2 * info().n_cells);
+        ctx_.check(kmu_kfilter_export(filter_, w.data(), KMU_MEM_HOST));
+        return w;
+    }
+    /// how many k-mer occurrences of the reads are class 2: what insert_reads_filtered is going to add
+    uint64_t nb_passing(const detail::Batch &reads) {
+        const detail::Batch b = detail::unpacked(reads);
+        uint64_t n = 0;
+        ctx_.check(kmu_kfilter_select_reads(filter_, b.bytes_ptr(), b.offsets_ptr(), b.n(), b.mem(), nullptr, 0, &n));
+        return n;
+    }
+    kmu_kfilter *raw() const { return filter_; }
+
+  private:
+    Context &ctx_;
+    kmu_kfilter *filter_ = nullptr;
+};
+
+/// what count_repeated_kmers returns: the counter of the k-mers that passed, the filter, and the occurrences that passed
+template <class Kmer> struct RepeatedKmers {
+    std::unique_ptr<KmerCounterPool<Kmer>> counter;
+    std::unique_ptr<KmerPrefilter<Kmer>> filter;
+    uint64_t nb_passed = 0;
+};
+
+/// count_repeated_kmers(reads, kmer_size, count_size, bits_per_kmer, nb_hashes, capacity): the counts of the k-mers seen at least
+/// twice without a table slot for (nearly) every singleton.  Two passes over the reads: the filter, sized from the number of k-mer
+/// occurrences, then the table, which gets the occurrences of class-2 k-mers only.  Every count held is exact and every k-mer seen
+/// at least twice is held, so get_above2_count and dump_kmer_counter answer as after count_kmer_threaded_one_to_many; a k-mer that
+/// is absent occurred 0 or 1 times, and get_nb_unique counts the singletons that slipped through the filter.  capacity 0: the
+/// number P of passing occurrences, which can never overflow (R repeated and F slipped k-mers need P >= 2 R + F >= R + F); a
+/// caller may pass something tighter from info().est_distinct - (info().n_added - P).
+template <class Kmer>
+RepeatedKmers<Kmer> count_repeated_kmers(const detail::Batch &reads, uint8_t kmer_size, size_t count_size = 8, uint32_t bits_per_kmer = 16,
+                                         uint32_t nb_hashes = 4, uint64_t capacity = 0, Context &ctx = Context::global()) {
+    const detail::Batch b = detail::unpacked(reads);
+    uint64_t occurrences = 0;
+    for (uint32_t i = 0; i < b.n(); i++) {
+        const uint64_t len = b.offsets[i + 1] - b.offsets[i];
+        if (len >= kmer_size) occurrences += len - kmer_size + 1;
+    }
+    RepeatedKmers<Kmer> r;
+    r.filter = std::make_unique<KmerPrefilter<Kmer>>(kmer_size, KmerPrefilter<Kmer>::cells_for(occurrences, bits_per_kmer), nb_hashes, ctx);
+    r.filter->insert_reads(b);
+    const uint64_t passing = r.filter->nb_passing(b);
+    r.counter = std::make_unique<KmerCounterPool<Kmer>>(std::max<uint64_t>(capacity ? capacity : passing, 1024), uint8_t(count_size), ctx);
+    r.nb_passed = r.counter->counter().insert_reads_filtered(*r.filter, b, kmer_size);
+    return r;
+}
+template <class Kmer>
+RepeatedKmers<Kmer> count_repeated_kmers(const std::vector<Sequence> &seqvec, uint8_t kmer_size, size_t count_size = 8,
+                                         uint32_t bits_per_kmer = 16, uint32_t nb_hashes = 4, uint64_t capacity = 0,
+                                         Context &ctx = Context::global()) {
+    return count_repeated_kmers<Kmer>(detail::gather(detail::pointers(seqvec)), kmer_size, count_size, bits_per_kmer, nb_hashes, capacity, ctx);
 }
 
 /// KmerCountReload (kmercount.rs:1132-1500): a dump of the counter read back -- for up-to-32-bit k-mers, as upstream

@@ -467,6 +467,77 @@ typedef struct kmu_read_abundance { /* 32 bytes */
  * sequence of 2^32 bases or more.  With stats_out alone the counts pass through a bounded workspace. */
 int kmu_count_read_profile(kmu_counter *c, const uint8_t *bases, const uint64_t *offsets, uint32_t n_seq, int mem,
                            uint32_t solid_min, uint16_t *counts_out, kmu_read_abundance *stats_out);
+
+/* ---- the count prefilter: a two-plane Bloom filter that keeps singletons off the table ---------------------------------------
+ * The reference keeps the k-mers seen once in a cuckoo filter and counts the others in a counting Bloom filter
+ * (src/base/kmercount.rs:70-123, :241-267); get_above2_count, dump_kmer_counter and the COUNTER_MULTIPLE file only ever ask for
+ * counts >= 2.  The exact table costs 11.4 bytes per DISTINCT k-mer, most of them sequencing errors seen once.  A kmu_kfilter is
+ * built in a first pass over the reads; a second pass (kmu_count_add_reads_filtered) counts only the k-mers the filter says may
+ * occur twice.  Contract: every count in the table is exact; every k-mer that occurs at least twice is in the table; a k-mer that
+ * is absent occurred 0 or 1 times.
+ *
+ * The structure (normative).  n_cells cells of 16 bytes {uint64 A, uint64 B}, n_cells in [1, 2^32 - 1], any value.  Modulo 2^64:
+ *   sm(z):  z += 0x9E3779B97F4A7C15; z = (z ^ z>>30) * 0xBF58476D1CE4E5B9; z = (z ^ z>>27) * 0x94D049BB133111EB; return z ^ z>>31
+ *   key v = the canonical compressed value as uint64;  h = sm(v);  g = sm(h)
+ *   cell(v) = ((h >> 32) * n_cells) >> 32
+ *   mask(v) = OR over i < n_hashes of 1 << ((g >> 6 i) & 63), 1 <= n_hashes <= 8 (coinciding positions collapse)
+ * Adding one occurrence of v: old = atomic_or(&A[cell], mask); rep = old & mask; if (rep) atomic_or(&B[cell], rep).  The final
+ * state is a function of the MULTISET of occurrences alone -- whatever the order, the launch shape or the number of add calls:
+ * A[c] = the OR of the masks that landed in c, bit b of B[c] = "at least two occurrences landed on bit b of c".
+ * The class of v: 0 -- some mask bit is missing in A: never added; 1 -- the mask is in A, not all of it in B: added exactly once;
+ * 2 -- the mask is in B: may have been added twice or more.  A k-mer added at least twice is always class 2; class 2 for a k-mer
+ * added once (or never) is the only error, at the Bloom rate of plane A (0.5 % of the singletons at 16 bits per distinct k-mer and
+ * 4 hashes). */
+typedef struct kmu_kfilter kmu_kfilter;
+typedef struct kmu_kfilter_params {
+    int32_t kmer_type;  /* a DNA k-mer type (amino acids: KMU_E_BAD_ARG) */
+    int32_t kmer_size;
+    uint32_t n_hashes;  /* 1 .. 8 */
+    uint32_t flags;     /* 0 */
+    uint64_t n_cells;   /* 1 .. 2^32 - 1: 16 bytes each (kmu_kfilter_cells_for) */
+} kmu_kfilter_params;
+typedef struct kmu_kfilter_info_t { /* 56 bytes */
+    uint64_t n_cells, bytes;     /* bytes = 16 n_cells */
+    uint32_t n_hashes, kmer_size;
+    uint64_t n_added;            /* the occurrences added since the last reset (those of merged filters included) */
+    uint64_t bits_a, bits_b;     /* set bits of the two planes */
+    double est_distinct;         /* -(m / n_hashes) ln(1 - bits_a / m), m = 64 n_cells; INFINITY when plane A is full */
+} kmu_kfilter_info_t;
+/* plain host C, no device: max(1, ceil(expected_distinct * bits_per_kmer / 64)) cells; 0 when that exceeds 2^32 - 1 */
+uint64_t kmu_kfilter_cells_for(uint64_t expected_distinct, uint32_t bits_per_kmer);
+/* KMU_E_BAD_ARG: null pointers, n_hashes outside [1, 8], n_cells outside [1, 2^32 - 1], flags != 0, an amino-acid k-mer type; a
+ * k-mer type and size that kmu_count_create refuses is refused the same way.  The filter starts empty. */
+int kmu_kfilter_create(kmu_ctx *ctx, const kmu_kfilter_params *p, kmu_kfilter **out);
+void kmu_kfilter_destroy(kmu_kfilter *f);
+int kmu_kfilter_reset(kmu_kfilter *f); /* both planes and n_added back to 0 */
+/* one occurrence of every canonical k-mer of every sequence.  Unpacked (ASCII) input only; non-ACGT bytes (KMU_E_NON_ACGT, the
+ * planes are then unspecified), reads shorter than k, offsets[0] != 0 and n_seq == 0 exactly as in kmu_count_add_reads. */
+int kmu_kfilter_add_reads(kmu_kfilter *f, const uint8_t *bases, const uint64_t *offsets, uint32_t n_seq, int mem);
+/* one occurrence of each of n canonical compressed values */
+int kmu_kfilter_add_kmers(kmu_kfilter *f, const uint64_t *canon_kmers, uint64_t n, int mem);
+/* class_out[i] = 0 / 1 / 2, the class of canon_kmers[i] */
+int kmu_kfilter_query(kmu_kfilter *f, const uint64_t *canon_kmers, uint64_t n, int mem, uint8_t *class_out);
+/* the popcounts of the planes (one kernel, one synchronisation) and the cardinality estimate, computed in double on the host */
+int kmu_kfilter_info(kmu_kfilter *f, kmu_kfilter_info_t *out);
+/* words_out[2 n_cells]: A0 B0 A1 B1 ... */
+int kmu_kfilter_export(kmu_kfilter *f, uint64_t *words_out, int mem);
+/* dst becomes the filter of the concatenated input: A = A1 | A2, B = B1 | B2 | (A1 & A2), n_added the sum -- the hook for ranks
+ * that each filtered a shard.  The two filters must share context and parameters (KMU_E_BAD_ARG otherwise, dst unchanged). */
+int kmu_kfilter_merge(kmu_kfilter *dst, const kmu_kfilter *src);
+/* The canonical k-mer of every class-2 occurrence of the given reads, in (sequence, position) order.  Call with kmers_out == NULL
+ * for the number of k-mers in *n_out (host memory in both modes); cap < that number: KMU_E_BAD_ARG with *n_out set and nothing
+ * written -- the rules of kmu_count_once_positions.  One synchronisation, for the total. */
+int kmu_kfilter_select_reads(kmu_kfilter *f, const uint8_t *bases, const uint64_t *offsets, uint32_t n_seq, int mem,
+                             uint64_t *kmers_out, uint64_t cap, uint64_t *n_out);
+/* Adds exactly the occurrences kmu_kfilter_select_reads lists to the counter; *n_passed_out (may be NULL): their number, by which
+ * kmu_count_nb_occurrences has grown.  After a filter built from the same reads: every k-mer seen at least twice is held with its
+ * exact count, and kmu_count_nb_unique counts the SINGLETONS THAT SLIPPED THROUGH the filter (its false positives), not the
+ * singletons of the reads.  The survivors pass through a workspace of KMU_KFILTER_CHUNK_KMERS k-mers (default 2^26) into the
+ * counter's own add of k-mer arrays, range by range.  KMU_E_BAD_ARG: a counter and a filter of different contexts, k-mer types or
+ * sizes.  KMU_E_UNSUPPORTED: a distributed counter.  KMU_E_NON_ACGT is found before anything is added; a later failure
+ * (KMU_E_TABLE_FULL) leaves the counter as a failed kmu_count_add_kmers does, *n_passed_out telling what went in before. */
+int kmu_count_add_reads_filtered(kmu_counter *c, kmu_kfilter *f, const uint8_t *bases, const uint64_t *offsets, uint32_t n_seq,
+                                 int mem, uint64_t *n_passed_out);
 /* multi-GPU merge (one process per GPU): export the entries whose owner (int64_hash(kmer) % n_parts,
  * kmercount.rs:412-420) is `part` as device/host arrays, and merge entries received from peers.
  * The exchange itself is done by the host layer (RCCL all_to_all over xGMI). */

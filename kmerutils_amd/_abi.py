@@ -134,6 +134,27 @@ READ_ABUNDANCE_DTYPE = [("n_kmers", "<u4"), ("n_absent", "<u4"), ("n_once", "<u4
                         ("median", "<u2"), ("max", "<u2"), ("reserved", "<u2"), ("sum", "<u8")]
 
 
+KFILTER_MAX_HASHES = 8            # kmu_kfilter: the most bits a key sets in its cell
+KFILTER_MAX_CELLS = (1 << 32) - 1  # ... and the most 16-byte cells of a filter
+
+
+class KFilterParams(C.Structure):
+    """kmu_kfilter_params"""
+    _fields_ = [("kmer_type", C.c_int32), ("kmer_size", C.c_int32), ("n_hashes", C.c_uint32), ("flags", C.c_uint32),
+                ("n_cells", C.c_uint64)]
+
+
+class KFilterInfo(C.Structure):
+    """kmu_kfilter_info_t"""
+    _fields_ = [("n_cells", C.c_uint64), ("bytes", C.c_uint64), ("n_hashes", C.c_uint32), ("kmer_size", C.c_uint32),
+                ("n_added", C.c_uint64), ("bits_a", C.c_uint64), ("bits_b", C.c_uint64), ("est_distinct", C.c_double)]
+
+
+# the same record as a numpy dtype (56 bytes, the field offsets of the structure)
+KFILTER_INFO_DTYPE = [("n_cells", "<u8"), ("bytes", "<u8"), ("n_hashes", "<u4"), ("kmer_size", "<u4"), ("n_added", "<u8"),
+                      ("bits_a", "<u8"), ("bits_b", "<u8"), ("est_distinct", "<f8")]
+
+
 class Overlap(C.Structure):
     """kmu_overlap: one read pair of kmu_anchor_overlaps"""
     _fields_ = [("read_a", C.c_uint32), ("read_b", C.c_uint32), ("strand", C.c_uint32), ("diag", C.c_int32),

@@ -4,6 +4,8 @@
   KmerCounter           kmercount.rs:70-123
   KmerCounterPool       kmercount.rs:424-565         one counter per thread -> here one counter per GPU
   count_kmer_threaded_one_to_many   kmercount.rs:881-974
+  KmerPrefilter, count_repeated_kmers   (the role of the cuckoo filter of k-mers seen once, kmercount.rs:70-123: a Bloom
+                        prefilter built in a first pass keeps them off the table)
 The reference's cuckoo + counting-Bloom pair is approximate and randomised per process; the device table is exact,
 i.e. the reference's own contract without its ~3 % false positives (counts saturate at 2^nb_bits - 1).
 """
@@ -32,6 +34,12 @@ class KmerCounter:
         """every canonical k-mer of every read: kmer.reverse_complement().min(kmer), kmercount.rs:313,938"""
         bases, offsets = _as_arrays(vseq)
         self._c.add_reads(bases, offsets)
+
+    def insert_reads_filtered(self, prefilter, vseq):
+        """the occurrences of the reads whose k-mer the KmerPrefilter puts in class 2 (may occur twice or more); returns their
+        number.  After a filter built from the same reads, get_nb_unique counts the singletons that slipped through it."""
+        bases, offsets = _as_arrays(vseq)
+        return self._c.add_reads_filtered(prefilter.raw, bases, offsets)
 
     def get_count(self, compressed_values):
         v = np.atleast_1d(np.asarray(compressed_values, dtype=np.uint64)).copy()
@@ -84,6 +92,85 @@ def count_kmer_threaded_one_to_many(seqvec, nb_threads, count_size, kmer_size, c
     kc = KmerCounter(kmer_size, capacity, count_size, ctx=ctx)
     kc.insert_reads((bases, offsets))
     return kc
+
+
+class KmerPrefilter:
+    """The count prefilter (kmu_kfilter): a two-plane Bloom filter that tells the canonical k-mers inserted once from those that
+    may have been inserted twice or more.  It stands where the reference keeps its cuckoo filter of k-mers seen once
+    (kmercount.rs:70-123): built in a first pass over the reads, it lets a second pass count only what may occur twice.  No k-mer
+    inserted twice is ever missed; a k-mer inserted once passes for "more" at the Bloom rate of the first plane."""
+
+    def __init__(self, kmer_size, nb_cells, nb_hashes=4, kmer_type=None, ctx=None):
+        self.ctx = ctx or default_context()
+        self.kmer_type = kmer_type if kmer_type is not None else A.kmer_type_for_k(kmer_size)
+        self.kmer_size = kmer_size
+        self._f = lib.KFilter(self.ctx, self.kmer_type, kmer_size, nb_cells, nb_hashes)
+
+    @staticmethod
+    def cells_for(expected_distinct, bits_per_kmer=16):
+        """cells for that many distinct k-mers at bits_per_kmer bits each (16 bits, 4 hashes: 0.5 % of the singletons pass)"""
+        n = lib.kfilter_cells_for(expected_distinct, bits_per_kmer)
+        if n == 0:
+            raise ValueError("more cells than a filter can have (2^32 - 1)")
+        return n
+
+    def insert_reads(self, vseq):
+        """one occurrence of every canonical k-mer of every read"""
+        bases, offsets = _as_arrays(vseq)
+        self._f.add_reads(bases, offsets)
+
+    def insert_kmer(self, compressed_values):
+        """one occurrence of one canonical `get_compressed_value()` value, or of every value of an array"""
+        self._f.add_kmers(np.atleast_1d(np.asarray(compressed_values, dtype=np.uint64)).copy())
+
+    def seen_class(self, compressed_values):
+        """0: never inserted; 1: inserted exactly once; 2: may have been inserted twice or more (uint8 per value)"""
+        return self._f.query(np.atleast_1d(np.asarray(compressed_values, dtype=np.uint64)).copy())
+
+    def info(self):
+        """n_cells, bytes, n_hashes, kmer_size, n_added, bits_a, bits_b and est_distinct, the estimate of the distinct k-mers"""
+        return self._f.info()
+
+    def merge(self, other):
+        """this filter becomes the filter of both inputs (same parameters): ranks that each filtered a shard"""
+        self._f.merge(other._f)
+
+    def words(self):
+        """the planes as uint64 words A0 B0 A1 B1 ..."""
+        return self._f.export()
+
+    def nb_passing(self, vseq):
+        """how many k-mer occurrences of the reads are class 2: what KmerCounter.insert_reads_filtered is going to add"""
+        bases, offsets = _as_arrays(vseq)
+        return self._f.n_passing(bases, offsets)
+
+    @property
+    def raw(self):
+        return self._f
+
+
+def count_repeated_kmers(seqvec, kmer_size, count_size, bits_per_kmer=16, nb_hashes=4, capacity=None, ctx=None):
+    """The counts of the k-mers seen at least twice, without a table slot for (nearly) every singleton: returns
+    (KmerCounter, KmerPrefilter).  Two passes over the reads: the filter, sized from the number of k-mer occurrences at
+    bits_per_kmer bits each, then the table, which gets the occurrences of class-2 k-mers only.  Every count held is exact and
+    every k-mer seen at least twice is held, so get_above2_count and above2_entries answer as after
+    count_kmer_threaded_one_to_many; a k-mer that is absent occurred 0 or 1 times, and get_nb_unique counts the singletons that
+    slipped through the filter.
+
+    capacity: the distinct k-mers the table is made for.  Default: the number P of passing occurrences, which can never overflow
+    (R repeated and F slipped k-mers make P >= 2 R + F >= R + F).  A caller may pass something tighter from
+    info().est_distinct - (info()["n_added"] - P): the distinct k-mers of the reads less the occurrences that did not pass, each of
+    them a k-mer of its own."""
+    bases, offsets = _as_arrays(seqvec)
+    ctx = ctx or default_context()
+    off_h = offsets.cpu().numpy() if lib._is_torch(offsets) else np.asarray(offsets)
+    occurrences = int(np.maximum(np.diff(off_h.astype(np.int64)) - kmer_size + 1, 0).sum())
+    kf = KmerPrefilter(kmer_size, KmerPrefilter.cells_for(occurrences, bits_per_kmer), nb_hashes, ctx=ctx)
+    kf.insert_reads((bases, offsets))
+    passing = kf.nb_passing((bases, offsets))
+    kc = KmerCounter(kmer_size, max(1024, passing if capacity is None else int(capacity)), count_size, ctx=ctx)
+    kc.insert_reads_filtered(kf, (bases, offsets))
+    return kc, kf
 
 
 class KmerFilter1:

@@ -40,6 +40,9 @@ SYMBOLS = [
     "kmu_chain_cigar", "kmu_chain_pileup", "kmu_pile_call", "kmu_pile_ins_plan", "kmu_chain_pile_ins", "kmu_pile_consensus",
     "kmu_pile_segments", "kmu_extract_ranges", "kmu_pile_consensus_pos", "kmu_sg_classify", "kmu_sg_graph",
     "kmu_sg_unitigs", "kmu_sg_unitig_seqs", "kmu_sg_clean", "kmu_sg_unitig_chains",
+    "kmu_kfilter_cells_for", "kmu_kfilter_create", "kmu_kfilter_destroy", "kmu_kfilter_reset", "kmu_kfilter_add_reads",
+    "kmu_kfilter_add_kmers", "kmu_kfilter_query", "kmu_kfilter_info", "kmu_kfilter_export", "kmu_kfilter_merge",
+    "kmu_kfilter_select_reads", "kmu_count_add_reads_filtered",
 ]
 
 
@@ -182,6 +185,20 @@ def load():
     L.kmu_count_once_positions.argtypes = [vp, vp, vp, C.c_uint32, C.c_int, vp, vp, vp, C.c_uint64, u64p]
     L.kmu_count_histogram.argtypes = [vp, vp, C.c_uint32, C.c_int]
     L.kmu_count_read_profile.argtypes = [vp, vp, vp, C.c_uint32, C.c_int, C.c_uint32, vp, vp]
+    L.kmu_kfilter_cells_for.argtypes = [C.c_uint64, C.c_uint32]
+    L.kmu_kfilter_cells_for.restype = C.c_uint64
+    L.kmu_kfilter_create.argtypes = [vp, C.POINTER(A.KFilterParams), C.POINTER(vp)]
+    L.kmu_kfilter_destroy.argtypes = [vp]
+    L.kmu_kfilter_destroy.restype = None
+    L.kmu_kfilter_reset.argtypes = [vp]
+    L.kmu_kfilter_add_reads.argtypes = [vp, vp, vp, C.c_uint32, C.c_int]
+    L.kmu_kfilter_add_kmers.argtypes = [vp, vp, C.c_uint64, C.c_int]
+    L.kmu_kfilter_query.argtypes = [vp, vp, C.c_uint64, C.c_int, vp]
+    L.kmu_kfilter_info.argtypes = [vp, C.POINTER(A.KFilterInfo)]
+    L.kmu_kfilter_export.argtypes = [vp, vp, C.c_int]
+    L.kmu_kfilter_merge.argtypes = [vp, vp]
+    L.kmu_kfilter_select_reads.argtypes = [vp, vp, vp, C.c_uint32, C.c_int, vp, C.c_uint64, u64p]
+    L.kmu_count_add_reads_filtered.argtypes = [vp, vp, vp, vp, C.c_uint32, C.c_int, u64p]
     L.kmu_dev_alloc.argtypes = [vp, C.c_uint64, C.POINTER(vp)]
     L.kmu_dev_free.argtypes = [vp, vp]
     L.kmu_copy_to_device.argtypes = [vp, vp, vp, C.c_uint64]
@@ -217,7 +234,8 @@ class _StreamOrdered:
 
     _PLAIN = ("kmu_last_error", "kmu_destroy", "kmu_stream", "kmu_version", "kmu_device_count", "kmu_create",
               "kmu_block_layout", "kmu_anchor_layout", "kmu_minimizer_layout", "kmu_sketch_partial_words", "kmu_count_destroy", "kmu_comm_get_id", "kmu_comm_rank",
-              "kmu_comm_nranks", "kmu_comm_get_stats", "kmu_kmer_owner", "kmu_comm_destroy", "kmu_anchor_index_info", "kmu_anchor_index_destroy")
+              "kmu_comm_nranks", "kmu_comm_get_stats", "kmu_kmer_owner", "kmu_comm_destroy", "kmu_anchor_index_info", "kmu_anchor_index_destroy",
+              "kmu_kfilter_cells_for", "kmu_kfilter_destroy")
 
     def __init__(self, lib, ctx):
         self._lib = lib
@@ -1539,6 +1557,10 @@ class Context:
     def counter(self, kmer_type, k, counter_bits=8, capacity_hint=1 << 20, distributed=False, owner_hash=False, hint_occurrences=False):
         return Counter(self, kmer_type, k, counter_bits, capacity_hint, distributed, owner_hash, hint_occurrences)
 
+    def kfilter(self, kmer_type, k, n_cells, n_hashes=4):
+        """kmu_kfilter_create: the count prefilter (KFilter) of n_cells 16-byte cells; kfilter_cells_for sizes it"""
+        return KFilter(self, kmer_type, k, n_cells, n_hashes)
+
 
 class AnchorIndex:
     """kmu_anchor_index: ndb bottom-k rows (numpy, or a torch cuda tensor), their n_keys smallest hashes sorted into buckets, and
@@ -1647,6 +1669,20 @@ class Counter:
         self.ctx._wait_producers(canon)
         n = canon.numel() if _is_torch(canon) else canon.size
         self.ctx._check(self.L.kmu_count_add_kmers(self.h, _ptr(canon)[0], n, mem))
+
+    def add_reads_filtered(self, kfilter, bases, offsets):
+        """kmu_count_add_reads_filtered: the occurrences of the reads whose k-mer the prefilter puts in class 2 (may occur twice
+        or more) go into the table; returns their number.  A failed call raises with `n_passed` on the exception."""
+        mem = Context._mem(bases, offsets)
+        self.ctx._wait_producers(bases)
+        n = C.c_uint64(0)
+        try:
+            self.ctx._check(self.L.kmu_count_add_reads_filtered(self.h, kfilter.h, _ptr(bases)[0], _ptr(offsets)[0], len(offsets) - 1, mem,
+                                                                C.byref(n)))
+        except KmuError as e:
+            e.n_passed = n.value
+            raise
+        return n.value
 
     def query(self, canon):
         mem = Context._mem(canon)
@@ -1849,6 +1885,115 @@ class Counter:
 
     def retain_part(self, part, n_parts):
         self.ctx._check(self.L.kmu_count_retain_part(self.h, part, n_parts))
+
+
+def kfilter_cells_for(expected_distinct, bits_per_kmer=16):
+    """kmu_kfilter_cells_for (plain host code): max(1, ceil(expected_distinct * bits_per_kmer / 64)) cells; 0 when that is more
+    than a filter can have (2^32 - 1)"""
+    return int(load().kmu_kfilter_cells_for(int(expected_distinct), int(bits_per_kmer)))
+
+
+class KFilter:
+    """kmu_kfilter: the count prefilter -- n_cells cells {A, B} that tell the canonical k-mers added once (class 1) from those that
+    may have been added twice or more (class 2); include/kmu.h has the structure.  Close it before its context."""
+
+    def __init__(self, ctx, kmer_type, k, n_cells, n_hashes=4):
+        self.ctx = ctx
+        self.L = ctx.L
+        self.h = None
+        self.p = A.KFilterParams(kmer_type, k, n_hashes, 0, n_cells)
+        h = C.c_void_p()
+        ctx._check(self.L.kmu_kfilter_create(ctx.h, C.byref(self.p), C.byref(h)))
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None) and getattr(self.ctx, "h", None):
+            self.L.kmu_kfilter_destroy(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def reset(self):
+        self.ctx._check(self.L.kmu_kfilter_reset(self.h))
+
+    def add_reads(self, bases, offsets):
+        """kmu_kfilter_add_reads: one occurrence of every canonical k-mer of every read (ASCII bases)"""
+        mem = Context._mem(bases, offsets)
+        self.ctx._check(self.L.kmu_kfilter_add_reads(self.h, _ptr(bases)[0], _ptr(offsets)[0], len(offsets) - 1, mem))
+
+    def add_kmers(self, canon):
+        mem = Context._mem(canon)
+        n = canon.numel() if _is_torch(canon) else canon.size
+        self.ctx._check(self.L.kmu_kfilter_add_kmers(self.h, _ptr(canon)[0], n, mem))
+
+    def query(self, canon):
+        """kmu_kfilter_query: the class (0 never added, 1 added once, 2 maybe more often) of every value; uint8"""
+        mem = Context._mem(canon)
+        if mem == A.MEM_DEVICE:
+            import torch
+            n = canon.numel()
+            out = torch.zeros(max(n, 1), dtype=torch.uint8, device=canon.device)
+        else:
+            canon = np.ascontiguousarray(canon, np.uint64)
+            n = canon.size
+            out = np.zeros(max(n, 1), np.uint8)
+        self.ctx._check(self.L.kmu_kfilter_query(self.h, _ptr(canon)[0], n, mem, _ptr(out)[0]))
+        return out[:n]
+
+    def info(self):
+        """kmu_kfilter_info as a dict: n_cells, bytes, n_hashes, kmer_size, n_added, bits_a, bits_b, est_distinct"""
+        t = A.KFilterInfo()
+        self.ctx._check(self.L.kmu_kfilter_info(self.h, C.byref(t)))
+        return {k: (float(t.est_distinct) if k == "est_distinct" else int(getattr(t, k))) for k, _ in A.KFilterInfo._fields_}
+
+    def export(self, device=None):
+        """kmu_kfilter_export: the 2 * n_cells words A0 B0 A1 B1 ...; a numpy uint64 array, or a torch int64 cuda tensor when
+        device is given"""
+        n = 2 * int(self.p.n_cells)
+        if device is not None:
+            import torch
+            out = torch.zeros(n, dtype=torch.int64, device=device)
+            self.ctx._check(self.L.kmu_kfilter_export(self.h, _ptr(out)[0], A.MEM_DEVICE))
+            return out
+        out = np.zeros(n, np.uint64)
+        self.ctx._check(self.L.kmu_kfilter_export(self.h, _ptr(out)[0], A.MEM_HOST))
+        return out
+
+    def merge(self, other):
+        """kmu_kfilter_merge: this filter becomes the filter of both inputs (same context and parameters)"""
+        self.ctx._check(self.L.kmu_kfilter_merge(self.h, other.h))
+
+    def select_reads(self, bases, offsets):
+        """kmu_kfilter_select_reads: the canonical k-mer of every class-2 occurrence of the reads, in (sequence, position) order;
+        a numpy array for host input, a torch cuda tensor for device input.  Two library calls: the size, then the k-mers."""
+        n = self.n_passing(bases, offsets)
+        mem = Context._mem(bases, offsets)
+        if mem == A.MEM_DEVICE:
+            import torch
+            k = torch.zeros(max(n, 1), dtype=torch.int64, device=bases.device)
+        else:
+            k = np.zeros(max(n, 1), np.uint64)
+        got = C.c_uint64(0)
+        self.ctx._check(self.L.kmu_kfilter_select_reads(self.h, _ptr(bases)[0], _ptr(offsets)[0], len(offsets) - 1, mem, _ptr(k)[0], n,
+                                                        C.byref(got)))
+        return k[:got.value]
+
+    def n_passing(self, bases, offsets):
+        """the size query of kmu_kfilter_select_reads: how many k-mer occurrences of the reads are class 2"""
+        mem = Context._mem(bases, offsets)
+        n = C.c_uint64(0)
+        self.ctx._check(self.L.kmu_kfilter_select_reads(self.h, _ptr(bases)[0], _ptr(offsets)[0], len(offsets) - 1, mem, None, 0, C.byref(n)))
+        return n.value
 
 
 def anchor_layout(offsets_host, window, overlap):

@@ -6,6 +6,9 @@ src/base/kmercount.rs:881-974) and the k-mers seen at least twice are written to
 reference's dump format (`threaded_dump_kmer_counter` / `dump_kmer_counter`, kmercount.rs:467-531, :653-791).  The
 k-mer type follows the tool: Kmer64bit for 16 < k <= 32 (here: <= 31, k = 32 is broken upstream), Kmer16b32bit for
 k == 16, Kmer32bit for k <= 14.
+
+`--repeated [--filter-bits N]` counts through the Bloom prefilter (kmercount.count_repeated_kmers' order of calls): two passes
+over the reads, the k-mers seen once stay off the table, and the dump is byte for byte that of the plain count.
 """
 import argparse
 import os
@@ -37,8 +40,15 @@ def main(argv=None):
                     "(KmerProcessing::Unicity, parsefastq.rs:238-247) instead of counting")
     ap.add_argument("--histo", metavar="FILE", help="after the count: the count spectrum, one `count<TAB>number of distinct "
                     "k-mers` line per non-empty bin, ascending")
+    ap.add_argument("--repeated", action="store_true", help="count through the Bloom prefilter (count_repeated_kmers): two passes "
+                    "over the reads, the k-mers seen once stay off the table; the dump is that of the plain count")
+    ap.add_argument("--filter-bits", type=int, default=16, metavar="N", help="with --repeated: filter bits per k-mer occurrence")
     ap.add_argument("--device", type=int, default=0)
     args = ap.parse_args(argv)
+    if args.repeated and args.histo:
+        ap.error("--histo with --repeated: the table holds no singletons, bin 1 would be meaningless")
+    if args.repeated and args.unique:
+        ap.error("--repeated goes with the count, not with --unique")
     kmer_type, val_bytes = kmer_type_for(args.kmer_size)
     ctx = lib.Context(args.device)
     t0 = time.time()
@@ -58,9 +68,19 @@ def main(argv=None):
         ctx.close()
         return 0
     nk = int(np.maximum(np.diff(offsets.astype(np.int64)) - args.kmer_size + 1, 0).sum())
-    counter = ctx.counter(kmer_type, args.kmer_size, 8, max(nk, 1024))
-    if info.n_kept:
-        counter.add_reads(bases, offsets)
+    if args.repeated and info.n_kept:  # the filter, the number of occurrences that pass it, the table for those alone
+        kf = ctx.kfilter(kmer_type, args.kmer_size, lib.kfilter_cells_for(nk, args.filter_bits) or A.KFILTER_MAX_CELLS)
+        kf.add_reads(bases, offsets)
+        passing = kf.n_passing(bases, offsets)
+        counter = ctx.counter(kmer_type, args.kmer_size, 8, max(passing, 1024))
+        counter.add_reads_filtered(kf, bases, offsets)
+        print("prefilter: %d of %d k-mer occurrences passed, filter bytes %d, estimated distinct %.0f" %
+              (passing, nk, kf.info()["bytes"], kf.info()["est_distinct"]), file=sys.stderr)
+        kf.close()
+    else:
+        counter = ctx.counter(kmer_type, args.kmer_size, 8, max(nk, 1024))
+        if info.n_kept:
+            counter.add_reads(bases, offsets)
     kmers, counts = counter.dump(2)
     out = os.path.join(args.outdir, os.path.basename(args.file) + ".multi_kmer.bin")  # parsefastq.rs:207-211
     print("dumping multiple kmers in file : %s " % out, file=sys.stderr)

@@ -1,4 +1,5 @@
-// parsefastq -f reads.fastq kmer (--count -s <kmer size> | --unique) [-t threads] [-b 2] [--outdir dir] [--device n] [--histo file]
+// parsefastq -f reads.fastq kmer (--count -s <kmer size> [--repeated [--filter-bits n]] | --unique) [-t threads] [-b 2] [--outdir dir]
+//            [--device n] [--histo file]
 //
 // The counting branch of the reference's tool (src/bin/parsefastq.rs:215-236: `kmer --count`) on the GPU path: the FASTQ
 // text is filtered on the device like parse_with_needletail does on the host (src/io.rs:37-57), every canonical k-mer of
@@ -7,6 +8,10 @@
 // Unicity branch (parsefastq.rs:238-247): the 16-mers seen exactly once, with (sequence, position), to <fastq>.once_kmer.bin.
 // `--histo <file>` (with --count; no counterpart upstream): the count spectrum of the table, one `count<TAB>number of distinct
 // k-mers` line per non-empty bin, ascending (counts saturate at 255).
+// `--repeated` (with --count; no counterpart upstream): the count through the Bloom prefilter (count_repeated_kmers) -- two passes
+// over the reads, the k-mers seen once stay off the table; the dump is byte for byte that of the plain count, counts >= 2 being
+// exact either way.  `--filter-bits <n>`: filter bits per k-mer occurrence (default 16).  `--histo` is refused with it: the table
+// holds no singletons, bin 1 would be meaningless.
 // Kmer type by size as upstream: k <= 14 Kmer32bit, k == 16 Kmer16b32bit, else Kmer64bit (k <= 31).
 #include <chrono>
 #include <cstdio>
@@ -18,8 +23,21 @@
 using namespace kmerutils;
 
 static void usage() {
-    std::fprintf(stderr, "usage: parsefastq -f <fastq> kmer (--count -s <kmer size> | --unique) [-t <threads>] [-b 2] [--outdir <dir>] [--device <n>] [--histo <file>]\n");
+    std::fprintf(stderr, "usage: parsefastq -f <fastq> kmer (--count -s <kmer size> [--repeated [--filter-bits <n>]] | --unique) [-t <threads>] [-b 2] "
+                         "[--outdir <dir>] [--device <n>] [--histo <file>]\n");
     std::exit(2);
+}
+
+template <class Kmer>
+static void count_repeated_and_dump(const DeviceReads &reads, uint8_t kmer_size, uint32_t filter_bits, const std::string &dumpfname, Context &ctx) {
+    RepeatedKmers<Kmer> r = count_repeated_kmers<Kmer>(reads.batch(0, reads.nb_reads()), kmer_size, 8, filter_bits, 4, 0, ctx);
+    const kmu_kfilter_info_t fi = r.filter->info();
+    std::fprintf(stderr, " prefilter: %llu of %llu kmer occurrences passed, filter bytes %llu, estimated distinct %.0f\n",
+                 (unsigned long long) r.nb_passed, (unsigned long long) fi.n_added, (unsigned long long) fi.bytes, fi.est_distinct);
+    std::fprintf(stderr, " nb distinct kmers held %llu, of which seen once %llu\n", (unsigned long long) r.counter->get_nb_distinct(),
+                 (unsigned long long) r.counter->get_nb_unique());
+    const size_t n = r.counter->dump_kmer_counter(dumpfname);
+    std::fprintf(stderr, " dumped %zu kmers seen at least twice in %s\n", n, dumpfname.c_str());
 }
 
 template <class Kmer>
@@ -42,8 +60,8 @@ static void count_and_dump(const DeviceReads &reads, uint8_t kmer_size, const st
 
 int main(int argc, char **argv) {
     std::string fname, outdir = ".", histo;
-    long kmer_size = 0, device = 0;
-    bool count = false, kmer_cmd = false, unique = false;
+    long kmer_size = 0, device = 0, filter_bits = 16;
+    bool count = false, kmer_cmd = false, unique = false, repeated = false;
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
         auto next = [&]() -> const char * {
@@ -64,9 +82,16 @@ int main(int argc, char **argv) {
         } else if (a == "--outdir") outdir = next();
         else if (a == "--device") device = std::atol(next());
         else if (a == "--histo") histo = next();
+        else if (a == "--repeated") repeated = true;
+        else if (a == "--filter-bits") filter_bits = std::atol(next());
         else usage();
     }
     if (fname.empty() || !kmer_cmd || (!count && !unique) || (count && (kmer_size < 1 || kmer_size > 31))) usage();
+    if (repeated && (!count || unique || filter_bits < 1)) usage();
+    if (repeated && !histo.empty()) {
+        std::fprintf(stderr, "--histo with --repeated: the table holds no singletons, bin 1 would be meaningless\n");
+        return 2;
+    }
     try {
         const auto t0 = std::chrono::steady_clock::now();
         Context ctx{int(device)};
@@ -86,6 +111,10 @@ int main(int argc, char **argv) {
             const size_t n = filter.dump_in_file_once_kmer16b32bit(oncefname, all);
             std::fprintf(stderr, "dump_in_file_once_kmer16b32bit, number of kmer dumped : %zu (distinct once-k-mers %llu)\n", n,
                          (unsigned long long) filter.get_nb_once());
+        } else if (repeated) {
+            if (kmer_size <= 14) count_repeated_and_dump<Kmer32bit>(reads, uint8_t(kmer_size), uint32_t(filter_bits), dumpfname, ctx);
+            else if (kmer_size == 16) count_repeated_and_dump<Kmer16b32bit>(reads, uint8_t(kmer_size), uint32_t(filter_bits), dumpfname, ctx);
+            else count_repeated_and_dump<Kmer64bit>(reads, uint8_t(kmer_size), uint32_t(filter_bits), dumpfname, ctx);
         } else if (kmer_size <= 14) count_and_dump<Kmer32bit>(reads, uint8_t(kmer_size), dumpfname, histo, ctx);
         else if (kmer_size == 16) count_and_dump<Kmer16b32bit>(reads, uint8_t(kmer_size), dumpfname, histo, ctx);
         else count_and_dump<Kmer64bit>(reads, uint8_t(kmer_size), dumpfname, histo, ctx);
