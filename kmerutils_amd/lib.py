@@ -17,33 +17,150 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.environ.get("KMU_LIB") or os.path.join(_HERE, "libkmu.so")
 _lib = None
 
-# every symbol include/kmu.h declares (tests check the library exports all of them)
-SYMBOLS = [
-    "kmu_version", "kmu_device_count", "kmu_create", "kmu_destroy", "kmu_last_error", "kmu_synchronize", "kmu_stream",
-    "kmu_profile_enable", "kmu_profile_reset", "kmu_profile_get", "kmu_count_non_acgt", "kmu_pack2b",
-    "kmu_kmer_hashes", "kmu_sketch", "kmu_block_layout", "kmu_sketch_hashed", "kmu_count_create", "kmu_count_destroy",
-    "kmu_count_reset", "kmu_count_add_reads", "kmu_count_add_kmers", "kmu_count_query", "kmu_count_nb_distinct",
-    "kmu_count_nb_unique", "kmu_count_dump", "kmu_count_export_part", "kmu_count_merge_entries",
-    "kmu_count_retain_part", "kmu_count_extract_by_owner", "kmu_sig_equal_pairs", "kmu_sig_equal_matrix", "kmu_sig_knn",
-    "kmu_minhash_distance_pairs", "kmu_ingest_fastq", "kmu_ingest_fasta", "kmu_ingest_fastx", "kmu_dev_alloc", "kmu_dev_free",
-    "kmu_copy_to_device", "kmu_copy_to_host", "kmu_count_once_positions", "kmu_count_eliminate_once", "kmu_sketch_partial_words",
-    "kmu_sketch_partial", "kmu_sketch_hashed_partial", "kmu_sketch_merge_partials", "kmu_kmer_hashes_compact", "kmu_set_hll_params",
-    "kmu_kmer_hashes_range", "kmu_kmer_distribution", "kmu_nthash", "kmu_sketch_groups",
-    "kmu_comm_get_id", "kmu_comm_init", "kmu_comm_init_custom", "kmu_comm_set_transport", "kmu_comm_transport", "kmu_comm_destroy", "kmu_comm_rank", "kmu_comm_nranks",
-    "kmu_comm_allgather", "kmu_comm_get_stats", "kmu_count_finalize", "kmu_kmer_owner",
-    "kmu_sketch_count", "kmu_host_alloc", "kmu_host_free", "kmu_count_nb_occurrences", "kmu_count_table_info",
-    "kmu_count_nb_saturated", "kmu_kmer_owner_minimizer", "kmu_count_owner_kind", "kmu_count_extract_superkmers", "kmu_count_add_superkmers",
-    "kmu_count_histogram", "kmu_count_read_profile", "kmu_anchor_layout", "kmu_read_anchors", "kmu_anchor_match",
-    "kmu_anchor_overlaps", "kmu_anchor_index_create", "kmu_anchor_index_destroy", "kmu_anchor_index_info",
-    "kmu_anchor_index_occupancy", "kmu_anchor_index_match", "kmu_components", "kmu_components_knn",
-    "kmu_minimizer_layout", "kmu_read_minimizers", "kmu_seed_chains", "kmu_chain_align",
-    "kmu_chain_cigar", "kmu_chain_pileup", "kmu_pile_call", "kmu_pile_ins_plan", "kmu_chain_pile_ins", "kmu_pile_consensus",
-    "kmu_pile_segments", "kmu_extract_ranges", "kmu_pile_consensus_pos", "kmu_sg_classify", "kmu_sg_graph",
-    "kmu_sg_unitigs", "kmu_sg_unitig_seqs", "kmu_sg_clean", "kmu_sg_unitig_chains",
-    "kmu_kfilter_cells_for", "kmu_kfilter_create", "kmu_kfilter_destroy", "kmu_kfilter_reset", "kmu_kfilter_add_reads",
-    "kmu_kfilter_add_kmers", "kmu_kfilter_query", "kmu_kfilter_info", "kmu_kfilter_export", "kmu_kfilter_merge",
-    "kmu_kfilter_select_reads", "kmu_count_add_reads_filtered",
-]
+
+def _entry_points():
+    """Every entry point include/kmu.h declares: name -> (argtypes, restype, plain).  The one list of them: load() declares each
+    signature from it, SYMBOLS is its names (tests check the library exports all of them), and `plain` marks the calls that
+    _StreamOrdered does not order behind torch's stream -- they touch no device buffer, or free a handle."""
+    vp, u64p, u32p = C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)
+    ingest = [vp, vp, C.c_uint64, C.c_int, vp, C.c_uint64, vp, C.c_uint64, vp, C.POINTER(A.IngestInfo)]
+    table = {}
+
+    def d(name, argtypes, restype=C.c_int, plain=False):
+        table[name] = (argtypes, restype, plain)
+    d("kmu_version", [], C.c_char_p, plain=True)
+    d("kmu_device_count", [], plain=True)
+    d("kmu_create", [C.POINTER(A.DeviceCfg), C.POINTER(vp)], plain=True)
+    d("kmu_destroy", [vp], None, plain=True)
+    d("kmu_last_error", [vp], C.c_char_p, plain=True)
+    d("kmu_synchronize", [vp])
+    d("kmu_stream", [vp], vp, plain=True)
+    d("kmu_profile_enable", [vp, C.c_int])
+    d("kmu_profile_reset", [vp])
+    d("kmu_profile_get", [vp, C.POINTER(A.KernelStat), C.c_int])
+    d("kmu_count_non_acgt", [vp, vp, vp, C.c_uint32, C.c_int, vp])
+    d("kmu_pack2b", [vp, vp, vp, C.c_uint32, C.c_int, vp, vp])
+    d("kmu_kmer_hashes", [vp, C.POINTER(A.HashParams), vp, vp, vp, C.c_uint32, vp])
+    d("kmu_kmer_hashes_range", [vp, C.POINTER(A.HashParams), vp, vp, vp, C.c_uint32, vp, vp, vp])
+    d("kmu_kmer_distribution", [vp, C.POINTER(A.HashParams), vp, vp, vp, C.c_uint32, vp, vp, C.c_uint64, vp, u64p])
+    d("kmu_nthash", [vp, C.POINTER(A.NthashParams), vp, vp, vp, C.c_uint32, vp, vp])
+    d("kmu_sketch_count", [vp, C.POINTER(A.SketchParams), vp, vp, vp, C.c_uint32, vp])
+    d("kmu_host_alloc", [vp, C.c_uint64, C.POINTER(vp)])
+    d("kmu_host_free", [vp, vp])
+    d("kmu_count_nb_occurrences", [vp, u64p])
+    d("kmu_count_nb_saturated", [vp, u64p])
+    d("kmu_count_table_info", [vp, C.POINTER(A.CountTableInfo)])
+    d("kmu_comm_get_id", [C.POINTER(A.CommId)], plain=True)
+    d("kmu_comm_init", [vp, C.POINTER(A.CommId), C.c_int, C.c_int])
+    d("kmu_comm_init_custom", [vp, C.c_int, C.c_int, A.ALLTOALLV_FN, A.ALLGATHER_FN, vp])
+    d("kmu_comm_set_transport", [vp, C.c_int])
+    d("kmu_comm_transport", [vp])
+    d("kmu_comm_destroy", [vp], plain=True)
+    d("kmu_comm_rank", [vp], plain=True)
+    d("kmu_comm_nranks", [vp], plain=True)
+    d("kmu_comm_allgather", [vp, vp, vp, C.c_uint64])
+    d("kmu_comm_get_stats", [vp, C.POINTER(A.CommStats)], plain=True)
+    d("kmu_count_finalize", [vp])
+    d("kmu_kmer_owner", [C.c_int, vp, C.c_uint64, C.c_uint32, vp], plain=True)
+    d("kmu_kmer_owner_minimizer", [C.c_int, vp, C.c_uint64, C.c_uint32, vp])
+    d("kmu_count_owner_kind", [vp])
+    d("kmu_count_extract_superkmers", [vp, vp, vp, C.c_uint32, C.c_int, C.c_uint32, C.POINTER(vp), vp, vp])
+    d("kmu_count_add_superkmers", [vp, vp, C.c_uint64, C.c_int])
+    d("kmu_sketch", [vp, C.POINTER(A.SketchParams), vp, vp, vp, C.c_uint32, vp, vp, vp])
+    d("kmu_sketch_groups", [vp, C.POINTER(A.SketchParams), vp, vp, vp, C.c_uint32, vp, C.c_uint32, vp])
+    d("kmu_block_layout", [vp, C.c_uint32, C.c_uint32, vp], plain=True)
+    d("kmu_anchor_layout", [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp], plain=True)
+    d("kmu_read_anchors", [vp, C.POINTER(A.SketchParams), vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp])
+    d("kmu_sketch_hashed", [vp, C.POINTER(A.SketchParams), vp, vp, C.c_uint32, vp, vp])
+    d("kmu_count_create", [vp, C.POINTER(A.CountParams), C.POINTER(vp)])
+    d("kmu_count_destroy", [vp], None, plain=True)
+    d("kmu_count_reset", [vp])
+    d("kmu_count_add_reads", [vp, vp, vp, vp, C.c_uint32, C.c_int, C.c_int])
+    d("kmu_count_add_kmers", [vp, vp, C.c_uint64, C.c_int])
+    d("kmu_count_query", [vp, vp, C.c_uint64, C.c_int, vp])
+    d("kmu_count_nb_distinct", [vp, u64p])
+    d("kmu_count_nb_unique", [vp, u64p])
+    d("kmu_count_dump", [vp, C.c_uint32, vp, vp, C.c_uint64, u64p])
+    d("kmu_count_export_part", [vp, C.c_uint32, C.c_uint32, vp, vp, C.c_uint64, C.c_int, u64p])
+    d("kmu_count_merge_entries", [vp, vp, vp, C.c_uint64, C.c_int])
+    d("kmu_count_retain_part", [vp, C.c_uint32, C.c_uint32])
+    d("kmu_count_extract_by_owner", [vp, vp, vp, C.c_uint32, C.c_int, C.c_uint32, C.POINTER(vp), vp])
+    d("kmu_sig_equal_pairs", [vp, vp, C.c_uint32, vp, C.c_uint32, C.c_uint32, C.c_int, vp, vp, C.c_uint64, C.c_int, vp])
+    d("kmu_sig_equal_matrix", [vp, vp, C.c_uint32, vp, C.c_uint32, C.c_uint32, C.c_int, C.c_int, vp])
+    d("kmu_sig_knn", [vp, vp, C.c_uint32, vp, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, vp, vp, C.c_int, vp, vp])
+    d("kmu_minhash_distance_pairs", [vp, vp, C.c_uint32, vp, C.c_uint32, C.c_uint32, vp, vp, C.c_uint64, C.c_int, vp])
+    d("kmu_anchor_match", [vp, vp, C.c_uint32, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, C.c_int, vp, vp,
+                           C.c_uint64, u64p])
+    d("kmu_anchor_overlaps", [vp, vp, vp, C.c_uint64, vp, C.c_uint32, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                              C.c_uint32, C.c_int, vp, C.c_uint64, u64p])
+    d("kmu_anchor_index_create", [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, C.c_int, C.POINTER(vp)])
+    d("kmu_anchor_index_destroy", [vp], None, plain=True)
+    d("kmu_anchor_index_info", [vp, C.POINTER(A.AnchorIndexInfo)], plain=True)
+    d("kmu_anchor_index_occupancy", [vp, vp, C.c_uint32, C.c_int])
+    d("kmu_anchor_index_match", [vp, vp, C.c_uint32, vp, C.c_uint32, C.c_uint32, C.c_int, vp, vp, C.c_uint64, u64p])
+    d("kmu_components", [vp, C.c_uint32, vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, vp, vp, vp, vp, u32p])
+    d("kmu_components_knn", [vp, C.c_uint32, vp, vp, C.c_uint32, C.c_uint32, C.c_int, vp, vp, vp, vp, u32p])
+    d("kmu_minimizer_layout", [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp], plain=True)
+    d("kmu_read_minimizers", [vp, C.POINTER(A.HashParams), vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp, C.c_uint64, vp, u64p])
+    d("kmu_seed_chains", [vp, vp, C.c_uint64, vp, vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp, C.c_uint32, C.c_uint32,
+                          C.POINTER(A.ChainParams), C.c_int, vp, C.c_uint64, u64p])
+    d("kmu_chain_align", [vp, vp, C.c_uint64, vp, vp, C.c_uint32, vp, vp, C.c_uint32, C.POINTER(A.AlignParams), C.c_int, vp])
+    d("kmu_chain_cigar", [vp, vp, C.c_uint64, vp, vp, C.c_uint32, vp, vp, C.c_uint32, C.POINTER(A.CigarParams), C.c_int, vp, vp,
+                          vp, C.c_uint64, u64p])
+    d("kmu_chain_pileup", [vp, vp, C.c_uint64, vp, vp, vp, C.c_uint64, vp, vp, C.c_uint32, vp, vp, C.c_uint32,
+                           C.POINTER(A.PileupParams), C.c_int, vp, vp])
+    d("kmu_pile_call", [vp, vp, vp, vp, C.c_uint32, C.POINTER(A.PileCallParams), C.c_int, vp, vp])
+    d("kmu_pile_ins_plan", [vp, vp, vp, C.c_uint64, C.POINTER(A.InsPlanParams), C.c_int, vp, C.POINTER(C.c_uint64)])
+    d("kmu_chain_pile_ins", [vp, vp, C.c_uint64, vp, vp, vp, C.c_uint64, vp, vp, C.c_uint32, vp, vp, C.c_uint32,
+                             C.POINTER(A.PileupParams), C.c_int, vp, C.c_uint64, vp, vp, C.c_uint64, vp])
+    d("kmu_pile_consensus", [vp, vp, vp, vp, C.c_uint64, vp, vp, vp, C.c_uint32, C.POINTER(A.ConsensusParams), C.c_int, vp, vp,
+                             C.c_uint64, C.POINTER(C.c_uint64)])
+    d("kmu_pile_segments", [vp, vp, vp, C.c_uint32, C.POINTER(A.PileSegParams), C.c_int, vp, vp, C.c_uint64, C.POINTER(C.c_uint64), vp])
+    d("kmu_extract_ranges", [vp, vp, C.c_uint64, vp, vp, C.c_uint64, C.c_int, vp, vp, C.c_uint64, C.POINTER(C.c_uint64)])
+    d("kmu_pile_consensus_pos", [vp, vp, vp, vp, C.c_uint64, vp, vp, vp, C.c_uint32, C.POINTER(A.ConsensusParams), C.c_int, vp,
+                                 C.c_uint64, vp])
+    d("kmu_sg_classify", [vp, vp, vp, C.c_uint64, vp, C.c_uint32, C.POINTER(A.SgParams), C.c_int, vp, vp])
+    d("kmu_sg_graph", [vp, vp, vp, C.c_uint64, vp, C.c_uint32, C.POINTER(A.SgParams), C.c_int, vp, vp, vp, C.c_uint64, vp,
+                       C.POINTER(C.c_uint64)])
+    d("kmu_sg_unitigs", [vp, vp, C.c_uint64, vp, vp, C.c_uint32, C.c_int, vp, vp, vp, u64p, u64p])
+    d("kmu_sg_unitig_seqs", [vp, vp, C.c_uint64, vp, C.c_uint64, vp, vp, C.c_uint32, C.c_int, vp, vp, C.c_uint64, u64p])
+    d("kmu_sg_clean", [vp, vp, C.c_uint64, vp, C.c_uint32, C.POINTER(A.SgCleanParams), C.c_int, vp, vp, C.POINTER(A.SgCleanStats)])
+    d("kmu_sg_unitig_chains", [vp, vp, C.c_uint64, vp, C.c_uint64, vp, vp, vp, C.c_uint64, vp, C.c_uint32, C.POINTER(A.UmParams),
+                               C.c_int, vp, C.POINTER(A.UmStats), u64p])
+    d("kmu_set_hll_params", [vp, C.POINTER(A.HllParams)])
+    d("kmu_kmer_hashes_compact", [vp, C.POINTER(A.HashParams), vp, vp, vp, C.c_uint32, vp, C.c_uint64, u64p])
+    d("kmu_sketch_partial_words", [C.POINTER(A.SketchParams)], C.c_uint32, plain=True)
+    d("kmu_sketch_partial", [vp, C.POINTER(A.SketchParams), vp, vp, vp, C.c_uint32, vp])
+    d("kmu_sketch_hashed_partial", [vp, C.POINTER(A.SketchParams), vp, vp, C.c_uint32, vp])
+    d("kmu_sketch_merge_partials", [vp, C.POINTER(A.SketchParams), vp, C.c_uint32, vp])
+    d("kmu_count_eliminate_once", [vp])
+    d("kmu_count_once_positions", [vp, vp, vp, C.c_uint32, C.c_int, vp, vp, vp, C.c_uint64, u64p])
+    d("kmu_count_histogram", [vp, vp, C.c_uint32, C.c_int])
+    d("kmu_count_read_profile", [vp, vp, vp, C.c_uint32, C.c_int, C.c_uint32, vp, vp])
+    d("kmu_kfilter_cells_for", [C.c_uint64, C.c_uint32], C.c_uint64, plain=True)
+    d("kmu_kfilter_create", [vp, C.POINTER(A.KFilterParams), C.POINTER(vp)])
+    d("kmu_kfilter_destroy", [vp], None, plain=True)
+    d("kmu_kfilter_reset", [vp])
+    d("kmu_kfilter_add_reads", [vp, vp, vp, C.c_uint32, C.c_int])
+    d("kmu_kfilter_add_kmers", [vp, vp, C.c_uint64, C.c_int])
+    d("kmu_kfilter_query", [vp, vp, C.c_uint64, C.c_int, vp])
+    d("kmu_kfilter_info", [vp, C.POINTER(A.KFilterInfo)])
+    d("kmu_kfilter_export", [vp, vp, C.c_int])
+    d("kmu_kfilter_merge", [vp, vp])
+    d("kmu_kfilter_select_reads", [vp, vp, vp, C.c_uint32, C.c_int, vp, C.c_uint64, u64p])
+    d("kmu_count_add_reads_filtered", [vp, vp, vp, vp, C.c_uint32, C.c_int, u64p])
+    d("kmu_dev_alloc", [vp, C.c_uint64, C.POINTER(vp)])
+    d("kmu_dev_free", [vp, vp])
+    d("kmu_copy_to_device", [vp, vp, vp, C.c_uint64])
+    d("kmu_copy_to_host", [vp, vp, vp, C.c_uint64])
+    d("kmu_ingest_fastq", ingest)
+    d("kmu_ingest_fasta", ingest)
+    d("kmu_ingest_fastx", ingest)
+    return table
+
+
+_ENTRY_POINTS = _entry_points()
+SYMBOLS = list(_ENTRY_POINTS)
 
 
 # what Context.components / components_knn return: label [n] (the smallest node of every node's component), cluster [n] (dense
@@ -70,141 +187,9 @@ def load():
         raise ImportError("kmerutils_amd: %s is missing -- run `python -c 'import __graft_entry__ as g; g.build()'` "
                           "(hipcc --offload-arch=gfx950). There is no CPU fallback." % SO_PATH)
     L = C.CDLL(SO_PATH)
-    vp, u64p = C.c_void_p, C.POINTER(C.c_uint64)
-    L.kmu_version.restype = C.c_char_p
-    L.kmu_device_count.restype = C.c_int
-    L.kmu_create.argtypes = [C.POINTER(A.DeviceCfg), C.POINTER(vp)]
-    L.kmu_destroy.argtypes = [vp]
-    L.kmu_destroy.restype = None
-    L.kmu_last_error.argtypes = [vp]
-    L.kmu_last_error.restype = C.c_char_p
-    L.kmu_synchronize.argtypes = [vp]
-    L.kmu_stream.argtypes = [vp]
-    L.kmu_stream.restype = vp
-    L.kmu_profile_enable.argtypes = [vp, C.c_int]
-    L.kmu_profile_reset.argtypes = [vp]
-    L.kmu_profile_get.argtypes = [vp, C.POINTER(A.KernelStat), C.c_int]
-    L.kmu_count_non_acgt.argtypes = [vp, vp, vp, C.c_uint32, C.c_int, vp]
-    L.kmu_pack2b.argtypes = [vp, vp, vp, C.c_uint32, C.c_int, vp, vp]
-    L.kmu_kmer_hashes.argtypes = [vp, C.POINTER(A.HashParams), vp, vp, vp, C.c_uint32, vp]
-    L.kmu_kmer_hashes_range.argtypes = [vp, C.POINTER(A.HashParams), vp, vp, vp, C.c_uint32, vp, vp, vp]
-    L.kmu_kmer_distribution.argtypes = [vp, C.POINTER(A.HashParams), vp, vp, vp, C.c_uint32, vp, vp, C.c_uint64, vp, u64p]
-    L.kmu_nthash.argtypes = [vp, C.POINTER(A.NthashParams), vp, vp, vp, C.c_uint32, vp, vp]
-    L.kmu_sketch_count.argtypes = [vp, C.POINTER(A.SketchParams), vp, vp, vp, C.c_uint32, vp]
-    L.kmu_host_alloc.argtypes = [vp, C.c_uint64, C.POINTER(vp)]
-    L.kmu_host_free.argtypes = [vp, vp]
-    L.kmu_count_nb_occurrences.argtypes = [vp, u64p]
-    L.kmu_count_nb_saturated.argtypes = [vp, u64p]
-    L.kmu_count_table_info.argtypes = [vp, C.POINTER(A.CountTableInfo)]
-    L.kmu_comm_get_id.argtypes = [C.POINTER(A.CommId)]
-    L.kmu_comm_init.argtypes = [vp, C.POINTER(A.CommId), C.c_int, C.c_int]
-    L.kmu_comm_init_custom.argtypes = [vp, C.c_int, C.c_int, A.ALLTOALLV_FN, A.ALLGATHER_FN, vp]
-    L.kmu_comm_destroy.argtypes = [vp]
-    L.kmu_comm_rank.argtypes = [vp]
-    L.kmu_comm_nranks.argtypes = [vp]
-    L.kmu_comm_allgather.argtypes = [vp, vp, vp, C.c_uint64]
-    L.kmu_comm_get_stats.argtypes = [vp, C.POINTER(A.CommStats)]
-    L.kmu_count_finalize.argtypes = [vp]
-    L.kmu_kmer_owner.argtypes = [C.c_int, vp, C.c_uint64, C.c_uint32, vp]
-    L.kmu_kmer_owner_minimizer.argtypes = [C.c_int, vp, C.c_uint64, C.c_uint32, vp]
-    L.kmu_count_owner_kind.argtypes = [vp]
-    L.kmu_count_extract_superkmers.argtypes = [vp, vp, vp, C.c_uint32, C.c_int, C.c_uint32, C.POINTER(vp), vp, vp]
-    L.kmu_count_add_superkmers.argtypes = [vp, vp, C.c_uint64, C.c_int]
-    L.kmu_sketch.argtypes = [vp, C.POINTER(A.SketchParams), vp, vp, vp, C.c_uint32, vp, vp, vp]
-    L.kmu_sketch_groups.argtypes = [vp, C.POINTER(A.SketchParams), vp, vp, vp, C.c_uint32, vp, C.c_uint32, vp]
-    L.kmu_block_layout.argtypes = [vp, C.c_uint32, C.c_uint32, vp]
-    L.kmu_anchor_layout.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp]
-    L.kmu_read_anchors.argtypes = [vp, C.POINTER(A.SketchParams), vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp]
-    L.kmu_sketch_hashed.argtypes = [vp, C.POINTER(A.SketchParams), vp, vp, C.c_uint32, vp, vp]
-    L.kmu_count_create.argtypes = [vp, C.POINTER(A.CountParams), C.POINTER(vp)]
-    L.kmu_count_destroy.argtypes = [vp]
-    L.kmu_count_destroy.restype = None
-    L.kmu_count_reset.argtypes = [vp]
-    L.kmu_count_add_reads.argtypes = [vp, vp, vp, vp, C.c_uint32, C.c_int, C.c_int]
-    L.kmu_count_add_kmers.argtypes = [vp, vp, C.c_uint64, C.c_int]
-    L.kmu_count_query.argtypes = [vp, vp, C.c_uint64, C.c_int, vp]
-    L.kmu_count_nb_distinct.argtypes = [vp, u64p]
-    L.kmu_count_nb_unique.argtypes = [vp, u64p]
-    L.kmu_count_dump.argtypes = [vp, C.c_uint32, vp, vp, C.c_uint64, u64p]
-    L.kmu_count_export_part.argtypes = [vp, C.c_uint32, C.c_uint32, vp, vp, C.c_uint64, C.c_int, u64p]
-    L.kmu_count_merge_entries.argtypes = [vp, vp, vp, C.c_uint64, C.c_int]
-    L.kmu_count_retain_part.argtypes = [vp, C.c_uint32, C.c_uint32]
-    L.kmu_count_extract_by_owner.argtypes = [vp, vp, vp, C.c_uint32, C.c_int, C.c_uint32, C.POINTER(vp), vp]
-    L.kmu_sig_equal_pairs.argtypes = [vp, vp, C.c_uint32, vp, C.c_uint32, C.c_uint32, C.c_int, vp, vp, C.c_uint64, C.c_int, vp]
-    L.kmu_sig_equal_matrix.argtypes = [vp, vp, C.c_uint32, vp, C.c_uint32, C.c_uint32, C.c_int, C.c_int, vp]
-    L.kmu_sig_knn.argtypes = [vp, vp, C.c_uint32, vp, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, vp, vp, C.c_int, vp, vp]
-    L.kmu_minhash_distance_pairs.argtypes = [vp, vp, C.c_uint32, vp, C.c_uint32, C.c_uint32, vp, vp, C.c_uint64, C.c_int, vp]
-    L.kmu_anchor_match.argtypes = [vp, vp, C.c_uint32, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, C.c_int, vp, vp,
-                                   C.c_uint64, u64p]
-    L.kmu_anchor_overlaps.argtypes = [vp, vp, vp, C.c_uint64, vp, C.c_uint32, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
-                                      C.c_uint32, C.c_int, vp, C.c_uint64, u64p]
-    L.kmu_anchor_index_create.argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, C.c_int, C.POINTER(vp)]
-    L.kmu_anchor_index_destroy.argtypes = [vp]
-    L.kmu_anchor_index_destroy.restype = None
-    L.kmu_anchor_index_info.argtypes = [vp, C.POINTER(A.AnchorIndexInfo)]
-    L.kmu_anchor_index_occupancy.argtypes = [vp, vp, C.c_uint32, C.c_int]
-    L.kmu_anchor_index_match.argtypes = [vp, vp, C.c_uint32, vp, C.c_uint32, C.c_uint32, C.c_int, vp, vp, C.c_uint64, u64p]
-    u32p = C.POINTER(C.c_uint32)
-    L.kmu_components.argtypes = [vp, C.c_uint32, vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, vp, vp, vp, vp, u32p]
-    L.kmu_components_knn.argtypes = [vp, C.c_uint32, vp, vp, C.c_uint32, C.c_uint32, C.c_int, vp, vp, vp, vp, u32p]
-    L.kmu_minimizer_layout.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp]
-    L.kmu_read_minimizers.argtypes = [vp, C.POINTER(A.HashParams), vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp, C.c_uint64, vp, u64p]
-    L.kmu_seed_chains.argtypes = [vp, vp, C.c_uint64, vp, vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp, C.c_uint32, C.c_uint32,
-                                  C.POINTER(A.ChainParams), C.c_int, vp, C.c_uint64, u64p]
-    L.kmu_chain_align.argtypes = [vp, vp, C.c_uint64, vp, vp, C.c_uint32, vp, vp, C.c_uint32, C.POINTER(A.AlignParams), C.c_int, vp]
-    L.kmu_chain_cigar.argtypes = [vp, vp, C.c_uint64, vp, vp, C.c_uint32, vp, vp, C.c_uint32, C.POINTER(A.CigarParams), C.c_int, vp, vp,
-                                  vp, C.c_uint64, u64p]
-    L.kmu_chain_pileup.argtypes = [vp, vp, C.c_uint64, vp, vp, vp, C.c_uint64, vp, vp, C.c_uint32, vp, vp, C.c_uint32,
-                                   C.POINTER(A.PileupParams), C.c_int, vp, vp]
-    L.kmu_pile_call.argtypes = [vp, vp, vp, vp, C.c_uint32, C.POINTER(A.PileCallParams), C.c_int, vp, vp]
-    L.kmu_pile_ins_plan.argtypes = [vp, vp, vp, C.c_uint64, C.POINTER(A.InsPlanParams), C.c_int, vp, C.POINTER(C.c_uint64)]
-    L.kmu_chain_pile_ins.argtypes = [vp, vp, C.c_uint64, vp, vp, vp, C.c_uint64, vp, vp, C.c_uint32, vp, vp, C.c_uint32,
-                                     C.POINTER(A.PileupParams), C.c_int, vp, C.c_uint64, vp, vp, C.c_uint64, vp]
-    L.kmu_pile_consensus.argtypes = [vp, vp, vp, vp, C.c_uint64, vp, vp, vp, C.c_uint32, C.POINTER(A.ConsensusParams), C.c_int, vp, vp,
-                                     C.c_uint64, C.POINTER(C.c_uint64)]
-    L.kmu_pile_segments.argtypes = [vp, vp, vp, C.c_uint32, C.POINTER(A.PileSegParams), C.c_int, vp, vp, C.c_uint64, C.POINTER(C.c_uint64), vp]
-    L.kmu_extract_ranges.argtypes = [vp, vp, C.c_uint64, vp, vp, C.c_uint64, C.c_int, vp, vp, C.c_uint64, C.POINTER(C.c_uint64)]
-    L.kmu_pile_consensus_pos.argtypes = [vp, vp, vp, vp, C.c_uint64, vp, vp, vp, C.c_uint32, C.POINTER(A.ConsensusParams), C.c_int, vp,
-                                         C.c_uint64, vp]
-    L.kmu_sg_classify.argtypes = [vp, vp, vp, C.c_uint64, vp, C.c_uint32, C.POINTER(A.SgParams), C.c_int, vp, vp]
-    L.kmu_sg_graph.argtypes = [vp, vp, vp, C.c_uint64, vp, C.c_uint32, C.POINTER(A.SgParams), C.c_int, vp, vp, vp, C.c_uint64, vp,
-                               C.POINTER(C.c_uint64)]
-    L.kmu_sg_unitigs.argtypes = [vp, vp, C.c_uint64, vp, vp, C.c_uint32, C.c_int, vp, vp, vp, u64p, u64p]
-    L.kmu_sg_unitig_seqs.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, vp, vp, C.c_uint32, C.c_int, vp, vp, C.c_uint64, u64p]
-    L.kmu_sg_clean.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint32, C.POINTER(A.SgCleanParams), C.c_int, vp, vp, C.POINTER(A.SgCleanStats)]
-    L.kmu_sg_unitig_chains.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, vp, vp, vp, C.c_uint64, vp, C.c_uint32, C.POINTER(A.UmParams),
-                                       C.c_int, vp, C.POINTER(A.UmStats), u64p]
-    L.kmu_set_hll_params.argtypes = [vp, C.POINTER(A.HllParams)]
-    L.kmu_kmer_hashes_compact.argtypes = [vp, C.POINTER(A.HashParams), vp, vp, vp, C.c_uint32, vp, C.c_uint64, u64p]
-    L.kmu_sketch_partial_words.argtypes = [C.POINTER(A.SketchParams)]
-    L.kmu_sketch_partial_words.restype = C.c_uint32
-    L.kmu_sketch_partial.argtypes = [vp, C.POINTER(A.SketchParams), vp, vp, vp, C.c_uint32, vp]
-    L.kmu_sketch_hashed_partial.argtypes = [vp, C.POINTER(A.SketchParams), vp, vp, C.c_uint32, vp]
-    L.kmu_sketch_merge_partials.argtypes = [vp, C.POINTER(A.SketchParams), vp, C.c_uint32, vp]
-    L.kmu_count_eliminate_once.argtypes = [vp]
-    L.kmu_count_once_positions.argtypes = [vp, vp, vp, C.c_uint32, C.c_int, vp, vp, vp, C.c_uint64, u64p]
-    L.kmu_count_histogram.argtypes = [vp, vp, C.c_uint32, C.c_int]
-    L.kmu_count_read_profile.argtypes = [vp, vp, vp, C.c_uint32, C.c_int, C.c_uint32, vp, vp]
-    L.kmu_kfilter_cells_for.argtypes = [C.c_uint64, C.c_uint32]
-    L.kmu_kfilter_cells_for.restype = C.c_uint64
-    L.kmu_kfilter_create.argtypes = [vp, C.POINTER(A.KFilterParams), C.POINTER(vp)]
-    L.kmu_kfilter_destroy.argtypes = [vp]
-    L.kmu_kfilter_destroy.restype = None
-    L.kmu_kfilter_reset.argtypes = [vp]
-    L.kmu_kfilter_add_reads.argtypes = [vp, vp, vp, C.c_uint32, C.c_int]
-    L.kmu_kfilter_add_kmers.argtypes = [vp, vp, C.c_uint64, C.c_int]
-    L.kmu_kfilter_query.argtypes = [vp, vp, C.c_uint64, C.c_int, vp]
-    L.kmu_kfilter_info.argtypes = [vp, C.POINTER(A.KFilterInfo)]
-    L.kmu_kfilter_export.argtypes = [vp, vp, C.c_int]
-    L.kmu_kfilter_merge.argtypes = [vp, vp]
-    L.kmu_kfilter_select_reads.argtypes = [vp, vp, vp, C.c_uint32, C.c_int, vp, C.c_uint64, u64p]
-    L.kmu_count_add_reads_filtered.argtypes = [vp, vp, vp, vp, C.c_uint32, C.c_int, u64p]
-    L.kmu_dev_alloc.argtypes = [vp, C.c_uint64, C.POINTER(vp)]
-    L.kmu_dev_free.argtypes = [vp, vp]
-    L.kmu_copy_to_device.argtypes = [vp, vp, vp, C.c_uint64]
-    L.kmu_copy_to_host.argtypes = [vp, vp, vp, C.c_uint64]
-    for f in (L.kmu_ingest_fastq, L.kmu_ingest_fasta, L.kmu_ingest_fastx):
-        f.argtypes = [vp, vp, C.c_uint64, C.c_int, vp, C.c_uint64, vp, C.c_uint64, vp, C.POINTER(A.IngestInfo)]
+    for name, (argtypes, restype, _) in _ENTRY_POINTS.items():
+        f = getattr(L, name)
+        f.argtypes, f.restype = argtypes, restype
     _lib = L
     return L
 
@@ -232,10 +217,7 @@ class _StreamOrdered:
     the zero-fill of an output tensor allocated a line earlier, which could otherwise land on top of the kernel's results.
     Doing it here, at the one place every call passes through, covers the buffers of every present and future method."""
 
-    _PLAIN = ("kmu_last_error", "kmu_destroy", "kmu_stream", "kmu_version", "kmu_device_count", "kmu_create",
-              "kmu_block_layout", "kmu_anchor_layout", "kmu_minimizer_layout", "kmu_sketch_partial_words", "kmu_count_destroy", "kmu_comm_get_id", "kmu_comm_rank",
-              "kmu_comm_nranks", "kmu_comm_get_stats", "kmu_kmer_owner", "kmu_comm_destroy", "kmu_anchor_index_info", "kmu_anchor_index_destroy",
-              "kmu_kfilter_cells_for", "kmu_kfilter_destroy")
+    _PLAIN = frozenset(name for name, entry in _ENTRY_POINTS.items() if entry[2])
 
     def __init__(self, lib, ctx):
         self._lib = lib
@@ -398,10 +380,6 @@ class Context:
         if cur.cuda_stream != self._stream:
             cur.synchronize()
 
-    def _wait_producers(self, *xs):
-        """Kept for callers of round 1: the ordering now happens inside every library call (_StreamOrdered)."""
-        self._order_after_torch()
-
     # ---- helpers ----
     @staticmethod
     def _mem(*xs):
@@ -410,14 +388,121 @@ class Context:
             raise ValueError("all buffers of one call must live on the same side (host or device)")
         return A.MEM_DEVICE if dev and dev[0] else A.MEM_HOST
 
+    def _new_like(self, ref, shape, np_dtype, torch_dtype_name):
+        if _is_torch(ref) and ref.is_cuda:
+            import torch
+            return torch.zeros(shape, dtype=getattr(torch, torch_dtype_name), device=ref.device)
+        return np.zeros(shape, np_dtype)
+
+    def _records(self, like, n, dtype):
+        """n records of a structured A.*_DTYPE where `like` lives, one at least so that there is an address: a structured array
+        on the host, an int32 tensor [n, words of a record] holding the same bits on the device"""
+        dtype = np.dtype(dtype)
+        if _is_torch(like) and like.is_cuda:
+            return self._new_like(like, (max(n, 1), dtype.itemsize // 4), np.int32, "int32")
+        return np.zeros(max(n, 1), dtype)
+
+    def _ptrs(self, like):
+        """ptr(x) for the inputs of one call: the pointer of x, or where x has no rows (`rows`, where another count decides) that
+        of a placeholder of 16 bytes where `like` lives -- an empty array has no address worth passing (an empty device tensor's
+        is null), and the library reads no row of it.  The placeholder is made when it is first needed and shared by every ptr
+        of one _ptrs call, and lives as long as `ptr` does; a second _ptrs call has a second one."""
+        none = []
+
+        def ptr(x, rows=None):
+            if int(x.shape[0]) if rows is None else rows:
+                return _ptr(x)[0]
+            if not none:
+                none.append(self._new_like(like, 16, np.uint8, "uint8"))
+            return _ptr(none[0])[0]
+        return ptr
+
+    def _offsets_like(self, x, ref, mem):
+        """the offsets of a batch as uint64 where the arrays of the call live (int64 holding the same bits for torch)"""
+        if _is_torch(x):
+            if x.is_cuda == (mem == A.MEM_DEVICE):
+                return x
+            x = x.cpu().numpy()
+        x = np.ascontiguousarray(np.asarray(x).astype(np.uint64))
+        if mem == A.MEM_DEVICE:
+            import torch
+            return torch.from_numpy(x.view(np.int64)).to(ref.device)
+        return x
+
+    def _offsets_pair(self, offsets_q, offsets_db, ref, mem):
+        """_offsets_like of the two batches of a call; one object given for both is converted once"""
+        off_q = self._offsets_like(offsets_q, ref, mem)
+        return off_q, off_q if offsets_db is offsets_q else self._offsets_like(offsets_db, ref, mem)
+
+    @staticmethod
+    def _db_batch(bases_q, offsets_q, bases_db, offsets_db):
+        """(bases, offsets) of the second batch of a chain call: the first batch again for the self-join (bases_db None)"""
+        if bases_db is None:
+            return bases_q, offsets_q
+        if offsets_db is None:
+            raise ValueError("bases_db without offsets_db")
+        return bases_db, offsets_db
+
+    def _runs_of_chains(self, chains, aln, ops, op_offsets, *more):
+        """what chain_pileup and chain_pile_ins take from chain_cigar: (chains, aln) contiguous, the side of the call over these
+        and `more`, and the number of chains, with one alignment record and one run offset (and one more) each"""
+        if not _is_torch(chains):
+            chains = np.ascontiguousarray(chains)
+        if not _is_torch(aln):
+            aln = np.ascontiguousarray(aln)
+        mem = self._mem(chains, aln, ops, op_offsets, *more)
+        n = int(chains.shape[0])
+        if int(aln.shape[0]) != n or int(op_offsets.shape[0]) != n + 1:
+            raise ValueError("%d chains need %d alignment records and %d run offsets" % (n, n, n + 1))
+        return chains, aln, mem, n
+
+    def _side_tables(self, like, sides, own, into, rows_q, rows_db, cols):
+        """(table_q, table_db) of chain_pileup / chain_pile_ins: into=(table_q, table_db), or one table for both, as given;
+        otherwise uint32 [rows, cols] tables of zeros where `like` lives, one under both names for the self-join (`own`).  rows_*:
+        a number, or a function that gives it and is asked only for a table that is made (where the number has to be read back
+        from the device).  The table of a side that `sides` leaves out is None."""
+        def rows(r):
+            return r() if callable(r) else r
+        if into is not None:
+            table_q, table_db = into if isinstance(into, (tuple, list)) else (into, into)
+            if (sides & A.PILE_Q and table_q is None) or (sides & A.PILE_DB and table_db is None):
+                raise ValueError("into lacks the table of a side that is asked for")
+            return table_q, table_db
+        table_q = self._new_like(like, (rows(rows_q), cols), np.uint32, "int32") if sides & A.PILE_Q else None
+        if own and table_q is not None:
+            return table_q, (table_q if sides & A.PILE_DB else None)
+        return table_q, (self._new_like(like, (rows(rows_db), cols), np.uint32, "int32") if sides & A.PILE_DB else None)
+
+    def _kmer_values(self, canon):
+        """(values, how many, mem) of k-mer values to look up: a device tensor as it is, anything on the host as contiguous uint64"""
+        mem = self._mem(canon)
+        if mem == A.MEM_DEVICE:
+            return canon, canon.numel(), mem
+        canon = np.ascontiguousarray(canon, np.uint64)
+        return canon, canon.size, mem
+
+    def _two_calls(self, fn, args, alloc, n_out=1, cap_at=None, always=False):
+        """The count-then-write protocol of the library, fn(*args, *outputs, capacity, &total): once with null outputs and
+        capacity 0 for the total, then alloc(total) gives the n_out outputs (a tuple) and the call is made again with exactly that
+        capacity -- with a total of 0 only if `always` (the calls whose second pass also writes offsets or summaries).  cap_at: the
+        capacity stands behind the first cap_at outputs, not behind all.  Returns (outputs, total)."""
+        total = C.c_uint64(0)
+        at = n_out if cap_at is None else cap_at
+
+        def call(outs, cap):
+            p = [_ptr(x)[0] for x in outs]
+            self._check(fn(*args, *p[:at], cap, *p[at:], C.byref(total)))
+        call((None,) * n_out, 0)
+        n = int(total.value)
+        outs = alloc(n)
+        if n or always:
+            call(outs, n)
+        return outs, n
+
     def count_non_acgt(self, bases, offsets):
         n = len(offsets) - 1
         mem = self._mem(bases, offsets)
-        if mem == A.MEM_DEVICE:
-            import torch
-            out = torch.zeros(max(n, 1), dtype=torch.int64, device=bases.device)
-        else:
-            out = np.zeros(max(n, 1), np.uint64)
+        out = self._new_like(bases, max(n, 1), np.uint64, "int64")
         self._check(self.L.kmu_count_non_acgt(self.h, _ptr(bases)[0], _ptr(offsets)[0], n, mem, _ptr(out)[0]))
         return out[:n]
 
@@ -434,7 +519,6 @@ class Context:
                     out=None):
         n = len(offsets) - 1
         mem = self._mem(bases, offsets)
-        self._wait_producers(bases)
         hp = A.HashParams(kmer_type, k, fhash, input_kind, mem, 0)
         if out is None:
             if mem == A.MEM_DEVICE:
@@ -470,18 +554,11 @@ class Context:
         n = len(offsets) - 1
         mem = self._mem(bases, offsets)
         hp = A.HashParams(kmer_type, k, fhash, input_kind, mem, 0)
-        cnt = C.c_uint64(0)
         args = (self.h, C.byref(hp), _ptr(bases)[0], _ptr(offsets)[0], _ptr(packed_offsets)[0], n)
-        self._check(self.L.kmu_kmer_distribution(*args, None, None, 0, None, C.byref(cnt)))
-        if mem == A.MEM_DEVICE:
-            import torch
-            kk = torch.zeros(max(cnt.value, 1), dtype=torch.int64, device=bases.device)
-            cc = torch.zeros(max(cnt.value, 1), dtype=torch.int32, device=bases.device)
-            do = torch.zeros(n + 1, dtype=torch.int64, device=bases.device)
-        else:
-            kk, cc, do = np.zeros(max(cnt.value, 1), np.uint64), np.zeros(max(cnt.value, 1), np.uint32), np.zeros(n + 1, np.uint64)
-        self._check(self.L.kmu_kmer_distribution(*args, _ptr(kk)[0], _ptr(cc)[0], cnt.value, _ptr(do)[0], C.byref(cnt)))
-        return kk[:cnt.value], cc[:cnt.value], do
+        (kk, cc, do), cnt = self._two_calls(self.L.kmu_kmer_distribution, args, lambda cnt: (
+            self._new_like(bases, max(cnt, 1), np.uint64, "int64"), self._new_like(bases, max(cnt, 1), np.uint32, "int32"),
+            self._new_like(bases, n + 1, np.uint64, "int64")), n_out=3, cap_at=2, always=True)
+        return kk[:cnt], cc[:cnt], do
 
     def nthash(self, bases, offsets, k, n_hashes=1, mode=A.NTHASH_CANONICAL, table=A.NTHASH_TABLE_2B,
                input_kind=A.INPUT_ASCII, packed_offsets=None, want_strand=True, out=None, strand_out=None):
@@ -511,19 +588,11 @@ class Context:
         """kmu_kmer_hashes_compact: fhash of every k-mer, sequence after sequence, no gaps (uint64 / int64 tensor)"""
         n = len(offsets) - 1
         mem = self._mem(bases, offsets)
-        self._wait_producers(bases)
         hp = A.HashParams(kmer_type, k, fhash, input_kind, mem, 0)
-        cnt = C.c_uint64(0)
-        self._check(self.L.kmu_kmer_hashes_compact(self.h, C.byref(hp), _ptr(bases)[0], _ptr(offsets)[0], _ptr(packed_offsets)[0],
-                                                   n, None, 0, C.byref(cnt)))
-        if mem == A.MEM_DEVICE:
-            import torch
-            out = torch.zeros(max(cnt.value, 1), dtype=torch.int64, device=bases.device)
-        else:
-            out = np.zeros(max(cnt.value, 1), np.uint64)
-        self._check(self.L.kmu_kmer_hashes_compact(self.h, C.byref(hp), _ptr(bases)[0], _ptr(offsets)[0], _ptr(packed_offsets)[0],
-                                                   n, _ptr(out)[0], cnt.value, C.byref(cnt)))
-        return out[:cnt.value]
+        args = (self.h, C.byref(hp), _ptr(bases)[0], _ptr(offsets)[0], _ptr(packed_offsets)[0], n)
+        (out,), cnt = self._two_calls(self.L.kmu_kmer_hashes_compact, args,
+                                      lambda cnt: (self._new_like(bases, max(cnt, 1), np.uint64, "int64"),), always=True)
+        return out[:cnt]
 
     def block_layout(self, offsets_host, block_size):
         n = len(offsets_host) - 1
@@ -537,7 +606,6 @@ class Context:
         """kmu_sketch.  Host (numpy) or device (torch cuda) buffers.  Returns sig [rows, m] (and counts)."""
         n = len(offsets) - 1
         mem = self._mem(bases, offsets)
-        self._wait_producers(bases)
         p = A.SketchParams.from_buffer_copy(params)
         p.mem = mem
         m = p.sketch_size
@@ -640,9 +708,8 @@ class Context:
         hp = A.HashParams(kmer_type, k, fhash, A.INPUT_ASCII, mem, 0)
         moff = self._new_like(bases, n + 1, np.uint64, "int64")
         total = C.c_uint64(0)
-        if not int(bases.shape[0]):  # a batch of empty reads: an empty array has no address worth passing
-            bases = self._new_like(bases, 16, np.uint8, "uint8")
-        args = (self.h, C.byref(hp), _ptr(bases)[0], _ptr(offsets)[0], n, int(w))
+        ptr = self._ptrs(bases)  # (a batch of empty reads has no bases)
+        args = (self.h, C.byref(hp), ptr(bases), _ptr(offsets)[0], n, int(w))
         # (the strand pointer of the count-only call is NULL: an ntHash order is refused only where a strand is asked for)
         self._check(self.L.kmu_read_minimizers(*args, None, None, None, None, 0, _ptr(moff)[0], C.byref(total)))
         m = int(total.value)
@@ -682,7 +749,6 @@ class Context:
         sequence i in hashed[offsets[i]:offsets[i+1]]."""
         n = len(offsets) - 1
         mem = self._mem(hashed, offsets)
-        self._wait_producers(hashed)
         p = A.SketchParams.from_buffer_copy(params)
         p.mem = mem
         m = p.sketch_size
@@ -714,7 +780,6 @@ class Context:
     def sketch_partial(self, bases, offsets, params, packed_offsets=None):
         """kmu_sketch_partial: per-slot minima of these sequences (one row of kmu_sketch_partial_words words)"""
         mem = self._mem(bases, offsets)
-        self._wait_producers(bases)
         p = A.SketchParams.from_buffer_copy(params)
         p.mem = mem
         out = self._partial_buf(p, bases)
@@ -725,7 +790,6 @@ class Context:
     def sketch_hashed_partial(self, hashed, offsets, params):
         """kmu_sketch_hashed_partial: the same for caller-hashed values (disjoint key sets per rank for ProbMinHash)"""
         mem = self._mem(hashed, offsets)
-        self._wait_producers(hashed)
         p = A.SketchParams.from_buffer_copy(params)
         p.mem = mem
         out = self._partial_buf(p, hashed)
@@ -736,7 +800,6 @@ class Context:
     def sketch_merge_partials(self, partials, params):
         """kmu_sketch_merge_partials: [n_parts, words] partial rows -> one signature row"""
         mem = self._mem(partials)
-        self._wait_producers(partials)
         p = A.SketchParams.from_buffer_copy(params)
         p.mem = mem
         m = p.sketch_size
@@ -767,7 +830,6 @@ class Context:
             text = np.frombuffer(bytes(text), np.uint8)
         dev = _is_torch(text) and text.is_cuda
         mem = A.MEM_DEVICE if dev else A.MEM_HOST
-        self._wait_producers(text)
         n = int(text.shape[0])
         info = A.IngestInfo()
         self._check(call(self.h, _ptr(text)[0] if n else None, n, mem, None, 0, None, 0, None, C.byref(info)))
@@ -787,12 +849,6 @@ class Context:
         return res + (idx[:int(info.n_kept)],) if want_index else res
 
     # ---- signature comparison (kmu_compare.hip) ----
-    def _new_like(self, ref, shape, np_dtype, torch_dtype_name):
-        if _is_torch(ref) and ref.is_cuda:
-            import torch
-            return torch.zeros(shape, dtype=getattr(torch, torch_dtype_name), device=ref.device)
-        return np.zeros(shape, np_dtype)
-
     @staticmethod
     def _sig_type_of(sig):
         name = str(sig.dtype).replace("torch.", "")
@@ -802,7 +858,6 @@ class Context:
     def sig_equal_pairs(self, sig_a, sig_b, ia, ib):
         """kmu_sig_equal_pairs: number of equal slots of rows sig_a[ia[p]] and sig_b[ib[p]]."""
         mem = self._mem(sig_a, sig_b, ia, ib)
-        self._wait_producers(sig_a, sig_b)
         n = int(ia.shape[0])
         out = self._new_like(sig_a, max(n, 1), np.uint32, "int32")
         self._check(self.L.kmu_sig_equal_pairs(self.h, _ptr(sig_a)[0], sig_a.shape[0], _ptr(sig_b)[0], sig_b.shape[0],
@@ -813,9 +868,8 @@ class Context:
     def sig_equal_matrix(self, sig_a, sig_b):
         """kmu_sig_equal_matrix: equal-slot counts of every row of sig_a against every row of sig_b."""
         mem = self._mem(sig_a, sig_b)
-        self._wait_producers(sig_a, sig_b)
         out = self._new_like(sig_a, (max(sig_a.shape[0], 1), max(sig_b.shape[0], 1)), np.uint16, "int16")
-        # an empty array has no address worth passing (an empty device tensor's is null): the library reads no row of it
+        # (the output stands in for a side without rows: it is there already, and the library reads no row through it)
         pa = _ptr(sig_a)[0] if sig_a.shape[0] else _ptr(out)[0]
         pb = _ptr(sig_b)[0] if sig_b.shape[0] else _ptr(out)[0]
         self._check(self.L.kmu_sig_equal_matrix(self.h, pa, sig_a.shape[0], pb, sig_b.shape[0],
@@ -828,13 +882,12 @@ class Context:
         exist are idx = KNN_NONE, eq = 0.  Device tensors in give device tensors out (int32 / int16 holding the same
         bits, like the other comparison calls)."""
         mem = self._mem(sig_q, sig_db, group_q, group_db)
-        self._wait_producers(sig_q, sig_db)
         nq, ndb, k = int(sig_q.shape[0]), int(sig_db.shape[0]), int(k)
         if self._sig_type_of(sig_q) != self._sig_type_of(sig_db) or sig_q.shape[1] != sig_db.shape[1]:
             raise ValueError("query and database signatures differ in type or sketch size")
         idx = self._new_like(sig_q, (max(nq, 1), max(k, 1)), np.uint32, "int32")
         eq = self._new_like(sig_q, (max(nq, 1), max(k, 1)), np.uint16, "int16")
-        # an empty array has no address worth passing: the library reads no row of it
+        # (as in sig_equal_matrix, an output stands in for a side without rows)
         pq = _ptr(sig_q)[0] if nq else _ptr(idx)[0]
         pdb = _ptr(sig_db)[0] if ndb else _ptr(idx)[0]
         self._check(self.L.kmu_sig_knn(self.h, pq, nq, pdb, ndb, sig_q.shape[1], self._sig_type_of(sig_q), k,
@@ -844,7 +897,6 @@ class Context:
     def minhash_distance_pairs(self, hashes_a, hashes_b, ia, ib):
         """kmu_minhash_distance_pairs on bottom-k rows: (common, total, i) per pair."""
         mem = self._mem(hashes_a, hashes_b, ia, ib)
-        self._wait_producers(hashes_a, hashes_b)
         n = int(ia.shape[0])
         out = self._new_like(hashes_a, (max(n, 1), 3), np.uint32, "int32")
         self._check(self.L.kmu_minhash_distance_pairs(self.h, _ptr(hashes_a)[0], hashes_a.shape[0], _ptr(hashes_b)[0],
@@ -863,22 +915,15 @@ class Context:
         if hashes_q.shape[1] != hashes_db.shape[1]:
             raise ValueError("query and database rows differ in length")
         m = int(hashes_q.shape[1])
-        none = self._new_like(hashes_q, 2, np.uint64, "int64")  # an empty array has no address worth passing
-        pq = _ptr(hashes_q)[0] if nq else _ptr(none)[0]
-        pdb = _ptr(hashes_db)[0] if ndb else _ptr(none)[0]
-        args = (self.h, pq, nq, pdb, ndb, m, int(n_keys), int(min_common), _ptr(group_q)[0], _ptr(group_db)[0], mem)
+        ptr = self._ptrs(hashes_q)
+        args = (self.h, ptr(hashes_q), nq, ptr(hashes_db), ndb, m, int(n_keys), int(min_common), _ptr(group_q)[0], _ptr(group_db)[0], mem)
         return self._count_then_write(self.L.kmu_anchor_match, args, hashes_q)
 
     def _count_then_write(self, fn, args, like):
-        """the call pair of anchor_match and AnchorIndex.match: fn(*args, pairs_out, dist_out, cap, n_out) once to count, then
-        once with exactly that capacity; (pairs [n, 2], dist [n, 3]) allocated where `like` lives"""
-        total = C.c_uint64(0)
-        self._check(fn(*args, None, None, 0, C.byref(total)))
-        n = int(total.value)
-        pairs = self._new_like(like, (max(n, 1), 2), np.uint32, "int32")
-        dist = self._new_like(like, (max(n, 1), 3), np.uint32, "int32")
-        if n:
-            self._check(fn(*args, _ptr(pairs)[0], _ptr(dist)[0], n, C.byref(total)))
+        """the call pair of anchor_match and AnchorIndex.match, fn(*args, pairs_out, dist_out, cap, n_out): (pairs [n, 2], dist
+        [n, 3]) allocated where `like` lives"""
+        (pairs, dist), n = self._two_calls(fn, args, lambda n: (self._new_like(like, (max(n, 1), 2), np.uint32, "int32"),
+                                                                 self._new_like(like, (max(n, 1), 3), np.uint32, "int32")), n_out=2)
         return pairs[:n], dist[:n]
 
     def anchor_overlaps(self, pairs, dist, row_offsets_q, row_offsets_db=None, strands=2, band=1, min_score=1, upper=False):
@@ -890,31 +935,11 @@ class Context:
         that are numpy arrays are copied up).  Two library calls: one that counts, one with exactly that capacity."""
         mem = self._mem(pairs, dist)
         n_pairs = int(pairs.shape[0])
-
-        def offsets(x):
-            if _is_torch(x):
-                if x.is_cuda == (mem == A.MEM_DEVICE):
-                    return x
-                x = x.cpu().numpy()
-            x = np.ascontiguousarray(np.asarray(x).astype(np.uint64))
-            if mem == A.MEM_DEVICE:
-                import torch
-                return torch.from_numpy(x.view(np.int64)).to(pairs.device)
-            return x
-        off_q = offsets(row_offsets_q)
-        off_db = off_q if row_offsets_db is None or row_offsets_db is row_offsets_q else offsets(row_offsets_db)
-        none = self._new_like(pairs, 2, np.uint32, "int32")  # an empty array has no address worth passing
-        total = C.c_uint64(0)
-        args = (self.h, _ptr(pairs)[0] if n_pairs else _ptr(none)[0], _ptr(dist)[0], n_pairs, _ptr(off_q)[0], int(off_q.shape[0]) - 1,
+        off_q, off_db = self._offsets_pair(row_offsets_q, row_offsets_q if row_offsets_db is None else row_offsets_db, pairs, mem)
+        ptr = self._ptrs(pairs)
+        args = (self.h, ptr(pairs), _ptr(dist)[0], n_pairs, _ptr(off_q)[0], int(off_q.shape[0]) - 1,
                 _ptr(off_db)[0], int(off_db.shape[0]) - 1, int(strands), int(band), int(min_score), A.OVL_UPPER if upper else 0, mem)
-        self._check(self.L.kmu_anchor_overlaps(*args, None, 0, C.byref(total)))
-        n = int(total.value)
-        if mem == A.MEM_DEVICE:
-            out = self._new_like(pairs, (max(n, 1), 8), np.int32, "int32")
-        else:
-            out = np.zeros(max(n, 1), np.dtype(A.OVERLAP_DTYPE))
-        if n:
-            self._check(self.L.kmu_anchor_overlaps(*args, _ptr(out)[0], n, C.byref(total)))
+        (out,), n = self._two_calls(self.L.kmu_anchor_overlaps, args, lambda n: (self._records(pairs, n, A.OVERLAP_DTYPE),))
         return out[:n]
 
     def seed_chains(self, pairs, q, db, span, max_gap, band, min_seeds=1, min_score=0, max_pos=0, upper=False):
@@ -930,22 +955,13 @@ class Context:
         mem = self._mem(pairs, q.pos, q.read, q.strand, db.pos, db.read, db.strand)
         n_pairs = int(pairs.shape[0])
         p = A.ChainParams(int(span), int(max_gap), int(band), int(min_seeds), int(min_score), int(max_pos), A.CHAIN_UPPER if upper else 0)
-        none = self._new_like(pairs, 2, np.uint32, "int32")  # an empty array has no address worth passing
+        ptr = self._ptrs(pairs)
 
         def side(m):
-            n = int(m.pos.shape[0])
-            return (_ptr(m.pos)[0] if n else _ptr(none)[0], _ptr(m.read)[0] if n else _ptr(none)[0],
-                    _ptr(m.strand)[0] if n else None, n, len(m.offsets) - 1)
-        total = C.c_uint64(0)
-        args = (self.h, _ptr(pairs)[0] if n_pairs else _ptr(none)[0], n_pairs, *side(q), *side(db), C.byref(p), mem)
-        self._check(self.L.kmu_seed_chains(*args, None, 0, C.byref(total)))
-        n = int(total.value)
-        if mem == A.MEM_DEVICE:
-            out = self._new_like(pairs, (max(n, 1), 10), np.int32, "int32")
-        else:
-            out = np.zeros(max(n, 1), np.dtype(A.CHAIN_DTYPE))
-        if n:
-            self._check(self.L.kmu_seed_chains(*args, _ptr(out)[0], n, C.byref(total)))
+            n = int(m.pos.shape[0])  # the entries of a side: pos, read and strand have as many
+            return ptr(m.pos), ptr(m.read), _ptr(m.strand)[0] if n else None, n, len(m.offsets) - 1
+        args = (self.h, ptr(pairs), n_pairs, *side(q), *side(db), C.byref(p), mem)
+        (out,), n = self._two_calls(self.L.kmu_seed_chains, args, lambda n: (self._records(pairs, n, A.CHAIN_DTYPE),))
         return out[:n]
 
     def chain_align(self, chains, bases_q, offsets_q, bases_db=None, offsets_db=None, band=64):
@@ -955,36 +971,15 @@ class Context:
         self-join on one batch).  numpy in (a structured A.CHAIN_DTYPE array) gives a structured A.CHAIN_ALN_DTYPE array; torch
         cuda tensors (the int32 [n, 10] records) stay on the device and give an int32 tensor [n, 4] holding the same bits
         (offsets that are numpy arrays are copied up)."""
-        if bases_db is None:
-            bases_db, offsets_db = bases_q, offsets_q
-        elif offsets_db is None:
-            raise ValueError("bases_db without offsets_db")
+        bases_db, offsets_db = self._db_batch(bases_q, offsets_q, bases_db, offsets_db)
         if not _is_torch(chains):
             chains = np.ascontiguousarray(chains)
         mem = self._mem(chains, bases_q, bases_db)
         n = int(chains.shape[0])
-
-        def offsets(x):
-            if _is_torch(x):
-                if x.is_cuda == (mem == A.MEM_DEVICE):
-                    return x
-                x = x.cpu().numpy()
-            x = np.ascontiguousarray(np.asarray(x).astype(np.uint64))
-            if mem == A.MEM_DEVICE:
-                import torch
-                return torch.from_numpy(x.view(np.int64)).to(chains.device)
-            return x
-        off_q = offsets(offsets_q)
-        off_db = off_q if offsets_db is offsets_q else offsets(offsets_db)
+        off_q, off_db = self._offsets_pair(offsets_q, offsets_db, chains, mem)
         p = A.AlignParams(int(band), 0)
-        if mem == A.MEM_DEVICE:
-            out = self._new_like(chains, (max(n, 1), 4), np.int32, "int32")
-        else:
-            out = np.zeros(max(n, 1), np.dtype(A.CHAIN_ALN_DTYPE))
-        none = self._new_like(chains, 16, np.uint8, "uint8")  # an empty array has no address worth passing
-
-        def ptr(x):
-            return _ptr(x)[0] if int(x.shape[0]) else _ptr(none)[0]
+        out = self._records(chains, n, A.CHAIN_ALN_DTYPE)
+        ptr = self._ptrs(chains)
         self._check(self.L.kmu_chain_align(self.h, ptr(chains), n, ptr(bases_q), _ptr(off_q)[0], int(off_q.shape[0]) - 1, ptr(bases_db),
                                            _ptr(off_db)[0], int(off_db.shape[0]) - 1, C.byref(p), mem, _ptr(out)[0]))
         return out[:n]
@@ -998,65 +993,33 @@ class Context:
         direction bits of one batch of chains may take (0: A.CIGAR_TRACE_DEFAULT); a chain whose own bits need more gets its record
         without A.ALN_PATH and no runs.  aln: the records chain_align gave for the same chains at the same band -- ops is then sized
         by 2 edit + 1 runs per chain and the library is called once; without it twice: one call that counts, one that writes."""
-        if bases_db is None:
-            bases_db, offsets_db = bases_q, offsets_q
-        elif offsets_db is None:
-            raise ValueError("bases_db without offsets_db")
+        bases_db, offsets_db = self._db_batch(bases_q, offsets_q, bases_db, offsets_db)
         if not _is_torch(chains):
             chains = np.ascontiguousarray(chains)
         mem = self._mem(chains, bases_q, bases_db)
         n = int(chains.shape[0])
-
-        def offsets(x):
-            if _is_torch(x):
-                if x.is_cuda == (mem == A.MEM_DEVICE):
-                    return x
-                x = x.cpu().numpy()
-            x = np.ascontiguousarray(np.asarray(x).astype(np.uint64))
-            if mem == A.MEM_DEVICE:
-                import torch
-                return torch.from_numpy(x.view(np.int64)).to(chains.device)
-            return x
-        off_q = offsets(offsets_q)
-        off_db = off_q if offsets_db is offsets_q else offsets(offsets_db)
+        off_q, off_db = self._offsets_pair(offsets_q, offsets_db, chains, mem)
         p = A.CigarParams(int(band), 0, int(max_trace_bytes))
-        if mem == A.MEM_DEVICE:
-            out = self._new_like(chains, (max(n, 1), 4), np.int32, "int32")
-        else:
-            out = np.zeros(max(n, 1), np.dtype(A.CHAIN_ALN_DTYPE))
+        out = self._records(chains, n, A.CHAIN_ALN_DTYPE)
         op_off = self._new_like(chains, n + 1, np.uint64, "int64")
-        none = self._new_like(chains, 16, np.uint8, "uint8")  # an empty array has no address worth passing
-
-        def ptr(x):
-            return _ptr(x)[0] if int(x.shape[0]) else _ptr(none)[0]
-        total = C.c_uint64(0)
+        ptr = self._ptrs(chains)
         args = (self.h, ptr(chains), n, ptr(bases_q), _ptr(off_q)[0], int(off_q.shape[0]) - 1, ptr(bases_db), _ptr(off_db)[0],
                 int(off_db.shape[0]) - 1, C.byref(p), mem, _ptr(out)[0], _ptr(op_off)[0])
+
+        def runs(cap):
+            return (self._new_like(chains, max(cap, 1), np.uint32, "int32"),)
         if aln is None:
-            self._check(self.L.kmu_chain_cigar(*args, None, 0, C.byref(total)))
-            cap = int(total.value)
-        else:  # at most 2 edit + 1 runs for a chain that was aligned, none for the others
+            (ops,), total = self._two_calls(self.L.kmu_chain_cigar, args, runs)
+        else:  # one call: at most 2 edit + 1 runs for a chain that was aligned, none for the others
             rec = aln.cpu().numpy().view(np.uint32).reshape(-1, 4) if _is_torch(aln) else np.asarray(aln).view(np.uint32).reshape(-1, 4)
             if rec.shape[0] != n:
                 raise ValueError("aln holds %d records for %d chains" % (rec.shape[0], n))
             done = (rec[:, 3] & A.ALN_DONE) != 0
-            cap = int((2 * rec[done, 0].astype(np.int64) + 1).sum())
-        ops = self._new_like(chains, max(cap, 1), np.uint32, "int32")
-        if aln is not None or cap:
-            self._check(self.L.kmu_chain_cigar(*args, _ptr(ops)[0], cap, C.byref(total)))
-        return out[:n], ops[:int(total.value)], op_off
-
-    def _offsets_like(self, x, ref, mem):
-        """the offsets of a batch as uint64 where the arrays of the call live (int64 holding the same bits for torch)"""
-        if _is_torch(x):
-            if x.is_cuda == (mem == A.MEM_DEVICE):
-                return x
-            x = x.cpu().numpy()
-        x = np.ascontiguousarray(np.asarray(x).astype(np.uint64))
-        if mem == A.MEM_DEVICE:
-            import torch
-            return torch.from_numpy(x.view(np.int64)).to(ref.device)
-        return x
+            cap, written = int((2 * rec[done, 0].astype(np.int64) + 1).sum()), C.c_uint64(0)
+            ops, = runs(cap)
+            self._check(self.L.kmu_chain_cigar(*args, _ptr(ops)[0], cap, C.byref(written)))
+            total = int(written.value)
+        return out[:n], ops[:total], op_off
 
     def chain_pileup(self, chains, aln, ops, op_offsets, bases_q, offsets_q, bases_db=None, offsets_db=None, sides=A.PILE_Q | A.PILE_DB,
                      into=None):
@@ -1068,36 +1031,13 @@ class Context:
         `sides` (A.PILE_Q, A.PILE_DB) leaves out is None.  into=(pile_q, pile_db), or one table for the self-join: tables to
         accumulate into; otherwise they are allocated here, zeroed."""
         own = bases_db is None
-        if own:
-            bases_db, offsets_db = bases_q, offsets_q
-        elif offsets_db is None:
-            raise ValueError("bases_db without offsets_db")
-        if not _is_torch(chains):
-            chains = np.ascontiguousarray(chains)
-        if not _is_torch(aln):
-            aln = np.ascontiguousarray(aln)
-        mem = self._mem(chains, aln, ops, op_offsets, bases_q, bases_db)
-        n = int(chains.shape[0])
-        if int(aln.shape[0]) != n or int(op_offsets.shape[0]) != n + 1:
-            raise ValueError("%d chains need %d alignment records and %d run offsets" % (n, n, n + 1))
-        off_q = self._offsets_like(offsets_q, chains, mem)
-        off_db = off_q if offsets_db is offsets_q else self._offsets_like(offsets_db, chains, mem)
+        bases_db, offsets_db = self._db_batch(bases_q, offsets_q, bases_db, offsets_db)
+        chains, aln, mem, n = self._runs_of_chains(chains, aln, ops, op_offsets, bases_q, bases_db)
+        off_q, off_db = self._offsets_pair(offsets_q, offsets_db, chains, mem)
         sides = int(sides)
-        if into is None:
-            pile_q = self._new_like(chains, (int(off_q[-1]), A.PILE_COLS), np.uint32, "int32") if sides & A.PILE_Q else None
-            if own and pile_q is not None:
-                pile_db = pile_q if sides & A.PILE_DB else None
-            else:
-                pile_db = self._new_like(chains, (int(off_db[-1]), A.PILE_COLS), np.uint32, "int32") if sides & A.PILE_DB else None
-        else:
-            pile_q, pile_db = into if isinstance(into, (tuple, list)) else (into, into)
-            if (sides & A.PILE_Q and pile_q is None) or (sides & A.PILE_DB and pile_db is None):
-                raise ValueError("into lacks the table of a side that is asked for")
+        pile_q, pile_db = self._side_tables(chains, sides, own, into, lambda: int(off_q[-1]), lambda: int(off_db[-1]), A.PILE_COLS)
         p = A.PileupParams(sides)
-        none = self._new_like(chains, 16, np.uint8, "uint8")  # an empty array has no address worth passing
-
-        def ptr(x):
-            return _ptr(x)[0] if int(x.shape[0]) else _ptr(none)[0]
+        ptr = self._ptrs(chains)
         self._check(self.L.kmu_chain_pileup(self.h, ptr(chains), n, ptr(aln), _ptr(op_offsets)[0], ptr(ops), int(ops.shape[0]), ptr(bases_q),
                                             _ptr(off_q)[0], int(off_q.shape[0]) - 1, ptr(bases_db), _ptr(off_db)[0], int(off_db.shape[0]) - 1,
                                             C.byref(p), mem, ptr(pile_q) if sides & A.PILE_Q else None,
@@ -1119,17 +1059,9 @@ class Context:
         if int(pile.shape[0]) != n_bases or int(bases.shape[0]) != n_bases:
             raise ValueError("the batch has %d bases: the table and the bases must have as many rows" % n_bases)
         call = self._new_like(pile, max(n_bases, 1), np.uint8, "uint8") if "call" in want else None
-        if "reads" not in want:
-            reads = None
-        elif mem == A.MEM_DEVICE:
-            reads = self._new_like(pile, (max(n_reads, 1), 8), np.int32, "int32")
-        else:
-            reads = np.zeros(max(n_reads, 1), np.dtype(A.READ_PILE_DTYPE))
+        reads = self._records(pile, n_reads, A.READ_PILE_DTYPE) if "reads" in want else None
         p = A.PileCallParams(int(min_depth), 0)
-        none = self._new_like(pile, 16, np.uint8, "uint8")  # an empty array has no address worth passing
-
-        def ptr(x):
-            return _ptr(x)[0] if int(x.shape[0]) else _ptr(none)[0]
+        ptr = self._ptrs(pile)
         self._check(self.L.kmu_pile_call(self.h, ptr(pile), ptr(bases), _ptr(off)[0], n_reads, C.byref(p), mem, _ptr(call)[0], _ptr(reads)[0]))
         return (call[:n_bases] if call is not None else None), (reads[:n_reads] if reads is not None else None)
 
@@ -1144,11 +1076,7 @@ class Context:
             raise ValueError("the table has %d rows: call must have as many bytes" % n_bases)
         ins_len = self._new_like(pile, max(n_bases, 1), np.uint8, "uint8")
         p = A.InsPlanParams(int(max_ins), 0)
-        none = self._new_like(pile, 16, np.uint8, "uint8")  # an empty array has no address worth passing
-        total = C.c_uint64(0)
-
-        def ptr(x):
-            return _ptr(x)[0] if int(x.shape[0]) else _ptr(none)[0]
+        ptr, total = self._ptrs(pile), C.c_uint64(0)
         self._check(self.L.kmu_pile_ins_plan(self.h, ptr(pile), ptr(call), n_bases, C.byref(p), mem, _ptr(ins_len)[0], C.byref(total)))
         return ins_len[:n_bases], int(total.value)
 
@@ -1161,49 +1089,40 @@ class Context:
         that `sides` leaves out is None.  into=(ins_q, ins_db), or one table for the self-join: tables to accumulate into;
         otherwise they are allocated here, zeroed."""
         own = bases_db is None
+        bases_db, offsets_db = self._db_batch(bases_q, offsets_q, bases_db, offsets_db)
         if own:
-            bases_db, offsets_db, ins_len_db, n_slots_db = bases_q, offsets_q, ins_len_q, n_slots_q
-        elif offsets_db is None:
-            raise ValueError("bases_db without offsets_db")
-        if not _is_torch(chains):
-            chains = np.ascontiguousarray(chains)
-        if not _is_torch(aln):
-            aln = np.ascontiguousarray(aln)
+            ins_len_db, n_slots_db = ins_len_q, n_slots_q
         sides = int(sides)
         if (sides & A.PILE_Q and ins_len_q is None) or (sides & A.PILE_DB and ins_len_db is None):
             raise ValueError("a side that is asked for needs its ins_len and n_slots")
-        mem = self._mem(chains, aln, ops, op_offsets, bases_q, bases_db, ins_len_q, ins_len_db)
-        n = int(chains.shape[0])
-        if int(aln.shape[0]) != n or int(op_offsets.shape[0]) != n + 1:
-            raise ValueError("%d chains need %d alignment records and %d run offsets" % (n, n, n + 1))
-        off_q = self._offsets_like(offsets_q, chains, mem)
-        off_db = off_q if offsets_db is offsets_q else self._offsets_like(offsets_db, chains, mem)
+        chains, aln, mem, n = self._runs_of_chains(chains, aln, ops, op_offsets, bases_q, bases_db, ins_len_q, ins_len_db)
+        off_q, off_db = self._offsets_pair(offsets_q, offsets_db, chains, mem)
         n_slots_q, n_slots_db = int(n_slots_q or 0), int(n_slots_db or 0)
-        if into is None:
-            ins_q = self._new_like(chains, (n_slots_q, A.INS_COLS), np.uint32, "int32") if sides & A.PILE_Q else None
-            if own and ins_q is not None:
-                ins_db = ins_q if sides & A.PILE_DB else None
-            else:
-                ins_db = self._new_like(chains, (n_slots_db, A.INS_COLS), np.uint32, "int32") if sides & A.PILE_DB else None
-        else:
-            ins_q, ins_db = into if isinstance(into, (tuple, list)) else (into, into)
-            if (sides & A.PILE_Q and ins_q is None) or (sides & A.PILE_DB and ins_db is None):
-                raise ValueError("into lacks the table of a side that is asked for")
+        ins_q, ins_db = self._side_tables(chains, sides, own, into, n_slots_q, n_slots_db, A.INS_COLS)
         p = A.PileupParams(sides)
-        none = self._new_like(chains, 16, np.uint8, "uint8")  # an empty array has no address worth passing
-
-        def ptr(x):
-            return _ptr(x)[0] if int(x.shape[0]) else _ptr(none)[0]
+        ptr, spare = self._ptrs(chains), self._ptrs(chains)  # two empty tables are still two tables: a placeholder each
         q, db = bool(sides & A.PILE_Q), bool(sides & A.PILE_DB)
-        spare = self._new_like(chains, 16, np.uint8, "uint8")  # two empty tables are still two tables
 
         def table(x):
-            return _ptr(x)[0] if int(x.shape[0]) else _ptr(none if x is ins_q else spare)[0]
+            return (ptr if x is ins_q else spare)(x)
         self._check(self.L.kmu_chain_pile_ins(self.h, ptr(chains), n, ptr(aln), _ptr(op_offsets)[0], ptr(ops), int(ops.shape[0]), ptr(bases_q),
                                               _ptr(off_q)[0], int(off_q.shape[0]) - 1, ptr(bases_db), _ptr(off_db)[0], int(off_db.shape[0]) - 1,
                                               C.byref(p), mem, ptr(ins_len_q) if q else None, n_slots_q, table(ins_q) if q else None,
                                               ptr(ins_len_db) if db else None, n_slots_db, table(ins_db) if db else None))
         return ins_q, ins_db
+
+    def _consensus_inputs(self, pile, call, ins_len, n_slots, ins, bases, offsets, *more):
+        """the checks pile_consensus and pile_consensus_pos share, `more` being further arrays of the call: (the offsets where the
+        arrays live, n_reads, n_bases, n_slots, mem)"""
+        mem = self._mem(pile, call, ins_len, ins, bases, *more)
+        off = self._offsets_like(offsets, pile, mem)
+        n_bases = int(off[-1])
+        if any(int(x.shape[0]) != n_bases for x in (pile, call, ins_len, bases)):
+            raise ValueError("the batch has %d bases: the table, call, ins_len and the bases must have as many rows" % n_bases)
+        n_slots = int(n_slots)
+        if int(ins.shape[0]) != n_slots:
+            raise ValueError("ins has %d slots, not n_slots = %d" % (int(ins.shape[0]), n_slots))
+        return off, int(off.shape[0]) - 1, n_bases, n_slots, mem
 
     def pile_consensus(self, pile, call, ins_len, n_slots, ins, bases, offsets):
         """kmu_pile_consensus: the corrected reads of a batch -- per base the called letter (the read's own byte where there is no
@@ -1211,24 +1130,11 @@ class Context:
         n_slots: of pile_ins_plan; ins: of chain_pile_ins.  Returns (cons_bases, cons_offsets): a new ASCII batch, uint8 and uint64
         [n_reads + 1] (int64 holding the same bits for torch), where the arrays live.  A row gives at most one byte and its slots, so
         the output is sized by n_bases + n_slots and the library is called once."""
-        mem = self._mem(pile, call, ins_len, ins, bases)
-        off = self._offsets_like(offsets, pile, mem)
-        n_reads = int(off.shape[0]) - 1
-        n_bases = int(off[-1])
-        if any(int(x.shape[0]) != n_bases for x in (pile, call, ins_len, bases)):
-            raise ValueError("the batch has %d bases: the table, call, ins_len and the bases must have as many rows" % n_bases)
-        n_slots = int(n_slots)
-        if int(ins.shape[0]) != n_slots:
-            raise ValueError("ins has %d slots, not n_slots = %d" % (int(ins.shape[0]), n_slots))
+        off, n_reads, n_bases, n_slots, mem = self._consensus_inputs(pile, call, ins_len, n_slots, ins, bases, offsets)
         cons_off = self._new_like(pile, n_reads + 1, np.uint64, "int64")
         cap = n_bases + n_slots
         cons = self._new_like(pile, max(cap, 1), np.uint8, "uint8")
-        p = A.ConsensusParams(0)
-        none = self._new_like(pile, 16, np.uint8, "uint8")  # an empty array has no address worth passing
-        total = C.c_uint64(0)
-
-        def ptr(x):
-            return _ptr(x)[0] if int(x.shape[0]) else _ptr(none)[0]
+        p, ptr, total = A.ConsensusParams(0), self._ptrs(pile), C.c_uint64(0)
         self._check(self.L.kmu_pile_consensus(self.h, ptr(pile), ptr(call), ptr(ins_len), n_slots, ptr(ins), ptr(bases), _ptr(off)[0], n_reads,
                                               C.byref(p), mem, _ptr(cons_off)[0], _ptr(cons)[0], cap, C.byref(total)))
         return cons[:int(total.value)], cons_off
@@ -1250,16 +1156,10 @@ class Context:
         min_span = int(min_depth if min_span is None else min_span)
         cap = min(n_bases // max(int(min_len), 1), n_reads if longest else n_bases)
         seg_off = self._new_like(pile, n_reads + 1, np.uint64, "int64")
-        if mem == A.MEM_DEVICE:
-            segs = self._new_like(pile, (max(cap, 1), 4), np.int32, "int32")
-            reads = self._new_like(pile, (max(n_reads, 1), 8), np.int32, "int32")
-        else:
-            segs = np.zeros(max(cap, 1), np.dtype(A.PILE_SEG_DTYPE))
-            reads = np.zeros(max(n_reads, 1), np.dtype(A.READ_TRIM_DTYPE))
+        segs, reads = self._records(pile, cap, A.PILE_SEG_DTYPE), self._records(pile, n_reads, A.READ_TRIM_DTYPE)
         p = A.PileSegParams(int(min_depth), min_span, int(min_len), A.SEG_LONGEST if longest else 0)
-        none = self._new_like(pile, 16, np.uint8, "uint8")  # an empty array has no address worth passing
-        total = C.c_uint64(0)
-        self._check(self.L.kmu_pile_segments(self.h, _ptr(pile if n_bases else none)[0], _ptr(off)[0], n_reads, C.byref(p), mem,
+        ptr, total = self._ptrs(pile), C.c_uint64(0)
+        self._check(self.L.kmu_pile_segments(self.h, ptr(pile), _ptr(off)[0], n_reads, C.byref(p), mem,
                                              _ptr(seg_off)[0], _ptr(segs)[0], cap, C.byref(total), _ptr(reads)[0]))
         return segs[:int(total.value)], seg_off, reads[:n_reads]
 
@@ -1276,41 +1176,21 @@ class Context:
             begin, end = (np.ascontiguousarray(np.asarray(x).astype(np.uint64)) for x in (begin, end))
         n_bases = int(bases.shape[0])
         out_off = self._new_like(bases, n + 1, np.uint64, "int64")
-        none = self._new_like(bases, 16, np.uint8, "uint8")  # an empty array has no address worth passing
-
-        def ptr(x):
-            return _ptr(x)[0] if int(x.shape[0]) else _ptr(none)[0]
-        total = C.c_uint64(0)
-        self._check(self.L.kmu_extract_ranges(self.h, ptr(bases), n_bases, ptr(begin), ptr(end), n, mem, _ptr(out_off)[0], None, 0, C.byref(total)))
-        cap = int(total.value)
-        out = self._new_like(bases, max(cap, 1), np.uint8, "uint8")
-        if cap:
-            self._check(self.L.kmu_extract_ranges(self.h, ptr(bases), n_bases, ptr(begin), ptr(end), n, mem, _ptr(out_off)[0], _ptr(out)[0], cap,
-                                                  C.byref(total)))
+        ptr = self._ptrs(bases)
+        args = (self.h, ptr(bases), n_bases, ptr(begin), ptr(end), n, mem, _ptr(out_off)[0])
+        (out,), cap = self._two_calls(self.L.kmu_extract_ranges, args, lambda cap: (self._new_like(bases, max(cap, 1), np.uint8, "uint8"),))
         return out[:cap], out_off
 
     def pile_consensus_pos(self, pile, call, ins_len, n_slots, ins, bases, offsets, rows):
         """kmu_pile_consensus_pos: where raw rows land in the corrected batch -- pos[i] is the number of consensus bytes that the
         rows before row rows[i] of the batch produce (rows[i] == n_bases: the total), from the inputs of pile_consensus.  rows =
         offsets gives the cons_offsets of pile_consensus.  Returns pos: uint64 like rows (int64 for torch), where the arrays live."""
-        mem = self._mem(pile, call, ins_len, ins, bases, rows)
-        off = self._offsets_like(offsets, pile, mem)
-        n_reads = int(off.shape[0]) - 1
-        n_bases = int(off[-1])
-        if any(int(x.shape[0]) != n_bases for x in (pile, call, ins_len, bases)):
-            raise ValueError("the batch has %d bases: the table, call, ins_len and the bases must have as many rows" % n_bases)
-        n_slots = int(n_slots)
-        if int(ins.shape[0]) != n_slots:
-            raise ValueError("ins has %d slots, not n_slots = %d" % (int(ins.shape[0]), n_slots))
+        off, n_reads, n_bases, n_slots, mem = self._consensus_inputs(pile, call, ins_len, n_slots, ins, bases, offsets, rows)
         if not _is_torch(rows):
             rows = np.ascontiguousarray(np.asarray(rows).astype(np.uint64))
         n = int(rows.shape[0])
         pos = self._new_like(pile, max(n, 1), np.uint64, "int64")
-        p = A.ConsensusParams(0)
-        none = self._new_like(pile, 16, np.uint8, "uint8")  # an empty array has no address worth passing
-
-        def ptr(x):
-            return _ptr(x)[0] if int(x.shape[0]) else _ptr(none)[0]
+        p, ptr = A.ConsensusParams(0), self._ptrs(pile)
         self._check(self.L.kmu_pile_consensus_pos(self.h, ptr(pile), ptr(call), ptr(ins_len), n_slots, ptr(ins), ptr(bases), _ptr(off)[0], n_reads,
                                                   C.byref(p), mem, ptr(rows), n, _ptr(pos)[0]))
         return pos[:n]
@@ -1329,10 +1209,9 @@ class Context:
         off = self._offsets_like(offsets, chains, mem)
         n_reads = int(off.shape[0]) - 1
         p = A.SgParams(int(min_overlap), int(max_hang), int(int_permille), int(min_identity_permille), int(fuzz), 0)
-        none = self._new_like(chains, 16, np.uint8, "uint8")  # an empty array has no address worth passing
-        args = (self.h, _ptr(chains if n else none)[0], _ptr(aln if n else None)[0] if aln is not None else None, n, _ptr(off)[0], n_reads,
-                C.byref(p), mem)
-        return args, (chains, aln, off, p), mem, n, n_reads
+        ptr = self._ptrs(chains)
+        args = (self.h, ptr(chains), _ptr(aln if n else None)[0], n, _ptr(off)[0], n_reads, C.byref(p), mem)
+        return args, (chains, aln, off, p, ptr), mem, n, n_reads
 
     def sg_classify(self, chains, aln, offsets, min_overlap=500, max_hang=1000, int_permille=250, min_identity_permille=0, fuzz=10):
         """kmu_sg_classify: the class of every chain record of a self-join (A.SG_SKIP .. A.SG_DOVETAIL; include/kmu.h has the rules)
@@ -1343,10 +1222,7 @@ class Context:
         args, keep, mem, n, n_reads = self._sg_inputs(chains, aln, offsets, min_overlap, max_hang, int_permille, min_identity_permille, fuzz)
         like = keep[0]
         classes = self._new_like(like, max(n, 1), np.uint8, "uint8")
-        if mem == A.MEM_DEVICE:
-            reads = self._new_like(like, (max(n_reads, 1), 4), np.int32, "int32")
-        else:
-            reads = np.zeros(max(n_reads, 1), np.dtype(A.SG_READ_DTYPE))
+        reads = self._records(like, n_reads, A.SG_READ_DTYPE)
         self._check(self.L.kmu_sg_classify(*args, _ptr(classes)[0], _ptr(reads)[0]))
         return classes[:n], reads[:n_reads]
 
@@ -1360,18 +1236,9 @@ class Context:
         counts, one with exactly that capacity."""
         args, keep, mem, n, n_reads = self._sg_inputs(chains, aln, offsets, min_overlap, max_hang, int_permille, min_identity_permille, fuzz)
         like = keep[0]
-        total = C.c_uint64(0)
-        self._check(self.L.kmu_sg_graph(*args, None, None, None, 0, None, C.byref(total)))
-        cap = int(total.value)
-        classes = self._new_like(like, max(n, 1), np.uint8, "uint8")
-        arc_off = self._new_like(like, 2 * n_reads + 1, np.uint64, "int64")
-        if mem == A.MEM_DEVICE:
-            reads = self._new_like(like, (max(n_reads, 1), 4), np.int32, "int32")
-            arcs = self._new_like(like, (max(cap, 1), 8), np.int32, "int32")
-        else:
-            reads = np.zeros(max(n_reads, 1), np.dtype(A.SG_READ_DTYPE))
-            arcs = np.zeros(max(cap, 1), np.dtype(A.SG_ARC_DTYPE))
-        self._check(self.L.kmu_sg_graph(*args, _ptr(classes)[0], _ptr(reads)[0], _ptr(arcs)[0], cap, _ptr(arc_off)[0], C.byref(total)))
+        (classes, reads, arcs, arc_off), cap = self._two_calls(self.L.kmu_sg_graph, args, lambda cap: (
+            self._new_like(like, max(n, 1), np.uint8, "uint8"), self._records(like, n_reads, A.SG_READ_DTYPE),
+            self._records(like, cap, A.SG_ARC_DTYPE), self._new_like(like, 2 * n_reads + 1, np.uint64, "int64")), n_out=4, cap_at=3, always=True)
         return arcs[:cap], arc_off, classes[:n], reads[:n_reads]
 
     def sg_unitigs(self, arcs, reads, offsets):
@@ -1392,17 +1259,9 @@ class Context:
         n_reads = int(off.shape[0]) - 1
         if reads is not None and int(reads.shape[0]) != n_reads:
             raise ValueError("%d reads need as many summaries" % n_reads)
-        if mem == A.MEM_DEVICE:
-            unitigs = self._new_like(arcs, (max(n_reads, 1), 8), np.int32, "int32")
-            path = self._new_like(arcs, (max(n_reads, 1), 4), np.int32, "int32")
-            place = self._new_like(arcs, (max(n_reads, 1), 4), np.int32, "int32")
-        else:
-            unitigs = np.zeros(max(n_reads, 1), np.dtype(A.SG_UNITIG_DTYPE))
-            path = np.zeros(max(n_reads, 1), np.dtype(A.SG_STEP_DTYPE))
-            place = np.zeros(max(n_reads, 1), np.dtype(A.SG_PLACE_DTYPE))
-        none = self._new_like(arcs, 16, np.uint8, "uint8")  # an empty array has no address worth passing
-        n_steps, total = C.c_uint64(0), C.c_uint64(0)
-        self._check(self.L.kmu_sg_unitigs(self.h, _ptr(arcs if n else none)[0], n, _ptr(reads if n_reads else None)[0], _ptr(off)[0], n_reads, mem,
+        unitigs, path, place = (self._records(arcs, n_reads, dt) for dt in (A.SG_UNITIG_DTYPE, A.SG_STEP_DTYPE, A.SG_PLACE_DTYPE))
+        ptr, n_steps, total = self._ptrs(arcs), C.c_uint64(0), C.c_uint64(0)
+        self._check(self.L.kmu_sg_unitigs(self.h, ptr(arcs), n, _ptr(reads if n_reads else None)[0], _ptr(off)[0], n_reads, mem,
                                           _ptr(unitigs)[0], _ptr(path)[0], _ptr(place)[0], C.byref(n_steps), C.byref(total)))
         return unitigs[:int(total.value)], path[:int(n_steps.value)], place[:n_reads]
 
@@ -1421,15 +1280,9 @@ class Context:
         n, n_reads = int(arcs.shape[0]), int(n_reads)
         if reads is not None and int(reads.shape[0]) != n_reads:
             raise ValueError("%d reads need as many summaries" % n_reads)
-        if mem == A.MEM_DEVICE:
-            arcs_out = self._new_like(arcs, (max(n, 1), 8), np.int32, "int32")
-            reads_out = self._new_like(arcs, (max(n_reads, 1), 4), np.int32, "int32")
-        else:
-            arcs_out = np.zeros(max(n, 1), np.dtype(A.SG_ARC_DTYPE))
-            reads_out = np.zeros(max(n_reads, 1), np.dtype(A.SG_READ_DTYPE))
-        none = self._new_like(arcs, 16, np.uint8, "uint8")  # an empty array has no address worth passing
-        p, stats = A.SgCleanParams(int(max_tip_reads), int(max_bubble_reads), 0, 0), A.SgCleanStats()
-        self._check(self.L.kmu_sg_clean(self.h, _ptr(arcs if n else none)[0], n, _ptr(reads if n_reads else None)[0], n_reads, C.byref(p), mem,
+        arcs_out, reads_out = self._records(arcs, n, A.SG_ARC_DTYPE), self._records(arcs, n_reads, A.SG_READ_DTYPE)
+        p, stats, ptr = A.SgCleanParams(int(max_tip_reads), int(max_bubble_reads), 0, 0), A.SgCleanStats(), self._ptrs(arcs)
+        self._check(self.L.kmu_sg_clean(self.h, ptr(arcs), n, _ptr(reads if n_reads else None)[0], n_reads, C.byref(p), mem,
                                         _ptr(arcs_out)[0], _ptr(reads_out)[0], C.byref(stats)))
         return arcs_out[:n], reads_out[:n_reads], {name: int(getattr(stats, name)) for name in A.SG_CLEAN_STATS}
 
@@ -1456,14 +1309,7 @@ class Context:
         n_reads = int(off.shape[0]) - 1
         if int(place.shape[0]) != n_reads:
             raise ValueError("%d reads need as many places" % n_reads)
-        if mem == A.MEM_DEVICE:
-            out = self._new_like(place, (max(n_reads, 1), 10), np.int32, "int32")
-        else:
-            out = np.zeros(max(n_reads, 1), np.dtype(A.CHAIN_DTYPE))
-        none = self._new_like(place, 16, np.uint8, "uint8")  # an empty array has no address worth passing
-
-        def ptr(x):
-            return _ptr(x)[0] if int(x.shape[0]) else _ptr(none)[0]
+        out, ptr = self._records(place, n_reads, A.CHAIN_DTYPE), self._ptrs(place)
         p, stats, total = A.UmParams(0, 0), A.UmStats(), C.c_uint64(0)
         self._check(self.L.kmu_sg_unitig_chains(self.h, ptr(unitigs), n, ptr(path), n_steps, ptr(place), ptr(chains) if n_chains else None,
                                                 ptr(classes) if n_chains else None, n_chains, _ptr(off)[0], n_reads, C.byref(p), mem,
@@ -1482,17 +1328,10 @@ class Context:
         n, n_steps = int(unitigs.shape[0]), int(path.shape[0])
         off = self._offsets_like(offsets, bases, mem)
         n_reads = int(off.shape[0]) - 1
-        seq_off = self._new_like(bases, n + 1, np.uint64, "int64")
-        none = self._new_like(bases, 16, np.uint8, "uint8")  # an empty array has no address worth passing
-
-        def ptr(x):
-            return _ptr(x)[0] if int(x.shape[0]) else _ptr(none)[0]
+        ptr = self._ptrs(bases)
         args = (self.h, ptr(unitigs), n, ptr(path), n_steps, ptr(bases), _ptr(off)[0], n_reads, mem)
-        total = C.c_uint64(0)
-        self._check(self.L.kmu_sg_unitig_seqs(*args, None, None, 0, C.byref(total)))
-        cap = int(total.value)
-        seq = self._new_like(bases, max(cap, 1), np.uint8, "uint8")
-        self._check(self.L.kmu_sg_unitig_seqs(*args, _ptr(seq_off)[0], _ptr(seq)[0], cap, C.byref(total)))
+        (seq_off, seq), cap = self._two_calls(self.L.kmu_sg_unitig_seqs, args, lambda cap: (
+            self._new_like(bases, n + 1, np.uint64, "int64"), self._new_like(bases, max(cap, 1), np.uint8, "uint8")), n_out=2, always=True)
         return seq[:cap], seq_off
 
     def _components(self, call, like, n_nodes, want, count):
@@ -1529,8 +1368,8 @@ class Context:
             raise ValueError("edges must be a [n, stride] array of uint32 / int32 words")
         n_edges, stride = int(edges.shape[0]), int(edges.shape[1])
         mem = self._mem(edges)
-        none = self._new_like(edges, 2, np.uint32, "int32")  # an empty array has no address worth passing
-        pe = _ptr(edges)[0] if n_edges else _ptr(none)[0]
+        ptr = self._ptrs(edges)
+        pe = ptr(edges)
 
         def call(*outs):
             return self.L.kmu_components(self.h, int(n_nodes), pe, n_edges, stride, int(weight_at), int(min_weight), mem, *outs)
@@ -1543,8 +1382,8 @@ class Context:
         mem = self._mem(idx, eq)
         if eq is not None and tuple(eq.shape) != (n, k):
             raise ValueError("idx and eq differ in shape")
-        none = self._new_like(idx, 2, np.uint32, "int32")
-        pi = _ptr(idx)[0] if n * k else _ptr(none)[0]
+        ptr = self._ptrs(idx)
+        pi = ptr(idx, n * k)
 
         def call(*outs):
             return self.L.kmu_components_knn(self.h, n, pi, _ptr(eq)[0], k, int(min_eq), mem, *outs)
@@ -1562,27 +1401,17 @@ class Context:
         return KFilter(self, kmer_type, k, n_cells, n_hashes)
 
 
-class AnchorIndex:
-    """kmu_anchor_index: ndb bottom-k rows (numpy, or a torch cuda tensor), their n_keys smallest hashes sorted into buckets, and
-    optionally the group of every row, kept on the device: built once, matched against by any number of query batches, and the
-    owner of the bucket sizes behind the repeat mask `max_occ` (include/kmu.h has the rules).  The index copies what it is given;
-    close it before its context."""
+class _Handle:
+    """An object of the library that lives on a context: `ctx`, its entry points `L`, the handle `h` and `_destroy`, the name of the
+    call that frees it.  Close it (or leave its `with` block) before its context; closing it afterwards, or twice, is silent."""
+    _destroy = None
 
-    def __init__(self, ctx, hashes_db, n_keys=1, group_db=None):
-        self.ctx = ctx
-        self.L = ctx.L
-        self.h = None
-        mem = ctx._mem(hashes_db, group_db)
-        ndb, self.m = int(hashes_db.shape[0]), int(hashes_db.shape[1])
-        none = ctx._new_like(hashes_db, 2, np.uint64, "int64")  # an empty array has no address worth passing
-        h = C.c_void_p()
-        ctx._check(self.L.kmu_anchor_index_create(ctx.h, _ptr(hashes_db)[0] if ndb else _ptr(none)[0], ndb, self.m, int(n_keys),
-                                                  _ptr(group_db)[0], mem, C.byref(h)))
-        self.h = h
+    def __init__(self, ctx):
+        self.ctx, self.L, self.h = ctx, ctx.L, None
 
     def close(self):
-        if getattr(self, "h", None) and self.ctx.h:
-            self.L.kmu_anchor_index_destroy(self.h)
+        if getattr(self, "h", None) and getattr(self.ctx, "h", None):
+            getattr(self.L, self._destroy)(self.h)
         self.h = None
 
     def __del__(self):
@@ -1596,6 +1425,23 @@ class AnchorIndex:
 
     def __exit__(self, *exc):
         self.close()
+
+
+class AnchorIndex(_Handle):
+    """kmu_anchor_index: ndb bottom-k rows (numpy, or a torch cuda tensor), their n_keys smallest hashes sorted into buckets, and
+    optionally the group of every row, kept on the device: built once, matched against by any number of query batches, and the
+    owner of the bucket sizes behind the repeat mask `max_occ` (include/kmu.h has the rules).  The index copies what it is given;
+    close it before its context."""
+
+    _destroy = "kmu_anchor_index_destroy"
+
+    def __init__(self, ctx, hashes_db, n_keys=1, group_db=None):
+        super().__init__(ctx)
+        mem = ctx._mem(hashes_db, group_db)
+        ndb, self.m = int(hashes_db.shape[0]), int(hashes_db.shape[1])
+        ptr, h = ctx._ptrs(hashes_db), C.c_void_p()
+        ctx._check(self.L.kmu_anchor_index_create(ctx.h, ptr(hashes_db), ndb, self.m, int(n_keys), _ptr(group_db)[0], mem, C.byref(h)))
+        self.h = h
 
     def info(self):
         """kmu_anchor_index_info as a dict: ndb, m, n_keys, has_groups, n_entries, n_distinct, max_occupancy, device_bytes"""
@@ -1620,36 +1466,25 @@ class AnchorIndex:
         nq = int(hashes_q.shape[0])
         if int(hashes_q.shape[1]) != self.m:
             raise ValueError("query rows and the index's rows differ in length")
-        none = ctx._new_like(hashes_q, 2, np.uint64, "int64")  # an empty array has no address worth passing
-        args = (self.h, _ptr(hashes_q)[0] if nq else _ptr(none)[0], nq, _ptr(group_q)[0], int(min_common), int(max_occ), mem)
+        ptr = ctx._ptrs(hashes_q)
+        args = (self.h, ptr(hashes_q), nq, _ptr(group_q)[0], int(min_common), int(max_occ), mem)
         return ctx._count_then_write(self.L.kmu_anchor_index_match, args, hashes_q)
 
 
-class Counter:
+class Counter(_Handle):
     """kmu_counter: exact canonical k-mer multiplicities on the device (KmerCountT contract)."""
+    _destroy = "kmu_count_destroy"
 
     def __init__(self, ctx, kmer_type, k, counter_bits=8, capacity_hint=1 << 20, distributed=False, owner_hash=False,
                  hint_occurrences=False):
         """hint_occurrences: capacity_hint counts k-mer occurrences; the first add sizes the table from the duplication it measures"""
-        self.ctx = ctx
-        self.L = ctx.L
+        super().__init__(ctx)
         flags = ((A.COUNT_DISTRIBUTED if distributed else 0) | (A.COUNT_OWNER_HASH if owner_hash else 0)
                  | (A.COUNT_HINT_OCCURRENCES if hint_occurrences else 0))
         self.p = A.CountParams(kmer_type, k, counter_bits, flags, capacity_hint)
         h = C.c_void_p()
         ctx._check(self.L.kmu_count_create(ctx.h, C.byref(self.p), C.byref(h)))
         self.h = h
-
-    def close(self):
-        if getattr(self, "h", None) and getattr(self.ctx, "h", None):
-            self.L.kmu_count_destroy(self.h)
-        self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def reset(self):
         self.ctx._check(self.L.kmu_count_reset(self.h))
@@ -1660,13 +1495,11 @@ class Counter:
 
     def add_reads(self, bases, offsets, input_kind=A.INPUT_ASCII, packed_offsets=None):
         mem = Context._mem(bases, offsets)
-        self.ctx._wait_producers(bases)
         self.ctx._check(self.L.kmu_count_add_reads(self.h, _ptr(bases)[0], _ptr(offsets)[0], _ptr(packed_offsets)[0],
                                                    len(offsets) - 1, input_kind, mem))
 
     def add_kmers(self, canon):
         mem = Context._mem(canon)
-        self.ctx._wait_producers(canon)
         n = canon.numel() if _is_torch(canon) else canon.size
         self.ctx._check(self.L.kmu_count_add_kmers(self.h, _ptr(canon)[0], n, mem))
 
@@ -1674,7 +1507,6 @@ class Counter:
         """kmu_count_add_reads_filtered: the occurrences of the reads whose k-mer the prefilter puts in class 2 (may occur twice
         or more) go into the table; returns their number.  A failed call raises with `n_passed` on the exception."""
         mem = Context._mem(bases, offsets)
-        self.ctx._wait_producers(bases)
         n = C.c_uint64(0)
         try:
             self.ctx._check(self.L.kmu_count_add_reads_filtered(self.h, kfilter.h, _ptr(bases)[0], _ptr(offsets)[0], len(offsets) - 1, mem,
@@ -1685,15 +1517,8 @@ class Counter:
         return n.value
 
     def query(self, canon):
-        mem = Context._mem(canon)
-        if mem == A.MEM_DEVICE:
-            import torch
-            n = canon.numel()
-            out = torch.zeros(max(n, 1), dtype=torch.int32, device=canon.device)
-        else:
-            canon = np.ascontiguousarray(canon, np.uint64)
-            n = canon.size
-            out = np.zeros(max(n, 1), np.uint32)
+        canon, n, mem = self.ctx._kmer_values(canon)
+        out = self.ctx._new_like(canon, max(n, 1), np.uint32, "int32")
         self.ctx._check(self.L.kmu_count_query(self.h, _ptr(canon)[0], n, mem, _ptr(out)[0]))
         return out[:n]
 
@@ -1730,12 +1555,9 @@ class Counter:
         return v.value
 
     def dump(self, min_count=2):
-        n = C.c_uint64(0)
-        self.ctx._check(self.L.kmu_count_dump(self.h, min_count, None, None, 0, C.byref(n)))
-        k = np.zeros(max(n.value, 1), np.uint64)
-        c = np.zeros(max(n.value, 1), np.uint32)
-        self.ctx._check(self.L.kmu_count_dump(self.h, min_count, _ptr(k)[0], _ptr(c)[0], n.value, C.byref(n)))
-        return k[:n.value], c[:n.value]
+        (k, c), n = self.ctx._two_calls(self.L.kmu_count_dump, (self.h, min_count),
+                                        lambda n: (np.zeros(max(n, 1), np.uint64), np.zeros(max(n, 1), np.uint32)), n_out=2, always=True)
+        return k[:n], c[:n]
 
     def eliminate_once(self):
         """kmu_count_eliminate_once: drop the k-mers seen once"""
@@ -1745,21 +1567,11 @@ class Counter:
         """kmu_count_once_positions: (canonical k-mers, numseq, numkmer) of the occurrences whose k-mer has count 1, in
         (sequence, position) order; numpy arrays for host input, torch cuda tensors for device input"""
         mem = Context._mem(bases, offsets)
-        self.ctx._wait_producers(bases)
-        n = C.c_uint64(0)
-        nseq = len(offsets) - 1
-        self.ctx._check(self.L.kmu_count_once_positions(self.h, _ptr(bases)[0], _ptr(offsets)[0], nseq, mem, None, None, None, 0,
-                                                        C.byref(n)))
-        if mem == A.MEM_DEVICE:
-            import torch
-            k = torch.zeros(max(n.value, 1), dtype=torch.int64, device=bases.device)
-            s = torch.zeros(max(n.value, 1), dtype=torch.int32, device=bases.device)
-            p = torch.zeros(max(n.value, 1), dtype=torch.int32, device=bases.device)
-        else:
-            k, s, p = np.zeros(max(n.value, 1), np.uint64), np.zeros(max(n.value, 1), np.uint32), np.zeros(max(n.value, 1), np.uint32)
-        self.ctx._check(self.L.kmu_count_once_positions(self.h, _ptr(bases)[0], _ptr(offsets)[0], nseq, mem, _ptr(k)[0], _ptr(s)[0],
-                                                        _ptr(p)[0], n.value, C.byref(n)))
-        return k[:n.value], s[:n.value], p[:n.value]
+        new, args = self.ctx._new_like, (self.h, _ptr(bases)[0], _ptr(offsets)[0], len(offsets) - 1, mem)
+        (k, s, p), n = self.ctx._two_calls(self.L.kmu_count_once_positions, args, lambda n: (
+            new(bases, max(n, 1), np.uint64, "int64"), new(bases, max(n, 1), np.uint32, "int32"), new(bases, max(n, 1), np.uint32, "int32")),
+            n_out=3, always=True)
+        return k[:n], s[:n], p[:n]
 
     def histogram(self, n_bins=None, device=None):
         """kmu_count_histogram: hist[v] = distinct k-mers whose reported count is v, the last bin collecting every count
@@ -1784,7 +1596,6 @@ class Counter:
         stats: a numpy array of A.READ_ABUNDANCE_DTYPE records for host input; for device input a torch uint8 cuda tensor
         [n_seq, 32] holding the same records (`.cpu().numpy().view(A.READ_ABUNDANCE_DTYPE).reshape(-1)`)."""
         mem = Context._mem(bases, offsets)
-        self.ctx._wait_producers(bases)
         nseq = len(offsets) - 1
         counts = stats = None
         if mem == A.MEM_DEVICE:
@@ -1830,7 +1641,6 @@ class Counter:
         counter call; bounds[n_parts + 1] (numpy) delimits the groups."""
         import torch
         mem = Context._mem(bases, offsets)
-        self.ctx._wait_producers(bases)
         ptr = C.c_void_p()
         bounds = np.zeros(n_parts + 1, np.uint64)
         self.ctx._check(self.L.kmu_count_extract_by_owner(self.h, _ptr(bases)[0], _ptr(offsets)[0], len(offsets) - 1, mem,
@@ -1855,7 +1665,6 @@ class Counter:
         counter call; bounds[n_parts + 1] (numpy, in records); kmers[n_parts] the k-mers every group holds."""
         import torch
         mem = Context._mem(bases, offsets)
-        self.ctx._wait_producers(bases)
         ptr = C.c_void_p()
         bounds = np.zeros(n_parts + 1, np.uint64)
         kmers = np.zeros(n_parts, np.uint64)
@@ -1873,13 +1682,11 @@ class Counter:
     def add_superkmers(self, records):
         """kmu_count_add_superkmers: records as an [n, 3] int32 / uint32 array (numpy or torch cuda tensor)"""
         mem = Context._mem(records)
-        self.ctx._wait_producers(records)
         n = (records.numel() if _is_torch(records) else records.size) // 3
         self.ctx._check(self.L.kmu_count_add_superkmers(self.h, _ptr(records)[0], n, mem))
 
     def merge_entries(self, kmers, counts):
         mem = Context._mem(kmers, counts)
-        self.ctx._wait_producers(kmers)
         n = kmers.numel() if _is_torch(kmers) else kmers.size
         self.ctx._check(self.L.kmu_count_merge_entries(self.h, _ptr(kmers)[0], _ptr(counts)[0], n, mem))
 
@@ -1893,35 +1700,17 @@ def kfilter_cells_for(expected_distinct, bits_per_kmer=16):
     return int(load().kmu_kfilter_cells_for(int(expected_distinct), int(bits_per_kmer)))
 
 
-class KFilter:
+class KFilter(_Handle):
     """kmu_kfilter: the count prefilter -- n_cells cells {A, B} that tell the canonical k-mers added once (class 1) from those that
     may have been added twice or more (class 2); include/kmu.h has the structure.  Close it before its context."""
+    _destroy = "kmu_kfilter_destroy"
 
     def __init__(self, ctx, kmer_type, k, n_cells, n_hashes=4):
-        self.ctx = ctx
-        self.L = ctx.L
-        self.h = None
+        super().__init__(ctx)
         self.p = A.KFilterParams(kmer_type, k, n_hashes, 0, n_cells)
         h = C.c_void_p()
         ctx._check(self.L.kmu_kfilter_create(ctx.h, C.byref(self.p), C.byref(h)))
         self.h = h
-
-    def close(self):
-        if getattr(self, "h", None) and getattr(self.ctx, "h", None):
-            self.L.kmu_kfilter_destroy(self.h)
-        self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
 
     def reset(self):
         self.ctx._check(self.L.kmu_kfilter_reset(self.h))
@@ -1938,15 +1727,8 @@ class KFilter:
 
     def query(self, canon):
         """kmu_kfilter_query: the class (0 never added, 1 added once, 2 maybe more often) of every value; uint8"""
-        mem = Context._mem(canon)
-        if mem == A.MEM_DEVICE:
-            import torch
-            n = canon.numel()
-            out = torch.zeros(max(n, 1), dtype=torch.uint8, device=canon.device)
-        else:
-            canon = np.ascontiguousarray(canon, np.uint64)
-            n = canon.size
-            out = np.zeros(max(n, 1), np.uint8)
+        canon, n, mem = self.ctx._kmer_values(canon)
+        out = self.ctx._new_like(canon, max(n, 1), np.uint8, "uint8")
         self.ctx._check(self.L.kmu_kfilter_query(self.h, _ptr(canon)[0], n, mem, _ptr(out)[0]))
         return out[:n]
 
@@ -1978,11 +1760,7 @@ class KFilter:
         a numpy array for host input, a torch cuda tensor for device input.  Two library calls: the size, then the k-mers."""
         n = self.n_passing(bases, offsets)
         mem = Context._mem(bases, offsets)
-        if mem == A.MEM_DEVICE:
-            import torch
-            k = torch.zeros(max(n, 1), dtype=torch.int64, device=bases.device)
-        else:
-            k = np.zeros(max(n, 1), np.uint64)
+        k = self.ctx._new_like(bases, max(n, 1), np.uint64, "int64")
         got = C.c_uint64(0)
         self.ctx._check(self.L.kmu_kfilter_select_reads(self.h, _ptr(bases)[0], _ptr(offsets)[0], len(offsets) - 1, mem, _ptr(k)[0], n,
                                                         C.byref(got)))

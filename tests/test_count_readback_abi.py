@@ -55,3 +55,20 @@ def test_record_layout():
     for name, _ in A.ReadAbundance._fields_:
         assert dt.fields[name][1] == getattr(A.ReadAbundance, name).offset, name
         assert dt.fields[name][0].itemsize == getattr(A.ReadAbundance, name).size, name
+
+
+def test_counter_closes_at_the_end_of_a_with_block():
+    """Counter has the life cycle of the other handles: `with` closes it once, and a close after the context's is silent"""
+    import types
+    from kmerutils_amd import lib
+    freed = []
+    ctx = types.SimpleNamespace(h=1, L=types.SimpleNamespace(kmu_count_destroy=freed.append))
+    counter = object.__new__(lib.Counter)
+    counter.ctx, counter.L, counter.h = ctx, ctx.L, 7
+    with counter as same:
+        assert same is counter and not freed
+    assert counter.h is None and freed == [7]
+    counter.close()
+    counter.h, ctx.h = 8, None
+    counter.close()
+    assert counter.h is None and freed == [7]

@@ -266,6 +266,22 @@ def test_device_mode_equals_host_mode(ctx):
     assert empty.shape == want.shape and not empty.any()
 
 
+def test_two_empty_batches_on_the_device(ctx):
+    """two batches of empty reads as device tensors: every input has no rows, and the two empty tables are still two tables"""
+    import torch
+
+    def dev(shape, dtype):
+        return torch.zeros(shape, dtype=dtype, device="cuda")
+    chains, aln, ops, op_off = dev((0, 10), torch.int32), dev((0, 4), torch.int32), dev(0, torch.int32), dev(1, torch.int64)
+    bases, off_q, off_db, ins_len = dev(0, torch.uint8), dev(3, torch.int64), np.zeros(2, np.uint64), dev(0, torch.uint8)
+    q, db = ctx.chain_pile_ins(chains, aln, ops, op_off, bases, off_q, ins_len, 0, bases.clone(), off_db, ins_len.clone(), 0)
+    assert q is not db and all(t.is_cuda and t.dtype == torch.int32 and tuple(t.shape) == (0, A.INS_COLS) for t in (q, db))
+    one = ctx.chain_pile_ins(chains, aln, ops, op_off, bases, off_q, ins_len, 0)
+    assert one[0] is one[1] and tuple(one[0].shape) == (0, A.INS_COLS)
+    pile = ctx.chain_pileup(chains, aln, ops, op_off, bases, off_q)
+    assert pile[0] is pile[1] and pile[0].is_cuda and pile[0].dtype == torch.int32 and tuple(pile[0].shape) == (0, A.PILE_COLS)
+
+
 # ---- capacity -----------------------------------------------------------------------------------------------------------------------
 def raw_consensus(ctx, pile, call, ins_len, n_slots, ins, bases, offsets, cons_off, cons, cap):
     """kmu_pile_consensus on host arrays as they are; returns (status, total)"""
