@@ -497,6 +497,72 @@ template <class Seq> std::vector<const Seq *> pointers(const std::vector<Seq> &v
     return p;
 }
 
+// ---- the marshalling steps of the wrappers below, each written once; where kmerutils_amd/lib.py has the same step, under its name
+// there -------------------------------------------------------------------------------------------------
+
+/// An empty vector has no address worth passing.  ptr(v): the base of v, or a spare element of its type where v is empty, for
+/// the arrays the C-ABI requires (lib.py's _ptrs); opt(v): the base of v, or null where v is empty, for the optional ones.
+/// An output of zero elements is sized exactly and passed through ptr like any other array.
+template <class T> inline T spare_element{};
+template <class T> const T *ptr(const std::vector<T> &v) { return v.empty() ? &spare_element<T> : v.data(); }
+template <class T> T *ptr(std::vector<T> &v) { return v.empty() ? &spare_element<T> : v.data(); }
+template <class T> const T *opt(const std::vector<T> &v) { return v.empty() ? nullptr : v.data(); }
+template <class T> T *opt(std::vector<T> &v) { return v.empty() ? nullptr : v.data(); }
+
+/// Count, allocate, call again (lib.py's _two_calls).  `call(write, cap, &total)` runs once with write == false and cap 0 -- it
+/// passes null outputs then -- `alloc(total)` sizes the outputs exactly, and the second call gets that capacity.  `always`:
+/// whether the second call is made for a total of 0 (it is where it also writes offsets or summaries).  Returns the total.
+template <class Alloc, class Call> uint64_t two_calls(Context &ctx, bool always, Alloc alloc, Call call) {
+    uint64_t total = 0;
+    ctx.check(call(false, uint64_t(0), &total));
+    alloc(total);
+    if (total || always) ctx.check(call(true, total, &total));
+    return total;
+}
+
+/// the batch of a wrapper that returns host arrays: unpacked, and refused where its sequences lie on the device
+inline Batch host_batch(const char *who, const Batch &batch) {
+    Batch b = unpacked(batch);
+    if (b.on_device()) throw std::invalid_argument(std::string(who) + " returns host arrays: it needs the sequences in host memory");
+    return b;
+}
+
+/// the two batches of a chain call, as host_batch gives them; without a db batch (the self-join) db() is q (lib.py's _db_batch)
+struct Sides {
+    Batch q, own_db;
+    bool two;
+    const Batch &db() const { return two ? own_db : q; }
+};
+inline Sides host_sides(const char *who, const Batch &q, const Batch *db) {
+    Sides s{unpacked(q), db ? unpacked(*db) : Batch(), db != nullptr};
+    if (s.q.on_device() || s.db().on_device())
+        throw std::invalid_argument(std::string(who) + " returns host arrays: it needs the sequences in host memory");
+    return s;
+}
+
+/// the number of reads behind the offsets of a batch, which have one entry more
+inline uint32_t n_reads_of(const char *who, const std::vector<uint64_t> &offsets) {
+    if (offsets.empty()) throw std::invalid_argument(std::string(who) + ": the offsets of a batch have at least one entry");
+    return uint32_t(offsets.size() - 1);
+}
+
+template <class Kmer> kmu_hash_params hash_params(size_t k, int fhash, int input_kind) {
+    kmu_hash_params hp{};
+    hp.kmer_type = Kmer::kmu_type;
+    hp.kmer_size = int32_t(k);
+    hp.fhash = fhash;
+    hp.input_kind = input_kind;
+    hp.mem = KMU_MEM_HOST;
+    return hp;
+}
+
+/// the values a counter or a prefilter takes for a list of k-mers
+template <class Kmer> std::vector<uint64_t> compressed_values(const std::vector<Kmer> &kmers) {
+    std::vector<uint64_t> keys;
+    for (const Kmer &k : kmers) keys.push_back(uint64_t(k.get_compressed_value()));
+    return keys;
+}
+
 template <class Sig> constexpr int sig_type_of() {
     if constexpr (std::is_same_v<Sig, uint32_t>) return KMU_SIG_U32;
     else if constexpr (std::is_same_v<Sig, uint64_t>) return KMU_SIG_U64;
@@ -533,14 +599,9 @@ inline kmu_sketch_params sketch_params(int algo, int kmer_type, size_t k, size_t
 /// raw `.0` of every k-mer of every sequence, generated on the device (KmerSeqIterator::next, kmergenerator.rs:75-106)
 template <class Kmer> std::vector<std::vector<Kmer>> device_kmers(Context &ctx, const Batch &b, size_t k) {
     if (b.on_device()) throw std::invalid_argument("k-mer lists / host closures need the sequences in host memory");
-    kmu_hash_params hp{};
-    hp.kmer_type = Kmer::kmu_type;
-    hp.kmer_size = int32_t(k);
-    hp.fhash = KMU_FHASH_IDENTITY_RAW;
-    hp.input_kind = b.input_kind;
-    hp.mem = KMU_MEM_HOST;
-    std::vector<uint64_t> raw(std::max<uint64_t>(b.offsets.back(), 1), 0);
-    ctx.check(kmu_kmer_hashes(ctx.raw(), &hp, b.bytes.data(), b.offsets.data(), b.packed_ptr(), b.n(), raw.data()));
+    const kmu_hash_params hp = hash_params<Kmer>(k, KMU_FHASH_IDENTITY_RAW, b.input_kind);
+    std::vector<uint64_t> raw(b.offsets.back(), 0);
+    ctx.check(kmu_kmer_hashes(ctx.raw(), &hp, b.bytes.data(), b.offsets.data(), b.packed_ptr(), b.n(), ptr(raw)));
     std::vector<std::vector<Kmer>> out(b.n());
     for (uint32_t i = 0; i < b.n(); i++) {
         const uint64_t len = b.offsets[i + 1] - b.offsets[i];
@@ -581,11 +642,10 @@ size_t run_sketch_flat(Context &ctx, const Batch &b, int algo, size_t k, size_t 
             for (const Kmer &km : seq) hashed.push_back(fhash(km));
             off.push_back(hashed.size());
         }
-        if (hashed.empty()) hashed.push_back(0);
         kmu_sketch_params p = sketch_params(algo, Kmer::kmu_type, k, m, sig_type_of<Sig>(), hasher, KMU_FHASH_IDENTITY_RAW, 0,
                                             mode, KMU_INPUT_ASCII);
         p.flags = flags;
-        ctx.check(kmu_sketch_hashed(ctx.raw(), &p, hashed.data(), off.data(), b.n(), flat.data(), nullptr));
+        ctx.check(kmu_sketch_hashed(ctx.raw(), &p, ptr(hashed), off.data(), b.n(), flat.data(), nullptr));
     }
     return rows;
 }
@@ -603,9 +663,9 @@ std::vector<std::vector<Sig>> run_sketch_groups(Context &ctx, const std::vector<
     const Batch b = gather(all);
     kmu_sketch_params p = sketch_params(algo, Kmer::kmu_type, k, m, sig_type, hasher, int(fhash), 0, KMU_MODE_ALL_SEQS, b.input_kind);
     p.flags = flags;
-    std::vector<Sig> flat(std::max<size_t>(groups.size(), 1) * m);
+    std::vector<Sig> flat(groups.size() * m);
     ctx.check(kmu_sketch_groups(ctx.raw(), &p, b.bytes.data(), b.offsets.data(), b.packed_ptr(), b.n(), group_offsets.data(),
-                                uint32_t(groups.size()), flat.data()));
+                                uint32_t(groups.size()), ptr(flat)));
     return split_rows(flat, groups.size(), m);
 }
 
@@ -638,12 +698,7 @@ template <class Kmer> class KmerGenerator {
     template <class Seq> std::vector<Kmer> generate_kmer_in_range(const Seq &seq, size_t begin, size_t end) const {
         if (begin >= end) throw KmuError(KMU_E_BAD_ARG, "KmerGenerationPattern bad range for kmer iteration");  // kmergenerator.rs:284-286
         const detail::Batch b = detail::gather(std::vector<const Seq *>{&seq});
-        kmu_hash_params hp{};
-        hp.kmer_type = Kmer::kmu_type;
-        hp.kmer_size = int32_t(k_);
-        hp.fhash = KMU_FHASH_IDENTITY_RAW;
-        hp.input_kind = b.input_kind;
-        hp.mem = KMU_MEM_HOST;
+        const kmu_hash_params hp = detail::hash_params<Kmer>(k_, KMU_FHASH_IDENTITY_RAW, b.input_kind);
         std::vector<uint64_t> raw(std::max<uint64_t>(b.offsets.back(), 1), 0);
         const uint64_t rb = begin, re = end;
         ctx_.check(kmu_kmer_hashes_range(ctx_.raw(), &hp, b.bytes.data(), b.offsets.data(), b.packed_ptr(), 1, &rb, &re, raw.data()));
@@ -655,12 +710,7 @@ template <class Kmer> class KmerGenerator {
     /// counted on the device (kmu_kmer_distribution); returned as (k-mer, count) pairs in no particular order
     template <class Seq> std::vector<std::pair<Kmer, uint32_t>> generate_weighted_kmer(const Seq &seq) const {
         const detail::Batch b = detail::gather(std::vector<const Seq *>{&seq});
-        kmu_hash_params hp{};
-        hp.kmer_type = Kmer::kmu_type;
-        hp.kmer_size = int32_t(k_);
-        hp.fhash = KMU_FHASH_IDENTITY_RAW;
-        hp.input_kind = b.input_kind;
-        hp.mem = KMU_MEM_HOST;
+        const kmu_hash_params hp = detail::hash_params<Kmer>(k_, KMU_FHASH_IDENTITY_RAW, b.input_kind);
         uint64_t n = 0;
         ctx_.check(kmu_kmer_distribution(ctx_.raw(), &hp, b.bytes.data(), b.offsets.data(), b.packed_ptr(), 1, nullptr, nullptr, 0,
                                          nullptr, &n));
@@ -883,23 +933,24 @@ template <class Kmer, class S> class HyperLogLogSketch : public SeqSketcherT<Kme
     }
     std::vector<std::vector<S>> sketch_compressedkmer_seqs_groups(const std::vector<std::vector<const Seq *>> &groups,
                                                                   FHash fhash) const override {
-        kmu_hll_params hp{hll_.b, hll_.a, hll_.q, 0};
-        ctx_.check(kmu_set_hll_params(ctx_.raw(), &hp));
-        const int sig = std::is_same_v<S, uint16_t> ? KMU_SIG_U16 : std::is_same_v<S, uint32_t> ? KMU_SIG_U32 : KMU_SIG_U64;
+        set_hll_params();
         return detail::run_sketch_groups<Kmer, S>(ctx_, groups, KMU_ALGO_HLL, params_.get_kmer_size(), hll_.m, sig, KMU_HASHER_NOHASH, fhash);
     }
 
   private:
-    std::vector<std::vector<S>> run(const std::vector<const Seq *> &vseq, FHash fhash, int mode) const {
+    static constexpr int sig = std::is_same_v<S, uint16_t> ? KMU_SIG_U16 : std::is_same_v<S, uint32_t> ? KMU_SIG_U32 : KMU_SIG_U64;
+    void set_hll_params() const {
         kmu_hll_params hp{hll_.b, hll_.a, hll_.q, 0};
         ctx_.check(kmu_set_hll_params(ctx_.raw(), &hp));
+    }
+    std::vector<std::vector<S>> run(const std::vector<const Seq *> &vseq, FHash fhash, int mode) const {
+        set_hll_params();
         const detail::Batch b = detail::gather(vseq);
-        const int sig = std::is_same_v<S, uint16_t> ? KMU_SIG_U16 : std::is_same_v<S, uint32_t> ? KMU_SIG_U32 : KMU_SIG_U64;
         kmu_sketch_params p = detail::sketch_params(KMU_ALGO_HLL, Kmer::kmu_type, params_.get_kmer_size(), hll_.m, sig,
                                                     KMU_HASHER_NOHASH, int(fhash), 0, mode, b.input_kind);
         const size_t rows = mode == KMU_MODE_ALL_SEQS ? 1 : b.n();
-        std::vector<S> flat(std::max<size_t>(rows, 1) * hll_.m);
-        ctx_.check(kmu_sketch(ctx_.raw(), &p, b.bytes.data(), b.offsets.data(), b.packed_ptr(), b.n(), nullptr, flat.data(), nullptr));
+        std::vector<S> flat(rows * hll_.m);
+        ctx_.check(kmu_sketch(ctx_.raw(), &p, b.bytes.data(), b.offsets.data(), b.packed_ptr(), b.n(), nullptr, detail::ptr(flat), nullptr));
         return detail::split_rows(flat, rows, hll_.m);
     }
     SeqSketcherParams params_;
@@ -1079,13 +1130,10 @@ struct Neighbour {
 template <class D>
 void sig_knn(const D *sig_q, size_t nq, const D *sig_db, size_t ndb, size_t m, size_t k, const uint32_t *group_q,
              const uint32_t *group_db, std::vector<uint32_t> &idx, std::vector<uint16_t> &eq, Context &ctx = Context::global()) {
-    idx.assign(std::max<size_t>(nq * k, 1), KMU_KNN_NONE);
-    eq.assign(std::max<size_t>(nq * k, 1), 0);
-    const D none{};
-    ctx.check(kmu_sig_knn(ctx.raw(), nq ? sig_q : &none, uint32_t(nq), ndb ? sig_db : &none, uint32_t(ndb), uint32_t(m),
-                          detail::sig_type_of<D>(), uint32_t(k), group_q, group_db, KMU_MEM_HOST, idx.data(), eq.data()));
-    idx.resize(nq * k);
-    eq.resize(nq * k);
+    idx.assign(nq * k, KMU_KNN_NONE);
+    eq.assign(nq * k, 0);
+    ctx.check(kmu_sig_knn(ctx.raw(), nq ? sig_q : &detail::spare_element<D>, uint32_t(nq), ndb ? sig_db : &detail::spare_element<D>, uint32_t(ndb),
+                          uint32_t(m), detail::sig_type_of<D>(), uint32_t(k), group_q, group_db, KMU_MEM_HOST, detail::ptr(idx), detail::ptr(eq)));
 }
 
 /// The exact answer to the query an HNSW index under DistHamming / DistBlockSketched approximates
@@ -1265,6 +1313,16 @@ struct MinHashDist {   // minhash.rs:134-190: containment, jaccard, common, tota
     uint64_t common, total;
 };
 
+namespace detail {
+/// kmu_minhash_distance_pairs on the one pair of two padded sketches of one length
+inline MinHashDist minhash_pair(Context &ctx, const std::vector<uint64_t> &ha, const std::vector<uint64_t> &hb) {
+    const uint32_t zero = 0;
+    uint32_t out[3] = {0, 0, 0};
+    ctx.check(kmu_minhash_distance_pairs(ctx.raw(), ha.data(), 1, hb.data(), 1, uint32_t(ha.size()), &zero, &zero, 1, KMU_MEM_HOST, out));
+    return MinHashDist{double(out[0]) / double(out[2]), double(out[0]) / double(out[1]), out[0], out[1]};
+}
+}  // namespace detail
+
 /// MinInvHashCountKmer<Kmer, H>: the `size` smallest int64_hash(value) with u16 multiplicities (minhash.rs:194-290)
 template <class Kmer> class MinInvHashCountKmer {
   public:
@@ -1308,12 +1366,7 @@ template <class Kmer>
 MinHashDist mininvhash_distance(const MinInvHashCountKmer<Kmer> &a, const MinInvHashCountKmer<Kmer> &b,
                                 Context &ctx = Context::global()) {
     if (a.size() != b.size()) throw std::invalid_argument("sketches of different sizes");
-    auto ha = a.get_hashes_padded(), hb = b.get_hashes_padded();
-    const uint32_t zero = 0;
-    uint32_t out[3] = {0, 0, 0};
-    ctx.check(kmu_minhash_distance_pairs(ctx.raw(), ha.data(), 1, hb.data(), 1, uint32_t(a.size()), &zero, &zero, 1,
-                                         KMU_MEM_HOST, out));
-    return MinHashDist{double(out[0]) / double(out[2]), double(out[0]) / double(out[1]), out[0], out[1]};
+    return detail::minhash_pair(ctx, a.get_hashes_padded(), b.get_hashes_padded());
 }
 
 /// HashCount<u32> of seqminhash.rs: a kept hash and its multiplicity
@@ -1376,11 +1429,7 @@ inline MinHashDist minhash_distance(const std::vector<HashCount> &sk1, const std
     std::vector<uint64_t> ha(std::max<size_t>(m, 1), UINT64_MAX), hb(std::max<size_t>(m, 1), UINT64_MAX);
     for (size_t i = 0; i < sk1.size(); i++) ha[i] = sk1[i].hashed;
     for (size_t i = 0; i < sk2.size(); i++) hb[i] = sk2[i].hashed;
-    const uint32_t zero = 0;
-    uint32_t out[3] = {0, 0, 0};
-    ctx.check(kmu_minhash_distance_pairs(ctx.raw(), ha.data(), 1, hb.data(), 1, uint32_t(ha.size()), &zero, &zero, 1,
-                                         KMU_MEM_HOST, out));
-    return MinHashDist{double(out[0]) / double(out[2]), double(out[0]) / double(out[1]), out[0], out[1]};
+    return detail::minhash_pair(ctx, ha, hb);
 }
 
 // =====================================================================================================================
@@ -1482,16 +1531,11 @@ struct AnchorMatch {
 };
 
 namespace detail {
-/// The call pair of anchor matching: `call(pairs_out, dist_out, cap, n_out)` once to count, then once with exactly that capacity.
-/// Returns the number of pairs; `pairs` holds 2 and `dist` 3 values for each.
-template <class Call>
-uint64_t count_then_write(Context &ctx, std::vector<uint32_t> &pairs, std::vector<uint32_t> &dist, Call call) {
-    uint64_t total = 0;
-    ctx.check(call(nullptr, nullptr, 0, &total));
-    pairs.assign(size_t(total) * 2, 0);
-    dist.assign(size_t(total) * 3, 0);
-    if (total) ctx.check(call(pairs.data(), dist.data(), total, &total));
-    return total;
+/// two_calls of anchor matching: `call(pairs_out, dist_out, cap, n_out)`; `pairs` holds 2 and `dist` 3 values for each pair
+template <class Call> uint64_t match_calls(Context &ctx, std::vector<uint32_t> &pairs, std::vector<uint32_t> &dist, Call call) {
+    return two_calls(
+        ctx, false, [&](uint64_t total) { pairs.assign(size_t(total) * 2, 0), dist.assign(size_t(total) * 3, 0); },
+        [&](bool write, uint64_t cap, uint64_t *total) { return call(write ? pairs.data() : nullptr, write ? dist.data() : nullptr, cap, total); });
 }
 }  // namespace detail
 
@@ -1506,9 +1550,8 @@ class AnchorIndex {
         : ctx_(&ctx), m_(m) {
         if (hashes_db.size() < size_t(ndb) * m || (!group_db.empty() && group_db.size() < ndb))
             throw std::invalid_argument("AnchorIndex: hashes_db holds ndb x m hashes, group_db ndb groups");
-        const uint64_t none[2] = {UINT64_MAX, UINT64_MAX}; // an empty vector has no address worth passing
-        ctx.check(kmu_anchor_index_create(ctx.raw(), ndb ? hashes_db.data() : none, ndb, m, n_keys,
-                                          group_db.empty() ? nullptr : group_db.data(), KMU_MEM_HOST, &ix_));
+        ctx.check(kmu_anchor_index_create(ctx.raw(), ndb ? hashes_db.data() : &detail::spare_element<uint64_t>, ndb, m, n_keys, detail::opt(group_db),
+                                          KMU_MEM_HOST, &ix_));
     }
     ~AnchorIndex() { kmu_anchor_index_destroy(ix_); }
     AnchorIndex(AnchorIndex &&o) noexcept : ctx_(o.ctx_), ix_(o.ix_), m_(o.m_) { o.ix_ = nullptr; }
@@ -1534,10 +1577,9 @@ class AnchorIndex {
                    uint32_t max_occ, std::vector<uint32_t> &pairs, std::vector<uint32_t> &dist) const {
         if (hashes_q.size() < size_t(nq) * m_ || (!group_q.empty() && group_q.size() < nq))
             throw std::invalid_argument("AnchorIndex::match: hashes_q holds nq x m hashes, group_q nq groups");
-        const uint64_t none[2] = {UINT64_MAX, UINT64_MAX};
-        const uint64_t *q = nq ? hashes_q.data() : none;
-        const uint32_t *g = group_q.empty() ? nullptr : group_q.data();
-        return detail::count_then_write(*ctx_, pairs, dist, [&](uint32_t *p, uint32_t *d, uint64_t cap, uint64_t *n) {
+        const uint64_t *q = nq ? hashes_q.data() : &detail::spare_element<uint64_t>;
+        const uint32_t *g = detail::opt(group_q);
+        return detail::match_calls(*ctx_, pairs, dist, [&](uint32_t *p, uint32_t *d, uint64_t cap, uint64_t *n) {
             return kmu_anchor_index_match(ix_, q, nq, g, min_common, max_occ, KMU_MEM_HOST, p, d, cap, n);
         });
     }
@@ -1549,6 +1591,20 @@ class AnchorIndex {
 };
 
 namespace detail {
+/// the slices of `reads` as bottom-k rows of m hashes (UINT64_MAX padding; one padding row where there is no slice), and the read
+/// of every slice as its group
+template <class Kmer> std::vector<uint64_t> anchor_rows(const std::vector<ReadAnchors<Kmer>> &reads, size_t m, std::vector<uint32_t> &group) {
+    for (size_t i = 0; i < reads.size(); i++) group.insert(group.end(), reads[i].anchors.size(), uint32_t(i));
+    std::vector<uint64_t> h(std::max<size_t>(group.size(), 1) * m, UINT64_MAX);
+    size_t r = 0;
+    for (const ReadAnchors<Kmer> &ra : reads)
+        for (const SliceAnchor<Kmer> &s : ra.anchors) {
+            for (size_t t = 0; t < s.minhash.size() && t < m; t++) h[r * m + t] = s.minhash[t].hashed;
+            r++;
+        }
+    return h;
+}
+
 /// the window pairs of `rows` bottom-k rows against themselves, slices of one group never paired: kmu_anchor_match, or with a repeat
 /// mask (max_occ > 0) an AnchorIndex of the rows
 inline void anchor_self_join(const std::vector<uint64_t> &h, uint32_t rows, uint32_t m, uint32_t n_keys, uint32_t min_common,
@@ -1559,7 +1615,7 @@ inline void anchor_self_join(const std::vector<uint64_t> &h, uint32_t rows, uint
         else { pairs.clear(); dist.clear(); }
         return;
     }
-    count_then_write(ctx, pairs, dist, [&](uint32_t *p, uint32_t *d, uint64_t cap, uint64_t *n) {
+    match_calls(ctx, pairs, dist, [&](uint32_t *p, uint32_t *d, uint64_t cap, uint64_t *n) {
         return kmu_anchor_match(ctx.raw(), h.data(), rows, h.data(), rows, m, n_keys, min_common, group.data(), group.data(), KMU_MEM_HOST,
                                 p, d, cap, n);
     });
@@ -1577,15 +1633,10 @@ std::vector<AnchorMatch> match_read_anchors(const std::vector<ReadAnchors<Kmer>>
                                             Context &ctx = Context::global()) {
     const size_t m = params.get_nbkmer();
     std::vector<const SliceAnchor<Kmer> *> slices;
+    for (const ReadAnchors<Kmer> &ra : reads)
+        for (const SliceAnchor<Kmer> &s : ra.anchors) slices.push_back(&s);
     std::vector<uint32_t> group;
-    for (size_t i = 0; i < reads.size(); i++)
-        for (const SliceAnchor<Kmer> &s : reads[i].anchors) {
-            slices.push_back(&s);
-            group.push_back(uint32_t(i));
-        }
-    std::vector<uint64_t> h(std::max<size_t>(slices.size(), 1) * m, UINT64_MAX);
-    for (size_t r = 0; r < slices.size(); r++)
-        for (size_t t = 0; t < slices[r]->minhash.size() && t < m; t++) h[r * m + t] = slices[r]->minhash[t].hashed;
+    const std::vector<uint64_t> h = detail::anchor_rows(reads, m, group);
     const uint32_t rows = uint32_t(slices.size());
     std::vector<uint32_t> pairs, dist;
     detail::anchor_self_join(h, rows, uint32_t(m), n_keys, min_common, group, max_occ, ctx, pairs, dist);
@@ -1608,15 +1659,14 @@ inline std::vector<kmu_overlap> anchor_overlaps(const std::vector<uint32_t> &pai
     if (!dist.empty() && dist.size() / 3 != pairs.size() / 2) throw std::invalid_argument("anchor_overlaps: dist holds 3 values per pair");
     const uint64_t n_pairs = pairs.size() / 2;
     const uint32_t flags = upper ? KMU_OVL_UPPER : 0u, nq = uint32_t(row_offsets_q.size() - 1), ndb = uint32_t(row_offsets_db.size() - 1);
-    const uint32_t none[2] = {0, 0}; // an empty vector has no address worth passing
-    const uint32_t *pp = n_pairs ? pairs.data() : none, *pd = dist.empty() ? nullptr : dist.data();
-    uint64_t total = 0;
-    ctx.check(kmu_anchor_overlaps(ctx.raw(), pp, pd, n_pairs, row_offsets_q.data(), nq, row_offsets_db.data(), ndb, strands, band,
-                                  min_score, flags, KMU_MEM_HOST, nullptr, 0, &total));
-    std::vector<kmu_overlap> out(static_cast<size_t>(total));
-    if (total)
-        ctx.check(kmu_anchor_overlaps(ctx.raw(), pp, pd, n_pairs, row_offsets_q.data(), nq, row_offsets_db.data(), ndb, strands, band,
-                                      min_score, flags, KMU_MEM_HOST, out.data(), total, &total));
+    const uint32_t *pp = n_pairs ? pairs.data() : &detail::spare_element<uint32_t>;
+    std::vector<kmu_overlap> out;
+    detail::two_calls(
+        ctx, false, [&](uint64_t total) { out.resize(size_t(total)); },
+        [&](bool, uint64_t cap, uint64_t *total) {
+            return kmu_anchor_overlaps(ctx.raw(), pp, detail::opt(dist), n_pairs, row_offsets_q.data(), nq, row_offsets_db.data(), ndb, strands, band,
+                                       min_score, flags, KMU_MEM_HOST, detail::opt(out), cap, total);
+        });
     return out;
 }
 
@@ -1642,19 +1692,10 @@ std::vector<kmu_overlap> read_overlap_records(const std::vector<ReadAnchors<Kmer
                                               uint32_t max_occ, Context &ctx) {
     const size_t m = params.get_nbkmer();
     std::vector<uint64_t> row_offsets(reads.size() + 1, 0);
+    for (size_t i = 0; i < reads.size(); i++) row_offsets[i + 1] = row_offsets[i] + reads[i].anchors.size();
     std::vector<uint32_t> group;
-    for (size_t i = 0; i < reads.size(); i++) {
-        row_offsets[i + 1] = row_offsets[i] + reads[i].anchors.size();
-        group.insert(group.end(), reads[i].anchors.size(), uint32_t(i));
-    }
+    const std::vector<uint64_t> h = anchor_rows(reads, m, group);
     const uint32_t rows = uint32_t(group.size());
-    std::vector<uint64_t> h(std::max<size_t>(rows, 1) * m, UINT64_MAX);
-    size_t r = 0;
-    for (const ReadAnchors<Kmer> &ra : reads)
-        for (const SliceAnchor<Kmer> &s : ra.anchors) {
-            for (size_t t = 0; t < s.minhash.size() && t < m; t++) h[r * m + t] = s.minhash[t].hashed;
-            r++;
-        }
     std::vector<uint32_t> pairs, dist;
     anchor_self_join(h, rows, uint32_t(m), n_keys, min_common, group, max_occ, ctx, pairs, dist);
     return anchor_overlaps(pairs, dist, row_offsets, row_offsets, strands, band, min_score, true, ctx);
@@ -1687,15 +1728,11 @@ struct Components {
 namespace detail {
 template <class Call> Components components_call(Context &ctx, uint32_t n_nodes, Call call) {
     Components c;
-    const size_t n = std::max<size_t>(n_nodes, 1); // an empty vector has no address worth passing
-    c.label.assign(n, 0);
-    c.cluster.assign(n, 0);
-    c.size.assign(n, 0);
-    c.members.assign(n, 0);
-    ctx.check(call(c.label.data(), c.cluster.data(), c.size.data(), c.members.data(), &c.n_components));
-    c.label.resize(n_nodes);
-    c.cluster.resize(n_nodes);
-    c.members.resize(n_nodes);
+    c.label.assign(n_nodes, 0);
+    c.cluster.assign(n_nodes, 0);
+    c.size.assign(n_nodes, 0);
+    c.members.assign(n_nodes, 0);
+    ctx.check(call(ptr(c.label), ptr(c.cluster), ptr(c.size), ptr(c.members), &c.n_components));
     c.size.resize(c.n_components);
     return c;
 }
@@ -1707,11 +1744,9 @@ template <class Call> Components components_call(Context &ctx, uint32_t n_nodes,
 inline Components components(const std::vector<uint32_t> &edges, uint32_t n_nodes, uint32_t stride = 2, uint32_t weight_at = 0,
                              uint32_t min_weight = 0, Context &ctx = Context::global()) {
     if (stride < 2 || edges.size() % stride != 0) throw std::invalid_argument("components: edges holds records of stride >= 2 words");
-    const uint32_t none[2] = {0, 0};
     const uint64_t n_edges = edges.size() / stride;
     return detail::components_call(ctx, n_nodes, [&](uint32_t *l, uint32_t *c, uint32_t *s, uint32_t *m, uint32_t *n) {
-        return kmu_components(ctx.raw(), n_nodes, n_edges ? edges.data() : none, n_edges, stride, weight_at, min_weight, KMU_MEM_HOST, l, c,
-                              s, m, n);
+        return kmu_components(ctx.raw(), n_nodes, detail::ptr(edges), n_edges, stride, weight_at, min_weight, KMU_MEM_HOST, l, c, s, m, n);
     });
 }
 
@@ -1719,10 +1754,9 @@ inline Components components(const std::vector<uint32_t> &edges, uint32_t n_node
 inline Components components(const std::vector<kmu_overlap> &records, uint32_t n_nodes, uint32_t min_weight = 0, bool by_votes = false,
                              Context &ctx = Context::global()) {
     static_assert(sizeof(kmu_overlap) == 32, "a record is 8 words");
-    const kmu_overlap none{};
     return detail::components_call(ctx, n_nodes, [&](uint32_t *l, uint32_t *c, uint32_t *s, uint32_t *m, uint32_t *n) {
-        return kmu_components(ctx.raw(), n_nodes, reinterpret_cast<const uint32_t *>(records.empty() ? &none : records.data()),
-                              records.size(), 8, by_votes ? 5 : 4, min_weight, KMU_MEM_HOST, l, c, s, m, n);
+        return kmu_components(ctx.raw(), n_nodes, reinterpret_cast<const uint32_t *>(detail::ptr(records)), records.size(), 8, by_votes ? 5 : 4,
+                              min_weight, KMU_MEM_HOST, l, c, s, m, n);
     });
 }
 
@@ -1732,10 +1766,8 @@ inline Components components_knn(const std::vector<uint32_t> &idx, const std::ve
                                  uint32_t min_eq = 0, Context &ctx = Context::global()) {
     if (idx.size() != size_t(n_nodes) * k) throw std::invalid_argument("components_knn: idx holds n_nodes x k entries");
     if (!eq.empty() && eq.size() != idx.size()) throw std::invalid_argument("components_knn: eq holds one value per entry of idx");
-    const uint32_t none[2] = {0, 0};
     return detail::components_call(ctx, n_nodes, [&](uint32_t *l, uint32_t *c, uint32_t *s, uint32_t *m, uint32_t *n) {
-        return kmu_components_knn(ctx.raw(), n_nodes, idx.empty() ? none : idx.data(), eq.empty() ? nullptr : eq.data(), k, min_eq,
-                                  KMU_MEM_HOST, l, c, s, m, n);
+        return kmu_components_knn(ctx.raw(), n_nodes, detail::ptr(idx), detail::opt(eq), k, min_eq, KMU_MEM_HOST, l, c, s, m, n);
     });
 }
 
@@ -1769,13 +1801,8 @@ ReadClusters read_clusters(const std::vector<ReadAnchors<Kmer>> &reads, const An
 template <class Kmer>
 std::vector<uint64_t> kmer_hashes(const detail::Batch &b, size_t k, FHash fhash, Context &ctx = Context::global()) {
     if (b.on_device()) throw std::invalid_argument("kmer_hashes returns host arrays: it needs the sequences in host memory");
-    kmu_hash_params hp{};
-    hp.kmer_type = Kmer::kmu_type;
-    hp.kmer_size = int32_t(k);
-    hp.fhash = int(fhash);
-    hp.input_kind = b.input_kind;
-    hp.mem = KMU_MEM_HOST;
-    std::vector<uint64_t> out(std::max<uint64_t>(b.offsets.back(), 1), 0);
+    const kmu_hash_params hp = detail::hash_params<Kmer>(k, int(fhash), b.input_kind);
+    std::vector<uint64_t> out(std::max<uint64_t>(b.offsets.back(), 1), 0);   // (a batch without bases gets one entry: kept as it was)
     ctx.check(kmu_kmer_hashes(ctx.raw(), &hp, b.bytes.data(), b.offsets.data(), b.packed_ptr(), b.n(), out.data()));
     return out;
 }
@@ -1805,26 +1832,19 @@ struct Minimizers {
 template <class Kmer>
 Minimizers read_minimizers(const detail::Batch &batch, size_t k, uint32_t w, FHash fhash = FHash::canon_invhash,
                            Context &ctx = Context::global()) {
-    const detail::Batch b = detail::unpacked(batch);
-    if (b.on_device()) throw std::invalid_argument("read_minimizers returns host arrays: it needs the sequences in host memory");
+    const detail::Batch b = detail::host_batch("read_minimizers", batch);
     const bool with_strand = fhash != FHash::canon_nthash && fhash != FHash::canon_nthash_8b;
     const uint64_t cap = minimizer_layout(b, k, w).back();
-    kmu_hash_params hp{};
-    hp.kmer_type = Kmer::kmu_type;
-    hp.kmer_size = int32_t(k);
-    hp.fhash = int(fhash);
-    hp.input_kind = KMU_INPUT_ASCII;
-    hp.mem = KMU_MEM_HOST;
+    const kmu_hash_params hp = detail::hash_params<Kmer>(k, int(fhash), KMU_INPUT_ASCII);
     Minimizers m;
-    const size_t room = size_t(std::max<uint64_t>(cap, 1)); // an empty vector has no address worth passing
-    m.hashes.assign(room, 0);
-    m.pos.assign(room, 0);
-    m.read.assign(room, 0);
-    if (with_strand) m.strand.assign(room, 0);
+    m.hashes.assign(size_t(cap), 0);
+    m.pos.assign(size_t(cap), 0);
+    m.read.assign(size_t(cap), 0);
+    if (with_strand) m.strand.assign(size_t(cap), 0);
     m.offsets.assign(b.offsets.size(), 0);
     uint64_t total = 0;
-    ctx.check(kmu_read_minimizers(ctx.raw(), &hp, b.bytes.data(), b.offsets.data(), b.n(), w, m.hashes.data(), m.pos.data(), m.read.data(),
-                                  with_strand ? m.strand.data() : nullptr, cap, m.offsets.data(), &total));
+    ctx.check(kmu_read_minimizers(ctx.raw(), &hp, b.bytes.data(), b.offsets.data(), b.n(), w, detail::ptr(m.hashes), detail::ptr(m.pos), detail::ptr(m.read),
+                                  with_strand ? detail::ptr(m.strand) : nullptr, cap, m.offsets.data(), &total));
     m.hashes.resize(size_t(total));
     m.pos.resize(size_t(total));
     m.read.resize(size_t(total));
@@ -1850,18 +1870,16 @@ inline std::vector<kmu_chain> seed_chains(const std::vector<uint32_t> &pairs, co
         (!db.strand.empty() && db.strand.size() != db.pos.size()))
         throw std::invalid_argument("seed_chains: pos, read and strand hold one value per minimizer");
     const uint64_t n_pairs = pairs.size() / 2;
-    const uint32_t none[2] = {0, 0}; // an empty vector has no address worth passing
-    auto call = [&](kmu_chain *out, uint64_t cap, uint64_t *total) {
-        return kmu_seed_chains(ctx.raw(), n_pairs ? pairs.data() : none, n_pairs, q.pos.empty() ? none : q.pos.data(),
-                               q.read.empty() ? none : q.read.data(), q.strand.empty() ? nullptr : q.strand.data(), uint32_t(q.pos.size()),
-                               uint32_t(q.offsets.size() - 1), db.pos.empty() ? none : db.pos.data(), db.read.empty() ? none : db.read.data(),
-                               db.strand.empty() ? nullptr : db.strand.data(), uint32_t(db.pos.size()), uint32_t(db.offsets.size() - 1), &p,
-                               KMU_MEM_HOST, out, cap, total);
-    };
-    uint64_t total = 0;
-    ctx.check(call(nullptr, 0, &total));
-    std::vector<kmu_chain> out(static_cast<size_t>(total));
-    if (total) ctx.check(call(out.data(), total, &total));
+    using detail::opt;
+    using detail::ptr;
+    std::vector<kmu_chain> out;
+    detail::two_calls(
+        ctx, false, [&](uint64_t total) { out.resize(size_t(total)); },
+        [&](bool, uint64_t cap, uint64_t *total) {
+            return kmu_seed_chains(ctx.raw(), n_pairs ? pairs.data() : &detail::spare_element<uint32_t>, n_pairs, ptr(q.pos), ptr(q.read), opt(q.strand),
+                                   uint32_t(q.pos.size()), uint32_t(q.offsets.size() - 1), ptr(db.pos), ptr(db.read), opt(db.strand),
+                                   uint32_t(db.pos.size()), uint32_t(db.offsets.size() - 1), &p, KMU_MEM_HOST, opt(out), cap, total);
+        });
     return out;
 }
 
@@ -1912,11 +1930,8 @@ std::vector<kmu_chain> read_chains(const detail::Batch &batch, size_t k, uint32_
 /// the batches the chains' reads are numbered in (db == nullptr: the self-join on one batch); packed batches are unpacked first.
 inline std::vector<kmu_chain_aln> chain_align(const std::vector<kmu_chain> &chains, const detail::Batch &q, const detail::Batch *db = nullptr,
                                               uint32_t band = 64, Context &ctx = Context::global()) {
-    const detail::Batch bq = detail::unpacked(q);
-    detail::Batch bdb_own;
-    if (db) bdb_own = detail::unpacked(*db);
-    const detail::Batch &bdb = db ? bdb_own : bq;
-    if (bq.on_device() || bdb.on_device()) throw std::invalid_argument("chain_align returns host arrays: it needs the sequences in host memory");
+    const detail::Sides both = detail::host_sides("chain_align", q, db);
+    const detail::Batch &bq = both.q, &bdb = both.db();
     std::vector<kmu_chain_aln> out(chains.size());
     if (chains.empty()) return out;
     kmu_align_params p{};
@@ -1975,11 +1990,8 @@ struct ChainCigars {
 /// (0: KMU_CIGAR_TRACE_DEFAULT).  Two library calls: one that counts, one with exactly that capacity.
 inline ChainCigars chain_cigar(const std::vector<kmu_chain> &chains, const detail::Batch &q, const detail::Batch *db = nullptr,
                                uint32_t band = 64, uint64_t max_trace_bytes = 0, Context &ctx = Context::global()) {
-    const detail::Batch bq = detail::unpacked(q);
-    detail::Batch bdb_own;
-    if (db) bdb_own = detail::unpacked(*db);
-    const detail::Batch &bdb = db ? bdb_own : bq;
-    if (bq.on_device() || bdb.on_device()) throw std::invalid_argument("chain_cigar returns host arrays: it needs the sequences in host memory");
+    const detail::Sides both = detail::host_sides("chain_cigar", q, db);
+    const detail::Batch &bq = both.q, &bdb = both.db();
     ChainCigars out;
     out.aln.resize(chains.size());
     out.op_offsets.assign(chains.size() + 1, 0);
@@ -1987,14 +1999,12 @@ inline ChainCigars chain_cigar(const std::vector<kmu_chain> &chains, const detai
     kmu_cigar_params p{};
     p.band = band;
     p.max_trace_bytes = max_trace_bytes;
-    uint64_t total = 0;
-    auto call = [&](uint32_t *ops, uint64_t cap) {
-        ctx.check(kmu_chain_cigar(ctx.raw(), chains.data(), chains.size(), bq.bytes.data(), bq.offsets.data(), bq.n(), bdb.bytes.data(),
-                                  bdb.offsets.data(), bdb.n(), &p, KMU_MEM_HOST, out.aln.data(), out.op_offsets.data(), ops, cap, &total));
-    };
-    call(nullptr, 0);
-    out.ops.resize(total);
-    if (total) call(out.ops.data(), total);
+    detail::two_calls(
+        ctx, false, [&](uint64_t total) { out.ops.resize(total); },
+        [&](bool, uint64_t cap, uint64_t *total) {
+            return kmu_chain_cigar(ctx.raw(), chains.data(), chains.size(), bq.bytes.data(), bq.offsets.data(), bq.n(), bdb.bytes.data(),
+                                   bdb.offsets.data(), bdb.n(), &p, KMU_MEM_HOST, out.aln.data(), out.op_offsets.data(), detail::opt(out.ops), cap, total);
+        });
     return out;
 }
 /// The same under the name of the Python route (minimizer.cigar_chains)
@@ -2051,24 +2061,33 @@ struct ChainPileups {
     }
 };
 
+namespace detail {
+/// the records and run offsets of `cigars` are those of `chains` (lib.py's _runs_of_chains)
+inline void cigars_of_chains(const char *who, const std::vector<kmu_chain> &chains, const ChainCigars &cigars) {
+    if (cigars.aln.size() != chains.size() || cigars.op_offsets.size() != chains.size() + 1)
+        throw std::invalid_argument(std::string(who) + ": the records and run offsets are not those of the chains");
+}
+/// The vote tables of the two sides (lib.py's _side_tables), grown to size_q and size_db entries where they are voted into: the
+/// self-join (`two` false) has ONE table, q, also when only the B side votes, and `shared` says that both sides vote into it.
+template <class Tables> void side_tables(Tables &out, bool two, uint32_t sides, size_t size_q, size_t size_db) {
+    out.shared = !two && (sides & KMU_PILE_Q) && (sides & KMU_PILE_DB);
+    const bool db_in_q = !two && !(sides & KMU_PILE_Q);
+    if ((sides & KMU_PILE_Q) || db_in_q) out.q.resize(size_q, 0u);
+    if ((sides & KMU_PILE_DB) && two) out.db.resize(size_db, 0u);
+}
+}  // namespace detail
+
 /// kmu_chain_pileup on host arrays: the votes of every chain's runs onto the bases of both reads.  chains and cigars: the chains
 /// given to chain_cigar and what it returned; q, db as there (db == nullptr: the self-join, one shared table); sides: KMU_PILE_Q,
 /// KMU_PILE_DB or both.  into: tables of an earlier call on the same batches to add to (moved from).
 inline ChainPileups chain_pileup(const std::vector<kmu_chain> &chains, const ChainCigars &cigars, const detail::Batch &q,
                                  const detail::Batch *db = nullptr, uint32_t sides = KMU_PILE_Q | KMU_PILE_DB, ChainPileups into = {},
                                  Context &ctx = Context::global()) {
-    const detail::Batch bq = detail::unpacked(q);
-    detail::Batch bdb_own;
-    if (db) bdb_own = detail::unpacked(*db);
-    const detail::Batch &bdb = db ? bdb_own : bq;
-    if (bq.on_device() || bdb.on_device()) throw std::invalid_argument("chain_pileup returns host arrays: it needs the sequences in host memory");
-    if (cigars.aln.size() != chains.size() || cigars.op_offsets.size() != chains.size() + 1)
-        throw std::invalid_argument("chain_pileup: the records and run offsets are not those of the chains");
+    const detail::Sides both = detail::host_sides("chain_pileup", q, db);
+    const detail::Batch &bq = both.q, &bdb = both.db();
+    detail::cigars_of_chains("chain_pileup", chains, cigars);
     ChainPileups out = std::move(into);
-    out.shared = !db && (sides & KMU_PILE_Q) && (sides & KMU_PILE_DB);
-    const bool db_in_q = !db && !(sides & KMU_PILE_Q); // the self-join's one table also when only the B side votes
-    if ((sides & KMU_PILE_Q) || db_in_q) out.q.resize(size_t(bq.offsets.back()) * KMU_PILE_COLS, 0u);
-    if ((sides & KMU_PILE_DB) && db) out.db.resize(size_t(bdb.offsets.back()) * KMU_PILE_COLS, 0u);
+    detail::side_tables(out, both.two, sides, size_t(bq.offsets.back()) * KMU_PILE_COLS, size_t(bdb.offsets.back()) * KMU_PILE_COLS);
     if (chains.empty()) return out;
     kmu_pileup_params p{};
     p.flags = sides;
@@ -2094,8 +2113,7 @@ struct PileCalls {
 
 /// kmu_pile_call on host arrays: `table` is a table of chain_pileup for `batch`.
 inline PileCalls pile_call(const std::vector<uint32_t> &table, const detail::Batch &batch, uint32_t min_depth = 3, Context &ctx = Context::global()) {
-    const detail::Batch b = detail::unpacked(batch);
-    if (b.on_device()) throw std::invalid_argument("pile_call returns host arrays: it needs the sequences in host memory");
+    const detail::Batch b = detail::host_batch("pile_call", batch);
     if (table.size() != size_t(b.offsets.back()) * KMU_PILE_COLS) throw std::invalid_argument("pile_call: the table is not one of this batch");
     PileCalls out;
     out.call.resize(b.offsets.back());
@@ -2103,10 +2121,8 @@ inline PileCalls pile_call(const std::vector<uint32_t> &table, const detail::Bat
     if (!b.n()) return out;
     kmu_pile_call_params p{};
     p.min_depth = min_depth;
-    uint8_t none = 0;
-    ctx.check(kmu_pile_call(ctx.raw(), table.empty() ? reinterpret_cast<const uint32_t *>(&none) : table.data(),
-                            b.bytes.empty() ? &none : b.bytes.data(), b.offsets.data(), b.n(), &p, KMU_MEM_HOST,
-                            out.call.empty() ? &none : out.call.data(), out.reads.data()));
+    ctx.check(kmu_pile_call(ctx.raw(), detail::ptr(table), detail::ptr(b.bytes), b.offsets.data(), b.n(), &p, KMU_MEM_HOST, detail::ptr(out.call),
+                            out.reads.data()));
     return out;
 }
 
@@ -2129,9 +2145,7 @@ inline InsPlan pile_ins_plan(const std::vector<uint32_t> &table, const std::vect
     out.ins_len.resize(call.size());
     kmu_ins_plan_params p{};
     p.max_ins = max_ins;
-    uint8_t none = 0;
-    ctx.check(kmu_pile_ins_plan(ctx.raw(), table.empty() ? reinterpret_cast<const uint32_t *>(&none) : table.data(), call.empty() ? &none : call.data(),
-                                call.size(), &p, KMU_MEM_HOST, out.ins_len.empty() ? &none : out.ins_len.data(), &out.n_slots));
+    ctx.check(kmu_pile_ins_plan(ctx.raw(), detail::ptr(table), detail::ptr(call), call.size(), &p, KMU_MEM_HOST, detail::ptr(out.ins_len), &out.n_slots));
     return out;
 }
 
@@ -2149,34 +2163,25 @@ struct ChainInsertions {
 inline ChainInsertions chain_pile_ins(const std::vector<kmu_chain> &chains, const ChainCigars &cigars, const detail::Batch &q, const InsPlan &plan_q,
                                       const detail::Batch *db = nullptr, const InsPlan *plan_db = nullptr, uint32_t sides = KMU_PILE_Q | KMU_PILE_DB,
                                       ChainInsertions into = {}, Context &ctx = Context::global()) {
-    const detail::Batch bq = detail::unpacked(q);
-    detail::Batch bdb_own;
-    if (db) bdb_own = detail::unpacked(*db);
-    const detail::Batch &bdb = db ? bdb_own : bq;
-    if (bq.on_device() || bdb.on_device()) throw std::invalid_argument("chain_pile_ins returns host arrays: it needs the sequences in host memory");
-    if (cigars.aln.size() != chains.size() || cigars.op_offsets.size() != chains.size() + 1)
-        throw std::invalid_argument("chain_pile_ins: the records and run offsets are not those of the chains");
+    const detail::Sides both = detail::host_sides("chain_pile_ins", q, db);
+    const detail::Batch &bq = both.q, &bdb = both.db();
+    detail::cigars_of_chains("chain_pile_ins", chains, cigars);
     if (bool(db) != bool(plan_db)) throw std::invalid_argument("chain_pile_ins: a db batch and its plan come together");
     const InsPlan &pdb = db ? *plan_db : plan_q;
     if (plan_q.ins_len.size() != bq.offsets.back() || pdb.ins_len.size() != bdb.offsets.back())
         throw std::invalid_argument("chain_pile_ins: a plan is not one of its batch");
     ChainInsertions out = std::move(into);
-    out.shared = !db && (sides & KMU_PILE_Q) && (sides & KMU_PILE_DB);
-    const bool db_in_q = !db && !(sides & KMU_PILE_Q); // the self-join's one table also when only the B side votes
-    if ((sides & KMU_PILE_Q) || db_in_q) out.q.resize(size_t(plan_q.n_slots) * KMU_INS_COLS, 0u);
-    if ((sides & KMU_PILE_DB) && db) out.db.resize(size_t(pdb.n_slots) * KMU_INS_COLS, 0u);
+    detail::side_tables(out, both.two, sides, size_t(plan_q.n_slots) * KMU_INS_COLS, size_t(pdb.n_slots) * KMU_INS_COLS);
     if (chains.empty()) return out;
     kmu_pileup_params p{};
     p.flags = sides;
-    uint32_t none_q = 0, none_db = 0; // an empty table has no address worth passing
-    uint32_t *table_q = out.q.empty() ? &none_q : out.q.data();
+    uint32_t none_db = 0; // the db table's own spare: the library takes two equal table addresses for the self-join's one table
+    uint32_t *table_q = detail::ptr(out.q);
     uint32_t *table_db = !db ? table_q : out.db.empty() ? &none_db : out.db.data();
-    uint8_t none = 0;
     ctx.check(kmu_chain_pile_ins(ctx.raw(), chains.data(), chains.size(), cigars.aln.data(), cigars.op_offsets.data(), cigars.ops.data(),
                                  cigars.ops.size(), bq.bytes.data(), bq.offsets.data(), bq.n(), bdb.bytes.data(), bdb.offsets.data(), bdb.n(), &p,
-                                 KMU_MEM_HOST, plan_q.ins_len.empty() ? &none : plan_q.ins_len.data(), plan_q.n_slots,
-                                 (sides & KMU_PILE_Q) ? table_q : nullptr, pdb.ins_len.empty() ? &none : pdb.ins_len.data(), pdb.n_slots,
-                                 (sides & KMU_PILE_DB) ? table_db : nullptr));
+                                 KMU_MEM_HOST, detail::ptr(plan_q.ins_len), plan_q.n_slots, (sides & KMU_PILE_Q) ? table_q : nullptr,
+                                 detail::ptr(pdb.ins_len), pdb.n_slots, (sides & KMU_PILE_DB) ? table_db : nullptr));
     return out;
 }
 /// The same under the name of the Python route (minimizer.insertions_chains)
@@ -2193,25 +2198,31 @@ struct ConsensusReads {
     std::string read(size_t r) const { return std::string(bases.begin() + offsets[r], bases.begin() + offsets[r + 1]); }
 };
 
+namespace detail {
+/// the host batch of a consensus call, once its table, calls, plan and slots were found to be of that batch (lib.py's _consensus_inputs)
+inline Batch consensus_inputs(const char *who, const std::vector<uint32_t> &table, const std::vector<uint8_t> &call, const InsPlan &plan,
+                              const std::vector<uint32_t> &ins, const Batch &batch) {
+    Batch b = host_batch(who, batch);
+    const size_t n_bases = b.offsets.back();
+    if (table.size() != n_bases * KMU_PILE_COLS || call.size() != n_bases || plan.ins_len.size() != n_bases || ins.size() != plan.n_slots * KMU_INS_COLS)
+        throw std::invalid_argument(std::string(who) + ": the table, the calls, the plan or the slots are not of this batch");
+    return b;
+}
+}  // namespace detail
+
 /// kmu_pile_consensus on host arrays: table, call, plan and ins (a table of chain_pile_ins) belong to `batch`.  A row gives at most
 /// one byte and its slots, so the output is sized by n_bases + n_slots and the library is called once.
 inline ConsensusReads pile_consensus(const std::vector<uint32_t> &table, const std::vector<uint8_t> &call, const InsPlan &plan,
                                      const std::vector<uint32_t> &ins, const detail::Batch &batch, Context &ctx = Context::global()) {
-    const detail::Batch b = detail::unpacked(batch);
-    if (b.on_device()) throw std::invalid_argument("pile_consensus returns host arrays: it needs the sequences in host memory");
-    const size_t n_bases = b.offsets.back();
-    if (table.size() != n_bases * KMU_PILE_COLS || call.size() != n_bases || plan.ins_len.size() != n_bases || ins.size() != plan.n_slots * KMU_INS_COLS)
-        throw std::invalid_argument("pile_consensus: the table, the calls, the plan or the slots are not of this batch");
+    using detail::ptr;
+    const detail::Batch b = detail::consensus_inputs("pile_consensus", table, call, plan, ins, batch);
     ConsensusReads out;
     out.offsets.assign(size_t(b.n()) + 1, 0);
-    out.bases.resize(n_bases + plan.n_slots + 1);
+    out.bases.resize(size_t(b.offsets.back()) + plan.n_slots + 1);   // (the capacity the library is told: one more than the bound, kept as it was)
     kmu_consensus_params p{};
-    uint8_t none = 0;
     uint64_t total = 0;
-    ctx.check(kmu_pile_consensus(ctx.raw(), table.empty() ? reinterpret_cast<const uint32_t *>(&none) : table.data(), call.empty() ? &none : call.data(),
-                                 plan.ins_len.empty() ? &none : plan.ins_len.data(), plan.n_slots, ins.empty() ? nullptr : ins.data(),
-                                 b.bytes.empty() ? &none : b.bytes.data(), b.offsets.data(), b.n(), &p, KMU_MEM_HOST, out.offsets.data(),
-                                 out.bases.data(), out.bases.size(), &total));
+    ctx.check(kmu_pile_consensus(ctx.raw(), ptr(table), ptr(call), ptr(plan.ins_len), plan.n_slots, detail::opt(ins), ptr(b.bytes), b.offsets.data(), b.n(),
+                                 &p, KMU_MEM_HOST, out.offsets.data(), out.bases.data(), out.bases.size(), &total));
     out.bases.resize(total);
     return out;
 }
@@ -2272,17 +2283,16 @@ inline PileSegments pile_segments(const std::vector<uint32_t> &table, const std:
     const uint32_t n_reads = uint32_t(offsets.size() - 1);
     const size_t n_bases = offsets.back(), by_len = n_bases / (min_len ? min_len : 1), cap = longest && n_reads < by_len ? n_reads : by_len;
     out.seg_offsets.assign(size_t(n_reads) + 1, 0);
-    out.segs.resize(cap + 1);
+    out.segs.resize(cap);
     out.reads.resize(n_reads);
     kmu_pile_seg_params p{};
     p.min_depth = min_depth;
     p.min_span = min_span;
     p.min_len = min_len;
     p.flags = longest ? KMU_SEG_LONGEST : 0u;
-    uint32_t none = 0;
     uint64_t total = 0;
-    ctx.check(kmu_pile_segments(ctx.raw(), table.empty() ? &none : table.data(), offsets.data(), n_reads, &p, KMU_MEM_HOST, out.seg_offsets.data(),
-                                out.segs.data(), cap, &total, out.reads.empty() ? nullptr : out.reads.data()));
+    ctx.check(kmu_pile_segments(ctx.raw(), detail::ptr(table), offsets.data(), n_reads, &p, KMU_MEM_HOST, out.seg_offsets.data(), detail::ptr(out.segs), cap,
+                                &total, detail::opt(out.reads)));
     out.segs.resize(total);
     return out;
 }
@@ -2294,14 +2304,12 @@ inline ConsensusReads extract_ranges(const std::vector<uint8_t> &bases, const st
     if (begin.size() != end.size()) throw std::invalid_argument("extract_ranges: as many ends as begins");
     ConsensusReads out;
     out.offsets.assign(begin.size() + 1, 0);
-    uint8_t none = 0;
-    uint64_t none_range = 0, total = 0;
-    const uint8_t *src = bases.empty() ? &none : bases.data();
-    const uint64_t *b = begin.empty() ? &none_range : begin.data(), *e = end.empty() ? &none_range : end.data();
-    ctx.check(kmu_extract_ranges(ctx.raw(), src, bases.size(), b, e, begin.size(), KMU_MEM_HOST, out.offsets.data(), nullptr, 0, &total));
-    out.bases.resize(total);
-    if (total)
-        ctx.check(kmu_extract_ranges(ctx.raw(), src, bases.size(), b, e, begin.size(), KMU_MEM_HOST, out.offsets.data(), out.bases.data(), total, &total));
+    detail::two_calls(
+        ctx, false, [&](uint64_t total) { out.bases.resize(total); },
+        [&](bool, uint64_t cap, uint64_t *total) {
+            return kmu_extract_ranges(ctx.raw(), detail::ptr(bases), bases.size(), detail::ptr(begin), detail::ptr(end), begin.size(), KMU_MEM_HOST,
+                                      out.offsets.data(), detail::opt(out.bases), cap, total);
+        });
     return out;
 }
 
@@ -2310,18 +2318,13 @@ inline ConsensusReads extract_ranges(const std::vector<uint8_t> &bases, const st
 inline std::vector<uint64_t> pile_consensus_pos(const std::vector<uint32_t> &table, const std::vector<uint8_t> &call, const InsPlan &plan,
                                                 const std::vector<uint32_t> &ins, const detail::Batch &batch, const std::vector<uint64_t> &rows,
                                                 Context &ctx = Context::global()) {
-    const detail::Batch b = detail::unpacked(batch);
-    if (b.on_device()) throw std::invalid_argument("pile_consensus_pos returns host arrays: it needs the sequences in host memory");
-    const size_t n_bases = b.offsets.back();
-    if (table.size() != n_bases * KMU_PILE_COLS || call.size() != n_bases || plan.ins_len.size() != n_bases || ins.size() != plan.n_slots * KMU_INS_COLS)
-        throw std::invalid_argument("pile_consensus_pos: the table, the calls, the plan or the slots are not of this batch");
+    using detail::opt;
+    using detail::ptr;
+    const detail::Batch b = detail::consensus_inputs("pile_consensus_pos", table, call, plan, ins, batch);
     std::vector<uint64_t> pos(rows.size(), 0);
     kmu_consensus_params p{};
-    uint8_t none = 0;
-    ctx.check(kmu_pile_consensus_pos(ctx.raw(), table.empty() ? reinterpret_cast<const uint32_t *>(&none) : table.data(), call.empty() ? &none : call.data(),
-                                     plan.ins_len.empty() ? &none : plan.ins_len.data(), plan.n_slots, ins.empty() ? nullptr : ins.data(),
-                                     b.bytes.empty() ? &none : b.bytes.data(), b.offsets.data(), b.n(), &p, KMU_MEM_HOST, rows.empty() ? nullptr : rows.data(),
-                                     rows.size(), pos.empty() ? nullptr : pos.data()));
+    ctx.check(kmu_pile_consensus_pos(ctx.raw(), ptr(table), ptr(call), ptr(plan.ins_len), plan.n_slots, opt(ins), ptr(b.bytes), b.offsets.data(), b.n(), &p,
+                                     KMU_MEM_HOST, opt(rows), rows.size(), opt(pos)));
     return pos;
 }
 
@@ -2347,8 +2350,7 @@ inline void segment_rows(const std::vector<kmu_pile_seg> &segs, const std::vecto
 /// batch's bytes.  Every kept segment becomes a read: uncovered ends go, a chimera comes out as its parts.
 inline TrimmedReads trim_reads(const std::vector<uint32_t> &table, const detail::Batch &batch, uint32_t min_depth = 3, uint32_t min_span = 3,
                                uint32_t min_len = 100, bool longest = false, Context &ctx = Context::global()) {
-    const detail::Batch b = detail::unpacked(batch);
-    if (b.on_device()) throw std::invalid_argument("trim_reads returns host arrays: it needs the sequences in host memory");
+    const detail::Batch b = detail::host_batch("trim_reads", batch);
     PileSegments s = pile_segments(table, b.offsets, min_depth, min_span, min_len, longest, ctx);
     std::vector<uint64_t> first, last;
     detail::segment_rows(s.segs, b.offsets, first, last);
@@ -2369,8 +2371,7 @@ struct CorrectedTrimmedReads {
 inline CorrectedTrimmedReads correct_trim_chains(const std::vector<kmu_chain> &chains, const detail::Batch &batch, uint32_t band = 64, uint32_t min_depth = 3,
                                                  uint32_t max_ins = 16, uint32_t min_span = 3, uint32_t min_len = 100, bool longest = false,
                                                  Context &ctx = Context::global()) {
-    const detail::Batch b = detail::unpacked(batch);
-    if (b.on_device()) throw std::invalid_argument("correct_trim_chains returns host arrays: it needs the sequences in host memory");
+    const detail::Batch b = detail::host_batch("correct_trim_chains", batch);
     const ChainCigars cigars = chain_cigar(chains, batch, nullptr, band, 0, ctx);
     const ChainPileups pile = chain_pileup(chains, cigars, batch, nullptr, KMU_PILE_Q | KMU_PILE_DB, {}, ctx);
     PileCalls calls = pile_call(pile.q, batch, min_depth, ctx);
@@ -2434,26 +2435,24 @@ inline kmu_sg_params sg_params(const GraphParams &g) {
     p.fuzz = g.fuzz;
     return p;
 }
-inline void sg_check_sizes(const char *who, const std::vector<kmu_chain> &chains, const std::vector<kmu_chain_aln> &aln, const std::vector<uint64_t> &offsets) {
-    if (offsets.empty()) throw std::invalid_argument(std::string(who) + ": the offsets of a batch have at least one entry");
+/// the number of reads, once the offsets and the alignment records were found to fit
+inline uint32_t sg_check_sizes(const char *who, const std::vector<kmu_chain> &chains, const std::vector<kmu_chain_aln> &aln, const std::vector<uint64_t> &offsets) {
+    const uint32_t n_reads = n_reads_of(who, offsets);
     if (!aln.empty() && aln.size() != chains.size()) throw std::invalid_argument(std::string(who) + ": as many alignment records as chains, or none");
+    return n_reads;
 }
 } // namespace detail
 
 /// kmu_sg_classify on host arrays: chains of a self-join, their alignment records (empty: no identity test) and the batch's offsets.
 inline OverlapClasses sg_classify(const std::vector<kmu_chain> &chains, const std::vector<kmu_chain_aln> &aln, const std::vector<uint64_t> &offsets,
                                   const GraphParams &g = GraphParams(), Context &ctx = Context::global()) {
-    detail::sg_check_sizes("sg_classify", chains, aln, offsets);
+    const uint32_t n_reads = detail::sg_check_sizes("sg_classify", chains, aln, offsets);
     OverlapClasses out;
-    const uint32_t n_reads = uint32_t(offsets.size() - 1);
-    out.classes.assign(chains.size() + 1, 0); // an empty vector has no address worth passing
-    out.reads.assign(size_t(n_reads) + 1, kmu_sg_read{});
+    out.classes.assign(chains.size(), 0);
+    out.reads.assign(n_reads, kmu_sg_read{});
     const kmu_sg_params p = detail::sg_params(g);
-    const kmu_chain none{};
-    ctx.check(kmu_sg_classify(ctx.raw(), chains.empty() ? &none : chains.data(), aln.empty() ? nullptr : aln.data(), chains.size(), offsets.data(), n_reads,
-                              &p, KMU_MEM_HOST, out.classes.data(), out.reads.data()));
-    out.classes.resize(chains.size());
-    out.reads.resize(n_reads);
+    ctx.check(kmu_sg_classify(ctx.raw(), detail::ptr(chains), detail::opt(aln), chains.size(), offsets.data(), n_reads, &p, KMU_MEM_HOST,
+                              detail::ptr(out.classes), detail::ptr(out.reads)));
     return out;
 }
 
@@ -2461,24 +2460,23 @@ inline OverlapClasses sg_classify(const std::vector<kmu_chain> &chains, const st
 /// graph, transitively reduced.  Two library calls: one that counts, one with exactly that capacity.
 inline OverlapGraph overlap_graph(const std::vector<kmu_chain> &chains, const std::vector<kmu_chain_aln> &aln, const std::vector<uint64_t> &offsets,
                                   const GraphParams &g = GraphParams(), Context &ctx = Context::global()) {
-    detail::sg_check_sizes("overlap_graph", chains, aln, offsets);
+    const uint32_t n_reads = detail::sg_check_sizes("overlap_graph", chains, aln, offsets);
     OverlapGraph out;
-    const uint32_t n_reads = uint32_t(offsets.size() - 1);
     const kmu_sg_params p = detail::sg_params(g);
-    const kmu_chain none{};
-    const kmu_chain *c = chains.empty() ? &none : chains.data();
-    const kmu_chain_aln *a = aln.empty() ? nullptr : aln.data();
-    uint64_t total = 0;
-    ctx.check(kmu_sg_graph(ctx.raw(), c, a, chains.size(), offsets.data(), n_reads, &p, KMU_MEM_HOST, nullptr, nullptr, nullptr, 0, nullptr, &total));
-    out.arcs.assign(total + 1, kmu_sg_arc{});
-    out.arc_offsets.assign(2 * size_t(n_reads) + 1, 0);
-    out.classes.assign(chains.size() + 1, 0);
-    out.reads.assign(size_t(n_reads) + 1, kmu_sg_read{});
-    ctx.check(kmu_sg_graph(ctx.raw(), c, a, chains.size(), offsets.data(), n_reads, &p, KMU_MEM_HOST, out.classes.data(), out.reads.data(), out.arcs.data(),
-                           total, out.arc_offsets.data(), &total));
-    out.arcs.resize(total);
-    out.classes.resize(chains.size());
-    out.reads.resize(n_reads);
+    using detail::ptr;
+    detail::two_calls(
+        ctx, true,
+        [&](uint64_t total) {
+            out.arcs.assign(total, kmu_sg_arc{});
+            out.arc_offsets.assign(2 * size_t(n_reads) + 1, 0);
+            out.classes.assign(chains.size(), 0);
+            out.reads.assign(n_reads, kmu_sg_read{});
+        },
+        [&](bool write, uint64_t cap, uint64_t *total) {
+            return kmu_sg_graph(ctx.raw(), ptr(chains), detail::opt(aln), chains.size(), offsets.data(), n_reads, &p, KMU_MEM_HOST,
+                                write ? ptr(out.classes) : nullptr, write ? ptr(out.reads) : nullptr, write ? ptr(out.arcs) : nullptr, cap,
+                                write ? out.arc_offsets.data() : nullptr, total);
+        });
     return out;
 }
 
@@ -2487,8 +2485,7 @@ template <class Kmer>
 OverlapGraph read_graph(const detail::Batch &batch, size_t k, uint32_t w, const GraphParams &g = GraphParams(), FHash fhash = FHash::canon_invhash,
                         uint32_t max_occ = 0, uint32_t max_gap = 5000, uint32_t band_chain = 500, uint32_t min_seeds = 3, uint32_t min_score = 0,
                         uint32_t band = 64, Context &ctx = Context::global()) {
-    const detail::Batch b = detail::unpacked(batch);
-    if (b.on_device()) throw std::invalid_argument("read_graph returns host arrays: it needs the sequences in host memory");
+    const detail::Batch b = detail::host_batch("read_graph", batch);
     const auto records = read_alignments<Kmer>(batch, k, w, fhash, max_occ, max_gap, band_chain, min_seeds, min_score, band, ctx);
     return overlap_graph(records.first, records.second, b.offsets, g, ctx);
 }
@@ -2497,10 +2494,9 @@ OverlapGraph read_graph(const detail::Batch &batch, size_t k, uint32_t w, const 
 /// is 1, each unitig once per strand; a read's label is the smaller of the labels of its two vertices.
 inline std::vector<uint32_t> unitig_labels(const std::vector<kmu_sg_arc> &arcs, uint32_t n_reads, Context &ctx = Context::global()) {
     static_assert(sizeof(kmu_sg_arc) == 32, "a record is 8 words");
-    const kmu_sg_arc none{};
     const Components c = detail::components_call(ctx, 2 * n_reads, [&](uint32_t *l, uint32_t *cl, uint32_t *s, uint32_t *m, uint32_t *n) {
-        return kmu_components(ctx.raw(), 2 * n_reads, reinterpret_cast<const uint32_t *>(arcs.empty() ? &none : arcs.data()), arcs.size(), 8, 6, 1,
-                              KMU_MEM_HOST, l, cl, s, m, n);
+        return kmu_components(ctx.raw(), 2 * n_reads, reinterpret_cast<const uint32_t *>(detail::ptr(arcs)), arcs.size(), 8, 6, 1, KMU_MEM_HOST, l, cl,
+                              s, m, n);
     });
     std::vector<uint32_t> labels(n_reads);
     for (uint32_t r = 0; r < n_reads; r++) labels[r] = std::min(c.label[2 * size_t(r)], c.label[2 * size_t(r) + 1]);
@@ -2542,20 +2538,17 @@ struct ReadUnitigs {
 /// overlap_graph (reads empty: no read is contained); offsets: the batch's.  One library call: both counts are at most n_reads.
 inline Unitigs sg_unitigs(const std::vector<kmu_sg_arc> &arcs, const std::vector<kmu_sg_read> &reads, const std::vector<uint64_t> &offsets,
                           Context &ctx = Context::global()) {
-    if (offsets.empty()) throw std::invalid_argument("sg_unitigs: the offsets of a batch have at least one entry");
-    const uint32_t n_reads = uint32_t(offsets.size() - 1);
+    const uint32_t n_reads = detail::n_reads_of("sg_unitigs", offsets);
     if (!reads.empty() && reads.size() != n_reads) throw std::invalid_argument("sg_unitigs: as many summaries as reads, or none");
     Unitigs out;
-    out.unitigs.assign(size_t(n_reads) + 1, kmu_sg_unitig{}); // an empty vector has no address worth passing
-    out.path.assign(size_t(n_reads) + 1, kmu_sg_step{});
-    out.place.assign(size_t(n_reads) + 1, kmu_sg_place{});
-    const kmu_sg_arc none{};
+    out.unitigs.assign(n_reads, kmu_sg_unitig{});
+    out.path.assign(n_reads, kmu_sg_step{});
+    out.place.assign(n_reads, kmu_sg_place{});
     uint64_t n_steps = 0, total = 0;
-    ctx.check(kmu_sg_unitigs(ctx.raw(), arcs.empty() ? &none : arcs.data(), arcs.size(), reads.empty() ? nullptr : reads.data(), offsets.data(), n_reads,
-                             KMU_MEM_HOST, out.unitigs.data(), out.path.data(), out.place.data(), &n_steps, &total));
+    ctx.check(kmu_sg_unitigs(ctx.raw(), detail::ptr(arcs), arcs.size(), detail::opt(reads), offsets.data(), n_reads, KMU_MEM_HOST, detail::ptr(out.unitigs),
+                             detail::ptr(out.path), detail::ptr(out.place), &n_steps, &total));
     out.unitigs.resize(total);
     out.path.resize(n_steps);
-    out.place.resize(n_reads);
     return out;
 }
 
@@ -2563,23 +2556,15 @@ inline Unitigs sg_unitigs(const std::vector<kmu_sg_arc> &arcs, const std::vector
 /// that counts, one with exactly that capacity.
 inline UnitigSequences unitig_sequences(const Unitigs &layout, const std::vector<uint8_t> &bases, const std::vector<uint64_t> &offsets,
                                         Context &ctx = Context::global()) {
-    if (offsets.empty()) throw std::invalid_argument("unitig_sequences: the offsets of a batch have at least one entry");
-    const uint32_t n_reads = uint32_t(offsets.size() - 1);
-    const kmu_sg_unitig no_unitig{};
-    const kmu_sg_step no_step{};
-    const uint8_t no_base = 0;
-    const kmu_sg_unitig *u = layout.unitigs.empty() ? &no_unitig : layout.unitigs.data();
-    const kmu_sg_step *s = layout.path.empty() ? &no_step : layout.path.data();
-    const uint8_t *b = bases.empty() ? &no_base : bases.data();
+    const uint32_t n_reads = detail::n_reads_of("unitig_sequences", offsets);
+    using detail::ptr;
     UnitigSequences out;
-    uint64_t total = 0;
-    ctx.check(kmu_sg_unitig_seqs(ctx.raw(), u, layout.unitigs.size(), s, layout.path.size(), b, offsets.data(), n_reads, KMU_MEM_HOST, nullptr, nullptr, 0,
-                                 &total));
-    out.seq.assign(total + 1, 0);
-    out.seq_offsets.assign(layout.unitigs.size() + 1, 0);
-    ctx.check(kmu_sg_unitig_seqs(ctx.raw(), u, layout.unitigs.size(), s, layout.path.size(), b, offsets.data(), n_reads, KMU_MEM_HOST,
-                                 out.seq_offsets.data(), out.seq.data(), total, &total));
-    out.seq.resize(total);
+    detail::two_calls(
+        ctx, true, [&](uint64_t total) { out.seq.assign(total, 0), out.seq_offsets.assign(layout.unitigs.size() + 1, 0); },
+        [&](bool write, uint64_t cap, uint64_t *total) {
+            return kmu_sg_unitig_seqs(ctx.raw(), ptr(layout.unitigs), layout.unitigs.size(), ptr(layout.path), layout.path.size(), ptr(bases), offsets.data(),
+                                      n_reads, KMU_MEM_HOST, write ? out.seq_offsets.data() : nullptr, write ? ptr(out.seq) : nullptr, cap, total);
+        });
     return out;
 }
 
@@ -2589,8 +2574,7 @@ template <class Kmer>
 ReadUnitigs read_unitigs(const detail::Batch &batch, size_t k, uint32_t w, const GraphParams &g = GraphParams(), FHash fhash = FHash::canon_invhash,
                          uint32_t max_occ = 0, uint32_t max_gap = 5000, uint32_t band_chain = 500, uint32_t min_seeds = 3, uint32_t min_score = 0,
                          uint32_t band = 64, Context &ctx = Context::global()) {
-    const detail::Batch b = detail::unpacked(batch);
-    if (b.on_device()) throw std::invalid_argument("read_unitigs returns host arrays: it needs the sequences in host memory");
+    const detail::Batch b = detail::host_batch("read_unitigs", batch);
     const OverlapGraph graph = read_graph<Kmer>(batch, k, w, g, fhash, max_occ, max_gap, band_chain, min_seeds, min_score, band, ctx);
     ReadUnitigs out;
     out.layout = sg_unitigs(graph.arcs, graph.reads, b.offsets, ctx);
@@ -2630,14 +2614,11 @@ inline CleanGraph sg_clean(const std::vector<kmu_sg_arc> &arcs, const std::vecto
                            uint32_t max_bubble_reads = 8, Context &ctx = Context::global()) {
     if (!reads.empty() && reads.size() != n_reads) throw std::invalid_argument("sg_clean: as many summaries as reads, or none");
     CleanGraph out;
-    out.arcs.assign(arcs.size() + 1, kmu_sg_arc{}); // an empty vector has no address worth passing
-    out.reads.assign(size_t(n_reads) + 1, kmu_sg_read{});
-    const kmu_sg_arc none{};
+    out.arcs.assign(arcs.size(), kmu_sg_arc{});
+    out.reads.assign(n_reads, kmu_sg_read{});
     const kmu_sg_clean_params p{max_tip_reads, max_bubble_reads, 0u, 0u};
-    ctx.check(kmu_sg_clean(ctx.raw(), arcs.empty() ? &none : arcs.data(), arcs.size(), reads.empty() ? nullptr : reads.data(), n_reads, &p, KMU_MEM_HOST,
-                           out.arcs.data(), out.reads.data(), &out.stats));
-    out.arcs.resize(arcs.size());
-    out.reads.resize(n_reads);
+    ctx.check(kmu_sg_clean(ctx.raw(), detail::ptr(arcs), arcs.size(), detail::opt(reads), n_reads, &p, KMU_MEM_HOST, detail::ptr(out.arcs),
+                           detail::ptr(out.reads), &out.stats));
     return out;
 }
 
@@ -2682,22 +2663,17 @@ struct UnitigChains {
 /// chains, classes: the self-join and its classes of overlap_graph (both empty: no contained read is placed); offsets: the batch's.
 inline UnitigChains sg_unitig_chains(const Unitigs &layout, const std::vector<kmu_chain> &chains, const std::vector<uint8_t> &classes,
                                      const std::vector<uint64_t> &offsets, Context &ctx = Context::global()) {
-    if (offsets.empty()) throw std::invalid_argument("sg_unitig_chains: the offsets of a batch have at least one entry");
-    const uint32_t n_reads = uint32_t(offsets.size() - 1);
+    const uint32_t n_reads = detail::n_reads_of("sg_unitig_chains", offsets);
     if (layout.place.size() != n_reads) throw std::invalid_argument("sg_unitig_chains: as many places as reads");
     if (chains.size() != classes.size()) throw std::invalid_argument("sg_unitig_chains: as many classes as chains");
     UnitigChains out;
-    out.records.assign(size_t(n_reads) + 1, kmu_chain{}); // an empty vector has no address worth passing
-    const kmu_sg_unitig no_unitig{};
-    const kmu_sg_step no_step{};
-    const kmu_sg_place no_place{};
+    using detail::opt;
+    using detail::ptr;
+    out.records.assign(n_reads, kmu_chain{});
     const kmu_um_params p{0u, 0u};
     uint64_t total = 0;
-    ctx.check(kmu_sg_unitig_chains(ctx.raw(), layout.unitigs.empty() ? &no_unitig : layout.unitigs.data(), layout.unitigs.size(),
-                                   layout.path.empty() ? &no_step : layout.path.data(), layout.path.size(),
-                                   layout.place.empty() ? &no_place : layout.place.data(), chains.empty() ? nullptr : chains.data(),
-                                   classes.empty() ? nullptr : classes.data(), chains.size(), offsets.data(), n_reads, &p, KMU_MEM_HOST,
-                                   out.records.data(), &out.stats, &total));
+    ctx.check(kmu_sg_unitig_chains(ctx.raw(), ptr(layout.unitigs), layout.unitigs.size(), ptr(layout.path), layout.path.size(), ptr(layout.place), opt(chains),
+                                   opt(classes), chains.size(), offsets.data(), n_reads, &p, KMU_MEM_HOST, ptr(out.records), &out.stats, &total));
     out.records.resize(total);
     return out;
 }
@@ -2726,8 +2702,7 @@ inline PolishedUnitigs polish_unitigs(const Unitigs &layout, const UnitigSequenc
                                       const std::vector<kmu_chain> &chains = {}, const std::vector<uint8_t> &classes = {}, uint32_t band = 64,
                                       uint64_t max_trace_bytes = 0, uint32_t min_depth = 2, uint32_t max_ins = 16, uint32_t rounds = 1,
                                       Context &ctx = Context::global()) {
-    const detail::Batch db = detail::unpacked(reads);
-    if (db.on_device()) throw std::invalid_argument("polish_unitigs returns host arrays: it needs the sequences in host memory");
+    const detail::Batch db = detail::host_batch("polish_unitigs", reads);
     UnitigChains map = sg_unitig_chains(layout, chains, classes, db.offsets, ctx);
     PolishedUnitigs out;
     out.stats = map.stats;
@@ -2839,8 +2814,7 @@ template <class Kmer> class KmerCounter : public KmerCountT<Kmer> {
         if (kmers.empty()) return {};
         ensure(kmers[0].get_nb_base());
         flush();
-        std::vector<uint64_t> keys;
-        for (const Kmer &k : kmers) keys.push_back(k.get_compressed_value());
+        const std::vector<uint64_t> keys = detail::compressed_values(kmers);
         std::vector<uint32_t> c(keys.size());
         ctx_.check(kmu_count_query(counter_, keys.data(), keys.size(), KMU_MEM_HOST, c.data()));
         return c;
@@ -2875,13 +2849,13 @@ template <class Kmer> class KmerCounter : public KmerCountT<Kmer> {
     std::pair<std::vector<uint64_t>, std::vector<uint32_t>> above2_entries() {
         if (!counter_) return {};
         flush();
-        uint64_t n = 0;
-        ctx_.check(kmu_count_dump(counter_, 2, nullptr, nullptr, 0, &n));
-        std::vector<uint64_t> k(std::max<uint64_t>(n, 1));
-        std::vector<uint32_t> c(std::max<uint64_t>(n, 1));
-        ctx_.check(kmu_count_dump(counter_, 2, k.data(), c.data(), n, &n));
-        k.resize(n);
-        c.resize(n);
+        std::vector<uint64_t> k;
+        std::vector<uint32_t> c;
+        detail::two_calls(
+            ctx_, true, [&](uint64_t n) { k.resize(n), c.resize(n); },
+            [&](bool write, uint64_t cap, uint64_t *n) {
+                return kmu_count_dump(counter_, 2, write ? detail::ptr(k) : nullptr, write ? detail::ptr(c) : nullptr, cap, n);
+            });
         return {std::move(k), std::move(c)};
     }
     /// the count spectrum: hist[v] = distinct k-mers whose count (saturated at 2^nb_bits - 1) is v; hist[0] is 0
@@ -2906,12 +2880,11 @@ template <class Kmer> class KmerCounter : public KmerCountT<Kmer> {
         if (!counter_) throw KmuError(KMU_E_BAD_ARG, "get_reads_abundance: nothing has been inserted (the k-mer size is not known yet)");
         flush();
         ReadsAbundance r;
-        r.counts.assign(std::max<size_t>(b.offsets.empty() ? 0 : size_t(b.offsets.back()), 1), 0);
-        r.stats.assign(std::max<size_t>(b.n(), 1), kmu_read_abundance{});
+        r.counts.assign(std::max<size_t>(b.offsets.empty() ? 0 : size_t(b.offsets.back()), 1), 0);   // (without bases: one count, kept as it was)
+        r.stats.assign(b.n(), kmu_read_abundance{});
         if (b.mem() != KMU_MEM_HOST) throw KmuError(KMU_E_UNSUPPORTED, "get_reads_abundance takes host-resident reads");
         ctx_.check(kmu_count_read_profile(counter_, b.bytes.data(), b.offsets.data(), b.n(), KMU_MEM_HOST, solid_min, r.counts.data(),
-                                          r.stats.data()));
-        r.stats.resize(b.n());
+                                          detail::ptr(r.stats)));
         return r;
     }
     uint8_t kmer_size() const { return kmer_size_; }
@@ -3147,15 +3120,13 @@ template <class Kmer> class KmerPrefilter {
     /// one occurrence of a canonical k-mer (the caller passes kmer.reverse_complement().min(kmer))
     void insert_kmer(Kmer kmer) { insert_kmer(std::vector<Kmer>{kmer}); }
     void insert_kmer(const std::vector<Kmer> &kmers) {
-        std::vector<uint64_t> keys;
-        for (const Kmer &k : kmers) keys.push_back(uint64_t(k.get_compressed_value()));
+        const std::vector<uint64_t> keys = detail::compressed_values(kmers);
         ctx_.check(kmu_kfilter_add_kmers(filter_, keys.data(), keys.size(), KMU_MEM_HOST));
     }
     /// 0: never inserted; 1: inserted exactly once; 2: may have been inserted twice or more
     uint8_t seen_class(Kmer kmer) { return seen_class(std::vector<Kmer>{kmer})[0]; }
     std::vector<uint8_t> seen_class(const std::vector<Kmer> &kmers) {
-        std::vector<uint64_t> keys;
-        for (const Kmer &k : kmers) keys.push_back(uint64_t(k.get_compressed_value()));
+        const std::vector<uint64_t> keys = detail::compressed_values(kmers);
         std::vector<uint8_t> cls(keys.size());
         ctx_.check(kmu_kfilter_query(filter_, keys.data(), keys.size(), KMU_MEM_HOST, cls.data()));
         return cls;
