@@ -66,7 +66,10 @@
 #include <unistd.h>
 
 #include <algorithm>
+#include <array>
 #include <atomic>
+#include <charconv>
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -3321,6 +3324,30 @@ class DeviceReads {
         b.dev_offsets = offsets_dev_.as<uint64_t>() + first;
         return b;
     }
+    /// whether the quality lines were kept (a FASTQ text read with_quals), and then the raw quality bytes of reads [first, last)
+    /// laid out as their bases are
+    bool has_quals() const { return quals_.data() != nullptr; }
+    detail::Batch quals_batch(size_t first, size_t last) const {
+        detail::Batch b = batch(first, last);
+        b.dev_bytes = quals_.as<uint8_t>();
+        return b;
+    }
+    /// from_device_text that keeps the quality lines of a FASTQ text on the device too (kmu_ingest_fastq_qual); a FASTA text has none
+    static DeviceReads from_device_text_qual(Context &ctx, const uint8_t *d_text, uint64_t n) {
+        uint8_t first = 0;
+        if (n) ctx.check(kmu_copy_to_host(ctx.raw(), &first, d_text, 1));
+        if (first != '@') return from_device_text(ctx, d_text, n);
+        DeviceReads r;
+        ctx.check(kmu_ingest_fastq_qual(ctx.raw(), d_text, n, KMU_MEM_DEVICE, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, &r.info));
+        r.bases_ = DeviceBuffer(ctx, r.info.kept_bases + 64);
+        r.quals_ = DeviceBuffer(ctx, r.info.kept_bases + 64);
+        r.offsets_dev_ = DeviceBuffer(ctx, (r.info.n_kept + 1) * 8);
+        ctx.check(kmu_ingest_fastq_qual(ctx.raw(), d_text, n, KMU_MEM_DEVICE, r.bases_.as<uint8_t>(), r.bases_.bytes(), r.quals_.as<uint8_t>(),
+                                        r.quals_.bytes(), r.offsets_dev_.as<uint64_t>(), r.info.n_kept + 1, nullptr, &r.info));
+        r.offsets.resize(r.info.n_kept + 1);
+        r.offsets_dev_.download(r.offsets.data(), r.offsets.size() * 8);
+        return r;
+    }
     /// FASTQ / FASTA text already on the device (16-byte aligned) -> accepted reads on the device
     static DeviceReads from_device_text(Context &ctx, const uint8_t *d_text, uint64_t n) {
         DeviceReads r;
@@ -3337,6 +3364,21 @@ class DeviceReads {
     /// as it is in memory (uploads are serialised: one context, one thread at a time), so reading and PCIe overlap.
     static DeviceReads from_file(const std::string &fname, Context &ctx = Context::global(), size_t slab = size_t(64) << 20,
                                  unsigned n_readers = 4) {
+        uint64_t n = 0;
+        const DeviceBuffer text = upload_file(fname, ctx, slab, n_readers, &n);
+        return from_device_text(ctx, text.as<uint8_t>(), n);
+    }
+    /// from_file through from_device_text_qual
+    static DeviceReads from_file_qual(const std::string &fname, Context &ctx = Context::global(), size_t slab = size_t(64) << 20,
+                                      unsigned n_readers = 4) {
+        uint64_t n = 0;
+        const DeviceBuffer text = upload_file(fname, ctx, slab, n_readers, &n);
+        return from_device_text_qual(ctx, text.as<uint8_t>(), n);
+    }
+
+  private:
+    /// the text of a file in a device buffer, *n_out its size
+    static DeviceBuffer upload_file(const std::string &fname, Context &ctx, size_t slab, unsigned n_readers, uint64_t *n_out) {
         const int fd = ::open(fname.c_str(), O_RDONLY);
         if (fd < 0) throw std::runtime_error("cannot open " + fname);
         struct stat st;
@@ -3383,11 +3425,10 @@ class DeviceReads {
         for (auto &t : pool) t.join();
         ::close(fd);
         if (!error.empty()) throw std::runtime_error(error);
-        return from_device_text(ctx, text.as<uint8_t>(), n);
+        *n_out = n;
+        return text;
     }
-
-  private:
-    DeviceBuffer bases_, offsets_dev_;
+    DeviceBuffer bases_, offsets_dev_, quals_;
 };
 
 inline FastqReads parse_fastq_file(const std::string &fname, Context &ctx = Context::global()) {
@@ -3398,6 +3439,170 @@ inline FastqReads parse_fastq_file(const std::string &fname, Context &ctx = Cont
     std::vector<uint8_t> text(size_t(n) + 16);
     in.read(reinterpret_cast<char *>(text.data()), n);
     return parse_fastq_text(text.data(), size_t(n), ctx);
+}
+
+// =====================================================================================================================
+// statutils + quality: the base and quality distributions of a read set, on the device (kmu_read_stats.hip)
+// =====================================================================================================================
+
+/// a double as Rust's `{}` prints it: the shortest decimal that reads back to the same value, never an exponent, no `.0`
+inline std::string rust_display(double x) {
+    if (std::isnan(x)) return "NaN";
+    if (std::isinf(x)) return x > 0 ? "inf" : "-inf";
+    char buf[400];
+    const std::to_chars_result r = std::to_chars(buf, buf + sizeof buf, x, std::chars_format::fixed);
+    return std::string(buf, r.ptr);
+}
+
+/// statutils.rs:38-50.  acgt_distribution: [101][4] row-major, the reads whose base (column A C G T) sits at a percentage (row) over
+/// the number of reads.  The read sizes are the counts of the length buckets of (maxreadlen, prec) -- HdrHistogram's layout,
+/// include/kmu.h -- with histo_out the reads beyond them; non_acgt the bytes that are no base.
+/// value_at_quantile is written from that layout; the hdrhistogram crate's source was not at hand to check its rule to the letter, so
+/// readlen.histo is NOT claimed to be byte for byte the reference's (bases.histo has no such caveat).
+class ReadBaseDistribution {
+  public:
+    std::vector<double> acgt_distribution;
+    std::vector<uint64_t> len_hist;
+    uint64_t nb_reads = 0, upper_histo = 0, histo_out = 0, non_acgt = 0;
+    int prec = 3;
+
+    ReadBaseDistribution(const std::vector<uint64_t> &pct_hist, std::vector<uint64_t> len_hist_, uint64_t nb_reads_, uint64_t histo_out_,
+                         uint64_t non_acgt_, uint64_t maxreadlen, int prec_)
+        : acgt_distribution(pct_hist.size()), len_hist(std::move(len_hist_)), nb_reads(nb_reads_), upper_histo(maxreadlen), histo_out(histo_out_),
+          non_acgt(non_acgt_), prec(prec_ > 5 ? 5 : prec_) {
+        const double inv = 1. / double(nb_reads);   // (statutils.rs:333: the table times the inverse)
+        for (size_t i = 0; i < pct_hist.size(); i++) acgt_distribution[i] = double(pct_hist[i]) * inv;
+    }
+    /// Histogram::len(): the number of recorded lengths
+    uint64_t readsize_len() const {
+        uint64_t n = 0;
+        for (uint64_t c : len_hist) n += c;
+        return n;
+    }
+    /// the highest length of the first bucket whose running count reaches max(1, ceil(q * recorded)); 0 for an empty histogram
+    uint64_t value_at_quantile(double q) const {
+        const uint64_t total = readsize_len();
+        if (total == 0) return 0;
+        const uint64_t need = std::max<uint64_t>(1, std::min<uint64_t>(total, uint64_t(std::ceil(std::min(q, 1.0) * double(total)))));
+        uint64_t running = 0, lowest = 0, highest = 0;
+        for (size_t b = 0; b < len_hist.size(); b++) {
+            running += len_hist[b];
+            if (running >= need) {
+                if (kmu_len_bucket_range(prec, uint32_t(b), &lowest, &highest) != KMU_OK) throw std::invalid_argument("value_at_quantile: bad precision");
+                return highest;
+            }
+        }
+        return highest;
+    }
+    /// 101 lines `a c  g  t ` (statutils.rs:96-103)
+    void ascii_dump_acgt_distribution(const std::string &name) const {
+        std::ofstream f(name, std::ios::trunc);
+        if (!f) throw std::runtime_error("could not open file " + name);
+        for (size_t i = 0; i + 3 < acgt_distribution.size(); i += 4)
+            f << rust_display(acgt_distribution[i]) << " " << rust_display(acgt_distribution[i + 1]) << "  " << rust_display(acgt_distribution[i + 2])
+              << "  " << rust_display(acgt_distribution[i + 3]) << " \n";
+    }
+    /// statutils.rs:118-190, step by step: `readsize  nb reads ` lines at regular quantiles.  A histogram of fewer than 100 entries
+    /// is refused: nothing is written and the error text is returned (empty otherwise).
+    std::string ascii_dump_readlen_distribution(const std::string &name) const {
+        const uint64_t nb_entries = readsize_len();
+        if (nb_entries == 0) return "histogram error!, empty histogram";
+        const uint64_t maxlen = nb_entries;   // (statutils.rs:127: the number of entries, not a length)
+        std::printf("ascii_dump_readlen_distribution nb_entries %llu  maxlen %llu\n", (unsigned long long) nb_entries, (unsigned long long) maxlen);
+        if (nb_entries < 100) {
+            std::printf("Error : ascii_dump_readlen_distribution nb_entries too small : %llu\n", (unsigned long long) nb_entries);
+            return "histogram error!";
+        }
+        const uint64_t nbslot = nb_entries / 100;
+        std::vector<uint64_t> readsize(nbslot + 1);
+        for (uint64_t i = 0; i <= nbslot; i++) readsize[i] = value_at_quantile(double(i) / double(nbslot));
+        const uint64_t nb_points = 1000;
+        std::vector<std::pair<uint64_t, uint64_t>> points;
+        uint64_t first_i = 0, current_i = 0;
+        for (uint64_t j = 0; j < nb_points; j++) {
+            const uint64_t threshold = (maxlen * j) / nb_points;
+            while (readsize[current_i] < threshold && current_i < nbslot) current_i++;
+            if (current_i < nbslot && current_i > first_i) points.emplace_back(readsize[current_i], ((current_i - first_i) * nb_entries) / nbslot);
+            first_i = current_i;
+        }
+        std::ofstream f(name, std::ios::trunc);
+        if (!f) return "could not open file " + name;
+        for (const auto &pt : points) f << pt.first << "  " << pt.second << " \n";
+        return "";
+    }
+};
+
+/// statutils.rs:276-347 on the device: the reads of a batch, in host memory or left on the device by DeviceReads.  (The reference
+/// also writes `bases.histo` into the working directory here; the caller does that, where it wants the file.)
+inline ReadBaseDistribution get_base_count_par(const detail::Batch &reads, uint64_t maxreadlen, uint8_t prec, Context &ctx = Context::global()) {
+    const detail::Batch b = detail::unpacked(reads);
+    kmu_read_stats_params p{};
+    p.sig_digits = prec > 5 ? 5 : prec;
+    p.max_len = maxreadlen;
+    uint32_t n_buckets = 0;
+    uint64_t limit = 0;
+    if (kmu_len_hist_layout(p.max_len, p.sig_digits, &n_buckets, &limit) != KMU_OK)
+        throw std::invalid_argument("get_base_count_par: maxreadlen must be positive and prec at least 1");
+    std::vector<uint64_t> pct(101 * 4), hist(n_buckets);
+    kmu_read_stats_info info{};
+    if (b.on_device()) {
+        DeviceBuffer d_pct(ctx, pct.size() * 8), d_hist(ctx, hist.size() * 8);
+        ctx.check(kmu_read_stats(ctx.raw(), &p, b.bytes_ptr(), b.offsets_ptr(), b.n(), KMU_MEM_DEVICE, nullptr, d_pct.as<uint64_t>(),
+                                 d_hist.as<uint64_t>(), &info));
+        d_pct.download(pct.data(), pct.size() * 8);
+        d_hist.download(hist.data(), hist.size() * 8);
+    } else {
+        ctx.check(kmu_read_stats(ctx.raw(), &p, detail::ptr(b.bytes), b.offsets.data(), b.n(), KMU_MEM_HOST, nullptr, pct.data(), hist.data(), &info));
+    }
+    return ReadBaseDistribution(pct, std::move(hist), info.n_reads, info.histo_out, info.n_other, maxreadlen, p.sig_digits);
+}
+
+/// quality.rs:33-43 in integers: 0 below 0x25, then one class per three values, 7 from 0x37 on
+inline uint8_t remap_quality8(uint8_t q) { return q < 0x25 ? uint8_t(0) : uint8_t(std::min(7, 1 + (int(q) - 0x25) / 3)); }
+
+/// FastqReads with the raw quality byte of every base: quals[offsets[i] + p] belongs to base p of kept read i
+struct FastqQualReads : FastqReads {
+    std::vector<uint8_t> quals;
+};
+/// kmu_ingest_fastq_qual on a host text: the reads kmu_ingest_fastq keeps, and their quality lines
+inline FastqQualReads ingest_fastq_qual(const uint8_t *text, size_t n, Context &ctx = Context::global()) {
+    FastqQualReads r;
+    ctx.check(kmu_ingest_fastq_qual(ctx.raw(), text, n, KMU_MEM_HOST, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, &r.info));
+    r.bases.resize(r.info.kept_bases + 16);
+    r.quals.resize(r.info.kept_bases + 16);
+    r.offsets.resize(r.info.n_kept + 1);
+    ctx.check(kmu_ingest_fastq_qual(ctx.raw(), text, n, KMU_MEM_HOST, r.bases.data(), r.bases.size(), r.quals.data(), r.quals.size(),
+                                    r.offsets.data(), r.offsets.size(), nullptr, &r.info));
+    return r;
+}
+
+/// kmu_read_qual_stats: one record per read and the bases of the batch per quality class
+struct ReadQualityStats {
+    std::vector<kmu_read_qual> reads;
+    std::array<uint64_t, 8> class_hist{};
+};
+/// of a batch whose bytes are raw qualities (DeviceReads::quals_batch, or host arrays); want_reads false: the class totals alone
+inline ReadQualityStats read_quality_stats(const detail::Batch &quals, bool want_reads = true, Context &ctx = Context::global()) {
+    ReadQualityStats r;
+    if (want_reads) r.reads.resize(quals.n());
+    if (quals.on_device()) {
+        DeviceBuffer d_reads(ctx, std::max<uint64_t>(r.reads.size() * sizeof(kmu_read_qual), 16)), d_hist(ctx, 64);
+        ctx.check(kmu_read_qual_stats(ctx.raw(), quals.bytes_ptr(), quals.offsets_ptr(), quals.n(), KMU_MEM_DEVICE,
+                                      want_reads ? d_reads.as<kmu_read_qual>() : nullptr, d_hist.as<uint64_t>()));
+        if (!r.reads.empty()) d_reads.download(r.reads.data(), r.reads.size() * sizeof(kmu_read_qual));
+        d_hist.download(r.class_hist.data(), 64);
+    } else {
+        ctx.check(kmu_read_qual_stats(ctx.raw(), detail::ptr(quals.bytes), quals.offsets.data(), quals.n(), KMU_MEM_HOST,
+                                      want_reads ? detail::ptr(r.reads) : nullptr, r.class_hist.data()));
+    }
+    return r;
+}
+inline ReadQualityStats read_quality_stats(const std::vector<uint8_t> &quals, const std::vector<uint64_t> &offsets, Context &ctx = Context::global()) {
+    detail::Batch b;
+    b.bytes = quals;
+    b.offsets = offsets;
+    detail::n_reads_of("read_quality_stats", offsets);
+    return read_quality_stats(b, true, ctx);
 }
 
 }  // namespace kmerutils

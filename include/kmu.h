@@ -689,6 +689,80 @@ int kmu_ingest_fasta(kmu_ctx *ctx, const uint8_t *text, uint64_t n_bytes, int me
  * '>' FASTA, '@' FASTQ; anything else is KMU_E_BAD_ARG.  (Compressed input is not handled: decompress first.) */
 int kmu_ingest_fastx(kmu_ctx *ctx, const uint8_t *text, uint64_t n_bytes, int mem, uint8_t *bases_out, uint64_t bases_cap,
                      uint64_t *offsets_out, uint64_t offsets_cap, uint32_t *record_index_out, kmu_ingest_info *info);
+/* kmu_ingest_fastq that keeps the quality line: everything kmu_ingest_fastq returns is the same byte for byte (the sizes-only
+ * call with every output NULL included), and quals_out[offsets_out[i] + p] is the raw quality byte of base p of kept read i
+ * (quals_cap >= info->kept_bases; bases_out, quals_out and offsets_out go together).  The quality line starts after the newline
+ * that ends the separator line and ends at the next newline (a '\r' before it is dropped; the last record may have no final
+ * newline, and a '\r' that ends the text is dropped the same way).  A record -- kept or dropped -- whose quality line differs in length from its sequence is KMU_E_BAD_ARG ("invalid
+ * record": needletail refuses such a file), found before any output is written. */
+int kmu_ingest_fastq_qual(kmu_ctx *ctx, const uint8_t *text, uint64_t n_bytes, int mem, uint8_t *bases_out, uint64_t bases_cap,
+                          uint8_t *quals_out, uint64_t quals_cap, uint64_t *offsets_out, uint64_t offsets_cap,
+                          uint32_t *record_index_out, kmu_ingest_info *info);
+
+/* ---- read statistics: the base and quality distributions of a batch -----------------------------------
+ * Reference: get_base_count_par (src/statutils.rs:229-347) -- the read-length histogram and the table of per-read base
+ * percentages that parsefastq writes as readlen.histo and bases.histo -- and remap_quality8 (src/quality/quality.rs:33-43).
+ * Integers only; every output is a pure function of the input (integer atomics that commute), whatever the launch shape.
+ *   class of a base byte   A/a 0, C/c 1, G/g 2, T/t 3, every other byte (N, '\n', 0x00, 0xFF, ...) "other"
+ *   pct of base b          (200 h + L) / (2 L) in integer division for a read of L bases with h of b; 0 for L == 0.  This is
+ *                          ((100 * h) as f64 / L as f64).round() of statutils.rs:255-256: ties go up (L 8, h 1: 13)
+ *   length bucket          HdrHistogram's layout of Histogram::new_with_bounds(1, max_len, sig_digits), statutils.rs:67:
+ *                          sub_bits = ceil(log2(2 * 10^sig_digits)) (5, 8, 11, 15, 18 for 1 .. 5), half = 2^(sub_bits - 1),
+ *                          shift = max(0, floor(log2(len)) - (sub_bits - 1)) (0 for len 0), bucket = shift * half + (len >> shift).
+ *                          ranges = the smallest j >= 1 with 2^sub_bits * 2^(j - 1) > max_len, limit = 2^sub_bits << (ranges - 1),
+ *                          n_buckets = (ranges + 1) * half; a length >= limit has no bucket and is counted in histo_out
+ *                          (record_read_len, statutils.rs:193-199).  max_len 1 000 000, sig_digits 3: limit 1 048 576 and
+ *                          11 264 buckets.  The lowest length of a bucket is (bucket - shift * half) << shift with
+ *                          shift = max(0, bucket / half - 1), its highest that + 2^shift - 1.
+ *   quality class          0 for q < 0x25, else min(7, 1 + (q - 0x25) / 3): remap_quality8's f32 expression on all 256 bytes */
+typedef struct kmu_read_comp {   /* 48 bytes */
+    uint64_t n_base[4];          /* A C G T, either case */
+    uint64_t n_other;
+    uint8_t  pct[4];             /* as defined above */
+    uint32_t len_bucket;         /* 0xFFFFFFFF when the length is >= limit */
+} kmu_read_comp;
+typedef struct kmu_read_stats_params { /* 16 bytes */
+    int32_t  sig_digits;         /* 1 .. 5 */
+    int32_t  flags;              /* 0 */
+    uint64_t max_len;            /* > 0 */
+} kmu_read_stats_params;
+typedef struct kmu_read_stats_info {  /* 96 bytes */
+    uint64_t n_reads, n_bases, n_base[4], n_other;
+    uint64_t n_empty;            /* reads of length 0 */
+    uint64_t histo_out;          /* reads with a length >= limit */
+    uint64_t min_len, max_len;   /* over the reads of the batch; both 0 for n_reads == 0 */
+    uint64_t n_buckets;
+} kmu_read_stats_info;
+typedef struct kmu_read_qual {   /* 80 bytes */
+    uint64_t n_class[8];
+    uint64_t sum_q;              /* sum of the raw bytes */
+    uint8_t  min_q, max_q, median_class, pad[5]; /* min 0xFF / max 0 / median 0 for an empty read;
+                                    median_class = smallest c with 2 * (n_class[0..c] summed) >= len */
+} kmu_read_qual;
+/* the layout of a length histogram and the range of one of its buckets; no device, no context.  KMU_E_BAD_ARG: sig_digits
+ * outside 1 .. 5, max_len == 0, a null output. */
+int kmu_len_hist_layout(uint64_t max_len, int sig_digits, uint32_t *n_buckets, uint64_t *limit);
+int kmu_len_bucket_range(int sig_digits, uint32_t bucket, uint64_t *lowest, uint64_t *highest);
+/* The statistics of the reads offsets[0 .. n_seq] of `bases` (unpacked bytes; offsets[0] need not be 0 nor aligned: the batch may
+ * be a range of a larger one).  comp_out [n_seq], pct_hist [101][4] and len_hist [n_buckets] may each be NULL; info (host memory
+ * in both modes) is required.  pct_hist[p * 4 + b] = the reads whose base b sits at percentage p (an empty read: row 0; every
+ * read adds 4 to the table); len_hist[bucket] = the reads of that bucket.  The call owns its outputs: it zeroes them itself (a
+ * second call into the same buffers gives the same values; device buffers may hold anything on entry).  n_seq == 0 is valid.
+ * KMU_MEM_DEVICE: every array except p and info is device memory, `bases` 16-byte aligned; the call synchronises the stream once,
+ * to hand info over (also in async_device contexts).  KMU_MEM_HOST: through the context's workspace.
+ * KMU_E_BAD_ARG, nothing is written: null ctx / p / info / offsets, null bases with n_seq > 0, sig_digits outside 1 .. 5,
+ * max_len == 0, flags != 0, bad mem. */
+int kmu_read_stats(kmu_ctx *ctx, const kmu_read_stats_params *p, const uint8_t *bases, const uint64_t *offsets, uint32_t n_seq, int mem,
+                   kmu_read_comp *comp_out, uint64_t *pct_hist, uint64_t *len_hist, kmu_read_stats_info *info);
+/* classes_out[i] = the quality class of quals[i]; classes_out == quals is allowed.  KMU_E_BAD_ARG: null ctx, null arrays with n > 0,
+ * bad mem. */
+int kmu_quality_remap(kmu_ctx *ctx, const uint8_t *quals, uint64_t n, int mem, uint8_t *classes_out);
+/* The same walk over the quality bytes of a batch (kmu_ingest_fastq_qual's quals_out with its offsets): out [n_seq] and class_hist
+ * [8] (the batch totals per class) may each be NULL; both are zeroed by the call.  Memory as in kmu_read_stats; the call ends as
+ * every other (no synchronisation of a KMU_MEM_DEVICE call in an async_device context).  KMU_E_BAD_ARG: null ctx / offsets, null
+ * quals with n_seq > 0, bad mem. */
+int kmu_read_qual_stats(kmu_ctx *ctx, const uint8_t *quals, const uint64_t *offsets, uint32_t n_seq, int mem, kmu_read_qual *out,
+                        uint64_t *class_hist);
 
 /* ---- L4 signature comparison: what the callers do with the signatures next --------------------
  * Rows are compared as raw words (4 bytes for KMU_SIG_U32 / F32, 8 for U64 / F64).

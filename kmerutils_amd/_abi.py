@@ -333,6 +333,41 @@ class IngestInfo(C.Structure):
                 ("nb_bad_bases", C.c_uint64), ("nb_bad_reads", C.c_uint64)]
 
 
+RS_PCT_ROWS = 101            # kmu_read_stats: the rows of pct_hist (percentages 0 .. 100), four columns A C G T
+RS_QUAL_CLASSES = 8          # kmu_read_qual_stats / kmu_quality_remap: the classes of remap_quality8
+RS_NO_BUCKET = 0xFFFFFFFF    # kmu_read_comp.len_bucket of a read beyond the histogram
+
+
+class ReadStatsParams(C.Structure):
+    """kmu_read_stats_params: the layout of the length histogram"""
+    _fields_ = [("sig_digits", C.c_int32), ("flags", C.c_int32), ("max_len", C.c_uint64)]
+
+
+class ReadComp(C.Structure):
+    """kmu_read_comp: the base composition of one read (kmu_read_stats)"""
+    _fields_ = [("n_base", C.c_uint64 * 4), ("n_other", C.c_uint64), ("pct", C.c_uint8 * 4), ("len_bucket", C.c_uint32)]
+
+
+READ_STATS_INFO = ("n_reads", "n_bases", "n_base", "n_other", "n_empty", "histo_out", "min_len", "max_len", "n_buckets")
+
+
+class ReadStatsInfo(C.Structure):
+    """kmu_read_stats_info: the totals of one kmu_read_stats call"""
+    _fields_ = [(name, C.c_uint64 * 4 if name == "n_base" else C.c_uint64) for name in READ_STATS_INFO]
+
+
+class ReadQual(C.Structure):
+    """kmu_read_qual: the quality classes of one read (kmu_read_qual_stats)"""
+    _fields_ = [("n_class", C.c_uint64 * 8), ("sum_q", C.c_uint64), ("min_q", C.c_uint8), ("max_q", C.c_uint8),
+                ("median_class", C.c_uint8), ("pad", C.c_uint8 * 5)]
+
+
+# the same records as numpy dtypes (48, 96 and 80 bytes, the field offsets of the structures)
+READ_COMP_DTYPE = [("n_base", "<u8", (4,)), ("n_other", "<u8"), ("pct", "u1", (4,)), ("len_bucket", "<u4")]
+READ_STATS_INFO_DTYPE = [(name, "<u8", (4,)) if name == "n_base" else (name, "<u8") for name in READ_STATS_INFO]
+READ_QUAL_DTYPE = [("n_class", "<u8", (8,)), ("sum_q", "<u8"), ("min_q", "u1"), ("max_q", "u1"), ("median_class", "u1"), ("pad", "u1", (5,))]
+
+
 class KernelStat(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("launches", C.c_uint64), ("total_ms", C.c_double)]
 

@@ -24,7 +24,7 @@
 namespace kmu {
 
 static constexpr uint32_t ING_REGION = 16384; // bytes walked by one wave
-enum : uint32_t { IERR_HEADER = 1u, IERR_SEPARATOR = 2u };
+enum : uint32_t { IERR_HEADER = 1u, IERR_SEPARATOR = 2u, IERR_QUAL_LEN = 8u };
 
 // 16-bit mask of the bytes of an aligned 16-byte chunk at `pos` that are '\n' (bytes at or past n are ignored)
 __device__ __forceinline__ uint32_t newline_mask16(const uint8_t *text, uint64_t pos, uint64_t n) {
@@ -138,9 +138,10 @@ __global__ void __launch_bounds__(1024) k_scan_tiles(const T *in, uint64_t n, co
     if (blockIdx.x == 0 && threadIdx.x == 0) out[n] = tile_off[n_tiles];
 }
 
-// line walk: seq_start[r] / seq_end[r] of every record
+// line walk: seq_start[r] / seq_end[r] of every record, and (qual_start non-null) qual_start[r] / qual_end[r] of its quality line
 __global__ void __launch_bounds__(256) k_ing_lines(const uint8_t *text, uint64_t n, uint64_t n_regions, const uint64_t *line_base,
-                                                   uint64_t n_records, uint64_t *seq_start, uint64_t *seq_end, uint32_t *err) {
+                                                   uint64_t n_records, uint64_t *seq_start, uint64_t *seq_end, uint32_t *err,
+                                                   uint64_t *qual_start, uint64_t *qual_end) {
     const uint64_t wave_global = ((uint64_t) blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const uint64_t nwaves = ((uint64_t) gridDim.x * blockDim.x) >> 6;
     uint32_t bad = 0;
@@ -162,6 +163,10 @@ __global__ void __launch_bounds__(256) k_ing_lines(const uint8_t *text, uint64_t
                 if (rec < n_records) {
                     if (kind == 0u) seq_start[rec] = p + 1;
                     if (kind == 1u) seq_end[rec] = (p > 0 && text[p - 1] == '\r') ? p - 1 : p;
+                    if (qual_start) {
+                        if (kind == 2u) qual_start[rec] = p + 1;
+                        if (kind == 3u) qual_end[rec] = text[p - 1] == '\r' ? p - 1 : p;
+                    }
                 }
                 if (p + 1 < n) {
                     const uint64_t nrec = (l + 1) >> 2;
@@ -176,7 +181,16 @@ __global__ void __launch_bounds__(256) k_ing_lines(const uint8_t *text, uint64_t
         }
     }
     if (wave_global == 0 && lane_id() == 0 && n_records && text[0] != '@') bad |= IERR_HEADER;
+    if (wave_global == 0 && lane_id() == 0 && qual_start && n_records && text[n - 1] != '\n') // (no final newline: the text ends the line)
+        qual_end[n_records - 1] = text[n - 1] == '\r' ? n - 1 : n;
     if (bad) atomicOr(err, bad);
+}
+
+// a quality line has the length of its sequence line, in every record
+__global__ void __launch_bounds__(256) k_ing_qual_check(const uint64_t *seq_start, const uint64_t *seq_end, const uint64_t *qual_start,
+                                                        const uint64_t *qual_end, uint64_t n_records, uint32_t *err) {
+    for (uint64_t r = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x; r < n_records; r += (uint64_t) gridDim.x * blockDim.x)
+        if (qual_end[r] - qual_start[r] != seq_end[r] - seq_start[r]) atomicOr(err, IERR_QUAL_LEN);
 }
 
 // per record: non-ACGT bytes; keep flag and kept length; totals[0] += bases, [1] += bad bases, [2] += bad reads
@@ -230,6 +244,16 @@ __global__ void __launch_bounds__(256) k_ing_copy(const uint8_t *text, const uin
         }
     }
     if (blockIdx.x == 0 && threadIdx.x == 0) offsets_out[rank[n_records]] = out_off[n_records];
+}
+
+// the quality bytes of the kept records, through the same keep / length / offset arrays
+__global__ void __launch_bounds__(256) k_ing_copy_qual(const uint8_t *text, const uint64_t *qual_start, const uint32_t *keep,
+                                                       const uint64_t *kept_len, const uint64_t *out_off, uint64_t n_records, uint8_t *quals_out) {
+    for (uint64_t r = blockIdx.x; r < n_records; r += gridDim.x) {
+        if (!keep[r]) continue;
+        const uint64_t src = qual_start[r], dst = out_off[r], len = kept_len[r];
+        for (uint64_t i = threadIdx.x; i < len; i += blockDim.x) quals_out[dst + i] = text[src + i];
+    }
 }
 
 // ---- FASTA ---------------------------------------------------------------------------------------------------------------
@@ -345,10 +369,18 @@ namespace kmu {
 int device_scan_u32(kmu_ctx *ctx, const uint32_t *in, uint64_t n, uint64_t *out) { return device_scan<uint32_t>(ctx, in, n, out); }
 }
 
-// steps 3 and 4 shared by both formats: filter the records [seq_start, seq_end) of `d_text`, scan, copy out
+// the quality lines of a FASTQ text for ingest_filter_copy: where they start and end, and the caller's array for the kept ones
+struct IngestQuals {
+    const uint64_t *qstart, *qend;
+    uint8_t *quals_out;
+    uint64_t quals_cap;
+};
+
+// steps 3 and 4 shared by both formats: filter the records [seq_start, seq_end) of `d_text`, scan, copy out; quals (kmu_ingest_fastq_qual,
+// null otherwise): the quality lines are checked before the first read-back and copied beside the bases
 static int ingest_filter_copy(kmu_ctx *ctx, const uint8_t *d_text, uint64_t n_text, uint64_t n_records, void *sstart, void *send,
                               void *scal, int mem, uint8_t *bases_out, uint64_t bases_cap, uint64_t *offsets_out,
-                              uint64_t offsets_cap, uint32_t *record_index_out, kmu_ingest_info *info) {
+                              uint64_t offsets_cap, uint32_t *record_index_out, kmu_ingest_info *info, const IngestQuals *quals = nullptr) {
     uint64_t *ooff, *rank, *klen;
     uint32_t *keep;
     KMU_TRY(dev_array(ctx, "ing.keep", n_records + 1, &keep));
@@ -360,6 +392,9 @@ static int ingest_filter_copy(kmu_ctx *ctx, const uint8_t *d_text, uint64_t n_te
                    n_records, keep, klen, (unsigned long long *) scal));
     KMU_TRY(device_scan(ctx, keep, n_records, rank));
     KMU_TRY(device_scan(ctx, klen, n_records, ooff));
+    if (quals)
+        KMU_TRY(launch(ctx, "k_ing_qual_check", k_ing_qual_check, dim3(grid_for(ctx, n_records, 256)), dim3(256), 0, (const uint64_t *) sstart,
+                       (const uint64_t *) send, quals->qstart, quals->qend, n_records, (uint32_t *) scal + 8));
     uint64_t h_scal[8], n_kept = 0, kept_bases = 0;
     KMU_HIP(ctx, hipMemcpyAsync(h_scal, scal, 64, hipMemcpyDeviceToHost, ctx->stream));
     KMU_HIP(ctx, hipMemcpyAsync(&n_kept, rank + n_records, 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -368,18 +403,21 @@ static int ingest_filter_copy(kmu_ctx *ctx, const uint8_t *d_text, uint64_t n_te
     const uint32_t errw = (uint32_t) h_scal[4];
     if (errw & IERR_HEADER) return fail(ctx, KMU_E_BAD_ARG, "invalid record: a header line does not start with '@'");
     if (errw & IERR_SEPARATOR) return fail(ctx, KMU_E_BAD_ARG, "invalid record: a separator line does not start with '+'");
+    if (errw & IERR_QUAL_LEN) return fail(ctx, KMU_E_BAD_ARG, "invalid record: a quality line differs in length from its sequence");
     info->n_records = n_records;
     info->n_kept = n_kept;
     info->kept_bases = kept_bases;
     info->n_bases = h_scal[0];
     info->nb_bad_bases = h_scal[1];
     info->nb_bad_reads = h_scal[2];
-    if (!bases_out && !offsets_out) return KMU_OK; // sizes only
+    uint8_t *quals_out = quals ? quals->quals_out : nullptr;
+    if (!bases_out && !offsets_out && !quals_out) return KMU_OK; // sizes only
     if (!bases_out || !offsets_out) return fail(ctx, KMU_E_BAD_ARG, "bases_out and offsets_out go together");
-    if (bases_cap < kept_bases || offsets_cap < n_kept + 1)
-        return fail(ctx, KMU_E_BAD_ARG, "output too small: need %llu bases and %llu offsets", (unsigned long long) kept_bases,
-                    (unsigned long long) (n_kept + 1));
-    uint8_t *d_bases = bases_out;
+    if (quals && !quals_out) return fail(ctx, KMU_E_BAD_ARG, "bases_out, quals_out and offsets_out go together");
+    if (bases_cap < kept_bases || offsets_cap < n_kept + 1 || (quals && quals->quals_cap < kept_bases))
+        return fail(ctx, KMU_E_BAD_ARG, "output too small: need %llu bases%s and %llu offsets", (unsigned long long) kept_bases,
+                    quals ? " (as many bytes in quals_out)" : "", (unsigned long long) (n_kept + 1));
+    uint8_t *d_bases = bases_out, *d_quals = quals_out;
     uint64_t *d_off = offsets_out;
     uint32_t *d_idx = record_index_out;
     if (mem == KMU_MEM_HOST) {
@@ -388,10 +426,13 @@ static int ingest_filter_copy(kmu_ctx *ctx, const uint8_t *d_text, uint64_t n_te
         d_bases = (uint8_t *) q;
         KMU_TRY(dev_array(ctx, "ing.off", n_kept + 1, &d_off));
         if (record_index_out) KMU_TRY(dev_array(ctx, "ing.idx", n_kept + 1, &d_idx));
+        if (quals) KMU_TRY(dev_array(ctx, "ing.quals", kept_bases + 64, &d_quals));
     }
     KMU_TRY(launch(ctx, "k_ing_copy", k_ing_copy, dim3(grid_r), dim3(256), 0, d_text, (const uint64_t *) sstart, keep, klen, rank, ooff, n_records,
                    d_bases, d_off, d_idx));
+    if (quals) KMU_TRY(launch(ctx, "k_ing_copy_qual", k_ing_copy_qual, dim3(grid_r), dim3(256), 0, d_text, quals->qstart, keep, klen, ooff, n_records, d_quals));
     if (mem == KMU_MEM_HOST) {
+        if (quals) KMU_HIP(ctx, hipMemcpyAsync(quals_out, d_quals, kept_bases, hipMemcpyDeviceToHost, ctx->stream));
         KMU_HIP(ctx, hipMemcpyAsync(bases_out, d_bases, kept_bases, hipMemcpyDeviceToHost, ctx->stream));
         KMU_HIP(ctx, hipMemcpyAsync(offsets_out, d_off, (n_kept + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
         if (record_index_out)
@@ -446,9 +487,10 @@ static int ingest_empty(kmu_ctx *ctx, int mem, uint64_t *offsets_out, uint64_t o
     return KMU_OK;
 }
 
-extern "C" int kmu_ingest_fastq(kmu_ctx *ctx, const uint8_t *text, uint64_t n_bytes, int mem, uint8_t *bases_out,
-                                uint64_t bases_cap, uint64_t *offsets_out, uint64_t offsets_cap, uint32_t *record_index_out,
-                                kmu_ingest_info *info) {
+// kmu_ingest_fastq, and with want_quals kmu_ingest_fastq_qual
+static int ingest_fastq(kmu_ctx *ctx, const uint8_t *text, uint64_t n_bytes, int mem, uint8_t *bases_out, uint64_t bases_cap, bool want_quals,
+                        uint8_t *quals_out, uint64_t quals_cap, uint64_t *offsets_out, uint64_t offsets_cap, uint32_t *record_index_out,
+                        kmu_ingest_info *info) {
     if (!ctx || !info || (n_bytes && !text)) return fail(ctx, KMU_E_BAD_ARG, "null argument");
     memset(info, 0, sizeof *info);
     KMU_HIP(ctx, hipSetDevice(ctx->device));
@@ -466,10 +508,28 @@ extern "C" int kmu_ingest_fastq(kmu_ctx *ctx, const uint8_t *text, uint64_t n_by
     uint64_t *send, *sstart;
     KMU_TRY(dev_array(ctx, "ing.sstart", n_records + 1, &sstart));
     KMU_TRY(dev_array(ctx, "ing.send", n_records + 1, &send));
+    uint64_t *qend = nullptr, *qstart = nullptr;
+    if (want_quals) {
+        KMU_TRY(dev_array(ctx, "ing.qstart", n_records + 1, &qstart));
+        KMU_TRY(dev_array(ctx, "ing.qend", n_records + 1, &qend));
+    }
     KMU_TRY(launch(ctx, "k_ing_lines", k_ing_lines, dim3(grid_w), dim3(256), 0, d_text, n_bytes, n_regions, (const uint64_t *) lbase, n_records,
-                   sstart, send, (uint32_t *) scal + 8));
+                   sstart, send, (uint32_t *) scal + 8, qstart, qend));
+    const IngestQuals q = {qstart, qend, quals_out, quals_cap};
     return ingest_filter_copy(ctx, d_text, n_bytes, n_records, sstart, send, scal, mem, bases_out, bases_cap, offsets_out,
-                              offsets_cap, record_index_out, info);
+                              offsets_cap, record_index_out, info, want_quals ? &q : nullptr);
+}
+
+extern "C" int kmu_ingest_fastq(kmu_ctx *ctx, const uint8_t *text, uint64_t n_bytes, int mem, uint8_t *bases_out,
+                                uint64_t bases_cap, uint64_t *offsets_out, uint64_t offsets_cap, uint32_t *record_index_out,
+                                kmu_ingest_info *info) {
+    return ingest_fastq(ctx, text, n_bytes, mem, bases_out, bases_cap, false, nullptr, 0, offsets_out, offsets_cap, record_index_out, info);
+}
+
+extern "C" int kmu_ingest_fastq_qual(kmu_ctx *ctx, const uint8_t *text, uint64_t n_bytes, int mem, uint8_t *bases_out, uint64_t bases_cap,
+                                     uint8_t *quals_out, uint64_t quals_cap, uint64_t *offsets_out, uint64_t offsets_cap,
+                                     uint32_t *record_index_out, kmu_ingest_info *info) {
+    return ingest_fastq(ctx, text, n_bytes, mem, bases_out, bases_cap, true, quals_out, quals_cap, offsets_out, offsets_cap, record_index_out, info);
 }
 
 extern "C" int kmu_ingest_fasta(kmu_ctx *ctx, const uint8_t *text, uint64_t n_bytes, int mem, uint8_t *bases_out,

@@ -156,6 +156,12 @@ def _entry_points():
     d("kmu_ingest_fastq", ingest)
     d("kmu_ingest_fasta", ingest)
     d("kmu_ingest_fastx", ingest)
+    d("kmu_ingest_fastq_qual", ingest[:6] + [vp, C.c_uint64] + ingest[6:])
+    d("kmu_len_hist_layout", [C.c_uint64, C.c_int, u32p, u64p], plain=True)
+    d("kmu_len_bucket_range", [C.c_int, C.c_uint32, u64p, u64p], plain=True)
+    d("kmu_read_stats", [vp, C.POINTER(A.ReadStatsParams), vp, vp, C.c_uint32, C.c_int, vp, vp, vp, C.POINTER(A.ReadStatsInfo)])
+    d("kmu_quality_remap", [vp, vp, C.c_uint64, C.c_int, vp])
+    d("kmu_read_qual_stats", [vp, vp, vp, C.c_uint32, C.c_int, vp, vp])
     return table
 
 
@@ -169,6 +175,8 @@ SYMBOLS = list(_ENTRY_POINTS)
 Components = collections.namedtuple("Components", "label cluster size members n_components")
 COMPONENTS_WANT = ("cluster", "size", "members")
 MINIMIZERS_WANT = ("pos", "read", "strand")  # the optional outputs of Context.read_minimizers
+READ_STATS_WANT = ("comp", "pct", "len")     # the optional outputs of Context.read_stats
+READ_QUAL_WANT = ("reads", "hist")           # the optional outputs of Context.read_qual_stats
 PILE_CALL_WANT = ("call", "reads")           # the outputs of Context.pile_call
 
 
@@ -822,17 +830,31 @@ class Context:
         """kmu_ingest_fastx: FASTA or FASTQ by the first byte (needletail::parse_fastx_file)"""
         return self.ingest_fastq(text, want_index, fn="kmu_ingest_fastx")
 
+    def ingest_fastq_qual(self, text, want_index=False):
+        """kmu_ingest_fastq_qual: ingest_fastq that keeps the quality line -> (bases, quals, offsets, info[, record_index]);
+        quals[offsets[i] + p] is the raw quality byte of base p of kept read i"""
+        return self.ingest_fastq(text, want_index, fn="kmu_ingest_fastq_qual")
+
     def ingest_fastq(self, text, want_index=False, fn="kmu_ingest_fastq"):
         """kmu_ingest_fastq: FASTQ text (bytes / numpy uint8 on the host, torch uint8 tensor on the device) -> (bases,
         offsets, info[, record_index]) of the reads made of ACGTacgt only, in file order."""
-        call = getattr(self.L, fn)
+        quals = fn == "kmu_ingest_fastq_qual"
+        entry = getattr(self.L, fn)
+
+        def call(text_p, bases, offs, idx, qual, info):
+            """one call of the entry point; kmu_ingest_fastq_qual has quals_out and quals_cap behind bases_cap"""
+            cap = 0 if bases is None else bases.shape[0]
+            more = (_ptr(qual)[0], cap) if quals else ()
+            return entry(self.h, text_p, n, mem, _ptr(bases)[0], cap, *more, _ptr(offs)[0], 0 if offs is None else offs.shape[0], _ptr(idx)[0],
+                         C.byref(info))
         if isinstance(text, (bytes, bytearray, memoryview)):
             text = np.frombuffer(bytes(text), np.uint8)
         dev = _is_torch(text) and text.is_cuda
         mem = A.MEM_DEVICE if dev else A.MEM_HOST
         n = int(text.shape[0])
         info = A.IngestInfo()
-        self._check(call(self.h, _ptr(text)[0] if n else None, n, mem, None, 0, None, 0, None, C.byref(info)))
+        self._check(call(_ptr(text)[0] if n else None, None, None, None, None, info))
+        qual = self._new_like(text, max(int(info.kept_bases), 1), np.uint8, "uint8") if quals else None
         if dev:
             import torch
             bases = torch.zeros(max(int(info.kept_bases), 1), dtype=torch.uint8, device=text.device)
@@ -843,10 +865,61 @@ class Context:
             offs = np.zeros(int(info.n_kept) + 1, np.uint64)
             idx = np.zeros(max(int(info.n_kept), 1), np.uint32) if want_index else None
         info2 = A.IngestInfo()
-        self._check(call(self.h, _ptr(text)[0] if n else None, n, mem, _ptr(bases)[0], bases.shape[0], _ptr(offs)[0],
-                         offs.shape[0], _ptr(idx)[0], C.byref(info2)))
-        res = (bases[:int(info.kept_bases)], offs, info2)
+        self._check(call(_ptr(text)[0] if n else None, bases, offs, idx, qual, info2))
+        res = (bases[:int(info.kept_bases)],) + ((qual[:int(info.kept_bases)],) if quals else ()) + (offs, info2)
         return res + (idx[:int(info.n_kept)],) if want_index else res
+
+    # ---- read statistics (kmu_read_stats.hip) ----
+    def read_stats(self, bases, offsets, max_len=1000000, sig_digits=3, want=READ_STATS_WANT, into=None):
+        """kmu_read_stats: the base composition of every read, the 101 x 4 table of base percentages, the length histogram in
+        HdrHistogram's layout of (max_len, sig_digits) and the totals.  Returns (comp, pct_hist, len_hist, info); an output that
+        `want` leaves out is None.  comp: A.READ_COMP_DTYPE records on the host, an int32 tensor [n, 12] holding the same bits
+        on the device; pct_hist [101, 4] and len_hist [n_buckets]: uint64 (int64 tensors); info: a dict of A.READ_STATS_INFO.
+        into=(comp, pct_hist, len_hist): arrays to fill instead of new ones (the call zeroes them itself)."""
+        unknown = [w for w in want if w not in READ_STATS_WANT]
+        if unknown:
+            raise ValueError("want holds %r: the optional outputs are %r" % (unknown, READ_STATS_WANT))
+        n_buckets, _ = len_hist_layout(max_len, sig_digits)
+        mem = self._mem(bases)
+        off = self._offsets_like(offsets, bases, mem)
+        n = int(off.shape[0]) - 1
+        if into is not None:
+            comp, pct, hist = into
+        else:
+            comp = self._records(bases, n, A.READ_COMP_DTYPE) if "comp" in want else None
+            pct = self._new_like(bases, (A.RS_PCT_ROWS, 4), np.uint64, "int64") if "pct" in want else None
+            hist = self._new_like(bases, n_buckets, np.uint64, "int64") if "len" in want else None
+        p, info = A.ReadStatsParams(sig_digits, 0, max_len), A.ReadStatsInfo()
+        ptr = self._ptrs(bases)
+        self._check(self.L.kmu_read_stats(self.h, C.byref(p), ptr(bases), _ptr(off)[0], n, mem, _ptr(comp)[0], _ptr(pct)[0], _ptr(hist)[0],
+                                          C.byref(info)))
+        info = {k: [int(x) for x in info.n_base] if k == "n_base" else int(getattr(info, k)) for k in A.READ_STATS_INFO}
+        return (comp[:n] if comp is not None else None), pct, hist, info
+
+    def quality_remap(self, quals, out=None):
+        """kmu_quality_remap: the class (remap_quality8: 0 .. 7) of every quality byte; out=quals remaps in place"""
+        mem = self._mem(quals)
+        n = int(quals.shape[0])
+        if out is None:
+            out = self._new_like(quals, max(n, 1), np.uint8, "uint8")
+        ptr = self._ptrs(quals)
+        self._check(self.L.kmu_quality_remap(self.h, ptr(quals), n, mem, ptr(out, n)))
+        return out[:n]
+
+    def read_qual_stats(self, quals, offsets, want=READ_QUAL_WANT):
+        """kmu_read_qual_stats: (records, class_hist) -- one A.READ_QUAL_DTYPE record per read (an int32 tensor [n, 20] holding
+        the same bits on the device) and the bases of the batch per quality class, uint64 [8]; one not in `want` is None"""
+        unknown = [w for w in want if w not in READ_QUAL_WANT]
+        if unknown:
+            raise ValueError("want holds %r: the optional outputs are %r" % (unknown, READ_QUAL_WANT))
+        mem = self._mem(quals)
+        off = self._offsets_like(offsets, quals, mem)
+        n = int(off.shape[0]) - 1
+        recs = self._records(quals, n, A.READ_QUAL_DTYPE) if "reads" in want else None
+        hist = self._new_like(quals, A.RS_QUAL_CLASSES, np.uint64, "int64") if "hist" in want else None
+        ptr = self._ptrs(quals)
+        self._check(self.L.kmu_read_qual_stats(self.h, ptr(quals), _ptr(off)[0], n, mem, _ptr(recs)[0], _ptr(hist)[0]))
+        return (recs[:n] if recs is not None else None), hist
 
     # ---- signature comparison (kmu_compare.hip) ----
     @staticmethod
@@ -1692,6 +1765,24 @@ class Counter(_Handle):
 
     def retain_part(self, part, n_parts):
         self.ctx._check(self.L.kmu_count_retain_part(self.h, part, n_parts))
+
+
+def len_hist_layout(max_len, sig_digits):
+    """kmu_len_hist_layout (plain host code): (n_buckets, limit) of the length histogram of kmu_read_stats"""
+    n, limit = C.c_uint32(), C.c_uint64()
+    rc = load().kmu_len_hist_layout(int(max_len), int(sig_digits), C.byref(n), C.byref(limit))
+    if rc != A.OK:
+        raise KmuError(rc, "max_len must be positive and sig_digits in [1, 5]")
+    return int(n.value), int(limit.value)
+
+
+def len_bucket_range(sig_digits, bucket):
+    """kmu_len_bucket_range (plain host code): the (lowest, highest) length of a bucket"""
+    lo, hi = C.c_uint64(), C.c_uint64()
+    rc = load().kmu_len_bucket_range(int(sig_digits), int(bucket), C.byref(lo), C.byref(hi))
+    if rc != A.OK:
+        raise KmuError(rc, "sig_digits must be in [1, 5]")
+    return int(lo.value), int(hi.value)
 
 
 def kfilter_cells_for(expected_distinct, bits_per_kmer=16):

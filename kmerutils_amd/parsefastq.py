@@ -9,6 +9,11 @@ k == 16, Kmer32bit for k <= 14.
 
 `--repeated [--filter-bits N]` counts through the Bloom prefilter (kmercount.count_repeated_kmers' order of calls): two passes
 over the reads, the k-mers seen once stay off the table, and the dump is byte for byte that of the plain count.
+
+`--stats` is what the reference's tool does before it counts (parsefastq.rs:193-203): `get_base_count_par(reads, 1000000, 3)`, then
+`bases.histo` and `readlen.histo` in --outdir, and for a FASTQ text `quality.histo`, eight lines `class<TAB>number of bases` of the
+kept reads' qualities (remap_quality8).  Off by default: a run without it writes what it always wrote.  This tool has no task word
+(it always counted), so `--stats --no-count` is the statistics alone, what the C++ tool does for `--stats` without a `kmer` task.
 """
 import argparse
 import os
@@ -31,6 +36,21 @@ def kmer_type_for(k):
     raise ValueError("no k-mer type for k = %d (parsefastq.rs:215-236)" % k)
 
 
+def write_stats(ctx, bases, quals, offsets, outdir):
+    """parsefastq.rs:193-203: bases.histo, readlen.histo (its refusal of fewer than 100 reads is discarded, as upstream) and, where
+    there are qualities, quality.histo"""
+    from . import statutils
+    dist = statutils.get_base_count_par((bases, offsets), 1000000, 3, ctx=ctx)
+    print("nb read outside max size for histogram %d" % dist.histo_out, file=sys.stderr)  # statutils.rs:338-341
+    dist.ascii_dump_acgt_distribution(os.path.join(outdir, "bases.histo"))
+    dist.ascii_dump_readlen_distribution(os.path.join(outdir, "readlen.histo"))
+    if quals is not None:
+        _, hist = ctx.read_qual_stats(quals, offsets, want=("hist",))
+        with open(os.path.join(outdir, "quality.histo"), "w") as f:
+            for c in range(A.RS_QUAL_CLASSES):
+                f.write("%d\t%d\n" % (c, hist[c]))
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="parsefastq", description=__doc__.splitlines()[0])
     ap.add_argument("-f", "--file", required=True)
@@ -43,8 +63,14 @@ def main(argv=None):
     ap.add_argument("--repeated", action="store_true", help="count through the Bloom prefilter (count_repeated_kmers): two passes "
                     "over the reads, the k-mers seen once stay off the table; the dump is that of the plain count")
     ap.add_argument("--filter-bits", type=int, default=16, metavar="N", help="with --repeated: filter bits per k-mer occurrence")
+    ap.add_argument("--stats", action="store_true", help="before the count: bases.histo, readlen.histo and (FASTQ) quality.histo in "
+                    "--outdir (get_base_count_par, parsefastq.rs:193-203)")
+    ap.add_argument("--no-count", action="store_true", help="with --stats: write the statistics and stop (this tool has no `kmer` task "
+                    "word to leave out, as the C++ tool has)")
     ap.add_argument("--device", type=int, default=0)
     args = ap.parse_args(argv)
+    if args.no_count and (not args.stats or args.unique or args.repeated or args.histo):
+        ap.error("--no-count goes with --stats alone")
     if args.repeated and args.histo:
         ap.error("--histo with --repeated: the table holds no singletons, bin 1 would be meaningless")
     if args.repeated and args.unique:
@@ -53,9 +79,18 @@ def main(argv=None):
     ctx = lib.Context(args.device)
     t0 = time.time()
     text = np.fromfile(args.file, dtype=np.uint8)
-    bases, offsets, info = ctx.ingest_fastx(text)
+    quals = None
+    if args.stats and text.size and text[0] == ord("@"):
+        bases, quals, offsets, info = ctx.ingest_fastq_qual(text)
+    else:
+        bases, offsets, info = ctx.ingest_fastx(text)
     print(" nb rec loaded = %d \nnb_bases %d\nnb_bad_bases %d\nnb_bad_read %d" %
           (info.n_kept, info.n_bases, info.nb_bad_bases, info.nb_bad_reads), file=sys.stderr)  # io.rs:63-68
+    if args.stats:
+        write_stats(ctx, bases, quals, offsets, args.outdir)
+    if args.no_count:
+        ctx.close()
+        return 0
     if args.unique:  # filter1_kmer_16b32bit + dump_in_file_once_kmer16b32bit -> <file>.once_kmer.bin
         from . import kmercount
         flt = kmercount.KmerFilter1(16, max(1024, int(info.kept_bases)), ctx=ctx)

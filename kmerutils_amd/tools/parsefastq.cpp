@@ -1,5 +1,5 @@
-// parsefastq -f reads.fastq kmer (--count -s <kmer size> [--repeated [--filter-bits n]] | --unique) [-t threads] [-b 2] [--outdir dir]
-//            [--device n] [--histo file]
+// parsefastq -f reads.fastq [--stats] [kmer (--count -s <kmer size> [--repeated [--filter-bits n]] | --unique)] [-t threads] [-b 2]
+//            [--outdir dir] [--device n] [--histo file]
 //
 // The counting branch of the reference's tool (src/bin/parsefastq.rs:215-236: `kmer --count`) on the GPU path: the FASTQ
 // text is filtered on the device like parse_with_needletail does on the host (src/io.rs:37-57), every canonical k-mer of
@@ -12,6 +12,10 @@
 // over the reads, the k-mers seen once stay off the table; the dump is byte for byte that of the plain count, counts >= 2 being
 // exact either way.  `--filter-bits <n>`: filter bits per k-mer occurrence (default 16).  `--histo` is refused with it: the table
 // holds no singletons, bin 1 would be meaningless.
+// `--stats` is what the reference's tool does before it counts (parsefastq.rs:193-203): get_base_count_par(reads, 1000000, 3), then
+// bases.histo and readlen.histo in --outdir (the refusal of fewer than 100 reads is discarded, as upstream), and for a FASTQ text
+// quality.histo, eight lines `class<TAB>number of bases` of the kept reads' qualities (remap_quality8).  Off by default: a run without
+// it writes what it always wrote.  It needs no `kmer` task: `parsefastq -f reads.fastq --stats` writes the statistics alone.
 // Kmer type by size as upstream: k <= 14 Kmer32bit, k == 16 Kmer16b32bit, else Kmer64bit (k <= 31).
 #include <chrono>
 #include <cstdio>
@@ -23,9 +27,23 @@
 using namespace kmerutils;
 
 static void usage() {
-    std::fprintf(stderr, "usage: parsefastq -f <fastq> kmer (--count -s <kmer size> [--repeated [--filter-bits <n>]] | --unique) [-t <threads>] [-b 2] "
-                         "[--outdir <dir>] [--device <n>] [--histo <file>]\n");
+    std::fprintf(stderr, "usage: parsefastq -f <fastq> [--stats] [kmer (--count -s <kmer size> [--repeated [--filter-bits <n>]] | --unique)] "
+                         "[-t <threads>] [-b 2] [--outdir <dir>] [--device <n>] [--histo <file>]\n");
     std::exit(2);
+}
+
+// parsefastq.rs:193-203, and the quality classes where the text had quality lines
+static void write_stats(const DeviceReads &reads, const std::string &outdir, Context &ctx) {
+    const ReadBaseDistribution dist = get_base_count_par(reads.batch(0, reads.nb_reads()), 1000000, 3, ctx);
+    std::fprintf(stderr, "nb read outside max size for histogram %llu\n", (unsigned long long) dist.histo_out);   // statutils.rs:338-341
+    dist.ascii_dump_acgt_distribution(outdir + "/bases.histo");
+    (void) dist.ascii_dump_readlen_distribution(outdir + "/readlen.histo");
+    if (!reads.has_quals()) return;
+    const ReadQualityStats q = read_quality_stats(reads.quals_batch(0, reads.nb_reads()), false, ctx);
+    std::FILE *f = std::fopen((outdir + "/quality.histo").c_str(), "w");
+    if (!f) throw std::runtime_error("cannot write " + outdir + "/quality.histo");
+    for (size_t c = 0; c < q.class_hist.size(); c++) std::fprintf(f, "%zu\t%llu\n", c, (unsigned long long) q.class_hist[c]);
+    std::fclose(f);
 }
 
 template <class Kmer>
@@ -61,7 +79,7 @@ static void count_and_dump(const DeviceReads &reads, uint8_t kmer_size, const st
 int main(int argc, char **argv) {
     std::string fname, outdir = ".", histo;
     long kmer_size = 0, device = 0, filter_bits = 16;
-    bool count = false, kmer_cmd = false, unique = false, repeated = false;
+    bool count = false, kmer_cmd = false, unique = false, repeated = false, stats = false;
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
         auto next = [&]() -> const char * {
@@ -83,10 +101,12 @@ int main(int argc, char **argv) {
         else if (a == "--device") device = std::atol(next());
         else if (a == "--histo") histo = next();
         else if (a == "--repeated") repeated = true;
+        else if (a == "--stats") stats = true;
         else if (a == "--filter-bits") filter_bits = std::atol(next());
         else usage();
     }
-    if (fname.empty() || !kmer_cmd || (!count && !unique) || (count && (kmer_size < 1 || kmer_size > 31))) usage();
+    const bool stats_alone = stats && !kmer_cmd && !count && !unique;
+    if (fname.empty() || (!stats_alone && (!kmer_cmd || (!count && !unique))) || (count && (kmer_size < 1 || kmer_size > 31))) usage();
     if (repeated && (!count || unique || filter_bits < 1)) usage();
     if (repeated && !histo.empty()) {
         std::fprintf(stderr, "--histo with --repeated: the table holds no singletons, bin 1 would be meaningless\n");
@@ -95,14 +115,16 @@ int main(int argc, char **argv) {
     try {
         const auto t0 = std::chrono::steady_clock::now();
         Context ctx{int(device)};
-        DeviceReads reads = DeviceReads::from_file(fname, ctx);
+        DeviceReads reads = stats ? DeviceReads::from_file_qual(fname, ctx) : DeviceReads::from_file(fname, ctx);
         std::fprintf(stderr, " nb reads %llu, nb bases %llu, nb bad bases %llu, nb reads with non acgt %llu\n",
                      (unsigned long long) reads.info.n_records, (unsigned long long) reads.info.n_bases,
                      (unsigned long long) reads.info.nb_bad_bases, (unsigned long long) reads.info.nb_bad_reads);
+        if (stats) write_stats(reads, outdir, ctx);
         // the tool writes <basename>.multi_kmer.bin into the working directory (parsefastq.rs:207-211)
         const size_t slash = fname.rfind('/');
         const std::string dumpfname = outdir + "/" + (slash == std::string::npos ? fname : fname.substr(slash + 1)) + ".multi_kmer.bin";
-        if (unique) {   // KmerProcessing::Unicity (parsefastq.rs:238-247): filter1_kmer_16b32bit + the once-k-mer dump
+        if (stats_alone) {   // no k-mer task: the statistics were all there was to do
+        } else if (unique) {   // KmerProcessing::Unicity (parsefastq.rs:238-247): filter1_kmer_16b32bit + the once-k-mer dump
             KmerFilter1 filter(16, uint32_t(std::min<uint64_t>(std::max<uint64_t>(reads.info.kept_bases, 1024), 0xFFFFFFFFu)), ctx);
             detail::Batch all = reads.batch(0, reads.nb_reads());
             filter.insert_reads(all);
