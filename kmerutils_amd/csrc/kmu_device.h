@@ -108,6 +108,13 @@ __device__ __forceinline__ void step_val_rc(const StepWin &s, uint32_t j, uint64
     val = ((s.hi << (2 * j)) | (((uint64_t) s.w2 << (2 * j)) >> 32)) >> s.sh;
     rc = (j ? (s.rlo >> (2 * j)) | ((uint64_t) s.rhi << (64 - 2 * j)) : s.rlo) & s.kmask;
 }
+// the same where j is a lane's own offset (k_multiset_uq, k_multiset_long): no select for j = 0, whose lane mask is a thread constant that
+// the compiler forms in front of the read loop and keeps in (or reloads into) a pair of scalar registers for every key.  R's top word
+// stands 32 bits up and goes the remaining 32 - 2 j: at j = 0 it leaves the 64 bits by itself.
+__device__ __forceinline__ void step_val_rc_lane(const StepWin &s, uint32_t j, uint64_t &val, uint64_t &rc) {
+    val = ((s.hi << (2 * j)) | (((uint64_t) s.w2 << (2 * j)) >> 32)) >> s.sh;
+    rc = ((s.rlo >> (2 * j)) | (((uint64_t) s.rhi << 32) << (32 - 2 * j))) & s.kmask;
+}
 __device__ __forceinline__ uint64_t step_canonical(const StepWin &s, uint32_t j) {
     uint64_t val, rc;
     step_val_rc(s, j, val, rc);
@@ -374,6 +381,35 @@ __device__ __forceinline__ int lane_id() { return (int) (threadIdx.x & 63u); }
 // store of the wave (s_waitcnt vmcnt(0)), which serialises HBM streaming against the LDS phases of a kernel; use this
 // one where the waves of a workgroup hand data to each other through LDS alone.
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+// A field of the kernel's argument block, read from the kernarg segment WHERE IT IS USED (one s_load there) instead of at the kernel's
+// entry.  An argument taken by value is loaded at the top and stays live to its last use: in a kernel whose read loop already fills the
+// scalar register file, every such field is one more SGPR spilled to a lane of a VGPR and reloaded around the loop.  The pointer goes
+// through an empty asm statement, so the load can neither be merged with the entry's loads nor hoisted out of a loop.  `byte_off`: the
+// field's offset in the argument block, which must be the kernel's first argument (KMU_COLD_ARG, kmu_sketch_kernels.h).
+template <typename T>
+__device__ __forceinline__ T kernarg_at(uint32_t byte_off) {
+    const __attribute__((address_space(4))) uint8_t *p =
+        (const __attribute__((address_space(4))) uint8_t *) __builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(p));
+    return *reinterpret_cast<const __attribute__((address_space(4))) T *>(p + byte_off);
+}
+// A uniform value the compiler is to know nothing about from here on: what is derived from the result is formed behind this point (not
+// in front of a loop around it, to be kept -- or spilled -- across everything the loop holds).
+__device__ __forceinline__ uint32_t opaque_u32(uint32_t v) {
+    asm volatile("" : "+s"(v));
+    return v;
+}
+// The same for a lane's own value: a test of the result (`lane == 0`) is one compare where it stands, not a lane mask formed at the
+// kernel's entry and held in two scalar registers; an LDS address formed from it is an add in the lane, not a scalar kept from the entry.
+__device__ __forceinline__ uint32_t opaque_lane_u32(uint32_t v) {
+    asm volatile("" : "+v"(v));
+    return v;
+}
+// `p`, `byte_off` bytes on (an opaque zero of the lane: the address is then one add of a literal in the lane)
+template <typename T>
+__device__ __forceinline__ T *lane_ptr(T *p, uint32_t byte_off) {
+    return reinterpret_cast<T *>(reinterpret_cast<uint8_t *>(p) + byte_off);
+}
 // inclusive prefix sum over the 64 lanes with DPP moves (row_shr 1/2/4/8 inside the rows of 16, then row_bcast15 /
 // row_bcast31 across rows): six VALU instructions, no LDS crossbar round trips.  All lanes must be active.
 __device__ __forceinline__ uint32_t wave_incl_scan_u32(uint32_t v) {

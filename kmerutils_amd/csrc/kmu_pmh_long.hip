@@ -61,13 +61,13 @@ __global__ void __launch_bounds__(1024, 4) k_multiset_long(SketchArgs a) {
     for (uint32_t i = tid; i < UQ_BUCKETS + 1; i += UQ_THREADS) bst[i] = 0;
     auto take = [&]() -> uint32_t { // thread 0: the next queue entry (the queue is asked a read before the chunk runs out)
         if (misc[8] == misc[9]) {
-            if (!misc[11]) misc[10] = atomicAdd(a.queue, (uint32_t) QCHUNK);
+            if (!misc[11]) misc[10] = atomicAdd(KMU_COLD_ARG(queue), (uint32_t) QCHUNK);
             misc[8] = misc[10];
             misc[9] = misc[10] + QCHUNK;
             misc[11] = 0;
         }
         const uint32_t v = misc[8]++;
-        if (misc[8] == misc[9] && !misc[11]) { misc[10] = atomicAdd(a.queue, (uint32_t) QCHUNK); misc[11] = 1; }
+        if (misc[8] == misc[9] && !misc[11]) { misc[10] = atomicAdd(KMU_COLD_ARG(queue), (uint32_t) QCHUNK); misc[11] = 1; }
         return v;
     };
     if (tid == 0) {
@@ -77,7 +77,10 @@ __global__ void __launch_bounds__(1024, 4) k_multiset_long(SketchArgs a) {
     __syncthreads();
     const uint64_t off_first = uniform_u64(a.offsets[0]);
     const uint64_t total = a.total_bytes ? a.total_bytes : uniform_u64(a.offsets[a.n_seq]);
-    auto seq_of = [&](uint32_t q) -> uint32_t { return a.read_list ? a.read_list[q] : q; };
+    auto seq_of = [&](uint32_t q) -> uint32_t {
+        const uint32_t *rl = KMU_COLD_ARG(read_list);
+        return rl ? rl[q] : q;
+    };
     uint32_t r = uniform_u32(misc[4]);
     uint32_t rs = r < a.n_queue ? uniform_u32(seq_of(r)) : 0u; // the sequence
     SeqView sv;
@@ -124,11 +127,12 @@ __global__ void __launch_bounds__(1024, 4) k_multiset_long(SketchArgs a) {
                     }
                     lds_barrier();
                     const uint32_t span_t = span - t0; // places of this tile and the ones behind it
+                    const int kq = (int) opaque_u32((uint32_t) k); // (the k-mer mask and shift: formed here, as in k_multiset_uq)
 #pragma unroll
                     for (int q0 = 0; q0 < UQ_KREG; q0 += 4) {
                         if (!(4u * (uint32_t) UQ_THREADS * (uint32_t) (q0 >> 2) < span_t)) continue;
                         const uint32_t wi = ((uint32_t) tid >> 2) + (uint32_t) (UQ_THREADS / 4) * (uint32_t) (q0 >> 2); // the quarter's word
-                        const StepWin sw = step_win(words[wi], words[wi + 1], words[wi + 2], k);
+                        const StepWin sw = step_win(words[wi], words[wi + 1], words[wi + 2], kq);
                         // the four keys of the quarter first, then their four ds_add_rtn, then the answers: no answer is looked at inside the
                         // per-lane branch that asked for it (where it was waited for on the spot: one LDS round trip per key, in turn)
                         uint64_t key[4];
@@ -139,7 +143,7 @@ __global__ void __launch_bounds__(1024, 4) k_multiset_long(SketchArgs a) {
                             part[u] = 0xFFFFFFFFu; // no key
                             if (t0 + place_of(q0 + u) - l0 < nk) {
                                 uint64_t val, rc;
-                                step_val_rc(sw, 4u * ((uint32_t) tid & 3u) + (uint32_t) u, val, rc);
+                                step_val_rc_lane(sw, 4u * ((uint32_t) tid & 3u) + (uint32_t) u, val, rc);
                                 key[u] = FAST ? int64_hash(rc < val ? rc : val) : apply_fhash(cfg, val, rc);
                                 part[u] = pmh_long_part_of(key[u], P);
                             }
@@ -234,9 +238,11 @@ __global__ void __launch_bounds__(1024, 4) k_multiset_long(SketchArgs a) {
                         ct += (uint32_t) __popcll(cm[u]);
                     }
                     uint32_t ub = 0, cb = 0; // one atomic per wave, list and group of four register slots
-                    if (lane == 0) {
-                        if (ut) ub = atomicAdd(&misc[0], ut);
-                        if (ct) cb = atomicAdd(&misc[1], ct);
+                    // (lane 0 by a compare made here, the counters addressed from the lane: see opaque_lane_u32)
+                    const uint32_t ln = opaque_lane_u32((uint32_t) lane), z0 = opaque_lane_u32(0u);
+                    if (ln == 0) {
+                        if (ut) ub = atomicAdd(lane_ptr(misc, z0), ut);
+                        if (ct) cb = atomicAdd(lane_ptr(misc + 1, z0), ct);
                     }
                     ub = bcast_u32(ub, 0);
                     cb = bcast_u32(cb, 0);
@@ -322,27 +328,28 @@ __global__ void __launch_bounds__(1024, 4) k_multiset_long(SketchArgs a) {
             __syncthreads(); // (the entries set aside have reached memory; ccnt[] is written)
             if (!over) {
                 n_u = uniform_u32(misc[0]);
+                uint32_t *lst_w = KMU_COLD_ARG(lst_w);
                 for (uint32_t p = 0; p < P; p++) {
                     const uint32_t n_c = uniform_u32(ccnt[p]);
                     const uint64_t *seg = seg0 + (uint64_t) p * DEF_SEG;
                     const uint32_t *seg_w = reinterpret_cast<const uint32_t *>(seg + UQ_KEYS + UQ_COLL);
                     for (uint32_t i = tid; i < n_c; i += UQ_THREADS) {
                         a.lst_keys[lb + n_u + n_ct + i] = ld_scr(&seg[UQ_KEYS + i]);
-                        a.lst_w[lb + n_u + n_ct + i] = ld_scr(&seg_w[i]);
+                        lst_w[lb + n_u + n_ct + i] = ld_scr(&seg_w[i]);
                     }
                     n_ct += n_c;
                 }
             }
         }
         if (tid == 0) {
-            if (mine && !over) { a.lst_n[rs] = n_u + n_ct; a.lst_nu[rs] = n_u; }
+            if (mine && !over) { KMU_COLD_ARG(lst_n)[rs] = n_u + n_ct; KMU_COLD_ARG(lst_nu)[rs] = n_u; }
             else if (nk != 0) { // the general kernel's
-                a.lst_n[rs] = 0u;
-                a.lst_nu[rs] = 0u;
-                a.redo_list[atomicAdd(a.queue + 56, 1u)] = rs;
+                KMU_COLD_ARG(lst_n)[rs] = 0u;
+                KMU_COLD_ARG(lst_nu)[rs] = 0u;
+                KMU_COLD_ARG(redo_list)[atomicAdd(KMU_COLD_ARG(queue) + 56, 1u)] = rs;
             }
         }
-        if (bad) atomicOr(a.err, DERR_NON_ACGT);
+        if (bad) atomicOr(KMU_COLD_ARG(err), DERR_NON_ACGT);
         r = r_next;
         rs = uniform_u32(rs_n);
         if (has_next) {

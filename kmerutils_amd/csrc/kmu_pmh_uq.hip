@@ -39,7 +39,7 @@ __global__ void __launch_bounds__(UQ_THREADS, MINW) k_multiset_uq(SketchArgs a) 
     uint32_t *bst = dw + UQ_COLL;          // UQ_BUCKETS + 1
     uint32_t *words = bst + UQ_BUCKETS + 1; // UQ_TILE
     uint32_t *wtot = words + UQ_TILE;       // one per wave
-    // [0] unique entries, [1] keys in collision groups, [4] first read, [5] the read after the current one
+    // [0] unique entries, [1] keys in collision groups, [4] first read, [5] the read after it, [6] the queue entry taken last (three reads ahead)
     uint32_t *misc = wtot + UQ_THREADS / 64;
     // the next read's chunks land here straight from HBM (global_load_lds: no register is held while they are in flight):
     // chunk t of the read at byte 16 t, i.e. lane l of the wave instruction that fetches chunks 64 j .. 64 j + 63 at 1024 j + 16 l
@@ -54,25 +54,29 @@ __global__ void __launch_bounds__(UQ_THREADS, MINW) k_multiset_uq(SketchArgs a) 
     // is (in LDS: registers of thread 0 alone would be registers of every thread)
     auto take = [&]() -> uint32_t { // thread 0: the next queue entry (the queue is asked a read before the chunk runs out)
         if (misc[8] == misc[9]) {
-            if (!misc[11]) misc[10] = atomicAdd(a.queue, (uint32_t) QCHUNK);
+            if (!misc[11]) misc[10] = atomicAdd(KMU_COLD_ARG(queue), (uint32_t) QCHUNK);
             misc[8] = misc[10];
             misc[9] = misc[10] + QCHUNK;
             misc[11] = 0;
         }
         const uint32_t v = misc[8]++;
-        if (misc[8] == misc[9] && !misc[11]) { misc[10] = atomicAdd(a.queue, (uint32_t) QCHUNK); misc[11] = 1; }
+        if (misc[8] == misc[9] && !misc[11]) { misc[10] = atomicAdd(KMU_COLD_ARG(queue), (uint32_t) QCHUNK); misc[11] = 1; }
         return v;
     };
     if (tid == 0) {
         misc[8] = misc[9] = misc[10] = misc[11] = 0;
         misc[4] = take();
         misc[5] = take(); // the header of a read is fetched TWO reads ahead: its words can then be requested a whole read ahead
+        misc[6] = take(); // ... and its entry of read_list (the second shape's launch) THREE reads ahead: the header's address is then known
     }
     __syncthreads();
     const uint64_t off_first = uniform_u64(a.offsets[0]);
     const uint64_t total = a.total_bytes ? a.total_bytes : uniform_u64(a.offsets[a.n_seq]);
     // queue entry q stands for sequence read_list[q] when a list is given (the second shape's launch), else for sequence q
-    auto seq_of = [&](uint32_t q) -> uint32_t { return a.read_list ? a.read_list[q] : q; };
+    auto seq_of = [&](uint32_t q) -> uint32_t {
+        const uint32_t *rl = KMU_COLD_ARG(read_list);
+        return rl ? rl[q] : q;
+    };
     uint32_t r = uniform_u32(misc[4]);
     uint32_t rs = r < a.n_queue ? uniform_u32(seq_of(r)) : 0u; // the sequence
     SeqView sv;
@@ -100,7 +104,12 @@ __global__ void __launch_bounds__(UQ_THREADS, MINW) k_multiset_uq(SketchArgs a) 
         nv.len = uniform_u64(a.offsets[rs_next + 1]) - nv.begin;
         nv_mine = fits(nv);
     }
-    __syncthreads(); // (misc[5] is rewritten at the top of the first turn)
+    // the read after next: its sequence is known from the start of the current read's turn (asked for a turn earlier, looked at at the end
+    // of that turn: the list entry and the header it points to are a dependent pair of round trips, and every wave of the workgroup sat
+    // out the first of them at the top of each turn)
+    uint32_t r_nn = uniform_u32(misc[6]);
+    uint32_t rs_nn = r_nn < a.n_queue ? uniform_u32(seq_of(r_nn)) : 0u;
+    __syncthreads(); // (misc[6] is rewritten at the top of the first turn)
     uint32_t pf_bad = 0; // non-ACGT bytes among this thread's words of the current read, fetched a read ahead
     bool pf_valid = false;                    // uniform
     auto n_words = [&](const SeqView &v) -> uint32_t { // staged words of a read of 1 .. UQ_KEYS k-mers (its k-mers' windows + 1)
@@ -109,7 +118,7 @@ __global__ void __launch_bounds__(UQ_THREADS, MINW) k_multiset_uq(SketchArgs a) 
     };
     while (r < a.n_queue) {
         if (tid == 0) {
-            misc[5] = take(); // the read after the next one
+            misc[6] = take(); // the read three behind the current one
             misc[0] = 0;
             misc[1] = 0;
         }
@@ -117,7 +126,7 @@ __global__ void __launch_bounds__(UQ_THREADS, MINW) k_multiset_uq(SketchArgs a) 
         const uint32_t nk = L >= (uint32_t) k ? L - (uint32_t) k + 1u : 0u;
         const bool mine = nk >= 1u && nk + seq_lead(sv) <= UQ_KEYS; // else: no k-mer at all (row of zeros), or the general kernel's
         uint32_t bad = 0;
-        if (L == 0 && tid == 0) atomicOr(a.err, DERR_EMPTY_SEQ);
+        if (L == 0 && tid == 0) atomicOr(KMU_COLD_ARG(err), DERR_EMPTY_SEQ);
         if (nk == 0) bad |= wave_validate_seq(sv, wave, UQ_THREADS / 64, false);
         const uint32_t lead = seq_lead(sv), wfirst = lead >> 4;
         if (mine) { // stage the read's code words (prefetched ones first), wipe the bitmaps
@@ -138,10 +147,10 @@ __global__ void __launch_bounds__(UQ_THREADS, MINW) k_multiset_uq(SketchArgs a) 
             }
         }
         lds_barrier();
-        const uint32_t r_nn = uniform_u32(misc[5]);
         const bool has_nn = r_nn < a.n_queue;
-        // the header of the read after next: requested now, looked at at the end of this turn
-        const uint32_t rs_nn = has_nn ? seq_of(r_nn) : 0u;
+        // the header of the read after next, and the list entry of the read behind it: requested now, looked at at the end of this turn
+        const uint32_t r_n3 = uniform_u32(misc[6]);
+        const uint32_t rs_n3 = r_n3 < a.n_queue ? seq_of(r_n3) : 0u;
         const uint64_t nn_o0 = has_nn ? a.offsets[rs_nn] : 0ull, nn_o1 = has_nn ? a.offsets[rs_nn + 1] : 0ull;
         // the next read's chunks: requested now, they land in LDS under the key phase and become code words behind it
         // (round 2 requested them behind the key phase and converted them on the spot: 12 % of a read's turn in that wait).
@@ -185,6 +194,9 @@ __global__ void __launch_bounds__(UQ_THREADS, MINW) k_multiset_uq(SketchArgs a) 
             const uint32_t l0 = lead - 16u * wfirst; // place of the read's first base
             auto key_phase = [&](auto fast_tag) __attribute__((always_inline)) {
                 constexpr bool FAST = decltype(fast_tag)::value;
+                // (k-mer mask and shift are formed HERE, once per read: formed in front of the read loop they were spilled across it and
+                //  reloaded -- three v_readlane_b32 and their s_nop -- for every key)
+                const int kq = (int) opaque_u32((uint32_t) k);
 #pragma unroll
                 for (int q0 = 0; q0 < UQ_KREG; q0 += 4) {
                     if (!group_used(q0)) {
@@ -197,7 +209,7 @@ __global__ void __launch_bounds__(UQ_THREADS, MINW) k_multiset_uq(SketchArgs a) 
                     }
                     uint32_t bit[4], rbw[4], rbb[4]; // a slot's word of the bitmap and its bit there
                     const uint32_t wi = ((uint32_t) tid >> 2) + (uint32_t) (UQ_THREADS / 4) * (uint32_t) (q0 >> 2); // the quarter's word
-                    const StepWin sw = step_win(words[wi], words[wi + 1], words[wi + 2], k);
+                    const StepWin sw = step_win(words[wi], words[wi + 1], words[wi + 2], kq);
                     // (round 4, measured and not kept: a branch-free form for the waves whose quarters are whole -- 10.6 against 10.1 ms
                     //  per launch, 19 instead of 15 spilled registers)
 #pragma unroll
@@ -210,7 +222,7 @@ __global__ void __launch_bounds__(UQ_THREADS, MINW) k_multiset_uq(SketchArgs a) 
                         rk[q] = 0;
                         if (place_of(q) - l0 < nk) {
                             uint64_t val, rc;
-                            step_val_rc(sw, 4u * ((uint32_t) tid & 3u) + (uint32_t) u, val, rc);
+                            step_val_rc_lane(sw, 4u * ((uint32_t) tid & 3u) + (uint32_t) u, val, rc);
                             const uint64_t key = FAST ? int64_hash(rc < val ? rc : val) : apply_fhash(cfg, val, rc);
                             rk[q] = key;
                             const uint32_t bi = bm_index(key);
@@ -280,9 +292,11 @@ __global__ void __launch_bounds__(UQ_THREADS, MINW) k_multiset_uq(SketchArgs a) 
                     ct += (uint32_t) __popcll(cm[u]);
                 }
                 uint32_t ub = 0, cb = 0; // one atomic per wave, list and group of four register slots
-                if (lane == 0) {
-                    if (ut) ub = atomicAdd(&misc[0], ut);
-                    if (ct) cb = atomicAdd(&misc[1], ct);
+                // (lane 0 by a compare made here, the counters addressed from the lane: see opaque_lane_u32)
+                const uint32_t ln = opaque_lane_u32((uint32_t) lane), z0 = opaque_lane_u32(0u);
+                if (ln == 0) {
+                    if (ut) ub = atomicAdd(lane_ptr(misc, z0), ut);
+                    if (ct) cb = atomicAdd(lane_ptr(misc + 1, z0), ct);
                 }
                 ub = bcast_u32(ub, 0);
                 cb = bcast_u32(cb, 0);
@@ -353,30 +367,35 @@ __global__ void __launch_bounds__(UQ_THREADS, MINW) k_multiset_uq(SketchArgs a) 
                             }
                     }
                 lds_barrier();
+                uint32_t *lst_w = KMU_COLD_ARG(lst_w);
                 for (uint32_t i = tid; i < n_c; i += UQ_THREADS) {
                     a.lst_keys[lb + n_u + i] = dk[i];
-                    a.lst_w[lb + n_u + i] = dw[i];
+                    lst_w[lb + n_u + i] = dw[i];
                 }
                 bst[2 * tid] = 0;
                 bst[2 * tid + 1] = 0;
             }
-            if (tid == 0 && !over) { a.lst_n[rs] = n_u + n_c; a.lst_nu[rs] = n_u; }
+            if (tid == 0 && !over) { KMU_COLD_ARG(lst_n)[rs] = n_u + n_c; KMU_COLD_ARG(lst_nu)[rs] = n_u; }
         }
         if (tid == 0) {
-            if (nk == 0) a.lst_n[rs] = 0u; // no k-mer: k_pmh_points writes the row of an empty multiset
+            if (nk == 0) KMU_COLD_ARG(lst_n)[rs] = 0u; // no k-mer: k_pmh_points writes the row of an empty multiset
             else if (!mine || over) {       // the next kernel's: longer than the registers, or too repetitive
-                a.lst_n[rs] = 0u;
-                a.redo_list[atomicAdd(a.queue + 56, 1u)] = rs;
+                KMU_COLD_ARG(lst_n)[rs] = 0u;
+                KMU_COLD_ARG(redo_list)[atomicAdd(KMU_COLD_ARG(queue) + 56, 1u)] = rs;
             }
         }
-        if (bad) atomicOr(a.err, DERR_NON_ACGT);
+        if (bad) atomicOr(KMU_COLD_ARG(err), DERR_NON_ACGT);
         pf_valid = nv_mine;
         r = r_next;
         rs = rs_next;
         sv = nv;
         r_next = r_nn;
-        rs_next = uniform_u32(rs_nn);
+        rs_next = rs_nn;
+        r_nn = r_n3;
+        rs_nn = uniform_u32(rs_n3);
         nv_mine = false;
+        // (measured and not kept: the header words looked at on every path, which takes the compiler's `vmcnt(0)` -- pending on the path
+        //  without a read after next -- from the top of the next turn: 7.58-7.59 against 7.57-7.59 ms per launch)
         if (has_nn) {
             nv.begin = uniform_u64(nn_o0);
             nv.len = uniform_u64(nn_o1) - nv.begin;

@@ -74,6 +74,9 @@ struct SketchArgs {
     uint32_t *queue; // atomic read counter
     uint32_t *err;
 };
+// field `f` of a kernel's SketchArgs, fetched where the kernel uses it (kernarg_at): for the fields a kernel looks at once per read or
+// less, in the kernels whose read loop leaves no scalar register for them (k_multiset_uq, k_multiset_long)
+#define KMU_COLD_ARG(f) kernarg_at<decltype(SketchArgs::f)>((uint32_t) offsetof(SketchArgs, f))
 
 // misc words in LDS
 enum { M_READ = 0, M_NSCR = 1, M_NEXT = 2, M_DEF = 3, M_QMAX = 4 /* 4,5: u64 */, M_FLAGS = 6 /* 6,7 */, M_WORDS = 8 };
