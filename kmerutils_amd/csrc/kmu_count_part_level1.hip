@@ -177,7 +177,7 @@ __global__ void __launch_bounds__(SCATTER_THREADS) k_part_scatter1(const uint8_t
     SegOut sg;
     uint32_t *cursor;
     seg_open(ls, bins1, blockIdx.x % seg.sets, seg.cap, seg.ovf, seg.state, sg, cursor);
-    const uint64_t total = offsets[n_seq];
+    const uint64_t total = offsets[n_seq], start = offsets[0];
     const uint64_t nsteps_all = flat_wave_steps(total);
     const uint64_t nsteps = seg.step_end ? seg.step_end : nsteps_all;
     const UnitSteps u = unit_steps(seg.step_base, pl.steps_per_unit, nsteps);
@@ -189,7 +189,7 @@ __global__ void __launch_bounds__(SCATTER_THREADS) k_part_scatter1(const uint8_t
     const Digit d1 = plan_digit1(pl);
     for (uint64_t t0 = u.s0; t0 < u.s1; t0 += u.nwaves) {
         uint64_t it[16];
-        flat_step_words(bases, total, t0 + u.wave, t0 + u.wave < u.s1, raw, w0, ex, bad);
+        flat_step_words(bases, total, start, t0 + u.wave, t0 + u.wave < u.s1, raw, w0, ex, bad);
         flat_step_items_nv(k, t0 + u.wave < u.s1, w0, ex, raw.nv, it);
         // the next step's chunks and its "no k-mer" bits are requested now; they arrive under the tile sort, which waits for them
         // before its write-out

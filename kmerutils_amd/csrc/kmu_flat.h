@@ -35,9 +35,20 @@ __device__ __forceinline__ uint32_t wave_find_read_from(const uint64_t *offsets,
     return wave_find_read(offsets, n, g);
 }
 
-// the code words of wave step `st`: this lane's word and (lanes 0/1) the two words after the wave's last
+// The non-ACGT bits of the 16-base word at flat position g0 that are the call's, the first read starting at `lo`: the stream of a
+// device range `offsets + first` begins up to 1023 bases before its first read (flat_stream_extent), and what lies there belongs to
+// reads the call was not given -- staged host input never holds them.  Callers ask only for the steps that begin before `lo`
+// (wave-uniform: the first step of a stream, the first two of the super-k-mer walk).  Behind the last read nothing is to be done:
+// load_code_word keeps the bits below `total`, and the prefetched form is taken only where every word of the step is whole.
+__device__ __forceinline__ uint32_t bad_from(uint32_t bad, uint64_t g0, uint64_t lo) {
+    const uint32_t lead = lo > g0 ? (lo - g0 < 16 ? (uint32_t) (lo - g0) : 16u) : 0u;
+    return bad & ~((1u << lead) - 1u);
+}
+
+// the code words of wave step `st`: this lane's word and (lanes 0/1) the two words after the wave's last; bad_acc collects the
+// non-ACGT bytes of the lane's word at or behind flat position `lo`
 __device__ __forceinline__ void flat_step_load(const uint8_t *bases, uint64_t total, uint64_t st, bool active, uint32_t &w0,
-                                               uint32_t &ex, uint32_t *bad_acc = nullptr) {
+                                               uint32_t &ex, uint32_t *bad_acc = nullptr, uint64_t lo = 0) {
     w0 = 0;
     ex = 0;
     if (!active) return; // wave-uniform
@@ -46,7 +57,9 @@ __device__ __forceinline__ void flat_step_load(const uint8_t *bases, uint64_t to
     uint32_t bad, bad2;
     w0 = load_code_word(s, st * 64 + (uint64_t) lane_id(), bad);
     ex = load_code_word(s, st * 64 + 64 + (uint64_t) (lane_id() & 1), bad2);
-    if (bad_acc) *bad_acc |= bad; // (every word is some step's own word: the halo words need no second look)
+    if (!bad_acc) return;
+    if (st * 1024 < lo) bad = bad_from(bad, (st * 64 + (uint64_t) lane_id()) * 16, lo);
+    *bad_acc |= bad; // (every word is some step's own word: the halo words need no second look)
 }
 
 // One wave step (64 words = 1024 bases) of the flat base stream, from its loaded words (flat_step_load): f(j, canon, r) for
@@ -98,12 +111,12 @@ __device__ __forceinline__ void flat_step_visit_words(const uint64_t *offsets, u
     }
 }
 
-// the same from the bases: load + visit.  Returns a non-zero mask if this lane saw a non-ACGT byte.
+// the same from the bases: load + visit.  Returns a non-zero mask if this lane saw a non-ACGT byte at or behind `lo`.
 template <bool FAST, typename F>
 __device__ __forceinline__ uint32_t flat_step_visit(const uint8_t *bases, const uint64_t *offsets, uint32_t n_seq, uint64_t total,
                                                     uint64_t lo, int k, uint64_t st, uint32_t &r_hint, F &&f) {
     uint32_t w0, ex, bad = 0;
-    flat_step_load(bases, total, st, true, w0, ex, &bad);
+    flat_step_load(bases, total, st, true, w0, ex, &bad, lo);
     flat_step_visit_words<FAST>(offsets, n_seq, total, lo, k, st, w0, ex, r_hint, f);
     return bad;
 }
@@ -136,7 +149,7 @@ __device__ __forceinline__ void flat_step_fetch(const uint8_t *bases, uint64_t t
     r.c0 = *reinterpret_cast<const uint4 *>(bases + (a0 < lastc ? a0 : lastc));
     r.cx = *reinterpret_cast<const uint4 *>(bases + (ax < lastc ? ax : lastc));
 }
-__device__ __forceinline__ void flat_step_words(const uint8_t *bases, uint64_t total, uint64_t st, bool active, const FlatRaw &r,
+__device__ __forceinline__ void flat_step_words(const uint8_t *bases, uint64_t total, uint64_t lo, uint64_t st, bool active, const FlatRaw &r,
                                                 uint32_t &w0, uint32_t &ex, uint32_t &bad_acc) {
     w0 = 0;
     ex = 0;
@@ -152,6 +165,7 @@ __device__ __forceinline__ void flat_step_words(const uint8_t *bases, uint64_t t
         w0 = load_code_word(s, i0, bad);
         ex = load_code_word(s, ix, bad2);
     }
+    if (st * 1024 < lo) bad = bad_from(bad, i0 * 16, lo); // (the stream's first step)
     bad_acc |= bad; // (every word is some step's own word: the halo words need no second look)
 }
 

@@ -24,6 +24,12 @@ namespace kmu {
 static constexpr int SMER_STEP_WORDS = 61; // code words whose k-mers one wave step emits
 static constexpr int SMER_THREADS = 256;
 static constexpr uint32_t SMER_FLUSH_STEPS = 1024; // census: a lane's 16-bit fields take 31 per step
+// 31: per step a lane counts, for one owner, at most one record of up to SMER_REC_KMERS k-mers that starts at its last position plus at
+// most 15 k-mers of the records before it.  The flush itself runs only where a wave takes SMER_FLUSH_STEPS steps -- some 8 Gbases in
+// one call on a 256-CU device -- and has no GPU test: what it rests on is pinned here.
+static constexpr uint32_t SMER_LANE_STEP_KMERS = SMER_REC_KMERS + 15;
+static_assert(SMER_LANE_STEP_KMERS * SMER_FLUSH_STEPS <= 0xFFFFu, "census: a lane's 16-bit field overflows between two flushes");
+static_assert(SMER_LANE_STEP_KMERS <= 0xFFu, "census: a lane's 8-bit per-step field overflows");
 
 // lane i <- lane i + 1 (lane 63 <- 0) / lane i <- lane i - 1 (lane 0 <- 0): full-rate DPP moves, no LDS crossbar
 __device__ __forceinline__ uint32_t dpp_shl1(uint32_t v) { return (uint32_t) __builtin_amdgcn_update_dpp(0, (int) v, 0x130, 0xf, 0xf, false); }
@@ -102,7 +108,7 @@ struct SmerLane {
     uint32_t K;   // positions a run cannot continue through: a boundary (owner change / first k-mer of a read) or no k-mer
     uint32_t rm;  // positions that start a record (output lanes only)
     uint32_t fbn; // the next lane's first break (0 .. 16); 0 behind the last output lane: runs end with the step
-    uint32_t bad; // non-ACGT bytes of the lane's own word
+    uint32_t bad; // non-ACGT bytes of the lane's own word, from the first read on
 };
 
 // record length at start position s of a lane
@@ -150,9 +156,10 @@ __device__ __forceinline__ void smer_fetch(const uint8_t *bases, const uint16_t 
     r.nv = novalid[widx < nwords_mask ? widx : nwords_mask - 1];
 }
 
-// `own[j]`: owner of position j.
+// `own[j]`: owner of position j.  `start`: flat position of the first read, for a.bad (bad_from, kmu_flat.h); a caller that takes no
+// notice of a.bad passes 0.
 template <int W>
-__device__ __forceinline__ void smer_step(const uint8_t *bases, uint64_t total, const SmerCfg &cf, uint32_t n_parts, uint64_t st,
+__device__ __forceinline__ void smer_step(const uint8_t *bases, uint64_t total, uint64_t start, const SmerCfg &cf, uint32_t n_parts, uint64_t st,
                                           const SmerRaw &raw, SmerLane &a, uint32_t (&mw)[16], uint32_t (&own)[16]) {
     const uint32_t lane = (uint32_t) lane_id();
     const uint64_t widx = st * SMER_STEP_WORDS + lane;
@@ -162,6 +169,7 @@ __device__ __forceinline__ void smer_step(const uint8_t *bases, uint64_t total, 
         s.base = bases; s.begin = 0; s.len = total; s.total = total; s.packed = 0;
         a.w0 = load_code_word(s, widx, a.bad);
     }
+    if (st * (uint64_t) (SMER_STEP_WORDS * 16) < start) a.bad = bad_from(a.bad, widx * 16, start); // (wave-uniform: a range's first steps)
     a.w1 = dpp_shl1(a.w0);
     a.w2 = dpp_shl1(a.w1);
     a.w3 = dpp_shl1(a.w2);
@@ -241,7 +249,7 @@ struct SmerGeom {
 // PACK8 (n_parts <= 8: one node's GPUs): per-owner counts travel in 8-bit fields of a register and reach LDS as wave sums;
 // otherwise one LDS atomic per record.
 template <int W, bool PACK8>
-__global__ void __launch_bounds__(SMER_THREADS) k_smer_census(const uint8_t *bases, const uint16_t *novalid, uint64_t total, int k,
+__global__ void __launch_bounds__(SMER_THREADS) k_smer_census(const uint8_t *bases, const uint64_t *offsets, const uint16_t *novalid, uint64_t total, int k,
                                                                uint32_t n_parts, uint32_t steps_per_unit, uint32_t *hist,
                                                                unsigned long long *kmers_per_owner, uint32_t *err, SampleArgs sa) {
     extern __shared__ uint32_t lh[]; // [n_parts] records, [n_parts] k-mers, then the sample: counter (2 words) + list
@@ -256,6 +264,7 @@ __global__ void __launch_bounds__(SMER_THREADS) k_smer_census(const uint8_t *bas
     const uint64_t s0 = (uint64_t) blockIdx.x * steps_per_unit;
     const uint64_t s1 = s0 + steps_per_unit < nsteps ? s0 + steps_per_unit : nsteps;
     const uint32_t wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
+    const uint64_t start = offsets[0];
     uint32_t bad = 0;
     SmerRaw raw;
     smer_fetch(bases, novalid, total, nwm, s0 + wave, raw);
@@ -283,7 +292,7 @@ __global__ void __launch_bounds__(SMER_THREADS) k_smer_census(const uint8_t *bas
         uint32_t mw[16], own[16];
         const SmerRaw cur = raw;
         smer_fetch(bases, novalid, total, nwm, st + nwaves, raw); // the next step of this wave, in flight under this one's arithmetic
-        smer_step<W>(bases, total, cf, n_parts, st, cur, a, mw, own);
+        smer_step<W>(bases, total, start, cf, n_parts, st, cur, a, mw, own);
         bad |= a.bad;
         uint64_t pr = 0, pk = 0;
         uint32_t rm = a.rm;
@@ -404,7 +413,7 @@ __global__ void __launch_bounds__(SMER_THREADS) k_smer_scatter(const uint8_t *ba
         uint32_t mw[16], own[16];
         const SmerRaw cur = raw;
         smer_fetch(bases, novalid, total, nwm, st + nwaves, raw);
-        smer_step<W>(bases, total, cf, n_parts, st, cur, a, mw, own);
+        smer_step<W>(bases, total, 0, cf, n_parts, st, cur, a, mw, own); // (the census validated the bases)
         uint32_t ex[4] = {0, 0, 0, 0}; // PACK8: records of the lower lanes of this step, per owner
         OwnerOf<PACK8> oo;
         oo.set(own);
@@ -490,6 +499,11 @@ __global__ void __launch_bounds__(256) k_smer_expand(const uint32_t *recs, uint6
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------------
+// One unit per wave step up to 8 workgroups per CU; smer_census then gives every unit steps_per_unit = ceil(nsteps / units) steps, which
+// its four waves take in turn.  A wave takes a SECOND step -- the loop runs again, the prefetch is of a real step, the waves of a
+// workgroup share the unit's cursors in k_smer_scatter -- only from steps_per_unit > 4 on, i.e. above 4 * 8 * CUs steps of 976 bases;
+// with just above (8 * 8 * CUs + 1) * 976 bases (16.0 Mbases on 256 CUs) steps_per_unit is 9: every wave takes two steps, wave 0
+// three.  tests/test_gpu_superkmer_edges.py sizes its multi-step input by this formula and has to follow it.
 uint32_t smer_units(const kmu_ctx *ctx, uint64_t total_bases) {
     const uint64_t nwords = (total_bases + 15) / 16, nsteps = std::max<uint64_t>(1, (nwords + SMER_STEP_WORDS - 1) / SMER_STEP_WORDS);
     return (uint32_t) std::min<uint64_t>(nsteps, (uint64_t) ctx->num_cus * 8);
@@ -543,7 +557,7 @@ int smer_census(kmu_ctx *ctx, const DevSeqs &ds, uint64_t total_bases, int k, ui
     const SmerCfg cf = smer_cfg(k);
     KMU_TRY(smer_dispatch(cf.w, n_parts <= 8, [&](auto W, auto P8) {
         return launch(ctx, "k_smer_census", k_smer_census<decltype(W)::value, decltype(P8)::value>, dim3(units), dim3(SMER_THREADS), lds, ds.bases,
-                      (const uint16_t *) g->novalid, total_bases, k, n_parts, spu, (uint32_t *) g->hist, (unsigned long long *) g->kmers, d_err, sa);
+                      ds.offsets, (const uint16_t *) g->novalid, total_bases, k, n_parts, spu, (uint32_t *) g->hist, (unsigned long long *) g->kmers, d_err, sa);
     }));
     {
         KernelTimer tm(ctx, "k_smer_scan");
