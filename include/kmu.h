@@ -681,8 +681,9 @@ int kmu_ingest_fastq(kmu_ctx *ctx, const uint8_t *text, uint64_t n_bytes, int me
                      uint64_t *offsets_out, uint64_t offsets_cap, uint32_t *record_index_out, kmu_ingest_info *info);
 
 /* FASTA, needletail's other format (what gsearch feeds): a line that starts with '>' opens a record; its sequence is the
- * following lines up to the next such line with the line ends removed (record.seq()).  Same rule, outputs and calling
- * convention as kmu_ingest_fastq.  KMU_E_BAD_ARG if the text does not start with '>'. */
+ * following lines up to the next such line with the line ends removed (record.seq()).  The last line may have no final newline,
+ * and a '\r' that ends the text is dropped like one before a newline.  Same rule, outputs and calling convention as
+ * kmu_ingest_fastq.  KMU_E_BAD_ARG if the text does not start with '>'. */
 int kmu_ingest_fasta(kmu_ctx *ctx, const uint8_t *text, uint64_t n_bytes, int mem, uint8_t *bases_out, uint64_t bases_cap,
                      uint64_t *offsets_out, uint64_t offsets_cap, uint32_t *record_index_out, kmu_ingest_info *info);
 /* needletail::parse_fastx_file (src/io.rs:37, src/bin/datasketcher.rs:211): the first byte names the format,

@@ -289,7 +289,7 @@ __global__ void __launch_bounds__(256) k_fa_lines(const uint8_t *text, uint64_t 
     if (wave_global == 0 && lane_id() == 0) {
         line_start[0] = 0;
         is_hdr[0] = text[0] == '>';
-        if (text[n - 1] != '\n') line_end[n_lines - 1] = n; // last line without a line end
+        if (text[n - 1] != '\n') line_end[n_lines - 1] = text[n - 1] == '\r' ? n - 1 : n; // last line without a line end (as in k_ing_lines)
     }
 }
 
