@@ -26,18 +26,20 @@ __device__ __forceinline__ bool pmh3a_first_point_may_matter(const SketchArgs &a
 }
 
 // the other half, for a key that passed pmh3a_first_point_may_matter: s0 / s3 are the two state words it computed
+// UNIT_W: every key of the call has weight 1 -- no look-up, and the point is x itself (x times 1.0 is x, bit for bit)
+template <bool UNIT_W = false>
 __device__ __forceinline__ void pmh3a_first_point_rest(const SketchArgs &a, bool sig32, uint64_t *hmin, uint64_t *sig,
                                                        const uint64_t *qmax_sh, bool have, uint64_t key, uint32_t w,
                                                        uint64_t s0, uint64_t s3, const double *winv_lut) {
     const uint64_t qb = __hip_atomic_load(qmax_sh, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     if (have) {
-        const double winv = winv_of(winv_lut, w);
+        const double winv = UNIT_W ? 1.0 : winv_of(winv_lut, w);
         const uint64_t r1 = rotl64(s0 + s3, 23) + s0;
         const double u1 = __longlong_as_double((long long) ((r1 >> 12) | 0x3FF0000000000000ull)) - 1.0;
         double x = a.e01.c1 * u1;
         const double qmax = __longlong_as_double((long long) qb);
         const bool slow = !(x < 1.0);
-        if (slow || winv * x < qmax) { // (q_max may have fallen since the key was queued)
+        if (slow || (UNIT_W ? x : winv * x) < qmax) { // (q_max may have fallen since the key was queued)
             const uint64_t seed = hasher_finish(KMU_HASHER_NOHASH, key, sig32);
             Xoshiro rng;
             rng.s0 = s0;
@@ -46,7 +48,7 @@ __device__ __forceinline__ void pmh3a_first_point_rest(const SketchArgs &a, bool
             rng.s2 = splitmix_at(seed, 3);
             (void) rng.next(); // the draw already used
             if (slow) x = exp01_rest(a.e01, rng);
-            const double h = winv * x;
+            const double h = UNIT_W ? x : winv * x;
             if (h < qmax) slot_update_wave(hmin, sig, draw_slot(a, rng), h, key);
         }
     }
@@ -117,7 +119,7 @@ __device__ __forceinline__ void pts_one_read(const SketchArgs &a, uint32_t r, ui
         if (tau < 1.0) tau_b = (uint64_t) __double_as_longlong(tau);
         tau_b = uniform_u64(tau_b);
     }
-    uint32_t wmax = 0;          // largest weight this lane saw
+    uint32_t wmax = n_u ? 1u : 0u; // largest weight this lane saw (the prefix's chunks do not look: a list with a prefix has a weight 1)
     uint64_t qb = H_INIT;
     for (int turn = 0; turn < 2; turn++) { // the second turn runs without tau: H_INIT bounds every q_max, it cannot fail
         for (int t = lane; t < a.m; t += 64) { hmin[t] = H_INIT; sig[t] = 0; }
@@ -126,6 +128,9 @@ __device__ __forceinline__ void pts_one_read(const SketchArgs &a, uint32_t r, ui
         // ---- pass 1 ----
         uint32_t chunk = 0, qn = 0; // qn: queued pairs (uniform)
         qb = tau_b;
+        // while tau bounds the pass, the running q_max lies above it for the first part of the list and a refresh there is clamped back
+        // to tau: none before `hold` of this wave's chunks (PTS_TAU_HOLD; the turn without tau refreshes from its first chunk on)
+        const uint32_t hold = tau_b != H_INIT && n > cstart ? (uint32_t) (((uint64_t) ((n - cstart + cstride - 1u) / cstride) * a.tau_hold) >> 8) : 0u;
         // (Round 5, measured and not kept: the keys of 2 / 4 / 8 chunks in flight instead of one -- 18.40 / 18.42 / 19.60 against 18.38 ms,
         //  profiles/r05_pts_ahead.txt.  With everything but the list walk switched off the kernel takes 9.3 ms -- 38 GB of lists at
         //  4.1 TB/s -- but the whole kernel is bound by instruction issue: 1.008e10 vector wave-instructions at the half-rate peak are
@@ -136,42 +141,51 @@ __device__ __forceinline__ void pts_one_read(const SketchArgs &a, uint32_t r, ui
             const uint32_t i = cstart + (uint32_t) lane;
             if (i < n) { key_nx = a.lst_keys[base + i]; w_nx = i < n_u ? 1u : a.lst_w[base + i]; }
         }
-        for (uint32_t c = cstart; c < n; c += cstride, chunk++) { // uniform trip count
+        // The chunks that lie wholly inside the weight-1 prefix (c + 64 <= n_u; WG: this wave's own) are walked without weights: every
+        // lane has an entry, its weight is 1, a survivor is queued without a weight word and worked off with h = x.  The general form
+        // takes the rest, from the chunk that straddles n_u on; chunk counter, refresh cadence and the queue run on across both.
+        uint32_t c = cstart;
+        auto step = [&](auto unit_tag) __attribute__((always_inline)) {
+            constexpr bool UNIT = decltype(unit_tag)::value;
             const uint32_t i = c + (uint32_t) lane;
             const uint64_t key = key_nx;
-            const uint32_t w = w_nx;
-            const bool have = i < n && w != 0u; // weight 0: a repeat of an earlier entry
-            if (have) wmax = w > wmax ? w : wmax;
+            const uint32_t w = UNIT ? 1u : w_nx;
+            const bool have = UNIT || (i < n && w != 0u); // weight 0: a repeat of an earlier entry
+            if (!UNIT && have) wmax = w > wmax ? w : wmax;
             if (i + cstride < n) key_nx = a.lst_keys[base + i + cstride];
-            w_nx = 1u;
+            if (!UNIT) w_nx = 1u; // (UNIT: it is 1 since the walk began)
             if (c + cstride + 64u > n_u) { // (uniform: the next chunk reaches beyond the weight-1 prefix)
                 if (i + cstride < n && i + cstride >= n_u) w_nx = a.lst_w[base + i + cstride];
             }
             // (WG: the four waves advance through the list together, so the merged q_max is refreshed four times as often per own
             //  chunk while it still falls fast -- the first 64 own chunks -- and at the single wave's cadence per own chunk after that)
-            if ((chunk & (WG && chunk < 64u ? PTS_REFRESH_MASK >> 2 : PTS_REFRESH_MASK)) == 0u) {
+            if ((chunk & (WG && chunk < 64u ? PTS_REFRESH_MASK >> 2 : PTS_REFRESH_MASK)) == 0u && chunk >= hold) {
                 qb = WG ? wg4_qmax(arrays, wave_words, a.m) : wave_qmax(hmin, a.m);
                 qb = qb < tau_b ? qb : tau_b;
                 if (lane == 0) *qmax_sh = qb;
             }
             uint64_t s0 = 0, s3 = 0;
-            const bool pass = c + 64u <= n_u ? have && pmh3a_first_point_may_matter<true>(a, sig32, qb, key, w, winv_lut, s0, s3) // (uniform)
-                                             : have && pmh3a_first_point_may_matter(a, sig32, qb, key, w, winv_lut, s0, s3);
+            const bool pass = have && pmh3a_first_point_may_matter<UNIT>(a, sig32, qb, key, w, winv_lut, s0, s3);
             const uint64_t pm = __ballot(pass);
             if (pass) {
                 const uint32_t pos = qn + (uint32_t) __popcll(pm & ((1ull << lane) - 1ull));
                 qk[pos] = key;
-                qw[pos] = w;
+                if (!UNIT) qw[pos] = w;
                 qs0[pos] = s0;
                 qs3[pos] = s3;
             }
             qn += (uint32_t) __popcll(pm);
             if (qn >= 64u) { // the newest 64
                 qn -= 64u;
-                pmh3a_first_point_rest(a, sig32, hmin, sig, qmax_sh, true, qk[qn + lane], qw[qn + lane], qs0[qn + lane], qs3[qn + lane],
-                                       winv_lut);
+                pmh3a_first_point_rest<UNIT>(a, sig32, hmin, sig, qmax_sh, true, qk[qn + lane], UNIT ? 1u : qw[qn + lane], qs0[qn + lane],
+                                             qs3[qn + lane], winv_lut);
             }
-        }
+        };
+        for (; c + 64u <= n_u; c += cstride, chunk++) step(std::true_type{}); // uniform trip counts
+        // (the prefix's survivors still queued get their weight word now, once per read, and leave with the next full 64: a flush here
+        //  would run the expensive half with a partly filled wave)
+        if ((uint32_t) lane < qn) qw[lane] = 1u;
+        for (; c < n; c += cstride, chunk++) step(std::false_type{});
         if (qn) {
             const bool have = (uint32_t) lane < qn;
             pmh3a_first_point_rest(a, sig32, hmin, sig, qmax_sh, have, have ? qk[lane] : 0ull, have ? qw[lane] : 1u, have ? qs0[lane] : 0ull,

@@ -183,7 +183,12 @@ __global__ void __launch_bounds__(UQ_THREADS, MINW) k_multiset_uq(SketchArgs a) 
         // reads, compares, ballots and branch skeletons for nothing: the mean read of the first shape fills 2.6 of its 5 groups).
         // Both phases skip by this one test: rk[] of a skipped group holds no key and is not looked at.
         const uint32_t span = uniform_u32(nk + (lead - 16u * wfirst));
-        auto group_used = [&](int q0) -> bool { return 4u * (uint32_t) UQ_THREADS * (uint32_t) (q0 >> 2) < span; };
+        // A wave owns 256 consecutive places of a group, from 4 (UQ_THREADS g + 64 wave) on, and a read ends inside one wave: the waves
+        // behind that one have no k-mer in this group and in all later ones.  The test is made for the wave's own first place -- it
+        // contains the group's (wave 0's place is the group's first) and stays one scalar compare: the wave's number is read off the
+        // first lane here, once per read (kept from the kernel's top it would be one more scalar register live around the read loop).
+        const uint32_t wave_first = 256u * uniform_u32((uint32_t) tid >> 6);
+        auto group_used = [&](int q0) -> bool { return 4u * (uint32_t) UQ_THREADS * (uint32_t) (q0 >> 2) + wave_first < span; };
         bool over = false; // uniform: too many keys in collision groups
         if (mine) {
             // ---- keys: extract, closure, bitmaps; the four ds_or_rtn of a slot group in flight together (in the compiled kernel: back to

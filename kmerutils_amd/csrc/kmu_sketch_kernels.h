@@ -69,6 +69,8 @@ struct SketchArgs {
     uint32_t idx_thresh;  // rand 0.9 Uniform<usize>(0, m): reject while lo < (2^32 - m) % m
     uint64_t idx_zone;    // rand 0.8 Uniform<usize>(0, m): accept while lo <= zone
     uint32_t tau_min_n;   // ... lists with fewer entries get no bound (~ tau_num: the keys tau wants below it); 2^32 - 1: bound off
+    uint32_t tau_hold;    // ... in 1/256 of a wave's chunks of the list: no q_max refresh before that many while tau bounds pass 1 (PTS_TAU_HOLD;
+                          //     the word stands in what was padding in front of e01: no other field moves)
     Exp01 e01;
     void *sig_out;
     uint32_t *queue; // atomic read counter
@@ -96,6 +98,11 @@ static constexpr size_t PTS_WAVE_WORDS = 2 + 128 + 64 + 256;
 // k_pmh_points: c of the a-priori q_max bound tau = m (ln m + c) / W of a read with W k-mer occurrences: the bound fails (the read
 // starts over) with probability ~ e^-c, ~ m (ln m + c) keys reach the expensive half of a first point.  DESIGN 3.2 has the table.
 static constexpr double PTS_TAU_C = 4.6;
+// While tau bounds pass 1 the running q_max, ~ m (ln m + gamma) / i after i keys, lies above tau = m (ln m + c) / W for the first
+// (ln m + gamma) / (ln m + c) ~ 0.6 of a read's keys: a refresh there is clamped back to tau.  k_pmh_points makes none before this
+// share of a wave's chunks of the list, in 1/256 (0: from the first chunk on).  A stale bound only lets more keys into the expensive half.
+// (Measured on the ONT workload: 0 / 64 / 128: 14.61-14.64 / 14.49-14.51 / 14.40-14.42 ms, profiles/uq_waves_bench.txt.)
+static constexpr uint32_t PTS_TAU_HOLD = 128;
 static constexpr int UQ_KREG = 20;
 // The two shapes' bitmap sizes (log2 bits) and collected-key capacities.  Round 4: bitmaps twice as large (nearly every key of a
 // collision group of an ONT read is a false positive of the bitmap: 9 % of the keys at 2^16 bits, 4.5 % at 2^17), collected-key

@@ -163,6 +163,7 @@ static int launch_points(kmu_ctx *ctx, SketchArgs a, int cus, uint32_t thr) {
     a.tau_redo = (uint32_t *) tr;
     a.tau_num = (double) a.m * (std::log((double) a.m) + ctx->pmh_tau_c);
     a.tau_min_n = ctx->pmh_tau_c != 0.0 && a.tau_num > 0.0 ? (uint32_t) std::min(a.tau_num, 4.0e9) : 0xFFFFFFFFu;
+    a.tau_hold = PTS_TAU_HOLD;
     return launch(ctx, "k_pmh_points", kpts, dim3(grid2), dim3(256), lds2, a);
 }
 
