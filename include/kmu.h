@@ -284,7 +284,13 @@ int kmu_kmer_hashes_compact(kmu_ctx *ctx, const kmu_hash_params *p, const uint8_
  *                                     (block_row_offsets from kmu_block_layout; may be NULL if block_size==0)
  *          ALL_SEQS                 : 1 row
  * BOTTOMK: sig_out rows are sketch_size uint64 hashes ascending, padded with UINT64_MAX; counts_out (may be
- *          NULL) gets sketch_size uint32 multiplicities per row. */
+ *          NULL) gets sketch_size uint32 multiplicities per row.
+ * sketch_size: 2 .. 65536 (BOTTOMK: 1 .. 65536), KMU_E_BAD_ARG outside.  SUPER and SUPER2: 2 .. 8872; 8873 and above are
+ *          KMU_E_UNSUPPORTED, returned before any kernel is launched, in every mode and for kmu_sketch_hashed, kmu_sketch_groups
+ *          and kmu_sketch_partial alike (the context stays usable).  Why: a workgroup keeps the sketch in the 160 KiB of LDS of
+ *          a CU -- 16 sketch_size + 4128 bytes of slot minima, index bounds and staged k-mers, and per k-mer in flight a
+ *          permutation of sketch_size entries, of one byte up to sketch_size 256 and two above.  Above 1109 fewer than 64 k-mers
+ *          are in flight (2500: 23, 8872: one); at 8873, 18 sketch_size + 4128 bytes exceed the 160 KiB. */
 int kmu_sketch(kmu_ctx *ctx, const kmu_sketch_params *p, const uint8_t *bases, const uint64_t *offsets,
                const uint64_t *packed_offsets, uint32_t n_seq, const uint64_t *block_row_offsets, void *sig_out,
                uint32_t *counts_out);

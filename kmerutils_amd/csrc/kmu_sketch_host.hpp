@@ -4,6 +4,8 @@
 // kmu_sketch_dens.hip, kmu_sketch_groups.hip: kernels and launchers of their own (what the last two share: kmu_sketch_dens.h).
 #pragma once
 
+#include <algorithm>
+
 #include "kmu_ctx.hpp"
 #include "kmu_device.h"
 
@@ -51,6 +53,39 @@ __host__ __device__ inline uint32_t pmh_long_part_of(uint64_t key, uint32_t part
 __host__ __device__ inline uint64_t super_chunk_count(uint64_t n) {
     const uint64_t c = (n + 16383) / 16384;
     return c < 1 ? 1 : (c > 8192 ? 8192 : c);
+}
+// The launch shape of k_sketch_super for a sketch of m slots that stages `chunk` items, on a device that gives a workgroup lds_max
+// bytes of LDS.  The kernel carves 16 m + 8 chunk + 16 bytes (slot minima, staged seeds, index bounds, two words) and one
+// permutation column of m entries per item lane out of `lds`; an entry is one byte up to m = 256 and two above (`wide`).  The
+// columns dominate: the workgroup shrinks from 256 to 64 threads (every thread an item lane) until they fit, and beyond that one
+// wave keeps as many item lanes as columns fit.  ncol == 0: not even one column fits, the launcher refuses the sketch size.
+struct SuperPlan {
+    int threads;       // workgroup size
+    int ncol;          // item lanes that own a permutation column (<= threads)
+    int wide;          // two-byte permutation entries
+    size_t lds;        // dynamic LDS of the launch, a multiple of 16
+    int blocks_per_cu; // workgroups per CU of the grid
+};
+inline SuperPlan super_plan(int m, uint32_t chunk, size_t lds_max) {
+    SuperPlan sp;
+    sp.wide = m > 256 ? 1 : 0;
+    const size_t pt = sp.wide ? 2 : 1;
+    sp.threads = 256;
+    sp.lds = 0;
+    sp.ncol = 0;
+    for (; sp.threads >= 64; sp.threads -= 64) {
+        sp.lds = (size_t) 16 * m + (size_t) 8 * chunk + 16 + pt * m * sp.threads;
+        sp.lds = (sp.lds + 15) & ~(size_t) 15;
+        if (sp.lds <= lds_max) { sp.ncol = sp.threads; break; }
+    }
+    if (!sp.ncol) { // very large sketches: one wave, as many item lanes as columns fit
+        sp.threads = 64;
+        const size_t fixed = (size_t) 16 * m + (size_t) 8 * chunk + 16 + 16;
+        if (fixed < lds_max) sp.ncol = (int) std::min<size_t>(64, (lds_max - fixed) / (pt * (size_t) m));
+        sp.lds = (fixed + pt * (size_t) m * sp.ncol + 15) & ~(size_t) 15;
+    }
+    sp.blocks_per_cu = std::max<int>(1, std::min<int>(2048 / sp.threads, (int) (lds_max / sp.lds)));
+    return sp;
 }
 
 // n lists of pre-hashed values as "sequences": list i = vals[offsets[i] .. offsets[i + 1]) (the launchers get `vals` as `hashed` too)

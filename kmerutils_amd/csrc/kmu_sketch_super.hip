@@ -296,9 +296,11 @@ int launch_super(kmu_ctx *ctx, const kmu_sketch_params *p, const DevSeqs &ds, vo
     // read takes -- four waves and 512 staged items: 7.93 -> 7.25 ms on config 5's shard (scripts/r04_superthreads.sh; 1 024
     // staged items: 8.7).
     a.chunk = 512;
-    const bool wide = a.m > 256;
-    const size_t pt = wide ? 2 : 1;
+    // the per-lane permutation columns dominate the LDS footprint: super_plan shrinks the workgroup for large m
     const size_t lds_max = 160 * 1024;
+    const SuperPlan sp = super_plan(a.m, a.chunk, lds_max);
+    const bool wide = sp.wide != 0;
+    const size_t lds = sp.lds;
     typedef void (*super_kernel_t)(SuperArgs);
     super_kernel_t kern = nullptr;
 #define KMU_SUPER_PICK(PT_) \
@@ -311,31 +313,15 @@ int launch_super(kmu_ctx *ctx, const kmu_sketch_params *p, const DevSeqs &ds, vo
     if (wide) { KMU_SUPER_PICK(uint16_t) } else { KMU_SUPER_PICK(uint8_t) }
 #undef KMU_SUPER_PICK
     auto fn = (const void *) kern;
-    // the per-lane permutation columns dominate the LDS footprint: shrink the workgroup for large m
-    int threads = 256;
-    size_t lds = 0;
-    int ncol = 0;
-    for (; threads >= 64; threads -= 64) {
-        lds = (size_t) 16 * a.m + (size_t) 8 * a.chunk + 16 + pt * a.m * threads;
-        lds = (lds + 15) & ~(size_t) 15;
-        if (lds <= lds_max) { ncol = threads; break; }
-    }
-    if (!ncol) { // very large sketches: one wave, as many item lanes as columns fit
-        threads = 64;
-        const size_t fixed = (size_t) 16 * a.m + (size_t) 8 * a.chunk + 16 + 16;
-        if (fixed < lds_max) ncol = (int) std::min<size_t>(64, (lds_max - fixed) / (pt * (size_t) a.m));
-        lds = (fixed + pt * (size_t) a.m * ncol + 15) & ~(size_t) 15;
-    }
-    a.ncol = ncol;
-    if (ncol < 1) return fail(ctx, KMU_E_UNSUPPORTED, "sketch_size %d too large for LDS (%zu B)", a.m, lds);
+    a.ncol = sp.ncol;
+    if (sp.ncol < 1) return fail(ctx, KMU_E_UNSUPPORTED, "sketch_size %d too large for LDS (%zu B)", a.m, lds);
     if (lds > 64 * 1024) {
         if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds_max) != hipSuccess) {
             (void) hipGetLastError();
             return fail(ctx, KMU_E_UNSUPPORTED, "sketch_size %d needs %zu B of LDS", a.m, lds);
         }
     }
-    int blocks_per_cu = std::max<int>(1, std::min<int>(2048 / threads, (int) (lds_max / lds)));
-    return launch(ctx, "k_sketch_super", kern, dim3(grid_for(ctx, ds.n_seq, 1, blocks_per_cu)), dim3(threads), lds, a);
+    return launch(ctx, "k_sketch_super", kern, dim3(grid_for(ctx, ds.n_seq, 1, sp.blocks_per_cu)), dim3(sp.threads), lds, a);
 }
 
 } // namespace kmu
