@@ -183,10 +183,7 @@ extern "C" int kmu_read_anchors(kmu_ctx *ctx, const kmu_sketch_params *p_in, con
         if (!std::equal(want.begin(), want.end(), anchor_row_offsets))
             return fail(ctx, KMU_E_BAD_ARG, "anchor_row_offsets is not the layout of kmu_anchor_layout for these reads");
         rows = want[n_seq];
-    } else if (p->mem == KMU_MEM_DEVICE) {
-        KMU_HIP(ctx, hipMemcpyAsync(&rows, anchor_row_offsets + n_seq, 8, hipMemcpyDeviceToHost, ctx->stream));
-        KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    }
+    } else if (p->mem == KMU_MEM_DEVICE) KMU_TRY(read_back(ctx, {{&rows, anchor_row_offsets + n_seq}}));
     if (rows > 0xFFFFFFFFull) return fail(ctx, KMU_E_UNSUPPORTED, "%llu anchor rows: more than 2^32 - 1", (unsigned long long) rows);
     if (rows == 0) return KMU_OK;
     if (!hashes_out) return fail(ctx, KMU_E_BAD_ARG, "null hashes_out");
@@ -196,7 +193,6 @@ extern "C" int kmu_read_anchors(kmu_ctx *ctx, const kmu_sketch_params *p_in, con
     AnchorArgs a;
     a.bases = ds.bases;
     a.offsets = ds.offsets;
-    a.row_off = anchor_row_offsets;
     a.n_seq = n_seq;
     a.rows = (uint32_t) rows;
     a.total_bytes = ds.total_bytes;
@@ -206,25 +202,15 @@ extern "C" int kmu_read_anchors(kmu_ctx *ctx, const kmu_sketch_params *p_in, con
     a.m = (uint32_t) m;
     a.hasher = p->hasher;
     a.count_mask = p->hasher == KMU_HASHER_INT64HASH ? 0xFFu : 0xFFFFu; // MinInvHashCountKmer: u8, MinHashCount: u16
-    a.hashes_out = hashes_out;
-    a.counts_out = counts_out;
-    a.n_out = n_out;
-    if (p->mem == KMU_MEM_HOST) {
-        void *q;
-        KMU_TRY(dev_buf(ctx, "in.anchorrows", ((size_t) n_seq + 1) * 8, &q));
-        KMU_HIP(ctx, hipMemcpyAsync(q, anchor_row_offsets, ((size_t) n_seq + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
-        a.row_off = (const uint64_t *) q;
-        KMU_TRY(dev_array(ctx, "out.sig", rows * m + 8, &a.hashes_out));
-        if (counts_out) KMU_TRY(dev_array(ctx, "out.counts", rows * m + 16, &a.counts_out));
-        if (n_out) KMU_TRY(dev_array(ctx, "out.anchor_n", rows + 16, &a.n_out));
-    }
+    KMU_TRY(stage_to_device(ctx, "in.anchorrows", anchor_row_offsets, (size_t) n_seq + 1, p->mem, &a.row_off));
+    KMU_TRY(place_output(ctx, "out.sig", hashes_out, rows * m + 8, p->mem, &a.hashes_out));
+    KMU_TRY(place_output(ctx, "out.counts", counts_out, rows * m + 16, p->mem, &a.counts_out));
+    KMU_TRY(place_output(ctx, "out.anchor_n", n_out, rows + 16, p->mem, &a.n_out));
     KMU_TRY(get_err_word(ctx, &a.err));
     const uint32_t grid = (uint32_t) std::min<uint64_t>(rows, (uint64_t) ctx->num_cus * 40);
     KMU_TRY(launch(ctx, "k_read_anchors", k_read_anchors, dim3(grid), dim3(64), 0, a));
-    if (p->mem == KMU_MEM_HOST) {
-        KMU_HIP(ctx, hipMemcpyAsync(hashes_out, a.hashes_out, rows * m * 8, hipMemcpyDeviceToHost, ctx->stream));
-        if (counts_out) KMU_HIP(ctx, hipMemcpyAsync(counts_out, a.counts_out, rows * m * 4, hipMemcpyDeviceToHost, ctx->stream));
-        if (n_out) KMU_HIP(ctx, hipMemcpyAsync(n_out, a.n_out, rows * 4, hipMemcpyDeviceToHost, ctx->stream));
-    }
+    KMU_TRY(bring_output(ctx, hashes_out, a.hashes_out, rows * m, p->mem));
+    KMU_TRY(bring_output(ctx, counts_out, a.counts_out, rows * m, p->mem));
+    KMU_TRY(bring_output(ctx, n_out, a.n_out, rows, p->mem));
     return finish_checked(ctx, p->mem, a.err);
 }

@@ -165,9 +165,7 @@ static int aix_create(kmu_anchor_index *ix, const uint64_t *hashes_db, const uin
     KMU_TRY(anchor_db_build(ctx, &ws, &d_real));
     const uint64_t n = (uint64_t) ndb * ix->n_keys;
     uint32_t n_real = 0, n_distinct = 0;
-    KMU_HIP(ctx, hipMemcpyAsync(&n_real, d_real, 4, hipMemcpyDeviceToHost, ctx->stream));
-    KMU_HIP(ctx, hipMemcpyAsync(&n_distinct, ws.n_distinct, 4, hipMemcpyDeviceToHost, ctx->stream));
-    KMU_HIP(ctx, hipStreamSynchronize(ctx->stream)); // the directory is allocated at its size
+    KMU_TRY(read_back(ctx, {{&n_real, d_real}, {&n_distinct, ws.n_distinct}})); // the directory is allocated at its size
     if (n_distinct > n_real || n_real > n) return fail(ctx, KMU_E_HIP, "anchor index: %u keys over %u of %llu entries", n_distinct, n_real, (unsigned long long) n);
     ix->n_entries = n_real;
     ix->n_distinct = n_distinct;
@@ -180,16 +178,13 @@ static int aix_create(kmu_anchor_index *ix, const uint64_t *hashes_db, const uin
     KMU_HIP(ctx, hipMemcpyAsync(ix->ukeys, ws.ukeys, (size_t) n_distinct * 8, hipMemcpyDeviceToDevice, ctx->stream));
     KMU_HIP(ctx, hipMemcpyAsync(ix->ubeg, ws.ubeg, ((size_t) n_distinct + 1) * 4, hipMemcpyDeviceToDevice, ctx->stream));
     KMU_HIP(ctx, hipMemcpyAsync(ix->n_distinct_dev, ws.n_distinct, 4, hipMemcpyDeviceToDevice, ctx->stream));
-    void *d_max;
-    KMU_TRY(dev_buf(ctx, "aix.max_occ", 4, &d_max));
+    uint32_t *d_max;
+    KMU_TRY(dev_array(ctx, "aix.max_occ", 1, &d_max));
     KMU_HIP(ctx, hipMemsetAsync(d_max, 0, 4, ctx->stream));
-    KMU_TRY(launch(ctx, "k_aix_max_occ", k_aix_max_occ, dim3(grid_for(ctx, n_distinct, 256)), dim3(256), 0, (const uint32_t *) ix->ubeg, n_distinct,
-                   (uint32_t *) d_max));
-    KMU_HIP(ctx, hipMemcpyAsync(&ix->max_occupancy, d_max, 4, hipMemcpyDeviceToHost, ctx->stream));
+    KMU_TRY(launch(ctx, "k_aix_max_occ", k_aix_max_occ, dim3(grid_for(ctx, n_distinct, 256)), dim3(256), 0, (const uint32_t *) ix->ubeg, n_distinct, d_max));
+    KMU_TRY(read_back(ctx, {{&ix->max_occupancy, d_max}}));
     // the caller's arrays are free from here on, in both modes
-    KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (ctx->profiling) profile_collect(ctx);
-    return KMU_OK;
+    return finish_synced(ctx);
 }
 
 } // namespace kmu
@@ -215,7 +210,7 @@ int kmu_anchor_index_create(kmu_ctx *ctx, const uint64_t *hashes_db, uint32_t nd
     if (!ctx || !hashes_db || !out || m == 0) return fail(ctx, KMU_E_BAD_ARG, "null argument or m == 0");
     *out = nullptr;
     if (n_keys == 0 || n_keys > m) return fail(ctx, KMU_E_BAD_ARG, "n_keys = %u: must be 1 .. m = %u", n_keys, m);
-    if (mem != KMU_MEM_HOST && mem != KMU_MEM_DEVICE) return fail(ctx, KMU_E_BAD_ARG, "bad mem %d", mem);
+    KMU_TRY(check_mem(ctx, mem));
     if (m > KMU_ANCHOR_MAX_NBKMER) return fail(ctx, KMU_E_UNSUPPORTED, "m = %u above KMU_ANCHOR_MAX_NBKMER (%d)", m, KMU_ANCHOR_MAX_NBKMER);
     if ((uint64_t) ndb * n_keys > 0xFFFFFFFFull)
         return fail(ctx, KMU_E_UNSUPPORTED, "%u rows x %u keys: 2^32 index entries or more", ndb, n_keys);
@@ -246,16 +241,16 @@ int kmu_anchor_index_occupancy(kmu_anchor_index *ix, uint64_t *hist_out, uint32_
     if (!ix || !hist_out) return fail(ix ? ix->ctx : nullptr, KMU_E_BAD_ARG, "null argument");
     kmu_ctx *ctx = ix->ctx;
     if (n_bins < 2 || n_bins > 65536) return fail(ctx, KMU_E_BAD_ARG, "n_bins = %u: must be 2 .. 65536", n_bins);
-    if (mem != KMU_MEM_HOST && mem != KMU_MEM_DEVICE) return fail(ctx, KMU_E_BAD_ARG, "bad mem %d", mem);
+    KMU_TRY(check_mem(ctx, mem));
     KMU_HIP(ctx, hipSetDevice(ctx->device));
-    uint64_t *d_h = hist_out;
-    if (mem == KMU_MEM_HOST) KMU_TRY(dev_array(ctx, "aix.hist", (size_t) n_bins, &d_h));
+    uint64_t *d_h;
+    KMU_TRY(place_output(ctx, "aix.hist", hist_out, (size_t) n_bins, mem, &d_h));
     KMU_HIP(ctx, hipMemsetAsync(d_h, 0, (size_t) n_bins * 8, ctx->stream));
     if (ix->n_distinct) {
         KMU_TRY(launch(ctx, "k_aix_occupancy", k_aix_occupancy, dim3(grid_for(ctx, ix->n_distinct, 256)), dim3(256), 0, (const uint32_t *) ix->ubeg,
                        (uint32_t) ix->n_distinct, n_bins - 1, (unsigned long long *) d_h));
     }
-    if (mem == KMU_MEM_HOST) KMU_HIP(ctx, hipMemcpyAsync(hist_out, d_h, (size_t) n_bins * 8, hipMemcpyDeviceToHost, ctx->stream));
+    KMU_TRY(bring_output(ctx, hist_out, d_h, (size_t) n_bins, mem));
     return finish_call(ctx, mem);
 }
 
@@ -265,18 +260,15 @@ int kmu_anchor_index_match(kmu_anchor_index *ix, const uint64_t *hashes_q, uint3
     kmu_ctx *ctx = ix->ctx;
     if ((group_q != nullptr) != ix->has_groups)
         return fail(ctx, KMU_E_BAD_ARG, "group_q and the index's groups go together: both or neither");
-    if (mem != KMU_MEM_HOST && mem != KMU_MEM_DEVICE) return fail(ctx, KMU_E_BAD_ARG, "bad mem %d", mem);
+    KMU_TRY(check_mem(ctx, mem));
     *n_out = 0;
     KMU_HIP(ctx, hipSetDevice(ctx->device));
     if (nq == 0 || ix->n_distinct == 0) return KMU_OK;
 
     MatchArgs a{};
-    const void *p;
-    KMU_TRY(stage_to_device(ctx, "am.q", hashes_q, (size_t) nq * ix->m * 8, mem, &p));
-    a.q = (const uint64_t *) p;
+    KMU_TRY(stage_to_device(ctx, "am.q", hashes_q, (size_t) nq * ix->m, mem, &a.q));
     if (group_q) {
-        KMU_TRY(stage_to_device(ctx, "am.gq", group_q, (size_t) nq * 4, mem, &p));
-        a.gq = (const uint32_t *) p;
+        KMU_TRY(stage_to_device(ctx, "am.gq", group_q, (size_t) nq, mem, &a.gq));
     }
     a.db = aix_view(ix);
     a.min_common = min_common;

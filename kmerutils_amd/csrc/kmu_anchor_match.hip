@@ -140,8 +140,7 @@ int anchor_match_run(kmu_ctx *ctx, MatchArgs &a, uint32_t nq, int mem, uint32_t 
     KMU_TRY(launch(ctx, "k_anchor_match_count", k_anchor_match<false>, dim3(grid), dim3(64), 0, a));
     KMU_TRY(device_scan_u32(ctx, counts, nq, offs));
     uint64_t total = 0;
-    KMU_HIP(ctx, hipMemcpyAsync(&total, offs + nq, 8, hipMemcpyDeviceToHost, ctx->stream));
-    KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    KMU_TRY(read_back(ctx, {{&total, offs + nq}}));
     *n_out = total;
     if (!pairs_out || total == 0) return finish_call(ctx, mem);
     if (cap < total) {
@@ -152,22 +151,11 @@ int anchor_match_run(kmu_ctx *ctx, MatchArgs &a, uint32_t nq, int mem, uint32_t 
     // WRITE
     a.offs = offs;
     a.total = total;
-    a.pairs = pairs_out;
-    a.dist = dist_out;
-    if (mem == KMU_MEM_HOST) {
-        void *d;
-        KMU_TRY(dev_buf(ctx, "am.pairs", total * 8, &d));
-        a.pairs = (uint32_t *) d;
-        if (dist_out) {
-            KMU_TRY(dev_buf(ctx, "am.dist", total * 12, &d));
-            a.dist = (uint32_t *) d;
-        }
-    }
+    KMU_TRY(place_output(ctx, "am.pairs", pairs_out, total * 2, mem, &a.pairs));
+    KMU_TRY(place_output(ctx, "am.dist", dist_out, total * 3, mem, &a.dist));
     KMU_TRY(launch(ctx, "k_anchor_match_write", k_anchor_match<true>, dim3(grid), dim3(64), 0, a));
-    if (mem == KMU_MEM_HOST) {
-        KMU_HIP(ctx, hipMemcpyAsync(pairs_out, a.pairs, total * 8, hipMemcpyDeviceToHost, ctx->stream));
-        if (dist_out) KMU_HIP(ctx, hipMemcpyAsync(dist_out, a.dist, total * 12, hipMemcpyDeviceToHost, ctx->stream));
-    }
+    KMU_TRY(bring_output(ctx, pairs_out, a.pairs, total * 2, mem));
+    KMU_TRY(bring_output(ctx, dist_out, a.dist, total * 3, mem));
     return finish_call(ctx, mem);
 }
 
@@ -182,7 +170,7 @@ extern "C" int kmu_anchor_match(kmu_ctx *ctx, const uint64_t *hashes_q, uint32_t
     if (n_keys == 0 || n_keys > m) return fail(ctx, KMU_E_BAD_ARG, "n_keys = %u: must be 1 .. m = %u", n_keys, m);
     if ((group_q == nullptr) != (group_db == nullptr))
         return fail(ctx, KMU_E_BAD_ARG, "group_q and group_db go together: both null or both given");
-    if (mem != KMU_MEM_HOST && mem != KMU_MEM_DEVICE) return fail(ctx, KMU_E_BAD_ARG, "bad mem %d", mem);
+    KMU_TRY(check_mem(ctx, mem));
     if (m > KMU_ANCHOR_MAX_NBKMER) return fail(ctx, KMU_E_UNSUPPORTED, "m = %u above KMU_ANCHOR_MAX_NBKMER (%d)", m, KMU_ANCHOR_MAX_NBKMER);
     if ((uint64_t) ndb * n_keys > 0xFFFFFFFFull)
         return fail(ctx, KMU_E_UNSUPPORTED, "%u rows x %u keys: 2^32 index entries or more", ndb, n_keys);
@@ -191,19 +179,14 @@ extern "C" int kmu_anchor_match(kmu_ctx *ctx, const uint64_t *hashes_q, uint32_t
     if (nq == 0 || ndb == 0) return KMU_OK;
 
     MatchArgs a{};
-    const void *p;
-    KMU_TRY(stage_to_device(ctx, "am.q", hashes_q, (size_t) nq * m * 8, mem, &p));
-    a.q = (const uint64_t *) p;
+    KMU_TRY(stage_to_device(ctx, "am.q", hashes_q, (size_t) nq * m, mem, &a.q));
     if (hashes_db == hashes_q && ndb == nq) a.db.rows = a.q; // a self-join is staged once
     else {
-        KMU_TRY(stage_to_device(ctx, "am.db", hashes_db, (size_t) ndb * m * 8, mem, &p));
-        a.db.rows = (const uint64_t *) p;
+        KMU_TRY(stage_to_device(ctx, "am.db", hashes_db, (size_t) ndb * m, mem, &a.db.rows));
     }
     if (group_q) {
-        KMU_TRY(stage_to_device(ctx, "am.gq", group_q, (size_t) nq * 4, mem, &p));
-        a.gq = (const uint32_t *) p;
-        KMU_TRY(stage_to_device(ctx, "am.gdb", group_db, (size_t) ndb * 4, mem, &p));
-        a.db.groups = (const uint32_t *) p;
+        KMU_TRY(stage_to_device(ctx, "am.gq", group_q, (size_t) nq, mem, &a.gq));
+        KMU_TRY(stage_to_device(ctx, "am.gdb", group_db, (size_t) ndb, mem, &a.db.groups));
     }
     a.db.ndb = ndb;
     a.db.m = m;

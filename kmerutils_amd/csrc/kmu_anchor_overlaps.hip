@@ -193,7 +193,7 @@ extern "C" int kmu_anchor_overlaps(kmu_ctx *ctx, const uint32_t *pairs, const ui
     if (!ctx || !pairs || !row_offsets_q || !row_offsets_db || !n_out) return fail(ctx, KMU_E_BAD_ARG, "null argument");
     if (strands != 1 && strands != 2) return fail(ctx, KMU_E_BAD_ARG, "strands = %u: must be 1 or 2", strands);
     if (flags & ~KMU_OVL_UPPER) return fail(ctx, KMU_E_BAD_ARG, "unknown flag bits 0x%x", flags & ~KMU_OVL_UPPER);
-    if (mem != KMU_MEM_HOST && mem != KMU_MEM_DEVICE) return fail(ctx, KMU_E_BAD_ARG, "bad mem %d", mem);
+    KMU_TRY(check_mem(ctx, mem));
     if (band > KMU_OVL_MAX_BAND) return fail(ctx, KMU_E_UNSUPPORTED, "band = %u above KMU_OVL_MAX_BAND (%d)", band, KMU_OVL_MAX_BAND);
     if (n_pairs > 0xFFFFFFFFull / strands)
         return fail(ctx, KMU_E_UNSUPPORTED, "%llu pairs x %u strands: 2^32 entries or more", (unsigned long long) n_pairs, strands);
@@ -209,17 +209,12 @@ extern "C" int kmu_anchor_overlaps(kmu_ctx *ctx, const uint32_t *pairs, const ui
     KMU_HIP(ctx, hipSetDevice(ctx->device));
 
     OvlArgs a{};
-    const void *p;
-    KMU_TRY(stage_to_device(ctx, "ovl.pairs", pairs, (size_t) n_pairs * 8, mem, &p));
-    a.pairs = (const uint32_t *) p;
-    KMU_TRY(stage_to_device(ctx, "ovl.dist", dist, (size_t) n_pairs * 12, mem, &p));
-    a.dist = (const uint32_t *) p;
-    KMU_TRY(stage_to_device(ctx, "ovl.offq", row_offsets_q, ((size_t) n_reads_q + 1) * 8, mem, &p));
-    a.off_q = (const uint64_t *) p;
+    KMU_TRY(stage_to_device(ctx, "ovl.pairs", pairs, (size_t) n_pairs * 2, mem, &a.pairs));
+    KMU_TRY(stage_to_device(ctx, "ovl.dist", dist, (size_t) n_pairs * 3, mem, &a.dist));
+    KMU_TRY(stage_to_device(ctx, "ovl.offq", row_offsets_q, (size_t) n_reads_q + 1, mem, &a.off_q));
     if (row_offsets_db == row_offsets_q && n_reads_db == n_reads_q) a.off_db = a.off_q; // a self-join is staged once
     else {
-        KMU_TRY(stage_to_device(ctx, "ovl.offdb", row_offsets_db, ((size_t) n_reads_db + 1) * 8, mem, &p));
-        a.off_db = (const uint64_t *) p;
+        KMU_TRY(stage_to_device(ctx, "ovl.offdb", row_offsets_db, (size_t) n_reads_db + 1, mem, &a.off_db));
     }
     a.n_reads_q = n_reads_q;
     a.n_reads_db = n_reads_db;

@@ -64,7 +64,7 @@ int stage_sequences(kmu_ctx *ctx, const uint8_t *bases, const uint64_t *offsets,
         out->total_bytes = 0; // kernels derive it from offsets[n_seq] / packed_offsets
         return KMU_OK;
     }
-    if (mem != KMU_MEM_HOST) return fail(ctx, KMU_E_BAD_ARG, "bad mem %d", mem);
+    KMU_TRY(check_mem(ctx, mem));
     // The sequences may be a range of a larger set (offsets[0] > 0): only their bytes go up, offsets re-based to 0.
     const uint64_t off0 = offsets[0];
     uint64_t first_byte = off0, end_byte = offsets[n_seq];
@@ -124,8 +124,7 @@ int get_err_word(kmu_ctx *ctx, uint32_t **out) {
 
 int check_err_word(kmu_ctx *ctx, uint32_t *d_err) {
     uint32_t h = 0;
-    KMU_HIP(ctx, hipMemcpyAsync(&h, d_err, 4, hipMemcpyDeviceToHost, ctx->stream));
-    KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    KMU_TRY(read_back(ctx, {{&h, d_err}}));
     ctx->err_unread = false; // read: the next call starts from a cleared word
     if (h) KMU_HIP(ctx, hipMemsetAsync(d_err, 0, 4, ctx->stream)); // ... and a second read (kmu_synchronize) does not report it again
     if (h & DERR_NON_ACGT) return fail(ctx, KMU_E_NON_ACGT, "pattern not a code in alphabet_2b (non-ACGT byte in a sequence)");
@@ -138,9 +137,7 @@ int check_err_word(kmu_ctx *ctx, uint32_t *d_err) {
 
 int finish_call(kmu_ctx *ctx, int mem) {
     if (mem == KMU_MEM_DEVICE && ctx->async_device) return KMU_OK;
-    KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (ctx->profiling) profile_collect(ctx);
-    return KMU_OK;
+    return finish_sync(ctx);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -325,8 +322,7 @@ const char *kmu_last_error(const kmu_ctx *ctx) { return ctx ? ctx->err.c_str() :
 
 int kmu_synchronize(kmu_ctx *ctx) {
     if (!ctx) return KMU_E_BAD_ARG;
-    KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (ctx->profiling) profile_collect(ctx);
+    KMU_TRY(finish_sync(ctx));
     auto it = ctx->bufs.find("errword");
     if (it != ctx->bufs.end() && it->second.p) return check_err_word(ctx, (uint32_t *) it->second.p);
     return KMU_OK;
@@ -433,8 +429,7 @@ int kmu_profile_get(kmu_ctx *ctx, kmu_kernel_stat *stats, int cap) {
     auto tr = ctx->bufs.find("pmh.tau_redo");
     if (tr != ctx->bufs.end() && tr->second.p) {
         uint32_t redone = 0;
-        KMU_HIP(ctx, hipMemcpyAsync(&redone, tr->second.p, 4, hipMemcpyDeviceToHost, ctx->stream));
-        KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        KMU_TRY(read_back(ctx, {{&redone, tr->second.p, 4}}));
         if (redone) {
             if (stats && n < cap) {
                 memset(&stats[n], 0, sizeof(kmu_kernel_stat));
@@ -453,14 +448,13 @@ int kmu_count_non_acgt(kmu_ctx *ctx, const uint8_t *bases, const uint64_t *offse
     KMU_HIP(ctx, hipSetDevice(ctx->device));
     DevSeqs ds;
     KMU_TRY(stage_sequences(ctx, bases, offsets, nullptr, n_seq, KMU_INPUT_ASCII, mem, &ds));
-    uint64_t *d_counts = counts_out;
-    if (mem == KMU_MEM_HOST) KMU_TRY(dev_array(ctx, "out.u64", (size_t) n_seq + 1, &d_counts));
+    uint64_t *d_counts;
+    KMU_TRY(place_output(ctx, "out.u64", counts_out, (size_t) n_seq + 1, mem, &d_counts));
     if (n_seq) {
         const int grid = grid_for(ctx, n_seq, 1);
         KMU_TRY(launch(ctx, "k_count_non_acgt", k_count_non_acgt, dim3(grid), dim3(256), 0, ds.bases, ds.offsets, n_seq, ds.total_bytes, d_counts));
     }
-    if (mem == KMU_MEM_HOST)
-        KMU_HIP(ctx, hipMemcpyAsync(counts_out, d_counts, (size_t) n_seq * 8, hipMemcpyDeviceToHost, ctx->stream));
+    KMU_TRY(bring_output(ctx, counts_out, d_counts, (size_t) n_seq, mem));
     return finish_call(ctx, mem);
 }
 
@@ -498,21 +492,15 @@ static int kmer_hashes_impl(kmu_ctx *ctx, const kmu_hash_params *p, const uint8_
     if (!ctx || !p || !out) return KMU_E_BAD_ARG;
     KMU_TRY(check_hash_params(ctx, p));
     KMU_HIP(ctx, hipSetDevice(ctx->device));
-    const uint64_t *d_rb = range_begin, *d_re = range_end;
-    if (range_begin && p->mem == KMU_MEM_HOST) {
+    const uint64_t *d_rb, *d_re;
+    if (range_begin && p->mem == KMU_MEM_HOST)
         for (uint32_t i = 0; i < n_seq; i++) // IterSequence::set_range, sequence.rs:563-565
             if (range_end[i] <= range_begin[i] || range_end[i] > offsets[i + 1] - offsets[i])
                 return fail(ctx, KMU_E_BAD_ARG, "bad range [%llu, %llu) for kmer iteration on sequence %u of %llu bases",
                             (unsigned long long) range_begin[i], (unsigned long long) range_end[i], i,
                             (unsigned long long) (offsets[i + 1] - offsets[i]));
-        uint64_t *q;
-        KMU_TRY(dev_array(ctx, "in.range_b", (size_t) n_seq + 1, &q));
-        KMU_HIP(ctx, hipMemcpyAsync(q, range_begin, (size_t) n_seq * 8, hipMemcpyHostToDevice, ctx->stream));
-        d_rb = q;
-        KMU_TRY(dev_array(ctx, "in.range_e", (size_t) n_seq + 1, &q));
-        KMU_HIP(ctx, hipMemcpyAsync(q, range_end, (size_t) n_seq * 8, hipMemcpyHostToDevice, ctx->stream));
-        d_re = q;
-    }
+    KMU_TRY(stage_to_device(ctx, "in.range_b", range_begin, (size_t) n_seq, p->mem, &d_rb, 1));
+    KMU_TRY(stage_to_device(ctx, "in.range_e", range_begin ? range_end : nullptr, (size_t) n_seq, p->mem, &d_re, 1));
     DevSeqs ds;
     KMU_TRY(stage_sequences(ctx, bases, offsets, packed_offsets, n_seq, p->input_kind, p->mem, &ds));
     uint64_t *d_out = out;

@@ -82,43 +82,35 @@ extern "C" int kmu_chain_align(kmu_ctx *ctx, const kmu_chain *chains, uint64_t n
     if (p->flags) return fail(ctx, KMU_E_BAD_ARG, "unknown flag bits 0x%x", p->flags);
     if (p->band > (KMU_ALIGN_MAX_DIAGS - 1u) / 2u)
         return fail(ctx, KMU_E_BAD_ARG, "band = %u: 2 band + 1 is above KMU_ALIGN_MAX_DIAGS = %d", p->band, KMU_ALIGN_MAX_DIAGS);
-    if (mem != KMU_MEM_HOST && mem != KMU_MEM_DEVICE) return fail(ctx, KMU_E_BAD_ARG, "bad mem %d", mem);
+    KMU_TRY(check_mem(ctx, mem));
     if (n_chains == 0) return KMU_OK;
     if (n_reads_q == 0 || n_reads_db == 0) return fail(ctx, KMU_E_BAD_ARG, "chains but no reads");
     KMU_HIP(ctx, hipSetDevice(ctx->device));
 
     AlignArgs a{};
-    const void *d;
-    KMU_TRY(stage_to_device(ctx, "align.chains", chains, (size_t) n_chains * sizeof(kmu_chain), mem, &d));
-    a.chains = (const kmu_chain *) d;
+    KMU_TRY(stage_to_device(ctx, "align.chains", chains, (size_t) n_chains, mem, &a.chains));
     a.n_chains = n_chains;
-    KMU_TRY(stage_to_device(ctx, "align.basesq", bases_q, mem == KMU_MEM_HOST ? (size_t) offsets_q[n_reads_q] : 0, mem, &d));
-    a.bases_q = (const uint8_t *) d;
-    KMU_TRY(stage_to_device(ctx, "align.offq", offsets_q, ((size_t) n_reads_q + 1) * 8, mem, &d));
-    a.off_q = (const uint64_t *) d;
+    KMU_TRY(stage_to_device(ctx, "align.basesq", bases_q, mem == KMU_MEM_HOST ? (size_t) offsets_q[n_reads_q] : 0, mem, &a.bases_q));
+    KMU_TRY(stage_to_device(ctx, "align.offq", offsets_q, (size_t) n_reads_q + 1, mem, &a.off_q));
     if (bases_db == bases_q && offsets_db == offsets_q && n_reads_db == n_reads_q) { // a self-join is staged once
         a.bases_db = a.bases_q;
         a.off_db = a.off_q;
     } else {
-        KMU_TRY(stage_to_device(ctx, "align.basesdb", bases_db, mem == KMU_MEM_HOST ? (size_t) offsets_db[n_reads_db] : 0, mem, &d));
-        a.bases_db = (const uint8_t *) d;
-        KMU_TRY(stage_to_device(ctx, "align.offdb", offsets_db, ((size_t) n_reads_db + 1) * 8, mem, &d));
-        a.off_db = (const uint64_t *) d;
+        KMU_TRY(stage_to_device(ctx, "align.basesdb", bases_db, mem == KMU_MEM_HOST ? (size_t) offsets_db[n_reads_db] : 0, mem, &a.bases_db));
+        KMU_TRY(stage_to_device(ctx, "align.offdb", offsets_db, (size_t) n_reads_db + 1, mem, &a.off_db));
     }
     a.n_reads_q = n_reads_q;
     a.n_reads_db = n_reads_db;
     a.band = p->band;
     KMU_TRY(dev_array(ctx, "align.info", 2, &a.info));
     KMU_HIP(ctx, hipMemsetAsync(a.info, 0, 8, ctx->stream));
-    a.out = out;
-    if (mem == KMU_MEM_HOST) KMU_TRY(dev_array(ctx, "align.out", n_chains, &a.out));
+    KMU_TRY(place_output(ctx, "align.out", out, n_chains, mem, &a.out));
 
     KMU_TRY(launch(ctx, "k_chain_align", k_chain_align, dim3(grid_for(ctx, n_chains, 1, 16)), dim3(64), 0, a)); // (one-wave workgroups)
     uint32_t h_info[2] = {0, 0};
-    if (mem == KMU_MEM_HOST) KMU_HIP(ctx, hipMemcpyAsync(out, a.out, (size_t) n_chains * sizeof(kmu_chain_aln), hipMemcpyDeviceToHost, ctx->stream));
-    KMU_HIP(ctx, hipMemcpyAsync(h_info, a.info, 8, hipMemcpyDeviceToHost, ctx->stream));
-    KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (ctx->profiling) profile_collect(ctx);
+    KMU_TRY(bring_output(ctx, out, a.out, n_chains, mem));
+    KMU_TRY(read_back(ctx, {{h_info, a.info, sizeof h_info}}));
+    KMU_TRY(finish_synced(ctx));
     if (h_info[0])
         return fail(ctx, KMU_E_UNSUPPORTED, "a chain names a read that does not exist, a strand above 1, a start behind its end or an end "
                                             "behind the end of its read");

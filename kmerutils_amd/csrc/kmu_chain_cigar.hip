@@ -208,16 +208,12 @@ extern "C" int kmu_chain_cigar(kmu_ctx *ctx, const kmu_chain *chains, uint64_t n
     if (p->flags) return fail(ctx, KMU_E_BAD_ARG, "unknown flag bits 0x%x", p->flags);
     if (p->band > (KMU_ALIGN_MAX_DIAGS - 1u) / 2u)
         return fail(ctx, KMU_E_BAD_ARG, "band = %u: 2 band + 1 is above KMU_ALIGN_MAX_DIAGS = %d", p->band, KMU_ALIGN_MAX_DIAGS);
-    if (mem != KMU_MEM_HOST && mem != KMU_MEM_DEVICE) return fail(ctx, KMU_E_BAD_ARG, "bad mem %d", mem);
+    KMU_TRY(check_mem(ctx, mem));
     *n_ops_out = 0;
     if (n_chains == 0) {
-        if (mem == KMU_MEM_HOST) {
-            op_offsets_out[0] = 0;
-            return KMU_OK;
-        }
         KMU_HIP(ctx, hipSetDevice(ctx->device));
-        KMU_HIP(ctx, hipMemsetAsync(op_offsets_out, 0, 8, ctx->stream));
-        KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        KMU_TRY(zero_first_offset(ctx, op_offsets_out, mem));
+        if (mem == KMU_MEM_DEVICE) KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
         return KMU_OK;
     }
     if (n_reads_q == 0 || n_reads_db == 0) return fail(ctx, KMU_E_BAD_ARG, "chains but no reads");
@@ -225,36 +221,27 @@ extern "C" int kmu_chain_cigar(kmu_ctx *ctx, const kmu_chain *chains, uint64_t n
 
     CigarArgs c{};
     AlignArgs &a = c.a;
-    const void *d;
-    KMU_TRY(stage_to_device(ctx, "cigar.chains", chains, (size_t) n_chains * sizeof(kmu_chain), mem, &d));
-    a.chains = (const kmu_chain *) d;
+    KMU_TRY(stage_to_device(ctx, "cigar.chains", chains, (size_t) n_chains, mem, &a.chains));
     a.n_chains = n_chains;
-    KMU_TRY(stage_to_device(ctx, "cigar.basesq", bases_q, mem == KMU_MEM_HOST ? (size_t) offsets_q[n_reads_q] : 0, mem, &d));
-    a.bases_q = (const uint8_t *) d;
-    KMU_TRY(stage_to_device(ctx, "cigar.offq", offsets_q, ((size_t) n_reads_q + 1) * 8, mem, &d));
-    a.off_q = (const uint64_t *) d;
+    KMU_TRY(stage_to_device(ctx, "cigar.basesq", bases_q, mem == KMU_MEM_HOST ? (size_t) offsets_q[n_reads_q] : 0, mem, &a.bases_q));
+    KMU_TRY(stage_to_device(ctx, "cigar.offq", offsets_q, (size_t) n_reads_q + 1, mem, &a.off_q));
     if (bases_db == bases_q && offsets_db == offsets_q && n_reads_db == n_reads_q) { // a self-join is staged once
         a.bases_db = a.bases_q;
         a.off_db = a.off_q;
     } else {
-        KMU_TRY(stage_to_device(ctx, "cigar.basesdb", bases_db, mem == KMU_MEM_HOST ? (size_t) offsets_db[n_reads_db] : 0, mem, &d));
-        a.bases_db = (const uint8_t *) d;
-        KMU_TRY(stage_to_device(ctx, "cigar.offdb", offsets_db, ((size_t) n_reads_db + 1) * 8, mem, &d));
-        a.off_db = (const uint64_t *) d;
+        KMU_TRY(stage_to_device(ctx, "cigar.basesdb", bases_db, mem == KMU_MEM_HOST ? (size_t) offsets_db[n_reads_db] : 0, mem, &a.bases_db));
+        KMU_TRY(stage_to_device(ctx, "cigar.offdb", offsets_db, (size_t) n_reads_db + 1, mem, &a.off_db));
     }
     a.n_reads_q = n_reads_q;
     a.n_reads_db = n_reads_db;
     a.band = p->band;
     KMU_TRY(dev_array(ctx, "cigar.info", 2, &a.info));
     KMU_HIP(ctx, hipMemsetAsync(a.info, 0, 8, ctx->stream));
-    a.out = aln_out;
-    uint64_t *d_opoff = op_offsets_out;
-    uint32_t *d_ops = ops_out;
-    if (mem == KMU_MEM_HOST) {
-        KMU_TRY(dev_array(ctx, "cigar.aln", n_chains, &a.out));
-        KMU_TRY(dev_array(ctx, "cigar.opoff", n_chains + 1, &d_opoff));
-        if (ops_out) KMU_TRY(dev_array(ctx, "cigar.ops", cap ? cap : 1, &d_ops));
-    }
+    uint64_t *d_opoff;
+    uint32_t *d_ops;
+    KMU_TRY(place_output(ctx, "cigar.aln", aln_out, n_chains, mem, &a.out));
+    KMU_TRY(place_output(ctx, "cigar.opoff", op_offsets_out, n_chains + 1, mem, &d_opoff));
+    KMU_TRY(place_output(ctx, "cigar.ops", ops_out, cap ? cap : 1, mem, &d_ops));
 
     // the plan: rows per chain, their offsets, and the batches
     const uint64_t budget = p->max_trace_bytes ? p->max_trace_bytes : KMU_CIGAR_TRACE_DEFAULT;
@@ -268,15 +255,10 @@ extern "C" int kmu_chain_cigar(kmu_ctx *ctx, const kmu_chain *chains, uint64_t n
     KMU_TRY(device_scan_u32(ctx, c.rows, n_chains, d_roff));
     std::vector<uint64_t> roff(n_chains + 1);
     uint32_t h_info[2] = {0, 0};
-    KMU_HIP(ctx, hipMemcpyAsync(roff.data(), d_roff, (n_chains + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
-    KMU_HIP(ctx, hipMemcpyAsync(h_info, a.info, 8, hipMemcpyDeviceToHost, ctx->stream));
-    KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    KMU_TRY(read_back(ctx, {{roff.data(), d_roff, (n_chains + 1) * 8}, {h_info, a.info, sizeof h_info}})); // (the plan comes with the words)
     const char *refused = "a chain names a read that does not exist, a strand above 1, a start behind its end or an end behind the end of "
                           "its read";
-    if (h_info[0]) {
-        if (ctx->profiling) profile_collect(ctx);
-        return fail(ctx, KMU_E_UNSUPPORTED, "%s", refused);
-    }
+    if (h_info[0]) return refuse(ctx, KMU_E_UNSUPPORTED, "%s", refused);
     std::vector<uint64_t> cuts{0}; // batch k: the chains cuts[k] .. cuts[k + 1] - 1; a chain's own rows are within the budget
     uint64_t max_rows = 1, max_nb = 0;
     for (uint64_t b0 = 0; b0 < n_chains;) {
@@ -306,21 +288,17 @@ extern "C" int kmu_chain_cigar(kmu_ctx *ctx, const kmu_chain *chains, uint64_t n
     }
 
     uint64_t total = 0;
-    KMU_HIP(ctx, hipMemcpyAsync(&total, d_base + n_batches, 8, hipMemcpyDeviceToHost, ctx->stream));
-    KMU_HIP(ctx, hipMemcpyAsync(h_info, a.info, 8, hipMemcpyDeviceToHost, ctx->stream));
-    if (mem == KMU_MEM_HOST) {
-        KMU_HIP(ctx, hipMemcpyAsync(aln_out, a.out, (size_t) n_chains * sizeof(kmu_chain_aln), hipMemcpyDeviceToHost, ctx->stream));
-        KMU_HIP(ctx, hipMemcpyAsync(op_offsets_out, d_opoff, (size_t) (n_chains + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (ctx->profiling) profile_collect(ctx);
+    KMU_TRY(bring_output(ctx, aln_out, a.out, n_chains, mem));
+    KMU_TRY(bring_output(ctx, op_offsets_out, d_opoff, n_chains + 1, mem));
+    KMU_TRY(read_back(ctx, {{&total, d_base + n_batches}, {h_info, a.info, sizeof h_info}}));
+    KMU_TRY(finish_synced(ctx));
     if (h_info[0]) return fail(ctx, KMU_E_UNSUPPORTED, "%s", refused);
     if (h_info[1]) return fail(ctx, KMU_E_NON_ACGT, "pattern not a code in alphabet_2b (non-ACGT byte in an aligned segment)");
     *n_ops_out = total;
     if (ops_out && cap < total)
         return fail(ctx, KMU_E_BAD_ARG, "cap = %llu is below the %llu runs", (unsigned long long) cap, (unsigned long long) total);
     if (ops_out && mem == KMU_MEM_HOST && total) {
-        KMU_HIP(ctx, hipMemcpyAsync(ops_out, d_ops, (size_t) total * 4, hipMemcpyDeviceToHost, ctx->stream));
+        KMU_TRY(bring_output(ctx, ops_out, d_ops, total, mem));
         KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
     }
     return KMU_OK;

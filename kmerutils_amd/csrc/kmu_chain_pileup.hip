@@ -244,7 +244,7 @@ int pile_check_inputs(kmu_ctx *ctx, const PileInputs &in, const void *table_q, c
     if (!flags || (flags & ~(KMU_PILE_Q | KMU_PILE_DB))) return fail(ctx, KMU_E_BAD_ARG, "flags 0x%x: KMU_PILE_Q, KMU_PILE_DB or both", flags);
     const bool side_q = flags & KMU_PILE_Q, side_db = flags & KMU_PILE_DB;
     if ((side_q && !table_q) || (side_db && !table_db)) return fail(ctx, KMU_E_BAD_ARG, "null table for a side that is asked for");
-    if (in.mem != KMU_MEM_HOST && in.mem != KMU_MEM_DEVICE) return fail(ctx, KMU_E_BAD_ARG, "bad mem %d", in.mem);
+    KMU_TRY(check_mem(ctx, in.mem));
     if (side_q && side_db && table_q == table_db && !in.self())
         return fail(ctx, KMU_E_BAD_ARG, "one table for both sides needs the two batches to be the same arrays");
     if (in.n_chains && (in.n_reads_q == 0 || in.n_reads_db == 0)) return fail(ctx, KMU_E_BAD_ARG, "chains but no reads");
@@ -255,29 +255,20 @@ int pile_plan(kmu_ctx *ctx, const PileInputs &in, PileArgs *out, uint64_t *n_til
     const int mem = in.mem;
     const uint64_t n_chains = in.n_chains;
     PileArgs a{};
-    const void *d;
-    KMU_TRY(stage_to_device(ctx, "pile.chains", in.chains, (size_t) n_chains * sizeof(kmu_chain), mem, &d));
-    a.chains = (const kmu_chain *) d;
+    KMU_TRY(stage_to_device(ctx, "pile.chains", in.chains, (size_t) n_chains, mem, &a.chains));
     a.n_chains = n_chains;
-    KMU_TRY(stage_to_device(ctx, "pile.aln", in.aln, (size_t) n_chains * sizeof(kmu_chain_aln), mem, &d));
-    a.aln = (const kmu_chain_aln *) d;
-    KMU_TRY(stage_to_device(ctx, "pile.opoff", in.op_offsets, (size_t) (n_chains + 1) * 8, mem, &d));
-    a.op_off = (const uint64_t *) d;
-    KMU_TRY(stage_to_device(ctx, "pile.ops", in.ops, (size_t) in.n_ops * 4, mem, &d));
-    a.ops = (const uint32_t *) d;
+    KMU_TRY(stage_to_device(ctx, "pile.aln", in.aln, (size_t) n_chains, mem, &a.aln));
+    KMU_TRY(stage_to_device(ctx, "pile.opoff", in.op_offsets, (size_t) (n_chains + 1), mem, &a.op_off));
+    KMU_TRY(stage_to_device(ctx, "pile.ops", in.ops, (size_t) in.n_ops, mem, &a.ops));
     a.n_ops = in.n_ops;
-    KMU_TRY(stage_to_device(ctx, "pile.basesq", in.bases_q, mem == KMU_MEM_HOST ? (size_t) in.offsets_q[in.n_reads_q] : 0, mem, &d));
-    a.bases_q = (const uint8_t *) d;
-    KMU_TRY(stage_to_device(ctx, "pile.offq", in.offsets_q, ((size_t) in.n_reads_q + 1) * 8, mem, &d));
-    a.off_q = (const uint64_t *) d;
+    KMU_TRY(stage_to_device(ctx, "pile.basesq", in.bases_q, mem == KMU_MEM_HOST ? (size_t) in.offsets_q[in.n_reads_q] : 0, mem, &a.bases_q));
+    KMU_TRY(stage_to_device(ctx, "pile.offq", in.offsets_q, (size_t) in.n_reads_q + 1, mem, &a.off_q));
     if (in.self()) { // a self-join is staged once
         a.bases_db = a.bases_q;
         a.off_db = a.off_q;
     } else {
-        KMU_TRY(stage_to_device(ctx, "pile.basesdb", in.bases_db, mem == KMU_MEM_HOST ? (size_t) in.offsets_db[in.n_reads_db] : 0, mem, &d));
-        a.bases_db = (const uint8_t *) d;
-        KMU_TRY(stage_to_device(ctx, "pile.offdb", in.offsets_db, ((size_t) in.n_reads_db + 1) * 8, mem, &d));
-        a.off_db = (const uint64_t *) d;
+        KMU_TRY(stage_to_device(ctx, "pile.basesdb", in.bases_db, mem == KMU_MEM_HOST ? (size_t) in.offsets_db[in.n_reads_db] : 0, mem, &a.bases_db));
+        KMU_TRY(stage_to_device(ctx, "pile.offdb", in.offsets_db, (size_t) in.n_reads_db + 1, mem, &a.off_db));
     }
     a.n_reads_q = in.n_reads_q;
     a.n_reads_db = in.n_reads_db;
@@ -296,14 +287,10 @@ int pile_plan(kmu_ctx *ctx, const PileInputs &in, PileArgs *out, uint64_t *n_til
     KMU_TRY(launch(ctx, "k_pile_starts", k_pile_starts, dim3(grid_for(ctx, n_chains, 1, 16)), dim3(64), 0, a));
     uint32_t h_info[2] = {0, 0};
     uint64_t n_tiles = 0;
-    KMU_HIP(ctx, hipMemcpyAsync(h_info, a.info, 8, hipMemcpyDeviceToHost, ctx->stream));
-    KMU_HIP(ctx, hipMemcpyAsync(&n_tiles, d_tile_off + n_chains, 8, hipMemcpyDeviceToHost, ctx->stream));
-    KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (h_info[0] || n_tiles > a.tile_cap) {
-        if (ctx->profiling) profile_collect(ctx);
-        return fail(ctx, KMU_E_UNSUPPORTED, "a chain record kmu_chain_cigar would refuse, run offsets that decrease or end above n_ops, runs on a chain "
-                                            "without PATH, a run with an unknown op or of length 0, or runs that do not sum to the chain's segments");
-    }
+    KMU_TRY(read_back(ctx, {{h_info, a.info, sizeof h_info}, {&n_tiles, d_tile_off + n_chains}}));
+    if (h_info[0] || n_tiles > a.tile_cap)
+        return refuse(ctx, KMU_E_UNSUPPORTED, "a chain record kmu_chain_cigar would refuse, run offsets that decrease or end above n_ops, runs on a chain "
+                                              "without PATH, a run with an unknown op or of length 0, or runs that do not sum to the chain's segments");
     *out = a;
     *n_tiles_out = n_tiles;
     return KMU_OK;
@@ -342,7 +329,8 @@ extern "C" int kmu_chain_pileup(kmu_ctx *ctx, const kmu_chain *chains, uint64_t 
     }
     uint32_t h_info[2] = {0, 0};
     if (n_tiles) KMU_TRY(launch(ctx, "k_pile_vote", k_pile_vote, dim3(grid_for(ctx, n_tiles, 1, 32)), dim3(64), 0, a, n_tiles));
-    KMU_HIP(ctx, hipMemcpyAsync(h_info, a.info, 8, hipMemcpyDeviceToHost, ctx->stream));
+    KMU_TRY(read_back(ctx, {{h_info, a.info, sizeof h_info}}));
+    KMU_TRY(finish_synced(ctx));
     std::vector<uint32_t> got;
     auto add_down = [&](uint32_t *mine, const uint32_t *dev, size_t words) -> int { // the caller's table += this call's
         got.resize(words);
@@ -350,8 +338,6 @@ extern "C" int kmu_chain_pileup(kmu_ctx *ctx, const kmu_chain *chains, uint64_t 
         for (size_t k = 0; k < words; k++) mine[k] += got[k];
         return KMU_OK;
     };
-    KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (ctx->profiling) profile_collect(ctx);
     if (mem == KMU_MEM_HOST) {
         if (side_q) KMU_TRY(add_down(pile_q, a.pile_q, words_q));
         if (side_db && !shared) KMU_TRY(add_down(pile_db, a.pile_db, words_db));
@@ -365,38 +351,23 @@ extern "C" int kmu_pile_call(kmu_ctx *ctx, const uint32_t *pile, const uint8_t *
     if (!ctx || !pile || !bases || !offsets || !p || (!call_out && !reads_out)) return fail(ctx, KMU_E_BAD_ARG, "null argument");
     if (p->min_depth == 0) return fail(ctx, KMU_E_BAD_ARG, "min_depth must be at least 1");
     if (p->flags) return fail(ctx, KMU_E_BAD_ARG, "unknown flag bits 0x%x", p->flags);
-    if (mem != KMU_MEM_HOST && mem != KMU_MEM_DEVICE) return fail(ctx, KMU_E_BAD_ARG, "bad mem %d", mem);
+    KMU_TRY(check_mem(ctx, mem));
     if (n_reads == 0) return KMU_OK;
     KMU_HIP(ctx, hipSetDevice(ctx->device));
     uint64_t n_bases = 0;
-    if (mem == KMU_MEM_HOST) n_bases = offsets[n_reads];
-    else KMU_HIP(ctx, hipMemcpyAsync(&n_bases, offsets + n_reads, 8, hipMemcpyDeviceToHost, ctx->stream)); // (the grid; read below)
+    KMU_TRY(caller_word(ctx, offsets + n_reads, mem, &n_bases)); // (the grid)
 
     PileCallArgs a{};
-    const void *d;
-    KMU_TRY(stage_to_device(ctx, "pcall.pile", pile, (size_t) n_bases * PILE_COLS * 4, mem, &d));
-    a.pile = (const uint32_t *) d;
-    KMU_TRY(stage_to_device(ctx, "pcall.bases", bases, (size_t) n_bases, mem, &d));
-    a.bases = (const uint8_t *) d;
-    KMU_TRY(stage_to_device(ctx, "pcall.off", offsets, ((size_t) n_reads + 1) * 8, mem, &d));
-    a.off = (const uint64_t *) d;
+    KMU_TRY(stage_to_device(ctx, "pcall.pile", pile, (size_t) n_bases * PILE_COLS, mem, &a.pile));
+    KMU_TRY(stage_to_device(ctx, "pcall.bases", bases, (size_t) n_bases, mem, &a.bases));
+    KMU_TRY(stage_to_device(ctx, "pcall.off", offsets, (size_t) n_reads + 1, mem, &a.off));
     a.n_reads = n_reads;
     a.min_depth = p->min_depth;
-    a.call = call_out;
-    a.reads = reads_out;
-    if (mem == KMU_MEM_HOST) {
-        if (call_out) KMU_TRY(dev_array(ctx, "pcall.call", n_bases ? n_bases : 1, &a.call));
-        if (reads_out) KMU_TRY(dev_array(ctx, "pcall.reads", n_reads, &a.reads));
-    } else {
-        KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    }
+    KMU_TRY(place_output(ctx, "pcall.call", call_out, n_bases ? n_bases : 1, mem, &a.call));
+    KMU_TRY(place_output(ctx, "pcall.reads", reads_out, n_reads, mem, &a.reads));
     if (call_out && n_bases) KMU_TRY(launch(ctx, "k_pile_call", k_pile_call, dim3(grid_for(ctx, n_bases, 256)), dim3(256), 0, a));
     if (reads_out) KMU_TRY(launch(ctx, "k_pile_reads", k_pile_reads, dim3(grid_for(ctx, n_reads, 4)), dim3(256), 0, a));
-    if (mem == KMU_MEM_HOST) {
-        if (call_out && n_bases) KMU_HIP(ctx, hipMemcpyAsync(call_out, a.call, n_bases, hipMemcpyDeviceToHost, ctx->stream));
-        if (reads_out) KMU_HIP(ctx, hipMemcpyAsync(reads_out, a.reads, (size_t) n_reads * sizeof(kmu_read_pile), hipMemcpyDeviceToHost, ctx->stream));
-    }
-    KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (ctx->profiling) profile_collect(ctx);
-    return KMU_OK;
+    if (n_bases) KMU_TRY(bring_output(ctx, call_out, a.call, n_bases, mem));
+    KMU_TRY(bring_output(ctx, reads_out, a.reads, n_reads, mem));
+    return finish_sync(ctx);
 }

@@ -173,7 +173,7 @@ extern "C" int kmu_sg_clean(kmu_ctx *ctx, const kmu_sg_arc *arcs, uint64_t n_arc
     if (p->max_tip_reads > KMU_SG_CLEAN_MAX || p->max_bubble_reads > KMU_SG_CLEAN_MAX)
         return fail(ctx, KMU_E_BAD_ARG, "max_tip_reads = %u, max_bubble_reads = %u: at most %u", p->max_tip_reads, p->max_bubble_reads,
                     KMU_SG_CLEAN_MAX);
-    if (mem != KMU_MEM_HOST && mem != KMU_MEM_DEVICE) return fail(ctx, KMU_E_BAD_ARG, "bad mem %d", mem);
+    KMU_TRY(check_mem(ctx, mem));
     if (n_reads >= 0x80000000u) return fail(ctx, KMU_E_UNSUPPORTED, "%u reads: 2^31 or more", n_reads);
     if (n_arcs >= 0x100000000ull) return fail(ctx, KMU_E_UNSUPPORTED, "%llu arcs: 2^32 or more", (unsigned long long) n_arcs);
     if (n_arcs && !n_reads) return fail(ctx, KMU_E_BAD_ARG, "arcs but no reads");
@@ -188,12 +188,9 @@ extern "C" int kmu_sg_clean(kmu_ctx *ctx, const kmu_sg_arc *arcs, uint64_t n_arc
     }
     KMU_HIP(ctx, hipSetDevice(ctx->device));
     ClArgs a{};
-    const void *d;
-    KMU_TRY(stage_to_device(ctx, "cl.arcs", arcs, (size_t) n_arcs * sizeof(kmu_sg_arc), mem, &d));
-    a.arcs = (const kmu_sg_arc *) d;
+    KMU_TRY(stage_to_device(ctx, "cl.arcs", arcs, (size_t) n_arcs, mem, &a.arcs));
     a.n_arcs = n_arcs;
-    KMU_TRY(stage_to_device(ctx, "cl.reads", reads, (size_t) n_reads * sizeof(kmu_sg_read), mem, &d));
-    a.reads = (const kmu_sg_read *) d;
+    KMU_TRY(stage_to_device(ctx, "cl.reads", reads, (size_t) n_reads, mem, &a.reads));
     a.n_reads = n_reads;
     a.T = p->max_tip_reads;
     a.B = p->max_bubble_reads;
@@ -212,12 +209,8 @@ extern "C" int kmu_sg_clean(kmu_ctx *ctx, const kmu_sg_arc *arcs, uint64_t n_arc
     a.spared = a.tipcnt + n_v;
     a.rflag = a.spared + n_v;
     a.sole2 = a.sole1 + n_v;
-    a.arcs_out = arcs_out;
-    a.reads_out = reads_out;
-    if (mem == KMU_MEM_HOST) {
-        KMU_TRY(dev_array(ctx, "cl.out", n_arcs ? n_arcs : 1, &a.arcs_out));
-        if (reads_out) KMU_TRY(dev_array(ctx, "cl.readsout", n_reads, &a.reads_out));
-    }
+    KMU_TRY(place_output(ctx, "cl.out", arcs_out, n_arcs ? n_arcs : 1, mem, &a.arcs_out));
+    KMU_TRY(place_output(ctx, "cl.readsout", reads_out, n_reads, mem, &a.reads_out));
     KMU_HIP(ctx, hipMemsetAsync(zeros, 0, n_zero * 4, ctx->stream));
     KMU_HIP(ctx, hipMemsetAsync(a.sole1, 0xFF, 2 * n_v * 4, ctx->stream));
 
@@ -235,8 +228,7 @@ extern "C" int kmu_sg_clean(kmu_ctx *ctx, const kmu_sg_arc *arcs, uint64_t n_arc
 
     // the stats and the refusal flag come to the host (the synchronisation)
     uint32_t h[18];
-    KMU_HIP(ctx, hipMemcpyAsync(h, zeros, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
-    KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    KMU_TRY(read_back(ctx, {{h, zeros, sizeof h}}));
     if (h[16]) {
         (void) finish_call(ctx, mem);
         return fail(ctx, KMU_E_UNSUPPORTED,
@@ -245,9 +237,7 @@ extern "C" int kmu_sg_clean(kmu_ctx *ctx, const kmu_sg_arc *arcs, uint64_t n_arc
     }
     static_assert(sizeof(kmu_sg_clean_stats) == 64, "8 counters");
     memcpy(stats_out, h, sizeof(kmu_sg_clean_stats));
-    if (mem == KMU_MEM_HOST) {
-        KMU_TRY(copy_out(ctx, arcs_out, a.arcs_out, (size_t) n_arcs * sizeof(kmu_sg_arc), mem));
-        KMU_TRY(copy_out(ctx, reads_out, a.reads_out, (size_t) n_reads * sizeof(kmu_sg_read), mem));
-    }
+    KMU_TRY(bring_output(ctx, arcs_out, a.arcs_out, n_arcs, mem));
+    KMU_TRY(bring_output(ctx, reads_out, a.reads_out, n_reads, mem));
     return finish_call(ctx, mem);
 }

@@ -108,17 +108,18 @@ int kmu_sig_equal_pairs(kmu_ctx *ctx, const void *sig_a, uint32_t na, const void
     if (mem == KMU_MEM_HOST) // row indices are checked where the host can see them
         for (uint64_t p = 0; p < n_pairs; p++)
             if (ia[p] >= na || ib[p] >= nb) return fail(ctx, KMU_E_BAD_ARG, "pair %llu names a row out of range", (unsigned long long) p);
-    const void *da, *db, *dia, *dib;
+    const void *da, *db;
+    const uint32_t *dia, *dib;
     KMU_TRY(stage_to_device(ctx, "cmp.a", sig_a, (size_t) na * m * wb, mem, &da));
     KMU_TRY(stage_to_device(ctx, "cmp.b", sig_b, (size_t) nb * m * wb, mem, &db));
-    KMU_TRY(stage_to_device(ctx, "cmp.ia", ia, n_pairs * 4, mem, &dia));
-    KMU_TRY(stage_to_device(ctx, "cmp.ib", ib, n_pairs * 4, mem, &dib));
-    uint32_t *dout = out;
-    if (mem == KMU_MEM_HOST) KMU_TRY(dev_array(ctx, "cmp.out", n_pairs, &dout));
+    KMU_TRY(stage_to_device(ctx, "cmp.ia", ia, n_pairs, mem, &dia));
+    KMU_TRY(stage_to_device(ctx, "cmp.ib", ib, n_pairs, mem, &dib));
+    uint32_t *dout;
+    KMU_TRY(place_output(ctx, "cmp.out", out, n_pairs, mem, &dout));
     const int grid = grid_for(ctx, n_pairs, 4, 16);
     if (wb == 4) KMU_TRY(launch(ctx, "k_sig_equal_pairs", k_sig_equal_pairs<uint32_t>, dim3(grid), dim3(256), 0, da, db, m, dia, dib, n_pairs, dout));
     else KMU_TRY(launch(ctx, "k_sig_equal_pairs", k_sig_equal_pairs<uint64_t>, dim3(grid), dim3(256), 0, da, db, m, dia, dib, n_pairs, dout));
-    if (mem == KMU_MEM_HOST) KMU_HIP(ctx, hipMemcpyAsync(out, dout, n_pairs * 4, hipMemcpyDeviceToHost, ctx->stream));
+    KMU_TRY(bring_output(ctx, out, dout, n_pairs, mem));
     return finish_call(ctx, mem);
 }
 
@@ -133,14 +134,13 @@ int kmu_sig_equal_matrix(kmu_ctx *ctx, const void *sig_a, uint32_t na, const voi
     const void *da, *db;
     KMU_TRY(stage_to_device(ctx, "cmp.a", sig_a, (size_t) na * m * wb, mem, &da));
     KMU_TRY(stage_to_device(ctx, "cmp.b", sig_b, (size_t) nb * m * wb, mem, &db));
-    uint16_t *dout = out;
-    if (mem == KMU_MEM_HOST) KMU_TRY(dev_array(ctx, "cmp.out", (size_t) na * nb, &dout));
+    uint16_t *dout;
+    KMU_TRY(place_output(ctx, "cmp.out", out, (size_t) na * nb, mem, &dout));
     const uint64_t tiles = (uint64_t) ((na + MT - 1) / MT) * ((nb + MT - 1) / MT);
     if (tiles > 0x7FFFFFFFull) return fail(ctx, KMU_E_UNSUPPORTED, "matrix too large for one launch: split the rows");
     if (wb == 4) KMU_TRY(launch(ctx, "k_sig_equal_matrix", k_sig_equal_matrix<uint32_t>, dim3((uint32_t) tiles), dim3(256), 0, da, na, db, nb, m, dout));
     else KMU_TRY(launch(ctx, "k_sig_equal_matrix", k_sig_equal_matrix<uint64_t>, dim3((uint32_t) tiles), dim3(256), 0, da, na, db, nb, m, dout));
-    if (mem == KMU_MEM_HOST)
-        KMU_HIP(ctx, hipMemcpyAsync(out, dout, (size_t) na * nb * 2, hipMemcpyDeviceToHost, ctx->stream));
+    KMU_TRY(bring_output(ctx, out, dout, (size_t) na * nb, mem));
     return finish_call(ctx, mem);
 }
 
@@ -153,21 +153,17 @@ int kmu_minhash_distance_pairs(kmu_ctx *ctx, const uint64_t *hashes_a, uint32_t 
     if (mem == KMU_MEM_HOST)
         for (uint64_t p = 0; p < n_pairs; p++)
             if (ia[p] >= na || ib[p] >= nb) return fail(ctx, KMU_E_BAD_ARG, "pair %llu names a row out of range", (unsigned long long) p);
-    const void *da, *db, *dia, *dib;
-    KMU_TRY(stage_to_device(ctx, "cmp.a", hashes_a, (size_t) na * m * 8, mem, &da));
-    KMU_TRY(stage_to_device(ctx, "cmp.b", hashes_b, (size_t) nb * m * 8, mem, &db));
-    KMU_TRY(stage_to_device(ctx, "cmp.ia", ia, n_pairs * 4, mem, &dia));
-    KMU_TRY(stage_to_device(ctx, "cmp.ib", ib, n_pairs * 4, mem, &dib));
-    uint32_t *dout = out;
-    if (mem == KMU_MEM_HOST) {
-        void *q;
-        KMU_TRY(dev_buf(ctx, "cmp.out", n_pairs * 12, &q));
-        dout = (uint32_t *) q;
-    }
+    const uint64_t *da, *db;
+    const uint32_t *dia, *dib;
+    KMU_TRY(stage_to_device(ctx, "cmp.a", hashes_a, (size_t) na * m, mem, &da));
+    KMU_TRY(stage_to_device(ctx, "cmp.b", hashes_b, (size_t) nb * m, mem, &db));
+    KMU_TRY(stage_to_device(ctx, "cmp.ia", ia, n_pairs, mem, &dia));
+    KMU_TRY(stage_to_device(ctx, "cmp.ib", ib, n_pairs, mem, &dib));
+    uint32_t *dout;
+    KMU_TRY(place_output(ctx, "cmp.out", out, n_pairs * 3, mem, &dout));
     const int grid = (int) std::min<uint64_t>((n_pairs + 255) / 256, (uint64_t) ctx->num_cus * 8);
-    KMU_TRY(launch(ctx, "k_minhash_distance", k_minhash_distance, dim3(grid), dim3(256), 0, (const uint64_t *) da, (const uint64_t *) db, m,
-                   (const uint32_t *) dia, (const uint32_t *) dib, n_pairs, dout));
-    if (mem == KMU_MEM_HOST) KMU_HIP(ctx, hipMemcpyAsync(out, dout, n_pairs * 12, hipMemcpyDeviceToHost, ctx->stream));
+    KMU_TRY(launch(ctx, "k_minhash_distance", k_minhash_distance, dim3(grid), dim3(256), 0, da, db, m, dia, dib, n_pairs, dout));
+    KMU_TRY(bring_output(ctx, out, dout, n_pairs * 3, mem));
     return finish_call(ctx, mem);
 }
 

@@ -137,13 +137,10 @@ __global__ void __launch_bounds__(256) k_cc_number(const uint32_t *label, const 
 template <class E>
 static int components_run(kmu_ctx *ctx, uint32_t n_nodes, const E &edges, uint64_t n_edges, int mem, uint32_t *label_out,
                           uint32_t *cluster_out, uint32_t *size_out, uint32_t *members_out, uint32_t *n_components_out) {
-    const size_t nb = (size_t) n_nodes * 4;
-    uint32_t *label = label_out, *cluster = cluster_out, *size = size_out;
-    if (mem == KMU_MEM_HOST) {
-        KMU_TRY(dev_array(ctx, "cc.label", n_nodes, &label));
-        if (cluster_out) KMU_TRY(dev_array(ctx, "cc.cluster", n_nodes, &cluster));
-        if (size_out) KMU_TRY(dev_array(ctx, "cc.size", n_nodes, &size));
-    }
+    uint32_t *label, *cluster, *size;
+    KMU_TRY(place_output(ctx, "cc.label", label_out, n_nodes, mem, &label));
+    KMU_TRY(place_output(ctx, "cc.cluster", cluster_out, n_nodes, mem, &cluster));
+    KMU_TRY(place_output(ctx, "cc.size", size_out, n_nodes, mem, &size));
     const bool numbered = cluster_out || size_out || members_out;
     const bool ranked = numbered || n_components_out;
     uint32_t *is_root = nullptr, *v0 = nullptr, *v1 = nullptr;
@@ -167,18 +164,14 @@ static int components_run(kmu_ctx *ctx, uint32_t n_nodes, const E &edges, uint64
     if (numbered) KMU_TRY(launch(ctx, "k_cc_number", k_cc_number, dim3(node_grid), dim3(256), 0, label, rank, n_nodes, cluster, size, k0, v0));
     if (members_out) {
         KMU_TRY(radix_sort_pairs_passes(ctx, k0, v0, k1, v1, n_nodes, radix_id_passes(n_nodes), nullptr));
-        KMU_HIP(ctx, hipMemcpyAsync(members_out, v0, nb, mem == KMU_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice,
-                                    ctx->stream));
+        KMU_TRY(copy_out(ctx, members_out, v0, (size_t) n_nodes * 4, mem));
     }
-    if (mem == KMU_MEM_HOST) {
-        KMU_HIP(ctx, hipMemcpyAsync(label_out, label, nb, hipMemcpyDeviceToHost, ctx->stream));
-        if (cluster_out) KMU_HIP(ctx, hipMemcpyAsync(cluster_out, cluster, nb, hipMemcpyDeviceToHost, ctx->stream));
-        if (size_out) KMU_HIP(ctx, hipMemcpyAsync(size_out, size, nb, hipMemcpyDeviceToHost, ctx->stream));
-    }
+    KMU_TRY(bring_output(ctx, label_out, label, n_nodes, mem));
+    KMU_TRY(bring_output(ctx, cluster_out, cluster, n_nodes, mem));
+    KMU_TRY(bring_output(ctx, size_out, size, n_nodes, mem));
     if (n_components_out) { // the one synchronisation of a device call: the count crosses to the host
         uint64_t total = 0;
-        KMU_HIP(ctx, hipMemcpyAsync(&total, rank + n_nodes, 8, hipMemcpyDeviceToHost, ctx->stream));
-        KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        KMU_TRY(read_back(ctx, {{&total, rank + n_nodes}}));
         *n_components_out = (uint32_t) total;
     }
     return finish_call(ctx, mem);
@@ -186,7 +179,7 @@ static int components_run(kmu_ctx *ctx, uint32_t n_nodes, const E &edges, uint64
 
 static int cc_check_common(kmu_ctx *ctx, uint32_t n_nodes, int mem, const uint32_t *label_out) {
     if (!ctx || !label_out) return fail(ctx, KMU_E_BAD_ARG, "null argument");
-    if (mem != KMU_MEM_HOST && mem != KMU_MEM_DEVICE) return fail(ctx, KMU_E_BAD_ARG, "bad mem %d", mem);
+    KMU_TRY(check_mem(ctx, mem));
     if (n_nodes == 0xFFFFFFFFu) return fail(ctx, KMU_E_UNSUPPORTED, "n_nodes = 2^32 - 1: node numbers must stay below KMU_KNN_NONE");
     return KMU_OK;
 }
@@ -207,9 +200,9 @@ extern "C" int kmu_components(kmu_ctx *ctx, uint32_t n_nodes, const uint32_t *ed
     if (n_nodes == 0) return KMU_OK;
     if (n_edges > SIZE_MAX / 4 / stride) return fail(ctx, KMU_E_UNSUPPORTED, "%llu records of %u words", (unsigned long long) n_edges, stride);
     KMU_HIP(ctx, hipSetDevice(ctx->device));
-    const void *p;
-    KMU_TRY(stage_to_device(ctx, "cc.edges", edges, (size_t) n_edges * stride * 4, mem, &p));
-    const CcRecords rec{(const uint32_t *) p, stride, weight_at, min_weight};
+    const uint32_t *d_edges;
+    KMU_TRY(stage_to_device(ctx, "cc.edges", edges, (size_t) n_edges * stride, mem, &d_edges));
+    const CcRecords rec{d_edges, stride, weight_at, min_weight};
     return components_run(ctx, n_nodes, rec, n_edges, mem, label_out, cluster_out, size_out, members_out, n_components_out);
 }
 
@@ -224,9 +217,10 @@ extern "C" int kmu_components_knn(kmu_ctx *ctx, uint32_t n_nodes, const uint32_t
     if (n_nodes == 0) return KMU_OK;
     KMU_HIP(ctx, hipSetDevice(ctx->device));
     const uint64_t n_edges = (uint64_t) n_nodes * k;
-    const void *p, *q;
-    KMU_TRY(stage_to_device(ctx, "cc.edges", idx, (size_t) n_edges * 4, mem, &p));
-    KMU_TRY(stage_to_device(ctx, "cc.eq", eq, (size_t) n_edges * 2, mem, &q));
-    const CcKnn lists{(const uint32_t *) p, (const uint16_t *) q, k, eq ? min_eq : 0u};
+    const uint32_t *d_idx;
+    const uint16_t *d_eq;
+    KMU_TRY(stage_to_device(ctx, "cc.edges", idx, (size_t) n_edges, mem, &d_idx));
+    KMU_TRY(stage_to_device(ctx, "cc.eq", eq, (size_t) n_edges, mem, &d_eq));
+    const CcKnn lists{d_idx, d_eq, k, eq ? min_eq : 0u};
     return components_run(ctx, n_nodes, lists, n_edges, mem, label_out, cluster_out, size_out, members_out, n_components_out);
 }

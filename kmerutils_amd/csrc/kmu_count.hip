@@ -357,9 +357,7 @@ int flat_stream_extent(kmu_ctx *ctx, const uint64_t *host_offsets, uint32_t n_se
         return KMU_OK;
     }
     uint64_t first = 0, last = 0;
-    KMU_HIP(ctx, hipMemcpyAsync(&first, ds.offsets, 8, hipMemcpyDeviceToHost, ctx->stream));
-    KMU_HIP(ctx, hipMemcpyAsync(&last, ds.offsets + n_seq, 8, hipMemcpyDeviceToHost, ctx->stream));
-    KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    KMU_TRY(read_back(ctx, {{&first, ds.offsets}, {&last, ds.offsets + n_seq}}));
     const uint64_t shift = first & ~(uint64_t) 1023;
     if (shift) {
         uint64_t *q;
@@ -392,19 +390,10 @@ int add_entries(kmu_counter *c, const uint64_t *kmers, const uint32_t *counts, u
     kmu_ctx *ctx = c->ctx;
     KMU_HIP(ctx, hipSetDevice(ctx->device));
     if (n == 0) return KMU_OK;
-    const uint64_t *d_k = kmers;
-    const uint32_t *d_c = counts;
-    if (mem == KMU_MEM_HOST) {
-        void *q;
-        KMU_TRY(dev_buf(ctx, "cnt.in.k", n * 8, &q));
-        KMU_HIP(ctx, hipMemcpyAsync(q, kmers, n * 8, hipMemcpyHostToDevice, ctx->stream));
-        d_k = (const uint64_t *) q;
-        if (counts) {
-            KMU_TRY(dev_buf(ctx, "cnt.in.c", n * 4, &q));
-            KMU_HIP(ctx, hipMemcpyAsync(q, counts, n * 4, hipMemcpyHostToDevice, ctx->stream));
-            d_c = (const uint32_t *) q;
-        }
-    }
+    const uint64_t *d_k;
+    const uint32_t *d_c;
+    KMU_TRY(stage_to_device(ctx, "cnt.in.k", kmers, n, mem, &d_k));
+    KMU_TRY(stage_to_device(ctx, "cnt.in.c", counts, n, mem, &d_c));
     uint32_t *d_err;
     KMU_TRY(get_err_word(ctx, &d_err));
     KMU_TRY(table_alloc_for(c, nullptr, 0, d_err, 0.0, std::max<uint64_t>(c->p.capacity_hint, n)));
@@ -470,8 +459,7 @@ static int count_stats(kmu_counter *c, uint64_t *distinct, uint64_t *unique, uin
     KMU_TRY(launch(ctx, "k_count_stats", k_count_stats, dim3(grid_for(ctx, c->nslots, 1024)), dim3(256), 0, table_of(c), c->nslots, c->scalars,
                    (uint32_t) std::min<uint64_t>(count_ceiling(c), 0xFFFFFFFFull)));
     uint64_t h[4];
-    KMU_HIP(ctx, hipMemcpyAsync(h, c->scalars, 32, hipMemcpyDeviceToHost, ctx->stream));
-    KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    KMU_TRY(read_back(ctx, {{h, c->scalars, sizeof h}}));
     if (distinct) *distinct = h[0];
     if (unique) *unique = h[1];
     if (occurrences) *occurrences = h[3];
@@ -505,8 +493,7 @@ int select_entries(kmu_counter *c, uint32_t min_count, uint32_t maxc, uint32_t p
     KMU_TRY(launch(ctx, "k_count_select", k_count_select, dim3(grid_for(ctx, c->nslots, 1024)), dim3(256), 0, table_of(c), c->nslots, min_count, maxc,
                    w32, part, n_parts, cap, d_k, d_c, c->scalars + 2));
     uint64_t n = 0;
-    KMU_HIP(ctx, hipMemcpyAsync(&n, c->scalars + 2, 8, hipMemcpyDeviceToHost, ctx->stream));
-    KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    KMU_TRY(read_back(ctx, {{&n, c->scalars + 2}}));
     *n_out = n;
     if (!kmers_out) return KMU_OK;
     if (n > cap) return fail(ctx, KMU_E_BAD_ARG, "output capacity %llu < %llu records", (unsigned long long) cap, (unsigned long long) n);
@@ -659,17 +646,12 @@ int kmu_count_query(kmu_counter *c, const uint64_t *canon_kmers, uint64_t n, int
     KMU_HIP(ctx, hipSetDevice(ctx->device));
     if (n == 0) return KMU_OK;
     KMU_TRY(materialize(c));
-    const uint64_t *d_k = canon_kmers;
-    uint32_t *d_o = counts_out;
-    if (mem == KMU_MEM_HOST) {
-        void *q;
-        KMU_TRY(dev_buf(ctx, "cnt.in.k", n * 8, &q));
-        KMU_HIP(ctx, hipMemcpyAsync(q, canon_kmers, n * 8, hipMemcpyHostToDevice, ctx->stream));
-        d_k = (const uint64_t *) q;
-        KMU_TRY(dev_array(ctx, "cnt.out.c", n, &d_o));
-    }
+    const uint64_t *d_k;
+    uint32_t *d_o;
+    KMU_TRY(stage_to_device(ctx, "cnt.in.k", canon_kmers, n, mem, &d_k));
+    KMU_TRY(place_output(ctx, "cnt.out.c", counts_out, n, mem, &d_o));
     KMU_TRY(launch(ctx, "k_count_query", k_count_query, dim3(grid_for(ctx, n, 256)), dim3(256), 0, d_k, n, table_of(c), max_count(c), d_o));
-    if (mem == KMU_MEM_HOST) KMU_HIP(ctx, hipMemcpyAsync(counts_out, d_o, n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    KMU_TRY(bring_output(ctx, counts_out, d_o, n, mem));
     return finish_call(ctx, mem);
 }
 
@@ -745,26 +727,21 @@ int kmu_count_once_positions(kmu_counter *c, const uint8_t *bases, const uint64_
     KMU_TRY(launch(ctx, "k_once_count", k_once_count, dim3(grid), dim3(256), 0, ds.bases, ds.offsets, n_seq, c->p.kmer_size, table_of(c), cnt));
     KMU_TRY(device_scan_u32(ctx, cnt, nsteps, base));
     uint64_t n = 0;
-    KMU_HIP(ctx, hipMemcpyAsync(&n, base + nsteps, 8, hipMemcpyDeviceToHost, ctx->stream));
-    KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    KMU_TRY(read_back(ctx, {{&n, base + nsteps}}));
     *n_out = n;
     if (!kmers_out) return KMU_OK; // size query
     if (cap < n) return fail(ctx, KMU_E_BAD_ARG, "output too small: %llu records", (unsigned long long) n);
     if (n == 0) return KMU_OK;
-    uint64_t *d_k = kmers_out;
-    uint32_t *d_s = numseq_out, *d_p = numkmer_out;
-    if (mem == KMU_MEM_HOST) {
-        KMU_TRY(dev_array(ctx, "once.k", n + 8, &d_k));
-        KMU_TRY(dev_array(ctx, "once.s", n + 16, &d_s));
-        KMU_TRY(dev_array(ctx, "once.p", n + 16, &d_p));
-    }
+    uint64_t *d_k;
+    uint32_t *d_s, *d_p;
+    KMU_TRY(place_output(ctx, "once.k", kmers_out, n + 8, mem, &d_k));
+    KMU_TRY(place_output(ctx, "once.s", numseq_out, n + 16, mem, &d_s));
+    KMU_TRY(place_output(ctx, "once.p", numkmer_out, n + 16, mem, &d_p));
     KMU_TRY(launch(ctx, "k_once_emit", k_once_emit, dim3(grid), dim3(256), 0, ds.bases, ds.offsets, n_seq, c->p.kmer_size, table_of(c), base, d_k,
                    d_s, d_p));
-    if (mem == KMU_MEM_HOST) {
-        KMU_HIP(ctx, hipMemcpyAsync(kmers_out, d_k, n * 8, hipMemcpyDeviceToHost, ctx->stream));
-        KMU_HIP(ctx, hipMemcpyAsync(numseq_out, d_s, n * 4, hipMemcpyDeviceToHost, ctx->stream));
-        KMU_HIP(ctx, hipMemcpyAsync(numkmer_out, d_p, n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    }
+    KMU_TRY(bring_output(ctx, kmers_out, d_k, n, mem));
+    KMU_TRY(bring_output(ctx, numseq_out, d_s, n, mem));
+    KMU_TRY(bring_output(ctx, numkmer_out, d_p, n, mem));
     return finish_call(ctx, mem);
 }
 
@@ -774,19 +751,13 @@ int kmu_count_add_superkmers(kmu_counter *c, const void *records, uint64_t n_rec
     KMU_HIP(ctx, hipSetDevice(ctx->device));
     if (!smer_supported(c->p.kmer_type, c->p.kmer_size)) return fail(ctx, KMU_E_UNSUPPORTED, "super-k-mers need Kmer64bit with 17 <= k <= 31");
     if (n_records == 0) return KMU_OK;
-    const void *d_r = records;
-    if (mem == KMU_MEM_HOST) {
-        void *q;
-        KMU_TRY(dev_buf(ctx, "cnt.in.k", n_records * SMER_REC_BYTES + 64, &q));
-        KMU_HIP(ctx, hipMemcpyAsync(q, records, n_records * SMER_REC_BYTES, hipMemcpyHostToDevice, ctx->stream));
-        d_r = q;
-    }
-    void *cur;
-    KMU_TRY(dev_buf(ctx, "cnt.smer_cur", 64, &cur));
+    const uint8_t *d_r;
+    KMU_TRY(stage_to_device(ctx, "cnt.in.k", (const uint8_t *) records, n_records * SMER_REC_BYTES, mem, &d_r, 64));
+    uint64_t *cur;
+    KMU_TRY(dev_array(ctx, "cnt.smer_cur", 8, &cur));
     uint64_t n_kmers = 0;
-    KMU_TRY(smer_count_kmers(ctx, d_r, n_records, (uint64_t *) cur));
-    KMU_HIP(ctx, hipMemcpyAsync(&n_kmers, cur, 8, hipMemcpyDeviceToHost, ctx->stream));
-    KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    KMU_TRY(smer_count_kmers(ctx, d_r, n_records, cur));
+    KMU_TRY(read_back(ctx, {{&n_kmers, cur}}));
     KMU_TRY(add_superkmers(c, d_r, n_records, n_kmers));
     return finish_call(ctx, mem);
 }

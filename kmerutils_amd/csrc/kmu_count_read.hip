@@ -434,8 +434,7 @@ static int stats_chunked(const ProfileCall &pc, uint64_t total_bases, uint64_t c
     ProfChunk *d_plan = (ProfChunk *) (d_head + 2);
     KMU_TRY(launch(ctx, nullptr, k_profile_plan, dim3(1), dim3(64), 0, pc.ds->offsets, pc.ds->n_seq, chunk, (uint32_t) max_ch, d_head, d_plan));
     uint64_t head[2] = {0, 0};
-    KMU_HIP(ctx, hipMemcpyAsync(head, d_head, 16, hipMemcpyDeviceToHost, ctx->stream));
-    KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    KMU_TRY(read_back(ctx, {{head, d_head, sizeof head}}));
     if (head[1] || head[0] > max_ch) return fail(ctx, KMU_E_HIP, "read profile: the chunk plan overflowed (%llu chunks)", (unsigned long long) max_ch);
     std::vector<ProfChunk> plan((size_t) head[0]);
     if (!plan.empty()) KMU_HIP(ctx, hipMemcpy(plan.data(), d_plan, plan.size() * sizeof(ProfChunk), hipMemcpyDeviceToHost));
@@ -481,15 +480,15 @@ int kmu_count_histogram(kmu_counter *c, uint64_t *hist_out, uint32_t n_bins, int
     if (!c || !hist_out || n_bins < 2 || n_bins > 65536 || (mem != KMU_MEM_HOST && mem != KMU_MEM_DEVICE)) return KMU_E_BAD_ARG;
     kmu_ctx *ctx = c->ctx;
     KMU_HIP(ctx, hipSetDevice(ctx->device));
-    uint64_t *d_h = hist_out;
-    if (mem == KMU_MEM_HOST) KMU_TRY(dev_array(ctx, "cnt.hist", (size_t) n_bins, &d_h));
+    uint64_t *d_h;
+    KMU_TRY(place_output(ctx, "cnt.hist", hist_out, (size_t) n_bins, mem, &d_h));
     KMU_HIP(ctx, hipMemsetAsync(d_h, 0, (size_t) n_bins * 8, ctx->stream));
     if (!c->empty) { // (an empty counter, or one whose table waits for its first add: nothing is launched on the table)
         KMU_TRY(materialize(c));
         KMU_TRY(launch(ctx, "k_count_hist", k_count_hist, dim3(grid_for(ctx, c->nslots, 1024)), dim3(256), 0, table_of(c), c->nslots, max_count(c),
                        n_bins - 1, (unsigned long long *) d_h));
     }
-    if (mem == KMU_MEM_HOST) KMU_HIP(ctx, hipMemcpyAsync(hist_out, d_h, (size_t) n_bins * 8, hipMemcpyDeviceToHost, ctx->stream));
+    KMU_TRY(bring_output(ctx, hist_out, d_h, (size_t) n_bins, mem));
     return finish_call(ctx, mem);
 }
 
@@ -514,16 +513,15 @@ int kmu_count_read_profile(kmu_counter *c, const uint8_t *bases, const uint64_t 
     const uint64_t shift = mem == KMU_MEM_DEVICE ? (uint64_t) (ds.bases - bases) : 0;
     const uint64_t off0 = mem == KMU_MEM_HOST ? offsets[0] : 0;
     if (mem == KMU_MEM_DEVICE && total_bases >= (1ull << 32)) {
-        unsigned long long longest = 0;
+        uint64_t longest = 0;
         KMU_HIP(ctx, hipMemsetAsync(c->scalars, 0, 8, ctx->stream));
         KMU_TRY(launch(ctx, nullptr, k_profile_maxlen, dim3(grid_for(ctx, n_seq, 256)), dim3(256), 0, ds.offsets, n_seq,
                        (unsigned long long *) c->scalars));
-        KMU_HIP(ctx, hipMemcpyAsync(&longest, c->scalars, 8, hipMemcpyDeviceToHost, ctx->stream));
-        KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        KMU_TRY(read_back(ctx, {{&longest, c->scalars}}));
         if (longest >= (1ull << 32)) return fail(ctx, KMU_E_UNSUPPORTED, "a sequence has 2^32 bases or more");
     }
-    kmu_read_abundance *d_stats = stats_out;
-    if (stats_out && mem == KMU_MEM_HOST) KMU_TRY(dev_array(ctx, "prof.stats", (size_t) n_seq, &d_stats));
+    kmu_read_abundance *d_stats = nullptr;
+    KMU_TRY(place_output(ctx, "prof.stats", stats_out, (size_t) n_seq, mem, &d_stats));
     if (total_bases == 0) { // nothing but empty sequences: no k-mer anywhere
         if (stats_out) {
             KMU_HIP(ctx, hipMemsetAsync(d_stats, 0, (size_t) n_seq * sizeof(kmu_read_abundance), ctx->stream));
@@ -555,8 +553,7 @@ int kmu_count_read_profile(kmu_counter *c, const uint8_t *bases, const uint64_t 
         if (counts_out && mem == KMU_MEM_HOST)
             KMU_HIP(ctx, hipMemcpyAsync(counts_out + off0, d_counts, (size_t) total_bases * 2, hipMemcpyDeviceToHost, ctx->stream));
     } else KMU_TRY(stats_chunked(pc, total_bases, chunk, d_stats));
-    if (stats_out && mem == KMU_MEM_HOST)
-        KMU_HIP(ctx, hipMemcpyAsync(stats_out, d_stats, (size_t) n_seq * sizeof(kmu_read_abundance), hipMemcpyDeviceToHost, ctx->stream));
+    KMU_TRY(bring_output(ctx, stats_out, d_stats, (size_t) n_seq, mem));
     return finish_checked(ctx, mem, d_err);
 }
 

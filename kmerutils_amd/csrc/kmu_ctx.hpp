@@ -1,9 +1,20 @@
-// kmu_ctx.hpp -- host-side context of libkmu: device, stream, error text, workspace arena, per-kernel timing, and the three steps
-// every host driver is written in:
+// kmu_ctx.hpp -- host-side context of libkmu: device, stream, error text, workspace arena, per-kernel timing, and the steps every
+// host driver is written in:
 //   dev_array<T>(ctx, name, count, &p)  workspace `name` as `count` elements of T (dev_buf: the same in bytes, for padded or mixed buffers)
 //   grid_for(ctx, n, per_block, per_cu) ceil(n / per_block) workgroups, at least 1, at most per_cu per CU (the rest by grid stride)
 //   launch(ctx, name, kernel, grid, block, lds, args...)  the ONLY kernel launch of the library: on ctx->stream, timed as `name`
 //                                       (nullptr: not timed), hipGetLastError checked behind every launch
+//   check_mem(ctx, mem)                 the one "bad mem" refusal
+//   stage_to_device(ctx, name, p, count, mem, &d)   an input: a host array staged in workspace `name`, a device array as it is
+//   place_output(ctx, name, caller, count, mem, &d) / bring_output(ctx, caller, d, count, mem)   an output the kernels write in place:
+//                                       the caller's array on a device call; workspace `name`, copied down behind the kernels, on a
+//                                       host call (copy_out: a result produced in the workspace on both kinds of call)
+//   read_back(ctx, {{&host, device}, ...})   a few words for the host: the copies and ONE synchronisation, no return in between
+//                                       (caller_word: an element of a caller's input array, already here on a host call)
+//   zero_first_offset(ctx, out, mem)    the first offset of an empty result
+//   finish_call / finish_checked        the end of a call: synchronise and collect the kernel times, but leave a device call of an
+//                                       async_device context in flight; finish_sync: always synchronise; finish_synced: behind a
+//                                       read_back; refuse(ctx, code, fmt, ...): the error exit after work was enqueued
 // A launch that was never timed stays untimed (profile_get reads at most 32 names and tests read the set of names as route probes);
 // a timer that spans two kernels stays ONE KernelTimer scope around two launch(ctx, nullptr, ...).
 #pragma once
@@ -117,19 +128,70 @@ template <class T> inline int dev_array(kmu_ctx *ctx, const char *name, size_t c
     *out = static_cast<T *>(p);
     return KMU_OK;
 }
-// a host array of a KMU_MEM_HOST call staged in workspace `name`; a device array (or null) as it is
-inline int stage_to_device(kmu_ctx *ctx, const char *name, const void *p, size_t bytes, int mem, const void **out) {
+inline int check_mem(kmu_ctx *ctx, int mem) {
+    if (mem != KMU_MEM_HOST && mem != KMU_MEM_DEVICE) return fail(ctx, KMU_E_BAD_ARG, "bad mem %d", mem);
+    return KMU_OK;
+}
+// `count` elements of a host array of a KMU_MEM_HOST call staged in workspace `name` (of `count + pad` elements); a device array
+// (or null) as it is
+template <class T> inline int stage_to_device(kmu_ctx *ctx, const char *name, const T *p, size_t count, int mem, const T **out, size_t pad = 0) {
     if (mem == KMU_MEM_DEVICE || !p) { *out = p; return KMU_OK; }
-    void *d;
-    KMU_TRY(dev_buf(ctx, name, bytes ? bytes : 1, &d));
-    if (bytes) KMU_HIP(ctx, hipMemcpyAsync(d, p, bytes, hipMemcpyHostToDevice, ctx->stream));
+    T *d;
+    KMU_TRY(dev_array(ctx, name, count + pad ? count + pad : 1, &d));
+    if (count) KMU_HIP(ctx, hipMemcpyAsync(d, p, count * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
     *out = d;
+    return KMU_OK;
+}
+// (an array whose element type the call chooses at run time: in bytes)
+inline int stage_to_device(kmu_ctx *ctx, const char *name, const void *p, size_t bytes, int mem, const void **out, size_t pad = 0) {
+    return stage_to_device(ctx, name, static_cast<const uint8_t *>(p), bytes, mem, reinterpret_cast<const uint8_t **>(out), pad);
+}
+// where the kernels write a caller's output: the caller's array on a device call, workspace `name` of `count` elements on a host
+// call (an output the caller does not want, null, stays null)
+template <class T> inline int place_output(kmu_ctx *ctx, const char *name, T *caller, size_t count, int mem, T **out) {
+    if (mem == KMU_MEM_HOST && caller) return dev_array(ctx, name, count, out);
+    *out = caller;
+    return KMU_OK;
+}
+// ... and behind the kernels: a host call copies `count` elements of the workspace down, a device call has nothing to do
+template <class T> inline int bring_output(kmu_ctx *ctx, T *caller, const T *placed, size_t count, int mem) {
+    if (mem == KMU_MEM_HOST && caller && count) KMU_HIP(ctx, hipMemcpyAsync(caller, placed, count * sizeof(T), hipMemcpyDeviceToHost, ctx->stream));
     return KMU_OK;
 }
 // a device array of the workspace to a caller's array that lives where `mem` says
 inline int copy_out(kmu_ctx *ctx, void *dst, const void *src, size_t bytes, int mem) {
     if (!dst || !bytes) return KMU_OK;
     KMU_HIP(ctx, hipMemcpyAsync(dst, src, bytes, mem == KMU_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, ctx->stream));
+    return KMU_OK;
+}
+// a few words of device memory for the host (a null source: none): every copy on the stream, then ONE synchronisation.  The destinations are mostly stack
+// locals, so this does not return before the stream was synchronised, whatever a copy said.
+struct Word {
+    void *dst;
+    const void *src;
+    size_t bytes;
+    template <class T> Word(T *d, const T *s) : dst(d), src(s), bytes(sizeof(T)) {}
+    Word(void *d, const void *s, size_t n) : dst(d), src(s), bytes(n) {} // (a short array)
+};
+inline int read_back(kmu_ctx *ctx, std::initializer_list<Word> words) {
+    hipError_t e = hipSuccess;
+    for (const Word &w : words)
+        if (w.src && e == hipSuccess) e = hipMemcpyAsync(w.dst, w.src, w.bytes, hipMemcpyDeviceToHost, ctx->stream);
+    const hipError_t s = hipStreamSynchronize(ctx->stream);
+    KMU_HIP(ctx, e);
+    KMU_HIP(ctx, s);
+    return KMU_OK;
+}
+// one element of a caller's input array: already here on a host call, read back on a device call
+template <class T> inline int caller_word(kmu_ctx *ctx, const T *p, int mem, T *out) {
+    if (mem == KMU_MEM_HOST) { *out = *p; return KMU_OK; }
+    return read_back(ctx, {{out, p}});
+}
+// the first offset of an empty result, on either side of `mem`
+inline int zero_first_offset(kmu_ctx *ctx, uint64_t *offsets_out, int mem) {
+    if (!offsets_out) return KMU_OK;
+    if (mem == KMU_MEM_HOST) offsets_out[0] = 0;
+    else KMU_HIP(ctx, hipMemsetAsync(offsets_out, 0, 8, ctx->stream));
     return KMU_OK;
 }
 inline int host_buf(kmu_ctx *ctx, const char *name, size_t bytes, void **out) {
@@ -226,7 +288,24 @@ struct DevSeqs {
 int stage_sequences(kmu_ctx *ctx, const uint8_t *bases, const uint64_t *offsets, const uint64_t *packed_offsets,
                     uint32_t n_seq, int input_kind, int mem, DevSeqs *out);
 
+// the end of a call: synchronise and collect the kernel times, but leave a device call of an async_device context in flight
 int finish_call(kmu_ctx *ctx, int mem);
+// the end of a call whose contract is to synchronise in every context (its counts are on the host when it returns)
+inline int finish_sync(kmu_ctx *ctx) {
+    KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (ctx->profiling) profile_collect(ctx);
+    return KMU_OK;
+}
+// ... where the last operation of the call was a read_back: the stream is synchronised already
+inline int finish_synced(kmu_ctx *ctx) {
+    if (ctx->profiling) profile_collect(ctx);
+    return KMU_OK;
+}
+// a refusal after kernels were enqueued: their times are collected (profile_collect synchronises), then fail
+template <class... A> inline int refuse(kmu_ctx *ctx, int code, const char *fmt, A... args) {
+    (void) finish_synced(ctx);
+    return fail(ctx, code, fmt, args...);
+}
 
 // device error word (bit flags set by kernels)
 enum : uint32_t { DERR_NON_ACGT = 1u, DERR_TABLE_FULL = 2u, DERR_BAD_AA = 4u, DERR_EMPTY_SEQ = 8u, DERR_BAD_RANGE = 16u };

@@ -396,10 +396,7 @@ static int ingest_filter_copy(kmu_ctx *ctx, const uint8_t *d_text, uint64_t n_te
         KMU_TRY(launch(ctx, "k_ing_qual_check", k_ing_qual_check, dim3(grid_for(ctx, n_records, 256)), dim3(256), 0, (const uint64_t *) sstart,
                        (const uint64_t *) send, quals->qstart, quals->qend, n_records, (uint32_t *) scal + 8));
     uint64_t h_scal[8], n_kept = 0, kept_bases = 0;
-    KMU_HIP(ctx, hipMemcpyAsync(h_scal, scal, 64, hipMemcpyDeviceToHost, ctx->stream));
-    KMU_HIP(ctx, hipMemcpyAsync(&n_kept, rank + n_records, 8, hipMemcpyDeviceToHost, ctx->stream));
-    KMU_HIP(ctx, hipMemcpyAsync(&kept_bases, ooff + n_records, 8, hipMemcpyDeviceToHost, ctx->stream));
-    KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    KMU_TRY(read_back(ctx, {{h_scal, scal, sizeof h_scal}, {&n_kept, rank + n_records}, {&kept_bases, ooff + n_records}}));
     const uint32_t errw = (uint32_t) h_scal[4];
     if (errw & IERR_HEADER) return fail(ctx, KMU_E_BAD_ARG, "invalid record: a header line does not start with '@'");
     if (errw & IERR_SEPARATOR) return fail(ctx, KMU_E_BAD_ARG, "invalid record: a separator line does not start with '+'");
@@ -417,41 +414,29 @@ static int ingest_filter_copy(kmu_ctx *ctx, const uint8_t *d_text, uint64_t n_te
     if (bases_cap < kept_bases || offsets_cap < n_kept + 1 || (quals && quals->quals_cap < kept_bases))
         return fail(ctx, KMU_E_BAD_ARG, "output too small: need %llu bases%s and %llu offsets", (unsigned long long) kept_bases,
                     quals ? " (as many bytes in quals_out)" : "", (unsigned long long) (n_kept + 1));
-    uint8_t *d_bases = bases_out, *d_quals = quals_out;
-    uint64_t *d_off = offsets_out;
-    uint32_t *d_idx = record_index_out;
-    if (mem == KMU_MEM_HOST) {
-        void *q;
-        KMU_TRY(dev_buf(ctx, "ing.bases", kept_bases + 64, &q));
-        d_bases = (uint8_t *) q;
-        KMU_TRY(dev_array(ctx, "ing.off", n_kept + 1, &d_off));
-        if (record_index_out) KMU_TRY(dev_array(ctx, "ing.idx", n_kept + 1, &d_idx));
-        if (quals) KMU_TRY(dev_array(ctx, "ing.quals", kept_bases + 64, &d_quals));
-    }
+    uint8_t *d_bases, *d_quals;
+    uint64_t *d_off;
+    uint32_t *d_idx;
+    KMU_TRY(place_output(ctx, "ing.bases", bases_out, kept_bases + 64, mem, &d_bases));
+    KMU_TRY(place_output(ctx, "ing.off", offsets_out, n_kept + 1, mem, &d_off));
+    KMU_TRY(place_output(ctx, "ing.idx", record_index_out, n_kept + 1, mem, &d_idx));
+    KMU_TRY(place_output(ctx, "ing.quals", quals_out, kept_bases + 64, mem, &d_quals));
     KMU_TRY(launch(ctx, "k_ing_copy", k_ing_copy, dim3(grid_r), dim3(256), 0, d_text, (const uint64_t *) sstart, keep, klen, rank, ooff, n_records,
                    d_bases, d_off, d_idx));
     if (quals) KMU_TRY(launch(ctx, "k_ing_copy_qual", k_ing_copy_qual, dim3(grid_r), dim3(256), 0, d_text, quals->qstart, keep, klen, ooff, n_records, d_quals));
-    if (mem == KMU_MEM_HOST) {
-        if (quals) KMU_HIP(ctx, hipMemcpyAsync(quals_out, d_quals, kept_bases, hipMemcpyDeviceToHost, ctx->stream));
-        KMU_HIP(ctx, hipMemcpyAsync(bases_out, d_bases, kept_bases, hipMemcpyDeviceToHost, ctx->stream));
-        KMU_HIP(ctx, hipMemcpyAsync(offsets_out, d_off, (n_kept + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
-        if (record_index_out)
-            KMU_HIP(ctx, hipMemcpyAsync(record_index_out, d_idx, n_kept * 4, hipMemcpyDeviceToHost, ctx->stream));
-    }
+    KMU_TRY(bring_output(ctx, quals_out, d_quals, kept_bases, mem));
+    KMU_TRY(bring_output(ctx, bases_out, d_bases, kept_bases, mem));
+    KMU_TRY(bring_output(ctx, offsets_out, d_off, n_kept + 1, mem));
+    KMU_TRY(bring_output(ctx, record_index_out, d_idx, n_kept, mem));
     return finish_call(ctx, mem);
 }
 
 // text to the device (host mode), newline census and its scan; *n_lines_out = lines of the text
 static int ingest_lines(kmu_ctx *ctx, const uint8_t *text, uint64_t n_bytes, int mem, const uint8_t **d_text_out, void **lbase_out,
                         void **scal_out, uint64_t *n_regions_out, int *grid_out, uint64_t *n_lines_out) {
-    const uint8_t *d_text = text;
+    const uint8_t *d_text;
     if (mem == KMU_MEM_DEVICE && ((uintptr_t) text & 15u) != 0) return fail(ctx, KMU_E_BAD_ARG, "device `text` must be 16-byte aligned");
-    if (mem == KMU_MEM_HOST) {
-        void *q;
-        KMU_TRY(dev_buf(ctx, "ing.text", n_bytes + 64, &q));
-        KMU_HIP(ctx, hipMemcpyAsync(q, text, n_bytes, hipMemcpyHostToDevice, ctx->stream));
-        d_text = (const uint8_t *) q;
-    }
+    KMU_TRY(stage_to_device(ctx, "ing.text", text, n_bytes, mem, &d_text, 64));
     const uint64_t n_regions = (n_bytes + ING_REGION - 1) / ING_REGION;
     uint64_t *lbase;
     uint32_t *cnt;
@@ -465,9 +450,7 @@ static int ingest_lines(kmu_ctx *ctx, const uint8_t *text, uint64_t n_bytes, int
     KMU_TRY(device_scan(ctx, cnt, n_regions, lbase));
     uint64_t total_nl = 0;
     uint8_t last = 0;
-    KMU_HIP(ctx, hipMemcpyAsync(&total_nl, lbase + n_regions, 8, hipMemcpyDeviceToHost, ctx->stream));
-    KMU_HIP(ctx, hipMemcpyAsync(&last, d_text + n_bytes - 1, 1, hipMemcpyDeviceToHost, ctx->stream));
-    KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    KMU_TRY(read_back(ctx, {{&total_nl, lbase + n_regions}, {&last, d_text + n_bytes - 1}}));
     *d_text_out = d_text;
     *lbase_out = lbase;
     *scal_out = scal;
@@ -563,10 +546,7 @@ extern "C" int kmu_ingest_fasta(kmu_ctx *ctx, const uint8_t *text, uint64_t n_by
     KMU_TRY(device_scan(ctx, slen, n_lines, spos));
     uint64_t n_records = 0, n_stream = 0;
     uint32_t first_hdr = 0;
-    KMU_HIP(ctx, hipMemcpyAsync(&n_records, hrank + n_lines, 8, hipMemcpyDeviceToHost, ctx->stream));
-    KMU_HIP(ctx, hipMemcpyAsync(&n_stream, spos + n_lines, 8, hipMemcpyDeviceToHost, ctx->stream));
-    KMU_HIP(ctx, hipMemcpyAsync(&first_hdr, hdr, 4, hipMemcpyDeviceToHost, ctx->stream));
-    KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    KMU_TRY(read_back(ctx, {{&n_records, hrank + n_lines}, {&n_stream, spos + n_lines}, {&first_hdr, hdr}}));
     if (!first_hdr) return fail(ctx, KMU_E_BAD_ARG, "invalid record: a FASTA text starts with '>'");
     if (n_records > 0xFFFFFFFFull) return fail(ctx, KMU_E_UNSUPPORTED, "more than 2^32 records in one call");
     uint64_t *send, *sstart;
@@ -591,12 +571,8 @@ extern "C" int kmu_ingest_fastx(kmu_ctx *ctx, const uint8_t *text, uint64_t n_by
     if (!ctx || !info || (n_bytes && !text)) return fail(ctx, KMU_E_BAD_ARG, "null argument");
     uint8_t first = '@';
     if (n_bytes) {
-        if (mem == KMU_MEM_HOST) first = text[0];
-        else {
-            KMU_HIP(ctx, hipSetDevice(ctx->device));
-            KMU_HIP(ctx, hipMemcpyAsync(&first, text, 1, hipMemcpyDeviceToHost, ctx->stream));
-            KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        }
+        if (mem == KMU_MEM_DEVICE) KMU_HIP(ctx, hipSetDevice(ctx->device));
+        KMU_TRY(caller_word(ctx, text, mem, &first));
     }
     if (first == '>') return kmu_ingest_fasta(ctx, text, n_bytes, mem, bases_out, bases_cap, offsets_out, offsets_cap, record_index_out, info);
     if (first == '@') return kmu_ingest_fastq(ctx, text, n_bytes, mem, bases_out, bases_cap, offsets_out, offsets_cap, record_index_out, info);

@@ -311,9 +311,9 @@ int kmu_kfilter_add_kmers(kmu_kfilter *f, const uint64_t *canon_kmers, uint64_t 
     kmu_ctx *ctx = f->ctx;
     KMU_HIP(ctx, hipSetDevice(ctx->device));
     if (n == 0) return KMU_OK;
-    const void *d_k;
-    KMU_TRY(stage_to_device(ctx, "kf.in.k", canon_kmers, n * 8, mem, &d_k));
-    KMU_TRY(launch(ctx, "k_kf_add_kmers", k_kf_add_kmers, dim3(grid_for(ctx, n, 256)), dim3(256), 0, (const uint64_t *) d_k, n, view_of(f), f->scalars));
+    const uint64_t *d_k;
+    KMU_TRY(stage_to_device(ctx, "kf.in.k", canon_kmers, n, mem, &d_k));
+    KMU_TRY(launch(ctx, "k_kf_add_kmers", k_kf_add_kmers, dim3(grid_for(ctx, n, 256)), dim3(256), 0, d_k, n, view_of(f), f->scalars));
     return finish_call(ctx, mem);
 }
 
@@ -322,12 +322,12 @@ int kmu_kfilter_query(kmu_kfilter *f, const uint64_t *canon_kmers, uint64_t n, i
     kmu_ctx *ctx = f->ctx;
     KMU_HIP(ctx, hipSetDevice(ctx->device));
     if (n == 0) return KMU_OK;
-    const void *d_k;
-    KMU_TRY(stage_to_device(ctx, "kf.in.k", canon_kmers, n * 8, mem, &d_k));
-    uint8_t *d_o = class_out;
-    if (mem == KMU_MEM_HOST) KMU_TRY(dev_array(ctx, "kf.out.c", n + 16, &d_o));
-    KMU_TRY(launch(ctx, "k_kf_query", k_kf_query, dim3(grid_for(ctx, n, 256)), dim3(256), 0, (const uint64_t *) d_k, n, view_of(f), d_o));
-    if (mem == KMU_MEM_HOST) KMU_HIP(ctx, hipMemcpyAsync(class_out, d_o, n, hipMemcpyDeviceToHost, ctx->stream));
+    const uint64_t *d_k;
+    KMU_TRY(stage_to_device(ctx, "kf.in.k", canon_kmers, n, mem, &d_k));
+    uint8_t *d_o;
+    KMU_TRY(place_output(ctx, "kf.out.c", class_out, n + 16, mem, &d_o));
+    KMU_TRY(launch(ctx, "k_kf_query", k_kf_query, dim3(grid_for(ctx, n, 256)), dim3(256), 0, d_k, n, view_of(f), d_o));
+    KMU_TRY(bring_output(ctx, class_out, d_o, n, mem));
     return finish_call(ctx, mem);
 }
 
@@ -338,8 +338,7 @@ int kmu_kfilter_info(kmu_kfilter *f, kmu_kfilter_info_t *out) {
     KMU_HIP(ctx, hipMemsetAsync(f->scalars + 1, 0, 16, ctx->stream));
     KMU_TRY(launch(ctx, "k_kf_popcount", k_kf_popcount, dim3(grid_for(ctx, f->p.n_cells, 1024)), dim3(256), 0, f->cells, f->p.n_cells, f->scalars));
     uint64_t h[3];
-    KMU_HIP(ctx, hipMemcpyAsync(h, f->scalars, 24, hipMemcpyDeviceToHost, ctx->stream));
-    KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    KMU_TRY(read_back(ctx, {{h, f->scalars, sizeof h}}));
     out->n_cells = f->p.n_cells;
     out->bytes = f->p.n_cells * 16;
     out->n_hashes = f->p.n_hashes;
@@ -389,17 +388,18 @@ int kmu_kfilter_select_reads(kmu_kfilter *f, const uint8_t *bases, const uint64_
     int grid;
     KMU_TRY(kf_pass_scan(f, r, d_err, &base, &nsteps, &grid));
     uint64_t n = 0;
+    // (not read_back: the copy of the error word goes between this copy and the one synchronisation, check_err_word's)
     KMU_HIP(ctx, hipMemcpyAsync(&n, base + nsteps, 8, hipMemcpyDeviceToHost, ctx->stream));
-    KMU_TRY(check_err_word(ctx, d_err)); // (the one synchronisation: the total and what the walk found)
+    KMU_TRY(check_err_word(ctx, d_err));
     *n_out = n;
     if (!kmers_out) return KMU_OK; // size query
     if (cap < n) return fail(ctx, KMU_E_BAD_ARG, "output too small: %llu k-mers", (unsigned long long) n);
     if (n == 0) return KMU_OK;
-    uint64_t *d_k = kmers_out;
-    if (mem == KMU_MEM_HOST) KMU_TRY(dev_array(ctx, "kf.ws", n + 8, &d_k));
+    uint64_t *d_k;
+    KMU_TRY(place_output(ctx, "kf.ws", kmers_out, n + 8, mem, &d_k));
     KMU_TRY(launch(ctx, "k_kf_pass_emit", k_kf_pass_emit, dim3(grid), dim3(256), 0, r.ds.bases, r.ds.offsets, n_seq, f->p.kmer_size, view_of(f),
                    (const uint64_t *) base, (uint64_t) 0, nsteps, d_k));
-    if (mem == KMU_MEM_HOST) KMU_HIP(ctx, hipMemcpyAsync(kmers_out, d_k, n * 8, hipMemcpyDeviceToHost, ctx->stream));
+    KMU_TRY(bring_output(ctx, kmers_out, d_k, n, mem));
     return finish_call(ctx, mem);
 }
 

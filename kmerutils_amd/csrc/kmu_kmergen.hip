@@ -412,20 +412,15 @@ extern "C" int kmu_nthash(kmu_ctx *ctx, const kmu_nthash_params *p, const uint8_
     KMU_HIP(ctx, hipSetDevice(ctx->device));
     DevSeqs ds;
     KMU_TRY(stage_sequences(ctx, bases, offsets, packed_offsets, n_seq, p->input_kind, p->mem, &ds));
-    uint64_t *d_out = hashes_out;
-    uint8_t *d_strand = strand_out;
-    uint64_t total = 0;
+    uint64_t *d_out;
+    uint8_t *d_strand;
     const uint64_t off0 = p->mem == KMU_MEM_HOST && n_seq ? offsets[0] : 0;
+    const uint64_t total = p->mem == KMU_MEM_HOST && n_seq ? offsets[n_seq] - off0 : 0; // (host arrays come back whole)
+    KMU_TRY(place_output(ctx, "out.u64", hashes_out, (size_t) total * p->n_hashes + 1, p->mem, &d_out));
+    KMU_TRY(place_output(ctx, "out.u8", strand_out, (size_t) total + 8, p->mem, &d_strand));
     if (p->mem == KMU_MEM_HOST) {
-        total = n_seq ? offsets[n_seq] - off0 : 0;
-        void *q;
-        KMU_TRY(dev_array(ctx, "out.u64", (size_t) total * p->n_hashes + 1, &d_out));
         KMU_HIP(ctx, hipMemsetAsync(d_out, 0, (size_t) total * 8 * p->n_hashes, ctx->stream));
-        if (strand_out) {
-            KMU_TRY(dev_buf(ctx, "out.u8", (size_t) total + 8, &q));
-            d_strand = (uint8_t *) q;
-            KMU_HIP(ctx, hipMemsetAsync(d_strand, 0, (size_t) total, ctx->stream));
-        }
+        if (strand_out) KMU_HIP(ctx, hipMemsetAsync(d_strand, 0, (size_t) total, ctx->stream));
     }
     uint32_t *d_err;
     KMU_TRY(get_err_word(ctx, &d_err));
@@ -434,8 +429,7 @@ extern "C" int kmu_nthash(kmu_ctx *ctx, const kmu_nthash_params *p, const uint8_
                  d_out, d_strand, d_err, nullptr};
         if (!ds.packed) { // the positions that start no k-mer, once per call (the end of the stream as the kernel sees it: offsets[n_seq])
             uint64_t end = 0;
-            KMU_HIP(ctx, hipMemcpyAsync(&end, ds.offsets + n_seq, 8, hipMemcpyDeviceToHost, ctx->stream));
-            KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
+            KMU_TRY(read_back(ctx, {{&end, ds.offsets + n_seq}}));
             void *nvp;
             KMU_TRY(flat_novalid(ctx, ds, end, p->kmer_size, (end + 15) / 16 + 128, "nt.novalid", &nvp));
             a.novalid = (const uint16_t *) nvp;
@@ -450,10 +444,8 @@ extern "C" int kmu_nthash(kmu_ctx *ctx, const kmu_nthash_params *p, const uint8_
             KMU_TRY(launch(ctx, "k_nthash", k_nthash<false>, dim3(grid), dim3(256), 0, a));
         }
     }
-    if (p->mem == KMU_MEM_HOST) {
-        KMU_HIP(ctx, hipMemcpyAsync(hashes_out + off0 * p->n_hashes, d_out, (size_t) total * 8 * p->n_hashes, hipMemcpyDeviceToHost, ctx->stream));
-        if (strand_out) KMU_HIP(ctx, hipMemcpyAsync(strand_out + off0, d_strand, (size_t) total, hipMemcpyDeviceToHost, ctx->stream));
-    }
+    KMU_TRY(bring_output(ctx, hashes_out + off0 * p->n_hashes, d_out, (size_t) total * p->n_hashes, p->mem));
+    if (strand_out) KMU_TRY(bring_output(ctx, strand_out + off0, d_strand, (size_t) total, p->mem));
     return finish_checked(ctx, p->mem, d_err);
 }
 
@@ -491,8 +483,7 @@ extern "C" int kmu_kmer_distribution(kmu_ctx *ctx, const kmu_hash_params *p, con
     KMU_TRY(launch(ctx, nullptr, k_dist_plan, dim3(grid_s), dim3(256), 0, koff, n_seq, passes));
     KMU_TRY(device_scan_u32(ctx, passes, n_seq, item_off));
     uint64_t n_items = 0;
-    KMU_HIP(ctx, hipMemcpyAsync(&n_items, item_off + n_seq, 8, hipMemcpyDeviceToHost, ctx->stream));
-    KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    KMU_TRY(read_back(ctx, {{&n_items, item_off + n_seq}}));
     if (n_items) {
         const int grid = (int) std::min<uint64_t>(n_items, (uint64_t) ctx->num_cus * 3);
         KMU_TRY(launch(ctx, "k_kmer_dist", k_kmer_dist, dim3(grid), dim3(DIST_THREADS), 0, vals, koff, item_off, n_seq, n_items, tk, tc, nd,
@@ -500,8 +491,9 @@ extern "C" int kmu_kmer_distribution(kmu_ctx *ctx, const kmu_hash_params *p, con
     }
     KMU_TRY(device_scan_u32(ctx, nd, n_seq, doff));
     uint64_t n_pairs = 0;
+    // (not read_back: the copy of the error word goes between this copy and the one synchronisation, check_err_word's)
     KMU_HIP(ctx, hipMemcpyAsync(&n_pairs, doff + n_seq, 8, hipMemcpyDeviceToHost, ctx->stream));
-    KMU_TRY(check_err_word(ctx, d_err)); // (synchronises)
+    KMU_TRY(check_err_word(ctx, d_err));
     *n_out = n_pairs;
     if (dist_offsets_out) {
         if (p->mem == KMU_MEM_HOST) KMU_HIP(ctx, hipMemcpy(dist_offsets_out, doff, ((size_t) n_seq + 1) * 8, hipMemcpyDeviceToHost));
@@ -509,19 +501,15 @@ extern "C" int kmu_kmer_distribution(kmu_ctx *ctx, const kmu_hash_params *p, con
     }
     if (!kmers_out) return finish_call(ctx, p->mem); // sizes only
     if (cap < n_pairs) return fail(ctx, KMU_E_BAD_ARG, "output too small: %llu pairs", (unsigned long long) n_pairs);
-    uint64_t *d_k = kmers_out;
-    uint32_t *d_c = mult_out;
-    if (p->mem == KMU_MEM_HOST) {
-        KMU_TRY(dev_array(ctx, "dist.out_k", n_pairs + 8, &d_k));
-        KMU_TRY(dev_array(ctx, "dist.out_c", n_pairs + 16, &d_c));
-    }
+    uint64_t *d_k;
+    uint32_t *d_c;
+    KMU_TRY(place_output(ctx, "dist.out_k", kmers_out, n_pairs + 8, p->mem, &d_k));
+    KMU_TRY(place_output(ctx, "dist.out_c", mult_out, n_pairs + 16, p->mem, &d_c));
     if (n_pairs) {
         const int grid = grid_for(ctx, n_seq, 1);
         KMU_TRY(launch(ctx, nullptr, k_dist_compact, dim3(grid), dim3(256), 0, tk, tc, koff, doff, n_seq, d_k, d_c));
     }
-    if (p->mem == KMU_MEM_HOST) {
-        KMU_HIP(ctx, hipMemcpyAsync(kmers_out, d_k, n_pairs * 8, hipMemcpyDeviceToHost, ctx->stream));
-        KMU_HIP(ctx, hipMemcpyAsync(mult_out, d_c, n_pairs * 4, hipMemcpyDeviceToHost, ctx->stream));
-    }
+    KMU_TRY(bring_output(ctx, kmers_out, d_k, n_pairs, p->mem));
+    KMU_TRY(bring_output(ctx, mult_out, d_c, n_pairs, p->mem));
     return finish_call(ctx, p->mem);
 }

@@ -205,24 +205,23 @@ extern "C" int kmu_sig_knn(kmu_ctx *ctx, const void *sig_q, uint32_t nq, const v
     KMU_HIP(ctx, hipSetDevice(ctx->device));
     if (nq == 0) return KMU_OK;
     const int wb = (sig_type == KMU_SIG_U32 || sig_type == KMU_SIG_F32) ? 4 : 8;
-    uint32_t *didx = idx_out;
-    uint16_t *deq = eq_out;
+    uint32_t *didx;
+    uint16_t *deq;
     const size_t n_out = (size_t) nq * k;
-    if (mem == KMU_MEM_HOST) {
-        KMU_TRY(dev_array(ctx, "knn.idx", n_out, &didx));
-        KMU_TRY(dev_array(ctx, "knn.eq", n_out, &deq));
-    }
+    KMU_TRY(place_output(ctx, "knn.idx", idx_out, n_out, mem, &didx));
+    KMU_TRY(place_output(ctx, "knn.eq", eq_out, n_out, mem, &deq));
     if (ndb == 0) { // every list is "none"
         KMU_HIP(ctx, hipMemsetAsync(didx, 0xFF, n_out * 4, ctx->stream));
         KMU_HIP(ctx, hipMemsetAsync(deq, 0, n_out * 2, ctx->stream));
     } else {
-        const void *dq, *ddb, *dgq = nullptr, *dgdb = nullptr;
+        const void *dq, *ddb;
+        const uint32_t *dgq = nullptr, *dgdb = nullptr;
         KMU_TRY(stage_to_device(ctx, "knn.q", sig_q, (size_t) nq * m * wb, mem, &dq));
         if (sig_db == sig_q && ndb == nq) ddb = dq; // a self-join is staged once
         else KMU_TRY(stage_to_device(ctx, "knn.db", sig_db, (size_t) ndb * m * wb, mem, &ddb));
         if (group_q) {
-            KMU_TRY(stage_to_device(ctx, "knn.gq", group_q, (size_t) nq * 4, mem, &dgq));
-            KMU_TRY(stage_to_device(ctx, "knn.gdb", group_db, (size_t) ndb * 4, mem, &dgdb));
+            KMU_TRY(stage_to_device(ctx, "knn.gq", group_q, (size_t) nq, mem, &dgq));
+            KMU_TRY(stage_to_device(ctx, "knn.gdb", group_db, (size_t) ndb, mem, &dgdb));
         }
         // database segments: enough workgroups for every CU a few times over, no more (each segment costs a partial list
         // per query row).  KMU_KNN_SEG_ROWS fixes the segment height (tests: several segments on a small database).
@@ -247,7 +246,7 @@ extern "C" int kmu_sig_knn(kmu_ctx *ctx, const void *sig_q, uint32_t nq, const v
             const uint32_t rows = (uint32_t) std::min<uint64_t>(slab, nq - s0);
             const dim3 grid((rows + KT - 1) / KT, nseg);
             const size_t dyn = (size_t) KT * k * 8;
-            const uint32_t *gqs = dgq ? (const uint32_t *) dgq + s0 : nullptr;
+            const uint32_t *gqs = dgq ? dgq + s0 : nullptr;
             if (wb == 4)
                 KMU_TRY(launch(ctx, "k_sig_knn", k_sig_knn<uint32_t>, grid, dim3(256), dyn, (const uint32_t *) dq + s0 * m, rows, ddb, ndb, m, k,
                                (uint32_t) seg_rows, gqs, dgdb, dpart));
@@ -258,9 +257,7 @@ extern "C" int kmu_sig_knn(kmu_ctx *ctx, const void *sig_q, uint32_t nq, const v
                            deq + s0 * k));
         }
     }
-    if (mem == KMU_MEM_HOST) {
-        KMU_HIP(ctx, hipMemcpyAsync(idx_out, didx, n_out * 4, hipMemcpyDeviceToHost, ctx->stream));
-        KMU_HIP(ctx, hipMemcpyAsync(eq_out, deq, n_out * 2, hipMemcpyDeviceToHost, ctx->stream));
-    }
+    KMU_TRY(bring_output(ctx, idx_out, didx, n_out, mem));
+    KMU_TRY(bring_output(ctx, eq_out, deq, n_out, mem));
     return finish_call(ctx, mem);
 }

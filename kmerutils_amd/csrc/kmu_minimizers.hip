@@ -200,7 +200,7 @@ extern "C" int kmu_read_minimizers(kmu_ctx *ctx, const kmu_hash_params *p, const
     if (w == 0) return fail(ctx, KMU_E_BAD_ARG, "minimizers need a window of w >= 1 k-mers");
     if (w > KMU_MINIMIZER_MAX_W) return fail(ctx, KMU_E_UNSUPPORTED, "w = %u above KMU_MINIMIZER_MAX_W (%d)", w, KMU_MINIMIZER_MAX_W);
     const int mem = p->mem;
-    if (mem != KMU_MEM_HOST && mem != KMU_MEM_DEVICE) return fail(ctx, KMU_E_BAD_ARG, "bad mem %d", mem);
+    KMU_TRY(check_mem(ctx, mem));
     if (kmer_is_aa(p->kmer_type)) return fail(ctx, KMU_E_BAD_ALPHABET, "minimizers are defined on DNA k-mers");
     if (p->input_kind == KMU_INPUT_PACKED2) return fail(ctx, KMU_E_UNSUPPORTED, "minimizers take unpacked (ASCII) bases");
     KMU_TRY(check_hash_params(ctx, p));
@@ -208,8 +208,7 @@ extern "C" int kmu_read_minimizers(kmu_ctx *ctx, const kmu_hash_params *p, const
         return fail(ctx, KMU_E_UNSUPPORTED, "the canonical ntHash does not expose its strand: pass strand_out = NULL");
     KMU_HIP(ctx, hipSetDevice(ctx->device));
     if (n_seq == 0) {
-        if (mini_offsets_out && mem == KMU_MEM_HOST) mini_offsets_out[0] = 0;
-        if (mini_offsets_out && mem == KMU_MEM_DEVICE) KMU_HIP(ctx, hipMemsetAsync(mini_offsets_out, 0, 8, ctx->stream));
+        KMU_TRY(zero_first_offset(ctx, mini_offsets_out, mem));
         return finish_call(ctx, mem);
     }
     if (!offsets || !bases) return fail(ctx, KMU_E_BAD_ARG, "null sequence buffers");
@@ -256,20 +255,17 @@ extern "C" int kmu_read_minimizers(kmu_ctx *ctx, const kmu_hash_params *p, const
         const uint32_t grid = (uint32_t) std::min<uint64_t>(room, (uint64_t) ctx->num_cus * 40);
         KMU_TRY(launch(ctx, "k_read_minimizers_count", k_read_minimizers<false>, dim3(grid), dim3(64), 0, a));
         KMU_TRY(device_scan_u32(ctx, a.counts, room, coff));
-        KMU_HIP(ctx, hipMemcpyAsync(&head[0], tile_off + n_seq, 8, hipMemcpyDeviceToHost, ctx->stream));
-        KMU_HIP(ctx, hipMemcpyAsync(&head[1], coff + room, 8, hipMemcpyDeviceToHost, ctx->stream));
-        KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        KMU_TRY(read_back(ctx, {{&head[0], tile_off + n_seq}, {&head[1], coff + room}}));
         if (head[0] <= room) break;
         room = head[0]; // (device arrays, more tiles than the workspace had room for)
     }
     const uint64_t n_tiles = head[0], total = head[1];
     *n_out = total;
-    uint64_t *d_moff = mini_offsets_out;
+    uint64_t *d_moff;
+    KMU_TRY(place_output(ctx, "mini.moff", mini_offsets_out, (size_t) n_seq + 1, mem, &d_moff));
     if (mini_offsets_out) {
-        if (mem == KMU_MEM_HOST) KMU_TRY(dev_array(ctx, "mini.moff", (size_t) n_seq + 1, &d_moff));
         KMU_TRY(launch(ctx, nullptr, k_mini_offsets, dim3(grid_for(ctx, (uint64_t) n_seq + 1, 256)), dim3(256), 0, tile_off, coff, n_seq, d_moff));
-        if (mem == KMU_MEM_HOST)
-            KMU_HIP(ctx, hipMemcpyAsync(mini_offsets_out, d_moff, ((size_t) n_seq + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
+        KMU_TRY(bring_output(ctx, mini_offsets_out, d_moff, (size_t) n_seq + 1, mem));
     }
     if (!hashes_out || total == 0) return finish_checked(ctx, mem, a.err);
     if (cap < total) {
@@ -280,23 +276,15 @@ extern "C" int kmu_read_minimizers(kmu_ctx *ctx, const kmu_hash_params *p, const
     // WRITE
     a.room = n_tiles;
     a.coff = coff;
-    a.hashes = hashes_out;
-    a.pos = pos_out;
-    a.read = read_out;
-    a.strand = strand_out;
-    if (mem == KMU_MEM_HOST) {
-        KMU_TRY(dev_array(ctx, "mini.hashes", (size_t) total, &a.hashes));
-        if (pos_out) KMU_TRY(dev_array(ctx, "mini.pos", (size_t) total, &a.pos));
-        if (read_out) KMU_TRY(dev_array(ctx, "mini.read", (size_t) total, &a.read));
-        if (strand_out) KMU_TRY(dev_array(ctx, "mini.strand", (size_t) total, &a.strand));
-    }
+    KMU_TRY(place_output(ctx, "mini.hashes", hashes_out, (size_t) total, mem, &a.hashes));
+    KMU_TRY(place_output(ctx, "mini.pos", pos_out, (size_t) total, mem, &a.pos));
+    KMU_TRY(place_output(ctx, "mini.read", read_out, (size_t) total, mem, &a.read));
+    KMU_TRY(place_output(ctx, "mini.strand", strand_out, (size_t) total, mem, &a.strand));
     const uint32_t grid = (uint32_t) std::min<uint64_t>(n_tiles, (uint64_t) ctx->num_cus * 40);
     KMU_TRY(launch(ctx, "k_read_minimizers_write", k_read_minimizers<true>, dim3(grid), dim3(64), 0, a));
-    if (mem == KMU_MEM_HOST) {
-        KMU_HIP(ctx, hipMemcpyAsync(hashes_out, a.hashes, total * 8, hipMemcpyDeviceToHost, ctx->stream));
-        if (pos_out) KMU_HIP(ctx, hipMemcpyAsync(pos_out, a.pos, total * 4, hipMemcpyDeviceToHost, ctx->stream));
-        if (read_out) KMU_HIP(ctx, hipMemcpyAsync(read_out, a.read, total * 4, hipMemcpyDeviceToHost, ctx->stream));
-        if (strand_out) KMU_HIP(ctx, hipMemcpyAsync(strand_out, a.strand, total, hipMemcpyDeviceToHost, ctx->stream));
-    }
+    KMU_TRY(bring_output(ctx, hashes_out, a.hashes, (size_t) total, mem));
+    KMU_TRY(bring_output(ctx, pos_out, a.pos, (size_t) total, mem));
+    KMU_TRY(bring_output(ctx, read_out, a.read, (size_t) total, mem));
+    KMU_TRY(bring_output(ctx, strand_out, a.strand, (size_t) total, mem));
     return finish_checked(ctx, mem, a.err);
 }

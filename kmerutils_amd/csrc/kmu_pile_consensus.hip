@@ -110,26 +110,15 @@ static int cons_plan(kmu_ctx *ctx, const uint32_t *pile, const uint8_t *call, co
     KMU_HIP(ctx, hipSetDevice(ctx->device));
     ConsArgs a{};
     uint64_t n_rows = 0;
-    if (mem == KMU_MEM_HOST) n_rows = offsets[n_reads];
-    else {
-        KMU_HIP(ctx, hipMemcpyAsync(&n_rows, offsets + n_reads, 8, hipMemcpyDeviceToHost, ctx->stream));
-        KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    }
+    KMU_TRY(caller_word(ctx, offsets + n_reads, mem, &n_rows));
 
-    const void *d;
-    KMU_TRY(stage_to_device(ctx, "cons.pile", pile, (size_t) n_rows * PILE_COLS * 4, mem, &d));
-    a.pile = (const uint32_t *) d;
-    KMU_TRY(stage_to_device(ctx, "cons.call", call, (size_t) n_rows, mem, &d));
-    a.call = (const uint8_t *) d;
-    KMU_TRY(stage_to_device(ctx, "cons.len", ins_len, (size_t) n_rows, mem, &d));
-    a.ins_len = (const uint8_t *) d;
-    KMU_TRY(stage_to_device(ctx, "cons.ins", ins, (size_t) n_slots * CONS_LETTERS * 4, mem, &d));
-    a.ins = (const uint32_t *) d;
+    KMU_TRY(stage_to_device(ctx, "cons.pile", pile, (size_t) n_rows * PILE_COLS, mem, &a.pile));
+    KMU_TRY(stage_to_device(ctx, "cons.call", call, (size_t) n_rows, mem, &a.call));
+    KMU_TRY(stage_to_device(ctx, "cons.len", ins_len, (size_t) n_rows, mem, &a.ins_len));
+    KMU_TRY(stage_to_device(ctx, "cons.ins", ins, (size_t) n_slots * CONS_LETTERS, mem, &a.ins));
     a.n_slots = n_slots;
-    KMU_TRY(stage_to_device(ctx, "cons.bases", bases, (size_t) n_rows, mem, &d));
-    a.bases = (const uint8_t *) d;
-    KMU_TRY(stage_to_device(ctx, "cons.off", offsets, ((size_t) n_reads + 1) * 8, mem, &d));
-    a.off = (const uint64_t *) d;
+    KMU_TRY(stage_to_device(ctx, "cons.bases", bases, (size_t) n_rows, mem, &a.bases));
+    KMU_TRY(stage_to_device(ctx, "cons.off", offsets, (size_t) n_reads + 1, mem, &a.off));
     a.n_reads = n_reads;
     a.n_rows = n_rows;
     a.n_tiles = cons_n_blocks(n_rows);
@@ -138,12 +127,9 @@ static int cons_plan(kmu_ctx *ctx, const uint32_t *pile, const uint8_t *call, co
     uint64_t *slot_off, total_slots = 0;
     KMU_TRY(ins_block_offsets(ctx, "cons.slotoff", a.ins_len, n_rows, &slot_off));
     a.slot_off = slot_off;
-    KMU_HIP(ctx, hipMemcpyAsync(&total_slots, slot_off + a.n_tiles, 8, hipMemcpyDeviceToHost, ctx->stream));
-    KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (total_slots != n_slots) {
-        if (ctx->profiling) profile_collect(ctx);
-        return fail(ctx, KMU_E_UNSUPPORTED, "ins_len sums to %llu slots, not to n_slots = %llu", (unsigned long long) total_slots, (unsigned long long) n_slots);
-    }
+    KMU_TRY(read_back(ctx, {{&total_slots, slot_off + a.n_tiles}}));
+    if (total_slots != n_slots)
+        return refuse(ctx, KMU_E_UNSUPPORTED, "ins_len sums to %llu slots, not to n_slots = %llu", (unsigned long long) total_slots, (unsigned long long) n_slots);
 
     uint64_t *tile_off;
     KMU_TRY(dev_array(ctx, "cons.tilelen", a.n_tiles ? a.n_tiles : 1, &a.tile_len));
@@ -167,34 +153,26 @@ extern "C" int kmu_pile_consensus(kmu_ctx *ctx, const uint32_t *pile, const uint
     if (!ctx || !pile || !call || !ins_len || !bases || !offsets || !p || !cons_offsets_out || !n_cons_out) return fail(ctx, KMU_E_BAD_ARG, "null argument");
     if (!ins && n_slots) return fail(ctx, KMU_E_BAD_ARG, "ins is null with n_slots = %llu", (unsigned long long) n_slots);
     if (p->flags) return fail(ctx, KMU_E_BAD_ARG, "unknown flag bits 0x%x", p->flags);
-    if (mem != KMU_MEM_HOST && mem != KMU_MEM_DEVICE) return fail(ctx, KMU_E_BAD_ARG, "bad mem %d", mem);
+    KMU_TRY(check_mem(ctx, mem));
     *n_cons_out = 0;
     ConsArgs a{};
     uint64_t *tile_off, total = 0;
     KMU_TRY(cons_plan(ctx, pile, call, ins_len, n_slots, ins, bases, offsets, n_reads, mem, &a, &tile_off));
     const dim3 grid(grid_for(ctx, a.n_tiles, 4));
-    a.cons_off = cons_offsets_out;
-    if (mem == KMU_MEM_HOST) KMU_TRY(dev_array(ctx, "cons.consoff", (size_t) n_reads + 1, &a.cons_off));
+    KMU_TRY(place_output(ctx, "cons.consoff", cons_offsets_out, (size_t) n_reads + 1, mem, &a.cons_off));
     KMU_TRY(launch(ctx, "k_cons_offsets", k_cons_offsets, dim3(grid_for(ctx, (uint64_t) n_reads + 1, 256)), dim3(256), 0, a));
-    if (mem == KMU_MEM_HOST)
-        KMU_HIP(ctx, hipMemcpyAsync(cons_offsets_out, a.cons_off, ((size_t) n_reads + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
-    // (into a local: nothing may return between this copy and the synchronisation)
-    KMU_HIP(ctx, hipMemcpyAsync(&total, tile_off + a.n_tiles, 8, hipMemcpyDeviceToHost, ctx->stream));
-    KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    KMU_TRY(bring_output(ctx, cons_offsets_out, a.cons_off, (size_t) n_reads + 1, mem));
+    KMU_TRY(read_back(ctx, {{&total, tile_off + a.n_tiles}}));
     *n_cons_out = total;
-    if (cons_out && cap < total) {
-        if (ctx->profiling) profile_collect(ctx);
-        return fail(ctx, KMU_E_BAD_ARG, "cap = %llu is below the %llu bytes", (unsigned long long) cap, (unsigned long long) total);
-    }
+    if (cons_out && cap < total)
+        return refuse(ctx, KMU_E_BAD_ARG, "cap = %llu is below the %llu bytes", (unsigned long long) cap, (unsigned long long) total);
     if (cons_out && total) {
-        a.cons = cons_out;
-        if (mem == KMU_MEM_HOST) KMU_TRY(dev_array(ctx, "cons.cons", total, &a.cons));
+        KMU_TRY(place_output(ctx, "cons.cons", cons_out, total, mem, &a.cons));
         KMU_TRY(launch(ctx, "k_cons_write", k_cons_tiles<true>, grid, dim3(256), 0, a));
-        if (mem == KMU_MEM_HOST) KMU_HIP(ctx, hipMemcpyAsync(cons_out, a.cons, total, hipMemcpyDeviceToHost, ctx->stream));
-        KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        KMU_TRY(bring_output(ctx, cons_out, a.cons, total, mem));
+        return finish_sync(ctx);
     }
-    if (ctx->profiling) profile_collect(ctx);
-    return KMU_OK;
+    return finish_synced(ctx);
 }
 
 extern "C" int kmu_pile_consensus_pos(kmu_ctx *ctx, const uint32_t *pile, const uint8_t *call, const uint8_t *ins_len, uint64_t n_slots, const uint32_t *ins,
@@ -203,32 +181,24 @@ extern "C" int kmu_pile_consensus_pos(kmu_ctx *ctx, const uint32_t *pile, const 
     if (!ctx || !pile || !call || !ins_len || !bases || !offsets || !p || (n_rows_q && (!rows || !pos_out))) return fail(ctx, KMU_E_BAD_ARG, "null argument");
     if (!ins && n_slots) return fail(ctx, KMU_E_BAD_ARG, "ins is null with n_slots = %llu", (unsigned long long) n_slots);
     if (p->flags) return fail(ctx, KMU_E_BAD_ARG, "unknown flag bits 0x%x", p->flags);
-    if (mem != KMU_MEM_HOST && mem != KMU_MEM_DEVICE) return fail(ctx, KMU_E_BAD_ARG, "bad mem %d", mem);
+    KMU_TRY(check_mem(ctx, mem));
     ConsArgs a{};
     uint64_t *tile_off;
     KMU_TRY(cons_plan(ctx, pile, call, ins_len, n_slots, ins, bases, offsets, n_reads, mem, &a, &tile_off));
-    if (n_rows_q == 0) {
-        if (ctx->profiling) profile_collect(ctx);
-        return KMU_OK;
-    }
-    const void *d;
-    KMU_TRY(stage_to_device(ctx, "cons.rows", rows, (size_t) n_rows_q * 8, mem, &d));
+    if (n_rows_q == 0) return finish_synced(ctx);
+    const uint64_t *d_rows;
+    KMU_TRY(stage_to_device(ctx, "cons.rows", rows, (size_t) n_rows_q, mem, &d_rows));
     uint32_t *info, h_info = 0;
     KMU_TRY(dev_array(ctx, "cons.info", 1, &info));
     KMU_HIP(ctx, hipMemsetAsync(info, 0, 4, ctx->stream));
     const dim3 grid(grid_for(ctx, n_rows_q, 256));
-    KMU_TRY(launch(ctx, "k_cons_pos_check", k_cons_pos_check, grid, dim3(256), 0, (const uint64_t *) d, n_rows_q, a.n_rows, info));
-    KMU_HIP(ctx, hipMemcpyAsync(&h_info, info, 4, hipMemcpyDeviceToHost, ctx->stream));
-    KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (h_info) {
-        if (ctx->profiling) profile_collect(ctx);
-        return fail(ctx, KMU_E_UNSUPPORTED, "a query row above n_bases = %llu", (unsigned long long) a.n_rows);
-    }
-    uint64_t *pos = pos_out;
-    if (mem == KMU_MEM_HOST) KMU_TRY(dev_array(ctx, "cons.pos", (size_t) n_rows_q, &pos));
-    KMU_TRY(launch(ctx, "k_cons_pos", k_cons_pos, grid, dim3(256), 0, a, (const uint64_t *) d, n_rows_q, pos));
-    if (mem == KMU_MEM_HOST) KMU_HIP(ctx, hipMemcpyAsync(pos_out, pos, (size_t) n_rows_q * 8, hipMemcpyDeviceToHost, ctx->stream));
-    KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (ctx->profiling) profile_collect(ctx);
-    return KMU_OK;
+    KMU_TRY(launch(ctx, "k_cons_pos_check", k_cons_pos_check, grid, dim3(256), 0, d_rows, n_rows_q, a.n_rows, info));
+    KMU_TRY(read_back(ctx, {{&h_info, info}}));
+    if (h_info)
+        return refuse(ctx, KMU_E_UNSUPPORTED, "a query row above n_bases = %llu", (unsigned long long) a.n_rows);
+    uint64_t *pos;
+    KMU_TRY(place_output(ctx, "cons.pos", pos_out, (size_t) n_rows_q, mem, &pos));
+    KMU_TRY(launch(ctx, "k_cons_pos", k_cons_pos, grid, dim3(256), 0, a, d_rows, n_rows_q, pos));
+    KMU_TRY(bring_output(ctx, pos_out, pos, (size_t) n_rows_q, mem));
+    return finish_sync(ctx);
 }

@@ -59,18 +59,6 @@ int ins_block_offsets(kmu_ctx *ctx, const char *name, const uint8_t *ins_len, ui
     return device_scan_u32(ctx, sums, n_blocks, *block_off);
 }
 
-// two device words (a null source: none) brought into host variables: the stream is synchronised before this returns, whatever a
-// copy answered, so no copy is left pending into the caller's frame
-static int fetch_u64(kmu_ctx *ctx, const uint64_t *const src[2], uint64_t dst[2]) {
-    hipError_t copied = hipSuccess;
-    for (int k = 0; k < 2 && copied == hipSuccess; k++)
-        if (src[k]) copied = hipMemcpyAsync(dst + k, src[k], 8, hipMemcpyDeviceToHost, ctx->stream);
-    const hipError_t synced = hipStreamSynchronize(ctx->stream);
-    KMU_HIP(ctx, copied);
-    KMU_HIP(ctx, synced);
-    return KMU_OK;
-}
-
 struct InsArgs {
     PileArgs p;                       // the chains, their runs and tiles; the pile tables are not used
     const uint8_t *len_q, *len_db;    // ins_len of the two batches
@@ -144,28 +132,25 @@ extern "C" int kmu_pile_ins_plan(kmu_ctx *ctx, const uint32_t *pile, const uint8
     if (!ctx || !pile || !call || !p || !ins_len_out || !n_slots_out) return fail(ctx, KMU_E_BAD_ARG, "null argument");
     if (p->max_ins == 0 || p->max_ins > KMU_INS_MAX) return fail(ctx, KMU_E_BAD_ARG, "max_ins = %u: 1 .. %u", p->max_ins, KMU_INS_MAX);
     if (p->flags) return fail(ctx, KMU_E_BAD_ARG, "unknown flag bits 0x%x", p->flags);
-    if (mem != KMU_MEM_HOST && mem != KMU_MEM_DEVICE) return fail(ctx, KMU_E_BAD_ARG, "bad mem %d", mem);
+    KMU_TRY(check_mem(ctx, mem));
     *n_slots_out = 0;
     if (n_bases == 0) return KMU_OK;
     KMU_HIP(ctx, hipSetDevice(ctx->device));
-    const void *d;
-    KMU_TRY(stage_to_device(ctx, "insplan.pile", pile, (size_t) n_bases * PILE_COLS * 4, mem, &d));
-    const uint32_t *d_pile = (const uint32_t *) d;
-    KMU_TRY(stage_to_device(ctx, "insplan.call", call, (size_t) n_bases, mem, &d));
-    const uint8_t *d_call = (const uint8_t *) d;
-    uint8_t *d_len = ins_len_out;
-    if (mem == KMU_MEM_HOST) KMU_TRY(dev_array(ctx, "insplan.len", n_bases, &d_len));
+    const uint32_t *d_pile;
+    const uint8_t *d_call;
+    KMU_TRY(stage_to_device(ctx, "insplan.pile", pile, (size_t) n_bases * PILE_COLS, mem, &d_pile));
+    KMU_TRY(stage_to_device(ctx, "insplan.call", call, (size_t) n_bases, mem, &d_call));
+    uint8_t *d_len;
+    KMU_TRY(place_output(ctx, "insplan.len", ins_len_out, n_bases, mem, &d_len));
     unsigned long long *d_total;
     KMU_TRY(dev_array(ctx, "insplan.total", 1, &d_total));
     KMU_HIP(ctx, hipMemsetAsync(d_total, 0, 8, ctx->stream));
     KMU_TRY(launch(ctx, "k_ins_plan", k_ins_plan, dim3(grid_for(ctx, n_bases, 256)), dim3(256), 0, d_pile, d_call, n_bases, p->max_ins, d_len, d_total));
     unsigned long long total = 0;
-    if (mem == KMU_MEM_HOST) KMU_HIP(ctx, hipMemcpyAsync(ins_len_out, d_len, n_bases, hipMemcpyDeviceToHost, ctx->stream));
-    KMU_HIP(ctx, hipMemcpyAsync(&total, d_total, 8, hipMemcpyDeviceToHost, ctx->stream));
-    KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (ctx->profiling) profile_collect(ctx);
+    KMU_TRY(bring_output(ctx, ins_len_out, d_len, n_bases, mem));
+    KMU_TRY(read_back(ctx, {{&total, d_total}}));
     *n_slots_out = total;
-    return KMU_OK;
+    return finish_synced(ctx);
 }
 
 extern "C" int kmu_chain_pile_ins(kmu_ctx *ctx, const kmu_chain *chains, uint64_t n_chains, const kmu_chain_aln *aln, const uint64_t *op_offsets,
@@ -192,19 +177,14 @@ extern "C" int kmu_chain_pile_ins(kmu_ctx *ctx, const kmu_chain *chains, uint64_
     if (mem == KMU_MEM_HOST) {
         n_bases[0] = offsets_q[n_reads_q];
         n_bases[1] = offsets_db[n_reads_db];
-    } else {
-        const uint64_t *const src[2] = {offsets_q + n_reads_q, offsets_db + n_reads_db};
-        KMU_TRY(fetch_u64(ctx, src, n_bases));
-    }
+    } else KMU_TRY(read_back(ctx, {{&n_bases[0], offsets_q + n_reads_q}, {&n_bases[1], offsets_db + n_reads_db}}));
     const uint64_t n_bases_q = n_bases[0], n_bases_db = n_bases[1];
 
     // the slot index of the voted sides, and the refusal of an ins_len that does not belong to n_slots
-    const void *d;
     uint64_t *boff;
     const uint64_t *sums[2] = {nullptr, nullptr};
     if (side_q) {
-        KMU_TRY(stage_to_device(ctx, "ins.lenq", ins_len_q, (size_t) n_bases_q, mem, &d));
-        a.len_q = (const uint8_t *) d;
+        KMU_TRY(stage_to_device(ctx, "ins.lenq", ins_len_q, (size_t) n_bases_q, mem, &a.len_q));
         KMU_TRY(ins_block_offsets(ctx, "ins.boffq", a.len_q, n_bases_q, &boff));
         a.boff_q = boff;
         sums[0] = boff + cons_n_blocks(n_bases_q);
@@ -213,20 +193,17 @@ extern "C" int kmu_chain_pile_ins(kmu_ctx *ctx, const kmu_chain *chains, uint64_
         a.len_db = a.len_q;
         a.boff_db = a.boff_q;
     } else if (side_db) {
-        KMU_TRY(stage_to_device(ctx, "ins.lendb", ins_len_db, (size_t) n_bases_db, mem, &d));
-        a.len_db = (const uint8_t *) d;
+        KMU_TRY(stage_to_device(ctx, "ins.lendb", ins_len_db, (size_t) n_bases_db, mem, &a.len_db));
         KMU_TRY(ins_block_offsets(ctx, "ins.boffdb", a.len_db, n_bases_db, &boff));
         a.boff_db = boff;
         sums[1] = boff + cons_n_blocks(n_bases_db);
     }
     uint64_t totals[2] = {n_slots_q, n_slots_db};
-    KMU_TRY(fetch_u64(ctx, sums, totals));
+    KMU_TRY(read_back(ctx, {{&totals[0], sums[0]}, {&totals[1], sums[1]}}));
     const uint64_t total_q = totals[0], total_db = totals[1];
-    if (total_q != n_slots_q || total_db != n_slots_db) {
-        if (ctx->profiling) profile_collect(ctx);
-        return fail(ctx, KMU_E_UNSUPPORTED, "ins_len sums to %llu (q) and %llu (db) slots, not to n_slots", (unsigned long long) total_q,
-                    (unsigned long long) total_db);
-    }
+    if (total_q != n_slots_q || total_db != n_slots_db)
+        return refuse(ctx, KMU_E_UNSUPPORTED, "ins_len sums to %llu (q) and %llu (db) slots, not to n_slots", (unsigned long long) total_q,
+                      (unsigned long long) total_db);
     a.n_slots_q = n_slots_q;
     a.n_slots_db = n_slots_db;
     a.ins_q = side_q ? ins_q : nullptr;
@@ -246,9 +223,8 @@ extern "C" int kmu_chain_pile_ins(kmu_ctx *ctx, const kmu_chain *chains, uint64_
     }
     uint32_t h_info[2] = {0, 0};
     if (n_tiles && (n_slots_q || n_slots_db)) KMU_TRY(launch(ctx, "k_ins_vote", k_ins_vote, dim3(grid_for(ctx, n_tiles, 1, 32)), dim3(64), 0, a, n_tiles));
-    KMU_HIP(ctx, hipMemcpyAsync(h_info, a.p.info, 8, hipMemcpyDeviceToHost, ctx->stream));
-    KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (ctx->profiling) profile_collect(ctx);
+    KMU_TRY(read_back(ctx, {{h_info, a.p.info, sizeof h_info}}));
+    KMU_TRY(finish_synced(ctx));
     std::vector<uint32_t> got;
     auto add_down = [&](uint32_t *mine, const uint32_t *dev, size_t words) -> int { // the caller's table += this call's
         got.resize(words);

@@ -226,31 +226,21 @@ extern "C" int kmu_pile_segments(kmu_ctx *ctx, const uint32_t *pile, const uint6
     if (p->min_depth == 0) return fail(ctx, KMU_E_BAD_ARG, "min_depth must be at least 1");
     if (p->min_len == 0) return fail(ctx, KMU_E_BAD_ARG, "min_len must be at least 1");
     if (p->flags & ~KMU_SEG_LONGEST) return fail(ctx, KMU_E_BAD_ARG, "unknown flag bits 0x%x", p->flags);
-    if (mem != KMU_MEM_HOST && mem != KMU_MEM_DEVICE) return fail(ctx, KMU_E_BAD_ARG, "bad mem %d", mem);
+    KMU_TRY(check_mem(ctx, mem));
     *n_segs_out = 0;
     KMU_HIP(ctx, hipSetDevice(ctx->device));
     if (n_reads == 0) {
-        if (seg_offsets_out) {
-            if (mem == KMU_MEM_HOST) seg_offsets_out[0] = 0;
-            else KMU_HIP(ctx, hipMemsetAsync(seg_offsets_out, 0, 8, ctx->stream));
-            KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        }
+        KMU_TRY(zero_first_offset(ctx, seg_offsets_out, mem));
+        if (seg_offsets_out) KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
         return KMU_OK;
     }
     uint64_t n_rows = 0;
-    if (mem == KMU_MEM_HOST) n_rows = offsets[n_reads];
-    else {
-        KMU_HIP(ctx, hipMemcpyAsync(&n_rows, offsets + n_reads, 8, hipMemcpyDeviceToHost, ctx->stream));
-        KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    }
+    KMU_TRY(caller_word(ctx, offsets + n_reads, mem, &n_rows));
     const bool longest = p->flags & KMU_SEG_LONGEST;
 
     SegArgs a{};
-    const void *d;
-    KMU_TRY(stage_to_device(ctx, "seg.pile", pile, (size_t) n_rows * PILE_COLS * 4, mem, &d));
-    a.pile = (const uint32_t *) d;
-    KMU_TRY(stage_to_device(ctx, "seg.off", offsets, ((size_t) n_reads + 1) * 8, mem, &d));
-    a.off = (const uint64_t *) d;
+    KMU_TRY(stage_to_device(ctx, "seg.pile", pile, (size_t) n_rows * PILE_COLS, mem, &a.pile));
+    KMU_TRY(stage_to_device(ctx, "seg.off", offsets, (size_t) n_reads + 1, mem, &a.off));
     a.n_reads = n_reads;
     a.n_rows = n_rows;
     a.n_tiles = seg_n_tiles(n_rows);
@@ -284,13 +274,9 @@ extern "C" int kmu_pile_segments(kmu_ctx *ctx, const uint32_t *pile, const uint6
     KMU_TRY(device_scan_u32(ctx, a.cnt_s, a.n_tiles, soff));
     KMU_TRY(device_scan_u32(ctx, a.cnt_e, a.n_tiles, eoff));
     uint64_t n_starts = 0, n_ends = 0;
-    KMU_HIP(ctx, hipMemcpyAsync(&n_starts, soff + a.n_tiles, 8, hipMemcpyDeviceToHost, ctx->stream));
-    KMU_HIP(ctx, hipMemcpyAsync(&n_ends, eoff + a.n_tiles, 8, hipMemcpyDeviceToHost, ctx->stream));
-    KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (n_starts != n_ends || n_starts > n_rows) {
-        if (ctx->profiling) profile_collect(ctx);
-        return fail(ctx, KMU_E_HIP, "internal: %llu starts and %llu ends", (unsigned long long) n_starts, (unsigned long long) n_ends);
-    }
+    KMU_TRY(read_back(ctx, {{&n_starts, soff + a.n_tiles}, {&n_ends, eoff + a.n_tiles}}));
+    if (n_starts != n_ends || n_starts > n_rows)
+        return refuse(ctx, KMU_E_HIP, "internal: %llu starts and %llu ends", (unsigned long long) n_starts, (unsigned long long) n_ends);
     a.n_runs = n_starts;
 
     // the runs, what is kept of them, and where it goes
@@ -323,45 +309,36 @@ extern "C" int kmu_pile_segments(kmu_ctx *ctx, const uint32_t *pile, const uint6
         out_segs = a.longest;
     }
     uint64_t total = 0;
-    KMU_HIP(ctx, hipMemcpyAsync(&total, out_off + n_reads, 8, hipMemcpyDeviceToHost, ctx->stream));
     KMU_TRY(copy_out(ctx, seg_offsets_out, out_off, ((size_t) n_reads + 1) * 8, mem));
     KMU_TRY(copy_out(ctx, reads_out, a.reads, (size_t) n_reads * sizeof(kmu_read_trim), mem));
-    KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    KMU_TRY(read_back(ctx, {{&total, out_off + n_reads}}));
     *n_segs_out = total;
-    if (segs_out && cap < total) {
-        if (ctx->profiling) profile_collect(ctx);
-        return fail(ctx, KMU_E_BAD_ARG, "cap = %llu is below the %llu segments", (unsigned long long) cap, (unsigned long long) total);
-    }
+    if (segs_out && cap < total)
+        return refuse(ctx, KMU_E_BAD_ARG, "cap = %llu is below the %llu segments", (unsigned long long) cap, (unsigned long long) total);
     if (segs_out && total) {
         KMU_TRY(copy_out(ctx, segs_out, out_segs, (size_t) total * sizeof(kmu_pile_seg), mem));
-        KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        return finish_sync(ctx);
     }
-    if (ctx->profiling) profile_collect(ctx);
-    return KMU_OK;
+    return finish_synced(ctx);
 }
 
 extern "C" int kmu_extract_ranges(kmu_ctx *ctx, const uint8_t *bases, uint64_t n_bases, const uint64_t *begin, const uint64_t *end, uint64_t n_ranges,
                                   int mem, uint64_t *out_offsets, uint8_t *out, uint64_t cap, uint64_t *n_out) {
     if (!ctx || !out_offsets || !n_out) return fail(ctx, KMU_E_BAD_ARG, "null argument");
     if ((!bases && n_bases) || ((!begin || !end) && n_ranges)) return fail(ctx, KMU_E_BAD_ARG, "null argument");
-    if (mem != KMU_MEM_HOST && mem != KMU_MEM_DEVICE) return fail(ctx, KMU_E_BAD_ARG, "bad mem %d", mem);
+    KMU_TRY(check_mem(ctx, mem));
     *n_out = 0;
     KMU_HIP(ctx, hipSetDevice(ctx->device));
     if (n_ranges == 0) {
-        if (mem == KMU_MEM_HOST) out_offsets[0] = 0;
-        else KMU_HIP(ctx, hipMemsetAsync(out_offsets, 0, 8, ctx->stream));
+        KMU_TRY(zero_first_offset(ctx, out_offsets, mem));
         KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
         return KMU_OK;
     }
     ExtArgs a{};
-    const void *d;
-    KMU_TRY(stage_to_device(ctx, "ext.bases", bases, (size_t) n_bases, mem, &d));
-    a.bases = (const uint8_t *) d;
+    KMU_TRY(stage_to_device(ctx, "ext.bases", bases, (size_t) n_bases, mem, &a.bases));
     a.n_bases = n_bases;
-    KMU_TRY(stage_to_device(ctx, "ext.begin", begin, (size_t) n_ranges * 8, mem, &d));
-    a.begin = (const uint64_t *) d;
-    KMU_TRY(stage_to_device(ctx, "ext.end", end, (size_t) n_ranges * 8, mem, &d));
-    a.end = (const uint64_t *) d;
+    KMU_TRY(stage_to_device(ctx, "ext.begin", begin, (size_t) n_ranges, mem, &a.begin));
+    KMU_TRY(stage_to_device(ctx, "ext.end", end, (size_t) n_ranges, mem, &a.end));
     a.n_ranges = n_ranges;
     uint64_t *off_lo, *off_hi;
     KMU_TRY(dev_array(ctx, "ext.lenlo", n_ranges, &a.len_lo));
@@ -380,33 +357,23 @@ extern "C" int kmu_extract_ranges(kmu_ctx *ctx, const uint8_t *bases, uint64_t n
     KMU_TRY(device_scan_u32(ctx, a.len_hi, n_ranges, off_hi));
     uint32_t h_info = 0;
     uint64_t t_lo = 0, t_hi = 0;
-    KMU_HIP(ctx, hipMemcpyAsync(&h_info, a.info, 4, hipMemcpyDeviceToHost, ctx->stream));
-    KMU_HIP(ctx, hipMemcpyAsync(&t_lo, off_lo + n_ranges, 8, hipMemcpyDeviceToHost, ctx->stream));
-    KMU_HIP(ctx, hipMemcpyAsync(&t_hi, off_hi + n_ranges, 8, hipMemcpyDeviceToHost, ctx->stream));
-    KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (h_info) {
-        if (ctx->profiling) profile_collect(ctx);
-        return fail(ctx, KMU_E_UNSUPPORTED, "a range with begin > end or end > n_bases = %llu", (unsigned long long) n_bases);
-    }
+    KMU_TRY(read_back(ctx, {{&h_info, a.info}, {&t_lo, off_lo + n_ranges}, {&t_hi, off_hi + n_ranges}}));
+    if (h_info)
+        return refuse(ctx, KMU_E_UNSUPPORTED, "a range with begin > end or end > n_bases = %llu", (unsigned long long) n_bases);
     a.total = t_lo + (t_hi << 32);
     a.n_tiles = (a.total + GATHER_TILE - 1u) / GATHER_TILE;
-    a.out_off = out_offsets;
-    if (mem == KMU_MEM_HOST) KMU_TRY(dev_array(ctx, "ext.outoff", n_ranges + 1, &a.out_off));
+    KMU_TRY(place_output(ctx, "ext.outoff", out_offsets, n_ranges + 1, mem, &a.out_off));
     KMU_TRY(launch(ctx, "k_ext_offsets", k_gather_offsets, grid_n, dim3(256), 0, a.off_lo, a.off_hi, n_ranges, a.out_off));
-    if (mem == KMU_MEM_HOST) KMU_HIP(ctx, hipMemcpyAsync(out_offsets, a.out_off, (size_t) (n_ranges + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
+    KMU_TRY(bring_output(ctx, out_offsets, a.out_off, n_ranges + 1, mem));
     *n_out = a.total;
     if (out && cap < a.total) {
-        KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        if (ctx->profiling) profile_collect(ctx);
+        KMU_TRY(finish_sync(ctx));
         return fail(ctx, KMU_E_BAD_ARG, "cap = %llu is below the %llu bytes", (unsigned long long) cap, (unsigned long long) a.total);
     }
     if (out && a.total) {
-        a.out = out;
-        if (mem == KMU_MEM_HOST) KMU_TRY(dev_array(ctx, "ext.out", a.total, &a.out));
+        KMU_TRY(place_output(ctx, "ext.out", out, a.total, mem, &a.out));
         KMU_TRY(launch(ctx, "k_ext_copy", k_ext_copy, dim3(grid_for(ctx, a.n_tiles, 4)), dim3(256), 0, a));
-        if (mem == KMU_MEM_HOST) KMU_HIP(ctx, hipMemcpyAsync(out, a.out, a.total, hipMemcpyDeviceToHost, ctx->stream));
+        KMU_TRY(bring_output(ctx, out, a.out, a.total, mem));
     }
-    KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (ctx->profiling) profile_collect(ctx);
-    return KMU_OK;
+    return finish_sync(ctx);
 }

@@ -287,13 +287,6 @@ __global__ void __launch_bounds__(256) k_rq_remap(const uint8_t *quals, uint64_t
 
 static bool rs_bad_mem(int mem) { return mem != KMU_MEM_HOST && mem != KMU_MEM_DEVICE; }
 
-// where a call writes an optional output of `count` elements: the caller's device array, a workspace for a host array, null for none
-template <class T> static int rs_out(kmu_ctx *ctx, const char *name, T *user, size_t count, int mem, T **d_out) {
-    *d_out = user;
-    if (user && mem == KMU_MEM_HOST) KMU_TRY(dev_array(ctx, name, count + 1, d_out));
-    return KMU_OK;
-}
-
 // the reads staged, their rows of accumulators zeroed and filled by k_rs_class_count
 template <class C> static int rs_count(kmu_ctx *ctx, const char *kname, const uint8_t *bytes, const uint64_t *offsets, uint32_t n_seq, int mem,
                                        DevSeqs *ds, unsigned long long **acc_out) {
@@ -342,9 +335,9 @@ int kmu_read_stats(kmu_ctx *ctx, const kmu_read_stats_params *p, const uint8_t *
     kmu_read_comp *d_comp;
     KMU_TRY(rs_count<BaseClasses>(ctx, "k_rs_base_count", bases, offsets, n_seq, mem, &ds, &acc));
     KMU_TRY(dev_array(ctx, "rs.scal", RSS_WORDS, &scal));
-    KMU_TRY(rs_out(ctx, "rs.comp", comp_out, n_seq, mem, &d_comp));
-    KMU_TRY(rs_out(ctx, "rs.pct", (unsigned long long *) pct_hist, RS_PCT_ROWS * 4, mem, &d_pct));
-    KMU_TRY(rs_out(ctx, "rs.len", (unsigned long long *) len_hist, n_buckets, mem, &d_len));
+    KMU_TRY(place_output(ctx, "rs.comp", comp_out, (size_t) n_seq + 1, mem, &d_comp));
+    KMU_TRY(place_output(ctx, "rs.pct", (unsigned long long *) pct_hist, RS_PCT_ROWS * 4 + 1, mem, &d_pct));
+    KMU_TRY(place_output(ctx, "rs.len", (unsigned long long *) len_hist, (size_t) n_buckets + 1, mem, &d_len));
     KMU_HIP(ctx, hipMemsetAsync(scal, 0, RSS_WORDS * 8, ctx->stream));
     if (d_pct) KMU_HIP(ctx, hipMemsetAsync(d_pct, 0, RS_PCT_ROWS * 4 * 8, ctx->stream));
     if (d_len) KMU_HIP(ctx, hipMemsetAsync(d_len, 0, (size_t) n_buckets * 8, ctx->stream));
@@ -375,12 +368,12 @@ int kmu_quality_remap(kmu_ctx *ctx, const uint8_t *quals, uint64_t n, int mem, u
     if (!ctx || ((!quals || !classes_out) && n) || rs_bad_mem(mem)) return fail(ctx, KMU_E_BAD_ARG, "kmu_quality_remap: null argument or bad mem");
     KMU_HIP(ctx, hipSetDevice(ctx->device));
     if (n == 0) return KMU_OK;
-    const void *d_q;
+    const uint8_t *d_q;
     KMU_TRY(stage_to_device(ctx, "rq.in", quals, n, mem, &d_q));
     uint8_t *d_o;
-    KMU_TRY(rs_out(ctx, "rq.out", classes_out, n + 16, mem, &d_o));
+    KMU_TRY(place_output(ctx, "rq.out", classes_out, n + 17, mem, &d_o));
     const uint64_t n_chunks = (((uintptr_t) d_q | (uintptr_t) d_o) & 15u) ? 0 : n / 16;
-    KMU_TRY(launch(ctx, "k_rq_remap", k_rq_remap, dim3(grid_for(ctx, n_chunks + 256, 256)), dim3(256), 0, (const uint8_t *) d_q, n, n_chunks, d_o));
+    KMU_TRY(launch(ctx, "k_rq_remap", k_rq_remap, dim3(grid_for(ctx, n_chunks + 256, 256)), dim3(256), 0, d_q, n, n_chunks, d_o));
     if (mem == KMU_MEM_HOST) KMU_TRY(copy_out(ctx, classes_out, d_o, n, mem));
     return finish_call(ctx, mem);
 }
@@ -393,8 +386,8 @@ int kmu_read_qual_stats(kmu_ctx *ctx, const uint8_t *quals, const uint64_t *offs
     unsigned long long *acc, *d_hist;
     kmu_read_qual *d_out;
     KMU_TRY(rs_count<QualClasses>(ctx, "k_rs_qual_count", quals, offsets, n_seq, mem, &ds, &acc));
-    KMU_TRY(rs_out(ctx, "rq.reads", out, n_seq, mem, &d_out));
-    KMU_TRY(rs_out(ctx, "rq.hist", (unsigned long long *) class_hist, RS_QUAL_CLASSES, mem, &d_hist));
+    KMU_TRY(place_output(ctx, "rq.reads", out, (size_t) n_seq + 1, mem, &d_out));
+    KMU_TRY(place_output(ctx, "rq.hist", (unsigned long long *) class_hist, RS_QUAL_CLASSES + 1, mem, &d_hist));
     if (d_hist) KMU_HIP(ctx, hipMemsetAsync(d_hist, 0, RS_QUAL_CLASSES * 8, ctx->stream));
     if (n_seq) KMU_TRY(launch(ctx, "k_rq_reads", k_rq_reads, dim3(grid_for(ctx, n_seq, 256)), dim3(256), 0, ds.offsets, n_seq, acc, d_out, d_hist));
     if (mem == KMU_MEM_HOST) {

@@ -176,9 +176,7 @@ static inline int runs_total(kmu_ctx *ctx, PairRuns &r, int mem, bool writing, u
     *emit = false;
     KMU_TRY(device_scan_u32(ctx, r.keep, r.n_max, r.ooff));
     RunInfo h_info{};
-    KMU_HIP(ctx, hipMemcpyAsync(&r.total, r.ooff + r.n_max, 8, hipMemcpyDeviceToHost, ctx->stream));
-    KMU_HIP(ctx, hipMemcpyAsync(&h_info, r.info, sizeof h_info, hipMemcpyDeviceToHost, ctx->stream));
-    KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    KMU_TRY(read_back(ctx, {{&r.total, r.ooff + r.n_max}, {&h_info, r.info}}));
     if (h_info.bad) {
         (void) finish_call(ctx, mem);
         return fail(ctx, KMU_E_UNSUPPORTED, "%s", refusal);
@@ -195,10 +193,10 @@ static inline int runs_total(kmu_ctx *ctx, PairRuns &r, int mem, bool writing, u
 
 // the r.total records: write(where) launches the unit's WRITE kernel; a host caller's records pass through the workspace
 template <class T, class Write> static inline int runs_emit(kmu_ctx *ctx, const PairRuns &r, int mem, T *out, Write write) {
-    T *dev = out;
-    if (mem == KMU_MEM_HOST) KMU_TRY(dev_array(ctx, "runs.out", r.total, &dev));
+    T *dev;
+    KMU_TRY(place_output(ctx, "runs.out", out, r.total, mem, &dev));
     KMU_TRY(write(dev));
-    if (mem == KMU_MEM_HOST) KMU_HIP(ctx, hipMemcpyAsync(out, dev, r.total * sizeof(T), hipMemcpyDeviceToHost, ctx->stream));
+    KMU_TRY(bring_output(ctx, out, dev, r.total, mem));
     return finish_call(ctx, mem);
 }
 

@@ -210,7 +210,7 @@ extern "C" int kmu_seed_chains(kmu_ctx *ctx, const uint32_t *pairs, uint64_t n_p
     if (p->max_gap == 0) return fail(ctx, KMU_E_BAD_ARG, "max_gap = 0: no seed could follow another");
     if (p->min_seeds == 0) return fail(ctx, KMU_E_BAD_ARG, "min_seeds = 0: a chain has at least one seed");
     if (p->flags & ~KMU_CHAIN_UPPER) return fail(ctx, KMU_E_BAD_ARG, "unknown flag bits 0x%x", p->flags & ~KMU_CHAIN_UPPER);
-    if (mem != KMU_MEM_HOST && mem != KMU_MEM_DEVICE) return fail(ctx, KMU_E_BAD_ARG, "bad mem %d", mem);
+    KMU_TRY(check_mem(ctx, mem));
     if (n_pairs > 0xFFFFFFFFull) return fail(ctx, KMU_E_UNSUPPORTED, "%llu pairs: 2^32 or more", (unsigned long long) n_pairs);
     *n_out = 0;
     if (n_pairs == 0) return KMU_OK;
@@ -218,26 +218,18 @@ extern "C" int kmu_seed_chains(kmu_ctx *ctx, const uint32_t *pairs, uint64_t n_p
     KMU_HIP(ctx, hipSetDevice(ctx->device));
 
     ChainArgs a{};
-    const void *d;
-    KMU_TRY(stage_to_device(ctx, "chain.pairs", pairs, (size_t) n_pairs * 8, mem, &d));
-    a.pairs = (const uint32_t *) d;
-    KMU_TRY(stage_to_device(ctx, "chain.posq", pos_q, (size_t) n_q * 4, mem, &d));
-    a.pos_q = (const uint32_t *) d;
-    KMU_TRY(stage_to_device(ctx, "chain.readq", read_q, (size_t) n_q * 4, mem, &d));
-    a.read_q = (const uint32_t *) d;
-    KMU_TRY(stage_to_device(ctx, "chain.strandq", strand_q, (size_t) n_q, mem, &d));
-    a.strand_q = (const uint8_t *) d;
+    KMU_TRY(stage_to_device(ctx, "chain.pairs", pairs, (size_t) n_pairs * 2, mem, &a.pairs));
+    KMU_TRY(stage_to_device(ctx, "chain.posq", pos_q, (size_t) n_q, mem, &a.pos_q));
+    KMU_TRY(stage_to_device(ctx, "chain.readq", read_q, (size_t) n_q, mem, &a.read_q));
+    KMU_TRY(stage_to_device(ctx, "chain.strandq", strand_q, (size_t) n_q, mem, &a.strand_q));
     if (pos_db == pos_q && read_db == read_q && strand_db == strand_q && n_db == n_q) { // a self-join is staged once
         a.pos_db = a.pos_q;
         a.read_db = a.read_q;
         a.strand_db = a.strand_q;
     } else {
-        KMU_TRY(stage_to_device(ctx, "chain.posdb", pos_db, (size_t) n_db * 4, mem, &d));
-        a.pos_db = (const uint32_t *) d;
-        KMU_TRY(stage_to_device(ctx, "chain.readdb", read_db, (size_t) n_db * 4, mem, &d));
-        a.read_db = (const uint32_t *) d;
-        KMU_TRY(stage_to_device(ctx, "chain.stranddb", strand_db, (size_t) n_db, mem, &d));
-        a.strand_db = (const uint8_t *) d;
+        KMU_TRY(stage_to_device(ctx, "chain.posdb", pos_db, (size_t) n_db, mem, &a.pos_db));
+        KMU_TRY(stage_to_device(ctx, "chain.readdb", read_db, (size_t) n_db, mem, &a.read_db));
+        KMU_TRY(stage_to_device(ctx, "chain.stranddb", strand_db, (size_t) n_db, mem, &a.strand_db));
     }
     a.n_q = n_q;
     a.n_reads_q = n_reads_q;

@@ -85,9 +85,7 @@ int launch_nk_scan(kmu_ctx *ctx, const DevSeqs &ds, int kmer_size, uint32_t *d_e
 
 int count_kmers(kmu_ctx *ctx, const DevSeqs &ds, int kmer_size, uint32_t *d_err, const uint64_t **koff, uint64_t *n_items) {
     KMU_TRY(launch_nk_scan(ctx, ds, kmer_size, d_err, koff));
-    KMU_HIP(ctx, hipMemcpyAsync(n_items, *koff + ds.n_seq, 8, hipMemcpyDeviceToHost, ctx->stream));
-    KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return KMU_OK;
+    return read_back(ctx, {{n_items, *koff + ds.n_seq}});
 }
 
 int launch_hashes_compact(kmu_ctx *ctx, const DevSeqs &ds, const KmerCfg &cfg, const uint64_t *koff, uint64_t *d_out, uint32_t *d_err) {
@@ -177,40 +175,19 @@ extern "C" int kmu_sketch(kmu_ctx *ctx, const kmu_sketch_params *p_in, const uin
     DevSeqs ds;
     KMU_TRY(stage_sequences(ctx, bases, offsets, packed_offsets, n_seq, p->input_kind, p->mem, &ds));
     const size_t sigb = sig_elem_bytes(p->sig_type);
-    uint64_t rows = n_seq;
+    const bool all = p->mode == KMU_MODE_ALL_SEQS, host_blocks = p->mem == KMU_MEM_HOST && p->block_size > 0;
+    const uint64_t rows = all ? 1 : host_blocks ? block_row_offsets[n_seq] : n_seq; // (of a host call: what is copied down)
     const uint64_t *d_block_rows = nullptr;
-    void *d_sig = sig_out;
-    uint32_t *d_counts = counts_out;
-    if (p->mem == KMU_MEM_HOST) {
-        if (p->block_size > 0) {
-            rows = block_row_offsets[n_seq];
-            uint64_t *q;
-            KMU_TRY(dev_array(ctx, "in.blockrows", (size_t) n_seq + 1, &q));
-            KMU_HIP(ctx, hipMemcpyAsync(q, block_row_offsets, (size_t) (n_seq + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
-            d_block_rows = q;
-        }
-        void *q;
-        KMU_TRY(dev_buf(ctx, "out.sig", rows * p->sketch_size * sigb + 64, &q));
-        d_sig = q;
-        if (counts_out) KMU_TRY(dev_array(ctx, "out.counts", rows * p->sketch_size + 16, &d_counts));
-    } else {
-        d_block_rows = block_row_offsets;
-    }
+    uint8_t *d_sig;
+    uint32_t *d_counts;
+    if (host_blocks || p->mem == KMU_MEM_DEVICE) KMU_TRY(stage_to_device(ctx, "in.blockrows", block_row_offsets, (size_t) n_seq + 1, p->mem, &d_block_rows));
+    KMU_TRY(place_output(ctx, "out.sig", (uint8_t *) sig_out, rows * p->sketch_size * sigb + 64, p->mem, &d_sig));
+    KMU_TRY(place_output(ctx, "out.counts", counts_out, rows * p->sketch_size + 16, p->mem, &d_counts));
     uint32_t *d_err;
     KMU_TRY(get_err_word(ctx, &d_err));
-    if (p->mode == KMU_MODE_ALL_SEQS) {
-        rows = 1;
-        if (p->mem == KMU_MEM_HOST) {
-            void *q;
-            KMU_TRY(dev_buf(ctx, "out.sig", (size_t) p->sketch_size * sigb + 64, &q));
-            d_sig = q;
-        }
-        if (algo_is_dens(p->algo)) { // one set of bins for every sequence, filled in place (setsketchert.rs:429-463)
-            KMU_TRY(launch_dens(ctx, p, ds, d_sig, d_err, nullptr, 0));
-            if (p->mem == KMU_MEM_HOST)
-                KMU_HIP(ctx, hipMemcpyAsync(sig_out, d_sig, (size_t) p->sketch_size * sigb, hipMemcpyDeviceToHost, ctx->stream));
-            return finish_checked(ctx, p->mem, d_err);
-        }
+    if (all && algo_is_dens(p->algo)) { // one set of bins for every sequence, filled in place (setsketchert.rs:429-463)
+        KMU_TRY(launch_dens(ctx, p, ds, d_sig, d_err, nullptr, 0));
+    } else if (all) {
         // sketch_compressedkmer_seqs (setsketchert.rs:160-202, :299-335): one multiset / one stream over every
         // sequence.  fhash values of all k-mers, compact; then the pre-hashed all-sequences path.
         const uint64_t *hk;
@@ -220,11 +197,8 @@ extern "C" int kmu_sketch(kmu_ctx *ctx, const kmu_sketch_params *p_in, const uin
     } else if (n_seq) {
         KMU_TRY(sketch_per_seq_device(ctx, p, ds, d_block_rows, d_counts, d_sig, d_err, nullptr));
     }
-    if (p->mem == KMU_MEM_HOST) {
-        KMU_HIP(ctx, hipMemcpyAsync(sig_out, d_sig, rows * p->sketch_size * sigb, hipMemcpyDeviceToHost, ctx->stream));
-        if (counts_out && p->mode != KMU_MODE_ALL_SEQS)
-            KMU_HIP(ctx, hipMemcpyAsync(counts_out, d_counts, rows * p->sketch_size * 4, hipMemcpyDeviceToHost, ctx->stream));
-    }
+    KMU_TRY(bring_output(ctx, (uint8_t *) sig_out, d_sig, rows * p->sketch_size * sigb, p->mem));
+    if (!all) KMU_TRY(bring_output(ctx, counts_out, d_counts, rows * p->sketch_size, p->mem));
     return finish_checked(ctx, p->mem, d_err);
 }
 
@@ -243,29 +217,20 @@ extern "C" int kmu_sketch_hashed(kmu_ctx *ctx, const kmu_sketch_params *p_in, co
     const size_t sigb = sig_elem_bytes(p->sig_type);
     const int m = p->sketch_size;
     const uint64_t rows = p->mode == KMU_MODE_ALL_SEQS ? 1 : n_seq;
-    const void *d_vals = hashed;
-    const uint64_t *d_off = offsets;
-    void *d_sig = sig_out;
-    uint32_t *d_counts = counts_out;
+    const uint8_t *d_vals;
+    const uint64_t *d_off;
+    uint8_t *d_sig;
+    uint32_t *d_counts;
     uint64_t n_items = 0, first_item = 0; // the values of the sequences are hashed[offsets[0] .. offsets[n_seq])
     if (p->mem == KMU_MEM_HOST) {
         n_items = offsets[n_seq];
         first_item = n_seq ? offsets[0] : 0;
-        void *q;
-        KMU_TRY(dev_buf(ctx, "in.bases", n_items * w + 64, &q));
-        KMU_HIP(ctx, hipMemcpyAsync(q, hashed, n_items * w, hipMemcpyHostToDevice, ctx->stream));
-        d_vals = q;
-        KMU_TRY(dev_buf(ctx, "in.offsets", ((size_t) n_seq + 1) * 8, &q));
-        KMU_HIP(ctx, hipMemcpyAsync(q, offsets, ((size_t) n_seq + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
-        d_off = (const uint64_t *) q;
-        KMU_TRY(dev_buf(ctx, "out.sig", rows * m * sigb + 64, &q));
-        d_sig = q;
-        if (counts_out) KMU_TRY(dev_array(ctx, "out.counts", rows * m + 16, &d_counts));
-    } else {
-        KMU_HIP(ctx, hipMemcpyAsync(&n_items, offsets + n_seq, 8, hipMemcpyDeviceToHost, ctx->stream));
-        if (n_seq) KMU_HIP(ctx, hipMemcpyAsync(&first_item, offsets, 8, hipMemcpyDeviceToHost, ctx->stream));
-        KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    }
+    } else if (n_seq) KMU_TRY(read_back(ctx, {{&n_items, offsets + n_seq}, {&first_item, offsets}}));
+    else KMU_TRY(read_back(ctx, {{&n_items, offsets + n_seq}}));
+    KMU_TRY(stage_to_device(ctx, "in.bases", (const uint8_t *) hashed, n_items * w, p->mem, &d_vals, 64));
+    KMU_TRY(stage_to_device(ctx, "in.offsets", offsets, (size_t) n_seq + 1, p->mem, &d_off));
+    KMU_TRY(place_output(ctx, "out.sig", (uint8_t *) sig_out, rows * m * sigb + 64, p->mem, &d_sig));
+    KMU_TRY(place_output(ctx, "out.counts", counts_out, rows * m + 16, p->mem, &d_counts));
     uint32_t *d_err;
     KMU_TRY(get_err_word(ctx, &d_err));
     const DevSeqs ds = hashed_seqs(d_vals, d_off, n_seq);
@@ -292,11 +257,8 @@ extern "C" int kmu_sketch_hashed(kmu_ctx *ctx, const kmu_sketch_params *p_in, co
             KMU_TRY(launch_pmh3a(ctx, p, ds, d_sig, d_err, in));
         }
     }
-    if (p->mem == KMU_MEM_HOST) {
-        KMU_HIP(ctx, hipMemcpyAsync(sig_out, d_sig, rows * m * sigb, hipMemcpyDeviceToHost, ctx->stream));
-        if (counts_out && p->mode != KMU_MODE_ALL_SEQS)
-            KMU_HIP(ctx, hipMemcpyAsync(counts_out, d_counts, rows * m * 4, hipMemcpyDeviceToHost, ctx->stream));
-    }
+    KMU_TRY(bring_output(ctx, (uint8_t *) sig_out, d_sig, rows * m * sigb, p->mem));
+    if (p->mode != KMU_MODE_ALL_SEQS) KMU_TRY(bring_output(ctx, counts_out, d_counts, rows * m, p->mem));
     return finish_checked(ctx, p->mem, d_err);
 }
 
@@ -318,22 +280,14 @@ static int partial_begin(kmu_ctx *ctx, const kmu_sketch_params *p_in, kmu_sketch
     p->block_size = 0;
     if (p->algo == KMU_ALGO_BOTTOMK) return fail(ctx, KMU_E_UNSUPPORTED, "the reference has no bottom-k sketch over a list of sequences");
     KMU_HIP(ctx, hipSetDevice(ctx->device));
-    *d_part = partial_out;
-    if (p->mem == KMU_MEM_HOST) {
-        void *q;
-        KMU_TRY(dev_buf(ctx, "out.partial", (size_t) kmu_sketch_partial_words(p) * 8 + 64, &q));
-        *d_part = (uint64_t *) q;
-    }
-    return KMU_OK;
+    return place_output(ctx, "out.partial", partial_out, (size_t) kmu_sketch_partial_words(p) + 8, p->mem, d_part);
 }
 
 static int partial_end(kmu_ctx *ctx, const kmu_sketch_params *p, int rc, uint64_t *partial_out, const uint64_t *d_part) {
     ctx->partial_out = nullptr;
     if (rc != KMU_OK) return rc;
-    if (p->mem == KMU_MEM_HOST) {
-        KMU_HIP(ctx, hipMemcpyAsync(partial_out, d_part, (size_t) kmu_sketch_partial_words(p) * 8, hipMemcpyDeviceToHost, ctx->stream));
-        KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    }
+    KMU_TRY(bring_output(ctx, partial_out, d_part, (size_t) kmu_sketch_partial_words(p), p->mem));
+    if (p->mem == KMU_MEM_HOST) KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return KMU_OK;
 }
 
@@ -377,16 +331,10 @@ extern "C" int kmu_sketch_merge_partials(kmu_ctx *ctx, const kmu_sketch_params *
     const int m = p->sketch_size;
     const size_t sigb = sig_elem_bytes(p->sig_type);
     const uint64_t words = kmu_sketch_partial_words(p);
-    const uint64_t *d_parts = partials;
-    void *d_sig = sig_out;
-    if (p->mem == KMU_MEM_HOST) {
-        void *q;
-        KMU_TRY(dev_buf(ctx, "in.partials", (size_t) n_parts * words * 8 + 64, &q));
-        KMU_HIP(ctx, hipMemcpyAsync(q, partials, (size_t) n_parts * words * 8, hipMemcpyHostToDevice, ctx->stream));
-        d_parts = (const uint64_t *) q;
-        KMU_TRY(dev_buf(ctx, "out.sig", (size_t) m * sigb + 64, &q));
-        d_sig = q;
-    }
+    const uint64_t *d_parts;
+    uint8_t *d_sig;
+    KMU_TRY(stage_to_device(ctx, "in.partials", partials, (size_t) n_parts * words, p->mem, &d_parts, 8));
+    KMU_TRY(place_output(ctx, "out.sig", (uint8_t *) sig_out, (size_t) m * sigb + 64, p->mem, &d_sig));
     if (p->algo == KMU_ALGO_PROB3A) {
         KMU_TRY(launch(ctx, nullptr, k_pmh_reduce, dim3(m), dim3(256), 0, d_parts, d_parts + m, (uint64_t) n_parts, m, words,
                        kmer_val_bytes(p->kmer_type), d_sig, (uint64_t *) nullptr));
@@ -395,7 +343,7 @@ extern "C" int kmu_sketch_merge_partials(kmu_ctx *ctx, const kmu_sketch_params *
     } else {
         KMU_TRY(launch_super_reduce(ctx, p, d_parts, n_parts, d_sig));
     }
-    if (p->mem == KMU_MEM_HOST) KMU_HIP(ctx, hipMemcpyAsync(sig_out, d_sig, (size_t) m * sigb, hipMemcpyDeviceToHost, ctx->stream));
+    KMU_TRY(bring_output(ctx, (uint8_t *) sig_out, d_sig, (size_t) m * sigb, p->mem));
     return finish_call(ctx, p->mem);
 }
 
@@ -418,9 +366,9 @@ extern "C" int kmu_kmer_hashes_compact(kmu_ctx *ctx, const kmu_hash_params *p, c
     *n_out = n_items;
     if (!out) return KMU_OK;
     if (cap < n_items) return fail(ctx, KMU_E_BAD_ARG, "output too small: %llu values", (unsigned long long) n_items);
-    uint64_t *d_out = out;
-    if (p->mem == KMU_MEM_HOST) KMU_TRY(dev_array(ctx, "all.hashes", n_items + 8, &d_out));
+    uint64_t *d_out;
+    KMU_TRY(place_output(ctx, "all.hashes", out, n_items + 8, p->mem, &d_out));
     KMU_TRY(launch_hashes_compact(ctx, ds, KmerCfg{p->kmer_type, p->kmer_size, p->fhash}, koff, d_out, d_err));
-    if (p->mem == KMU_MEM_HOST) KMU_HIP(ctx, hipMemcpyAsync(out, d_out, n_items * 8, hipMemcpyDeviceToHost, ctx->stream));
+    KMU_TRY(bring_output(ctx, out, d_out, n_items, p->mem));
     return finish_checked(ctx, p->mem, d_err);
 }

@@ -224,8 +224,7 @@ int launch_dens(kmu_ctx *ctx, const kmu_sketch_params *p, const DevSeqs &ds, voi
         const uint32_t mgrid = (uint32_t) std::min<uint64_t>(((uint64_t) ds.n_seq + 1023) / 1024, (uint64_t) ctx->num_cus);
         KMU_TRY(launch(ctx, nullptr, k_dens_max_len, dim3(mgrid ? mgrid : 1), dim3(1024), 0, ds.offsets, ds.n_seq, (uint64_t *) mx));
         uint64_t max_len = 0;
-        KMU_HIP(ctx, hipMemcpyAsync(&max_len, mx, 8, hipMemcpyDeviceToHost, ctx->stream));
-        KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        KMU_TRY(read_back(ctx, {{&max_len, mx, 8}}));
         if (max_len > (uint64_t) DENS_LONG_KMERS + (uint64_t) a.cfg.k) {
             std::vector<uint64_t> h_off((size_t) ds.n_seq + 1);
             KMU_HIP(ctx, hipMemcpyAsync(h_off.data(), ds.offsets, ((size_t) ds.n_seq + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));

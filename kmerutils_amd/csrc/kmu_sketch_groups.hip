@@ -529,8 +529,7 @@ static int groups_dens(kmu_ctx *ctx, const kmu_sketch_params *p, const DevSeqs &
                    d_err));
     if (!host_checked) {
         uint64_t h_head[GD_WORDS] = {0, 0, 0, 0}; // the one device-to-host copy of the call
-        KMU_HIP(ctx, hipMemcpyAsync(h_head, head, sizeof h_head, hipMemcpyDeviceToHost, ctx->stream));
-        KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        KMU_TRY(read_back(ctx, {{h_head, head, sizeof h_head}}));
         if (h_head[GD_BAD]) {
             if (!ctx->async_device) (void) check_err_word(ctx, d_err); // (read, so that it starts clear next time)
             return fail(ctx, KMU_E_BAD_ARG, "%s", groups_bad_text((uint32_t) h_head[GD_BAD]));
@@ -561,8 +560,7 @@ static int groups_batched(kmu_ctx *ctx, const kmu_sketch_params *p, const DevSeq
     KMU_TRY(launch(ctx, "k_group_plan", k_group_plan, dim3(1), dim3(1024), 0, d_go, n_groups, n_seq, koff, super ? 1 : 0, gk, lbase, bits,
                    (uint64_t *) head));
     uint64_t h_head[3] = {0, 0, 0}; // the one device-to-host copy of the call
-    KMU_HIP(ctx, hipMemcpyAsync(h_head, head, sizeof h_head, hipMemcpyDeviceToHost, ctx->stream));
-    KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    KMU_TRY(read_back(ctx, {{h_head, head, sizeof h_head}}));
     if (h_head[2]) {
         if (!(p->mem == KMU_MEM_DEVICE && ctx->async_device)) (void) check_err_word(ctx, d_err); // (read, so that it starts clear next time)
         return fail(ctx, KMU_E_BAD_ARG, "%s", groups_bad_text((uint32_t) h_head[2]));
@@ -615,7 +613,7 @@ extern "C" int kmu_sketch_groups(kmu_ctx *ctx, const kmu_sketch_params *p_in, co
     p_all.mode = KMU_MODE_ALL_SEQS;
     KMU_TRY(sketch_params(ctx, &p_all, &p_res));
     const kmu_sketch_params *p = &p_res;
-    if (p->mem != KMU_MEM_HOST && p->mem != KMU_MEM_DEVICE) return fail(ctx, KMU_E_BAD_ARG, "bad mem %d", p->mem);
+    KMU_TRY(check_mem(ctx, p->mem));
     if (!offsets || (!bases && n_seq)) return fail(ctx, KMU_E_BAD_ARG, "null sequence buffers");
     if (n_groups == 0) return KMU_OK;
     const bool host = p->mem == KMU_MEM_HOST;
@@ -627,20 +625,14 @@ extern "C" int kmu_sketch_groups(kmu_ctx *ctx, const kmu_sketch_params *p_in, co
     DevSeqs ds;
     KMU_TRY(stage_sequences(ctx, bases, offsets, packed_offsets, n_seq, p->input_kind, p->mem, &ds));
     const size_t row_bytes = (size_t) p->sketch_size * sig_elem_bytes(p->sig_type);
-    void *d_sig = sig_out;
-    const uint64_t *d_go = group_offsets;
-    if (host) {
-        void *q;
-        KMU_TRY(dev_buf(ctx, "out.sig", (size_t) n_groups * row_bytes + 64, &q));
-        d_sig = q;
-        KMU_TRY(dev_buf(ctx, "grp.go", ((size_t) n_groups + 1) * 8, &q));
-        KMU_HIP(ctx, hipMemcpyAsync(q, group_offsets, ((size_t) n_groups + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
-        d_go = (const uint64_t *) q;
-    }
+    uint8_t *d_sig;
+    const uint64_t *d_go;
+    KMU_TRY(place_output(ctx, "out.sig", (uint8_t *) sig_out, (size_t) n_groups * row_bytes + 64, p->mem, &d_sig));
+    KMU_TRY(stage_to_device(ctx, "grp.go", group_offsets, (size_t) n_groups + 1, p->mem, &d_go));
     uint32_t *d_err;
     KMU_TRY(get_err_word(ctx, &d_err));
     if (algo_is_dens(p->algo)) KMU_TRY(groups_dens(ctx, p, ds, d_go, n_groups, d_sig, d_err, host));
     else KMU_TRY(groups_batched(ctx, p, ds, d_go, n_groups, d_sig, d_err));
-    if (host) KMU_HIP(ctx, hipMemcpyAsync(sig_out, d_sig, (size_t) n_groups * row_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    KMU_TRY(bring_output(ctx, (uint8_t *) sig_out, d_sig, (size_t) n_groups * row_bytes, p->mem));
     return finish_checked(ctx, p->mem, d_err);
 }

@@ -86,9 +86,7 @@ static int pmh_route(kmu_ctx *ctx, const kmu_sketch_params *p, const DevSeqs &ds
         else if (!ds.h_offsets.empty()) total = ds.h_offsets[ds.n_seq] - ds.h_offsets[0];
         else {
             uint64_t ends[2] = {0, 0};
-            KMU_HIP(ctx, hipMemcpyAsync(&ends[0], ds.offsets, 8, hipMemcpyDeviceToHost, ctx->stream));
-            KMU_HIP(ctx, hipMemcpyAsync(&ends[1], ds.offsets + ds.n_seq, 8, hipMemcpyDeviceToHost, ctx->stream));
-            KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
+            KMU_TRY(read_back(ctx, {{&ends[0], ds.offsets}, {&ends[1], ds.offsets + ds.n_seq}}));
             total = ends[1] - ends[0];
         }
         if (judge) {
@@ -256,9 +254,7 @@ static int launch_listed(kmu_ctx *ctx, SketchArgs a, sketch_kernel_t kern, const
 
 // the count of long / redo reads the last launch listed (a host synchronisation)
 static int read_count(kmu_ctx *ctx, const SketchArgs &a, uint32_t *n) {
-    KMU_HIP(ctx, hipMemcpyAsync(n, a.queue + 56, 4, hipMemcpyDeviceToHost, ctx->stream));
-    KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return KMU_OK;
+    return read_back(ctx, {{n, a.queue + 56}});
 }
 
 // every read of the batch has at most 256 k-mers: one wave per read builds its list (k_multiset_short), and one wave per
@@ -441,8 +437,7 @@ int sketch_pmh_per_seq(kmu_ctx *ctx, const kmu_sketch_params *p, const DevSeqs &
             KMU_HIP(ctx, hipMemsetAsync(mx, 0, 8, ctx->stream));
             const uint32_t mgrid = (uint32_t) std::min<uint64_t>(((uint64_t) n_seq + 1023) / 1024, (uint64_t) ctx->num_cus);
             KMU_TRY(launch(ctx, nullptr, k_max_len, dim3(mgrid ? mgrid : 1), dim3(1024), 0, ds.offsets, n_seq, (uint64_t *) mx));
-            KMU_HIP(ctx, hipMemcpyAsync(len_stats, mx, 16, hipMemcpyDeviceToHost, ctx->stream));
-            KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
+            KMU_TRY(read_back(ctx, {{len_stats, mx, 16}}));
         }
         const uint64_t max_len = len_stats[0];
         if (max_len > (uint64_t) LONG_SEQ_KMERS + (uint64_t) p->kmer_size) {

@@ -202,7 +202,7 @@ static int sg_check(kmu_ctx *ctx, const kmu_chain *chains, uint64_t n_chains, co
     if (p->flags) return fail(ctx, KMU_E_BAD_ARG, "unknown flag bits 0x%x", p->flags);
     if (p->int_permille > 1000u) return fail(ctx, KMU_E_BAD_ARG, "int_permille = %u: at most 1000", p->int_permille);
     if (p->min_identity_permille > 1000u) return fail(ctx, KMU_E_BAD_ARG, "min_identity_permille = %u: at most 1000", p->min_identity_permille);
-    if (mem != KMU_MEM_HOST && mem != KMU_MEM_DEVICE) return fail(ctx, KMU_E_BAD_ARG, "bad mem %d", mem);
+    KMU_TRY(check_mem(ctx, mem));
     if (n_reads >= 0x80000000u) return fail(ctx, KMU_E_UNSUPPORTED, "%u reads: 2^31 or more", n_reads);
     if (n_chains >= 0x80000000ull) return fail(ctx, KMU_E_UNSUPPORTED, "%llu records: 2^31 or more", (unsigned long long) n_chains);
     if (n_chains && !n_reads) return fail(ctx, KMU_E_BAD_ARG, "records but no reads");
@@ -213,13 +213,9 @@ static int sg_check(kmu_ctx *ctx, const kmu_chain *chains, uint64_t n_chains, co
 static int sg_begin(kmu_ctx *ctx, const kmu_chain *chains, const kmu_chain_aln *aln, uint64_t n_chains, const uint64_t *offsets,
                     uint32_t n_reads, const kmu_sg_params *p, int mem, SgArgs &a) {
     KMU_HIP(ctx, hipSetDevice(ctx->device));
-    const void *d;
-    KMU_TRY(stage_to_device(ctx, "sg.chains", chains, (size_t) n_chains * sizeof(kmu_chain), mem, &d));
-    a.chains = (const kmu_chain *) d;
-    KMU_TRY(stage_to_device(ctx, "sg.aln", aln, (size_t) n_chains * sizeof(kmu_chain_aln), mem, &d));
-    a.aln = (const kmu_chain_aln *) d;
-    KMU_TRY(stage_to_device(ctx, "sg.off", offsets, ((size_t) n_reads + 1) * 8, mem, &d));
-    a.off = (const uint64_t *) d;
+    KMU_TRY(stage_to_device(ctx, "sg.chains", chains, (size_t) n_chains, mem, &a.chains));
+    KMU_TRY(stage_to_device(ctx, "sg.aln", aln, (size_t) n_chains, mem, &a.aln));
+    KMU_TRY(stage_to_device(ctx, "sg.off", offsets, (size_t) n_reads + 1, mem, &a.off));
     a.n_chains = n_chains;
     a.n_reads = n_reads;
     a.p = *p;
@@ -238,8 +234,7 @@ extern "C" int kmu_sg_classify(kmu_ctx *ctx, const kmu_chain *chains, const kmu_
     SgArgs a{};
     KMU_TRY(sg_begin(ctx, chains, aln, n_chains, offsets, n_reads, p, mem, a));
     uint32_t h_bad = 0;
-    KMU_HIP(ctx, hipMemcpyAsync(&h_bad, a.bad, 4, hipMemcpyDeviceToHost, ctx->stream));
-    KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    KMU_TRY(read_back(ctx, {{&h_bad, a.bad}}));
     if (h_bad) {
         (void) finish_call(ctx, mem);
         return fail(ctx, KMU_E_UNSUPPORTED, "%s", SG_REFUSAL);
@@ -267,9 +262,7 @@ extern "C" int kmu_sg_graph(kmu_ctx *ctx, const kmu_chain *chains, const kmu_cha
     KMU_TRY(device_scan_u32(ctx, a.counts, a.n_tiles, coff));
     uint32_t h_bad = 0;
     uint64_t survivors = 0;
-    KMU_HIP(ctx, hipMemcpyAsync(&h_bad, a.bad, 4, hipMemcpyDeviceToHost, ctx->stream));
-    KMU_HIP(ctx, hipMemcpyAsync(&survivors, coff + a.n_tiles, 8, hipMemcpyDeviceToHost, ctx->stream));
-    KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    KMU_TRY(read_back(ctx, {{&h_bad, a.bad}, {&survivors, coff + a.n_tiles}}));
     if (h_bad) {
         (void) finish_call(ctx, mem);
         return fail(ctx, KMU_E_UNSUPPORTED, "%s", SG_REFUSAL);
@@ -296,8 +289,7 @@ extern "C" int kmu_sg_graph(kmu_ctx *ctx, const kmu_chain *chains, const kmu_cha
         KMU_TRY(dev_array(ctx, "sg.maxlen", n_v, &a.max_len));
         KMU_TRY(dev_array(ctx, "sg.first", n_v, &a.first));
         KMU_TRY(dev_array(ctx, "sg.mark", n_chains, &a.mark));
-        a.arcs = arcs_out;
-        if (mem == KMU_MEM_HOST) KMU_TRY(dev_array(ctx, "sg.arcs", a.n_arcs, &a.arcs));
+        KMU_TRY(place_output(ctx, "sg.arcs", arcs_out, a.n_arcs, mem, &a.arcs));
         KMU_HIP(ctx, hipMemsetAsync(a.mark, 0, n_chains, ctx->stream));
 
         KMU_TRY(launch(ctx, "k_sg_arcs_write", k_sg_arcs<true>, dim3(a.n_tiles), dim3(64), 0, a));
@@ -309,7 +301,7 @@ extern "C" int kmu_sg_graph(kmu_ctx *ctx, const kmu_chain *chains, const kmu_cha
         KMU_TRY(launch(ctx, "k_sg_reduce", k_sg_reduce, dim3(grid_for(ctx, a.n_arcs, 4)), dim3(256), 0, a)); // (a wave per arc)
         KMU_TRY(launch(ctx, "k_sg_finish", k_sg_finish, flat, dim3(256), 0, a));
         KMU_TRY(launch(ctx, "k_sg_unique", k_sg_unique, flat, dim3(256), 0, a));
-        if (mem == KMU_MEM_HOST) KMU_TRY(copy_out(ctx, arcs_out, a.arcs, (size_t) a.n_arcs * sizeof(kmu_sg_arc), mem));
+        KMU_TRY(bring_output(ctx, arcs_out, a.arcs, a.n_arcs, mem));
     }
     KMU_TRY(copy_out(ctx, class_out, a.cls, (size_t) n_chains, mem));
     KMU_TRY(copy_out(ctx, reads_out, a.reads, (size_t) n_reads * sizeof(kmu_sg_read), mem));

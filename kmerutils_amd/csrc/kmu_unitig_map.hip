@@ -120,7 +120,7 @@ extern "C" int kmu_sg_unitig_chains(kmu_ctx *ctx, const kmu_sg_unitig *unitigs, 
         ((!chains || !classes) && n_chains))
         return fail(ctx, KMU_E_BAD_ARG, "null argument");
     if (p->flags || p->zero) return fail(ctx, KMU_E_BAD_ARG, "flags = 0x%x and zero = %u must be 0", p->flags, p->zero);
-    if (mem != KMU_MEM_HOST && mem != KMU_MEM_DEVICE) return fail(ctx, KMU_E_BAD_ARG, "bad mem %d", mem);
+    KMU_TRY(check_mem(ctx, mem));
     if (n_reads >= 0x80000000u) return fail(ctx, KMU_E_UNSUPPORTED, "%u reads: 2^31 or more", n_reads);
     if (n_chains >= 0x100000000ull) return fail(ctx, KMU_E_UNSUPPORTED, "%llu chains: 2^32 or more", (unsigned long long) n_chains);
     if (!ctx) return fail(ctx, KMU_E_BAD_ARG, "null context");
@@ -131,22 +131,15 @@ extern "C" int kmu_sg_unitig_chains(kmu_ctx *ctx, const kmu_sg_unitig *unitigs, 
     }
     KMU_HIP(ctx, hipSetDevice(ctx->device));
     UmArgs a{};
-    const void *d;
-    KMU_TRY(stage_to_device(ctx, "um.unitigs", unitigs, (size_t) n_unitigs * sizeof(kmu_sg_unitig), mem, &d));
-    a.unitigs = (const kmu_sg_unitig *) d;
+    KMU_TRY(stage_to_device(ctx, "um.unitigs", unitigs, (size_t) n_unitigs, mem, &a.unitigs));
     a.n_unitigs = n_unitigs;
-    KMU_TRY(stage_to_device(ctx, "um.path", path, (size_t) n_steps * sizeof(kmu_sg_step), mem, &d));
-    a.path = (const kmu_sg_step *) d;
+    KMU_TRY(stage_to_device(ctx, "um.path", path, (size_t) n_steps, mem, &a.path));
     a.n_steps = n_steps;
-    KMU_TRY(stage_to_device(ctx, "um.place", place, (size_t) n_reads * sizeof(kmu_sg_place), mem, &d));
-    a.place = (const kmu_sg_place *) d;
-    KMU_TRY(stage_to_device(ctx, "um.chains", chains, (size_t) n_chains * sizeof(kmu_chain), mem, &d));
-    a.chains = (const kmu_chain *) d;
-    KMU_TRY(stage_to_device(ctx, "um.classes", classes, (size_t) n_chains, mem, &d));
-    a.classes = (const uint8_t *) d;
+    KMU_TRY(stage_to_device(ctx, "um.place", place, (size_t) n_reads, mem, &a.place));
+    KMU_TRY(stage_to_device(ctx, "um.chains", chains, (size_t) n_chains, mem, &a.chains));
+    KMU_TRY(stage_to_device(ctx, "um.classes", classes, (size_t) n_chains, mem, &a.classes));
     a.n_chains = n_chains;
-    KMU_TRY(stage_to_device(ctx, "um.off", offsets, ((size_t) n_reads + 1) * 8, mem, &d));
-    a.off = (const uint64_t *) d;
+    KMU_TRY(stage_to_device(ctx, "um.off", offsets, (size_t) n_reads + 1, mem, &a.off));
     a.n_reads = n_reads;
 
     // the workspace: the two counters, the keys (8-byte aligned, start as 0) and the refusal flag behind them; the flags and their scan
@@ -160,8 +153,7 @@ extern "C" int kmu_sg_unitig_chains(kmu_ctx *ctx, const kmu_sg_unitig *unitigs, 
     a.best = zeros + 2;
     a.bad = (uint32_t *) (zeros + 2 + n_reads);
     a.pos = pos;
-    a.out = out;
-    if (mem == KMU_MEM_HOST) KMU_TRY(dev_array(ctx, "um.out", n_reads, &a.out));
+    KMU_TRY(place_output(ctx, "um.out", out, n_reads, mem, &a.out));
     KMU_HIP(ctx, hipMemsetAsync(zeros, 0, n_zero * 8, ctx->stream));
     KMU_HIP(ctx, hipMemsetAsync(a.has, 0, (size_t) n_reads * 4, ctx->stream));
 
@@ -177,10 +169,7 @@ extern "C" int kmu_sg_unitig_chains(kmu_ctx *ctx, const kmu_sg_unitig *unitigs, 
     unsigned long long h_stats[2] = {0, 0};
     uint64_t n_rec = 0;
     uint32_t h_bad = 0;
-    KMU_HIP(ctx, hipMemcpyAsync(h_stats, a.stats, sizeof h_stats, hipMemcpyDeviceToHost, ctx->stream));
-    KMU_HIP(ctx, hipMemcpyAsync(&n_rec, pos + n_reads, 8, hipMemcpyDeviceToHost, ctx->stream));
-    KMU_HIP(ctx, hipMemcpyAsync(&h_bad, a.bad, 4, hipMemcpyDeviceToHost, ctx->stream));
-    KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    KMU_TRY(read_back(ctx, {{h_stats, a.stats, sizeof h_stats}, {&n_rec, pos + n_reads}, {&h_bad, a.bad}}));
     if (h_bad) {
         (void) finish_call(ctx, mem);
         return fail(ctx, KMU_E_UNSUPPORTED,
@@ -192,6 +181,6 @@ extern "C" int kmu_sg_unitig_chains(kmu_ctx *ctx, const kmu_sg_unitig *unitigs, 
     stats_out->n_contained = h_stats[UM_CONTAINED];
     stats_out->n_unplaced = (uint64_t) n_reads - h_stats[UM_LAYOUT] - h_stats[UM_CONTAINED];
     *n_out = n_rec;
-    if (mem == KMU_MEM_HOST) KMU_TRY(copy_out(ctx, out, a.out, (size_t) n_rec * sizeof(kmu_chain), mem));
+    KMU_TRY(bring_output(ctx, out, a.out, n_rec, mem));
     return finish_call(ctx, mem);
 }

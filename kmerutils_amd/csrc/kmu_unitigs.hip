@@ -245,7 +245,7 @@ extern "C" int kmu_sg_unitigs(kmu_ctx *ctx, const kmu_sg_arc *arcs, uint64_t n_a
                               uint32_t n_reads, int mem, kmu_sg_unitig *unitigs_out, kmu_sg_step *path_out, kmu_sg_place *place_out,
                               uint64_t *n_steps_out, uint64_t *n_out) {
     if (!ctx || !offsets || !n_out || !unitigs_out || !path_out || (!arcs && n_arcs)) return fail(ctx, KMU_E_BAD_ARG, "null argument");
-    if (mem != KMU_MEM_HOST && mem != KMU_MEM_DEVICE) return fail(ctx, KMU_E_BAD_ARG, "bad mem %d", mem);
+    KMU_TRY(check_mem(ctx, mem));
     if (n_reads >= 0x80000000u) return fail(ctx, KMU_E_UNSUPPORTED, "%u reads: 2^31 or more", n_reads);
     if (n_reads == 0) {
         if (n_arcs) return fail(ctx, KMU_E_BAD_ARG, "arcs but no reads");
@@ -255,14 +255,10 @@ extern "C" int kmu_sg_unitigs(kmu_ctx *ctx, const kmu_sg_arc *arcs, uint64_t n_a
     }
     KMU_HIP(ctx, hipSetDevice(ctx->device));
     UtArgs a{};
-    const void *d;
-    KMU_TRY(stage_to_device(ctx, "ut.arcs", arcs, (size_t) n_arcs * sizeof(kmu_sg_arc), mem, &d));
-    a.arcs = (const kmu_sg_arc *) d;
+    KMU_TRY(stage_to_device(ctx, "ut.arcs", arcs, (size_t) n_arcs, mem, &a.arcs));
     a.n_arcs = n_arcs;
-    KMU_TRY(stage_to_device(ctx, "ut.reads", reads, (size_t) n_reads * sizeof(kmu_sg_read), mem, &d));
-    a.reads = (const kmu_sg_read *) d;
-    KMU_TRY(stage_to_device(ctx, "ut.off", offsets, ((size_t) n_reads + 1) * 8, mem, &d));
-    a.off = (const uint64_t *) d;
+    KMU_TRY(stage_to_device(ctx, "ut.reads", reads, (size_t) n_reads, mem, &a.reads));
+    KMU_TRY(stage_to_device(ctx, "ut.off", offsets, (size_t) n_reads + 1, mem, &a.off));
     a.n_reads = n_reads;
 
     // the workspace: links (next and prev start as KMU_SG_NONE), degrees and per-read counts (start as 0), states
@@ -290,14 +286,9 @@ extern "C" int kmu_sg_unitigs(kmu_ctx *ctx, const kmu_sg_arc *arcs, uint64_t n_a
     KMU_TRY(dev_array(ctx, "ut.firsts", (size_t) n_reads + 1, &firsts));
     a.uid = uid;
     a.firsts = firsts;
-    a.unitigs = unitigs_out;
-    a.path = path_out;
-    a.place = place_out;
-    if (mem == KMU_MEM_HOST) {
-        KMU_TRY(dev_array(ctx, "ut.unitigs", n_reads, &a.unitigs));
-        KMU_TRY(dev_array(ctx, "ut.path", n_reads, &a.path));
-        if (place_out) KMU_TRY(dev_array(ctx, "ut.place", n_reads, &a.place));
-    }
+    KMU_TRY(place_output(ctx, "ut.unitigs", unitigs_out, n_reads, mem, &a.unitigs));
+    KMU_TRY(place_output(ctx, "ut.path", path_out, n_reads, mem, &a.path));
+    KMU_TRY(place_output(ctx, "ut.place", place_out, n_reads, mem, &a.place));
     KMU_HIP(ctx, hipMemsetAsync(links, 0xFF, 2 * n_v * 4, ctx->stream));
     KMU_HIP(ctx, hipMemsetAsync(zeros, 0, (2 * n_v + 2 * (size_t) n_reads + 2) * 4, ctx->stream));
     KMU_HIP(ctx, hipMemsetAsync(a.pmin, 0xFF, n_v * 4, ctx->stream));
@@ -323,10 +314,7 @@ extern "C" int kmu_sg_unitigs(kmu_ctx *ctx, const kmu_sg_arc *arcs, uint64_t n_a
     // the two counts and the refusal flag come to the host (the synchronisation)
     uint32_t h_bad = 0;
     uint64_t n_unitigs = 0, n_steps = 0;
-    KMU_HIP(ctx, hipMemcpyAsync(&h_bad, a.bad, 4, hipMemcpyDeviceToHost, ctx->stream));
-    KMU_HIP(ctx, hipMemcpyAsync(&n_unitigs, uid + n_reads, 8, hipMemcpyDeviceToHost, ctx->stream));
-    KMU_HIP(ctx, hipMemcpyAsync(&n_steps, firsts + n_reads, 8, hipMemcpyDeviceToHost, ctx->stream));
-    KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    KMU_TRY(read_back(ctx, {{&h_bad, a.bad}, {&n_unitigs, uid + n_reads}, {&n_steps, firsts + n_reads}}));
     if (h_bad) {
         (void) finish_call(ctx, mem);
         return fail(ctx, KMU_E_UNSUPPORTED,
@@ -335,11 +323,9 @@ extern "C" int kmu_sg_unitigs(kmu_ctx *ctx, const kmu_sg_arc *arcs, uint64_t n_a
     }
     *n_out = n_unitigs;
     if (n_steps_out) *n_steps_out = n_steps;
-    if (mem == KMU_MEM_HOST) {
-        KMU_TRY(copy_out(ctx, unitigs_out, a.unitigs, (size_t) n_unitigs * sizeof(kmu_sg_unitig), mem));
-        KMU_TRY(copy_out(ctx, path_out, a.path, (size_t) n_steps * sizeof(kmu_sg_step), mem));
-        KMU_TRY(copy_out(ctx, place_out, a.place, (size_t) n_reads * sizeof(kmu_sg_place), mem));
-    }
+    KMU_TRY(bring_output(ctx, unitigs_out, a.unitigs, n_unitigs, mem));
+    KMU_TRY(bring_output(ctx, path_out, a.path, n_steps, mem));
+    KMU_TRY(bring_output(ctx, place_out, a.place, n_reads, mem));
     return finish_call(ctx, mem);
 }
 
@@ -347,26 +333,19 @@ extern "C" int kmu_sg_unitig_seqs(kmu_ctx *ctx, const kmu_sg_unitig *unitigs, ui
                                   const uint8_t *bases, const uint64_t *offsets, uint32_t n_reads, int mem, uint64_t *seq_offsets_out,
                                   uint8_t *seq_out, uint64_t cap, uint64_t *n_out) {
     if (!ctx || !offsets || !n_out || (!unitigs && n_unitigs) || (!path && n_steps)) return fail(ctx, KMU_E_BAD_ARG, "null argument");
-    if (mem != KMU_MEM_HOST && mem != KMU_MEM_DEVICE) return fail(ctx, KMU_E_BAD_ARG, "bad mem %d", mem);
+    KMU_TRY(check_mem(ctx, mem));
     *n_out = 0;
     KMU_HIP(ctx, hipSetDevice(ctx->device));
     if (n_unitigs == 0) {
-        if (seq_out && seq_offsets_out) {
-            if (mem == KMU_MEM_HOST) seq_offsets_out[0] = 0;
-            else KMU_HIP(ctx, hipMemsetAsync(seq_offsets_out, 0, 8, ctx->stream));
-        }
+        if (seq_out) KMU_TRY(zero_first_offset(ctx, seq_offsets_out, mem));
         return finish_call(ctx, mem);
     }
     UsArgs a{};
-    const void *d;
-    KMU_TRY(stage_to_device(ctx, "us.unitigs", unitigs, (size_t) n_unitigs * sizeof(kmu_sg_unitig), mem, &d));
-    a.unitigs = (const kmu_sg_unitig *) d;
+    KMU_TRY(stage_to_device(ctx, "us.unitigs", unitigs, (size_t) n_unitigs, mem, &a.unitigs));
     a.n_unitigs = n_unitigs;
-    KMU_TRY(stage_to_device(ctx, "us.path", path, (size_t) n_steps * sizeof(kmu_sg_step), mem, &d));
-    a.path = (const kmu_sg_step *) d;
+    KMU_TRY(stage_to_device(ctx, "us.path", path, (size_t) n_steps, mem, &a.path));
     a.n_steps = n_steps;
-    KMU_TRY(stage_to_device(ctx, "us.off", offsets, ((size_t) n_reads + 1) * 8, mem, &d));
-    a.off = (const uint64_t *) d;
+    KMU_TRY(stage_to_device(ctx, "us.off", offsets, (size_t) n_reads + 1, mem, &a.off));
     a.n_reads = n_reads;
     uint64_t *off_lo, *off_hi, *item_off;
     KMU_TRY(dev_array(ctx, "us.lenlo", n_unitigs, &a.len_lo));
@@ -390,11 +369,7 @@ extern "C" int kmu_sg_unitig_seqs(kmu_ctx *ctx, const kmu_sg_unitig *unitigs, ui
     KMU_TRY(launch(ctx, "k_ut_seq_check", k_ut_seq_check, dim3(grid_for(ctx, std::max(n_steps, n_unitigs), 256)), block, 0, a));
     uint32_t h_bad = 0;
     uint64_t t_lo = 0, t_hi = 0;
-    KMU_HIP(ctx, hipMemcpyAsync(&h_bad, a.bad, 4, hipMemcpyDeviceToHost, ctx->stream));
-    KMU_HIP(ctx, hipMemcpyAsync(&t_lo, off_lo + n_unitigs, 8, hipMemcpyDeviceToHost, ctx->stream));
-    KMU_HIP(ctx, hipMemcpyAsync(&t_hi, off_hi + n_unitigs, 8, hipMemcpyDeviceToHost, ctx->stream));
-    KMU_HIP(ctx, hipMemcpyAsync(&a.n_items, item_off + n_unitigs, 8, hipMemcpyDeviceToHost, ctx->stream));
-    KMU_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    KMU_TRY(read_back(ctx, {{&h_bad, a.bad}, {&t_lo, off_lo + n_unitigs}, {&t_hi, off_hi + n_unitigs}, {&a.n_items, item_off + n_unitigs}}));
     if (h_bad) {
         (void) finish_call(ctx, mem);
         return fail(ctx, KMU_E_UNSUPPORTED,
@@ -415,22 +390,17 @@ extern "C" int kmu_sg_unitig_seqs(kmu_ctx *ctx, const kmu_sg_unitig *unitigs, ui
     a.seq_off = seq_offsets_out;
     if (mem == KMU_MEM_HOST || !seq_offsets_out) KMU_TRY(dev_array(ctx, "us.seqoff", n_unitigs + 1, &a.seq_off));
     KMU_TRY(launch(ctx, "k_ut_seq_offs", k_gather_offsets, per_u, block, 0, a.off_lo, a.off_hi, n_unitigs, a.seq_off));
-    if (mem == KMU_MEM_HOST) KMU_TRY(copy_out(ctx, seq_offsets_out, a.seq_off, (size_t) (n_unitigs + 1) * 8, mem));
+    KMU_TRY(bring_output(ctx, seq_offsets_out, a.seq_off, n_unitigs + 1, mem));
     if (a.total) {
-        if (mem == KMU_MEM_HOST) { // (the batch's size is its last offset)
-            KMU_TRY(stage_to_device(ctx, "us.bases", bases, (size_t) offsets[n_reads], mem, &d));
-            a.bases = (const uint8_t *) d;
-        } else {
-            a.bases = bases;
-        }
+        // (the batch's size is its last offset)
+        KMU_TRY(stage_to_device(ctx, "us.bases", bases, mem == KMU_MEM_HOST ? (size_t) offsets[n_reads] : 0, mem, &a.bases));
         KMU_TRY(dev_array(ctx, "us.ends", (size_t) a.n_items + 1, &a.ends));
         KMU_TRY(dev_array(ctx, "us.isrc", (size_t) a.n_items, &a.isrc));
         a.n_tiles = (a.total + GATHER_TILE - 1u) / GATHER_TILE;
-        a.out = seq_out;
-        if (mem == KMU_MEM_HOST) KMU_TRY(dev_array(ctx, "us.out", (size_t) a.total, &a.out));
+        KMU_TRY(place_output(ctx, "us.out", seq_out, (size_t) a.total, mem, &a.out));
         KMU_TRY(launch(ctx, "k_ut_seq_ends", k_ut_seq_ends, dim3(grid_for(ctx, a.n_items, 256)), block, 0, a));
         KMU_TRY(launch(ctx, "k_ut_seq_copy", k_ut_seq_copy, dim3(grid_for(ctx, a.n_tiles, 4)), block, 0, a));
-        if (mem == KMU_MEM_HOST) KMU_TRY(copy_out(ctx, seq_out, a.out, (size_t) a.total, mem));
+        KMU_TRY(bring_output(ctx, seq_out, a.out, (size_t) a.total, mem));
     }
     return finish_call(ctx, mem);
 }
