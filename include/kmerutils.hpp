@@ -40,6 +40,8 @@
  *                 CleanGraph, sg_clean, clean_graph, layout_reads (tips removed and simple bubbles popped before the layout)
  *                 UnitigChains, sg_unitig_chains, unitig_read_chains, PolishedUnitigs, polish_unitigs
  *                 (every read mapped onto its unitig from the layout, and the consensus of a unitig over its reads)
+ *                 seed_chains_all, chain_rank, chain_mapq, paf_line with a rank record (every chain of every read pair; primary
+ *                 and secondary chains per query read; mapping quality)
  *                 seed_chains, seed_pairs, chain_hits, read_chains (one base-resolution chain per read pair from minimizer
  *                                                            hits)                          (beyond the reference)
  *   counting      KmerCountT (trait), KmerCounter, KmerCounterPool, count_kmer_threaded_one_to_many
@@ -1864,26 +1866,60 @@ Minimizers read_minimizers(const std::vector<const Sequence *> &seqs, size_t k, 
 // seed chaining (kmu_seed_chains; the reference has no such unit)
 // =====================================================================================================================
 
+namespace detail {
+/// the one marshalling of both chaining entries (kmu_seed_chains, kmu_seed_chains_all): the count call, then the write call
+template <class Entry>
+std::vector<kmu_chain> seed_chains_with(Entry entry, const char *who, const std::vector<uint32_t> &pairs, const Minimizers &q,
+                                        const Minimizers &db, const kmu_chain_params &p, Context &ctx) {
+    if (q.offsets.empty() || db.offsets.empty()) throw std::invalid_argument(std::string(who) + ": offsets hold n_reads + 1 entries");
+    if (q.read.size() != q.pos.size() || db.read.size() != db.pos.size() || (!q.strand.empty() && q.strand.size() != q.pos.size()) ||
+        (!db.strand.empty() && db.strand.size() != db.pos.size()))
+        throw std::invalid_argument(std::string(who) + ": pos, read and strand hold one value per minimizer");
+    const uint64_t n_pairs = pairs.size() / 2;
+    std::vector<kmu_chain> out;
+    two_calls(
+        ctx, false, [&](uint64_t total) { out.resize(size_t(total)); },
+        [&](bool, uint64_t cap, uint64_t *total) {
+            return entry(ctx.raw(), n_pairs ? pairs.data() : &spare_element<uint32_t>, n_pairs, ptr(q.pos), ptr(q.read), opt(q.strand),
+                         uint32_t(q.pos.size()), uint32_t(q.offsets.size() - 1), ptr(db.pos), ptr(db.read), opt(db.strand),
+                         uint32_t(db.pos.size()), uint32_t(db.offsets.size() - 1), &p, KMU_MEM_HOST, opt(out), cap, total);
+        });
+    return out;
+}
+} // namespace detail
+
 /// kmu_seed_chains on host arrays: one chain per read pair behind `pairs` (2 per pair: an entry of q, an entry of db, in any order),
 /// one kmu_chain each, ordered by (read_a, read_b) (include/kmu.h has the rules).  The count call, then the write call.
 inline std::vector<kmu_chain> seed_chains(const std::vector<uint32_t> &pairs, const Minimizers &q, const Minimizers &db,
                                           const kmu_chain_params &p, Context &ctx = Context::global()) {
-    if (q.offsets.empty() || db.offsets.empty()) throw std::invalid_argument("seed_chains: offsets hold n_reads + 1 entries");
-    if (q.read.size() != q.pos.size() || db.read.size() != db.pos.size() || (!q.strand.empty() && q.strand.size() != q.pos.size()) ||
-        (!db.strand.empty() && db.strand.size() != db.pos.size()))
-        throw std::invalid_argument("seed_chains: pos, read and strand hold one value per minimizer");
-    const uint64_t n_pairs = pairs.size() / 2;
-    using detail::opt;
-    using detail::ptr;
-    std::vector<kmu_chain> out;
-    detail::two_calls(
-        ctx, false, [&](uint64_t total) { out.resize(size_t(total)); },
-        [&](bool, uint64_t cap, uint64_t *total) {
-            return kmu_seed_chains(ctx.raw(), n_pairs ? pairs.data() : &detail::spare_element<uint32_t>, n_pairs, ptr(q.pos), ptr(q.read), opt(q.strand),
-                                   uint32_t(q.pos.size()), uint32_t(q.offsets.size() - 1), ptr(db.pos), ptr(db.read), opt(db.strand),
-                                   uint32_t(db.pos.size()), uint32_t(db.offsets.size() - 1), &p, KMU_MEM_HOST, opt(out), cap, total);
-        });
+    return detail::seed_chains_with(kmu_seed_chains, "seed_chains", pairs, q, db, p, ctx);
+}
+
+/// kmu_seed_chains_all on host arrays: EVERY chain of every (read pair, strand) behind the same pairs, ordered by (read_a, read_b,
+/// strand, end anchor) (include/kmu.h has the rules).  Arguments and the two calls are those of seed_chains.
+inline std::vector<kmu_chain> seed_chains_all(const std::vector<uint32_t> &pairs, const Minimizers &q, const Minimizers &db,
+                                              const kmu_chain_params &p, Context &ctx = Context::global()) {
+    return detail::seed_chains_with(kmu_seed_chains_all, "seed_chains_all", pairs, q, db, p, ctx);
+}
+
+/// kmu_chain_rank on host arrays: rank, parent, sub_score and n_sub of every chain inside its query read, aligned with `chains`
+/// (the chains of one read_a together, read_a ascending: as both chaining entries write them; include/kmu.h has the rules).
+inline std::vector<kmu_chain_rank_rec> chain_rank(const std::vector<kmu_chain> &chains, uint32_t n_reads_q, uint32_t mask_permille = 500,
+                                                  Context &ctx = Context::global()) {
+    std::vector<kmu_chain_rank_rec> out(chains.size());
+    if (chains.empty()) return out;
+    kmu_rank_params p{};
+    p.mask_permille = mask_permille;
+    ctx.check(kmu_chain_rank(ctx.raw(), chains.data(), chains.size(), n_reads_q, &p, KMU_MEM_HOST, out.data()));
     return out;
+}
+
+/// The mapping quality of chain `at` (minimizer.chain_mapq), host code: for a primary min(60, floor(40 * (1 - sub_score / score) *
+/// min(1, n_seeds / 10) * ln(score))) in doubles, the formula of the minimap2 paper; 0 for a secondary and for a score of 0.
+inline uint32_t chain_mapq(const kmu_chain &c, const kmu_chain_rank_rec &r, size_t at) {
+    if (r.parent != at || c.score == 0) return 0;
+    const double q = 40.0 * (1.0 - double(r.sub_score) / double(c.score)) * std::min(1.0, double(c.n_seeds) / 10.0) * std::log(double(c.score));
+    return uint32_t(std::min(60.0, std::floor(q)));
 }
 
 /// The index join behind chain_hits: the pairs (entry of q, entry of db; 2 per pair) of minimizers that carry the same hash, through
@@ -1914,6 +1950,20 @@ inline std::vector<kmu_chain> chain_hits(const Minimizers &q, const Minimizers *
     p.flags = db ? 0u : KMU_CHAIN_UPPER;
     return seed_chains(seed_pairs(q, db, max_occ, ctx), q, db ? *db : q, p, ctx);
 }
+/// The same with the switch of the Python route (minimizer.chain_hits(..., all=...)): all == true reports every chain of every read
+/// pair (seed_chains_all), which is what mapping reads onto contigs needs.
+inline std::vector<kmu_chain> chain_hits(const Minimizers &q, const Minimizers *db, uint32_t span, uint32_t max_occ, uint32_t max_gap,
+                                         uint32_t band, uint32_t min_seeds, uint32_t min_score, Context &ctx, bool all) {
+    if (!all) return chain_hits(q, db, span, max_occ, max_gap, band, min_seeds, min_score, ctx);
+    kmu_chain_params p{};
+    p.span = span;
+    p.max_gap = max_gap;
+    p.band = band;
+    p.min_seeds = min_seeds;
+    p.min_score = min_score;
+    p.flags = db ? 0u : KMU_CHAIN_UPPER;
+    return seed_chains_all(seed_pairs(q, db, max_occ, ctx), q, db ? *db : q, p, ctx);
+}
 
 /// From the reads of a batch to the chains between them: read_minimizers, then the self-join of chain_hits.
 template <class Kmer>
@@ -1922,6 +1972,13 @@ std::vector<kmu_chain> read_chains(const detail::Batch &batch, size_t k, uint32_
                                    uint32_t min_score = 0, Context &ctx = Context::global()) {
     const Minimizers m = read_minimizers<Kmer>(batch, k, w, fhash, ctx);
     return chain_hits(m, nullptr, uint32_t(k), max_occ, max_gap, band, min_seeds, min_score, ctx);
+}
+/// The same with the switch of the Python route (minimizer.read_chains(..., all=...))
+template <class Kmer>
+std::vector<kmu_chain> read_chains(const detail::Batch &batch, size_t k, uint32_t w, FHash fhash, uint32_t max_occ, uint32_t max_gap,
+                                   uint32_t band, uint32_t min_seeds, uint32_t min_score, Context &ctx, bool all) {
+    const Minimizers m = read_minimizers<Kmer>(batch, k, w, fhash, ctx);
+    return chain_hits(m, nullptr, uint32_t(k), max_occ, max_gap, band, min_seeds, min_score, ctx, all);
 }
 
 // =====================================================================================================================
@@ -1974,6 +2031,18 @@ inline std::string paf_line(const kmu_chain &c, const kmu_chain_aln &a, const st
                     std::to_string(c.b_end) + "\t" + std::to_string(done ? a.matches : 0u) + "\t" + std::to_string(block) + "\t255";
     if (done) s += "\tNM:i:" + std::to_string(a.edit);
     return s + "\ts1:i:" + std::to_string(c.score) + "\tcm:i:" + std::to_string(c.n_seeds);
+}
+
+/// paf_line with the record of chain_rank for chain `at` of its array: column 12 is chain_mapq, and tp:A:P (primary) or tp:A:S
+/// (secondary) and s2:i:sub_score follow cm:i:.
+inline std::string paf_line(const kmu_chain &c, const kmu_chain_aln &a, const kmu_chain_rank_rec &r, size_t at, const std::string &name_q,
+                            uint64_t len_q, const std::string &name_db, uint64_t len_db) {
+    std::string s = paf_line(c, a, name_q, len_q, name_db, len_db);
+    size_t tab = 0; // where column 12 begins: behind the eleventh tab (names hold none)
+    for (int col = 0; col < 11; col++) tab = s.find('\t', tab) + 1;
+    const size_t end = s.find('\t', tab);
+    s.replace(tab, end - tab, std::to_string(chain_mapq(c, r, at)));
+    return s + "\ttp:A:" + (r.parent == at ? "P" : "S") + "\ts2:i:" + std::to_string(r.sub_score);
 }
 
 // =====================================================================================================================

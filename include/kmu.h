@@ -1073,6 +1073,74 @@ int kmu_seed_chains(kmu_ctx *ctx, const uint32_t *pairs, uint64_t n_pairs,
                     const uint32_t *pos_db, const uint32_t *read_db, const uint8_t *strand_db, uint32_t n_db, uint32_t n_reads_db,
                     const kmu_chain_params *p, int mem, kmu_chain *out, uint64_t cap, uint64_t *n_out);
 
+/* ---- seed chaining, every chain: all chains of every group, for mapping reads onto contigs or a reference -------------
+ * Arguments, kmu_chain_params (the same flag bits), mem, out, cap, n_out, the count-only call and every refusal are those of
+ *   kmu_seed_chains.  Anchors, groups, the predecessor relation, t(j, i), f(i) and the choice of the predecessor are word for word
+ *   those of kmu_seed_chains: the lookback of KMU_CHAIN_LOOKBACK, "strictly larger than span", "the largest j of the largest t".
+ *   pred(i) is the chosen predecessor of anchor i, or none.  Inside a group the pred links form a forest with pred(i) < i.
+ * Chains: defined on the forest alone, so not by how it is walked.
+ *   best(v): among v and every anchor whose pred path reaches v, the anchor d with the largest f(d); ties go to the smallest d.
+ *   Every anchor e with best(e) = e is the END of one chain; its members are { v : best(v) = e }, a path of pred links that ends in
+ *   e.  b is its member of smallest index and p = pred(b) where there is one (then best(p) != e: the chain branches off another).
+ *   This is the decomposition that back-tracking gives when it takes the ends by descending f (then ascending index) and walks
+ *   back until it meets an anchor already used (minimap2's), stated without an order of processing.
+ * Record: read_a, read_b, strand of the group; n_anchors = the size of the group; n_seeds = the number of members;
+ *   score = f(e) - f(p), or f(e) without a p, computed in 64 bits and clamped to 0 .. 2^32 - 1 (a branch may end below the f of the
+ *   anchor it left: its score is 0); a_start, a_end, b_start, b_end from b and e by the rules of kmu_seed_chains.
+ * Reported: a chain iff its clamped score >= min_score, n_seeds >= min_seeds and, under KMU_CHAIN_UPPER, read_a < read_b.  The
+ *   filters act per chain: one that fails is left out, and its anchors go to no other chain.
+ * Order: read_a, read_b, strand, then e, all ascending.  A pure function of the inputs.  Anchors equal in every field are
+ *   interchangeable: they stand next to each other in the (x, y) order, and f, pred, best and every field of a record are
+ *   functions of the sequence of (x, y) values and of positions in it -- exchanging two equal entries leaves that sequence, and so
+ *   every record, as it is; which pair of the input an anchor came from is in no record.
+ * Against kmu_seed_chains: every ancestor of a group's arg-max (the largest f, then the smallest index) carries it as its best, so
+ *   its chain runs back to a root, has score f(e) unclamped and is the one kmu_seed_chains walks.  Among the unfiltered chains of a
+ *   read pair, the first by (largest unclamped score, strand 0 before 1, smallest e) is exactly the record of kmu_seed_chains.
+ * Who takes which: kmu_chain_align, kmu_chain_cigar, kmu_chain_pileup and the PAF writer take these records as they take any
+ *   kmu_chain.  A pileup over several chains of one read pair counts the columns where they overlap once per chain.
+ *   kmu_sg_classify, kmu_sg_graph and kmu_sg_unitig_chains keep taking the one-per-pair records of kmu_seed_chains.
+ * How: keys, sorts and groups as in kmu_seed_chains; the DP also leaves f and pred per sorted anchor (12 bytes); one wave per
+ *   group then sweeps the group's chunks of 64 twice with both chunks a link can span in registers: from the last anchor to the
+ *   first, handing every anchor's best to the lane of its predecessor (readlane, no reduction), and from the first to the last
+ *   for the count and first member of every chain; the ends that pass the filters are counted per group, the offsets scanned,
+ *   and a second wave per group writes them.  No LDS, no atomics, no floating point.  DESIGN.md 3.28 has the kernels. */
+int kmu_seed_chains_all(kmu_ctx *ctx, const uint32_t *pairs, uint64_t n_pairs,
+                        const uint32_t *pos_q, const uint32_t *read_q, const uint8_t *strand_q, uint32_t n_q, uint32_t n_reads_q,
+                        const uint32_t *pos_db, const uint32_t *read_db, const uint8_t *strand_db, uint32_t n_db, uint32_t n_reads_db,
+                        const kmu_chain_params *p, int mem, kmu_chain *out, uint64_t cap, uint64_t *n_out);
+
+/* ---- chain ranking: primary and secondary chains of every query read -------------------------------------------------
+ * Input: chains[n_chains] of either chaining entry; the records of one read_a must be consecutive, with read_a non-decreasing
+ *   (both entries write them so).  n_reads_q: the reads of the q batch.  out[c] belongs to chains[c]: always n_chains records, so
+ *   the arrays of kmu_chain_align, kmu_chain_cigar and the rest stay aligned.
+ * Inside one query read:
+ *   rank: the 0-based position of the chain by score descending, then input index ascending.
+ *   len = a_end - a_start; ov(c, P) = max(0, min(a_end_c, a_end_P) - max(a_start_c, a_start_P)).
+ *   In rank order, chain c is SECONDARY TO an earlier primary P iff ov > 0 and ov * 1000 >= mask_permille * min(len_c, len_P)
+ *   (64-bit products).  parent(c) is the input index of the best-ranked such P.  A chain with no such P is PRIMARY and
+ *   parent(c) = c; a secondary is never a parent.
+ *   For a primary, sub_score is the largest score of its secondaries (0 without any) and n_sub their number; for a secondary
+ *   both are 0.  Integer compares only: a pure function of the input.
+ * KMU_MEM_DEVICE: chains and out are device memory; the call synchronises the stream once, to read the refusal flag.
+ *   KMU_MEM_HOST: the records go up through the context's workspace and the output comes back.
+ * n_chains == 0: KMU_OK.  KMU_E_BAD_ARG (nothing is launched): null ctx / chains / p / out, mask_permille > 1000, non-zero flags,
+ *   bad mem, chains while n_reads_q == 0.
+ * KMU_E_UNSUPPORTED: n_chains >= 2^32; read_a falling from one record to the next, read_a >= n_reads_q, a_start > a_end.  These are
+ *   found on the device and reported at the call's one synchronisation; no such record is used as an index, and the records of a
+ *   refused call are unspecified.
+ * How: one key per chain, (read_a, ~score) with the index as value, sorted by the stable radix sort (only the bytes n_reads_q
+ *   reaches, and the four of the score); the first sorted chain of every read by binary search; one wave per query read walks
+ *   its chains in rank order with the primaries so far in its lanes, tests a chain against them 64 at a time, and a ballot finds
+ *   the first hit.  A read of c chains costs up to c^2 / 64 such tests in one wave: the accepted limit -- reads have tens of
+ *   chains, not tens of thousands.  DESIGN.md 3.28 has the kernels. */
+typedef struct kmu_rank_params {
+    uint32_t mask_permille;  /* 0 .. 1000: the share of the shorter chain's query interval that must be covered */
+    uint32_t flags;          /* no flag bits yet: must be 0 */
+} kmu_rank_params;
+typedef struct { uint32_t rank, parent, sub_score, n_sub; } kmu_chain_rank_rec;   /* 16 bytes */
+int kmu_chain_rank(kmu_ctx *ctx, const kmu_chain *chains, uint64_t n_chains, uint32_t n_reads_q,
+                   const kmu_rank_params *p, int mem, kmu_chain_rank_rec *out);
+
 /* ---- chain alignment: banded edit distance and matches of the two segments a chain names -----------------------------
  * Segments: record c names A = read `read_a` of the q batch, bases [a_start, a_end), and B = read `read_b` of the db batch, bases
  *   [b_start, b_end); bases_* / offsets_* are KMU_INPUT_ASCII batches (letters of ACGTacgt, case does not matter) of n_reads_q /

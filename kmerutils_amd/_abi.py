@@ -184,6 +184,20 @@ CHAIN_DTYPE = [("read_a", "<u4"), ("read_b", "<u4"), ("strand", "<u4"), ("score"
                ("a_start", "<u4"), ("a_end", "<u4"), ("b_start", "<u4"), ("b_end", "<u4")]
 
 
+class RankParams(C.Structure):
+    """kmu_rank_params: the overlap share that makes a chain secondary (kmu_chain_rank)"""
+    _fields_ = [("mask_permille", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class ChainRank(C.Structure):
+    """kmu_chain_rank_rec: rank, parent and secondaries of one chain inside its query read (kmu_chain_rank)"""
+    _fields_ = [("rank", C.c_uint32), ("parent", C.c_uint32), ("sub_score", C.c_uint32), ("n_sub", C.c_uint32)]
+
+
+# the same record as a numpy dtype (16 bytes)
+CHAIN_RANK_DTYPE = [("rank", "<u4"), ("parent", "<u4"), ("sub_score", "<u4"), ("n_sub", "<u4")]
+
+
 class AlignParams(C.Structure):
     """kmu_align_params: the band of kmu_chain_align"""
     _fields_ = [("band", C.c_uint32), ("flags", C.c_uint32)]

@@ -104,6 +104,9 @@ def _entry_points():
     d("kmu_read_minimizers", [vp, C.POINTER(A.HashParams), vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp, C.c_uint64, vp, u64p])
     d("kmu_seed_chains", [vp, vp, C.c_uint64, vp, vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp, C.c_uint32, C.c_uint32,
                           C.POINTER(A.ChainParams), C.c_int, vp, C.c_uint64, u64p])
+    d("kmu_seed_chains_all", [vp, vp, C.c_uint64, vp, vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp, C.c_uint32, C.c_uint32,
+                              C.POINTER(A.ChainParams), C.c_int, vp, C.c_uint64, u64p])
+    d("kmu_chain_rank", [vp, vp, C.c_uint64, C.c_uint32, C.POINTER(A.RankParams), C.c_int, vp])
     d("kmu_chain_align", [vp, vp, C.c_uint64, vp, vp, C.c_uint32, vp, vp, C.c_uint32, C.POINTER(A.AlignParams), C.c_int, vp])
     d("kmu_chain_cigar", [vp, vp, C.c_uint64, vp, vp, C.c_uint32, vp, vp, C.c_uint32, C.POINTER(A.CigarParams), C.c_int, vp, vp,
                           vp, C.c_uint64, u64p])
@@ -1023,6 +1026,16 @@ class Context:
         above it; upper: only read_a < read_b.  numpy arrays give a structured array (A.CHAIN_DTYPE); torch cuda tensors stay on
         the device and give an int32 tensor [n, 10] holding the same bits.  Two library calls: one that counts, one with exactly
         that capacity."""
+        return self._seed_chains(self.L.kmu_seed_chains, pairs, q, db, span, max_gap, band, min_seeds, min_score, max_pos, upper)
+
+    def seed_chains_all(self, pairs, q, db, span, max_gap, band, min_seeds=1, min_score=0, max_pos=0, upper=False):
+        """kmu_seed_chains_all: EVERY chain of every (read pair, strand) behind the same entry pairs -- the repeat copies, the parts
+        of a chimeric read, both sides of a structural difference -- ordered by read_a, read_b, strand and end anchor
+        (include/kmu.h has the rules).  Arguments, records and the two library calls are those of seed_chains."""
+        return self._seed_chains(self.L.kmu_seed_chains_all, pairs, q, db, span, max_gap, band, min_seeds, min_score, max_pos, upper)
+
+    def _seed_chains(self, entry, pairs, q, db, span, max_gap, band, min_seeds, min_score, max_pos, upper):
+        """the one marshalling of both chaining entries"""
         if db is None:
             db = q
         mem = self._mem(pairs, q.pos, q.read, q.strand, db.pos, db.read, db.strand)
@@ -1034,7 +1047,24 @@ class Context:
             n = int(m.pos.shape[0])  # the entries of a side: pos, read and strand have as many
             return ptr(m.pos), ptr(m.read), _ptr(m.strand)[0] if n else None, n, len(m.offsets) - 1
         args = (self.h, ptr(pairs), n_pairs, *side(q), *side(db), C.byref(p), mem)
-        (out,), n = self._two_calls(self.L.kmu_seed_chains, args, lambda n: (self._records(pairs, n, A.CHAIN_DTYPE),))
+        (out,), n = self._two_calls(entry, args, lambda n: (self._records(pairs, n, A.CHAIN_DTYPE),))
+        return out[:n]
+
+    def chain_rank(self, chains, n_reads_q, mask_permille=500):
+        """kmu_chain_rank: for every chain its rank inside its query read (score descending), the chain it is secondary to
+        (parent; itself for a primary) and, for a primary, the best score and the number of its secondaries (include/kmu.h has the
+        rules).  chains: the records of seed_chains / seed_chains_all, the chains of one read_a together and read_a ascending;
+        n_reads_q: the reads of the q batch; mask_permille: the share of the shorter query interval that has to be covered.
+        numpy in (A.CHAIN_DTYPE) gives a structured A.CHAIN_RANK_DTYPE array; torch cuda tensors (the int32 [n, 10] records)
+        stay on the device and give an int32 tensor [n, 4] holding the same bits."""
+        if not _is_torch(chains):
+            chains = np.ascontiguousarray(chains)
+        mem = self._mem(chains)
+        n = int(chains.shape[0])
+        p = A.RankParams(int(mask_permille), 0)
+        out = self._records(chains, n, A.CHAIN_RANK_DTYPE)
+        ptr = self._ptrs(chains)
+        self._check(self.L.kmu_chain_rank(self.h, ptr(chains), n, int(n_reads_q), C.byref(p), mem, _ptr(out)[0]))
         return out[:n]
 
     def chain_align(self, chains, bases_q, offsets_q, bases_db=None, offsets_db=None, band=64):

@@ -6,6 +6,9 @@ AnchorIndex.match): every minimizer is a row of ONE hash (m = 1, n_keys = 1) and
 of different reads with that hash in common.  A hash equal to UINT64_MAX is the padding of the index's rows: such a minimizer is
 an empty row there and seeds nothing.  `seed_pairs` is that join as raw entry pairs; `chain_hits` hands them to kmu_seed_chains
 (Context.seed_chains): one colinear chain of seeds per read pair, at base resolution; `read_chains` goes from reads to chains.
+With all=True both hand them to kmu_seed_chains_all instead: every chain of every read pair; `rank_chains` (kmu_chain_rank) then says
+which chains of a query read are primary, `chain_mapq` turns that into mapping qualities on the host, `map_reads` goes from reads
+and contigs to (chains, rank), and `paf_lines(..., rank=rank)` writes the qualities and the tp / s2 tags.
 `align_chains` hands the chains and the reads to kmu_chain_align (Context.chain_align): the banded edit distance and the matching
 columns of every chain's two segments; `read_alignments` goes from reads to (chains, alignments), and `paf_lines` writes the two
 record arrays as PAF text on the host.  `cigar_chains` hands the same to kmu_chain_cigar (Context.chain_cigar): the records and the
@@ -34,6 +37,7 @@ unitig over its reads --, `polished_unitigs` gives the unitig records their new 
 polished unitigs.
 """
 import collections
+import math
 
 import numpy as np
 
@@ -102,23 +106,57 @@ def seed_hits(ctx, q, db=None, max_occ=0):
     return _gather6(seed_pairs(ctx, q, db, max_occ), q, q if db is None else db)
 
 
-def chain_hits(ctx, q, db=None, max_occ=0, max_gap=5000, band=500, min_seeds=3, min_score=0, upper=None):
+def chain_hits(ctx, q, db=None, max_occ=0, max_gap=5000, band=500, min_seeds=3, min_score=0, upper=None, all=False):
     """From minimizers to one chain per read pair (kmu_seed_chains on the pairs of seed_pairs): which reads overlap, on which
     strand, from where to where on both reads in bases, with how many seeds and which score.  q, db: Minimizers records of
     read_minimizers (their offsets say how many reads there are, q.k is the span of a seed); db=None is the self-join, and
     `upper` then defaults to True: each read pair once, read_a < read_b.  max_gap / band / min_seeds / min_score: the chaining
-    rules of include/kmu.h.  Returns a structured array of A.CHAIN_DTYPE for numpy records; for torch records an int32 tensor
-    [n, 10] holding the same bits, on the device, where the hits never left it."""
+    rules of include/kmu.h.  all=True: every chain of every read pair and strand (kmu_seed_chains_all), which is what mapping
+    reads onto contigs or a reference needs; the string graph keeps taking the one-per-pair records.  Returns a structured array
+    of A.CHAIN_DTYPE for numpy records; for torch records an int32 tensor [n, 10] holding the same bits, on the device, where the
+    hits never left it."""
     if upper is None:
         upper = db is None
     pairs = seed_pairs(ctx, q, db, max_occ)
-    return ctx.seed_chains(pairs, q, db, span=q.k, max_gap=max_gap, band=band, min_seeds=min_seeds, min_score=min_score, upper=upper)
+    chain = ctx.seed_chains_all if all else ctx.seed_chains
+    return chain(pairs, q, db, span=q.k, max_gap=max_gap, band=band, min_seeds=min_seeds, min_score=min_score, upper=upper)
 
 
-def read_chains(ctx, bases, offsets, k, w, fhash=A.FHASH_CANON_INVHASH, max_occ=0, max_gap=5000, band=500, min_seeds=3, min_score=0):
+def read_chains(ctx, bases, offsets, k, w, fhash=A.FHASH_CANON_INVHASH, max_occ=0, max_gap=5000, band=500, min_seeds=3, min_score=0,
+                all=False):
     """From the reads of a batch to the chains between them in one call: read_minimizers, then the self-join of chain_hits."""
     q = read_minimizers(ctx, bases, offsets, k, w, fhash)
-    return chain_hits(ctx, q, None, max_occ, max_gap, band, min_seeds, min_score)
+    return chain_hits(ctx, q, None, max_occ, max_gap, band, min_seeds, min_score, all=all)
+
+
+def rank_chains(ctx, chains, n_reads_q, mask_permille=500):
+    """Primary and secondary chains of every query read (kmu_chain_rank, Context.chain_rank): rank, parent, sub_score and n_sub
+    per chain, aligned with `chains` (include/kmu.h has the rules).  numpy records give a structured array of A.CHAIN_RANK_DTYPE;
+    torch records an int32 tensor [n, 4] holding the same bits, on the device."""
+    return ctx.chain_rank(chains, n_reads_q, mask_permille=mask_permille)
+
+
+def chain_mapq(chains, rank):
+    """The mapping quality of every chain, on the host, from numpy records of A.CHAIN_DTYPE and A.CHAIN_RANK_DTYPE: for a primary
+    min(60, floor(40 * (1 - sub_score / score) * min(1, n_seeds / 10) * ln(score))), the formula of the minimap2 paper, in
+    doubles; 0 for a secondary and for a score of 0.  Returns an int64 array."""
+    chains, rank = np.asarray(chains), np.asarray(rank)
+    out = np.zeros(chains.shape[0], np.int64)
+    for c, (score, n_seeds, sub, parent) in enumerate(zip(chains["score"].tolist(), chains["n_seeds"].tolist(),
+                                                          rank["sub_score"].tolist(), rank["parent"].tolist())):
+        if parent == c and score > 0:
+            out[c] = min(60, int(math.floor(40.0 * (1.0 - sub / score) * min(1.0, n_seeds / 10.0) * math.log(score))))
+    return out
+
+
+def map_reads(ctx, bases_q, offsets_q, bases_db, offsets_db, k, w, fhash=A.FHASH_CANON_INVHASH, max_occ=0, max_gap=5000, band=500,
+              min_seeds=3, min_score=0, mask_permille=500):
+    """From a batch of reads and a batch of contigs (or a reference) to every chain of every read on them and which of them to
+    believe: read_minimizers of both, chain_hits(all=True), rank_chains.  Returns (chains, rank)."""
+    q = read_minimizers(ctx, bases_q, offsets_q, k, w, fhash)
+    db = read_minimizers(ctx, bases_db, offsets_db, k, w, fhash)
+    chains = chain_hits(ctx, q, db, max_occ, max_gap, band, min_seeds, min_score, all=True)
+    return chains, rank_chains(ctx, chains, len(q.offsets) - 1, mask_permille)
 
 
 def align_chains(ctx, chains, bases_q, offsets_q, bases_db=None, offsets_db=None, band=64):
@@ -530,31 +568,38 @@ def cigar_strings(ops, op_offsets, chains=None, extended=True):
     return out
 
 
-def paf_lines(chains, aln, names_q, offsets_q, names_db=None, offsets_db=None, cigar=None):
+def paf_lines(chains, aln, names_q, offsets_q, names_db=None, offsets_db=None, cigar=None, rank=None):
     """One PAF line per chain, on the host: chains (A.CHAIN_DTYPE) and aln (A.CHAIN_ALN_DTYPE) are numpy records of the same
     length, names_* the names of the reads, offsets_* their offsets (db=None: the self-join).  The 12 standard columns -- query
     name, length, start, end, strand, target name, length, start, end, matches, matches + edit, mapq 255 -- then NM:i:edit,
     s1:i:score and cm:i:n_seeds.  A record without A.ALN_DONE writes 0 matches, a block of max(m, n) and no NM tag.
     cigar=(ops, op_offsets), the runs of cigar_chains for the same chains: a record with A.ALN_PATH also gets cg:Z: with its runs
-    along the target's forward strand (cigar_strings with `chains`)."""
+    along the target's forward strand (cigar_strings with `chains`).
+    rank, the records of rank_chains for the same chains (A.CHAIN_RANK_DTYPE): column 12 is chain_mapq, and tp:A:P (primary) or
+    tp:A:S (secondary) and s2:i:sub_score follow cm:i:; without it the lines are as above."""
     if names_db is None:
         names_db, offsets_db = names_q, offsets_q
     off_q, off_db = np.asarray(offsets_q).astype(np.int64), np.asarray(offsets_db).astype(np.int64)
     lines = []
     if cigar is not None:
         text = cigar_strings(cigar[0], cigar[1], chains)
-        for line, a, cg in zip(paf_lines(chains, aln, names_q, offsets_q, names_db, offsets_db), np.asarray(aln).tolist(), text):
+        for line, a, cg in zip(paf_lines(chains, aln, names_q, offsets_q, names_db, offsets_db, rank=rank), np.asarray(aln).tolist(), text):
             lines.append(line + "\tcg:Z:" + cg if a[3] & A.ALN_PATH else line)
         return lines
-    for c, a in zip(np.asarray(chains).tolist(), np.asarray(aln).tolist()):
+    n = np.asarray(chains).shape[0]
+    mapq = [255] * n if rank is None else chain_mapq(chains, rank).tolist()
+    ranks = [None] * n if rank is None else np.asarray(rank).tolist()
+    for i, (c, a) in enumerate(zip(np.asarray(chains).tolist(), np.asarray(aln).tolist())):
         read_a, read_b, strand, score, n_seeds, _, a_start, a_end, b_start, b_end = c
         edit, matches, _, flags = a
         done = bool(flags & A.ALN_DONE)
         cols = [names_q[read_a], int(off_q[read_a + 1] - off_q[read_a]), a_start, a_end, "-" if strand else "+",
                 names_db[read_b], int(off_db[read_b + 1] - off_db[read_b]), b_start, b_end,
-                matches if done else 0, matches + edit if done else max(a_end - a_start, b_end - b_start), 255]
+                matches if done else 0, matches + edit if done else max(a_end - a_start, b_end - b_start), mapq[i]]
         if done:
             cols.append("NM:i:%d" % edit)
         cols += ["s1:i:%d" % score, "cm:i:%d" % n_seeds]
+        if ranks[i] is not None:
+            cols += ["tp:A:%s" % ("P" if ranks[i][1] == i else "S"), "s2:i:%d" % ranks[i][2]]
         lines.append("\t".join(str(x) for x in cols))
     return lines
