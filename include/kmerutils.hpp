@@ -42,6 +42,7 @@
  *                 (every read mapped onto its unitig from the layout, and the consensus of a unitig over its reads)
  *                 seed_chains_all, chain_rank, chain_mapq, paf_line with a rank record (every chain of every read pair; primary
  *                 and secondary chains per query read; mapping quality)
+ *                 read_syncmers (closed and open syncmers of every read, in the record of read_minimizers)
  *                 seed_chains, seed_pairs, chain_hits, read_chains (one base-resolution chain per read pair from minimizer
  *                                                            hits)                          (beyond the reference)
  *   counting      KmerCountT (trait), KmerCounter, KmerCounterPool, count_kmer_threaded_one_to_many
@@ -1860,6 +1861,46 @@ template <class Kmer>
 Minimizers read_minimizers(const std::vector<const Sequence *> &seqs, size_t k, uint32_t w, FHash fhash = FHash::canon_invhash,
                            Context &ctx = Context::global()) {
     return read_minimizers<Kmer>(detail::gather(seqs), k, w, fhash, ctx);
+}
+
+// =====================================================================================================================
+// syncmers (kmu_read_syncmers; the reference has no such unit)
+// =====================================================================================================================
+
+/// The k-mer type the s-mers of a syncmer are hashed as: the reference's choice for s bases (_abi.kmer_type_for_k)
+inline int syncmer_s_type(size_t s) { return s <= 14 ? KMU_KMER32BIT : s == 16 ? KMU_KMER16B32BIT : KMU_KMER64BIT; }
+
+/// kmu_read_syncmers in one call: the number of k-mers (kmu_minimizer_layout with w = 1) is the capacity, so nothing is counted
+/// first.  The k-mers whose smallest s-mer value sits at offset t or k - s - t: t = 0 gives closed syncmers, 2 t == k - s open
+/// syncmers at the middle offset (include/kmu.h has the rules).  The s-mers are ordered by `fhash` too.  Returns the record of
+/// read_minimizers: seed_pairs, chain_hits and what follows take it as it is.
+template <class Kmer>
+Minimizers read_syncmers(const detail::Batch &batch, size_t k, size_t s, uint32_t t = 0, FHash fhash = FHash::canon_invhash,
+                         Context &ctx = Context::global()) {
+    const detail::Batch b = detail::host_batch("read_syncmers", batch);
+    const bool with_strand = fhash != FHash::canon_nthash && fhash != FHash::canon_nthash_8b;
+    const uint64_t cap = minimizer_layout(b, k, 1).back();
+    const kmu_hash_params hp = detail::hash_params<Kmer>(k, int(fhash), KMU_INPUT_ASCII);
+    const kmu_syncmer_params sp{syncmer_s_type(s), int32_t(s), int32_t(fhash), t};
+    Minimizers m;
+    m.hashes.assign(size_t(cap), 0);
+    m.pos.assign(size_t(cap), 0);
+    m.read.assign(size_t(cap), 0);
+    if (with_strand) m.strand.assign(size_t(cap), 0);
+    m.offsets.assign(b.offsets.size(), 0);
+    uint64_t total = 0;
+    ctx.check(kmu_read_syncmers(ctx.raw(), &hp, &sp, b.bytes.data(), b.offsets.data(), b.n(), detail::ptr(m.hashes), detail::ptr(m.pos),
+                                detail::ptr(m.read), with_strand ? detail::ptr(m.strand) : nullptr, cap, m.offsets.data(), &total));
+    m.hashes.resize(size_t(total));
+    m.pos.resize(size_t(total));
+    m.read.resize(size_t(total));
+    if (with_strand) m.strand.resize(size_t(total));
+    return m;
+}
+template <class Kmer>
+Minimizers read_syncmers(const std::vector<const Sequence *> &seqs, size_t k, size_t s, uint32_t t = 0, FHash fhash = FHash::canon_invhash,
+                         Context &ctx = Context::global()) {
+    return read_syncmers<Kmer>(detail::gather(seqs), k, s, t, fhash, ctx);
 }
 
 // =====================================================================================================================

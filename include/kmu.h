@@ -1014,6 +1014,56 @@ int kmu_read_minimizers(kmu_ctx *ctx, const kmu_hash_params *p, const uint8_t *b
                         uint64_t *mini_offsets_out, /* n_seq + 1, lives where `offsets` lives; may be NULL */
                         uint64_t *n_out);           /* host memory in both modes; required */
 
+/* ---- syncmers: the closed and open (k, s, t) syncmers of every read, selected on the device --------------------------
+ * Read i has L bases, nk = max(0, L - k + 1) k-mers and, with 1 <= s <= k, L - s + 1 s-mers.  h(p), p in [0, nk), is exactly the
+ * value kmu_kmer_hashes writes for (p->kmer_type, p->kmer_size = k, p->fhash); g(q) the one it writes for (sp->s_kmer_type,
+ * sp->s, sp->s_fhash); both 64-bit, zero-extended for the u32 types.  u = k - s; m(p) = min g(q) over q in [p, p + u]: the
+ * s-mers that lie inside the k-mer at p.
+ * Selection: THE K-MER AT p IS SELECTED IFF g(p + t) == m(p) OR g(p + u - t) == m(p), with 0 <= t <= u / 2 (integer division).
+ *   The comparison is by value, not by position: a tie anywhere does not block a k-mer whose end s-mer holds the minimum.  A
+ *   k-mer is chosen by its own k bases alone -- no neighbour takes part, unlike a window minimizer.
+ * Properties: t = 0 gives closed syncmers, about 2 / (u + 1) of the k-mers of random sequence; 2 t == u gives open syncmers at
+ *   the middle offset, about 1 / (u + 1).  s == k selects every k-mer, and so does a read that is one base repeated.  With a
+ *   canonical s_fhash and a canonical fhash the selection is strand-symmetric, ties included: the seeds of revcomp(read) are the
+ *   seeds of read at the positions nk - 1 - p, with the same hashes and the strand flipped, except on palindromic k-mers, whose
+ *   strand is 0 on both.  The result is a pure function of the inputs: it does not depend on the launch shape or on timing.
+ * Outputs: the selected k-mers of all reads, concatenated in read order, ascending in position within a read;
+ *   sync_offsets_out[i] .. sync_offsets_out[i + 1] are the entries of read i.  Entry e of read i at position p:
+ *   hashes_out[e] = h(p), pos_out[e] = p, read_out[e] = i and strand_out[e] as in kmu_read_minimizers: 1 iff the reverse
+ *   complement's value is numerically smaller than the forward value under KMU_FHASH_CANON_RAW / _VALUE / _INVHASH, else 0.
+ * Counts and capacity: *n_out (host memory in both modes, required) is always the total.  hashes_out == NULL is the count-only
+ *   call: it writes *n_out and, if given, sync_offsets_out, and nothing else.  cap < total: KMU_E_BAD_ARG with *n_out set and the
+ *   outputs unspecified.  The number of k-mers, kmu_minimizer_layout(offsets, n_seq, k, 1)[n_seq], is always a sufficient cap.
+ * KMU_MEM_DEVICE: every array except n_out is device memory; the call synchronises the stream once to hand n_out over (a call
+ *   with more tiles than the context's workspace holds counts a second time, as kmu_read_minimizers does).  The offsets are
+ *   trusted.  KMU_MEM_HOST: the inputs go up through the workspace and the results come back; a read of 2^32 bases or more is
+ *   KMU_E_UNSUPPORTED (positions are uint32).
+ * n_seq == 0: KMU_OK, *n_out = 0.  Empty reads and reads shorter than k contribute nothing.
+ * KMU_E_BAD_ARG: null ctx / p / sp / n_out, s == 0, s > k, t > (k - s) / 2, bad mem.  KMU_E_UNSUPPORTED: KMU_INPUT_PACKED2, or
+ * a non-NULL strand_out when p->fhash is an ntHash mode (the ntHash modes are fine for s_fhash, which only orders).
+ * KMU_E_BAD_ALPHABET: either type is an amino-acid type.  A (type, size) pair that kmu_kmer_hashes refuses is refused the same
+ * way, for k and for s.  A non-ACGT byte anywhere in a read (reads shorter than k included) is KMU_E_NON_ACGT, reported as
+ * kmu_read_minimizers reports it.
+ * How: one wave per tile of KMU_SYNCMER_TILE consecutive k-mer positions of one read, tiles dealt grid-stride; a tile needs
+ *   nothing of its neighbours but u more s-mers behind it.  Neither the launches nor the one synchronisation of a call depend on
+ *   the number or the lengths of the reads.  DESIGN.md 3.29 has the kernel. */
+typedef struct kmu_syncmer_params {
+    int32_t s_kmer_type; /* the k-mer type the s-mers are hashed as */
+    int32_t s;           /* 1 .. k */
+    int32_t s_fhash;     /* the order of the s-mers */
+    uint32_t t;          /* 0 .. (k - s) / 2 */
+} kmu_syncmer_params;
+#define KMU_SYNCMER_TILE 1024 /* k-mer positions one wave takes at a time */
+int kmu_read_syncmers(kmu_ctx *ctx, const kmu_hash_params *p, const kmu_syncmer_params *sp, const uint8_t *bases,
+                      const uint64_t *offsets, uint32_t n_seq,
+                      uint64_t *hashes_out,       /* NULL: the count-only call */
+                      uint32_t *pos_out,          /* may be NULL */
+                      uint32_t *read_out,         /* may be NULL */
+                      uint8_t *strand_out,        /* may be NULL */
+                      uint64_t cap,
+                      uint64_t *sync_offsets_out, /* n_seq + 1, lives where `offsets` lives; may be NULL */
+                      uint64_t *n_out);           /* host memory in both modes; required */
+
 /* ---- seed chaining: from minimizer hits to one colinear chain per read pair, at base resolution ----------------------
  * pairs[2p..] = (ea, eb): an entry of the query minimizers and an entry of the database minimizers, as kmu_anchor_index_match
  *   writes them for rows of one hash (minimizer.seed_pairs), in ANY order.  pos_* / read_* / strand_* are the arrays of

@@ -30,6 +30,7 @@ OVL_MAX_BAND = 8         # kmu_anchor_overlaps: the widest band
 OVL_UPPER = 1            # ... and its flag: only read pairs with read_a < read_b
 MINIMIZER_MAX_W = 256    # kmu_read_minimizers: the widest window (in k-mers)
 MINIMIZER_TILE = 1024    # ... and the windows one workgroup takes at a time
+SYNCMER_TILE = 1024      # kmu_read_syncmers: the k-mer positions one wave takes at a time
 CHAIN_LOOKBACK = 64      # kmu_seed_chains: the predecessors an anchor looks at
 CHAIN_UPPER = 1          # ... and its flag: only read pairs with read_a < read_b
 ALIGN_MAX_DIAGS = 1024   # kmu_chain_align: the widest band, in diagonals, one chain may need
@@ -164,6 +165,11 @@ class Overlap(C.Structure):
 # the same record as a numpy dtype (32 bytes)
 OVERLAP_DTYPE = [("read_a", "<u4"), ("read_b", "<u4"), ("strand", "<u4"), ("diag", "<i4"), ("score", "<u4"), ("votes", "<u4"),
                  ("slice_a_min", "<u4"), ("slice_a_max", "<u4")]
+
+
+class SyncmerParams(C.Structure):
+    """kmu_syncmer_params: the s-mers that order (type, s, fhash) and the offset t of kmu_read_syncmers"""
+    _fields_ = [("s_kmer_type", C.c_int32), ("s", C.c_int32), ("s_fhash", C.c_int32), ("t", C.c_uint32)]
 
 
 class ChainParams(C.Structure):

@@ -3,8 +3,9 @@
 //
 // The windows of a read are cut into tiles of KMU_MINIMIZER_TILE consecutive windows; a read with nwin windows has
 // ceil(nwin / TILE) tiles, a read without k-mers none.
-//  k_mini_tiles       one lane per read: its number of tiles (u32).  A read shorter than k has no tile and no k-mer that would
-//                     look at its bases: its bytes are validated here.  device_scan_u32 makes the tile offsets tile_off[n_seq + 1].
+//  k_mini_tiles       (kmu_seed_tiles.h) one lane per read: its number of tiles (u32).  A read shorter than k has no tile and no
+//                     k-mer that would look at its bases: its bytes are validated there.  device_scan_u32 makes the tile offsets
+//                     tile_off[n_seq + 1].
 //  k_read_minimizers  one wave (a 64-thread workgroup) per tile, tiles dealt grid-stride; tile -> read by wave_find_read over
 //                     tile_off.  The tile with windows [j0, j1) hashes the positions [j0 - 1, j1 - 1 + w) (clipped to the read)
 //                     into LDS with SeqView + wave_step_kmers + apply_fhash: TILE + w - 1 positions for its own windows and one
@@ -22,39 +23,20 @@
 //                     recomputes the tile and stores hash / position / read / strand at consecutive entries.  Recomputing costs
 //                     a second pass over the bases (one byte per base); a bitmask of chosen positions from the first pass would
 //                     need a workspace sized by the number of bases, which a KMU_MEM_DEVICE call does not know on the host.
-//  k_mini_offsets     mini_offsets[i] = the offset of read i's first tile.
+//  k_mini_offsets     (kmu_seed_tiles.h) mini_offsets[i] = the offset of read i's first tile.
 //  LDS: 10 KiB hashes + 2.5 KiB relative positions + 1.25 KiB strand bits = 13.75 KiB per one-wave workgroup (eleven per CU).
 #include <algorithm>
 
 #include "kmu_ctx.hpp"
 #include "kmu_flat.h"
+#include "kmu_seed_tiles.h"
 #include "kmu_stream.h"
 
 namespace kmu {
 
-static constexpr uint32_t MINI_T = KMU_MINIMIZER_TILE;
 static constexpr uint32_t MINI_NE = KMU_MINIMIZER_TILE + KMU_MINIMIZER_MAX_W; // positions a tile holds at most: TILE + w
 static constexpr uint32_t MINI_CH = MINI_NE / 64;                             // ... per lane
 static_assert(MINI_NE % 64 == 0 && MINI_NE <= 65536, "a tile's entries are dealt to 64 lanes and indexed by 16 bits");
-
-// windows of a read of L bases: nk = L - k + 1 k-mers, max(nk - w, 0) + 1 windows if it has a k-mer at all
-__host__ __device__ inline uint64_t mini_windows(uint64_t L, uint32_t k, uint32_t w) {
-    if (L < k) return 0;
-    const uint64_t nk = L - k + 1;
-    return nk > w ? nk - w + 1 : 1;
-}
-
-__global__ void __launch_bounds__(256) k_mini_tiles(const uint8_t *bases, const uint64_t *offsets, uint32_t n_seq, uint32_t k, uint32_t w,
-                                                    uint32_t *ntiles, uint32_t *err) {
-    uint32_t bad = 0;
-    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n_seq; i += gridDim.x * blockDim.x) {
-        const uint64_t beg = offsets[i], L = offsets[i + 1] - beg;
-        ntiles[i] = (uint32_t) ((mini_windows(L, k, w) + MINI_T - 1) / MINI_T);
-        if (L < k) // at most 31 bases
-            for (uint64_t j = 0; j < L; j++) bad |= !is_acgt(bases[beg + j]);
-    }
-    if (bad) atomicOr(err, DERR_NON_ACGT);
-}
 
 struct MiniArgs {
     const uint8_t *bases;
@@ -172,11 +154,6 @@ template <bool WRITE> __global__ void __launch_bounds__(64) k_read_minimizers(Mi
         __syncthreads(); // the next tile overwrites the LDS arrays
     }
     if (bad) atomicOr(a.err, DERR_NON_ACGT);
-}
-
-__global__ void __launch_bounds__(256) k_mini_offsets(const uint64_t *tile_off, const uint64_t *coff, uint32_t n_seq, uint64_t *out) {
-    for (uint64_t i = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x; i <= n_seq; i += (uint64_t) gridDim.x * blockDim.x)
-        out[i] = coff[tile_off[i]];
 }
 
 } // namespace kmu

@@ -102,6 +102,7 @@ def _entry_points():
     d("kmu_components_knn", [vp, C.c_uint32, vp, vp, C.c_uint32, C.c_uint32, C.c_int, vp, vp, vp, vp, u32p])
     d("kmu_minimizer_layout", [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp], plain=True)
     d("kmu_read_minimizers", [vp, C.POINTER(A.HashParams), vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp, C.c_uint64, vp, u64p])
+    d("kmu_read_syncmers", [vp, C.POINTER(A.HashParams), C.POINTER(A.SyncmerParams), vp, vp, C.c_uint32, vp, vp, vp, vp, C.c_uint64, vp, u64p])
     d("kmu_seed_chains", [vp, vp, C.c_uint64, vp, vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp, C.c_uint32, C.c_uint32,
                           C.POINTER(A.ChainParams), C.c_int, vp, C.c_uint64, u64p])
     d("kmu_seed_chains_all", [vp, vp, C.c_uint64, vp, vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp, C.c_uint32, C.c_uint32,
@@ -733,6 +734,36 @@ class Context:
                                                    C.byref(total)))
         return hashes[:m], (pos[:m] if pos is not None else None), (read[:m] if read is not None else None), \
             (strand[:m] if strand is not None else None), moff
+
+    def read_syncmers(self, bases, offsets, kmer_type, k, fhash, s, t=0, s_kmer_type=None, s_fhash=None, want=MINIMIZERS_WANT):
+        """kmu_read_syncmers: the (k, s, t) syncmers of every read -- the k-mers whose smallest s-mer value sits at offset t or
+        k - s - t (t = 0: closed syncmers; 2 t == k - s: open syncmers at the middle offset; include/kmu.h has the rules).  The
+        s-mers are ordered by (s_kmer_type, s, s_fhash); the type defaults to the reference's choice for s and the order to
+        `fhash`.  Returns (hashes, pos, read, strand, sync_offsets) exactly as read_minimizers does, with the same `want`, the
+        same dtypes and the same memory rule: numpy in gives numpy out, torch cuda tensors stay on the device.  Two library
+        calls: one that counts, one with exactly that capacity."""
+        unknown = [x for x in want if x not in MINIMIZERS_WANT]
+        if unknown:
+            raise ValueError("want holds %r: the optional outputs are %r" % (unknown, MINIMIZERS_WANT))
+        n = len(offsets) - 1
+        mem = self._mem(bases, offsets)
+        hp = A.HashParams(kmer_type, k, fhash, A.INPUT_ASCII, mem, 0)
+        sp = A.SyncmerParams(A.kmer_type_for_k(s) if s_kmer_type is None else s_kmer_type, int(s), fhash if s_fhash is None else s_fhash, int(t))
+        soff = self._new_like(bases, n + 1, np.uint64, "int64")
+        total = C.c_uint64(0)
+        ptr = self._ptrs(bases)  # (a batch of empty reads has no bases)
+        args = (self.h, C.byref(hp), C.byref(sp), ptr(bases), _ptr(offsets)[0], n)
+        self._check(self.L.kmu_read_syncmers(*args, None, None, None, None, 0, _ptr(soff)[0], C.byref(total)))
+        m = int(total.value)
+        hashes = self._new_like(bases, max(m, 1), np.uint64, "int64")
+        pos = self._new_like(bases, max(m, 1), np.uint32, "int32") if "pos" in want else None
+        read = self._new_like(bases, max(m, 1), np.uint32, "int32") if "read" in want else None
+        strand = self._new_like(bases, max(m, 1), np.uint8, "uint8") if "strand" in want else None
+        if m or strand is not None:  # (with no syncmer at all the call still says whether a strand can be had)
+            self._check(self.L.kmu_read_syncmers(*args, _ptr(hashes)[0], _ptr(pos)[0], _ptr(read)[0], _ptr(strand)[0], m, None,
+                                                 C.byref(total)))
+        return hashes[:m], (pos[:m] if pos is not None else None), (read[:m] if read is not None else None), \
+            (strand[:m] if strand is not None else None), soff
 
     def sketch_count(self, bases, offsets, params, counter=None, out=None):
         """kmu_sketch_count: the reads once, both results -- signature rows (returned) and, if `counter` is given, the

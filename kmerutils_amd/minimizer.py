@@ -1,6 +1,7 @@
 """Window minimizers of reads: base-resolution seeds, and the hits between them.
 
-`read_minimizers` runs kmu_read_minimizers over a batch of reads and returns a `Minimizers` record; `seed_hits` joins the
+`read_minimizers` runs kmu_read_minimizers over a batch of reads and returns a `Minimizers` record; `read_syncmers` runs
+kmu_read_syncmers and returns a `Syncmers` record, which everything below takes in a Minimizers record's place; `seed_hits` joins the
 minimizers of different reads that carry the same hash.  The join is the anchor index as it is (ctx.anchor_index /
 AnchorIndex.match): every minimizer is a row of ONE hash (m = 1, n_keys = 1) and its read is its group, so a hit is a pair of rows
 of different reads with that hash in common.  A hash equal to UINT64_MAX is the padding of the index's rows: such a minimizer is
@@ -57,6 +58,35 @@ def read_minimizers(ctx, bases, offsets, k, w, fhash=A.FHASH_CANON_INVHASH, kmer
     want = ("pos", "read") if nthash else ("pos", "read", "strand")
     hashes, pos, read, strand, moff = ctx.read_minimizers(bases, offsets, kmer_type, k, fhash, w, want=want)
     return Minimizers(hashes, pos, read, strand, moff, int(k), int(w), int(fhash))
+
+
+# the syncmers of a batch (Context.read_syncmers): the arrays of a Minimizers record; k, s, t, fhash say how they were chosen.
+# seed_pairs, seed_hits and chain_hits take either record: they read hashes, pos, read, strand, offsets and k only.
+Syncmers = collections.namedtuple("Syncmers", "hashes pos read strand offsets k s t fhash")
+
+
+def read_syncmers(ctx, bases, offsets, k, s, t=0, fhash=A.FHASH_CANON_INVHASH, s_fhash=None, kmer_type=None, s_kmer_type=None):
+    """The (k, s, t) syncmers of every read of a batch as a Syncmers record: the k-mers whose smallest s-mer sits at offset t or
+    k - s - t (t = 0: closed, 2 t == k - s: open).  The order of the s-mers defaults to `fhash`, the k-mer types to the reference's
+    choices for k and for s.  The ntHash orders have no strand: the record's strand is then None."""
+    if kmer_type is None:
+        kmer_type = A.kmer_type_for_k(k)
+    if s_kmer_type is None:
+        s_kmer_type = A.kmer_type_for_k(s)
+    if s_fhash is None:
+        s_fhash = fhash
+    nthash = fhash in (A.FHASH_CANON_NTHASH, A.FHASH_CANON_NTHASH_8B)
+    want = ("pos", "read") if nthash else ("pos", "read", "strand")
+    hashes, pos, read, strand, soff = ctx.read_syncmers(bases, offsets, kmer_type, k, fhash, s, t, s_kmer_type, s_fhash, want=want)
+    return Syncmers(hashes, pos, read, strand, soff, int(k), int(s), int(t), int(fhash))
+
+
+def _seeds(ctx, bases, offsets, k, w, fhash, syncmer):
+    """the seeds of read_chains and map_reads: window minimizers, or syncmers when a pair (s, t) is given"""
+    if syncmer is None:
+        return read_minimizers(ctx, bases, offsets, k, w, fhash)
+    s, t = syncmer
+    return read_syncmers(ctx, bases, offsets, k, s, t, fhash)
 
 
 def _is_torch(x):
@@ -123,9 +153,10 @@ def chain_hits(ctx, q, db=None, max_occ=0, max_gap=5000, band=500, min_seeds=3, 
 
 
 def read_chains(ctx, bases, offsets, k, w, fhash=A.FHASH_CANON_INVHASH, max_occ=0, max_gap=5000, band=500, min_seeds=3, min_score=0,
-                all=False):
-    """From the reads of a batch to the chains between them in one call: read_minimizers, then the self-join of chain_hits."""
-    q = read_minimizers(ctx, bases, offsets, k, w, fhash)
+                all=False, syncmer=None):
+    """From the reads of a batch to the chains between them in one call: read_minimizers, then the self-join of chain_hits.
+    syncmer=(s, t) seeds with read_syncmers(k, s, t) instead; w is then unused."""
+    q = _seeds(ctx, bases, offsets, k, w, fhash, syncmer)
     return chain_hits(ctx, q, None, max_occ, max_gap, band, min_seeds, min_score, all=all)
 
 
@@ -150,11 +181,12 @@ def chain_mapq(chains, rank):
 
 
 def map_reads(ctx, bases_q, offsets_q, bases_db, offsets_db, k, w, fhash=A.FHASH_CANON_INVHASH, max_occ=0, max_gap=5000, band=500,
-              min_seeds=3, min_score=0, mask_permille=500):
+              min_seeds=3, min_score=0, mask_permille=500, syncmer=None):
     """From a batch of reads and a batch of contigs (or a reference) to every chain of every read on them and which of them to
-    believe: read_minimizers of both, chain_hits(all=True), rank_chains.  Returns (chains, rank)."""
-    q = read_minimizers(ctx, bases_q, offsets_q, k, w, fhash)
-    db = read_minimizers(ctx, bases_db, offsets_db, k, w, fhash)
+    believe: read_minimizers of both, chain_hits(all=True), rank_chains.  Returns (chains, rank).  syncmer=(s, t) seeds both
+    batches with read_syncmers(k, s, t) instead; w is then unused."""
+    q = _seeds(ctx, bases_q, offsets_q, k, w, fhash, syncmer)
+    db = _seeds(ctx, bases_db, offsets_db, k, w, fhash, syncmer)
     chains = chain_hits(ctx, q, db, max_occ, max_gap, band, min_seeds, min_score, all=True)
     return chains, rank_chains(ctx, chains, len(q.offsets) - 1, mask_permille)
 
